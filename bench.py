@@ -2,6 +2,8 @@
 """bench.py — scans/s of the warpsense hot path (TSDF update + Point-to-TSDF registration) on MI355X.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full                 (+ every figure beyond the timed steps, see below)
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR     (+ what the last timed step computed, as .npy files)
     python bench.py --gpus N --steps K --warmup W          (N > 1 without a launcher: starts the N ranks itself, self_launch)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
@@ -16,7 +18,10 @@ all-reduce per iteration as the fallback) — total work is fix
 The same line also carries `replica_scans_per_s`: N independent sensor streams, one per GPU (weak scaling, the
 deployment DESIGN.md §6 recommends for clouds of this size), clearly labelled and never used as `value`.
 
-Rank 0 prints ONE JSON line (see the driver contract); extra keys: roofline, cpu_baseline, kernels.
+Rank 0 prints ONE JSON line (see the driver contract).  A plain run sets up, warms up, times the steps and prints it; everything
+else the benchmark measures runs only with --full, after the timed steps: per-class kernel times and the roofline, the
+dense-equivalent leg, the registration loop per iteration, the multi-rank routes on one GPU, the C++ drop-in, the H2D copy of
+the scan, the replica streams (N > 1) and the CPU baseline (extra keys: kernels, roofline, cpu_baseline, ...; None without --full).
 """
 from __future__ import annotations
 
@@ -44,7 +49,45 @@ def parse():
     ap.add_argument("--integrate", choices=["sparse", "dense", "separate"], default="sparse")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-registration", action="store_true", help="time the TSDF update alone (diagnostics)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything else (kernel classes, roofline, dense-equivalent leg, "
+                         "multi-rank routes, drop-in, H2D, replicas, CPU baseline); off: only the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (pose, iterations, a fixed sample of the map)")
     return ap.parse_args()
+
+
+DUMP_SAMPLE = 1 << 21  # voxels of the map in --dump-outputs' fixed sample (16 B each with its index: 32 MiB)
+
+
+def dump_outputs(out_dir, tsdf, host_map, tau, pose, iterations):
+    """--dump-outputs: what a caller of the timed path holds after its last step -- the registered pose, the Gauss-Newton
+    iterations and the averaged map the next registration reads -- as float32 / float64 .npy files, 32 MiB in all.  The map
+    (513^3 packed entries, 540 MB) is reduced to per-slab sums over its storage order (every voxel counts) and a fixed, seeded
+    sample of voxels (indices into that order, value and weight)."""
+    import warpsense_amd as W
+    os.makedirs(out_dir, exist_ok=True)
+    n_vox = host_map.n_voxels()
+    snap = W.DeviceMap(host_map.size_.copy(), host_map.offset_.copy(), np.empty(n_vox, dtype=np.uint32), host_map.pos_.copy())
+    tsdf.avg_map().to_host(snap)
+    raw = snap.data_
+    value = (raw & 0xFFFF).astype(np.uint16).view(np.int16)
+    weight = (raw >> 16).astype(np.uint16).view(np.int16)
+    slabs = (int(snap.size_[0]), -1)
+    arrays = {
+        "map_value_sum_per_slab": value.reshape(slabs).sum(axis=1, dtype=np.int64).astype(np.float64),
+        "map_weight_sum_per_slab": weight.reshape(slabs).sum(axis=1, dtype=np.int64).astype(np.float64),
+        "map_changed_per_slab": (raw != np.uint32(tau & 0xFFFF)).reshape(slabs).sum(axis=1).astype(np.float64),  # != (tau, 0)
+    }
+    idx = np.unique(np.random.default_rng(20261016).integers(0, n_vox, DUMP_SAMPLE))
+    arrays["map_sample_index"] = idx.astype(np.float64)
+    arrays["map_sample_value"] = value[idx].astype(np.float32)
+    arrays["map_sample_weight"] = weight[idx].astype(np.float32)
+    if pose is not None:
+        arrays["pose"] = np.asarray(pose, dtype=np.float32).reshape(4, 4)
+        arrays["iterations"] = np.array([iterations], dtype=np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def cpu_baseline(points, perturbed, size, tau, mw, res, reg_params):
@@ -225,6 +268,7 @@ def main():
                 backend.peers = None
     reg.prepare_registration(d_pert)
     its = []
+    last_pose = [None]  # the pose the last step's registration returned (--dump-outputs)
     graph_cache = {}
 
     def step():
@@ -235,11 +279,12 @@ def main():
         # resident in HBM, so this is a device-to-device copy into the registration buffer, inside the timed region
         reg.prepare_registration(d_pert)
         if world == 1 and not force_sharded:
-            _, it = reg.register_cloud(tsdf.device_map(), eye, *reg_params, res)
+            T, it = reg.register_cloud(tsdf.device_map(), eye, *reg_params, res)
         else:
             # device-side exchange if the peers' mailboxes are mapped; else RCCL with 16 iterations per (validated) HIP graph
-            _, it = sharded_register_cloud(backend, n, eye, *reg_params, graphs=graph_cache)
+            T, it = sharded_register_cloud(backend, n, eye, *reg_params, graphs=graph_cache)
         its.append(it)
+        last_pose[0] = T
 
     def fence():
         torch.cuda.synchronize()
@@ -288,20 +333,25 @@ def main():
     integrate_timed_us = 1000.0 * ms / cnt if cnt else None
     stats = tsdf.stats()
     ctx.prof_enable(0)
+    # what the last timed step handed its caller, before anything below runs more steps on the same map
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tsdf, host_map, tau, last_pose[0], its[-1] if its else None)
 
+    # Everything from here to the result line measures something beyond the timed steps: --full only.
     # per-class kernel times: the same steps again with an event pair per class (outside the timed region)
     kernels = {}
-    ctx.prof_reset()
-    ctx.prof_enable(tsdf_mask)
-    for _ in range(max(3, min(args.steps, 10))):
-        step()
-    fence()
-    for k in tsdf_classes:
-        name = _lib.KERNEL_CLASSES[k]
-        ms, cnt = ctx.prof_read(k)
-        if cnt:
-            kernels[name] = {"avg_us": 1000.0 * ms / cnt, "launches": cnt}
-    ctx.prof_enable(0)
+    if args.full:
+        ctx.prof_reset()
+        ctx.prof_enable(tsdf_mask)
+        for _ in range(max(3, min(args.steps, 10))):
+            step()
+        fence()
+        for k in tsdf_classes:
+            name = _lib.KERNEL_CLASSES[k]
+            ms, cnt = ctx.prof_read(k)
+            if cnt:
+                kernels[name] = {"avg_us": 1000.0 * ms / cnt, "launches": cnt}
+        ctx.prof_enable(0)
     if integrate_timed_us is not None and "integrate" in kernels:
         kernels["integrate"]["avg_us"] = integrate_timed_us  # the timed region's own measurement
 
@@ -310,7 +360,7 @@ def main():
     dense_eq = None
     # (WS_BENCH_SKIP_DENSE_EQ=1: the counter passes of tools/profile_r05.sh leave it out, so that every kernel name in a
     # pass belongs to ONE route -- VERDICT r4 weak #3: tile_resolve<false,false> of this leg was summed into the sparse traffic)
-    if world == 1 and args.integrate != "dense" and not force_sharded and os.environ.get("WS_BENCH_SKIP_DENSE_EQ") != "1":
+    if args.full and world == 1 and args.integrate != "dense" and not force_sharded and os.environ.get("WS_BENCH_SKIP_DENSE_EQ") != "1":
         tsdf.set_integrate(W.WS_INTEGRATE_DENSE)
         step()
         fence()
@@ -342,7 +392,7 @@ def main():
                     "update_frac": b_upd / (t_upd * 1e-6) / 1e9 / HBM_PEAK_GBS if t_upd else None}
 
     # registration iteration timing in a separate pass (events per iteration would perturb the timed region)
-    if not args.no_registration and world == 1:
+    if args.full and not args.no_registration and world == 1:
         ctx.prof_reset()
         ctx.prof_enable(1 << _lib.WS_K_REG)
         _, reg_its = reg.register_cloud(tsdf.device_map(), eye, *reg_params, res)
@@ -359,7 +409,7 @@ def main():
     # the multi-GPU code path (points sharded, RCCL all-reduce of the 44 sums each iteration, HIP-graph batches) on ONE
     # rank: what the RCCL route costs per scan before any xGMI hop is added (separate from the timed region)
     sharded_1rank = None
-    if world == 1 and not force_sharded and not args.no_registration and os.environ.get("WS_BENCH_SKIP_SHARDED") != "1":
+    if args.full and world == 1 and not force_sharded and not args.no_registration and os.environ.get("WS_BENCH_SKIP_SHARDED") != "1":
         try:
             os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
             os.environ.setdefault("MASTER_PORT", "29533")
@@ -402,7 +452,7 @@ def main():
 
     # N independent sensor streams, one per GPU (replicas: no exchange at all) -- reported NEXT TO the strong-scaling value
     replica = None
-    if world > 1 and not args.no_registration:
+    if args.full and world > 1 and not args.no_registration:
         def replica_step():
             tsdf.update_tsdf(d_points, (0, 0, 0), (0, 0, 32768))
             reg.prepare_registration(d_pert)
@@ -419,7 +469,7 @@ def main():
     # The multi-GPU loop with the device-side exchange, exercised on this ONE GPU: two ranks (own contexts / streams, 128
     # resident workgroups each) register the same cloud, every rank its half of the points, the 44 sums through mailboxes.
     sharded_2rank = None
-    if world == 1 and not force_sharded and not args.no_registration and os.environ.get("WS_BENCH_SKIP_SHARDED") != "1":
+    if args.full and world == 1 and not force_sharded and not args.no_registration and os.environ.get("WS_BENCH_SKIP_SHARDED") != "1":
         # (a process of its own, tools/peer_bench.py: this one already drives torch / RCCL streams, and the ranks' kernels
         # must be on the chip together)
         try:
@@ -438,7 +488,7 @@ def main():
     # host 6x6 solve per iteration), `one_line_change` = the resident device loop behind the same host vectors.  A process of
     # its own, outside the timed region; never part of `value`.
     dropin = None
-    if world == 1 and not force_sharded and not args.no_registration and os.environ.get("WS_BENCH_SKIP_DROPIN") != "1":
+    if args.full and world == 1 and not force_sharded and not args.no_registration and os.environ.get("WS_BENCH_SKIP_DROPIN") != "1":
         exe = os.path.join(ROOT, "examples", "dropin_bench")
         try:
             import subprocess
@@ -458,7 +508,7 @@ def main():
 
     # host buffers (H2D of the scan reported separately, never part of `value`): 1.5 MB pageable / pinned -> HBM
     h2d = None
-    if rank == 0:
+    if args.full and rank == 0:
         try:
             host_pts = torch.from_numpy(points)
             pinned = host_pts.pin_memory()
@@ -560,6 +610,7 @@ def main():
         "vs_baseline": None,
         "dtype": "int32/int64 fixed point (f32 pose, f64 6x6 solve)",
         "data": "synthetic",
+        "full": bool(args.full),
         "config": {"workload": f"OS1-128 synthetic scan, {n} pts, {size[0] + 1 - size[0] % 2}^3 TSDF map @ {res} mm, tau {tau}, "
                                f"HIP update_tsdf + Point-to-TSDF registration (BASELINE configs[1])",
                    "points": n, "map_voxels": n_vox, "integrate": args.integrate,
@@ -570,7 +621,7 @@ def main():
                    "contested_voxels": stats["contested_voxels"], "tiles_streamed": stats["tiles"], "tail_records": stats["records"],
                    "record_runs": stats["runs"]},
         "roofline": roofline,
-        "kernels": kernels,
+        "kernels": kernels if args.full else None,
         "sharded_1rank_scans_per_s": sharded_1rank["scans_per_s"] if sharded_1rank and "scans_per_s" in sharded_1rank else None,
         "sharded_1rank": sharded_1rank,
         "sharded_2rank_1gpu": sharded_2rank,
@@ -585,7 +636,7 @@ def main():
         roofline["dense_equivalent"] = dense_eq
     if h2d and "pageable_us" in h2d:
         out["scans_per_s_with_pageable_h2d"] = 1.0 / (elapsed / args.steps + 1e-6 * h2d["pageable_us"])
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(points, perturbed, size, tau, mw, res, reg_params)
     else:
         out["cpu_baseline"] = None

@@ -2,6 +2,7 @@
 """Generate tests/golden/ref_headers.npz from oracle/_ref (the REFERENCE'S OWN headers compiled by g++).
 
 Run in the build container (needs /root/reference):   make -C oracle ref && python tests/golden/make_ref_goldens.py
+(`--ring-index`: only ref_get_index.npz, get_index on the inputs of test_oracle_pins.py::test_live_reference_headers_if_present)
 
 The fixture holds inputs and the reference's outputs only (data, no reference source):
   ring-buffer index math        cuda::DeviceMap::{get_index,in_bounds,in_bounds_with_buffer_pos/neg}
@@ -167,7 +168,32 @@ def main():
     out["consts"] = np.array([R.ref_consts(0), R.ref_consts(1), R.ref_sizeof_entry(), R.ref_sizeof_long()], dtype=np.int64)
     np.savez_compressed(os.path.join(HERE, "ref_headers.npz"), **out)
     print("wrote", os.path.join(HERE, "ref_headers.npz"), {k: v.shape for k, v in out.items()})
+    ring_index(R)
+
+
+def ring_index(R):
+    """ref_get_index.npz: cuda::DeviceMap::get_index on the maps and queries of O.ring_index_cases() (the inputs of
+    test_live_reference_headers_if_present), so that the test holds the oracle to the reference where oracle/_ref is not built."""
+    maps, queries, index = [], [], []
+    for size, pos, off, qs in O.ring_index_cases():
+        data = np.zeros(int(np.prod(size)), dtype=np.uint32)
+        h = R.ref_map_create(size.ctypes.data, pos.ctypes.data, off.ctypes.data, data.ctypes.data)
+        index.append([R.ref_get_index(h, int(x), int(y), int(z)) for x, y, z in qs])
+        R.ref_map_destroy(h)
+        maps.append(np.concatenate([size, pos, off]))
+        queries.append(qs)
+    out = {"maps": np.array(maps, dtype=np.int32),        # size(3) pos(3) offset(3)
+           "queries": np.array(queries, dtype=np.int32),  # [case][200][3]
+           "index": np.array(index, dtype=np.int64)}      # [case][200]
+    np.savez_compressed(os.path.join(HERE, "ref_get_index.npz"), **out)
+    print("wrote", os.path.join(HERE, "ref_get_index.npz"), {k: v.shape for k, v in out.items()})
 
 
 if __name__ == "__main__":
-    main()
+    if "--ring-index" in sys.argv:  # only ref_get_index.npz
+        R = O.ref_lib()
+        if R is None:
+            raise SystemExit("oracle/_ref/libws_ref.so missing: run `make -C oracle ref` where the reference tree exists")
+        ring_index(R)
+    else:
+        main()

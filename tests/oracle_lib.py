@@ -251,6 +251,20 @@ def cpu_register_cloud(m: OracleMap, points, T_in_rowmajor, max_iterations=200, 
 
 
 # ---------------------------------------------------------------- oracle/_ref (reference headers, this container only)
+def ring_index_cases(seed=99, maps=20, queries=200):
+    """Random ring-buffer maps (odd sizes, positions, offsets) and queries inside each window: the inputs of
+    test_oracle_pins.py::test_live_reference_headers_if_present and of its fixture tests/golden/ref_get_index.npz."""
+    rng = np.random.default_rng(seed)
+    cases = []
+    for _ in range(maps):
+        size = (rng.integers(1, 30, 3) * 2 + 1).astype(np.int32)
+        pos = rng.integers(-100, 100, 3).astype(np.int32)
+        off = np.array([rng.integers(0, s) for s in size], dtype=np.int32)
+        qs = np.array([pos + rng.integers(-(size // 2), size // 2 + 1) for _ in range(queries)], dtype=np.int32)
+        cases.append((size, pos, off, qs))
+    return cases
+
+
 def ref_lib():
     so = os.path.join(ORACLE_DIR, "_ref", "libws_ref.so")
     if not os.path.exists(so):

@@ -314,6 +314,63 @@ def test_bench_gpus_flag_starts_the_ranks_or_checks_the_launcher(monkeypatch):
         bench.self_launch(argparse.Namespace(gpus=4))
 
 
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("ws_bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_bench_plain_run_times_the_steps_only_unless_full(monkeypatch):
+    """A plain run sets up, warms up and times --steps; every other measurement runs only with --full (off by default)."""
+    import sys
+    bench = _bench_module()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (5, 2, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "5", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "out"
+
+
+def test_bench_dump_outputs_are_float_arrays_of_a_fixed_sample(tmp_path):
+    """--dump-outputs writes float32 / float64 .npy files, at most 64 MB, from a seeded sample (the same from run to run)."""
+    import warpsense_amd as W
+    bench = _bench_module()
+    tau = 1000
+    lm = W.LocalMap(64, 64, 64, tau, 0)
+    rng = np.random.default_rng(5)
+    data = np.full(lm.device_map().n_voxels(), tau, dtype=np.uint32)
+    hit = rng.integers(0, data.size, 5000)
+    data[hit] = (rng.integers(0, 2000, hit.size) | (rng.integers(1, 640, hit.size) << 16)).astype(np.uint32)
+
+    class Avg:
+        def to_host(self, snap):
+            snap.data_[:] = data
+
+    class Tsdf:
+        def avg_map(self):
+            return Avg()
+
+    pose = np.eye(4, dtype=np.float32)
+    pose[:3, 3] = (1.5, -2.0, 0.25)
+    runs = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        bench.dump_outputs(str(d), Tsdf(), lm.device_map(), tau, pose, 42)
+        runs.append({f.name: np.load(f) for f in sorted(d.iterdir())})
+    a, b = runs
+    assert set(a) == set(b) and {"pose.npy", "iterations.npy", "map_sample_index.npy", "map_sample_value.npy"} <= set(a)
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 * 2 ** 20
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    assert np.array_equal(a["pose.npy"], pose) and a["iterations.npy"][0] == 42
+    assert a["map_changed_per_slab.npy"].sum() == np.count_nonzero(data != tau)
+    idx = a["map_sample_index.npy"].astype(np.int64)
+    assert np.array_equal(a["map_sample_weight.npy"], (data[idx] >> 16).astype(np.float32))
+
+
 def test_the_servers_mail_protocol_on_the_host_side():
     """the resident server behind ws_reg_iterate answers in seven 64-byte lines of seven words + a tag (request number, hash of the
     words) that it writes without waiting: the host must not take a stale answer, one that has not arrived completely, or a torn

@@ -372,7 +372,7 @@ def test_peer_mailbox_loop_processes_over_ipc(world, drop, monkeypatch):
 def test_bench_dry_run_two_ranks_share_the_gpu():
     """bench.py's N > 1 path cannot rot while there is no multi-GPU box to run it on: two ranks launched the way
     the driver launches them, both on cuda:0 with a gloo group (WS_BENCH_SHARE_GPU=1 WS_BENCH_BACKEND=gloo) -- IPC mailboxes,
-    device-side exchange, replica pass, reductions of the timings, and the keys the first real 8-GPU line will be read by."""
+    device-side exchange, replica pass (--full), reductions of the timings, and the keys the first real 8-GPU line will be read by."""
     import json
     import subprocess
     import sys
@@ -382,7 +382,8 @@ def test_bench_dry_run_two_ranks_share_the_gpu():
         port = s.getsockname()[1]
     env = dict(os.environ, WS_BENCH_SHARE_GPU="1", WS_BENCH_BACKEND="gloo", WS_REG_PEER_TIMEOUT_MS="250", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
+                        "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+                        "--full"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=900, cwd=root)
     lines = [l for l in r.stdout.decode(errors="replace").splitlines() if l.startswith("{")]
     assert r.returncode == 0 and lines, r.stderr.decode(errors="replace")[-3000:]

@@ -16,6 +16,7 @@ import oracle_lib as O
 from warpsense_amd import synthetic as S
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_headers.npz")
+GOLD_INDEX = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_get_index.npz")
 
 
 def calc_weight(value, tau, weight_epsilon):
@@ -345,25 +346,26 @@ def test_golden_jacobians_through_the_reference_types():
 
 
 def test_live_reference_headers_if_present():
-    """Where oracle/_ref was built (this container), cross-check fresh random inputs against it directly."""
+    """Ring-buffer index math on random maps and queries (O.ring_index_cases) against the answers of the reference header
+    recorded from oracle/_ref (tests/golden/ref_get_index.npz), and where oracle/_ref was built, against it directly."""
+    g = np.load(GOLD_INDEX)
     R = O.ref_lib()
-    if R is None:
-        pytest.skip("oracle/_ref not built (no /root/reference on this machine)")
-    rng = np.random.default_rng(99)
     L = O.lib()
-    for _ in range(20):
-        size = (rng.integers(1, 30, 3) * 2 + 1).astype(np.int32)
-        pos = rng.integers(-100, 100, 3).astype(np.int32)
-        off = np.array([rng.integers(0, s) for s in size], dtype=np.int32)
-        data = np.zeros(int(np.prod(size)), dtype=np.uint32)
-        h = R.ref_map_create(size.ctypes.data, pos.ctypes.data, off.ctypes.data, data.ctypes.data)
+    cases = O.ring_index_cases()
+    assert len(cases) == len(g["maps"])
+    for case, (size, pos, off, qs) in enumerate(cases):
+        # the fixture was recorded on these very inputs
+        assert np.array_equal(g["maps"][case], np.concatenate([size, pos, off])) and np.array_equal(g["queries"][case], qs)
         om = O.OracleMap(size, 0, 0, pos=pos, offset=off)
         v = om.view()
-        for _ in range(200):
-            q = pos + rng.integers(-(size // 2), size // 2 + 1)
-            x, y, z = (int(t) for t in q)
-            assert R.ref_get_index(h, x, y, z) == L.wso_get_index(C.byref(v), x, y, z)
-        R.ref_map_destroy(h)
+        got = np.array([L.wso_get_index(C.byref(v), int(x), int(y), int(z)) for x, y, z in qs])
+        assert np.array_equal(got, g["index"][case]), f"case {case}: differs at {np.nonzero(got != g['index'][case])[0][:5]}"
+        if R is not None:
+            data = np.zeros(int(np.prod(size)), dtype=np.uint32)
+            h = R.ref_map_create(size.ctypes.data, pos.ctypes.data, off.ctypes.data, data.ctypes.data)
+            live = np.array([R.ref_get_index(h, int(x), int(y), int(z)) for x, y, z in qs])
+            R.ref_map_destroy(h)
+            assert np.array_equal(live, got), f"case {case}"
 
 
 # ------------------------------------------------------------------ 3. whole-scan counters of the reference kernel source

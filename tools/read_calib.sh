@@ -1,13 +1,14 @@
 #!/bin/bash
-# FETCH_SIZE per byte loaded for the load shapes of the scatter's kernels (tools/read_calib.hip)  ->  gpurun_out/TAG_read_calib.txt
+# FETCH_SIZE per byte loaded for the load shapes of the scatter's kernels (tools/read_calib.hip)  ->  $WS_PROFILE_OUT/TAG_read_calib.txt
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
+export WS_PROFILE_OUT=${WS_PROFILE_OUT:-profile_out}; OUT=$WS_PROFILE_OUT  # where the passes write (git-ignored)
 TAG=${1:-r06}
-mkdir -p gpurun_out
+mkdir -p "$OUT"
 [ -x tools/read_calib.out ] || hipcc --offload-arch=gfx950 -O3 tools/read_calib.hip -o tools/read_calib.out
-rm -rf gpurun_out/prof_${TAG}_rcal
-rocprofv3 --kernel-trace --pmc FETCH_SIZE -d gpurun_out/prof_${TAG}_rcal -o pmc -- tools/read_calib.out > gpurun_out/prof_${TAG}_rcal.log 2>&1
-DB=$(ls gpurun_out/prof_${TAG}_rcal/*.db gpurun_out/prof_${TAG}_rcal/*/*.db 2>/dev/null | head -1)
-python - $DB > gpurun_out/${TAG}_read_calib.txt <<'PY'
+rm -rf $OUT/prof_${TAG}_rcal
+rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/prof_${TAG}_rcal -o pmc -- tools/read_calib.out > $OUT/prof_${TAG}_rcal.log 2>&1
+DB=$(ls $OUT/prof_${TAG}_rcal/*.db $OUT/prof_${TAG}_rcal/*/*.db 2>/dev/null | head -1)
+python - $DB > $OUT/${TAG}_read_calib.txt <<'PY'
 import sqlite3, sys
 db = sqlite3.connect(sys.argv[1])
 rows = db.execute("select name, avg(v), avg(d) from (select name, dispatch_id, sum(counter_value) as v, avg(duration) as d from pmc_events "
@@ -21,5 +22,5 @@ for name, kb, dur in sorted(rows):
         b = kb * 1024.0
         print(f"{key:<18} {N:>9} {loaded[key]:>13} {b:>17.0f} {b / loaded[key]:>15.2f} {b / N:>17.1f} {dur / 1e3:>8.1f}")
 PY
-cat gpurun_out/${TAG}_read_calib.txt
-rm -rf gpurun_out/prof_${TAG}_rcal
+cat $OUT/${TAG}_read_calib.txt
+rm -rf $OUT/prof_${TAG}_rcal
