@@ -130,6 +130,38 @@ constexpr size_t AZ_ALLOC = 1024 * 64 + 8; // direction-bin histogram / offsets 
 
 using namespace ws;
 
+// the Gauss-Newton state a registration starts from (tsdf_registration.cpp:28-33)
+static GnCore gn_init(const float T_in[16], int32_t max_iterations, float it_weight_gradient, float epsilon)
+{
+  GnCore c;
+  std::memset(&c, 0, sizeof c);
+  std::memcpy(c.T, T_in, 16 * sizeof(float));
+  for (int k = 0; k < 3; ++k) c.center[k] = (int32_t)T_in[12 + k]; // Point center = total_transform.block<3,1>(0,3).cast<int>()
+  c.it_weight_gradient = it_weight_gradient;
+  c.epsilon = epsilon;
+  c.max_iterations = max_iterations;
+  return c;
+}
+
+// Spin until done() -- a word a kernel writes into host-mapped memory: a microsecond or two, where waking up from
+// hipStreamSynchronize costs tens.  Bounded: after 20 ms the stream is synchronised the ordinary way (a kernel that never ends
+// is the runtime's to report), and if done() is still false then, the wait fails with `what`.
+template <typename Done>
+static int spin_wait(ws_reg *r, Done done, const char *what)
+{
+  const auto t0 = std::chrono::steady_clock::now();
+  for (uint32_t spins = 0; !done();)
+    if ((++spins & 0xfffu) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20))
+    {
+      WS_HIP(hipStreamSynchronize(r->ctx->stream));
+      if (done()) break;
+      set_error(what);
+      return WS_ERR_INTERNAL;
+    }
+  std::atomic_thread_fence(std::memory_order_acquire);
+  return WS_OK;
+}
+
 extern "C" {
 
 const char *ws_last_error(void) { return g_last_error.c_str(); }
@@ -856,7 +888,7 @@ int ws_reg_destroy(ws_reg *r)
   if (r->result_host) (void)hipHostFree(r->result_host);
   if (r->iter_host) (void)hipHostFree(r->iter_host);
   if (r->grid_bar) (void)hipFree(r->grid_bar);
-  if (r->shard_arrived) (void)hipFree(r->shard_arrived);
+  if (r->pass_arrived) (void)hipFree(r->pass_arrived);
   (void)ws_reg_peer_disconnect(r);
   if (r->mailbox) (void)hipFree(r->mailbox);
   if (r->peer_block_dev) (void)hipFree(r->peer_block_dev);
@@ -898,8 +930,8 @@ int ws_reg_create(ws_context *ctx, size_t max_points, ws_reg **out)
   if (rc == WS_OK && e == hipSuccess) std::memset(r->iter_host, 0, 64 * sizeof(int64_t));
   if (rc == WS_OK && e == hipSuccess) e = hipMemsetAsync(r->state, 0, 2 * sizeof(GnState), ctx->stream);
   if (rc == WS_OK && e == hipSuccess) e = hipMalloc((void **)&r->grid_bar, reg_barrier_bytes());
-  if (rc == WS_OK && e == hipSuccess) e = hipMalloc((void **)&r->shard_arrived, 256);
-  if (rc == WS_OK && e == hipSuccess) e = hipMemset(r->shard_arrived, 0, 256);
+  if (rc == WS_OK && e == hipSuccess) e = hipMalloc((void **)&r->pass_arrived, sizeof(uint32_t));
+  if (rc == WS_OK && e == hipSuccess) e = hipMemset(r->pass_arrived, 0, sizeof(uint32_t));
   if (rc == WS_OK && e == hipSuccess) r->loop_supported = reg_loop_supported(ctx->device);
   if (rc == WS_OK && e == hipSuccess) e = hipHostMalloc((void **)&r->srv_mail, reg_server_mail_bytes(), hipHostMallocMapped);
   if (rc == WS_OK && e == hipSuccess) e = hipHostGetDevicePointer((void **)&r->srv_mail_dev, r->srv_mail, 0);
@@ -957,21 +989,6 @@ const int32_t *ws_reg_points_dev(const ws_reg *r, size_t *n)
 static int reg_iterate_served(ws_reg *r, const ws_map *m, const float T[16], int32_t res, uint32_t flags, int64_t sums[44])
 {
   auto exited = [&]() { return reg_server_mail_exited(r->srv_mail); };
-  auto wait_gone = [&](uint32_t id) -> int {
-    const auto t0 = std::chrono::steady_clock::now();
-    uint32_t spins = 0;
-    while (exited() != id)
-      if ((++spins & 0xfffu) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20))
-      {
-        WS_HIP(hipStreamSynchronize(r->ctx->stream));
-        if (exited() != id)
-        {
-          set_error("ws_reg_iterate: the resident server did not leave");
-          return WS_ERR_INTERNAL;
-        }
-      }
-    return WS_OK;
-  };
   uint32_t id = r->srv_launch.load(std::memory_order_acquire);
   bool alive = id != 0 && exited() != id;
   const MapParams &par = m->par[WS_MAP_AVG];
@@ -982,7 +999,7 @@ static int reg_iterate_served(ws_reg *r, const ws_map *m, const float T[16], int
     // somebody has enqueued other work behind that server (or the call is for another map / cloud): it must be gone before a
     // request may be written -- it would answer from the state it was launched with
     reg_server_mail_stop(r->srv_mail, id);
-    const int rc = wait_gone(id);
+    const int rc = spin_wait(r, [&] { return exited() == id; }, "ws_reg_iterate: the resident server did not leave");
     if (rc != WS_OK) return rc;
     alive = false;
   }
@@ -1063,28 +1080,13 @@ int ws_reg_iterate(ws_reg *r, const ws_map *m, const float T[16], int32_t res, u
     WS_SETTLE(m);
     // One launch, nothing copied by the runtime: the pose travels in the kernel arguments (registration.cu:351 copies it), the
     // sums come back through host-mapped memory with the call's sequence number behind them (registration.cu:356-365 copies
-    // four results and adds 32 partials up on the host).  The caller cannot go on without them, so the wait is a spin on that
-    // word -- bounded: after 20 ms the stream is synchronised the ordinary way, and a kernel that never ends is the runtime's to report.
+    // four results and adds 32 partials up on the host).  The caller cannot go on without them, so the wait is a spin on that word.
     const uint32_t seq = ++r->iter_seq ? r->iter_seq : ++r->iter_seq; // (never 0: the block starts zeroed)
-    int rc = launch_reg_host_iter(r, m, T, res, flags, seq);
+    int rc = launch_reg_pass(r, m, res, flags, 0, r->n, r->iter_host_dev, 0, T, seq);
     if (rc != WS_OK) return rc;
     const volatile int64_t *done = r->iter_host + 44;
-    const auto t0 = std::chrono::steady_clock::now();
-    uint32_t spins = 0;
-    while ((uint32_t)*done != seq)
-    {
-      if ((++spins & 0xfffu) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20))
-      {
-        WS_HIP(hipStreamSynchronize(r->ctx->stream));
-        if ((uint32_t)*done != seq)
-        {
-          set_error("ws_reg_iterate: the launch ended without its result");
-          return WS_ERR_INTERNAL;
-        }
-        break;
-      }
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
+    rc = spin_wait(r, [&] { return (uint32_t)*done == seq; }, "ws_reg_iterate: the launch ended without its result");
+    if (rc != WS_OK) return rc;
     std::memcpy(sums, r->iter_host, sizeof sums);
   }
   std::memcpy(h, sums, 36 * sizeof(int64_t));
@@ -1114,13 +1116,7 @@ int ws_reg_begin(ws_reg *r, const float T_in[16], int32_t max_iterations, float 
   // the pinned staging block may still be read by an earlier async copy
   WS_HIP(hipStreamSynchronize(r->ctx->stream));
   std::memset(h, 0, sizeof(GnState));
-  std::memcpy(h->core.T, T_in, 16 * sizeof(float));
-  // Point center = total_transform.block<3,1>(0,3).cast<int>() — tsdf_registration.cpp:33
-  for (int k = 0; k < 3; ++k) h->core.center[k] = (int32_t)T_in[12 + k];
-  h->core.alpha = 0.f;
-  h->core.it_weight_gradient = it_weight_gradient;
-  h->core.epsilon = epsilon;
-  h->core.max_iterations = max_iterations;
+  h->core = gn_init(T_in, max_iterations, it_weight_gradient, epsilon);
   *(volatile int32_t *)r->host_flag = 0;
   WS_HIP(hipMemcpyAsync(&r->state[0], h, sizeof(GnState), hipMemcpyHostToDevice, r->ctx->stream));
   WS_HIP(hipMemcpyAsync(&r->state[1], h, sizeof(GnState), hipMemcpyHostToDevice, r->ctx->stream));
@@ -1132,7 +1128,7 @@ int ws_reg_accumulate_dev(ws_reg *r, const ws_map *m, int32_t res, uint32_t flag
 {
   if (!r || !m || !sums_dev) return invalid("ws_reg_accumulate_dev: NULL argument");
   WS_SETTLE(m);
-  return launch_reg_accumulate(r, m, nullptr, res, flags, first, count, sums_dev);
+  return launch_reg_pass(r, m, res, flags, first, count, sums_dev, 0);
 }
 
 int ws_reg_iterate_shard_dev(ws_reg *r, const ws_map *m, int32_t res, uint32_t flags, size_t first, size_t count, int64_t *sums_dev,
@@ -1140,7 +1136,7 @@ int ws_reg_iterate_shard_dev(ws_reg *r, const ws_map *m, int32_t res, uint32_t f
 {
   if (!r || !m || !sums_dev) return invalid("ws_reg_iterate_shard_dev: NULL argument");
   WS_SETTLE(m);
-  return launch_reg_shard(r, m, res, flags, first, count, sums_dev, apply_previous);
+  return launch_reg_pass(r, m, res, flags, first, count, sums_dev, apply_previous);
 }
 
 int ws_reg_solve_dev(ws_reg *r, const int64_t *sums_dev)
@@ -1164,19 +1160,8 @@ int ws_reg_poll(ws_reg *r, int32_t *finished, int32_t *iterations, float T_out[1
 // the host side of one resident launch: spin on the flag the kernel raises behind its result (host-mapped memory)
 static int wait_resident_loop(ws_reg *r)
 {
-  volatile int32_t *done = r->host_flag;
-  const auto t0 = std::chrono::steady_clock::now();
-  uint32_t spins = 0;
-  while (*done == 0)
-  {
-    if ((++spins & 0xfffu) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20))
-    {
-      WS_HIP(hipStreamSynchronize(r->ctx->stream));
-      break;
-    }
-  }
-  std::atomic_thread_fence(std::memory_order_acquire);
-  return WS_OK;
+  const volatile int32_t *done = r->host_flag;
+  return spin_wait(r, [&] { return *done != 0; }, "the resident registration loop ended without its result");
 }
 
 int ws_register_cloud(ws_reg *r, const ws_map *m, const float T_in[16], int32_t max_iterations, float it_weight_gradient,
@@ -1190,20 +1175,12 @@ int ws_register_cloud(ws_reg *r, const ws_map *m, const float T_in[16], int32_t 
     // one launch: the 256 workgroups stay resident and meet at a grid barrier between iterations.  The initial state
     // travels in the kernel arguments and the final state comes back through host-mapped memory, so the host neither
     // waits for earlier work on the stream before enqueueing nor copies anything afterwards.
-    GnCore init;
-    std::memset(&init, 0, sizeof init);
-    std::memcpy(init.T, T_in, 16 * sizeof(float));
-    for (int k = 0; k < 3; ++k) init.center[k] = (int32_t)T_in[12 + k]; // tsdf_registration.cpp:33
-    init.it_weight_gradient = it_weight_gradient;
-    init.epsilon = epsilon;
-    init.max_iterations = max_iterations;
     *(volatile int32_t *)r->host_flag = 0; // nothing on the stream writes it any more: every earlier registration was waited for
-    int rc = launch_reg_loop(r, m, res, flags, init);
+    int rc = launch_reg_loop(r, m, res, flags, gn_init(T_in, max_iterations, it_weight_gradient, epsilon));
     if (rc != WS_OK) return rc;
     r->latest = 0;
-    // The kernel raises the flag in host-mapped memory after its result (release at system scope).  Spinning on it costs a
-    // microsecond or two; waking up from hipStreamSynchronize costs tens (measured: 84 -> ~35 us between the end of a
-    // registration and the first kernel of the next scan).  Bounded: a kernel that never finishes is the runtime's to report.
+    // The kernel raises the flag in host-mapped memory after its result (release at system scope).  Spinning on it instead of
+    // hipStreamSynchronize: 84 -> ~35 us between the end of a registration and the first kernel of the next scan (measured).
     rc = wait_resident_loop(r);
     if (rc != WS_OK) return rc;
     const GnCore *h = &r->result_host->core;
@@ -1225,9 +1202,8 @@ int ws_register_cloud(ws_reg *r, const ws_map *m, const float T_in[16], int32_t 
   // convergence so the host can stop early (launches already enqueued exit at once).
   const volatile int32_t *flag = r->host_flag;
   int launched = 0;
-  for (int k = 0; k <= max_iterations; ++k)
+  for (int k = 0; k <= max_iterations && !*flag; ++k)
   {
-    if (*flag) break;
     rc = launch_reg_iteration(r, m, res, flags, k);
     if (rc != WS_OK) return rc;
     launched = k + 1;
@@ -1367,16 +1343,9 @@ int ws_register_cloud_peers(ws_reg *r, const ws_map *m, size_t first, size_t cou
   // plus its next one would reach count == world and pass for the all-rank total.  Nothing runs until the mailboxes are fresh.
   if (r->peer_dirty) return invalid("ws_register_cloud_peers: the last exchange failed; call ws_reg_peer_reset on every rank (between two barriers) or reconnect first");
   if (res < 1) return invalid("ws_register_cloud_peers: map_resolution must be positive");
-  GnCore init;
-  std::memset(&init, 0, sizeof init);
-  std::memcpy(init.T, T_in, 16 * sizeof(float));
-  for (int k = 0; k < 3; ++k) init.center[k] = (int32_t)T_in[12 + k]; // tsdf_registration.cpp:33
-  init.it_weight_gradient = it_weight_gradient;
-  init.epsilon = epsilon;
-  init.max_iterations = max_iterations;
   *(volatile int32_t *)r->host_flag = 0;
   r->peer_dirty = true; // until this exchange has completed on this rank
-  int rc = launch_reg_loop(r, m, res, flags, init, true, first, count);
+  int rc = launch_reg_loop(r, m, res, flags, gn_init(T_in, max_iterations, it_weight_gradient, epsilon), true, first, count);
   if (rc != WS_OK) return rc;
   r->latest = 0;
   rc = wait_resident_loop(r);

@@ -19,6 +19,7 @@
 // wrapping group accumulators whose words count their additions (the exchange is the barrier), a per-lane voxel cache.
 // reg_iter_kernel is one launch per iteration (state and 256 x 32 partials double buffered by launch parity, so no
 // fences or atomics are needed); it is the fallback when the grid cannot be resident, and the A/B reference.
+// reg_pass_kernel is one launch per call of the multi-GPU path and of perform_registration without the resident server.
 #include <cstdlib>
 #include <cstring>
 
@@ -1583,110 +1584,93 @@ __global__ __launch_bounds__(REG_THREADS) void reg_loop_kernel(LoopArgs a)
   }
 }
 
-// ---- the same pieces as separate kernels: perform_registration (host gets h,g,e,c) and the multi-GPU
-// path (partials -> 44 sums in HBM -> RCCL all-reduce -> solve) ----
-struct AccArgs
-{
-  PointArgs pts;
-  const float *T;       // 16 floats, column-major (device)
-  const GnState *state; // null: no early exit
-  int64_t *partials;    // [REG_BLOCKS][REG_SLOTS] (buffer 0)
-};
-
-// The three kernels of the sharded path hand small results to each other through HBM.  When they are replayed as nodes of a
-// HIP graph, the runtime (ROCm 7.0) does not give a later node the cache maintenance a stream gives a later kernel: a
-// batch of 16 iterations converged after ~25 instead of 178 because nodes read stale lines of their XCD's L2 (measured;
-// one iteration per graph was fine).  So everything that crosses a kernel boundary here is written and read at agent
-// scope (sc1: performed at the coherent level, like the exchange inside the resident loop).
+// ---- kernels that hand small results to each other through HBM --------------------------------------------------------
+// When they are replayed as nodes of a HIP graph, the runtime (ROCm 7.0) does not give a later node the cache maintenance a
+// stream gives a later kernel: a batch of 16 iterations converged after ~25 instead of 178 because nodes read stale lines of
+// their XCD's L2 (measured; one iteration per graph was fine).  So everything that crosses a kernel boundary here is written
+// and read at agent scope (sc1: performed at the coherent level, like the exchange inside the resident loop).
 __device__ __forceinline__ int32_t coherent_i32(const int32_t *p) { return __hip_atomic_load(const_cast<int32_t *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ float coherent_f32(const float *p) { return __hip_atomic_load(const_cast<float *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ int64_t coherent_i64(const int64_t *p) { return __hip_atomic_load(const_cast<int64_t *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void publish_i64(int64_t *p, int64_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ bool loop_over(const GnState *state)
+
+// the state the previous launch (or ws_reg_begin) left, read word by word at agent scope
+__device__ __forceinline__ void load_core(GnCore &st, const GnCore *src)
 {
-  return coherent_i32(&state->core.finished) != 0 || coherent_i32(&state->core.iterations) >= coherent_i32(&state->core.max_iterations);
+  int32_t *w = reinterpret_cast<int32_t *>(&st);
+  const int32_t *s = reinterpret_cast<const int32_t *>(src);
+#pragma unroll
+  for (int i = 0; i < (int)(sizeof(GnCore) / 4); ++i) w[i] = coherent_i32(&s[i]);
 }
 
-__global__ __launch_bounds__(REG_THREADS) void reg_accumulate_kernel(AccArgs a)
+// the updated state and the sums it was made from (e and c are `int` in the reference), written at agent scope
+__device__ __forceinline__ void store_state(GnState *state, const GnCore &st, const int64_t *sums)
 {
-  __shared__ int64_t wave_part[REG_THREADS / 64][REG_SLOTS];
-  __shared__ int64_t red[REG_SLOTS];
-  if (a.state != nullptr && loop_over(a.state)) return;
-  float T[16];
+  const int32_t *w = reinterpret_cast<const int32_t *>(&st);
+  int32_t *dst = reinterpret_cast<int32_t *>(&state->core);
 #pragma unroll
-  for (int i = 0; i < 16; ++i) T[i] = coherent_f32(&a.T[i]);
-  int64_t acc[REG_SLOTS];
+  for (int i = 0; i < (int)(sizeof(GnCore) / 4); ++i) __hip_atomic_store(&dst[i], w[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #pragma unroll
-  for (int t = 0; t < REG_SLOTS; ++t) acc[t] = 0;
-  accumulate_points(a.pts, T, prefetch_points(a.pts), acc);
-  block_reduce32(acc, wave_part, red);
-  if (threadIdx.x < REG_SLOTS) publish_i64(&a.partials[(size_t)blockIdx.x * REG_SLOTS + threadIdx.x], red[threadIdx.x]);
+  for (int k = 0; k < 42; ++k) publish_i64(&state->sums[k], sums[k]);
+  publish_i64(&state->sums[42], (int64_t)(int32_t)sums[42]);
+  publish_i64(&state->sums[43], (int64_t)(int32_t)sums[43]);
 }
 
-__global__ __launch_bounds__(REG_THREADS) void reg_sum_kernel(const int64_t *partials, const GnState *state, int64_t *sums_out)
-{
-  __shared__ int64_t wave_part[REG_THREADS / 64][REG_SLOTS];
-  __shared__ int64_t red[REG_SLOTS];
-  if (state != nullptr && loop_over(state)) return;
-  sum_partials<true>(partials, wave_part, red);
-  if (threadIdx.x == 0)
-  {
-    int64_t sums[44];
-    expand_sums(red, sums);
-#pragma unroll
-    for (int k = 0; k < 44; ++k) publish_i64(&sums_out[k], sums[k]);
-  }
-}
-
-// the solve alone, fed with externally (all-)reduced sums; updates state buffer 0
+// the solve alone, fed with externally (all-)reduced sums (multi-GPU path: partials -> 44 sums in HBM -> RCCL all-reduce -> solve)
 __global__ __launch_bounds__(64) void reg_solve_kernel(GnState *state, const int64_t *sums_dev)
 {
   if (blockIdx.x != 0 || threadIdx.x >= 64) return;
   GnCore st;
-  {
-    // the state the previous solve (or ws_reg_begin) left: read and written word by word at agent scope
-    int32_t *w = reinterpret_cast<int32_t *>(&st);
-    const int32_t *src = reinterpret_cast<const int32_t *>(&state->core);
-#pragma unroll
-    for (int i = 0; i < (int)(sizeof(GnCore) / 4); ++i) w[i] = coherent_i32(&src[i]);
-  }
+  load_core(st, &state->core);
   __shared__ int64_t s[44];
   if (threadIdx.x < 44) s[threadIdx.x] = coherent_i64(&sums_dev[threadIdx.x]);
   __syncthreads();
   gn_update(
       st, [](int r, int c) { return s[c * 6 + r]; }, [](int r) { return s[36 + r]; }, (int32_t)s[42], (int32_t)s[43]);
-  if (threadIdx.x == 0)
-  {
-    const int32_t *w = reinterpret_cast<const int32_t *>(&st);
-    int32_t *dst = reinterpret_cast<int32_t *>(&state->core);
-#pragma unroll
-    for (int i = 0; i < (int)(sizeof(GnCore) / 4); ++i) __hip_atomic_store(&dst[i], w[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-    for (int k = 0; k < 42; ++k) publish_i64(&state->sums[k], s[k]);
-    publish_i64(&state->sums[42], (int64_t)(int32_t)s[42]);
-    publish_i64(&state->sums[43], (int64_t)(int32_t)s[43]);
-  }
+  if (threadIdx.x == 0) store_state(state, st, s);
 }
 
-// ---- one launch per iteration of the point-sharded (multi-GPU) path -------------------------------------------------
-// [apply the Gauss-Newton update from the all-reduced sums of the previous iteration] -> accumulate this rank's shard ->
-// the 44 sums, in ONE kernel instead of reg_solve + reg_accumulate + reg_sum: every workgroup repeats the (cheap) update
-// from the same sums, like the resident loop does, and the last workgroup to arrive (an arrival counter, agent-scope
-// accesses as everywhere on this path: no cache-wide fences) adds the partials up AND writes the updated state.
-// ONE state buffer, read by every workgroup before it arrives and written by the last one after all have arrived: the
-// launch bakes in no buffer parity, so a batch of these launches captured into a HIP graph replays from whatever state
-// the buffer holds (a host-side parity flip per launch made every replay restart from a stale buffer).
-struct ShardArgs
+// ---- one launch per call: the multi-GPU path and perform_registration without the server ------------------------------
+// [apply the Gauss-Newton update from the sums of the previous iteration] -> stop test -> accumulate the cloud (or this rank's
+// shard) -> the 44 sums.  Every workgroup repeats the (cheap) update from the same sums, like the resident loop does, and the
+// last workgroup to arrive (an arrival counter, agent-scope accesses: no cache-wide fences) adds the partials up AND writes the
+// updated state.  The routes:
+//   ws_reg_iterate_shard_dev (apply as asked) and ws_reg_accumulate_dev (apply = 0): the multi-GPU path, sums all-reduced
+//     between two launches;
+//   ws_reg_iterate without the resident server: tsdf_registration.cpp:55-92 calls perform_registration once per iteration and
+//     needs h, g, e, c on the host before it can go on.  The pose travels in the kernel arguments (no state), and the last
+//     workgroup writes the 44 sums and, behind them, the call's sequence number into host-mapped memory, where the host spins.
+// ONE state buffer, read by every workgroup before it arrives and written by the last one after all have arrived: the launch
+// bakes in no buffer parity, so a batch of these launches captured into a HIP graph replays from whatever state the buffer holds
+// (a host-side parity flip per launch made every replay restart from a stale buffer).  A launch after the loop is
+// over changes neither the state nor the sums.  (ws_register_cloud's one launch per iteration stays with reg_iter_kernel: its
+// partials are summed at the head of the next launch by every workgroup at once, where this kernel's last arriver adds an
+// arrival round trip and a pass over the partials to every iteration -- 15.4 instead of 10.3 us per iteration, measured.)
+// POSE (ws_reg_iterate): the pose comes in the arguments, there is no state and no update, and the sums go to host-mapped
+// memory followed by the sequence number.  Two argument layouts, so the state route carries no pose.
+template <bool POSE>
+struct PassArgs
 {
-  PointArgs pts;          // first / end: this rank's shard
-  GnState *state;         // in: the state before this launch; out (if apply): the state after the update
-  int64_t *sums;          // in: the all-reduced sums of the previous iteration (if apply); out: this rank's 44 sums
-  int64_t *partials;      // [REG_BLOCKS][REG_SLOTS]
-  uint32_t *arrived;      // zero between launches
+  PointArgs pts;      // first / end: this rank's shard
+  GnState *state;     // in: the state before this launch; out (if apply): the state after the update
+  int64_t *sums;      // in: the all-reduced sums of the previous iteration (if apply); out: this rank's 44 sums
+  int64_t *partials;  // [REG_BLOCKS][REG_SLOTS]
+  uint32_t *arrived;  // zero between launches
   int32_t apply;
 };
+template <>
+struct PassArgs<true>
+{
+  PointArgs pts;
+  float T[16];        // column-major
+  int64_t *partials;  // [REG_BLOCKS][REG_SLOTS]
+  uint32_t *arrived;  // zero between launches
+  int64_t *sums;      // host-mapped: 44 sums, then (at [44]) the sequence number
+  uint32_t seq;
+};
+static_assert(sizeof(PassArgs<false>) <= 256 && sizeof(PassArgs<true>) <= 256, "reg_pass_kernel: more than 256 bytes of kernel arguments (see LoopArgs)");
 
-__global__ __launch_bounds__(REG_THREADS) void reg_shard_kernel(ShardArgs a)
+template <bool POSE>
+__global__ __launch_bounds__(REG_THREADS) void reg_pass_kernel(PassArgs<POSE> a)
 {
   __shared__ int64_t wave_part[REG_THREADS / 64][REG_SLOTS];
   __shared__ int64_t red[REG_SLOTS];
@@ -1695,36 +1679,40 @@ __global__ __launch_bounds__(REG_THREADS) void reg_shard_kernel(ShardArgs a)
   __shared__ int stop_sh, last_sh;
   const Prefetched pref = prefetch_points(a.pts);
   GnCore st; // first wave only, identical in all of its lanes
-  if (threadIdx.x < 64)
+  if constexpr (!POSE)
   {
+    if (threadIdx.x < 64)
     {
-      int32_t *w = reinterpret_cast<int32_t *>(&st);
-      const int32_t *src = reinterpret_cast<const int32_t *>(&a.state->core);
+      load_core(st, &a.state->core);
+      if (a.apply)
+      {
+        if (threadIdx.x < 44) s44[threadIdx.x] = coherent_i64(&a.sums[threadIdx.x]);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); // LDS written and read by this wave only
+        __builtin_amdgcn_wave_barrier();
+        gn_update(
+            st, [&](int r, int c) { return s44[c * 6 + r]; }, [&](int r) { return s44[36 + r]; }, (int32_t)s44[42], (int32_t)s44[43]);
+      }
+      if (threadIdx.x == 0)
+      {
 #pragma unroll
-      for (int i = 0; i < (int)(sizeof(GnCore) / 4); ++i) w[i] = coherent_i32(&src[i]);
+        for (int i = 0; i < 16; ++i) T_sh[i] = st.T[i];
+        stop_sh = (st.finished || st.iterations >= st.max_iterations) ? 1 : 0;
+      }
     }
-    if (a.apply)
-    {
-      if (threadIdx.x < 44) s44[threadIdx.x] = coherent_i64(&a.sums[threadIdx.x]);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); // LDS written and read by this wave only
-      __builtin_amdgcn_wave_barrier();
-      gn_update(
-          st, [&](int r, int c) { return s44[c * 6 + r]; }, [&](int r) { return s44[36 + r]; }, (int32_t)s44[42], (int32_t)s44[43]);
-    }
-    if (threadIdx.x == 0)
-    {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) T_sh[i] = st.T[i];
-      stop_sh = (st.finished || st.iterations >= st.max_iterations) ? 1 : 0;
-    }
+    __syncthreads();
   }
-  __syncthreads();
-  const bool stop = stop_sh != 0; // every workgroup alike
+  const bool stop = !POSE && stop_sh != 0; // every workgroup alike
   if (!stop)
   {
     float T[16];
 #pragma unroll
-    for (int i = 0; i < 16; ++i) T[i] = T_sh[i];
+    for (int i = 0; i < 16; ++i)
+    {
+      if constexpr (POSE)
+        T[i] = a.T[i];
+      else
+        T[i] = T_sh[i];
+    }
     int64_t acc[REG_SLOTS];
 #pragma unroll
     for (int t = 0; t < REG_SLOTS; ++t) acc[t] = 0;
@@ -1733,24 +1721,19 @@ __global__ __launch_bounds__(REG_THREADS) void reg_shard_kernel(ShardArgs a)
     if (threadIdx.x < REG_SLOTS) publish_i64(&a.partials[(size_t)blockIdx.x * REG_SLOTS + threadIdx.x], red[threadIdx.x]);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the write-through stores above have been acknowledged ...
   }
-  else if (!a.apply)
-    return; // the loop was over before this launch: nothing to update, nothing to add (the sums stay as they are)
+  else if constexpr (!POSE)
+  {
+    if (!a.apply) return; // the loop was over before this launch: nothing to update, nothing to add (the sums stay as they are)
+  }
   __syncthreads(); // ... for all 32 lanes that made them
   if (threadIdx.x == 0)
     last_sh = __hip_atomic_fetch_add(a.arrived, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1 ? 1 : 0;
   __syncthreads();
   if (!last_sh) return;
   // everybody has read the state and the all-reduced sums: both may change now
-  if (a.apply && threadIdx.x == 0)
+  if constexpr (!POSE)
   {
-    const int32_t *w = reinterpret_cast<const int32_t *>(&st);
-    int32_t *dst = reinterpret_cast<int32_t *>(&a.state->core);
-#pragma unroll
-    for (int i = 0; i < (int)(sizeof(GnCore) / 4); ++i) __hip_atomic_store(&dst[i], w[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-    for (int k = 0; k < 42; ++k) publish_i64(&a.state->sums[k], s44[k]);
-    publish_i64(&a.state->sums[42], (int64_t)(int32_t)s44[42]);
-    publish_i64(&a.state->sums[43], (int64_t)(int32_t)s44[43]);
+    if (a.apply && threadIdx.x == 0) store_state(a.state, st, s44);
   }
   if (!stop)
   {
@@ -1760,56 +1743,19 @@ __global__ __launch_bounds__(REG_THREADS) void reg_shard_kernel(ShardArgs a)
       int64_t sums[44];
       expand_sums(red, sums);
 #pragma unroll
-      for (int k = 0; k < 44; ++k) publish_i64(&a.sums[k], sums[k]);
+      for (int k = 0; k < 44; ++k)
+      {
+        if constexpr (POSE)
+          __hip_atomic_store(&a.sums[k], sums[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        else
+          publish_i64(&a.sums[k], sums[k]);
+      }
     }
   }
-  if (threadIdx.x == 0) __hip_atomic_store(a.arrived, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// ---- perform_registration for a HOST loop (registration.cu:347-368 as the reference's callers use it) in one launch ----
-// tsdf_registration.cpp:55-92 calls perform_registration once per Gauss-Newton iteration and needs h, g, e, c on the host
-// before it can go on: the call is a latency chain, and until round 5 it was a 64-byte copy to the device, two launches, a
-// 352-byte copy back into pageable memory and a stream synchronisation -- 34 us per iteration, 178 of them per scan.  Here the
-// pose travels in the kernel arguments, the last workgroup to arrive adds the partials up and writes the 44 sums and, behind
-// them, the call's sequence number into host-mapped memory; the host spins on that word (ws_reg_iterate).
-struct HostIterArgs
-{
-  PointArgs pts;
-  float T[16];        // column-major
-  int64_t *partials;  // [REG_BLOCKS][REG_SLOTS]
-  uint32_t *arrived;  // zero between launches
-  int64_t *sums_host; // host-mapped: 44 sums, then (at [44]) the sequence number
-  uint32_t seq;
-};
-
-__global__ __launch_bounds__(REG_THREADS) void reg_host_iter_kernel(HostIterArgs a)
-{
-  __shared__ int64_t wave_part[REG_THREADS / 64][REG_SLOTS];
-  __shared__ int64_t red[REG_SLOTS];
-  __shared__ int last_sh;
-  int64_t acc[REG_SLOTS];
-#pragma unroll
-  for (int t = 0; t < REG_SLOTS; ++t) acc[t] = 0;
-  float T[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) T[i] = a.T[i];
-  accumulate_points(a.pts, T, prefetch_points(a.pts), acc);
-  block_reduce32(acc, wave_part, red);
-  if (threadIdx.x < REG_SLOTS) publish_i64(&a.partials[(size_t)blockIdx.x * REG_SLOTS + threadIdx.x], red[threadIdx.x]);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the write-through stores above have been acknowledged ...
-  __syncthreads();                                  // ... for all 32 lanes that made them
-  if (threadIdx.x == 0) last_sh = __hip_atomic_fetch_add(a.arrived, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1 ? 1 : 0;
-  __syncthreads();
-  if (!last_sh) return;
-  sum_partials<true>(a.partials, wave_part, red);
   if (threadIdx.x == 0)
   {
-    int64_t sums[44];
-    expand_sums(red, sums);
-#pragma unroll
-    for (int k = 0; k < 44; ++k) __hip_atomic_store(&a.sums_host[k], sums[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     __hip_atomic_store(a.arrived, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(&a.sums_host[44], (int64_t)a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    if constexpr (POSE) __hip_atomic_store(&a.sums[44], (int64_t)a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
 
@@ -2222,40 +2168,6 @@ static PointArgs make_point_args(ws_reg *r, const ws_map *m, int32_t res, uint32
   return p;
 }
 
-int launch_reg_accumulate(ws_reg *r, const ws_map *m, const float *T_dev_or_null, int32_t res, uint32_t flags, size_t first,
-                          size_t count, int64_t *sums_dev)
-{
-  ws_context *ctx = r->ctx;
-  AccArgs a;
-  a.pts = make_point_args(r, m, res, flags, first, count);
-  a.T = T_dev_or_null ? T_dev_or_null : r->state[r->latest].core.T;
-  a.state = T_dev_or_null ? nullptr : &r->state[r->latest];
-  a.partials = r->partials;
-  prof_begin(ctx, WS_K_REG);
-  hipLaunchKernelGGL(reg_accumulate_kernel, dim3(REG_BLOCKS), dim3(REG_THREADS), 0, ctx->stream, a);
-  hipLaunchKernelGGL(reg_sum_kernel, dim3(1), dim3(REG_THREADS), 0, ctx->stream, (const int64_t *)r->partials, a.state, sums_dev);
-  prof_end(ctx, WS_K_REG);
-  WS_HIP(hipGetLastError());
-  return WS_OK;
-}
-
-int launch_reg_host_iter(ws_reg *r, const ws_map *m, const float T[16], int32_t res, uint32_t flags, uint32_t seq)
-{
-  ws_context *ctx = r->ctx;
-  HostIterArgs a;
-  a.pts = make_point_args(r, m, res, flags, 0, r->n);
-  for (int i = 0; i < 16; ++i) a.T[i] = T[i];
-  a.partials = r->partials;
-  a.arrived = r->shard_arrived + 16; // (a word of its own, a cache line away from reg_shard_kernel's)
-  a.sums_host = r->iter_host_dev;
-  a.seq = seq;
-  prof_begin(ctx, WS_K_REG);
-  hipLaunchKernelGGL(reg_host_iter_kernel, dim3(REG_BLOCKS), dim3(REG_THREADS), 0, ctx->stream, a);
-  prof_end(ctx, WS_K_REG);
-  WS_HIP(hipGetLastError());
-  return WS_OK;
-}
-
 int launch_reg_server(ws_reg *r, const ws_map *m, int32_t res, uint32_t flags, uint32_t launch_id, uint32_t served, uint32_t idle_us)
 {
   ws_context *ctx = r->ctx;
@@ -2284,18 +2196,33 @@ int launch_reg_solve(ws_reg *r, const int64_t *sums_dev)
   return WS_OK;
 }
 
-int launch_reg_shard(ws_reg *r, const ws_map *m, int32_t res, uint32_t flags, size_t first, size_t count, int64_t *sums_dev, int apply)
+int launch_reg_pass(ws_reg *r, const ws_map *m, int32_t res, uint32_t flags, size_t first, size_t count, int64_t *sums, int apply,
+                    const float *T, uint32_t seq)
 {
   ws_context *ctx = r->ctx;
-  ShardArgs a;
-  a.pts = make_point_args(r, m, res, flags, first, count);
-  a.state = &r->state[r->latest]; // one buffer, no parity: see reg_shard_kernel
-  a.sums = sums_dev;
-  a.partials = r->partials;
-  a.arrived = r->shard_arrived;
-  a.apply = apply ? 1 : 0;
   prof_begin(ctx, WS_K_REG);
-  hipLaunchKernelGGL(reg_shard_kernel, dim3(REG_BLOCKS), dim3(REG_THREADS), 0, ctx->stream, a);
+  if (T)
+  {
+    PassArgs<true> a;
+    a.pts = make_point_args(r, m, res, flags, first, count);
+    for (int i = 0; i < 16; ++i) a.T[i] = T[i];
+    a.partials = r->partials;
+    a.arrived = r->pass_arrived;
+    a.sums = sums;
+    a.seq = seq;
+    hipLaunchKernelGGL(reg_pass_kernel<true>, dim3(REG_BLOCKS), dim3(REG_THREADS), 0, ctx->stream, a);
+  }
+  else
+  {
+    PassArgs<false> a;
+    a.pts = make_point_args(r, m, res, flags, first, count);
+    a.state = &r->state[r->latest]; // one buffer, no parity: see reg_pass_kernel
+    a.sums = sums;
+    a.partials = r->partials;
+    a.arrived = r->pass_arrived;
+    a.apply = apply ? 1 : 0;
+    hipLaunchKernelGGL(reg_pass_kernel<false>, dim3(REG_BLOCKS), dim3(REG_THREADS), 0, ctx->stream, a);
+  }
   prof_end(ctx, WS_K_REG);
   WS_HIP(hipGetLastError());
   return WS_OK;

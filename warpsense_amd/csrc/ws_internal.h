@@ -296,8 +296,8 @@ struct ws_reg
   ws_context *ctx = nullptr;
   int32_t *points = nullptr;
   size_t cap = 0, n = 0;
-  int64_t *partials = nullptr; // [2][32][REG_BLOCKS]
-  ws::GnState *state = nullptr;      // [2] device, double buffered by launch parity
+  int64_t *partials = nullptr; // [2][REG_BLOCKS][32]: reg_iter_kernel alternates, reg_pass_kernel uses [0]
+  ws::GnState *state = nullptr;      // [2] device, double buffered by reg_iter_kernel's launch parity
   ws::GnState *state_host = nullptr; // pinned staging
   ws::GnState *result_host = nullptr;     // pinned + mapped: the resident loop writes its final state here
   ws::GnState *result_host_dev = nullptr; // device view of result_host
@@ -306,7 +306,7 @@ struct ws_reg
   int latest = 0;                    // state buffer holding the newest state
   int64_t *sums_dev = nullptr;       // 44
   uint32_t *grid_bar = nullptr;      // two sets of {abort flag, counted group accumulators} of reg_loop_kernel (alternate launches)
-  uint32_t *shard_arrived = nullptr;  // arrival counter of reg_shard_kernel (zero between launches); [16]: reg_host_iter_kernel's
+  uint32_t *pass_arrived = nullptr;   // arrival counter of reg_pass_kernel (zero between launches, which are ordered on the stream)
   int64_t *iter_host = nullptr;       // pinned + mapped: the 44 sums of ws_reg_iterate, then the call's sequence number
   int64_t *iter_host_dev = nullptr;   // device view of iter_host
   uint32_t iter_seq = 0;
@@ -319,7 +319,7 @@ struct ws_reg
   uint32_t srv_ids = 0;               // launch ids handed out
   uint32_t srv_seq = 0;               // request numbers handed out (1 .. 2^31 - 1)
   uint32_t srv_served = 0;            // the last request that was answered
-  int srv_enabled = 1;                // 0: one launch per ws_reg_iterate (reg_host_iter_kernel), WS_REG_SERVER=0
+  int srv_enabled = 1;                // 0: one launch per ws_reg_iterate (reg_pass_kernel), WS_REG_SERVER=0
   uint32_t srv_idle_us = 50;          // the server leaves after this long without a request
   uint32_t srv_launches = 0;          // statistics (ws_debug_reg_server)
   struct
@@ -399,12 +399,12 @@ int fill_u32(ws_context *ctx, uint32_t *dst, uint32_t value, int64_t n);
 int launch_box_fill(ws_map *m, const ws::MapParams &par, int which, const int32_t lo[3], const int32_t ext[3], uint32_t value, hipStream_t stream);
 int check_all_equal_host(const uint32_t *data, int64_t n, uint32_t value);
 
-int launch_reg_accumulate(ws_reg *r, const ws_map *m, const float *T_dev_or_null, int32_t res, uint32_t flags,
-                          size_t first, size_t count, int64_t *sums_dev);
 int launch_reg_iteration(ws_reg *r, const ws_map *m, int32_t res, uint32_t flags, int32_t k);
-int launch_reg_shard(ws_reg *r, const ws_map *m, int32_t res, uint32_t flags, size_t first, size_t count, int64_t *sums_dev, int apply);
+// reg_pass_kernel over points [first, first + count): from the newest state (first the update from `sums` if `apply`) into `sums`;
+// or, given a pose T, without a state into host-mapped `sums`, then `seq`
+int launch_reg_pass(ws_reg *r, const ws_map *m, int32_t res, uint32_t flags, size_t first, size_t count, int64_t *sums, int apply,
+                    const float *T = nullptr, uint32_t seq = 0);
 int launch_reg_solve(ws_reg *r, const int64_t *sums_dev);
-int launch_reg_host_iter(ws_reg *r, const ws_map *m, const float T[16], int32_t res, uint32_t flags, uint32_t seq);
 int launch_reg_server(ws_reg *r, const ws_map *m, int32_t res, uint32_t flags, uint32_t launch_id, uint32_t served, uint32_t idle_us);
 size_t reg_server_mail_bytes();
 size_t reg_server_ctl_bytes();
