@@ -211,17 +211,18 @@ __device__ __forceinline__ void block_reduce32(int64_t (&v)[REG_SLOTS], int64_t 
 // row-major upper triangle index of (i <= j)
 __host__ __device__ constexpr int tri_index(int i, int j) { return i * 6 - (i * (i - 1)) / 2 + (j - i); }
 
-// 29 reduced terms -> the reference's 44 words: h 6x6 column-major (math/matrix6x6.h:112-115), g[6], e, c
+// The reference's 44 words -- h 6x6 column-major (math/matrix6x6.h:112-115), g[6], e, c -- and the slot of the 29 reduced terms
+// word k is made from.  e and c are `int` in the reference (registration.cu:16-21): words 42 and 43 are their slot's low 32 bits,
+// sign-extended (word_value).  h_slot: element (r, c) of the symmetric h, word 6 c + r, for callers that index h at run time.
+__host__ __device__ constexpr int h_slot(int r, int c) { return r <= c ? tri_index(r, c) : tri_index(c, r); }
+__host__ __device__ constexpr int word_slot(int k) { return k < 36 ? h_slot(k % 6, k / 6) : k < 42 ? 21 + (k - 36) : 27 + (k - 42); }
+__device__ __forceinline__ int64_t word_value(int k, int64_t slot_value) { return k < 42 ? slot_value : (int64_t)(int32_t)slot_value; }
+
+// 29 reduced terms -> the reference's 44 words
 __device__ __forceinline__ void expand_sums(const int64_t *terms, int64_t *sums)
 {
 #pragma unroll
-  for (int j = 0; j < 6; ++j)
-#pragma unroll
-    for (int i = 0; i < 6; ++i) sums[j * 6 + i] = terms[i <= j ? tri_index(i, j) : tri_index(j, i)];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) sums[36 + i] = terms[21 + i];
-  sums[42] = (int64_t)(int32_t)terms[27]; // e and c are `int` in the reference (registration.cu:16-21)
-  sums[43] = (int64_t)(int32_t)terms[28];
+  for (int k = 0; k < 44; ++k) sums[k] = word_value(k, terms[word_slot(k)]);
 }
 
 // ---- 6x6 solve on one wave: Gauss-Jordan with partial pivoting in double, the same operations in the same order as
@@ -539,12 +540,12 @@ __device__ __forceinline__ void gn_update(GnCore &st, HF H, GF G, int32_t e, int
   gn_convergence(st, e, c);
 }
 
-// the update fed from the 29 reduced terms in LDS (e and c are `int` in the reference, registration.cu:16-21)
+// the update fed from the 29 reduced terms in LDS
 __device__ __forceinline__ void gn_update_terms(GnCore &st, const int64_t *terms)
 {
   gn_update(
-      st, [terms](int r, int c) { return terms[r <= c ? tri_index(r, c) : tri_index(c, r)]; }, [terms](int r) { return terms[21 + r]; },
-      (int32_t)terms[27], (int32_t)terms[28]);
+      st, [terms](int r, int c) { return terms[h_slot(r, c)]; }, [terms](int r) { return terms[word_slot(36 + r)]; },
+      (int32_t)terms[word_slot(42)], (int32_t)terms[word_slot(43)]);
 }
 
 // The update fed from REGISTERS (reg_loop_kernel): `total` is what the exchange left in lanes 0 .. 31 (the total of slot
@@ -555,14 +556,15 @@ __device__ __forceinline__ void gn_update_total(GnCore &st, int64_t total, float
 {
   const int lane = threadIdx.x & 63, lr = lane >> 3, lc = lane & 7;
   int src = 29; // an empty slot
-  if (lr < 6 && lc < 6) src = lr <= lc ? tri_index(lr, lc) : tri_index(lc, lr);
-  if (lr < 6 && lc == 6) src = 21 + lr;
+  if (lr < 6 && lc < 6) src = h_slot(lr, lc);
+  if (lr < 6 && lc == 6) src = word_slot(36 + lr);
   const int lo = __builtin_amdgcn_ds_bpermute(src << 2, (int)(uint32_t)((uint64_t)total & 0xffffffffull));
   const int hi = __builtin_amdgcn_ds_bpermute(src << 2, (int)(uint32_t)((uint64_t)total >> 32));
   const int64_t mine = pack64(lo, hi);
-  // (uniform values the vector unit computes with: kept out of the scalar registers, like the loop state)
-  int32_t e = __builtin_amdgcn_ds_bpermute(27 << 2, (int)(uint32_t)((uint64_t)total & 0xffffffffull));
-  int32_t c = __builtin_amdgcn_ds_bpermute(28 << 2, (int)(uint32_t)((uint64_t)total & 0xffffffffull));
+  // (uniform values the vector unit computes with: kept out of the scalar registers, like the loop state; the low 32 bits are the
+  // `int` words 42, 43)
+  int32_t e = __builtin_amdgcn_ds_bpermute(word_slot(42) << 2, (int)(uint32_t)((uint64_t)total & 0xffffffffull));
+  int32_t c = __builtin_amdgcn_ds_bpermute(word_slot(43) << 2, (int)(uint32_t)((uint64_t)total & 0xffffffffull));
   pin_vgpr(e);
   pin_vgpr(c);
   GnStep o;
@@ -1068,6 +1070,40 @@ __device__ __forceinline__ void accumulate_points(const PointArgs &a, const floa
   }
 }
 
+// One pass of a resident kernel (an iteration of the loop, a request to the server) over the points for the pose in T_sh / TI_sh:
+// the workgroup's totals added into wg_sum (zero before; the caller's barrier follows).  MFMA: one point per lane, the sums on the
+// matrix cores; else v_mad_i64_i32 and the transposing butterfly.  The voxel caches stay valid for as long as the map and the cloud
+// do not change, which is the whole launch of either kernel.  mid(): between the sums and their flush into wg_sum (timing stamps).
+template <bool MFMA, typename Mid>
+__device__ __forceinline__ void pass_sums(const PointArgs &a, const LoopGather &lg, const Prefetched &f, uint32_t stride, const float *T_sh,
+                                          const int32_t *TI_sh, VoxelCache (&cache)[2], uint32_t *mf_stage, const MfLane &mfl,
+                                          unsigned long long *wg_sum, Mid mid)
+{
+  if (MFMA)
+  {
+    const IntTransform t = load_int_pose(TI_sh);
+    const Gathered g0 = gather_point_loop(a, lg, t, f.p[0][0], f.p[0][1], f.p[0][2], f.valid[0], cache[0]);
+    mf_v16i C;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) C[i] = 0;
+    mfma_consume(g0, C, mf_stage + (threadIdx.x >> 6) * MF_STAGE_WORDS, mfl);
+    mid();
+    mfma_flush(C, wg_sum, mfl);
+  }
+  else
+  {
+    float T[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) T[i] = T_sh[i];
+    int64_t acc[REG_SLOTS];
+#pragma unroll
+    for (int t = 0; t < REG_SLOTS; ++t) acc[t] = 0;
+    accumulate_points<true>(a, T, f, acc, cache, stride);
+    mid();
+    wave_reduce32_add(acc, wg_sum);
+  }
+}
+
 // Sum of the partials [REG_BLOCKS][REG_SLOTS] a previous launch left in HBM -> red[0..31] in LDS.
 // Lane l of wave w adds slot (l >> 1) over 32 of the wave's 64 workgroups: 32 independent, fully coalesced
 // loads per lane (one memory latency), one shuffle, one LDS hop.
@@ -1242,9 +1278,66 @@ constexpr int REG_PEER_POLL_SLEEP = WS_REG_PEER_POLL_SLEEP; // x 64 clocks befor
 constexpr long long REG_BARRIER_TIMEOUT_TICKS = 500000ll;
 constexpr long long REG_PEER_TIMEOUT_TICKS = 2000000ll;
 
-// first wave (all 64 lanes), after wave_reduce32: workgroup total of every slot, one half per lane, into the group accumulator
+// The three steps of a counted exchange, for a wave with all 64 lanes active: lane l < 32 deals in the low half of slot l,
+// lane l + 32 in the high half of the same slot.
+// counted_add: `total` (in every lane the total of slot lane & 31) into the REG_WORDS words at `row`
+template <int SCOPE>
+__device__ __forceinline__ void counted_add(uint64_t *row, uint64_t total)
+{
+  const int lane = threadIdx.x & 63;
+  const uint32_t half = lane < REG_SLOTS ? (uint32_t)(total & 0xffffffffull) : (uint32_t)(total >> 32);
+  __hip_atomic_fetch_add(&row[lane], REG_COUNT_ONE | half, __ATOMIC_RELAXED, SCOPE);
+}
+
+// counted_poll: read this lane's N words (word g at words[g * REG_WORDS]) into w until every word of every lane has counted
+// `count` additions since then[g].  BOUNDED: false after `limit` ticks of the wall clock, or once another workgroup has given up
+// (*abort_flag, which a workgroup that gives up sets for the others); unbounded polls wait for as long as it takes.
+template <int N, int SCOPE, bool BOUNDED>
+__device__ __forceinline__ bool counted_poll(uint64_t *words, const uint64_t (&then)[N], uint32_t count, uint64_t (&w)[N], long long limit = 0,
+                                             uint32_t *abort_flag = nullptr)
+{
+  uint32_t spins = 0;
+  long long t0 = 0;
+  for (;;)
+  {
+    bool ok = true;
+#pragma unroll
+    for (int g = 0; g < N; ++g)
+    {
+      w[g] = __hip_atomic_load(&words[(size_t)g * REG_WORDS], __ATOMIC_RELAXED, SCOPE);
+      ok &= ((w[g] - then[g]) >> 56) == (uint64_t)count; // (&=, not &&: && became a branch per word and spilled the loop kernels)
+    }
+    if (__all(ok)) break;
+    __builtin_amdgcn_s_sleep(REG_POLL_SLEEP);
+    if (BOUNDED && (++spins & 1023u) == 0)
+    {
+      const long long now = wall_clock64();
+      if (t0 == 0) t0 = now;
+      const bool give_up = now - t0 > limit || __hip_atomic_load(abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
+      if (__any(give_up))
+      {
+        if ((threadIdx.x & 63) == 0) __hip_atomic_store(abort_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return false;
+      }
+    }
+  }
+  return true;
+}
+
+// counted_fold: lanes 0 .. 31 get the total of slot `lane` over the additions the words w have counted since then
+template <int N>
+__device__ __forceinline__ int64_t counted_fold(const uint64_t (&w)[N], const uint64_t (&then)[N])
+{
+  uint64_t s = 0;
+#pragma unroll
+  for (int g = 0; g < N; ++g) s += (w[g] - then[g]) & REG_SUM_MASK;
+  const uint64_t high = (uint64_t)shfl_xor_i64((int64_t)s, 32);
+  return (int64_t)(s + (high << 32));
+}
+
+// first wave (all 64 lanes), after the workgroup's sums are in wg_sum: its total of every slot into the group accumulator
 template <bool MFMA = false>
-__device__ __forceinline__ void counted_publish(uint64_t *accum /* [REG_GROUPS][REG_WORDS] of this parity */, unsigned long long *wg_sum, bool publish,
+__device__ __forceinline__ void counted_publish(uint64_t *accum /* [REG_GROUPS][REG_WORDS] */, unsigned long long *wg_sum, bool publish,
                                                 const uint32_t per_group = REG_BLOCKS / REG_GROUPS, const MfLane *mf = nullptr)
 {
   const int lane = threadIdx.x & 63, slot = lane & (REG_SLOTS - 1);
@@ -1254,12 +1347,10 @@ __device__ __forceinline__ void counted_publish(uint64_t *accum /* [REG_GROUPS][
   else
   {
     s = wg_sum[slot];
-    if (lane < REG_SLOTS) wg_sum[slot] = 0; // for the next iteration (the same wave read it one instruction ago)
+    if (lane < REG_SLOTS) wg_sum[slot] = 0; // for the next pass (the same wave read it one instruction ago)
   }
   if (!publish) return;
-  const uint32_t half = lane < REG_SLOTS ? (uint32_t)((uint64_t)s & 0xffffffffull) : (uint32_t)((uint64_t)s >> 32);
-  const int group = (int)(blockIdx.x / per_group);
-  __hip_atomic_fetch_add(&accum[(size_t)group * REG_WORDS + lane], REG_COUNT_ONE | half, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  counted_add<__HIP_MEMORY_SCOPE_AGENT>(accum + (size_t)(blockIdx.x / per_group) * REG_WORDS, s);
 }
 
 // first wave: poll the accumulators of one parity until all workgroups have added, then red[0..31] = the totals of the
@@ -1271,43 +1362,15 @@ __device__ __forceinline__ bool counted_collect(uint64_t *accum, uint32_t *abort
 {
   const int lane = threadIdx.x & 63;
   uint64_t w[REG_GROUPS];
-  uint32_t spins = 0;
-  long long t0 = 0;
   __builtin_amdgcn_s_sleep(REG_FIRST_POLL_SLEEP); // see above: a poll that fails is worse than a poll that starts late
-  for (;;)
-  {
-    bool ok = true;
-#pragma unroll
-    for (int g = 0; g < REG_GROUPS; ++g)
-    {
-      w[g] = __hip_atomic_load(&accum[(size_t)g * REG_WORDS + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      ok = ok && ((w[g] - then_cur[g]) >> 56) == (uint64_t)per_group;
-    }
-    if (__all(ok)) break;
-    __builtin_amdgcn_s_sleep(REG_POLL_SLEEP);
-    if ((++spins & 1023u) == 0)
-    {
-      const long long now = wall_clock64();
-      if (t0 == 0) t0 = now;
-      const bool give_up = now - t0 > REG_BARRIER_TIMEOUT_TICKS || __hip_atomic_load(abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
-      if (__any(give_up))
-      {
-        if (lane == 0) __hip_atomic_store(abort_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return false;
-      }
-    }
-  }
-  uint64_t s = 0;
+  if (!counted_poll<REG_GROUPS, __HIP_MEMORY_SCOPE_AGENT, true>(accum + lane, then_cur, per_group, w, REG_BARRIER_TIMEOUT_TICKS, abort_flag)) return false;
+  const int64_t total = counted_fold(w, then_cur); // lanes 0 .. 31: the total of slot `lane`
 #pragma unroll
   for (int g = 0; g < REG_GROUPS; ++g)
   {
-    s += (w[g] - then_cur[g]) & REG_SUM_MASK;
-    const uint64_t t = then_other[g]; // the other parity is read next
+    then_cur[g] = then_other[g]; // the other parity is read next
     then_other[g] = w[g];
-    then_cur[g] = t;
   }
-  const uint64_t high = (uint64_t)shfl_xor_i64((int64_t)s, 32);
-  const int64_t total = (int64_t)(s + (high << 32)); // lanes 0 .. 31: the total of slot `lane`
   if (lane < REG_SLOTS) red[lane] = total;
   if (total_out) *total_out = total;
   return true;
@@ -1339,38 +1402,15 @@ __device__ __forceinline__ bool peer_exchange(const PeerBlock *pb, int parity, u
   const int64_t other = shfl_xor_i64(total, 32); // lanes 32 .. 63 take the total of slot lane - 32 from the lower half
   const uint64_t mine = (uint64_t)(lane < REG_SLOTS ? total : other);
   if (blockIdx.x == 0)
-  {
-    const uint32_t half = lane < REG_SLOTS ? (uint32_t)(mine & 0xffffffffull) : (uint32_t)(mine >> 32);
-    for (int r = 0; r < world; ++r)
-      __hip_atomic_fetch_add(pb->mailbox[r] + (size_t)parity * REG_WORDS + lane, REG_COUNT_ONE | half, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
-  uint64_t *own = pb->mailbox[pb->rank] + (size_t)parity * REG_WORDS + lane;
-  uint64_t w;
-  uint32_t spins = 0;
-  long long t0 = 0;
-  const long long limit = pb->timeout_ticks;
+    for (int r = 0; r < world; ++r) counted_add<__HIP_MEMORY_SCOPE_SYSTEM>(pb->mailbox[r] + (size_t)parity * REG_WORDS, mine);
+  const uint64_t before[1] = {then};
+  uint64_t w[1];
   __builtin_amdgcn_s_sleep(REG_PEER_POLL_SLEEP);
-  for (;;)
-  {
-    w = __hip_atomic_load(own, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    if (__all(((w - then) >> 56) == (uint64_t)world)) break;
-    __builtin_amdgcn_s_sleep(REG_POLL_SLEEP);
-    if ((++spins & 1023u) == 0)
-    {
-      const long long now = wall_clock64();
-      if (t0 == 0) t0 = now;
-      const bool give_up = now - t0 > limit || __hip_atomic_load(abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
-      if (__any(give_up))
-      {
-        if (lane == 0) __hip_atomic_store(abort_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return false;
-      }
-    }
-  }
-  const uint64_t sum = (w - then) & REG_SUM_MASK;
-  then = w;
-  const uint64_t high = (uint64_t)shfl_xor_i64((int64_t)sum, 32);
-  total = (int64_t)(sum + (high << 32));
+  if (!counted_poll<1, __HIP_MEMORY_SCOPE_SYSTEM, true>(pb->mailbox[pb->rank] + (size_t)parity * REG_WORDS + lane, before, world, w, pb->timeout_ticks,
+                                                        abort_flag))
+    return false;
+  then = w[0];
+  total = counted_fold(w, before);
   if (lane < REG_SLOTS) red[lane] = total;
   return true;
 }
@@ -1496,31 +1536,7 @@ __global__ __launch_bounds__(REG_THREADS) void reg_loop_kernel(LoopArgs a)
     const bool ofilled = cache[0].filled;
 #endif
     if (wave_has_points) // (uniform per wave; point_slot(): a small cloud or shard leaves whole waves of every workgroup without points)
-    {
-      if (MFMA)
-      {
-        const IntTransform t = load_int_pose(TI_sh);
-        const Gathered g0 = gather_point_loop(a.pts, lg, t, pref.p[0][0], pref.p[0][1], pref.p[0][2], pref.valid[0], cache[0]);
-        mf_v16i C;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) C[i] = 0;
-        mfma_consume(g0, C, mf_stage + (threadIdx.x >> 6) * MF_STAGE_WORDS, mfl);
-        WS_LSTAMP(4);
-        mfma_flush(C, wg_sum, mfl);
-      }
-      else
-      {
-        float T[16];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) T[i] = T_sh[i];
-        int64_t acc[REG_SLOTS];
-#pragma unroll
-        for (int t = 0; t < REG_SLOTS; ++t) acc[t] = 0;
-        accumulate_points<true>(a.pts, T, pref, acc, cache, stride);
-        WS_LSTAMP(4);
-        wave_reduce32_add(acc, wg_sum);
-      }
-    }
+      pass_sums<MFMA>(a.pts, lg, pref, stride, T_sh, TI_sh, cache, mf_stage, mfl, wg_sum, [&] { WS_LSTAMP(4); });
     __syncthreads();
     WS_LSTAMP(5);
     if (threadIdx.x < 64)
@@ -1792,13 +1808,15 @@ __host__ __device__ inline uint64_t server_line_tag(uint32_t seq, const uint64_t
   return ((uint64_t)seq << 32) | (uint32_t)(x ^ (x >> 32));
 }
 size_t reg_server_mail_bytes() { return sizeof(ServerMail); }
-__host__ __device__ inline uint32_t server_checksum(const uint32_t *line)
+// checksum of the request line: its number `seq` (word 3) and the pose words; word(i) gives word i of the line
+template <typename Word>
+__host__ __device__ __forceinline__ uint32_t server_checksum(uint32_t seq, Word word)
 {
-  uint32_t c = 0x5bd1e995u ^ line[3];
+  uint32_t c = 0x5bd1e995u ^ seq;
 #pragma unroll
   for (int j = 0; j < 4; ++j)
 #pragma unroll
-    for (int i = 0; i < 3; ++i) c = (c << 5 | c >> 27) ^ line[j * 4 + i];
+    for (int i = 0; i < 3; ++i) c = (c << 5 | c >> 27) ^ word(j * 4 + i);
   return c;
 }
 void reg_server_mail_write(void *mail, const float T[16], uint32_t seq)
@@ -1811,7 +1829,7 @@ void reg_server_mail_write(void *mail, const float T[16], uint32_t seq)
   volatile uint32_t *dst = m->line;
   for (int j = 0; j < 4; ++j)
     for (int i = 0; i < 3; ++i) dst[j * 4 + i] = line[j * 4 + i];
-  dst[11] = server_checksum(line);
+  dst[11] = server_checksum(seq, [&](int i) { return line[i]; });
   std::atomic_thread_fence(std::memory_order_release);
   dst[3] = seq; // the request is complete
 }
@@ -1886,7 +1904,7 @@ int reg_server_mail_selftest()
   reg_server_mail_write(m, T, 77);
   uint32_t line[16];
   for (int i = 0; i < 16; ++i) line[i] = m->line[i];
-  if (line[3] != 77 || line[11] != server_checksum(line)) bad |= 64;
+  if (line[3] != 77 || line[11] != server_checksum(line[3], [&](int i) { return line[i]; })) bad |= 64;
   delete m;
   return bad;
 }
@@ -1927,35 +1945,33 @@ __device__ __forceinline__ int server_line_state(uint32_t w /* lane l < 16: word
   if (seq == served || seq == 0) return leave ? 2 : 0;
   // a consistent snapshot?  (the writer stores the number last; a read that saw it and not all of the pose -- torn in two on the
   // way -- fails the checksum and is simply repeated)
-  uint32_t c = 0x5bd1e995u ^ seq;
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-#pragma unroll
-    for (int i = 0; i < 3; ++i) c = (c << 5 | c >> 27) ^ (uint32_t)__builtin_amdgcn_readlane((int)w, j * 4 + i);
-  return c == (uint32_t)__builtin_amdgcn_readlane((int)w, 11) ? 1 : 0;
+  const auto word = [w](int i) { return (uint32_t)__builtin_amdgcn_readlane((int)w, i); };
+  return server_checksum(seq, word) == word(11) ? 1 : 0;
 }
 
 template <bool MFMA>
 __global__ __launch_bounds__(REG_THREADS) void reg_server_kernel(ServerArgs a)
 {
-  __shared__ int64_t wave_part[MFMA ? 1 : REG_THREADS / 64][REG_SLOTS];
-  __shared__ int64_t red[REG_SLOTS];
-  __shared__ unsigned long long wg_sum[REG_SLOTS + MF_AUX]; // MFMA: the workgroup's totals of a request (LDS atomics of the eight waves)
+  __shared__ unsigned long long wg_sum[REG_SLOTS + MF_AUX]; // the workgroup's totals of a request (LDS atomics of the eight waves)
   __shared__ alignas(16) uint32_t mf_stage[MFMA ? (REG_THREADS / 64) * MF_STAGE_WORDS : 4];
   __shared__ alignas(16) float T_sh[16];
   __shared__ alignas(16) int32_t TI_sh[16];
   __shared__ uint32_t bell_sh; // 0: leave
   // the cloud does not change while a server lives (ws_reg_prepare* stops it): its points stay in registers from call to call,
-  // and -- MFMA, clouds of at most one point per lane -- so does the voxel each point fell into with its seven entries (the map does
-  // not change either: whoever enqueues an update asks the server to leave first)
+  // and so do the voxels its first two points per lane fell into with their seven entries (the map does not change either: whoever
+  // enqueues an update asks the server to leave first)
   const Prefetched f = prefetch_points(a.pts);
   const bool wave_has_points = __ballot(f.valid[0]) != 0ull;
   const MfLane mfl = make_mf_lane();
   const LoopGather lg = make_loop_gather(a.pts);
-  VoxelCache cache;
-  cache.bx = cache.by = cache.bz = 0;
-  cache.cur = cache.xn = cache.xl = cache.yn = cache.yl = cache.zn = cache.zl = 0;
-  cache.filled = false;
+  VoxelCache cache[2];
+#pragma unroll
+  for (int u = 0; u < 2; ++u)
+  {
+    cache[u].bx = cache[u].by = cache[u].bz = 0;
+    cache[u].cur = cache[u].xn = cache[u].xl = cache[u].yn = cache[u].yl = cache[u].zn = cache[u].zl = 0;
+    cache[u].filled = false;
+  }
   constexpr uint32_t per_group = REG_BLOCKS / REG_GROUPS;
   const int lane = threadIdx.x & 63;
   const int group = (int)(blockIdx.x / per_group);
@@ -1966,7 +1982,7 @@ __global__ __launch_bounds__(REG_THREADS) void reg_server_kernel(ServerArgs a)
 #pragma unroll
     for (int g = 0; g < REG_GROUPS; ++g) then[g] = a.ctl->then[g][lane];
   }
-  if (MFMA && threadIdx.x < REG_SLOTS + MF_AUX) wg_sum[threadIdx.x] = 0;
+  if (threadIdx.x < REG_SLOTS + MF_AUX) wg_sum[threadIdx.x] = 0;
   for (;;)
   {
     // ---- wave 0 waits for a request
@@ -2019,81 +2035,23 @@ __global__ __launch_bounds__(REG_THREADS) void reg_server_kernel(ServerArgs a)
     const uint32_t bell = bell_sh;
     if (bell == 0) break;
     // ---- perform_registration (registration.cu:347-368) for that pose
-    if (MFMA)
-    {
-      // the sums on the matrix cores, as in the resident loop (reg_loop_kernel)
-      if (wave_has_points)
-      {
-        const IntTransform t = load_int_pose(TI_sh);
-        const Gathered g0 = gather_point_loop(a.pts, lg, t, f.p[0][0], f.p[0][1], f.p[0][2], f.valid[0], cache);
-        mf_v16i C;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) C[i] = 0;
-        mfma_consume(g0, C, mf_stage + (threadIdx.x >> 6) * MF_STAGE_WORDS, mfl);
-        mfma_flush(C, wg_sum, mfl);
-      }
-      __syncthreads(); // (also keeps T_sh / TI_sh / bell_sh from being rewritten while anybody reads them)
-    }
-    else
-    {
-      float T[16];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) T[i] = T_sh[i];
-      int64_t acc[REG_SLOTS];
-#pragma unroll
-      for (int t = 0; t < REG_SLOTS; ++t) acc[t] = 0;
-      accumulate_points(a.pts, T, f, acc);
-      block_reduce32(acc, wave_part, red); // (its barriers: see above)
-    }
+    if (wave_has_points) pass_sums<MFMA>(a.pts, lg, f, REG_STRIDE, T_sh, TI_sh, cache, mf_stage, mfl, wg_sum, [] {});
+    __syncthreads(); // (also keeps T_sh / TI_sh / bell_sh from being rewritten while anybody reads them)
     if (threadIdx.x < 64)
     {
-      uint64_t s;
-      if (MFMA)
-        s = mfma_finalize(wg_sum, mfl); // lanes 0..31 and 32..63: the total of slot lane & 31 (and wg_sum is zero again)
-      else
-        s = (uint64_t)red[lane & (REG_SLOTS - 1)];
-      const uint32_t half = lane < REG_SLOTS ? (uint32_t)(s & 0xffffffffull) : (uint32_t)(s >> 32);
-      __hip_atomic_fetch_add(&a.ctl->accum[group][lane], REG_COUNT_ONE | half, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      counted_publish<MFMA>(&a.ctl->accum[0][0], wg_sum, true, per_group, &mfl);
       if (blockIdx.x == 0)
       {
         // ---- all 256 additions, then the 44 words of the reference's h, g, e, c to the host
         uint64_t wv[REG_GROUPS];
-        for (;;)
-        {
-          bool ok = true;
+        counted_poll<REG_GROUPS, __HIP_MEMORY_SCOPE_AGENT, false>(&a.ctl->accum[0][lane], then, per_group, wv);
+        const int64_t total = counted_fold(wv, then); // lanes 0 .. 31: the total of slot `lane`
 #pragma unroll
-          for (int g = 0; g < REG_GROUPS; ++g)
-          {
-            wv[g] = __hip_atomic_load(&a.ctl->accum[g][lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            ok = ok && (((wv[g] - then[g]) >> 56) & 0xffu) == (uint64_t)per_group;
-          }
-          if (__all(ok)) break;
-          __builtin_amdgcn_s_sleep(2);
-        }
-        uint64_t sum = 0;
-#pragma unroll
-        for (int g = 0; g < REG_GROUPS; ++g)
-        {
-          sum += (wv[g] - then[g]) & REG_SUM_MASK;
-          then[g] = wv[g];
-        }
-        const uint64_t high = (uint64_t)shfl_xor_i64((int64_t)sum, 32);
-        const int64_t total = (int64_t)(sum + (high << 32)); // lanes 0 .. 31: the total of slot `lane`
+        for (int g = 0; g < REG_GROUPS; ++g) then[g] = wv[g];
         // expand_sums: word k of the reference's 44 comes from the lane that holds its term; lane 8 j + i (i < 7) of the answer holds
         // word 7 j + i, lane 8 j + 7 the tag of line j
         const int line = lane >> 3, wi = lane & 7, k = 7 * line + wi;
-        int src = 0;
-        if (k < 36)
-        {
-          const int i = k % 6, j = k / 6;
-          src = i <= j ? tri_index(i, j) : tri_index(j, i);
-        }
-        else if (k < 42)
-          src = 21 + (k - 36);
-        else if (k < 44)
-          src = 27 + (k - 42);
-        int64_t v = shfl_i64(total, src);
-        if (k >= 42) v = (int64_t)(int32_t)v; // e and c are `int` in the reference (registration.cu:16-21)
+        int64_t v = word_value(k, shfl_i64(total, k < 44 ? word_slot(k) : 0));
         if (k >= 44 || wi == 7) v = 0;
         // the tag of a line: from its seven words, gathered into the line's last lane
         uint64_t x = 0x9E3779B97F4A7C15ull;
