@@ -231,8 +231,7 @@ __device__ __forceinline__ void ray_setup_block(const ScatterArgs &a)
     a.counters->free_cursor = 0;
     a.counters->n_listed = 0;
     a.counters->n_appended = 0;
-    a.counters->abort = 0;
-    a.counters->error = 0;
+    a.counters->abort = 0; // (set by later launches only: the key-range verdict of this pass goes to range_seq)
     a.counters->last_free_keyed = 0;
     a.counters->last_unlisted = 0;
   }
@@ -307,13 +306,13 @@ __device__ __forceinline__ void ray_setup_block(const ScatterArgs &a)
         {
           // Outside the range of the record's step / fan fields for a scan of this many points.  With the widest split (scans of
           // up to 16 384 points: 65 536 steps, 255 fan steps) that is the end: the ray is dropped and the error is sticky.  A
-          // larger scan is ABORTED instead (bit 1 of the abort word; nothing of it reaches the maps) and the host repeats it in
+          // larger scan is ABORTED instead (range_seq = scan_seq; nothing of it reaches the maps) and the host repeats it in
           // pieces of 16 384 points, each with the widest split, one after the other into new_map (settle_tsdf: the serial order
           // is the order of the points, so consecutive pieces folded on top of each other are the same schedule).
           if ((a.rec_fmt & 0xffu) == 16u && (a.rec_fmt >> 8) == 8u)
             raise_error(a.counters, a.status, ERR_RANGE);
           else
-            __hip_atomic_fetch_or(&a.counters->abort, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&a.counters->range_seq, a.scan_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         else
         {
@@ -538,7 +537,7 @@ __device__ __forceinline__ uint32_t big_slot(unsigned long long key, uint32_t ma
 // back and the host repeats the scan with a larger pool (launch_tsdf_scatter)
 __device__ __forceinline__ void raise_abort(const ScatterArgs &a)
 {
-  __hip_atomic_fetch_or(&a.counters->abort, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // (bit 1: a ray beyond the key range, ray_setup_block)
+  __hip_atomic_fetch_or(&a.counters->abort, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // (pool exhausted only; a ray beyond the key range goes to range_seq, ray_setup_block)
 }
 
 // The pool, bottom to top: [one block of SUB_WG_BLOCK ids per work item of the tail march | what its waves ask for on top of
@@ -1313,7 +1312,7 @@ __global__ __launch_bounds__(WS_FREE_THREADS, WS_FREE_WGS * 256 / WS_FREE_THREAD
 #ifdef WS_FREE_TIMING
   const long long t_free_begin = wall_clock64();
 #endif
-  if (a.counters->abort != 0) return; // (the tail march ran out of sub-chunks: the host repeats the scan)
+  if (a.counters->abort != 0 || a.counters->range_seq == a.scan_seq) return; // (out of sub-chunks, or a ray beyond the key range: the host repeats the scan)
   __shared__ uint32_t s_keyed[WS_FREE_THREADS / 64];
   const uint32_t ix = blockIdx.x * (uint32_t)(WS_FREE_THREADS / FREE_LANES) + threadIdx.x / (uint32_t)FREE_LANES;
   const int32_t c = (int32_t)(threadIdx.x % (uint32_t)FREE_LANES);
@@ -1632,7 +1631,7 @@ __global__ __launch_bounds__(256, WS_RESOLVE_WGS) void tile_resolve_kernel(Resol
   const long long t_begin = wall_clock64();
 #endif
   const uint32_t n_list = a.counters->n_listed; // the tiles with records
-  const bool aborted = a.counters->abort != 0;
+  const bool aborted = a.counters->abort != 0 || a.counters->range_seq == a.scan_seq;
   const int32_t weight_epsilon = a.tau / 10;
   const uint32_t reset = pack_entry(a.tau, 0);
   const int lane = threadIdx.x & 63;
@@ -1787,7 +1786,8 @@ __global__ __launch_bounds__(256, WS_RESOLVE_WGS) void tile_resolve_kernel(Resol
     c->last_need = c->ub_total & ((1ull << 48) - 1ull);
     c->ub_total = 0;
     __hip_atomic_store(a.status + 10, c->big_inserted, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(a.status + 9, a.counters->abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); // (bit 0: pool exhausted, bit 1: key range)
+    const uint32_t verdict = (c->abort != 0 ? 1u : 0u) | (c->range_seq == a.scan_seq ? 2u : 0u);
+    __hip_atomic_store(a.status + 9, verdict, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); // (bit 0: pool exhausted, bit 1: key range)
     __hip_atomic_store(a.status + 8, a.scan_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }
   // The tiles with records: the scan's tile list (the marches appended every tile at its first reservation), dealt out

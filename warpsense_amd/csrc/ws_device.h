@@ -81,12 +81,12 @@ __device__ __forceinline__ int32_t div_trunc(int32_t x, const FastDiv &f) { retu
 // Vector3<int>::l2norm — include/warpsense/math/vector3.h:318-330: int(sqrtf(float(int sum))).
 // sqrtf, NOT __fsqrt_rn: without OCML_BASIC_ROUNDED_OPERATIONS the latter is the 1-ulp hardware approximation, and the
 // truncation turns one ulp into a different integer (sqrt(19838114) -> 4453 instead of 4454: one ray in 65 536).
-__device__ __forceinline__ int32_t l2norm_i(int32_t x, int32_t y, int32_t z)
+__device__ __forceinline__ int32_t sqrt_trunc_i(int32_t sq)
 {
-  int32_t sq = wadd(wadd(wmul(x, x), wmul(y, y)), wmul(z, z));
   if (sq < 0) return 0; // NaN -> 0 like the reference's cvt.rzi.s32.f32 (and v_cvt_i32_f32); explicit: fptosi of NaN is poison to the compiler
   return (int32_t)sqrtf((float)sq);
 }
+__device__ __forceinline__ int32_t l2norm_i(int32_t x, int32_t y, int32_t z) { return sqrt_trunc_i(wadd(wadd(wmul(x, x), wmul(y, y)), wmul(z, z))); }
 // Vector3<long>::l2norm — same header, T = long.  A wrapped (negative) sum is NaN after sqrtf; the reference's CUDA code
 // converts it with cvt.rzi.s64.f32 (= __float2ll_rz), which gives 0x8000000000000000 for NaN (the 32-bit conversion
 // above gives 0, like v_cvt_i32_f32).  gfx950 has no f32 -> i64 instruction and the compiler's expansion is not

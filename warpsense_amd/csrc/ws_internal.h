@@ -159,11 +159,15 @@ struct TsdfCounters // device-resident
   unsigned long long last_need; // record bound of the last scan
   uint32_t last_unlisted; // tiles without records (marks of the byte planes only) the resolve found by its scan
   uint32_t pad1;
-  // ---- a line of their own (round 6): the two words that EVERY workgroup of the free pass and of the resolve reads when it starts.
+  // ---- a line of their own (round 6): the words that EVERY workgroup of the free pass and of the resolve reads when it starts.
   // Next to the cursors above they shared a cache line with the launch's own atomics -- a look at `abort` at the start of the tail
   // march's workgroups took that kernel from 135 to 210 us.
-  alignas(128) uint32_t abort; // != 0: the scan in flight leaves no trace and is repeated -- bit 0: it ran out of sub-chunks, bit 1: a ray beyond the key range
-  uint32_t error;              // bits of this scatter (also OR-ed into the map's sticky host-visible error word)
+  // No launch clears a word that the same launch can set (the set-up pass used to clear both while its other
+  // workgroups OR-ed into them, and an OR that landed first was lost -- a ray beyond the key range then vanished without a repeat).
+  alignas(128) uint32_t abort; // != 0: the scan in flight leaves no trace and is repeated: it ran out of sub-chunks (set by the marches, cleared by the set-up pass)
+  uint32_t error;              // error bits since the map's buffers were last prepared (also OR-ed into the sticky host-visible error word, which is what is read)
+  uint32_t range_seq;          // scan_seq of the last scan whose set-up pass found a ray beyond its key range (never cleared: only equality with
+                               // the scan in flight counts, and every writer of one launch writes the same value); folded into abort by its readers
 };
 static_assert(offsetof(TsdfCounters, abort) % 128 == 0 && offsetof(TsdfCounters, abort) >= 128, "TsdfCounters: abort / error in a line of their own");
 
@@ -249,7 +253,7 @@ struct ws_map
   ws::TsdfCounters *counters = nullptr;
   ws::TsdfCounters *counters_host = nullptr; // pinned
   uint32_t *status_host = nullptr;           // pinned + mapped: [0] sticky error bits, [4..5] record bound of the scan in flight (u64), [6] its sequence number,
-                                             // [8] sequence number of the last scan whose marches have finished, [9] != 0: that scan was aborted (pool exhausted),
+                                             // [8] sequence number of the last scan whose marches have finished, [9] != 0: that scan was aborted (bit 0 pool exhausted, bit 1 key range),
                                              // [10] keys in the (tile, entry) hash
   uint32_t *status_dev = nullptr;            // device view of status_host
   uint32_t *box_stage = nullptr; // device staging for ws_map_extract_box / ws_map_insert_box
