@@ -145,6 +145,34 @@ int ws_map_get_params(const ws_map *map, int which, int32_t size[3], int32_t pos
 void *ws_map_device_data(ws_map *map, int which);
 int64_t ws_map_n_voxels(const ws_map *map);
 
+/* The surface cloud of a device map: publish_local_map (include/warpsense/visualization/map.h:14-121; called after every map
+ * update, src/cpu/fastsense.cpp:115, and for all four maps in test/pcd2tsdf.cpp:134-137) without the whole-map download.  Every
+ * voxel of an inclusive world-voxel box with weight > 0 && abs(value) < band (map.h:45; abs on the value as int32, so -32768 never
+ * qualifies) becomes one 16-byte RECORD: int32 x, y, z in world voxels, then uint32 raw, the packed entry.  Records come in
+ * ascending world (x, y, z), z fastest -- the order of the reference's collapse(3) schedule(static) loop -- so two calls on the
+ * same map give identical bytes.  With WS_SURFACE_MARKER the reference's marker is computed as well, 7 float32 per record in a
+ * second array of the same order: x y z r g b a, with x = (float)x * (float)map_resolution / 1000.f (two IEEE single roundings,
+ * map.h:51-53; geometry_msgs::Point widens these floats to double, which is lossless), r = value / (float)tau, g = 0 for
+ * value >= 0, else r = 0, g = -value / (float)tau, b = 0, a = 1 (map.h:55-64; tau is the map's, whatever `band` is).
+ *   lo / hi: the box, under the rule of ws_map_extract_box (outside the window: WS_ERR_INVALID); both NULL: the whole window,
+ *     [pos - size/2, pos - size/2 + size - 1] per axis.  For the reference's odd sizes that is its left..right loop; for an even size
+ *     it visits each ring cell once, where the reference's loop (size + 1 steps) would visit one cell twice -- an explicit box of
+ *     more voxels than the ring holds along an axis is refused for the same reason.
+ *   band <= 0: the map's tau.
+ * Synchronises (the count comes back).  The result buffers belong to the map, grow on demand and stay valid until the next
+ * ws_map_surface on it; a result of zero points is WS_OK with *n_out = 0 (the reference only logs).  Read-only on the maps: may run
+ * next to ws_register_cloud under the reference's shared lock; calls that use the result buffers are serialised inside the library. */
+#define WS_SURFACE_RECORDS 0u /* 16-byte records: x, y, z (world voxels), raw entry */
+#define WS_SURFACE_MARKER 1u  /* + the reference's float point and colour per record */
+int ws_map_surface(ws_map *map, int which, const int32_t lo[3], const int32_t hi[3], int32_t band, uint32_t flags, size_t *n_out);
+const void *ws_map_surface_records_dev(const ws_map *map, size_t *n); /* device memory, n x 16 bytes; NULL when n == 0 */
+const float *ws_map_surface_marker_dev(const ws_map *map, size_t *n); /* device memory, n x 7 floats; NULL unless the last call asked for it */
+/* copies at most capacity_points points and always reports the total in *n_out; either host pointer may be NULL */
+int ws_map_surface_download(ws_map *map, void *records_host, float *marker_host, size_t capacity_points, size_t *n_out);
+/* Measurement entry: with enable != 0 the calls above record events around their three launches; ms_out (may be NULL) receives the
+ * device time of the count pass, the scan and the emit pass of the last such call.  enable < 0 leaves the setting as it is. */
+int ws_debug_surface_timing(ws_map *map, int32_t enable, float ms_out[3]);
+
 /* ------------------------------------------------------------------ TSDF update ---- */
 /* TSDFCuda::update_tsdf(scan_points, scanner_pos, up) — update_tsdf.cu:143-166.
  * xyz_host: n x 3 int32 (rmagine::Pointi AoS); scanner_pos in voxel units, up scaled by 32768.

@@ -22,6 +22,7 @@
 #include <thread>
 
 #include "warpsense_hip/mapping.hpp"
+#include "warpsense_hip/visualization.hpp"
 #ifdef WARPSENSE_HIP_WITH_H5
 #include "warpsense_h5.h"
 #endif
@@ -513,6 +514,8 @@ public:
   }
   // the reference's route, kept for comparison: whole window to the host array of the local map
   void download() { gpu_.tsdf().avg_map().to_host(view_); }
+  // publish_local_map's cloud of the averaged map (visualization/map.h:14-121), selected on the device: no whole-map download
+  SurfaceCloud surface(bool marker = true) { return local_map_cloud(gpu_.tsdf(), WS_MAP_AVG, marker); }
 
 private:
   cuda::HotPathParams params_;
@@ -641,6 +644,7 @@ public:
   int n_updates() const { return n_updates_; }
   int n_shifts() const { return n_shifts_; }
   MappingNode &node() { return node_; }
+  SurfaceCloud surface(bool marker = true) { return node_.surface(marker); }
   LocalMap &local_map() { return local_map_; }
   GlobalMap &global_map() { return global_map_; }
 

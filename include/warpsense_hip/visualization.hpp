@@ -1,0 +1,91 @@
+// visualization.hpp — the data behind the reference's two map markers (include/warpsense/visualization/map.h), without ROS:
+//
+//   local_map_cloud      publish_local_map           map.h:14-121    the surface cloud of a DEVICE map, over ws_map_surface
+//   local_map_skeleton   publish_local_map_skeleton  map.h:175-227   the 24 end points of the window's line list (host only)
+//
+// The reference walks every voxel of a host map (after a whole-map download for the CUDA map, test/pcd2tsdf.cpp:134-137); here
+// the selection runs on the device and only the qualifying voxels travel.  What a caller with ROS does with the result is the
+// rest of map.h: marker.points / marker.colors from the 7 floats per point (x y z r g b a, a float widened to the double of
+// geometry_msgs::Point is the same number), header, scale = map_resolution * 0.6 / 1000.
+// There is deliberately no forwarding header under the reference's visualization/map.h name: its functions take a ros::Publisher.
+#pragma once
+
+#include <array>
+#include <vector>
+
+#include "warpsense_hip/compat.hpp"
+
+namespace warpsense
+{
+struct SurfaceRecord // one record of ws_map_surface
+{
+  int32_t x, y, z; // world voxels
+  uint32_t raw;    // the packed TSDFEntry
+};
+static_assert(sizeof(SurfaceRecord) == 16, "ws_map_surface writes 16-byte records");
+
+struct SurfaceCloud
+{
+  std::vector<SurfaceRecord> records; // ascending world (x, y, z), z fastest
+  std::vector<float> marker;          // 7 floats per record (x y z in metres, r g b a), empty unless asked for
+};
+
+// The voxels of `which` (WS_MAP_AVG / WS_MAP_NEW) with weight > 0 && abs(value) < band (map.h:45; band <= 0: tau) inside the
+// inclusive world-voxel box [lo, hi] (both nullptr: the whole window, map.h:19-26).
+inline SurfaceCloud local_map_cloud(cuda::TSDFCuda &tsdf, int which = WS_MAP_AVG, bool marker = true, const rmagine::Pointi *lo = nullptr,
+                                    const rmagine::Pointi *hi = nullptr, int band = 0)
+{
+  SurfaceCloud out;
+  size_t n = 0;
+  WS_CHECK(ws_map_surface(tsdf.handle(), which, lo ? &lo->x : nullptr, hi ? &hi->x : nullptr, band, marker ? WS_SURFACE_MARKER : WS_SURFACE_RECORDS, &n));
+  out.records.resize(n);
+  if (marker) out.marker.resize(n * 7);
+  size_t got = 0;
+  WS_CHECK(ws_map_surface_download(tsdf.handle(), n ? out.records.data() : nullptr, n && marker ? out.marker.data() : nullptr, n, &got));
+  return out;
+}
+
+// publish_local_map_skeleton (map.h:175-227): the line list of the window's edges, 12 lines = 24 end points in the reference's
+// order, in metres truncated to integers exactly as written there (`int *= float`: the corner in voxels goes to float, is
+// multiplied by (float)map_resolution / 1000.f and truncated toward zero; map.h:182-185).
+inline std::vector<std::array<double, 3>> local_map_skeleton(const int size[3], const int pos[3], int map_resolution)
+{
+  const float metres_per_voxel = (float)map_resolution / 1000.f;
+  int top_left[3], bottom_right[3], dims[3];
+  for (int k = 0; k < 3; ++k)
+  {
+    // the compound assignment of the reference spelled out: int -> float, one float product, truncation toward zero
+    bottom_right[k] = (int)((float)(pos[k] - size[k] / 2) * metres_per_voxel);
+    top_left[k] = (int)((float)(pos[k] + size[k] / 2) * metres_per_voxel);
+    dims[k] = top_left[k] - bottom_right[k];
+  }
+  std::vector<std::array<double, 3>> pts;
+  pts.reserve(24);
+  auto line = [&pts](const std::array<double, 3> &from, const std::array<double, 3> &to) {
+    pts.push_back(from);
+    pts.push_back(to);
+  };
+  auto rectangle = [&](int z_offset) { // draw_rectangle, map.h:150-173
+    std::array<double, 3> bbr = {(double)bottom_right[0], (double)bottom_right[1], (double)(bottom_right[2] + z_offset)};
+    std::array<double, 3> btr = bbr;
+    btr[0] += dims[0];
+    line(bbr, btr);
+    std::array<double, 3> btl = btr;
+    btl[1] += dims[1];
+    line(btr, btl);
+    std::array<double, 3> bbl = btl;
+    bbl[0] -= dims[0];
+    line(btl, bbl);
+    line(bbl, bbr);
+  };
+  auto ipt = [](int x, int y, int z) { return std::array<double, 3>{(double)x, (double)y, (double)z}; };
+  rectangle(0);       // map.h:192
+  rectangle(dims[2]); // map.h:193
+  line(ipt(top_left[0], top_left[1], top_left[2]), ipt(top_left[0], top_left[1], top_left[2] - dims[2]));                             // :195-199
+  line(ipt(bottom_right[0], bottom_right[1], bottom_right[2]), ipt(bottom_right[0], bottom_right[1], bottom_right[2] + dims[2]));       // :201-205
+  line(ipt(top_left[0] - dims[0], top_left[1], top_left[2]), ipt(top_left[0] - dims[0], top_left[1], top_left[2] - dims[2]));           // :207-216
+  line(ipt(bottom_right[0] + dims[0], bottom_right[1], bottom_right[2]), ipt(bottom_right[0] + dims[0], bottom_right[1], bottom_right[2] + dims[2])); // :218-227
+  return pts;
+}
+
+} // namespace warpsense

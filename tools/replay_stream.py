@@ -2,7 +2,7 @@
 sliding TSDF map @ 5 cm, one MI355X): sensor clouds in float metres -> device pre-processing -> TSDF update
 (when the sensor moved > 0.3 m) -> Point-to-TSDF registration -> pose -> map shift (device-side slabs).
 
-    python tools/replay_stream.py --map 1024 --scans 30 [--h5 /tmp/stream.h5]
+    python tools/replay_stream.py --map 1024 --scans 30 [--h5 /tmp/stream.h5] [--surface-ply DIR [--surface-every N]]
 
 Prints one JSON line: scans/s over the stream and the mean per-stage times (the reference's RuntimeEvaluator
 forms "preprocess", "tsdf", "registration", "total")."""
@@ -30,6 +30,9 @@ def main():
                     "(0 = back to back; the sensor of configs[2] delivers 10 Hz, and the slab filing of an asynchronous shift "
                     "has the time between two shifts of a paced stream to finish)")
     ap.add_argument("--async-shift", action="store_true", help="map shift off the scan path (TSDFMapping.shift_map_async)")
+    ap.add_argument("--surface-ply", default=None, metavar="DIR", help="write the marker cloud of the window (publish_local_map, selected on the "
+                    "device: TSDFMapping.surface_cloud) as binary little-endian PLY (xyz + rgb) into DIR")
+    ap.add_argument("--surface-every", type=int, default=10, metavar="N", help="... after every N-th scan")
     args = ap.parse_args()
     import warpsense_amd as W
     from warpsense_amd import synthetic as S
@@ -49,6 +52,9 @@ def main():
     W.pause()
     t1 = time.perf_counter()
     busy = 0.0
+    surface = {"files": 0, "points": 0, "seconds": 0.0}
+    if args.surface_ply:
+        os.makedirs(args.surface_ply, exist_ok=True)
     for k, c in enumerate(clouds):
         if args.hz > 0.0:
             wait = t1 + k / args.hz - time.perf_counter()
@@ -57,6 +63,12 @@ def main():
         tb = time.perf_counter()
         app.cloud_callback(c)
         busy += time.perf_counter() - tb
+        if args.surface_ply and (k + 1) % max(args.surface_every, 1) == 0:
+            ts = time.perf_counter()
+            _, marker = app.gpu_.surface_cloud(marker=True)
+            surface["points"] = W.write_surface_ply(os.path.join(args.surface_ply, f"surface_{k + 1:05d}.ply"), marker)
+            surface["files"] += 1
+            surface["seconds"] += time.perf_counter() - ts
     W.pause()
     t2 = time.perf_counter()
     stages = {}
@@ -76,7 +88,8 @@ def main():
                       "points_after_preprocess": float(np.mean([t["points"] for t in app.timings])),
                       "iterations_mean": float(np.mean([t["iterations"] for t in app.timings])),
                       "final_position_error_mm": float(np.linalg.norm(app.poses[-1][:3, 3] - true_last)),
-                      "terminate_write_back_s": t4 - t3, "h5": args.h5}))
+                      "terminate_write_back_s": t4 - t3, "h5": args.h5,
+                      "surface_ply": surface if args.surface_ply else None}))
 
 
 if __name__ == "__main__":

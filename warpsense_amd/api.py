@@ -75,6 +75,42 @@ def unpack_entry(raw):
     return (raw & 0xFFFF).astype(np.uint16).astype(np.int16), (raw >> 16).astype(np.uint16).astype(np.int16)
 
 
+# one record of ws_map_surface: world voxel coordinates and the packed entry (16 bytes)
+SURFACE_RECORD = np.dtype([("x", "<i4"), ("y", "<i4"), ("z", "<i4"), ("raw", "<u4")])
+
+
+class _DeviceArray:
+    """a library-owned device buffer as torch sees it (__cuda_array_interface__); `owner` keeps the handle alive"""
+
+    def __init__(self, ptr: int, shape, typestr: str, owner):
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2}
+        self._owner = owner
+
+
+def _device_tensor(ptr, shape, typestr: str, owner):
+    import torch
+    if not ptr or shape[0] == 0:
+        return torch.empty(shape, dtype=torch.int32 if typestr == "<i4" else torch.float32, device="cuda")
+    return torch.as_tensor(_DeviceArray(ptr, shape, typestr, owner), device="cuda")
+
+
+def write_surface_ply(path, marker):
+    """The marker cloud of DeviceMapMemWrapper.surface(marker=True) as a binary little-endian PLY: float x y z (metres) and
+    uchar red green blue (the reference's r / g / b in [0, 1) scaled by 255 and truncated)."""
+    marker = np.asarray(marker, dtype=np.float32).reshape(-1, 7)
+    out = np.empty(len(marker), dtype=np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")]))
+    out["x"], out["y"], out["z"] = marker[:, 0], marker[:, 1], marker[:, 2]
+    for name, col in (("red", 3), ("green", 4), ("blue", 5)):
+        out[name] = np.clip(marker[:, col] * np.float32(255.0), 0.0, 255.0).astype(np.uint8)
+    header = ("ply\nformat binary_little_endian 1.0\ncomment warpsense_amd surface cloud\n"
+              f"element vertex {len(out)}\nproperty float x\nproperty float y\nproperty float z\n"
+              "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n")
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(out.tobytes())
+    return len(out)
+
+
 class Context:
     """One per process and GPU: device + HIP stream (the reference uses the implicit CUDA context)."""
 
@@ -511,6 +547,37 @@ class DeviceMapMemWrapper:
         assert data.size == int(np.prod((hi - lo + 1).astype(np.int64)))
         check(t._L.ws_map_insert_box(t.handle, self._which, _ptr(lo), _ptr(hi), _ptr(data)), "ws_map_insert_box")
 
+    def surface(self, lo=None, hi=None, band=None, marker=False, device=False):
+        """The surface cloud of this map — publish_local_map (include/warpsense/visualization/map.h:14-121) on the device
+        (ws_map_surface): every voxel of the inclusive world-voxel box [lo, hi] (both None: the whole window) with
+        weight > 0 and abs(value) < band (None: tau), in ascending world (x, y, z), z fastest.
+
+        Returns the records as a numpy array of dtype SURFACE_RECORD (x, y, z in world voxels, raw entry); with `marker`
+        a pair (records, (n, 7) float32: x y z in metres, r g b a as the reference computes them).
+        device=True: torch tensors on the GPU instead — (n, 4) int32 and (n, 7) float32 — that ALIAS the library's buffers:
+        valid until the next surface() on this TSDFCuda, copy them (.clone()) to keep them."""
+        t = self._t
+        if (lo is None) != (hi is None):
+            raise WsError("surface: give both lo and hi, or neither")
+        n = C.c_size_t(0)
+        flags = _lib.WS_SURFACE_MARKER if marker else _lib.WS_SURFACE_RECORDS
+        check(t._L.ws_map_surface(t.handle, self._which, _ptr(_i3(lo)) if lo is not None else None, _ptr(_i3(hi)) if hi is not None else None,
+                                  int(band) if band is not None else 0, flags, C.byref(n)), "ws_map_surface")
+        n = int(n.value)
+        if device:
+            cnt = C.c_size_t(0)
+            rec = _device_tensor(t._L.ws_map_surface_records_dev(t.handle, C.byref(cnt)), (n, 4), "<i4", t)
+            if not marker:
+                return rec
+            return rec, _device_tensor(t._L.ws_map_surface_marker_dev(t.handle, C.byref(cnt)), (n, 7), "<f4", t)
+        rec = np.empty(n, dtype=SURFACE_RECORD)
+        mk = np.empty((n, 7), dtype=np.float32) if marker else None
+        got = C.c_size_t(0)
+        check(t._L.ws_map_surface_download(t.handle, _ptr(rec), _ptr(mk), n, C.byref(got)), "ws_map_surface_download")
+        if int(got.value) != n:
+            raise WsError("surface: another call replaced the result before it was downloaded")
+        return (rec, mk) if marker else rec
+
     def dev(self):
         return self._t.handle
 
@@ -813,6 +880,12 @@ class TSDFMapping:
 
     def tsdf(self) -> TSDFCuda:
         return self.tsdf_
+
+    def surface_cloud(self, **kw):
+        """publish_local_map's cloud of the averaged map (visualization/map.h:14-121; the reference publishes it after every
+        update, src/cpu/fastsense.cpp:115): DeviceMapMemWrapper.surface on avg_map(), under the mapping's lock like a reader."""
+        with self.mutex_:
+            return self.tsdf_.avg_map().surface(**kw)
 
     def shift_map(self, new_pos):
         """TSDFMapping::map_shift (tsdf_mapping.cpp:109-126) with the window moved ON THE DEVICE: per axis, the slab

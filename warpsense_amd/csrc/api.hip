@@ -287,9 +287,13 @@ static int map_free(ws_map *m)
   }
   map_free_records(m);
   void *ptrs[] = {m->data[0], m->data[1], m->vstate, m->az_hist, m->az_off, m->ray_bin, m->ray_order, m->fan_steps, m->rays, m->scan_dev, m->counters, m->tile_nsub,
-                  m->tile_ent, m->tile_dirty, m->tile_list, m->block_stats, m->box_stage};
+                  m->tile_ent, m->tile_dirty, m->tile_list, m->block_stats, m->box_stage,
+                  m->surf_col_cnt, m->surf_blk_tot, m->surf_blk_off, m->surf_total_dev, m->surf_rec, m->surf_marker};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
+  if (m->surf_total_host) (void)hipHostFree(m->surf_total_host);
+  for (hipEvent_t e : m->surf_ev)
+    if (e) (void)hipEventDestroy(e);
   if (m->counters_host) (void)hipHostFree(m->counters_host);
   if (m->status_host) (void)hipHostFree(m->status_host);
   if (m->shift_open) delete m->shift_open;
@@ -563,6 +567,158 @@ int ws_map_insert_box(ws_map *m, int which, const int32_t lo[3], const int32_t h
   if (rc != WS_OK) return rc;
   WS_HIP(hipStreamSynchronize(m->ctx->stream)); // the host buffer may be reused by the caller
   if (which == WS_MAP_NEW) m->new_is_default = false;
+  return WS_OK;
+}
+
+// ---- surface cloud: publish_local_map's extraction (visualization/map.h:14-121) on the device, map_surface.hip
+// a device buffer of at least `need` elements; the contents are not kept.  The caller has synchronised the stream.
+static int surf_grow(void **p, size_t *cap, size_t need, size_t elem_bytes)
+{
+  if (need <= *cap) return WS_OK;
+  if (*p) WS_HIP(hipFree(*p));
+  *p = nullptr;
+  *cap = 0;
+  need += need / 8; // a little room: a map that gains a few points per scan does not reallocate on every call
+  WS_HIP(hipMalloc(p, need * elem_bytes));
+  *cap = need;
+  return WS_OK;
+}
+
+int ws_map_surface(ws_map *m, int which, const int32_t lo[3], const int32_t hi[3], int32_t band, uint32_t flags, size_t *n_out)
+{
+  if (!m || (which != WS_MAP_AVG && which != WS_MAP_NEW) || (flags & ~WS_SURFACE_MARKER) || ((lo == nullptr) != (hi == nullptr)))
+    return invalid("ws_map_surface: bad argument");
+  WS_SETTLE(m);
+  std::lock_guard<std::mutex> lock(m->surf_mu);
+  const MapParams &p = m->par[which];
+  int32_t l[3], ext[3];
+  for (int k = 0; k < 3; ++k)
+  {
+    if (lo)
+    {
+      if (hi[k] < lo[k]) return invalid("ws_map_surface: hi < lo");
+      if (std::abs(lo[k] - p.pos[k]) > p.size[k] / 2 || std::abs(hi[k] - p.pos[k]) > p.size[k] / 2)
+        return invalid("ws_map_surface: box outside the local map window");
+      l[k] = lo[k];
+      ext[k] = hi[k] - lo[k] + 1;
+      // (an even size admits pos - size/2 .. pos + size/2: size + 1 voxels, the first and the last the same ring cell)
+      if (ext[k] > p.size[k]) return invalid("ws_map_surface: box wraps onto itself (more voxels than the ring holds along an axis)");
+    }
+    else
+    {
+      l[k] = p.pos[k] - p.size[k] / 2;
+      ext[k] = p.size[k];
+    }
+  }
+  if (band <= 0) band = m->tau;
+  const bool marker = (flags & WS_SURFACE_MARKER) != 0;
+  hipStream_t s = m->ctx->stream;
+  const int64_t n_cols = (int64_t)ext[0] * ext[1]; // < 2^31 (ws_map_create)
+  if (!m->surf_total_dev)
+  {
+    WS_HIP(hipMalloc((void **)&m->surf_total_dev, sizeof(unsigned long long)));
+    WS_HIP(hipHostMalloc((void **)&m->surf_total_host, sizeof(unsigned long long), hipHostMallocDefault));
+  }
+  if (m->surf_timing)
+    for (hipEvent_t &e : m->surf_ev)
+      if (!e) WS_HIP(hipEventCreate(&e));
+  if ((size_t)n_cols > m->surf_cols_cap)
+  {
+    WS_HIP(hipStreamSynchronize(s));
+    // all three anew, for this many columns (the whole window asks for the most there will ever be)
+    m->surf_cols_cap = 0;
+    size_t c0 = 0, c1 = 0, c2 = 0;
+    const size_t blocks = surface_blocks_for(n_cols);
+    int rc = surf_grow((void **)&m->surf_col_cnt, &c0, (size_t)n_cols, sizeof(uint32_t));
+    if (rc == WS_OK) rc = surf_grow((void **)&m->surf_blk_tot, &c1, blocks, sizeof(uint32_t));
+    if (rc == WS_OK) rc = surf_grow((void **)&m->surf_blk_off, &c2, blocks, sizeof(unsigned long long));
+    if (rc != WS_OK) return rc;
+    m->surf_cols_cap = (size_t)n_cols;
+  }
+  m->surf_n = 0;
+  m->surf_has_marker = false;
+  m->surf_ev_emit = false;
+  int rc = launch_surface_count(m, which, l, ext, band);
+  if (rc != WS_OK) return rc;
+  WS_HIP(hipStreamSynchronize(s)); // the one host read the call needs: the output is sized from the counted total
+  const size_t total = (size_t)*m->surf_total_host;
+  rc = surf_grow(&m->surf_rec, &m->surf_cap, total, 16);
+  if (rc == WS_OK && marker)
+  {
+    size_t cap7 = m->surf_marker_cap * 7;
+    rc = surf_grow((void **)&m->surf_marker, &cap7, total * 7, sizeof(float));
+    m->surf_marker_cap = cap7 / 7;
+  }
+  if (rc != WS_OK) return rc;
+  if (total)
+  {
+    const size_t cap_all = m->surf_cap;
+    if (marker && m->surf_marker_cap < m->surf_cap) m->surf_cap = m->surf_marker_cap; // (the kernel's bound holds for both buffers)
+    rc = launch_surface_emit(m, which, l, ext, band, marker);
+    m->surf_cap = cap_all;
+    if (rc != WS_OK) return rc;
+    m->surf_ev_emit = true;
+    WS_HIP(hipStreamSynchronize(s));
+  }
+  m->surf_n = total;
+  m->surf_has_marker = marker;
+  if (n_out) *n_out = total;
+  return map_take_error(m);
+}
+
+const void *ws_map_surface_records_dev(const ws_map *m, size_t *n)
+{
+  if (n) *n = m ? m->surf_n : 0;
+  return m && m->surf_n ? m->surf_rec : nullptr;
+}
+
+const float *ws_map_surface_marker_dev(const ws_map *m, size_t *n)
+{
+  const bool have = m && m->surf_has_marker && m->surf_n;
+  if (n) *n = have ? m->surf_n : 0;
+  return have ? m->surf_marker : nullptr;
+}
+
+int ws_map_surface_download(ws_map *m, void *records_host, float *marker_host, size_t capacity_points, size_t *n_out)
+{
+  if (!m || !n_out) return invalid("ws_map_surface_download: NULL argument");
+  std::lock_guard<std::mutex> lock(m->surf_mu);
+  *n_out = m->surf_n;
+  const size_t k = std::min(capacity_points, m->surf_n);
+  if (k == 0) return WS_OK;
+  if (marker_host && !m->surf_has_marker) return invalid("ws_map_surface_download: the last ws_map_surface did not ask for WS_SURFACE_MARKER");
+  if (records_host) WS_HIP(hipMemcpyAsync(records_host, m->surf_rec, k * 16, hipMemcpyDeviceToHost, m->ctx->stream));
+  if (marker_host) WS_HIP(hipMemcpyAsync(marker_host, m->surf_marker, k * 7 * sizeof(float), hipMemcpyDeviceToHost, m->ctx->stream));
+  WS_HIP(hipStreamSynchronize(m->ctx->stream));
+  return WS_OK;
+}
+
+int ws_debug_surface_timing(ws_map *m, int32_t enable, float ms_out[3])
+{
+  if (!m) return invalid("ws_debug_surface_timing: map is NULL");
+  std::lock_guard<std::mutex> lock(m->surf_mu);
+  if (ms_out)
+  {
+    ms_out[0] = ms_out[1] = ms_out[2] = 0.f;
+    if (m->surf_timing && m->surf_ev[0])
+    {
+      WS_HIP(hipStreamSynchronize(m->ctx->stream));
+      WS_HIP(hipEventElapsedTime(&ms_out[0], m->surf_ev[0], m->surf_ev[1]));
+      WS_HIP(hipEventElapsedTime(&ms_out[1], m->surf_ev[1], m->surf_ev[2]));
+      if (m->surf_ev_emit) WS_HIP(hipEventElapsedTime(&ms_out[2], m->surf_ev[3], m->surf_ev[4]));
+    }
+  }
+  if (enable >= 0)
+  {
+    if (!enable || !m->surf_timing)
+      for (hipEvent_t &e : m->surf_ev)
+      {
+        // (events of an earlier enabled period are not read again: a fresh set is recorded by the next call)
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+      }
+    m->surf_timing = enable != 0;
+  }
   return WS_OK;
 }
 

@@ -1,0 +1,250 @@
+// map_surface.hip — the surface cloud of a device map (gfx950): what publish_local_map
+// (include/warpsense/visualization/map.h:14-121) collects on the host from a downloaded map, as an ORDERED stream compaction on the
+// device.  A voxel qualifies if weight > 0 && abs(value) < band (map.h:45, band = tau there); the output is in ascending world
+// (x, y, z), z fastest -- the order in which the reference's collapse(3) schedule(static) loop concatenates its per-thread results
+// -- so it is the same bytes on every run.
+//
+//   surface_kernel<COUNT>    qualifying voxels per (x, y) column of the box, and per workgroup (SURF_COLS consecutive columns)
+//   surface_scan_kernel      exclusive scan of the workgroup totals (one workgroup; the last element is the total)
+//   surface_kernel<EMIT..>   the predicate again; a record goes to (workgroup base + columns before + rank inside the column)
+//
+// Plain launches on the context's stream, nothing waits for another workgroup, no atomics.
+// Memory is z fastest and rotated by `offset` on every axis (get_index, ws_device.h), so the world-order z run of one column is at
+// most two contiguous storage runs: [zs0, size_z) then [0, ...).  Each run is read as ALIGNED 16-byte loads (four voxels per lane,
+// 1 KiB per wave instruction) whose first and last group are masked: size_z is odd for the reference's maps, so no column starts on
+// a 16-byte boundary.  The maps carry 16 bytes of slack behind the last voxel (ws_map_create), which the last group may touch.
+#include "ws_device.h"
+
+namespace ws
+{
+typedef uint32_t su32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int SURF_COLS = 16; // columns per workgroup: four per wave, one after the other
+constexpr int SURF_WAVES = 4;
+constexpr int SURF_COUNT = 0, SURF_EMIT = 1, SURF_EMIT_MARKER = 2;
+
+struct SurfArgs
+{
+  const uint32_t *data;
+  MapParams mp;
+  int32_t lo[3];
+  int32_t ey, ez;
+  uint32_t n_cols;
+  int32_t band, tau, res;
+  uint32_t *col_cnt;                  // [n_cols]
+  uint32_t *blk_tot;                  // [workgroups]
+  const unsigned long long *blk_off;  // [workgroups] exclusive scan of blk_tot
+  su32x4 *rec;                        // x, y, z, raw
+  float *marker;                      // 7 floats per record: x y z (metres) r g b a
+  unsigned long long cap;             // records the output buffers hold
+};
+
+__device__ __forceinline__ bool surf_pred(uint32_t raw, int32_t band) { return entry_weight(raw) > 0 && iabs32(entry_value(raw)) < band; }
+__device__ __forceinline__ uint32_t lanes_below(unsigned long long mask)
+{
+  return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void surface_kernel(SurfArgs a)
+{
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint32_t col0 = blockIdx.x * (uint32_t)SURF_COLS;
+  uint32_t before = 0; // EMIT: records of the workgroup's columns before column `lane`
+  unsigned long long base = 0;
+  if (MODE != SURF_COUNT)
+  {
+    const uint32_t c = (lane < SURF_COLS && col0 + lane < a.n_cols) ? a.col_cnt[col0 + lane] : 0u;
+    uint32_t inc = c;
+#pragma unroll
+    for (int d = 1; d < SURF_COLS; d <<= 1)
+    {
+      const uint32_t t = __shfl_up(inc, d, 64);
+      if (lane >= d) inc += t;
+    }
+    before = inc - c;
+    base = a.blk_off[blockIdx.x];
+  }
+  const int32_t sz = a.mp.size[2];
+  const int32_t zs0 = ring(a.lo[2] - a.mp.pos[2] + a.mp.offset[2] + sz, sz); // storage z of the box's first world z
+  const int32_t len_a = min(a.ez, sz - zs0);                                  // voxels up to the ring seam; the rest starts at storage z 0
+  const float fres = (float)a.res, ftau = (float)a.tau;
+  uint32_t wave_total = 0;
+  for (int k = 0; k < SURF_COLS / SURF_WAVES; ++k)
+  {
+    const int ci = wave * (SURF_COLS / SURF_WAVES) + k;
+    const uint32_t col = col0 + (uint32_t)ci;
+    if (col >= a.n_cols) break; // (the same for the whole wave)
+    const int32_t xr = (int32_t)(col / (uint32_t)a.ey), yr = (int32_t)(col - (uint32_t)xr * (uint32_t)a.ey);
+    const int32_t x = a.lo[0] + xr, y = a.lo[1] + yr;
+    const int32_t xi = ring(x - a.mp.pos[0] + a.mp.offset[0] + a.mp.size[0], a.mp.size[0]);
+    const int32_t yi = ring(y - a.mp.pos[1] + a.mp.offset[1] + a.mp.size[1], a.mp.size[1]);
+    const int64_t cbase = (int64_t)(xi * a.mp.size[1] + yi) * (int64_t)sz; // size[0] * size[1] < 2^31 (ws_map_create)
+    unsigned long long out = base + __shfl(before, ci, 64);
+    // publish_local_map's point (map.h:51-53): (float)x * (float)map_resolution / 1000.f -- a rounded product, then a correctly
+    // rounded division (no contraction, no reciprocal: -ffp-contract=off and hipcc's default IEEE division)
+    const float px = (float)x * fres / 1000.f, py = (float)y * fres / 1000.f;
+    uint32_t cnt = 0;
+#pragma unroll
+    for (int run = 0; run < 2; ++run)
+    {
+      const int32_t len = run ? a.ez - len_a : len_a;
+      if (len <= 0) continue;
+      const int32_t zw0 = a.lo[2] + (run ? len_a : 0); // world z of the run's first voxel
+      const int64_t first = cbase + (run ? 0 : zs0), last = first + len;
+      for (int64_t g0 = first & ~(int64_t)3; g0 < last; g0 += 256)
+      {
+        const int64_t g = g0 + 4 * lane;
+        su32x4 v = {0u, 0u, 0u, 0u};
+        if (g < last) v = __builtin_nontemporal_load(reinterpret_cast<const su32x4 *>(a.data + g));
+        const uint32_t raw[4] = {v.x, v.y, v.z, v.w};
+        bool q[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) q[j] = g + j >= first && g + j < last && surf_pred(raw[j], a.band);
+        if (MODE == SURF_COUNT)
+        {
+          cnt += (uint32_t)q[0] + (uint32_t)q[1] + (uint32_t)q[2] + (uint32_t)q[3];
+        }
+        else
+        {
+          // world order = lane major, then the lane's four voxels: records of lower lanes first
+          const unsigned long long b0 = __ballot(q[0]), b1 = __ballot(q[1]), b2 = __ballot(q[2]), b3 = __ballot(q[3]);
+          unsigned long long o = out + (lanes_below(b0) + lanes_below(b1) + lanes_below(b2) + lanes_below(b3));
+          const int32_t z0 = zw0 + (int32_t)(g - first);
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+          {
+            if (!q[j]) continue;
+            if (o < a.cap) // (the count pass sized the buffers; a map that changed in between must not write beyond them)
+            {
+              const int32_t z = z0 + j;
+              const su32x4 r = {(uint32_t)x, (uint32_t)y, (uint32_t)z, raw[j]};
+              a.rec[o] = r;
+              if (MODE == SURF_EMIT_MARKER)
+              {
+                const int32_t val = entry_value(raw[j]);
+                float *m = a.marker + o * 7ull;
+                m[0] = px;
+                m[1] = py;
+                m[2] = (float)z * fres / 1000.f;
+                // map.h:55-64: r = value / (float)tau, g = 0 for value >= 0, else r = 0, g = -value / (float)tau; b = 0, a = 1
+                const float c = (float)(val >= 0 ? val : -val) / ftau;
+                m[3] = val >= 0 ? c : 0.f;
+                m[4] = val >= 0 ? 0.f : c;
+                m[5] = 0.f;
+                m[6] = 1.f;
+              }
+            }
+            ++o;
+          }
+          out += (unsigned long long)(__popcll(b0) + __popcll(b1) + __popcll(b2) + __popcll(b3));
+        }
+      }
+    }
+    if (MODE == SURF_COUNT)
+    {
+#pragma unroll
+      for (int d = 32; d > 0; d >>= 1) cnt += __shfl_xor(cnt, d, 64);
+      if (lane == 0) a.col_cnt[col] = cnt;
+      wave_total += cnt;
+    }
+  }
+  if (MODE == SURF_COUNT)
+  {
+    __shared__ uint32_t wtot[SURF_WAVES];
+    if (lane == 0) wtot[wave] = wave_total;
+    __syncthreads();
+    if (threadIdx.x == 0) a.blk_tot[blockIdx.x] = wtot[0] + wtot[1] + wtot[2] + wtot[3];
+  }
+}
+
+// exclusive scan of the workgroup totals: 16 K words for a 513^3 window, 256 K for 2049^3 -- one workgroup, every thread a
+// contiguous piece
+__global__ __launch_bounds__(1024) void surface_scan_kernel(const uint32_t *tot, unsigned long long *off, uint32_t n, unsigned long long *total)
+{
+  __shared__ unsigned long long part[1024];
+  const uint32_t t = threadIdx.x, seg = (n + 1023u) / 1024u;
+  const uint32_t b = min(n, t * seg), e = min(n, b + seg);
+  unsigned long long s = 0;
+  for (uint32_t i = b; i < e; ++i) s += tot[i];
+  part[t] = s;
+  __syncthreads();
+  for (uint32_t d = 1; d < 1024; d <<= 1)
+  {
+    const unsigned long long v = t >= d ? part[t - d] : 0ull;
+    __syncthreads();
+    part[t] += v;
+    __syncthreads();
+  }
+  unsigned long long run = part[t] - s;
+  for (uint32_t i = b; i < e; ++i)
+  {
+    off[i] = run;
+    run += tot[i];
+  }
+  if (t == 1023) *total = part[1023];
+}
+
+static uint32_t surf_blocks(uint32_t n_cols) { return (n_cols + SURF_COLS - 1) / SURF_COLS; }
+
+static void surf_args(SurfArgs &a, const ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], int32_t band)
+{
+  a.data = m->data[which];
+  a.mp = m->par[which];
+  for (int k = 0; k < 3; ++k) a.lo[k] = lo[k];
+  a.ey = ext[1];
+  a.ez = ext[2];
+  a.n_cols = (uint32_t)((int64_t)ext[0] * ext[1]);
+  a.band = band;
+  a.tau = m->tau;
+  a.res = m->res;
+  a.col_cnt = m->surf_col_cnt;
+  a.blk_tot = m->surf_blk_tot;
+  a.blk_off = m->surf_blk_off;
+  a.rec = reinterpret_cast<su32x4 *>(m->surf_rec);
+  a.marker = m->surf_marker;
+  a.cap = 0;
+}
+
+static void surf_mark(ws_map *m, int i)
+{
+  if (m->surf_timing) (void)hipEventRecord(m->surf_ev[i], m->ctx->stream);
+}
+
+size_t surface_blocks_for(int64_t n_cols) { return (size_t)surf_blocks((uint32_t)n_cols); }
+
+// passes 1 and 2; the total arrives in m->surf_total_host (pinned) once the stream has been synchronised
+int launch_surface_count(ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], int32_t band)
+{
+  SurfArgs a;
+  surf_args(a, m, which, lo, ext, band);
+  const uint32_t blocks = surf_blocks(a.n_cols);
+  hipStream_t s = m->ctx->stream;
+  surf_mark(m, 0);
+  hipLaunchKernelGGL((surface_kernel<SURF_COUNT>), dim3(blocks), dim3(256), 0, s, a);
+  surf_mark(m, 1);
+  hipLaunchKernelGGL(surface_scan_kernel, dim3(1), dim3(1024), 0, s, (const uint32_t *)m->surf_blk_tot, m->surf_blk_off, blocks, m->surf_total_dev);
+  surf_mark(m, 2);
+  WS_HIP(hipGetLastError());
+  WS_HIP(hipMemcpyAsync(m->surf_total_host, m->surf_total_dev, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  return WS_OK;
+}
+
+// pass 3
+int launch_surface_emit(ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], int32_t band, bool marker)
+{
+  SurfArgs a;
+  surf_args(a, m, which, lo, ext, band);
+  a.cap = m->surf_cap;
+  const uint32_t blocks = surf_blocks(a.n_cols);
+  surf_mark(m, 3);
+  if (marker)
+    hipLaunchKernelGGL((surface_kernel<SURF_EMIT_MARKER>), dim3(blocks), dim3(256), 0, m->ctx->stream, a);
+  else
+    hipLaunchKernelGGL((surface_kernel<SURF_EMIT>), dim3(blocks), dim3(256), 0, m->ctx->stream, a);
+  surf_mark(m, 4);
+  WS_HIP(hipGetLastError());
+  return WS_OK;
+}
+
+} // namespace ws

@@ -259,6 +259,23 @@ struct ws_map
   uint32_t *box_stage = nullptr; // device staging for ws_map_extract_box / ws_map_insert_box
   size_t box_stage_cap = 0;
   uint32_t last_error_bits = 0;  // device error bits already taken from status_host, not yet shown by ws_tsdf_stats
+  // ws_map_surface (map_surface.hip): the surface cloud of the last call and the scratch of its passes; all of it allocated on first
+  // use and grown on demand.  surf_mu serialises the calls that use these buffers (the reference's readers hold a SHARED lock).
+  std::mutex surf_mu;
+  uint32_t *surf_col_cnt = nullptr;            // [surf_cols_cap] qualifying voxels per (x, y) column of the box
+  uint32_t *surf_blk_tot = nullptr;            // [workgroups] the same per workgroup of the count pass
+  unsigned long long *surf_blk_off = nullptr;  // [workgroups] exclusive scan
+  size_t surf_cols_cap = 0;
+  unsigned long long *surf_total_dev = nullptr;  // the scan's last element
+  unsigned long long *surf_total_host = nullptr; // pinned
+  void *surf_rec = nullptr;                    // [surf_cap] 16-byte records
+  float *surf_marker = nullptr;                // [surf_marker_cap][7]
+  size_t surf_cap = 0, surf_marker_cap = 0;
+  size_t surf_n = 0;                           // records of the last call
+  bool surf_has_marker = false;                // the last call also wrote surf_marker
+  bool surf_timing = false;                    // ws_debug_surface_timing: events around the three launches
+  hipEvent_t surf_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  bool surf_ev_emit = false;                   // the last call launched the emit pass (events 3, 4 are recorded)
   // The scan whose verdict (did its records fit the pool?) has not been looked at yet: ws_tsdf_update* return after the
   // launches, like the reference's update_tsdf (update_tsdf.cu:165); the next call that takes this map settles it first
   // (settle_tsdf: the verdict is in host-mapped memory ~0.35 ms after the launches) and repeats the scan if it was aborted.
@@ -399,6 +416,10 @@ uint64_t subs_for_scan(const ws_map *m, uint64_t need_records, uint64_t n_points
 int launch_tsdf_integrate(ws_map *m);
 int launch_tsdf_stats(ws_map *m); // fills the last_* statistics of TsdfCounters from the per-workgroup slots
 int launch_box_copy(ws_map *m, const ws::MapParams &par, int which, const int32_t lo[3], const int32_t ext[3], uint32_t *box_dev, bool pack, hipStream_t stream);
+// map_surface.hip: count + scan (the total arrives in ws_map::surf_total_host after a stream synchronise), then the emit pass
+size_t surface_blocks_for(int64_t n_cols);
+int launch_surface_count(ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], int32_t band);
+int launch_surface_emit(ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], int32_t band, bool marker);
 int fill_u32(ws_context *ctx, uint32_t *dst, uint32_t value, int64_t n);
 int launch_box_fill(ws_map *m, const ws::MapParams &par, int which, const int32_t lo[3], const int32_t ext[3], uint32_t value, hipStream_t stream);
 int check_all_equal_host(const uint32_t *data, int64_t n, uint32_t value);
