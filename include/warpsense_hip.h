@@ -173,6 +173,43 @@ int ws_map_surface_download(ws_map *map, void *records_host, float *marker_host,
  * device time of the count pass, the scan and the emit pass of the last such call.  enable < 0 leaves the setting as it is. */
 int ws_debug_surface_timing(ws_map *map, int32_t enable, float ms_out[3]);
 
+/* A triangle mesh of a device map by naive surface nets: one vertex per cell the surface passes through, one quad (two triangles)
+ * per lattice edge that crosses the surface.  No table, integers only: the result is exact and the same bytes on every run.
+ *   value, weight: the entry's two int16.  A voxel is VALID iff weight > 0; with WS_MESH_ANY_WEIGHT iff weight != 0 (the rule the
+ *     registration uses: the fan of the update writes negative weights).  A voxel is INSIDE iff value < 0.
+ *   box: inclusive world voxels [lo, hi] under the rules of ws_map_surface (both NULL: the whole window, each ring cell once;
+ *     outside the window, hi < lo or more voxels than the ring holds along an axis: WS_ERR_INVALID).
+ *   cell c = (x, y, z): the cube with corner voxels c + {0,1}^3, for lo <= c <= hi - 1 per axis (a box one voxel thick along an
+ *     axis has no cells: WS_OK, zero vertices, zero faces).  A cell is valid iff its 8 corners are valid, ACTIVE iff valid and its
+ *     corners are neither all inside nor all outside.
+ *   crossing of the lattice edge from voxel a to b = a + e_k (owner a, axis k): exists iff inside(a) != inside(b).  Its offset
+ *     from a along k in mm: o = (2 |va| res + m) / (2 m), m = |va| + |vb| (int64, floor; |-32768| is 32768); 0 <= o <= res.
+ *   vertex of an active cell: over the cell's n crossing edges (n >= 3 of its 12) the sum of the crossings' local positions --
+ *     per axis 0 or res across the edge, o along it -- divided per axis by n (floor).  World position in mm per axis:
+ *     c res + res / 2 + local (res / 2 truncated: the voxel centre of the update).  Record, 16 bytes: int32 x_mm, y_mm, z_mm;
+ *     uint32 weight = the smallest corner weight of the cell (of |weight| under WS_MESH_ANY_WEIGHT).
+ *     Order: ascending cell (x, y, z), z fastest; a vertex's index is its position in that order.
+ *   faces: for every crossing edge (owner a, axis k; i = (k + 1) % 3, j = (k + 2) % 3) whose four cells q0 = a - e_i - e_j,
+ *     q1 = a - e_j, q2 = a, q3 = a - e_i all lie in the box's cell range and are all valid, two triangles: (q0, q1, q2), (q0, q2, q3)
+ *     if inside(a), else (q0, q2, q1), (q0, q3, q2) -- normals point to the outside, towards the sensor.  Record: 3 uint32 vertex
+ *     indices, 12 bytes.  Order: ascending owner voxel (x, y, z), z fastest, then axis 0, 1, 2; the two triangles of a quad adjacent.
+ *   A vertex at the rim of the observed region (or of the box) may be referenced by no face; it stays.  Faces of a box refer to
+ *     vertices of that box only: the mesh of a box is not a subset of the mesh of the window at its rim.
+ * WS_ERR_RANGE: (|coordinate| + 1) res of a box corner does not fit int32, or more than 2^32 - 1 vertices.
+ * Synchronises (the two counts come back).  The result buffers belong to the map, grow on demand and stay valid until the next
+ * ws_map_mesh on it; they are apart from those of ws_map_surface, neither call invalidates the other's result.  Read-only on the
+ * maps: may run next to ws_register_cloud under the reference's shared lock; calls that use the result buffers are serialised
+ * inside the library.  Nothing is allocated before the first call. */
+#define WS_MESH_DEFAULT 0u
+#define WS_MESH_ANY_WEIGHT 1u
+int ws_map_mesh(ws_map *map, int which, const int32_t lo[3], const int32_t hi[3], uint32_t flags, size_t *n_vertices, size_t *n_faces);
+const void *ws_map_mesh_vertices_dev(const ws_map *map, size_t *n);  /* device memory, n x 16 bytes; NULL when n == 0 */
+const uint32_t *ws_map_mesh_faces_dev(const ws_map *map, size_t *n); /* device memory, n x 3 uint32; NULL when n == 0 */
+/* copies at most cap_vertices vertices and cap_faces faces (prefixes) and always reports the totals; either host pointer may be NULL */
+int ws_map_mesh_download(ws_map *map, void *vertices_host, uint32_t *faces_host, size_t cap_vertices, size_t cap_faces, size_t *n_vertices, size_t *n_faces);
+/* Measurement entry, as ws_debug_surface_timing: ms_out receives the device time of the count passes, the scan and the emit passes */
+int ws_debug_mesh_timing(ws_map *map, int32_t enable, float ms_out[3]);
+
 /* ------------------------------------------------------------------ TSDF update ---- */
 /* TSDFCuda::update_tsdf(scan_points, scanner_pos, up) — update_tsdf.cu:143-166.
  * xyz_host: n x 3 int32 (rmagine::Pointi AoS); scanner_pos in voxel units, up scaled by 32768.

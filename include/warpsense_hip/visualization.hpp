@@ -1,6 +1,7 @@
 // visualization.hpp — the data behind the reference's two map markers (include/warpsense/visualization/map.h), without ROS:
 //
 //   local_map_cloud      publish_local_map           map.h:14-121    the surface cloud of a DEVICE map, over ws_map_surface
+//   local_map_mesh       (no counterpart: the reference sends the user to an offline mesher)   a triangle mesh, over ws_map_mesh
 //   local_map_skeleton   publish_local_map_skeleton  map.h:175-227   the 24 end points of the window's line list (host only)
 //
 // The reference walks every voxel of a host map (after a whole-map download for the CUDA map, test/pcd2tsdf.cpp:134-137); here
@@ -42,6 +43,38 @@ inline SurfaceCloud local_map_cloud(cuda::TSDFCuda &tsdf, int which = WS_MAP_AVG
   if (marker) out.marker.resize(n * 7);
   size_t got = 0;
   WS_CHECK(ws_map_surface_download(tsdf.handle(), n ? out.records.data() : nullptr, n && marker ? out.marker.data() : nullptr, n, &got));
+  return out;
+}
+
+struct MeshVertex // one vertex of ws_map_mesh
+{
+  int32_t x_mm, y_mm, z_mm; // world position in millimetres
+  uint32_t weight;          // the smallest corner weight of the vertex's cell
+};
+struct MeshFace
+{
+  uint32_t v[3]; // vertex indices, normal towards the outside
+};
+static_assert(sizeof(MeshVertex) == 16 && sizeof(MeshFace) == 12, "ws_map_mesh writes 16-byte vertices and 12-byte faces");
+
+struct SurfaceMesh
+{
+  std::vector<MeshVertex> vertices; // ascending cell (x, y, z), z fastest
+  std::vector<MeshFace> faces;      // ascending owner voxel, then axis; the two triangles of a quad adjacent
+};
+
+// A triangle mesh of `which` by naive surface nets (the rules: warpsense_hip.h at ws_map_mesh) inside the inclusive world-voxel box
+// [lo, hi] (both nullptr: the whole window).  any_weight: voxels with a negative weight count as observed (WS_MESH_ANY_WEIGHT).
+inline SurfaceMesh local_map_mesh(cuda::TSDFCuda &tsdf, int which = WS_MAP_AVG, bool any_weight = false, const rmagine::Pointi *lo = nullptr,
+                                  const rmagine::Pointi *hi = nullptr)
+{
+  SurfaceMesh out;
+  size_t nv = 0, nf = 0;
+  WS_CHECK(ws_map_mesh(tsdf.handle(), which, lo ? &lo->x : nullptr, hi ? &hi->x : nullptr, any_weight ? WS_MESH_ANY_WEIGHT : WS_MESH_DEFAULT, &nv, &nf));
+  out.vertices.resize(nv);
+  out.faces.resize(nf);
+  size_t gv = 0, gf = 0;
+  WS_CHECK(ws_map_mesh_download(tsdf.handle(), nv ? out.vertices.data() : nullptr, nf ? &out.faces.data()->v[0] : nullptr, nv, nf, &gv, &gf));
   return out;
 }
 

@@ -2,7 +2,7 @@
 sliding TSDF map @ 5 cm, one MI355X): sensor clouds in float metres -> device pre-processing -> TSDF update
 (when the sensor moved > 0.3 m) -> Point-to-TSDF registration -> pose -> map shift (device-side slabs).
 
-    python tools/replay_stream.py --map 1024 --scans 30 [--h5 /tmp/stream.h5] [--surface-ply DIR [--surface-every N]]
+    python tools/replay_stream.py --map 1024 --scans 30 [--h5 /tmp/stream.h5] [--surface-ply DIR [--surface-every N]] [--mesh-ply DIR]
 
 Prints one JSON line: scans/s over the stream and the mean per-stage times (the reference's RuntimeEvaluator
 forms "preprocess", "tsdf", "registration", "total")."""
@@ -32,6 +32,8 @@ def main():
     ap.add_argument("--async-shift", action="store_true", help="map shift off the scan path (TSDFMapping.shift_map_async)")
     ap.add_argument("--surface-ply", default=None, metavar="DIR", help="write the marker cloud of the window (publish_local_map, selected on the "
                     "device: TSDFMapping.surface_cloud) as binary little-endian PLY (xyz + rgb) into DIR")
+    ap.add_argument("--mesh-ply", default=None, metavar="DIR", help="write a triangle mesh of the window (surface nets on the device: "
+                    "TSDFMapping.surface_mesh) as binary little-endian PLY into DIR, after every N-th scan like --surface-ply")
     ap.add_argument("--surface-every", type=int, default=10, metavar="N", help="... after every N-th scan")
     args = ap.parse_args()
     import warpsense_amd as W
@@ -53,8 +55,11 @@ def main():
     t1 = time.perf_counter()
     busy = 0.0
     surface = {"files": 0, "points": 0, "seconds": 0.0}
+    mesh = {"files": 0, "vertices": 0, "faces": 0, "seconds": 0.0}
     if args.surface_ply:
         os.makedirs(args.surface_ply, exist_ok=True)
+    if args.mesh_ply:
+        os.makedirs(args.mesh_ply, exist_ok=True)
     for k, c in enumerate(clouds):
         if args.hz > 0.0:
             wait = t1 + k / args.hz - time.perf_counter()
@@ -69,6 +74,11 @@ def main():
             surface["points"] = W.write_surface_ply(os.path.join(args.surface_ply, f"surface_{k + 1:05d}.ply"), marker)
             surface["files"] += 1
             surface["seconds"] += time.perf_counter() - ts
+        if args.mesh_ply and (k + 1) % max(args.surface_every, 1) == 0:
+            ts = time.perf_counter()
+            mesh["vertices"], mesh["faces"] = W.write_mesh_ply(os.path.join(args.mesh_ply, f"mesh_{k + 1:05d}.ply"), *app.gpu_.surface_mesh())
+            mesh["files"] += 1
+            mesh["seconds"] += time.perf_counter() - ts
     W.pause()
     t2 = time.perf_counter()
     stages = {}
@@ -89,7 +99,8 @@ def main():
                       "iterations_mean": float(np.mean([t["iterations"] for t in app.timings])),
                       "final_position_error_mm": float(np.linalg.norm(app.poses[-1][:3, 3] - true_last)),
                       "terminate_write_back_s": t4 - t3, "h5": args.h5,
-                      "surface_ply": surface if args.surface_ply else None}))
+                      "surface_ply": surface if args.surface_ply else None,
+                      "mesh_ply": mesh if args.mesh_ply else None}))
 
 
 if __name__ == "__main__":

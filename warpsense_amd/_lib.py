@@ -30,8 +30,10 @@ EXPORTS = [
     "ws_reg_peer_disconnect", "ws_reg_peer_reset", "ws_register_cloud_peers", "ws_reg_set_loop", "ws_debug_solve6", "ws_debug_reg_stall", "ws_debug_reg_server", "ws_debug_reg_mail_selftest", "ws_debug_reg_sums", "ws_debug_block_stats", "ws_scan_create", "ws_scan_destroy", "ws_scan_preprocess",
     "ws_scan_preprocess_dev", "ws_scan_points_dev", "ws_scan_download", "ws_prof_enable", "ws_prof_read", "ws_prof_reset",
     "ws_map_surface", "ws_map_surface_records_dev", "ws_map_surface_marker_dev", "ws_map_surface_download", "ws_debug_surface_timing",
+    "ws_map_mesh", "ws_map_mesh_vertices_dev", "ws_map_mesh_faces_dev", "ws_map_mesh_download", "ws_debug_mesh_timing",
 ]
 WS_SURFACE_RECORDS, WS_SURFACE_MARKER = 0, 1
+WS_MESH_DEFAULT, WS_MESH_ANY_WEIGHT = 0, 1
 
 
 class WsError(RuntimeError):
@@ -129,6 +131,13 @@ def load() -> C.CDLL:
     L.ws_map_surface_marker_dev.restype = vp
     L.ws_map_surface_download.argtypes = [vp, vp, vp, sz, P(sz)]
     L.ws_debug_surface_timing.argtypes = [vp, i32, vp]
+    L.ws_map_mesh.argtypes = [vp, C.c_int, vp, vp, u32, P(sz), P(sz)]
+    L.ws_map_mesh_vertices_dev.argtypes = [vp, P(sz)]
+    L.ws_map_mesh_vertices_dev.restype = vp
+    L.ws_map_mesh_faces_dev.argtypes = [vp, P(sz)]
+    L.ws_map_mesh_faces_dev.restype = vp
+    L.ws_map_mesh_download.argtypes = [vp, vp, vp, sz, sz, P(sz), P(sz)]
+    L.ws_debug_mesh_timing.argtypes = [vp, i32, vp]
     L.ws_shift_begin.argtypes = [vp, vp, u32, P(vp)]
     L.ws_shift_count.argtypes = [vp]
     L.ws_shift_reserve.argtypes = [vp, C.c_uint64]

@@ -79,6 +79,10 @@ def unpack_entry(raw):
 SURFACE_RECORD = np.dtype([("x", "<i4"), ("y", "<i4"), ("z", "<i4"), ("raw", "<u4")])
 
 
+# one vertex of ws_map_mesh: world position in millimetres and the smallest corner weight of its cell (16 bytes)
+VERT = np.dtype([("x_mm", "<i4"), ("y_mm", "<i4"), ("z_mm", "<i4"), ("weight", "<u4")])
+
+
 class _DeviceArray:
     """a library-owned device buffer as torch sees it (__cuda_array_interface__); `owner` keeps the handle alive"""
 
@@ -109,6 +113,27 @@ def write_surface_ply(path, marker):
         f.write(header.encode("ascii"))
         f.write(out.tobytes())
     return len(out)
+
+
+def write_mesh_ply(path, vertices, faces):
+    """The mesh of DeviceMapMemWrapper.mesh() as a binary little-endian PLY: float x y z in metres (mm / 1000.f in single
+    precision), faces as a uchar count (3) and int vertex indices.  Returns (vertices, faces) written."""
+    vertices = np.asarray(vertices, dtype=VERT).reshape(-1)
+    faces = np.asarray(faces, dtype=np.uint32).reshape(-1, 3)
+    v = np.empty(len(vertices), dtype=np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4")]))
+    for name in "xyz":
+        v[name] = vertices[name + "_mm"].astype(np.float32) / np.float32(1000.0)
+    f = np.empty(len(faces), dtype=np.dtype([("n", "u1"), ("i", "<i4", (3,))]))
+    f["n"] = 3
+    f["i"] = faces.astype(np.int32)
+    header = ("ply\nformat binary_little_endian 1.0\ncomment warpsense_amd surface-nets mesh\n"
+              f"element vertex {len(v)}\nproperty float x\nproperty float y\nproperty float z\n"
+              f"element face {len(f)}\nproperty list uchar int vertex_indices\nend_header\n")
+    with open(path, "wb") as out:
+        out.write(header.encode("ascii"))
+        out.write(v.tobytes())
+        out.write(f.tobytes())
+    return len(v), len(f)
 
 
 class Context:
@@ -578,6 +603,35 @@ class DeviceMapMemWrapper:
             raise WsError("surface: another call replaced the result before it was downloaded")
         return (rec, mk) if marker else rec
 
+    def mesh(self, lo=None, hi=None, any_weight=False, device=False):
+        """A triangle mesh of this map by naive surface nets on the device (ws_map_mesh; the rules are stated in
+        include/warpsense_hip.h): one vertex per active cell of the inclusive world-voxel box [lo, hi] (both None: the whole
+        window), two triangles per crossing lattice edge whose four cells are valid.  any_weight: voxels with a negative weight
+        count as observed too (the rule of the registration).
+
+        Returns (vertices, faces): a numpy array of dtype VERT (x_mm, y_mm, z_mm, weight) in ascending cell order and an (n, 3)
+        uint32 array of vertex indices, normals towards the outside.
+        device=True: torch tensors on the GPU instead -- (n, 4) int32 and (n, 3) int32 -- that ALIAS the library's buffers: valid
+        until the next mesh() on this TSDFCuda, copy them (.clone()) to keep them."""
+        t = self._t
+        if (lo is None) != (hi is None):
+            raise WsError("mesh: give both lo and hi, or neither")
+        nv, nf = C.c_size_t(0), C.c_size_t(0)
+        flags = _lib.WS_MESH_ANY_WEIGHT if any_weight else _lib.WS_MESH_DEFAULT
+        check(t._L.ws_map_mesh(t.handle, self._which, _ptr(_i3(lo)) if lo is not None else None, _ptr(_i3(hi)) if hi is not None else None,
+                               flags, C.byref(nv), C.byref(nf)), "ws_map_mesh")
+        nv, nf = int(nv.value), int(nf.value)
+        if device:
+            cnt = C.c_size_t(0)
+            return (_device_tensor(t._L.ws_map_mesh_vertices_dev(t.handle, C.byref(cnt)), (nv, 4), "<i4", t),
+                    _device_tensor(t._L.ws_map_mesh_faces_dev(t.handle, C.byref(cnt)), (nf, 3), "<i4", t))
+        vert, face = np.empty(nv, dtype=VERT), np.empty((nf, 3), dtype=np.uint32)
+        gv, gf = C.c_size_t(0), C.c_size_t(0)
+        check(t._L.ws_map_mesh_download(t.handle, _ptr(vert), _ptr(face), nv, nf, C.byref(gv), C.byref(gf)), "ws_map_mesh_download")
+        if (int(gv.value), int(gf.value)) != (nv, nf):
+            raise WsError("mesh: another call replaced the result before it was downloaded")
+        return vert, face
+
     def dev(self):
         return self._t.handle
 
@@ -886,6 +940,11 @@ class TSDFMapping:
         update, src/cpu/fastsense.cpp:115): DeviceMapMemWrapper.surface on avg_map(), under the mapping's lock like a reader."""
         with self.mutex_:
             return self.tsdf_.avg_map().surface(**kw)
+
+    def surface_mesh(self, **kw):
+        """A triangle mesh of the averaged map (DeviceMapMemWrapper.mesh on avg_map()), under the mapping's lock like a reader."""
+        with self.mutex_:
+            return self.tsdf_.avg_map().mesh(**kw)
 
     def shift_map(self, new_pos):
         """TSDFMapping::map_shift (tsdf_mapping.cpp:109-126) with the window moved ON THE DEVICE: per axis, the slab

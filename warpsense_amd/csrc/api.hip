@@ -288,11 +288,15 @@ static int map_free(ws_map *m)
   map_free_records(m);
   void *ptrs[] = {m->data[0], m->data[1], m->vstate, m->az_hist, m->az_off, m->ray_bin, m->ray_order, m->fan_steps, m->rays, m->scan_dev, m->counters, m->tile_nsub,
                   m->tile_ent, m->tile_dirty, m->tile_list, m->block_stats, m->box_stage,
-                  m->surf_col_cnt, m->surf_blk_tot, m->surf_blk_off, m->surf_total_dev, m->surf_rec, m->surf_marker};
+                  m->surf_col_cnt, m->surf_blk_tot, m->surf_blk_off, m->surf_total_dev, m->surf_rec, m->surf_marker,
+                  m->mesh_scratch, m->mesh_vert, m->mesh_face};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   if (m->surf_total_host) (void)hipHostFree(m->surf_total_host);
   for (hipEvent_t e : m->surf_ev)
+    if (e) (void)hipEventDestroy(e);
+  if (m->mesh_total_host) (void)hipHostFree(m->mesh_total_host);
+  for (hipEvent_t e : m->mesh_ev)
     if (e) (void)hipEventDestroy(e);
   if (m->counters_host) (void)hipHostFree(m->counters_host);
   if (m->status_host) (void)hipHostFree(m->status_host);
@@ -718,6 +722,138 @@ int ws_debug_surface_timing(ws_map *m, int32_t enable, float ms_out[3])
         e = nullptr;
       }
     m->surf_timing = enable != 0;
+  }
+  return WS_OK;
+}
+
+// ---- mesh: naive surface nets over a device map, map_mesh.hip (the rules are stated in warpsense_hip.h)
+int ws_map_mesh(ws_map *m, int which, const int32_t lo[3], const int32_t hi[3], uint32_t flags, size_t *n_vertices, size_t *n_faces)
+{
+  if (!m || (which != WS_MAP_AVG && which != WS_MAP_NEW) || (flags & ~WS_MESH_ANY_WEIGHT) || ((lo == nullptr) != (hi == nullptr)))
+    return invalid("ws_map_mesh: bad argument");
+  WS_SETTLE(m);
+  std::lock_guard<std::mutex> lock(m->mesh_mu);
+  const MapParams &p = m->par[which];
+  int32_t l[3], ext[3];
+  for (int k = 0; k < 3; ++k)
+  {
+    if (lo)
+    {
+      if (hi[k] < lo[k]) return invalid("ws_map_mesh: hi < lo");
+      if (std::abs(lo[k] - p.pos[k]) > p.size[k] / 2 || std::abs(hi[k] - p.pos[k]) > p.size[k] / 2)
+        return invalid("ws_map_mesh: box outside the local map window");
+      l[k] = lo[k];
+      ext[k] = hi[k] - lo[k] + 1;
+      if (ext[k] > p.size[k]) return invalid("ws_map_mesh: box wraps onto itself (more voxels than the ring holds along an axis)");
+    }
+    else
+    {
+      l[k] = p.pos[k] - p.size[k] / 2;
+      ext[k] = p.size[k];
+    }
+  }
+  for (int k = 0; k < 3; ++k)
+    for (int64_t c : {(int64_t)l[k], (int64_t)l[k] + ext[k] - 1})
+      if (((c < 0 ? -c : c) + 1) * (int64_t)m->res > (int64_t)INT32_MAX)
+      {
+        set_error("ws_map_mesh: a box corner in millimetres does not fit int32");
+        return WS_ERR_RANGE;
+      }
+  m->mesh_nv = m->mesh_nf = 0;
+  m->mesh_ev_count = m->mesh_ev_emit = false;
+  if (n_vertices) *n_vertices = 0;
+  if (n_faces) *n_faces = 0;
+  hipStream_t s = m->ctx->stream;
+  const uint64_t n_words = (uint64_t)ext[0] * (uint64_t)ext[1] * (uint64_t)((ext[2] + 63) / 64);
+  if (n_words >= (1ull << 31))
+  {
+    set_error("ws_map_mesh: box too large (columns x 64-voxel words must stay below 2^31)");
+    return WS_ERR_RANGE;
+  }
+  if (!m->mesh_total_host) WS_HIP(hipHostMalloc((void **)&m->mesh_total_host, 2 * sizeof(unsigned long long), hipHostMallocDefault));
+  if (m->mesh_timing)
+    for (hipEvent_t &e : m->mesh_ev)
+      if (!e) WS_HIP(hipEventCreate(&e));
+  if (ext[0] < 2 || ext[1] < 2 || ext[2] < 2) return map_take_error(m); // one voxel thick along an axis: no cells
+  WS_HIP(hipStreamSynchronize(s));
+  int rc = surf_grow(&m->mesh_scratch, &m->mesh_scratch_cap, mesh_scratch_bytes(n_words), 1);
+  if (rc != WS_OK) return rc;
+  rc = launch_mesh_count(m, which, l, ext, flags);
+  if (rc != WS_OK) return rc;
+  m->mesh_ev_count = true;
+  WS_HIP(hipStreamSynchronize(s)); // the one host read the call needs: the outputs are sized from the two totals
+  const unsigned long long nv = m->mesh_total_host[0], nq = m->mesh_total_host[1];
+  if (nv > 0xffffffffull)
+  {
+    set_error("ws_map_mesh: more than 2^32 - 1 vertices");
+    return WS_ERR_RANGE;
+  }
+  rc = surf_grow(&m->mesh_vert, &m->mesh_vert_cap, (size_t)nv, 16);
+  if (rc == WS_OK) rc = surf_grow((void **)&m->mesh_face, &m->mesh_face_cap, (size_t)nq * 2, 12);
+  if (rc != WS_OK) return rc;
+  if (nv)
+  {
+    rc = launch_mesh_emit(m, which, l, ext, flags);
+    if (rc != WS_OK) return rc;
+    m->mesh_ev_emit = true;
+    WS_HIP(hipStreamSynchronize(s));
+  }
+  m->mesh_nv = (size_t)nv;
+  m->mesh_nf = (size_t)nq * 2;
+  if (n_vertices) *n_vertices = m->mesh_nv;
+  if (n_faces) *n_faces = m->mesh_nf;
+  return map_take_error(m);
+}
+
+const void *ws_map_mesh_vertices_dev(const ws_map *m, size_t *n)
+{
+  if (n) *n = m ? m->mesh_nv : 0;
+  return m && m->mesh_nv ? m->mesh_vert : nullptr;
+}
+
+const uint32_t *ws_map_mesh_faces_dev(const ws_map *m, size_t *n)
+{
+  if (n) *n = m ? m->mesh_nf : 0;
+  return m && m->mesh_nf ? m->mesh_face : nullptr;
+}
+
+int ws_map_mesh_download(ws_map *m, void *vertices_host, uint32_t *faces_host, size_t cap_vertices, size_t cap_faces, size_t *n_vertices, size_t *n_faces)
+{
+  if (!m || !n_vertices || !n_faces) return invalid("ws_map_mesh_download: NULL argument");
+  std::lock_guard<std::mutex> lock(m->mesh_mu);
+  *n_vertices = m->mesh_nv;
+  *n_faces = m->mesh_nf;
+  const size_t kv = vertices_host ? std::min(cap_vertices, m->mesh_nv) : 0, kf = faces_host ? std::min(cap_faces, m->mesh_nf) : 0;
+  if (kv) WS_HIP(hipMemcpyAsync(vertices_host, m->mesh_vert, kv * 16, hipMemcpyDeviceToHost, m->ctx->stream));
+  if (kf) WS_HIP(hipMemcpyAsync(faces_host, m->mesh_face, kf * 12, hipMemcpyDeviceToHost, m->ctx->stream));
+  if (kv || kf) WS_HIP(hipStreamSynchronize(m->ctx->stream));
+  return WS_OK;
+}
+
+int ws_debug_mesh_timing(ws_map *m, int32_t enable, float ms_out[3])
+{
+  if (!m) return invalid("ws_debug_mesh_timing: map is NULL");
+  std::lock_guard<std::mutex> lock(m->mesh_mu);
+  if (ms_out)
+  {
+    ms_out[0] = ms_out[1] = ms_out[2] = 0.f;
+    if (m->mesh_timing && m->mesh_ev[0] && m->mesh_ev_count)
+    {
+      WS_HIP(hipStreamSynchronize(m->ctx->stream));
+      WS_HIP(hipEventElapsedTime(&ms_out[0], m->mesh_ev[0], m->mesh_ev[1]));
+      WS_HIP(hipEventElapsedTime(&ms_out[1], m->mesh_ev[1], m->mesh_ev[2]));
+      if (m->mesh_ev_emit) WS_HIP(hipEventElapsedTime(&ms_out[2], m->mesh_ev[3], m->mesh_ev[4]));
+    }
+  }
+  if (enable >= 0)
+  {
+    if (!enable || !m->mesh_timing)
+      for (hipEvent_t &e : m->mesh_ev)
+      {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+      }
+    m->mesh_timing = enable != 0;
   }
   return WS_OK;
 }

@@ -276,6 +276,19 @@ struct ws_map
   bool surf_timing = false;                    // ws_debug_surface_timing: events around the three launches
   hipEvent_t surf_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   bool surf_ev_emit = false;                   // the last call launched the emit pass (events 3, 4 are recorded)
+  // ws_map_mesh (map_mesh.hip): the mesh of the last call and the scratch of its passes, apart from the surface cloud's; allocated on
+  // first use and grown on demand.  mesh_mu serialises the calls that use these buffers.
+  std::mutex mesh_mu;
+  void *mesh_scratch = nullptr;                // bit planes, per-word bases and counts, workgroup totals and their scans (mesh_scratch_bytes)
+  size_t mesh_scratch_cap = 0;                 // bytes
+  unsigned long long *mesh_total_host = nullptr; // pinned: vertices, quads
+  void *mesh_vert = nullptr;                   // [mesh_vert_cap] 16-byte vertices
+  uint32_t *mesh_face = nullptr;               // [mesh_face_cap][3]
+  size_t mesh_vert_cap = 0, mesh_face_cap = 0;
+  size_t mesh_nv = 0, mesh_nf = 0;             // vertices and faces of the last call
+  bool mesh_timing = false;                    // ws_debug_mesh_timing: events around the count passes, the scan and the emit passes
+  hipEvent_t mesh_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  bool mesh_ev_count = false, mesh_ev_emit = false; // the last call recorded events 0..2 / 3, 4
   // The scan whose verdict (did its records fit the pool?) has not been looked at yet: ws_tsdf_update* return after the
   // launches, like the reference's update_tsdf (update_tsdf.cu:165); the next call that takes this map settles it first
   // (settle_tsdf: the verdict is in host-mapped memory ~0.35 ms after the launches) and repeats the scan if it was aborted.
@@ -420,6 +433,10 @@ int launch_box_copy(ws_map *m, const ws::MapParams &par, int which, const int32_
 size_t surface_blocks_for(int64_t n_cols);
 int launch_surface_count(ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], int32_t band);
 int launch_surface_emit(ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], int32_t band, bool marker);
+// map_mesh.hip: bits + cells + quads + scans (the totals arrive in ws_map::mesh_total_host after a stream synchronise), then the emit passes
+size_t mesh_scratch_bytes(uint64_t n_words);
+int launch_mesh_count(ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], uint32_t flags);
+int launch_mesh_emit(ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], uint32_t flags);
 int fill_u32(ws_context *ctx, uint32_t *dst, uint32_t value, int64_t n);
 int launch_box_fill(ws_map *m, const ws::MapParams &par, int which, const int32_t lo[3], const int32_t ext[3], uint32_t value, hipStream_t stream);
 int check_all_equal_host(const uint32_t *data, int64_t n, uint32_t value);
