@@ -210,6 +210,54 @@ int ws_map_mesh_download(ws_map *map, void *vertices_host, uint32_t *faces_host,
 /* Measurement entry, as ws_debug_surface_timing: ms_out receives the device time of the count passes, the scan and the emit passes */
 int ws_debug_mesh_timing(ws_map *map, int32_t enable, float ms_out[3]);
 
+/* Ray cast of a device map: what the sensor would see from a pose -- per ray the first crossing of the surface from the outside,
+ * as hit point and range, and on request the TSDF gradient there.  Integers only: the result is exact and the same bytes on every
+ * run.  All products and quotients below are int64; "trunc" is C division, "floor" is floor division.
+ *   value, weight: the entry's two int16.  A voxel is VALID iff it lies in the window [pos - size/2, pos - size/2 + size - 1] per
+ *     axis (the window of ws_map_surface: each ring cell once) and weight > 0; with WS_RAYCAST_ANY_WEIGHT iff weight != 0 (the
+ *     registration's rule, as WS_MESH_ANY_WEIGHT).  The sample of voxel v sits at v res + h mm per axis, h = res / 2 truncated (the
+ *     voxel centre of the update, the lattice of the mesh).
+ *   field at a point p (mm): q = p - h, base voxel b = floor(q / res), f = q - b res (0 <= f < res, per axis).  The cell is the 8
+ *     voxels b + {0,1}^3; it is valid iff all 8 are valid.  T(p) = sum over the corners c of value(c) wx wy wz, with w = f on the
+ *     far side and res - f on the near side of each axis: the trilinear interpolant times res^3, never divided.  res <= 1024
+ *     (else WS_ERR_RANGE), so |T| < 2^46.
+ *   ray i: origin o (int32 mm, one for all rays of a call), direction d_i (3 int32, any length, |component| < 2^30; a ray with a
+ *     larger component is a no-hit).  L = floor(sqrt(dx^2 + dy^2 + dz^2)) exactly (integer square root).  L == 0: no hit.
+ *     Samples k = 0, 1, ..., K, K = max_range / step, step = max(res / 2, 1) (the update's march step), at s_k = k step,
+ *     p_k = o + trunc(d s_k / L) per axis (the update's pos + dir * len / distance).
+ *   hit: the first k >= 1 with: cell of p_{k-1} valid and T(p_{k-1}) > 0, cell of p_k valid and T(p_k) <= 0 -- a crossing from
+ *     outside to inside, seen from the front.  Crossings from inside to outside and anything next to an invalid cell are walked
+ *     past; the march goes on to K.  Range t = s_{k-1} + floor(step T_{k-1} / (T_{k-1} - T_k)) (so s_{k-1} <= t <= s_k), hit point
+ *     o + trunc(d t / L).
+ *   record, 16 bytes, one per ray, in ray order (index i of the input): int32 x_mm, y_mm, z_mm, range_mm; no hit: 0, 0, 0, -1.
+ *     With WS_RAYCAST_GRADIENT a second array, 3 int32 per ray in the same order: at g = floor(hit / res) per axis,
+ *     value(g + e_k) - value(g - e_k) for k = 0, 1, 2 if all six neighbours are valid, else 0, 0, 0 (also for no hit).  It points
+ *     to the outside, towards the sensor; it is not normalised.
+ *   WS_RAYCAST_TARGETS: the n x 3 int32 are not directions but map-frame points in mm, d_i = point_i - origin (int64; a component
+ *     with |d| >= 2^30 makes that ray a no-hit): a scan left on the device by ws_scan_preprocess or ws_reg_prepare_dev
+ *     (ws_scan_points_dev, ws_reg_points_dev) is ray cast where it lies.
+ *   A ray may start or run outside the window: those cells are invalid, nothing more.
+ * max_range <= 0: WS_ERR_INVALID.  |o| + max_range + 2 res does not fit int32 on an axis, n > 2^27 or res > 1024: WS_ERR_RANGE.
+ * n == 0: WS_OK, nothing written.  The walk above defines the records; the implementation shortens it only where they stay the same.
+ * Synchronises (*n_hits, may be NULL, is the number of records with range_mm >= 0).  The result buffers belong to the map, grow on
+ * demand and stay valid until the next ray cast on it; they are apart from those of ws_map_surface and ws_map_mesh, none of the
+ * three calls invalidates another's result.  Read-only on the maps: may run next to ws_register_cloud under the reference's shared
+ * lock; calls that use the result buffers are serialised inside the library.  Nothing is allocated before the first call.
+ * ws_map_raycast_dev takes an array that is already in device memory (it must stay untouched until the call returns). */
+#define WS_RAYCAST_DEFAULT 0u
+#define WS_RAYCAST_ANY_WEIGHT 1u
+#define WS_RAYCAST_GRADIENT 2u
+#define WS_RAYCAST_TARGETS 4u
+int ws_map_raycast(ws_map *map, int which, const int32_t origin_mm[3], const int32_t *dirs_host, size_t n, int32_t max_range_mm, uint32_t flags, size_t *n_hits);
+int ws_map_raycast_dev(ws_map *map, int which, const int32_t origin_mm[3], const int32_t *dirs_dev, size_t n, int32_t max_range_mm, uint32_t flags, size_t *n_hits);
+const void *ws_map_raycast_records_dev(const ws_map *map, size_t *n);     /* device memory, n x 16 bytes; NULL when n == 0 */
+const int32_t *ws_map_raycast_gradient_dev(const ws_map *map, size_t *n); /* n x 3 int32; NULL unless the last call asked for it */
+/* copies at most capacity_rays records (and gradients: a prefix) and always reports the number of rays; either host pointer may be NULL */
+int ws_map_raycast_download(ws_map *map, void *records_host, int32_t *gradient_host, size_t capacity_rays, size_t *n_out);
+/* Measurement entry, as ws_debug_surface_timing: ms_out receives the device time of the upload of the directions (0 for the _dev
+ * form), of the march and of the gradient pass of the last call */
+int ws_debug_raycast_timing(ws_map *map, int32_t enable, float ms_out[3]);
+
 /* ------------------------------------------------------------------ TSDF update ---- */
 /* TSDFCuda::update_tsdf(scan_points, scanner_pos, up) — update_tsdf.cu:143-166.
  * xyz_host: n x 3 int32 (rmagine::Pointi AoS); scanner_pos in voxel units, up scaled by 32768.

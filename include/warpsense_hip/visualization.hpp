@@ -2,6 +2,7 @@
 //
 //   local_map_cloud      publish_local_map           map.h:14-121    the surface cloud of a DEVICE map, over ws_map_surface
 //   local_map_mesh       (no counterpart: the reference sends the user to an offline mesher)   a triangle mesh, over ws_map_mesh
+//   local_map_raycast    (no counterpart: the reference leaves all viewing to RViz)            a predicted scan, over ws_map_raycast
 //   local_map_skeleton   publish_local_map_skeleton  map.h:175-227   the 24 end points of the window's line list (host only)
 //
 // The reference walks every voxel of a host map (after a whole-map download for the CUDA map, test/pcd2tsdf.cpp:134-137); here
@@ -75,6 +76,37 @@ inline SurfaceMesh local_map_mesh(cuda::TSDFCuda &tsdf, int which = WS_MAP_AVG, 
   out.faces.resize(nf);
   size_t gv = 0, gf = 0;
   WS_CHECK(ws_map_mesh_download(tsdf.handle(), nv ? out.vertices.data() : nullptr, nf ? &out.faces.data()->v[0] : nullptr, nv, nf, &gv, &gf));
+  return out;
+}
+
+struct RayHit // one record of ws_map_raycast
+{
+  int32_t x_mm, y_mm, z_mm; // the hit point in the map frame; 0, 0, 0 without a hit
+  int32_t range_mm;         // along the ray; -1 without a hit
+};
+static_assert(sizeof(RayHit) == 16, "ws_map_raycast writes 16-byte records");
+
+struct RayCast
+{
+  std::vector<RayHit> records;          // in ray order
+  std::vector<rmagine::Pointi> gradient; // with_gradient: value(g + e_k) - value(g - e_k) at the hit, towards the outside; else empty
+  size_t hits = 0;                      // records with range_mm >= 0
+};
+
+// The ray cast of `which` from origin_mm (the rules: warpsense_hip.h at ws_map_raycast): one ray per element of `dirs`, integer
+// directions of any length, or -- targets -- map-frame points in millimetres the rays run towards.  any_weight: voxels with a
+// negative weight count as observed (WS_RAYCAST_ANY_WEIGHT).
+inline RayCast local_map_raycast(cuda::TSDFCuda &tsdf, const rmagine::Pointi &origin_mm, const std::vector<rmagine::Pointi> &dirs, int32_t max_range_mm,
+                                 bool with_gradient = false, bool any_weight = false, bool targets = false, int which = WS_MAP_AVG)
+{
+  RayCast out;
+  const uint32_t flags = (any_weight ? WS_RAYCAST_ANY_WEIGHT : 0u) | (with_gradient ? WS_RAYCAST_GRADIENT : 0u) | (targets ? WS_RAYCAST_TARGETS : 0u);
+  WS_CHECK(ws_map_raycast(tsdf.handle(), which, &origin_mm.x, dirs.empty() ? nullptr : &dirs.data()->x, dirs.size(), max_range_mm, flags, &out.hits));
+  out.records.resize(dirs.size());
+  if (with_gradient) out.gradient.resize(dirs.size());
+  size_t got = 0;
+  WS_CHECK(ws_map_raycast_download(tsdf.handle(), dirs.empty() ? nullptr : out.records.data(), with_gradient && !dirs.empty() ? &out.gradient.data()->x : nullptr,
+                                   dirs.size(), &got));
   return out;
 }
 

@@ -3,6 +3,7 @@ sliding TSDF map @ 5 cm, one MI355X): sensor clouds in float metres -> device pr
 (when the sensor moved > 0.3 m) -> Point-to-TSDF registration -> pose -> map shift (device-side slabs).
 
     python tools/replay_stream.py --map 1024 --scans 30 [--h5 /tmp/stream.h5] [--surface-ply DIR [--surface-every N]] [--mesh-ply DIR]
+                                   [--raycast-ply DIR]
 
 Prints one JSON line: scans/s over the stream and the mean per-stage times (the reference's RuntimeEvaluator
 forms "preprocess", "tsdf", "registration", "total")."""
@@ -34,6 +35,9 @@ def main():
                     "device: TSDFMapping.surface_cloud) as binary little-endian PLY (xyz + rgb) into DIR")
     ap.add_argument("--mesh-ply", default=None, metavar="DIR", help="write a triangle mesh of the window (surface nets on the device: "
                     "TSDFMapping.surface_mesh) as binary little-endian PLY into DIR, after every N-th scan like --surface-ply")
+    ap.add_argument("--raycast-ply", default=None, metavar="DIR", help="after every registered scan: the ray cast of the map from the registered pose "
+                    "(TSDFMapping.raycast, the OS1-128 pattern, hits with normals) as binary little-endian PLY into DIR, and the median absolute "
+                    "scan_residual of the scan printed")
     ap.add_argument("--surface-every", type=int, default=10, metavar="N", help="... after every N-th scan")
     args = ap.parse_args()
     import warpsense_amd as W
@@ -60,6 +64,9 @@ def main():
         os.makedirs(args.surface_ply, exist_ok=True)
     if args.mesh_ply:
         os.makedirs(args.mesh_ply, exist_ok=True)
+    raycast = {"files": 0, "hits": 0, "median_abs_residual_mm": [], "seconds": 0.0}
+    if args.raycast_ply:
+        os.makedirs(args.raycast_ply, exist_ok=True)
     for k, c in enumerate(clouds):
         if args.hz > 0.0:
             wait = t1 + k / args.hz - time.perf_counter()
@@ -79,6 +86,17 @@ def main():
             mesh["vertices"], mesh["faces"] = W.write_mesh_ply(os.path.join(args.mesh_ply, f"mesh_{k + 1:05d}.ply"), *app.gpu_.surface_mesh())
             mesh["files"] += 1
             mesh["seconds"] += time.perf_counter() - ts
+        if args.raycast_ply:
+            ts = time.perf_counter()
+            pose_m = app.pose_.astype(np.float64)
+            pose_m[:3, 3] /= 1000.0  # (the app keeps its translation in millimetres)
+            raycast["hits"] = W.write_raycast_ply(os.path.join(args.raycast_ply, f"raycast_{k + 1:05d}.ply"), *app.gpu_.raycast(pose_m, gradient=True))
+            resid = app.gpu_.scan_residual(app.preprocess(c), pose_m)  # the scan at the registered pose, where it lies on the device
+            med = float(np.nanmedian(np.abs(resid))) if np.any(~np.isnan(resid)) else None
+            print(f"scan {k + 1}: raycast hits {raycast['hits']}, median |scan residual| {med} mm", file=sys.stderr)
+            raycast["median_abs_residual_mm"].append(med)
+            raycast["files"] += 1
+            raycast["seconds"] += time.perf_counter() - ts
     W.pause()
     t2 = time.perf_counter()
     stages = {}
@@ -100,7 +118,8 @@ def main():
                       "final_position_error_mm": float(np.linalg.norm(app.poses[-1][:3, 3] - true_last)),
                       "terminate_write_back_s": t4 - t3, "h5": args.h5,
                       "surface_ply": surface if args.surface_ply else None,
-                      "mesh_ply": mesh if args.mesh_ply else None}))
+                      "mesh_ply": mesh if args.mesh_ply else None,
+                      "raycast_ply": raycast if args.raycast_ply else None}))
 
 
 if __name__ == "__main__":

@@ -31,9 +31,11 @@ EXPORTS = [
     "ws_scan_preprocess_dev", "ws_scan_points_dev", "ws_scan_download", "ws_prof_enable", "ws_prof_read", "ws_prof_reset",
     "ws_map_surface", "ws_map_surface_records_dev", "ws_map_surface_marker_dev", "ws_map_surface_download", "ws_debug_surface_timing",
     "ws_map_mesh", "ws_map_mesh_vertices_dev", "ws_map_mesh_faces_dev", "ws_map_mesh_download", "ws_debug_mesh_timing",
+    "ws_map_raycast", "ws_map_raycast_dev", "ws_map_raycast_records_dev", "ws_map_raycast_gradient_dev", "ws_map_raycast_download", "ws_debug_raycast_timing",
 ]
 WS_SURFACE_RECORDS, WS_SURFACE_MARKER = 0, 1
 WS_MESH_DEFAULT, WS_MESH_ANY_WEIGHT = 0, 1
+WS_RAYCAST_DEFAULT, WS_RAYCAST_ANY_WEIGHT, WS_RAYCAST_GRADIENT, WS_RAYCAST_TARGETS = 0, 1, 2, 4
 
 
 class WsError(RuntimeError):
@@ -138,6 +140,14 @@ def load() -> C.CDLL:
     L.ws_map_mesh_faces_dev.restype = vp
     L.ws_map_mesh_download.argtypes = [vp, vp, vp, sz, sz, P(sz), P(sz)]
     L.ws_debug_mesh_timing.argtypes = [vp, i32, vp]
+    L.ws_map_raycast.argtypes = [vp, C.c_int, vp, vp, sz, i32, u32, P(sz)]
+    L.ws_map_raycast_dev.argtypes = [vp, C.c_int, vp, vp, sz, i32, u32, P(sz)]
+    L.ws_map_raycast_records_dev.argtypes = [vp, P(sz)]
+    L.ws_map_raycast_records_dev.restype = vp
+    L.ws_map_raycast_gradient_dev.argtypes = [vp, P(sz)]
+    L.ws_map_raycast_gradient_dev.restype = vp
+    L.ws_map_raycast_download.argtypes = [vp, vp, vp, sz, P(sz)]
+    L.ws_debug_raycast_timing.argtypes = [vp, i32, vp]
     L.ws_shift_begin.argtypes = [vp, vp, u32, P(vp)]
     L.ws_shift_count.argtypes = [vp]
     L.ws_shift_reserve.argtypes = [vp, C.c_uint64]

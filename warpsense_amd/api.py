@@ -83,6 +83,10 @@ SURFACE_RECORD = np.dtype([("x", "<i4"), ("y", "<i4"), ("z", "<i4"), ("raw", "<u
 VERT = np.dtype([("x_mm", "<i4"), ("y_mm", "<i4"), ("z_mm", "<i4"), ("weight", "<u4")])
 
 
+# one record of ws_map_raycast: the hit point and the range along the ray in millimetres; no hit: 0, 0, 0, -1 (16 bytes)
+RAY = np.dtype([("x_mm", "<i4"), ("y_mm", "<i4"), ("z_mm", "<i4"), ("range_mm", "<i4")])
+
+
 class _DeviceArray:
     """a library-owned device buffer as torch sees it (__cuda_array_interface__); `owner` keeps the handle alive"""
 
@@ -134,6 +138,30 @@ def write_mesh_ply(path, vertices, faces):
         out.write(v.tobytes())
         out.write(f.tobytes())
     return len(v), len(f)
+
+
+def write_raycast_ply(path, records, gradient=None):
+    """The hits of DeviceMapMemWrapper.raycast() (records with range_mm >= 0) as a binary little-endian PLY point cloud: float x y z
+    in metres (mm / 1000.f in single precision, as write_mesh_ply) and, when `gradient` is given, float nx ny nz: the gradient
+    normalised in float64, then cast (a zero gradient stays zero).  Returns the number of points written."""
+    records = np.asarray(records, dtype=RAY).reshape(-1)
+    hit = records["range_mm"] >= 0
+    names = ["x", "y", "z"] + (["nx", "ny", "nz"] if gradient is not None else [])
+    v = np.empty(int(np.count_nonzero(hit)), dtype=np.dtype([(n, "<f4") for n in names]))
+    for name in "xyz":
+        v[name] = records[name + "_mm"][hit].astype(np.float32) / np.float32(1000.0)
+    if gradient is not None:
+        g = np.asarray(gradient, dtype=np.int32).reshape(-1, 3)[hit].astype(np.float64)
+        length = np.sqrt(np.sum(g * g, axis=1))
+        g = g / np.where(length > 0, length, 1.0)[:, None]
+        for k, name in enumerate(("nx", "ny", "nz")):
+            v[name] = g[:, k].astype(np.float32)
+    header = ("ply\nformat binary_little_endian 1.0\ncomment warpsense_amd ray cast\n"
+              f"element vertex {len(v)}\n" + "".join(f"property float {n}\n" for n in names) + "end_header\n")
+    with open(path, "wb") as out:
+        out.write(header.encode("ascii"))
+        out.write(v.tobytes())
+    return len(v)
 
 
 class Context:
@@ -632,6 +660,37 @@ class DeviceMapMemWrapper:
             raise WsError("mesh: another call replaced the result before it was downloaded")
         return vert, face
 
+    def raycast(self, origin_mm, dirs, max_range_mm, any_weight=False, gradient=False, targets=False):
+        """Ray cast of this map on the device (ws_map_raycast; the rules are stated in include/warpsense_hip.h): per ray the first
+        crossing of the surface from the outside within max_range_mm.  origin_mm: three int32 (map frame, millimetres); dirs:
+        (n, 3) int32 directions of any length (|component| < 2^30), a numpy array or a device array (a CUDA tensor, DevicePoints);
+        targets=True: `dirs` holds map-frame points in mm instead and every ray runs from the origin towards its point.
+        any_weight: voxels with a negative weight count as observed too (the rule of the registration).
+
+        Returns (records, gradient): a numpy array of dtype RAY (x_mm, y_mm, z_mm, range_mm; no hit: 0, 0, 0, -1) in ray order
+        and, with gradient=True, an (n, 3) int32 array of central differences of the TSDF value at the hit (towards the outside,
+        not normalised; zeros where a neighbour is unobserved), else None.  `last_hits` keeps the call's number of hits."""
+        t = self._t
+        n = int(dirs.shape[0])
+        flags = ((_lib.WS_RAYCAST_ANY_WEIGHT if any_weight else 0) | (_lib.WS_RAYCAST_GRADIENT if gradient else 0)
+                 | (_lib.WS_RAYCAST_TARGETS if targets else 0))
+        hits = C.c_size_t(0)
+        if _is_device(dirs):
+            check(t._L.ws_map_raycast_dev(t.handle, self._which, _ptr(_i3(origin_mm)), _ptr(dirs), n, int(max_range_mm), flags, C.byref(hits)),
+                  "ws_map_raycast_dev")
+        else:
+            d = np.ascontiguousarray(dirs, dtype=np.int32).reshape(-1, 3)
+            check(t._L.ws_map_raycast(t.handle, self._which, _ptr(_i3(origin_mm)), _ptr(d), n, int(max_range_mm), flags, C.byref(hits)),
+                  "ws_map_raycast")
+        rec = np.empty(n, dtype=RAY)
+        grad = np.empty((n, 3), dtype=np.int32) if gradient else None
+        got = C.c_size_t(0)
+        check(t._L.ws_map_raycast_download(t.handle, _ptr(rec), _ptr(grad), n, C.byref(got)), "ws_map_raycast_download")
+        if int(got.value) != n:
+            raise WsError("raycast: another call replaced the result before it was downloaded")
+        self.last_hits = int(hits.value)
+        return rec, grad
+
     def dev(self):
         return self._t.handle
 
@@ -945,6 +1004,48 @@ class TSDFMapping:
         """A triangle mesh of the averaged map (DeviceMapMemWrapper.mesh on avg_map()), under the mapping's lock like a reader."""
         with self.mutex_:
             return self.tsdf_.avg_map().mesh(**kw)
+
+    @staticmethod
+    def raycast_rays(pose, dirs):
+        """The integers of a ray cast from a pose, in float64 numpy: origin = the pose's translation in metres times 1000, rounded
+        to nearest (ties to even); every direction (unit-free, sensor frame) is rotated by the pose's 3 x 3 block and scaled so
+        that its longest component is 2^20 in magnitude, then rounded to nearest; a zero direction stays zero (a no-hit).
+        Returns (origin_mm (3,) int32, dirs (n, 3) int32)."""
+        pose = np.asarray(pose, dtype=np.float64).reshape(4, 4)
+        origin = np.rint(pose[:3, 3] * 1000.0).astype(np.int32)
+        d = np.asarray(dirs, dtype=np.float64).reshape(-1, 3) @ pose[:3, :3].T
+        longest = np.max(np.abs(d), axis=1)
+        d = d * (float(1 << 20) / np.where(longest > 0, longest, 1.0))[:, None]
+        return origin, np.rint(d).astype(np.int32)
+
+    def _diagonal_mm(self):
+        size = np.asarray(self.local_map_.size, dtype=np.float64) * float(self.params_.map.resolution)
+        return int(np.ceil(np.sqrt(np.sum(size * size))))
+
+    def raycast(self, pose, dirs=None, max_range_mm=None, **kw):
+        """The predicted scan of the averaged map from `pose` (4 x 4, metres): DeviceMapMemWrapper.raycast on avg_map(), under the
+        mapping's lock like a reader.  dirs: (n, 3) float directions in the sensor frame (None: the 128 x 1024 table of the
+        OS1-128 pattern, synthetic.os1_128_dirs); they and the pose become integers by the rule of raycast_rays.
+        max_range_mm None: the window's diagonal.  Returns (records, gradient | None)."""
+        if dirs is None:
+            from .synthetic import os1_128_dirs
+            dirs = os1_128_dirs()
+        origin, d = self.raycast_rays(pose, dirs)
+        with self.mutex_:
+            return self.tsdf_.avg_map().raycast(origin, d, self._diagonal_mm() if max_range_mm is None else max_range_mm, **kw)
+
+    def scan_residual(self, points_mm, pose, **kw):
+        """Per point of a scan in the map frame (n x 3 int32 millimetres, numpy or on the device as it lies: a CUDA tensor,
+        DevicePoints) the range the averaged map shows along the ray from the pose's origin (raycast_rays) towards the point,
+        minus the point's own distance |point - origin|, in millimetres (float64; NaN where the ray does not hit within the
+        window's diagonal).  The median of its absolute value is the quality figure of a registration."""
+        origin = self.raycast_rays(pose, np.zeros((0, 3)))[0]
+        with self.mutex_:
+            rec, _ = self.tsdf_.avg_map().raycast(origin, points_mm, self._diagonal_mm(), targets=True, **kw)
+        if _is_device(points_mm):
+            points_mm = points_mm.to_host() if hasattr(points_mm, "to_host") else points_mm.cpu().numpy()
+        d = np.asarray(points_mm, dtype=np.float64).reshape(-1, 3) - origin.astype(np.float64)
+        return np.where(rec["range_mm"] >= 0, rec["range_mm"].astype(np.float64) - np.sqrt(np.sum(d * d, axis=1)), np.nan)
 
     def shift_map(self, new_pos):
         """TSDFMapping::map_shift (tsdf_mapping.cpp:109-126) with the window moved ON THE DEVICE: per axis, the slab

@@ -289,7 +289,7 @@ static int map_free(ws_map *m)
   void *ptrs[] = {m->data[0], m->data[1], m->vstate, m->az_hist, m->az_off, m->ray_bin, m->ray_order, m->fan_steps, m->rays, m->scan_dev, m->counters, m->tile_nsub,
                   m->tile_ent, m->tile_dirty, m->tile_list, m->block_stats, m->box_stage,
                   m->surf_col_cnt, m->surf_blk_tot, m->surf_blk_off, m->surf_total_dev, m->surf_rec, m->surf_marker,
-                  m->mesh_scratch, m->mesh_vert, m->mesh_face};
+                  m->mesh_scratch, m->mesh_vert, m->mesh_face, m->ray_dirs, m->ray_rec, m->ray_grad, m->ray_hits_dev};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   if (m->surf_total_host) (void)hipHostFree(m->surf_total_host);
@@ -297,6 +297,9 @@ static int map_free(ws_map *m)
     if (e) (void)hipEventDestroy(e);
   if (m->mesh_total_host) (void)hipHostFree(m->mesh_total_host);
   for (hipEvent_t e : m->mesh_ev)
+    if (e) (void)hipEventDestroy(e);
+  if (m->ray_hits_host) (void)hipHostFree(m->ray_hits_host);
+  for (hipEvent_t e : m->ray_ev)
     if (e) (void)hipEventDestroy(e);
   if (m->counters_host) (void)hipHostFree(m->counters_host);
   if (m->status_host) (void)hipHostFree(m->status_host);
@@ -854,6 +857,139 @@ int ws_debug_mesh_timing(ws_map *m, int32_t enable, float ms_out[3])
         e = nullptr;
       }
     m->mesh_timing = enable != 0;
+  }
+  return WS_OK;
+}
+
+// ---- ray cast: the range image of a device map, map_raycast.hip (the rules are stated in warpsense_hip.h)
+static int raycast_run(ws_map *m, int which, const int32_t origin[3], const int32_t *dirs, bool dirs_on_host, size_t n, int32_t max_range, uint32_t flags,
+                       size_t *n_hits)
+{
+  const uint32_t known = WS_RAYCAST_ANY_WEIGHT | WS_RAYCAST_GRADIENT | WS_RAYCAST_TARGETS;
+  if (!m || (which != WS_MAP_AVG && which != WS_MAP_NEW) || (flags & ~known) || !origin || (n && !dirs)) return invalid("ws_map_raycast: bad argument");
+  if (max_range <= 0) return invalid("ws_map_raycast: max_range_mm <= 0");
+  if (m->res > 1024)
+  {
+    set_error("ws_map_raycast: the resolution must not exceed 1024 mm (the interpolant is carried times res^3 in 64 bits)");
+    return WS_ERR_RANGE;
+  }
+  if (n > ((size_t)1 << 27))
+  {
+    set_error("ws_map_raycast: more than 2^27 rays");
+    return WS_ERR_RANGE;
+  }
+  for (int k = 0; k < 3; ++k)
+  {
+    const int64_t o = origin[k];
+    if ((o < 0 ? -o : o) + (int64_t)max_range + 2 * (int64_t)m->res > (int64_t)INT32_MAX)
+    {
+      set_error("ws_map_raycast: |origin| + max_range + 2 res does not fit int32");
+      return WS_ERR_RANGE;
+    }
+  }
+  WS_SETTLE(m);
+  std::lock_guard<std::mutex> lock(m->ray_mu);
+  if (n_hits) *n_hits = 0;
+  m->ray_n = 0;
+  m->ray_has_grad = false;
+  m->ray_ev_done = false;
+  if (n == 0) return map_take_error(m);
+  hipStream_t s = m->ctx->stream;
+  const bool grad = (flags & WS_RAYCAST_GRADIENT) != 0;
+  if (!m->ray_hits_dev)
+  {
+    WS_HIP(hipMalloc((void **)&m->ray_hits_dev, sizeof(unsigned long long)));
+    WS_HIP(hipHostMalloc((void **)&m->ray_hits_host, sizeof(unsigned long long), hipHostMallocDefault));
+  }
+  if (m->ray_timing)
+    for (hipEvent_t &e : m->ray_ev)
+      if (!e) WS_HIP(hipEventCreate(&e));
+  if (n > m->ray_rec_cap || (grad && n > m->ray_grad_cap) || (dirs_on_host && n > m->ray_dirs_cap))
+  {
+    WS_HIP(hipStreamSynchronize(s));
+    int rc = surf_grow(&m->ray_rec, &m->ray_rec_cap, n, 16);
+    if (rc == WS_OK && grad) rc = surf_grow((void **)&m->ray_grad, &m->ray_grad_cap, n, 3 * sizeof(int32_t));
+    if (rc == WS_OK && dirs_on_host) rc = surf_grow((void **)&m->ray_dirs, &m->ray_dirs_cap, n, 3 * sizeof(int32_t));
+    if (rc != WS_OK) return rc;
+  }
+  if (m->ray_timing) (void)hipEventRecord(m->ray_ev[0], s);
+  if (dirs_on_host)
+  {
+    WS_HIP(hipMemcpyAsync(m->ray_dirs, dirs, n * 3 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    dirs = m->ray_dirs;
+  }
+  const int rc = launch_raycast(m, which, origin, dirs, n, max_range, flags);
+  if (rc != WS_OK) return rc;
+  WS_HIP(hipStreamSynchronize(s));
+  m->ray_ev_done = m->ray_timing;
+  m->ray_n = n;
+  m->ray_has_grad = grad;
+  if (n_hits) *n_hits = (size_t)*m->ray_hits_host;
+  return map_take_error(m);
+}
+
+int ws_map_raycast(ws_map *m, int which, const int32_t origin_mm[3], const int32_t *dirs_host, size_t n, int32_t max_range_mm, uint32_t flags, size_t *n_hits)
+{
+  return raycast_run(m, which, origin_mm, dirs_host, true, n, max_range_mm, flags, n_hits);
+}
+
+int ws_map_raycast_dev(ws_map *m, int which, const int32_t origin_mm[3], const int32_t *dirs_dev, size_t n, int32_t max_range_mm, uint32_t flags, size_t *n_hits)
+{
+  return raycast_run(m, which, origin_mm, dirs_dev, false, n, max_range_mm, flags, n_hits);
+}
+
+const void *ws_map_raycast_records_dev(const ws_map *m, size_t *n)
+{
+  if (n) *n = m ? m->ray_n : 0;
+  return m && m->ray_n ? m->ray_rec : nullptr;
+}
+
+const int32_t *ws_map_raycast_gradient_dev(const ws_map *m, size_t *n)
+{
+  const bool have = m && m->ray_has_grad && m->ray_n;
+  if (n) *n = have ? m->ray_n : 0;
+  return have ? m->ray_grad : nullptr;
+}
+
+int ws_map_raycast_download(ws_map *m, void *records_host, int32_t *gradient_host, size_t capacity_rays, size_t *n_out)
+{
+  if (!m || !n_out) return invalid("ws_map_raycast_download: NULL argument");
+  std::lock_guard<std::mutex> lock(m->ray_mu);
+  *n_out = m->ray_n;
+  const size_t k = std::min(capacity_rays, m->ray_n);
+  if (k == 0) return WS_OK;
+  if (gradient_host && !m->ray_has_grad) return invalid("ws_map_raycast_download: the last ws_map_raycast did not ask for WS_RAYCAST_GRADIENT");
+  if (records_host) WS_HIP(hipMemcpyAsync(records_host, m->ray_rec, k * 16, hipMemcpyDeviceToHost, m->ctx->stream));
+  if (gradient_host) WS_HIP(hipMemcpyAsync(gradient_host, m->ray_grad, k * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, m->ctx->stream));
+  WS_HIP(hipStreamSynchronize(m->ctx->stream));
+  return WS_OK;
+}
+
+int ws_debug_raycast_timing(ws_map *m, int32_t enable, float ms_out[3])
+{
+  if (!m) return invalid("ws_debug_raycast_timing: map is NULL");
+  std::lock_guard<std::mutex> lock(m->ray_mu);
+  if (ms_out)
+  {
+    ms_out[0] = ms_out[1] = ms_out[2] = 0.f;
+    if (m->ray_timing && m->ray_ev[0] && m->ray_ev_done)
+    {
+      WS_HIP(hipStreamSynchronize(m->ctx->stream));
+      for (int k = 0; k < 3; ++k) WS_HIP(hipEventElapsedTime(&ms_out[k], m->ray_ev[k], m->ray_ev[k + 1]));
+    }
+  }
+  if (enable >= 0)
+  {
+    if (!enable || !m->ray_timing)
+    {
+      for (hipEvent_t &e : m->ray_ev)
+      {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+      }
+      m->ray_ev_done = false;
+    }
+    m->ray_timing = enable != 0;
   }
   return WS_OK;
 }

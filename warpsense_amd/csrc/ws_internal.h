@@ -289,6 +289,20 @@ struct ws_map
   bool mesh_timing = false;                    // ws_debug_mesh_timing: events around the count passes, the scan and the emit passes
   hipEvent_t mesh_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   bool mesh_ev_count = false, mesh_ev_emit = false; // the last call recorded events 0..2 / 3, 4
+  // ws_map_raycast (map_raycast.hip): the records of the last call, apart from the surface cloud's and the mesh's; allocated on first
+  // use and grown on demand.  ray_mu serialises the calls that use these buffers.
+  std::mutex ray_mu;
+  int32_t *ray_dirs = nullptr;                 // [ray_dirs_cap][3] staging of host directions
+  void *ray_rec = nullptr;                     // [ray_rec_cap] 16-byte records
+  int32_t *ray_grad = nullptr;                 // [ray_grad_cap][3]
+  size_t ray_dirs_cap = 0, ray_rec_cap = 0, ray_grad_cap = 0;
+  unsigned long long *ray_hits_dev = nullptr;  // records with range_mm >= 0
+  unsigned long long *ray_hits_host = nullptr; // pinned
+  size_t ray_n = 0;                            // rays of the last call
+  bool ray_has_grad = false;                   // the last call also wrote ray_grad
+  bool ray_timing = false;                     // ws_debug_raycast_timing: events around the upload, the march and the gradient
+  hipEvent_t ray_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  bool ray_ev_done = false;                    // the last call recorded them
   // The scan whose verdict (did its records fit the pool?) has not been looked at yet: ws_tsdf_update* return after the
   // launches, like the reference's update_tsdf (update_tsdf.cu:165); the next call that takes this map settles it first
   // (settle_tsdf: the verdict is in host-mapped memory ~0.35 ms after the launches) and repeats the scan if it was aborted.
@@ -437,6 +451,8 @@ int launch_surface_emit(ws_map *m, int which, const int32_t lo[3], const int32_t
 size_t mesh_scratch_bytes(uint64_t n_words);
 int launch_mesh_count(ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], uint32_t flags);
 int launch_mesh_emit(ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], uint32_t flags);
+// map_raycast.hip: the march and, with WS_RAYCAST_GRADIENT, the gradient pass (the hit count arrives in ws_map::ray_hits_host after a stream synchronise)
+int launch_raycast(ws_map *m, int which, const int32_t origin[3], const int32_t *dirs_dev, size_t n, int32_t max_range, uint32_t flags);
 int fill_u32(ws_context *ctx, uint32_t *dst, uint32_t value, int64_t n);
 int launch_box_fill(ws_map *m, const ws::MapParams &par, int which, const int32_t lo[3], const int32_t ext[3], uint32_t value, hipStream_t stream);
 int check_all_equal_host(const uint32_t *data, int64_t n, uint32_t value);

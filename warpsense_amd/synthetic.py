@@ -45,16 +45,21 @@ def lcg_noise(n: int, seed: int = 12345) -> np.ndarray:
     return out
 
 
-def os1_128_scan(sensor_mm=(0.0, 0.0, 0.0), rings: int = RINGS, azimuths: int = AZIMUTHS, seed: int = 12345,
-                 half_extents_mm=HALF_EXTENTS_MM, yaw_rad: float = 0.0) -> np.ndarray:
-    """Return an (rings*azimuths, 3) int32 array of points in the MAP frame (mm)."""
+def os1_128_dirs(rings: int = RINGS, azimuths: int = AZIMUTHS, yaw_rad: float = 0.0) -> np.ndarray:
+    """The pattern's (rings*azimuths, 3) float64 unit directions, ring-major."""
     i = np.arange(rings, dtype=np.float64)
     j = np.arange(azimuths, dtype=np.float64)
     el = np.deg2rad(-22.5 + 45.0 * i / max(rings - 1, 1))
     az = 2.0 * np.pi * j / azimuths + yaw_rad
     ce, se = np.cos(el)[:, None], np.sin(el)[:, None]
     ca, sa = np.cos(az)[None, :], np.sin(az)[None, :]
-    d = np.stack([ce * ca, ce * sa, np.broadcast_to(se, (rings, azimuths))], axis=-1).reshape(-1, 3)
+    return np.stack([ce * ca, ce * sa, np.broadcast_to(se, (rings, azimuths))], axis=-1).reshape(-1, 3)
+
+
+def os1_128_scan(sensor_mm=(0.0, 0.0, 0.0), rings: int = RINGS, azimuths: int = AZIMUTHS, seed: int = 12345,
+                 half_extents_mm=HALF_EXTENTS_MM, yaw_rad: float = 0.0) -> np.ndarray:
+    """Return an (rings*azimuths, 3) int32 array of points in the MAP frame (mm)."""
+    d = os1_128_dirs(rings, azimuths, yaw_rad)
     o = np.asarray(sensor_mm, dtype=np.float64)
     he = np.asarray(half_extents_mm, dtype=np.float64)
     with np.errstate(divide="ignore", invalid="ignore"):
