@@ -258,6 +258,48 @@ int ws_map_raycast_download(ws_map *map, void *records_host, int32_t *gradient_h
  * form), of the march and of the gradient pass of the last call */
 int ws_debug_raycast_timing(ws_map *map, int32_t enable, float ms_out[3]);
 
+/* Distance field of a device map: per voxel of a box the squared Euclidean distance, in voxels, to the nearest obstacle of that
+ * box -- the untruncated distance a planner, a collision checker or a cost map asks for, which the TSDF (truncated at tau) cannot
+ * give.  Integers only: the result is exact and the same bytes on every run.  "d2" is a squared distance in voxels.
+ *   box: inclusive world voxels [lo, hi] under the rules of ws_map_surface (both NULL: the whole window,
+ *     [pos - size/2, pos - size/2 + size - 1] per axis, each ring cell once; outside the window, hi < lo or more voxels than the
+ *     ring holds along an axis: WS_ERR_INVALID).  n = (nx, ny, nz) its extent.
+ *   classes of a voxel of the box, from its entry's two int16: VALID iff weight > 0; with WS_DISTANCE_ANY_WEIGHT iff weight != 0
+ *     (the registration's rule, as WS_MESH_ANY_WEIGHT).  class 2 = OCCUPIED: valid and value < 0 (the mesh's "inside");
+ *     class 1 = FREE: valid and value >= 0; class 0 = UNKNOWN: not valid.
+ *   sites: the occupied voxels of the box; with WS_DISTANCE_UNKNOWN_OCCUPIED also its unknown voxels (the conservative planner's
+ *     reading: what was never seen is not free).  Voxels outside the box are never sites: the field of a box is NOT the
+ *     restriction of the field of the window to it -- an obstacle just beyond a face of the box does not show (as with the rim of
+ *     the mesh of a box).
+ *   field: R = max_dist_vox, 1 <= R <= 255 (else WS_ERR_RANGE; R^2 = 65 025 fits 16 bits, which is what lets the passes over the
+ *     box carry 2 bytes per voxel).  For every voxel v of the box d2(v) = min(R², min over sites s of |v - s|²); no site in
+ *     reach: R².  A site has d2 = 0.
+ *   record, one uint32 per voxel: bits 0..23 d2, bits 30..31 the class, the rest 0.  Order: the dense box, x major, z fastest --
+ *     the order of ws_map_extract_box.  nx ny nz records.
+ *   WS_DISTANCE_COLUMNS (the 2-D cost map of a ground robot; the box's z range is the robot's height band): a column (x, y) is a
+ *     site iff any voxel of it in the box is a site; its class is that of a site's (2, or 0 if only unknown voxels made it a site),
+ *     else 1 if any voxel of it is free, else 0.  d2 is the 2-D squared distance between columns, same clamp.  nx ny records, y
+ *     fastest.
+ * A box without any site is WS_OK, every d2 = R².  More than 2^32 - 1 records: WS_ERR_RANGE.  Unknown flag bits: WS_ERR_INVALID.
+ * The minimum above defines the records; the implementation (three separable line passes) gets there another way and leaves
+ * them the same.
+ * Synchronises (*n_sites, may be NULL, receives the number of site voxels / site columns).  The result buffer belongs to the map,
+ * grows on demand, stays valid until the next ws_map_distance on it and is apart from those of ws_map_surface, ws_map_mesh and
+ * ws_map_raycast: none of the four calls invalidates another's result.  Read-only on the maps: may run next to ws_register_cloud
+ * under the reference's shared lock; calls that use the result buffer are serialised inside the library.  Nothing is allocated
+ * before the first call; an allocation that fails returns WS_ERR_HIP and leaves the map usable. */
+#define WS_DISTANCE_DEFAULT 0u
+#define WS_DISTANCE_ANY_WEIGHT 1u
+#define WS_DISTANCE_UNKNOWN_OCCUPIED 2u
+#define WS_DISTANCE_COLUMNS 4u
+int ws_map_distance(ws_map *map, int which, const int32_t lo[3], const int32_t hi[3], int32_t max_dist_vox, uint32_t flags, size_t *n_sites);
+const uint32_t *ws_map_distance_dev(const ws_map *map, size_t *n); /* device memory, n records; NULL before the first call (n == 0) */
+/* copies at most `capacity` records (a prefix) and always reports the total in *n_out; host may be NULL */
+int ws_map_distance_download(ws_map *map, uint32_t *host, size_t capacity, size_t *n_out);
+/* Measurement entry, as ws_debug_surface_timing: ms_out receives the device time of pass 0 (classification) and of the x, y and z
+ * line passes of the last call (under WS_DISTANCE_COLUMNS: pass 0, the x pass, the y pass, 0) */
+int ws_debug_distance_timing(ws_map *map, int32_t enable, float ms_out[4]);
+
 /* ------------------------------------------------------------------ TSDF update ---- */
 /* TSDFCuda::update_tsdf(scan_points, scanner_pos, up) — update_tsdf.cu:143-166.
  * xyz_host: n x 3 int32 (rmagine::Pointi AoS); scanner_pos in voxel units, up scaled by 32768.

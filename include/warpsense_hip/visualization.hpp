@@ -3,6 +3,7 @@
 //   local_map_cloud      publish_local_map           map.h:14-121    the surface cloud of a DEVICE map, over ws_map_surface
 //   local_map_mesh       (no counterpart: the reference sends the user to an offline mesher)   a triangle mesh, over ws_map_mesh
 //   local_map_raycast    (no counterpart: the reference leaves all viewing to RViz)            a predicted scan, over ws_map_raycast
+//   local_map_distance   (no counterpart: the reference has no distance field)                   a cost map, over ws_map_distance
 //   local_map_skeleton   publish_local_map_skeleton  map.h:175-227   the 24 end points of the window's line list (host only)
 //
 // The reference walks every voxel of a host map (after a whole-map download for the CUDA map, test/pcd2tsdf.cpp:134-137); here
@@ -107,6 +108,41 @@ inline RayCast local_map_raycast(cuda::TSDFCuda &tsdf, const rmagine::Pointi &or
   size_t got = 0;
   WS_CHECK(ws_map_raycast_download(tsdf.handle(), dirs.empty() ? nullptr : out.records.data(), with_gradient && !dirs.empty() ? &out.gradient.data()->x : nullptr,
                                    dirs.size(), &got));
+  return out;
+}
+
+struct DistanceField
+{
+  int32_t extent[3] = {0, 0, 0};  // nx, ny, nz of the box (nz = 1 for a column field)
+  std::vector<uint32_t> records;  // x major, z fastest (columns: y fastest): bits 0..23 d2 in voxels, bits 30..31 the class
+  size_t sites = 0;               // site voxels / site columns
+  static uint32_t d2(uint32_t rec) { return rec & 0xffffffu; }
+  static uint32_t cls(uint32_t rec) { return rec >> 30; } // 2 occupied, 1 free, 0 unknown
+};
+
+// The distance field of `which` (the rules: warpsense_hip.h at ws_map_distance) inside the inclusive world-voxel box [lo, hi] (both
+// nullptr: the whole window): per voxel the squared distance in voxels to the nearest occupied voxel of the box, clamped at
+// max_dist_vox squared.  unknown_occupied: never observed voxels are obstacles too; columns: the 2-D field over the (x, y) columns;
+// any_weight: voxels with a negative weight count as observed (WS_DISTANCE_ANY_WEIGHT).
+inline DistanceField local_map_distance(cuda::TSDFCuda &tsdf, int32_t max_dist_vox, bool unknown_occupied = false, bool columns = false,
+                                        bool any_weight = false, const rmagine::Pointi *lo = nullptr, const rmagine::Pointi *hi = nullptr,
+                                        int which = WS_MAP_AVG)
+{
+  DistanceField out;
+  const uint32_t flags = (any_weight ? WS_DISTANCE_ANY_WEIGHT : 0u) | (unknown_occupied ? WS_DISTANCE_UNKNOWN_OCCUPIED : 0u) | (columns ? WS_DISTANCE_COLUMNS : 0u);
+  WS_CHECK(ws_map_distance(tsdf.handle(), which, lo ? &lo->x : nullptr, hi ? &hi->x : nullptr, max_dist_vox, flags, &out.sites));
+  if (lo)
+  {
+    const int32_t *a = &lo->x, *b = &hi->x;
+    for (int k = 0; k < 3; ++k) out.extent[k] = b[k] - a[k] + 1;
+  }
+  else
+    WS_CHECK(ws_map_get_params(tsdf.handle(), which, out.extent, nullptr, nullptr));
+  if (columns) out.extent[2] = 1;
+  size_t n = 0;
+  WS_CHECK(ws_map_distance_download(tsdf.handle(), nullptr, 0, &n));
+  out.records.resize(n);
+  WS_CHECK(ws_map_distance_download(tsdf.handle(), n ? out.records.data() : nullptr, n, &n));
   return out;
 }
 

@@ -3,7 +3,7 @@ sliding TSDF map @ 5 cm, one MI355X): sensor clouds in float metres -> device pr
 (when the sensor moved > 0.3 m) -> Point-to-TSDF registration -> pose -> map shift (device-side slabs).
 
     python tools/replay_stream.py --map 1024 --scans 30 [--h5 /tmp/stream.h5] [--surface-ply DIR [--surface-every N]] [--mesh-ply DIR]
-                                   [--raycast-ply DIR]
+                                   [--raycast-ply DIR] [--distance-npy DIR [--distance-m M]]
 
 Prints one JSON line: scans/s over the stream and the mean per-stage times (the reference's RuntimeEvaluator
 forms "preprocess", "tsdf", "registration", "total")."""
@@ -38,6 +38,10 @@ def main():
     ap.add_argument("--raycast-ply", default=None, metavar="DIR", help="after every registered scan: the ray cast of the map from the registered pose "
                     "(TSDFMapping.raycast, the OS1-128 pattern, hits with normals) as binary little-endian PLY into DIR, and the median absolute "
                     "scan_residual of the scan printed")
+    ap.add_argument("--distance-npy", default=None, metavar="DIR", help="after every TSDF update: the 2-D cost map of the window (TSDFMapping.distance_field, "
+                    "columns=True: per (x, y) column the squared distance in voxels to the nearest column with an occupied voxel, and its class) as "
+                    "a uint32 .npy into DIR")
+    ap.add_argument("--distance-m", type=float, default=2.0, metavar="M", help="... clamped at M metres")
     ap.add_argument("--surface-every", type=int, default=10, metavar="N", help="... after every N-th scan")
     args = ap.parse_args()
     import warpsense_amd as W
@@ -67,6 +71,10 @@ def main():
     raycast = {"files": 0, "hits": 0, "median_abs_residual_mm": [], "seconds": 0.0}
     if args.raycast_ply:
         os.makedirs(args.raycast_ply, exist_ok=True)
+    distance = {"files": 0, "site_columns": 0, "seconds": 0.0}
+    if args.distance_npy:
+        os.makedirs(args.distance_npy, exist_ok=True)
+    updates_seen = app.n_updates
     for k, c in enumerate(clouds):
         if args.hz > 0.0:
             wait = t1 + k / args.hz - time.perf_counter()
@@ -86,6 +94,13 @@ def main():
             mesh["vertices"], mesh["faces"] = W.write_mesh_ply(os.path.join(args.mesh_ply, f"mesh_{k + 1:05d}.ply"), *app.gpu_.surface_mesh())
             mesh["files"] += 1
             mesh["seconds"] += time.perf_counter() - ts
+        if args.distance_npy and app.n_updates != updates_seen:
+            updates_seen = app.n_updates
+            ts = time.perf_counter()
+            np.save(os.path.join(args.distance_npy, f"costmap_{k + 1:05d}.npy"), app.gpu_.distance_field(max_dist_m=args.distance_m, columns=True))
+            distance["site_columns"] = app.gpu_.tsdf().avg_map().last_sites
+            distance["files"] += 1
+            distance["seconds"] += time.perf_counter() - ts
         if args.raycast_ply:
             ts = time.perf_counter()
             pose_m = app.pose_.astype(np.float64)
@@ -119,7 +134,8 @@ def main():
                       "terminate_write_back_s": t4 - t3, "h5": args.h5,
                       "surface_ply": surface if args.surface_ply else None,
                       "mesh_ply": mesh if args.mesh_ply else None,
-                      "raycast_ply": raycast if args.raycast_ply else None}))
+                      "raycast_ply": raycast if args.raycast_ply else None,
+                      "distance_npy": distance if args.distance_npy else None}))
 
 
 if __name__ == "__main__":

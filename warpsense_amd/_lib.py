@@ -32,10 +32,12 @@ EXPORTS = [
     "ws_map_surface", "ws_map_surface_records_dev", "ws_map_surface_marker_dev", "ws_map_surface_download", "ws_debug_surface_timing",
     "ws_map_mesh", "ws_map_mesh_vertices_dev", "ws_map_mesh_faces_dev", "ws_map_mesh_download", "ws_debug_mesh_timing",
     "ws_map_raycast", "ws_map_raycast_dev", "ws_map_raycast_records_dev", "ws_map_raycast_gradient_dev", "ws_map_raycast_download", "ws_debug_raycast_timing",
+    "ws_map_distance", "ws_map_distance_dev", "ws_map_distance_download", "ws_debug_distance_timing",
 ]
 WS_SURFACE_RECORDS, WS_SURFACE_MARKER = 0, 1
 WS_MESH_DEFAULT, WS_MESH_ANY_WEIGHT = 0, 1
 WS_RAYCAST_DEFAULT, WS_RAYCAST_ANY_WEIGHT, WS_RAYCAST_GRADIENT, WS_RAYCAST_TARGETS = 0, 1, 2, 4
+WS_DISTANCE_DEFAULT, WS_DISTANCE_ANY_WEIGHT, WS_DISTANCE_UNKNOWN_OCCUPIED, WS_DISTANCE_COLUMNS = 0, 1, 2, 4
 
 
 class WsError(RuntimeError):
@@ -148,6 +150,11 @@ def load() -> C.CDLL:
     L.ws_map_raycast_gradient_dev.restype = vp
     L.ws_map_raycast_download.argtypes = [vp, vp, vp, sz, P(sz)]
     L.ws_debug_raycast_timing.argtypes = [vp, i32, vp]
+    L.ws_map_distance.argtypes = [vp, C.c_int, vp, vp, i32, u32, P(sz)]
+    L.ws_map_distance_dev.argtypes = [vp, P(sz)]
+    L.ws_map_distance_dev.restype = vp
+    L.ws_map_distance_download.argtypes = [vp, vp, sz, P(sz)]
+    L.ws_debug_distance_timing.argtypes = [vp, i32, vp]
     L.ws_shift_begin.argtypes = [vp, vp, u32, P(vp)]
     L.ws_shift_count.argtypes = [vp]
     L.ws_shift_reserve.argtypes = [vp, C.c_uint64]

@@ -87,6 +87,22 @@ VERT = np.dtype([("x_mm", "<i4"), ("y_mm", "<i4"), ("z_mm", "<i4"), ("weight", "
 RAY = np.dtype([("x_mm", "<i4"), ("y_mm", "<i4"), ("z_mm", "<i4"), ("range_mm", "<i4")])
 
 
+def distance_class(rec):
+    """The class bits of ws_map_distance records: 2 occupied, 1 free, 0 unknown (uint8)."""
+    return (np.asarray(rec, dtype=np.uint32) >> np.uint32(30)).astype(np.uint8)
+
+
+def distance_d2(rec):
+    """The squared distance in voxels of ws_map_distance records (bits 0..23, uint32), clamped at max_dist_vox squared."""
+    return np.asarray(rec, dtype=np.uint32) & np.uint32(0xFFFFFF)
+
+
+def distance_mm(rec, res):
+    """The distance of ws_map_distance records in millimetres, res * sqrt(d2) as float32 -- the only float of the route, and it
+    is made on the host."""
+    return (np.float32(res) * np.sqrt(distance_d2(rec).astype(np.float32))).astype(np.float32)
+
+
 class _DeviceArray:
     """a library-owned device buffer as torch sees it (__cuda_array_interface__); `owner` keeps the handle alive"""
 
@@ -691,6 +707,48 @@ class DeviceMapMemWrapper:
         self.last_hits = int(hits.value)
         return rec, grad
 
+    def distance(self, lo=None, hi=None, max_dist_vox=20, unknown_occupied=False, columns=False, any_weight=False, device=False):
+        """The distance field of this map on the device (ws_map_distance; the rules are stated in include/warpsense_hip.h): per
+        voxel of the inclusive world-voxel box [lo, hi] (both None: the whole window) the squared Euclidean distance in voxels to
+        the nearest occupied voxel of the box (valid and value < 0; unknown_occupied: or never observed), clamped at
+        max_dist_vox squared (1 .. 255).  columns: the 2-D field over the (x, y) columns of the box.  any_weight: voxels with a
+        negative weight count as observed too (the rule of the registration).
+
+        Returns the records as a uint32 array shaped (nx, ny, nz), or (nx, ny) with columns: bits 0..23 the squared distance,
+        bits 30..31 the class (distance_d2, distance_class, distance_mm take them apart).  `last_sites` keeps the call's number
+        of site voxels / columns.
+        device=True: a torch int32 tensor of that shape on the GPU instead that ALIASES the library's buffer: valid until the next
+        distance() on this TSDFCuda, copy it (.clone()) to keep it."""
+        t = self._t
+        if (lo is None) != (hi is None):
+            raise WsError("distance: give both lo and hi, or neither")
+        flags = ((_lib.WS_DISTANCE_ANY_WEIGHT if any_weight else 0) | (_lib.WS_DISTANCE_UNKNOWN_OCCUPIED if unknown_occupied else 0)
+                 | (_lib.WS_DISTANCE_COLUMNS if columns else 0))
+        sites = C.c_size_t(0)
+        check(t._L.ws_map_distance(t.handle, self._which, _ptr(_i3(lo)) if lo is not None else None, _ptr(_i3(hi)) if hi is not None else None,
+                                   int(max_dist_vox), flags, C.byref(sites)), "ws_map_distance")
+        self.last_sites = int(sites.value)
+        if lo is not None:
+            shape = tuple(int(v) for v in (_i3(hi).astype(np.int64) - _i3(lo).astype(np.int64) + 1))
+        else:
+            size = np.zeros(3, np.int32)
+            check(t._L.ws_map_get_params(t.handle, self._which, _ptr(size), None, None), "ws_map_get_params")
+            shape = tuple(int(v) for v in size)
+        if columns:
+            shape = shape[:2]
+        n = int(np.prod(shape, dtype=np.int64))
+        cnt = C.c_size_t(0)
+        if device:
+            ptr = t._L.ws_map_distance_dev(t.handle, C.byref(cnt))
+            if int(cnt.value) != n:
+                raise WsError("distance: another call replaced the result")
+            return _device_tensor(ptr, shape, "<i4", t)
+        rec = np.empty(n, dtype=np.uint32)
+        check(t._L.ws_map_distance_download(t.handle, _ptr(rec), n, C.byref(cnt)), "ws_map_distance_download")
+        if int(cnt.value) != n:
+            raise WsError("distance: another call replaced the result before it was downloaded")
+        return rec.reshape(shape)
+
     def dev(self):
         return self._t.handle
 
@@ -1004,6 +1062,17 @@ class TSDFMapping:
         """A triangle mesh of the averaged map (DeviceMapMemWrapper.mesh on avg_map()), under the mapping's lock like a reader."""
         with self.mutex_:
             return self.tsdf_.avg_map().mesh(**kw)
+
+    def distance_field(self, lo=None, hi=None, max_dist_m=1.0, unknown_occupied=False, columns=False, any_weight=False):
+        """The distance field of the averaged map (DeviceMapMemWrapper.distance on avg_map()), under the mapping's lock like a
+        reader: how far every voxel of the box (None: the window) is from the nearest obstacle, up to max_dist_m metres
+        (rounded to whole millimetres, then ceil(mm / resolution) voxels, 1 .. 255).  columns: the 2-D cost map of a ground robot whose height band is the box's
+        z range.  Returns the uint32 records shaped (nx, ny, nz) or (nx, ny); distance_mm(rec, resolution) gives millimetres."""
+        mm = int(np.rint(float(max_dist_m) * 1000.0))
+        res = int(self.params_.map.resolution)
+        with self.mutex_:
+            return self.tsdf_.avg_map().distance(lo=lo, hi=hi, max_dist_vox=-(-mm // res), unknown_occupied=unknown_occupied, columns=columns,
+                                                 any_weight=any_weight)
 
     @staticmethod
     def raycast_rays(pose, dirs):

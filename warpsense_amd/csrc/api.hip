@@ -289,7 +289,8 @@ static int map_free(ws_map *m)
   void *ptrs[] = {m->data[0], m->data[1], m->vstate, m->az_hist, m->az_off, m->ray_bin, m->ray_order, m->fan_steps, m->rays, m->scan_dev, m->counters, m->tile_nsub,
                   m->tile_ent, m->tile_dirty, m->tile_list, m->block_stats, m->box_stage,
                   m->surf_col_cnt, m->surf_blk_tot, m->surf_blk_off, m->surf_total_dev, m->surf_rec, m->surf_marker,
-                  m->mesh_scratch, m->mesh_vert, m->mesh_face, m->ray_dirs, m->ray_rec, m->ray_grad, m->ray_hits_dev};
+                  m->mesh_scratch, m->mesh_vert, m->mesh_face, m->ray_dirs, m->ray_rec, m->ray_grad, m->ray_hits_dev,
+                  m->dist_rec, m->dist_plane, m->dist_sites_dev};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   if (m->surf_total_host) (void)hipHostFree(m->surf_total_host);
@@ -300,6 +301,9 @@ static int map_free(ws_map *m)
     if (e) (void)hipEventDestroy(e);
   if (m->ray_hits_host) (void)hipHostFree(m->ray_hits_host);
   for (hipEvent_t e : m->ray_ev)
+    if (e) (void)hipEventDestroy(e);
+  if (m->dist_sites_host) (void)hipHostFree(m->dist_sites_host);
+  for (hipEvent_t e : m->dist_ev)
     if (e) (void)hipEventDestroy(e);
   if (m->counters_host) (void)hipHostFree(m->counters_host);
   if (m->status_host) (void)hipHostFree(m->status_host);
@@ -990,6 +994,118 @@ int ws_debug_raycast_timing(ws_map *m, int32_t enable, float ms_out[3])
       m->ray_ev_done = false;
     }
     m->ray_timing = enable != 0;
+  }
+  return WS_OK;
+}
+
+// ---- distance field: the exact Euclidean transform of a device map, map_distance.hip (the rules are stated in warpsense_hip.h)
+int ws_map_distance(ws_map *m, int which, const int32_t lo[3], const int32_t hi[3], int32_t max_dist_vox, uint32_t flags, size_t *n_sites)
+{
+  const uint32_t known = WS_DISTANCE_ANY_WEIGHT | WS_DISTANCE_UNKNOWN_OCCUPIED | WS_DISTANCE_COLUMNS;
+  if (!m || (which != WS_MAP_AVG && which != WS_MAP_NEW) || (flags & ~known) || ((lo == nullptr) != (hi == nullptr)))
+    return invalid("ws_map_distance: bad argument");
+  if (max_dist_vox < 1 || max_dist_vox > 255)
+  {
+    set_error("ws_map_distance: max_dist_vox must be 1 .. 255 (its square is carried in 16 bits)");
+    return WS_ERR_RANGE;
+  }
+  WS_SETTLE(m);
+  std::lock_guard<std::mutex> lock(m->dist_mu);
+  const MapParams &p = m->par[which];
+  int32_t l[3], ext[3];
+  for (int k = 0; k < 3; ++k)
+  {
+    if (lo)
+    {
+      if (hi[k] < lo[k]) return invalid("ws_map_distance: hi < lo");
+      if (std::abs(lo[k] - p.pos[k]) > p.size[k] / 2 || std::abs(hi[k] - p.pos[k]) > p.size[k] / 2)
+        return invalid("ws_map_distance: box outside the local map window");
+      l[k] = lo[k];
+      ext[k] = hi[k] - lo[k] + 1;
+      if (ext[k] > p.size[k]) return invalid("ws_map_distance: box wraps onto itself (more voxels than the ring holds along an axis)");
+    }
+    else
+    {
+      l[k] = p.pos[k] - p.size[k] / 2;
+      ext[k] = p.size[k];
+    }
+  }
+  const bool columns = (flags & WS_DISTANCE_COLUMNS) != 0;
+  const uint64_t n64 = (uint64_t)ext[0] * (uint64_t)ext[1] * (uint64_t)(columns ? 1 : ext[2]); // ext[0] ext[1] < 2^31, ext[2] <= 2^20
+  if (n64 > 0xffffffffull)
+  {
+    set_error("ws_map_distance: more than 2^32 - 1 records");
+    return WS_ERR_RANGE;
+  }
+  const size_t n = (size_t)n64;
+  if (n_sites) *n_sites = 0;
+  m->dist_n = 0;
+  m->dist_ev_done = false;
+  hipStream_t s = m->ctx->stream;
+  if (!m->dist_sites_dev) WS_HIP(hipMalloc((void **)&m->dist_sites_dev, sizeof(unsigned long long)));
+  if (!m->dist_sites_host) WS_HIP(hipHostMalloc((void **)&m->dist_sites_host, sizeof(unsigned long long), hipHostMallocDefault));
+  if (m->dist_timing)
+    for (hipEvent_t &e : m->dist_ev)
+      if (!e) WS_HIP(hipEventCreate(&e));
+  if (n > m->dist_rec_cap || n > m->dist_plane_cap)
+  {
+    WS_HIP(hipStreamSynchronize(s));
+    int rc = surf_grow((void **)&m->dist_rec, &m->dist_rec_cap, n, sizeof(uint32_t));
+    if (rc == WS_OK) rc = surf_grow((void **)&m->dist_plane, &m->dist_plane_cap, n, 2 * sizeof(uint16_t)); // both planes
+    if (rc != WS_OK) return rc;
+  }
+  const int rc = launch_distance(m, which, l, ext, max_dist_vox, flags, n);
+  if (rc != WS_OK) return rc;
+  WS_HIP(hipStreamSynchronize(s));
+  m->dist_ev_done = m->dist_timing;
+  m->dist_n = n;
+  if (n_sites) *n_sites = (size_t)*m->dist_sites_host;
+  return map_take_error(m);
+}
+
+const uint32_t *ws_map_distance_dev(const ws_map *m, size_t *n)
+{
+  if (n) *n = m ? m->dist_n : 0;
+  return m && m->dist_n ? m->dist_rec : nullptr;
+}
+
+int ws_map_distance_download(ws_map *m, uint32_t *host, size_t capacity, size_t *n_out)
+{
+  if (!m || !n_out) return invalid("ws_map_distance_download: NULL argument");
+  std::lock_guard<std::mutex> lock(m->dist_mu);
+  *n_out = m->dist_n;
+  const size_t k = host ? std::min(capacity, m->dist_n) : 0;
+  if (k == 0) return WS_OK;
+  WS_HIP(hipMemcpyAsync(host, m->dist_rec, k * sizeof(uint32_t), hipMemcpyDeviceToHost, m->ctx->stream));
+  WS_HIP(hipStreamSynchronize(m->ctx->stream));
+  return WS_OK;
+}
+
+int ws_debug_distance_timing(ws_map *m, int32_t enable, float ms_out[4])
+{
+  if (!m) return invalid("ws_debug_distance_timing: map is NULL");
+  std::lock_guard<std::mutex> lock(m->dist_mu);
+  if (ms_out)
+  {
+    ms_out[0] = ms_out[1] = ms_out[2] = ms_out[3] = 0.f;
+    if (m->dist_timing && m->dist_ev[0] && m->dist_ev_done)
+    {
+      WS_HIP(hipStreamSynchronize(m->ctx->stream));
+      for (int k = 0; k < 4; ++k) WS_HIP(hipEventElapsedTime(&ms_out[k], m->dist_ev[k], m->dist_ev[k + 1]));
+    }
+  }
+  if (enable >= 0)
+  {
+    if (!enable || !m->dist_timing)
+    {
+      for (hipEvent_t &e : m->dist_ev)
+      {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+      }
+      m->dist_ev_done = false;
+    }
+    m->dist_timing = enable != 0;
   }
   return WS_OK;
 }

@@ -303,6 +303,18 @@ struct ws_map
   bool ray_timing = false;                     // ws_debug_raycast_timing: events around the upload, the march and the gradient
   hipEvent_t ray_ev[4] = {nullptr, nullptr, nullptr, nullptr};
   bool ray_ev_done = false;                    // the last call recorded them
+  // ws_map_distance (map_distance.hip): the records of the last call and the two 16-bit planes of its line passes, apart from the
+  // results of the three calls above; allocated on first use and grown on demand.  dist_mu serialises the calls that use them.
+  std::mutex dist_mu;
+  uint32_t *dist_rec = nullptr;                // [dist_rec_cap] one record per voxel (per column under WS_DISTANCE_COLUMNS)
+  uint16_t *dist_plane = nullptr;              // [2][dist_plane_cap] ping-pong planes of the running minimum
+  size_t dist_rec_cap = 0, dist_plane_cap = 0;
+  unsigned long long *dist_sites_dev = nullptr;  // site voxels / site columns of the last call
+  unsigned long long *dist_sites_host = nullptr; // pinned
+  size_t dist_n = 0;                           // records of the last call
+  bool dist_timing = false;                    // ws_debug_distance_timing: events around pass 0 and the line passes
+  hipEvent_t dist_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  bool dist_ev_done = false;                   // the last call recorded them
   // The scan whose verdict (did its records fit the pool?) has not been looked at yet: ws_tsdf_update* return after the
   // launches, like the reference's update_tsdf (update_tsdf.cu:165); the next call that takes this map settles it first
   // (settle_tsdf: the verdict is in host-mapped memory ~0.35 ms after the launches) and repeats the scan if it was aborted.
@@ -453,6 +465,8 @@ int launch_mesh_count(ws_map *m, int which, const int32_t lo[3], const int32_t e
 int launch_mesh_emit(ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], uint32_t flags);
 // map_raycast.hip: the march and, with WS_RAYCAST_GRADIENT, the gradient pass (the hit count arrives in ws_map::ray_hits_host after a stream synchronise)
 int launch_raycast(ws_map *m, int which, const int32_t origin[3], const int32_t *dirs_dev, size_t n, int32_t max_range, uint32_t flags);
+// map_distance.hip: pass 0 and the line passes over `n` records (the site count arrives in ws_map::dist_sites_host after a stream synchronise)
+int launch_distance(ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], int32_t R, uint32_t flags, size_t n);
 int fill_u32(ws_context *ctx, uint32_t *dst, uint32_t value, int64_t n);
 int launch_box_fill(ws_map *m, const ws::MapParams &par, int which, const int32_t lo[3], const int32_t ext[3], uint32_t value, hipStream_t stream);
 int check_all_equal_host(const uint32_t *data, int64_t n, uint32_t value);
