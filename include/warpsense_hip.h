@@ -117,7 +117,12 @@ int ws_map_download(ws_map *map, int which, int32_t size[3], int32_t pos[3], int
  * src/map/hdf5_local_map.cpp:53-118): instead of moving the WHOLE map through the host, only the slabs that leave
  * or enter the window are packed / unpacked.  Boxes are inclusive world-voxel ranges inside the current window;
  * the host buffer is dense, x major, z fastest.  The caller updates pos/offset with ws_map_set_params in between
- * (exactly the three steps of HDF5LocalMap::shift: save, move window, load).  Both synchronise. */
+ * (exactly the three steps of HDF5LocalMap::shift: save, move window, load).  Both synchronise.
+ * The window is pos - size/2 .. pos - size/2 + size - 1 per axis: every ring cell once.  For the reference's odd sizes that is
+ * pos - size/2 .. pos + size/2.  An even size (which this ABI admits, the reference's maps never have one) has no centre voxel:
+ * its window ends at pos + size/2 - 1, and world voxel pos + size/2 is the ring cell of pos - size/2 again.  A box passes if
+ * every corner is within size/2 of pos AND it has no more voxels along any axis than the ring has cells (otherwise
+ * WS_ERR_INVALID, nothing is moved): no box addresses a ring cell twice.  ws_map_surface, _mesh, _distance use the same rule. */
 int ws_map_extract_box(ws_map *map, int which, const int32_t lo[3], const int32_t hi[3], uint32_t *host_out);
 int ws_map_insert_box(ws_map *map, int which, const int32_t lo[3], const int32_t hi[3], const uint32_t *host_in);
 /* The same shift OFF the scan path (in the reference TSDFMapping::map_shift runs on its own thread and only blocks the
@@ -129,7 +134,12 @@ int ws_map_insert_box(ws_map *map, int which, const int32_t lo[3], const int32_t
  *   - overwrites, with ws_map_insert_box, those parts of the entering slabs the global map already holds (revisits),
  *   - and, typically on a worker thread: ws_shift_wait (blocks on the second stream only), ws_shift_slab for each
  *     leaving slab -> global map, ws_shift_end.
- * One shift can be in flight per map: ws_shift_begin fails with WS_ERR_INVALID while a ticket is open. */
+ * The window that moves is the one above (pos - size/2 .. pos - size/2 + size - 1, also for an even size): leaving and entering
+ * slabs are parts of it, never wider than `size` along an axis, and a slab's voxels are those of the window before its axis
+ * step that the window after it no longer holds.  A step of up to `size` voxels per axis is accepted, a larger one refused.
+ * new_pos equal to pos gives a ticket without slabs that is ended like any other.
+ * One shift can be in flight per map: ws_shift_begin and ws_shift_reserve fail with WS_ERR_INVALID while a ticket is open, and
+ * ws_shift_begin while new_map holds entries that have not been integrated.  A refusal leaves both maps as they were. */
 typedef struct ws_shift ws_shift;
 int ws_shift_begin(ws_map *map, const int32_t new_pos[3], uint32_t fill_entry, ws_shift **out);
 /* staging (device + pinned host) for shifts of up to `voxels` leaving voxels, so that no shift has to allocate */

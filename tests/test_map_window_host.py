@@ -1,0 +1,96 @@
+"""The world model of tests/window_model.py proved on the CPU: its walks through LocalMap.shift (pinned to the reference by
+test_oracle_pins.py::test_kat_ring_buffer_shift), and the walks themselves counted for what they are meant to contain.
+tests/test_gpu_map_window.py runs the same walks (same shapes, same seeds) through the device routes."""
+import numpy as np
+import pytest
+
+import window_model as M
+from window_model import WALKS
+
+TAU = 1000
+
+
+class HostRoute:
+    """LocalMap.shift on a host map with an in-memory GlobalMap"""
+
+    def __init__(self, size):
+        import warpsense_amd as W
+        self.W = W
+        self.lm = W.LocalMap(*size, TAU, 0)
+        assert tuple(self.lm.size) == tuple(size)
+
+    def insert(self, lo, hi, words):
+        lm = self.lm
+        ax = M.ring_axes(lm.size, lm.pos, lm.offset, lo, hi)
+        lm.data.reshape(tuple(int(s) for s in lm.size))[np.ix_(*ax)] = words.reshape(tuple(int(v) for v in hi - lo + 1))
+
+    def shift(self, world, new_pos):
+        self.lm.shift(new_pos)
+
+    def check(self, w):
+        lm = self.lm
+        assert np.array_equal(lm.pos, w.pos) and np.array_equal(lm.offset, w.offset())
+        assert np.array_equal(lm.data, w.ring())
+        w.check_chunks(lm.map_.chunks)
+
+
+@pytest.mark.parametrize("size,seed", WALKS)
+def test_model_matches_local_map_shift(size, seed):
+    import warpsense_amd as W
+    walk = M.make_walk(size, seed)
+    w = M.run_walk(size, walk, seed, HostRoute(size), W.pack_entry(TAU, 0))
+    assert np.all(w.pos == 0)
+    assert np.count_nonzero(w.world != w.default_raw) > 0 and np.count_nonzero(w.store != w.default_raw) > 0
+
+
+@pytest.mark.parametrize("size,seed", WALKS)
+def test_walks_contain_what_they_are_meant_to(size, seed):
+    """conditions on the INPUTS, counted from the walk itself"""
+    walk = M.make_walk(size, seed)
+    assert walk == M.make_walk(size, seed)  # deterministic
+    pos = np.asarray([(0, 0, 0)] + walk)
+    assert np.all(np.abs(np.diff(pos, axis=0)) <= np.asarray(size))  # every step is one the library admits
+    cov = M.walk_coverage(size, walk, seed)
+    for axis in range(3):
+        want = {d for d in (1, size[axis] // 2, size[axis] // 2 + 1, size[axis] - 1, size[axis]) if d >= 1}
+        assert want == {d for (a, d) in cov["steps"] if a == axis}
+    # each |d| out and back along its axis alone: at least twice
+    assert all(n >= 2 for n in cov["steps"].values()), cov["steps"]
+    assert cov["diagonal"] >= 3, cov       # three-axis steps
+    assert cov["corner"] >= 3, cov         # a corner enters with an earlier axis and leaves with a later one in the same shift
+    assert cov["revisit"] >= 5, cov        # the entering slab holds voxels written before they left
+    assert cov["origin"] >= 1, cov         # back at the origin: every voxel written on the way is in the window or the store
+    assert tuple(walk[-1]) == (0, 0, 0)
+    assert cov["seam_boxes"] >= 3, cov     # written boxes that lie across the ring seam of every axis
+    if max(size) > 64:
+        assert cov["chunk_borders"] >= 10 and cov["negative_chunks"] >= 10, cov
+
+
+def test_expected_slabs_partition_the_move():
+    """the slab boxes the GPU tests expect, against the model's own move: together the leaving boxes hold every voxel of the old
+    window that the new one lacks (and, for a corner, voxels that were in neither), and no box is wider than the ring"""
+    rng = np.random.default_rng(5)
+    for size in [(21, 17, 13), (16, 18, 20), (3, 19, 5), (4, 4, 4)]:
+        size = np.asarray(size)
+        for _ in range(40):
+            pos = rng.integers(-30, 31, 3)
+            new_pos = pos + np.array([rng.integers(-int(s), int(s) + 1) for s in size])
+            olo, ohi = M.window(size, pos)
+            nlo, nhi = M.window(size, new_pos)
+            blo, bhi = np.minimum(olo, nlo) - 1, np.maximum(ohi, nhi) + 1
+            shape = tuple(int(v) for v in bhi - blo + 1)
+            sl = lambda lo, hi: tuple(slice(int(lo[k] - blo[k]), int(hi[k] - blo[k]) + 1) for k in range(3))
+            inside = np.zeros(shape, dtype=bool)
+            inside[sl(olo, ohi)] = True
+            slabs = M.expected_slabs(size, pos, new_pos)
+            assert len(slabs) == int(np.count_nonzero(new_pos != pos))
+            for s in slabs:  # replay: what leaves was inside, what enters was not
+                for lo, hi in (s["leave"], s["enter"]):
+                    assert np.all(hi - lo + 1 <= size) and np.all(hi >= lo)
+                assert inside[sl(*s["leave"])].all()
+                inside[sl(*s["leave"])] = False
+                assert not inside[sl(*s["enter"])].any()
+                inside[sl(*s["enter"])] = True
+            want = np.zeros(shape, dtype=bool)
+            want[sl(nlo, nhi)] = True
+            assert np.array_equal(inside, want)

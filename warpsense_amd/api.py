@@ -1132,8 +1132,10 @@ class TSDFMapping:
                 d = int(diff[axis])
                 if d == 0:
                     continue
-                half = lm.size.astype(np.int64) // 2
-                start, end = lm.pos.astype(np.int64) - half, lm.pos.astype(np.int64) + half
+                # the window: every ring cell once (pos + size/2 for the odd sizes of LocalMap; an even size ends one voxel earlier)
+                half, size = lm.size.astype(np.int64) // 2, lm.size.astype(np.int64)
+                start = lm.pos.astype(np.int64) - half
+                end = start + size - 1
                 if d > 0:
                     end[axis] = start[axis] + d - 1
                 else:
@@ -1144,7 +1146,8 @@ class TSDFMapping:
                 view = lm.device_map()
                 avg.update_params(view)
                 new.update_params(view)  # new_map is (tau, 0) everywhere: only its window moves
-                start, end = lm.pos.astype(np.int64) - half, lm.pos.astype(np.int64) + half
+                start = lm.pos.astype(np.int64) - half
+                end = start + size - 1
                 if d > 0:
                     start[axis] = end[axis] - (d - 1)
                 else:
@@ -1229,7 +1232,7 @@ class TSDFMapping:
             # a later axis step moves the window again: only the part of the slab still inside the FINAL window counts
             half = lm.size.astype(np.int64) // 2
             a = np.maximum(lo.astype(np.int64), lm.pos.astype(np.int64) - half)
-            b = np.minimum(hi.astype(np.int64), lm.pos.astype(np.int64) + half)
+            b = np.minimum(hi.astype(np.int64), lm.pos.astype(np.int64) - half + lm.size.astype(np.int64) - 1)
             if np.any(a > b):
                 continue
             c0, c1 = np.floor_divide(a, cs), np.floor_divide(b, cs)
@@ -1269,8 +1272,8 @@ class TSDFMapping:
         lm, avg = self.local_map_, self.tsdf_.avg_map()
         cs = GlobalMap.CHUNK_SIZE
         with self.mutex_:
-            half = lm.size.astype(np.int64) // 2
-            lo, hi = lm.pos.astype(np.int64) - half, lm.pos.astype(np.int64) + half
+            lo = lm.pos.astype(np.int64) - lm.size.astype(np.int64) // 2
+            hi = lo + lm.size.astype(np.int64) - 1
             if box_lo is not None:
                 lo = np.maximum(lo, np.asarray(box_lo, dtype=np.int64))
             if box_hi is not None:

@@ -535,6 +535,9 @@ static int box_check(ws_map *m, int which, const int32_t lo[3], const int32_t hi
     if (std::abs(lo[k] - p.pos[k]) > p.size[k] / 2 || std::abs(hi[k] - p.pos[k]) > p.size[k] / 2)
       return invalid("box transfer: box outside the local map window");
     ext[k] = hi[k] - lo[k] + 1;
+    // (an even size admits pos - size/2 .. pos + size/2: size + 1 voxels, the first and the last the same ring cell -- two lanes
+    // of an insert would store to one address)
+    if (ext[k] > p.size[k]) return invalid("box transfer: box wraps onto itself (more voxels than the ring holds along an axis)");
     cnt *= (size_t)ext[k];
   }
   *n = cnt;
@@ -1148,7 +1151,9 @@ int ws_shift_begin(ws_map *m, const int32_t new_pos[3], uint32_t fill_entry, ws_
   ws_shift *sh = new (std::nothrow) ws_shift();
   if (!sh) return invalid("ws_shift_begin: out of host memory");
   sh->map = m;
-  // plan: per axis, like HDF5LocalMap::shift (hdf5_local_map.cpp:53-118), with the window as it is when that axis moves
+  // plan: per axis, like HDF5LocalMap::shift (hdf5_local_map.cpp:53-118), with the window as it is when that axis moves.
+  // The window is pos - size/2 .. pos - size/2 + size - 1, every ring cell once: the reference's pos + size/2 for its odd sizes;
+  // for an even size pos + size/2 would be the ring cell of pos - size/2 again, filed under a second world position
   int32_t pos[3] = {p0.pos[0], p0.pos[1], p0.pos[2]};
   size_t total = 0;
   for (int axis = 0; axis < 3; ++axis)
@@ -1165,7 +1170,7 @@ int ws_shift_begin(ws_map *m, const int32_t new_pos[3], uint32_t fill_entry, ws_
     for (int k = 0; k < 3; ++k)
     {
       start[k] = pos[k] - p0.size[k] / 2;
-      end[k] = pos[k] + p0.size[k] / 2;
+      end[k] = start[k] + p0.size[k] - 1;
     }
     if (d > 0)
       end[axis] = start[axis] + (int32_t)d - 1;
@@ -1177,7 +1182,7 @@ int ws_shift_begin(ws_map *m, const int32_t new_pos[3], uint32_t fill_entry, ws_
     for (int k = 0; k < 3; ++k)
     {
       start[k] = pos[k] - p0.size[k] / 2;
-      end[k] = pos[k] + p0.size[k] / 2;
+      end[k] = start[k] + p0.size[k] - 1;
     }
     if (d > 0)
       start[axis] = end[axis] - ((int32_t)d - 1);
