@@ -376,6 +376,24 @@ int ws_register_cloud(ws_reg *reg, const ws_map *map, const float T_in[16], int3
                       float T_out[16], int32_t *iterations);
 int ws_reg_set_loop(ws_reg *reg, int mode /* WS_REG_LOOP_* */);
 
+/* K registrations of the prepared cloud against one map, each from its own start pose, in one launch.
+ * T_in, T_out: k x 16 floats, column-major; iterations, e_out, c_out: k each (the last three may be NULL).
+ * Result k is bit for bit what ws_register_cloud(reg, map, T_in + 16 k, ...) returns alone;
+ * e_out[k], c_out[k] are e and c of ws_reg_iterate at T_out + 16 k.  k == 0 is WS_OK.  Synchronises.
+ * One workgroup runs the whole Gauss-Newton loop of one start pose: no exchange between workgroups, nothing that must be
+ * resident together, so k may exceed the number of compute units.  `flags` select the points exactly as for ws_register_cloud.
+ * WS_ERR_INVALID: NULL reg / map, NULL T_in / T_out with k > 0, map_resolution < 1.  A living resident server of ws_reg_iterate
+ * is asked to leave first.  The call leaves the single route alone: the handle's loop mode, the sums ws_debug_reg_sums
+ * reports and the state ws_reg_poll reads are those of the last ws_register_cloud.  The per-pose device records live in `reg`
+ * and grow on demand. */
+int ws_register_cloud_batch(ws_reg *reg, const ws_map *map, const float *T_in, size_t k, int32_t max_iterations,
+                            float it_weight_gradient, float epsilon, int32_t map_resolution, uint32_t flags,
+                            float *T_out, int32_t *iterations, int32_t *e_out, int32_t *c_out);
+/* Host only: the best hypothesis of a batch.  Among those with c[i] >= min_count the one with the smallest e[i] / c[i],
+ * compared exactly as e[a] * c[b] < e[b] * c[a] in int64; ties: larger c, then lower index.  *best = -1 if none.
+ * (e is a sum of |value|, so e >= 0; a hypothesis with c[i] <= 0 has no mean and is never chosen.) */
+int ws_reg_batch_best(const int32_t *e, const int32_t *c, size_t k, int32_t min_count, int64_t *best);
+
 /* Building blocks of the same loop for point-sharded multi-GPU runs: every rank owns the
  * points [first, first+count) of the prepared cloud, accumulates its 44 int64 partial sums
  * (h[36] column-major, g[6], e, c) into sums_dev, the caller all-reduces sums_dev (RCCL), then every

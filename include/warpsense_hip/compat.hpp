@@ -360,6 +360,28 @@ public:
     if (iterations) *iterations = it;
     return out;
   }
+  // K registrations of the prepared cloud in one launch, one per start pose (ws_register_cloud_batch): poses[k] and iterations[k]
+  // are what register_cloud returns from pretransforms[k] alone, e[k] and c[k] what perform_registration returns at poses[k]
+  struct BatchResult
+  {
+    std::vector<rmagine::Matrix4x4f> poses;
+    std::vector<int32_t> iterations, e, c;
+  };
+  BatchResult register_cloud_batch(const DeviceMap *map_dev, const std::vector<rmagine::Matrix4x4f> &pretransforms, int max_iterations,
+                                   float it_weight_gradient, float epsilon, int map_resolution)
+  {
+    static_assert(sizeof(rmagine::Matrix4x4f) == 16 * sizeof(float), "k x 16 floats, column-major");
+    const size_t k = pretransforms.size();
+    BatchResult out;
+    out.poses.resize(k);
+    out.iterations.resize(k);
+    out.e.resize(k);
+    out.c.resize(k);
+    WS_CHECK(ws_register_cloud_batch(reg_, reinterpret_cast<const ws_map *>(map_dev), k ? &pretransforms[0].data[0][0] : nullptr, k, max_iterations,
+                                     it_weight_gradient, epsilon, map_resolution, flags_, k ? &out.poses[0].data[0][0] : nullptr,
+                                     out.iterations.data(), out.e.data(), out.c.data()));
+    return out;
+  }
   void set_flags(uint32_t flags) { flags_ = flags; }
 
   // ---- point-sharded registration over several GPUs (one process per GPU, the map replicated, every rank has prepared the

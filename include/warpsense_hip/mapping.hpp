@@ -96,6 +96,15 @@ public:
     return reg_->register_cloud(tsdf_->device_map(), pretransform, params_.max_iterations, params_.it_weight_gradient,
                                 params_.epsilon, params_.map_resolution, &last_iterations_);
   }
+  // register_cloud from every pose of `pretransforms` in one launch (re-localisation, a doubtful pre-transform, a pose lattice);
+  // rank the results with warpsense::batch_best
+  RegistrationCuda::BatchResult register_candidates(std::vector<rmagine::Pointi> &cloud, const std::vector<rmagine::Matrix4x4f> &pretransforms)
+  {
+    reg_->prepare_registration(cloud);
+    std::shared_lock lock(mutex_);
+    return reg_->register_cloud_batch(tsdf_->device_map(), pretransforms, params_.max_iterations, params_.it_weight_gradient, params_.epsilon,
+                                      params_.map_resolution);
+  }
   // The reference's OWN loop shape (tsdf_registration.cpp:55-92), for a caller that is relinked and not changed: one
   // perform_registration per iteration -- launch, 44 sums back to the host -- then the 6x6 solve (the reference: Eigen's
   // hf.inverse() * gf; here the elimination of oracle/ws_oracle.c:wso_solve6, so that the poses are the oracle's bit for bit),
@@ -231,3 +240,15 @@ private:
 };
 
 } // namespace cuda
+
+namespace warpsense
+{
+// the best hypothesis of a batch (ws_reg_batch_best): among those that matched at least min_count points the smallest mean error
+// e / c, compared exactly; ties: larger c, then lower index.  -1 if none.
+inline long long batch_best(const std::vector<int32_t> &e, const std::vector<int32_t> &c, int32_t min_count)
+{
+  int64_t best = -1;
+  WS_CHECK(ws_reg_batch_best(e.data(), c.data(), e.size() < c.size() ? e.size() : c.size(), min_count, &best));
+  return (long long)best;
+}
+} // namespace warpsense

@@ -18,6 +18,34 @@ import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
 
+def relocalize_after_kidnap(app, cloud, args, true_position_mm):
+    """The tracked pose is lost: put a wrong one in its place, register the scan (in the sensor frame) from every pose of the lattice
+    around it in one launch, take the best, report, and hand the recovered pose back to the tracker."""
+    import warpsense_amd as W
+    a = np.deg2rad(args.kidnap_yaw)
+    wrong = app.pose_.astype(np.float64)
+    wrong[:3, :3] = np.array([[np.cos(a), -np.sin(a), 0.0], [np.sin(a), np.cos(a), 0.0], [0.0, 0.0, 1.0]]) @ wrong[:3, :3]
+    wrong[0, 3] += 1000.0 * args.kidnap_offset[0]
+    wrong[1, 3] += 1000.0 * args.kidnap_offset[1]
+    app.pose_ = wrong.astype(np.float32)
+    pts = app.pre_.preprocess(cloud, np.eye(4, dtype=np.float32), app.params_.map.resolution)  # the scan where the sensor is the origin
+    t0 = time.perf_counter()
+    radius, step, yaw_range, yaw_step = args.kidnap_lattice
+    pose, best, table = app.gpu_.relocalize(pts, app.pose_, radius, step, yaw_range, yaw_step)
+    dt = time.perf_counter() - t0
+    app.pose_ = pose.astype(np.float32)
+    out = {"scan": args.kidnap, "candidates": int(len(table["e"])), "chosen": int(best), "seconds": dt,
+           "chosen_start_error_mm": float(np.linalg.norm(table["start"][best][:3, 3] - true_position_mm)),
+           "wrong_pose_error_mm": float(np.linalg.norm(wrong[:3, 3] - true_position_mm)),
+           "recovered_pose_error_mm": float(np.linalg.norm(pose[:3, 3] - true_position_mm)),
+           "recovered_yaw_error_deg": float(np.rad2deg(np.arctan2(pose[1, 0], pose[0, 0]))),
+           "iterations": int(table["iterations"][best]), "mean_error": float(table["e"][best]) / max(int(table["c"][best]), 1)}
+    print(f"kidnap at scan {args.kidnap}: candidate {best} of {out['candidates']} in {1000.0 * dt:.1f} ms, "
+          f"{out['recovered_pose_error_mm']:.1f} mm / {out['recovered_yaw_error_deg']:.2f} deg from the true pose "
+          f"(the wrong pose: {out['wrong_pose_error_mm']:.1f} mm / {args.kidnap_yaw:.2f} deg)", file=sys.stderr)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--map", type=int, default=1024)
@@ -43,6 +71,12 @@ def main():
                     "a uint32 .npy into DIR")
     ap.add_argument("--distance-m", type=float, default=2.0, metavar="M", help="... clamped at M metres")
     ap.add_argument("--surface-every", type=int, default=10, metavar="N", help="... after every N-th scan")
+    ap.add_argument("--kidnap", type=int, default=0, metavar="N", help="at scan N (1-based) replace the tracked pose by a wrong one (--kidnap-offset, "
+                    "--kidnap-yaw), re-localise with TSDFRegistration.relocalize on a pose lattice around it (one launch for all candidates), "
+                    "print the chosen candidate and its distance to the stream's true pose, and go on tracking from it")
+    ap.add_argument("--kidnap-offset", type=float, nargs=2, default=(0.8, -0.4), metavar=("DX", "DY"), help="... offset of the wrong pose in metres")
+    ap.add_argument("--kidnap-yaw", type=float, default=20.0, metavar="DEG", help="... and its yaw error")
+    ap.add_argument("--kidnap-lattice", type=float, nargs=4, default=(1.2, 0.4, 30.0, 10.0), metavar=("RADIUS_M", "STEP_M", "YAW_RANGE", "YAW_STEP"))
     args = ap.parse_args()
     import warpsense_amd as W
     from warpsense_amd import synthetic as S
@@ -75,12 +109,15 @@ def main():
     if args.distance_npy:
         os.makedirs(args.distance_npy, exist_ok=True)
     updates_seen = app.n_updates
+    kidnap = None
     for k, c in enumerate(clouds):
         if args.hz > 0.0:
             wait = t1 + k / args.hz - time.perf_counter()
             if wait > 0.0:
                 time.sleep(wait)
         tb = time.perf_counter()
+        if args.kidnap and k + 1 == args.kidnap:
+            kidnap = relocalize_after_kidnap(app, c, args, np.array([1000.0 * args.step * k, 500.0 * args.step * k, 0.0]))
         app.cloud_callback(c)
         busy += time.perf_counter() - tb
         if args.surface_ply and (k + 1) % max(args.surface_every, 1) == 0:
@@ -135,7 +172,8 @@ def main():
                       "surface_ply": surface if args.surface_ply else None,
                       "mesh_ply": mesh if args.mesh_ply else None,
                       "raycast_ply": raycast if args.raycast_ply else None,
-                      "distance_npy": distance if args.distance_npy else None}))
+                      "distance_npy": distance if args.distance_npy else None,
+                      "kidnap": kidnap}))
 
 
 if __name__ == "__main__":

@@ -33,6 +33,7 @@ EXPORTS = [
     "ws_map_mesh", "ws_map_mesh_vertices_dev", "ws_map_mesh_faces_dev", "ws_map_mesh_download", "ws_debug_mesh_timing",
     "ws_map_raycast", "ws_map_raycast_dev", "ws_map_raycast_records_dev", "ws_map_raycast_gradient_dev", "ws_map_raycast_download", "ws_debug_raycast_timing",
     "ws_map_distance", "ws_map_distance_dev", "ws_map_distance_download", "ws_debug_distance_timing",
+    "ws_register_cloud_batch", "ws_reg_batch_best",
 ]
 WS_SURFACE_RECORDS, WS_SURFACE_MARKER = 0, 1
 WS_MESH_DEFAULT, WS_MESH_ANY_WEIGHT = 0, 1
@@ -207,6 +208,8 @@ def load() -> C.CDLL:
     L.ws_reg_peer_disconnect.argtypes = [vp]
     L.ws_reg_peer_reset.argtypes = [vp]
     L.ws_register_cloud_peers.argtypes = [vp, vp, sz, sz, vp, i32, C.c_float, C.c_float, i32, u32, vp, P(i32)]
+    L.ws_register_cloud_batch.argtypes = [vp, vp, vp, sz, i32, C.c_float, C.c_float, i32, u32, vp, vp, vp, vp]
+    L.ws_reg_batch_best.argtypes = [vp, vp, sz, i32, P(i64)]
     L.ws_prof_enable.argtypes = [vp, u32]
     L.ws_prof_read.argtypes = [vp, C.c_int, P(C.c_double), P(i64)]
     L.ws_prof_reset.argtypes = [vp]

@@ -901,6 +901,20 @@ class RegistrationCuda:
               "ws_register_cloud")
         return np.array(out_c, dtype=np.float32).reshape(4, 4).T.copy(), it.value
 
+    def register_cloud_batch(self, map_dev, poses, max_iterations, it_weight_gradient, epsilon, map_resolution):
+        """K registrations of the prepared cloud, one per start pose, in one launch (ws_register_cloud_batch).
+        poses: (k, 4, 4).  Returns (T[k, 4, 4] float32, iterations[k], e[k], c[k]): pose k and its iteration count are what
+        register_cloud returns from poses[k] alone; e[k], c[k] are perform_registration's e and c at T[k]."""
+        P = np.asarray(poses, dtype=np.float32).reshape(-1, 4, 4)
+        k = int(P.shape[0])
+        T_in = np.ascontiguousarray(P.transpose(0, 2, 1)).reshape(k, 16)
+        T_out = np.zeros((k, 16), dtype=np.float32)
+        it, e, c = (np.zeros(k, dtype=np.int32) for _ in range(3))
+        check(self._L.ws_register_cloud_batch(self.handle, map_dev, _ptr(T_in), k, int(max_iterations), C.c_float(it_weight_gradient),
+                                              C.c_float(epsilon), int(map_resolution), self.flags, _ptr(T_out), _ptr(it), _ptr(e), _ptr(c)),
+              "ws_register_cloud_batch")
+        return np.ascontiguousarray(T_out.reshape(k, 4, 4).transpose(0, 2, 1)), it, e, c
+
     def last_sums(self):
         """(h 6x6 int64, g[6], e, c) the last Gauss-Newton update of the last register_cloud was made from (test entry)"""
         out = np.empty(44, dtype=np.int64)
@@ -921,6 +935,46 @@ class RegistrationCuda:
             self.close()
         except Exception:
             pass
+
+
+def batch_best(e, c, min_count: int = 1) -> int:
+    """Index of the best hypothesis of a batch (ws_reg_batch_best): among those with c[i] >= min_count the smallest mean error
+    e[i] / c[i], compared exactly; ties: larger c, then lower index.  -1 if none qualifies."""
+    e = np.ascontiguousarray(e, dtype=np.int32).reshape(-1)
+    c = np.ascontiguousarray(c, dtype=np.int32).reshape(-1)
+    if e.shape != c.shape:
+        raise ValueError("batch_best: e and c differ in length")
+    best = C.c_int64(-1)
+    check(_lib.load().ws_reg_batch_best(_ptr(e), _ptr(c), int(e.shape[0]), int(min_count), C.byref(best)), "ws_reg_batch_best")
+    return int(best.value)
+
+
+def candidate_poses(guess, radius_m: float, step_m: float, yaw_range_deg: float = 0.0, yaw_step_deg: float = 0.0) -> np.ndarray:
+    """The local pose lattice of TSDFRegistration.relocalize around `guess` (4x4, translation in mm): (n, 4, 4) float32.
+
+    x and y offsets i * step_m, |i| <= floor(radius_m / step_m), on a square grid in the map frame; yaw offsets j * yaw_step_deg,
+    |j| <= floor(yaw_range_deg / yaw_step_deg), about the map's z axis through the guess's own position (the rotation is
+    multiplied from the left, the translation keeps its place).  A step <= 0 leaves that axis at the guess.  Candidate 0 is the
+    guess itself, unchanged; the others follow row-major (x slowest, then y, yaw fastest, each from its most negative offset
+    upwards) without the node of all-zero offsets, whose place the guess has taken: (2 nx + 1)(2 ny + 1)(2 nyaw + 1) poses.
+    Computed in float64, rounded once to float32."""
+    G = np.asarray(guess, dtype=np.float64).reshape(4, 4)
+    n_xy = int(np.floor(radius_m / step_m + 1e-9)) if step_m > 0 and radius_m > 0 else 0
+    n_yaw = int(np.floor(yaw_range_deg / yaw_step_deg + 1e-9)) if yaw_step_deg > 0 and yaw_range_deg > 0 else 0
+    out = [G.copy()]
+    for ix in range(-n_xy, n_xy + 1):
+        for iy in range(-n_xy, n_xy + 1):
+            for iw in range(-n_yaw, n_yaw + 1):
+                if ix == 0 and iy == 0 and iw == 0:
+                    continue
+                a = np.deg2rad(iw * float(yaw_step_deg))
+                Rz = np.array([[np.cos(a), -np.sin(a), 0.0], [np.sin(a), np.cos(a), 0.0], [0.0, 0.0, 1.0]])
+                Tc = G.copy()
+                Tc[:3, :3] = Rz @ G[:3, :3]
+                Tc[0, 3] = G[0, 3] + ix * float(step_m) * 1000.0
+                Tc[1, 3] = G[1, 3] + iy * float(step_m) * 1000.0
+                out.append(Tc)
+    return np.stack(out).astype(np.float32)
 
 
 class DevicePoints:
@@ -1304,3 +1358,28 @@ class TSDFRegistration(TSDFMapping):
                                              r.epsilon, m.resolution)
         self.last_iterations = it
         return T
+
+    def register_candidates(self, cloud, poses):
+        """register_cloud from every pose of `poses` (k, 4, 4) in one launch: (T[k, 4, 4], iterations[k], e[k], c[k]); rank them
+        with batch_best(e, c, min_count)."""
+        self.reg_.prepare_registration(cloud)
+        r, m = self.params_.registration, self.params_.map
+        with self.mutex_:
+            return self.reg_.register_cloud_batch(self.tsdf_.device_map(), poses, r.max_iterations, r.it_weight_gradient, r.epsilon,
+                                                  m.resolution)
+
+    def relocalize(self, cloud, guess, radius_m, step_m, yaw_range_deg=0.0, yaw_step_deg=0.0, min_fraction=0.5):
+        """Re-localise inside the map: register `cloud` from every pose of candidate_poses(guess, ...) and keep the one whose final
+        mean error is smallest among those that matched at least min_fraction of the points.
+        Returns (best_pose 4x4 float32, best_index, table) with table = dict(start=, pose=, iterations=, e=, c=) over all candidates;
+        raises WsError if no candidate reaches min_fraction."""
+        poses = candidate_poses(guess, radius_m, step_m, yaw_range_deg, yaw_step_deg)
+        T, it, e, c = self.register_candidates(cloud, poses)
+        n = int(cloud.shape[0])
+        min_count = max(1, int(np.ceil(float(min_fraction) * n)))
+        best = batch_best(e, c, min_count)
+        table = {"start": poses, "pose": T, "iterations": it, "e": e, "c": c}
+        if best < 0:
+            raise WsError(f"relocalize: none of the {len(poses)} candidates matched {min_count} of {n} points (best count {int(c.max()) if len(c) else 0})")
+        self.last_iterations = int(it[best])
+        return T[best].copy(), best, table

@@ -1438,6 +1438,7 @@ int ws_reg_destroy(ws_reg *r)
   if (r->iter_host) (void)hipHostFree(r->iter_host);
   if (r->grid_bar) (void)hipFree(r->grid_bar);
   if (r->pass_arrived) (void)hipFree(r->pass_arrived);
+  if (r->batch_host) (void)hipHostFree(r->batch_host);
   (void)ws_reg_peer_disconnect(r);
   if (r->mailbox) (void)hipFree(r->mailbox);
   if (r->peer_block_dev) (void)hipFree(r->peer_block_dev);
@@ -1491,6 +1492,8 @@ int ws_reg_create(ws_context *ctx, size_t max_points, ws_reg **out)
   {
     if (const char *env = std::getenv("WS_REG_SERVER")) r->srv_enabled = std::atoi(env) != 0;
     if (const char *env = std::getenv("WS_REG_SERVER_IDLE_US")) r->srv_idle_us = (uint32_t)std::max(1, std::atoi(env));
+    r->batch_variant = reg_batch_default_variant();
+    if (const char *env = std::getenv("WS_REG_BATCH_VARIANT")) r->batch_variant = std::atoi(env) & 1;
   }
   if (rc != WS_OK || e != hipSuccess)
   {
@@ -1763,6 +1766,65 @@ int ws_register_cloud(ws_reg *r, const ws_map *m, const float T_in[16], int32_t 
   if (rc != WS_OK) return rc;
   if (iterations) *iterations = iters;
   return map_take_error(const_cast<ws_map *>(m));
+}
+
+// ------------------------------------------------------------------ many start poses, one launch
+static int reg_batch_reserve(ws_reg *r, size_t k)
+{
+  if (k <= r->batch_cap) return WS_OK;
+  WS_HIP(hipStreamSynchronize(r->ctx->stream)); // (every batch call has waited for its kernel: nothing reads the old block)
+  if (r->batch_host) WS_HIP(hipHostFree(r->batch_host));
+  r->batch_host = r->batch_dev = nullptr;
+  r->batch_cap = 0;
+  size_t cap = 64;
+  while (cap < k) cap *= 2;
+  WS_HIP(hipHostMalloc(&r->batch_host, cap * reg_batch_record_bytes(), hipHostMallocMapped));
+  WS_HIP(hipHostGetDevicePointer(&r->batch_dev, r->batch_host, 0));
+  r->batch_cap = cap;
+  return WS_OK;
+}
+
+int ws_register_cloud_batch(ws_reg *r, const ws_map *m, const float *T_in, size_t k, int32_t max_iterations, float it_weight_gradient,
+                            float epsilon, int32_t res, uint32_t flags, float *T_out, int32_t *iterations, int32_t *e_out, int32_t *c_out)
+{
+  if (!r || !m || (k && (!T_in || !T_out))) return invalid("ws_register_cloud_batch: NULL argument");
+  if (res < 1) return invalid("ws_register_cloud_batch: map_resolution must be positive");
+  if (k > 0x7fffffffu) return invalid("ws_register_cloud_batch: more than 2^31 - 1 start poses");
+  // (a living resident server of ws_reg_iterate is asked to leave here: the launch below is ordered behind it on the stream and
+  // must not wait for its idle time to run out)
+  WS_SETTLE(m);
+  if (k == 0) return map_take_error(const_cast<ws_map *>(m));
+  int rc = reg_batch_reserve(r, k);
+  if (rc != WS_OK) return rc;
+  for (size_t i = 0; i < k; ++i) reg_batch_write(r->batch_host, i, T_in + 16 * i);
+  // One launch, nothing copied by the runtime: the start records are read from, and the results written to, host-mapped memory.
+  // Neither the state buffers, the loop mode nor the sums of the single route are touched.
+  rc = launch_reg_batch(r, m, res, flags, k, max_iterations, it_weight_gradient, epsilon);
+  if (rc != WS_OK) return rc;
+  WS_HIP(hipStreamSynchronize(r->ctx->stream));
+  for (size_t i = 0; i < k; ++i)
+    reg_batch_read(r->batch_host, k, i, T_out + 16 * i, iterations ? iterations + i : nullptr, e_out ? e_out + i : nullptr, c_out ? c_out + i : nullptr);
+  return map_take_error(const_cast<ws_map *>(m));
+}
+
+int ws_reg_batch_best(const int32_t *e, const int32_t *c, size_t k, int32_t min_count, int64_t *best)
+{
+  if (!best || (k && (!e || !c))) return invalid("ws_reg_batch_best: NULL argument");
+  int64_t b = -1;
+  for (size_t i = 0; i < k; ++i)
+  {
+    if (c[i] < min_count || c[i] <= 0) continue; // (a mean over no points is no score)
+    if (b < 0)
+    {
+      b = (int64_t)i;
+      continue;
+    }
+    // e[i] / c[i] < e[b] / c[b] with positive counts, exactly: |e| and c are below 2^31, the products below 2^62
+    const int64_t lhs = (int64_t)e[i] * (int64_t)c[b], rhs = (int64_t)e[b] * (int64_t)c[i];
+    if (lhs < rhs || (lhs == rhs && c[i] > c[b])) b = (int64_t)i;
+  }
+  *best = b;
+  return WS_OK;
 }
 
 // ------------------------------------------------------------------ multi-GPU resident loop

@@ -405,6 +405,11 @@ struct ws_reg
   int peer_rank = 0, peer_world = 0; // 0: not connected
   int peer_blocks = 0;               // grid of the peer loop on this rank
   bool peer_dirty = false;           // an exchange failed or was given up: the mailboxes hold partial additions until ws_reg_peer_reset / reconnect
+  // ws_register_cloud_batch (reg_batch_kernel): per hypothesis a start record, then a result record; grows on demand
+  void *batch_host = nullptr;        // pinned + mapped
+  void *batch_dev = nullptr;         // device view
+  size_t batch_cap = 0;              // hypotheses the block holds
+  int batch_variant = 0;             // 1: reg_batch_kernel with the per-lane voxel cache (WS_REG_BATCH_VARIANT in the environment: tuning)
 };
 
 // scan pre-processing buffers (App::preprocess on the device, scan_preprocess.hip)
@@ -488,6 +493,12 @@ uint32_t reg_server_mail_exited(const void *mail);
 int launch_scan_preprocess(ws_scan *sc, const float *xyz_dev, size_t n, size_t stride, const int32_t M[16], int32_t res);
 size_t pre_table_slots(size_t max_points);
 int launch_reg_loop(ws_reg *r, const ws_map *m, int32_t res, uint32_t flags, const ws::GnCore &init, bool peers = false, size_t first = 0, size_t count = 0);
+// reg_batch_kernel: k workgroups, one Gauss-Newton loop each, from the start records in ws_reg::batch_host into its result records
+int launch_reg_batch(ws_reg *r, const ws_map *m, int32_t res, uint32_t flags, size_t k, int32_t max_iterations, float it_weight_gradient, float epsilon);
+size_t reg_batch_record_bytes(); // start + result record of one hypothesis
+void reg_batch_write(void *records, size_t k, const float T[16]);
+void reg_batch_read(const void *records, size_t n, size_t k, float T[16], int32_t *iterations, int32_t *e, int32_t *c);
+int reg_batch_default_variant();
 size_t reg_peer_block_bytes();
 void reg_peer_block_fill(void *host_image, void *const mailbox[8], int rank, int world);
 size_t reg_mailbox_bytes();
