@@ -287,24 +287,13 @@ static int map_free(ws_map *m)
   }
   map_free_records(m);
   void *ptrs[] = {m->data[0], m->data[1], m->vstate, m->az_hist, m->az_off, m->ray_bin, m->ray_order, m->fan_steps, m->rays, m->scan_dev, m->counters, m->tile_nsub,
-                  m->tile_ent, m->tile_dirty, m->tile_list, m->block_stats, m->box_stage,
-                  m->surf_col_cnt, m->surf_blk_tot, m->surf_blk_off, m->surf_total_dev, m->surf_rec, m->surf_marker,
-                  m->mesh_scratch, m->mesh_vert, m->mesh_face, m->ray_dirs, m->ray_rec, m->ray_grad, m->ray_hits_dev,
-                  m->dist_rec, m->dist_plane, m->dist_sites_dev};
+                  m->tile_ent, m->tile_dirty, m->tile_list, m->block_stats, m->box_stage};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
-  if (m->surf_total_host) (void)hipHostFree(m->surf_total_host);
-  for (hipEvent_t e : m->surf_ev)
-    if (e) (void)hipEventDestroy(e);
-  if (m->mesh_total_host) (void)hipHostFree(m->mesh_total_host);
-  for (hipEvent_t e : m->mesh_ev)
-    if (e) (void)hipEventDestroy(e);
-  if (m->ray_hits_host) (void)hipHostFree(m->ray_hits_host);
-  for (hipEvent_t e : m->ray_ev)
-    if (e) (void)hipEventDestroy(e);
-  if (m->dist_sites_host) (void)hipHostFree(m->dist_sites_host);
-  for (hipEvent_t e : m->dist_ev)
-    if (e) (void)hipEventDestroy(e);
+  m->surf.release();
+  m->mesh.release();
+  m->ray.release();
+  m->dist.release();
   if (m->counters_host) (void)hipHostFree(m->counters_host);
   if (m->status_host) (void)hipHostFree(m->status_host);
   if (m->shift_open) delete m->shift_open;
@@ -524,22 +513,39 @@ int ws_map_download(ws_map *m, int which, int32_t size[3], int32_t pos[3], int32
 }
 
 // ---- box transfers: the device side of the map shift (only the slabs that leave / enter move)
-static int box_check(ws_map *m, int which, const int32_t lo[3], const int32_t hi[3], int32_t ext[3], size_t *n)
+// The one copy of the box rules.  [lo, hi] in world voxels, both ends included, against the window of map `which`: its first voxel
+// into l, its extent into ext.  lo == hi == NULL is the whole window where `allow_whole`.  `name` starts the error texts.
+static int resolve_box(const ws_map *m, int which, const int32_t lo[3], const int32_t hi[3], bool allow_whole, const char *name, int32_t l[3], int32_t ext[3])
 {
-  if (!m || !lo || !hi || (which != WS_MAP_AVG && which != WS_MAP_NEW)) return invalid("box transfer: bad argument");
+  const auto bad = [name](const char *what) { return invalid((std::string(name) + what).c_str()); };
+  if (!allow_whole && (!lo || !hi)) return bad(": bad argument");
   const MapParams &p = m->par[which];
-  size_t cnt = 1;
   for (int k = 0; k < 3; ++k)
   {
-    if (hi[k] < lo[k]) return invalid("box transfer: hi < lo");
-    if (std::abs(lo[k] - p.pos[k]) > p.size[k] / 2 || std::abs(hi[k] - p.pos[k]) > p.size[k] / 2)
-      return invalid("box transfer: box outside the local map window");
+    if (!lo)
+    {
+      l[k] = p.pos[k] - p.size[k] / 2;
+      ext[k] = p.size[k];
+      continue;
+    }
+    if (hi[k] < lo[k]) return bad(": hi < lo");
+    if (std::abs(lo[k] - p.pos[k]) > p.size[k] / 2 || std::abs(hi[k] - p.pos[k]) > p.size[k] / 2) return bad(": box outside the local map window");
+    l[k] = lo[k];
     ext[k] = hi[k] - lo[k] + 1;
     // (an even size admits pos - size/2 .. pos + size/2: size + 1 voxels, the first and the last the same ring cell -- two lanes
     // of an insert would store to one address)
-    if (ext[k] > p.size[k]) return invalid("box transfer: box wraps onto itself (more voxels than the ring holds along an axis)");
-    cnt *= (size_t)ext[k];
+    if (ext[k] > p.size[k]) return bad(": box wraps onto itself (more voxels than the ring holds along an axis)");
   }
+  return WS_OK;
+}
+
+static int box_check(ws_map *m, int which, const int32_t lo[3], const int32_t hi[3], int32_t ext[3], size_t *n)
+{
+  if (!m || (which != WS_MAP_AVG && which != WS_MAP_NEW)) return invalid("box transfer: bad argument");
+  int32_t l[3];
+  const int rc = resolve_box(m, which, lo, hi, false, "box transfer", l, ext);
+  if (rc != WS_OK) return rc;
+  const size_t cnt = (size_t)ext[0] * (size_t)ext[1] * (size_t)ext[2];
   *n = cnt;
   if (cnt > m->box_stage_cap)
   {
@@ -585,155 +591,93 @@ int ws_map_insert_box(ws_map *m, int which, const int32_t lo[3], const int32_t h
 }
 
 // ---- surface cloud: publish_local_map's extraction (visualization/map.h:14-121) on the device, map_surface.hip
-// a device buffer of at least `need` elements; the contents are not kept.  The caller has synchronised the stream.
-static int surf_grow(void **p, size_t *cap, size_t need, size_t elem_bytes)
-{
-  if (need <= *cap) return WS_OK;
-  if (*p) WS_HIP(hipFree(*p));
-  *p = nullptr;
-  *cap = 0;
-  need += need / 8; // a little room: a map that gains a few points per scan does not reallocate on every call
-  WS_HIP(hipMalloc(p, need * elem_bytes));
-  *cap = need;
-  return WS_OK;
-}
-
 int ws_map_surface(ws_map *m, int which, const int32_t lo[3], const int32_t hi[3], int32_t band, uint32_t flags, size_t *n_out)
 {
   if (!m || (which != WS_MAP_AVG && which != WS_MAP_NEW) || (flags & ~WS_SURFACE_MARKER) || ((lo == nullptr) != (hi == nullptr)))
     return invalid("ws_map_surface: bad argument");
   WS_SETTLE(m);
-  std::lock_guard<std::mutex> lock(m->surf_mu);
-  const MapParams &p = m->par[which];
+  std::lock_guard<std::mutex> lock(m->surf.mu);
+  ws_map::Surface &q = m->surf;
+  int rc = q.timer.arm();
   int32_t l[3], ext[3];
-  for (int k = 0; k < 3; ++k)
-  {
-    if (lo)
-    {
-      if (hi[k] < lo[k]) return invalid("ws_map_surface: hi < lo");
-      if (std::abs(lo[k] - p.pos[k]) > p.size[k] / 2 || std::abs(hi[k] - p.pos[k]) > p.size[k] / 2)
-        return invalid("ws_map_surface: box outside the local map window");
-      l[k] = lo[k];
-      ext[k] = hi[k] - lo[k] + 1;
-      // (an even size admits pos - size/2 .. pos + size/2: size + 1 voxels, the first and the last the same ring cell)
-      if (ext[k] > p.size[k]) return invalid("ws_map_surface: box wraps onto itself (more voxels than the ring holds along an axis)");
-    }
-    else
-    {
-      l[k] = p.pos[k] - p.size[k] / 2;
-      ext[k] = p.size[k];
-    }
-  }
+  if (rc == WS_OK) rc = resolve_box(m, which, lo, hi, true, "ws_map_surface", l, ext);
+  if (rc == WS_OK) rc = q.total.alloc(1);
+  if (rc != WS_OK) return rc;
   if (band <= 0) band = m->tau;
   const bool marker = (flags & WS_SURFACE_MARKER) != 0;
   hipStream_t s = m->ctx->stream;
-  const int64_t n_cols = (int64_t)ext[0] * ext[1]; // < 2^31 (ws_map_create)
-  if (!m->surf_total_dev)
-  {
-    WS_HIP(hipMalloc((void **)&m->surf_total_dev, sizeof(unsigned long long)));
-    WS_HIP(hipHostMalloc((void **)&m->surf_total_host, sizeof(unsigned long long), hipHostMallocDefault));
-  }
-  if (m->surf_timing)
-    for (hipEvent_t &e : m->surf_ev)
-      if (!e) WS_HIP(hipEventCreate(&e));
-  if ((size_t)n_cols > m->surf_cols_cap)
+  const size_t n_cols = (size_t)ext[0] * (size_t)ext[1], blocks = surface_blocks_for((int64_t)n_cols); // n_cols < 2^31 (ws_map_create)
+  if (n_cols > q.col_cnt.cap || blocks > q.blk_tot.cap || blocks > q.blk_off.cap)
   {
     WS_HIP(hipStreamSynchronize(s));
-    // all three anew, for this many columns (the whole window asks for the most there will ever be)
-    m->surf_cols_cap = 0;
-    size_t c0 = 0, c1 = 0, c2 = 0;
-    const size_t blocks = surface_blocks_for(n_cols);
-    int rc = surf_grow((void **)&m->surf_col_cnt, &c0, (size_t)n_cols, sizeof(uint32_t));
-    if (rc == WS_OK) rc = surf_grow((void **)&m->surf_blk_tot, &c1, blocks, sizeof(uint32_t));
-    if (rc == WS_OK) rc = surf_grow((void **)&m->surf_blk_off, &c2, blocks, sizeof(unsigned long long));
+    rc = q.col_cnt.grow(n_cols, sizeof(uint32_t));
+    if (rc == WS_OK) rc = q.blk_tot.grow(blocks, sizeof(uint32_t));
+    if (rc == WS_OK) rc = q.blk_off.grow(blocks, sizeof(unsigned long long));
     if (rc != WS_OK) return rc;
-    m->surf_cols_cap = (size_t)n_cols;
   }
-  m->surf_n = 0;
-  m->surf_has_marker = false;
-  m->surf_ev_emit = false;
-  int rc = launch_surface_count(m, which, l, ext, band);
+  q.n = 0;
+  q.has_marker = false;
+  rc = launch_surface_count(m, which, l, ext, band);
   if (rc != WS_OK) return rc;
   WS_HIP(hipStreamSynchronize(s)); // the one host read the call needs: the output is sized from the counted total
-  const size_t total = (size_t)*m->surf_total_host;
-  rc = surf_grow(&m->surf_rec, &m->surf_cap, total, 16);
-  if (rc == WS_OK && marker)
-  {
-    size_t cap7 = m->surf_marker_cap * 7;
-    rc = surf_grow((void **)&m->surf_marker, &cap7, total * 7, sizeof(float));
-    m->surf_marker_cap = cap7 / 7;
-  }
+  const size_t total = (size_t)*q.total.host;
+  rc = q.rec.grow(total, 16);
+  if (rc == WS_OK && marker) rc = q.marker.grow(total, 7 * sizeof(float));
   if (rc != WS_OK) return rc;
   if (total)
   {
-    const size_t cap_all = m->surf_cap;
-    if (marker && m->surf_marker_cap < m->surf_cap) m->surf_cap = m->surf_marker_cap; // (the kernel's bound holds for both buffers)
-    rc = launch_surface_emit(m, which, l, ext, band, marker);
-    m->surf_cap = cap_all;
+    // (the kernel's bound holds for both buffers)
+    rc = launch_surface_emit(m, which, l, ext, band, marker, marker ? std::min(q.rec.cap, q.marker.cap) : q.rec.cap);
     if (rc != WS_OK) return rc;
-    m->surf_ev_emit = true;
     WS_HIP(hipStreamSynchronize(s));
   }
-  m->surf_n = total;
-  m->surf_has_marker = marker;
+  q.n = total;
+  q.has_marker = marker;
   if (n_out) *n_out = total;
   return map_take_error(m);
 }
 
 const void *ws_map_surface_records_dev(const ws_map *m, size_t *n)
 {
-  if (n) *n = m ? m->surf_n : 0;
-  return m && m->surf_n ? m->surf_rec : nullptr;
+  if (n) *n = m ? m->surf.n : 0;
+  return m && m->surf.n ? m->surf.rec.p : nullptr;
 }
 
 const float *ws_map_surface_marker_dev(const ws_map *m, size_t *n)
 {
-  const bool have = m && m->surf_has_marker && m->surf_n;
-  if (n) *n = have ? m->surf_n : 0;
-  return have ? m->surf_marker : nullptr;
+  const bool have = m && m->surf.has_marker && m->surf.n;
+  if (n) *n = have ? m->surf.n : 0;
+  return have ? static_cast<const float *>(m->surf.marker.p) : nullptr;
 }
 
 int ws_map_surface_download(ws_map *m, void *records_host, float *marker_host, size_t capacity_points, size_t *n_out)
 {
   if (!m || !n_out) return invalid("ws_map_surface_download: NULL argument");
-  std::lock_guard<std::mutex> lock(m->surf_mu);
-  *n_out = m->surf_n;
-  const size_t k = std::min(capacity_points, m->surf_n);
+  std::lock_guard<std::mutex> lock(m->surf.mu);
+  *n_out = m->surf.n;
+  const size_t k = std::min(capacity_points, m->surf.n);
   if (k == 0) return WS_OK;
-  if (marker_host && !m->surf_has_marker) return invalid("ws_map_surface_download: the last ws_map_surface did not ask for WS_SURFACE_MARKER");
-  if (records_host) WS_HIP(hipMemcpyAsync(records_host, m->surf_rec, k * 16, hipMemcpyDeviceToHost, m->ctx->stream));
-  if (marker_host) WS_HIP(hipMemcpyAsync(marker_host, m->surf_marker, k * 7 * sizeof(float), hipMemcpyDeviceToHost, m->ctx->stream));
+  if (marker_host && !m->surf.has_marker) return invalid("ws_map_surface_download: the last ws_map_surface did not ask for WS_SURFACE_MARKER");
+  if (records_host) WS_HIP(hipMemcpyAsync(records_host, m->surf.rec.p, k * 16, hipMemcpyDeviceToHost, m->ctx->stream));
+  if (marker_host) WS_HIP(hipMemcpyAsync(marker_host, m->surf.marker.p, k * 7 * sizeof(float), hipMemcpyDeviceToHost, m->ctx->stream));
   WS_HIP(hipStreamSynchronize(m->ctx->stream));
   return WS_OK;
+}
+
+// ws_debug_*_timing: the times of the last call between the event pairs of `pairs`, then the switch
+static int query_timing(ws_map *m, QueryTimer &t, int32_t enable, float *ms_out, const int (*pairs)[2], int n)
+{
+  const int rc = t.read(ms_out, pairs, n, m->ctx->stream);
+  if (rc == WS_OK) t.set(enable);
+  return rc;
 }
 
 int ws_debug_surface_timing(ws_map *m, int32_t enable, float ms_out[3])
 {
   if (!m) return invalid("ws_debug_surface_timing: map is NULL");
-  std::lock_guard<std::mutex> lock(m->surf_mu);
-  if (ms_out)
-  {
-    ms_out[0] = ms_out[1] = ms_out[2] = 0.f;
-    if (m->surf_timing && m->surf_ev[0])
-    {
-      WS_HIP(hipStreamSynchronize(m->ctx->stream));
-      WS_HIP(hipEventElapsedTime(&ms_out[0], m->surf_ev[0], m->surf_ev[1]));
-      WS_HIP(hipEventElapsedTime(&ms_out[1], m->surf_ev[1], m->surf_ev[2]));
-      if (m->surf_ev_emit) WS_HIP(hipEventElapsedTime(&ms_out[2], m->surf_ev[3], m->surf_ev[4]));
-    }
-  }
-  if (enable >= 0)
-  {
-    if (!enable || !m->surf_timing)
-      for (hipEvent_t &e : m->surf_ev)
-      {
-        // (events of an earlier enabled period are not read again: a fresh set is recorded by the next call)
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-      }
-    m->surf_timing = enable != 0;
-  }
-  return WS_OK;
+  std::lock_guard<std::mutex> lock(m->surf.mu);
+  static const int pairs[3][2] = {{0, 1}, {1, 2}, {3, 4}};
+  return query_timing(m, m->surf.timer, enable, ms_out, pairs, 3);
 }
 
 // ---- mesh: naive surface nets over a device map, map_mesh.hip (the rules are stated in warpsense_hip.h)
@@ -742,26 +686,12 @@ int ws_map_mesh(ws_map *m, int which, const int32_t lo[3], const int32_t hi[3], 
   if (!m || (which != WS_MAP_AVG && which != WS_MAP_NEW) || (flags & ~WS_MESH_ANY_WEIGHT) || ((lo == nullptr) != (hi == nullptr)))
     return invalid("ws_map_mesh: bad argument");
   WS_SETTLE(m);
-  std::lock_guard<std::mutex> lock(m->mesh_mu);
-  const MapParams &p = m->par[which];
+  std::lock_guard<std::mutex> lock(m->mesh.mu);
+  ws_map::Mesh &q = m->mesh;
+  int rc = q.timer.arm();
   int32_t l[3], ext[3];
-  for (int k = 0; k < 3; ++k)
-  {
-    if (lo)
-    {
-      if (hi[k] < lo[k]) return invalid("ws_map_mesh: hi < lo");
-      if (std::abs(lo[k] - p.pos[k]) > p.size[k] / 2 || std::abs(hi[k] - p.pos[k]) > p.size[k] / 2)
-        return invalid("ws_map_mesh: box outside the local map window");
-      l[k] = lo[k];
-      ext[k] = hi[k] - lo[k] + 1;
-      if (ext[k] > p.size[k]) return invalid("ws_map_mesh: box wraps onto itself (more voxels than the ring holds along an axis)");
-    }
-    else
-    {
-      l[k] = p.pos[k] - p.size[k] / 2;
-      ext[k] = p.size[k];
-    }
-  }
+  if (rc == WS_OK) rc = resolve_box(m, which, lo, hi, true, "ws_map_mesh", l, ext);
+  if (rc != WS_OK) return rc;
   for (int k = 0; k < 3; ++k)
     for (int64_t c : {(int64_t)l[k], (int64_t)l[k] + ext[k] - 1})
       if (((c < 0 ? -c : c) + 1) * (int64_t)m->res > (int64_t)INT32_MAX)
@@ -769,8 +699,7 @@ int ws_map_mesh(ws_map *m, int which, const int32_t lo[3], const int32_t hi[3], 
         set_error("ws_map_mesh: a box corner in millimetres does not fit int32");
         return WS_ERR_RANGE;
       }
-  m->mesh_nv = m->mesh_nf = 0;
-  m->mesh_ev_count = m->mesh_ev_emit = false;
+  q.nv = q.nf = 0;
   if (n_vertices) *n_vertices = 0;
   if (n_faces) *n_faces = 0;
   hipStream_t s = m->ctx->stream;
@@ -780,62 +709,58 @@ int ws_map_mesh(ws_map *m, int which, const int32_t lo[3], const int32_t hi[3], 
     set_error("ws_map_mesh: box too large (columns x 64-voxel words must stay below 2^31)");
     return WS_ERR_RANGE;
   }
-  if (!m->mesh_total_host) WS_HIP(hipHostMalloc((void **)&m->mesh_total_host, 2 * sizeof(unsigned long long), hipHostMallocDefault));
-  if (m->mesh_timing)
-    for (hipEvent_t &e : m->mesh_ev)
-      if (!e) WS_HIP(hipEventCreate(&e));
+  rc = q.total.alloc(2, false);
+  if (rc != WS_OK) return rc;
   if (ext[0] < 2 || ext[1] < 2 || ext[2] < 2) return map_take_error(m); // one voxel thick along an axis: no cells
   WS_HIP(hipStreamSynchronize(s));
-  int rc = surf_grow(&m->mesh_scratch, &m->mesh_scratch_cap, mesh_scratch_bytes(n_words), 1);
+  rc = q.scratch.grow(mesh_scratch_bytes(n_words), 1);
   if (rc != WS_OK) return rc;
   rc = launch_mesh_count(m, which, l, ext, flags);
   if (rc != WS_OK) return rc;
-  m->mesh_ev_count = true;
   WS_HIP(hipStreamSynchronize(s)); // the one host read the call needs: the outputs are sized from the two totals
-  const unsigned long long nv = m->mesh_total_host[0], nq = m->mesh_total_host[1];
+  const unsigned long long nv = q.total.host[0], nq = q.total.host[1];
   if (nv > 0xffffffffull)
   {
     set_error("ws_map_mesh: more than 2^32 - 1 vertices");
     return WS_ERR_RANGE;
   }
-  rc = surf_grow(&m->mesh_vert, &m->mesh_vert_cap, (size_t)nv, 16);
-  if (rc == WS_OK) rc = surf_grow((void **)&m->mesh_face, &m->mesh_face_cap, (size_t)nq * 2, 12);
+  rc = q.vert.grow((size_t)nv, 16);
+  if (rc == WS_OK) rc = q.face.grow((size_t)nq * 2, 12);
   if (rc != WS_OK) return rc;
   if (nv)
   {
     rc = launch_mesh_emit(m, which, l, ext, flags);
     if (rc != WS_OK) return rc;
-    m->mesh_ev_emit = true;
     WS_HIP(hipStreamSynchronize(s));
   }
-  m->mesh_nv = (size_t)nv;
-  m->mesh_nf = (size_t)nq * 2;
-  if (n_vertices) *n_vertices = m->mesh_nv;
-  if (n_faces) *n_faces = m->mesh_nf;
+  q.nv = (size_t)nv;
+  q.nf = (size_t)nq * 2;
+  if (n_vertices) *n_vertices = q.nv;
+  if (n_faces) *n_faces = q.nf;
   return map_take_error(m);
 }
 
 const void *ws_map_mesh_vertices_dev(const ws_map *m, size_t *n)
 {
-  if (n) *n = m ? m->mesh_nv : 0;
-  return m && m->mesh_nv ? m->mesh_vert : nullptr;
+  if (n) *n = m ? m->mesh.nv : 0;
+  return m && m->mesh.nv ? m->mesh.vert.p : nullptr;
 }
 
 const uint32_t *ws_map_mesh_faces_dev(const ws_map *m, size_t *n)
 {
-  if (n) *n = m ? m->mesh_nf : 0;
-  return m && m->mesh_nf ? m->mesh_face : nullptr;
+  if (n) *n = m ? m->mesh.nf : 0;
+  return m && m->mesh.nf ? static_cast<const uint32_t *>(m->mesh.face.p) : nullptr;
 }
 
 int ws_map_mesh_download(ws_map *m, void *vertices_host, uint32_t *faces_host, size_t cap_vertices, size_t cap_faces, size_t *n_vertices, size_t *n_faces)
 {
   if (!m || !n_vertices || !n_faces) return invalid("ws_map_mesh_download: NULL argument");
-  std::lock_guard<std::mutex> lock(m->mesh_mu);
-  *n_vertices = m->mesh_nv;
-  *n_faces = m->mesh_nf;
-  const size_t kv = vertices_host ? std::min(cap_vertices, m->mesh_nv) : 0, kf = faces_host ? std::min(cap_faces, m->mesh_nf) : 0;
-  if (kv) WS_HIP(hipMemcpyAsync(vertices_host, m->mesh_vert, kv * 16, hipMemcpyDeviceToHost, m->ctx->stream));
-  if (kf) WS_HIP(hipMemcpyAsync(faces_host, m->mesh_face, kf * 12, hipMemcpyDeviceToHost, m->ctx->stream));
+  std::lock_guard<std::mutex> lock(m->mesh.mu);
+  *n_vertices = m->mesh.nv;
+  *n_faces = m->mesh.nf;
+  const size_t kv = vertices_host ? std::min(cap_vertices, m->mesh.nv) : 0, kf = faces_host ? std::min(cap_faces, m->mesh.nf) : 0;
+  if (kv) WS_HIP(hipMemcpyAsync(vertices_host, m->mesh.vert.p, kv * 16, hipMemcpyDeviceToHost, m->ctx->stream));
+  if (kf) WS_HIP(hipMemcpyAsync(faces_host, m->mesh.face.p, kf * 12, hipMemcpyDeviceToHost, m->ctx->stream));
   if (kv || kf) WS_HIP(hipStreamSynchronize(m->ctx->stream));
   return WS_OK;
 }
@@ -843,29 +768,9 @@ int ws_map_mesh_download(ws_map *m, void *vertices_host, uint32_t *faces_host, s
 int ws_debug_mesh_timing(ws_map *m, int32_t enable, float ms_out[3])
 {
   if (!m) return invalid("ws_debug_mesh_timing: map is NULL");
-  std::lock_guard<std::mutex> lock(m->mesh_mu);
-  if (ms_out)
-  {
-    ms_out[0] = ms_out[1] = ms_out[2] = 0.f;
-    if (m->mesh_timing && m->mesh_ev[0] && m->mesh_ev_count)
-    {
-      WS_HIP(hipStreamSynchronize(m->ctx->stream));
-      WS_HIP(hipEventElapsedTime(&ms_out[0], m->mesh_ev[0], m->mesh_ev[1]));
-      WS_HIP(hipEventElapsedTime(&ms_out[1], m->mesh_ev[1], m->mesh_ev[2]));
-      if (m->mesh_ev_emit) WS_HIP(hipEventElapsedTime(&ms_out[2], m->mesh_ev[3], m->mesh_ev[4]));
-    }
-  }
-  if (enable >= 0)
-  {
-    if (!enable || !m->mesh_timing)
-      for (hipEvent_t &e : m->mesh_ev)
-      {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-      }
-    m->mesh_timing = enable != 0;
-  }
-  return WS_OK;
+  std::lock_guard<std::mutex> lock(m->mesh.mu);
+  static const int pairs[3][2] = {{0, 1}, {1, 2}, {3, 4}};
+  return query_timing(m, m->mesh.timer, enable, ms_out, pairs, 3);
 }
 
 // ---- ray cast: the range image of a device map, map_raycast.hip (the rules are stated in warpsense_hip.h)
@@ -895,43 +800,38 @@ static int raycast_run(ws_map *m, int which, const int32_t origin[3], const int3
     }
   }
   WS_SETTLE(m);
-  std::lock_guard<std::mutex> lock(m->ray_mu);
+  std::lock_guard<std::mutex> lock(m->ray.mu);
+  ws_map::Raycast &q = m->ray;
+  int rc = q.timer.arm();
+  if (rc != WS_OK) return rc;
   if (n_hits) *n_hits = 0;
-  m->ray_n = 0;
-  m->ray_has_grad = false;
-  m->ray_ev_done = false;
+  q.n = 0;
+  q.has_grad = false;
   if (n == 0) return map_take_error(m);
   hipStream_t s = m->ctx->stream;
   const bool grad = (flags & WS_RAYCAST_GRADIENT) != 0;
-  if (!m->ray_hits_dev)
-  {
-    WS_HIP(hipMalloc((void **)&m->ray_hits_dev, sizeof(unsigned long long)));
-    WS_HIP(hipHostMalloc((void **)&m->ray_hits_host, sizeof(unsigned long long), hipHostMallocDefault));
-  }
-  if (m->ray_timing)
-    for (hipEvent_t &e : m->ray_ev)
-      if (!e) WS_HIP(hipEventCreate(&e));
-  if (n > m->ray_rec_cap || (grad && n > m->ray_grad_cap) || (dirs_on_host && n > m->ray_dirs_cap))
+  rc = q.hits.alloc(1);
+  if (rc != WS_OK) return rc;
+  if (n > q.rec.cap || (grad && n > q.grad.cap) || (dirs_on_host && n > q.dirs.cap))
   {
     WS_HIP(hipStreamSynchronize(s));
-    int rc = surf_grow(&m->ray_rec, &m->ray_rec_cap, n, 16);
-    if (rc == WS_OK && grad) rc = surf_grow((void **)&m->ray_grad, &m->ray_grad_cap, n, 3 * sizeof(int32_t));
-    if (rc == WS_OK && dirs_on_host) rc = surf_grow((void **)&m->ray_dirs, &m->ray_dirs_cap, n, 3 * sizeof(int32_t));
+    rc = q.rec.grow(n, 16);
+    if (rc == WS_OK && grad) rc = q.grad.grow(n, 3 * sizeof(int32_t));
+    if (rc == WS_OK && dirs_on_host) rc = q.dirs.grow(n, 3 * sizeof(int32_t));
     if (rc != WS_OK) return rc;
   }
-  if (m->ray_timing) (void)hipEventRecord(m->ray_ev[0], s);
+  q.timer.mark(0, s);
   if (dirs_on_host)
   {
-    WS_HIP(hipMemcpyAsync(m->ray_dirs, dirs, n * 3 * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    dirs = m->ray_dirs;
+    WS_HIP(hipMemcpyAsync(q.dirs.p, dirs, n * 3 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    dirs = static_cast<const int32_t *>(q.dirs.p);
   }
-  const int rc = launch_raycast(m, which, origin, dirs, n, max_range, flags);
+  rc = launch_raycast(m, which, origin, dirs, n, max_range, flags);
   if (rc != WS_OK) return rc;
   WS_HIP(hipStreamSynchronize(s));
-  m->ray_ev_done = m->ray_timing;
-  m->ray_n = n;
-  m->ray_has_grad = grad;
-  if (n_hits) *n_hits = (size_t)*m->ray_hits_host;
+  q.n = n;
+  q.has_grad = grad;
+  if (n_hits) *n_hits = (size_t)*q.hits.host;
   return map_take_error(m);
 }
 
@@ -947,27 +847,27 @@ int ws_map_raycast_dev(ws_map *m, int which, const int32_t origin_mm[3], const i
 
 const void *ws_map_raycast_records_dev(const ws_map *m, size_t *n)
 {
-  if (n) *n = m ? m->ray_n : 0;
-  return m && m->ray_n ? m->ray_rec : nullptr;
+  if (n) *n = m ? m->ray.n : 0;
+  return m && m->ray.n ? m->ray.rec.p : nullptr;
 }
 
 const int32_t *ws_map_raycast_gradient_dev(const ws_map *m, size_t *n)
 {
-  const bool have = m && m->ray_has_grad && m->ray_n;
-  if (n) *n = have ? m->ray_n : 0;
-  return have ? m->ray_grad : nullptr;
+  const bool have = m && m->ray.has_grad && m->ray.n;
+  if (n) *n = have ? m->ray.n : 0;
+  return have ? static_cast<const int32_t *>(m->ray.grad.p) : nullptr;
 }
 
 int ws_map_raycast_download(ws_map *m, void *records_host, int32_t *gradient_host, size_t capacity_rays, size_t *n_out)
 {
   if (!m || !n_out) return invalid("ws_map_raycast_download: NULL argument");
-  std::lock_guard<std::mutex> lock(m->ray_mu);
-  *n_out = m->ray_n;
-  const size_t k = std::min(capacity_rays, m->ray_n);
+  std::lock_guard<std::mutex> lock(m->ray.mu);
+  *n_out = m->ray.n;
+  const size_t k = std::min(capacity_rays, m->ray.n);
   if (k == 0) return WS_OK;
-  if (gradient_host && !m->ray_has_grad) return invalid("ws_map_raycast_download: the last ws_map_raycast did not ask for WS_RAYCAST_GRADIENT");
-  if (records_host) WS_HIP(hipMemcpyAsync(records_host, m->ray_rec, k * 16, hipMemcpyDeviceToHost, m->ctx->stream));
-  if (gradient_host) WS_HIP(hipMemcpyAsync(gradient_host, m->ray_grad, k * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, m->ctx->stream));
+  if (gradient_host && !m->ray.has_grad) return invalid("ws_map_raycast_download: the last ws_map_raycast did not ask for WS_RAYCAST_GRADIENT");
+  if (records_host) WS_HIP(hipMemcpyAsync(records_host, m->ray.rec.p, k * 16, hipMemcpyDeviceToHost, m->ctx->stream));
+  if (gradient_host) WS_HIP(hipMemcpyAsync(gradient_host, m->ray.grad.p, k * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, m->ctx->stream));
   WS_HIP(hipStreamSynchronize(m->ctx->stream));
   return WS_OK;
 }
@@ -975,30 +875,9 @@ int ws_map_raycast_download(ws_map *m, void *records_host, int32_t *gradient_hos
 int ws_debug_raycast_timing(ws_map *m, int32_t enable, float ms_out[3])
 {
   if (!m) return invalid("ws_debug_raycast_timing: map is NULL");
-  std::lock_guard<std::mutex> lock(m->ray_mu);
-  if (ms_out)
-  {
-    ms_out[0] = ms_out[1] = ms_out[2] = 0.f;
-    if (m->ray_timing && m->ray_ev[0] && m->ray_ev_done)
-    {
-      WS_HIP(hipStreamSynchronize(m->ctx->stream));
-      for (int k = 0; k < 3; ++k) WS_HIP(hipEventElapsedTime(&ms_out[k], m->ray_ev[k], m->ray_ev[k + 1]));
-    }
-  }
-  if (enable >= 0)
-  {
-    if (!enable || !m->ray_timing)
-    {
-      for (hipEvent_t &e : m->ray_ev)
-      {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-      }
-      m->ray_ev_done = false;
-    }
-    m->ray_timing = enable != 0;
-  }
-  return WS_OK;
+  std::lock_guard<std::mutex> lock(m->ray.mu);
+  static const int pairs[3][2] = {{0, 1}, {1, 2}, {2, 3}};
+  return query_timing(m, m->ray.timer, enable, ms_out, pairs, 3);
 }
 
 // ---- distance field: the exact Euclidean transform of a device map, map_distance.hip (the rules are stated in warpsense_hip.h)
@@ -1013,26 +892,12 @@ int ws_map_distance(ws_map *m, int which, const int32_t lo[3], const int32_t hi[
     return WS_ERR_RANGE;
   }
   WS_SETTLE(m);
-  std::lock_guard<std::mutex> lock(m->dist_mu);
-  const MapParams &p = m->par[which];
+  std::lock_guard<std::mutex> lock(m->dist.mu);
+  ws_map::Distance &q = m->dist;
+  int rc = q.timer.arm();
   int32_t l[3], ext[3];
-  for (int k = 0; k < 3; ++k)
-  {
-    if (lo)
-    {
-      if (hi[k] < lo[k]) return invalid("ws_map_distance: hi < lo");
-      if (std::abs(lo[k] - p.pos[k]) > p.size[k] / 2 || std::abs(hi[k] - p.pos[k]) > p.size[k] / 2)
-        return invalid("ws_map_distance: box outside the local map window");
-      l[k] = lo[k];
-      ext[k] = hi[k] - lo[k] + 1;
-      if (ext[k] > p.size[k]) return invalid("ws_map_distance: box wraps onto itself (more voxels than the ring holds along an axis)");
-    }
-    else
-    {
-      l[k] = p.pos[k] - p.size[k] / 2;
-      ext[k] = p.size[k];
-    }
-  }
+  if (rc == WS_OK) rc = resolve_box(m, which, lo, hi, true, "ws_map_distance", l, ext);
+  if (rc != WS_OK) return rc;
   const bool columns = (flags & WS_DISTANCE_COLUMNS) != 0;
   const uint64_t n64 = (uint64_t)ext[0] * (uint64_t)ext[1] * (uint64_t)(columns ? 1 : ext[2]); // ext[0] ext[1] < 2^31, ext[2] <= 2^20
   if (n64 > 0xffffffffull)
@@ -1042,44 +907,39 @@ int ws_map_distance(ws_map *m, int which, const int32_t lo[3], const int32_t hi[
   }
   const size_t n = (size_t)n64;
   if (n_sites) *n_sites = 0;
-  m->dist_n = 0;
-  m->dist_ev_done = false;
+  q.n = 0;
   hipStream_t s = m->ctx->stream;
-  if (!m->dist_sites_dev) WS_HIP(hipMalloc((void **)&m->dist_sites_dev, sizeof(unsigned long long)));
-  if (!m->dist_sites_host) WS_HIP(hipHostMalloc((void **)&m->dist_sites_host, sizeof(unsigned long long), hipHostMallocDefault));
-  if (m->dist_timing)
-    for (hipEvent_t &e : m->dist_ev)
-      if (!e) WS_HIP(hipEventCreate(&e));
-  if (n > m->dist_rec_cap || n > m->dist_plane_cap)
+  rc = q.sites.alloc(1);
+  if (rc != WS_OK) return rc;
+  if (n > q.rec.cap || n > q.plane.cap)
   {
     WS_HIP(hipStreamSynchronize(s));
-    int rc = surf_grow((void **)&m->dist_rec, &m->dist_rec_cap, n, sizeof(uint32_t));
-    if (rc == WS_OK) rc = surf_grow((void **)&m->dist_plane, &m->dist_plane_cap, n, 2 * sizeof(uint16_t)); // both planes
+    rc = q.rec.grow(n, sizeof(uint32_t));
+    if (rc == WS_OK) rc = q.plane.grow(n, 2 * sizeof(uint16_t)); // both planes
     if (rc != WS_OK) return rc;
   }
-  const int rc = launch_distance(m, which, l, ext, max_dist_vox, flags, n);
+  rc = launch_distance(m, which, l, ext, max_dist_vox, flags, n);
   if (rc != WS_OK) return rc;
   WS_HIP(hipStreamSynchronize(s));
-  m->dist_ev_done = m->dist_timing;
-  m->dist_n = n;
-  if (n_sites) *n_sites = (size_t)*m->dist_sites_host;
+  q.n = n;
+  if (n_sites) *n_sites = (size_t)*q.sites.host;
   return map_take_error(m);
 }
 
 const uint32_t *ws_map_distance_dev(const ws_map *m, size_t *n)
 {
-  if (n) *n = m ? m->dist_n : 0;
-  return m && m->dist_n ? m->dist_rec : nullptr;
+  if (n) *n = m ? m->dist.n : 0;
+  return m && m->dist.n ? static_cast<const uint32_t *>(m->dist.rec.p) : nullptr;
 }
 
 int ws_map_distance_download(ws_map *m, uint32_t *host, size_t capacity, size_t *n_out)
 {
   if (!m || !n_out) return invalid("ws_map_distance_download: NULL argument");
-  std::lock_guard<std::mutex> lock(m->dist_mu);
-  *n_out = m->dist_n;
-  const size_t k = host ? std::min(capacity, m->dist_n) : 0;
+  std::lock_guard<std::mutex> lock(m->dist.mu);
+  *n_out = m->dist.n;
+  const size_t k = host ? std::min(capacity, m->dist.n) : 0;
   if (k == 0) return WS_OK;
-  WS_HIP(hipMemcpyAsync(host, m->dist_rec, k * sizeof(uint32_t), hipMemcpyDeviceToHost, m->ctx->stream));
+  WS_HIP(hipMemcpyAsync(host, m->dist.rec.p, k * sizeof(uint32_t), hipMemcpyDeviceToHost, m->ctx->stream));
   WS_HIP(hipStreamSynchronize(m->ctx->stream));
   return WS_OK;
 }
@@ -1087,30 +947,9 @@ int ws_map_distance_download(ws_map *m, uint32_t *host, size_t capacity, size_t 
 int ws_debug_distance_timing(ws_map *m, int32_t enable, float ms_out[4])
 {
   if (!m) return invalid("ws_debug_distance_timing: map is NULL");
-  std::lock_guard<std::mutex> lock(m->dist_mu);
-  if (ms_out)
-  {
-    ms_out[0] = ms_out[1] = ms_out[2] = ms_out[3] = 0.f;
-    if (m->dist_timing && m->dist_ev[0] && m->dist_ev_done)
-    {
-      WS_HIP(hipStreamSynchronize(m->ctx->stream));
-      for (int k = 0; k < 4; ++k) WS_HIP(hipEventElapsedTime(&ms_out[k], m->dist_ev[k], m->dist_ev[k + 1]));
-    }
-  }
-  if (enable >= 0)
-  {
-    if (!enable || !m->dist_timing)
-    {
-      for (hipEvent_t &e : m->dist_ev)
-      {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-      }
-      m->dist_ev_done = false;
-    }
-    m->dist_timing = enable != 0;
-  }
-  return WS_OK;
+  std::lock_guard<std::mutex> lock(m->dist.mu);
+  static const int pairs[4][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 4}};
+  return query_timing(m, m->dist.timer, enable, ms_out, pairs, 4);
 }
 
 // ---- map shift off the scan path

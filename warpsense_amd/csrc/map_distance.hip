@@ -27,11 +27,7 @@ constexpr uint32_t DIST_OUTSIDE = 0xffffu; // beyond the end of a line: never a 
 
 struct DistArgs
 {
-  const uint32_t *data;
-  MapParams mp;
-  int32_t lo[3];
-  int32_t ey, ez;
-  uint32_t n_cols;
+  BoxArgs box;
   uint32_t r2;
   uint32_t flags;
   uint32_t *rec;
@@ -47,36 +43,26 @@ __device__ __forceinline__ uint32_t dist_class(uint32_t raw, bool any_weight)
   return valid ? (entry_value(raw) < 0 ? 2u : 1u) : 0u;
 }
 
-// storage index of the first voxel of box column `col` and the storage z of the box's first world z
-__device__ __forceinline__ int64_t dist_column(const DistArgs &a, uint32_t col, int32_t &zs0)
-{
-  const int32_t xr = (int32_t)(col / (uint32_t)a.ey), yr = (int32_t)(col - (uint32_t)xr * (uint32_t)a.ey);
-  const int32_t xi = ring(a.lo[0] + xr - a.mp.pos[0] + a.mp.offset[0] + a.mp.size[0], a.mp.size[0]);
-  const int32_t yi = ring(a.lo[1] + yr - a.mp.pos[1] + a.mp.offset[1] + a.mp.size[1], a.mp.size[1]);
-  zs0 = ring(a.lo[2] - a.mp.pos[2] + a.mp.offset[2] + a.mp.size[2], a.mp.size[2]);
-  return (int64_t)(xi * a.mp.size[1] + yi) * (int64_t)a.mp.size[2]; // size[0] * size[1] < 2^31 (ws_map_create)
-}
-
 template <bool COLUMNS>
 __global__ __launch_bounds__(256) void dist_classify_kernel(DistArgs a)
 {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const uint32_t col = blockIdx.x * 4u + (uint32_t)wave;
-  if (col >= a.n_cols) return; // (the same for the whole wave)
+  if (col >= a.box.n_cols) return; // (the same for the whole wave)
   const bool any_weight = (a.flags & WS_DISTANCE_ANY_WEIGHT) != 0, unknown_occ = (a.flags & WS_DISTANCE_UNKNOWN_OCCUPIED) != 0;
-  int32_t zs0;
-  const int64_t cbase = dist_column(a, col, zs0);
-  const int32_t sz = a.mp.size[2];
-  const uint64_t out0 = (uint64_t)col * (uint64_t)a.ez;
+  int32_t x, y, zs0;
+  const int64_t cbase = box_column(a.box, col, x, y, zs0);
+  const int32_t sz = a.box.mp.size[2];
+  const uint64_t out0 = (uint64_t)col * (uint64_t)a.box.ez;
   uint32_t n_sites = 0;
   bool occ = false, unk = false, fre = false; // COLUMNS: what the column holds
-  for (int32_t z0 = 0; z0 < a.ez; z0 += 64)
+  for (int32_t z0 = 0; z0 < a.box.ez; z0 += 64)
   {
     const int32_t z = z0 + lane;
-    const bool in = z < a.ez;
+    const bool in = z < a.box.ez;
     int32_t zi = zs0 + (in ? z : 0); // the ring's seam in z: the run goes on at storage z 0
     if (zi >= sz) zi -= sz;
-    const uint32_t cls = dist_class(a.data[cbase + zi], any_weight);
+    const uint32_t cls = dist_class(a.box.data[cbase + zi], any_weight);
     const bool site = in && (cls == 2u || (unknown_occ && cls == 0u));
     if (COLUMNS)
     {
@@ -183,11 +169,6 @@ __global__ __launch_bounds__(DIST_ROW) void dist_row_kernel(DistRowArgs a)
   if (active) a.rec[row + (uint64_t)z] = (a.rec[row + (uint64_t)z] & 0xc0000000u) | best;
 }
 
-static void dist_mark(ws_map *m, int i)
-{
-  if (m->dist_timing) (void)hipEventRecord(m->dist_ev[i], m->ctx->stream);
-}
-
 static void dist_line(hipStream_t s, const uint16_t *in, uint16_t *out, uint32_t outer, uint32_t line, uint32_t inner, int32_t R)
 {
   DistLineArgs a;
@@ -206,57 +187,52 @@ static void dist_line(hipStream_t s, const uint16_t *in, uint16_t *out, uint32_t
 }
 
 // Pass 0 (events 0, 1), the x, y and z passes (events 1 .. 4); under WS_DISTANCE_COLUMNS pass 0, the x and the y pass (events 3, 4
-// coincide).  m->dist_plane holds two planes of `n` uint16.  The site count arrives in m->dist_sites_host (pinned) once the stream
+// coincide).  m->dist.plane holds two planes of `n` uint16.  The site count arrives in m->dist.sites.host (pinned) once the stream
 // has been synchronised.
 int launch_distance(ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], int32_t R, uint32_t flags, size_t n)
 {
   DistArgs a;
-  a.data = m->data[which];
-  a.mp = m->par[which];
-  for (int k = 0; k < 3; ++k) a.lo[k] = lo[k];
-  a.ey = ext[1];
-  a.ez = ext[2];
-  a.n_cols = (uint32_t)((int64_t)ext[0] * ext[1]);
+  a.box = box_args(m, which, lo, ext);
   a.r2 = (uint32_t)(R * R);
   a.flags = flags;
-  a.rec = m->dist_rec;
-  uint16_t *p0 = m->dist_plane, *p1 = m->dist_plane + n;
+  a.rec = static_cast<uint32_t *>(m->dist.rec.p);
+  uint16_t *p0 = static_cast<uint16_t *>(m->dist.plane.p), *p1 = p0 + n;
   a.plane = p0;
-  a.sites = m->dist_sites_dev;
+  a.sites = m->dist.sites.dev;
   hipStream_t s = m->ctx->stream;
   const uint32_t nx = (uint32_t)ext[0], ny = (uint32_t)ext[1], nz = (uint32_t)ext[2];
-  WS_HIP(hipMemsetAsync(m->dist_sites_dev, 0, sizeof(unsigned long long), s));
-  dist_mark(m, 0);
+  WS_HIP(hipMemsetAsync(a.sites, 0, sizeof(unsigned long long), s));
+  QueryTimer &t = m->dist.timer;
+  t.mark(0, s);
   DistRowArgs r;
-  r.rec = m->dist_rec;
+  r.rec = a.rec;
   r.R = R;
   if (flags & WS_DISTANCE_COLUMNS)
   {
-    hipLaunchKernelGGL((dist_classify_kernel<true>), dim3((a.n_cols + 3u) / 4u), dim3(256), 0, s, a);
-    dist_mark(m, 1);
+    hipLaunchKernelGGL((dist_classify_kernel<true>), dim3((a.box.n_cols + 3u) / 4u), dim3(256), 0, s, a);
+    t.mark(1, s);
     dist_line(s, p0, p1, 1u, nx, ny, R);
-    dist_mark(m, 2);
+    t.mark(2, s);
     r.in = p1;
     r.len = ny;
     hipLaunchKernelGGL(dist_row_kernel, dim3(nx, (ny + DIST_ROW - 1) / DIST_ROW), dim3(DIST_ROW), 0, s, r);
-    dist_mark(m, 3);
+    t.mark(3, s);
   }
   else
   {
-    hipLaunchKernelGGL((dist_classify_kernel<false>), dim3((a.n_cols + 3u) / 4u), dim3(256), 0, s, a);
-    dist_mark(m, 1);
+    hipLaunchKernelGGL((dist_classify_kernel<false>), dim3((a.box.n_cols + 3u) / 4u), dim3(256), 0, s, a);
+    t.mark(1, s);
     dist_line(s, p0, p1, 1u, nx, ny * nz, R); // ny nz < 2^32: the records are counted in 32 bits
-    dist_mark(m, 2);
+    t.mark(2, s);
     dist_line(s, p1, p0, nx, ny, nz, R);
-    dist_mark(m, 3);
+    t.mark(3, s);
     r.in = p0;
     r.len = nz;
-    hipLaunchKernelGGL(dist_row_kernel, dim3(a.n_cols, (nz + DIST_ROW - 1) / DIST_ROW), dim3(DIST_ROW), 0, s, r);
+    hipLaunchKernelGGL(dist_row_kernel, dim3(a.box.n_cols, (nz + DIST_ROW - 1) / DIST_ROW), dim3(DIST_ROW), 0, s, r);
   }
-  dist_mark(m, 4);
+  t.mark(4, s);
   WS_HIP(hipGetLastError());
-  WS_HIP(hipMemcpyAsync(m->dist_sites_host, m->dist_sites_dev, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-  return WS_OK;
+  return m->dist.sites.fetch(s);
 }
 
 } // namespace ws

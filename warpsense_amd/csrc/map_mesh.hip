@@ -33,11 +33,8 @@ constexpr uint32_t MESH_WORDS = 256; // words per workgroup of the word passes (
 
 struct MeshArgs
 {
-  const uint32_t *data;
-  MapParams mp;
-  int32_t lo[3];
-  int32_t ex, ey, ez;
-  uint32_t n_cols, nw, n_words; // columns of the box, words per column, n_cols * nw (< 2^31)
+  BoxArgs box;
+  uint32_t nw, n_words; // words per column, box.n_cols * nw (< 2^31)
   int32_t res;
   uint32_t any_weight;
   mu64 *valid, *inside, *act; // [n_words]
@@ -59,13 +56,10 @@ __global__ __launch_bounds__(256) void mesh_bits_kernel(MeshArgs a)
 {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const uint32_t col = blockIdx.x * 4u + (uint32_t)wave;
-  if (col >= a.n_cols) return; // (the same for the whole wave; no barrier in this kernel)
-  const int32_t xr = (int32_t)(col / (uint32_t)a.ey), yr = (int32_t)(col - (uint32_t)xr * (uint32_t)a.ey);
-  const int32_t xi = ring(a.lo[0] + xr - a.mp.pos[0] + a.mp.offset[0] + a.mp.size[0], a.mp.size[0]);
-  const int32_t yi = ring(a.lo[1] + yr - a.mp.pos[1] + a.mp.offset[1] + a.mp.size[1], a.mp.size[1]);
-  const int32_t sz = a.mp.size[2];
-  const uint32_t *column = a.data + (int64_t)(xi * a.mp.size[1] + yi) * (int64_t)sz; // size[0] * size[1] < 2^31 (ws_map_create)
-  const int32_t zs0 = ring(a.lo[2] - a.mp.pos[2] + a.mp.offset[2] + sz, sz);       // storage z of the box's first world z
+  if (col >= a.box.n_cols) return; // (the same for the whole wave; no barrier in this kernel)
+  int32_t x, y, zs0;
+  const uint32_t *column = a.box.data + box_column(a.box, col, x, y, zs0);
+  const int32_t sz = a.box.mp.size[2];
   mu64 *vout = a.valid + (size_t)col * a.nw, *iout = a.inside + (size_t)col * a.nw;
   for (uint32_t w0 = 0; w0 < a.nw; w0 += 4)
   {
@@ -76,7 +70,7 @@ __global__ __launch_bounds__(256) void mesh_bits_kernel(MeshArgs a)
     {
       const int32_t z = (int32_t)(w0 + j) * 64 + lane;
       raw[j] = 0u; // weight 0: not valid; value 0: not inside
-      if (z < a.ez)
+      if (z < a.box.ez)
       {
         int32_t zs = zs0 + z; // < 2 sz
         if (zs >= sz) zs -= sz;
@@ -103,16 +97,16 @@ __global__ __launch_bounds__(256) void mesh_cells_kernel(MeshArgs a)
   const uint32_t t = blockIdx.x * MESH_WORDS + threadIdx.x;
   if (t >= a.n_words) return;
   const uint32_t col = t / a.nw, w = t - col * a.nw;
-  const int32_t x = (int32_t)(col / (uint32_t)a.ey), y = (int32_t)(col - (uint32_t)x * (uint32_t)a.ey);
+  const int32_t x = (int32_t)(col / (uint32_t)a.box.ey), y = (int32_t)(col - (uint32_t)x * (uint32_t)a.box.ey);
   mu64 A = 0;
-  if (x + 1 < a.ex && y + 1 < a.ey)
+  if (x + 1 < a.box.ex && y + 1 < a.box.ey)
   {
     const bool more = w + 1 < a.nw;
     mu64 V = ~0ull, any = 0, all = ~0ull, Vn = ~0ull, anyn = 0, alln = ~0ull; // of the four corner columns; *n: the next word
 #pragma unroll
     for (int c = 0; c < 4; ++c)
     {
-      const uint32_t tt = t + ((c >> 1) * (uint32_t)a.ey + (c & 1)) * a.nw;
+      const uint32_t tt = t + ((c >> 1) * (uint32_t)a.box.ey + (c & 1)) * a.nw;
       const mu64 v = a.valid[tt], i = a.inside[tt];
       const mu64 vn = more ? a.valid[tt + 1] : 0ull, in = more ? a.inside[tt + 1] : 0ull;
       V &= v, any |= i, all &= i;
@@ -135,7 +129,7 @@ struct QuadWords
 };
 __device__ __forceinline__ void quad_words(const MeshArgs &a, uint32_t t, uint32_t w, int32_t x, int32_t y, mu64 Ac, QuadWords &o)
 {
-  const uint32_t dy = a.nw, dx = (uint32_t)a.ey * a.nw;
+  const uint32_t dy = a.nw, dx = (uint32_t)a.box.ey * a.nw;
   const bool hx = x > 0, hy = y > 0, hw = w > 0;
   o.A[0] = Ac;
   o.A[1] = hy ? a.act[t - dy] : 0ull;
@@ -163,7 +157,7 @@ __global__ __launch_bounds__(256) void mesh_quads_kernel(MeshArgs a)
     if (Ac)
     {
       const uint32_t col = t / a.nw, w = t - col * a.nw;
-      const int32_t x = (int32_t)(col / (uint32_t)a.ey), y = (int32_t)(col - (uint32_t)x * (uint32_t)a.ey);
+      const int32_t x = (int32_t)(col / (uint32_t)a.box.ey), y = (int32_t)(col - (uint32_t)x * (uint32_t)a.box.ey);
       QuadWords q;
       quad_words(a, t, w, x, y, Ac, q);
       nv = (uint32_t)__popcll(Ac);
@@ -194,29 +188,7 @@ __global__ __launch_bounds__(256) void mesh_quads_kernel(MeshArgs a)
 // ---- exclusive scans of the workgroup totals: workgroup 0 the vertices, workgroup 1 the quads; every thread a contiguous piece
 __global__ __launch_bounds__(1024) void mesh_scan_kernel(MeshArgs a, uint32_t n)
 {
-  const uint32_t *tot = blockIdx.x ? a.qtot : a.vtot;
-  mu64 *off = blockIdx.x ? a.qoff : a.voff;
-  __shared__ mu64 part[1024];
-  const uint32_t t = threadIdx.x, seg = (n + 1023u) / 1024u;
-  const uint32_t b = min(n, t * seg), e = min(n, b + seg);
-  mu64 s = 0;
-  for (uint32_t i = b; i < e; ++i) s += tot[i];
-  part[t] = s;
-  __syncthreads();
-  for (uint32_t d = 1; d < 1024; d <<= 1)
-  {
-    const mu64 v = t >= d ? part[t - d] : 0ull;
-    __syncthreads();
-    part[t] += v;
-    __syncthreads();
-  }
-  mu64 run = part[t] - s;
-  for (uint32_t i = b; i < e; ++i)
-  {
-    off[i] = run;
-    run += tot[i];
-  }
-  if (t == 1023) a.totals[blockIdx.x] = part[1023];
+  scan_block_totals(blockIdx.x ? a.qtot : a.vtot, blockIdx.x ? a.qoff : a.voff, n, a.totals + blockIdx.x);
 }
 
 // exclusive scan of one value per thread over the workgroup (256 threads)
@@ -260,8 +232,7 @@ __global__ __launch_bounds__(256) void mesh_vertex_kernel(MeshArgs a)
   sA[threadIdx.x] = At;
   sB[threadIdx.x] = base;
   __syncthreads();
-  const int32_t sz = a.mp.size[2];
-  const int32_t zs0 = ring(a.lo[2] - a.mp.pos[2] + a.mp.offset[2] + sz, sz);
+  const int32_t sz = a.box.mp.size[2], sy = a.box.mp.size[1];
   const int32_t res = a.res;
   for (int i = 0; i < 64; ++i) // the wave's 64 words, one after the other; lane = z inside the word
   {
@@ -269,12 +240,12 @@ __global__ __launch_bounds__(256) void mesh_vertex_kernel(MeshArgs a)
     const mu64 A = sA[idx];
     if (!((A >> lane) & 1ull)) continue; // (most words have no active cell)
     const uint32_t tt = t0 + (uint32_t)idx, col = tt / a.nw, w = tt - col * a.nw;
-    const int32_t x = (int32_t)(col / (uint32_t)a.ey), y = (int32_t)(col - (uint32_t)x * (uint32_t)a.ey), z = (int32_t)w * 64 + lane;
+    const int32_t z = (int32_t)w * 64 + lane;
     const mu64 out = (mu64)sB[idx] + popc_below(A, lane);
     // the eight corners: storage columns of x, x + 1 and y, y + 1, storage z of z and z + 1 (each one step along the ring)
-    const int32_t xi0 = ring(a.lo[0] + x - a.mp.pos[0] + a.mp.offset[0] + a.mp.size[0], a.mp.size[0]);
-    const int32_t yi0 = ring(a.lo[1] + y - a.mp.pos[1] + a.mp.offset[1] + a.mp.size[1], a.mp.size[1]);
-    const int32_t xi1 = xi0 + 1 == a.mp.size[0] ? 0 : xi0 + 1, yi1 = yi0 + 1 == a.mp.size[1] ? 0 : yi0 + 1;
+    int32_t x, y, xi0, yi0, zs0; // x, y: of the world
+    box_column_xy(a.box, col, x, y, xi0, yi0, zs0);
+    const int32_t xi1 = xi0 + 1 == a.box.mp.size[0] ? 0 : xi0 + 1, yi1 = yi0 + 1 == sy ? 0 : yi0 + 1;
     int32_t zi0 = zs0 + z;
     if (zi0 >= sz) zi0 -= sz;
     const int32_t zi1 = zi0 + 1 == sz ? 0 : zi0 + 1;
@@ -284,7 +255,7 @@ __global__ __launch_bounds__(256) void mesh_vertex_kernel(MeshArgs a)
     for (int k = 0; k < 8; ++k) // k = dx * 4 + dy * 2 + dz
     {
       const int32_t xi = (k & 4) ? xi1 : xi0, yi = (k & 2) ? yi1 : yi0, zi = (k & 1) ? zi1 : zi0;
-      const uint32_t raw = a.data[(int64_t)(xi * a.mp.size[1] + yi) * (int64_t)sz + zi];
+      const uint32_t raw = a.box.data[(int64_t)(xi * sy + yi) * (int64_t)sz + zi];
       v[k] = entry_value(raw);
       wmin = min(wmin, (uint32_t)iabs32(entry_weight(raw))); // (weights are positive unless WS_MESH_ANY_WEIGHT admits negative ones)
     }
@@ -308,7 +279,7 @@ __global__ __launch_bounds__(256) void mesh_vertex_kernel(MeshArgs a)
     }
     if (out < a.vcap) // (the count pass sized the buffer; a map that changed in between must not write beyond it)
     {
-      const int32_t c3[3] = {a.lo[0] + x, a.lo[1] + y, a.lo[2] + z};
+      const int32_t c3[3] = {x, y, a.box.lo[2] + z};
       int32_t p[3];
 #pragma unroll
       for (int d = 0; d < 3; ++d) p[d] = c3[d] * res + res / 2 + (int32_t)div_trunc_i64(s[d], n > 0 ? n : 1); // fits: the host checked the box
@@ -342,13 +313,13 @@ __global__ __launch_bounds__(256) void mesh_face_kernel(MeshArgs a)
   sQ[threadIdx.x] = c;
   sF[threadIdx.x] = a.qoff[blockIdx.x] + pre;
   __syncthreads();
-  const uint32_t dy = a.nw, dx = (uint32_t)a.ey * a.nw;
+  const uint32_t dy = a.nw, dx = (uint32_t)a.box.ey * a.nw;
   for (int i = 0; i < 64; ++i)
   {
     const int idx = wave * 64 + i;
     if (sQ[idx] == 0u) continue; // (the same for the whole wave)
     const uint32_t tt = t0 + (uint32_t)idx, col = tt / a.nw, w = tt - col * a.nw;
-    const int32_t x = (int32_t)(col / (uint32_t)a.ey), y = (int32_t)(col - (uint32_t)x * (uint32_t)a.ey);
+    const int32_t x = (int32_t)(col / (uint32_t)a.box.ey), y = (int32_t)(col - (uint32_t)x * (uint32_t)a.box.ey);
     QuadWords q;
     quad_words(a, tt, w, x, y, a.act[tt], q);
     const bool k0 = (q.q[0] >> lane) & 1ull, k1 = (q.q[1] >> lane) & 1ull, k2 = (q.q[2] >> lane) & 1ull;
@@ -376,21 +347,16 @@ size_t mesh_scratch_bytes(uint64_t n_words)
   return 3 * up256(nwd * 8) + up256(nwd * 4) + up256(nwd) + 2 * up256(nb * 4) + 2 * up256(nb * 8) + 256;
 }
 
-static void mesh_args(MeshArgs &a, const ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], uint32_t flags)
+static MeshArgs mesh_args(const ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], uint32_t flags, mu64 vcap, mu64 qcap)
 {
-  a.data = m->data[which];
-  a.mp = m->par[which];
-  for (int k = 0; k < 3; ++k) a.lo[k] = lo[k];
-  a.ex = ext[0];
-  a.ey = ext[1];
-  a.ez = ext[2];
-  a.n_cols = (uint32_t)((int64_t)ext[0] * ext[1]);
+  MeshArgs a;
+  a.box = box_args(m, which, lo, ext);
   a.nw = (uint32_t)((ext[2] + 63) / 64);
-  a.n_words = a.n_cols * a.nw;
+  a.n_words = a.box.n_cols * a.nw;
   a.res = m->res;
   a.any_weight = (flags & WS_MESH_ANY_WEIGHT) ? 1u : 0u;
   const size_t nwd = a.n_words, nb = mesh_blocks(a.n_words);
-  char *p = static_cast<char *>(m->mesh_scratch);
+  char *p = static_cast<char *>(m->mesh.scratch.p);
   auto take = [&p](size_t bytes) {
     char *r = p;
     p += up256(bytes);
@@ -406,49 +372,41 @@ static void mesh_args(MeshArgs &a, const ws_map *m, int which, const int32_t lo[
   a.voff = reinterpret_cast<mu64 *>(take(nb * 8));
   a.qoff = reinterpret_cast<mu64 *>(take(nb * 8));
   a.totals = reinterpret_cast<mu64 *>(take(16));
-  a.vert = reinterpret_cast<mi32x4 *>(m->mesh_vert);
-  a.face = m->mesh_face;
-  a.vcap = 0;
-  a.qcap = 0;
+  a.vert = static_cast<mi32x4 *>(m->mesh.vert.p);
+  a.face = static_cast<uint32_t *>(m->mesh.face.p);
+  a.vcap = vcap;
+  a.qcap = qcap;
+  return a;
 }
 
-static void mesh_mark(ws_map *m, int i)
-{
-  if (m->mesh_timing) (void)hipEventRecord(m->mesh_ev[i], m->ctx->stream);
-}
-
-// bits, cells, quads and the scans; the two totals arrive in m->mesh_total_host (pinned) once the stream has been synchronised
+// bits, cells, quads and the scans; the two totals arrive in m->mesh.total.host (pinned) once the stream has been synchronised
 int launch_mesh_count(ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], uint32_t flags)
 {
-  MeshArgs a;
-  mesh_args(a, m, which, lo, ext, flags);
+  const MeshArgs a = mesh_args(m, which, lo, ext, flags, 0, 0);
   const uint32_t blocks = mesh_blocks(a.n_words);
   hipStream_t s = m->ctx->stream;
-  mesh_mark(m, 0);
-  hipLaunchKernelGGL(mesh_bits_kernel, dim3((a.n_cols + 3) / 4), dim3(256), 0, s, a);
+  QueryTimer &t = m->mesh.timer;
+  t.mark(0, s);
+  hipLaunchKernelGGL(mesh_bits_kernel, dim3((a.box.n_cols + 3) / 4), dim3(256), 0, s, a);
   hipLaunchKernelGGL(mesh_cells_kernel, dim3(blocks), dim3(256), 0, s, a);
   hipLaunchKernelGGL(mesh_quads_kernel, dim3(blocks), dim3(256), 0, s, a);
-  mesh_mark(m, 1);
+  t.mark(1, s);
   hipLaunchKernelGGL(mesh_scan_kernel, dim3(2), dim3(1024), 0, s, a, blocks);
-  mesh_mark(m, 2);
+  t.mark(2, s);
   WS_HIP(hipGetLastError());
-  WS_HIP(hipMemcpyAsync(m->mesh_total_host, a.totals, 2 * sizeof(mu64), hipMemcpyDeviceToHost, s));
-  return WS_OK;
+  return m->mesh.total.fetch(s, 2, a.totals);
 }
 
 // vertices, then faces (which read the vertex pass's vbase)
 int launch_mesh_emit(ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], uint32_t flags)
 {
-  MeshArgs a;
-  mesh_args(a, m, which, lo, ext, flags);
-  a.vcap = m->mesh_vert_cap;
-  a.qcap = m->mesh_face_cap / 2;
+  const MeshArgs a = mesh_args(m, which, lo, ext, flags, m->mesh.vert.cap, m->mesh.face.cap / 2);
   const uint32_t blocks = mesh_blocks(a.n_words);
   hipStream_t s = m->ctx->stream;
-  mesh_mark(m, 3);
+  m->mesh.timer.mark(3, s);
   hipLaunchKernelGGL(mesh_vertex_kernel, dim3(blocks), dim3(256), 0, s, a);
   hipLaunchKernelGGL(mesh_face_kernel, dim3(blocks), dim3(256), 0, s, a);
-  mesh_mark(m, 4);
+  m->mesh.timer.mark(4, s);
   WS_HIP(hipGetLastError());
   return WS_OK;
 }

@@ -295,12 +295,7 @@ __global__ __launch_bounds__(64) void raycast_grad_kernel(RayArgs a)
   a.grad[3 * (size_t)i + 2] = g[2];
 }
 
-static void ray_mark(ws_map *m, int i)
-{
-  if (m->ray_timing) (void)hipEventRecord(m->ray_ev[i], m->ctx->stream);
-}
-
-// the march (events 1, 2), then the gradient if asked for (events 2, 3); the hit count arrives in m->ray_hits_host (pinned)
+// the march (events 1, 2), then the gradient if asked for (events 2, 3); the hit count arrives in m->ray.hits.host (pinned)
 // once the stream has been synchronised
 int launch_raycast(ws_map *m, int which, const int32_t origin[3], const int32_t *dirs_dev, size_t n, int32_t max_range, uint32_t flags)
 {
@@ -321,20 +316,19 @@ int launch_raycast(ws_map *m, int which, const int32_t origin[3], const int32_t 
   a.K = (uint32_t)(max_range / a.step);
   a.rdiv = make_fastdiv(m->res);
   a.flags = flags;
-  a.rec = reinterpret_cast<ri32x4 *>(m->ray_rec);
-  a.grad = m->ray_grad;
-  a.hits = m->ray_hits_dev;
+  a.rec = static_cast<ri32x4 *>(m->ray.rec.p);
+  a.grad = static_cast<int32_t *>(m->ray.grad.p);
+  a.hits = m->ray.hits.dev;
   hipStream_t s = m->ctx->stream;
   const uint32_t blocks = (uint32_t)((n + 63) / 64);
-  WS_HIP(hipMemsetAsync(m->ray_hits_dev, 0, sizeof(unsigned long long), s));
-  ray_mark(m, 1);
+  WS_HIP(hipMemsetAsync(a.hits, 0, sizeof(unsigned long long), s));
+  m->ray.timer.mark(1, s);
   hipLaunchKernelGGL(raycast_kernel, dim3(blocks), dim3(64), 0, s, a);
-  ray_mark(m, 2);
+  m->ray.timer.mark(2, s);
   if (flags & WS_RAYCAST_GRADIENT) hipLaunchKernelGGL(raycast_grad_kernel, dim3(blocks), dim3(64), 0, s, a);
-  ray_mark(m, 3);
+  m->ray.timer.mark(3, s);
   WS_HIP(hipGetLastError());
-  WS_HIP(hipMemcpyAsync(m->ray_hits_host, m->ray_hits_dev, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-  return WS_OK;
+  return m->ray.hits.fetch(s);
 }
 
 } // namespace ws

@@ -25,11 +25,7 @@ constexpr int SURF_COUNT = 0, SURF_EMIT = 1, SURF_EMIT_MARKER = 2;
 
 struct SurfArgs
 {
-  const uint32_t *data;
-  MapParams mp;
-  int32_t lo[3];
-  int32_t ey, ez;
-  uint32_t n_cols;
+  BoxArgs box;
   int32_t band, tau, res;
   uint32_t *col_cnt;                  // [n_cols]
   uint32_t *blk_tot;                  // [workgroups]
@@ -54,7 +50,7 @@ __global__ __launch_bounds__(256) void surface_kernel(SurfArgs a)
   unsigned long long base = 0;
   if (MODE != SURF_COUNT)
   {
-    const uint32_t c = (lane < SURF_COLS && col0 + lane < a.n_cols) ? a.col_cnt[col0 + lane] : 0u;
+    const uint32_t c = (lane < SURF_COLS && col0 + lane < a.box.n_cols) ? a.col_cnt[col0 + lane] : 0u;
     uint32_t inc = c;
 #pragma unroll
     for (int d = 1; d < SURF_COLS; d <<= 1)
@@ -65,21 +61,16 @@ __global__ __launch_bounds__(256) void surface_kernel(SurfArgs a)
     before = inc - c;
     base = a.blk_off[blockIdx.x];
   }
-  const int32_t sz = a.mp.size[2];
-  const int32_t zs0 = ring(a.lo[2] - a.mp.pos[2] + a.mp.offset[2] + sz, sz); // storage z of the box's first world z
-  const int32_t len_a = min(a.ez, sz - zs0);                                  // voxels up to the ring seam; the rest starts at storage z 0
   const float fres = (float)a.res, ftau = (float)a.tau;
   uint32_t wave_total = 0;
   for (int k = 0; k < SURF_COLS / SURF_WAVES; ++k)
   {
     const int ci = wave * (SURF_COLS / SURF_WAVES) + k;
     const uint32_t col = col0 + (uint32_t)ci;
-    if (col >= a.n_cols) break; // (the same for the whole wave)
-    const int32_t xr = (int32_t)(col / (uint32_t)a.ey), yr = (int32_t)(col - (uint32_t)xr * (uint32_t)a.ey);
-    const int32_t x = a.lo[0] + xr, y = a.lo[1] + yr;
-    const int32_t xi = ring(x - a.mp.pos[0] + a.mp.offset[0] + a.mp.size[0], a.mp.size[0]);
-    const int32_t yi = ring(y - a.mp.pos[1] + a.mp.offset[1] + a.mp.size[1], a.mp.size[1]);
-    const int64_t cbase = (int64_t)(xi * a.mp.size[1] + yi) * (int64_t)sz; // size[0] * size[1] < 2^31 (ws_map_create)
+    if (col >= a.box.n_cols) break; // (the same for the whole wave)
+    int32_t x, y, zs0;
+    const int64_t cbase = box_column(a.box, col, x, y, zs0);
+    const int32_t len_a = min(a.box.ez, a.box.mp.size[2] - zs0); // voxels up to the ring seam; the rest starts at storage z 0
     unsigned long long out = base + __shfl(before, ci, 64);
     // publish_local_map's point (map.h:51-53): (float)x * (float)map_resolution / 1000.f -- a rounded product, then a correctly
     // rounded division (no contraction, no reciprocal: -ffp-contract=off and hipcc's default IEEE division)
@@ -88,15 +79,15 @@ __global__ __launch_bounds__(256) void surface_kernel(SurfArgs a)
 #pragma unroll
     for (int run = 0; run < 2; ++run)
     {
-      const int32_t len = run ? a.ez - len_a : len_a;
+      const int32_t len = run ? a.box.ez - len_a : len_a;
       if (len <= 0) continue;
-      const int32_t zw0 = a.lo[2] + (run ? len_a : 0); // world z of the run's first voxel
+      const int32_t zw0 = a.box.lo[2] + (run ? len_a : 0); // world z of the run's first voxel
       const int64_t first = cbase + (run ? 0 : zs0), last = first + len;
       for (int64_t g0 = first & ~(int64_t)3; g0 < last; g0 += 256)
       {
         const int64_t g = g0 + 4 * lane;
         su32x4 v = {0u, 0u, 0u, 0u};
-        if (g < last) v = __builtin_nontemporal_load(reinterpret_cast<const su32x4 *>(a.data + g));
+        if (g < last) v = __builtin_nontemporal_load(reinterpret_cast<const su32x4 *>(a.box.data + g));
         const uint32_t raw[4] = {v.x, v.y, v.z, v.w};
         bool q[4];
 #pragma unroll
@@ -158,91 +149,60 @@ __global__ __launch_bounds__(256) void surface_kernel(SurfArgs a)
   }
 }
 
-// exclusive scan of the workgroup totals: 16 K words for a 513^3 window, 256 K for 2049^3 -- one workgroup, every thread a
-// contiguous piece
+// exclusive scan of the workgroup totals
 __global__ __launch_bounds__(1024) void surface_scan_kernel(const uint32_t *tot, unsigned long long *off, uint32_t n, unsigned long long *total)
 {
-  __shared__ unsigned long long part[1024];
-  const uint32_t t = threadIdx.x, seg = (n + 1023u) / 1024u;
-  const uint32_t b = min(n, t * seg), e = min(n, b + seg);
-  unsigned long long s = 0;
-  for (uint32_t i = b; i < e; ++i) s += tot[i];
-  part[t] = s;
-  __syncthreads();
-  for (uint32_t d = 1; d < 1024; d <<= 1)
-  {
-    const unsigned long long v = t >= d ? part[t - d] : 0ull;
-    __syncthreads();
-    part[t] += v;
-    __syncthreads();
-  }
-  unsigned long long run = part[t] - s;
-  for (uint32_t i = b; i < e; ++i)
-  {
-    off[i] = run;
-    run += tot[i];
-  }
-  if (t == 1023) *total = part[1023];
+  scan_block_totals(tot, off, n, total);
 }
 
 static uint32_t surf_blocks(uint32_t n_cols) { return (n_cols + SURF_COLS - 1) / SURF_COLS; }
 
-static void surf_args(SurfArgs &a, const ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], int32_t band)
+static SurfArgs surf_args(const ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], int32_t band, size_t cap)
 {
-  a.data = m->data[which];
-  a.mp = m->par[which];
-  for (int k = 0; k < 3; ++k) a.lo[k] = lo[k];
-  a.ey = ext[1];
-  a.ez = ext[2];
-  a.n_cols = (uint32_t)((int64_t)ext[0] * ext[1]);
+  SurfArgs a;
+  a.box = box_args(m, which, lo, ext);
   a.band = band;
   a.tau = m->tau;
   a.res = m->res;
-  a.col_cnt = m->surf_col_cnt;
-  a.blk_tot = m->surf_blk_tot;
-  a.blk_off = m->surf_blk_off;
-  a.rec = reinterpret_cast<su32x4 *>(m->surf_rec);
-  a.marker = m->surf_marker;
-  a.cap = 0;
-}
-
-static void surf_mark(ws_map *m, int i)
-{
-  if (m->surf_timing) (void)hipEventRecord(m->surf_ev[i], m->ctx->stream);
+  a.col_cnt = static_cast<uint32_t *>(m->surf.col_cnt.p);
+  a.blk_tot = static_cast<uint32_t *>(m->surf.blk_tot.p);
+  a.blk_off = static_cast<unsigned long long *>(m->surf.blk_off.p);
+  a.rec = static_cast<su32x4 *>(m->surf.rec.p);
+  a.marker = static_cast<float *>(m->surf.marker.p);
+  a.cap = cap;
+  return a;
 }
 
 size_t surface_blocks_for(int64_t n_cols) { return (size_t)surf_blocks((uint32_t)n_cols); }
 
-// passes 1 and 2; the total arrives in m->surf_total_host (pinned) once the stream has been synchronised
+// passes 1 and 2; the total arrives in m->surf.total.host (pinned) once the stream has been synchronised
 int launch_surface_count(ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], int32_t band)
 {
-  SurfArgs a;
-  surf_args(a, m, which, lo, ext, band);
-  const uint32_t blocks = surf_blocks(a.n_cols);
+  const SurfArgs a = surf_args(m, which, lo, ext, band, 0);
+  const uint32_t blocks = surf_blocks(a.box.n_cols);
   hipStream_t s = m->ctx->stream;
-  surf_mark(m, 0);
+  QueryTimer &t = m->surf.timer;
+  t.mark(0, s);
   hipLaunchKernelGGL((surface_kernel<SURF_COUNT>), dim3(blocks), dim3(256), 0, s, a);
-  surf_mark(m, 1);
-  hipLaunchKernelGGL(surface_scan_kernel, dim3(1), dim3(1024), 0, s, (const uint32_t *)m->surf_blk_tot, m->surf_blk_off, blocks, m->surf_total_dev);
-  surf_mark(m, 2);
+  t.mark(1, s);
+  hipLaunchKernelGGL(surface_scan_kernel, dim3(1), dim3(1024), 0, s, (const uint32_t *)a.blk_tot, static_cast<unsigned long long *>(m->surf.blk_off.p), blocks, m->surf.total.dev);
+  t.mark(2, s);
   WS_HIP(hipGetLastError());
-  WS_HIP(hipMemcpyAsync(m->surf_total_host, m->surf_total_dev, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-  return WS_OK;
+  return m->surf.total.fetch(s);
 }
 
-// pass 3
-int launch_surface_emit(ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], int32_t band, bool marker)
+// pass 3: no record at or beyond `cap` is written
+int launch_surface_emit(ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], int32_t band, bool marker, size_t cap)
 {
-  SurfArgs a;
-  surf_args(a, m, which, lo, ext, band);
-  a.cap = m->surf_cap;
-  const uint32_t blocks = surf_blocks(a.n_cols);
-  surf_mark(m, 3);
+  const SurfArgs a = surf_args(m, which, lo, ext, band, cap);
+  const uint32_t blocks = surf_blocks(a.box.n_cols);
+  hipStream_t s = m->ctx->stream;
+  m->surf.timer.mark(3, s);
   if (marker)
-    hipLaunchKernelGGL((surface_kernel<SURF_EMIT_MARKER>), dim3(blocks), dim3(256), 0, m->ctx->stream, a);
+    hipLaunchKernelGGL((surface_kernel<SURF_EMIT_MARKER>), dim3(blocks), dim3(256), 0, s, a);
   else
-    hipLaunchKernelGGL((surface_kernel<SURF_EMIT>), dim3(blocks), dim3(256), 0, m->ctx->stream, a);
-  surf_mark(m, 4);
+    hipLaunchKernelGGL((surface_kernel<SURF_EMIT>), dim3(blocks), dim3(256), 0, s, a);
+  m->surf.timer.mark(4, s);
   WS_HIP(hipGetLastError());
   return WS_OK;
 }

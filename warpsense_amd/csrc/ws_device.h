@@ -125,6 +125,74 @@ __device__ __forceinline__ int64_t get_index(const MapParams &m, int32_t x, int3
   return (int64_t)row * (int64_t)m.size[2] + zi;
 }
 
+// ---- the box queries (map_surface.hip, map_mesh.hip, map_distance.hip): the map and the box as their kernels see them
+struct BoxArgs
+{
+  const uint32_t *data;
+  MapParams mp;
+  int32_t lo[3];      // the box's first world voxel
+  int32_t ex, ey, ez; // its extent
+  uint32_t n_cols;    // (x, y) columns: ex * ey < 2^31
+};
+inline BoxArgs box_args(const ws_map *m, int which, const int32_t lo[3], const int32_t ext[3])
+{
+  BoxArgs b;
+  b.data = m->data[which];
+  b.mp = m->par[which];
+  for (int k = 0; k < 3; ++k) b.lo[k] = lo[k];
+  b.ex = ext[0];
+  b.ey = ext[1];
+  b.ez = ext[2];
+  b.n_cols = (uint32_t)((int64_t)ext[0] * ext[1]);
+  return b;
+}
+// Column `col` = xr * ey + yr of the box: its world x and y, their storage indices, and the storage z of the box's first world z.
+// Memory is z fastest and rotated by `offset` on every axis (get_index), so the world-order z run of the column is [zs0, size_z),
+// then [0, ...).
+__device__ __forceinline__ void box_column_xy(const BoxArgs &b, uint32_t col, int32_t &x, int32_t &y, int32_t &xi, int32_t &yi, int32_t &zs0)
+{
+  const int32_t xr = (int32_t)(col / (uint32_t)b.ey), yr = (int32_t)(col - (uint32_t)xr * (uint32_t)b.ey);
+  x = b.lo[0] + xr;
+  y = b.lo[1] + yr;
+  xi = ring(x - b.mp.pos[0] + b.mp.offset[0] + b.mp.size[0], b.mp.size[0]);
+  yi = ring(y - b.mp.pos[1] + b.mp.offset[1] + b.mp.size[1], b.mp.size[1]);
+  zs0 = ring(b.lo[2] - b.mp.pos[2] + b.mp.offset[2] + b.mp.size[2], b.mp.size[2]);
+}
+// ... and the storage index of the column's storage z 0
+__device__ __forceinline__ int64_t box_column(const BoxArgs &b, uint32_t col, int32_t &x, int32_t &y, int32_t &zs0)
+{
+  int32_t xi, yi;
+  box_column_xy(b, col, x, y, xi, yi, zs0);
+  return (int64_t)(xi * b.mp.size[1] + yi) * (int64_t)b.mp.size[2]; // size[0] * size[1] < 2^31 (ws_map_create)
+}
+
+// Exclusive scan of n workgroup totals by ONE workgroup of 1024 threads, every thread a contiguous piece (16 K words for the columns
+// of a 513^3 window, 256 K for 2049^3); *total is the sum
+__device__ __forceinline__ void scan_block_totals(const uint32_t *tot, unsigned long long *off, uint32_t n, unsigned long long *total)
+{
+  __shared__ unsigned long long part[1024];
+  const uint32_t t = threadIdx.x, seg = (n + 1023u) / 1024u;
+  const uint32_t b = min(n, t * seg), e = min(n, b + seg);
+  unsigned long long s = 0;
+  for (uint32_t i = b; i < e; ++i) s += tot[i];
+  part[t] = s;
+  __syncthreads();
+  for (uint32_t d = 1; d < 1024; d <<= 1)
+  {
+    const unsigned long long v = t >= d ? part[t - d] : 0ull;
+    __syncthreads();
+    part[t] += v;
+    __syncthreads();
+  }
+  unsigned long long run = part[t] - s;
+  for (uint32_t i = b; i < e; ++i)
+  {
+    off[i] = run;
+    run += tot[i];
+  }
+  if (t == 1023) *total = part[1023];
+}
+
 // DeviceMap::in_bounds — device_map.h:109-114
 __device__ __forceinline__ bool in_bounds(const MapParams &m, int32_t x, int32_t y, int32_t z)
 {

@@ -191,6 +191,116 @@ struct GnState
   int64_t sums[44]; // last h(36) g(6) e c
 };
 
+void set_error(const std::string &msg);
+int hip_fail(hipError_t e, const char *what, const char *file, int line);
+
+#define WS_HIP(call)                                                     \
+  do                                                                     \
+  {                                                                      \
+    hipError_t e__ = (call);                                             \
+    if (e__ != hipSuccess) return ws::hip_fail(e__, #call, __FILE__, __LINE__); \
+  } while (0)
+
+// ---- host state of the map queries (ws_map::surf, mesh, ray, dist): allocated on first use, grown on demand
+// a device buffer whose contents are not kept when it grows
+struct DevBuf
+{
+  void *p = nullptr;
+  size_t cap = 0; // elements
+  // room for at least `need` elements.  The caller has synchronised the stream.
+  int grow(size_t need, size_t elem_bytes)
+  {
+    if (need <= cap) return WS_OK;
+    if (p) WS_HIP(hipFree(p));
+    p = nullptr;
+    cap = 0;
+    need += need / 8; // a little room: a map that gains a few points per scan does not reallocate on every call
+    WS_HIP(hipMalloc(&p, need * elem_bytes));
+    cap = need;
+    return WS_OK;
+  }
+  void release()
+  {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+};
+
+// 64-bit words a query's kernels leave on the device, and the pinned words the host reads them from after a stream synchronise
+struct DevCounter
+{
+  unsigned long long *dev = nullptr, *host = nullptr;
+  int alloc(size_t words, bool on_device = true)
+  {
+    if (on_device && !dev) WS_HIP(hipMalloc((void **)&dev, words * sizeof(unsigned long long)));
+    if (!host) WS_HIP(hipHostMalloc((void **)&host, words * sizeof(unsigned long long), hipHostMallocDefault));
+    return WS_OK;
+  }
+  // enqueue the copy into the pinned words, from `dev` unless the device words live elsewhere
+  int fetch(hipStream_t s, size_t words = 1, const unsigned long long *from = nullptr)
+  {
+    WS_HIP(hipMemcpyAsync(host, from ? from : dev, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    return WS_OK;
+  }
+  void release()
+  {
+    if (dev) (void)hipFree(dev);
+    if (host) (void)hipHostFree(host);
+    dev = host = nullptr;
+  }
+};
+
+// events around the launches of a query (ws_debug_*_timing)
+struct QueryTimer
+{
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  bool on = false;
+  uint32_t marked = 0; // bit i: ev[i] has been recorded since the last arm() / set()
+  // the start of a query call: nothing recorded yet, and the events exist if they are wanted
+  int arm()
+  {
+    marked = 0;
+    if (on)
+      for (hipEvent_t &e : ev)
+        if (!e) WS_HIP(hipEventCreate(&e));
+    return WS_OK;
+  }
+  void mark(int i, hipStream_t s)
+  {
+    if (!on) return;
+    (void)hipEventRecord(ev[i], s);
+    marked |= 1u << i;
+  }
+  // ms_out[k]: from event pairs[k][0] to event pairs[k][1] of the last call, 0 unless that call recorded both
+  int read(float *ms_out, const int (*pairs)[2], int n, hipStream_t s)
+  {
+    if (!ms_out) return WS_OK;
+    for (int k = 0; k < n; ++k) ms_out[k] = 0.f;
+    if (!marked) return WS_OK;
+    WS_HIP(hipStreamSynchronize(s));
+    for (int k = 0; k < n; ++k)
+      if ((marked >> pairs[k][0]) & (marked >> pairs[k][1]) & 1u) WS_HIP(hipEventElapsedTime(&ms_out[k], ev[pairs[k][0]], ev[pairs[k][1]]));
+    return WS_OK;
+  }
+  // enable < 0: leave as it is; 0: off; 1: on, with a fresh set of events (those of an earlier enabled period are not read again)
+  void set(int32_t enable)
+  {
+    if (enable < 0) return;
+    if (!enable || !on) release();
+    on = enable != 0;
+    marked = 0;
+  }
+  void release()
+  {
+    for (hipEvent_t &e : ev)
+    {
+      if (e) (void)hipEventDestroy(e);
+      e = nullptr;
+    }
+  }
+};
+
 } // namespace ws
 
 struct ws_context
@@ -259,62 +369,50 @@ struct ws_map
   uint32_t *box_stage = nullptr; // device staging for ws_map_extract_box / ws_map_insert_box
   size_t box_stage_cap = 0;
   uint32_t last_error_bits = 0;  // device error bits already taken from status_host, not yet shown by ws_tsdf_stats
-  // ws_map_surface (map_surface.hip): the surface cloud of the last call and the scratch of its passes; all of it allocated on first
-  // use and grown on demand.  surf_mu serialises the calls that use these buffers (the reference's readers hold a SHARED lock).
-  std::mutex surf_mu;
-  uint32_t *surf_col_cnt = nullptr;            // [surf_cols_cap] qualifying voxels per (x, y) column of the box
-  uint32_t *surf_blk_tot = nullptr;            // [workgroups] the same per workgroup of the count pass
-  unsigned long long *surf_blk_off = nullptr;  // [workgroups] exclusive scan
-  size_t surf_cols_cap = 0;
-  unsigned long long *surf_total_dev = nullptr;  // the scan's last element
-  unsigned long long *surf_total_host = nullptr; // pinned
-  void *surf_rec = nullptr;                    // [surf_cap] 16-byte records
-  float *surf_marker = nullptr;                // [surf_marker_cap][7]
-  size_t surf_cap = 0, surf_marker_cap = 0;
-  size_t surf_n = 0;                           // records of the last call
-  bool surf_has_marker = false;                // the last call also wrote surf_marker
-  bool surf_timing = false;                    // ws_debug_surface_timing: events around the three launches
-  hipEvent_t surf_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  bool surf_ev_emit = false;                   // the last call launched the emit pass (events 3, 4 are recorded)
-  // ws_map_mesh (map_mesh.hip): the mesh of the last call and the scratch of its passes, apart from the surface cloud's; allocated on
-  // first use and grown on demand.  mesh_mu serialises the calls that use these buffers.
-  std::mutex mesh_mu;
-  void *mesh_scratch = nullptr;                // bit planes, per-word bases and counts, workgroup totals and their scans (mesh_scratch_bytes)
-  size_t mesh_scratch_cap = 0;                 // bytes
-  unsigned long long *mesh_total_host = nullptr; // pinned: vertices, quads
-  void *mesh_vert = nullptr;                   // [mesh_vert_cap] 16-byte vertices
-  uint32_t *mesh_face = nullptr;               // [mesh_face_cap][3]
-  size_t mesh_vert_cap = 0, mesh_face_cap = 0;
-  size_t mesh_nv = 0, mesh_nf = 0;             // vertices and faces of the last call
-  bool mesh_timing = false;                    // ws_debug_mesh_timing: events around the count passes, the scan and the emit passes
-  hipEvent_t mesh_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  bool mesh_ev_count = false, mesh_ev_emit = false; // the last call recorded events 0..2 / 3, 4
-  // ws_map_raycast (map_raycast.hip): the records of the last call, apart from the surface cloud's and the mesh's; allocated on first
-  // use and grown on demand.  ray_mu serialises the calls that use these buffers.
-  std::mutex ray_mu;
-  int32_t *ray_dirs = nullptr;                 // [ray_dirs_cap][3] staging of host directions
-  void *ray_rec = nullptr;                     // [ray_rec_cap] 16-byte records
-  int32_t *ray_grad = nullptr;                 // [ray_grad_cap][3]
-  size_t ray_dirs_cap = 0, ray_rec_cap = 0, ray_grad_cap = 0;
-  unsigned long long *ray_hits_dev = nullptr;  // records with range_mm >= 0
-  unsigned long long *ray_hits_host = nullptr; // pinned
-  size_t ray_n = 0;                            // rays of the last call
-  bool ray_has_grad = false;                   // the last call also wrote ray_grad
-  bool ray_timing = false;                     // ws_debug_raycast_timing: events around the upload, the march and the gradient
-  hipEvent_t ray_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  bool ray_ev_done = false;                    // the last call recorded them
-  // ws_map_distance (map_distance.hip): the records of the last call and the two 16-bit planes of its line passes, apart from the
-  // results of the three calls above; allocated on first use and grown on demand.  dist_mu serialises the calls that use them.
-  std::mutex dist_mu;
-  uint32_t *dist_rec = nullptr;                // [dist_rec_cap] one record per voxel (per column under WS_DISTANCE_COLUMNS)
-  uint16_t *dist_plane = nullptr;              // [2][dist_plane_cap] ping-pong planes of the running minimum
-  size_t dist_rec_cap = 0, dist_plane_cap = 0;
-  unsigned long long *dist_sites_dev = nullptr;  // site voxels / site columns of the last call
-  unsigned long long *dist_sites_host = nullptr; // pinned
-  size_t dist_n = 0;                           // records of the last call
-  bool dist_timing = false;                    // ws_debug_distance_timing: events around pass 0 and the line passes
-  hipEvent_t dist_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  bool dist_ev_done = false;                   // the last call recorded them
+  // The map queries: each keeps the result of its last call and the scratch of its passes apart from the others', all of it allocated
+  // on first use and grown on demand.  `mu` serialises the calls that use them (the reference's readers hold a SHARED lock).
+  struct Surface // ws_map_surface (map_surface.hip)
+  {
+    std::mutex mu;
+    ws::QueryTimer timer;                // events around the three launches: 0 count 1 scan 2, 3 emit 4
+    ws::DevBuf col_cnt;                  // uint32 [columns of the box] qualifying voxels per (x, y) column
+    ws::DevBuf blk_tot, blk_off;         // uint32 / uint64 [workgroups of the count pass] the same per workgroup, and its exclusive scan
+    ws::DevCounter total;                // the scan's last element
+    ws::DevBuf rec, marker;              // 16-byte records; 7 floats per record
+    size_t n = 0;                        // records of the last call
+    bool has_marker = false;             // the last call also wrote `marker`
+    void release() { timer.release(), total.release(); for (ws::DevBuf *b : {&col_cnt, &blk_tot, &blk_off, &rec, &marker}) b->release(); }
+  } surf;
+  struct Mesh // ws_map_mesh (map_mesh.hip)
+  {
+    std::mutex mu;
+    ws::QueryTimer timer;                // 0 count passes 1 scans 2, 3 emit passes 4
+    ws::DevBuf scratch;                  // bytes: bit planes, per-word bases and counts, workgroup totals and their scans (mesh_scratch_bytes)
+    ws::DevCounter total;                // pinned half only: vertices, quads (the device words are in `scratch`)
+    ws::DevBuf vert, face;               // 16-byte vertices; 3 indices per face
+    size_t nv = 0, nf = 0;               // vertices and faces of the last call
+    void release() { timer.release(), total.release(); for (ws::DevBuf *b : {&scratch, &vert, &face}) b->release(); }
+  } mesh;
+  struct Raycast // ws_map_raycast (map_raycast.hip)
+  {
+    std::mutex mu;
+    ws::QueryTimer timer;                // 0 upload 1 march 2 gradient 3
+    ws::DevBuf dirs, rec, grad;          // int32 [rays][3] staging of host directions; 16-byte records; int32 [rays][3]
+    ws::DevCounter hits;                 // records with range_mm >= 0
+    size_t n = 0;                        // rays of the last call
+    bool has_grad = false;               // the last call also wrote `grad`
+    void release() { timer.release(), hits.release(); for (ws::DevBuf *b : {&dirs, &rec, &grad}) b->release(); }
+  } ray;
+  struct Distance // ws_map_distance (map_distance.hip)
+  {
+    std::mutex mu;
+    ws::QueryTimer timer;                // 0 pass 0, 1 x 2 y 3 z 4
+    ws::DevBuf rec;                      // uint32: one record per voxel (per column under WS_DISTANCE_COLUMNS)
+    ws::DevBuf plane;                    // 2 x uint16 per record: ping-pong planes of the running minimum
+    ws::DevCounter sites;                // site voxels / site columns of the last call
+    size_t n = 0;                        // records of the last call
+    void release() { timer.release(), sites.release(); for (ws::DevBuf *b : {&rec, &plane}) b->release(); }
+  } dist;
   // The scan whose verdict (did its records fit the pool?) has not been looked at yet: ws_tsdf_update* return after the
   // launches, like the reference's update_tsdf (update_tsdf.cu:165); the next call that takes this map settles it first
   // (settle_tsdf: the verdict is in host-mapped memory ~0.35 ms after the launches) and repeats the scan if it was aborted.
@@ -435,16 +533,6 @@ struct ws_scan
 
 namespace ws
 {
-void set_error(const std::string &msg);
-int hip_fail(hipError_t e, const char *what, const char *file, int line);
-
-#define WS_HIP(call)                                                     \
-  do                                                                     \
-  {                                                                      \
-    hipError_t e__ = (call);                                             \
-    if (e__ != hipSuccess) return ws::hip_fail(e__, #call, __FILE__, __LINE__); \
-  } while (0)
-
 // profiling spans around a kernel class
 void prof_begin(ws_context *ctx, int cls);
 void prof_end(ws_context *ctx, int cls);
@@ -460,17 +548,18 @@ uint64_t subs_for_scan(const ws_map *m, uint64_t need_records, uint64_t n_points
 int launch_tsdf_integrate(ws_map *m);
 int launch_tsdf_stats(ws_map *m); // fills the last_* statistics of TsdfCounters from the per-workgroup slots
 int launch_box_copy(ws_map *m, const ws::MapParams &par, int which, const int32_t lo[3], const int32_t ext[3], uint32_t *box_dev, bool pack, hipStream_t stream);
-// map_surface.hip: count + scan (the total arrives in ws_map::surf_total_host after a stream synchronise), then the emit pass
+// map_surface.hip: count + scan (the total arrives in ws_map::surf.total.host after a stream synchronise), then the emit pass, which
+// writes no record at or beyond `cap`
 size_t surface_blocks_for(int64_t n_cols);
 int launch_surface_count(ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], int32_t band);
-int launch_surface_emit(ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], int32_t band, bool marker);
-// map_mesh.hip: bits + cells + quads + scans (the totals arrive in ws_map::mesh_total_host after a stream synchronise), then the emit passes
+int launch_surface_emit(ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], int32_t band, bool marker, size_t cap);
+// map_mesh.hip: bits + cells + quads + scans (the totals arrive in ws_map::mesh.total.host after a stream synchronise), then the emit passes
 size_t mesh_scratch_bytes(uint64_t n_words);
 int launch_mesh_count(ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], uint32_t flags);
 int launch_mesh_emit(ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], uint32_t flags);
-// map_raycast.hip: the march and, with WS_RAYCAST_GRADIENT, the gradient pass (the hit count arrives in ws_map::ray_hits_host after a stream synchronise)
+// map_raycast.hip: the march and, with WS_RAYCAST_GRADIENT, the gradient pass (the hit count arrives in ws_map::ray.hits.host after a stream synchronise)
 int launch_raycast(ws_map *m, int which, const int32_t origin[3], const int32_t *dirs_dev, size_t n, int32_t max_range, uint32_t flags);
-// map_distance.hip: pass 0 and the line passes over `n` records (the site count arrives in ws_map::dist_sites_host after a stream synchronise)
+// map_distance.hip: pass 0 and the line passes over `n` records (the site count arrives in ws_map::dist.sites.host after a stream synchronise)
 int launch_distance(ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], int32_t R, uint32_t flags, size_t n);
 int fill_u32(ws_context *ctx, uint32_t *dst, uint32_t value, int64_t n);
 int launch_box_fill(ws_map *m, const ws::MapParams &par, int which, const int32_t lo[3], const int32_t ext[3], uint32_t value, hipStream_t stream);
