@@ -1,4 +1,4 @@
-"""Host-side units of the record key / voxel-byte layout (ws_internal.h) and of the walk over column changes (ws_dda.h), built and
+"""Host-side units of the record key / voxel-byte layout and the owning memory types (ws_internal.h) and of the walk over column changes (ws_dda.h), built and
 run on the CPU: no GPU needed (hipcc cross-compiles; only host code runs)."""
 import os
 import shutil
@@ -25,6 +25,20 @@ def test_record_key_split_and_brick_order(tmp_path):
                            os.path.join(ROOT, "tests", "cpp", "host_units.hip"), "-o", str(exe)])
     out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stdout + out.stderr
+
+
+def test_owning_types_are_empty_after_a_failed_allocation(tmp_path):
+    """DevBuf, HostBlock and DevCounter (ws_internal.h), which own every device and pinned allocation of the library: after WS_OK
+    the pointer is there and the capacity covers the request (exactly, where exact was asked for); after an error the object is
+    empty and the code is a WS_ERR_*; release() twice is safe, and a second attempt behaves like the first.  Without a GPU every
+    allocation fails, which is the path no GPU test reaches; with one they all succeed.  (tests/cpp/owner_units.hip)"""
+    if not os.path.exists(_hipcc()):
+        pytest.skip("hipcc not installed")
+    exe = tmp_path / "owner_units"
+    subprocess.check_call([_hipcc(), "--offload-arch=gfx950", "-O1", "-std=c++17", "-Wall", "-Werror", f"-I{os.path.join(ROOT, 'include')}", f"-I{CSRC}",
+                           os.path.join(ROOT, "tests", "cpp", "owner_units.hip"), "-o", str(exe)])
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and out.stdout.strip().startswith("ok:"), out.stdout + out.stderr
 
 
 def test_column_change_walk_equals_the_sample_walk(tmp_path):

@@ -109,8 +109,8 @@ static void servers_leave(ws_context *ctx)
   for (ws_reg *r : ctx->regs)
   {
     const uint32_t id = r->srv_launch.load(std::memory_order_acquire);
-    if (id == 0 || ws::reg_server_mail_exited(r->srv_mail) == id) continue;
-    ws::reg_server_mail_stop(r->srv_mail, id);
+    if (id == 0 || ws::reg_server_mail_exited(r->srv_mail.p) == id) continue;
+    ws::reg_server_mail_stop(r->srv_mail.p, id);
     r->srv_stopping.store(true, std::memory_order_release);
   }
 }
@@ -244,27 +244,20 @@ int ws_device_reset(void)
 }
 
 // ------------------------------------------------------------------ maps
-static void map_free_records(ws_map *m)
-{
-  if (m->rec) (void)hipFree(m->rec);
-  if (m->big_keys) (void)hipFree(m->big_keys);
-  m->rec = nullptr;
-  m->big_keys = nullptr;
-  m->sub_cap = 0;
-  m->big_slots = 0;
-}
-
 // candidate records of the ray tails: the pool of sub-chunks (32 x 8 bytes, one tile each) and the (tile, entry number) ->
 // entry hash for tiles of more than TILE_DIRECT sub-chunks (two slots per sub-chunk of the pool; keys, then uint32 values)
 static int map_alloc_records(ws_map *m, uint64_t subs)
 {
   if (subs < 32768) subs = 32768;
   if (subs > SUB_ID_LIMIT) subs = SUB_ID_LIMIT;
-  map_free_records(m);
+  m->rec.release();
+  m->big_keys.release();
+  m->sub_cap = 0;
+  m->big_slots = 0;
   uint64_t slots = 1u << 16;
   while (slots < 2 * subs && slots < (1ull << 31)) slots <<= 1;
-  WS_HIP(hipMalloc((void **)&m->rec, (size_t)subs * SUB_RECS * sizeof(unsigned long long)));
-  WS_HIP(hipMalloc((void **)&m->big_keys, (size_t)slots * (sizeof(unsigned long long) + sizeof(uint32_t))));
+  WS_TRY(m->rec.alloc((size_t)subs * SUB_RECS, sizeof(unsigned long long)));
+  WS_TRY(m->big_keys.alloc((size_t)slots, sizeof(unsigned long long) + sizeof(uint32_t)));
   m->sub_cap = (uint32_t)subs;
   m->big_slots = (uint32_t)slots;
   m->prepped = false; // the new hash is filled by the stand-alone preparation pass
@@ -285,20 +278,8 @@ static int map_free(ws_map *m)
         break;
       }
   }
-  map_free_records(m);
-  void *ptrs[] = {m->data[0], m->data[1], m->vstate, m->az_hist, m->az_off, m->ray_bin, m->ray_order, m->fan_steps, m->rays, m->scan_dev, m->counters, m->tile_nsub,
-                  m->tile_ent, m->tile_dirty, m->tile_list, m->block_stats, m->box_stage};
-  for (void *p : ptrs)
-    if (p) (void)hipFree(p);
-  m->surf.release();
-  m->mesh.release();
-  m->ray.release();
-  m->dist.release();
-  if (m->counters_host) (void)hipHostFree(m->counters_host);
-  if (m->status_host) (void)hipHostFree(m->status_host);
+  m->release();
   if (m->shift_open) delete m->shift_open;
-  if (m->shift_stage_dev) (void)hipFree(m->shift_stage_dev);
-  if (m->shift_stage_host) (void)hipHostFree(m->shift_stage_host);
   if (m->shift_event) (void)hipEventDestroy(m->shift_event);
   if (m->shift_stream) (void)hipStreamDestroy(m->shift_stream);
   delete m;
@@ -310,11 +291,11 @@ static int map_free(ws_map *m)
 // looks at it: an inexact map is reported ONCE, by the first such call after the update that produced it.
 static int map_take_error(ws_map *m)
 {
-  if (!m || !m->status_host) return WS_OK;
-  volatile uint32_t *st = m->status_host;
+  if (!m || !m->status.p) return WS_OK;
+  volatile uint32_t *st = m->status.as<uint32_t>();
   const uint32_t bits = st[0];
   if (!bits) return WS_OK;
-  __atomic_fetch_and(m->status_host, ~bits, __ATOMIC_RELAXED);
+  __atomic_fetch_and(m->status.as<uint32_t>(), ~bits, __ATOMIC_RELAXED);
   m->last_error_bits |= bits;
   if (bits & 8u)
   {
@@ -346,6 +327,67 @@ static int ctx_take_errors(ws_context *ctx)
     if (rc == WS_OK) rc = r;
   }
   return rc;
+}
+
+// the allocations and first contents of a map whose geometry is set; on an error ws_map_create frees what is there
+static int map_build(ws_map *m, const uint32_t *host_data)
+{
+  hipStream_t s = m->ctx->stream;
+  const size_t map_bytes = (size_t)m->n_vox * sizeof(uint32_t);
+  // 16 bytes of slack: the tile kernels read the four voxels of a column as one access, also at the very end
+  WS_TRY(m->data[0].alloc(map_bytes + 16));
+  WS_TRY(m->data[1].alloc(map_bytes + 16));
+  WS_TRY(m->vstate.alloc(2 * vstate_plane_bytes(m->n_tiles)));
+  WS_HIP(hipMemsetAsync(m->vstate.p, 0, 2 * vstate_plane_bytes(m->n_tiles), s));
+  WS_TRY(m->rays.alloc(MAX_SCAN_POINTS, ray_setup_bytes()));
+  WS_TRY(m->az_hist.alloc(AZ_ALLOC, sizeof(uint32_t)));
+  WS_TRY(m->az_off.alloc(AZ_ALLOC, sizeof(uint32_t)));
+  WS_TRY(m->ray_bin.alloc(MAX_SCAN_POINTS, 2 * sizeof(uint32_t)));
+  WS_TRY(m->ray_order.alloc(MAX_SCAN_POINTS, sizeof(uint32_t)));
+  WS_TRY(m->fan_steps.alloc(WS_FAN_TABLE, sizeof(int32_t)));
+  ws::fill_fan_steps(m->fan_steps_host, m->res, m->ntz, m->nty);
+  WS_HIP(hipMemcpyAsync(m->fan_steps.p, m->fan_steps_host, WS_FAN_TABLE * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  WS_HIP(hipMemsetAsync(m->az_hist.p, 0, AZ_ALLOC * sizeof(uint32_t), s));
+  WS_HIP(hipMemsetAsync(m->az_off.p, 0, AZ_ALLOC * sizeof(uint32_t), s));
+  WS_TRY(m->scan_dev.alloc(MAX_SCAN_POINTS, 3 * sizeof(int32_t)));
+  WS_TRY(m->counters.alloc(1, sizeof(TsdfCounters)));
+  WS_HIP(hipMemsetAsync(m->counters.p, 0, sizeof(TsdfCounters), s));
+  // per-tile bookkeeping of the scatter: entry count, entry table (64 x 4 bytes), two bytes, one 16-byte list entry per 1024 voxels
+  WS_TRY(m->tile_nsub.alloc((size_t)m->n_tiles, sizeof(uint32_t)));
+  WS_TRY(m->tile_ent.alloc((size_t)m->n_tiles * TILE_DIRECT * sizeof(uint32_t) + 256));
+  WS_TRY(m->tile_dirty.alloc(2 * tile_flag_plane_bytes(m->n_tiles)));
+  WS_TRY(m->tile_list.alloc((size_t)m->n_tiles, sizeof(TileEntry)));
+  WS_HIP(hipMemsetAsync(m->tile_nsub.p, 0, (size_t)m->n_tiles * sizeof(uint32_t), s));
+  WS_HIP(hipMemsetAsync(m->tile_dirty.p, 0, 2 * tile_flag_plane_bytes(m->n_tiles), s));
+  WS_TRY(m->block_stats.alloc(WS_BLOCK_STATS, sizeof(uint32_t)));
+  WS_HIP(hipMemsetAsync(m->block_stats.p, 0, (size_t)WS_BLOCK_STATS * sizeof(uint32_t), s));
+  WS_TRY(m->counters_host.alloc(1, sizeof(TsdfCounters), HostBlock::PINNED));
+  WS_TRY(m->status.alloc(16, sizeof(uint32_t), HostBlock::MAPPED, true));
+  // the pool of the ray tails' records: what a 131 072-point scan can need on a map of the reference's size (its record bound is
+  // ~75 M at 50 mm) -- scaled down for small maps (ADVICE r4: 1.1 GB for a 64^3 map): 32 records per voxel, scans of 16 384
+  // points.  Only a first guess: a scan that needs more is aborted and repeated with a larger pool (settle_tsdf),
+  // ws_tsdf_set_capacity() reserves up front.
+  {
+    const bool small_map = m->n_vox < (16ll << 20);
+    const unsigned long long need0 = small_map ? std::max<unsigned long long>(1ull << 20, 32ull * (unsigned long long)m->n_vox) : (80ull << 20);
+    WS_TRY(map_alloc_records(m, subs_for_scan(m, std::min<unsigned long long>(need0, 80ull << 20), small_map ? 16384 : 131072)));
+  }
+  const uint32_t def = ((uint32_t)m->tau & 0xffffu);
+  if (host_data)
+  {
+    // DeviceMapMemWrapper(existing_map) x2: avg_map_ and new_map_ both start as the host map (update_tsdf.cu:135-136)
+    WS_HIP(hipMemcpyAsync(m->data[0].p, host_data, map_bytes, hipMemcpyHostToDevice, s));
+    WS_HIP(hipMemcpyAsync(m->data[1].p, m->data[0].p, map_bytes, hipMemcpyDeviceToDevice, s));
+    WS_HIP(hipStreamSynchronize(s));
+    m->new_is_default = check_all_equal_host(host_data, m->n_vox, def) != 0;
+  }
+  else
+  {
+    WS_TRY(fill_u32(m->ctx, m->data[0].as<uint32_t>(), def, m->n_vox));
+    WS_TRY(fill_u32(m->ctx, m->data[1].as<uint32_t>(), def, m->n_vox));
+    m->new_is_default = true;
+  }
+  return WS_OK;
 }
 
 int ws_map_create(ws_context *ctx, const int32_t size[3], const int32_t pos[3], const int32_t offset[3],
@@ -383,86 +425,12 @@ int ws_map_create(ws_context *ctx, const int32_t size[3], const int32_t pos[3], 
   m->max_weight = max_weight;
   m->res = res;
 
-  hipStream_t s = ctx->stream;
-  int rc = WS_OK;
-#define TRY(call)                                                   \
-  do                                                                \
-  {                                                                 \
-    hipError_t e__ = (call);                                        \
-    if (e__ != hipSuccess)                                          \
-    {                                                               \
-      rc = hip_fail(e__, #call, __FILE__, __LINE__);                \
-      map_free(m);                                                  \
-      return rc;                                                    \
-    }                                                               \
-  } while (0)
-  const size_t map_bytes = (size_t)m->n_vox * sizeof(uint32_t);
-  // 16 bytes of slack: the tile kernels read the four voxels of a column as one access, also at the very end
-  TRY(hipMalloc((void **)&m->data[0], map_bytes + 16));
-  TRY(hipMalloc((void **)&m->data[1], map_bytes + 16));
-  TRY(hipMalloc((void **)&m->vstate, 2 * vstate_plane_bytes(m->n_tiles)));
-  TRY(hipMemsetAsync(m->vstate, 0, 2 * vstate_plane_bytes(m->n_tiles), s));
-  TRY(hipMalloc((void **)&m->rays, MAX_SCAN_POINTS * ray_setup_bytes()));
-  TRY(hipMalloc((void **)&m->az_hist, AZ_ALLOC * sizeof(uint32_t)));
-  TRY(hipMalloc((void **)&m->az_off, AZ_ALLOC * sizeof(uint32_t)));
-  TRY(hipMalloc((void **)&m->ray_bin, MAX_SCAN_POINTS * 2 * sizeof(uint32_t)));
-  TRY(hipMalloc((void **)&m->ray_order, MAX_SCAN_POINTS * sizeof(uint32_t)));
-  TRY(hipMalloc((void **)&m->fan_steps, WS_FAN_TABLE * sizeof(int32_t)));
-  ws::fill_fan_steps(m->fan_steps_host, m->res, m->ntz, m->nty);
-  TRY(hipMemcpyAsync(m->fan_steps, m->fan_steps_host, WS_FAN_TABLE * sizeof(int32_t), hipMemcpyHostToDevice, s));
-  TRY(hipMemsetAsync(m->az_hist, 0, AZ_ALLOC * sizeof(uint32_t), s));
-  TRY(hipMemsetAsync(m->az_off, 0, AZ_ALLOC * sizeof(uint32_t), s));
-  TRY(hipMalloc((void **)&m->scan_dev, MAX_SCAN_POINTS * 3 * sizeof(int32_t)));
-  TRY(hipMalloc((void **)&m->counters, sizeof(TsdfCounters)));
-  TRY(hipMemsetAsync(m->counters, 0, sizeof(TsdfCounters), s));
-  // per-tile bookkeeping of the scatter: entry count, entry table (64 x 4 bytes), two bytes, one 16-byte list entry per 1024 voxels
-  TRY(hipMalloc((void **)&m->tile_nsub, (size_t)m->n_tiles * sizeof(uint32_t)));
-  TRY(hipMalloc((void **)&m->tile_ent, (size_t)m->n_tiles * TILE_DIRECT * sizeof(uint32_t) + 256));
-  TRY(hipMalloc((void **)&m->tile_dirty, 2 * tile_flag_plane_bytes(m->n_tiles)));
-  TRY(hipMalloc((void **)&m->tile_list, (size_t)m->n_tiles * sizeof(TileEntry)));
-  TRY(hipMemsetAsync(m->tile_nsub, 0, (size_t)m->n_tiles * sizeof(uint32_t), s));
-  TRY(hipMemsetAsync(m->tile_dirty, 0, 2 * tile_flag_plane_bytes(m->n_tiles), s));
-  TRY(hipMalloc((void **)&m->block_stats, (size_t)WS_BLOCK_STATS * sizeof(uint32_t)));
-  TRY(hipMemsetAsync(m->block_stats, 0, (size_t)WS_BLOCK_STATS * sizeof(uint32_t), s));
-  TRY(hipHostMalloc((void **)&m->counters_host, sizeof(TsdfCounters), hipHostMallocDefault));
-  TRY(hipHostMalloc((void **)&m->status_host, 64, hipHostMallocMapped));
-  std::memset(m->status_host, 0, 64);
-  TRY(hipHostGetDevicePointer((void **)&m->status_dev, m->status_host, 0));
-  // the pool of the ray tails' records: what a 131 072-point scan can need on a map of the reference's size (its record bound is
-  // ~75 M at 50 mm) -- scaled down for small maps (ADVICE r4: 1.1 GB for a 64^3 map): 32 records per voxel, scans of 16 384
-  // points.  Only a first guess: a scan that needs more is aborted and repeated with a larger pool (settle_tsdf),
-  // ws_tsdf_set_capacity() reserves up front.
-  {
-    const bool small_map = m->n_vox < (16ll << 20);
-    const unsigned long long need0 = small_map ? std::max<unsigned long long>(1ull << 20, 32ull * (unsigned long long)m->n_vox) : (80ull << 20);
-    rc = map_alloc_records(m, subs_for_scan(m, std::min<unsigned long long>(need0, 80ull << 20), small_map ? 16384 : 131072));
-  }
+  const int rc = map_build(m, host_data);
   if (rc != WS_OK)
   {
     map_free(m);
     return rc;
   }
-  const uint32_t def = ((uint32_t)tau & 0xffffu);
-  if (host_data)
-  {
-    // DeviceMapMemWrapper(existing_map) x2: avg_map_ and new_map_ both start as the host map (update_tsdf.cu:135-136)
-    TRY(hipMemcpyAsync(m->data[0], host_data, map_bytes, hipMemcpyHostToDevice, s));
-    TRY(hipMemcpyAsync(m->data[1], m->data[0], map_bytes, hipMemcpyDeviceToDevice, s));
-    TRY(hipStreamSynchronize(s));
-    m->new_is_default = check_all_equal_host(host_data, m->n_vox, def) != 0;
-  }
-  else
-  {
-    rc = fill_u32(ctx, m->data[0], def, m->n_vox);
-    if (rc == WS_OK) rc = fill_u32(ctx, m->data[1], def, m->n_vox);
-    if (rc != WS_OK)
-    {
-      map_free(m);
-      return rc;
-    }
-    m->new_is_default = true;
-  }
-#undef TRY
   {
     std::lock_guard<std::mutex> lock(ctx->lists_mu);
     ctx->maps.push_back(m);
@@ -491,7 +459,7 @@ int ws_map_upload(ws_map *m, int which, const int32_t size[3], const int32_t pos
   if (!host_data) return invalid("ws_map_upload: host_data is NULL");
   int rc = ws_map_set_params(m, which, size, pos, offset);
   if (rc != WS_OK) return rc;
-  WS_HIP(hipMemcpyAsync(m->data[which], host_data, (size_t)m->n_vox * sizeof(uint32_t), hipMemcpyHostToDevice, m->ctx->stream));
+  WS_HIP(hipMemcpyAsync(m->data[which].p, host_data, (size_t)m->n_vox * sizeof(uint32_t), hipMemcpyHostToDevice, m->ctx->stream));
   WS_HIP(hipStreamSynchronize(m->ctx->stream)); // cudaMemcpy of the reference is synchronous; the host buffer may be reused
   if (which == WS_MAP_NEW) m->new_is_default = check_all_equal_host(host_data, m->n_vox, ((uint32_t)m->tau & 0xffffu)) != 0;
   return WS_OK;
@@ -506,7 +474,7 @@ int ws_map_download(ws_map *m, int which, int32_t size[3], int32_t pos[3], int32
   if (offset) copy3(offset, m->par[which].offset);
   if (host_data)
   {
-    WS_HIP(hipMemcpyAsync(host_data, m->data[which], (size_t)m->n_vox * sizeof(uint32_t), hipMemcpyDeviceToHost, m->ctx->stream));
+    WS_HIP(hipMemcpyAsync(host_data, m->data[which].p, (size_t)m->n_vox * sizeof(uint32_t), hipMemcpyDeviceToHost, m->ctx->stream));
   }
   WS_HIP(hipStreamSynchronize(m->ctx->stream));
   return map_take_error(m);
@@ -547,14 +515,10 @@ static int box_check(ws_map *m, int which, const int32_t lo[3], const int32_t hi
   if (rc != WS_OK) return rc;
   const size_t cnt = (size_t)ext[0] * (size_t)ext[1] * (size_t)ext[2];
   *n = cnt;
-  if (cnt > m->box_stage_cap)
+  if (cnt > m->box_stage.cap)
   {
     WS_HIP(hipStreamSynchronize(m->ctx->stream));
-    if (m->box_stage) WS_HIP(hipFree(m->box_stage));
-    m->box_stage = nullptr;
-    m->box_stage_cap = 0;
-    WS_HIP(hipMalloc((void **)&m->box_stage, cnt * sizeof(uint32_t)));
-    m->box_stage_cap = cnt;
+    WS_TRY(m->box_stage.grow(cnt, sizeof(uint32_t), DevBuf::EXACT));
   }
   return WS_OK;
 }
@@ -567,9 +531,9 @@ int ws_map_extract_box(ws_map *m, int which, const int32_t lo[3], const int32_t 
   size_t n = 0;
   int rc = box_check(m, which, lo, hi, ext, &n);
   if (rc != WS_OK) return rc;
-  rc = launch_box_copy(m, m->par[which], which, lo, ext, m->box_stage, true, m->ctx->stream);
+  rc = launch_box_copy(m, m->par[which], which, lo, ext, m->box_stage.as<uint32_t>(), true, m->ctx->stream);
   if (rc != WS_OK) return rc;
-  WS_HIP(hipMemcpyAsync(host_out, m->box_stage, n * sizeof(uint32_t), hipMemcpyDeviceToHost, m->ctx->stream));
+  WS_HIP(hipMemcpyAsync(host_out, m->box_stage.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, m->ctx->stream));
   WS_HIP(hipStreamSynchronize(m->ctx->stream));
   return WS_OK;
 }
@@ -582,8 +546,8 @@ int ws_map_insert_box(ws_map *m, int which, const int32_t lo[3], const int32_t h
   size_t n = 0;
   int rc = box_check(m, which, lo, hi, ext, &n);
   if (rc != WS_OK) return rc;
-  WS_HIP(hipMemcpyAsync(m->box_stage, host_in, n * sizeof(uint32_t), hipMemcpyHostToDevice, m->ctx->stream));
-  rc = launch_box_copy(m, m->par[which], which, lo, ext, m->box_stage, false, m->ctx->stream);
+  WS_HIP(hipMemcpyAsync(m->box_stage.p, host_in, n * sizeof(uint32_t), hipMemcpyHostToDevice, m->ctx->stream));
+  rc = launch_box_copy(m, m->par[which], which, lo, ext, m->box_stage.as<uint32_t>(), false, m->ctx->stream);
   if (rc != WS_OK) return rc;
   WS_HIP(hipStreamSynchronize(m->ctx->stream)); // the host buffer may be reused by the caller
   if (which == WS_MAP_NEW) m->new_is_default = false;
@@ -955,19 +919,12 @@ int ws_debug_distance_timing(ws_map *m, int32_t enable, float ms_out[4])
 // ---- map shift off the scan path
 static int shift_reserve(ws_map *m, size_t total)
 {
-  if (total <= m->shift_stage_cap) return WS_OK;
-  hipError_t e = hipStreamSynchronize(m->ctx->stream);
-  if (e == hipSuccess && m->shift_stage_dev) e = hipFree(m->shift_stage_dev);
-  if (e == hipSuccess && m->shift_stage_host) e = hipHostFree(m->shift_stage_host);
-  m->shift_stage_dev = nullptr;
-  m->shift_stage_host = nullptr;
-  m->shift_stage_cap = 0;
-  if (e == hipSuccess) e = hipMalloc((void **)&m->shift_stage_dev, total * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipHostMalloc((void **)&m->shift_stage_host, total * sizeof(uint32_t), hipHostMallocDefault);
-  if (e == hipSuccess && !m->shift_stream) e = hipStreamCreateWithFlags(&m->shift_stream, hipStreamNonBlocking);
-  if (e == hipSuccess && !m->shift_event) e = hipEventCreateWithFlags(&m->shift_event, hipEventDisableTiming);
-  if (e != hipSuccess) return hip_fail(e, "map shift staging", __FILE__, __LINE__);
-  m->shift_stage_cap = total;
+  if (total <= m->shift_stage_dev.cap && total <= m->shift_stage_host.cap) return WS_OK;
+  WS_HIP(hipStreamSynchronize(m->ctx->stream));
+  WS_TRY(m->shift_stage_dev.grow(total, sizeof(uint32_t), DevBuf::EXACT));
+  WS_TRY(m->shift_stage_host.grow(total, sizeof(uint32_t), HostBlock::PINNED));
+  if (!m->shift_stream) WS_HIP(hipStreamCreateWithFlags(&m->shift_stream, hipStreamNonBlocking));
+  if (!m->shift_event) WS_HIP(hipEventCreateWithFlags(&m->shift_event, hipEventDisableTiming));
   return WS_OK;
 }
 
@@ -1054,7 +1011,7 @@ int ws_shift_begin(ws_map *m, const int32_t new_pos[3], uint32_t fill_entry, ws_
     while (new_pos[axis] == par[WS_MAP_AVG].pos[axis]) ++axis; // the axis slab i belongs to
     int32_t ext[3];
     for (int k = 0; k < 3; ++k) ext[k] = sh->leave_hi[i][k] - sh->leave_lo[i][k] + 1;
-    rc = launch_box_copy(m, par[WS_MAP_AVG], WS_MAP_AVG, sh->leave_lo[i], ext, m->shift_stage_dev + sh->offset[i], true, s);
+    rc = launch_box_copy(m, par[WS_MAP_AVG], WS_MAP_AVG, sh->leave_lo[i], ext, m->shift_stage_dev.as<uint32_t>() + sh->offset[i], true, s);
     const int32_t d = new_pos[axis] - par[WS_MAP_AVG].pos[axis];
     for (int w = 0; w < 2; ++w)
     {
@@ -1070,7 +1027,7 @@ int ws_shift_begin(ws_map *m, const int32_t new_pos[3], uint32_t fill_entry, ws_
   {
     hipError_t e = hipEventRecord(m->shift_event, s);
     if (e == hipSuccess) e = hipStreamWaitEvent(m->shift_stream, m->shift_event, 0);
-    if (e == hipSuccess) e = hipMemcpyAsync(m->shift_stage_host, m->shift_stage_dev, total * sizeof(uint32_t), hipMemcpyDeviceToHost, m->shift_stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(m->shift_stage_host.p, m->shift_stage_dev.p, total * sizeof(uint32_t), hipMemcpyDeviceToHost, m->shift_stream);
     if (e != hipSuccess) rc = hip_fail(e, "ws_shift_begin copy", __FILE__, __LINE__);
   }
   if (rc != WS_OK)
@@ -1107,7 +1064,7 @@ int ws_shift_slab(const ws_shift *sh, int i, int32_t lo[3], int32_t hi[3], const
   if (!sh || i < 0 || i >= sh->n || !lo || !hi || !host_data) return invalid("ws_shift_slab: bad argument");
   copy3(lo, sh->leave_lo[i]);
   copy3(hi, sh->leave_hi[i]);
-  *host_data = sh->map->shift_stage_host + sh->offset[i];
+  *host_data = sh->map->shift_stage_host.as<uint32_t>() + sh->offset[i];
   return WS_OK;
 }
 
@@ -1132,7 +1089,7 @@ int ws_map_get_params(const ws_map *m, int which, int32_t size[3], int32_t pos[3
 void *ws_map_device_data(ws_map *m, int which)
 {
   if (!m || (which != WS_MAP_AVG && which != WS_MAP_NEW)) return nullptr;
-  return m->data[which];
+  return m->data[which].p;
 }
 
 int64_t ws_map_n_voxels(const ws_map *m) { return m ? m->n_vox : 0; }
@@ -1217,9 +1174,9 @@ int ws_tsdf_update(ws_map *m, const int32_t *xyz_host, size_t n, const int32_t s
     // (scan_dev is what a repeat of the PREVIOUS scan would read -- its verdict first, then the new points)
     WS_SETTLE(m);
     // pageable source: hipMemcpyAsync stages the data before it returns, like the reference's cudaMemcpy (update_tsdf.cu:152)
-    WS_HIP(hipMemcpyAsync(m->scan_dev, xyz_host, n * 3 * sizeof(int32_t), hipMemcpyHostToDevice, m->ctx->stream));
+    WS_HIP(hipMemcpyAsync(m->scan_dev.p, xyz_host, n * 3 * sizeof(int32_t), hipMemcpyHostToDevice, m->ctx->stream));
   }
-  return ws_tsdf_update_dev(m, m->scan_dev, n, scanner_pos, up);
+  return ws_tsdf_update_dev(m, m->scan_dev.as<int32_t>(), n, scanner_pos, up);
 }
 
 int ws_tsdf_stats(ws_map *m, ws_tsdf_stats_t *out)
@@ -1231,9 +1188,9 @@ int ws_tsdf_stats(ws_map *m, ws_tsdf_stats_t *out)
     const int rc0 = launch_tsdf_stats(m);
     if (rc0 != WS_OK) return rc0;
   }
-  WS_HIP(hipMemcpyAsync(m->counters_host, m->counters, sizeof(TsdfCounters), hipMemcpyDeviceToHost, m->ctx->stream));
+  WS_HIP(hipMemcpyAsync(m->counters_host.p, m->counters.p, sizeof(TsdfCounters), hipMemcpyDeviceToHost, m->ctx->stream));
   WS_HIP(hipStreamSynchronize(m->ctx->stream));
-  const TsdfCounters *c = m->counters_host;
+  const TsdfCounters *c = m->counters_host.as<TsdfCounters>();
   out->contested_voxels = c->last_contested;
   out->records = c->last_records;
   out->tiles = (int64_t)c->last_listed + c->last_unlisted;
@@ -1243,7 +1200,7 @@ int ws_tsdf_stats(ws_map *m, ws_tsdf_stats_t *out)
   out->record_capacity = (int64_t)m->sub_cap * SUB_RECS;
   const int rc = map_take_error(m);
   out->error_flags = (int32_t)m->last_error_bits;
-  out->hash_entries = (int32_t)m->status_host[10];
+  out->hash_entries = (int32_t)m->status.as<uint32_t>()[10];
   m->last_error_bits = 0;
   return rc;
 }
@@ -1252,9 +1209,8 @@ int ws_tsdf_stats(ws_map *m, ws_tsdf_stats_t *out)
 int ws_reg_destroy(ws_reg *r)
 {
   if (!r) return WS_OK;
-  if (r->ctx)
+  servers_leave(r->ctx);
   {
-    servers_leave(r->ctx);
     std::lock_guard<std::mutex> lock(r->ctx->lists_mu);
     auto &v = r->ctx->regs;
     for (size_t i = 0; i < v.size(); ++i)
@@ -1265,35 +1221,42 @@ int ws_reg_destroy(ws_reg *r)
       }
   }
   (void)hipStreamSynchronize(r->ctx->stream);
-  if (r->srv_mail) (void)hipHostFree(r->srv_mail);
-  if (r->srv_ctl) (void)hipFree(r->srv_ctl);
-  if (r->points) (void)hipFree(r->points);
-  if (r->partials) (void)hipFree(r->partials);
-  if (r->state) (void)hipFree(r->state);
-  if (r->sums_dev) (void)hipFree(r->sums_dev);
-  if (r->state_host) (void)hipHostFree(r->state_host);
-  if (r->host_flag) (void)hipHostFree(r->host_flag);
-  if (r->result_host) (void)hipHostFree(r->result_host);
-  if (r->iter_host) (void)hipHostFree(r->iter_host);
-  if (r->grid_bar) (void)hipFree(r->grid_bar);
-  if (r->pass_arrived) (void)hipFree(r->pass_arrived);
-  if (r->batch_host) (void)hipHostFree(r->batch_host);
   (void)ws_reg_peer_disconnect(r);
-  if (r->mailbox) (void)hipFree(r->mailbox);
-  if (r->peer_block_dev) (void)hipFree(r->peer_block_dev);
+  r->release();
   delete r;
   return WS_OK;
 }
 
 static int reg_reserve(ws_reg *r, size_t n)
 {
-  if (n <= r->cap) return WS_OK;
+  if (n <= r->points.cap) return WS_OK;
   WS_HIP(hipStreamSynchronize(r->ctx->stream));
-  if (r->points) WS_HIP(hipFree(r->points));
-  r->points = nullptr;
-  r->cap = 0;
-  WS_HIP(hipMalloc((void **)&r->points, n * 3 * sizeof(int32_t)));
-  r->cap = n;
+  return r->points.grow(n, 3 * sizeof(int32_t), DevBuf::EXACT);
+}
+
+// the allocations and first contents of a registration; on an error ws_reg_create frees what is there
+static int reg_build(ws_reg *r, size_t max_points)
+{
+  WS_TRY(reg_reserve(r, max_points));
+  WS_TRY(r->partials.alloc(reg_partials_bytes()));
+  WS_TRY(r->state.alloc(2, sizeof(GnState)));
+  WS_TRY(r->sums_dev.alloc(44, sizeof(int64_t)));
+  WS_TRY(r->state_host.alloc(1, sizeof(GnState), HostBlock::PINNED));
+  WS_TRY(r->host_flag.alloc(16, sizeof(int32_t), HostBlock::MAPPED));
+  WS_TRY(r->result_host.alloc(1, sizeof(GnState), HostBlock::MAPPED));
+  WS_TRY(r->iter_host.alloc(64, sizeof(int64_t), HostBlock::MAPPED, true));
+  WS_HIP(hipMemsetAsync(r->state.p, 0, 2 * sizeof(GnState), r->ctx->stream));
+  WS_TRY(r->grid_bar.alloc(reg_barrier_bytes()));
+  WS_TRY(r->pass_arrived.alloc(1, sizeof(uint32_t)));
+  WS_HIP(hipMemset(r->pass_arrived.p, 0, sizeof(uint32_t)));
+  r->loop_supported = reg_loop_supported(r->ctx->device);
+  WS_TRY(r->srv_mail.alloc(reg_server_mail_bytes(), 1, HostBlock::MAPPED, true));
+  WS_TRY(r->srv_ctl.alloc(reg_server_ctl_bytes()));
+  WS_HIP(hipMemset(r->srv_ctl.p, 0, reg_server_ctl_bytes()));
+  if (const char *env = std::getenv("WS_REG_SERVER")) r->srv_enabled = std::atoi(env) != 0;
+  if (const char *env = std::getenv("WS_REG_SERVER_IDLE_US")) r->srv_idle_us = (uint32_t)std::max(1, std::atoi(env));
+  r->batch_variant = reg_batch_default_variant();
+  if (const char *env = std::getenv("WS_REG_BATCH_VARIANT")) r->batch_variant = std::atoi(env) & 1;
   return WS_OK;
 }
 
@@ -1304,39 +1267,9 @@ int ws_reg_create(ws_context *ctx, size_t max_points, ws_reg **out)
   if (!r) return invalid("ws_reg_create: out of host memory");
   r->ctx = ctx;
   if (max_points == 0) max_points = 128 * 1024; // registration.cu:261
-  int rc = reg_reserve(r, max_points);
-  hipError_t e = hipSuccess;
-  if (rc == WS_OK) e = hipMalloc((void **)&r->partials, reg_partials_bytes());
-  if (rc == WS_OK && e == hipSuccess) e = hipMalloc((void **)&r->state, 2 * sizeof(GnState));
-  if (rc == WS_OK && e == hipSuccess) e = hipMalloc((void **)&r->sums_dev, 44 * sizeof(int64_t));
-  if (rc == WS_OK && e == hipSuccess) e = hipHostMalloc((void **)&r->state_host, sizeof(GnState), hipHostMallocDefault);
-  if (rc == WS_OK && e == hipSuccess) e = hipHostMalloc((void **)&r->host_flag, 64, hipHostMallocMapped);
-  if (rc == WS_OK && e == hipSuccess) e = hipHostGetDevicePointer((void **)&r->host_flag_dev, r->host_flag, 0);
-  if (rc == WS_OK && e == hipSuccess) e = hipHostMalloc((void **)&r->result_host, sizeof(GnState), hipHostMallocMapped);
-  if (rc == WS_OK && e == hipSuccess) e = hipHostGetDevicePointer((void **)&r->result_host_dev, r->result_host, 0);
-  if (rc == WS_OK && e == hipSuccess) e = hipHostMalloc((void **)&r->iter_host, 64 * sizeof(int64_t), hipHostMallocMapped);
-  if (rc == WS_OK && e == hipSuccess) e = hipHostGetDevicePointer((void **)&r->iter_host_dev, r->iter_host, 0);
-  if (rc == WS_OK && e == hipSuccess) std::memset(r->iter_host, 0, 64 * sizeof(int64_t));
-  if (rc == WS_OK && e == hipSuccess) e = hipMemsetAsync(r->state, 0, 2 * sizeof(GnState), ctx->stream);
-  if (rc == WS_OK && e == hipSuccess) e = hipMalloc((void **)&r->grid_bar, reg_barrier_bytes());
-  if (rc == WS_OK && e == hipSuccess) e = hipMalloc((void **)&r->pass_arrived, sizeof(uint32_t));
-  if (rc == WS_OK && e == hipSuccess) e = hipMemset(r->pass_arrived, 0, sizeof(uint32_t));
-  if (rc == WS_OK && e == hipSuccess) r->loop_supported = reg_loop_supported(ctx->device);
-  if (rc == WS_OK && e == hipSuccess) e = hipHostMalloc((void **)&r->srv_mail, reg_server_mail_bytes(), hipHostMallocMapped);
-  if (rc == WS_OK && e == hipSuccess) e = hipHostGetDevicePointer((void **)&r->srv_mail_dev, r->srv_mail, 0);
-  if (rc == WS_OK && e == hipSuccess) std::memset(r->srv_mail, 0, reg_server_mail_bytes());
-  if (rc == WS_OK && e == hipSuccess) e = hipMalloc((void **)&r->srv_ctl, reg_server_ctl_bytes());
-  if (rc == WS_OK && e == hipSuccess) e = hipMemset(r->srv_ctl, 0, reg_server_ctl_bytes());
-  if (rc == WS_OK && e == hipSuccess)
+  const int rc = reg_build(r, max_points);
+  if (rc != WS_OK)
   {
-    if (const char *env = std::getenv("WS_REG_SERVER")) r->srv_enabled = std::atoi(env) != 0;
-    if (const char *env = std::getenv("WS_REG_SERVER_IDLE_US")) r->srv_idle_us = (uint32_t)std::max(1, std::atoi(env));
-    r->batch_variant = reg_batch_default_variant();
-    if (const char *env = std::getenv("WS_REG_BATCH_VARIANT")) r->batch_variant = std::atoi(env) & 1;
-  }
-  if (rc != WS_OK || e != hipSuccess)
-  {
-    if (e != hipSuccess) rc = hip_fail(e, "ws_reg_create allocation", __FILE__, __LINE__);
     ws_reg_destroy(r);
     return rc;
   }
@@ -1355,7 +1288,7 @@ int ws_reg_prepare(ws_reg *r, const int32_t *xyz_host, size_t n)
   int rc = reg_reserve(r, n);
   if (rc != WS_OK) return rc;
   r->n = n;
-  if (n) WS_HIP(hipMemcpyAsync(r->points, xyz_host, n * 3 * sizeof(int32_t), hipMemcpyHostToDevice, r->ctx->stream));
+  if (n) WS_HIP(hipMemcpyAsync(r->points.p, xyz_host, n * 3 * sizeof(int32_t), hipMemcpyHostToDevice, r->ctx->stream));
   return WS_OK;
 }
 
@@ -1366,30 +1299,30 @@ int ws_reg_prepare_dev(ws_reg *r, const int32_t *xyz_dev, size_t n)
   int rc = reg_reserve(r, n);
   if (rc != WS_OK) return rc;
   r->n = n;
-  if (n) WS_HIP(hipMemcpyAsync(r->points, xyz_dev, n * 3 * sizeof(int32_t), hipMemcpyDeviceToDevice, r->ctx->stream));
+  if (n) WS_HIP(hipMemcpyAsync(r->points.p, xyz_dev, n * 3 * sizeof(int32_t), hipMemcpyDeviceToDevice, r->ctx->stream));
   return WS_OK;
 }
 
 const int32_t *ws_reg_points_dev(const ws_reg *r, size_t *n)
 {
   if (n) *n = r ? r->n : 0;
-  return r ? r->points : nullptr;
+  return r ? r->points.as<int32_t>() : nullptr;
 }
 
 // ws_reg_iterate through the resident server (reg_server_kernel): see there.  Returns WS_OK with the 44 sums, or an error.
 static int reg_iterate_served(ws_reg *r, const ws_map *m, const float T[16], int32_t res, uint32_t flags, int64_t sums[44])
 {
-  auto exited = [&]() { return reg_server_mail_exited(r->srv_mail); };
+  auto exited = [&]() { return reg_server_mail_exited(r->srv_mail.p); };
   uint32_t id = r->srv_launch.load(std::memory_order_acquire);
   bool alive = id != 0 && exited() != id;
   const MapParams &par = m->par[WS_MAP_AVG];
-  const bool same = r->srv_sig.map == m && r->srv_sig.points == r->points && r->srv_sig.map_data == m->data[WS_MAP_AVG] && r->srv_sig.n == r->n &&
+  const bool same = r->srv_sig.map == m && r->srv_sig.points == r->points.p && r->srv_sig.map_data == m->data[WS_MAP_AVG].p && r->srv_sig.n == r->n &&
                     r->srv_sig.res == res && r->srv_sig.flags == flags && std::memcmp(&r->srv_sig.par, &par, sizeof par) == 0;
   if (alive && (!same || r->srv_stopping.load(std::memory_order_acquire)))
   {
     // somebody has enqueued other work behind that server (or the call is for another map / cloud): it must be gone before a
     // request may be written -- it would answer from the state it was launched with
-    reg_server_mail_stop(r->srv_mail, id);
+    reg_server_mail_stop(r->srv_mail.p, id);
     const int rc = spin_wait(r, [&] { return exited() == id; }, "ws_reg_iterate: the resident server did not leave");
     if (rc != WS_OK) return rc;
     alive = false;
@@ -1397,12 +1330,12 @@ static int reg_iterate_served(ws_reg *r, const ws_map *m, const float T[16], int
   uint32_t seq = r->srv_seq + 1;
   if (seq >= 0x7fffffffu) seq = 1;
   r->srv_seq = seq;
-  reg_server_mail_write(r->srv_mail, T, seq);
+  reg_server_mail_write(r->srv_mail.p, T, seq);
   auto launch = [&]() -> int {
     id = ++r->srv_ids ? r->srv_ids : ++r->srv_ids;
     r->srv_sig.map = m;
-    r->srv_sig.points = r->points;
-    r->srv_sig.map_data = m->data[WS_MAP_AVG];
+    r->srv_sig.points = r->points.p;
+    r->srv_sig.map_data = m->data[WS_MAP_AVG].p;
     r->srv_sig.n = r->n;
     r->srv_sig.res = res;
     r->srv_sig.flags = flags;
@@ -1419,12 +1352,12 @@ static int reg_iterate_served(ws_reg *r, const ws_map *m, const float T[16], int
   }
   const auto t0 = std::chrono::steady_clock::now();
   uint32_t spins = 0;
-  while (!reg_server_mail_answer(r->srv_mail, seq, sums))
+  while (!reg_server_mail_answer(r->srv_mail.p, seq, sums))
   {
     if (exited() == id)
     {
       // the server left (idle for too long, or asked to by another thread's call) without having seen this request
-      if (reg_server_mail_answer(r->srv_mail, seq, sums)) break;
+      if (reg_server_mail_answer(r->srv_mail.p, seq, sums)) break;
       const int rc = launch();
       if (rc != WS_OK) return rc;
     }
@@ -1434,14 +1367,14 @@ static int reg_iterate_served(ws_reg *r, const ws_map *m, const float T[16], int
       // map takes longer than this).  Drain the stream the ordinary way -- a server that starts finds the request, answers it and
       // leaves when nothing else comes -- and only then look again; a kernel that never ends is the runtime's to report.
       WS_HIP(hipStreamSynchronize(r->ctx->stream));
-      if (reg_server_mail_answer(r->srv_mail, seq, sums)) break;
+      if (reg_server_mail_answer(r->srv_mail.p, seq, sums)) break;
       if (exited() == id)
       {
         // (it left on another thread's request without having seen this one: the next turn of the loop starts a new one)
         const int rc = launch();
         if (rc != WS_OK) return rc;
         WS_HIP(hipStreamSynchronize(r->ctx->stream));
-        if (reg_server_mail_answer(r->srv_mail, seq, sums)) break;
+        if (reg_server_mail_answer(r->srv_mail.p, seq, sums)) break;
       }
       set_error("ws_reg_iterate: the resident server did not answer");
       return WS_ERR_INTERNAL;
@@ -1473,12 +1406,12 @@ int ws_reg_iterate(ws_reg *r, const ws_map *m, const float T[16], int32_t res, u
     // sums come back through host-mapped memory with the call's sequence number behind them (registration.cu:356-365 copies
     // four results and adds 32 partials up on the host).  The caller cannot go on without them, so the wait is a spin on that word.
     const uint32_t seq = ++r->iter_seq ? r->iter_seq : ++r->iter_seq; // (never 0: the block starts zeroed)
-    int rc = launch_reg_pass(r, m, res, flags, 0, r->n, r->iter_host_dev, 0, T, seq);
+    int rc = launch_reg_pass(r, m, res, flags, 0, r->n, r->iter_host.dev_as<int64_t>(), 0, T, seq);
     if (rc != WS_OK) return rc;
-    const volatile int64_t *done = r->iter_host + 44;
+    const volatile int64_t *done = r->iter_host.as<int64_t>() + 44;
     rc = spin_wait(r, [&] { return (uint32_t)*done == seq; }, "ws_reg_iterate: the launch ended without its result");
     if (rc != WS_OK) return rc;
-    std::memcpy(sums, r->iter_host, sizeof sums);
+    std::memcpy(sums, r->iter_host.p, sizeof sums);
   }
   std::memcpy(h, sums, 36 * sizeof(int64_t));
   std::memcpy(g, sums + 36, 6 * sizeof(int64_t));
@@ -1503,14 +1436,14 @@ int ws_debug_reg_server(ws_reg *r, int32_t enable, int32_t idle_us, int32_t *lau
 int ws_reg_begin(ws_reg *r, const float T_in[16], int32_t max_iterations, float it_weight_gradient, float epsilon)
 {
   if (!r || !T_in) return invalid("ws_reg_begin: NULL argument");
-  GnState *h = r->state_host;
+  GnState *h = r->state_host.as<GnState>();
   // the pinned staging block may still be read by an earlier async copy
   WS_HIP(hipStreamSynchronize(r->ctx->stream));
   std::memset(h, 0, sizeof(GnState));
   h->core = gn_init(T_in, max_iterations, it_weight_gradient, epsilon);
-  *(volatile int32_t *)r->host_flag = 0;
-  WS_HIP(hipMemcpyAsync(&r->state[0], h, sizeof(GnState), hipMemcpyHostToDevice, r->ctx->stream));
-  WS_HIP(hipMemcpyAsync(&r->state[1], h, sizeof(GnState), hipMemcpyHostToDevice, r->ctx->stream));
+  *r->host_flag.as<volatile int32_t>() = 0;
+  WS_HIP(hipMemcpyAsync(&r->state.as<GnState>()[0], h, sizeof(GnState), hipMemcpyHostToDevice, r->ctx->stream));
+  WS_HIP(hipMemcpyAsync(&r->state.as<GnState>()[1], h, sizeof(GnState), hipMemcpyHostToDevice, r->ctx->stream));
   r->latest = 0;
   return WS_OK;
 }
@@ -1539,9 +1472,9 @@ int ws_reg_solve_dev(ws_reg *r, const int64_t *sums_dev)
 int ws_reg_poll(ws_reg *r, int32_t *finished, int32_t *iterations, float T_out[16])
 {
   if (!r) return invalid("ws_reg_poll: reg is NULL");
-  WS_HIP(hipMemcpyAsync(r->state_host, &r->state[r->latest], sizeof(GnState), hipMemcpyDeviceToHost, r->ctx->stream));
+  WS_HIP(hipMemcpyAsync(r->state_host.p, &r->state.as<GnState>()[r->latest], sizeof(GnState), hipMemcpyDeviceToHost, r->ctx->stream));
   WS_HIP(hipStreamSynchronize(r->ctx->stream));
-  const GnCore *h = &r->state_host->core;
+  const GnCore *h = &r->state_host.as<GnState>()->core;
   if (finished) *finished = (h->finished || h->iterations >= h->max_iterations) ? 1 : 0;
   if (iterations) *iterations = h->iterations;
   if (T_out) std::memcpy(T_out, h->T, 16 * sizeof(float));
@@ -1551,7 +1484,7 @@ int ws_reg_poll(ws_reg *r, int32_t *finished, int32_t *iterations, float T_out[1
 // the host side of one resident launch: spin on the flag the kernel raises behind its result (host-mapped memory)
 static int wait_resident_loop(ws_reg *r)
 {
-  const volatile int32_t *done = r->host_flag;
+  const volatile int32_t *done = r->host_flag.as<int32_t>();
   return spin_wait(r, [&] { return *done != 0; }, "the resident registration loop ended without its result");
 }
 
@@ -1566,7 +1499,7 @@ int ws_register_cloud(ws_reg *r, const ws_map *m, const float T_in[16], int32_t 
     // one launch: the 256 workgroups stay resident and meet at a grid barrier between iterations.  The initial state
     // travels in the kernel arguments and the final state comes back through host-mapped memory, so the host neither
     // waits for earlier work on the stream before enqueueing nor copies anything afterwards.
-    *(volatile int32_t *)r->host_flag = 0; // nothing on the stream writes it any more: every earlier registration was waited for
+    *r->host_flag.as<volatile int32_t>() = 0; // nothing on the stream writes it any more: every earlier registration was waited for
     int rc = launch_reg_loop(r, m, res, flags, gn_init(T_in, max_iterations, it_weight_gradient, epsilon));
     if (rc != WS_OK) return rc;
     r->latest = 0;
@@ -1574,7 +1507,7 @@ int ws_register_cloud(ws_reg *r, const ws_map *m, const float T_in[16], int32_t 
     // hipStreamSynchronize: 84 -> ~35 us between the end of a registration and the first kernel of the next scan (measured).
     rc = wait_resident_loop(r);
     if (rc != WS_OK) return rc;
-    const GnCore *h = &r->result_host->core;
+    const GnCore *h = &r->result_host.as<GnState>()->core;
     if (!h->error)
     {
       std::memcpy(T_out, h->T, 16 * sizeof(float));
@@ -1591,7 +1524,7 @@ int ws_register_cloud(ws_reg *r, const ws_map *m, const float T_in[16], int32_t 
   // One launch per iteration: launch k applies update k (from the partial sums launch k-1 left behind) and
   // accumulates for iteration k.  The host just enqueues; the device raises a flag in host-mapped memory on
   // convergence so the host can stop early (launches already enqueued exit at once).
-  const volatile int32_t *flag = r->host_flag;
+  const volatile int32_t *flag = r->host_flag.as<int32_t>();
   int launched = 0;
   for (int k = 0; k <= max_iterations && !*flag; ++k)
   {
@@ -1610,17 +1543,11 @@ int ws_register_cloud(ws_reg *r, const ws_map *m, const float T_in[16], int32_t 
 // ------------------------------------------------------------------ many start poses, one launch
 static int reg_batch_reserve(ws_reg *r, size_t k)
 {
-  if (k <= r->batch_cap) return WS_OK;
+  if (k <= r->batch.cap) return WS_OK;
   WS_HIP(hipStreamSynchronize(r->ctx->stream)); // (every batch call has waited for its kernel: nothing reads the old block)
-  if (r->batch_host) WS_HIP(hipHostFree(r->batch_host));
-  r->batch_host = r->batch_dev = nullptr;
-  r->batch_cap = 0;
   size_t cap = 64;
   while (cap < k) cap *= 2;
-  WS_HIP(hipHostMalloc(&r->batch_host, cap * reg_batch_record_bytes(), hipHostMallocMapped));
-  WS_HIP(hipHostGetDevicePointer(&r->batch_dev, r->batch_host, 0));
-  r->batch_cap = cap;
-  return WS_OK;
+  return r->batch.grow(cap, reg_batch_record_bytes(), HostBlock::MAPPED);
 }
 
 int ws_register_cloud_batch(ws_reg *r, const ws_map *m, const float *T_in, size_t k, int32_t max_iterations, float it_weight_gradient,
@@ -1635,14 +1562,14 @@ int ws_register_cloud_batch(ws_reg *r, const ws_map *m, const float *T_in, size_
   if (k == 0) return map_take_error(const_cast<ws_map *>(m));
   int rc = reg_batch_reserve(r, k);
   if (rc != WS_OK) return rc;
-  for (size_t i = 0; i < k; ++i) reg_batch_write(r->batch_host, i, T_in + 16 * i);
+  for (size_t i = 0; i < k; ++i) reg_batch_write(r->batch.p, i, T_in + 16 * i);
   // One launch, nothing copied by the runtime: the start records are read from, and the results written to, host-mapped memory.
   // Neither the state buffers, the loop mode nor the sums of the single route are touched.
   rc = launch_reg_batch(r, m, res, flags, k, max_iterations, it_weight_gradient, epsilon);
   if (rc != WS_OK) return rc;
   WS_HIP(hipStreamSynchronize(r->ctx->stream));
   for (size_t i = 0; i < k; ++i)
-    reg_batch_read(r->batch_host, k, i, T_out + 16 * i, iterations ? iterations + i : nullptr, e_out ? e_out + i : nullptr, c_out ? c_out + i : nullptr);
+    reg_batch_read(r->batch.p, k, i, T_out + 16 * i, iterations ? iterations + i : nullptr, e_out ? e_out + i : nullptr, c_out ? c_out + i : nullptr);
   return map_take_error(const_cast<ws_map *>(m));
 }
 
@@ -1669,10 +1596,12 @@ int ws_reg_batch_best(const int32_t *e, const int32_t *c, size_t k, int32_t min_
 // ------------------------------------------------------------------ multi-GPU resident loop
 static int peer_own_mailbox(ws_reg *r)
 {
-  if (r->mailbox) return WS_OK;
-  // fine-grained: coherent for system-scope atomics from every GPU that maps it (and for the polls of the owner)
-  WS_HIP(hipExtMallocWithFlags(&r->mailbox, 4096, hipDeviceMallocFinegrained));
-  WS_HIP(hipMemset(r->mailbox, 0, 4096));
+  if (r->mailbox.p) return WS_OK;
+  // fine-grained: coherent for system-scope atomics from every GPU that maps it (and for the polls of the owner).  The one
+  // allocation DevBuf does not make itself; it frees it like any other
+  WS_HIP(hipExtMallocWithFlags(&r->mailbox.p, 4096, hipDeviceMallocFinegrained));
+  r->mailbox.cap = 4096;
+  WS_HIP(hipMemset(r->mailbox.p, 0, 4096));
   return WS_OK;
 }
 
@@ -1685,7 +1614,7 @@ int ws_reg_peer_mailbox(ws_reg *r, void *ipc_handle_out)
   if (ipc_handle_out)
   {
     hipIpcMemHandle_t h;
-    WS_HIP(hipIpcGetMemHandle(&h, r->mailbox));
+    WS_HIP(hipIpcGetMemHandle(&h, r->mailbox.p));
     std::memcpy(ipc_handle_out, &h, sizeof h);
   }
   return WS_OK;
@@ -1711,9 +1640,9 @@ static int peer_finish_connect(ws_reg *r, int rank, int world, int blocks)
   if (blocks % reg_groups() != 0 || blocks > reg_default_blocks()) return invalid("ws_reg_peer_connect: blocks must be a multiple of 8, at most 256");
   std::vector<unsigned char> image(reg_peer_block_bytes());
   reg_peer_block_fill(image.data(), r->peer_mailbox, rank, world);
-  if (!r->peer_block_dev) WS_HIP(hipMalloc(&r->peer_block_dev, reg_peer_block_bytes()));
-  WS_HIP(hipMemcpy(r->peer_block_dev, image.data(), image.size(), hipMemcpyHostToDevice)); // also zeroes `then`: the mailboxes are fresh
-  WS_HIP(hipMemset(r->mailbox, 0, reg_mailbox_bytes()));
+  if (!r->peer_block_dev.p) WS_TRY(r->peer_block_dev.alloc(reg_peer_block_bytes()));
+  WS_HIP(hipMemcpy(r->peer_block_dev.p, image.data(), image.size(), hipMemcpyHostToDevice)); // also zeroes `then`: the mailboxes are fresh
+  WS_HIP(hipMemset(r->mailbox.p, 0, reg_mailbox_bytes()));
   r->peer_rank = rank;
   r->peer_world = world;
   r->peer_blocks = blocks;
@@ -1743,7 +1672,7 @@ int ws_reg_peer_connect(ws_reg *r, int32_t rank, int32_t world, const void *ipc_
   {
     if (i == rank)
     {
-      r->peer_mailbox[i] = r->mailbox;
+      r->peer_mailbox[i] = r->mailbox.p;
       continue;
     }
     hipIpcMemHandle_t h;
@@ -1771,7 +1700,7 @@ int ws_reg_peer_connect_local(ws_reg *r, int32_t rank, int32_t world, ws_reg *co
     if (!regs[i]) return invalid("ws_reg_peer_connect_local: NULL rank");
     const int rc = peer_own_mailbox(regs[i]);
     if (rc != WS_OK) return rc;
-    r->peer_mailbox[i] = regs[i]->mailbox;
+    r->peer_mailbox[i] = regs[i]->mailbox.p;
   }
   return peer_finish_connect(r, rank, world, blocks);
 }
@@ -1793,14 +1722,14 @@ int ws_register_cloud_peers(ws_reg *r, const ws_map *m, size_t first, size_t cou
   // plus its next one would reach count == world and pass for the all-rank total.  Nothing runs until the mailboxes are fresh.
   if (r->peer_dirty) return invalid("ws_register_cloud_peers: the last exchange failed; call ws_reg_peer_reset on every rank (between two barriers) or reconnect first");
   if (res < 1) return invalid("ws_register_cloud_peers: map_resolution must be positive");
-  *(volatile int32_t *)r->host_flag = 0;
+  *r->host_flag.as<volatile int32_t>() = 0;
   r->peer_dirty = true; // until this exchange has completed on this rank
   int rc = launch_reg_loop(r, m, res, flags, gn_init(T_in, max_iterations, it_weight_gradient, epsilon), true, first, count);
   if (rc != WS_OK) return rc;
   r->latest = 0;
   rc = wait_resident_loop(r);
   if (rc != WS_OK) return rc;
-  const GnCore *h = &r->result_host->core;
+  const GnCore *h = &r->result_host.as<GnState>()->core;
   if (h->error)
   {
     // a rank did not deliver (its kernel was not on the chip, or the process is gone): every rank times out within one
@@ -1827,7 +1756,7 @@ int ws_debug_block_stats(ws_map *m, uint32_t *out, size_t words)
   if (!m || !out) return invalid("ws_debug_block_stats: NULL argument");
   WS_SETTLE(m);
   if (words > WS_BLOCK_STATS) words = WS_BLOCK_STATS;
-  WS_HIP(hipMemcpyAsync(out, m->block_stats, words * sizeof(uint32_t), hipMemcpyDeviceToHost, m->ctx->stream));
+  WS_HIP(hipMemcpyAsync(out, m->block_stats.p, words * sizeof(uint32_t), hipMemcpyDeviceToHost, m->ctx->stream));
   WS_HIP(hipStreamSynchronize(m->ctx->stream));
   return WS_OK;
 }
@@ -1843,7 +1772,7 @@ int ws_debug_reg_stall(ws_reg *r, int32_t stall_next, int32_t *fallbacks)
 int ws_debug_reg_sums(ws_reg *r, int64_t sums_out[44])
 {
   if (!r || !sums_out) return invalid("ws_debug_reg_sums: NULL argument");
-  WS_HIP(hipMemcpyAsync(sums_out, r->state[r->latest].sums, 44 * sizeof(int64_t), hipMemcpyDeviceToHost, r->ctx->stream));
+  WS_HIP(hipMemcpyAsync(sums_out, r->state.as<GnState>()[r->latest].sums, 44 * sizeof(int64_t), hipMemcpyDeviceToHost, r->ctx->stream));
   WS_HIP(hipStreamSynchronize(r->ctx->stream));
   return WS_OK;
 }
@@ -1851,28 +1780,24 @@ int ws_debug_reg_sums(ws_reg *r, int64_t sums_out[44])
 int ws_debug_solve6(ws_context *ctx, const double *A, const double *b, size_t n, double *x, int32_t *status)
 {
   if (!ctx || !A || !b || !x || !status) return invalid("ws_debug_solve6: NULL argument");
-  double *dA = nullptr, *db = nullptr, *dx = nullptr;
-  int32_t *ds = nullptr;
-  hipError_t e = hipMalloc((void **)&dA, (n ? n : 1) * 36 * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc((void **)&db, (n ? n : 1) * 6 * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc((void **)&dx, (n ? n : 1) * 6 * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc((void **)&ds, (n ? n : 1) * sizeof(int32_t));
-  int rc = WS_OK;
-  if (e == hipSuccess && n)
+  DevBuf dA, db, dx, ds;
+  const size_t k = n ? n : 1;
+  int rc = dA.alloc(k, 36 * sizeof(double));
+  if (rc == WS_OK) rc = db.alloc(k, 6 * sizeof(double));
+  if (rc == WS_OK) rc = dx.alloc(k, 6 * sizeof(double));
+  if (rc == WS_OK) rc = ds.alloc(k, sizeof(int32_t));
+  if (rc == WS_OK && n)
   {
     hipStream_t s = ctx->stream;
-    e = hipMemcpyAsync(dA, A, n * 36 * sizeof(double), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(db, b, n * 6 * sizeof(double), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) rc = launch_solve6_test(ctx, dA, db, n, dx, ds);
-    if (e == hipSuccess && rc == WS_OK) e = hipMemcpyAsync(x, dx, n * 6 * sizeof(double), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && rc == WS_OK) e = hipMemcpyAsync(status, ds, n * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+    hipError_t e = hipMemcpyAsync(dA.p, A, n * 36 * sizeof(double), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(db.p, b, n * 6 * sizeof(double), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) rc = launch_solve6_test(ctx, dA.as<double>(), db.as<double>(), n, dx.as<double>(), ds.as<int32_t>());
+    if (e == hipSuccess && rc == WS_OK) e = hipMemcpyAsync(x, dx.p, n * 6 * sizeof(double), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && rc == WS_OK) e = hipMemcpyAsync(status, ds.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) rc = hip_fail(e, "ws_debug_solve6", __FILE__, __LINE__);
   }
-  if (dA) (void)hipFree(dA);
-  if (db) (void)hipFree(db);
-  if (dx) (void)hipFree(dx);
-  if (ds) (void)hipFree(ds);
-  if (e != hipSuccess) return hip_fail(e, "ws_debug_solve6", __FILE__, __LINE__);
+  for (DevBuf *buf : {&dA, &db, &dx, &ds}) buf->release();
   return rc;
 }
 
@@ -1881,12 +1806,24 @@ int ws_scan_destroy(ws_scan *sc)
 {
   if (!sc) return WS_OK;
   (void)hipStreamSynchronize(sc->ctx->stream);
-  void *dev[] = {sc->in_stage, sc->tmp, sc->slot_of, sc->keys, sc->first, sc->wg_count, sc->wg_off, sc->counters, sc->out};
-  for (void *p : dev)
-    if (p) (void)hipFree(p);
-  if (sc->host_count) (void)hipHostFree(sc->host_count);
+  sc->release();
   delete sc;
   return WS_OK;
+}
+
+// the allocations of a scan pre-processor; on an error ws_scan_create frees what is there
+static int scan_build(ws_scan *sc)
+{
+  const size_t blocks = (sc->cap + 255) / 256;
+  WS_TRY(sc->tmp.alloc(sc->cap, 3 * sizeof(int32_t)));
+  WS_TRY(sc->out.alloc(sc->cap, 3 * sizeof(int32_t)));
+  WS_TRY(sc->slot_of.alloc(sc->cap, sizeof(uint32_t)));
+  WS_TRY(sc->keys.alloc(sc->table_slots, sizeof(uint64_t)));
+  WS_TRY(sc->first.alloc(sc->table_slots, sizeof(uint32_t)));
+  WS_TRY(sc->wg_count.alloc(blocks, sizeof(uint32_t)));
+  WS_TRY(sc->wg_off.alloc(blocks, sizeof(uint32_t)));
+  WS_TRY(sc->counters.alloc(16, sizeof(uint32_t)));
+  return sc->host_count.alloc(16, sizeof(uint32_t), HostBlock::MAPPED);
 }
 
 int ws_scan_create(ws_context *ctx, size_t max_points, ws_scan **out)
@@ -1899,20 +1836,9 @@ int ws_scan_create(ws_context *ctx, size_t max_points, ws_scan **out)
   sc->ctx = ctx;
   sc->cap = max_points;
   sc->table_slots = pre_table_slots(max_points);
-  const size_t blocks = (max_points + 255) / 256;
-  hipError_t e = hipMalloc((void **)&sc->tmp, max_points * 3 * sizeof(int32_t));
-  if (e == hipSuccess) e = hipMalloc((void **)&sc->out, max_points * 3 * sizeof(int32_t));
-  if (e == hipSuccess) e = hipMalloc((void **)&sc->slot_of, max_points * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMalloc((void **)&sc->keys, sc->table_slots * sizeof(uint64_t));
-  if (e == hipSuccess) e = hipMalloc((void **)&sc->first, sc->table_slots * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMalloc((void **)&sc->wg_count, blocks * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMalloc((void **)&sc->wg_off, blocks * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMalloc((void **)&sc->counters, 64);
-  if (e == hipSuccess) e = hipHostMalloc((void **)&sc->host_count, 64, hipHostMallocMapped);
-  if (e == hipSuccess) e = hipHostGetDevicePointer((void **)&sc->host_count_dev, sc->host_count, 0);
-  if (e != hipSuccess)
+  const int rc = scan_build(sc);
+  if (rc != WS_OK)
   {
-    const int rc = hip_fail(e, "ws_scan_create allocation", __FILE__, __LINE__);
     ws_scan_destroy(sc);
     return rc;
   }
@@ -1927,7 +1853,7 @@ static int scan_run(ws_scan *sc, const float *xyz_dev, size_t n, size_t stride, 
   int rc = launch_scan_preprocess(sc, xyz_dev, n, stride, M, res);
   if (rc != WS_OK) return rc;
   uint32_t counters[2] = {0, 0};
-  WS_HIP(hipMemcpyAsync(counters, sc->counters, sizeof counters, hipMemcpyDeviceToHost, sc->ctx->stream));
+  WS_HIP(hipMemcpyAsync(counters, sc->counters.p, sizeof counters, hipMemcpyDeviceToHost, sc->ctx->stream));
   WS_HIP(hipStreamSynchronize(sc->ctx->stream));
   sc->n_out = counters[0];
   if (n_out) *n_out = sc->n_out;
@@ -1955,20 +1881,16 @@ int ws_scan_preprocess(ws_scan *sc, const float *xyz_host, size_t n, size_t stri
   if (res < 1) return invalid("ws_scan_preprocess: map_resolution must be positive");
   if (n > sc->cap) return invalid("ws_scan_preprocess: more points than ws_scan_create reserved");
   const size_t floats = n * stride;
-  if (floats > sc->in_stage_floats)
+  if (floats > sc->in_stage.cap)
   {
     WS_HIP(hipStreamSynchronize(sc->ctx->stream));
-    if (sc->in_stage) WS_HIP(hipFree(sc->in_stage));
-    sc->in_stage = nullptr;
-    sc->in_stage_floats = 0;
-    WS_HIP(hipMalloc((void **)&sc->in_stage, floats * sizeof(float)));
-    sc->in_stage_floats = floats;
+    WS_TRY(sc->in_stage.grow(floats, sizeof(float), DevBuf::EXACT));
   }
-  if (floats) WS_HIP(hipMemcpyAsync(sc->in_stage, xyz_host, floats * sizeof(float), hipMemcpyHostToDevice, sc->ctx->stream));
-  return scan_run(sc, sc->in_stage, n, stride, pose, res, n_out);
+  if (floats) WS_HIP(hipMemcpyAsync(sc->in_stage.p, xyz_host, floats * sizeof(float), hipMemcpyHostToDevice, sc->ctx->stream));
+  return scan_run(sc, sc->in_stage.as<float>(), n, stride, pose, res, n_out);
 }
 
-const int32_t *ws_scan_points_dev(const ws_scan *sc) { return sc ? sc->out : nullptr; }
+const int32_t *ws_scan_points_dev(const ws_scan *sc) { return sc ? sc->out.as<int32_t>() : nullptr; }
 
 int ws_scan_download(ws_scan *sc, int32_t *xyz_host, size_t capacity_points, size_t *n_out)
 {
@@ -1976,7 +1898,7 @@ int ws_scan_download(ws_scan *sc, int32_t *xyz_host, size_t capacity_points, siz
   *n_out = sc->n_out;
   if (sc->n_out == 0) return WS_OK;
   if (!xyz_host || capacity_points < sc->n_out) return invalid("ws_scan_download: buffer too small");
-  WS_HIP(hipMemcpyAsync(xyz_host, sc->out, sc->n_out * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, sc->ctx->stream));
+  WS_HIP(hipMemcpyAsync(xyz_host, sc->out.p, sc->n_out * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, sc->ctx->stream));
   WS_HIP(hipStreamSynchronize(sc->ctx->stream));
   return WS_OK;
 }

@@ -300,7 +300,7 @@ __global__ __launch_bounds__(64) void raycast_grad_kernel(RayArgs a)
 int launch_raycast(ws_map *m, int which, const int32_t origin[3], const int32_t *dirs_dev, size_t n, int32_t max_range, uint32_t flags)
 {
   RayArgs a;
-  a.data = m->data[which];
+  a.data = m->data[which].as<uint32_t>();
   a.mp = m->par[which];
   for (int k = 0; k < 3; ++k)
   {

@@ -2120,10 +2120,10 @@ static PointArgs make_point_args(ws_reg *r, const ws_map *m, int32_t res, uint32
   }
   if (first > end) first = end;
   PointArgs p;
-  p.points = r->points;
+  p.points = r->points.as<int32_t>();
   p.first = (uint32_t)first;
   p.end = (uint32_t)end;
-  p.map_data = m->data[WS_MAP_AVG];
+  p.map_data = m->data[WS_MAP_AVG].as<uint32_t>();
   p.map = m->par[WS_MAP_AVG];
   p.resdiv = make_fastdiv(res);
   return p;
@@ -2134,8 +2134,8 @@ int launch_reg_server(ws_reg *r, const ws_map *m, int32_t res, uint32_t flags, u
   ws_context *ctx = r->ctx;
   ServerArgs a;
   a.pts = make_point_args(r, m, res, flags, 0, r->n);
-  a.ctl = reinterpret_cast<ServerCtl *>(r->srv_ctl);
-  a.mail = static_cast<ServerMail *>(r->srv_mail_dev);
+  a.ctl = r->srv_ctl.as<ServerCtl>();
+  a.mail = r->srv_mail.dev_as<ServerMail>();
   a.launch_id = launch_id;
   a.served = served;
   a.idle_ticks = idle_us * 100u; // wall_clock64: 100 MHz
@@ -2152,7 +2152,7 @@ int launch_reg_server(ws_reg *r, const ws_map *m, int32_t res, uint32_t flags, u
 
 int launch_reg_solve(ws_reg *r, const int64_t *sums_dev)
 {
-  hipLaunchKernelGGL(reg_solve_kernel, dim3(1), dim3(64), 0, r->ctx->stream, &r->state[r->latest], sums_dev);
+  hipLaunchKernelGGL(reg_solve_kernel, dim3(1), dim3(64), 0, r->ctx->stream, &r->state.as<GnState>()[r->latest], sums_dev);
   WS_HIP(hipGetLastError());
   return WS_OK;
 }
@@ -2167,8 +2167,8 @@ int launch_reg_pass(ws_reg *r, const ws_map *m, int32_t res, uint32_t flags, siz
     PassArgs<true> a;
     a.pts = make_point_args(r, m, res, flags, first, count);
     for (int i = 0; i < 16; ++i) a.T[i] = T[i];
-    a.partials = r->partials;
-    a.arrived = r->pass_arrived;
+    a.partials = r->partials.as<int64_t>();
+    a.arrived = r->pass_arrived.as<uint32_t>();
     a.sums = sums;
     a.seq = seq;
     hipLaunchKernelGGL(reg_pass_kernel<true>, dim3(REG_BLOCKS), dim3(REG_THREADS), 0, ctx->stream, a);
@@ -2177,10 +2177,10 @@ int launch_reg_pass(ws_reg *r, const ws_map *m, int32_t res, uint32_t flags, siz
   {
     PassArgs<false> a;
     a.pts = make_point_args(r, m, res, flags, first, count);
-    a.state = &r->state[r->latest]; // one buffer, no parity: see reg_pass_kernel
+    a.state = &r->state.as<GnState>()[r->latest]; // one buffer, no parity: see reg_pass_kernel
     a.sums = sums;
-    a.partials = r->partials;
-    a.arrived = r->pass_arrived;
+    a.partials = r->partials.as<int64_t>();
+    a.arrived = r->pass_arrived.as<uint32_t>();
     a.apply = apply ? 1 : 0;
     hipLaunchKernelGGL(reg_pass_kernel<false>, dim3(REG_BLOCKS), dim3(REG_THREADS), 0, ctx->stream, a);
   }
@@ -2194,10 +2194,10 @@ int launch_reg_iteration(ws_reg *r, const ws_map *m, int32_t res, uint32_t flags
   ws_context *ctx = r->ctx;
   IterArgs a;
   a.pts = make_point_args(r, m, res, flags, 0, r->n);
-  a.state = r->state;
-  a.partials = r->partials;
+  a.state = r->state.as<GnState>();
+  a.partials = r->partials.as<int64_t>();
   a.k = k;
-  a.host_flag = r->host_flag_dev;
+  a.host_flag = r->host_flag.dev_as<int32_t>();
   prof_begin(ctx, WS_K_REG);
   hipLaunchKernelGGL(reg_iter_kernel, dim3(REG_BLOCKS), dim3(REG_THREADS), 0, ctx->stream, a);
   prof_end(ctx, WS_K_REG);
@@ -2225,21 +2225,21 @@ int launch_reg_loop(ws_reg *r, const ws_map *m, int32_t res, uint32_t flags, con
   LoopArgs a;
   a.pts = make_point_args(r, m, res, flags, peers ? first : 0, peers ? count : r->n);
   a.init = init;
-  a.state = r->state;
-  a.result_host = r->result_host_dev;
+  a.state = r->state.as<GnState>();
+  a.result_host = r->result_host.dev_as<GnState>();
   if (!r->loop_sets_clear)
   {
-    WS_HIP(hipMemsetAsync(r->grid_bar, 0, 2 * REG_SET_BYTES, ctx->stream));
+    WS_HIP(hipMemsetAsync(r->grid_bar.p, 0, 2 * REG_SET_BYTES, ctx->stream));
     r->loop_sets_clear = true;
   }
-  char *mine = reinterpret_cast<char *>(r->grid_bar) + (r->loop_launches & 1u) * REG_SET_BYTES;
-  char *other = reinterpret_cast<char *>(r->grid_bar) + ((r->loop_launches + 1) & 1u) * REG_SET_BYTES;
+  char *mine = r->grid_bar.as<char>() + (r->loop_launches & 1u) * REG_SET_BYTES;
+  char *other = r->grid_bar.as<char>() + ((r->loop_launches + 1) & 1u) * REG_SET_BYTES;
   r->loop_launches += 1;
   a.accum = reinterpret_cast<uint64_t *>(mine + REG_ACCUM_OFFSET); // (the abort flag is the first word of the set)
-  a.peers = reinterpret_cast<PeerBlock *>(r->peer_block_dev);
+  a.peers = r->peer_block_dev.as<PeerBlock>();
   a.clear_next = reinterpret_cast<uint32_t *>(other);
   a.clear_words = (uint32_t)(REG_SET_BYTES / sizeof(uint32_t));
-  a.host_flag = r->host_flag_dev;
+  a.host_flag = r->host_flag.dev_as<int32_t>();
   a.debug_stall = r->debug_stall_next;
   r->debug_stall_next = 0;
   prof_begin(ctx, WS_K_REG);
@@ -2486,8 +2486,8 @@ int launch_reg_batch(ws_reg *r, const ws_map *m, int32_t res, uint32_t flags, si
   ws_context *ctx = r->ctx;
   BatchArgs a;
   a.pts = make_point_args(r, m, res, flags, 0, r->n);
-  a.in = static_cast<const BatchIn *>(r->batch_dev);
-  a.out = reinterpret_cast<BatchOut *>(static_cast<BatchIn *>(r->batch_dev) + k);
+  a.in = r->batch.dev_as<BatchIn>();
+  a.out = reinterpret_cast<BatchOut *>(r->batch.dev_as<BatchIn>() + k);
   a.max_iterations = max_iterations;
   a.it_weight_gradient = it_weight_gradient;
   a.epsilon = epsilon;

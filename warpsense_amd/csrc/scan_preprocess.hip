@@ -172,30 +172,30 @@ size_t pre_table_slots(size_t max_points)
 int launch_scan_preprocess(ws_scan *sc, const float *xyz_dev, size_t n, size_t stride, const int32_t M[16], int32_t res)
 {
   hipStream_t s = sc->ctx->stream;
-  WS_HIP(hipMemsetAsync(sc->counters, 0, 2 * sizeof(uint32_t), s));
-  *(volatile uint32_t *)sc->host_count = 0;
+  WS_HIP(hipMemsetAsync(sc->counters.p, 0, 2 * sizeof(uint32_t), s));
+  *sc->host_count.as<volatile uint32_t>() = 0;
   if (n == 0) return WS_OK;
-  WS_HIP(hipMemsetAsync(sc->keys, 0xff, sc->table_slots * sizeof(uint64_t), s));
-  WS_HIP(hipMemsetAsync(sc->first, 0xff, sc->table_slots * sizeof(uint32_t), s));
+  WS_HIP(hipMemsetAsync(sc->keys.p, 0xff, sc->table_slots * sizeof(uint64_t), s));
+  WS_HIP(hipMemsetAsync(sc->first.p, 0xff, sc->table_slots * sizeof(uint32_t), s));
   PreArgs a;
   a.xyz = xyz_dev;
   a.n = (uint32_t)n;
   a.stride = (uint32_t)stride;
   for (int k = 0; k < 16; ++k) a.M[k] = M[k];
   a.res = res;
-  a.tmp = sc->tmp;
-  a.slot_of = sc->slot_of;
-  a.keys = sc->keys;
-  a.first = sc->first;
+  a.tmp = sc->tmp.as<int32_t>();
+  a.slot_of = sc->slot_of.as<uint32_t>();
+  a.keys = sc->keys.as<uint64_t>();
+  a.first = sc->first.as<uint32_t>();
   a.mask = (uint32_t)(sc->table_slots - 1);
-  a.wg_count = sc->wg_count;
-  a.wg_off = sc->wg_off;
-  a.counters = sc->counters;
-  a.out = sc->out;
+  a.wg_count = sc->wg_count.as<uint32_t>();
+  a.wg_off = sc->wg_off.as<uint32_t>();
+  a.counters = sc->counters.as<uint32_t>();
+  a.out = sc->out.as<int32_t>();
   const uint32_t blocks = (uint32_t)((n + 255) / 256);
   hipLaunchKernelGGL(pre_insert_kernel, dim3(blocks), dim3(256), 0, s, a);
   hipLaunchKernelGGL(pre_count_kernel, dim3(blocks), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(pre_scan_kernel, dim3(1), dim3(1024), 0, s, a, blocks, sc->host_count_dev);
+  hipLaunchKernelGGL(pre_scan_kernel, dim3(1), dim3(1024), 0, s, a, blocks, sc->host_count.dev_as<uint32_t>());
   hipLaunchKernelGGL(pre_scatter_kernel, dim3(blocks), dim3(256), 0, s, a);
   WS_HIP(hipGetLastError());
   return WS_OK;

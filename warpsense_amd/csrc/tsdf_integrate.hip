@@ -109,8 +109,8 @@ __global__ __launch_bounds__(256) void tsdf_stats_kernel(TsdfCounters *c, const 
 }
 int launch_tsdf_stats(ws_map *m)
 {
-  hipLaunchKernelGGL(tsdf_stats_kernel, dim3(1), dim3(256), 0, m->ctx->stream, m->counters, (const uint32_t *)m->block_stats, m->tail_blocks,
-                     (const uint32_t *)(m->block_stats + 2 * WS_TAIL_STATS), m->resolve_blocks);
+  hipLaunchKernelGGL(tsdf_stats_kernel, dim3(1), dim3(256), 0, m->ctx->stream, m->counters.as<TsdfCounters>(), (const uint32_t *)m->block_stats.as<uint32_t>(), m->tail_blocks,
+                     (const uint32_t *)(m->block_stats.as<uint32_t>() + 2 * WS_TAIL_STATS), m->resolve_blocks);
   WS_HIP(hipGetLastError());
   return WS_OK;
 }
@@ -199,10 +199,10 @@ int launch_box_copy(ws_map *m, const MapParams &par, int which, const int32_t lo
   if (blocks > 4096) blocks = 4096;
   if (blocks < 1) blocks = 1;
   if (pack)
-    hipLaunchKernelGGL((box_copy_kernel<true>), dim3((unsigned)blocks), dim3(256), 0, s, m->data[which], par, lo[0], lo[1], lo[2],
+    hipLaunchKernelGGL((box_copy_kernel<true>), dim3((unsigned)blocks), dim3(256), 0, s, m->data[which].as<uint32_t>(), par, lo[0], lo[1], lo[2],
                        ext[0], ext[1], ext[2], box_dev);
   else
-    hipLaunchKernelGGL((box_copy_kernel<false>), dim3((unsigned)blocks), dim3(256), 0, s, m->data[which], par, lo[0], lo[1], lo[2],
+    hipLaunchKernelGGL((box_copy_kernel<false>), dim3((unsigned)blocks), dim3(256), 0, s, m->data[which].as<uint32_t>(), par, lo[0], lo[1], lo[2],
                        ext[0], ext[1], ext[2], box_dev);
   WS_HIP(hipGetLastError());
   return WS_OK;
@@ -228,7 +228,7 @@ int launch_box_fill(ws_map *m, const MapParams &par, int which, const int32_t lo
   int64_t blocks = (n + 255) / 256;
   if (blocks > 4096) blocks = 4096;
   if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(box_fill_kernel, dim3((unsigned)blocks), dim3(256), 0, s, m->data[which], par, lo[0], lo[1], lo[2], ext[0], ext[1],
+  hipLaunchKernelGGL(box_fill_kernel, dim3((unsigned)blocks), dim3(256), 0, s, m->data[which].as<uint32_t>(), par, lo[0], lo[1], lo[2], ext[0], ext[1],
                      ext[2], value);
   WS_HIP(hipGetLastError());
   return WS_OK;
@@ -249,16 +249,16 @@ int launch_tsdf_integrate(ws_map *m)
   ws_context *ctx = m->ctx;
   hipStream_t s = ctx->stream;
   IntegrateArgs ia;
-  ia.new_data = m->data[WS_MAP_NEW];
-  ia.avg_data = m->data[WS_MAP_AVG];
-  ia.tile_list = m->tile_list;
+  ia.new_data = m->data[WS_MAP_NEW].as<uint32_t>();
+  ia.avg_data = m->data[WS_MAP_AVG].as<uint32_t>();
+  ia.tile_list = m->tile_list.as<TileEntry>();
   ia.map = m->par[WS_MAP_NEW];
   ia.nty = m->nty;
   ia.ntz = m->ntz;
   ia.n_vox = m->n_vox;
   ia.max_weight = m->max_weight;
   ia.tau = m->tau;
-  ia.counters = m->counters;
+  ia.counters = m->counters.as<TsdfCounters>();
   const dim3 block(256);
   if (!m->fused_done)
   {

@@ -2208,13 +2208,13 @@ constexpr int PREP_GRID = 512;
 static PrepArgs make_prep_args(ws_map *m)
 {
   PrepArgs p;
-  p.counters = m->counters;
-  p.az_hist = m->az_hist;
+  p.counters = m->counters.as<TsdfCounters>();
+  p.az_hist = m->az_hist.as<uint32_t>();
   p.n_hist = (uint32_t)(AZ_BINS + 1);
-  p.tile_nsub = m->tile_nsub;
-  p.tile_dirty = m->tile_dirty;
+  p.tile_nsub = m->tile_nsub.as<uint32_t>();
+  p.tile_dirty = m->tile_dirty.as<uint8_t>();
   p.n_tiles = m->n_tiles;
-  p.big_keys = m->big_keys;
+  p.big_keys = m->big_keys.as<unsigned long long>();
   p.big_slots = m->big_slots;
   return p;
 }
@@ -2222,7 +2222,7 @@ int launch_scatter_prep(ws_map *m)
 {
   hipLaunchKernelGGL(scatter_prep_kernel, dim3(PREP_GRID), dim3(256), 0, m->ctx->stream, make_prep_args(m));
   WS_HIP(hipGetLastError());
-  m->status_host[10] = 0;
+  m->status.as<uint32_t>()[10] = 0;
   m->prepped = true;
   return WS_OK;
 }
@@ -2258,11 +2258,11 @@ static int enqueue_scatter(ws_map *m, const int32_t *xyz_dev, size_t n, const in
   ws_context *ctx = m->ctx;
   hipStream_t s = ctx->stream;
   // the (tile, entry) hash keeps the keys of released tiles: empty it before it fills up
-  if (m->status_host[10] > m->big_slots / 4) m->prepped = false;
+  if (m->status.as<uint32_t>()[10] > m->big_slots / 4) m->prepped = false;
   ScatterArgs sa;
   sa.xyz = xyz_dev;
   // (a scan, or a piece of one, that already lies in the map's own buffer is not copied there)
-  sa.xyz_keep = (xyz_dev >= m->scan_dev && xyz_dev < m->scan_dev + 3 * MAX_SCAN_POINTS) ? nullptr : m->scan_dev;
+  sa.xyz_keep = (xyz_dev >= m->scan_dev.as<int32_t>() && xyz_dev < m->scan_dev.as<int32_t>() + 3 * MAX_SCAN_POINTS) ? nullptr : m->scan_dev.as<int32_t>();
   sa.n = (uint32_t)n;
   for (int k = 0; k < 3; ++k)
   {
@@ -2284,29 +2284,29 @@ static int enqueue_scatter(ws_map *m, const int32_t *xyz_dev, size_t n, const in
     sa.keyed_len_neg = (int32_t)(len_neg > INT32_MAX ? INT32_MAX : len_neg);
     sa.keyed_slack = (int32_t)(2 * (dz_min + 1) + 3 * (int64_t)m->res + 4);
   }
-  sa.rays = (RaySetup *)m->rays;
-  sa.az_hist = m->az_hist;
-  sa.az_off = m->az_off;
-  sa.ray_bin = reinterpret_cast<uint2 *>(m->ray_bin);
-  sa.ray_order = m->ray_order;
-  sa.fan_steps = m->fan_steps;
-  sa.vstate = m->vstate;
-  sa.tile_dirty = m->tile_dirty;
-  sa.tile_nsub = m->tile_nsub;
-  sa.tile_ent = m->tile_ent;
-  sa.tile_list = m->tile_list;
-  sa.rec = m->rec;
+  sa.rays = m->rays.as<RaySetup>();
+  sa.az_hist = m->az_hist.as<uint32_t>();
+  sa.az_off = m->az_off.as<uint32_t>();
+  sa.ray_bin = m->ray_bin.as<uint2>();
+  sa.ray_order = m->ray_order.as<uint32_t>();
+  sa.fan_steps = m->fan_steps.as<int32_t>();
+  sa.vstate = m->vstate.as<uint8_t>();
+  sa.tile_dirty = m->tile_dirty.as<uint8_t>();
+  sa.tile_nsub = m->tile_nsub.as<uint32_t>();
+  sa.tile_ent = m->tile_ent.as<uint32_t>();
+  sa.tile_list = m->tile_list.as<TileEntry>();
+  sa.rec = m->rec.as<unsigned long long>();
   sa.sub_cap = m->sub_cap;
   sa.scan_seq = ++m->scan_seq;
-  sa.big_keys = m->big_keys;
+  sa.big_keys = m->big_keys.as<unsigned long long>();
   sa.big_mask = m->big_slots - 1;
   {
     const RecFormat rf = rec_format(n);
     sa.rec_fmt = (uint32_t)rf.S | ((uint32_t)rf.F << 8);
   }
-  sa.tail_stats = m->block_stats;
-  sa.counters = m->counters;
-  sa.status = m->status_dev;
+  sa.tail_stats = m->block_stats.as<uint32_t>();
+  sa.counters = m->counters.as<TsdfCounters>();
+  sa.status = m->status.dev_as<uint32_t>();
 
   const dim3 block(256);
   const dim3 grid_setup((unsigned)((n + 255) / 256));
@@ -2319,7 +2319,7 @@ static int enqueue_scatter(ws_map *m, const int32_t *xyz_dev, size_t n, const in
   if (!m->prepped)
   {
     hipLaunchKernelGGL(scatter_prep_kernel, dim3(PREP_GRID), block, 0, s, make_prep_args(m));
-    m->status_host[10] = 0;
+    m->status.as<uint32_t>()[10] = 0;
   }
   m->prepped = false;
   hipLaunchKernelGGL(ray_setup_kernel, grid_setup, block, 0, s, sa);
@@ -2344,20 +2344,20 @@ static int enqueue_scatter(ws_map *m, const int32_t *xyz_dev, size_t n, const in
   }
 
   ResolveArgs ra;
-  ra.tile_list = m->tile_list;
-  ra.tile_nsub = m->tile_nsub;
-  ra.tile_ent = m->tile_ent;
+  ra.tile_list = m->tile_list.as<TileEntry>();
+  ra.tile_nsub = m->tile_nsub.as<uint32_t>();
+  ra.tile_ent = m->tile_ent.as<uint32_t>();
   ra.sub_cap = m->sub_cap;
-  ra.tile_dirty = m->tile_dirty;
-  ra.recs = m->rec;
-  ra.big_keys = m->big_keys;
+  ra.tile_dirty = m->tile_dirty.as<uint8_t>();
+  ra.recs = m->rec.as<unsigned long long>();
+  ra.big_keys = m->big_keys.as<unsigned long long>();
   ra.big_mask = m->big_slots - 1;
   ra.scan_seq = sa.scan_seq;
   ra.fan_mask = (1u << (sa.rec_fmt >> 8)) - 1u;
   ra.fan_mid = rec_fan_mid((int32_t)(sa.rec_fmt >> 8));
-  ra.new_data = m->data[WS_MAP_NEW];
-  ra.avg_data = m->data[WS_MAP_AVG];
-  ra.vstate = m->vstate;
+  ra.new_data = m->data[WS_MAP_NEW].as<uint32_t>();
+  ra.avg_data = m->data[WS_MAP_AVG].as<uint32_t>();
+  ra.vstate = m->vstate.as<uint8_t>();
   ra.map = m->par[WS_MAP_NEW];
   ra.nty = m->nty;
   ra.ntz = m->ntz;
@@ -2368,9 +2368,9 @@ static int enqueue_scatter(ws_map *m, const int32_t *xyz_dev, size_t n, const in
     ra.wM32 = (uint32_t)wd.M;
     ra.wS = wd.k - 32;
   }
-  ra.resolve_stats = m->block_stats + 2 * WS_TAIL_STATS;
-  ra.counters = m->counters;
-  ra.status = m->status_dev;
+  ra.resolve_stats = m->block_stats.as<uint32_t>() + 2 * WS_TAIL_STATS;
+  ra.counters = m->counters.as<TsdfCounters>();
+  ra.status = m->status.dev_as<uint32_t>();
   ra.n_tiles = m->n_tiles;
   m->resolve_blocks = RESOLVE_GRID;
   prof_begin(ctx, WS_K_TILE_RESOLVE);
@@ -2405,7 +2405,7 @@ int settle_tsdf(ws_map *m)
   if (!m->pending.active.load(std::memory_order_acquire)) return WS_OK;
   ws_context *ctx = m->ctx;
   hipStream_t s = ctx->stream;
-  volatile uint32_t *st = m->status_host;
+  volatile uint32_t *st = m->status.as<uint32_t>();
   auto done = [&](int rc) {
     m->pending.active.store(false, std::memory_order_release);
     return rc;
@@ -2431,7 +2431,7 @@ int settle_tsdf(ws_map *m)
   };
   // a larger pool for a scan of n points that has just been aborted for lack of one
   auto grow_pool = [&](size_t n) -> int {
-    const unsigned long long need = *reinterpret_cast<volatile unsigned long long *>(m->status_host + 4) & ((1ull << 48) - 1ull);
+    const unsigned long long need = *reinterpret_cast<volatile unsigned long long *>(m->status.as<uint32_t>() + 4) & ((1ull << 48) - 1ull);
     uint64_t grow_to = subs_for_scan(m, need, n);
     if (grow_to < (uint64_t)m->sub_cap * 2) grow_to = (uint64_t)m->sub_cap * 2;
     if (grow_to > SUB_ID_LIMIT)
@@ -2465,7 +2465,7 @@ int settle_tsdf(ws_map *m)
         for (int attempt = 0;; ++attempt)
         {
           uint32_t seq = 0;
-          int rc = enqueue_scatter(m, m->scan_dev + 3 * off, cnt, m->pending.pos, m->pending.up, false, s0, &seq);
+          int rc = enqueue_scatter(m, m->scan_dev.as<int32_t>() + 3 * off, cnt, m->pending.pos, m->pending.up, false, s0, &seq);
           if (rc != WS_OK) return done(rc);
           const int pv = verdict(seq);
           if (pv < 0) return done(pv);
@@ -2496,7 +2496,7 @@ int settle_tsdf(ws_map *m)
     // The repeat reads the copy of the scan the set-up pass of the aborted attempt has left in scan_dev, and takes the route
     // (default / non-default new_map) of the first attempt.
     int rc = grow_pool(m->pending.n);
-    if (rc == WS_OK) rc = enqueue_scatter(m, m->scan_dev, m->pending.n, m->pending.pos, m->pending.up, m->pending.fused, m->pending.s0, &m->pending.seq);
+    if (rc == WS_OK) rc = enqueue_scatter(m, m->scan_dev.as<int32_t>(), m->pending.n, m->pending.pos, m->pending.up, m->pending.fused, m->pending.s0, &m->pending.seq);
     if (rc == WS_OK && m->pending.integrate_after) rc = launch_tsdf_integrate(m);
     if (rc != WS_OK) return done(rc);
   }
@@ -2515,8 +2515,8 @@ int launch_tsdf_scatter(ws_map *m, const int32_t *xyz_dev, size_t n, const int32
   {
     m->resolve_blocks = 0;
     // nothing listed: a following integrate pass has nothing to do
-    WS_HIP(hipMemsetAsync(&m->counters->n_listed, 0, sizeof(uint32_t), s));
-    WS_HIP(hipMemsetAsync(&m->counters->n_appended, 0, sizeof(uint32_t), s));
+    WS_HIP(hipMemsetAsync(&m->counters.as<TsdfCounters>()->n_listed, 0, sizeof(uint32_t), s));
+    WS_HIP(hipMemsetAsync(&m->counters.as<TsdfCounters>()->n_appended, 0, sizeof(uint32_t), s));
     return WS_OK;
   }
   uint32_t seq = 0;

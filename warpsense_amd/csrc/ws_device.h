@@ -137,7 +137,7 @@ struct BoxArgs
 inline BoxArgs box_args(const ws_map *m, int which, const int32_t lo[3], const int32_t ext[3])
 {
   BoxArgs b;
-  b.data = m->data[which];
+  b.data = m->data[which].as<uint32_t>();
   b.mp = m->par[which];
   for (int k = 0; k < 3; ++k) b.lo[k] = lo[k];
   b.ex = ext[0];

@@ -7,6 +7,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -201,28 +202,86 @@ int hip_fail(hipError_t e, const char *what, const char *file, int line);
     if (e__ != hipSuccess) return ws::hip_fail(e__, #call, __FILE__, __LINE__); \
   } while (0)
 
-// ---- host state of the map queries (ws_map::surf, mesh, ray, dist): allocated on first use, grown on demand
+#define WS_TRY(call)                        \
+  do                                        \
+  {                                         \
+    const int rc__ = (call);                \
+    if (rc__ != WS_OK) return rc__;         \
+  } while (0)
+
+// ---- the owners of every device and pinned allocation of the library.  For each of them: after a failed allocation the object is
+// empty (null pointers, zero capacity), release() may be called any number of times, and a successful grow(need) leaves cap >= need.
 // a device buffer whose contents are not kept when it grows
 struct DevBuf
 {
+  enum Slack
+  {
+    EXACT,  // what was asked for: fixed-size members, and staging that follows boxes of gigabytes
+    EIGHTH, // an eighth more: a result that gains a few records per call does not reallocate on every call
+  };
   void *p = nullptr;
   size_t cap = 0; // elements
-  // room for at least `need` elements.  The caller has synchronised the stream.
-  int grow(size_t need, size_t elem_bytes)
+  template <typename T> T *as() { return static_cast<T *>(p); }
+  template <typename T> const T *as() const { return static_cast<const T *>(p); }
+  // exactly `n` elements in place of whatever it held.  The caller has synchronised the stream.
+  int alloc(size_t n, size_t elem_bytes = 1)
   {
-    if (need <= cap) return WS_OK;
-    if (p) WS_HIP(hipFree(p));
-    p = nullptr;
-    cap = 0;
-    need += need / 8; // a little room: a map that gains a few points per scan does not reallocate on every call
-    WS_HIP(hipMalloc(&p, need * elem_bytes));
-    cap = need;
+    release();
+    const hipError_t e = hipMalloc(&p, n * elem_bytes);
+    if (e != hipSuccess)
+    {
+      p = nullptr;
+      return hip_fail(e, "hipMalloc", __FILE__, __LINE__);
+    }
+    cap = n;
     return WS_OK;
   }
+  // room for at least `need` elements.  The caller has synchronised the stream.
+  int grow(size_t need, size_t elem_bytes, Slack slack = EIGHTH) { return need <= cap ? WS_OK : alloc(slack == EIGHTH ? need + need / 8 : need, elem_bytes); }
   void release()
   {
     if (p) (void)hipFree(p);
     p = nullptr;
+    cap = 0;
+  }
+};
+
+// pinned host memory; a MAPPED block is also addressed by the device, through `dev`.  Its contents are not kept when it grows
+struct HostBlock
+{
+  enum Kind
+  {
+    PINNED = hipHostMallocDefault,
+    MAPPED = hipHostMallocMapped,
+  };
+  void *p = nullptr;   // as the host addresses it
+  void *dev = nullptr; // device view (MAPPED only)
+  size_t cap = 0;      // elements
+  template <typename T> T *as() { return static_cast<T *>(p); }
+  template <typename T> const T *as() const { return static_cast<const T *>(p); }
+  template <typename T> T *dev_as() { return static_cast<T *>(dev); }
+  template <typename T> const T *dev_as() const { return static_cast<const T *>(dev); }
+  // exactly `n` elements in place of whatever it held, zero-filled if `zero`.  Nothing on the device uses the old block any more.
+  int alloc(size_t n, size_t elem_bytes, Kind kind, bool zero = false)
+  {
+    release();
+    hipError_t e = hipHostMalloc(&p, n * elem_bytes, (unsigned)kind);
+    if (e != hipSuccess) p = nullptr;
+    if (e == hipSuccess && kind == MAPPED) e = hipHostGetDevicePointer(&dev, p, 0);
+    if (e != hipSuccess)
+    {
+      release();
+      return hip_fail(e, kind == MAPPED ? "hipHostMalloc (mapped)" : "hipHostMalloc", __FILE__, __LINE__);
+    }
+    if (zero) std::memset(p, 0, n * elem_bytes);
+    cap = n;
+    return WS_OK;
+  }
+  int grow(size_t need, size_t elem_bytes, Kind kind, bool zero = false) { return need <= cap ? WS_OK : alloc(need, elem_bytes, kind, zero); }
+  void release()
+  {
+    if (p) (void)hipHostFree(p);
+    p = dev = nullptr;
     cap = 0;
   }
 };
@@ -233,9 +292,12 @@ struct DevCounter
   unsigned long long *dev = nullptr, *host = nullptr;
   int alloc(size_t words, bool on_device = true)
   {
-    if (on_device && !dev) WS_HIP(hipMalloc((void **)&dev, words * sizeof(unsigned long long)));
-    if (!host) WS_HIP(hipHostMalloc((void **)&host, words * sizeof(unsigned long long), hipHostMallocDefault));
-    return WS_OK;
+    hipError_t e = hipSuccess;
+    if (on_device && !dev && (e = hipMalloc((void **)&dev, words * sizeof(unsigned long long))) != hipSuccess) dev = nullptr;
+    if (e == hipSuccess && !host && (e = hipHostMalloc((void **)&host, words * sizeof(unsigned long long), hipHostMallocDefault)) != hipSuccess) host = nullptr;
+    if (e == hipSuccess) return WS_OK;
+    release();
+    return hip_fail(e, "hipMalloc / hipHostMalloc (query counter)", __FILE__, __LINE__);
   }
   // enqueue the copy into the pinned words, from `dev` unless the device words live elsewhere
   int fetch(hipStream_t s, size_t words = 1, const unsigned long long *from = nullptr)
@@ -329,46 +391,44 @@ struct ws_map
   ws_context *ctx = nullptr;
   ws::MapParams par[2]; // [WS_MAP_AVG], [WS_MAP_NEW]
   int64_t n_vox = 0;
-  uint32_t *data[2] = {nullptr, nullptr};
-  uint8_t *vstate = nullptr; // two planes of one byte per voxel, tile-major in bricks (vstate_plane_bytes, vbrick): keyed / touched by free space / free-space hit on a keyed voxel; off-ray free-space hit
-  void *rays = nullptr;      // per-ray set-up records (sizeof(RaySetup) x 1 000 000)
-  uint32_t *az_hist = nullptr, *az_off = nullptr, *ray_order = nullptr; // rays grouped by direction bin
-  void *ray_bin = nullptr;   // [1 000 000] uint2: (direction bin, rank inside the bin) per ray
-  int32_t *fan_steps = nullptr;       // [256] first ray step whose fan has j + 1 targets (depends on res only), see tail_bound
+  ws::DevBuf data[2];       // uint32 [n_vox] (+ 16 bytes: the tile kernels read the four voxels of a column as one access, also at the very end)
+  ws::DevBuf vstate;        // uint8: two planes of one byte per voxel, tile-major in bricks (vstate_plane_bytes, vbrick): keyed / touched by free space / free-space hit on a keyed voxel; off-ray free-space hit
+  ws::DevBuf rays;          // per-ray set-up records (sizeof(RaySetup) x 1 000 000)
+  ws::DevBuf az_hist, az_off, ray_order; // uint32: rays grouped by direction bin
+  ws::DevBuf ray_bin;       // [1 000 000] uint2: (direction bin, rank inside the bin) per ray
+  ws::DevBuf fan_steps;     // int32 [256] first ray step whose fan has j + 1 targets (depends on res only), see tail_bound
   int32_t fan_steps_host[ws::WS_FAN_TABLE] = {}; // staging of the same (lives as long as the map: async upload); [256..259]: division constants of ntz, nty
   bool prepped = false; // the scatter's scratch (histograms, tile counters, free-space hash) is zero / empty
   int32_t tau = 0, max_weight = 0, res = 0;
   bool new_is_default = false; // new_map known to be (tau,0) everywhere
   int integrate_mode = WS_INTEGRATE_SPARSE;
-  int32_t *scan_dev = nullptr; // 1 000 000-point upload buffer
+  ws::DevBuf scan_dev;      // int32: 1 000 000-point upload buffer
   // tile grid (4 x 4 x 64 voxels of storage space)
   int32_t ntx = 0, nty = 0, ntz = 0;
   int64_t n_tiles = 0;
-  uint32_t *tile_nsub = nullptr;    // [n_tiles] sub-chunks (= entries) of the tile in the scan in flight (zero between scans)
-  uint32_t *tile_ent = nullptr;     // [n_tiles][TILE_DIRECT] entries: sub-chunk id << 5 | records - 1 (never cleared: tile_nsub says how many are valid)
-  uint8_t *tile_dirty = nullptr;    // two planes of [n_tiles] bytes (tile_flag_plane_bytes): touched by the free-space pass / an off-ray mark; on the list
-  ws::TileEntry *tile_list = nullptr; // [n_tiles] touched tiles of the scan in flight
+  ws::DevBuf tile_nsub;     // uint32 [n_tiles] sub-chunks (= entries) of the tile in the scan in flight (zero between scans)
+  ws::DevBuf tile_ent;      // uint32 [n_tiles][TILE_DIRECT] entries: sub-chunk id << 5 | records - 1 (never cleared: tile_nsub says how many are valid)
+  ws::DevBuf tile_dirty;    // uint8: two planes of [n_tiles] bytes (tile_flag_plane_bytes): touched by the free-space pass / an off-ray mark; on the list
+  ws::DevBuf tile_list;     // TileEntry [n_tiles] touched tiles of the scan in flight
   // candidate records of the ray tails: the pool of sub-chunks (32 x 8 bytes)
-  unsigned long long *rec = nullptr;
+  ws::DevBuf rec;           // uint64
   uint32_t sub_cap = 0;
-  unsigned long long *big_keys = nullptr; // (tile, entry number) -> entry + 1 for entries beyond TILE_DIRECT: keys, then uint32 values
+  ws::DevBuf big_keys;      // uint64: (tile, entry number) -> entry + 1 for entries beyond TILE_DIRECT: keys, then uint32 values
   uint32_t big_slots = 0;
-  uint32_t *block_stats = nullptr; // per-workgroup statistics (no shared counters in the hot kernels)
+  ws::DevBuf block_stats;   // uint32: per-workgroup statistics (no shared counters in the hot kernels)
   uint32_t tail_blocks = 0;        // workgroups of the last tail march
   uint32_t resolve_blocks = 0;     // workgroups of the last tile resolve
   bool fused_done = false;         // the last scatter already integrated into avg_map
   uint32_t scan_seq = 0;           // scatters launched on this map (ray_setup reports its record bound under this number)
   uint64_t chunk_budget_bytes = 0; // (test entry, unused since round 4's sub-chunks: the pool is always sized by estimate)
   uint32_t est_shift = 0;          // the pool's share for the records is the record bound / 32 >> (est_shift - 1) (0: the whole bound; tests shrink it to force the abort route)
-  ws::TsdfCounters *counters = nullptr;
-  ws::TsdfCounters *counters_host = nullptr; // pinned
-  uint32_t *status_host = nullptr;           // pinned + mapped: [0] sticky error bits, [4..5] record bound of the scan in flight (u64), [6] its sequence number,
+  ws::DevBuf counters;         // TsdfCounters
+  ws::HostBlock counters_host; // pinned copy of the same (ws_tsdf_stats)
+  ws::HostBlock status;                      // uint32, mapped: [0] sticky error bits, [4..5] record bound of the scan in flight (u64), [6] its sequence number,
                                              // [8] sequence number of the last scan whose marches have finished, [9] != 0: that scan was aborted (bit 0 pool exhausted, bit 1 key range),
                                              // [10] keys in the (tile, entry) hash
-  uint32_t *status_dev = nullptr;            // device view of status_host
-  uint32_t *box_stage = nullptr; // device staging for ws_map_extract_box / ws_map_insert_box
-  size_t box_stage_cap = 0;
-  uint32_t last_error_bits = 0;  // device error bits already taken from status_host, not yet shown by ws_tsdf_stats
+  ws::DevBuf box_stage;          // uint32: device staging for ws_map_extract_box / ws_map_insert_box
+  uint32_t last_error_bits = 0;  // device error bits already taken from `status`, not yet shown by ws_tsdf_stats
   // The map queries: each keeps the result of its last call and the scratch of its passes apart from the others', all of it allocated
   // on first use and grown on demand.  `mu` serialises the calls that use them (the reference's readers hold a SHARED lock).
   struct Surface // ws_map_surface (map_surface.hip)
@@ -433,10 +493,18 @@ struct ws_map
   std::mutex settle_mu;
   hipStream_t shift_stream = nullptr; // second stream for asynchronous slab transfers (map shift off the scan path)
   hipEvent_t shift_event = nullptr;
-  uint32_t *shift_stage_dev = nullptr;  // packed leaving slabs
-  uint32_t *shift_stage_host = nullptr; // pinned
-  size_t shift_stage_cap = 0;           // voxels
+  ws::DevBuf shift_stage_dev;         // uint32: packed leaving slabs
+  ws::HostBlock shift_stage_host;     // pinned; the two grow together (shift_reserve)
   ws_shift *shift_open = nullptr;       // the ticket in flight
+  // every allocation of the map (streams, events and the ticket are the caller's: map_free)
+  void release()
+  {
+    for (ws::DevBuf *b : {&data[0], &data[1], &vstate, &rays, &az_hist, &az_off, &ray_order, &ray_bin, &fan_steps, &scan_dev, &tile_nsub, &tile_ent, &tile_dirty,
+                          &tile_list, &rec, &big_keys, &block_stats, &counters, &box_stage, &shift_stage_dev})
+      b->release();
+    for (ws::HostBlock *b : {&counters_host, &status, &shift_stage_host}) b->release();
+    surf.release(), mesh.release(), ray.release(), dist.release();
+  }
 };
 
 struct ws_shift
@@ -452,26 +520,22 @@ struct ws_shift
 struct ws_reg
 {
   ws_context *ctx = nullptr;
-  int32_t *points = nullptr;
-  size_t cap = 0, n = 0;
-  int64_t *partials = nullptr; // [2][REG_BLOCKS][32]: reg_iter_kernel alternates, reg_pass_kernel uses [0]
-  ws::GnState *state = nullptr;      // [2] device, double buffered by reg_iter_kernel's launch parity
-  ws::GnState *state_host = nullptr; // pinned staging
-  ws::GnState *result_host = nullptr;     // pinned + mapped: the resident loop writes its final state here
-  ws::GnState *result_host_dev = nullptr; // device view of result_host
-  int32_t *host_flag = nullptr;      // pinned + mapped: the device sets it when the loop has finished
-  int32_t *host_flag_dev = nullptr;  // device view of host_flag
+  ws::DevBuf points; // int32 [cap][3]
+  size_t n = 0;
+  ws::DevBuf partials; // int64 [2][REG_BLOCKS][32]: reg_iter_kernel alternates, reg_pass_kernel uses [0]
+  ws::DevBuf state;                  // GnState [2], double buffered by reg_iter_kernel's launch parity
+  ws::HostBlock state_host;          // GnState, pinned staging
+  ws::HostBlock result_host;         // GnState, mapped: the resident loop writes its final state here
+  ws::HostBlock host_flag;           // int32, mapped: the device sets it when the loop has finished
   int latest = 0;                    // state buffer holding the newest state
-  int64_t *sums_dev = nullptr;       // 44
-  uint32_t *grid_bar = nullptr;      // two sets of {abort flag, counted group accumulators} of reg_loop_kernel (alternate launches)
-  uint32_t *pass_arrived = nullptr;   // arrival counter of reg_pass_kernel (zero between launches, which are ordered on the stream)
-  int64_t *iter_host = nullptr;       // pinned + mapped: the 44 sums of ws_reg_iterate, then the call's sequence number
-  int64_t *iter_host_dev = nullptr;   // device view of iter_host
+  ws::DevBuf sums_dev;               // int64 [44]
+  ws::DevBuf grid_bar;               // uint32: two sets of {abort flag, counted group accumulators} of reg_loop_kernel (alternate launches)
+  ws::DevBuf pass_arrived;            // uint32: arrival counter of reg_pass_kernel (zero between launches, which are ordered on the stream)
+  ws::HostBlock iter_host;            // int64, mapped: the 44 sums of ws_reg_iterate, then the call's sequence number
   uint32_t iter_seq = 0;
   // the resident server behind ws_reg_iterate (reg_server_kernel, registration.hip): requests travel through host-mapped memory
-  void *srv_mail = nullptr;           // ServerMail, pinned + mapped
-  void *srv_mail_dev = nullptr;       // device view
-  uint32_t *srv_ctl = nullptr;        // device words of the server (bell, pose, arrival counters), zero at creation
+  ws::HostBlock srv_mail;             // ServerMail, mapped
+  ws::DevBuf srv_ctl;                 // uint32: device words of the server (bell, pose, arrival counters), zero at creation
   std::atomic<uint32_t> srv_launch{0};   // id of the last server launched (0: none yet); it lives until ServerMail::exited says so
   std::atomic<bool> srv_stopping{false}; // somebody has asked that server to leave: the next request waits for it and starts a new one
   uint32_t srv_ids = 0;               // launch ids handed out
@@ -496,18 +560,22 @@ struct ws_reg
   int debug_stall_next = 0;          // ws_debug_reg_stall
   int resident_fallbacks = 0;        // registrations redone with one launch per iteration after a barrier timeout
   // multi-GPU resident loop (ws_reg_peer_*): the ranks' totals meet in mailboxes in each other's HBM
-  void *mailbox = nullptr;           // own mailbox: fine-grained device memory, [2][64] uint64
+  ws::DevBuf mailbox;                // own mailbox, [2][64] uint64: fine-grained device memory, which peer_own_mailbox allocates itself
   void *peer_mailbox[8] = {};        // every rank's mailbox as this process addresses it ([peer_rank] == mailbox)
   bool peer_opened[8] = {};          // opened with hipIpcOpenMemHandle (to be closed)
-  void *peer_block_dev = nullptr;    // PeerBlock
+  ws::DevBuf peer_block_dev;         // PeerBlock
   int peer_rank = 0, peer_world = 0; // 0: not connected
   int peer_blocks = 0;               // grid of the peer loop on this rank
   bool peer_dirty = false;           // an exchange failed or was given up: the mailboxes hold partial additions until ws_reg_peer_reset / reconnect
   // ws_register_cloud_batch (reg_batch_kernel): per hypothesis a start record, then a result record; grows on demand
-  void *batch_host = nullptr;        // pinned + mapped
-  void *batch_dev = nullptr;         // device view
-  size_t batch_cap = 0;              // hypotheses the block holds
+  ws::HostBlock batch;               // mapped; cap: hypotheses the block holds
   int batch_variant = 0;             // 1: reg_batch_kernel with the per-lane voxel cache (WS_REG_BATCH_VARIANT in the environment: tuning)
+  // every allocation but the peers' mailboxes, which ws_reg_peer_disconnect closes
+  void release()
+  {
+    for (ws::DevBuf *b : {&points, &partials, &state, &sums_dev, &grid_bar, &pass_arrived, &srv_ctl, &mailbox, &peer_block_dev}) b->release();
+    for (ws::HostBlock *b : {&state_host, &result_host, &host_flag, &iter_host, &srv_mail, &batch}) b->release();
+  }
 };
 
 // scan pre-processing buffers (App::preprocess on the device, scan_preprocess.hip)
@@ -516,19 +584,19 @@ struct ws_scan
   ws_context *ctx = nullptr;
   size_t cap = 0;         // points
   size_t table_slots = 0; // power of two >= 2 * cap
-  float *in_stage = nullptr;
-  size_t in_stage_floats = 0;
-  int32_t *tmp = nullptr;
-  uint32_t *slot_of = nullptr;
-  uint64_t *keys = nullptr;
-  uint32_t *first = nullptr;
-  uint32_t *wg_count = nullptr;
-  uint32_t *wg_off = nullptr;
-  uint32_t *counters = nullptr;
-  int32_t *out = nullptr;
-  uint32_t *host_count = nullptr;     // pinned + mapped
-  uint32_t *host_count_dev = nullptr;
+  ws::DevBuf in_stage;              // float: staging of a host cloud, grown on demand
+  ws::DevBuf tmp, out;              // int32 [cap][3]
+  ws::DevBuf slot_of;               // uint32 [cap]
+  ws::DevBuf keys, first;           // uint64 / uint32 [table_slots]
+  ws::DevBuf wg_count, wg_off;      // uint32 [workgroups]
+  ws::DevBuf counters;              // uint32
+  ws::HostBlock host_count;         // uint32, mapped
   size_t n_out = 0;
+  void release()
+  {
+    for (ws::DevBuf *b : {&in_stage, &tmp, &out, &slot_of, &keys, &first, &wg_count, &wg_off, &counters}) b->release();
+    host_count.release();
+  }
 };
 
 namespace ws
@@ -582,7 +650,7 @@ uint32_t reg_server_mail_exited(const void *mail);
 int launch_scan_preprocess(ws_scan *sc, const float *xyz_dev, size_t n, size_t stride, const int32_t M[16], int32_t res);
 size_t pre_table_slots(size_t max_points);
 int launch_reg_loop(ws_reg *r, const ws_map *m, int32_t res, uint32_t flags, const ws::GnCore &init, bool peers = false, size_t first = 0, size_t count = 0);
-// reg_batch_kernel: k workgroups, one Gauss-Newton loop each, from the start records in ws_reg::batch_host into its result records
+// reg_batch_kernel: k workgroups, one Gauss-Newton loop each, from the start records in ws_reg::batch into its result records
 int launch_reg_batch(ws_reg *r, const ws_map *m, int32_t res, uint32_t flags, size_t k, int32_t max_iterations, float it_weight_gradient, float epsilon);
 size_t reg_batch_record_bytes(); // start + result record of one hypothesis
 void reg_batch_write(void *records, size_t k, const float T[16]);
