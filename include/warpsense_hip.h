@@ -310,6 +310,65 @@ int ws_map_distance_download(ws_map *map, uint32_t *host, size_t capacity, size_
  * line passes of the last call (under WS_DISTANCE_COLUMNS: pass 0, the x pass, the y pass, 0) */
 int ws_debug_distance_timing(ws_map *map, int32_t enable, float ms_out[4]);
 
+/* ------------------------------------------------------------------ the global map in device memory ---- */
+/* ws_store: the device twin of HDF5GlobalMap (src/map/hdf5_global_map.cpp) -- a pool of 64^3-voxel chunks in HBM, so that a map shift
+ * is a device-to-device copy in stream order: the leaving slabs, the window move and the entering slabs with revisits and corners,
+ * without a PCIe transfer, pinned staging or a worker thread.  The host global map and its file are written from the store when the
+ * caller asks (ws_store_get_chunk per key of ws_store_keys).
+ *   chunk: 262 144 uint32, index x * 4096 + y * 64 + z (hdf5_global_map.cpp:53-57); its key is floor(world voxel / 64) per axis, for
+ *     negative coordinates too.  A chunk the store has never seen holds `fill_entry` everywhere.
+ *   directory: key -> slot lives on the HOST and slots are handed out before anything is launched: which chunks exist, and every
+ *     byte of them, is the same on every run, and a call that cannot get its chunks is refused before it changes anything.
+ *   pool: grows in segments of `segment_chunks` chunks (0: 256; rounded up to a power of two).  Growing never copies or moves a chunk,
+ *     so ws_store_chunk_dev pointers stay valid until the chunk is dropped.  max_chunks: 0 = no limit but the device's memory.
+ *   boxes: inclusive world voxels of the window of `map` under the rule of ws_map_extract_box (even sizes included; otherwise
+ *     WS_ERR_INVALID and nothing moves).
+ *   ws_store_save_box: LocalMap._area(save) on the device.  Every chunk the box overlaps exists afterwards (HDF5GlobalMap's
+ *     activate_chunk); a chunk this call creates holds fill_entry wherever the box does not cover it; an existing chunk keeps its
+ *     voxels outside the box.
+ *   ws_store_load_box: voxels of present chunks are copied into the ring, voxels of absent chunks become fill_entry, and NO chunk
+ *     is created (the bytes of ws_map_insert_box after a plain fill).  Loading into WS_MAP_NEW clears the map's "new_map is default".
+ *   ws_shift_device: HDF5LocalMap::shift (hdf5_local_map.cpp:53-118) wholly on the device -- per axis x, y, z the leaving slab is
+ *     saved, pos / offset of BOTH maps move, the entering slab is loaded.  The slabs are those of ws_shift_begin (same window, a
+ *     step of up to `size` per axis).  A pending scan is settled first.  WS_ERR_INVALID, nothing changed: a ws_shift_begin ticket is
+ *     open, new_map holds entries that have not been integrated, a step larger than the window, a store of another context.
+ *     new_pos == pos: WS_OK, nothing happens.  The parameters of both maps are committed only after every launch is enqueued.
+ *   planning before launching: the new chunks of ALL axes of a call are counted before its first launch.  If they do not fit under
+ *     max_chunks: WS_ERR_CAPACITY; if a segment cannot be allocated: WS_ERR_HIP; both maps and the store stay as they were.  Only
+ *     these planning failures (and the WS_ERR_INVALID refusals) are free of side effects: a HIP error while the launches are being
+ *     enqueued takes the chunks the call created out of the directory again and leaves the maps' parameters as they were, but
+ *     launches already enqueued still run and may have overwritten existing chunks and parts of the ring.
+ *   no waiting: save_box, load_box and the shift are stream-ordered on the context's stream and return after enqueueing.  They wait
+ *     for the device only where a segment has to be allocated (ws_store_reserve does that up front), or where a box overlaps more
+ *     than 8192 chunks (a whole 1025^3 window overlaps 4913): its slot table grows inside the call.  The slot tables of a call --
+ *     dense over the chunk range of its box, one word per chunk with a "new chunk" bit -- travel through a ring of eight pinned
+ *     tables, allocated with the store, each guarded by an event behind the launch that read it.
+ *   ws_store_get_chunk / _put_chunk synchronise.  ws_store_drop_chunk does not: the slot goes to whichever later call needs one,
+ *     whose work is ordered behind everything enqueued so far.
+ *   ws_store_keys: ascending (cx, cy, cz); copies at most `capacity` keys and always reports the count.
+ *   threads: calls on one store are serialised by a mutex inside the library; a shift is a writer on the map, as in the reference
+ *     (tsdf_mapping.cpp:114-124). */
+typedef struct ws_store ws_store;
+int ws_store_create(ws_context *ctx, uint32_t fill_entry, uint64_t max_chunks, uint32_t segment_chunks, ws_store **out);
+int ws_store_destroy(ws_store *st);
+int ws_store_reserve(ws_store *st, uint64_t chunks); /* segments for that many chunks now, so that no shift allocates */
+int ws_store_count(const ws_store *st, uint64_t *chunks, uint64_t *capacity_chunks);
+int ws_store_keys(const ws_store *st, int32_t *keys /* n x 3 */, size_t capacity, size_t *n_out);
+int ws_store_has(const ws_store *st, const int32_t key[3]); /* 1 / 0 */
+int ws_store_get_chunk(ws_store *st, const int32_t key[3], uint32_t *host /* 262144 */, int32_t *found); /* absent: found = 0, host untouched */
+int ws_store_put_chunk(ws_store *st, const int32_t key[3], const uint32_t *host); /* create or overwrite */
+int ws_store_drop_chunk(ws_store *st, const int32_t key[3]); /* absent: WS_ERR_INVALID */
+const uint32_t *ws_store_chunk_dev(const ws_store *st, const int32_t key[3]); /* device memory, 262144 words; NULL if absent */
+int ws_store_save_box(ws_store *st, ws_map *map, int which, const int32_t lo[3], const int32_t hi[3]);
+int ws_store_load_box(ws_store *st, ws_map *map, int which, const int32_t lo[3], const int32_t hi[3]);
+int ws_shift_device(ws_map *map, ws_store *st, const int32_t new_pos[3]);
+/* host only: the chunk keys an inclusive world box overlaps, ascending (cx, cy, cz); at most `capacity` are copied, the count is
+ * always reported.  hi < lo: WS_ERR_INVALID */
+int ws_store_chunks_of_box(const int32_t lo[3], const int32_t hi[3], int32_t *keys, size_t capacity, size_t *n_out);
+/* Measurement entry, as ws_debug_surface_timing: ms_out receives the device time of the save launches and of the load launches of the
+ * last save_box / load_box / shift on the store (summed over the axes of a shift) */
+int ws_debug_store_timing(ws_store *st, int32_t enable, float ms_out[2]);
+
 /* ------------------------------------------------------------------ TSDF update ---- */
 /* TSDFCuda::update_tsdf(scan_points, scanner_pos, up) — update_tsdf.cu:143-166.
  * xyz_host: n x 3 int32 (rmagine::Pointi AoS); scanner_pos in voxel units, up scaled by 32768.

@@ -15,6 +15,7 @@
 #include <cmath>
 #include <list>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <set>
 #include <stdexcept>
@@ -128,6 +129,19 @@ public:
   {
     box.resize((size_t)(hi.x - lo.x + 1) * (size_t)(hi.y - lo.y + 1) * (size_t)(hi.z - lo.z + 1));
     move_box(lo, hi, box.data(), false);
+  }
+  // a whole chunk from elsewhere (DeviceGlobalMap::flush_to): over the cached copy if the chunk is active; else straight into the
+  // file of a file-backed map (no read, no default fill, no turn of the LRU), or into the cache of a memory-only one
+  void put_chunk(const Key &c, const std::vector<TSDFEntry::RawType> &data)
+  {
+    std::lock_guard<std::recursive_mutex> g(mutex_);
+    auto it = chunks_.find(c);
+    if (it != chunks_.end())
+      it->second = data;
+    else if (file_backed())
+      write_chunk(c, data);
+    else
+      chunks_[c] = data;
   }
   void write_back() // :160-176
   {
@@ -256,6 +270,65 @@ private:
 #endif
 };
 
+// ---------------------------------------------------------------------------------------------------- DeviceGlobalMap
+// The global map in device memory (ws_store, warpsense_hip.h): 64^3 chunks in HBM, the key -> slot directory on the host.  A
+// MappingNode that has one attached shifts with device-to-device copies (shift_map_device) and writes back through it.
+class DeviceGlobalMap
+{
+public:
+  using Key = GlobalMap::Key;
+  static constexpr size_t CHUNK_WORDS = (size_t)GlobalMap::CHUNK_SIZE * GlobalMap::CHUNK_SIZE * GlobalMap::CHUNK_SIZE;
+  explicit DeviceGlobalMap(const TSDFEntry &default_entry, uint64_t max_chunks = 0, uint32_t segment_chunks = 0)
+  {
+    WS_CHECK(ws_store_create(cuda::detail::context(), default_entry.raw(), max_chunks, segment_chunks, &store_));
+  }
+  ~DeviceGlobalMap() { ws_store_destroy(store_); }
+  DeviceGlobalMap(const DeviceGlobalMap &) = delete;
+  DeviceGlobalMap &operator=(const DeviceGlobalMap &) = delete;
+  ws_store *handle() { return store_; }
+  void reserve(uint64_t chunks) { WS_CHECK(ws_store_reserve(store_, chunks)); }
+  size_t count() const
+  {
+    uint64_t n = 0;
+    WS_CHECK(ws_store_count(store_, &n, nullptr));
+    return (size_t)n;
+  }
+  std::vector<Key> keys() const // ascending (cx, cy, cz)
+  {
+    size_t n = 0;
+    WS_CHECK(ws_store_keys(store_, nullptr, 0, &n));
+    std::vector<int32_t> flat(3 * n);
+    WS_CHECK(ws_store_keys(store_, flat.data(), n, &n));
+    std::vector<Key> out(n);
+    for (size_t i = 0; i < n; ++i) out[i] = Key{flat[3 * i], flat[3 * i + 1], flat[3 * i + 2]};
+    return out;
+  }
+  bool has_chunk(const Key &c) const { return ws_store_has(store_, c.data()) != 0; }
+  bool chunk(const Key &c, std::vector<TSDFEntry::RawType> &out) // false: the store does not hold it
+  {
+    out.resize(CHUNK_WORDS);
+    int32_t found = 0;
+    WS_CHECK(ws_store_get_chunk(store_, c.data(), out.data(), &found));
+    return found != 0;
+  }
+  void put_chunk(const Key &c, const std::vector<TSDFEntry::RawType> &data)
+  {
+    if (data.size() != CHUNK_WORDS) throw std::invalid_argument("DeviceGlobalMap::put_chunk: a chunk is 64^3 entries");
+    WS_CHECK(ws_store_put_chunk(store_, c.data(), data.data()));
+  }
+  void drop_chunk(const Key &c) { WS_CHECK(ws_store_drop_chunk(store_, c.data())); }
+  // every chunk merged into the host global map (and through it into its file)
+  void flush_to(GlobalMap &g)
+  {
+    std::vector<TSDFEntry::RawType> data;
+    for (const Key &c : keys())
+      if (chunk(c, data)) g.put_chunk(c, data);
+  }
+
+private:
+  ws_store *store_ = nullptr;
+};
+
 // ---------------------------------------------------------------------------------------------------- LocalMap
 // The in-memory state of HDF5LocalMap (hdf5_local_map.cpp:5-20): odd sizes, offset = size / 2, default-filled.
 class LocalMap
@@ -300,6 +373,26 @@ public:
   {
   }
   cuda::TSDFRegistration &gpu() { return gpu_; }
+  // the global map in device memory: shift_map_device and write_back go through it from now on (nullptr: detach)
+  void attach(DeviceGlobalMap *device_global_map) { device_global_map_ = device_global_map; }
+
+  // The shift with the global map in device memory (ws_shift_device): per axis the leaving slab goes into the store's chunks,
+  // pos / offset of both maps move, the entering slab comes out of them -- revisits and corners included -- in stream order.
+  // No transfer, no staging, no worker; returns after enqueueing.
+  void shift_map_device(const rm::Pointi &new_pos)
+  {
+    if (!device_global_map_) throw std::logic_error("shift_map_device: no DeviceGlobalMap attached");
+    wait_shift();
+    WS_CHECK(ws_shift_device(gpu_.tsdf().handle(), device_global_map_->handle(), &new_pos.x));
+    rm::Pointi &size = local_map_.get_size(), &pos = local_map_.get_pos(), &off = local_map_.get_offset();
+    int *sz = &size.x, *ps = &pos.x, *of = &off.x;
+    const int np[3] = {new_pos.x, new_pos.y, new_pos.z};
+    for (int axis = 0; axis < 3; ++axis)
+    {
+      of[axis] = (int)((((int64_t)of[axis] + np[axis] - ps[axis]) % sz[axis] + sz[axis]) % sz[axis]);
+      ps[axis] = np[axis];
+    }
+  }
 
   // TSDFMapping::map_shift body (tsdf_mapping.cpp:109-126) == HDF5LocalMap::shift (hdf5_local_map.cpp:53-118) per axis:
   // save the slab that leaves, move pos/offset, load the slab that enters -- each slab packed / unpacked by the GPU.
@@ -496,13 +589,25 @@ public:
   }
 
   // HDF5LocalMap::write_back + HDF5GlobalMap::write_back (hdf5_local_map.cpp:210-217, app.cpp:215-221) from the device map
-  void write_back()
+  // box_lo / box_hi (inclusive world voxels, either may be null) restrict the export to a part of the window
+  void write_back(const rm::Pointi *box_lo = nullptr, const rm::Pointi *box_hi = nullptr)
   {
     wait_shift();
     auto &avg = gpu_.tsdf().avg_map();
     const rm::Pointi &size = local_map_.get_size(), &pos = local_map_.get_pos();
     const int cs = GlobalMap::CHUNK_SIZE;
-    const rm::Pointi lo(pos.x - size.x / 2, pos.y - size.y / 2, pos.z - size.z / 2), hi(pos.x + size.x / 2, pos.y + size.y / 2, pos.z + size.z / 2);
+    rm::Pointi lo(pos.x - size.x / 2, pos.y - size.y / 2, pos.z - size.z / 2), hi(pos.x + size.x / 2, pos.y + size.y / 2, pos.z + size.z / 2);
+    if (box_lo) lo = rm::Pointi(std::max(lo.x, box_lo->x), std::max(lo.y, box_lo->y), std::max(lo.z, box_lo->z));
+    if (box_hi) hi = rm::Pointi(std::min(hi.x, box_hi->x), std::min(hi.y, box_hi->y), std::min(hi.z, box_hi->z));
+    if (lo.x > hi.x || lo.y > hi.y || lo.z > hi.z) return; // the box misses the window
+    if (device_global_map_)
+    {
+      // the window into the device chunks in one launch, the chunks into the host map, the host map into its file
+      WS_CHECK(ws_store_save_box(device_global_map_->handle(), gpu_.tsdf().handle(), WS_MAP_AVG, &lo.x, &hi.x));
+      device_global_map_->flush_to(local_map_.global_map());
+      local_map_.global_map().write_back();
+      return;
+    }
     std::vector<TSDFEntry> slab;
     for (int cx = floor_div(lo.x, cs); cx <= floor_div(hi.x, cs); ++cx)
     {
@@ -522,6 +627,7 @@ private:
   LocalMap &local_map_;
   cuda::DeviceMap view_;
   cuda::TSDFRegistration gpu_;
+  DeviceGlobalMap *device_global_map_ = nullptr;
   std::thread shift_worker_;
   std::string shift_error_; // written by the worker, read after join()
 };
@@ -535,6 +641,7 @@ struct AppParams
   int map_size[3] = {513, 513, 513}; // voxels
   int initial_weight = 0;
   bool async_shift = false; // MappingNode::shift_map_async: the map shift off the scan path
+  bool device_shift = false; // MappingNode::shift_map_device: the global map in device memory (takes precedence over async_shift)
 };
 
 // wall-clock microseconds of the stages of one cloud_callback -- the reference's RuntimeEvaluator forms "preprocess", "tsdf",
@@ -554,7 +661,12 @@ public:
     pose_.setIdentity();
     last_tsdf_pose_.setIdentity();
     last_shift_pose_.setIdentity();
-    if (p.async_shift) node_.reserve_shift((int)std::ceil(p.shift * 1000.f / (float)p.hot.map_resolution));
+    if (p.device_shift)
+    {
+      device_global_map_.reset(new DeviceGlobalMap(global_map_.get_default_tsdf_entry()));
+      node_.attach(device_global_map_.get());
+    }
+    else if (p.async_shift) node_.reserve_shift((int)std::ceil(p.shift * 1000.f / (float)p.hot.map_resolution));
     if (global_map_.has_file()) global_map_.write_meta(p.hot.tau, local_map_.get_size(), p.max_distance, p.hot.map_resolution, p.hot.max_weight);
   }
 
@@ -624,7 +736,9 @@ public:
       const int res = params_.hot.map_resolution;
       const rm::Pointi target((int)std::floor(pose_.at(0, 3) / (float)res), (int)std::floor(pose_.at(1, 3) / (float)res),
                               (int)std::floor(pose_.at(2, 3) / (float)res)); // to_map, util/util.h:52-56
-      if (params_.async_shift)
+      if (params_.device_shift)
+        node_.shift_map_device(target);
+      else if (params_.async_shift)
         node_.shift_map_async(target);
       else
         node_.shift_map(target);
@@ -664,6 +778,7 @@ private:
   GlobalMap global_map_;
   LocalMap local_map_;
   MappingNode node_;
+  std::unique_ptr<DeviceGlobalMap> device_global_map_; // AppParams::device_shift
   cuda::ScanPreprocessor pre_;
   rm::Matrix4x4f pose_, last_tsdf_pose_, last_shift_pose_;
   bool initialized_ = false, shifted_ = false;

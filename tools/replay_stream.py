@@ -2,7 +2,7 @@
 sliding TSDF map @ 5 cm, one MI355X): sensor clouds in float metres -> device pre-processing -> TSDF update
 (when the sensor moved > 0.3 m) -> Point-to-TSDF registration -> pose -> map shift (device-side slabs).
 
-    python tools/replay_stream.py --map 1024 --scans 30 [--h5 /tmp/stream.h5] [--surface-ply DIR [--surface-every N]] [--mesh-ply DIR]
+    python tools/replay_stream.py --map 1024 --scans 30 [--h5 /tmp/stream.h5] [--async-shift | --device-global-map] [--surface-ply DIR [--surface-every N]] [--mesh-ply DIR]
                                    [--raycast-ply DIR] [--distance-npy DIR [--distance-m M]]
 
 Prints one JSON line: scans/s over the stream and the mean per-stage times (the reference's RuntimeEvaluator
@@ -59,6 +59,8 @@ def main():
                     "(0 = back to back; the sensor of configs[2] delivers 10 Hz, and the slab filing of an asynchronous shift "
                     "has the time between two shifts of a paced stream to finish)")
     ap.add_argument("--async-shift", action="store_true", help="map shift off the scan path (TSDFMapping.shift_map_async)")
+    ap.add_argument("--device-global-map", action="store_true", help="the global map in device memory (DeviceGlobalMap): shifts are device-to-device "
+                    "copies (TSDFMapping.shift_map_device), the host map and its file are written from the chunks at the end")
     ap.add_argument("--surface-ply", default=None, metavar="DIR", help="write the marker cloud of the window (publish_local_map, selected on the "
                     "device: TSDFMapping.surface_cloud) as binary little-endian PLY (xyz + rgb) into DIR")
     ap.add_argument("--mesh-ply", default=None, metavar="DIR", help="write a triangle mesh of the window (surface nets on the device: "
@@ -85,7 +87,7 @@ def main():
     params = W.Params(W.MapParams(resolution=args.res, max_distance=1.0, max_weight=10, size=(size_m, size_m, size_m), shift=args.shift),
                       W.RegistrationParams(200, 0.1, 0.03))
     t0 = time.perf_counter()
-    app = W.App(params, args.h5, async_shift=args.async_shift)
+    app = W.App(params, args.h5, async_shift=args.async_shift, shift="device" if args.device_global_map else None)
     t_setup = time.perf_counter() - t0
     he = tuple(1000.0 * r for r in args.room)
     clouds = []
@@ -162,7 +164,7 @@ def main():
     print(json.dumps({"workload": f"{args.scans} synthetic OS1-128 scans (131072 pts), {args.map}^3 sliding map @ {args.res} mm, App replay",
                       "args": {"step_m": args.step, "shift_m": args.shift, "room_m": list(args.room), "h5": bool(args.h5), "hz": args.hz},
                       "scans_per_s": args.scans / (t2 - t1), "stream_s": t2 - t1, "callback_busy_s": busy, "setup_s": t_setup, **stages,
-                      "tsdf_updates": app.n_updates, "map_shifts": app.n_shifts, "async_shift": bool(args.async_shift),
+                      "tsdf_updates": app.n_updates, "map_shifts": app.n_shifts, "async_shift": bool(args.async_shift), "device_global_map": bool(args.device_global_map),
                       "slowest_scan_ms": 1000.0 * float(max(t["total"] for t in app.timings[2:])),
                       "scans_over_100ms": int(sum(1 for t in app.timings[2:] if t["total"] > 0.1)),
                       "points_after_preprocess": float(np.mean([t["points"] for t in app.timings])),

@@ -3,7 +3,7 @@
 The compute lives in libwarpsense_hip.so (warpsense_amd/csrc, C ABI in include/warpsense_hip.h);
 this package is the thin host-side mirror of the reference's device API plus the synthetic workload.
 """
-from .api import (Context, DeviceMap, DeviceMapMemWrapper, DevicePoints, GlobalMap, LocalMap, MapParams, Params, RegistrationCuda,  # noqa: F401
+from .api import (Context, DeviceGlobalMap, chunks_of_box, DeviceMap, DeviceMapMemWrapper, DevicePoints, GlobalMap, LocalMap, MapParams, Params, RegistrationCuda,  # noqa: F401
                   RegistrationParams, ScanPreprocessor, TSDFCuda, TSDFMapping, TSDFRegistration, cleanup, pack_entry, pause, pose_to_values, to_int_mat,
                   to_map, unpack_entry, SURFACE_RECORD, write_surface_ply, VERT, write_mesh_ply, RAY, write_raycast_ply, distance_class, distance_d2, distance_mm, batch_best, candidate_poses)
 from ._lib import (WS_INTEGRATE_DENSE, WS_INTEGRATE_SPARSE, WS_INTEGRATE_SPARSE_SEPARATE, WS_MAP_AVG, WS_MAP_NEW, WS_REG_ALL_POINTS,  # noqa: F401

@@ -34,6 +34,8 @@ EXPORTS = [
     "ws_map_raycast", "ws_map_raycast_dev", "ws_map_raycast_records_dev", "ws_map_raycast_gradient_dev", "ws_map_raycast_download", "ws_debug_raycast_timing",
     "ws_map_distance", "ws_map_distance_dev", "ws_map_distance_download", "ws_debug_distance_timing",
     "ws_register_cloud_batch", "ws_reg_batch_best",
+    "ws_store_create", "ws_store_destroy", "ws_store_reserve", "ws_store_count", "ws_store_keys", "ws_store_has", "ws_store_get_chunk", "ws_store_put_chunk",
+    "ws_store_drop_chunk", "ws_store_chunk_dev", "ws_store_save_box", "ws_store_load_box", "ws_shift_device", "ws_store_chunks_of_box", "ws_debug_store_timing",
 ]
 WS_SURFACE_RECORDS, WS_SURFACE_MARKER = 0, 1
 WS_MESH_DEFAULT, WS_MESH_ANY_WEIGHT = 0, 1
@@ -210,6 +212,22 @@ def load() -> C.CDLL:
     L.ws_register_cloud_peers.argtypes = [vp, vp, sz, sz, vp, i32, C.c_float, C.c_float, i32, u32, vp, P(i32)]
     L.ws_register_cloud_batch.argtypes = [vp, vp, vp, sz, i32, C.c_float, C.c_float, i32, u32, vp, vp, vp, vp]
     L.ws_reg_batch_best.argtypes = [vp, vp, sz, i32, P(i64)]
+    L.ws_store_create.argtypes = [vp, u32, C.c_uint64, u32, P(vp)]
+    L.ws_store_destroy.argtypes = [vp]
+    L.ws_store_reserve.argtypes = [vp, C.c_uint64]
+    L.ws_store_count.argtypes = [vp, P(C.c_uint64), P(C.c_uint64)]
+    L.ws_store_keys.argtypes = [vp, vp, sz, P(sz)]
+    L.ws_store_has.argtypes = [vp, vp]
+    L.ws_store_get_chunk.argtypes = [vp, vp, vp, P(i32)]
+    L.ws_store_put_chunk.argtypes = [vp, vp, vp]
+    L.ws_store_drop_chunk.argtypes = [vp, vp]
+    L.ws_store_chunk_dev.argtypes = [vp, vp]
+    L.ws_store_chunk_dev.restype = vp
+    L.ws_store_save_box.argtypes = [vp, vp, C.c_int, vp, vp]
+    L.ws_store_load_box.argtypes = [vp, vp, C.c_int, vp, vp]
+    L.ws_shift_device.argtypes = [vp, vp, vp]
+    L.ws_store_chunks_of_box.argtypes = [vp, vp, vp, sz, P(sz)]
+    L.ws_debug_store_timing.argtypes = [vp, i32, vp]
     L.ws_prof_enable.argtypes = [vp, u32]
     L.ws_prof_read.argtypes = [vp, C.c_int, P(C.c_double), P(i64)]
     L.ws_prof_reset.argtypes = [vp]

@@ -482,6 +482,121 @@ class GlobalMap:
         return buf
 
 
+class DeviceGlobalMap:
+    """The global map in device memory (ws_store, include/warpsense_hip.h): the device twin of GlobalMap.  64^3-voxel chunks of raw
+    uint32 entries in HBM, index x*4096 + y*64 + z, keyed by floor(world voxel / 64); chunks never seen hold the default entry.  The
+    key -> slot directory is the host's.  TSDFMapping(..., device_global_map=this).shift_map_device saves the leaving slabs into
+    it and loads the entering ones from it in stream order; flush_to() merges it into a host GlobalMap (and its .h5 file)."""
+
+    CHUNK_SIZE = 64
+    CHUNK_WORDS = 64 ** 3
+
+    def __init__(self, default_value, default_weight=0, max_chunks: int = 0, segment_chunks: int = 0, ctx: Context | None = None):
+        self.ctx = ctx or Context.default()
+        self._L = self.ctx._L
+        self.default_raw = int(pack_entry(default_value, default_weight))
+        h = C.c_void_p()
+        check(self._L.ws_store_create(self.ctx.handle, self.default_raw, int(max_chunks), int(segment_chunks), C.byref(h)), "ws_store_create")
+        self.handle = h
+
+    def count(self) -> int:
+        n = C.c_uint64(0)
+        check(self._L.ws_store_count(self.handle, C.byref(n), None), "ws_store_count")
+        return int(n.value)
+
+    def capacity(self) -> int:
+        n = C.c_uint64(0)
+        check(self._L.ws_store_count(self.handle, None, C.byref(n)), "ws_store_count")
+        return int(n.value)
+
+    def reserve(self, n: int):
+        """segments for n chunks now, so that no shift has to allocate (and wait for the device)"""
+        check(self._L.ws_store_reserve(self.handle, int(n)), "ws_store_reserve")
+
+    def keys(self) -> list:
+        """the chunk keys, ascending (cx, cy, cz)"""
+        n = C.c_size_t(0)
+        check(self._L.ws_store_keys(self.handle, None, 0, C.byref(n)), "ws_store_keys")
+        keys = np.zeros((n.value, 3), dtype=np.int32)
+        check(self._L.ws_store_keys(self.handle, _ptr(keys), n.value, C.byref(n)), "ws_store_keys")
+        return [tuple(int(v) for v in k) for k in keys[:n.value]]
+
+    def has_chunk(self, cx, cy, cz) -> bool:
+        return bool(self._L.ws_store_has(self.handle, _i3c((cx, cy, cz))))
+
+    def chunk(self, key):
+        """a host copy of one chunk (262 144 uint32), None if the store does not hold it"""
+        out = np.empty(self.CHUNK_WORDS, dtype=np.uint32)
+        found = C.c_int32(0)
+        check(self._L.ws_store_get_chunk(self.handle, _i3c(tuple(key)), _ptr(out), C.byref(found)), "ws_store_get_chunk")
+        return out if found.value else None
+
+    def put_chunk(self, key, data):
+        data = np.ascontiguousarray(data, dtype=np.uint32).reshape(-1)
+        assert data.size == self.CHUNK_WORDS
+        check(self._L.ws_store_put_chunk(self.handle, _i3c(tuple(key)), _ptr(data)), "ws_store_put_chunk")
+
+    def drop_chunk(self, key):
+        check(self._L.ws_store_drop_chunk(self.handle, _i3c(tuple(key))), "ws_store_drop_chunk")
+
+    def save_box(self, tsdf: "TSDFCuda", lo, hi, which: int = WS_MAP_AVG):
+        """the box [lo, hi] of the window of `tsdf` into the chunks (ws_store_save_box; stream-ordered, no wait)"""
+        check(self._L.ws_store_save_box(self.handle, tsdf.handle, int(which), _ptr(_i3(lo)), _ptr(_i3(hi))), "ws_store_save_box")
+
+    def load_box(self, tsdf: "TSDFCuda", lo, hi, which: int = WS_MAP_AVG):
+        """the chunks into the box [lo, hi] of the window of `tsdf`, the default entry where there is no chunk (ws_store_load_box)"""
+        check(self._L.ws_store_load_box(self.handle, tsdf.handle, int(which), _ptr(_i3(lo)), _ptr(_i3(hi))), "ws_store_load_box")
+
+    def timing(self, enable: int = -1):
+        """device milliseconds of the save and of the load launches of the last call (ws_debug_store_timing)"""
+        ms = (C.c_float * 2)()
+        check(self._L.ws_debug_store_timing(self.handle, int(enable), ms), "ws_debug_store_timing")
+        return float(ms[0]), float(ms[1])
+
+    def flush_to(self, global_map: GlobalMap):
+        """every chunk merged into a host GlobalMap: into its chunk cache (activate_chunk), or, for a map with a file, straight
+        into the file (GlobalMap._write_chunk) unless the chunk is active in the cache"""
+        for key in self.keys():
+            data = self.chunk(key)
+            with global_map.lock:
+                if global_map._file is not None and key not in global_map.chunks:
+                    global_map._write_chunk(key, data)
+                else:
+                    global_map.activate_chunk(*key)[:] = data
+
+    def load_from(self, global_map: GlobalMap, keys=None):
+        """chunks of a host GlobalMap (None: all it holds, in memory and in its file) into the store, to continue a saved map"""
+        if keys is None:
+            keys = set(global_map.chunks) | (set(global_map._in_file) if global_map._file is not None else set())
+        for key in sorted(tuple(int(v) for v in k) for k in keys):
+            if not global_map.has_chunk(*key):
+                continue
+            with global_map.lock:
+                self.put_chunk(key, global_map.activate_chunk(*key))
+
+    def close(self):
+        if self.handle:
+            self._L.ws_store_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def chunks_of_box(lo, hi) -> np.ndarray:
+    """host only: the (n, 3) chunk keys an inclusive world-voxel box overlaps, ascending (ws_store_chunks_of_box)"""
+    L = _lib.load()
+    n = C.c_size_t(0)
+    lo, hi = _i3(lo), _i3(hi)
+    check(L.ws_store_chunks_of_box(_ptr(lo), _ptr(hi), None, 0, C.byref(n)), "ws_store_chunks_of_box")
+    keys = np.zeros((n.value, 3), dtype=np.int32)
+    check(L.ws_store_chunks_of_box(_ptr(lo), _ptr(hi), _ptr(keys), n.value, C.byref(n)), "ws_store_chunks_of_box")
+    return keys
+
+
 class LocalMap:
     """HDF5LocalMap without the file (src/map/hdf5_local_map.cpp): a 3-D ring buffer of TSDF entries around `pos`.
     Sizes are forced odd, offset = size/2, every voxel starts as the global map's default entry (:5-20);
@@ -1084,12 +1199,14 @@ class Params:
 class TSDFMapping:
     """cuda::TSDFMapping without ROS (the protected constructor path, tsdf_mapping.cpp:30-41)."""
 
-    def __init__(self, params: Params, local_map: LocalMap, ctx: Context | None = None):
+    def __init__(self, params: Params, local_map: LocalMap, ctx: Context | None = None, device_global_map: "DeviceGlobalMap | None" = None):
         self.params_ = params
         self.local_map_ = local_map
         self.cuda_map_ = local_map.device_map()
         self.tsdf_ = TSDFCuda(self.cuda_map_, params.map.tau, params.map.max_weight, params.map.resolution, ctx)
         self.mutex_ = threading.RLock()  # the reference's shared_mutex: one writer or many readers
+        # the global map in device memory: shift_map_device and write_back go through it (shift_map / shift_map_async do not)
+        self.device_global_map_ = device_global_map
 
     def convert_pose_to_gpu(self, pose):
         """tsdf_mapping.cpp:77-85: pos = floor(t/res) voxels, up = (R_int * (0,0,MR)) / MR."""
@@ -1299,6 +1416,22 @@ class TSDFMapping:
                         sa, sb = np.maximum(a, base), np.minimum(b, base + cs - 1)
                         avg.insert_box(sa, sb, lm.map_.load_box(sa, sb))
 
+    def shift_map_device(self, new_pos):
+        """TSDFMapping::map_shift with the global map in device memory (ws_shift_device): per axis the leaving slab goes into
+        the chunks of device_global_map, pos / offset of both maps move, and the entering slab comes out of them -- revisited
+        space and corners included -- as device-to-device copies in stream order.  Nothing is transferred, staged or filed on the
+        host; the call returns after enqueueing.  The host LocalMap follows pos / offset."""
+        if self.device_global_map_ is None:
+            raise WsError("shift_map_device: this TSDFMapping has no device_global_map")
+        self.wait_shift()
+        lm = self.local_map_
+        new_pos = _i3(new_pos)
+        with self.mutex_:
+            check(self.tsdf_._L.ws_shift_device(self.tsdf_.handle, self.device_global_map_.handle, _ptr(new_pos)), "ws_shift_device")
+            d = new_pos.astype(np.int64) - lm.pos
+            lm.pos[:] = new_pos
+            lm.offset[:] = (lm.offset + d + lm.size) % lm.size
+
     def reserve_shift(self, shift_voxels: int):
         """staging for asynchronous shifts of up to `shift_voxels` per axis (plus slack), allocated now instead of inside
         the first shift (a pinned allocation of that size takes tens of milliseconds)"""
@@ -1321,7 +1454,9 @@ class TSDFMapping:
         DEVICE map: every 64^3 chunk the window overlaps is gathered out of the ring buffer by the GPU
         (ws_map_extract_box: chunk layout, x major / z fastest), merged into the global map's chunk and written to
         its file.  The reference downloads the whole window and copies voxel by voxel on the host.
-        box_lo / box_hi (inclusive world voxels) restrict the export to a part of the window."""
+        box_lo / box_hi (inclusive world voxels) restrict the export to a part of the window.
+        With a device_global_map: ws_store_save_box of the (clipped) window, DeviceGlobalMap.flush_to the host global map, its
+        write_back -- the same chunks and the same file."""
         self.wait_shift()
         lm, avg = self.local_map_, self.tsdf_.avg_map()
         cs = GlobalMap.CHUNK_SIZE
@@ -1332,6 +1467,12 @@ class TSDFMapping:
                 lo = np.maximum(lo, np.asarray(box_lo, dtype=np.int64))
             if box_hi is not None:
                 hi = np.minimum(hi, np.asarray(box_hi, dtype=np.int64))
+            if self.device_global_map_ is not None:
+                # the window goes into the device chunks in one launch, and the chunks into the host map and its file
+                self.device_global_map_.save_box(self.tsdf_, lo, hi)
+                self.device_global_map_.flush_to(lm.map_)
+                lm.map_.write_back()
+                return
             # one gather per 64-voxel-thick x slab of chunks (a few large device->host copies instead of one small one
             # per chunk); save_box cuts the slab into its chunks
             for cx in range(int(np.floor_divide(lo[0], cs)), int(np.floor_divide(hi[0], cs)) + 1):
@@ -1344,8 +1485,9 @@ class TSDFMapping:
 class TSDFRegistration(TSDFMapping):
     """cuda::TSDFRegistration (tsdf_registration.cpp:22-96)."""
 
-    def __init__(self, params: Params, local_map: LocalMap, ctx: Context | None = None, flags: int = WS_REG_ALL_POINTS):
-        super().__init__(params, local_map, ctx)
+    def __init__(self, params: Params, local_map: LocalMap, ctx: Context | None = None, flags: int = WS_REG_ALL_POINTS,
+                 device_global_map: "DeviceGlobalMap | None" = None):
+        super().__init__(params, local_map, ctx, device_global_map)
         self.reg_ = RegistrationCuda(self.cuda_map_, ctx, flags)
         self.last_iterations = 0
 

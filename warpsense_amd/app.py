@@ -17,20 +17,27 @@ import time
 
 import numpy as np
 
-from .api import (GlobalMap, LocalMap, Params, ScanPreprocessor, TSDFRegistration, to_map)
+from .api import (DeviceGlobalMap, GlobalMap, LocalMap, Params, ScanPreprocessor, TSDFRegistration, to_map)
 
 
 class App:
-    def __init__(self, params: Params, filename: str | None = None, ctx=None, max_points: int = 128 * 1024, async_shift: bool = False):
+    def __init__(self, params: Params, filename: str | None = None, ctx=None, max_points: int = 128 * 1024, async_shift: bool = False, shift: str | None = None):
+        # shift: "sync" (TSDFMapping.shift_map), "async" (shift_map_async, what async_shift=True selects) or "device": the global map
+        # lives in device memory (DeviceGlobalMap), shifts are device-to-device copies (shift_map_device) and terminate() writes the
+        # host global map and its file from the chunks
         # async_shift: TSDFMapping.shift_map_async — the window moves on the device inside the scan that triggers it and
         # the leaving slabs are filed into the global map by a worker thread (same maps and poses as the synchronous route)
-        self.async_shift_ = bool(async_shift)
+        if shift not in (None, "sync", "async", "device"):
+            raise ValueError(f"App: shift must be 'sync', 'async' or 'device', not {shift!r}")
+        self.async_shift_ = bool(async_shift) if shift is None else shift == "async"
+        self.device_shift_ = shift == "device"
         m = params.map
         self.params_ = params
         # app.cpp:33-41: global map (file), local map around the origin, the GPU mapping/registration object
         self.hdf5_global_map_ = GlobalMap(m.tau, m.initial_weight, filename=filename, map_params=m if filename else None)
         self.hdf5_local_map_ = LocalMap(m.size[0], m.size[1], m.size[2], m.tau, m.initial_weight, self.hdf5_global_map_)
-        self.gpu_ = TSDFRegistration(params, self.hdf5_local_map_, ctx)
+        self.device_global_map_ = DeviceGlobalMap(m.tau, m.initial_weight, ctx=ctx) if self.device_shift_ else None
+        self.gpu_ = TSDFRegistration(params, self.hdf5_local_map_, ctx, device_global_map=self.device_global_map_)
         self.pre_ = ScanPreprocessor(max_points, ctx)
         if self.async_shift_:
             self.gpu_.reserve_shift(int(np.ceil(m.shift * 1000.0 / m.resolution)))
@@ -67,7 +74,9 @@ class App:
         d = np.linalg.norm(self.last_shift_pose_[:3, 3] / np.float32(1000) - self.pose_[:3, 3] / np.float32(1000))
         if d >= self.params_.map.shift:
             self.last_shift_pose_ = self.pose_.copy()
-            if self.async_shift_:
+            if self.device_shift_:
+                self.gpu_.shift_map_device(to_map(self.pose_, self.params_.map.resolution))
+            elif self.async_shift_:
                 self.gpu_.shift_map_async(to_map(self.pose_, self.params_.map.resolution))
             else:
                 self.gpu_.shift_map(to_map(self.pose_, self.params_.map.resolution))

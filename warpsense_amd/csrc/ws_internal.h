@@ -3,12 +3,15 @@
 
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <atomic>
 #include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <map>
 #include <mutex>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -578,6 +581,63 @@ struct ws_reg
   }
 };
 
+// The chunk store (ws_store_*, map_store.hip): the global map in device memory.  64^3-voxel chunks, index x*4096 + y*64 + z like
+// HDF5GlobalMap's (hdf5_global_map.cpp:53-57), in a pool that grows by segments; a chunk never moves.  The DIRECTORY (key -> slot)
+// is the host's: slots are handed out before anything is launched, so which chunks exist never depends on what a kernel finds.
+namespace ws
+{
+constexpr int32_t STORE_CS = 64, STORE_CHUNK_WORDS = STORE_CS * STORE_CS * STORE_CS;
+constexpr uint32_t STORE_NEW = 0x80000000u;    // slot table of a save: the chunk was created by this call (the kernel writes all of it)
+constexpr uint32_t STORE_ABSENT = 0xffffffffu; // slot table of a load: the store has no such chunk (the kernel writes fill_entry)
+constexpr int STORE_TABLES = 8;                // per-call slot tables in flight: a shift enqueues up to six launches
+constexpr size_t STORE_TABLE_WORDS = 8192;     // chunks a table holds from the start (a whole 1025^3 window overlaps 17^3 = 4913)
+} // namespace ws
+
+struct ws_store
+{
+  ws_context *ctx = nullptr;
+  uint32_t fill = 0;
+  uint64_t max_chunks = 0;  // 0: no limit
+  uint32_t seg_shift = 0;   // a segment holds 1 << seg_shift chunks
+  std::mutex mu;            // every call on the store
+  struct Entry
+  {
+    uint32_t slot;
+    bool written; // false only inside the call that created the chunk, until its first save launch (which writes it whole) is enqueued
+  };
+  std::map<std::array<int32_t, 3>, Entry> dir;    // chunk key -> slot, ascending (cx, cy, cz)
+  std::vector<uint32_t> free_slots;               // of dropped chunks, reused first
+  uint32_t next_slot = 0;                         // slots ever handed out from the segments
+  std::vector<ws::DevBuf> segs;                   // uint32 [STORE_CHUNK_WORDS << seg_shift] each
+  std::vector<uint32_t *> seg_ptr;                // their base pointers ...
+  ws::DevBuf seg_tab;                             // ... and the copy the kernels read (rewritten when a segment is added, which waits for the stream)
+  // slot tables of the calls in flight: filled in pinned memory, copied in stream order, reused once the event behind the launch
+  // that read them has passed
+  struct Table
+  {
+    ws::HostBlock host;
+    ws::DevBuf dev;
+    hipEvent_t done = nullptr;
+    bool used = false;
+  } tab[ws::STORE_TABLES];
+  int tab_next = 0;
+  ws::QueryTimer timer[3]; // per axis of a shift: 0 save 1 load 2 (ws_store_save_box / _load_box use the first)
+  void release()
+  {
+    for (ws::DevBuf &b : segs) b.release();
+    segs.clear(), seg_ptr.clear();
+    seg_tab.release();
+    for (Table &t : tab)
+    {
+      t.host.release(), t.dev.release();
+      if (t.done) (void)hipEventDestroy(t.done);
+      t.done = nullptr;
+      t.used = false;
+    }
+    for (ws::QueryTimer &t : timer) t.release();
+  }
+};
+
 // scan pre-processing buffers (App::preprocess on the device, scan_preprocess.hip)
 struct ws_scan
 {
@@ -632,6 +692,11 @@ int launch_distance(ws_map *m, int which, const int32_t lo[3], const int32_t ext
 int fill_u32(ws_context *ctx, uint32_t *dst, uint32_t value, int64_t n);
 int launch_box_fill(ws_map *m, const ws::MapParams &par, int which, const int32_t lo[3], const int32_t ext[3], uint32_t value, hipStream_t stream);
 int check_all_equal_host(const uint32_t *data, int64_t n, uint32_t value);
+// map_store.hip: the inclusive world box [lo, hi] of map `which` (window parameters `par`) -> the chunks of the store (save) or back
+// (load).  c0 / nc: first key and count per axis of the chunks the box overlaps; table_dev: one slot word per such chunk, x major;
+// any_new: the table of a save holds a chunk flagged STORE_NEW
+int launch_store_copy(ws_store *st, ws_map *m, const ws::MapParams &par, int which, const int32_t lo[3], const int32_t hi[3], const int32_t c0[3],
+                      const int32_t nc[3], const uint32_t *table_dev, bool save, bool any_new, hipStream_t stream);
 
 int launch_reg_iteration(ws_reg *r, const ws_map *m, int32_t res, uint32_t flags, int32_t k);
 // reg_pass_kernel over points [first, first + count): from the newest state (first the update from `sums` if `apply`) into `sums`;
