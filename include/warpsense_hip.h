@@ -125,18 +125,32 @@ int ws_map_download(ws_map *map, int which, int32_t size[3], int32_t pos[3], int
  * WS_ERR_INVALID, nothing is moved): no box addresses a ring cell twice.  ws_map_surface, _mesh, _distance use the same rule. */
 int ws_map_extract_box(ws_map *map, int which, const int32_t lo[3], const int32_t hi[3], uint32_t *host_out);
 int ws_map_insert_box(ws_map *map, int which, const int32_t lo[3], const int32_t hi[3], const uint32_t *host_in);
+/* The geometry of a map shift, for every route (the box calls above, ws_shift_begin, ws_shift_device).  Host only: no map, no
+ * context, no GPU.  Per axis that moves (x, y, z, like HDF5LocalMap::shift, hdf5_local_map.cpp:53-118), with the window as it is
+ * when that axis moves: the box that leaves -- the voxels of the window before the axis step that the window after it no longer
+ * holds -- and the box that enters.  The window is the one above (pos - size/2 .. pos - size/2 + size - 1, also for an even
+ * size), so no slab is wider than `size` along an axis.  pos / offset: the window's parameters after the last step.
+ * A step of up to `size` voxels per axis is accepted, a larger one refused (WS_ERR_INVALID, as is a NULL argument);
+ * new_pos == pos gives n = 0. */
+typedef struct
+{
+  int32_t n;                                /* steps: 0 .. 3 */
+  int32_t axis[3], d[3];                    /* of step i: the axis that moves and by how much */
+  int32_t leave_lo[3][3], leave_hi[3][3];   /* world boxes that leave (coordinates of the window before that axis moved) */
+  int32_t enter_lo[3][3], enter_hi[3][3];   /* world boxes that enter */
+  int32_t pos[3], offset[3];                /* of the window after the shift */
+} ws_shift_plan_t;
+int ws_shift_plan(const int32_t size[3], const int32_t pos[3], const int32_t offset[3], const int32_t new_pos[3], ws_shift_plan_t *out);
 /* The same shift OFF the scan path (in the reference TSDFMapping::map_shift runs on its own thread and only blocks the
  * scans while it swaps the maps, tsdf_mapping.cpp:97-136).  ws_shift_begin is stream-ordered on the map's stream and
- * returns without waiting: per axis (x, y, z, like HDF5LocalMap::shift) the slab of avg_map that leaves the window is
+ * returns without waiting: per step of ws_shift_plan the slab of avg_map that leaves the window is
  * packed into a device staging buffer, pos/offset of BOTH device maps move, and the slab that enters is filled with
  * `fill_entry` (the global map's default entry).  The staged slabs then travel to pinned host memory on a SECOND stream
  * while the next scans already run against the new window.  The caller
  *   - overwrites, with ws_map_insert_box, those parts of the entering slabs the global map already holds (revisits),
  *   - and, typically on a worker thread: ws_shift_wait (blocks on the second stream only), ws_shift_slab for each
  *     leaving slab -> global map, ws_shift_end.
- * The window that moves is the one above (pos - size/2 .. pos - size/2 + size - 1, also for an even size): leaving and entering
- * slabs are parts of it, never wider than `size` along an axis, and a slab's voxels are those of the window before its axis
- * step that the window after it no longer holds.  A step of up to `size` voxels per axis is accepted, a larger one refused.
+ * The slabs and the refusal of a step larger than the window are ws_shift_plan's.
  * new_pos equal to pos gives a ticket without slabs that is ended like any other.
  * One shift can be in flight per map: ws_shift_begin and ws_shift_reserve fail with WS_ERR_INVALID while a ticket is open, and
  * ws_shift_begin while new_map holds entries that have not been integrated.  A refusal leaves both maps as they were. */
@@ -329,10 +343,10 @@ int ws_debug_distance_timing(ws_map *map, int32_t enable, float ms_out[4]);
  *   ws_store_load_box: voxels of present chunks are copied into the ring, voxels of absent chunks become fill_entry, and NO chunk
  *     is created (the bytes of ws_map_insert_box after a plain fill).  Loading into WS_MAP_NEW clears the map's "new_map is default".
  *   ws_shift_device: HDF5LocalMap::shift (hdf5_local_map.cpp:53-118) wholly on the device -- per axis x, y, z the leaving slab is
- *     saved, pos / offset of BOTH maps move, the entering slab is loaded.  The slabs are those of ws_shift_begin (same window, a
- *     step of up to `size` per axis).  A pending scan is settled first.  WS_ERR_INVALID, nothing changed: a ws_shift_begin ticket is
- *     open, new_map holds entries that have not been integrated, a step larger than the window, a store of another context.
- *     new_pos == pos: WS_OK, nothing happens.  The parameters of both maps are committed only after every launch is enqueued.
+ *     saved, pos / offset of BOTH maps move, the entering slab is loaded.  The slabs are those of ws_shift_plan.  A pending scan is
+ *     settled first.  WS_ERR_INVALID, nothing changed: a ws_shift_begin ticket is open, new_map holds entries that have not been
+ *     integrated, a step larger than the window, a store of another context.  new_pos == pos: WS_OK, nothing happens.  The
+ *     parameters of both maps are committed only after every launch is enqueued.
  *   planning before launching: the new chunks of ALL axes of a call are counted before its first launch.  If they do not fit under
  *     max_chunks: WS_ERR_CAPACITY; if a segment cannot be allocated: WS_ERR_HIP; both maps and the store stay as they were.  Only
  *     these planning failures (and the WS_ERR_INVALID refusals) are free of side effects: a HIP error while the launches are being

@@ -355,6 +355,23 @@ public:
                  zi = (size_t)((z - pos_.z + offset_.z + size_.z) % size_.z);
     return data_[(xi * size_.y + yi) * size_.z + zi];
   }
+  // the window in world voxels, every ring cell once: pos - size/2 .. pos - size/2 + size - 1 (ws_shift_plan's window)
+  void window(rm::Pointi &lo, rm::Pointi &hi) const
+  {
+    lo = rm::Pointi(pos_.x - size_.x / 2, pos_.y - size_.y / 2, pos_.z - size_.z / 2);
+    hi = rm::Pointi(lo.x + size_.x - 1, lo.y + size_.y - 1, lo.z + size_.z - 1);
+  }
+  // pos / offset after a shift the device has made (the data is not touched)
+  void follow(const rm::Pointi &new_pos)
+  {
+    const int *sz = &size_.x, *np = &new_pos.x;
+    int *ps = &pos_.x, *of = &offset_.x;
+    for (int k = 0; k < 3; ++k)
+    {
+      of[k] = (int)((((int64_t)of[k] + np[k] - ps[k]) % sz[k] + sz[k]) % sz[k]);
+      ps[k] = np[k];
+    }
+  }
 
 private:
   rm::Pointi size_, pos_, offset_;
@@ -384,14 +401,7 @@ public:
     if (!device_global_map_) throw std::logic_error("shift_map_device: no DeviceGlobalMap attached");
     wait_shift();
     WS_CHECK(ws_shift_device(gpu_.tsdf().handle(), device_global_map_->handle(), &new_pos.x));
-    rm::Pointi &size = local_map_.get_size(), &pos = local_map_.get_pos(), &off = local_map_.get_offset();
-    int *sz = &size.x, *ps = &pos.x, *of = &off.x;
-    const int np[3] = {new_pos.x, new_pos.y, new_pos.z};
-    for (int axis = 0; axis < 3; ++axis)
-    {
-      of[axis] = (int)((((int64_t)of[axis] + np[axis] - ps[axis]) % sz[axis] + sz[axis]) % sz[axis]);
-      ps[axis] = np[axis];
-    }
+    local_map_.follow(new_pos);
   }
 
   // TSDFMapping::map_shift body (tsdf_mapping.cpp:109-126) == HDF5LocalMap::shift (hdf5_local_map.cpp:53-118) per axis:
@@ -401,42 +411,23 @@ public:
     wait_shift();
     auto &avg = gpu_.tsdf().avg_map();
     auto &fresh = gpu_.tsdf().new_map();
-    rm::Pointi &size = local_map_.get_size(), &pos = local_map_.get_pos(), &off = local_map_.get_offset();
-    int *sz = &size.x, *ps = &pos.x, *of = &off.x;
-    const int np[3] = {new_pos.x, new_pos.y, new_pos.z};
+    GlobalMap &gm = local_map_.global_map();
+    ws_shift_plan_t plan;
+    if (ws_shift_plan(&local_map_.get_size().x, &local_map_.get_pos().x, &local_map_.get_offset().x, &new_pos.x, &plan) != WS_OK)
+      throw std::out_of_range("shift_map: further than one window");
+    const auto point = [](const int32_t v[3]) { return rm::Pointi(v[0], v[1], v[2]); };
     std::vector<TSDFEntry> slab;
-    for (int axis = 0; axis < 3; ++axis)
+    for (int i = 0; i < plan.n; ++i)
     {
-      const int d = np[axis] - ps[axis];
-      if (d == 0) continue;
-      if (std::abs(d) > sz[axis]) throw std::out_of_range("shift_map: further than one window");
-      int lo[3], hi[3];
-      for (int k = 0; k < 3; ++k)
-      {
-        lo[k] = ps[k] - sz[k] / 2;
-        hi[k] = ps[k] + sz[k] / 2;
-      }
-      if (d > 0)
-        hi[axis] = lo[axis] + d - 1;
-      else
-        lo[axis] = hi[axis] + d + 1;
-      avg.extract_box(rm::Pointi(lo[0], lo[1], lo[2]), rm::Pointi(hi[0], hi[1], hi[2]), slab);
-      local_map_.global_map().save_box(rm::Pointi(lo[0], lo[1], lo[2]), rm::Pointi(hi[0], hi[1], hi[2]), slab);
-      ps[axis] += d;
-      of[axis] = (of[axis] + d + sz[axis]) % sz[axis];
+      avg.extract_box(point(plan.leave_lo[i]), point(plan.leave_hi[i]), slab);
+      gm.save_box(point(plan.leave_lo[i]), point(plan.leave_hi[i]), slab);
+      rm::Pointi step = local_map_.get_pos();
+      (&step.x)[plan.axis[i]] += plan.d[i];
+      local_map_.follow(step);
       avg.update_params(view_);
       fresh.update_params(view_); // new_map is (tau, 0) everywhere: only its window moves
-      for (int k = 0; k < 3; ++k)
-      {
-        lo[k] = ps[k] - sz[k] / 2;
-        hi[k] = ps[k] + sz[k] / 2;
-      }
-      if (d > 0)
-        lo[axis] = hi[axis] - (d - 1);
-      else
-        hi[axis] = lo[axis] - d - 1;
-      local_map_.global_map().load_box(rm::Pointi(lo[0], lo[1], lo[2]), rm::Pointi(hi[0], hi[1], hi[2]), slab);
-      avg.insert_box(rm::Pointi(lo[0], lo[1], lo[2]), rm::Pointi(hi[0], hi[1], hi[2]), slab);
+      gm.load_box(point(plan.enter_lo[i]), point(plan.enter_hi[i]), slab);
+      avg.insert_box(point(plan.enter_lo[i]), point(plan.enter_hi[i]), slab);
     }
   }
 
@@ -457,11 +448,8 @@ public:
   {
     wait_shift();
     auto &avg = gpu_.tsdf().avg_map();
-    rm::Pointi &size = local_map_.get_size(), &pos = local_map_.get_pos(), &off = local_map_.get_offset();
-    int *sz = &size.x, *ps = &pos.x, *of = &off.x;
-    const int np[3] = {new_pos.x, new_pos.y, new_pos.z};
     ws_shift *ticket = nullptr;
-    WS_CHECK(ws_shift_begin(gpu_.tsdf().handle(), np, local_map_.global_map().get_default_tsdf_entry().raw(), &ticket));
+    WS_CHECK(ws_shift_begin(gpu_.tsdf().handle(), &new_pos.x, local_map_.global_map().get_default_tsdf_entry().raw(), &ticket));
     // Between ws_shift_begin and the start of the worker, loading the entering boxes can throw: the window has moved on the
     // device by then, so the leaving slabs are still filed (synchronously, by this guard) and the ticket is closed -- an
     // open ticket would make every later ws_shift_begin fail.
@@ -479,12 +467,9 @@ public:
         if (armed) file_leaving_slabs(t, n, gm, err);
       }
     } owner{ticket, ws_shift_count(ticket), gm, err, true};
-    for (int axis = 0; axis < 3; ++axis)
-    {
-      const int d = np[axis] - ps[axis];
-      ps[axis] += d;
-      of[axis] = ((of[axis] + d) % sz[axis] + sz[axis]) % sz[axis];
-    }
+    local_map_.follow(new_pos);
+    rm::Pointi wlo, whi;
+    local_map_.window(wlo, whi);
     const int n = ws_shift_count(ticket), cs = GlobalMap::CHUNK_SIZE;
     std::vector<TSDFEntry> part;
     for (int i = 0; i < n; ++i)
@@ -493,8 +478,8 @@ public:
       WS_CHECK(ws_shift_entering(ticket, i, lo, hi));
       for (int k = 0; k < 3; ++k) // only what is still inside the final window
       {
-        lo[k] = std::max(lo[k], ps[k] - sz[k] / 2);
-        hi[k] = std::min(hi[k], ps[k] + sz[k] / 2);
+        lo[k] = std::max(lo[k], (&wlo.x)[k]);
+        hi[k] = std::min(hi[k], (&whi.x)[k]);
       }
       if (lo[0] > hi[0] || lo[1] > hi[1] || lo[2] > hi[2]) continue;
       for (int cx = floor_div(lo[0], cs); cx <= floor_div(hi[0], cs); ++cx)
@@ -517,13 +502,13 @@ public:
   // map -- is kept for wait_shift() instead of being swallowed or ending the process through std::terminate.
   static void file_leaving_slabs(ws_shift *ticket, int n, GlobalMap *gm, std::string *err)
   {
-      struct Closer
-      {
-        ws_shift *t;
-        ~Closer() { ws_shift_end(t); }
-      } closer{ticket};
-      try
-      {
+    struct Closer
+    {
+      ws_shift *t;
+      ~Closer() { ws_shift_end(t); }
+    } closer{ticket};
+    try
+    {
       if (ws_shift_wait(ticket) != WS_OK)
       {
         *err = std::string("ws_shift_wait: ") + ws_last_error();
@@ -562,15 +547,15 @@ public:
         }
         gm->save_box(rm::Pointi(lo[0], lo[1], lo[2]), rm::Pointi(hi[0], hi[1], hi[2]), box);
       }
-      }
-      catch (const std::exception &e)
-      {
-        *err = std::string("filing the leaving slabs: ") + e.what();
-      }
-      catch (...)
-      {
-        *err = "filing the leaving slabs: unknown exception";
-      }
+    }
+    catch (const std::exception &e)
+    {
+      *err = std::string("filing the leaving slabs: ") + e.what();
+    }
+    catch (...)
+    {
+      *err = "filing the leaving slabs: unknown exception";
+    }
   }
   // joins the worker of the last asynchronous shift; throws if its slabs did not reach the global map
   void wait_shift()
@@ -594,9 +579,9 @@ public:
   {
     wait_shift();
     auto &avg = gpu_.tsdf().avg_map();
-    const rm::Pointi &size = local_map_.get_size(), &pos = local_map_.get_pos();
     const int cs = GlobalMap::CHUNK_SIZE;
-    rm::Pointi lo(pos.x - size.x / 2, pos.y - size.y / 2, pos.z - size.z / 2), hi(pos.x + size.x / 2, pos.y + size.y / 2, pos.z + size.z / 2);
+    rm::Pointi lo, hi;
+    local_map_.window(lo, hi);
     if (box_lo) lo = rm::Pointi(std::max(lo.x, box_lo->x), std::max(lo.y, box_lo->y), std::max(lo.z, box_lo->z));
     if (box_hi) hi = rm::Pointi(std::min(hi.x, box_hi->x), std::min(hi.y, box_hi->y), std::min(hi.z, box_hi->z));
     if (lo.x > hi.x || lo.y > hi.y || lo.z > hi.z) return; // the box misses the window

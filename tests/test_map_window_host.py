@@ -8,6 +8,7 @@ import window_model as M
 from window_model import WALKS
 
 TAU = 1000
+WS_ERR_INVALID = -1
 
 
 class HostRoute:
@@ -94,3 +95,49 @@ def test_expected_slabs_partition_the_move():
             want = np.zeros(shape, dtype=bool)
             want[sl(nlo, nhi)] = True
             assert np.array_equal(inside, want)
+
+
+def test_shift_plan_is_the_models_slabs():
+    """ws_shift_plan (no map, no GPU) against the model over the shapes of test_expected_slabs_partition_the_move: the steps, every
+    leaving and entering box, and the window's final pos / offset; no move, the largest step and the first one refused"""
+    import ctypes as C
+    from warpsense_amd import _lib
+    L = _lib.load()
+    i3 = lambda v: np.ascontiguousarray(v, dtype=np.int32)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+
+    def plan_of(size, pos, new_pos):
+        plan = _lib.ShiftPlan()
+        size, pos, off, new_pos = i3(size), i3(pos), i3(M.model_offset(size, pos)), i3(new_pos)
+        return L.ws_shift_plan(p(size), p(pos), p(off), p(new_pos), C.byref(plan)), plan
+
+    rng = np.random.default_rng(5)
+    for size in [(21, 17, 13), (16, 18, 20), (3, 19, 5), (4, 4, 4)]:
+        size = np.asarray(size)
+        for _ in range(40):
+            pos = rng.integers(-30, 31, 3)
+            new_pos = pos + np.array([rng.integers(-int(s), int(s) + 1) for s in size])
+            rc, plan = plan_of(size, pos, new_pos)
+            want = M.expected_slabs(size, pos, new_pos)
+            assert rc == 0 and plan.n == len(want)
+            for i, s in enumerate(want):
+                assert plan.axis[i] == s["axis"] and plan.d[i] == new_pos[s["axis"]] - pos[s["axis"]]
+                assert np.array_equal(plan.leave_lo[i], s["leave"][0]) and np.array_equal(plan.leave_hi[i], s["leave"][1])
+                assert np.array_equal(plan.enter_lo[i], s["enter"][0]) and np.array_equal(plan.enter_hi[i], s["enter"][1])
+            assert np.array_equal(plan.pos, new_pos) and np.array_equal(plan.offset, M.model_offset(size, new_pos))
+        pos = rng.integers(-30, 31, 3)
+        rc, plan = plan_of(size, pos, pos)
+        assert rc == 0 and plan.n == 0 and np.array_equal(plan.pos, pos) and np.array_equal(plan.offset, M.model_offset(size, pos))
+        for axis in range(3):
+            for sign in (1, -1):
+                step = np.zeros(3, dtype=np.int64)
+                step[axis] = sign * size[axis]
+                rc, plan = plan_of(size, pos, pos + step)
+                assert rc == 0 and plan.n == 1 and plan.axis[0] == axis and plan.d[0] == step[axis]
+                step[axis] += sign
+                assert plan_of(size, pos, pos + step)[0] == WS_ERR_INVALID
+    a, plan = i3((0, 0, 0)), _lib.ShiftPlan()
+    for k in range(5):
+        args = [p(i3((5, 5, 5))), p(a), p(a), p(a), C.byref(plan)]
+        args[k] = None
+        assert L.ws_shift_plan(*args) == WS_ERR_INVALID

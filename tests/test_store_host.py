@@ -10,7 +10,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["ws_store_create", "ws_store_destroy", "ws_store_reserve", "ws_store_count", "ws_store_keys", "ws_store_has", "ws_store_get_chunk",
        "ws_store_put_chunk", "ws_store_drop_chunk", "ws_store_chunk_dev", "ws_store_save_box", "ws_store_load_box", "ws_shift_device",
-       "ws_store_chunks_of_box", "ws_debug_store_timing"]
+       "ws_store_chunks_of_box", "ws_debug_store_timing", "ws_shift_plan"]
 WS_ERR_INVALID = -1
 
 

@@ -22,7 +22,7 @@ KERNEL_CLASSES = ["ray_setup", "march_tails", "march_free", "tile_bin", "tile_re
 EXPORTS = [
     "ws_last_error", "ws_version", "ws_ctx_create", "ws_ctx_destroy", "ws_ctx_set_stream", "ws_sync",
     "ws_device_reset", "ws_map_create", "ws_map_destroy", "ws_map_upload", "ws_map_set_params", "ws_map_download",
-    "ws_map_extract_box", "ws_map_insert_box", "ws_shift_begin", "ws_shift_reserve", "ws_shift_count", "ws_shift_entering", "ws_shift_wait", "ws_shift_slab",
+    "ws_map_extract_box", "ws_map_insert_box", "ws_shift_plan", "ws_shift_begin", "ws_shift_reserve", "ws_shift_count", "ws_shift_entering", "ws_shift_wait", "ws_shift_slab",
     "ws_shift_end", "ws_map_get_params", "ws_map_device_data", "ws_map_n_voxels", "ws_tsdf_update", "ws_tsdf_update_dev", "ws_tsdf_scatter_dev",
     "ws_tsdf_integrate", "ws_tsdf_set_integrate", "ws_tsdf_set_capacity", "ws_debug_tsdf_chunk_policy", "ws_tsdf_stats", "ws_reg_create", "ws_reg_destroy", "ws_reg_prepare",
     "ws_reg_prepare_dev", "ws_reg_points_dev", "ws_reg_iterate", "ws_register_cloud", "ws_reg_begin", "ws_reg_accumulate_dev",
@@ -97,6 +97,13 @@ class TsdfStats(C.Structure):
                 ("record_slots", C.c_int64), ("record_capacity", C.c_int64)]
 
 
+class ShiftPlan(C.Structure):
+    """ws_shift_plan_t: the steps of a map shift and their boxes"""
+    _fields_ = [("n", C.c_int32), ("axis", C.c_int32 * 3), ("d", C.c_int32 * 3),
+                ("leave_lo", C.c_int32 * 3 * 3), ("leave_hi", C.c_int32 * 3 * 3), ("enter_lo", C.c_int32 * 3 * 3), ("enter_hi", C.c_int32 * 3 * 3),
+                ("pos", C.c_int32 * 3), ("offset", C.c_int32 * 3)]
+
+
 _lib = None
 
 
@@ -158,6 +165,7 @@ def load() -> C.CDLL:
     L.ws_map_distance_dev.restype = vp
     L.ws_map_distance_download.argtypes = [vp, vp, sz, P(sz)]
     L.ws_debug_distance_timing.argtypes = [vp, i32, vp]
+    L.ws_shift_plan.argtypes = [vp, vp, vp, vp, P(ShiftPlan)]
     L.ws_shift_begin.argtypes = [vp, vp, u32, P(vp)]
     L.ws_shift_count.argtypes = [vp]
     L.ws_shift_reserve.argtypes = [vp, C.c_uint64]

@@ -685,6 +685,17 @@ class LocalMap:
                 end[axis] = start[axis] - diff[axis] - 1
             self._area(start, end, save=False)
 
+    def window(self):
+        """(lo, hi) of the window in world voxels, every ring cell once: pos - size/2 .. pos - size/2 + size - 1"""
+        lo = self.pos.astype(np.int64) - self.size.astype(np.int64) // 2
+        return lo, lo + self.size.astype(np.int64) - 1
+
+    def follow(self, new_pos):
+        """pos / offset after a shift the device has made (the data, if any, is not touched)"""
+        new_pos = np.asarray(new_pos, dtype=np.int64)
+        self.offset[:] = (self.offset + (new_pos - self.pos)) % self.size  # (numpy's % is >= 0 for a negative d)
+        self.pos[:] = new_pos
+
     def write_back(self):
         """hdf5_local_map.cpp:210-217: save the whole window to the global map."""
         self._area(self.pos.astype(np.int64) - self.size // 2, self.pos.astype(np.int64) + self.size // 2, save=True)
@@ -1295,36 +1306,21 @@ class TSDFMapping:
         until avg_map().to_host() is called."""
         self.wait_shift()
         lm, avg, new = self.local_map_, self.tsdf_.avg_map(), self.tsdf_.new_map()
-        new_pos = np.asarray(new_pos, dtype=np.int64)
         with self.mutex_:
-            diff = new_pos - lm.pos
-            assert np.all(np.abs(diff) <= lm.size)
-            for axis in range(3):
-                d = int(diff[axis])
-                if d == 0:
-                    continue
-                # the window: every ring cell once (pos + size/2 for the odd sizes of LocalMap; an even size ends one voxel earlier)
-                half, size = lm.size.astype(np.int64) // 2, lm.size.astype(np.int64)
-                start = lm.pos.astype(np.int64) - half
-                end = start + size - 1
-                if d > 0:
-                    end[axis] = start[axis] + d - 1
-                else:
-                    start[axis] = end[axis] + d + 1
-                lm.map_.save_box(start, end, avg.extract_box(start, end))
-                lm.pos[axis] += d
-                lm.offset[axis] = (lm.offset[axis] + d + lm.size[axis]) % lm.size[axis]
+            plan = _lib.ShiftPlan()  # per axis that moves: the boxes that leave and enter
+            check(self.tsdf_._L.ws_shift_plan(_ptr(_i3(lm.size)), _ptr(_i3(lm.pos)), _ptr(_i3(lm.offset)), _ptr(_i3(new_pos)), C.byref(plan)),
+                  "ws_shift_plan")
+            for i in range(plan.n):
+                lo, hi = np.array(plan.leave_lo[i], dtype=np.int64), np.array(plan.leave_hi[i], dtype=np.int64)
+                lm.map_.save_box(lo, hi, avg.extract_box(lo, hi))
+                step = lm.pos.copy()
+                step[plan.axis[i]] += plan.d[i]
+                lm.follow(step)
                 view = lm.device_map()
                 avg.update_params(view)
                 new.update_params(view)  # new_map is (tau, 0) everywhere: only its window moves
-                start = lm.pos.astype(np.int64) - half
-                end = start + size - 1
-                if d > 0:
-                    start[axis] = end[axis] - (d - 1)
-                else:
-                    end[axis] = start[axis] - d - 1
-                avg.insert_box(start, end, lm.map_.load_box(start, end))
-
+                lo, hi = np.array(plan.enter_lo[i], dtype=np.int64), np.array(plan.enter_hi[i], dtype=np.int64)
+                avg.insert_box(lo, hi, lm.map_.load_box(lo, hi))
 
     # ---- the same shift off the scan path ---------------------------------------------------------------
     def shift_map_async(self, new_pos):
@@ -1389,21 +1385,15 @@ class TSDFMapping:
 
     def _shift_enter(self, L, ticket, n, new_pos, lm, avg):
         """the host side of an asynchronous shift between ws_shift_begin and the start of the worker"""
-        # the host view of the window follows (pos / offset per axis exactly like HDF5LocalMap::shift)
-        diff = new_pos.astype(np.int64) - lm.pos
-        for axis in range(3):
-            d = int(diff[axis])
-            lm.pos[axis] += d
-            lm.offset[axis] = (lm.offset[axis] + d + lm.size[axis]) % lm.size[axis]
+        lm.follow(new_pos)  # the host view of the window
         # revisited space: chunks the global map already has overwrite the default fill
         cs = GlobalMap.CHUNK_SIZE
         lo, hi = np.zeros(3, dtype=np.int32), np.zeros(3, dtype=np.int32)
         for i in range(n):
             check(L.ws_shift_entering(ticket, i, _ptr(lo), _ptr(hi)), "ws_shift_entering")
             # a later axis step moves the window again: only the part of the slab still inside the FINAL window counts
-            half = lm.size.astype(np.int64) // 2
-            a = np.maximum(lo.astype(np.int64), lm.pos.astype(np.int64) - half)
-            b = np.minimum(hi.astype(np.int64), lm.pos.astype(np.int64) - half + lm.size.astype(np.int64) - 1)
+            wlo, whi = lm.window()
+            a, b = np.maximum(lo.astype(np.int64), wlo), np.minimum(hi.astype(np.int64), whi)
             if np.any(a > b):
                 continue
             c0, c1 = np.floor_divide(a, cs), np.floor_divide(b, cs)
@@ -1428,9 +1418,7 @@ class TSDFMapping:
         new_pos = _i3(new_pos)
         with self.mutex_:
             check(self.tsdf_._L.ws_shift_device(self.tsdf_.handle, self.device_global_map_.handle, _ptr(new_pos)), "ws_shift_device")
-            d = new_pos.astype(np.int64) - lm.pos
-            lm.pos[:] = new_pos
-            lm.offset[:] = (lm.offset + d + lm.size) % lm.size
+            lm.follow(new_pos)
 
     def reserve_shift(self, shift_voxels: int):
         """staging for asynchronous shifts of up to `shift_voxels` per axis (plus slack), allocated now instead of inside
@@ -1461,8 +1449,7 @@ class TSDFMapping:
         lm, avg = self.local_map_, self.tsdf_.avg_map()
         cs = GlobalMap.CHUNK_SIZE
         with self.mutex_:
-            lo = lm.pos.astype(np.int64) - lm.size.astype(np.int64) // 2
-            hi = lo + lm.size.astype(np.int64) - 1
+            lo, hi = lm.window()
             if box_lo is not None:
                 lo = np.maximum(lo, np.asarray(box_lo, dtype=np.int64))
             if box_hi is not None:

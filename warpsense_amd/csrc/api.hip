@@ -918,53 +918,58 @@ int ws_debug_distance_timing(ws_map *m, int32_t enable, float ms_out[4])
   return query_timing(m, m->dist.timer, enable, ms_out, pairs, 4);
 }
 
-// ---- map shift off the scan path
-// The plan of a shift, shared by ws_shift_begin and ws_shift_device: per axis, like HDF5LocalMap::shift (hdf5_local_map.cpp:53-118),
-// with the window as it is when that axis moves.  The window is pos - size/2 .. pos - size/2 + size - 1, every ring cell once: the
-// reference's pos + size/2 for its odd sizes; for an even size pos + size/2 would be the ring cell of pos - size/2 again, filed under
-// a second world position.  Fills n, the boxes, the slabs' offsets in a packed staging buffer and their total.
-static int plan_shift(const MapParams &p0, const int32_t new_pos[3], const char *name, ws_shift *sh)
+// ---- map shift
+// The plan of a shift (ws_shift_plan; `name` is the entry point the refusal speaks for): per axis, like HDF5LocalMap::shift
+// (hdf5_local_map.cpp:53-118), with the window as it is when that axis moves.  The window is pos - size/2 .. pos - size/2 + size - 1,
+// every ring cell once: the reference's pos + size/2 for its odd sizes; for an even size pos + size/2 would be the ring cell of
+// pos - size/2 again, filed under a second world position.
+static int plan_shift(const int32_t size[3], const int32_t pos0[3], const int32_t offset0[3], const int32_t new_pos[3], const char *name,
+                      ws_shift_plan_t *out)
 {
-  int32_t pos[3] = {p0.pos[0], p0.pos[1], p0.pos[2]};
-  size_t total = 0;
-  sh->n = 0;
+  int32_t *pos = out->pos;
+  copy3(pos, pos0);
+  copy3(out->offset, offset0);
+  out->n = 0;
+  const auto window = [&](int32_t lo[3], int32_t hi[3]) { // of `pos` as it is now
+    for (int k = 0; k < 3; ++k) lo[k] = pos[k] - size[k] / 2, hi[k] = lo[k] + size[k] - 1;
+  };
   for (int axis = 0; axis < 3; ++axis)
   {
     const int64_t d = (int64_t)new_pos[axis] - pos[axis];
     if (d == 0) continue;
-    if (std::llabs((long long)d) > p0.size[axis]) return invalid((std::string(name) + ": shift larger than the window").c_str());
-    const int i = sh->n++;
+    if (std::llabs((long long)d) > size[axis]) return invalid((std::string(name) + ": shift larger than the window").c_str());
+    const int i = out->n++;
+    out->axis[i] = axis;
+    out->d[i] = (int32_t)d;
     int32_t start[3], end[3];
-    for (int k = 0; k < 3; ++k)
-    {
-      start[k] = pos[k] - p0.size[k] / 2;
-      end[k] = start[k] + p0.size[k] - 1;
-    }
+    window(start, end);
     if (d > 0)
       end[axis] = start[axis] + (int32_t)d - 1;
     else
       start[axis] = end[axis] + (int32_t)d + 1;
-    copy3(sh->leave_lo[i], start);
-    copy3(sh->leave_hi[i], end);
+    copy3(out->leave_lo[i], start);
+    copy3(out->leave_hi[i], end);
     pos[axis] += (int32_t)d;
-    for (int k = 0; k < 3; ++k)
-    {
-      start[k] = pos[k] - p0.size[k] / 2;
-      end[k] = start[k] + p0.size[k] - 1;
-    }
+    out->offset[axis] = (int32_t)((((int64_t)out->offset[axis] + d) % size[axis] + size[axis]) % size[axis]);
+    window(start, end);
     if (d > 0)
       start[axis] = end[axis] - ((int32_t)d - 1);
     else
       end[axis] = start[axis] - (int32_t)d - 1;
-    copy3(sh->enter_lo[i], start);
-    copy3(sh->enter_hi[i], end);
-    sh->offset[i] = total;
-    total += (size_t)(sh->leave_hi[i][0] - sh->leave_lo[i][0] + 1) * (size_t)(sh->leave_hi[i][1] - sh->leave_lo[i][1] + 1) *
-             (size_t)(sh->leave_hi[i][2] - sh->leave_lo[i][2] + 1);
+    copy3(out->enter_lo[i], start);
+    copy3(out->enter_hi[i], end);
   }
-  sh->total = total;
   return WS_OK;
 }
+
+int ws_shift_plan(const int32_t size[3], const int32_t pos[3], const int32_t offset[3], const int32_t new_pos[3], ws_shift_plan_t *out)
+{
+  if (!size || !pos || !offset || !new_pos || !out) return invalid("ws_shift_plan: NULL argument");
+  for (int k = 0; k < 3; ++k)
+    if (size[k] < 1) return invalid("ws_shift_plan: size < 1");
+  return plan_shift(size, pos, offset, new_pos, "ws_shift_plan", out);
+}
+
 // the axis step of both maps' windows between the save and the load of a slab (pos and offset, DeviceMapMemWrapper::update_params)
 static void move_axis(MapParams par[2], int axis, int32_t d)
 {
@@ -975,6 +980,39 @@ static void move_axis(MapParams par[2], int axis, int32_t d)
     p.offset[axis] = (int32_t)((((int64_t)p.offset[axis] + d) % p.size[axis] + p.size[axis]) % p.size[axis]);
   }
 }
+
+// One shift of both maps' windows, for ws_shift_begin and ws_shift_device, which differ in what happens to a slab that leaves and
+// to one that enters.  `name` is the entry point and `open_text` its words for a ticket in flight.  After the shared refusals and
+// the plan (into `plan`): ready() before the first launch; per step leave(i, par), the axis step, enter(i, par), on a COPY of the
+// parameters (the box kernels take them by value); done() behind the last step.  The copy is committed only when all of it has
+// been enqueued: the first error is returned with the host's view of both maps as it was.
+extern "C++" {
+template <class Ready, class Leave, class Enter, class Done>
+static int run_shift(ws_map *m, const int32_t new_pos[3], const char *name, const char *open_text, ws_shift_plan_t &plan, Ready ready, Leave leave,
+                     Enter enter, Done done)
+{
+  WS_SETTLE(m);
+  if (m->shift_open) return invalid((std::string(name) + open_text).c_str());
+  // only new_map's WINDOW moves (DeviceMapMemWrapper::update_params), which is right iff it holds (tau, 0) everywhere -- not between
+  // ws_tsdf_scatter_dev and ws_tsdf_integrate, nor for a map created from non-default host data that has not been integrated yet
+  if (!m->new_is_default)
+    return invalid((std::string(name) + ": new_map holds entries that have not been integrated (ws_tsdf_integrate first)").c_str());
+  const MapParams &p0 = m->par[WS_MAP_AVG];
+  WS_TRY(plan_shift(p0.size, p0.pos, p0.offset, new_pos, name, &plan));
+  WS_TRY(ready());
+  MapParams par[2] = {m->par[0], m->par[1]};
+  int rc = WS_OK;
+  for (int i = 0; i < plan.n && rc == WS_OK; ++i)
+  {
+    rc = leave(i, par[WS_MAP_AVG]);
+    move_axis(par, plan.axis[i], plan.d[i]);
+    if (rc == WS_OK) rc = enter(i, par[WS_MAP_AVG]);
+  }
+  if (rc == WS_OK) rc = done();
+  if (rc == WS_OK) m->par[0] = par[0], m->par[1] = par[1];
+  return rc;
+}
+} // extern "C++"
 
 static int shift_reserve(ws_map *m, size_t total)
 {
@@ -994,78 +1032,62 @@ int ws_shift_reserve(ws_map *m, uint64_t voxels)
   return shift_reserve(m, (size_t)voxels);
 }
 
+static size_t box_extent(const int32_t lo[3], const int32_t hi[3], int32_t ext[3]) // the voxels of the box
+{
+  for (int k = 0; k < 3; ++k) ext[k] = hi[k] - lo[k] + 1;
+  return (size_t)ext[0] * (size_t)ext[1] * (size_t)ext[2];
+}
+
 int ws_shift_begin(ws_map *m, const int32_t new_pos[3], uint32_t fill_entry, ws_shift **out)
 {
   if (!m || !new_pos || !out) return invalid("ws_shift_begin: NULL argument");
-  WS_SETTLE(m);
-  if (m->shift_open) return invalid("ws_shift_begin: the previous shift of this map has not been ended (ws_shift_end)");
-  // only new_map's WINDOW moves here, which is right iff it holds (tau, 0) everywhere -- not between ws_tsdf_scatter_dev and
-  // ws_tsdf_integrate, nor for a map created from non-default host data that has not been integrated yet
-  if (!m->new_is_default) return invalid("ws_shift_begin: new_map holds entries that have not been integrated (ws_tsdf_integrate first)");
   ws_shift *sh = new (std::nothrow) ws_shift();
   if (!sh) return invalid("ws_shift_begin: out of host memory");
   sh->map = m;
-  {
-    const int rc0 = plan_shift(m->par[WS_MAP_AVG], new_pos, "ws_shift_begin", sh);
-    if (rc0 != WS_OK)
-    {
-      delete sh;
-      return rc0;
-    }
-  }
-  const size_t total = sh->total;
+  const ws_shift_plan_t &plan = sh->plan;
   hipStream_t s = m->ctx->stream;
-  {
-    // (a shift larger than anything reserved: the staging buffers grow, which waits for the stream once)
-    const int rc0 = shift_reserve(m, total ? total : 1);
-    if (rc0 != WS_OK)
-    {
-      delete sh;
-      return rc0;
-    }
-  }
-  // execute the plan on the map's stream.  The window moves in a COPY of the parameters (the box kernels take them by
-  // value) and is committed only when every launch and copy has been enqueued: a HIP error half-way leaves the host's
-  // view of both maps as it was.
-  int rc = WS_OK;
-  MapParams par[2] = {m->par[0], m->par[1]};
-  for (int i = 0, axis = 0; i < sh->n && rc == WS_OK; ++i, ++axis)
-  {
-    while (new_pos[axis] == par[WS_MAP_AVG].pos[axis]) ++axis; // the axis slab i belongs to
-    int32_t ext[3];
-    for (int k = 0; k < 3; ++k) ext[k] = sh->leave_hi[i][k] - sh->leave_lo[i][k] + 1;
-    rc = launch_box_copy(m, par[WS_MAP_AVG], WS_MAP_AVG, sh->leave_lo[i], ext, m->shift_stage_dev.as<uint32_t>() + sh->offset[i], true, s);
-    move_axis(par, axis, new_pos[axis] - par[WS_MAP_AVG].pos[axis]);
-    for (int k = 0; k < 3; ++k) ext[k] = sh->enter_hi[i][k] - sh->enter_lo[i][k] + 1;
-    if (rc == WS_OK) rc = launch_box_fill(m, par[WS_MAP_AVG], WS_MAP_AVG, sh->enter_lo[i], ext, fill_entry, s);
-    // new_map is (tau, 0) everywhere between updates (checked above): only its window moves (DeviceMapMemWrapper::update_params)
-  }
-  if (rc == WS_OK && total)
-  {
-    hipError_t e = hipEventRecord(m->shift_event, s);
-    if (e == hipSuccess) e = hipStreamWaitEvent(m->shift_stream, m->shift_event, 0);
-    if (e == hipSuccess) e = hipMemcpyAsync(m->shift_stage_host.p, m->shift_stage_dev.p, total * sizeof(uint32_t), hipMemcpyDeviceToHost, m->shift_stream);
-    if (e != hipSuccess) rc = hip_fail(e, "ws_shift_begin copy", __FILE__, __LINE__);
-  }
-  if (rc != WS_OK)
-  {
+  const int rc = run_shift(
+      m, new_pos, "ws_shift_begin", ": the previous shift of this map has not been ended (ws_shift_end)", sh->plan,
+      [&]() -> int {
+        // the leaving slabs lie packed in the staging buffers (a shift larger than anything reserved: they grow, which waits for the
+        // stream once)
+        int32_t ext[3];
+        sh->total = 0;
+        for (int i = 0; i < plan.n; ++i) sh->offset[i] = sh->total, sh->total += box_extent(plan.leave_lo[i], plan.leave_hi[i], ext);
+        return shift_reserve(m, sh->total ? sh->total : 1);
+      },
+      [&](int i, const MapParams &par) -> int {
+        int32_t ext[3];
+        box_extent(plan.leave_lo[i], plan.leave_hi[i], ext);
+        return launch_box_copy(m, par, WS_MAP_AVG, plan.leave_lo[i], ext, m->shift_stage_dev.as<uint32_t>() + sh->offset[i], true, s);
+      },
+      [&](int i, const MapParams &par) -> int {
+        int32_t ext[3];
+        box_extent(plan.enter_lo[i], plan.enter_hi[i], ext);
+        return launch_box_fill(m, par, WS_MAP_AVG, plan.enter_lo[i], ext, fill_entry, s);
+      },
+      [&]() -> int { // the staged slabs travel to the host on the second stream
+        if (!sh->total) return WS_OK;
+        hipError_t e = hipEventRecord(m->shift_event, s);
+        if (e == hipSuccess) e = hipStreamWaitEvent(m->shift_stream, m->shift_event, 0);
+        if (e == hipSuccess)
+          e = hipMemcpyAsync(m->shift_stage_host.p, m->shift_stage_dev.p, sh->total * sizeof(uint32_t), hipMemcpyDeviceToHost, m->shift_stream);
+        return e == hipSuccess ? WS_OK : hip_fail(e, "ws_shift_begin copy", __FILE__, __LINE__);
+      });
+  if (rc == WS_OK)
+    m->shift_open = *out = sh;
+  else
     delete sh;
-    return rc;
-  }
-  m->par[0] = par[0];
-  m->par[1] = par[1];
-  m->shift_open = sh;
-  *out = sh;
-  return WS_OK;
+  return rc;
 }
 
-int ws_shift_count(const ws_shift *sh) { return sh ? sh->n : 0; }
+int ws_shift_count(const ws_shift *sh) { return sh ? sh->plan.n : 0; }
 
 int ws_shift_entering(const ws_shift *sh, int i, int32_t lo[3], int32_t hi[3])
 {
-  if (!sh || i < 0 || i >= sh->n || !lo || !hi) return invalid("ws_shift_entering: bad argument");
-  copy3(lo, sh->enter_lo[i]);
-  copy3(hi, sh->enter_hi[i]);
+  if (!sh || i < 0 || i >= sh->plan.n || !lo || !hi) return invalid("ws_shift_entering: bad argument");
+  copy3(lo, sh->plan.enter_lo[i]);
+  copy3(hi, sh->plan.enter_hi[i]);
   return WS_OK;
 }
 
@@ -1078,9 +1100,9 @@ int ws_shift_wait(ws_shift *sh)
 
 int ws_shift_slab(const ws_shift *sh, int i, int32_t lo[3], int32_t hi[3], const uint32_t **host_data)
 {
-  if (!sh || i < 0 || i >= sh->n || !lo || !hi || !host_data) return invalid("ws_shift_slab: bad argument");
-  copy3(lo, sh->leave_lo[i]);
-  copy3(hi, sh->leave_hi[i]);
+  if (!sh || i < 0 || i >= sh->plan.n || !lo || !hi || !host_data) return invalid("ws_shift_slab: bad argument");
+  copy3(lo, sh->plan.leave_lo[i]);
+  copy3(hi, sh->plan.leave_hi[i]);
   *host_data = sh->map->shift_stage_host.as<uint32_t>() + sh->offset[i];
   return WS_OK;
 }
@@ -1448,42 +1470,38 @@ int ws_shift_device(ws_map *m, ws_store *st, const int32_t new_pos[3])
 {
   WS_TRY(store_args(st, m, WS_MAP_AVG, "ws_shift_device"));
   if (!new_pos) return invalid("ws_shift_device: new_pos is NULL");
-  WS_SETTLE(m);
-  if (m->shift_open) return invalid("ws_shift_device: a shift of this map is in flight (ws_shift_end)");
-  // as in ws_shift_begin: only new_map's window moves, which is right iff it holds (tau, 0) everywhere
-  if (!m->new_is_default) return invalid("ws_shift_device: new_map holds entries that have not been integrated (ws_tsdf_integrate first)");
-  std::lock_guard<std::mutex> lock(st->mu);
-  ws_shift plan;
-  WS_TRY(plan_shift(m->par[WS_MAP_AVG], new_pos, "ws_shift_device", &plan));
-  for (QueryTimer &t : st->timer) WS_TRY(t.arm());
-  if (plan.n == 0) return WS_OK;
-  // every chunk the leaving slabs of ALL axes create, before the first launch: a call that cannot get them changes nothing
-  std::set<StoreKey> fresh;
-  for (int i = 0; i < plan.n; ++i) store_missing(st, plan.leave_lo[i], plan.leave_hi[i], fresh);
-  WS_TRY(store_make_room(st, fresh.size(), "ws_shift_device"));
-  store_admit(st, fresh);
-  // the window moves in a copy of the parameters, committed when every launch has been enqueued (as ws_shift_begin does)
+  std::unique_lock<std::mutex> lock(st->mu, std::defer_lock); // taken in ready(), after the refusals, and held to the end of the call
+  ws_shift_plan_t plan;
+  std::set<StoreKey> fresh; // the chunks this call has created
   hipStream_t s = m->ctx->stream;
-  int rc = WS_OK;
-  MapParams par[2] = {m->par[0], m->par[1]};
-  for (int i = 0, axis = 0; i < plan.n && rc == WS_OK; ++i, ++axis)
-  {
-    while (new_pos[axis] == par[WS_MAP_AVG].pos[axis]) ++axis; // the axis slab i belongs to
-    st->timer[i].mark(0, s);
-    rc = store_enqueue(st, m, par[WS_MAP_AVG], WS_MAP_AVG, plan.leave_lo[i], plan.leave_hi[i], true);
-    st->timer[i].mark(1, s);
-    move_axis(par, axis, new_pos[axis] - par[WS_MAP_AVG].pos[axis]);
-    if (rc == WS_OK) rc = store_enqueue(st, m, par[WS_MAP_AVG], WS_MAP_AVG, plan.enter_lo[i], plan.enter_hi[i], false);
-    st->timer[i].mark(2, s);
-  }
-  if (rc != WS_OK)
-  {
-    store_evict(st, fresh);
-    return rc;
-  }
-  m->par[0] = par[0];
-  m->par[1] = par[1];
-  return WS_OK;
+  const int rc = run_shift(
+      m, new_pos, "ws_shift_device", ": a shift of this map is in flight (ws_shift_end)", plan,
+      [&]() -> int {
+        lock.lock();
+        for (QueryTimer &t : st->timer) WS_TRY(t.arm());
+        // every chunk the leaving slabs of ALL axes create, before the first launch: a call that cannot get them changes nothing
+        std::set<StoreKey> missing;
+        for (int i = 0; i < plan.n; ++i) store_missing(st, plan.leave_lo[i], plan.leave_hi[i], missing);
+        WS_TRY(store_make_room(st, missing.size(), "ws_shift_device"));
+        store_admit(st, missing);
+        fresh.swap(missing);
+        return WS_OK;
+      },
+      [&](int i, const MapParams &par) -> int {
+        st->timer[i].mark(0, s);
+        const int rc_save = store_enqueue(st, m, par, WS_MAP_AVG, plan.leave_lo[i], plan.leave_hi[i], true);
+        st->timer[i].mark(1, s);
+        if (rc_save != WS_OK) st->timer[i].mark(2, s); // the step ends here, its load is never enqueued: close its second interval too
+        return rc_save;
+      },
+      [&](int i, const MapParams &par) -> int {
+        const int rc_load = store_enqueue(st, m, par, WS_MAP_AVG, plan.enter_lo[i], plan.enter_hi[i], false);
+        st->timer[i].mark(2, s);
+        return rc_load;
+      },
+      []() -> int { return WS_OK; });
+  if (rc != WS_OK) store_evict(st, fresh); // (after a refusal, which holds no lock, `fresh` is empty)
+  return rc;
 }
 
 int ws_store_chunks_of_box(const int32_t lo[3], const int32_t hi[3], int32_t *keys, size_t capacity, size_t *n_out)

@@ -513,10 +513,8 @@ struct ws_map
 struct ws_shift
 {
   ws_map *map = nullptr;
-  int n = 0;
-  int32_t leave_lo[3][3], leave_hi[3][3]; // world boxes that left (coordinates of the window before that axis moved)
-  int32_t enter_lo[3][3], enter_hi[3][3]; // world boxes that entered
-  size_t offset[3];                       // of slab i in the staging buffers (voxels)
+  ws_shift_plan_t plan; // the steps and their boxes (ws_shift_plan)
+  size_t offset[3];     // of leaving slab i in the staging buffers (voxels)
   size_t total = 0;
 };
 
