@@ -550,6 +550,53 @@ int ws_scan_preprocess_dev(ws_scan *scan, const float *xyz_dev, size_t n, size_t
 const int32_t *ws_scan_points_dev(const ws_scan *scan); /* n_out x 3 int32, device memory */
 int ws_scan_download(ws_scan *scan, int32_t *xyz_host, size_t capacity_points, size_t *n_out);
 
+/* Motion-compensated pre-processing: one sensor pose per time bin of a sweep (a spinning lidar moves while it turns).
+ * A sweep is described by k poses (1 <= k <= WS_SWEEP_MAX_BINS; each 4x4 column-major float, translation in mm, as `pose` above;
+ * poses_host: k x 16 floats) and a rule that gives every input point a bin b in 0 .. k-1.  Point i is treated exactly as the
+ * plain call treats it with to_int_mat(poses[b]) in place of to_int_mat(pose): the same drop rule (x, y, z all < 0.3;
+ * non-finite dropped), the same float snapping to the voxel centre in the sensor frame, the same wrapping int32 products and
+ * truncating division by 32768, the same +-2^20 mm range check (WS_ERR_RANGE).  De-duplication runs over the whole sweep, not per
+ * bin: two points of different bins that land on the same integer point are kept once, at the first one's input position.  The
+ * output is the input order with later duplicates removed; it is read with ws_scan_points_dev / ws_scan_download as above.
+ * With k = 1 the result is that of the plain call with poses[0].
+ *
+ * The rule (ws_sweep_t) is one of two:
+ *   by index (time_field = -1): the cloud is organised, `columns` >= 1 firing columns with n % columns == 0.
+ *       col = ring_major ? i % columns : i / (n / columns);   b = (uint64)col * k / columns
+ *     (ring_major != 0: index = ring * columns + column, the order of an image row per ring; 0: column after column.)
+ *   by a per-point time (3 <= time_field < stride_floats): t is the float at that index of the point's record,
+ *       s = (t - t_begin) / (t_end - t_begin);   v = s * (float)k         (each operation in float32, not contracted)
+ *       b = v >= (float)k ? k - 1 : (v > 0 ? (uint32)v : 0)
+ *     so a time before t_begin goes to bin 0, one after t_end to bin k-1, and s * k exactly integral to the upper bin.  A NaN s
+ *     drops the point.  t_begin == t_end or a non-finite bound is refused; columns and ring_major are not read.
+ * WS_ERR_INVALID, before anything is launched (the next valid call works as usual): k out of range, n % columns != 0 or
+ * columns == 0, a time_field of 0..2, below -1 or >= stride_floats, bad time bounds, NULL arguments, stride_floats < 3,
+ * map_resolution < 1, n above what ws_scan_create reserved.
+ * The poses are converted on the host with the plain call's to_int_mat, one 64-byte row of 16 int32 per bin, and uploaded in stream
+ * order from pinned memory; the table and its staging belong to `scan` and are allocated by the first sweep call.  Synchronises. */
+#define WS_SWEEP_MAX_BINS 4096
+typedef struct
+{
+  uint32_t columns;   /* by index: firing columns of the organised cloud             */
+  int32_t ring_major; /* by index: != 0 if index = ring * columns + column          */
+  int32_t time_field; /* -1: by index; else the index of the time in a point record */
+  float t_begin, t_end; /* by time: the times of the sweep's begin and end           */
+} ws_sweep_t;
+int ws_scan_preprocess_sweep(ws_scan *scan, const float *xyz_host, size_t n, size_t stride_floats, const float *poses_host, uint32_t k,
+                             const ws_sweep_t *rule, int32_t map_resolution, size_t *n_out);
+int ws_scan_preprocess_sweep_dev(ws_scan *scan, const float *xyz_dev, size_t n, size_t stride_floats, const float *poses_host, uint32_t k,
+                                 const ws_sweep_t *rule, int32_t map_resolution, size_t *n_out);
+/* The k poses of a sweep from the pose at its end and the motion during it.  Pure host code in double; needs no device.
+ * motion: the sensor's pose at the end of the sweep expressed in its frame at the beginning, T_begin^-1 * T_end (column-major, mm).
+ * poses_out[b] (k x 16, column-major) is the pose at s_b = (b + 0.5) / k:  pose_end * rel(s_b), where
+ *   rotation of rel(s)    = exp((1 - s) * log(R_motion^T))
+ *   translation of rel(s) = (1 - s) * (-R_motion^T * t_motion)
+ * -- slerp and lerp towards the end frame: rel(1) = I, rel(0) = motion^-1 -- rounded to float32 once, at the end.  The logarithm
+ * is taken as axis and angle: axis from the skew part of R_motion^T, angle = atan2(|skew part|, (trace - 1) / 2).  A motion that is
+ * exactly the identity returns pose_end bit for bit in every bin.  WS_ERR_INVALID: k out of range, NULL or non-finite input, a
+ * rotation of more than 90 degrees within the sweep. */
+int ws_sweep_poses(const float pose_end[16], const float motion[16], uint32_t k, float *poses_out);
+
 /* ------------------------------------------------------------------ measurement ---- */
 /* Kernel classes for hipEvent timing (bench.py's roofline leg). */
 #define WS_K_SETUP 0         /* per-ray set-up + direction sort                                    */

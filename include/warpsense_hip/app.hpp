@@ -627,6 +627,11 @@ struct AppParams
   int initial_weight = 0;
   bool async_shift = false; // MappingNode::shift_map_async: the map shift off the scan path
   bool device_shift = false; // MappingNode::shift_map_device: the global map in device memory (takes precedence over async_shift)
+  // de-skewing: false -- every point of a scan is transformed with the one pose of the scan (the reference); true -- "constant
+  // velocity": one pose per time bin of the sweep (ScanPreprocessor::preprocess_sweep), the motion during the sweep taken to be
+  // the pose change between the last two scans (the identity for the first two)
+  bool deskew_constant_velocity = false;
+  uint32_t sweep_bins = 1024; // poses per sweep; also the columns of the default rule (by index, ring-major)
 };
 
 // wall-clock microseconds of the stages of one cloud_callback -- the reference's RuntimeEvaluator forms "preprocess", "tsdf",
@@ -657,12 +662,29 @@ public:
 
   // App::cloud_callback — app.cpp:65-117; `pretransform` stands for imu_acc_.acc_transform(stamp) (identity: no IMU).
   // The map-shift thread's turn (tsdf_mapping.cpp:104-127) runs synchronously at the end.
-  const rm::Matrix4x4f &cloud_callback(const float *cloud_xyz, size_t n, size_t stride_floats, const rm::Matrix4x4f *pretransform = nullptr)
+  // sweep_motion: the sensor's pose at the end of the sweep in its frame at the beginning (mm); with it, or with
+  // AppParams::deskew_constant_velocity, the scan is pre-processed with one pose per time bin, the sweep ending at the current
+  // pose.  sweep: the bin rule (default: by index, ring-major, sweep_bins columns).
+  const rm::Matrix4x4f &cloud_callback(const float *cloud_xyz, size_t n, size_t stride_floats, const rm::Matrix4x4f *pretransform = nullptr,
+                                       const rm::Matrix4x4f *sweep_motion = nullptr, const ws_sweep_t *sweep = nullptr)
   {
     using clk = std::chrono::steady_clock;
     auto us = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
     const clk::time_point t0 = clk::now();
-    const size_t n_pts = pre_.preprocess(cloud_xyz, n, stride_floats, pose_, params_.hot.map_resolution); // App::preprocess :119-148
+    rm::Matrix4x4f guessed;
+    if (!sweep_motion && params_.deskew_constant_velocity)
+    {
+      guessed = last_motion();
+      sweep_motion = &guessed;
+    }
+    size_t n_pts;
+    if (sweep_motion)
+    {
+      const ws_sweep_t rule = sweep ? *sweep : cuda::ScanPreprocessor::by_index(params_.sweep_bins);
+      n_pts = pre_.preprocess_sweep(cloud_xyz, n, stride_floats, sweep_poses(pose_, *sweep_motion, params_.sweep_bins), rule, params_.hot.map_resolution);
+    }
+    else
+      n_pts = pre_.preprocess(cloud_xyz, n, stride_floats, pose_, params_.hot.map_resolution); // App::preprocess :119-148
     const clk::time_point t1 = clk::now();
     if (!initialized_ || distance_m(last_tsdf_pose_, pose_) > 0.3f || shifted_)
     {
@@ -685,6 +707,9 @@ public:
         node_.gpu().registration().register_cloud(node_.gpu().tsdf().device_map(), pre, params_.hot.max_iterations, params_.hot.it_weight_gradient,
                                                   params_.hot.epsilon, params_.hot.map_resolution, &last_iterations_);
     update_pose_estimate(transform);
+    before_last_pose_ = last_pose_;
+    last_pose_ = pose_;
+    ++n_scans_;
     if (global_map_.has_file()) global_map_.write_pose(pose_, 1000.f);
     const clk::time_point t3 = clk::now();
     map_shift();
@@ -712,6 +737,27 @@ public:
       for (int j = 0; j < 3; ++j) pose_.at(i, j) = R[i][j];
       pose_.at(i, 3) += t.at(i, 3);
     }
+  }
+  // the pose change between the last two scans, inv(pose[-2]) * pose[-1] of rigid poses, in double (the identity for the first two)
+  rm::Matrix4x4f last_motion() const
+  {
+    rm::Matrix4x4f m;
+    m.setIdentity();
+    if (n_scans_ < 2) return m;
+    const rm::Matrix4x4f &a = before_last_pose_, &b = last_pose_;
+    for (int i = 0; i < 3; ++i)
+    {
+      for (int j = 0; j < 3; ++j)
+      {
+        double acc = 0.0;
+        for (int k = 0; k < 3; ++k) acc += (double)a.at(k, i) * (double)b.at(k, j);
+        m.at(i, j) = (float)acc;
+      }
+      double t = 0.0;
+      for (int k = 0; k < 3; ++k) t += (double)a.at(k, i) * ((double)b.at(k, 3) - (double)a.at(k, 3));
+      m.at(i, 3) = (float)t;
+    }
+    return m;
   }
   void map_shift()
   {
@@ -766,8 +812,9 @@ private:
   std::unique_ptr<DeviceGlobalMap> device_global_map_; // AppParams::device_shift
   cuda::ScanPreprocessor pre_;
   rm::Matrix4x4f pose_, last_tsdf_pose_, last_shift_pose_;
+  rm::Matrix4x4f last_pose_, before_last_pose_; // pose_ after the last two scans (last_motion)
   bool initialized_ = false, shifted_ = false;
-  int last_iterations_ = 0, n_updates_ = 0, n_shifts_ = 0;
+  int last_iterations_ = 0, n_updates_ = 0, n_shifts_ = 0, n_scans_ = 0;
   size_t last_points_ = 0;
   StageTimes times_;
 };

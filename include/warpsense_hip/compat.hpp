@@ -427,6 +427,34 @@ public:
     WS_CHECK(ws_scan_preprocess(scan_, cloud_xyz, n, stride_floats, &pose.data[0][0], map_resolution, &n_out_));
     return n_out_;
   }
+  // one sensor pose per time bin of the sweep (ws_scan_preprocess_sweep): poses e.g. from warpsense::sweep_poses, the bin of a point
+  // by its column (rule.time_field = -1) or by a time in its record
+  size_t preprocess_sweep(const float *cloud_xyz, size_t n, size_t stride_floats, const std::vector<rmagine::Matrix4x4f> &poses, const ws_sweep_t &rule,
+                          int map_resolution)
+  {
+    WS_CHECK(ws_scan_preprocess_sweep(scan_, cloud_xyz, n, stride_floats, poses.empty() ? nullptr : &poses[0].data[0][0], (uint32_t)poses.size(), &rule,
+                                      map_resolution, &n_out_));
+    return n_out_;
+  }
+  // the rule "by index": `columns` firing columns, ring-major (index = ring * columns + column) or column after column
+  static ws_sweep_t by_index(uint32_t columns, bool ring_major = true)
+  {
+    ws_sweep_t r;
+    r.columns = columns;
+    r.ring_major = ring_major ? 1 : 0;
+    r.time_field = -1;
+    r.t_begin = 0.f;
+    r.t_end = 1.f;
+    return r;
+  }
+  static ws_sweep_t by_time(int time_field, float t_begin = 0.f, float t_end = 1.f)
+  {
+    ws_sweep_t r = by_index(0);
+    r.time_field = time_field;
+    r.t_begin = t_begin;
+    r.t_end = t_end;
+    return r;
+  }
   const int32_t *points_dev() const { return ws_scan_points_dev(scan_); }
   size_t size() const { return n_out_; }
   std::vector<rmagine::Pointi> download() const

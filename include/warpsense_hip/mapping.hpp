@@ -251,4 +251,13 @@ inline long long batch_best(const std::vector<int32_t> &e, const std::vector<int
   WS_CHECK(ws_reg_batch_best(e.data(), c.data(), e.size() < c.size() ? e.size() : c.size(), min_count, &best));
   return (long long)best;
 }
+
+// the k sensor poses of a sweep that ends at pose_end after `motion` (inv(T_begin) * T_end, mm): ws_sweep_poses, host code in double
+inline std::vector<rmagine::Matrix4x4f> sweep_poses(const rmagine::Matrix4x4f &pose_end, const rmagine::Matrix4x4f &motion, uint32_t k)
+{
+  std::vector<rmagine::Matrix4x4f> out(k ? k : 1);
+  WS_CHECK(ws_sweep_poses(&pose_end.data[0][0], &motion.data[0][0], k, &out[0].data[0][0]));
+  out.resize(k);
+  return out;
+}
 } // namespace warpsense

@@ -4,6 +4,7 @@ sliding TSDF map @ 5 cm, one MI355X): sensor clouds in float metres -> device pr
 
     python tools/replay_stream.py --map 1024 --scans 30 [--h5 /tmp/stream.h5] [--async-shift | --device-global-map] [--surface-ply DIR [--surface-every N]] [--mesh-ply DIR]
                                    [--raycast-ply DIR] [--distance-npy DIR [--distance-m M]]
+                                   [--moving-sweeps] [--deskew]
 
 Prints one JSON line: scans/s over the stream and the mean per-stage times (the reference's RuntimeEvaluator
 forms "preprocess", "tsdf", "registration", "total")."""
@@ -79,6 +80,10 @@ def main():
     ap.add_argument("--kidnap-offset", type=float, nargs=2, default=(0.8, -0.4), metavar=("DX", "DY"), help="... offset of the wrong pose in metres")
     ap.add_argument("--kidnap-yaw", type=float, default=20.0, metavar="DEG", help="... and its yaw error")
     ap.add_argument("--kidnap-lattice", type=float, nargs=4, default=(1.2, 0.4, 30.0, 10.0), metavar=("RADIUS_M", "STEP_M", "YAW_RANGE", "YAW_STEP"))
+    ap.add_argument("--moving-sweeps", action="store_true", help="the sensor moves WHILE it turns: scan k is a sweep taken between the true poses of "
+                    "scan k - 1 and scan k (synthetic.os1_128_sweep; the first one stands), instead of a snapshot from the pose of scan k")
+    ap.add_argument("--deskew", action="store_true", help="App(deskew='constant-velocity'): one pose per firing column, the motion during a sweep "
+                    "taken from the last two registered poses")
     args = ap.parse_args()
     import warpsense_amd as W
     from warpsense_amd import synthetic as S
@@ -87,12 +92,19 @@ def main():
     params = W.Params(W.MapParams(resolution=args.res, max_distance=1.0, max_weight=10, size=(size_m, size_m, size_m), shift=args.shift),
                       W.RegistrationParams(200, 0.1, 0.03))
     t0 = time.perf_counter()
-    app = W.App(params, args.h5, async_shift=args.async_shift, shift="device" if args.device_global_map else None)
+    app = W.App(params, args.h5, async_shift=args.async_shift, shift="device" if args.device_global_map else None,
+                deskew="constant-velocity" if args.deskew else None)
     t_setup = time.perf_counter() - t0
     he = tuple(1000.0 * r for r in args.room)
     clouds = []
     for k in range(args.scans):
         sensor = np.array([1000.0 * args.step * k, 500.0 * args.step * k, 0.0])
+        if args.moving_sweeps:
+            T0, T1 = np.eye(4), np.eye(4)
+            T0[:3, 3] = (1000.0 * args.step * max(k - 1, 0), 500.0 * args.step * max(k - 1, 0), 0.0)
+            T1[:3, 3] = sensor
+            clouds.append(S.os1_128_sweep(T0, T1, half_extents_mm=he, seed=1000 + k))
+            continue
         pts = S.os1_128_scan(sensor_mm=tuple(sensor), half_extents_mm=he, seed=1000 + k)
         clouds.append(((pts.astype(np.float64) - sensor) / 1000.0).astype(np.float32))
     W.pause()
@@ -161,8 +173,10 @@ def main():
     t3 = time.perf_counter()
     app.terminate()
     t4 = time.perf_counter()
+    print(f"final position error against the ground truth: {float(np.linalg.norm(app.poses[-1][:3, 3] - true_last)):.1f} mm", file=sys.stderr)
     print(json.dumps({"workload": f"{args.scans} synthetic OS1-128 scans (131072 pts), {args.map}^3 sliding map @ {args.res} mm, App replay",
-                      "args": {"step_m": args.step, "shift_m": args.shift, "room_m": list(args.room), "h5": bool(args.h5), "hz": args.hz},
+                      "args": {"step_m": args.step, "shift_m": args.shift, "room_m": list(args.room), "h5": bool(args.h5), "hz": args.hz, "moving_sweeps": bool(args.moving_sweeps),
+                               "deskew": bool(args.deskew)},
                       "scans_per_s": args.scans / (t2 - t1), "stream_s": t2 - t1, "callback_busy_s": busy, "setup_s": t_setup, **stages,
                       "tsdf_updates": app.n_updates, "map_shifts": app.n_shifts, "async_shift": bool(args.async_shift), "device_global_map": bool(args.device_global_map),
                       "slowest_scan_ms": 1000.0 * float(max(t["total"] for t in app.timings[2:])),

@@ -28,7 +28,7 @@ EXPORTS = [
     "ws_reg_prepare_dev", "ws_reg_points_dev", "ws_reg_iterate", "ws_register_cloud", "ws_reg_begin", "ws_reg_accumulate_dev",
     "ws_reg_solve_dev", "ws_reg_iterate_shard_dev", "ws_reg_poll", "ws_reg_peer_mailbox", "ws_reg_peer_connect", "ws_reg_peer_connect_local",
     "ws_reg_peer_disconnect", "ws_reg_peer_reset", "ws_register_cloud_peers", "ws_reg_set_loop", "ws_debug_solve6", "ws_debug_reg_stall", "ws_debug_reg_server", "ws_debug_reg_mail_selftest", "ws_debug_reg_sums", "ws_debug_block_stats", "ws_scan_create", "ws_scan_destroy", "ws_scan_preprocess",
-    "ws_scan_preprocess_dev", "ws_scan_points_dev", "ws_scan_download", "ws_prof_enable", "ws_prof_read", "ws_prof_reset",
+    "ws_scan_preprocess_dev", "ws_scan_points_dev", "ws_scan_download", "ws_scan_preprocess_sweep", "ws_scan_preprocess_sweep_dev", "ws_sweep_poses", "ws_prof_enable", "ws_prof_read", "ws_prof_reset",
     "ws_map_surface", "ws_map_surface_records_dev", "ws_map_surface_marker_dev", "ws_map_surface_download", "ws_debug_surface_timing",
     "ws_map_mesh", "ws_map_mesh_vertices_dev", "ws_map_mesh_faces_dev", "ws_map_mesh_download", "ws_debug_mesh_timing",
     "ws_map_raycast", "ws_map_raycast_dev", "ws_map_raycast_records_dev", "ws_map_raycast_gradient_dev", "ws_map_raycast_download", "ws_debug_raycast_timing",
@@ -104,6 +104,12 @@ class ShiftPlan(C.Structure):
                 ("pos", C.c_int32 * 3), ("offset", C.c_int32 * 3)]
 
 
+class Sweep(C.Structure):
+    """ws_sweep_t: the rule that gives every point of a sweep its time bin"""
+    _fields_ = [("columns", C.c_uint32), ("ring_major", C.c_int32), ("time_field", C.c_int32), ("t_begin", C.c_float), ("t_end", C.c_float)]
+
+
+WS_SWEEP_MAX_BINS = 4096
 _lib = None
 
 
@@ -209,6 +215,9 @@ def load() -> C.CDLL:
     L.ws_scan_points_dev.argtypes = [vp]
     L.ws_scan_points_dev.restype = vp
     L.ws_scan_download.argtypes = [vp, vp, sz, P(sz)]
+    L.ws_scan_preprocess_sweep.argtypes = [vp, vp, sz, sz, vp, u32, P(Sweep), i32, P(sz)]
+    L.ws_scan_preprocess_sweep_dev.argtypes = [vp, vp, sz, sz, vp, u32, P(Sweep), i32, P(sz)]
+    L.ws_sweep_poses.argtypes = [vp, vp, u32, vp]
     L.ws_reg_accumulate_dev.argtypes = [vp, vp, i32, u32, sz, sz, vp]
     L.ws_reg_solve_dev.argtypes = [vp, vp]
     L.ws_reg_poll.argtypes = [vp, P(i32), P(i32), vp]

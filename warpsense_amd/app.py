@@ -17,11 +17,15 @@ import time
 
 import numpy as np
 
-from .api import (DeviceGlobalMap, GlobalMap, LocalMap, Params, ScanPreprocessor, TSDFRegistration, to_map)
+from .api import (DeviceGlobalMap, GlobalMap, LocalMap, Params, ScanPreprocessor, TSDFRegistration, sweep_poses, to_map)
 
 
 class App:
-    def __init__(self, params: Params, filename: str | None = None, ctx=None, max_points: int = 128 * 1024, async_shift: bool = False, shift: str | None = None):
+    def __init__(self, params: Params, filename: str | None = None, ctx=None, max_points: int = 128 * 1024, async_shift: bool = False, shift: str | None = None,
+                 deskew: str | None = None, sweep_bins: int | None = None):
+        # deskew: None -- every point of a scan is transformed with the one pose of the scan (the reference); "constant-velocity" --
+        # one pose per time bin of the sweep (ScanPreprocessor.preprocess_sweep, `sweep_bins` of them, default 1024), the motion
+        # during the sweep taken to be the pose change between the last two scans
         # shift: "sync" (TSDFMapping.shift_map), "async" (shift_map_async, what async_shift=True selects) or "device": the global map
         # lives in device memory (DeviceGlobalMap), shifts are device-to-device copies (shift_map_device) and terminate() writes the
         # host global map and its file from the chunks
@@ -29,6 +33,10 @@ class App:
         # the leaving slabs are filed into the global map by a worker thread (same maps and poses as the synchronous route)
         if shift not in (None, "sync", "async", "device"):
             raise ValueError(f"App: shift must be 'sync', 'async' or 'device', not {shift!r}")
+        if deskew not in (None, "constant-velocity"):
+            raise ValueError(f"App: deskew must be None or 'constant-velocity', not {deskew!r}")
+        self.deskew_ = deskew
+        self.sweep_bins_ = 1024 if sweep_bins is None else int(sweep_bins)
         self.async_shift_ = bool(async_shift) if shift is None else shift == "async"
         self.device_shift_ = shift == "device"
         m = params.map
@@ -51,9 +59,29 @@ class App:
         self.n_updates = 0
         self.n_shifts = 0
 
-    def preprocess(self, cloud):
-        """App::preprocess (app.cpp:119-148) -> points resident on the device."""
-        return self.pre_.preprocess(cloud, self.pose_, self.params_.map.resolution)
+    def preprocess(self, cloud, sweep_motion=None, sweep=None):
+        """App::preprocess (app.cpp:119-148) -> points resident on the device.  With sweep_motion (the sensor's pose at the end of
+        the sweep in its frame at the beginning, 4x4, mm) or deskew="constant-velocity": one pose per time bin, the sweep ending at
+        the current pose.  sweep: the bin rule, a dict of preprocess_sweep's keywords (columns, ring_major, time_field, t_begin,
+        t_end); default by index, ring-major, `sweep_bins` columns."""
+        if sweep_motion is None and self.deskew_ == "constant-velocity":
+            sweep_motion = self.last_motion()
+        if sweep_motion is None:
+            return self.pre_.preprocess(cloud, self.pose_, self.params_.map.resolution)
+        rule = {"columns": self.sweep_bins_, "ring_major": True} if sweep is None else dict(sweep)
+        return self.pre_.preprocess_sweep(cloud, sweep_poses(self.pose_, sweep_motion, self.sweep_bins_), self.params_.map.resolution, **rule)
+
+    def last_motion(self):
+        """the pose change between the last two scans, inv(pose[-2]) @ pose[-1] (the identity for the first two scans)"""
+        if len(self.poses) < 2:
+            return np.eye(4, dtype=np.float32)
+        a, b = self.poses[-2].astype(np.float64), self.poses[-1].astype(np.float64)
+        m = np.eye(4)
+        for i in range(3):  # R_a^T R_b and R_a^T (t_b - t_a), summed in index order (same as include/warpsense_hip/app.hpp)
+            for j in range(3):
+                m[i, j] = sum(a[k, i] * b[k, j] for k in range(3))
+            m[i, 3] = sum(a[k, i] * (b[k, 3] - a[k, 3]) for k in range(3))
+        return m.astype(np.float32)
 
     def update_pose_estimate(self, transform):
         """app.cpp:172-176."""
@@ -83,11 +111,11 @@ class App:
             self.shifted_ = True
             self.n_shifts += 1
 
-    def cloud_callback(self, cloud, pretransform=None):
-        """App::cloud_callback (app.cpp:65-117)."""
+    def cloud_callback(self, cloud, pretransform=None, sweep_motion=None, sweep=None):
+        """App::cloud_callback (app.cpp:65-117); sweep_motion / sweep: see preprocess."""
         t = {}
         t0 = time.perf_counter()
-        scan_points = self.preprocess(cloud)
+        scan_points = self.preprocess(cloud, sweep_motion, sweep)
         t["preprocess"] = time.perf_counter() - t0
         distance_tsdf = np.linalg.norm(self.last_tsdf_pose_[:3, 3] / np.float32(1000) - self.pose_[:3, 3] / np.float32(1000))
         if not self.initialized_ or distance_tsdf > 0.3 or self.shifted_:

@@ -45,52 +45,94 @@ __device__ __forceinline__ uint64_t pre_mix(uint64_t x)
   return x;
 }
 
+// app.cpp:129-132 compares the floats with the double literal 0.3; non-finite input (undefined in the reference:
+// float -> int conversion of NaN) is dropped
+__device__ __forceinline__ bool pre_wanted(float x, float y, float z)
+{
+  const bool finite = isfinite(x) && isfinite(y) && isfinite(z);
+  const bool near = (double)x < 0.3 && (double)y < 0.3 && (double)z < 0.3;
+  return finite && !near;
+}
+
+// snap, transform with the fixed-point matrix M (column-major, rows 0..2 used) and insert; returns the hash slot of the point
+// or PRE_NONE when a coordinate is out of range.  M is a.M (kernel arguments) or one row of the sweep's pose table (registers)
+__device__ __forceinline__ uint32_t pre_transform_insert(const PreArgs &a, uint32_t i, float x, float y, float z, const int32_t *M)
+{
+  const float res = (float)a.res;
+  const float half = (float)(a.res / 2);
+  // Pointf(x * 1000.f, ...); (int)(floor(p / res) * res + res / 2), all in float (app.cpp:134-140)
+  const int32_t cx = (int32_t)(floorf((x * 1000.f) / res) * res + half);
+  const int32_t cy = (int32_t)(floorf((y * 1000.f) / res) * res + half);
+  const int32_t cz = (int32_t)(floorf((z * 1000.f) / res) * res + half);
+  int32_t q[3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+    q[r] = wadd(wadd(wadd(wmul(M[0 * 4 + r], cx), wmul(M[1 * 4 + r], cy)), wmul(M[2 * 4 + r], cz)), M[3 * 4 + r]) / MATRIX_RESOLUTION;
+  a.tmp[3 * (size_t)i + 0] = q[0];
+  a.tmp[3 * (size_t)i + 1] = q[1];
+  a.tmp[3 * (size_t)i + 2] = q[2];
+  bool in_range = true;
+#pragma unroll
+  for (int r = 0; r < 3; ++r) in_range = in_range && q[r] > -PRE_COORD_LIMIT && q[r] < PRE_COORD_LIMIT;
+  if (!in_range)
+  {
+    atomicOr(&a.counters[1], 1u);
+    return PRE_NONE;
+  }
+  const uint64_t key = ((uint64_t)(uint32_t)(q[0] + PRE_COORD_LIMIT) << 42) | ((uint64_t)(uint32_t)(q[1] + PRE_COORD_LIMIT) << 21) |
+                       (uint64_t)(uint32_t)(q[2] + PRE_COORD_LIMIT);
+  uint32_t h = (uint32_t)pre_mix(key) & a.mask;
+  for (;;)
+  {
+    const uint64_t prev = atomicCAS((unsigned long long *)&a.keys[h], (unsigned long long)PRE_EMPTY, (unsigned long long)key);
+    if (prev == PRE_EMPTY || prev == key) break;
+    h = (h + 1) & a.mask; // the table has at least twice as many slots as points
+  }
+  atomicMin(&a.first[h], i);
+  return h;
+}
+
 __global__ __launch_bounds__(256) void pre_insert_kernel(PreArgs a)
 {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i >= a.n) return;
   const float x = a.xyz[(size_t)i * a.stride + 0], y = a.xyz[(size_t)i * a.stride + 1], z = a.xyz[(size_t)i * a.stride + 2];
   uint32_t slot = PRE_NONE;
-  // app.cpp:129-132 compares the floats with the double literal 0.3; non-finite input (undefined in the reference:
-  // float -> int conversion of NaN) is dropped
-  const bool finite = isfinite(x) && isfinite(y) && isfinite(z);
-  const bool near = (double)x < 0.3 && (double)y < 0.3 && (double)z < 0.3;
-  if (finite && !near)
+  if (pre_wanted(x, y, z)) slot = pre_transform_insert(a, i, x, y, z, a.M);
+  a.slot_of[i] = slot;
+}
+
+// The sweep form (ws_scan_preprocess_sweep, warpsense_hip.h): the same pass with one pose per time bin.  A lane computes the bin
+// of its point -- from the point's index, or from a time in its record -- fetches that bin's row of the table (16 int32 =
+// 64 bytes, four 16-byte loads; the table is at most 4096 rows = 256 KB and stays in L2) and goes on as above.  A column-major
+// cloud gives the lanes of a wave one or two distinct rows, a ring-major one 64 distinct rows: the loads do not care.
+__global__ __launch_bounds__(256) void pre_insert_sweep_kernel(PreArgs a, PreSweep w)
+{
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= a.n) return;
+  const float *p = a.xyz + (size_t)i * a.stride;
+  const float x = p[0], y = p[1], z = p[2];
+  uint32_t b = 0;
+  bool timed = true;
+  if (w.time_field >= 0)
   {
-    const float res = (float)a.res;
-    const float half = (float)(a.res / 2);
-    // Pointf(x * 1000.f, ...); (int)(floor(p / res) * res + res / 2), all in float (app.cpp:134-140)
-    const int32_t cx = (int32_t)(floorf((x * 1000.f) / res) * res + half);
-    const int32_t cy = (int32_t)(floorf((y * 1000.f) / res) * res + half);
-    const int32_t cz = (int32_t)(floorf((z * 1000.f) / res) * res + half);
-    int32_t q[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-      q[r] = wadd(wadd(wadd(wmul(a.M[0 * 4 + r], cx), wmul(a.M[1 * 4 + r], cy)), wmul(a.M[2 * 4 + r], cz)), a.M[3 * 4 + r]) / MATRIX_RESOLUTION;
-    a.tmp[3 * (size_t)i + 0] = q[0];
-    a.tmp[3 * (size_t)i + 1] = q[1];
-    a.tmp[3 * (size_t)i + 2] = q[2];
-    bool in_range = true;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) in_range = in_range && q[r] > -PRE_COORD_LIMIT && q[r] < PRE_COORD_LIMIT;
-    if (!in_range)
-    {
-      atomicOr(&a.counters[1], 1u);
-    }
-    else
-    {
-      const uint64_t key = ((uint64_t)(uint32_t)(q[0] + PRE_COORD_LIMIT) << 42) | ((uint64_t)(uint32_t)(q[1] + PRE_COORD_LIMIT) << 21) |
-                           (uint64_t)(uint32_t)(q[2] + PRE_COORD_LIMIT);
-      uint32_t h = (uint32_t)pre_mix(key) & a.mask;
-      for (;;)
-      {
-        const uint64_t prev = atomicCAS((unsigned long long *)&a.keys[h], (unsigned long long)PRE_EMPTY, (unsigned long long)key);
-        if (prev == PRE_EMPTY || prev == key) break;
-        h = (h + 1) & a.mask; // the table has at least twice as many slots as points
-      }
-      atomicMin(&a.first[h], i);
-      slot = h;
-    }
+    const float s = (p[w.time_field] - w.t_begin) / (w.t_end - w.t_begin);
+    const float v = s * (float)w.k;
+    timed = !isnan(s);
+    b = v >= (float)w.k ? w.k - 1u : (v > 0.f ? (uint32_t)v : 0u);
+  }
+  else
+  {
+    const uint32_t col = w.ring_major ? i % w.columns : i / w.rows;
+    b = (uint32_t)((uint64_t)col * w.k / w.columns);
+  }
+  uint32_t slot = PRE_NONE;
+  if (timed && pre_wanted(x, y, z))
+  {
+    const int4 *row = reinterpret_cast<const int4 *>(w.table + 16 * (size_t)b);
+    const int4 c0 = row[0], c1 = row[1], c2 = row[2], c3 = row[3];
+    const int32_t M[16] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w, c2.x, c2.y, c2.z, c2.w, c3.x, c3.y, c3.z, c3.w};
+    slot = pre_transform_insert(a, i, x, y, z, M);
   }
   a.slot_of[i] = slot;
 }
@@ -169,7 +211,8 @@ size_t pre_table_slots(size_t max_points)
   return s;
 }
 
-int launch_scan_preprocess(ws_scan *sc, const float *xyz_dev, size_t n, size_t stride, const int32_t M[16], int32_t res)
+// `sweep` == nullptr: every point with M.  Otherwise M is not read and every point takes its bin's row of sweep->table
+int launch_scan_preprocess(ws_scan *sc, const float *xyz_dev, size_t n, size_t stride, const int32_t M[16], int32_t res, const PreSweep *sweep)
 {
   hipStream_t s = sc->ctx->stream;
   WS_HIP(hipMemsetAsync(sc->counters.p, 0, 2 * sizeof(uint32_t), s));
@@ -181,7 +224,7 @@ int launch_scan_preprocess(ws_scan *sc, const float *xyz_dev, size_t n, size_t s
   a.xyz = xyz_dev;
   a.n = (uint32_t)n;
   a.stride = (uint32_t)stride;
-  for (int k = 0; k < 16; ++k) a.M[k] = M[k];
+  for (int k = 0; k < 16; ++k) a.M[k] = sweep ? 0 : M[k];
   a.res = res;
   a.tmp = sc->tmp.as<int32_t>();
   a.slot_of = sc->slot_of.as<uint32_t>();
@@ -193,7 +236,10 @@ int launch_scan_preprocess(ws_scan *sc, const float *xyz_dev, size_t n, size_t s
   a.counters = sc->counters.as<uint32_t>();
   a.out = sc->out.as<int32_t>();
   const uint32_t blocks = (uint32_t)((n + 255) / 256);
-  hipLaunchKernelGGL(pre_insert_kernel, dim3(blocks), dim3(256), 0, s, a);
+  if (sweep)
+    hipLaunchKernelGGL(pre_insert_sweep_kernel, dim3(blocks), dim3(256), 0, s, a, *sweep);
+  else
+    hipLaunchKernelGGL(pre_insert_kernel, dim3(blocks), dim3(256), 0, s, a);
   hipLaunchKernelGGL(pre_count_kernel, dim3(blocks), dim3(256), 0, s, a);
   hipLaunchKernelGGL(pre_scan_kernel, dim3(1), dim3(1024), 0, s, a, blocks, sc->host_count.dev_as<uint32_t>());
   hipLaunchKernelGGL(pre_scatter_kernel, dim3(blocks), dim3(256), 0, s, a);

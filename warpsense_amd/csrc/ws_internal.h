@@ -649,11 +649,14 @@ struct ws_scan
   ws::DevBuf wg_count, wg_off;      // uint32 [workgroups]
   ws::DevBuf counters;              // uint32
   ws::HostBlock host_count;         // uint32, mapped
+  ws::DevBuf sweep_table;           // int32 [WS_SWEEP_MAX_BINS][16]: the pose table of a sweep, allocated by the first sweep call
+  ws::HostBlock sweep_stage;        // ... and the pinned block it is uploaded from
   size_t n_out = 0;
   void release()
   {
-    for (ws::DevBuf *b : {&in_stage, &tmp, &out, &slot_of, &keys, &first, &wg_count, &wg_off, &counters}) b->release();
+    for (ws::DevBuf *b : {&in_stage, &tmp, &out, &slot_of, &keys, &first, &wg_count, &wg_off, &counters, &sweep_table}) b->release();
     host_count.release();
+    sweep_stage.release();
   }
 };
 
@@ -710,7 +713,18 @@ void reg_server_mail_stop(void *mail, uint32_t launch_id);
 int reg_server_mail_answer(const void *mail, uint32_t seq, int64_t sums[44]);
 int reg_server_mail_selftest();
 uint32_t reg_server_mail_exited(const void *mail);
-int launch_scan_preprocess(ws_scan *sc, const float *xyz_dev, size_t n, size_t stride, const int32_t M[16], int32_t res);
+// the bin rule of a sweep (ws_sweep_t, checked by api.hip) and its pose table on the device
+struct PreSweep
+{
+  const int32_t *table; // [k][16] to_int_mat(poses[b]), column-major, one 64-byte row per bin
+  uint32_t k;
+  uint32_t columns; // by index: bins follow the column of a point ...
+  uint32_t rows;    // ... n / columns
+  int32_t ring_major;
+  int32_t time_field; // >= 0: by the float at this index of the point's record
+  float t_begin, t_end;
+};
+int launch_scan_preprocess(ws_scan *sc, const float *xyz_dev, size_t n, size_t stride, const int32_t M[16], int32_t res, const PreSweep *sweep = nullptr);
 size_t pre_table_slots(size_t max_points);
 int launch_reg_loop(ws_reg *r, const ws_map *m, int32_t res, uint32_t flags, const ws::GnCore &init, bool peers = false, size_t first = 0, size_t count = 0);
 // reg_batch_kernel: k workgroups, one Gauss-Newton loop each, from the start records in ws_reg::batch into its result records

@@ -71,6 +71,50 @@ def os1_128_scan(sensor_mm=(0.0, 0.0, 0.0), rings: int = RINGS, azimuths: int = 
     return np.trunc(pts).astype(np.int32)
 
 
+def sweep_pose_at(pose_begin, pose_end, s) -> np.ndarray:
+    """The sensor pose at the fraction s of a sweep from pose_begin (s = 0) to pose_end (s = 1), in double, with the interpolation
+    of ws_sweep_poses (include/warpsense_hip.h): pose_end @ rel(s), the rotation of rel(s) = exp((1 - s) log(R_motion^T)), its
+    translation (1 - s) (-R_motion^T t_motion), motion = inv(pose_begin) @ pose_end."""
+    B, E = np.asarray(pose_begin, dtype=np.float64), np.asarray(pose_end, dtype=np.float64)
+    motion = np.linalg.inv(B) @ E
+    Q = motion[:3, :3].T
+    u = -Q @ motion[:3, 3]
+    v = 0.5 * np.array([Q[2, 1] - Q[1, 2], Q[0, 2] - Q[2, 0], Q[1, 0] - Q[0, 1]])
+    sn = float(np.linalg.norm(v))
+    angle = np.arctan2(sn, 0.5 * (np.trace(Q) - 1.0))
+    a = v / sn if sn > 0.0 else np.zeros(3)
+    K = np.array([[0.0, -a[2], a[1]], [a[2], 0.0, -a[0]], [-a[1], a[0], 0.0]])
+    w = 1.0 - float(s)
+    rel = np.eye(4)
+    rel[:3, :3] = np.eye(3) + np.sin(w * angle) * K + (1.0 - np.cos(w * angle)) * (K @ K)
+    rel[:3, 3] = w * u
+    return E @ rel
+
+
+def os1_128_sweep(pose_begin_mm, pose_end_mm, rings: int = RINGS, azimuths: int = AZIMUTHS, half_extents_mm=HALF_EXTENTS_MM, seed: int = 12345,
+                  noise: bool = True, with_time: bool = False) -> np.ndarray:
+    """One sweep of the pattern taken while the sensor moves from pose_begin_mm to pose_end_mm (4x4, map frame, mm): azimuth column
+    j is cast from the pose at s = (j + 0.5) / azimuths (sweep_pose_at).  Returns the cloud as the sensor reports it: (rings *
+    azimuths, 3) float32 METRES, every point in the sensor frame of its own column, ring-major; with_time appends s as a fourth
+    float.  The range noise is that of os1_128_scan (noise=False: none)."""
+    d = os1_128_dirs(rings, azimuths).reshape(rings, azimuths, 3)
+    he = np.asarray(half_extents_mm, dtype=np.float64)
+    s = (np.arange(azimuths, dtype=np.float64) + 0.5) / azimuths
+    T = np.stack([sweep_pose_at(pose_begin_mm, pose_end_mm, sj) for sj in s])  # (azimuths, 4, 4)
+    dw = np.einsum("jab,ijb->ija", T[:, :3, :3], d)  # ray directions in the map frame
+    o = T[None, :, :3, 3]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t_hi = (he - o) / dw
+        t_lo = (-he - o) / dw
+    t = np.where(dw > 0, t_hi, np.where(dw < 0, t_lo, np.inf)).min(axis=2)
+    if noise:
+        t = t + lcg_noise(rings * azimuths, seed).astype(np.float64).reshape(rings, azimuths)
+    pts = (t[:, :, None] * d / 1000.0).reshape(-1, 3)
+    if with_time:
+        pts = np.concatenate([pts, np.broadcast_to(s[None, :], (rings, azimuths)).reshape(-1, 1)], axis=1)
+    return pts.astype(np.float32)
+
+
 def perturbation(tx_mm: float = 100.0, ty_mm: float = 100.0, tz_mm: float = 0.0, rz_deg: float = 5.0) -> np.ndarray:
     """The known SE(3) of test/pcd_registration.cpp:30-34 as a 4x4 float32 (row-major numpy) matrix."""
     a = np.deg2rad(rz_deg)
