@@ -383,6 +383,41 @@ int ws_store_chunks_of_box(const int32_t lo[3], const int32_t hi[3], int32_t *ke
  * last save_box / load_box / shift on the store (summed over the axes of a shift) */
 int ws_debug_store_timing(ws_store *st, int32_t enable, float ms_out[2]);
 
+/* The mesh of the store: the surface nets of ws_map_mesh over the chunks of the global map, wherever they lie -- the mesh of the
+ * whole run, not of the window -- on the device, without a chunk leaving HBM.
+ *   field: a voxel of a present chunk holds that chunk's entry.  A voxel of an absent chunk is NOT VALID, whatever fill_entry is,
+ *     and is not inside.  Everything else is word for word the rule set of ws_map_mesh applied to that field: valid / inside and
+ *     WS_MESH_ANY_WEIGHT, cells, the crossing offset o, the vertex as the floor mean of its crossings, the weight word, the face
+ *     orientation, the four-valid-cells condition of a quad, the 16-byte vertex record and the 12-byte face record.
+ *   box: inclusive world voxels [lo, hi]; it need not lie in any window.  Both NULL: the bounding box of the present chunks,
+ *     64 kmin .. 64 kmax + 63 per axis.  Exactly one NULL, or hi < lo: WS_ERR_INVALID.  Voxels outside the box are not valid; the
+ *     cell range is lo .. hi - 1.  A box one voxel thick along an axis, an empty store and a box that meets no present chunk are
+ *     WS_OK with zero vertices and zero faces.
+ *   order: vertices by ascending cell (x, y, z), z fastest; faces by ascending owner voxel (x, y, z), z fastest, then axis 0, 1, 2,
+ *     the two triangles of a quad adjacent -- over the whole box, across chunk borders.  Consequence: if a window holds the same
+ *     voxels as the store inside a box, and fill_entry has weight 0 (so that what ws_store_load_box writes for an absent chunk is
+ *     not valid either), ws_map_mesh on that window and box returns the same bytes.
+ *   map_resolution: the store does not know the map's resolution, the caller passes it (mm per voxel); <= 0: WS_ERR_INVALID.
+ *   WS_ERR_RANGE, as for ws_map_mesh: (|coordinate| + 1) res of a corner of the box does not fit int32 (with the default box this
+ *     is decided on the bounding box), or more than 2^32 - 1 vertices; also a box that overlaps 2^19 present chunks or more (512 GB
+ *     of voxels).  Nothing is launched then, and the last result stays.  Unknown flag bits: WS_ERR_INVALID.
+ *   ordering: the work is stream-ordered behind every save, load and shift already enqueued on the store's context; the call
+ *     synchronises (the two counts come back), is read-only on the chunks and is serialised with the other store calls by the
+ *     store's mutex.
+ *   result buffers: they belong to the store, grow on demand and are not allocated before the first call; they stay valid until
+ *     the next ws_store_mesh on the store -- later saves, loads, shifts and drops leave them untouched -- and are destroyed with
+ *     it.  Every output write is bounded by the buffers' capacities.
+ *   cost: scratch and work follow the number of present chunks the box overlaps (4096 words of 64 voxels per chunk, 29 bytes of
+ *     scratch per word: 119 KB per chunk, plus 140 bytes of tables), never the volume of the box: three chunks a million voxels
+ *     apart cost three chunks, and nothing is refused because the bounding box is large. */
+int ws_store_mesh(ws_store *st, const int32_t lo[3], const int32_t hi[3], int32_t map_resolution, uint32_t flags, size_t *n_vertices, size_t *n_faces);
+const void *ws_store_mesh_vertices_dev(const ws_store *st, size_t *n);  /* device memory, n x 16 bytes; NULL when n == 0 */
+const uint32_t *ws_store_mesh_faces_dev(const ws_store *st, size_t *n); /* device memory, n x 3 uint32; NULL when n == 0 */
+/* copies at most cap_vertices vertices and cap_faces faces (prefixes) and always reports the totals; either host pointer may be NULL */
+int ws_store_mesh_download(ws_store *st, void *vertices_host, uint32_t *faces_host, size_t cap_vertices, size_t cap_faces, size_t *n_vertices, size_t *n_faces);
+/* Measurement entry, as ws_debug_mesh_timing: ms_out receives the device time of the count passes, the scan and the emit passes */
+int ws_debug_store_mesh_timing(ws_store *st, int32_t enable, float ms_out[3]);
+
 /* ------------------------------------------------------------------ TSDF update ---- */
 /* TSDFCuda::update_tsdf(scan_points, scanner_pos, up) — update_tsdf.cu:143-166.
  * xyz_host: n x 3 int32 (rmagine::Pointi AoS); scanner_pos in voxel units, up scaled by 32768.

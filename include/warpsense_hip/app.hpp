@@ -328,6 +328,11 @@ public:
 private:
   ws_store *store_ = nullptr;
 };
+// the mesh of the device global map (visualization.hpp, ws_store_mesh)
+inline SurfaceMesh global_map_mesh(DeviceGlobalMap &g, int resolution, bool any_weight = false, const rm::Pointi *lo = nullptr, const rm::Pointi *hi = nullptr)
+{
+  return global_map_mesh(g.handle(), resolution, any_weight, lo, hi);
+}
 
 // ---------------------------------------------------------------------------------------------------- LocalMap
 // The in-memory state of HDF5LocalMap (hdf5_local_map.cpp:5-20): odd sizes, offset = size / 2, default-filled.
@@ -601,6 +606,17 @@ public:
       local_map_.global_map().save_box(a, b, slab);
     }
     local_map_.global_map().write_back();
+  }
+  // The mesh of everything the run has seen: the window into the device chunks (the first step of write_back, with its capacity
+  // refusals), then the mesh of the store -- nothing leaves the device but the mesh
+  SurfaceMesh global_mesh(bool any_weight = false, const rm::Pointi *lo = nullptr, const rm::Pointi *hi = nullptr)
+  {
+    if (!device_global_map_) throw std::logic_error("global_mesh: no DeviceGlobalMap attached");
+    wait_shift();
+    rm::Pointi wlo, whi;
+    local_map_.window(wlo, whi);
+    WS_CHECK(ws_store_save_box(device_global_map_->handle(), gpu_.tsdf().handle(), WS_MAP_AVG, &wlo.x, &whi.x));
+    return global_map_mesh(*device_global_map_, params_.map_resolution, any_weight, lo, hi);
   }
   // the reference's route, kept for comparison: whole window to the host array of the local map
   void download() { gpu_.tsdf().avg_map().to_host(view_); }

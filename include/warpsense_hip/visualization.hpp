@@ -2,6 +2,7 @@
 //
 //   local_map_cloud      publish_local_map           map.h:14-121    the surface cloud of a DEVICE map, over ws_map_surface
 //   local_map_mesh       (no counterpart: the reference sends the user to an offline mesher)   a triangle mesh, over ws_map_mesh
+//   global_map_mesh      (no counterpart)                                                     the mesh of the device global map, over ws_store_mesh
 //   local_map_raycast    (no counterpart: the reference leaves all viewing to RViz)            a predicted scan, over ws_map_raycast
 //   local_map_distance   (no counterpart: the reference has no distance field)                   a cost map, over ws_map_distance
 //   local_map_skeleton   publish_local_map_skeleton  map.h:175-227   the 24 end points of the window's line list (host only)
@@ -77,6 +78,22 @@ inline SurfaceMesh local_map_mesh(cuda::TSDFCuda &tsdf, int which = WS_MAP_AVG, 
   out.faces.resize(nf);
   size_t gv = 0, gf = 0;
   WS_CHECK(ws_map_mesh_download(tsdf.handle(), nv ? out.vertices.data() : nullptr, nf ? &out.faces.data()->v[0] : nullptr, nv, nf, &gv, &gf));
+  return out;
+}
+
+// The mesh of the global map in device memory (the rules: warpsense_hip.h at ws_store_mesh): everything the store's chunks hold inside
+// the inclusive world-voxel box [lo, hi] (both nullptr: the bounding box of the present chunks), in the order of local_map_mesh across
+// chunk borders.  resolution: the map's, mm per voxel.  (app.hpp adds the overload that takes a DeviceGlobalMap.)
+inline SurfaceMesh global_map_mesh(ws_store *store, int resolution, bool any_weight = false, const rmagine::Pointi *lo = nullptr,
+                                   const rmagine::Pointi *hi = nullptr)
+{
+  SurfaceMesh out;
+  size_t nv = 0, nf = 0;
+  WS_CHECK(ws_store_mesh(store, lo ? &lo->x : nullptr, hi ? &hi->x : nullptr, resolution, any_weight ? WS_MESH_ANY_WEIGHT : WS_MESH_DEFAULT, &nv, &nf));
+  out.vertices.resize(nv);
+  out.faces.resize(nf);
+  size_t gv = 0, gf = 0;
+  WS_CHECK(ws_store_mesh_download(store, nv ? out.vertices.data() : nullptr, nf ? &out.faces.data()->v[0] : nullptr, nv, nf, &gv, &gf));
   return out;
 }
 

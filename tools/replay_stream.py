@@ -66,6 +66,8 @@ def main():
                     "device: TSDFMapping.surface_cloud) as binary little-endian PLY (xyz + rgb) into DIR")
     ap.add_argument("--mesh-ply", default=None, metavar="DIR", help="write a triangle mesh of the window (surface nets on the device: "
                     "TSDFMapping.surface_mesh) as binary little-endian PLY into DIR, after every N-th scan like --surface-ply")
+    ap.add_argument("--global-mesh-ply", default=None, metavar="FILE", help="after the last scan: the mesh of the WHOLE run, window and every chunk that "
+                    "has left it, from the device global map (TSDFMapping.global_mesh, ws_store_mesh); needs --device-global-map")
     ap.add_argument("--raycast-ply", default=None, metavar="DIR", help="after every registered scan: the ray cast of the map from the registered pose "
                     "(TSDFMapping.raycast, the OS1-128 pattern, hits with normals) as binary little-endian PLY into DIR, and the median absolute "
                     "scan_residual of the scan printed")
@@ -85,6 +87,8 @@ def main():
     ap.add_argument("--deskew", action="store_true", help="App(deskew='constant-velocity'): one pose per firing column, the motion during a sweep "
                     "taken from the last two registered poses")
     args = ap.parse_args()
+    if args.global_mesh_ply and not args.device_global_map:
+        ap.error("--global-mesh-ply requires --device-global-map")
     import warpsense_amd as W
     from warpsense_amd import synthetic as S
 
@@ -165,6 +169,16 @@ def main():
             raycast["seconds"] += time.perf_counter() - ts
     W.pause()
     t2 = time.perf_counter()
+    global_mesh = None
+    if args.global_mesh_ply:
+        tg = time.perf_counter()
+        gv, gf = app.gpu_.global_mesh()
+        tg = time.perf_counter() - tg
+        os.makedirs(os.path.dirname(os.path.abspath(args.global_mesh_ply)), exist_ok=True)
+        W.write_mesh_ply(args.global_mesh_ply, gv, gf)
+        global_mesh = {"file": args.global_mesh_ply, "vertices": int(len(gv)), "faces": int(len(gf)), "chunks": app.gpu_.device_global_map_.count(), "call_s": tg}
+        print(f"global mesh: {len(gv)} vertices, {len(gf)} faces from {global_mesh['chunks']} chunks in {1000.0 * tg:.2f} ms (save_box + ws_store_mesh + download)",
+              file=sys.stderr)
     stages = {}
     for key in ("preprocess", "tsdf", "registration", "total"):
         vals = [t[key] for t in app.timings if key in t]
@@ -187,6 +201,7 @@ def main():
                       "terminate_write_back_s": t4 - t3, "h5": args.h5,
                       "surface_ply": surface if args.surface_ply else None,
                       "mesh_ply": mesh if args.mesh_ply else None,
+                      "global_mesh_ply": global_mesh,
                       "raycast_ply": raycast if args.raycast_ply else None,
                       "distance_npy": distance if args.distance_npy else None,
                       "kidnap": kidnap}))

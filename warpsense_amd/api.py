@@ -553,6 +553,38 @@ class DeviceGlobalMap:
         check(self._L.ws_debug_store_timing(self.handle, int(enable), ms), "ws_debug_store_timing")
         return float(ms[0]), float(ms[1])
 
+    def mesh(self, resolution, lo=None, hi=None, any_weight=False, device=False):
+        """The mesh of the chunks on the device (ws_store_mesh; the rules are those of ws_map_mesh, stated in
+        include/warpsense_hip.h): the surface of everything the store holds inside the inclusive world-voxel box [lo, hi] (both
+        None: the bounding box of the present chunks), in the order of DeviceMapMemWrapper.mesh across chunk borders.  Voxels of
+        absent chunks are not valid.  resolution: the map's, in mm per voxel (the store does not know it).
+
+        Returns (vertices, faces) like DeviceMapMemWrapper.mesh; device=True: torch tensors that ALIAS the store's buffers, valid
+        until the next mesh() on this store."""
+        if (lo is None) != (hi is None):
+            raise WsError("mesh: give both lo and hi, or neither")
+        nv, nf = C.c_size_t(0), C.c_size_t(0)
+        flags = _lib.WS_MESH_ANY_WEIGHT if any_weight else _lib.WS_MESH_DEFAULT
+        check(self._L.ws_store_mesh(self.handle, _ptr(_i3(lo)) if lo is not None else None, _ptr(_i3(hi)) if hi is not None else None,
+                                    int(resolution), flags, C.byref(nv), C.byref(nf)), "ws_store_mesh")
+        nv, nf = int(nv.value), int(nf.value)
+        if device:
+            cnt = C.c_size_t(0)
+            return (_device_tensor(self._L.ws_store_mesh_vertices_dev(self.handle, C.byref(cnt)), (nv, 4), "<i4", self),
+                    _device_tensor(self._L.ws_store_mesh_faces_dev(self.handle, C.byref(cnt)), (nf, 3), "<i4", self))
+        vert, face = np.empty(nv, dtype=VERT), np.empty((nf, 3), dtype=np.uint32)
+        gv, gf = C.c_size_t(0), C.c_size_t(0)
+        check(self._L.ws_store_mesh_download(self.handle, _ptr(vert), _ptr(face), nv, nf, C.byref(gv), C.byref(gf)), "ws_store_mesh_download")
+        if (int(gv.value), int(gf.value)) != (nv, nf):
+            raise WsError("mesh: another call replaced the result before it was downloaded")
+        return vert, face
+
+    def mesh_timing(self, enable: int = -1):
+        """device milliseconds of the count passes, the scan and the emit passes of the last mesh() (ws_debug_store_mesh_timing)"""
+        ms = (C.c_float * 3)()
+        check(self._L.ws_debug_store_mesh_timing(self.handle, int(enable), ms), "ws_debug_store_mesh_timing")
+        return tuple(float(v) for v in ms)
+
     def flush_to(self, global_map: GlobalMap):
         """every chunk merged into a host GlobalMap: into its chunk cache (activate_chunk), or, for a map with a file, straight
         into the file (GlobalMap._write_chunk) unless the chunk is active in the cache"""
@@ -1355,6 +1387,18 @@ class TSDFMapping:
         with self.mutex_:
             return self.tsdf_.avg_map().distance(lo=lo, hi=hi, max_dist_vox=-(-mm // res), unknown_occupied=unknown_occupied, columns=columns,
                                                  any_weight=any_weight)
+
+    def global_mesh(self, **kw):
+        """The mesh of everything the run has seen: the window goes into the chunks of device_global_map (ws_store_save_box, the
+        first step of write_back, with its capacity refusals), then DeviceGlobalMap.mesh at the map's resolution -- under the
+        mapping's lock like a writer, nothing leaves the device but the mesh.  Keywords: lo, hi, any_weight, device."""
+        if self.device_global_map_ is None:
+            raise WsError("global_mesh: this TSDFMapping has no device_global_map")
+        self.wait_shift()
+        with self.mutex_:
+            lo, hi = self.local_map_.window()
+            self.device_global_map_.save_box(self.tsdf_, lo, hi)
+            return self.device_global_map_.mesh(int(self.params_.map.resolution), **kw)
 
     @staticmethod
     def raycast_rays(pose, dirs):

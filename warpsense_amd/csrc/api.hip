@@ -1537,6 +1537,183 @@ int ws_debug_store_timing(ws_store *st, int32_t enable, float ms_out[2])
   return WS_OK;
 }
 
+// ---- the mesh of the store: ws_map_mesh's rules over the chunks, store_mesh.hip (the semantics are stated in warpsense_hip.h)
+namespace
+{
+// The call's tables, into st->mesh.table_host: the present chunks the box overlaps, ascending (cx, cy, cz) like the directory; per
+// chunk the four counts that place its 4096 words in world order, its key and slot, and the list positions of its 26 neighbours.
+// Everything is O(listed chunks x log): nothing here follows the volume of the box.
+int store_mesh_tables(ws_store *st, const int32_t lo[3], const int32_t hi[3], std::vector<StoreKey> &keys)
+{
+  const ChunkRange cr(lo, hi);
+  keys.clear();
+  std::vector<uint32_t> slots;
+  // (the directory is ordered by cx first: only the keys of the box's cx range are visited)
+  for (auto it = st->dir.lower_bound(StoreKey{cr.c0[0], INT32_MIN, INT32_MIN}); it != st->dir.end() && it->first[0] - cr.c0[0] < cr.nc[0]; ++it)
+  {
+    bool in = it->second.written;
+    for (int k = 1; k < 3; ++k) in = in && it->first[k] >= cr.c0[k] && it->first[k] - cr.c0[k] < cr.nc[k];
+    if (!in) continue;
+    keys.push_back(it->first);
+    slots.push_back(it->second.slot);
+  }
+  const size_t n = keys.size();
+  if (n == 0 || n >= (1u << 19)) return WS_OK; // (the caller decides: nothing to do / WS_ERR_RANGE)
+  if (store_mesh_table_bytes(n) > st->mesh.table_host.cap)
+  {
+    WS_HIP(hipStreamSynchronize(st->ctx->stream));
+    const size_t want = store_mesh_table_bytes(n + n / 8);
+    WS_TRY(st->mesh.table_host.alloc(want, 1, HostBlock::PINNED));
+    WS_TRY(st->mesh.table_dev.alloc(want, 1));
+  }
+  uint32_t *grp = st->mesh.table_host.as<uint32_t>();
+  int32_t *key = reinterpret_cast<int32_t *>(grp + 4 * n);
+  uint32_t *nb = grp + 8 * n;
+  for (size_t b = 0; b < n;) // the chunks of one cx: [b, e)
+  {
+    size_t e = b;
+    while (e < n && keys[e][0] == keys[b][0]) ++e;
+    for (size_t p = b; p < e;) // the chunks of one (cx, cy): [p, q)
+    {
+      size_t q = p;
+      while (q < e && keys[q][1] == keys[p][1]) ++q;
+      for (size_t i = p; i < q; ++i)
+      {
+        grp[4 * i + 0] = (uint32_t)b, grp[4 * i + 1] = (uint32_t)(e - b), grp[4 * i + 2] = (uint32_t)(p - b), grp[4 * i + 3] = (uint32_t)(q - p);
+        for (int k = 0; k < 3; ++k) key[4 * i + k] = keys[i][k];
+        key[4 * i + 3] = (int32_t)slots[i];
+      }
+      p = q;
+    }
+    b = e;
+  }
+  for (size_t i = 0; i < n; ++i)
+    for (int c = 0; c < 27; ++c)
+    {
+      // (keys are floor(int32 / 64): a step of one cannot overflow)
+      const StoreKey k = {keys[i][0] + c / 9 - 1, keys[i][1] + c / 3 % 3 - 1, keys[i][2] + c % 3 - 1};
+      const auto it = std::lower_bound(keys.begin(), keys.end(), k);
+      nb[27 * i + c] = it != keys.end() && *it == k ? (uint32_t)(it - keys.begin()) : 0xffffffffu;
+    }
+  return WS_OK;
+}
+} // namespace
+
+int ws_store_mesh(ws_store *st, const int32_t lo[3], const int32_t hi[3], int32_t map_resolution, uint32_t flags, size_t *n_vertices, size_t *n_faces)
+{
+  if (!st || (flags & ~WS_MESH_ANY_WEIGHT) || ((lo == nullptr) != (hi == nullptr)) || map_resolution <= 0) return invalid("ws_store_mesh: bad argument");
+  if (lo)
+    for (int k = 0; k < 3; ++k)
+      if (hi[k] < lo[k]) return invalid("ws_store_mesh: hi < lo");
+  std::lock_guard<std::mutex> lock(st->mu);
+  ws_store::Mesh &q = st->mesh;
+  WS_TRY(q.timer.arm());
+  const auto done = [&](size_t nv, size_t nf) {
+    q.nv = nv, q.nf = nf;
+    if (n_vertices) *n_vertices = nv;
+    if (n_faces) *n_faces = nf;
+    return WS_OK;
+  };
+  int32_t l[3], h[3];
+  if (lo)
+    copy3(l, lo), copy3(h, hi);
+  else
+  {
+    if (st->dir.empty()) return done(0, 0);
+    // the bounding box of the present chunks (keys are floor(int32 / 64): 64 k + 63 fits)
+    for (int k = 0; k < 3; ++k) l[k] = INT32_MAX, h[k] = INT32_MIN;
+    for (const auto &kv : st->dir)
+      for (int k = 0; k < 3; ++k) l[k] = std::min(l[k], kv.first[k] * STORE_CS), h[k] = std::max(h[k], kv.first[k] * STORE_CS + STORE_CS - 1);
+  }
+  for (int k = 0; k < 3; ++k)
+    for (int64_t c : {(int64_t)l[k], (int64_t)h[k]})
+      if (((c < 0 ? -c : c) + 1) * (int64_t)map_resolution > (int64_t)INT32_MAX)
+      {
+        set_error("ws_store_mesh: a box corner in millimetres does not fit int32");
+        return WS_ERR_RANGE;
+      }
+  if (h[0] == l[0] || h[1] == l[1] || h[2] == l[2]) return done(0, 0); // one voxel thick along an axis: no cells
+  std::vector<StoreKey> keys;
+  WS_TRY(store_mesh_tables(st, l, h, keys));
+  if (keys.empty()) return done(0, 0); // the box meets no present chunk
+  if (keys.size() >= (1u << 19))
+  {
+    set_error("ws_store_mesh: the box overlaps 2^19 present chunks or more (4096 words each must stay below 2^31)");
+    return WS_ERR_RANGE;
+  }
+  q.nv = q.nf = 0; // (whatever happens from here on, the old result is gone: its buffers may be replaced)
+  if (n_vertices) *n_vertices = 0;
+  if (n_faces) *n_faces = 0;
+  StoreMeshCall c;
+  c.n_chunks = (uint32_t)keys.size();
+  c.res = map_resolution;
+  c.flags = flags;
+  copy3(c.lo, l), copy3(c.hi, h);
+  hipStream_t s = st->ctx->stream;
+  WS_TRY(q.total.alloc(2, false));
+  const size_t need = mesh_scratch_bytes((uint64_t)c.n_chunks * 4096u);
+  if (need > q.scratch.cap)
+  {
+    WS_HIP(hipStreamSynchronize(s));
+    WS_TRY(q.scratch.grow(need, 1));
+  }
+  int rc = launch_store_mesh_count(st, c);
+  const hipError_t e1 = hipStreamSynchronize(s); // the one host read the call needs: the outputs are sized from the two totals
+  if (rc != WS_OK) return rc;
+  WS_HIP(e1);
+  const unsigned long long nv = q.total.host[0], nq = q.total.host[1];
+  if (nv > 0xffffffffull)
+  {
+    set_error("ws_store_mesh: more than 2^32 - 1 vertices");
+    return WS_ERR_RANGE;
+  }
+  WS_TRY(q.vert.grow((size_t)nv, 16));
+  WS_TRY(q.face.grow((size_t)nq * 2, 12));
+  if (nv)
+  {
+    rc = launch_store_mesh_emit(st, c);
+    const hipError_t e2 = hipStreamSynchronize(s);
+    if (rc != WS_OK) return rc;
+    WS_HIP(e2);
+  }
+  return done((size_t)nv, (size_t)nq * 2);
+}
+
+const void *ws_store_mesh_vertices_dev(const ws_store *st, size_t *n)
+{
+  if (n) *n = st ? st->mesh.nv : 0;
+  return st && st->mesh.nv ? st->mesh.vert.p : nullptr;
+}
+
+const uint32_t *ws_store_mesh_faces_dev(const ws_store *st, size_t *n)
+{
+  if (n) *n = st ? st->mesh.nf : 0;
+  return st && st->mesh.nf ? static_cast<const uint32_t *>(st->mesh.face.p) : nullptr;
+}
+
+int ws_store_mesh_download(ws_store *st, void *vertices_host, uint32_t *faces_host, size_t cap_vertices, size_t cap_faces, size_t *n_vertices, size_t *n_faces)
+{
+  if (!st || !n_vertices || !n_faces) return invalid("ws_store_mesh_download: NULL argument");
+  std::lock_guard<std::mutex> lock(st->mu);
+  *n_vertices = st->mesh.nv;
+  *n_faces = st->mesh.nf;
+  const size_t kv = vertices_host ? std::min(cap_vertices, st->mesh.nv) : 0, kf = faces_host ? std::min(cap_faces, st->mesh.nf) : 0;
+  if (kv) WS_HIP(hipMemcpyAsync(vertices_host, st->mesh.vert.p, kv * 16, hipMemcpyDeviceToHost, st->ctx->stream));
+  if (kf) WS_HIP(hipMemcpyAsync(faces_host, st->mesh.face.p, kf * 12, hipMemcpyDeviceToHost, st->ctx->stream));
+  if (kv || kf) WS_HIP(hipStreamSynchronize(st->ctx->stream));
+  return WS_OK;
+}
+
+int ws_debug_store_mesh_timing(ws_store *st, int32_t enable, float ms_out[3])
+{
+  if (!st) return invalid("ws_debug_store_mesh_timing: store is NULL");
+  std::lock_guard<std::mutex> lock(st->mu);
+  static const int pairs[3][2] = {{0, 1}, {1, 2}, {3, 4}};
+  const int rc = st->mesh.timer.read(ms_out, pairs, 3, st->ctx->stream);
+  if (rc == WS_OK) st->mesh.timer.set(enable);
+  return rc;
+}
+
 int ws_map_get_params(const ws_map *m, int which, int32_t size[3], int32_t pos[3], int32_t offset[3])
 {
   if (!m || (which != WS_MAP_AVG && which != WS_MAP_NEW)) return invalid("ws_map_get_params: bad argument");

@@ -21,35 +21,19 @@
 // for x = ex - 1 or y = ey - 1, and act is zero there.
 // Scratch: valid, inside, act (one bit each), vbase (32 bits per 64 voxels), qcnt (8 bits per 64): 29 bytes per 64 voxels of the box,
 // plus 24 bytes per 256 words.
-#include "ws_device.h"
+#include "ws_mesh.h"
 
 namespace ws
 {
-typedef unsigned long long mu64;
-typedef uint32_t mu32x2 __attribute__((ext_vector_type(2)));
-typedef int32_t mi32x4 __attribute__((ext_vector_type(4)));
-
-constexpr uint32_t MESH_WORDS = 256; // words per workgroup of the word passes (one per thread)
-
-struct MeshArgs
+// the word-level rules (bits, active cells, quads, vertices, faces) are in ws_mesh.h, shared with store_mesh.hip; here a word index
+// is t = column of the box * nw + w, and the neighbouring words lie at fixed distances
+struct MeshArgs : MeshBuffers
 {
   BoxArgs box;
   uint32_t nw, n_words; // words per column, box.n_cols * nw (< 2^31)
   int32_t res;
   uint32_t any_weight;
-  mu64 *valid, *inside, *act; // [n_words]
-  uint32_t *vbase;            // [n_words]
-  uint8_t *qcnt;              // [n_words] quads owned by the word's voxels (<= 192)
-  uint32_t *vtot, *qtot;      // [workgroups]
-  mu64 *voff, *qoff;          // [workgroups] exclusive scans
-  mu64 *totals;               // vertices, quads
-  mi32x4 *vert;               // x_mm, y_mm, z_mm, weight
-  uint32_t *face;             // 3 indices per triangle
-  mu64 vcap, qcap;            // vertices / quads the output buffers hold
 };
-
-__device__ __forceinline__ mu64 shift_down(mu64 cur, mu64 next) { return (cur >> 1) | (next << 63); } // bit z := bit z + 1
-__device__ __forceinline__ uint32_t popc_below(mu64 mask, int lane) { return (uint32_t)__popcll(mask & ((1ull << lane) - 1ull)); }
 
 // ---- pass 1: the map, once
 __global__ __launch_bounds__(256) void mesh_bits_kernel(MeshArgs a)
@@ -80,8 +64,8 @@ __global__ __launch_bounds__(256) void mesh_bits_kernel(MeshArgs a)
 #pragma unroll
     for (int j = 0; j < 4; ++j)
     {
-      const int32_t wt = entry_weight(raw[j]);
-      const mu64 bv = __ballot(a.any_weight ? wt != 0 : wt > 0), bi = __ballot(entry_value(raw[j]) < 0);
+      mu64 bv, bi;
+      mesh_ballots(raw[j], a.any_weight, bv, bi);
       if (lane == j && w0 + j < a.nw)
       {
         vout[w0 + j] = bv;
@@ -102,49 +86,27 @@ __global__ __launch_bounds__(256) void mesh_cells_kernel(MeshArgs a)
   if (x + 1 < a.box.ex && y + 1 < a.box.ey)
   {
     const bool more = w + 1 < a.nw;
-    mu64 V = ~0ull, any = 0, all = ~0ull, Vn = ~0ull, anyn = 0, alln = ~0ull; // of the four corner columns; *n: the next word
+    mu64 v[4], i[4], vn[4], in[4]; // of the four corner columns; *n: the next word
 #pragma unroll
     for (int c = 0; c < 4; ++c)
     {
       const uint32_t tt = t + ((c >> 1) * (uint32_t)a.box.ey + (c & 1)) * a.nw;
-      const mu64 v = a.valid[tt], i = a.inside[tt];
-      const mu64 vn = more ? a.valid[tt + 1] : 0ull, in = more ? a.inside[tt + 1] : 0ull;
-      V &= v, any |= i, all &= i;
-      Vn &= vn, anyn |= in, alln &= in;
+      v[c] = a.valid[tt], i[c] = a.inside[tt];
+      vn[c] = more ? a.valid[tt + 1] : 0ull, in[c] = more ? a.inside[tt + 1] : 0ull;
     }
-    // cell z: voxels z and z + 1 of the four columns (no valid bit at z >= ez: the column's last voxel starts no cell)
-    const mu64 cv = V & shift_down(V, Vn), ca = any | shift_down(any, anyn), cl = all & shift_down(all, alln);
-    A = cv & ca & ~cl;
+    A = mesh_active_cells(v, i, vn, in);
   }
   a.act[t] = A;
 }
 
-// the quads owned by the voxels of word t (column c = (x, y), 64 z from 64 w): an edge from voxel a along axis k that crosses the
-// surface, and whose four cells are active (a valid cell at a crossing edge is active, an active cell is valid with valid corners)
-struct QuadWords
-{
-  mu64 q[3];  // per axis
-  mu64 A[4];  // active cells of the cell columns c, c - (0,1), c - (1,0), c - (1,1)
-  mu64 I;     // inside bits of the voxel column
-};
 __device__ __forceinline__ void quad_words(const MeshArgs &a, uint32_t t, uint32_t w, int32_t x, int32_t y, mu64 Ac, QuadWords &o)
 {
   const uint32_t dy = a.nw, dx = (uint32_t)a.box.ey * a.nw;
   const bool hx = x > 0, hy = y > 0, hw = w > 0;
-  o.A[0] = Ac;
-  o.A[1] = hy ? a.act[t - dy] : 0ull;
-  o.A[2] = hx ? a.act[t - dx] : 0ull;
-  o.A[3] = hx && hy ? a.act[t - dx - dy] : 0ull;
-  // the cells one below: bit z = cell z - 1
-  const mu64 m0 = (o.A[0] << 1) | (hw ? a.act[t - 1] >> 63 : 0ull);
-  const mu64 m1 = (o.A[1] << 1) | (hw && hy ? a.act[t - dy - 1] >> 63 : 0ull);
-  const mu64 m2 = (o.A[2] << 1) | (hw && hx ? a.act[t - dx - 1] >> 63 : 0ull);
+  const mu64 A[4] = {Ac, hy ? a.act[t - dy] : 0ull, hx ? a.act[t - dx] : 0ull, hx && hy ? a.act[t - dx - dy] : 0ull};
+  const mu64 below[3] = {hw ? a.act[t - 1] : 0ull, hw && hy ? a.act[t - dy - 1] : 0ull, hw && hx ? a.act[t - dx - 1] : 0ull};
   // Ac != 0: the columns x + 1 and y + 1 are in the box
-  const mu64 I = a.inside[t], Ix = a.inside[t + dx], Iy = a.inside[t + dy], In = w + 1 < a.nw ? a.inside[t + 1] : 0ull;
-  o.I = I;
-  o.q[0] = (I ^ Ix) & o.A[0] & o.A[1] & m0 & m1;                  // cells (x, y-1, z-1) (x, y, z-1) (x, y, z) (x, y-1, z)
-  o.q[1] = (I ^ Iy) & o.A[0] & o.A[2] & m0 & m2;                  // cells (x-1, y, z-1) (x-1, y, z) (x, y, z) (x, y, z-1)
-  o.q[2] = (I ^ shift_down(I, In)) & o.A[0] & o.A[1] & o.A[2] & o.A[3]; // cells (x-1, y-1, z) (x, y-1, z) (x, y, z) (x-1, y, z)
+  mesh_quad_masks(o, A, below, a.inside[t], a.inside[t + dx], a.inside[t + dy], w + 1 < a.nw ? a.inside[t + 1] : 0ull);
 }
 
 __global__ __launch_bounds__(256) void mesh_quads_kernel(MeshArgs a)
@@ -161,60 +123,17 @@ __global__ __launch_bounds__(256) void mesh_quads_kernel(MeshArgs a)
       QuadWords q;
       quad_words(a, t, w, x, y, Ac, q);
       nv = (uint32_t)__popcll(Ac);
-      nq = (uint32_t)(__popcll(q.q[0]) + __popcll(q.q[1]) + __popcll(q.q[2]));
+      nq = mesh_quad_count(q);
     }
     a.qcnt[t] = (uint8_t)nq;
   }
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1)
-  {
-    nv += __shfl_xor(nv, d, 64);
-    nq += __shfl_xor(nq, d, 64);
-  }
-  __shared__ uint32_t wv[4], wq[4];
-  if ((threadIdx.x & 63) == 0)
-  {
-    wv[threadIdx.x >> 6] = nv;
-    wq[threadIdx.x >> 6] = nq;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0)
-  {
-    a.vtot[blockIdx.x] = wv[0] + wv[1] + wv[2] + wv[3];
-    a.qtot[blockIdx.x] = wq[0] + wq[1] + wq[2] + wq[3];
-  }
+  mesh_block_totals(nv, nq, a.vtot, a.qtot);
 }
 
 // ---- exclusive scans of the workgroup totals: workgroup 0 the vertices, workgroup 1 the quads; every thread a contiguous piece
 __global__ __launch_bounds__(1024) void mesh_scan_kernel(MeshArgs a, uint32_t n)
 {
   scan_block_totals(blockIdx.x ? a.qtot : a.vtot, blockIdx.x ? a.qoff : a.voff, n, a.totals + blockIdx.x);
-}
-
-// exclusive scan of one value per thread over the workgroup (256 threads)
-__device__ __forceinline__ uint32_t block_scan_256(uint32_t c, uint32_t *wsum /* [4] shared */)
-{
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t inc = c;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1)
-  {
-    const uint32_t v = __shfl_up(inc, d, 64);
-    if (lane >= d) inc += v;
-  }
-  if (lane == 63) wsum[wave] = inc;
-  __syncthreads();
-  uint32_t pre = 0;
-  for (int k = 0; k < wave; ++k) pre += wsum[k];
-  return pre + inc - c;
-}
-
-// offset of the crossing from voxel a towards b, in mm: (2 |va| res + m) / (2 m), m = |va| + |vb| >= 1 (floor of non-negative
-// numbers below 2^53: one double division is exact, ws_device.h)
-__device__ __forceinline__ int64_t crossing(int32_t va, int32_t vb, int32_t res)
-{
-  const int64_t ua = va < 0 ? -(int64_t)va : (int64_t)va, ub = vb < 0 ? -(int64_t)vb : (int64_t)vb, m = ua + ub;
-  return div_trunc_i64(2 * ua * (int64_t)res + m, 2 * m);
 }
 
 // ---- pass 3a: vertices
@@ -233,7 +152,6 @@ __global__ __launch_bounds__(256) void mesh_vertex_kernel(MeshArgs a)
   sB[threadIdx.x] = base;
   __syncthreads();
   const int32_t sz = a.box.mp.size[2], sy = a.box.mp.size[1];
-  const int32_t res = a.res;
   for (int i = 0; i < 64; ++i) // the wave's 64 words, one after the other; lane = z inside the word
   {
     const int idx = wave * 64 + i;
@@ -249,58 +167,22 @@ __global__ __launch_bounds__(256) void mesh_vertex_kernel(MeshArgs a)
     int32_t zi0 = zs0 + z;
     if (zi0 >= sz) zi0 -= sz;
     const int32_t zi1 = zi0 + 1 == sz ? 0 : zi0 + 1;
-    int32_t v[8];
-    uint32_t wmin = 0xffffffffu;
+    uint32_t raw[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) // k = dx * 4 + dy * 2 + dz
     {
       const int32_t xi = (k & 4) ? xi1 : xi0, yi = (k & 2) ? yi1 : yi0, zi = (k & 1) ? zi1 : zi0;
-      const uint32_t raw = a.box.data[(int64_t)(xi * sy + yi) * (int64_t)sz + zi];
-      v[k] = entry_value(raw);
-      wmin = min(wmin, (uint32_t)iabs32(entry_weight(raw))); // (weights are positive unless WS_MESH_ANY_WEIGHT admits negative ones)
-    }
-    // the crossing edges: four per axis, from the corner without the axis' bit to the one with it
-    int64_t s[3] = {0, 0, 0};
-    int32_t n = 0;
-#pragma unroll
-    for (int ax = 0; ax < 3; ++ax)
-    {
-      const int bit = 4 >> ax;
-#pragma unroll
-      for (int k = 0; k < 8; ++k)
-      {
-        if (k & bit) continue;
-        const int32_t va = v[k], vb = v[k | bit];
-        if ((va < 0) == (vb < 0)) continue;
-        ++n;
-#pragma unroll
-        for (int d = 0; d < 3; ++d) s[d] += d == ax ? crossing(va, vb, res) : ((k & (4 >> d)) ? (int64_t)res : 0);
-      }
+      raw[k] = a.box.data[(int64_t)(xi * sy + yi) * (int64_t)sz + zi];
     }
     if (out < a.vcap) // (the count pass sized the buffer; a map that changed in between must not write beyond it)
     {
       const int32_t c3[3] = {x, y, a.box.lo[2] + z};
-      int32_t p[3];
-#pragma unroll
-      for (int d = 0; d < 3; ++d) p[d] = c3[d] * res + res / 2 + (int32_t)div_trunc_i64(s[d], n > 0 ? n : 1); // fits: the host checked the box
-      const mi32x4 r = {p[0], p[1], p[2], (int32_t)wmin};
-      a.vert[out] = r;
+      a.vert[out] = mesh_vertex(raw, c3, a.res);
     }
   }
 }
 
 // ---- pass 3b: faces
-__device__ __forceinline__ void put_quad(const MeshArgs &a, mu64 quad, uint32_t q0, uint32_t q1, uint32_t q2, uint32_t q3, bool inside)
-{
-  if (quad >= a.qcap) return;
-  mu32x2 *f = reinterpret_cast<mu32x2 *>(a.face + quad * 6ull); // 24 bytes per quad: 8-byte aligned
-  const uint32_t b = inside ? q1 : q2, c = inside ? q2 : q1, d = inside ? q2 : q3, e = inside ? q3 : q2;
-  const mu32x2 f0 = {q0, b}, f1 = {c, q0}, f2 = {d, e};
-  f[0] = f0; // (q0, q1, q2) (q0, q2, q3) if a is inside, else (q0, q2, q1) (q0, q3, q2)
-  f[1] = f1;
-  f[2] = f2;
-}
-
 __global__ __launch_bounds__(256) void mesh_face_kernel(MeshArgs a)
 {
   __shared__ uint32_t sQ[MESH_WORDS];
@@ -322,29 +204,17 @@ __global__ __launch_bounds__(256) void mesh_face_kernel(MeshArgs a)
     const int32_t x = (int32_t)(col / (uint32_t)a.box.ey), y = (int32_t)(col - (uint32_t)x * (uint32_t)a.box.ey);
     QuadWords q;
     quad_words(a, tt, w, x, y, a.act[tt], q);
-    const bool k0 = (q.q[0] >> lane) & 1ull, k1 = (q.q[1] >> lane) & 1ull, k2 = (q.q[2] >> lane) & 1ull;
-    if (!(k0 || k1 || k2)) continue;
-    // index of cell z of a column: the word's first vertex plus the active cells below; of cell z - 1 (active): one less
-    const uint32_t r0 = a.vbase[tt] + popc_below(q.A[0], lane);
-    const uint32_t r1 = y > 0 ? a.vbase[tt - dy] + popc_below(q.A[1], lane) : 0u;
-    const uint32_t r2 = x > 0 ? a.vbase[tt - dx] + popc_below(q.A[2], lane) : 0u;
-    const uint32_t r3 = x > 0 && y > 0 ? a.vbase[tt - dx - dy] + popc_below(q.A[3], lane) : 0u;
-    const bool in = (q.I >> lane) & 1ull;
-    mu64 o = sF[idx] + popc_below(q.q[0], lane) + popc_below(q.q[1], lane) + popc_below(q.q[2], lane);
-    if (k0) put_quad(a, o++, r1 - 1u, r0 - 1u, r0, r1, in);
-    if (k1) put_quad(a, o++, r2 - 1u, r2, r0, r0 - 1u, in);
-    if (k2) put_quad(a, o++, r3, r1, r0, r2, in);
+    if (!(((q.q[0] | q.q[1] | q.q[2]) >> lane) & 1ull)) continue;
+    const uint32_t vb[4] = {a.vbase[tt], y > 0 ? a.vbase[tt - dy] : 0u, x > 0 ? a.vbase[tt - dx] : 0u, x > 0 && y > 0 ? a.vbase[tt - dx - dy] : 0u};
+    mesh_emit_quads(q, lane, vb, sF[idx], a.face, a.qcap);
   }
 }
 
 // ---- host side
-static uint32_t mesh_blocks(uint32_t n_words) { return (n_words + MESH_WORDS - 1) / MESH_WORDS; }
-static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 size_t mesh_scratch_bytes(uint64_t n_words)
 {
   const size_t nwd = (size_t)n_words, nb = mesh_blocks((uint32_t)n_words);
-  return 3 * up256(nwd * 8) + up256(nwd * 4) + up256(nwd) + 2 * up256(nb * 4) + 2 * up256(nb * 8) + 256;
+  return 3 * mesh_up256(nwd * 8) + mesh_up256(nwd * 4) + mesh_up256(nwd) + 2 * mesh_up256(nb * 4) + 2 * mesh_up256(nb * 8) + 256;
 }
 
 static MeshArgs mesh_args(const ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], uint32_t flags, mu64 vcap, mu64 qcap)
@@ -355,23 +225,7 @@ static MeshArgs mesh_args(const ws_map *m, int which, const int32_t lo[3], const
   a.n_words = a.box.n_cols * a.nw;
   a.res = m->res;
   a.any_weight = (flags & WS_MESH_ANY_WEIGHT) ? 1u : 0u;
-  const size_t nwd = a.n_words, nb = mesh_blocks(a.n_words);
-  char *p = static_cast<char *>(m->mesh.scratch.p);
-  auto take = [&p](size_t bytes) {
-    char *r = p;
-    p += up256(bytes);
-    return r;
-  };
-  a.valid = reinterpret_cast<mu64 *>(take(nwd * 8));
-  a.inside = reinterpret_cast<mu64 *>(take(nwd * 8));
-  a.act = reinterpret_cast<mu64 *>(take(nwd * 8));
-  a.vbase = reinterpret_cast<uint32_t *>(take(nwd * 4));
-  a.qcnt = reinterpret_cast<uint8_t *>(take(nwd));
-  a.vtot = reinterpret_cast<uint32_t *>(take(nb * 4));
-  a.qtot = reinterpret_cast<uint32_t *>(take(nb * 4));
-  a.voff = reinterpret_cast<mu64 *>(take(nb * 8));
-  a.qoff = reinterpret_cast<mu64 *>(take(nb * 8));
-  a.totals = reinterpret_cast<mu64 *>(take(16));
+  mesh_take_scratch(a, m->mesh.scratch.p, a.n_words);
   a.vert = static_cast<mi32x4 *>(m->mesh.vert.p);
   a.face = static_cast<uint32_t *>(m->mesh.face.p);
   a.vcap = vcap;

@@ -620,8 +620,22 @@ struct ws_store
   } tab[ws::STORE_TABLES];
   int tab_next = 0;
   ws::QueryTimer timer[3]; // per axis of a shift: 0 save 1 load 2 (ws_store_save_box / _load_box use the first)
+  // ws_store_mesh (store_mesh.hip): the result of the last call and the scratch of its passes, allocated on first use and grown on
+  // demand like those of ws_map::Mesh; the store's mutex serialises the calls
+  struct Mesh
+  {
+    ws::QueryTimer timer;                // 0 count passes 1 scans 2, 3 emit passes 4
+    ws::DevBuf scratch;                  // bytes: mesh_scratch_bytes(4096 words per listed chunk)
+    ws::HostBlock table_host;            // bytes, pinned: the call's chunk tables (store_mesh_table_bytes); free again when the call returns, which synchronises
+    ws::DevBuf table_dev;                // ... and the copy the kernels read
+    ws::DevCounter total;                // pinned half only: vertices, quads (the device words are in `scratch`)
+    ws::DevBuf vert, face;               // 16-byte vertices; 3 indices per face
+    size_t nv = 0, nf = 0;               // vertices and faces of the last call
+    void release() { timer.release(), total.release(), table_host.release(); for (ws::DevBuf *b : {&scratch, &table_dev, &vert, &face}) b->release(); }
+  } mesh;
   void release()
   {
+    mesh.release();
     for (ws::DevBuf &b : segs) b.release();
     segs.clear(), seg_ptr.clear();
     seg_tab.release();
@@ -698,6 +712,20 @@ int check_all_equal_host(const uint32_t *data, int64_t n, uint32_t value);
 // any_new: the table of a save holds a chunk flagged STORE_NEW
 int launch_store_copy(ws_store *st, ws_map *m, const ws::MapParams &par, int which, const int32_t lo[3], const int32_t hi[3], const int32_t c0[3],
                       const int32_t nc[3], const uint32_t *table_dev, bool save, bool any_new, hipStream_t stream);
+
+// store_mesh.hip: the passes of map_mesh.hip over the chunks the call lists.  The host has written the tables of `n_chunks` listed
+// chunks (store_mesh_table_bytes: {B, N, P, n}, then {cx, cy, cz, slot}, then 27 neighbour positions per chunk) into
+// ws_store::mesh.table_host; the totals arrive in ws_store::mesh.total.host after a stream synchronise
+struct StoreMeshCall
+{
+  uint32_t n_chunks; // < 2^19: 4096 words each
+  int32_t res;
+  uint32_t flags;
+  int32_t lo[3], hi[3]; // the box, inclusive world voxels
+};
+size_t store_mesh_table_bytes(size_t n_chunks);
+int launch_store_mesh_count(ws_store *st, const StoreMeshCall &c);
+int launch_store_mesh_emit(ws_store *st, const StoreMeshCall &c);
 
 int launch_reg_iteration(ws_reg *r, const ws_map *m, int32_t res, uint32_t flags, int32_t k);
 // reg_pass_kernel over points [first, first + count): from the newest state (first the update from `sums` if `apply`) into `sums`;
