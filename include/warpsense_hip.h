@@ -418,6 +418,50 @@ int ws_store_mesh_download(ws_store *st, void *vertices_host, uint32_t *faces_ho
 /* Measurement entry, as ws_debug_mesh_timing: ms_out receives the device time of the count passes, the scan and the emit passes */
 int ws_debug_store_mesh_timing(ws_store *st, int32_t enable, float ms_out[3]);
 
+/* The ray cast of the store: ws_map_raycast over the chunks of the global map, wherever they lie -- the predicted scan, or the residual
+ * of a scan, from ANY pose of the run, not only from inside the window -- on the device, without a chunk leaving HBM.
+ *   rules: word for word those of ws_map_raycast -- samples, L and step; T as the trilinear interpolant times res^3; the hit
+ *     condition, the range t and the hit point; the 16-byte record and the gradient; WS_RAYCAST_ANY_WEIGHT, _GRADIENT and _TARGETS; the
+ *     dead rays -- applied to the field of ws_store_mesh: a voxel of a present chunk holds that chunk's entry; a voxel of an absent
+ *     chunk is NOT VALID, whatever fill_entry is.
+ *   box: inclusive world voxels [lo, hi]; it need not lie in any window.  Both NULL: everything.  Exactly one NULL, or hi < lo:
+ *     WS_ERR_INVALID.  Voxels outside the box are not valid; a cell is valid iff all 8 of its voxels are valid.
+ *   map_resolution: the store does not know the map's resolution, the caller passes it (mm per voxel); <= 0: WS_ERR_INVALID,
+ *     > 1024: WS_ERR_RANGE.
+ *   errors, as for ws_map_raycast: max_range <= 0 and unknown flag bits are WS_ERR_INVALID; |o| + max_range + 2 res does not fit
+ *     int32 on an axis, or n > 2^27: WS_ERR_RANGE; also WS_ERR_RANGE if the call lists 2^19 present chunks or more (those the box
+ *     overlaps; all of them without a box).  On a refusal nothing is launched, and the last result stays.  n == 0: WS_OK, nothing
+ *     written.  An empty store, or a box that meets no present chunk: WS_OK, every record a no-hit.
+ *   consequence: if a window holds the same voxels as the store inside a box, the box is that window, and fill_entry has weight 0
+ *     (so that what ws_store_load_box writes for an absent chunk is not valid either), ws_map_raycast on that window returns the
+ *     same bytes, records and gradient.
+ *   ordering: the work is stream-ordered behind every save, load and shift already enqueued on the store's context; the call
+ *     synchronises (*n_hits, may be NULL, comes back), is read-only on the chunks and is serialised with the other store calls by the
+ *     store's mutex.
+ *   result buffers: they belong to the store, are not allocated before the first call and grow on demand; they stay valid until
+ *     the next ws_store_raycast on the store -- later saves, loads, shifts and drops leave them untouched -- and are apart from
+ *     those of ws_store_mesh.  Every output write is bounded by the buffers' capacities.
+ *   cost: the host lists the present chunks the box overlaps and writes a lookup key -> slot of 32 to 64 bytes per listed chunk,
+ *     never anything that follows the volume of the box.  A ray does not sample absent chunks or the space outside the box: it
+ *     goes from the sample at which it enters one straight to the first sample behind it, which leaves the records as they are.
+ * ws_store_raycast_dev takes an array that is already in device memory (it must stay untouched until the call returns). */
+int ws_store_raycast(ws_store *st, const int32_t lo[3], const int32_t hi[3], const int32_t origin_mm[3], const int32_t *dirs_host, size_t n, int32_t max_range_mm,
+                     int32_t map_resolution, uint32_t flags, size_t *n_hits);
+int ws_store_raycast_dev(ws_store *st, const int32_t lo[3], const int32_t hi[3], const int32_t origin_mm[3], const int32_t *dirs_dev, size_t n, int32_t max_range_mm,
+                         int32_t map_resolution, uint32_t flags, size_t *n_hits);
+const void *ws_store_raycast_records_dev(const ws_store *st, size_t *n);     /* device memory, n x 16 bytes; NULL when n == 0 */
+const int32_t *ws_store_raycast_gradient_dev(const ws_store *st, size_t *n); /* n x 3 int32; NULL unless the last call asked for it */
+/* copies at most capacity_rays records (and gradients: a prefix) and always reports the number of rays; either host pointer may be NULL */
+int ws_store_raycast_download(ws_store *st, void *records_host, int32_t *gradient_host, size_t capacity_rays, size_t *n_out);
+/* Measurement entry, as ws_debug_raycast_timing: ms_out receives the device time of the upload (the chunk lookup and, for the host
+ * form, the directions), of the march and of the gradient pass of the last call */
+int ws_debug_store_raycast_timing(ws_store *st, int32_t enable, float ms_out[3]);
+/* Host only, for tests: the chunk lookup the kernels of ws_store_raycast read.  keys_slots: n x {cx, cy, cz, slot} with distinct keys,
+ * n < 2^19; *n_places receives the table's size in 16-byte places, the power of two >= max(2, 2 n); table (may be NULL) receives
+ * them if capacity_places allows.  _find returns the slot of `key` by the kernels' own probe, 0xffffffff if the table does not list it. */
+int ws_debug_store_raycast_table(const int32_t *keys_slots, size_t n, int32_t *table, size_t capacity_places, size_t *n_places);
+uint32_t ws_debug_store_raycast_find(const int32_t *table, size_t n_places, const int32_t key[3]);
+
 /* ------------------------------------------------------------------ TSDF update ---- */
 /* TSDFCuda::update_tsdf(scan_points, scanner_pos, up) — update_tsdf.cu:143-166.
  * xyz_host: n x 3 int32 (rmagine::Pointi AoS); scanner_pos in voxel units, up scaled by 32768.

@@ -334,6 +334,13 @@ inline SurfaceMesh global_map_mesh(DeviceGlobalMap &g, int resolution, bool any_
   return global_map_mesh(g.handle(), resolution, any_weight, lo, hi);
 }
 
+// the ray cast of the device global map (visualization.hpp, ws_store_raycast)
+inline RayCast global_map_raycast(DeviceGlobalMap &g, int resolution, const rm::Pointi &origin_mm, const std::vector<rm::Pointi> &dirs, int32_t max_range_mm,
+                                  bool any_weight = false, bool with_gradient = false, const rm::Pointi *lo = nullptr, const rm::Pointi *hi = nullptr, bool targets = false)
+{
+  return global_map_raycast(g.handle(), resolution, origin_mm, dirs, max_range_mm, any_weight, with_gradient, lo, hi, targets);
+}
+
 // ---------------------------------------------------------------------------------------------------- LocalMap
 // The in-memory state of HDF5LocalMap (hdf5_local_map.cpp:5-20): odd sizes, offset = size / 2, default-filled.
 class LocalMap
@@ -617,6 +624,18 @@ public:
     local_map_.window(wlo, whi);
     WS_CHECK(ws_store_save_box(device_global_map_->handle(), gpu_.tsdf().handle(), WS_MAP_AVG, &wlo.x, &whi.x));
     return global_map_mesh(*device_global_map_, params_.map_resolution, any_weight, lo, hi);
+  }
+  // The predicted scan from anywhere the run has been: the window into the device chunks, as global_mesh does, then the ray cast of
+  // the store -- nothing leaves the device but the records
+  RayCast global_raycast(const rm::Pointi &origin_mm, const std::vector<rm::Pointi> &dirs, int32_t max_range_mm, bool any_weight = false, bool with_gradient = false,
+                         const rm::Pointi *lo = nullptr, const rm::Pointi *hi = nullptr, bool targets = false)
+  {
+    if (!device_global_map_) throw std::logic_error("global_raycast: no DeviceGlobalMap attached");
+    wait_shift();
+    rm::Pointi wlo, whi;
+    local_map_.window(wlo, whi);
+    WS_CHECK(ws_store_save_box(device_global_map_->handle(), gpu_.tsdf().handle(), WS_MAP_AVG, &wlo.x, &whi.x));
+    return global_map_raycast(*device_global_map_, params_.map_resolution, origin_mm, dirs, max_range_mm, any_weight, with_gradient, lo, hi, targets);
   }
   // the reference's route, kept for comparison: whole window to the host array of the local map
   void download() { gpu_.tsdf().avg_map().to_host(view_); }

@@ -4,6 +4,7 @@
 //   local_map_mesh       (no counterpart: the reference sends the user to an offline mesher)   a triangle mesh, over ws_map_mesh
 //   global_map_mesh      (no counterpart)                                                     the mesh of the device global map, over ws_store_mesh
 //   local_map_raycast    (no counterpart: the reference leaves all viewing to RViz)            a predicted scan, over ws_map_raycast
+//   global_map_raycast   (no counterpart)                                                     a predicted scan from anywhere the run has been, over ws_store_raycast
 //   local_map_distance   (no counterpart: the reference has no distance field)                   a cost map, over ws_map_distance
 //   local_map_skeleton   publish_local_map_skeleton  map.h:175-227   the 24 end points of the window's line list (host only)
 //
@@ -125,6 +126,25 @@ inline RayCast local_map_raycast(cuda::TSDFCuda &tsdf, const rmagine::Pointi &or
   size_t got = 0;
   WS_CHECK(ws_map_raycast_download(tsdf.handle(), dirs.empty() ? nullptr : out.records.data(), with_gradient && !dirs.empty() ? &out.gradient.data()->x : nullptr,
                                    dirs.size(), &got));
+  return out;
+}
+
+// The ray cast of the global map in device memory (the rules: warpsense_hip.h at ws_store_raycast): ws_map_raycast's records through
+// everything the store's chunks hold inside the inclusive world-voxel box [lo, hi] (both nullptr: everything), from an origin that
+// need not lie in any window.  resolution: the map's, in mm per voxel.
+inline RayCast global_map_raycast(ws_store *store, int resolution, const rmagine::Pointi &origin_mm, const std::vector<rmagine::Pointi> &dirs, int32_t max_range_mm,
+                                  bool any_weight = false, bool with_gradient = false, const rmagine::Pointi *lo = nullptr, const rmagine::Pointi *hi = nullptr,
+                                  bool targets = false)
+{
+  RayCast out;
+  const uint32_t flags = (any_weight ? WS_RAYCAST_ANY_WEIGHT : 0u) | (with_gradient ? WS_RAYCAST_GRADIENT : 0u) | (targets ? WS_RAYCAST_TARGETS : 0u);
+  WS_CHECK(ws_store_raycast(store, lo ? &lo->x : nullptr, hi ? &hi->x : nullptr, &origin_mm.x, dirs.empty() ? nullptr : &dirs.data()->x, dirs.size(), max_range_mm,
+                            resolution, flags, &out.hits));
+  out.records.resize(dirs.size());
+  if (with_gradient) out.gradient.resize(dirs.size());
+  size_t got = 0;
+  WS_CHECK(ws_store_raycast_download(store, dirs.empty() ? nullptr : out.records.data(), with_gradient && !dirs.empty() ? &out.gradient.data()->x : nullptr,
+                                     dirs.size(), &got));
   return out;
 }
 

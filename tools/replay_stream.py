@@ -68,6 +68,9 @@ def main():
                     "TSDFMapping.surface_mesh) as binary little-endian PLY into DIR, after every N-th scan like --surface-ply")
     ap.add_argument("--global-mesh-ply", default=None, metavar="FILE", help="after the last scan: the mesh of the WHOLE run, window and every chunk that "
                     "has left it, from the device global map (TSDFMapping.global_mesh, ws_store_mesh); needs --device-global-map")
+    ap.add_argument("--global-raycast-ply", default=None, metavar="FILE", help="after the last scan: the predicted scan from the pose of the FIRST scan, "
+                    "which the window has left, through the device global map (TSDFMapping.global_raycast, ws_store_raycast) as PLY, and its hit "
+                    "share printed next to that of the window's raycast from the same pose; needs --device-global-map")
     ap.add_argument("--raycast-ply", default=None, metavar="DIR", help="after every registered scan: the ray cast of the map from the registered pose "
                     "(TSDFMapping.raycast, the OS1-128 pattern, hits with normals) as binary little-endian PLY into DIR, and the median absolute "
                     "scan_residual of the scan printed")
@@ -89,6 +92,8 @@ def main():
     args = ap.parse_args()
     if args.global_mesh_ply and not args.device_global_map:
         ap.error("--global-mesh-ply requires --device-global-map")
+    if args.global_raycast_ply and not args.device_global_map:
+        ap.error("--global-raycast-ply requires --device-global-map")
     import warpsense_amd as W
     from warpsense_amd import synthetic as S
 
@@ -179,6 +184,22 @@ def main():
         global_mesh = {"file": args.global_mesh_ply, "vertices": int(len(gv)), "faces": int(len(gf)), "chunks": app.gpu_.device_global_map_.count(), "call_s": tg}
         print(f"global mesh: {len(gv)} vertices, {len(gf)} faces from {global_mesh['chunks']} chunks in {1000.0 * tg:.2f} ms (save_box + ws_store_mesh + download)",
               file=sys.stderr)
+    global_raycast = None
+    if args.global_raycast_ply:
+        first = app.poses[0].astype(np.float64).copy()
+        first[:3, 3] /= 1000.0  # (the app keeps its translation in millimetres)
+        tg = time.perf_counter()
+        rec, grad = app.gpu_.global_raycast(first, gradient=True)
+        tg = time.perf_counter() - tg
+        rng = app.gpu_._global_range_mm(np.rint(first[:3, 3] * 1000.0))
+        rec_w, _ = app.gpu_.raycast(first, max_range_mm=rng)
+        os.makedirs(os.path.dirname(os.path.abspath(args.global_raycast_ply)), exist_ok=True)
+        hits = W.write_raycast_ply(args.global_raycast_ply, rec, grad)
+        share, share_w = hits / len(rec), float(np.count_nonzero(rec_w["range_mm"] >= 0)) / len(rec_w)
+        global_raycast = {"file": args.global_raycast_ply, "rays": int(len(rec)), "hit_share": share, "window_hit_share": share_w, "range_mm": rng,
+                          "chunks": app.gpu_.device_global_map_.count(), "call_s": tg}
+        print(f"global raycast from the first pose: hit share {share:.3f} (the window's raycast from the same pose: {share_w:.3f}), "
+              f"{global_raycast['chunks']} chunks, {1000.0 * tg:.2f} ms (save_box + ws_store_raycast + download)", file=sys.stderr)
     stages = {}
     for key in ("preprocess", "tsdf", "registration", "total"):
         vals = [t[key] for t in app.timings if key in t]
@@ -202,6 +223,7 @@ def main():
                       "surface_ply": surface if args.surface_ply else None,
                       "mesh_ply": mesh if args.mesh_ply else None,
                       "global_mesh_ply": global_mesh,
+                      "global_raycast_ply": global_raycast,
                       "raycast_ply": raycast if args.raycast_ply else None,
                       "distance_npy": distance if args.distance_npy else None,
                       "kidnap": kidnap}))

@@ -585,6 +585,41 @@ class DeviceGlobalMap:
         check(self._L.ws_debug_store_mesh_timing(self.handle, int(enable), ms), "ws_debug_store_mesh_timing")
         return tuple(float(v) for v in ms)
 
+    def raycast(self, resolution, origin_mm, dirs, max_range_mm, lo=None, hi=None, any_weight=False, gradient=False, targets=False):
+        """Ray cast of the chunks on the device (ws_store_raycast; the rules are those of ws_map_raycast, stated in
+        include/warpsense_hip.h): per ray the first crossing of the surface from the outside within max_range_mm, through
+        everything the store holds inside the inclusive world-voxel box [lo, hi] (both None: everything).  Voxels of absent chunks
+        are not valid.  resolution: the map's, in mm per voxel.  origin_mm, dirs, targets, any_weight, gradient and the returned
+        (records, gradient | None) are those of DeviceMapMemWrapper.raycast; `last_hits` keeps the call's number of hits."""
+        if (lo is None) != (hi is None):
+            raise WsError("raycast: give both lo and hi, or neither")
+        n = int(dirs.shape[0])
+        flags = ((_lib.WS_RAYCAST_ANY_WEIGHT if any_weight else 0) | (_lib.WS_RAYCAST_GRADIENT if gradient else 0)
+                 | (_lib.WS_RAYCAST_TARGETS if targets else 0))
+        box = (_ptr(_i3(lo)) if lo is not None else None, _ptr(_i3(hi)) if hi is not None else None)
+        hits = C.c_size_t(0)
+        if _is_device(dirs):
+            check(self._L.ws_store_raycast_dev(self.handle, *box, _ptr(_i3(origin_mm)), _ptr(dirs), n, int(max_range_mm), int(resolution), flags,
+                                               C.byref(hits)), "ws_store_raycast_dev")
+        else:
+            d = np.ascontiguousarray(dirs, dtype=np.int32).reshape(-1, 3)
+            check(self._L.ws_store_raycast(self.handle, *box, _ptr(_i3(origin_mm)), _ptr(d), n, int(max_range_mm), int(resolution), flags,
+                                           C.byref(hits)), "ws_store_raycast")
+        rec = np.empty(n, dtype=RAY)
+        grad = np.empty((n, 3), dtype=np.int32) if gradient else None
+        got = C.c_size_t(0)
+        check(self._L.ws_store_raycast_download(self.handle, _ptr(rec), _ptr(grad), n, C.byref(got)), "ws_store_raycast_download")
+        if int(got.value) != n:
+            raise WsError("raycast: another call replaced the result before it was downloaded")
+        self.last_hits = int(hits.value)
+        return rec, grad
+
+    def raycast_timing(self, enable: int = -1):
+        """device milliseconds of the upload, the march and the gradient pass of the last raycast() (ws_debug_store_raycast_timing)"""
+        ms = (C.c_float * 3)()
+        check(self._L.ws_debug_store_raycast_timing(self.handle, int(enable), ms), "ws_debug_store_raycast_timing")
+        return tuple(float(v) for v in ms)
+
     def flush_to(self, global_map: GlobalMap):
         """every chunk merged into a host GlobalMap: into its chunk cache (activate_chunk), or, for a map with a file, straight
         into the file (GlobalMap._write_chunk) unless the chunk is active in the cache"""
@@ -1437,6 +1472,46 @@ class TSDFMapping:
         origin = self.raycast_rays(pose, np.zeros((0, 3)))[0]
         with self.mutex_:
             rec, _ = self.tsdf_.avg_map().raycast(origin, points_mm, self._diagonal_mm(), targets=True, **kw)
+        if _is_device(points_mm):
+            points_mm = points_mm.to_host() if hasattr(points_mm, "to_host") else points_mm.cpu().numpy()
+        d = np.asarray(points_mm, dtype=np.float64).reshape(-1, 3) - origin.astype(np.float64)
+        return np.where(rec["range_mm"] >= 0, rec["range_mm"].astype(np.float64) - np.sqrt(np.sum(d * d, axis=1)), np.nan)
+
+    def _global_range_mm(self, origin):
+        """the diagonal of the bounding box of the present chunks in mm, capped so that |origin| + range + 2 res fits int32"""
+        res = int(self.params_.map.resolution)
+        keys = np.asarray(self.device_global_map_.keys(), dtype=np.float64).reshape(-1, 3)
+        ext = (keys.max(axis=0) - keys.min(axis=0) + 1.0) * 64.0 * res if len(keys) else np.ones(3)
+        cap = 2 ** 31 - 1 - 2 * res - int(np.max(np.abs(np.asarray(origin, dtype=np.int64))))
+        return int(max(1, min(cap, np.ceil(np.sqrt(np.sum(ext * ext))))))
+
+    def global_raycast(self, pose, dirs=None, max_range_mm=None, **kw):
+        """The predicted scan from `pose` through everything the run has seen, not only the window: the window goes into the
+        chunks of device_global_map exactly as in global_mesh (ws_store_save_box behind wait_shift, under the mapping's lock like a
+        writer), then DeviceGlobalMap.raycast at the map's resolution with the integers of raycast_rays.  dirs None: the OS1-128
+        table; max_range_mm None: the diagonal of the bounding box of the present chunks (capped to what the range check admits).
+        Keywords: lo, hi, any_weight, gradient, targets.  Returns (records, gradient | None)."""
+        if self.device_global_map_ is None:
+            raise WsError("global_raycast: this TSDFMapping has no device_global_map")
+        if kw.get("targets"):
+            origin, d = self.raycast_rays(pose, np.zeros((0, 3)))[0], dirs
+        else:
+            if dirs is None:
+                from .synthetic import os1_128_dirs
+                dirs = os1_128_dirs()
+            origin, d = self.raycast_rays(pose, dirs)
+        self.wait_shift()
+        with self.mutex_:
+            lo, hi = self.local_map_.window()
+            self.device_global_map_.save_box(self.tsdf_, lo, hi)
+            rng = self._global_range_mm(origin) if max_range_mm is None else max_range_mm
+            return self.device_global_map_.raycast(int(self.params_.map.resolution), origin, d, rng, **kw)
+
+    def global_scan_residual(self, points_mm, pose, **kw):
+        """scan_residual against the chunks of device_global_map (global_raycast with the points as targets): the pose may lie
+        anywhere the run has been.  NaN where the ray does not hit within the diagonal of the present chunks' bounding box."""
+        rec, _ = self.global_raycast(pose, points_mm, targets=True, **kw)
+        origin = self.raycast_rays(pose, np.zeros((0, 3)))[0]
         if _is_device(points_mm):
             points_mm = points_mm.to_host() if hasattr(points_mm, "to_host") else points_mm.cpu().numpy()
         d = np.asarray(points_mm, dtype=np.float64).reshape(-1, 3) - origin.astype(np.float64)

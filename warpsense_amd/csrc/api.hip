@@ -1714,6 +1714,191 @@ int ws_debug_store_mesh_timing(ws_store *st, int32_t enable, float ms_out[3])
   return rc;
 }
 
+// ---- the ray cast of the store: ws_map_raycast's rules over the chunks, store_raycast.hip (the semantics are stated in warpsense_hip.h)
+namespace
+{
+// The present chunks the box overlaps, ascending like the directory (the walk of store_mesh_tables): O(chunks of the box's cx range),
+// nothing here follows the volume of the box.
+void store_ray_list(const ws_store *st, const int32_t lo[3], const int32_t hi[3], std::vector<StoreRaySlot> &out)
+{
+  const ChunkRange cr(lo, hi);
+  out.clear();
+  for (auto it = st->dir.lower_bound(StoreKey{cr.c0[0], INT32_MIN, INT32_MIN}); it != st->dir.end() && it->first[0] - cr.c0[0] < cr.nc[0]; ++it)
+  {
+    bool in = it->second.written;
+    for (int k = 1; k < 3; ++k) in = in && it->first[k] >= cr.c0[k] && it->first[k] - cr.c0[k] < cr.nc[k];
+    if (in) out.push_back(StoreRaySlot{it->first[0], it->first[1], it->first[2], it->second.slot});
+  }
+}
+
+int store_raycast_run(ws_store *st, const int32_t lo[3], const int32_t hi[3], const int32_t origin[3], const int32_t *dirs, bool dirs_on_host, size_t n,
+                      int32_t max_range, int32_t res, uint32_t flags, size_t *n_hits)
+{
+  const uint32_t known = WS_RAYCAST_ANY_WEIGHT | WS_RAYCAST_GRADIENT | WS_RAYCAST_TARGETS;
+  if (!st || (flags & ~known) || !origin || (n && !dirs) || ((lo == nullptr) != (hi == nullptr))) return invalid("ws_store_raycast: bad argument");
+  if (lo)
+    for (int k = 0; k < 3; ++k)
+      if (hi[k] < lo[k]) return invalid("ws_store_raycast: hi < lo");
+  if (res <= 0) return invalid("ws_store_raycast: map_resolution <= 0");
+  if (max_range <= 0) return invalid("ws_store_raycast: max_range_mm <= 0");
+  if (res > 1024)
+  {
+    set_error("ws_store_raycast: the resolution must not exceed 1024 mm (the interpolant is carried times res^3 in 64 bits)");
+    return WS_ERR_RANGE;
+  }
+  if (n > ((size_t)1 << 27))
+  {
+    set_error("ws_store_raycast: more than 2^27 rays");
+    return WS_ERR_RANGE;
+  }
+  for (int k = 0; k < 3; ++k)
+  {
+    const int64_t o = origin[k];
+    if ((o < 0 ? -o : o) + (int64_t)max_range + 2 * (int64_t)res > (int64_t)INT32_MAX)
+    {
+      set_error("ws_store_raycast: |origin| + max_range + 2 res does not fit int32");
+      return WS_ERR_RANGE;
+    }
+  }
+  std::lock_guard<std::mutex> lock(st->mu);
+  ws_store::Ray &q = st->ray;
+  StoreRayCall c;
+  c.res = res;
+  std::vector<StoreRaySlot> listed;
+  if (lo)
+  {
+    copy3(c.lo, lo), copy3(c.hi, hi);
+    store_ray_list(st, lo, hi, listed);
+  }
+  else
+  {
+    for (int k = 0; k < 3; ++k) c.lo[k] = INT32_MIN, c.hi[k] = INT32_MAX; // everything
+    for (const auto &kv : st->dir)
+      if (kv.second.written) listed.push_back(StoreRaySlot{kv.first[0], kv.first[1], kv.first[2], kv.second.slot});
+  }
+  if (listed.size() >= (1u << 19))
+  {
+    set_error("ws_store_raycast: the call lists 2^19 present chunks or more");
+    return WS_ERR_RANGE;
+  }
+  c.n_chunks = (uint32_t)listed.size();
+  // the live box: the bounding box of the listed chunks (keys are floor(int32 / 64): 64 k + 63 fits), cut to the box
+  for (int k = 0; k < 3; ++k) c.blo[k] = INT32_MAX, c.bhi[k] = INT32_MIN;
+  for (const StoreRaySlot &e : listed)
+  {
+    const int32_t key[3] = {e.cx, e.cy, e.cz};
+    for (int k = 0; k < 3; ++k) c.blo[k] = std::min(c.blo[k], key[k] * STORE_CS), c.bhi[k] = std::max(c.bhi[k], key[k] * STORE_CS + STORE_CS - 1);
+  }
+  for (int k = 0; k < 3; ++k) c.blo[k] = std::max(c.blo[k], c.lo[k]), c.bhi[k] = std::min(c.bhi[k], c.hi[k]);
+  WS_TRY(q.timer.arm());
+  if (n_hits) *n_hits = 0;
+  q.n = 0; // (whatever happens from here on, the old result is gone: its buffers may be replaced)
+  q.has_grad = false;
+  if (n == 0) return WS_OK;
+  hipStream_t s = st->ctx->stream;
+  const bool grad = (flags & WS_RAYCAST_GRADIENT) != 0;
+  WS_TRY(q.hits.alloc(1));
+  const size_t places = c.n_chunks ? store_ray_table_slots(c.n_chunks) : 0;
+  if (n > q.rec.cap || (grad && n > q.grad.cap) || (dirs_on_host && n > q.dirs.cap) || places > q.table_host.cap)
+  {
+    WS_HIP(hipStreamSynchronize(s));
+    WS_TRY(q.rec.grow(n, 16));
+    if (grad) WS_TRY(q.grad.grow(n, 3 * sizeof(int32_t)));
+    if (dirs_on_host) WS_TRY(q.dirs.grow(n, 3 * sizeof(int32_t)));
+    if (places > q.table_host.cap)
+    {
+      WS_TRY(q.table_host.alloc(places, sizeof(StoreRaySlot), HostBlock::PINNED));
+      WS_TRY(q.table_dev.alloc(places, sizeof(StoreRaySlot)));
+    }
+  }
+  if (c.n_chunks) store_ray_table_fill(listed.data(), listed.size(), q.table_host.as<StoreRaySlot>());
+  q.timer.mark(0, s);
+  if (dirs_on_host)
+  {
+    WS_HIP(hipMemcpyAsync(q.dirs.p, dirs, n * 3 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    dirs = static_cast<const int32_t *>(q.dirs.p);
+  }
+  const int rc = launch_store_raycast(st, c, origin, dirs, n, max_range, flags);
+  const hipError_t e = hipStreamSynchronize(s); // (also after a failed enqueue: the pinned table is free again when the call returns)
+  if (rc != WS_OK) return rc;
+  WS_HIP(e);
+  q.n = n;
+  q.has_grad = grad;
+  if (n_hits) *n_hits = (size_t)*q.hits.host;
+  return WS_OK;
+}
+} // namespace
+
+int ws_store_raycast(ws_store *st, const int32_t lo[3], const int32_t hi[3], const int32_t origin_mm[3], const int32_t *dirs_host, size_t n, int32_t max_range_mm,
+                     int32_t map_resolution, uint32_t flags, size_t *n_hits)
+{
+  return store_raycast_run(st, lo, hi, origin_mm, dirs_host, true, n, max_range_mm, map_resolution, flags, n_hits);
+}
+
+int ws_store_raycast_dev(ws_store *st, const int32_t lo[3], const int32_t hi[3], const int32_t origin_mm[3], const int32_t *dirs_dev, size_t n, int32_t max_range_mm,
+                         int32_t map_resolution, uint32_t flags, size_t *n_hits)
+{
+  return store_raycast_run(st, lo, hi, origin_mm, dirs_dev, false, n, max_range_mm, map_resolution, flags, n_hits);
+}
+
+const void *ws_store_raycast_records_dev(const ws_store *st, size_t *n)
+{
+  if (n) *n = st ? st->ray.n : 0;
+  return st && st->ray.n ? st->ray.rec.p : nullptr;
+}
+
+const int32_t *ws_store_raycast_gradient_dev(const ws_store *st, size_t *n)
+{
+  const bool have = st && st->ray.has_grad && st->ray.n;
+  if (n) *n = have ? st->ray.n : 0;
+  return have ? static_cast<const int32_t *>(st->ray.grad.p) : nullptr;
+}
+
+int ws_store_raycast_download(ws_store *st, void *records_host, int32_t *gradient_host, size_t capacity_rays, size_t *n_out)
+{
+  if (!st || !n_out) return invalid("ws_store_raycast_download: NULL argument");
+  std::lock_guard<std::mutex> lock(st->mu);
+  *n_out = st->ray.n;
+  const size_t k = std::min(capacity_rays, st->ray.n);
+  if (k == 0) return WS_OK;
+  if (gradient_host && !st->ray.has_grad) return invalid("ws_store_raycast_download: the last ws_store_raycast did not ask for WS_RAYCAST_GRADIENT");
+  if (records_host) WS_HIP(hipMemcpyAsync(records_host, st->ray.rec.p, k * 16, hipMemcpyDeviceToHost, st->ctx->stream));
+  if (gradient_host) WS_HIP(hipMemcpyAsync(gradient_host, st->ray.grad.p, k * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, st->ctx->stream));
+  WS_HIP(hipStreamSynchronize(st->ctx->stream));
+  return WS_OK;
+}
+
+int ws_debug_store_raycast_timing(ws_store *st, int32_t enable, float ms_out[3])
+{
+  if (!st) return invalid("ws_debug_store_raycast_timing: store is NULL");
+  std::lock_guard<std::mutex> lock(st->mu);
+  static const int pairs[3][2] = {{0, 1}, {1, 2}, {2, 3}};
+  const int rc = st->ray.timer.read(ms_out, pairs, 3, st->ctx->stream);
+  if (rc == WS_OK) st->ray.timer.set(enable);
+  return rc;
+}
+
+int ws_debug_store_raycast_table(const int32_t *keys_slots, size_t n, int32_t *table, size_t capacity_places, size_t *n_places)
+{
+  if ((n && table && !keys_slots) || !n_places || n >= (1u << 19)) return invalid("ws_debug_store_raycast_table: bad argument");
+  *n_places = store_ray_table_slots(n);
+  if (!table) return WS_OK;
+  if (capacity_places < *n_places) return invalid("ws_debug_store_raycast_table: the table does not fit");
+  std::vector<StoreRaySlot> in(n), out(*n_places);
+  if (n) std::memcpy(in.data(), keys_slots, n * sizeof(StoreRaySlot));
+  store_ray_table_fill(in.data(), n, out.data());
+  std::memcpy(table, out.data(), out.size() * sizeof(StoreRaySlot));
+  return WS_OK;
+}
+
+uint32_t ws_debug_store_raycast_find(const int32_t *table, size_t n_places, const int32_t key[3])
+{
+  if (!table || !key || n_places < 2 || (n_places & (n_places - 1))) return STORE_ABSENT;
+  std::vector<StoreRaySlot> t(n_places);
+  std::memcpy(t.data(), table, n_places * sizeof(StoreRaySlot));
+  return store_ray_find(t.data(), (uint32_t)n_places - 1u, key[0], key[1], key[2]);
+}
+
 int ws_map_get_params(const ws_map *m, int which, int32_t size[3], int32_t pos[3], int32_t offset[3])
 {
   if (!m || (which != WS_MAP_AVG && which != WS_MAP_NEW)) return invalid("ws_map_get_params: bad argument");

@@ -633,9 +633,23 @@ struct ws_store
     size_t nv = 0, nf = 0;               // vertices and faces of the last call
     void release() { timer.release(), total.release(), table_host.release(); for (ws::DevBuf *b : {&scratch, &table_dev, &vert, &face}) b->release(); }
   } mesh;
+  // ws_store_raycast (store_raycast.hip): the result of the last call, apart from the mesh's, allocated on first use and grown on
+  // demand like those of ws_map::Raycast; the store's mutex serialises the calls
+  struct Ray
+  {
+    ws::QueryTimer timer;                // 0 upload 1 march 2 gradient 3
+    ws::HostBlock table_host;            // StoreRaySlot, pinned: the call's chunk lookup; free again when the call returns, which synchronises
+    ws::DevBuf table_dev;                // ... and the copy the kernels read
+    ws::DevBuf dirs, rec, grad;          // int32 [rays][3] staging of host directions; 16-byte records; int32 [rays][3]
+    ws::DevCounter hits;                 // records with range_mm >= 0
+    size_t n = 0;                        // rays of the last call
+    bool has_grad = false;               // the last call also wrote `grad`
+    void release() { timer.release(), hits.release(), table_host.release(); for (ws::DevBuf *b : {&table_dev, &dirs, &rec, &grad}) b->release(); }
+  } ray;
   void release()
   {
     mesh.release();
+    ray.release();
     for (ws::DevBuf &b : segs) b.release();
     segs.clear(), seg_ptr.clear();
     seg_tab.release();
@@ -726,6 +740,56 @@ struct StoreMeshCall
 size_t store_mesh_table_bytes(size_t n_chunks);
 int launch_store_mesh_count(ws_store *st, const StoreMeshCall &c);
 int launch_store_mesh_emit(ws_store *st, const StoreMeshCall &c);
+
+// store_raycast.hip: the march of ws_raycast.h over the chunks the call lists.  The kernels find a chunk through an open-addressing
+// table key -> slot of a power-of-two size >= 2 x listed chunks (linear probing from store_ray_hash; an empty place has slot
+// STORE_ABSENT), which the host has written into ws_store::ray.table_host; the hit count arrives in ws_store::ray.hits.host after a
+// stream synchronise
+struct alignas(16) StoreRaySlot
+{
+  int32_t cx, cy, cz;
+  uint32_t slot;
+};
+__host__ __device__ inline uint32_t store_ray_hash(int32_t cx, int32_t cy, int32_t cz)
+{
+  uint32_t h = (uint32_t)cx * 0x9e3779b1u ^ (uint32_t)cy * 0x85ebca77u ^ (uint32_t)cz * 0xc2b2ae3du;
+  return h ^ (h >> 15);
+}
+inline size_t store_ray_table_slots(size_t n_chunks)
+{
+  size_t s = 2;
+  while (s < 2 * n_chunks) s <<= 1;
+  return s;
+}
+// the table of `n` chunks ({cx, cy, cz, slot} each, distinct keys) into table[store_ray_table_slots(n)]
+inline void store_ray_table_fill(const StoreRaySlot *chunks, size_t n, StoreRaySlot *table)
+{
+  const size_t slots = store_ray_table_slots(n);
+  for (size_t i = 0; i < slots; ++i) table[i] = StoreRaySlot{0, 0, 0, STORE_ABSENT};
+  for (size_t i = 0; i < n; ++i)
+  {
+    size_t at = store_ray_hash(chunks[i].cx, chunks[i].cy, chunks[i].cz) & (slots - 1);
+    while (table[at].slot != STORE_ABSENT) at = (at + 1) & (slots - 1);
+    table[at] = chunks[i];
+  }
+}
+// the slot of a chunk, STORE_ABSENT if the table does not list it (at least half of the places are empty: the probe ends)
+__host__ __device__ inline uint32_t store_ray_find(const StoreRaySlot *table, uint32_t mask, int32_t cx, int32_t cy, int32_t cz)
+{
+  for (uint32_t at = store_ray_hash(cx, cy, cz) & mask;; at = (at + 1u) & mask)
+  {
+    const StoreRaySlot e = table[at];
+    if (e.slot == STORE_ABSENT || (e.cx == cx && e.cy == cy && e.cz == cz)) return e.slot;
+  }
+}
+struct StoreRayCall
+{
+  uint32_t n_chunks;    // listed chunks (< 2^19); 0: every record is a no-hit
+  int32_t res;
+  int32_t lo[3], hi[3]; // the box, inclusive world voxels
+  int32_t blo[3], bhi[3]; // the bounding box of the listed chunks, cut to the box
+};
+int launch_store_raycast(ws_store *st, const StoreRayCall &c, const int32_t origin[3], const int32_t *dirs_dev, size_t n, int32_t max_range, uint32_t flags);
 
 int launch_reg_iteration(ws_reg *r, const ws_map *m, int32_t res, uint32_t flags, int32_t k);
 // reg_pass_kernel over points [first, first + count): from the newest state (first the update from `sums` if `apply`) into `sums`;
