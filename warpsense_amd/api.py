@@ -482,6 +482,50 @@ class GlobalMap:
         return buf
 
 
+def _mesh_call(L, name, owner, lead, lo, hi, tail, any_weight, device):
+    """The mesh call `name` (ws_map_mesh, ws_store_mesh) on owner.handle and its result: `lead` and `tail` are the arguments of the
+    entry point before and behind the box.  owner keeps the device tensors' memory alive."""
+    if (lo is None) != (hi is None):
+        raise WsError("mesh: give both lo and hi, or neither")
+    nv, nf = C.c_size_t(0), C.c_size_t(0)
+    flags = _lib.WS_MESH_ANY_WEIGHT if any_weight else _lib.WS_MESH_DEFAULT
+    check(getattr(L, name)(owner.handle, *lead, _ptr(_i3(lo)) if lo is not None else None, _ptr(_i3(hi)) if hi is not None else None, *tail,
+                           flags, C.byref(nv), C.byref(nf)), name)
+    nv, nf = int(nv.value), int(nf.value)
+    if device:
+        cnt = C.c_size_t(0)
+        return (_device_tensor(getattr(L, name + "_vertices_dev")(owner.handle, C.byref(cnt)), (nv, 4), "<i4", owner),
+                _device_tensor(getattr(L, name + "_faces_dev")(owner.handle, C.byref(cnt)), (nf, 3), "<i4", owner))
+    vert, face = np.empty(nv, dtype=VERT), np.empty((nf, 3), dtype=np.uint32)
+    gv, gf = C.c_size_t(0), C.c_size_t(0)
+    check(getattr(L, name + "_download")(owner.handle, _ptr(vert), _ptr(face), nv, nf, C.byref(gv), C.byref(gf)), name + "_download")
+    if (int(gv.value), int(gf.value)) != (nv, nf):
+        raise WsError("mesh: another call replaced the result before it was downloaded")
+    return vert, face
+
+
+def _raycast_call(L, name, handle, lead, origin_mm, dirs, max_range_mm, tail, any_weight, gradient, targets):
+    """The ray cast `name` (ws_map_raycast, ws_store_raycast; name + "_dev" for directions on the device) and its download: `lead` are
+    the arguments of the entry point before the origin, `tail` those between the range and the flags.  Returns (records, gradient |
+    None, hits)."""
+    n = int(dirs.shape[0])
+    flags = ((_lib.WS_RAYCAST_ANY_WEIGHT if any_weight else 0) | (_lib.WS_RAYCAST_GRADIENT if gradient else 0)
+             | (_lib.WS_RAYCAST_TARGETS if targets else 0))
+    hits = C.c_size_t(0)
+    if _is_device(dirs):
+        name_call, d = name + "_dev", dirs
+    else:
+        name_call, d = name, np.ascontiguousarray(dirs, dtype=np.int32).reshape(-1, 3)
+    check(getattr(L, name_call)(handle, *lead, _ptr(_i3(origin_mm)), _ptr(d), n, int(max_range_mm), *tail, flags, C.byref(hits)), name_call)
+    rec = np.empty(n, dtype=RAY)
+    grad = np.empty((n, 3), dtype=np.int32) if gradient else None
+    got = C.c_size_t(0)
+    check(getattr(L, name + "_download")(handle, _ptr(rec), _ptr(grad), n, C.byref(got)), name + "_download")
+    if int(got.value) != n:
+        raise WsError("raycast: another call replaced the result before it was downloaded")
+    return rec, grad, int(hits.value)
+
+
 class DeviceGlobalMap:
     """The global map in device memory (ws_store, include/warpsense_hip.h): the device twin of GlobalMap.  64^3-voxel chunks of raw
     uint32 entries in HBM, index x*4096 + y*64 + z, keyed by floor(world voxel / 64); chunks never seen hold the default entry.  The
@@ -561,23 +605,7 @@ class DeviceGlobalMap:
 
         Returns (vertices, faces) like DeviceMapMemWrapper.mesh; device=True: torch tensors that ALIAS the store's buffers, valid
         until the next mesh() on this store."""
-        if (lo is None) != (hi is None):
-            raise WsError("mesh: give both lo and hi, or neither")
-        nv, nf = C.c_size_t(0), C.c_size_t(0)
-        flags = _lib.WS_MESH_ANY_WEIGHT if any_weight else _lib.WS_MESH_DEFAULT
-        check(self._L.ws_store_mesh(self.handle, _ptr(_i3(lo)) if lo is not None else None, _ptr(_i3(hi)) if hi is not None else None,
-                                    int(resolution), flags, C.byref(nv), C.byref(nf)), "ws_store_mesh")
-        nv, nf = int(nv.value), int(nf.value)
-        if device:
-            cnt = C.c_size_t(0)
-            return (_device_tensor(self._L.ws_store_mesh_vertices_dev(self.handle, C.byref(cnt)), (nv, 4), "<i4", self),
-                    _device_tensor(self._L.ws_store_mesh_faces_dev(self.handle, C.byref(cnt)), (nf, 3), "<i4", self))
-        vert, face = np.empty(nv, dtype=VERT), np.empty((nf, 3), dtype=np.uint32)
-        gv, gf = C.c_size_t(0), C.c_size_t(0)
-        check(self._L.ws_store_mesh_download(self.handle, _ptr(vert), _ptr(face), nv, nf, C.byref(gv), C.byref(gf)), "ws_store_mesh_download")
-        if (int(gv.value), int(gf.value)) != (nv, nf):
-            raise WsError("mesh: another call replaced the result before it was downloaded")
-        return vert, face
+        return _mesh_call(self._L, "ws_store_mesh", self, (), lo, hi, (int(resolution),), any_weight, device)
 
     def mesh_timing(self, enable: int = -1):
         """device milliseconds of the count passes, the scan and the emit passes of the last mesh() (ws_debug_store_mesh_timing)"""
@@ -593,25 +621,9 @@ class DeviceGlobalMap:
         (records, gradient | None) are those of DeviceMapMemWrapper.raycast; `last_hits` keeps the call's number of hits."""
         if (lo is None) != (hi is None):
             raise WsError("raycast: give both lo and hi, or neither")
-        n = int(dirs.shape[0])
-        flags = ((_lib.WS_RAYCAST_ANY_WEIGHT if any_weight else 0) | (_lib.WS_RAYCAST_GRADIENT if gradient else 0)
-                 | (_lib.WS_RAYCAST_TARGETS if targets else 0))
         box = (_ptr(_i3(lo)) if lo is not None else None, _ptr(_i3(hi)) if hi is not None else None)
-        hits = C.c_size_t(0)
-        if _is_device(dirs):
-            check(self._L.ws_store_raycast_dev(self.handle, *box, _ptr(_i3(origin_mm)), _ptr(dirs), n, int(max_range_mm), int(resolution), flags,
-                                               C.byref(hits)), "ws_store_raycast_dev")
-        else:
-            d = np.ascontiguousarray(dirs, dtype=np.int32).reshape(-1, 3)
-            check(self._L.ws_store_raycast(self.handle, *box, _ptr(_i3(origin_mm)), _ptr(d), n, int(max_range_mm), int(resolution), flags,
-                                           C.byref(hits)), "ws_store_raycast")
-        rec = np.empty(n, dtype=RAY)
-        grad = np.empty((n, 3), dtype=np.int32) if gradient else None
-        got = C.c_size_t(0)
-        check(self._L.ws_store_raycast_download(self.handle, _ptr(rec), _ptr(grad), n, C.byref(got)), "ws_store_raycast_download")
-        if int(got.value) != n:
-            raise WsError("raycast: another call replaced the result before it was downloaded")
-        self.last_hits = int(hits.value)
+        rec, grad, self.last_hits = _raycast_call(self._L, "ws_store_raycast", self.handle, box, origin_mm, dirs, max_range_mm, (int(resolution),),
+                                                  any_weight, gradient, targets)
         return rec, grad
 
     def raycast_timing(self, enable: int = -1):
@@ -850,24 +862,7 @@ class DeviceMapMemWrapper:
         uint32 array of vertex indices, normals towards the outside.
         device=True: torch tensors on the GPU instead -- (n, 4) int32 and (n, 3) int32 -- that ALIAS the library's buffers: valid
         until the next mesh() on this TSDFCuda, copy them (.clone()) to keep them."""
-        t = self._t
-        if (lo is None) != (hi is None):
-            raise WsError("mesh: give both lo and hi, or neither")
-        nv, nf = C.c_size_t(0), C.c_size_t(0)
-        flags = _lib.WS_MESH_ANY_WEIGHT if any_weight else _lib.WS_MESH_DEFAULT
-        check(t._L.ws_map_mesh(t.handle, self._which, _ptr(_i3(lo)) if lo is not None else None, _ptr(_i3(hi)) if hi is not None else None,
-                               flags, C.byref(nv), C.byref(nf)), "ws_map_mesh")
-        nv, nf = int(nv.value), int(nf.value)
-        if device:
-            cnt = C.c_size_t(0)
-            return (_device_tensor(t._L.ws_map_mesh_vertices_dev(t.handle, C.byref(cnt)), (nv, 4), "<i4", t),
-                    _device_tensor(t._L.ws_map_mesh_faces_dev(t.handle, C.byref(cnt)), (nf, 3), "<i4", t))
-        vert, face = np.empty(nv, dtype=VERT), np.empty((nf, 3), dtype=np.uint32)
-        gv, gf = C.c_size_t(0), C.c_size_t(0)
-        check(t._L.ws_map_mesh_download(t.handle, _ptr(vert), _ptr(face), nv, nf, C.byref(gv), C.byref(gf)), "ws_map_mesh_download")
-        if (int(gv.value), int(gf.value)) != (nv, nf):
-            raise WsError("mesh: another call replaced the result before it was downloaded")
-        return vert, face
+        return _mesh_call(self._t._L, "ws_map_mesh", self._t, (self._which,), lo, hi, (), any_weight, device)
 
     def raycast(self, origin_mm, dirs, max_range_mm, any_weight=False, gradient=False, targets=False):
         """Ray cast of this map on the device (ws_map_raycast; the rules are stated in include/warpsense_hip.h): per ray the first
@@ -879,25 +874,8 @@ class DeviceMapMemWrapper:
         Returns (records, gradient): a numpy array of dtype RAY (x_mm, y_mm, z_mm, range_mm; no hit: 0, 0, 0, -1) in ray order
         and, with gradient=True, an (n, 3) int32 array of central differences of the TSDF value at the hit (towards the outside,
         not normalised; zeros where a neighbour is unobserved), else None.  `last_hits` keeps the call's number of hits."""
-        t = self._t
-        n = int(dirs.shape[0])
-        flags = ((_lib.WS_RAYCAST_ANY_WEIGHT if any_weight else 0) | (_lib.WS_RAYCAST_GRADIENT if gradient else 0)
-                 | (_lib.WS_RAYCAST_TARGETS if targets else 0))
-        hits = C.c_size_t(0)
-        if _is_device(dirs):
-            check(t._L.ws_map_raycast_dev(t.handle, self._which, _ptr(_i3(origin_mm)), _ptr(dirs), n, int(max_range_mm), flags, C.byref(hits)),
-                  "ws_map_raycast_dev")
-        else:
-            d = np.ascontiguousarray(dirs, dtype=np.int32).reshape(-1, 3)
-            check(t._L.ws_map_raycast(t.handle, self._which, _ptr(_i3(origin_mm)), _ptr(d), n, int(max_range_mm), flags, C.byref(hits)),
-                  "ws_map_raycast")
-        rec = np.empty(n, dtype=RAY)
-        grad = np.empty((n, 3), dtype=np.int32) if gradient else None
-        got = C.c_size_t(0)
-        check(t._L.ws_map_raycast_download(t.handle, _ptr(rec), _ptr(grad), n, C.byref(got)), "ws_map_raycast_download")
-        if int(got.value) != n:
-            raise WsError("raycast: another call replaced the result before it was downloaded")
-        self.last_hits = int(hits.value)
+        rec, grad, self.last_hits = _raycast_call(self._t._L, "ws_map_raycast", self._t.handle, (self._which,), origin_mm, dirs, max_range_mm, (),
+                                                  any_weight, gradient, targets)
         return rec, grad
 
     def distance(self, lo=None, hi=None, max_dist_vox=20, unknown_occupied=False, columns=False, any_weight=False, device=False):

@@ -632,9 +632,9 @@ int ws_map_surface_download(ws_map *m, void *records_host, float *marker_host, s
 }
 
 // ws_debug_*_timing: the times of the last call between the event pairs of `pairs`, then the switch
-static int query_timing(ws_map *m, QueryTimer &t, int32_t enable, float *ms_out, const int (*pairs)[2], int n)
+static int query_timing(hipStream_t s, QueryTimer &t, int32_t enable, float *ms_out, const int (*pairs)[2], int n)
 {
-  const int rc = t.read(ms_out, pairs, n, m->ctx->stream);
+  const int rc = t.read(ms_out, pairs, n, s);
   if (rc == WS_OK) t.set(enable);
   return rc;
 }
@@ -644,8 +644,170 @@ int ws_debug_surface_timing(ws_map *m, int32_t enable, float ms_out[3])
   if (!m) return invalid("ws_debug_surface_timing: map is NULL");
   std::lock_guard<std::mutex> lock(m->surf.mu);
   static const int pairs[3][2] = {{0, 1}, {1, 2}, {3, 4}};
-  return query_timing(m, m->surf.timer, enable, ms_out, pairs, 3);
+  return query_timing(m->ctx->stream, m->surf.timer, enable, ms_out, pairs, 3);
 }
+
+// ---- mesh and ray cast: one host core for the window of a map (map_mesh.hip, map_raycast.hip) and for the chunks of the store
+// (store_mesh.hip, store_raycast.hip; their entry points are further down).  An entry point checks what is its own, takes its lock and
+// hands the shared flow its result holder, its stream and, as lambdas, the launchers of its source; `name` starts the refusal texts.
+extern "C++" {
+static int range_error(const char *name, const char *what)
+{
+  set_error(std::string(name) + what);
+  return WS_ERR_RANGE;
+}
+
+static int mesh_corners_fit(const int32_t lo[3], const int32_t hi[3], int32_t res, const char *name)
+{
+  for (int k = 0; k < 3; ++k)
+    for (int64_t c : {(int64_t)lo[k], (int64_t)hi[k]})
+      if (((c < 0 ? -c : c) + 1) * (int64_t)res > (int64_t)INT32_MAX) return range_error(name, ": a box corner in millimetres does not fit int32");
+  return WS_OK;
+}
+
+static int mesh_publish(MeshResult &q, size_t nv, size_t nf, size_t *n_vertices, size_t *n_faces)
+{
+  q.nv = nv, q.nf = nf;
+  if (n_vertices) *n_vertices = nv;
+  if (n_faces) *n_faces = nf;
+  return WS_OK;
+}
+
+// The flow of a mesh call over `n_words` words (< 2^31), from "the old result is dropped" to the publish.  count() and emit() enqueue
+// the passes of the source and return at once; what a source owes its caller after a failed enqueue is theirs (store_enqueued).
+template <typename Count, typename Emit>
+static int mesh_run(MeshResult &q, hipStream_t s, const char *name, uint64_t n_words, size_t *n_vertices, size_t *n_faces, Count count, Emit emit)
+{
+  mesh_publish(q, 0, 0, n_vertices, n_faces); // (whatever happens from here on, the old result is gone: its buffers may be replaced)
+  WS_TRY(q.total.alloc(2, false));
+  const size_t need = mesh_scratch_bytes(n_words);
+  if (need > q.scratch.cap)
+  {
+    WS_HIP(hipStreamSynchronize(s));
+    WS_TRY(q.scratch.grow(need, 1));
+  }
+  WS_TRY(count());
+  WS_HIP(hipStreamSynchronize(s)); // the one host read the call needs: the outputs are sized from the two totals
+  const unsigned long long nv = q.total.host[0], nq = q.total.host[1];
+  if (nv > 0xffffffffull) return range_error(name, ": more than 2^32 - 1 vertices");
+  WS_TRY(q.vert.grow((size_t)nv, 16));
+  WS_TRY(q.face.grow((size_t)nq * 2, 12));
+  if (nv)
+  {
+    WS_TRY(emit());
+    WS_HIP(hipStreamSynchronize(s));
+  }
+  return mesh_publish(q, (size_t)nv, (size_t)nq * 2, n_vertices, n_faces);
+}
+
+static const void *mesh_vertices_dev(const MeshResult *q, size_t *n)
+{
+  if (n) *n = q ? q->nv : 0;
+  return q && q->nv ? q->vert.p : nullptr;
+}
+
+static const uint32_t *mesh_faces_dev(const MeshResult *q, size_t *n)
+{
+  if (n) *n = q ? q->nf : 0;
+  return q && q->nf ? static_cast<const uint32_t *>(q->face.p) : nullptr;
+}
+
+static int mesh_download(const MeshResult &q, hipStream_t s, void *vertices_host, uint32_t *faces_host, size_t cap_vertices, size_t cap_faces, size_t *n_vertices,
+                         size_t *n_faces)
+{
+  *n_vertices = q.nv;
+  *n_faces = q.nf;
+  const size_t kv = vertices_host ? std::min(cap_vertices, q.nv) : 0, kf = faces_host ? std::min(cap_faces, q.nf) : 0;
+  if (kv) WS_HIP(hipMemcpyAsync(vertices_host, q.vert.p, kv * 16, hipMemcpyDeviceToHost, s));
+  if (kf) WS_HIP(hipMemcpyAsync(faces_host, q.face.p, kf * 12, hipMemcpyDeviceToHost, s));
+  if (kv || kf) WS_HIP(hipStreamSynchronize(s));
+  return WS_OK;
+}
+static const int MESH_PAIRS[3][2] = {{0, 1}, {1, 2}, {3, 4}};
+
+// The argument check of a ray cast.  `bad`: what the entry point found wrong with its own leading arguments; more(): its further
+// checks, which come before those of the ranges.
+template <typename More>
+static int raycast_check(const char *name, bool bad, const int32_t *origin, const int32_t *dirs, size_t n, int32_t max_range, int32_t res, uint32_t flags, More more)
+{
+  const uint32_t known = WS_RAYCAST_ANY_WEIGHT | WS_RAYCAST_GRADIENT | WS_RAYCAST_TARGETS;
+  if (bad || (flags & ~known) || !origin || (n && !dirs)) return invalid(std::string(name) + ": bad argument");
+  WS_TRY(more());
+  if (max_range <= 0) return invalid(std::string(name) + ": max_range_mm <= 0");
+  if (res > 1024) return range_error(name, ": the resolution must not exceed 1024 mm (the interpolant is carried times res^3 in 64 bits)");
+  if (n > ((size_t)1 << 27)) return range_error(name, ": more than 2^27 rays");
+  for (int k = 0; k < 3; ++k)
+  {
+    const int64_t o = origin[k];
+    if ((o < 0 ? -o : o) + (int64_t)max_range + 2 * (int64_t)res > (int64_t)INT32_MAX) return range_error(name, ": |origin| + max_range + 2 res does not fit int32");
+  }
+  return WS_OK;
+}
+
+// The flow of a ray cast whose arguments have passed raycast_check: arm, drop the old result, grow, upload the directions, launch,
+// synchronise, publish.  own_room: the source has buffers of its own that must grow; prepare() grows them (the stream has been
+// synchronised then) and fills them; launch(directions on the device) enqueues the passes of the source, like count() of mesh_run.
+template <typename Prepare, typename Launch>
+static int raycast_run(RayResult &q, hipStream_t s, const int32_t *dirs, bool dirs_on_host, size_t n, uint32_t flags, size_t *n_hits, bool own_room, Prepare prepare,
+                       Launch launch)
+{
+  WS_TRY(q.timer.arm());
+  if (n_hits) *n_hits = 0;
+  q.n = 0; // (whatever happens from here on, the old result is gone: its buffers may be replaced)
+  q.has_grad = false;
+  if (n == 0) return WS_OK;
+  const bool grad = (flags & WS_RAYCAST_GRADIENT) != 0;
+  WS_TRY(q.hits.alloc(1));
+  if (n > q.rec.cap || (grad && n > q.grad.cap) || (dirs_on_host && n > q.dirs.cap) || own_room)
+  {
+    WS_HIP(hipStreamSynchronize(s));
+    WS_TRY(q.rec.grow(n, 16));
+    if (grad) WS_TRY(q.grad.grow(n, 3 * sizeof(int32_t)));
+    if (dirs_on_host) WS_TRY(q.dirs.grow(n, 3 * sizeof(int32_t)));
+  }
+  WS_TRY(prepare());
+  q.timer.mark(0, s);
+  if (dirs_on_host)
+  {
+    WS_HIP(hipMemcpyAsync(q.dirs.p, dirs, n * 3 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    dirs = static_cast<const int32_t *>(q.dirs.p);
+  }
+  WS_TRY(launch(dirs));
+  WS_HIP(hipStreamSynchronize(s));
+  q.n = n;
+  q.has_grad = grad;
+  if (n_hits) *n_hits = (size_t)*q.hits.host;
+  return WS_OK;
+}
+
+static const void *raycast_records_dev(const RayResult *q, size_t *n)
+{
+  if (n) *n = q ? q->n : 0;
+  return q && q->n ? q->rec.p : nullptr;
+}
+
+static const int32_t *raycast_gradient_dev(const RayResult *q, size_t *n)
+{
+  const bool have = q && q->has_grad && q->n;
+  if (n) *n = have ? q->n : 0;
+  return have ? static_cast<const int32_t *>(q->grad.p) : nullptr;
+}
+
+// `name`, `call`: the download entry point, and the entry point whose flag it misses
+static int raycast_download(const RayResult &q, hipStream_t s, const char *name, const char *call, void *records_host, int32_t *gradient_host, size_t capacity_rays,
+                            size_t *n_out)
+{
+  *n_out = q.n;
+  const size_t k = std::min(capacity_rays, q.n);
+  if (k == 0) return WS_OK;
+  if (gradient_host && !q.has_grad) return invalid(std::string(name) + ": the last " + call + " did not ask for WS_RAYCAST_GRADIENT");
+  if (records_host) WS_HIP(hipMemcpyAsync(records_host, q.rec.p, k * 16, hipMemcpyDeviceToHost, s));
+  if (gradient_host) WS_HIP(hipMemcpyAsync(gradient_host, q.grad.p, k * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  WS_HIP(hipStreamSynchronize(s));
+  return WS_OK;
+}
+static const int RAY_PAIRS[3][2] = {{0, 1}, {1, 2}, {2, 3}};
+} // extern "C++"
 
 // ---- mesh: naive surface nets over a device map, map_mesh.hip (the rules are stated in warpsense_hip.h)
 int ws_map_mesh(ws_map *m, int which, const int32_t lo[3], const int32_t hi[3], uint32_t flags, size_t *n_vertices, size_t *n_faces)
@@ -654,197 +816,81 @@ int ws_map_mesh(ws_map *m, int which, const int32_t lo[3], const int32_t hi[3], 
     return invalid("ws_map_mesh: bad argument");
   WS_SETTLE(m);
   std::lock_guard<std::mutex> lock(m->mesh.mu);
-  ws_map::Mesh &q = m->mesh;
-  int rc = q.timer.arm();
+  MeshResult &q = m->mesh;
+  WS_TRY(q.timer.arm());
   int32_t l[3], ext[3];
-  if (rc == WS_OK) rc = resolve_box(m, which, lo, hi, true, "ws_map_mesh", l, ext);
-  if (rc != WS_OK) return rc;
-  for (int k = 0; k < 3; ++k)
-    for (int64_t c : {(int64_t)l[k], (int64_t)l[k] + ext[k] - 1})
-      if (((c < 0 ? -c : c) + 1) * (int64_t)m->res > (int64_t)INT32_MAX)
-      {
-        set_error("ws_map_mesh: a box corner in millimetres does not fit int32");
-        return WS_ERR_RANGE;
-      }
-  q.nv = q.nf = 0;
-  if (n_vertices) *n_vertices = 0;
-  if (n_faces) *n_faces = 0;
-  hipStream_t s = m->ctx->stream;
+  WS_TRY(resolve_box(m, which, lo, hi, true, "ws_map_mesh", l, ext));
+  const int32_t h[3] = {l[0] + (ext[0] - 1), l[1] + (ext[1] - 1), l[2] + (ext[2] - 1)}; // (a voxel of the window)
+  WS_TRY(mesh_corners_fit(l, h, m->res, "ws_map_mesh"));
+  mesh_publish(q, 0, 0, n_vertices, n_faces);
   const uint64_t n_words = (uint64_t)ext[0] * (uint64_t)ext[1] * (uint64_t)((ext[2] + 63) / 64);
-  if (n_words >= (1ull << 31))
-  {
-    set_error("ws_map_mesh: box too large (columns x 64-voxel words must stay below 2^31)");
-    return WS_ERR_RANGE;
-  }
-  rc = q.total.alloc(2, false);
-  if (rc != WS_OK) return rc;
+  if (n_words >= (1ull << 31)) return range_error("ws_map_mesh", ": box too large (columns x 64-voxel words must stay below 2^31)");
   if (ext[0] < 2 || ext[1] < 2 || ext[2] < 2) return map_take_error(m); // one voxel thick along an axis: no cells
-  WS_HIP(hipStreamSynchronize(s));
-  rc = q.scratch.grow(mesh_scratch_bytes(n_words), 1);
-  if (rc != WS_OK) return rc;
-  rc = launch_mesh_count(m, which, l, ext, flags);
-  if (rc != WS_OK) return rc;
-  WS_HIP(hipStreamSynchronize(s)); // the one host read the call needs: the outputs are sized from the two totals
-  const unsigned long long nv = q.total.host[0], nq = q.total.host[1];
-  if (nv > 0xffffffffull)
-  {
-    set_error("ws_map_mesh: more than 2^32 - 1 vertices");
-    return WS_ERR_RANGE;
-  }
-  rc = q.vert.grow((size_t)nv, 16);
-  if (rc == WS_OK) rc = q.face.grow((size_t)nq * 2, 12);
-  if (rc != WS_OK) return rc;
-  if (nv)
-  {
-    rc = launch_mesh_emit(m, which, l, ext, flags);
-    if (rc != WS_OK) return rc;
-    WS_HIP(hipStreamSynchronize(s));
-  }
-  q.nv = (size_t)nv;
-  q.nf = (size_t)nq * 2;
-  if (n_vertices) *n_vertices = q.nv;
-  if (n_faces) *n_faces = q.nf;
+  WS_TRY(mesh_run(
+      q, m->ctx->stream, "ws_map_mesh", n_words, n_vertices, n_faces, [&] { return launch_mesh_count(m, q, which, l, ext, flags); },
+      [&] { return launch_mesh_emit(m, q, which, l, ext, flags); }));
   return map_take_error(m);
 }
 
-const void *ws_map_mesh_vertices_dev(const ws_map *m, size_t *n)
-{
-  if (n) *n = m ? m->mesh.nv : 0;
-  return m && m->mesh.nv ? m->mesh.vert.p : nullptr;
-}
+const void *ws_map_mesh_vertices_dev(const ws_map *m, size_t *n) { return mesh_vertices_dev(m ? &m->mesh : nullptr, n); }
 
-const uint32_t *ws_map_mesh_faces_dev(const ws_map *m, size_t *n)
-{
-  if (n) *n = m ? m->mesh.nf : 0;
-  return m && m->mesh.nf ? static_cast<const uint32_t *>(m->mesh.face.p) : nullptr;
-}
+const uint32_t *ws_map_mesh_faces_dev(const ws_map *m, size_t *n) { return mesh_faces_dev(m ? &m->mesh : nullptr, n); }
 
 int ws_map_mesh_download(ws_map *m, void *vertices_host, uint32_t *faces_host, size_t cap_vertices, size_t cap_faces, size_t *n_vertices, size_t *n_faces)
 {
   if (!m || !n_vertices || !n_faces) return invalid("ws_map_mesh_download: NULL argument");
   std::lock_guard<std::mutex> lock(m->mesh.mu);
-  *n_vertices = m->mesh.nv;
-  *n_faces = m->mesh.nf;
-  const size_t kv = vertices_host ? std::min(cap_vertices, m->mesh.nv) : 0, kf = faces_host ? std::min(cap_faces, m->mesh.nf) : 0;
-  if (kv) WS_HIP(hipMemcpyAsync(vertices_host, m->mesh.vert.p, kv * 16, hipMemcpyDeviceToHost, m->ctx->stream));
-  if (kf) WS_HIP(hipMemcpyAsync(faces_host, m->mesh.face.p, kf * 12, hipMemcpyDeviceToHost, m->ctx->stream));
-  if (kv || kf) WS_HIP(hipStreamSynchronize(m->ctx->stream));
-  return WS_OK;
+  return mesh_download(m->mesh, m->ctx->stream, vertices_host, faces_host, cap_vertices, cap_faces, n_vertices, n_faces);
 }
 
 int ws_debug_mesh_timing(ws_map *m, int32_t enable, float ms_out[3])
 {
   if (!m) return invalid("ws_debug_mesh_timing: map is NULL");
   std::lock_guard<std::mutex> lock(m->mesh.mu);
-  static const int pairs[3][2] = {{0, 1}, {1, 2}, {3, 4}};
-  return query_timing(m, m->mesh.timer, enable, ms_out, pairs, 3);
+  return query_timing(m->ctx->stream, m->mesh.timer, enable, ms_out, MESH_PAIRS, 3);
 }
 
 // ---- ray cast: the range image of a device map, map_raycast.hip (the rules are stated in warpsense_hip.h)
-static int raycast_run(ws_map *m, int which, const int32_t origin[3], const int32_t *dirs, bool dirs_on_host, size_t n, int32_t max_range, uint32_t flags,
+static int map_raycast(ws_map *m, int which, const int32_t origin[3], const int32_t *dirs, bool dirs_on_host, size_t n, int32_t max_range, uint32_t flags,
                        size_t *n_hits)
 {
-  const uint32_t known = WS_RAYCAST_ANY_WEIGHT | WS_RAYCAST_GRADIENT | WS_RAYCAST_TARGETS;
-  if (!m || (which != WS_MAP_AVG && which != WS_MAP_NEW) || (flags & ~known) || !origin || (n && !dirs)) return invalid("ws_map_raycast: bad argument");
-  if (max_range <= 0) return invalid("ws_map_raycast: max_range_mm <= 0");
-  if (m->res > 1024)
-  {
-    set_error("ws_map_raycast: the resolution must not exceed 1024 mm (the interpolant is carried times res^3 in 64 bits)");
-    return WS_ERR_RANGE;
-  }
-  if (n > ((size_t)1 << 27))
-  {
-    set_error("ws_map_raycast: more than 2^27 rays");
-    return WS_ERR_RANGE;
-  }
-  for (int k = 0; k < 3; ++k)
-  {
-    const int64_t o = origin[k];
-    if ((o < 0 ? -o : o) + (int64_t)max_range + 2 * (int64_t)m->res > (int64_t)INT32_MAX)
-    {
-      set_error("ws_map_raycast: |origin| + max_range + 2 res does not fit int32");
-      return WS_ERR_RANGE;
-    }
-  }
+  WS_TRY(raycast_check("ws_map_raycast", !m || (which != WS_MAP_AVG && which != WS_MAP_NEW), origin, dirs, n, max_range, m ? m->res : 0, flags,
+                       [] { return WS_OK; }));
   WS_SETTLE(m);
   std::lock_guard<std::mutex> lock(m->ray.mu);
-  ws_map::Raycast &q = m->ray;
-  int rc = q.timer.arm();
-  if (rc != WS_OK) return rc;
-  if (n_hits) *n_hits = 0;
-  q.n = 0;
-  q.has_grad = false;
-  if (n == 0) return map_take_error(m);
-  hipStream_t s = m->ctx->stream;
-  const bool grad = (flags & WS_RAYCAST_GRADIENT) != 0;
-  rc = q.hits.alloc(1);
-  if (rc != WS_OK) return rc;
-  if (n > q.rec.cap || (grad && n > q.grad.cap) || (dirs_on_host && n > q.dirs.cap))
-  {
-    WS_HIP(hipStreamSynchronize(s));
-    rc = q.rec.grow(n, 16);
-    if (rc == WS_OK && grad) rc = q.grad.grow(n, 3 * sizeof(int32_t));
-    if (rc == WS_OK && dirs_on_host) rc = q.dirs.grow(n, 3 * sizeof(int32_t));
-    if (rc != WS_OK) return rc;
-  }
-  q.timer.mark(0, s);
-  if (dirs_on_host)
-  {
-    WS_HIP(hipMemcpyAsync(q.dirs.p, dirs, n * 3 * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    dirs = static_cast<const int32_t *>(q.dirs.p);
-  }
-  rc = launch_raycast(m, which, origin, dirs, n, max_range, flags);
-  if (rc != WS_OK) return rc;
-  WS_HIP(hipStreamSynchronize(s));
-  q.n = n;
-  q.has_grad = grad;
-  if (n_hits) *n_hits = (size_t)*q.hits.host;
+  RayResult &q = m->ray;
+  WS_TRY(raycast_run(
+      q, m->ctx->stream, dirs, dirs_on_host, n, flags, n_hits, false, [] { return WS_OK; },
+      [&](const int32_t *dirs_dev) { return launch_raycast(m, q, which, origin, dirs_dev, n, max_range, flags); }));
   return map_take_error(m);
 }
 
 int ws_map_raycast(ws_map *m, int which, const int32_t origin_mm[3], const int32_t *dirs_host, size_t n, int32_t max_range_mm, uint32_t flags, size_t *n_hits)
 {
-  return raycast_run(m, which, origin_mm, dirs_host, true, n, max_range_mm, flags, n_hits);
+  return map_raycast(m, which, origin_mm, dirs_host, true, n, max_range_mm, flags, n_hits);
 }
 
 int ws_map_raycast_dev(ws_map *m, int which, const int32_t origin_mm[3], const int32_t *dirs_dev, size_t n, int32_t max_range_mm, uint32_t flags, size_t *n_hits)
 {
-  return raycast_run(m, which, origin_mm, dirs_dev, false, n, max_range_mm, flags, n_hits);
+  return map_raycast(m, which, origin_mm, dirs_dev, false, n, max_range_mm, flags, n_hits);
 }
 
-const void *ws_map_raycast_records_dev(const ws_map *m, size_t *n)
-{
-  if (n) *n = m ? m->ray.n : 0;
-  return m && m->ray.n ? m->ray.rec.p : nullptr;
-}
+const void *ws_map_raycast_records_dev(const ws_map *m, size_t *n) { return raycast_records_dev(m ? &m->ray : nullptr, n); }
 
-const int32_t *ws_map_raycast_gradient_dev(const ws_map *m, size_t *n)
-{
-  const bool have = m && m->ray.has_grad && m->ray.n;
-  if (n) *n = have ? m->ray.n : 0;
-  return have ? static_cast<const int32_t *>(m->ray.grad.p) : nullptr;
-}
+const int32_t *ws_map_raycast_gradient_dev(const ws_map *m, size_t *n) { return raycast_gradient_dev(m ? &m->ray : nullptr, n); }
 
 int ws_map_raycast_download(ws_map *m, void *records_host, int32_t *gradient_host, size_t capacity_rays, size_t *n_out)
 {
   if (!m || !n_out) return invalid("ws_map_raycast_download: NULL argument");
   std::lock_guard<std::mutex> lock(m->ray.mu);
-  *n_out = m->ray.n;
-  const size_t k = std::min(capacity_rays, m->ray.n);
-  if (k == 0) return WS_OK;
-  if (gradient_host && !m->ray.has_grad) return invalid("ws_map_raycast_download: the last ws_map_raycast did not ask for WS_RAYCAST_GRADIENT");
-  if (records_host) WS_HIP(hipMemcpyAsync(records_host, m->ray.rec.p, k * 16, hipMemcpyDeviceToHost, m->ctx->stream));
-  if (gradient_host) WS_HIP(hipMemcpyAsync(gradient_host, m->ray.grad.p, k * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, m->ctx->stream));
-  WS_HIP(hipStreamSynchronize(m->ctx->stream));
-  return WS_OK;
+  return raycast_download(m->ray, m->ctx->stream, "ws_map_raycast_download", "ws_map_raycast", records_host, gradient_host, capacity_rays, n_out);
 }
 
 int ws_debug_raycast_timing(ws_map *m, int32_t enable, float ms_out[3])
 {
   if (!m) return invalid("ws_debug_raycast_timing: map is NULL");
   std::lock_guard<std::mutex> lock(m->ray.mu);
-  static const int pairs[3][2] = {{0, 1}, {1, 2}, {2, 3}};
-  return query_timing(m, m->ray.timer, enable, ms_out, pairs, 3);
+  return query_timing(m->ctx->stream, m->ray.timer, enable, ms_out, RAY_PAIRS, 3);
 }
 
 // ---- distance field: the exact Euclidean transform of a device map, map_distance.hip (the rules are stated in warpsense_hip.h)
@@ -916,7 +962,7 @@ int ws_debug_distance_timing(ws_map *m, int32_t enable, float ms_out[4])
   if (!m) return invalid("ws_debug_distance_timing: map is NULL");
   std::lock_guard<std::mutex> lock(m->dist.mu);
   static const int pairs[4][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 4}};
-  return query_timing(m, m->dist.timer, enable, ms_out, pairs, 4);
+  return query_timing(m->ctx->stream, m->dist.timer, enable, ms_out, pairs, 4);
 }
 
 // ---- map shift
@@ -1537,26 +1583,38 @@ int ws_debug_store_timing(ws_store *st, int32_t enable, float ms_out[2])
   return WS_OK;
 }
 
-// ---- the mesh of the store: ws_map_mesh's rules over the chunks, store_mesh.hip (the semantics are stated in warpsense_hip.h)
+// ---- the mesh and the ray cast of the store: the rules and the host flow of ws_map_mesh and ws_map_raycast over the chunks,
+// store_mesh.hip and store_raycast.hip (the semantics are stated in warpsense_hip.h)
 namespace
 {
-// The call's tables, into st->mesh.table_host: the present chunks the box overlaps, ascending (cx, cy, cz) like the directory; per
-// chunk the four counts that place its 4096 words in world order, its key and slot, and the list positions of its 26 neighbours.
-// Everything is O(listed chunks x log): nothing here follows the volume of the box.
-int store_mesh_tables(ws_store *st, const int32_t lo[3], const int32_t hi[3], std::vector<StoreKey> &keys)
+// The written chunks the box overlaps, ascending (cx, cy, cz) like the directory: visit(key, slot).  The directory is ordered by cx
+// first and only the keys of the box's cx range are visited: nothing here follows the volume of the box.
+extern "C++" template <typename Visit> void store_walk_box(const ws_store *st, const int32_t lo[3], const int32_t hi[3], Visit visit)
 {
   const ChunkRange cr(lo, hi);
-  keys.clear();
-  std::vector<uint32_t> slots;
-  // (the directory is ordered by cx first: only the keys of the box's cx range are visited)
   for (auto it = st->dir.lower_bound(StoreKey{cr.c0[0], INT32_MIN, INT32_MIN}); it != st->dir.end() && it->first[0] - cr.c0[0] < cr.nc[0]; ++it)
   {
     bool in = it->second.written;
     for (int k = 1; k < 3; ++k) in = in && it->first[k] >= cr.c0[k] && it->first[k] - cr.c0[k] < cr.nc[k];
-    if (!in) continue;
-    keys.push_back(it->first);
-    slots.push_back(it->second.slot);
+    if (in) visit(it->first, it->second.slot);
   }
+}
+
+// A store call waits for the stream even after a failed enqueue (whose error it reports): the pinned table of the call must be free
+// again when the call returns.
+int store_enqueued(const ws_store *st, int rc)
+{
+  if (rc != WS_OK) (void)hipStreamSynchronize(st->ctx->stream);
+  return rc;
+}
+
+// The call's tables, into st->mesh.table_host: the chunks store_walk_box lists; per chunk the four counts that place its 4096 words
+// in world order, its key and slot, and the list positions of its 26 neighbours.  Everything is O(listed chunks x log).
+int store_mesh_tables(ws_store *st, const int32_t lo[3], const int32_t hi[3], std::vector<StoreKey> &keys)
+{
+  keys.clear();
+  std::vector<uint32_t> slots;
+  store_walk_box(st, lo, hi, [&](const StoreKey &key, uint32_t slot) { keys.push_back(key), slots.push_back(slot); });
   const size_t n = keys.size();
   if (n == 0 || n >= (1u << 19)) return WS_OK; // (the caller decides: nothing to do / WS_ERR_RANGE)
   if (store_mesh_table_bytes(n) > st->mesh.table_host.cap)
@@ -1608,179 +1666,78 @@ int ws_store_mesh(ws_store *st, const int32_t lo[3], const int32_t hi[3], int32_
   std::lock_guard<std::mutex> lock(st->mu);
   ws_store::Mesh &q = st->mesh;
   WS_TRY(q.timer.arm());
-  const auto done = [&](size_t nv, size_t nf) {
-    q.nv = nv, q.nf = nf;
-    if (n_vertices) *n_vertices = nv;
-    if (n_faces) *n_faces = nf;
-    return WS_OK;
-  };
   int32_t l[3], h[3];
   if (lo)
     copy3(l, lo), copy3(h, hi);
   else
   {
-    if (st->dir.empty()) return done(0, 0);
+    if (st->dir.empty()) return mesh_publish(q, 0, 0, n_vertices, n_faces);
     // the bounding box of the present chunks (keys are floor(int32 / 64): 64 k + 63 fits)
     for (int k = 0; k < 3; ++k) l[k] = INT32_MAX, h[k] = INT32_MIN;
     for (const auto &kv : st->dir)
       for (int k = 0; k < 3; ++k) l[k] = std::min(l[k], kv.first[k] * STORE_CS), h[k] = std::max(h[k], kv.first[k] * STORE_CS + STORE_CS - 1);
   }
-  for (int k = 0; k < 3; ++k)
-    for (int64_t c : {(int64_t)l[k], (int64_t)h[k]})
-      if (((c < 0 ? -c : c) + 1) * (int64_t)map_resolution > (int64_t)INT32_MAX)
-      {
-        set_error("ws_store_mesh: a box corner in millimetres does not fit int32");
-        return WS_ERR_RANGE;
-      }
-  if (h[0] == l[0] || h[1] == l[1] || h[2] == l[2]) return done(0, 0); // one voxel thick along an axis: no cells
+  WS_TRY(mesh_corners_fit(l, h, map_resolution, "ws_store_mesh"));
+  if (h[0] == l[0] || h[1] == l[1] || h[2] == l[2]) return mesh_publish(q, 0, 0, n_vertices, n_faces); // one voxel thick along an axis: no cells
   std::vector<StoreKey> keys;
   WS_TRY(store_mesh_tables(st, l, h, keys));
-  if (keys.empty()) return done(0, 0); // the box meets no present chunk
-  if (keys.size() >= (1u << 19))
-  {
-    set_error("ws_store_mesh: the box overlaps 2^19 present chunks or more (4096 words each must stay below 2^31)");
-    return WS_ERR_RANGE;
-  }
-  q.nv = q.nf = 0; // (whatever happens from here on, the old result is gone: its buffers may be replaced)
-  if (n_vertices) *n_vertices = 0;
-  if (n_faces) *n_faces = 0;
+  if (keys.empty()) return mesh_publish(q, 0, 0, n_vertices, n_faces); // the box meets no present chunk
+  if (keys.size() >= (1u << 19)) return range_error("ws_store_mesh", ": the box overlaps 2^19 present chunks or more (4096 words each must stay below 2^31)");
   StoreMeshCall c;
   c.n_chunks = (uint32_t)keys.size();
   c.res = map_resolution;
   c.flags = flags;
   copy3(c.lo, l), copy3(c.hi, h);
-  hipStream_t s = st->ctx->stream;
-  WS_TRY(q.total.alloc(2, false));
-  const size_t need = mesh_scratch_bytes((uint64_t)c.n_chunks * 4096u);
-  if (need > q.scratch.cap)
-  {
-    WS_HIP(hipStreamSynchronize(s));
-    WS_TRY(q.scratch.grow(need, 1));
-  }
-  int rc = launch_store_mesh_count(st, c);
-  const hipError_t e1 = hipStreamSynchronize(s); // the one host read the call needs: the outputs are sized from the two totals
-  if (rc != WS_OK) return rc;
-  WS_HIP(e1);
-  const unsigned long long nv = q.total.host[0], nq = q.total.host[1];
-  if (nv > 0xffffffffull)
-  {
-    set_error("ws_store_mesh: more than 2^32 - 1 vertices");
-    return WS_ERR_RANGE;
-  }
-  WS_TRY(q.vert.grow((size_t)nv, 16));
-  WS_TRY(q.face.grow((size_t)nq * 2, 12));
-  if (nv)
-  {
-    rc = launch_store_mesh_emit(st, c);
-    const hipError_t e2 = hipStreamSynchronize(s);
-    if (rc != WS_OK) return rc;
-    WS_HIP(e2);
-  }
-  return done((size_t)nv, (size_t)nq * 2);
+  return mesh_run(
+      q, st->ctx->stream, "ws_store_mesh", (uint64_t)c.n_chunks * 4096u, n_vertices, n_faces, [&] { return store_enqueued(st, launch_store_mesh_count(st, q, c)); },
+      [&] { return store_enqueued(st, launch_store_mesh_emit(st, q, c)); });
 }
 
-const void *ws_store_mesh_vertices_dev(const ws_store *st, size_t *n)
-{
-  if (n) *n = st ? st->mesh.nv : 0;
-  return st && st->mesh.nv ? st->mesh.vert.p : nullptr;
-}
+const void *ws_store_mesh_vertices_dev(const ws_store *st, size_t *n) { return mesh_vertices_dev(st ? &st->mesh : nullptr, n); }
 
-const uint32_t *ws_store_mesh_faces_dev(const ws_store *st, size_t *n)
-{
-  if (n) *n = st ? st->mesh.nf : 0;
-  return st && st->mesh.nf ? static_cast<const uint32_t *>(st->mesh.face.p) : nullptr;
-}
+const uint32_t *ws_store_mesh_faces_dev(const ws_store *st, size_t *n) { return mesh_faces_dev(st ? &st->mesh : nullptr, n); }
 
 int ws_store_mesh_download(ws_store *st, void *vertices_host, uint32_t *faces_host, size_t cap_vertices, size_t cap_faces, size_t *n_vertices, size_t *n_faces)
 {
   if (!st || !n_vertices || !n_faces) return invalid("ws_store_mesh_download: NULL argument");
   std::lock_guard<std::mutex> lock(st->mu);
-  *n_vertices = st->mesh.nv;
-  *n_faces = st->mesh.nf;
-  const size_t kv = vertices_host ? std::min(cap_vertices, st->mesh.nv) : 0, kf = faces_host ? std::min(cap_faces, st->mesh.nf) : 0;
-  if (kv) WS_HIP(hipMemcpyAsync(vertices_host, st->mesh.vert.p, kv * 16, hipMemcpyDeviceToHost, st->ctx->stream));
-  if (kf) WS_HIP(hipMemcpyAsync(faces_host, st->mesh.face.p, kf * 12, hipMemcpyDeviceToHost, st->ctx->stream));
-  if (kv || kf) WS_HIP(hipStreamSynchronize(st->ctx->stream));
-  return WS_OK;
+  return mesh_download(st->mesh, st->ctx->stream, vertices_host, faces_host, cap_vertices, cap_faces, n_vertices, n_faces);
 }
 
 int ws_debug_store_mesh_timing(ws_store *st, int32_t enable, float ms_out[3])
 {
   if (!st) return invalid("ws_debug_store_mesh_timing: store is NULL");
   std::lock_guard<std::mutex> lock(st->mu);
-  static const int pairs[3][2] = {{0, 1}, {1, 2}, {3, 4}};
-  const int rc = st->mesh.timer.read(ms_out, pairs, 3, st->ctx->stream);
-  if (rc == WS_OK) st->mesh.timer.set(enable);
-  return rc;
+  return query_timing(st->ctx->stream, st->mesh.timer, enable, ms_out, MESH_PAIRS, 3);
 }
 
-// ---- the ray cast of the store: ws_map_raycast's rules over the chunks, store_raycast.hip (the semantics are stated in warpsense_hip.h)
-namespace
+static int store_raycast(ws_store *st, const int32_t lo[3], const int32_t hi[3], const int32_t origin[3], const int32_t *dirs, bool dirs_on_host, size_t n,
+                         int32_t max_range, int32_t res, uint32_t flags, size_t *n_hits)
 {
-// The present chunks the box overlaps, ascending like the directory (the walk of store_mesh_tables): O(chunks of the box's cx range),
-// nothing here follows the volume of the box.
-void store_ray_list(const ws_store *st, const int32_t lo[3], const int32_t hi[3], std::vector<StoreRaySlot> &out)
-{
-  const ChunkRange cr(lo, hi);
-  out.clear();
-  for (auto it = st->dir.lower_bound(StoreKey{cr.c0[0], INT32_MIN, INT32_MIN}); it != st->dir.end() && it->first[0] - cr.c0[0] < cr.nc[0]; ++it)
-  {
-    bool in = it->second.written;
-    for (int k = 1; k < 3; ++k) in = in && it->first[k] >= cr.c0[k] && it->first[k] - cr.c0[k] < cr.nc[k];
-    if (in) out.push_back(StoreRaySlot{it->first[0], it->first[1], it->first[2], it->second.slot});
-  }
-}
-
-int store_raycast_run(ws_store *st, const int32_t lo[3], const int32_t hi[3], const int32_t origin[3], const int32_t *dirs, bool dirs_on_host, size_t n,
-                      int32_t max_range, int32_t res, uint32_t flags, size_t *n_hits)
-{
-  const uint32_t known = WS_RAYCAST_ANY_WEIGHT | WS_RAYCAST_GRADIENT | WS_RAYCAST_TARGETS;
-  if (!st || (flags & ~known) || !origin || (n && !dirs) || ((lo == nullptr) != (hi == nullptr))) return invalid("ws_store_raycast: bad argument");
-  if (lo)
-    for (int k = 0; k < 3; ++k)
-      if (hi[k] < lo[k]) return invalid("ws_store_raycast: hi < lo");
-  if (res <= 0) return invalid("ws_store_raycast: map_resolution <= 0");
-  if (max_range <= 0) return invalid("ws_store_raycast: max_range_mm <= 0");
-  if (res > 1024)
-  {
-    set_error("ws_store_raycast: the resolution must not exceed 1024 mm (the interpolant is carried times res^3 in 64 bits)");
-    return WS_ERR_RANGE;
-  }
-  if (n > ((size_t)1 << 27))
-  {
-    set_error("ws_store_raycast: more than 2^27 rays");
-    return WS_ERR_RANGE;
-  }
-  for (int k = 0; k < 3; ++k)
-  {
-    const int64_t o = origin[k];
-    if ((o < 0 ? -o : o) + (int64_t)max_range + 2 * (int64_t)res > (int64_t)INT32_MAX)
-    {
-      set_error("ws_store_raycast: |origin| + max_range + 2 res does not fit int32");
-      return WS_ERR_RANGE;
-    }
-  }
+  WS_TRY(raycast_check("ws_store_raycast", !st || ((lo == nullptr) != (hi == nullptr)), origin, dirs, n, max_range, res, flags, [&] {
+    if (lo)
+      for (int k = 0; k < 3; ++k)
+        if (hi[k] < lo[k]) return invalid("ws_store_raycast: hi < lo");
+    return res <= 0 ? invalid("ws_store_raycast: map_resolution <= 0") : (int)WS_OK;
+  }));
   std::lock_guard<std::mutex> lock(st->mu);
   ws_store::Ray &q = st->ray;
   StoreRayCall c;
   c.res = res;
   std::vector<StoreRaySlot> listed;
+  const auto list = [&](const StoreKey &key, uint32_t slot) { listed.push_back(StoreRaySlot{key[0], key[1], key[2], slot}); };
   if (lo)
   {
     copy3(c.lo, lo), copy3(c.hi, hi);
-    store_ray_list(st, lo, hi, listed);
+    store_walk_box(st, lo, hi, list);
   }
   else
   {
     for (int k = 0; k < 3; ++k) c.lo[k] = INT32_MIN, c.hi[k] = INT32_MAX; // everything
     for (const auto &kv : st->dir)
-      if (kv.second.written) listed.push_back(StoreRaySlot{kv.first[0], kv.first[1], kv.first[2], kv.second.slot});
+      if (kv.second.written) list(kv.first, kv.second.slot);
   }
-  if (listed.size() >= (1u << 19))
-  {
-    set_error("ws_store_raycast: the call lists 2^19 present chunks or more");
-    return WS_ERR_RANGE;
-  }
+  if (listed.size() >= (1u << 19)) return range_error("ws_store_raycast", ": the call lists 2^19 present chunks or more");
   c.n_chunks = (uint32_t)listed.size();
   // the live box: the bounding box of the listed chunks (keys are floor(int32 / 64): 64 k + 63 fits), cut to the box
   for (int k = 0; k < 3; ++k) c.blo[k] = INT32_MAX, c.bhi[k] = INT32_MIN;
@@ -1790,92 +1747,50 @@ int store_raycast_run(ws_store *st, const int32_t lo[3], const int32_t hi[3], co
     for (int k = 0; k < 3; ++k) c.blo[k] = std::min(c.blo[k], key[k] * STORE_CS), c.bhi[k] = std::max(c.bhi[k], key[k] * STORE_CS + STORE_CS - 1);
   }
   for (int k = 0; k < 3; ++k) c.blo[k] = std::max(c.blo[k], c.lo[k]), c.bhi[k] = std::min(c.bhi[k], c.hi[k]);
-  WS_TRY(q.timer.arm());
-  if (n_hits) *n_hits = 0;
-  q.n = 0; // (whatever happens from here on, the old result is gone: its buffers may be replaced)
-  q.has_grad = false;
-  if (n == 0) return WS_OK;
-  hipStream_t s = st->ctx->stream;
-  const bool grad = (flags & WS_RAYCAST_GRADIENT) != 0;
-  WS_TRY(q.hits.alloc(1));
+  // (no listed chunk: the call still launches and answers no-hit for every ray)
   const size_t places = c.n_chunks ? store_ray_table_slots(c.n_chunks) : 0;
-  if (n > q.rec.cap || (grad && n > q.grad.cap) || (dirs_on_host && n > q.dirs.cap) || places > q.table_host.cap)
-  {
-    WS_HIP(hipStreamSynchronize(s));
-    WS_TRY(q.rec.grow(n, 16));
-    if (grad) WS_TRY(q.grad.grow(n, 3 * sizeof(int32_t)));
-    if (dirs_on_host) WS_TRY(q.dirs.grow(n, 3 * sizeof(int32_t)));
-    if (places > q.table_host.cap)
-    {
-      WS_TRY(q.table_host.alloc(places, sizeof(StoreRaySlot), HostBlock::PINNED));
-      WS_TRY(q.table_dev.alloc(places, sizeof(StoreRaySlot)));
-    }
-  }
-  if (c.n_chunks) store_ray_table_fill(listed.data(), listed.size(), q.table_host.as<StoreRaySlot>());
-  q.timer.mark(0, s);
-  if (dirs_on_host)
-  {
-    WS_HIP(hipMemcpyAsync(q.dirs.p, dirs, n * 3 * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    dirs = static_cast<const int32_t *>(q.dirs.p);
-  }
-  const int rc = launch_store_raycast(st, c, origin, dirs, n, max_range, flags);
-  const hipError_t e = hipStreamSynchronize(s); // (also after a failed enqueue: the pinned table is free again when the call returns)
-  if (rc != WS_OK) return rc;
-  WS_HIP(e);
-  q.n = n;
-  q.has_grad = grad;
-  if (n_hits) *n_hits = (size_t)*q.hits.host;
-  return WS_OK;
+  return raycast_run(
+      q, st->ctx->stream, dirs, dirs_on_host, n, flags, n_hits, places > q.table_host.cap,
+      [&] {
+        if (places > q.table_host.cap)
+        {
+          WS_TRY(q.table_host.alloc(places, sizeof(StoreRaySlot), HostBlock::PINNED));
+          WS_TRY(q.table_dev.alloc(places, sizeof(StoreRaySlot)));
+        }
+        if (c.n_chunks) store_ray_table_fill(listed.data(), listed.size(), q.table_host.as<StoreRaySlot>());
+        return (int)WS_OK;
+      },
+      [&](const int32_t *dirs_dev) { return store_enqueued(st, launch_store_raycast(st, q, c, origin, dirs_dev, n, max_range, flags)); });
 }
-} // namespace
 
 int ws_store_raycast(ws_store *st, const int32_t lo[3], const int32_t hi[3], const int32_t origin_mm[3], const int32_t *dirs_host, size_t n, int32_t max_range_mm,
                      int32_t map_resolution, uint32_t flags, size_t *n_hits)
 {
-  return store_raycast_run(st, lo, hi, origin_mm, dirs_host, true, n, max_range_mm, map_resolution, flags, n_hits);
+  return store_raycast(st, lo, hi, origin_mm, dirs_host, true, n, max_range_mm, map_resolution, flags, n_hits);
 }
 
 int ws_store_raycast_dev(ws_store *st, const int32_t lo[3], const int32_t hi[3], const int32_t origin_mm[3], const int32_t *dirs_dev, size_t n, int32_t max_range_mm,
                          int32_t map_resolution, uint32_t flags, size_t *n_hits)
 {
-  return store_raycast_run(st, lo, hi, origin_mm, dirs_dev, false, n, max_range_mm, map_resolution, flags, n_hits);
+  return store_raycast(st, lo, hi, origin_mm, dirs_dev, false, n, max_range_mm, map_resolution, flags, n_hits);
 }
 
-const void *ws_store_raycast_records_dev(const ws_store *st, size_t *n)
-{
-  if (n) *n = st ? st->ray.n : 0;
-  return st && st->ray.n ? st->ray.rec.p : nullptr;
-}
+const void *ws_store_raycast_records_dev(const ws_store *st, size_t *n) { return raycast_records_dev(st ? &st->ray : nullptr, n); }
 
-const int32_t *ws_store_raycast_gradient_dev(const ws_store *st, size_t *n)
-{
-  const bool have = st && st->ray.has_grad && st->ray.n;
-  if (n) *n = have ? st->ray.n : 0;
-  return have ? static_cast<const int32_t *>(st->ray.grad.p) : nullptr;
-}
+const int32_t *ws_store_raycast_gradient_dev(const ws_store *st, size_t *n) { return raycast_gradient_dev(st ? &st->ray : nullptr, n); }
 
 int ws_store_raycast_download(ws_store *st, void *records_host, int32_t *gradient_host, size_t capacity_rays, size_t *n_out)
 {
   if (!st || !n_out) return invalid("ws_store_raycast_download: NULL argument");
   std::lock_guard<std::mutex> lock(st->mu);
-  *n_out = st->ray.n;
-  const size_t k = std::min(capacity_rays, st->ray.n);
-  if (k == 0) return WS_OK;
-  if (gradient_host && !st->ray.has_grad) return invalid("ws_store_raycast_download: the last ws_store_raycast did not ask for WS_RAYCAST_GRADIENT");
-  if (records_host) WS_HIP(hipMemcpyAsync(records_host, st->ray.rec.p, k * 16, hipMemcpyDeviceToHost, st->ctx->stream));
-  if (gradient_host) WS_HIP(hipMemcpyAsync(gradient_host, st->ray.grad.p, k * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, st->ctx->stream));
-  WS_HIP(hipStreamSynchronize(st->ctx->stream));
-  return WS_OK;
+  return raycast_download(st->ray, st->ctx->stream, "ws_store_raycast_download", "ws_store_raycast", records_host, gradient_host, capacity_rays, n_out);
 }
 
 int ws_debug_store_raycast_timing(ws_store *st, int32_t enable, float ms_out[3])
 {
   if (!st) return invalid("ws_debug_store_raycast_timing: store is NULL");
   std::lock_guard<std::mutex> lock(st->mu);
-  static const int pairs[3][2] = {{0, 1}, {1, 2}, {2, 3}};
-  const int rc = st->ray.timer.read(ms_out, pairs, 3, st->ctx->stream);
-  if (rc == WS_OK) st->ray.timer.set(enable);
-  return rc;
+  return query_timing(st->ctx->stream, st->ray.timer, enable, ms_out, RAY_PAIRS, 3);
 }
 
 int ws_debug_store_raycast_table(const int32_t *keys_slots, size_t n, int32_t *table, size_t capacity_places, size_t *n_places)

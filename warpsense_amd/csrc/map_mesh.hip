@@ -217,7 +217,7 @@ size_t mesh_scratch_bytes(uint64_t n_words)
   return 3 * mesh_up256(nwd * 8) + mesh_up256(nwd * 4) + mesh_up256(nwd) + 2 * mesh_up256(nb * 4) + 2 * mesh_up256(nb * 8) + 256;
 }
 
-static MeshArgs mesh_args(const ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], uint32_t flags, mu64 vcap, mu64 qcap)
+static MeshArgs mesh_args(const ws_map *m, const MeshResult &q, int which, const int32_t lo[3], const int32_t ext[3], uint32_t flags, bool emit)
 {
   MeshArgs a;
   a.box = box_args(m, which, lo, ext);
@@ -225,44 +225,19 @@ static MeshArgs mesh_args(const ws_map *m, int which, const int32_t lo[3], const
   a.n_words = a.box.n_cols * a.nw;
   a.res = m->res;
   a.any_weight = (flags & WS_MESH_ANY_WEIGHT) ? 1u : 0u;
-  mesh_take_scratch(a, m->mesh.scratch.p, a.n_words);
-  a.vert = static_cast<mi32x4 *>(m->mesh.vert.p);
-  a.face = static_cast<uint32_t *>(m->mesh.face.p);
-  a.vcap = vcap;
-  a.qcap = qcap;
+  mesh_bind(a, q, a.n_words, emit);
   return a;
 }
 
-// bits, cells, quads and the scans; the two totals arrive in m->mesh.total.host (pinned) once the stream has been synchronised
-int launch_mesh_count(ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], uint32_t flags)
+int launch_mesh_count(ws_map *m, MeshResult &q, int which, const int32_t lo[3], const int32_t ext[3], uint32_t flags)
 {
-  const MeshArgs a = mesh_args(m, which, lo, ext, flags, 0, 0);
-  const uint32_t blocks = mesh_blocks(a.n_words);
-  hipStream_t s = m->ctx->stream;
-  QueryTimer &t = m->mesh.timer;
-  t.mark(0, s);
-  hipLaunchKernelGGL(mesh_bits_kernel, dim3((a.box.n_cols + 3) / 4), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(mesh_cells_kernel, dim3(blocks), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(mesh_quads_kernel, dim3(blocks), dim3(256), 0, s, a);
-  t.mark(1, s);
-  hipLaunchKernelGGL(mesh_scan_kernel, dim3(2), dim3(1024), 0, s, a, blocks);
-  t.mark(2, s);
-  WS_HIP(hipGetLastError());
-  return m->mesh.total.fetch(s, 2, a.totals);
+  const MeshArgs a = mesh_args(m, q, which, lo, ext, flags, false);
+  return mesh_launch_count(q, m->ctx->stream, a, (a.box.n_cols + 3) / 4, mesh_bits_kernel, mesh_cells_kernel, mesh_quads_kernel, mesh_scan_kernel);
 }
 
-// vertices, then faces (which read the vertex pass's vbase)
-int launch_mesh_emit(ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], uint32_t flags)
+int launch_mesh_emit(ws_map *m, MeshResult &q, int which, const int32_t lo[3], const int32_t ext[3], uint32_t flags)
 {
-  const MeshArgs a = mesh_args(m, which, lo, ext, flags, m->mesh.vert.cap, m->mesh.face.cap / 2);
-  const uint32_t blocks = mesh_blocks(a.n_words);
-  hipStream_t s = m->ctx->stream;
-  m->mesh.timer.mark(3, s);
-  hipLaunchKernelGGL(mesh_vertex_kernel, dim3(blocks), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(mesh_face_kernel, dim3(blocks), dim3(256), 0, s, a);
-  m->mesh.timer.mark(4, s);
-  WS_HIP(hipGetLastError());
-  return WS_OK;
+  return mesh_launch_emit(q, m->ctx->stream, mesh_args(m, q, which, lo, ext, flags, true), mesh_vertex_kernel, mesh_face_kernel);
 }
 
 } // namespace ws

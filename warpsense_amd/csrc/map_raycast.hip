@@ -114,9 +114,7 @@ __global__ __launch_bounds__(64) void raycast_grad_kernel(RayArgs a)
   ray_gradient(a.c, WindowField(a), i);
 }
 
-// the march (events 1, 2), then the gradient if asked for (events 2, 3); the hit count arrives in m->ray.hits.host (pinned)
-// once the stream has been synchronised
-int launch_raycast(ws_map *m, int which, const int32_t origin[3], const int32_t *dirs_dev, size_t n, int32_t max_range, uint32_t flags)
+int launch_raycast(ws_map *m, RayResult &q, int which, const int32_t origin[3], const int32_t *dirs_dev, size_t n, int32_t max_range, uint32_t flags)
 {
   RayArgs a;
   a.data = m->data[which].as<uint32_t>();
@@ -126,17 +124,8 @@ int launch_raycast(ws_map *m, int which, const int32_t origin[3], const int32_t 
     a.wlo[k] = a.mp.pos[k] - a.mp.size[k] / 2;
     a.whi[k] = a.wlo[k] + a.mp.size[k] - 1;
   }
-  a.c = ray_common(origin, dirs_dev, n, m->res, max_range, flags, m->ray.rec.p, m->ray.grad.p, m->ray.hits.dev);
-  hipStream_t s = m->ctx->stream;
-  const uint32_t blocks = (uint32_t)((n + 63) / 64);
-  WS_HIP(hipMemsetAsync(a.c.hits, 0, sizeof(unsigned long long), s));
-  m->ray.timer.mark(1, s);
-  hipLaunchKernelGGL(raycast_kernel, dim3(blocks), dim3(64), 0, s, a);
-  m->ray.timer.mark(2, s);
-  if (flags & WS_RAYCAST_GRADIENT) hipLaunchKernelGGL(raycast_grad_kernel, dim3(blocks), dim3(64), 0, s, a);
-  m->ray.timer.mark(3, s);
-  WS_HIP(hipGetLastError());
-  return m->ray.hits.fetch(s);
+  a.c = ray_common(q, origin, dirs_dev, n, m->res, max_range, flags);
+  return ray_launch(q, m->ctx->stream, a, raycast_kernel, raycast_grad_kernel);
 }
 
 } // namespace ws

@@ -263,7 +263,7 @@ __global__ __launch_bounds__(256) void store_mesh_face_kernel(StoreMeshArgs a)
 // ---- host side
 size_t store_mesh_table_bytes(size_t n_chunks) { return n_chunks * (16 + 16 + 27 * 4); }
 
-static StoreMeshArgs store_mesh_args(const ws_store *st, const StoreMeshCall &c, mu64 vcap, mu64 qcap)
+static StoreMeshArgs store_mesh_args(const ws_store *st, const ws_store::Mesh &q, const StoreMeshCall &c, bool emit)
 {
   StoreMeshArgs a;
   a.n_chunks = c.n_chunks;
@@ -271,51 +271,28 @@ static StoreMeshArgs store_mesh_args(const ws_store *st, const StoreMeshCall &c,
   a.res = c.res;
   a.any_weight = (c.flags & WS_MESH_ANY_WEIGHT) ? 1u : 0u;
   for (int k = 0; k < 3; ++k) a.lo[k] = c.lo[k], a.hi[k] = c.hi[k];
-  const char *tab = static_cast<const char *>(st->mesh.table_dev.p);
+  const char *tab = static_cast<const char *>(q.table_dev.p);
   a.grp = reinterpret_cast<const su32x4 *>(tab);
   a.key = reinterpret_cast<const mi32x4 *>(tab + (size_t)c.n_chunks * 16);
   a.nb = reinterpret_cast<const uint32_t *>(tab + (size_t)c.n_chunks * 32);
   a.segs = st->seg_tab.as<uint32_t *>();
   a.seg_shift = st->seg_shift;
-  mesh_take_scratch(a, st->mesh.scratch.p, a.n_words);
-  a.vert = static_cast<mi32x4 *>(st->mesh.vert.p);
-  a.face = static_cast<uint32_t *>(st->mesh.face.p);
-  a.vcap = vcap;
-  a.qcap = qcap;
+  mesh_bind(a, q, a.n_words, emit);
   return a;
 }
 
-// the tables' upload, bits, cells, quads and the scans; the two totals arrive in st->mesh.total.host once the stream has been synchronised
-int launch_store_mesh_count(ws_store *st, const StoreMeshCall &c)
+// the tables' upload, then the count passes
+int launch_store_mesh_count(ws_store *st, ws_store::Mesh &q, const StoreMeshCall &c)
 {
-  const StoreMeshArgs a = store_mesh_args(st, c, 0, 0);
-  const uint32_t blocks = mesh_blocks(a.n_words);
   hipStream_t s = st->ctx->stream;
-  WS_HIP(hipMemcpyAsync(st->mesh.table_dev.p, st->mesh.table_host.p, store_mesh_table_bytes(c.n_chunks), hipMemcpyHostToDevice, s));
-  QueryTimer &t = st->mesh.timer;
-  t.mark(0, s);
-  hipLaunchKernelGGL(store_mesh_bits_kernel, dim3(c.n_chunks * 256u), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(store_mesh_cells_kernel, dim3(blocks), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(store_mesh_quads_kernel, dim3(blocks), dim3(256), 0, s, a);
-  t.mark(1, s);
-  hipLaunchKernelGGL(store_mesh_scan_kernel, dim3(2), dim3(1024), 0, s, a, blocks);
-  t.mark(2, s);
-  WS_HIP(hipGetLastError());
-  return st->mesh.total.fetch(s, 2, a.totals);
+  WS_HIP(hipMemcpyAsync(q.table_dev.p, q.table_host.p, store_mesh_table_bytes(c.n_chunks), hipMemcpyHostToDevice, s));
+  return mesh_launch_count(q, s, store_mesh_args(st, q, c, false), c.n_chunks * 256u, store_mesh_bits_kernel, store_mesh_cells_kernel,
+                           store_mesh_quads_kernel, store_mesh_scan_kernel);
 }
 
-// vertices, then faces (which read the vertex pass's vbase)
-int launch_store_mesh_emit(ws_store *st, const StoreMeshCall &c)
+int launch_store_mesh_emit(ws_store *st, ws_store::Mesh &q, const StoreMeshCall &c)
 {
-  const StoreMeshArgs a = store_mesh_args(st, c, st->mesh.vert.cap, st->mesh.face.cap / 2);
-  const uint32_t blocks = mesh_blocks(a.n_words);
-  hipStream_t s = st->ctx->stream;
-  st->mesh.timer.mark(3, s);
-  hipLaunchKernelGGL(store_mesh_vertex_kernel, dim3(blocks), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(store_mesh_face_kernel, dim3(blocks), dim3(256), 0, s, a);
-  st->mesh.timer.mark(4, s);
-  WS_HIP(hipGetLastError());
-  return WS_OK;
+  return mesh_launch_emit(q, st->ctx->stream, store_mesh_args(st, q, c, true), store_mesh_vertex_kernel, store_mesh_face_kernel);
 }
 
 } // namespace ws

@@ -187,13 +187,11 @@ __global__ __launch_bounds__(64) void store_raycast_grad_kernel(StoreRayArgs a)
   ray_gradient(a.c, StoreField(a), i);
 }
 
-// the table's upload, the march (events 1, 2), then the gradient if asked for (events 2, 3); the hit count arrives in
-// st->ray.hits.host (pinned) once the stream has been synchronised
-int launch_store_raycast(ws_store *st, const StoreRayCall &c, const int32_t origin[3], const int32_t *dirs_dev, size_t n, int32_t max_range, uint32_t flags)
+// the table's upload, then the launch sequence
+int launch_store_raycast(ws_store *st, ws_store::Ray &q, const StoreRayCall &c, const int32_t origin[3], const int32_t *dirs_dev, size_t n, int32_t max_range, uint32_t flags)
 {
-  ws_store::Ray &q = st->ray;
   StoreRayArgs a;
-  a.c = ray_common(origin, dirs_dev, n, c.res, max_range, flags, q.rec.p, q.grad.p, q.hits.dev);
+  a.c = ray_common(q, origin, dirs_dev, n, c.res, max_range, flags);
   for (int k = 0; k < 3; ++k) a.lo[k] = c.lo[k], a.hi[k] = c.hi[k], a.blo[k] = c.blo[k], a.bhi[k] = c.bhi[k];
   a.n_chunks = c.n_chunks;
   a.table = q.table_dev.as<StoreRaySlot>();
@@ -201,17 +199,9 @@ int launch_store_raycast(ws_store *st, const StoreRayCall &c, const int32_t orig
   a.segs = st->seg_tab.as<uint32_t *>();
   a.seg_shift = st->seg_shift;
   hipStream_t s = st->ctx->stream;
-  const uint32_t blocks = (uint32_t)((n + 63) / 64);
   if (c.n_chunks)
     WS_HIP(hipMemcpyAsync(q.table_dev.p, q.table_host.p, store_ray_table_slots(c.n_chunks) * sizeof(StoreRaySlot), hipMemcpyHostToDevice, s));
-  WS_HIP(hipMemsetAsync(a.c.hits, 0, sizeof(unsigned long long), s));
-  q.timer.mark(1, s);
-  hipLaunchKernelGGL(store_raycast_kernel, dim3(blocks), dim3(64), 0, s, a);
-  q.timer.mark(2, s);
-  if (flags & WS_RAYCAST_GRADIENT) hipLaunchKernelGGL(store_raycast_grad_kernel, dim3(blocks), dim3(64), 0, s, a);
-  q.timer.mark(3, s);
-  WS_HIP(hipGetLastError());
-  return q.hits.fetch(s);
+  return ray_launch(q, s, a, store_raycast_kernel, store_raycast_grad_kernel);
 }
 
 } // namespace ws

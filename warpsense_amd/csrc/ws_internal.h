@@ -366,6 +366,28 @@ struct QueryTimer
   }
 };
 
+// ---- what a mesh call and a ray-cast call leave behind, whatever they ran over: the window of a map (ws_map::Mesh, ws_map::Raycast)
+// or the chunks of the store (ws_store::Mesh, ws_store::Ray).  Everything is allocated on first use and grown on demand; the one flow
+// of each query (mesh_run, raycast_run in api.hip) and the launchers of the four .hip files take these, not their owners.
+struct MeshResult
+{
+  QueryTimer timer;                    // 0 count passes 1 scans 2, 3 emit passes 4
+  DevBuf scratch;                      // bytes: bit planes, per-word bases and counts, workgroup totals and their scans (mesh_scratch_bytes)
+  DevCounter total;                    // pinned half only: vertices, quads (the device words are in `scratch`)
+  DevBuf vert, face;                   // 16-byte vertices; 3 indices per face
+  size_t nv = 0, nf = 0;               // vertices and faces of the last call
+  void release() { timer.release(), total.release(); for (DevBuf *b : {&scratch, &vert, &face}) b->release(); }
+};
+struct RayResult
+{
+  QueryTimer timer;                    // 0 upload 1 march 2 gradient 3
+  DevBuf dirs, rec, grad;              // int32 [rays][3] staging of host directions; 16-byte records; int32 [rays][3]
+  DevCounter hits;                     // records with range_mm >= 0
+  size_t n = 0;                        // rays of the last call
+  bool has_grad = false;               // the last call also wrote `grad`
+  void release() { timer.release(), hits.release(); for (DevBuf *b : {&dirs, &rec, &grad}) b->release(); }
+};
+
 } // namespace ws
 
 struct ws_context
@@ -446,25 +468,13 @@ struct ws_map
     bool has_marker = false;             // the last call also wrote `marker`
     void release() { timer.release(), total.release(); for (ws::DevBuf *b : {&col_cnt, &blk_tot, &blk_off, &rec, &marker}) b->release(); }
   } surf;
-  struct Mesh // ws_map_mesh (map_mesh.hip)
+  struct Mesh : ws::MeshResult // ws_map_mesh (map_mesh.hip)
   {
     std::mutex mu;
-    ws::QueryTimer timer;                // 0 count passes 1 scans 2, 3 emit passes 4
-    ws::DevBuf scratch;                  // bytes: bit planes, per-word bases and counts, workgroup totals and their scans (mesh_scratch_bytes)
-    ws::DevCounter total;                // pinned half only: vertices, quads (the device words are in `scratch`)
-    ws::DevBuf vert, face;               // 16-byte vertices; 3 indices per face
-    size_t nv = 0, nf = 0;               // vertices and faces of the last call
-    void release() { timer.release(), total.release(); for (ws::DevBuf *b : {&scratch, &vert, &face}) b->release(); }
   } mesh;
-  struct Raycast // ws_map_raycast (map_raycast.hip)
+  struct Raycast : ws::RayResult // ws_map_raycast (map_raycast.hip)
   {
     std::mutex mu;
-    ws::QueryTimer timer;                // 0 upload 1 march 2 gradient 3
-    ws::DevBuf dirs, rec, grad;          // int32 [rays][3] staging of host directions; 16-byte records; int32 [rays][3]
-    ws::DevCounter hits;                 // records with range_mm >= 0
-    size_t n = 0;                        // rays of the last call
-    bool has_grad = false;               // the last call also wrote `grad`
-    void release() { timer.release(), hits.release(); for (ws::DevBuf *b : {&dirs, &rec, &grad}) b->release(); }
   } ray;
   struct Distance // ws_map_distance (map_distance.hip)
   {
@@ -620,31 +630,19 @@ struct ws_store
   } tab[ws::STORE_TABLES];
   int tab_next = 0;
   ws::QueryTimer timer[3]; // per axis of a shift: 0 save 1 load 2 (ws_store_save_box / _load_box use the first)
-  // ws_store_mesh (store_mesh.hip): the result of the last call and the scratch of its passes, allocated on first use and grown on
-  // demand like those of ws_map::Mesh; the store's mutex serialises the calls
-  struct Mesh
+  // ws_store_mesh (store_mesh.hip) and ws_store_raycast (store_raycast.hip): the results of the last calls, apart from each other, and
+  // the chunk table of the call in flight; the store's mutex serialises the calls
+  struct Mesh : ws::MeshResult
   {
-    ws::QueryTimer timer;                // 0 count passes 1 scans 2, 3 emit passes 4
-    ws::DevBuf scratch;                  // bytes: mesh_scratch_bytes(4096 words per listed chunk)
     ws::HostBlock table_host;            // bytes, pinned: the call's chunk tables (store_mesh_table_bytes); free again when the call returns, which synchronises
     ws::DevBuf table_dev;                // ... and the copy the kernels read
-    ws::DevCounter total;                // pinned half only: vertices, quads (the device words are in `scratch`)
-    ws::DevBuf vert, face;               // 16-byte vertices; 3 indices per face
-    size_t nv = 0, nf = 0;               // vertices and faces of the last call
-    void release() { timer.release(), total.release(), table_host.release(); for (ws::DevBuf *b : {&scratch, &table_dev, &vert, &face}) b->release(); }
+    void release() { MeshResult::release(), table_host.release(), table_dev.release(); }
   } mesh;
-  // ws_store_raycast (store_raycast.hip): the result of the last call, apart from the mesh's, allocated on first use and grown on
-  // demand like those of ws_map::Raycast; the store's mutex serialises the calls
-  struct Ray
+  struct Ray : ws::RayResult
   {
-    ws::QueryTimer timer;                // 0 upload 1 march 2 gradient 3
     ws::HostBlock table_host;            // StoreRaySlot, pinned: the call's chunk lookup; free again when the call returns, which synchronises
     ws::DevBuf table_dev;                // ... and the copy the kernels read
-    ws::DevBuf dirs, rec, grad;          // int32 [rays][3] staging of host directions; 16-byte records; int32 [rays][3]
-    ws::DevCounter hits;                 // records with range_mm >= 0
-    size_t n = 0;                        // rays of the last call
-    bool has_grad = false;               // the last call also wrote `grad`
-    void release() { timer.release(), hits.release(), table_host.release(); for (ws::DevBuf *b : {&table_dev, &dirs, &rec, &grad}) b->release(); }
+    void release() { RayResult::release(), table_host.release(), table_dev.release(); }
   } ray;
   void release()
   {
@@ -710,12 +708,12 @@ int launch_box_copy(ws_map *m, const ws::MapParams &par, int which, const int32_
 size_t surface_blocks_for(int64_t n_cols);
 int launch_surface_count(ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], int32_t band);
 int launch_surface_emit(ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], int32_t band, bool marker, size_t cap);
-// map_mesh.hip: bits + cells + quads + scans (the totals arrive in ws_map::mesh.total.host after a stream synchronise), then the emit passes
+// map_mesh.hip: bits + cells + quads + scans (the totals arrive in q.total.host after a stream synchronise), then the emit passes
 size_t mesh_scratch_bytes(uint64_t n_words);
-int launch_mesh_count(ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], uint32_t flags);
-int launch_mesh_emit(ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], uint32_t flags);
-// map_raycast.hip: the march and, with WS_RAYCAST_GRADIENT, the gradient pass (the hit count arrives in ws_map::ray.hits.host after a stream synchronise)
-int launch_raycast(ws_map *m, int which, const int32_t origin[3], const int32_t *dirs_dev, size_t n, int32_t max_range, uint32_t flags);
+int launch_mesh_count(ws_map *m, MeshResult &q, int which, const int32_t lo[3], const int32_t ext[3], uint32_t flags);
+int launch_mesh_emit(ws_map *m, MeshResult &q, int which, const int32_t lo[3], const int32_t ext[3], uint32_t flags);
+// map_raycast.hip: the march and, with WS_RAYCAST_GRADIENT, the gradient pass (the hit count arrives in q.hits.host after a stream synchronise)
+int launch_raycast(ws_map *m, RayResult &q, int which, const int32_t origin[3], const int32_t *dirs_dev, size_t n, int32_t max_range, uint32_t flags);
 // map_distance.hip: pass 0 and the line passes over `n` records (the site count arrives in ws_map::dist.sites.host after a stream synchronise)
 int launch_distance(ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], int32_t R, uint32_t flags, size_t n);
 int fill_u32(ws_context *ctx, uint32_t *dst, uint32_t value, int64_t n);
@@ -729,7 +727,7 @@ int launch_store_copy(ws_store *st, ws_map *m, const ws::MapParams &par, int whi
 
 // store_mesh.hip: the passes of map_mesh.hip over the chunks the call lists.  The host has written the tables of `n_chunks` listed
 // chunks (store_mesh_table_bytes: {B, N, P, n}, then {cx, cy, cz, slot}, then 27 neighbour positions per chunk) into
-// ws_store::mesh.table_host; the totals arrive in ws_store::mesh.total.host after a stream synchronise
+// q.table_host; the totals arrive in q.total.host after a stream synchronise
 struct StoreMeshCall
 {
   uint32_t n_chunks; // < 2^19: 4096 words each
@@ -738,13 +736,12 @@ struct StoreMeshCall
   int32_t lo[3], hi[3]; // the box, inclusive world voxels
 };
 size_t store_mesh_table_bytes(size_t n_chunks);
-int launch_store_mesh_count(ws_store *st, const StoreMeshCall &c);
-int launch_store_mesh_emit(ws_store *st, const StoreMeshCall &c);
+int launch_store_mesh_count(ws_store *st, ws_store::Mesh &q, const StoreMeshCall &c);
+int launch_store_mesh_emit(ws_store *st, ws_store::Mesh &q, const StoreMeshCall &c);
 
 // store_raycast.hip: the march of ws_raycast.h over the chunks the call lists.  The kernels find a chunk through an open-addressing
 // table key -> slot of a power-of-two size >= 2 x listed chunks (linear probing from store_ray_hash; an empty place has slot
-// STORE_ABSENT), which the host has written into ws_store::ray.table_host; the hit count arrives in ws_store::ray.hits.host after a
-// stream synchronise
+// STORE_ABSENT), which the host has written into q.table_host; the hit count arrives in q.hits.host after a stream synchronise
 struct alignas(16) StoreRaySlot
 {
   int32_t cx, cy, cz;
@@ -789,7 +786,7 @@ struct StoreRayCall
   int32_t lo[3], hi[3]; // the box, inclusive world voxels
   int32_t blo[3], bhi[3]; // the bounding box of the listed chunks, cut to the box
 };
-int launch_store_raycast(ws_store *st, const StoreRayCall &c, const int32_t origin[3], const int32_t *dirs_dev, size_t n, int32_t max_range, uint32_t flags);
+int launch_store_raycast(ws_store *st, ws_store::Ray &q, const StoreRayCall &c, const int32_t origin[3], const int32_t *dirs_dev, size_t n, int32_t max_range, uint32_t flags);
 
 int launch_reg_iteration(ws_reg *r, const ws_map *m, int32_t res, uint32_t flags, int32_t k);
 // reg_pass_kernel over points [first, first + count): from the newest state (first the update from `sums` if `apply`) into `sums`;

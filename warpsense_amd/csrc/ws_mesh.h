@@ -54,6 +54,45 @@ inline void mesh_take_scratch(MeshBuffers &a, void *scratch, size_t n_words)
   a.totals = reinterpret_cast<mu64 *>(take(16));
 }
 
+// the scratch of `n_words` words and the outputs of a result holder.  The count passes write no output and are given no capacity
+inline void mesh_bind(MeshBuffers &a, const MeshResult &q, size_t n_words, bool emit)
+{
+  mesh_take_scratch(a, q.scratch.p, n_words);
+  a.vert = static_cast<mi32x4 *>(q.vert.p);
+  a.face = static_cast<uint32_t *>(q.face.p);
+  a.vcap = emit ? q.vert.cap : 0;
+  a.qcap = emit ? q.face.cap / 2 : 0;
+}
+
+// The two launch sequences, whatever a word index means: `Args` is the including file's MeshBuffers with n_words, the kernels are its six.
+// bits, cells, quads and the scans; the two totals arrive in q.total.host (pinned) once the stream has been synchronised
+template <typename Args>
+int mesh_launch_count(MeshResult &q, hipStream_t s, const Args &a, uint32_t bits_blocks, void (*bits)(Args), void (*cells)(Args), void (*quads)(Args),
+                      void (*scan)(Args, uint32_t))
+{
+  const uint32_t blocks = mesh_blocks(a.n_words);
+  q.timer.mark(0, s);
+  hipLaunchKernelGGL(bits, dim3(bits_blocks), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(cells, dim3(blocks), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(quads, dim3(blocks), dim3(256), 0, s, a);
+  q.timer.mark(1, s);
+  hipLaunchKernelGGL(scan, dim3(2), dim3(1024), 0, s, a, blocks);
+  q.timer.mark(2, s);
+  WS_HIP(hipGetLastError());
+  return q.total.fetch(s, 2, a.totals);
+}
+// vertices, then faces (which read the vertex pass's vbase)
+template <typename Args> int mesh_launch_emit(MeshResult &q, hipStream_t s, const Args &a, void (*vertex)(Args), void (*face)(Args))
+{
+  const uint32_t blocks = mesh_blocks(a.n_words);
+  q.timer.mark(3, s);
+  hipLaunchKernelGGL(vertex, dim3(blocks), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(face, dim3(blocks), dim3(256), 0, s, a);
+  q.timer.mark(4, s);
+  WS_HIP(hipGetLastError());
+  return WS_OK;
+}
+
 __device__ __forceinline__ mu64 shift_down(mu64 cur, mu64 next) { return (cur >> 1) | (next << 63); } // bit z := bit z + 1
 __device__ __forceinline__ uint32_t popc_below(mu64 mask, int lane) { return (uint32_t)__popcll(mask & ((1ull << lane) - 1ull)); }
 

@@ -34,8 +34,8 @@ struct RayCommon
   int32_t *grad;
   unsigned long long *hits;
 };
-inline RayCommon ray_common(const int32_t origin[3], const int32_t *dirs_dev, size_t n, int32_t res, int32_t max_range, uint32_t flags, void *rec, void *grad,
-                            unsigned long long *hits)
+// ... into the buffers of a result holder
+inline RayCommon ray_common(const RayResult &q, const int32_t origin[3], const int32_t *dirs_dev, size_t n, int32_t res, int32_t max_range, uint32_t flags)
 {
   RayCommon a;
   for (int k = 0; k < 3; ++k) a.origin[k] = origin[k];
@@ -47,10 +47,24 @@ inline RayCommon ray_common(const int32_t origin[3], const int32_t *dirs_dev, si
   a.K = (uint32_t)(max_range / a.step);
   a.rdiv = make_fastdiv(res);
   a.flags = flags;
-  a.rec = static_cast<ri32x4 *>(rec);
-  a.grad = static_cast<int32_t *>(grad);
-  a.hits = hits;
+  a.rec = static_cast<ri32x4 *>(q.rec.p);
+  a.grad = static_cast<int32_t *>(q.grad.p);
+  a.hits = q.hits.dev;
   return a;
+}
+// The launch sequence, whatever the field: `Args` is the including file's, with the RayCommon `c`.  The march (events 1, 2), then the
+// gradient if asked for (events 2, 3); the hit count arrives in q.hits.host (pinned) once the stream has been synchronised
+template <typename Args> int ray_launch(RayResult &q, hipStream_t s, const Args &a, void (*march)(Args), void (*gradient)(Args))
+{
+  const uint32_t blocks = (a.c.n + 63u) / 64u;
+  WS_HIP(hipMemsetAsync(a.c.hits, 0, sizeof(unsigned long long), s));
+  q.timer.mark(1, s);
+  hipLaunchKernelGGL(march, dim3(blocks), dim3(64), 0, s, a);
+  q.timer.mark(2, s);
+  if (a.c.flags & WS_RAYCAST_GRADIENT) hipLaunchKernelGGL(gradient, dim3(blocks), dim3(64), 0, s, a);
+  q.timer.mark(3, s);
+  WS_HIP(hipGetLastError());
+  return q.hits.fetch(s);
 }
 
 __device__ __forceinline__ bool ray_valid(uint32_t raw, bool any_weight)
