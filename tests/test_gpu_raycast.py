@@ -129,24 +129,25 @@ RANDOM_MAPS = [((21, 17, 13), 5), ((33, 33, 33), 7)]
 RANDOM_LO = (-7, 2, -3)
 
 
-def random_rays(size, seed, lo=RANDOM_LO, n=2048):
+def random_rays(size, seed, lo=RANDOM_LO, n=2048, res=RES):
     """origin at the window's centre, directions uniform in [-32768, 32768]^3"""
     rng = np.random.default_rng(seed)
-    o = ((np.asarray(lo) + np.asarray(size) / 2) * RES).astype(np.int64)
+    o = ((np.asarray(lo) + np.asarray(size) / 2) * res).astype(np.int64)
     return o, rng.integers(-32768, 32769, (n, 3))
 
 
-def sphere_rays(centre, radius, n=4096):
+def sphere_rays(centre, radius, n=4096, res=RES):
     """origin at (SPHERE_LO + 1.5) res, rays towards centre + N(0, (0.9 R)^2) points"""
     lo = np.asarray(M.SPHERE_LO)
-    c_mm = (lo + np.asarray(centre)) * RES
-    o = ((lo + 1.5) * RES).astype(np.int64)
-    tgt = c_mm + np.random.default_rng(1).normal(size=(n, 3)) * radius * RES * 0.9
+    c_mm = (lo + np.asarray(centre)) * res
+    o = ((lo + 1.5) * res).astype(np.int64)
+    tgt = c_mm + np.random.default_rng(1).normal(size=(n, 3)) * radius * res * 0.9
     return o, np.round(tgt - o).astype(np.int64), c_mm
 
 
-def check_sphere(rec, o, d, c_mm, r_mm):
-    """the conditions of a ray cast of a sphere map; returns (rays within 0.8 R, largest distance to the sphere, largest range error)"""
+def check_sphere(rec, o, d, c_mm, r_mm, bound=RES / 10):
+    """the conditions of a ray cast of a sphere map; returns (rays within 0.8 R, largest distance to the sphere, largest range error).
+    bound: of the two errors in mm, measured for the resolution of the map (res / 10 = 5 mm at res 50)"""
     hit = rec["range_mm"] >= 0
     u = d / np.linalg.norm(d.astype(np.float64), axis=1)[:, None]
     oc = (o - c_mm).astype(np.float64)
@@ -160,7 +161,7 @@ def check_sphere(rec, o, d, c_mm, r_mm):
     print("sphere", r_mm, "core", int(core.sum()), "hits", int(hit.sum()), "dist max", dist.max(), "range err max", err.max())
     assert core.sum() > 1000 and np.all(hit[core])              # every ray that passes the centre within 0.8 R hits
     assert not np.any(hit & (imp > r_mm))                       # no ray whose line misses the sphere hits
-    assert dist.max() <= RES / 10 and err.max() <= RES / 10    # 5 mm
+    assert dist.max() <= bound and err.max() <= bound
     return int(core.sum()), float(dist.max()), float(err.max())
 
 

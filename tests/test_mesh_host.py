@@ -87,18 +87,25 @@ def test_model_reproduces_the_hand_computed_case():
     assert (2 * 32768 * 50 + 65535) // (2 * 65535) == 25 and (2 * 0 * 50 + 1) // 2 == 0 and (2 * 1 * 50 + 1) // 2 == 50
 
 
+def sphere_mesh_numbers(edge, centre, radius, res=M.RES, tau=M.TAU):
+    """the model's mesh of a sphere map: closed, Euler characteristic 2; returns (volume / the sphere's, largest distance of a vertex
+    to the sphere in mm)"""
+    box = M.sphere_box(edge, centre, radius, res=res, tau=tau).reshape((edge,) * 3)
+    vert, face = M.model_box(box, M.SPHERE_LO, res)
+    rep = M.mesh_report(vert, face)
+    assert rep["closed"] and rep["directed_once"] and rep["chi"] == 2 and rep["unreferenced"] == 0, rep
+    sphere = 4.0 / 3.0 * np.pi * (radius * res) ** 3
+    p = np.stack([vert["x_mm"], vert["y_mm"], vert["z_mm"]], axis=1).astype(np.float64)
+    c = (np.asarray(M.SPHERE_LO) + np.asarray(centre)) * res
+    dist = np.abs(np.sqrt(np.sum((p - c) ** 2, axis=1)) - radius * res)
+    print(edge, res, len(vert), len(face), rep["volume"] / sphere, dist.max())
+    return rep["volume"] / sphere, float(dist.max())
+
+
 def test_sphere_maps_give_closed_meshes_of_the_right_size():
     for edge, centre, radius in M.SPHERES:
-        box = M.sphere_box(edge, centre, radius).reshape((edge,) * 3)
-        vert, face = M.model_box(box, M.SPHERE_LO, M.RES)
-        rep = M.mesh_report(vert, face)
-        assert rep["closed"] and rep["directed_once"] and rep["chi"] == 2 and rep["unreferenced"] == 0, rep
-        sphere = 4.0 / 3.0 * np.pi * (radius * M.RES) ** 3
-        p = np.stack([vert["x_mm"], vert["y_mm"], vert["z_mm"]], axis=1).astype(np.float64)
-        c = (np.asarray(M.SPHERE_LO) + np.asarray(centre)) * M.RES
-        dist = np.abs(np.sqrt(np.sum((p - c) ** 2, axis=1)) - radius * M.RES)
-        print(edge, len(vert), len(face), rep["volume"] / sphere, dist.max())
-        assert abs(rep["volume"] / sphere - 1.0) < 0.03 and dist.max() < M.RES / 10
+        ratio, dist = sphere_mesh_numbers(edge, centre, radius)
+        assert abs(ratio - 1.0) < 0.03 and dist < M.RES / 10
 
 
 def test_holes_in_the_map_never_double_an_edge():

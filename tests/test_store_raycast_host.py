@@ -24,20 +24,23 @@ CTYPE = dict(MH.CTYPE, **{"ws_store *": C.c_void_p, "const ws_store *": C.c_void
 
 
 # ------------------------------------------------------------------------------------------------ the field over chunks
-def _code(c):
-    """one ascending int64 per chunk key (|key| < 2^20 per axis)"""
-    c = np.asarray(c, dtype=np.int64)
+def _code(c, base=0):
+    """one ascending int64 per chunk key (|key - base| < 2^20 per axis)"""
+    c = np.asarray(c, dtype=np.int64) - base
     assert np.all(np.abs(c) < 2 ** 20)
     return ((c[..., 0] + 2 ** 20) << 42) | ((c[..., 1] + 2 ** 20) << 21) | (c[..., 2] + 2 ** 20)
 
 
 class Chunks:
     """the field of ws_store_raycast for test_gpu_raycast.model: a dict key -> 262 144 raw entries; a voxel of an absent chunk and a
-    voxel outside the inclusive box [lo, hi] (None: everything) are not valid"""
+    voxel outside the inclusive box [lo, hi] (None: everything) are not valid.  base: a chunk key near the chunks, for keys beyond the
+    2^20 of the packing; every voxel asked for must then lie within 2^20 chunks of it"""
 
-    def __init__(self, chunks, lo=None, hi=None):
+    def __init__(self, chunks, lo=None, hi=None, base=(0, 0, 0)):
         keys = sorted(chunks)
-        self.code = _code(np.asarray(keys, dtype=np.int64).reshape(-1, 3))
+        self.base = np.asarray(base, dtype=np.int64)
+        self.far_is_absent = bool(np.any(self.base != 0))
+        self.code = _code(np.asarray(keys, dtype=np.int64).reshape(-1, 3), self.base)
         self.data = (np.stack([np.asarray(chunks[k], dtype=np.uint32).reshape(CS, CS, CS) for k in keys]) if keys
                      else np.zeros((1, CS, CS, CS), dtype=np.uint32))
         self.lo = None if lo is None else np.asarray(lo, dtype=np.int64)
@@ -45,9 +48,12 @@ class Chunks:
 
     def entries(self, v, any_weight):
         v = np.asarray(v, dtype=np.int64)
-        code = _code(v >> 6)
+        key = v >> 6
+        near = np.all(np.abs(key - self.base) < 2 ** 20, axis=1)  # (no chunk lies beyond the packing: the key of such a voxel is not looked up)
+        assert self.far_is_absent or near.all()  # without a base a voxel beyond the packing is a mistake of the fixture
+        code = _code(np.where(near[:, None], key, self.base), self.base)
         i = np.minimum(np.searchsorted(self.code, code), max(len(self.code) - 1, 0))
-        present = (self.code[i] == code) if len(self.code) else np.zeros(len(v), dtype=bool)
+        present = ((self.code[i] == code) & near) if len(self.code) else np.zeros(len(v), dtype=bool)
         l = v & 63
         value, weight = M.unpack(self.data[i, l[:, 0], l[:, 1], l[:, 2]])
         value, weight = value.astype(np.int64), weight.astype(np.int64)

@@ -133,7 +133,7 @@ struct StoreField
       for (int x = 0; x < 3; ++x)
       {
         if (b[x] < a.blo[x]) kn = max(kn, w.first_voxel(rc, x, a.blo[x]));
-        if (b[x] >= a.bhi[x]) kn = max(kn, w.first_voxel(rc, x, a.bhi[x] - 1));
+        if (b[x] >= a.bhi[x]) kn = max(kn, w.first_voxel(rc, x, (int64_t)a.bhi[x] - 1));
       }
     }
     else if (!cp)
@@ -141,7 +141,7 @@ struct StoreField
       kn = 0xffffffffu;
 #pragma unroll
       for (int x = 0; x < 3; ++x)
-        if (w.sgn[x] != 0) kn = min(kn, w.first_voxel(rc, x, w.sgn[x] > 0 ? ck[x] * STORE_CS + STORE_CS : ck[x] * STORE_CS - 1));
+        if (w.sgn[x] != 0) kn = min(kn, w.first_voxel(rc, x, (int64_t)ck[x] * STORE_CS + (w.sgn[x] > 0 ? STORE_CS : -1))); // (up to 2^31)
     }
     else
       return k + 1u; // an unobserved corner, or a missing neighbour chunk: the next cell decides for itself

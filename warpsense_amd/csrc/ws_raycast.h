@@ -222,10 +222,10 @@ struct RayWalk
     return k > 0xfffffffeull ? 0xffffffffu : (uint32_t)k;
   }
   // the first sample whose base voxel on axis x is >= v (sgn > 0) / <= v (sgn < 0):  b >= v  iff  p - half >= v res,
-  // b <= v  iff  p - half <= v res + res - 1
-  __device__ __forceinline__ uint32_t first_voxel(const RayCommon &a, int x, int32_t v) const
+  // b <= v  iff  p - half <= v res + res - 1.  v is 64-bit: the voxel behind the last chunk of int32 voxel space is 2^31
+  __device__ __forceinline__ uint32_t first_voxel(const RayCommon &a, int x, int64_t v) const
   {
-    const int64_t edge = (int64_t)v * (int64_t)a.res + (int64_t)a.half - (int64_t)a.origin[x];
+    const int64_t edge = v * (int64_t)a.res + (int64_t)a.half - (int64_t)a.origin[x];
     return first_at(a, x, sgn[x] > 0 ? edge : -(edge + (int64_t)a.res - 1));
   }
 };
