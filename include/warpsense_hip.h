@@ -462,6 +462,46 @@ int ws_debug_store_raycast_timing(ws_store *st, int32_t enable, float ms_out[3])
 int ws_debug_store_raycast_table(const int32_t *keys_slots, size_t n, int32_t *table, size_t capacity_places, size_t *n_places);
 uint32_t ws_debug_store_raycast_find(const int32_t *table, size_t n_places, const int32_t key[3]);
 
+/* The distance field of the store: ws_map_distance applied to the field of ws_store_mesh -- the cost map of the whole run, not of the
+ * window around the sensor: a goal, a frontier or a return path lies exactly where the window no longer is -- on the device, without
+ * a chunk leaving HBM.
+ *   field: a voxel of a present chunk holds that chunk's entry.  A voxel of an absent chunk is NOT VALID (class 0, UNKNOWN), whatever
+ *     fill_entry is: under WS_DISTANCE_UNKNOWN_OCCUPIED such a voxel is therefore a site, and it counts in *n_sites.
+ *   rules: everything else is word for word the rule set of ws_map_distance applied to that field -- the classes and
+ *     WS_DISTANCE_ANY_WEIGHT; the sites, which lie inside the box only; 1 <= R <= 255, else WS_ERR_RANGE;
+ *     d2 = min(R², min over sites |v - s|²); the record (bits 0..23 d2, bits 30..31 the class); the dense order, x major, z fastest;
+ *     WS_DISTANCE_COLUMNS with its nx ny records, y fastest; the four flag values.  Under WS_DISTANCE_COLUMNS the precedence of a
+ *     column is part of the rules: occupied wins, then unknown-as-site, then free; an absent chunk contributes unknown voxels.
+ *   box: inclusive world voxels [lo, hi], anywhere in int32 voxel space; it need not lie in any window.  Extents are formed in 64 bits.
+ *     Both NULL: the bounding box of the present chunks, as for ws_store_mesh; an empty store with a NULL box is WS_OK with zero
+ *     records and zero sites.  Exactly one NULL, or hi < lo: WS_ERR_INVALID.
+ *   limits: more than 2^32 - 1 records (nx ny nz, or nx ny under WS_DISTANCE_COLUMNS, whose z extent is bounded only by int32) is
+ *     WS_ERR_RANGE, and so is a box that overlaps 2^19 present chunks or more.  Also WS_ERR_RANGE: more than 16 776 960 voxels along
+ *     the fastest axis of the records (nz, or ny under WS_DISTANCE_COLUMNS): the row pass holds a line in 65 535 workgroups.  Unknown
+ *     flag bits: WS_ERR_INVALID.  On a refusal nothing is launched and the last result stays.  An allocation that fails is
+ *     WS_ERR_HIP and leaves the store usable.
+ *   consequence: if a window holds the same voxels as the store inside a box, the box lies in that window, and fill_entry has weight 0
+ *     (so that what ws_store_load_box writes for an absent chunk is not valid either), ws_map_distance on that window and box returns
+ *     the same bytes and the same site count, under every flag combination.
+ *   ordering: the work is stream-ordered behind every save, load and shift already enqueued on the store's context; the call
+ *     synchronises (*n_sites, may be NULL, comes back), is read-only on the chunks and is serialised with the other store calls by the
+ *     store's mutex.
+ *   result buffer: it belongs to the store, is not allocated before the first call and grows on demand; it stays valid until the next
+ *     ws_store_distance on the store -- later saves, loads, shifts and drops leave it untouched -- and is apart from the results of
+ *     ws_store_mesh and ws_store_raycast.  Every output write is bounded by the buffers' capacities.
+ *   cost: unlike the store's mesh and ray cast, this result is DENSE.  Scratch and result are 8 bytes per record of the box, and the
+ *     line passes follow the box.  Only pass 0 follows the present chunks: absent chunks are never read, and under
+ *     WS_DISTANCE_COLUMNS a column is walked only across the z range of the listed chunks.  The chunk table is 32 to 64 bytes per
+ *     listed chunk and never follows the volume of the box. */
+int ws_store_distance(ws_store *st, const int32_t lo[3], const int32_t hi[3], int32_t max_dist_vox, uint32_t flags, size_t *n_sites);
+const uint32_t *ws_store_distance_dev(const ws_store *st, size_t *n); /* device memory, n records; NULL before the first call (n == 0) */
+/* copies at most `capacity` records (a prefix) and always reports the total in *n_out; host may be NULL */
+int ws_store_distance_download(ws_store *st, uint32_t *host, size_t capacity, size_t *n_out);
+/* Measurement entry, as ws_debug_distance_timing: ms_out receives the device time of pass 0 (the classification; the chunk table's
+ * upload lies in front of it) and of the x, y and z line passes of the last call (under WS_DISTANCE_COLUMNS: pass 0, the x pass, the
+ * y pass, 0) */
+int ws_debug_store_distance_timing(ws_store *st, int32_t enable, float ms_out[4]);
+
 /* ------------------------------------------------------------------ TSDF update ---- */
 /* TSDFCuda::update_tsdf(scan_points, scanner_pos, up) — update_tsdf.cu:143-166.
  * xyz_host: n x 3 int32 (rmagine::Pointi AoS); scanner_pos in voxel units, up scaled by 32768.

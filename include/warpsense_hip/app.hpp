@@ -317,6 +317,12 @@ public:
     WS_CHECK(ws_store_put_chunk(store_, c.data(), data.data()));
   }
   void drop_chunk(const Key &c) { WS_CHECK(ws_store_drop_chunk(store_, c.data())); }
+  // the distance field of the chunks (visualization.hpp, ws_store_distance)
+  DistanceField distance(int32_t max_dist_vox, bool unknown_occupied = false, bool columns = false, bool any_weight = false, const rm::Pointi *lo = nullptr,
+                         const rm::Pointi *hi = nullptr)
+  {
+    return global_map_distance(store_, max_dist_vox, unknown_occupied, columns, any_weight, lo, hi);
+  }
   // every chunk merged into the host global map (and through it into its file)
   void flush_to(GlobalMap &g)
   {
@@ -636,6 +642,18 @@ public:
     local_map_.window(wlo, whi);
     WS_CHECK(ws_store_save_box(device_global_map_->handle(), gpu_.tsdf().handle(), WS_MAP_AVG, &wlo.x, &whi.x));
     return global_map_raycast(*device_global_map_, params_.map_resolution, origin_mm, dirs, max_range_mm, any_weight, with_gradient, lo, hi, targets);
+  }
+  // The cost map of everything the run has seen: the window into the device chunks, as global_mesh does, then the distance field of
+  // the store -- nothing leaves the device but the records
+  DistanceField global_distance(int32_t max_dist_vox, bool unknown_occupied = false, bool columns = false, bool any_weight = false, const rm::Pointi *lo = nullptr,
+                                const rm::Pointi *hi = nullptr)
+  {
+    if (!device_global_map_) throw std::logic_error("global_distance: no DeviceGlobalMap attached");
+    wait_shift();
+    rm::Pointi wlo, whi;
+    local_map_.window(wlo, whi);
+    WS_CHECK(ws_store_save_box(device_global_map_->handle(), gpu_.tsdf().handle(), WS_MAP_AVG, &wlo.x, &whi.x));
+    return device_global_map_->distance(max_dist_vox, unknown_occupied, columns, any_weight, lo, hi);
   }
   // the reference's route, kept for comparison: whole window to the host array of the local map
   void download() { gpu_.tsdf().avg_map().to_host(view_); }

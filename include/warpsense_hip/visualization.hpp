@@ -6,6 +6,7 @@
 //   local_map_raycast    (no counterpart: the reference leaves all viewing to RViz)            a predicted scan, over ws_map_raycast
 //   global_map_raycast   (no counterpart)                                                     a predicted scan from anywhere the run has been, over ws_store_raycast
 //   local_map_distance   (no counterpart: the reference has no distance field)                   a cost map, over ws_map_distance
+//   global_map_distance  (no counterpart)                                                     the cost map of the whole run, over ws_store_distance
 //   local_map_skeleton   publish_local_map_skeleton  map.h:175-227   the 24 end points of the window's line list (host only)
 //
 // The reference walks every voxel of a host map (after a whole-map download for the CUDA map, test/pcd2tsdf.cpp:134-137); here
@@ -15,6 +16,7 @@
 // There is deliberately no forwarding header under the reference's visualization/map.h name: its functions take a ros::Publisher.
 #pragma once
 
+#include <algorithm>
 #include <array>
 #include <vector>
 
@@ -180,6 +182,42 @@ inline DistanceField local_map_distance(cuda::TSDFCuda &tsdf, int32_t max_dist_v
   WS_CHECK(ws_map_distance_download(tsdf.handle(), nullptr, 0, &n));
   out.records.resize(n);
   WS_CHECK(ws_map_distance_download(tsdf.handle(), n ? out.records.data() : nullptr, n, &n));
+  return out;
+}
+
+// The distance field of the global map in device memory (the rules: warpsense_hip.h at ws_store_distance): ws_map_distance's records
+// over everything the store's chunks hold inside the inclusive world-voxel box [lo, hi] (both nullptr: the bounding box of the present
+// chunks), which need not lie in any window.  Voxels of absent chunks are unknown.  The result is dense: 8 bytes of device memory per
+// record of the box.  (app.hpp adds DeviceGlobalMap::distance.)
+inline DistanceField global_map_distance(ws_store *store, int32_t max_dist_vox, bool unknown_occupied = false, bool columns = false, bool any_weight = false,
+                                         const rmagine::Pointi *lo = nullptr, const rmagine::Pointi *hi = nullptr)
+{
+  DistanceField out;
+  const uint32_t flags = (any_weight ? WS_DISTANCE_ANY_WEIGHT : 0u) | (unknown_occupied ? WS_DISTANCE_UNKNOWN_OCCUPIED : 0u) | (columns ? WS_DISTANCE_COLUMNS : 0u);
+  if (lo && hi)
+  {
+    const int32_t *a = &lo->x, *b = &hi->x;
+    for (int k = 0; k < 3; ++k) out.extent[k] = (int32_t)((int64_t)b[k] - (int64_t)a[k] + 1); // (a 3-D extent fits: the records are counted in 32 bits)
+  }
+  else if (!lo && !hi)
+  {
+    size_t nk = 0;
+    WS_CHECK(ws_store_keys(store, nullptr, 0, &nk));
+    std::vector<int32_t> keys(3 * nk);
+    WS_CHECK(ws_store_keys(store, keys.data(), nk, &nk));
+    for (int k = 0; k < 3 && nk; ++k)
+    {
+      int32_t kmin = keys[k], kmax = keys[k];
+      for (size_t i = 1; i < nk; ++i) kmin = std::min(kmin, keys[3 * i + k]), kmax = std::max(kmax, keys[3 * i + k]);
+      out.extent[k] = (int32_t)(((int64_t)kmax - (int64_t)kmin + 1) * 64);
+    }
+  }
+  WS_CHECK(ws_store_distance(store, lo ? &lo->x : nullptr, hi ? &hi->x : nullptr, max_dist_vox, flags, &out.sites));
+  if (columns) out.extent[2] = 1;
+  size_t n = 0;
+  WS_CHECK(ws_store_distance_download(store, nullptr, 0, &n));
+  out.records.resize(n);
+  WS_CHECK(ws_store_distance_download(store, n ? out.records.data() : nullptr, n, &n));
   return out;
 }
 

@@ -3,7 +3,7 @@ sliding TSDF map @ 5 cm, one MI355X): sensor clouds in float metres -> device pr
 (when the sensor moved > 0.3 m) -> Point-to-TSDF registration -> pose -> map shift (device-side slabs).
 
     python tools/replay_stream.py --map 1024 --scans 30 [--h5 /tmp/stream.h5] [--async-shift | --device-global-map] [--surface-ply DIR [--surface-every N]] [--mesh-ply DIR]
-                                   [--raycast-ply DIR] [--distance-npy DIR [--distance-m M]]
+                                   [--raycast-ply DIR] [--distance-npy DIR [--distance-m M]] [--global-distance-npy FILE [--global-distance-m M]]
                                    [--moving-sweeps] [--deskew]
 
 Prints one JSON line: scans/s over the stream and the mean per-stage times (the reference's RuntimeEvaluator
@@ -78,6 +78,10 @@ def main():
                     "columns=True: per (x, y) column the squared distance in voxels to the nearest column with an occupied voxel, and its class) as "
                     "a uint32 .npy into DIR")
     ap.add_argument("--distance-m", type=float, default=2.0, metavar="M", help="... clamped at M metres")
+    ap.add_argument("--global-distance-npy", default=None, metavar="FILE", help="after the last scan: the 2-D cost map of the WHOLE run (TSDFMapping."
+                    "global_distance_field, ws_store_distance, columns=True) over the x, y bounding box of the chunks of the device global map and the "
+                    "z range of the window, the band of --distance-npy, as a uint32 .npy; needs --device-global-map")
+    ap.add_argument("--global-distance-m", type=float, default=2.0, metavar="M", help="... clamped at M metres")
     ap.add_argument("--surface-every", type=int, default=10, metavar="N", help="... after every N-th scan")
     ap.add_argument("--kidnap", type=int, default=0, metavar="N", help="at scan N (1-based) replace the tracked pose by a wrong one (--kidnap-offset, "
                     "--kidnap-yaw), re-localise with TSDFRegistration.relocalize on a pose lattice around it (one launch for all candidates), "
@@ -94,6 +98,8 @@ def main():
         ap.error("--global-mesh-ply requires --device-global-map")
     if args.global_raycast_ply and not args.device_global_map:
         ap.error("--global-raycast-ply requires --device-global-map")
+    if args.global_distance_npy and not args.device_global_map:
+        ap.error("--global-distance-npy requires --device-global-map")
     import warpsense_amd as W
     from warpsense_amd import synthetic as S
 
@@ -184,6 +190,22 @@ def main():
         global_mesh = {"file": args.global_mesh_ply, "vertices": int(len(gv)), "faces": int(len(gf)), "chunks": app.gpu_.device_global_map_.count(), "call_s": tg}
         print(f"global mesh: {len(gv)} vertices, {len(gf)} faces from {global_mesh['chunks']} chunks in {1000.0 * tg:.2f} ms (save_box + ws_store_mesh + download)",
               file=sys.stderr)
+    global_distance = None
+    if args.global_distance_npy:
+        tg = time.perf_counter()
+        store = app.gpu_.device_global_map_
+        wlo, whi = app.hdf5_local_map_.window()
+        keys = np.asarray(store.keys() + [tuple(int(v) // 64 for v in wlo), tuple(int(v) // 64 for v in whi)], dtype=np.int64)
+        lo = (int(keys[:, 0].min()) * 64, int(keys[:, 1].min()) * 64, int(wlo[2]))
+        hi = (int(keys[:, 0].max()) * 64 + 63, int(keys[:, 1].max()) * 64 + 63, int(whi[2]))
+        cost = app.gpu_.global_distance_field(lo=lo, hi=hi, max_dist_m=args.global_distance_m, columns=True)
+        tg = time.perf_counter() - tg
+        os.makedirs(os.path.dirname(os.path.abspath(args.global_distance_npy)), exist_ok=True)
+        np.save(args.global_distance_npy, cost)
+        global_distance = {"file": args.global_distance_npy, "lo": lo, "hi": hi, "columns": [int(v) for v in cost.shape], "site_columns": int(store.last_sites),
+                           "chunks": store.count(), "call_s": tg}
+        print(f"global cost map: {cost.shape[0]} x {cost.shape[1]} columns, {store.last_sites} site columns from {global_distance['chunks']} chunks in "
+              f"{1000.0 * tg:.2f} ms (save_box + ws_store_distance + download)", file=sys.stderr)
     global_raycast = None
     if args.global_raycast_ply:
         first = app.poses[0].astype(np.float64).copy()
@@ -224,6 +246,7 @@ def main():
                       "mesh_ply": mesh if args.mesh_ply else None,
                       "global_mesh_ply": global_mesh,
                       "global_raycast_ply": global_raycast,
+                      "global_distance_npy": global_distance,
                       "raycast_ply": raycast if args.raycast_ply else None,
                       "distance_npy": distance if args.distance_npy else None,
                       "kidnap": kidnap}))

@@ -526,6 +526,37 @@ def _raycast_call(L, name, handle, lead, origin_mm, dirs, max_range_mm, tail, an
     return rec, grad, int(hits.value)
 
 
+def _distance_call(L, name, owner, lead, lo, hi, max_dist_vox, unknown_occupied, columns, any_weight, device, default_shape):
+    """The distance call `name` (ws_map_distance, ws_store_distance) on owner.handle and its result: `lead` are the arguments of the
+    entry point before the box, default_shape() the extent of the box that lo = hi = None stands for.  owner keeps a device tensor's
+    memory alive.  Returns (records, sites)."""
+    if (lo is None) != (hi is None):
+        raise WsError("distance: give both lo and hi, or neither")
+    flags = ((_lib.WS_DISTANCE_ANY_WEIGHT if any_weight else 0) | (_lib.WS_DISTANCE_UNKNOWN_OCCUPIED if unknown_occupied else 0)
+             | (_lib.WS_DISTANCE_COLUMNS if columns else 0))
+    if lo is not None:
+        shape = tuple(int(v) for v in (_i3(hi).astype(np.int64) - _i3(lo).astype(np.int64) + 1))
+    else:
+        shape = default_shape()
+    sites = C.c_size_t(0)
+    check(getattr(L, name)(owner.handle, *lead, _ptr(_i3(lo)) if lo is not None else None, _ptr(_i3(hi)) if hi is not None else None,
+                           int(max_dist_vox), flags, C.byref(sites)), name)
+    if columns:
+        shape = shape[:2]
+    n = int(np.prod(shape, dtype=np.int64))
+    cnt = C.c_size_t(0)
+    if device:
+        ptr = getattr(L, name + "_dev")(owner.handle, C.byref(cnt))
+        if int(cnt.value) != n:
+            raise WsError("distance: another call replaced the result")
+        return _device_tensor(ptr, shape, "<i4", owner), int(sites.value)
+    rec = np.empty(n, dtype=np.uint32)
+    check(getattr(L, name + "_download")(owner.handle, _ptr(rec), n, C.byref(cnt)), name + "_download")
+    if int(cnt.value) != n:
+        raise WsError("distance: another call replaced the result before it was downloaded")
+    return rec.reshape(shape), int(sites.value)
+
+
 class DeviceGlobalMap:
     """The global map in device memory (ws_store, include/warpsense_hip.h): the device twin of GlobalMap.  64^3-voxel chunks of raw
     uint32 entries in HBM, index x*4096 + y*64 + z, keyed by floor(world voxel / 64); chunks never seen hold the default entry.  The
@@ -630,6 +661,28 @@ class DeviceGlobalMap:
         """device milliseconds of the upload, the march and the gradient pass of the last raycast() (ws_debug_store_raycast_timing)"""
         ms = (C.c_float * 3)()
         check(self._L.ws_debug_store_raycast_timing(self.handle, int(enable), ms), "ws_debug_store_raycast_timing")
+        return tuple(float(v) for v in ms)
+
+    def distance(self, lo=None, hi=None, max_dist_vox=20, unknown_occupied=False, columns=False, any_weight=False, device=False):
+        """The distance field of the chunks on the device (ws_store_distance; the rules are those of ws_map_distance, stated in
+        include/warpsense_hip.h): per voxel of the inclusive world-voxel box [lo, hi] (both None: the bounding box of the present
+        chunks) the squared Euclidean distance in voxels to the nearest occupied voxel of the box, clamped at max_dist_vox squared
+        (1 .. 255).  Voxels of absent chunks are unknown: with unknown_occupied they are sites.  columns, any_weight, the returned
+        uint32 records shaped (nx, ny, nz) or (nx, ny) and `last_sites` are those of DeviceMapMemWrapper.distance.  Unlike mesh()
+        and raycast() the result is dense: 8 bytes of device memory per record of the box.
+        device=True: a torch int32 tensor of that shape on the GPU that ALIASES the store's buffer, valid until the next distance()
+        on this store."""
+        def bounding_shape():
+            keys = np.asarray(self.keys(), dtype=np.int64).reshape(-1, 3)
+            return tuple(int(v) for v in (keys.max(axis=0) - keys.min(axis=0) + 1) * self.CHUNK_SIZE) if len(keys) else (0, 0, 0)
+        rec, self.last_sites = _distance_call(self._L, "ws_store_distance", self, (), lo, hi, max_dist_vox, unknown_occupied, columns, any_weight,
+                                              device, bounding_shape)
+        return rec
+
+    def distance_timing(self, enable: int = -1):
+        """device milliseconds of pass 0 and of the x, y and z passes of the last distance() (ws_debug_store_distance_timing)"""
+        ms = (C.c_float * 4)()
+        check(self._L.ws_debug_store_distance_timing(self.handle, int(enable), ms), "ws_debug_store_distance_timing")
         return tuple(float(v) for v in ms)
 
     def flush_to(self, global_map: GlobalMap):
@@ -890,35 +943,13 @@ class DeviceMapMemWrapper:
         of site voxels / columns.
         device=True: a torch int32 tensor of that shape on the GPU instead that ALIASES the library's buffer: valid until the next
         distance() on this TSDFCuda, copy it (.clone()) to keep it."""
-        t = self._t
-        if (lo is None) != (hi is None):
-            raise WsError("distance: give both lo and hi, or neither")
-        flags = ((_lib.WS_DISTANCE_ANY_WEIGHT if any_weight else 0) | (_lib.WS_DISTANCE_UNKNOWN_OCCUPIED if unknown_occupied else 0)
-                 | (_lib.WS_DISTANCE_COLUMNS if columns else 0))
-        sites = C.c_size_t(0)
-        check(t._L.ws_map_distance(t.handle, self._which, _ptr(_i3(lo)) if lo is not None else None, _ptr(_i3(hi)) if hi is not None else None,
-                                   int(max_dist_vox), flags, C.byref(sites)), "ws_map_distance")
-        self.last_sites = int(sites.value)
-        if lo is not None:
-            shape = tuple(int(v) for v in (_i3(hi).astype(np.int64) - _i3(lo).astype(np.int64) + 1))
-        else:
+        def window_shape():
             size = np.zeros(3, np.int32)
-            check(t._L.ws_map_get_params(t.handle, self._which, _ptr(size), None, None), "ws_map_get_params")
-            shape = tuple(int(v) for v in size)
-        if columns:
-            shape = shape[:2]
-        n = int(np.prod(shape, dtype=np.int64))
-        cnt = C.c_size_t(0)
-        if device:
-            ptr = t._L.ws_map_distance_dev(t.handle, C.byref(cnt))
-            if int(cnt.value) != n:
-                raise WsError("distance: another call replaced the result")
-            return _device_tensor(ptr, shape, "<i4", t)
-        rec = np.empty(n, dtype=np.uint32)
-        check(t._L.ws_map_distance_download(t.handle, _ptr(rec), n, C.byref(cnt)), "ws_map_distance_download")
-        if int(cnt.value) != n:
-            raise WsError("distance: another call replaced the result before it was downloaded")
-        return rec.reshape(shape)
+            check(self._t._L.ws_map_get_params(self._t.handle, self._which, _ptr(size), None, None), "ws_map_get_params")
+            return tuple(int(v) for v in size)
+        rec, self.last_sites = _distance_call(self._t._L, "ws_map_distance", self._t, (self._which,), lo, hi, max_dist_vox, unknown_occupied, columns,
+                                              any_weight, device, window_shape)
+        return rec
 
     def dev(self):
         return self._t.handle
@@ -1412,6 +1443,23 @@ class TSDFMapping:
             lo, hi = self.local_map_.window()
             self.device_global_map_.save_box(self.tsdf_, lo, hi)
             return self.device_global_map_.mesh(int(self.params_.map.resolution), **kw)
+
+    def global_distance_field(self, lo=None, hi=None, max_dist_m=1.0, unknown_occupied=False, columns=False, any_weight=False, device=False):
+        """The distance field of everything the run has seen: the window goes into the chunks of device_global_map exactly as in
+        global_mesh (ws_store_save_box behind wait_shift, under the mapping's lock like a writer), then DeviceGlobalMap.distance.
+        The box (None: the bounding box of the chunks) need not lie in the window; max_dist_m becomes voxels by the rule of
+        distance_field (nearest millimetre, then ceil(mm / resolution), 1 .. 255).  The result is dense: 8 bytes of device memory
+        per record of the box."""
+        if self.device_global_map_ is None:
+            raise WsError("global_distance_field: this TSDFMapping has no device_global_map")
+        mm = int(np.rint(float(max_dist_m) * 1000.0))
+        res = int(self.params_.map.resolution)
+        self.wait_shift()
+        with self.mutex_:
+            wlo, whi = self.local_map_.window()
+            self.device_global_map_.save_box(self.tsdf_, wlo, whi)
+            return self.device_global_map_.distance(lo=lo, hi=hi, max_dist_vox=-(-mm // res), unknown_occupied=unknown_occupied, columns=columns,
+                                                    any_weight=any_weight, device=device)
 
     @staticmethod
     def raycast_rays(pose, dirs):

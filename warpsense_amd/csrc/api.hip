@@ -893,76 +893,109 @@ int ws_debug_raycast_timing(ws_map *m, int32_t enable, float ms_out[3])
   return query_timing(m->ctx->stream, m->ray.timer, enable, ms_out, RAY_PAIRS, 3);
 }
 
-// ---- distance field: the exact Euclidean transform of a device map, map_distance.hip (the rules are stated in warpsense_hip.h)
-int ws_map_distance(ws_map *m, int which, const int32_t lo[3], const int32_t hi[3], int32_t max_dist_vox, uint32_t flags, size_t *n_sites)
+// ---- distance field: one host core for the window of a map (map_distance.hip) and for the chunks of the store (store_distance.hip;
+// its entry points are further down), in the way of mesh_run and raycast_run above.  The sources differ in pass 0 only.
+extern "C++" {
+// The argument check of a distance call.  `bad`: what the entry point found wrong with its own leading arguments; box(e): its lock and
+// its box, which come behind the checks of the flags and of R -- the extents in 64 bits, all zero for "nothing to do".  ext and *n
+// receive the extents the passes take and the number of records.
+template <typename Box>
+static int distance_check(const char *name, bool bad, const int32_t *lo, const int32_t *hi, int32_t R, uint32_t flags, Box box, uint32_t ext[3], size_t *n)
 {
   const uint32_t known = WS_DISTANCE_ANY_WEIGHT | WS_DISTANCE_UNKNOWN_OCCUPIED | WS_DISTANCE_COLUMNS;
-  if (!m || (which != WS_MAP_AVG && which != WS_MAP_NEW) || (flags & ~known) || ((lo == nullptr) != (hi == nullptr)))
-    return invalid("ws_map_distance: bad argument");
-  if (max_dist_vox < 1 || max_dist_vox > 255)
-  {
-    set_error("ws_map_distance: max_dist_vox must be 1 .. 255 (its square is carried in 16 bits)");
-    return WS_ERR_RANGE;
-  }
-  WS_SETTLE(m);
-  std::lock_guard<std::mutex> lock(m->dist.mu);
-  ws_map::Distance &q = m->dist;
-  int rc = q.timer.arm();
-  int32_t l[3], ext[3];
-  if (rc == WS_OK) rc = resolve_box(m, which, lo, hi, true, "ws_map_distance", l, ext);
-  if (rc != WS_OK) return rc;
+  if (bad || (flags & ~known) || ((lo == nullptr) != (hi == nullptr))) return invalid(std::string(name) + ": bad argument");
+  if (R < 1 || R > 255) return range_error(name, ": max_dist_vox must be 1 .. 255 (its square is carried in 16 bits)");
+  uint64_t e[3] = {0, 0, 0};
+  WS_TRY(box(e));
   const bool columns = (flags & WS_DISTANCE_COLUMNS) != 0;
-  const uint64_t n64 = (uint64_t)ext[0] * (uint64_t)ext[1] * (uint64_t)(columns ? 1 : ext[2]); // ext[0] ext[1] < 2^31, ext[2] <= 2^20
-  if (n64 > 0xffffffffull)
-  {
-    set_error("ws_map_distance: more than 2^32 - 1 records");
-    return WS_ERR_RANGE;
-  }
-  const size_t n = (size_t)n64;
+  // (every extent is at most 2^32; one of 2^32 is too many records by itself, and the products of the others fit 64 bits)
+  const uint64_t n_cols = e[0] > 0xffffffffull || e[1] > 0xffffffffull ? ~0ull : e[0] * e[1];
+  if (n_cols > 0xffffffffull || (!columns && n_cols * e[2] > 0xffffffffull)) return range_error(name, ": more than 2^32 - 1 records");
+  if ((columns ? e[1] : e[2]) > (uint64_t)DIST_MAX_LINE) return range_error(name, ": more than 16 776 960 voxels along the fastest axis of the records");
+  for (int k = 0; k < 3; ++k) ext[k] = (uint32_t)std::min<uint64_t>(e[k], 0xffffffffull); // (under COLUMNS the passes do not read ext[2])
+  *n = (size_t)(columns ? n_cols : n_cols * e[2]);
+  return WS_OK;
+}
+
+// The flow of a distance call whose arguments have passed distance_check, from "the old result is dropped" to the publish.  pass0()
+// enqueues the source's classification into q.rec and the first plane of q.plane and returns at once.
+template <typename Pass0>
+static int distance_run(DistResult &q, hipStream_t s, const uint32_t ext[3], int32_t R, uint32_t flags, size_t n, size_t *n_sites, Pass0 pass0)
+{
   if (n_sites) *n_sites = 0;
-  q.n = 0;
-  hipStream_t s = m->ctx->stream;
-  rc = q.sites.alloc(1);
-  if (rc != WS_OK) return rc;
+  q.n = 0; // (whatever happens from here on, the old result is gone: its buffers may be replaced)
+  if (n == 0) return WS_OK;
+  WS_TRY(q.sites.alloc(1));
   if (n > q.rec.cap || n > q.plane.cap)
   {
     WS_HIP(hipStreamSynchronize(s));
-    rc = q.rec.grow(n, sizeof(uint32_t));
-    if (rc == WS_OK) rc = q.plane.grow(n, 2 * sizeof(uint16_t)); // both planes
-    if (rc != WS_OK) return rc;
+    WS_TRY(q.rec.grow(n, sizeof(uint32_t)));
+    WS_TRY(q.plane.grow(n, 2 * sizeof(uint16_t))); // both planes
   }
-  rc = launch_distance(m, which, l, ext, max_dist_vox, flags, n);
-  if (rc != WS_OK) return rc;
+  WS_TRY(pass0());
+  WS_TRY(dist_passes(s, q.timer, q.rec.as<uint32_t>(), q.plane.as<uint16_t>(), ext, R, flags));
+  WS_TRY(q.sites.fetch(s));
   WS_HIP(hipStreamSynchronize(s));
   q.n = n;
   if (n_sites) *n_sites = (size_t)*q.sites.host;
+  return WS_OK;
+}
+
+static const uint32_t *distance_dev(const DistResult *q, size_t *n)
+{
+  if (n) *n = q ? q->n : 0;
+  return q && q->n ? static_cast<const uint32_t *>(q->rec.p) : nullptr;
+}
+
+static int distance_download(const DistResult &q, hipStream_t s, uint32_t *host, size_t capacity, size_t *n_out)
+{
+  *n_out = q.n;
+  const size_t k = host ? std::min(capacity, q.n) : 0;
+  if (k == 0) return WS_OK;
+  WS_HIP(hipMemcpyAsync(host, q.rec.p, k * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  WS_HIP(hipStreamSynchronize(s));
+  return WS_OK;
+}
+static const int DIST_PAIRS[4][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 4}};
+} // extern "C++"
+
+// ---- distance field: the exact Euclidean transform of a device map, map_distance.hip (the rules are stated in warpsense_hip.h)
+int ws_map_distance(ws_map *m, int which, const int32_t lo[3], const int32_t hi[3], int32_t max_dist_vox, uint32_t flags, size_t *n_sites)
+{
+  std::unique_lock<std::mutex> lock;
+  int32_t l[3], ext[3];
+  uint32_t e32[3];
+  size_t n = 0;
+  WS_TRY(distance_check(
+      "ws_map_distance", !m || (which != WS_MAP_AVG && which != WS_MAP_NEW), lo, hi, max_dist_vox, flags,
+      [&](uint64_t e[3]) {
+        WS_SETTLE(m);
+        lock = std::unique_lock<std::mutex>(m->dist.mu);
+        WS_TRY(m->dist.timer.arm());
+        WS_TRY(resolve_box(m, which, lo, hi, true, "ws_map_distance", l, ext)); // ext[0] ext[1] < 2^31, ext[2] <= 2^20
+        for (int k = 0; k < 3; ++k) e[k] = (uint64_t)ext[k];
+        return (int)WS_OK;
+      },
+      e32, &n));
+  DistResult &q = m->dist;
+  WS_TRY(distance_run(q, m->ctx->stream, e32, max_dist_vox, flags, n, n_sites, [&] { return launch_dist_classify(m, q, which, l, ext, max_dist_vox, flags); }));
   return map_take_error(m);
 }
 
-const uint32_t *ws_map_distance_dev(const ws_map *m, size_t *n)
-{
-  if (n) *n = m ? m->dist.n : 0;
-  return m && m->dist.n ? static_cast<const uint32_t *>(m->dist.rec.p) : nullptr;
-}
+const uint32_t *ws_map_distance_dev(const ws_map *m, size_t *n) { return distance_dev(m ? &m->dist : nullptr, n); }
 
 int ws_map_distance_download(ws_map *m, uint32_t *host, size_t capacity, size_t *n_out)
 {
   if (!m || !n_out) return invalid("ws_map_distance_download: NULL argument");
   std::lock_guard<std::mutex> lock(m->dist.mu);
-  *n_out = m->dist.n;
-  const size_t k = host ? std::min(capacity, m->dist.n) : 0;
-  if (k == 0) return WS_OK;
-  WS_HIP(hipMemcpyAsync(host, m->dist.rec.p, k * sizeof(uint32_t), hipMemcpyDeviceToHost, m->ctx->stream));
-  WS_HIP(hipStreamSynchronize(m->ctx->stream));
-  return WS_OK;
+  return distance_download(m->dist, m->ctx->stream, host, capacity, n_out);
 }
 
 int ws_debug_distance_timing(ws_map *m, int32_t enable, float ms_out[4])
 {
   if (!m) return invalid("ws_debug_distance_timing: map is NULL");
   std::lock_guard<std::mutex> lock(m->dist.mu);
-  static const int pairs[4][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 4}};
-  return query_timing(m->ctx->stream, m->dist.timer, enable, ms_out, pairs, 4);
+  return query_timing(m->ctx->stream, m->dist.timer, enable, ms_out, DIST_PAIRS, 4);
 }
 
 // ---- map shift
@@ -1583,8 +1616,8 @@ int ws_debug_store_timing(ws_store *st, int32_t enable, float ms_out[2])
   return WS_OK;
 }
 
-// ---- the mesh and the ray cast of the store: the rules and the host flow of ws_map_mesh and ws_map_raycast over the chunks,
-// store_mesh.hip and store_raycast.hip (the semantics are stated in warpsense_hip.h)
+// ---- the mesh, the ray cast and the distance field of the store: the rules and the host flow of ws_map_mesh, ws_map_raycast and
+// ws_map_distance over the chunks, store_mesh.hip, store_raycast.hip and store_distance.hip (the semantics are stated in warpsense_hip.h)
 namespace
 {
 // The written chunks the box overlaps, ascending (cx, cy, cz) like the directory: visit(key, slot).  The directory is ordered by cx
@@ -1791,6 +1824,79 @@ int ws_debug_store_raycast_timing(ws_store *st, int32_t enable, float ms_out[3])
   if (!st) return invalid("ws_debug_store_raycast_timing: store is NULL");
   std::lock_guard<std::mutex> lock(st->mu);
   return query_timing(st->ctx->stream, st->ray.timer, enable, ms_out, RAY_PAIRS, 3);
+}
+
+// ---- the distance field of the store: the rules and the host flow of ws_map_distance over the chunks, store_distance.hip
+int ws_store_distance(ws_store *st, const int32_t lo[3], const int32_t hi[3], int32_t max_dist_vox, uint32_t flags, size_t *n_sites)
+{
+  std::unique_lock<std::mutex> lock;
+  StoreDistCall c;
+  uint32_t ext[3];
+  size_t n = 0;
+  WS_TRY(distance_check(
+      "ws_store_distance", !st, lo, hi, max_dist_vox, flags,
+      [&](uint64_t e[3]) {
+        if (lo)
+          for (int k = 0; k < 3; ++k)
+            if (hi[k] < lo[k]) return invalid("ws_store_distance: hi < lo");
+        lock = std::unique_lock<std::mutex>(st->mu);
+        WS_TRY(st->dist.timer.arm());
+        if (lo)
+          copy3(c.lo, lo), copy3(c.hi, hi);
+        else
+        {
+          if (st->dir.empty()) return (int)WS_OK; // nothing to do: zero records
+          // the bounding box of the present chunks (keys are floor(int32 / 64): 64 k + 63 fits)
+          for (int k = 0; k < 3; ++k) c.lo[k] = INT32_MAX, c.hi[k] = INT32_MIN;
+          for (const auto &kv : st->dir)
+            for (int k = 0; k < 3; ++k) c.lo[k] = std::min(c.lo[k], kv.first[k] * STORE_CS), c.hi[k] = std::max(c.hi[k], kv.first[k] * STORE_CS + STORE_CS - 1);
+        }
+        for (int k = 0; k < 3; ++k) e[k] = (uint64_t)((int64_t)c.hi[k] - (int64_t)c.lo[k]) + 1u;
+        return (int)WS_OK;
+      },
+      ext, &n));
+  ws_store::Dist &q = st->dist;
+  hipStream_t s = st->ctx->stream;
+  // the present chunks the box overlaps, and the z range they cover inside it
+  std::vector<StoreRaySlot> listed;
+  if (n) store_walk_box(st, c.lo, c.hi, [&](const StoreKey &key, uint32_t slot) { listed.push_back(StoreRaySlot{key[0], key[1], key[2], slot}); });
+  if (listed.size() >= (1u << 19)) return range_error("ws_store_distance", ": the box overlaps 2^19 present chunks or more");
+  c.n_chunks = (uint32_t)listed.size();
+  c.nx = ext[0], c.ny = ext[1];
+  c.zlo = 1, c.zhi = 0;
+  if (c.n_chunks)
+  {
+    c.zlo = INT32_MAX, c.zhi = INT32_MIN;
+    for (const StoreRaySlot &e : listed) c.zlo = std::min(c.zlo, e.cz * STORE_CS), c.zhi = std::max(c.zhi, e.cz * STORE_CS + STORE_CS - 1);
+    c.zlo = std::max(c.zlo, c.lo[2]), c.zhi = std::min(c.zhi, c.hi[2]);
+  }
+  return store_enqueued(st, distance_run(q, s, ext, max_dist_vox, flags, n, n_sites, [&] {
+    const size_t places = c.n_chunks ? store_ray_table_slots(c.n_chunks) : 0;
+    if (places > q.table_host.cap)
+    {
+      WS_HIP(hipStreamSynchronize(s));
+      WS_TRY(q.table_host.alloc(places, sizeof(StoreRaySlot), HostBlock::PINNED));
+      WS_TRY(q.table_dev.alloc(places, sizeof(StoreRaySlot)));
+    }
+    if (c.n_chunks) store_ray_table_fill(listed.data(), listed.size(), q.table_host.as<StoreRaySlot>());
+    return launch_store_dist_classify(st, q, c, max_dist_vox, flags);
+  }));
+}
+
+const uint32_t *ws_store_distance_dev(const ws_store *st, size_t *n) { return distance_dev(st ? &st->dist : nullptr, n); }
+
+int ws_store_distance_download(ws_store *st, uint32_t *host, size_t capacity, size_t *n_out)
+{
+  if (!st || !n_out) return invalid("ws_store_distance_download: NULL argument");
+  std::lock_guard<std::mutex> lock(st->mu);
+  return distance_download(st->dist, st->ctx->stream, host, capacity, n_out);
+}
+
+int ws_debug_store_distance_timing(ws_store *st, int32_t enable, float ms_out[4])
+{
+  if (!st) return invalid("ws_debug_store_distance_timing: store is NULL");
+  std::lock_guard<std::mutex> lock(st->mu);
+  return query_timing(st->ctx->stream, st->dist.timer, enable, ms_out, DIST_PAIRS, 4);
 }
 
 int ws_debug_store_raycast_table(const int32_t *keys_slots, size_t n, int32_t *table, size_t capacity_places, size_t *n_places)

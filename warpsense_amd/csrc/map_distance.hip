@@ -35,14 +35,6 @@ struct DistArgs
   unsigned long long *sites;
 };
 
-// 2 occupied, 1 free, 0 unknown
-__device__ __forceinline__ uint32_t dist_class(uint32_t raw, bool any_weight)
-{
-  const int32_t w = entry_weight(raw);
-  const bool valid = any_weight ? w != 0 : w > 0;
-  return valid ? (entry_value(raw) < 0 ? 2u : 1u) : 0u;
-}
-
 template <bool COLUMNS>
 __global__ __launch_bounds__(256) void dist_classify_kernel(DistArgs a)
 {
@@ -186,53 +178,70 @@ static void dist_line(hipStream_t s, const uint16_t *in, uint16_t *out, uint32_t
     }
 }
 
-// Pass 0 (events 0, 1), the x, y and z passes (events 1 .. 4); under WS_DISTANCE_COLUMNS pass 0, the x and the y pass (events 3, 4
-// coincide).  m->dist.plane holds two planes of `n` uint16.  The site count arrives in m->dist.sites.host (pinned) once the stream
-// has been synchronised.
-int launch_distance(ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], int32_t R, uint32_t flags, size_t n)
+// Pass 0 over the ring (events 0, 1): the site counter is cleared in front of it.
+int launch_dist_classify(ws_map *m, DistResult &q, int which, const int32_t lo[3], const int32_t ext[3], int32_t R, uint32_t flags)
 {
   DistArgs a;
   a.box = box_args(m, which, lo, ext);
   a.r2 = (uint32_t)(R * R);
   a.flags = flags;
-  a.rec = static_cast<uint32_t *>(m->dist.rec.p);
-  uint16_t *p0 = static_cast<uint16_t *>(m->dist.plane.p), *p1 = p0 + n;
-  a.plane = p0;
-  a.sites = m->dist.sites.dev;
+  a.rec = q.rec.as<uint32_t>();
+  a.plane = q.plane.as<uint16_t>();
+  a.sites = q.sites.dev;
   hipStream_t s = m->ctx->stream;
-  const uint32_t nx = (uint32_t)ext[0], ny = (uint32_t)ext[1], nz = (uint32_t)ext[2];
   WS_HIP(hipMemsetAsync(a.sites, 0, sizeof(unsigned long long), s));
-  QueryTimer &t = m->dist.timer;
-  t.mark(0, s);
+  q.timer.mark(0, s);
+  if (flags & WS_DISTANCE_COLUMNS)
+    hipLaunchKernelGGL((dist_classify_kernel<true>), dim3((a.box.n_cols + 3u) / 4u), dim3(256), 0, s, a);
+  else
+    hipLaunchKernelGGL((dist_classify_kernel<false>), dim3((a.box.n_cols + 3u) / 4u), dim3(256), 0, s, a);
+  q.timer.mark(1, s);
+  return WS_OK;
+}
+
+// the row pass over `lines` lines; a launch holds at most 2^23 of them (its threads are counted in 32 bits), the next one goes on
+// behind them
+static void dist_rows(hipStream_t s, const uint16_t *in, uint32_t *rec, uint32_t lines, uint32_t len, int32_t R)
+{
   DistRowArgs r;
-  r.rec = a.rec;
+  r.len = len;
   r.R = R;
+  for (uint32_t l0 = 0; l0 < lines; l0 += 1u << 23)
+  {
+    r.in = in + (uint64_t)l0 * len;
+    r.rec = rec + (uint64_t)l0 * len;
+    hipLaunchKernelGGL(dist_row_kernel, dim3(std::min(lines - l0, 1u << 23), (len + DIST_ROW - 1) / DIST_ROW), dim3(DIST_ROW), 0, s, r);
+  }
+}
+
+// The x, y and z passes (events 1 .. 4) behind a pass 0 that has written the class bits into `rec` and g0 into the first of the two
+// planes of `plane`; under WS_DISTANCE_COLUMNS the x and the y pass (events 3, 4 coincide).  Both sources of a distance field come
+// here: the window of a map (launch_dist_classify) and the chunks of the store (store_distance.hip).
+int dist_passes(hipStream_t s, QueryTimer &t, uint32_t *rec, uint16_t *plane, const uint32_t ext[3], int32_t R, uint32_t flags)
+{
+  static_assert(DIST_MAX_LINE == 65535u * (uint32_t)DIST_ROW, "a line of the row pass: 65 535 workgroups of DIST_ROW outputs");
+  const uint32_t nx = ext[0], ny = ext[1];
   if (flags & WS_DISTANCE_COLUMNS)
   {
-    hipLaunchKernelGGL((dist_classify_kernel<true>), dim3((a.box.n_cols + 3u) / 4u), dim3(256), 0, s, a);
-    t.mark(1, s);
+    uint16_t *p0 = plane, *p1 = p0 + (uint64_t)nx * ny;
     dist_line(s, p0, p1, 1u, nx, ny, R);
     t.mark(2, s);
-    r.in = p1;
-    r.len = ny;
-    hipLaunchKernelGGL(dist_row_kernel, dim3(nx, (ny + DIST_ROW - 1) / DIST_ROW), dim3(DIST_ROW), 0, s, r);
+    dist_rows(s, p1, rec, nx, ny, R);
     t.mark(3, s);
   }
   else
   {
-    hipLaunchKernelGGL((dist_classify_kernel<false>), dim3((a.box.n_cols + 3u) / 4u), dim3(256), 0, s, a);
-    t.mark(1, s);
+    const uint32_t nz = ext[2];
+    uint16_t *p0 = plane, *p1 = p0 + (uint64_t)nx * ny * nz;
     dist_line(s, p0, p1, 1u, nx, ny * nz, R); // ny nz < 2^32: the records are counted in 32 bits
     t.mark(2, s);
     dist_line(s, p1, p0, nx, ny, nz, R);
     t.mark(3, s);
-    r.in = p0;
-    r.len = nz;
-    hipLaunchKernelGGL(dist_row_kernel, dim3(a.box.n_cols, (nz + DIST_ROW - 1) / DIST_ROW), dim3(DIST_ROW), 0, s, r);
+    dist_rows(s, p0, rec, nx * ny, nz, R);
   }
   t.mark(4, s);
   WS_HIP(hipGetLastError());
-  return m->dist.sites.fetch(s);
+  return WS_OK;
 }
 
 } // namespace ws

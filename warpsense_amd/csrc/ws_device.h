@@ -166,6 +166,14 @@ __device__ __forceinline__ int64_t box_column(const BoxArgs &b, uint32_t col, in
   return (int64_t)(xi * b.mp.size[1] + yi) * (int64_t)b.mp.size[2]; // size[0] * size[1] < 2^31 (ws_map_create)
 }
 
+// the class of a voxel in a distance field (ws_map_distance): 2 occupied, 1 free, 0 unknown
+__device__ __forceinline__ uint32_t dist_class(uint32_t raw, bool any_weight)
+{
+  const int32_t w = entry_weight(raw);
+  const bool valid = any_weight ? w != 0 : w > 0;
+  return valid ? (entry_value(raw) < 0 ? 2u : 1u) : 0u;
+}
+
 // Exclusive scan of n workgroup totals by ONE workgroup of 1024 threads, every thread a contiguous piece (16 K words for the columns
 // of a 513^3 window, 256 K for 2049^3); *total is the sum
 __device__ __forceinline__ void scan_block_totals(const uint32_t *tot, unsigned long long *off, uint32_t n, unsigned long long *total)

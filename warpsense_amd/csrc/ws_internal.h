@@ -387,6 +387,16 @@ struct RayResult
   bool has_grad = false;               // the last call also wrote `grad`
   void release() { timer.release(), hits.release(); for (DevBuf *b : {&dirs, &rec, &grad}) b->release(); }
 };
+// ... and a distance call (ws_map::Distance, ws_store::Dist; the one flow is distance_run in api.hip)
+struct DistResult
+{
+  QueryTimer timer;                    // 0 pass 0, 1 x 2 y 3 z 4
+  DevBuf rec;                          // uint32: one record per voxel (per column under WS_DISTANCE_COLUMNS)
+  DevBuf plane;                        // 2 x uint16 per record: ping-pong planes of the running minimum
+  DevCounter sites;                    // site voxels / site columns of the last call
+  size_t n = 0;                        // records of the last call
+  void release() { timer.release(), sites.release(); for (DevBuf *b : {&rec, &plane}) b->release(); }
+};
 
 } // namespace ws
 
@@ -476,15 +486,9 @@ struct ws_map
   {
     std::mutex mu;
   } ray;
-  struct Distance // ws_map_distance (map_distance.hip)
+  struct Distance : ws::DistResult // ws_map_distance (map_distance.hip)
   {
     std::mutex mu;
-    ws::QueryTimer timer;                // 0 pass 0, 1 x 2 y 3 z 4
-    ws::DevBuf rec;                      // uint32: one record per voxel (per column under WS_DISTANCE_COLUMNS)
-    ws::DevBuf plane;                    // 2 x uint16 per record: ping-pong planes of the running minimum
-    ws::DevCounter sites;                // site voxels / site columns of the last call
-    size_t n = 0;                        // records of the last call
-    void release() { timer.release(), sites.release(); for (ws::DevBuf *b : {&rec, &plane}) b->release(); }
   } dist;
   // The scan whose verdict (did its records fit the pool?) has not been looked at yet: ws_tsdf_update* return after the
   // launches, like the reference's update_tsdf (update_tsdf.cu:165); the next call that takes this map settles it first
@@ -630,8 +634,8 @@ struct ws_store
   } tab[ws::STORE_TABLES];
   int tab_next = 0;
   ws::QueryTimer timer[3]; // per axis of a shift: 0 save 1 load 2 (ws_store_save_box / _load_box use the first)
-  // ws_store_mesh (store_mesh.hip) and ws_store_raycast (store_raycast.hip): the results of the last calls, apart from each other, and
-  // the chunk table of the call in flight; the store's mutex serialises the calls
+  // ws_store_mesh (store_mesh.hip), ws_store_raycast (store_raycast.hip) and ws_store_distance (store_distance.hip): the results of the
+  // last calls, apart from each other, and the chunk table of the call in flight; the store's mutex serialises the calls
   struct Mesh : ws::MeshResult
   {
     ws::HostBlock table_host;            // bytes, pinned: the call's chunk tables (store_mesh_table_bytes); free again when the call returns, which synchronises
@@ -644,10 +648,17 @@ struct ws_store
     ws::DevBuf table_dev;                // ... and the copy the kernels read
     void release() { RayResult::release(), table_host.release(), table_dev.release(); }
   } ray;
+  struct Dist : ws::DistResult
+  {
+    ws::HostBlock table_host;            // StoreRaySlot, pinned: the call's chunk lookup; free again when the call returns, which synchronises
+    ws::DevBuf table_dev;                // ... and the copy the kernel reads
+    void release() { DistResult::release(), table_host.release(), table_dev.release(); }
+  } dist;
   void release()
   {
     mesh.release();
     ray.release();
+    dist.release();
     for (ws::DevBuf &b : segs) b.release();
     segs.clear(), seg_ptr.clear();
     seg_tab.release();
@@ -714,8 +725,12 @@ int launch_mesh_count(ws_map *m, MeshResult &q, int which, const int32_t lo[3], 
 int launch_mesh_emit(ws_map *m, MeshResult &q, int which, const int32_t lo[3], const int32_t ext[3], uint32_t flags);
 // map_raycast.hip: the march and, with WS_RAYCAST_GRADIENT, the gradient pass (the hit count arrives in q.hits.host after a stream synchronise)
 int launch_raycast(ws_map *m, RayResult &q, int which, const int32_t origin[3], const int32_t *dirs_dev, size_t n, int32_t max_range, uint32_t flags);
-// map_distance.hip: pass 0 and the line passes over `n` records (the site count arrives in ws_map::dist.sites.host after a stream synchronise)
-int launch_distance(ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], int32_t R, uint32_t flags, size_t n);
+// map_distance.hip: pass 0 over the ring (it clears q.sites.dev and marks events 0, 1), and the line passes over the records of a box
+// of extent `ext` that a pass 0 has prepared (events 1 .. 4; `plane`: two planes of one uint16 per record, the first one written by
+// pass 0; under WS_DISTANCE_COLUMNS ext[2] is not read).  A line of the fastest axis holds at most DIST_MAX_LINE voxels.
+constexpr uint32_t DIST_MAX_LINE = 65535u * 256u;
+int launch_dist_classify(ws_map *m, DistResult &q, int which, const int32_t lo[3], const int32_t ext[3], int32_t R, uint32_t flags);
+int dist_passes(hipStream_t s, QueryTimer &t, uint32_t *rec, uint16_t *plane, const uint32_t ext[3], int32_t R, uint32_t flags);
 int fill_u32(ws_context *ctx, uint32_t *dst, uint32_t value, int64_t n);
 int launch_box_fill(ws_map *m, const ws::MapParams &par, int which, const int32_t lo[3], const int32_t ext[3], uint32_t value, hipStream_t stream);
 int check_all_equal_host(const uint32_t *data, int64_t n, uint32_t value);
@@ -787,6 +802,17 @@ struct StoreRayCall
   int32_t blo[3], bhi[3]; // the bounding box of the listed chunks, cut to the box
 };
 int launch_store_raycast(ws_store *st, ws_store::Ray &q, const StoreRayCall &c, const int32_t origin[3], const int32_t *dirs_dev, size_t n, int32_t max_range, uint32_t flags);
+
+// store_distance.hip: pass 0 of the distance field over the chunks the call lists (it clears q.sites.dev and marks events 0, 1).  The
+// host has written the lookup of store_raycast.hip (store_ray_table_fill) for `n_chunks` listed chunks into q.table_host
+struct StoreDistCall
+{
+  uint32_t n_chunks;    // listed chunks (< 2^19); 0: every voxel is unknown
+  int32_t lo[3], hi[3]; // the box, inclusive world voxels
+  int32_t zlo, zhi;     // the z range of the listed chunks, cut to the box (zlo > zhi without a listed chunk)
+  uint32_t nx, ny;      // columns of the box (nx ny < 2^32)
+};
+int launch_store_dist_classify(ws_store *st, ws_store::Dist &q, const StoreDistCall &c, int32_t R, uint32_t flags);
 
 int launch_reg_iteration(ws_reg *r, const ws_map *m, int32_t res, uint32_t flags, int32_t k);
 // reg_pass_kernel over points [first, first + count): from the newest state (first the update from `sums` if `apply`) into `sums`;
