@@ -122,7 +122,11 @@ int ws_map_download(ws_map *map, int which, int32_t size[3], int32_t pos[3], int
  * pos - size/2 .. pos + size/2.  An even size (which this ABI admits, the reference's maps never have one) has no centre voxel:
  * its window ends at pos + size/2 - 1, and world voxel pos + size/2 is the ring cell of pos - size/2 again.  A box passes if
  * every corner is within size/2 of pos AND it has no more voxels along any axis than the ring has cells (otherwise
- * WS_ERR_INVALID, nothing is moved): no box addresses a ring cell twice.  ws_map_surface, _mesh, _distance use the same rule. */
+ * WS_ERR_INVALID, nothing is moved): no box addresses a ring cell twice.  ws_map_surface, _mesh, _distance use the same rule.
+ * Where a window may be: pos - size/2 .. pos - size/2 + size - 1 must lie in int32 on every axis (the last voxel may be INT32_MAX,
+ * the first INT32_MIN).  A map whose window does not (ws_map_create, ws_map_set_params and ws_map_upload do not ask) is refused
+ * here, by the three queries and by ws_store_save_box / ws_store_load_box with WS_ERR_RANGE before anything is allocated or
+ * launched; the inside-the-window test itself is made in 64 bits. */
 int ws_map_extract_box(ws_map *map, int which, const int32_t lo[3], const int32_t hi[3], uint32_t *host_out);
 int ws_map_insert_box(ws_map *map, int which, const int32_t lo[3], const int32_t hi[3], const uint32_t *host_in);
 /* The geometry of a map shift, for every route (the box calls above, ws_shift_begin, ws_shift_device).  Host only: no map, no
@@ -131,7 +135,12 @@ int ws_map_insert_box(ws_map *map, int which, const int32_t lo[3], const int32_t
  * holds -- and the box that enters.  The window is the one above (pos - size/2 .. pos - size/2 + size - 1, also for an even
  * size), so no slab is wider than `size` along an axis.  pos / offset: the window's parameters after the last step.
  * A step of up to `size` voxels per axis is accepted, a larger one refused (WS_ERR_INVALID, as is a NULL argument);
- * new_pos == pos gives n = 0. */
+ * new_pos == pos gives n = 0.
+ * Every window of the plan -- the one at `pos`, the one behind each axis step, the one at new_pos -- must lie in int32 on every
+ * axis (the rule stated at ws_map_extract_box), else WS_ERR_RANGE.  Per axis in the order x, y, z the size of the step is tested
+ * first and the window behind it second, so a step that is both too large and out of range is WS_ERR_INVALID.  ws_shift_begin and
+ * ws_shift_device refuse the same way, in their own name, before anything is allocated or launched: both maps, the store and its
+ * directory stay as they were. */
 typedef struct
 {
   int32_t n;                                /* steps: 0 .. 3 */
@@ -150,7 +159,8 @@ int ws_shift_plan(const int32_t size[3], const int32_t pos[3], const int32_t off
  *   - overwrites, with ws_map_insert_box, those parts of the entering slabs the global map already holds (revisits),
  *   - and, typically on a worker thread: ws_shift_wait (blocks on the second stream only), ws_shift_slab for each
  *     leaving slab -> global map, ws_shift_end.
- * The slabs and the refusal of a step larger than the window are ws_shift_plan's.
+ * The slabs and the refusals of a step larger than the window (WS_ERR_INVALID) and of a window outside int32 (WS_ERR_RANGE) are
+ * ws_shift_plan's.
  * new_pos equal to pos gives a ticket without slabs that is ended like any other.
  * One shift can be in flight per map: ws_shift_begin and ws_shift_reserve fail with WS_ERR_INVALID while a ticket is open, and
  * ws_shift_begin while new_map holds entries that have not been integrated.  A refusal leaves both maps as they were. */
@@ -336,7 +346,7 @@ int ws_debug_distance_timing(ws_map *map, int32_t enable, float ms_out[4]);
  *   pool: grows in segments of `segment_chunks` chunks (0: 256; rounded up to a power of two).  Growing never copies or moves a chunk,
  *     so ws_store_chunk_dev pointers stay valid until the chunk is dropped.  max_chunks: 0 = no limit but the device's memory.
  *   boxes: inclusive world voxels of the window of `map` under the rule of ws_map_extract_box (even sizes included; otherwise
- *     WS_ERR_INVALID and nothing moves).
+ *     WS_ERR_INVALID and nothing moves; a window that does not lie in int32: WS_ERR_RANGE, likewise).
  *   ws_store_save_box: LocalMap._area(save) on the device.  Every chunk the box overlaps exists afterwards (HDF5GlobalMap's
  *     activate_chunk); a chunk this call creates holds fill_entry wherever the box does not cover it; an existing chunk keeps its
  *     voxels outside the box.
@@ -345,7 +355,8 @@ int ws_debug_distance_timing(ws_map *map, int32_t enable, float ms_out[4]);
  *   ws_shift_device: HDF5LocalMap::shift (hdf5_local_map.cpp:53-118) wholly on the device -- per axis x, y, z the leaving slab is
  *     saved, pos / offset of BOTH maps move, the entering slab is loaded.  The slabs are those of ws_shift_plan.  A pending scan is
  *     settled first.  WS_ERR_INVALID, nothing changed: a ws_shift_begin ticket is open, new_map holds entries that have not been
- *     integrated, a step larger than the window, a store of another context.  new_pos == pos: WS_OK, nothing happens.  The
+ *     integrated, a step larger than the window, a store of another context.  WS_ERR_RANGE, nothing changed: a window of the plan
+ *     does not lie in int32 (ws_shift_plan).  new_pos == pos: WS_OK, nothing happens.  The
  *     parameters of both maps are committed only after every launch is enqueued.
  *   planning before launching: the new chunks of ALL axes of a call are counted before its first launch.  If they do not fit under
  *     max_chunks: WS_ERR_CAPACITY; if a segment cannot be allocated: WS_ERR_HIP; both maps and the store stay as they were.  Only

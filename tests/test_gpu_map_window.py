@@ -77,10 +77,13 @@ def check_device(t, w, new_default=True):
 class MappingRoute:
     """TSDFMapping.shift_map / shift_map_async with an in-memory GlobalMap"""
 
-    def __init__(self, size, asyn, reserve=None):
+    def __init__(self, size, asyn, reserve=None, base=None):
         import warpsense_amd as W
         self.lm = W.LocalMap(*size, TAU, 0)
         assert tuple(self.lm.size) == tuple(size)
+        if base is not None:  # the window starts there: through the parameters, before the device map exists
+            self.lm.pos[:] = base
+            self.lm.offset[:] = M.model_offset(size, base)
         self.tm = W.TSDFMapping(_params(size), self.lm)
         self.t = self.tm.tsdf()
         self.asyn = asyn

@@ -20,10 +20,13 @@ CW = 64 ** 3
 class StoreRoute:
     """TSDFMapping.shift_map_device with a DeviceGlobalMap"""
 
-    def __init__(self, size, segment_chunks=0, max_chunks=0):
+    def __init__(self, size, segment_chunks=0, max_chunks=0, base=None):
         import warpsense_amd as W
         self.lm = W.LocalMap(*size, TAU, 0)
         assert tuple(self.lm.size) == tuple(size)
+        if base is not None:  # the window starts there: through the parameters, before the device map exists
+            self.lm.pos[:] = base
+            self.lm.offset[:] = M.model_offset(size, base)
         self.store = W.DeviceGlobalMap(TAU, 0, max_chunks=max_chunks, segment_chunks=segment_chunks)
         self.tm = W.TSDFMapping(_params(size), self.lm, device_global_map=self.store)
         self.t = self.tm.tsdf()

@@ -32,7 +32,7 @@ def box_inter(alo, ahi, blo, bhi):
 
 
 class World:
-    def __init__(self, size, bb_lo, bb_hi, default_raw):
+    def __init__(self, size, bb_lo, bb_hi, default_raw, pos=(0, 0, 0)):
         self.size = np.asarray(size, dtype=np.int64)
         self.bb_lo, self.bb_hi = np.asarray(bb_lo, dtype=np.int64), np.asarray(bb_hi, dtype=np.int64)
         shape = tuple(int(v) for v in self.bb_hi - self.bb_lo + 1)
@@ -40,7 +40,7 @@ class World:
         self.world = np.full(shape, self.default_raw, dtype=np.uint32)
         self.store = np.full(shape, self.default_raw, dtype=np.uint32)
         self.written = np.zeros(shape, dtype=bool)  # voxels a test has written (for the revisit count of the walks)
-        self.pos = np.zeros(3, dtype=np.int64)
+        self.pos = np.asarray(pos, dtype=np.int64).copy()
 
     def sl(self, lo, hi):
         lo, hi = np.asarray(lo, dtype=np.int64), np.asarray(hi, dtype=np.int64)
@@ -126,8 +126,8 @@ def step_sizes(n):
     return sorted({d for d in (1, n // 2, n // 2 + 1, n - 1, n) if 1 <= d <= n})
 
 
-def make_walk(size, seed, diagonals=4):
-    """positions of a walk from the origin and back.  Per axis and per required |d| a step out and the step back (the way back is
+def make_walk(size, seed, diagonals=4, base=(0, 0, 0)):
+    """positions of a walk from `base` and back: the walk from the origin and back, moved by `base`.  Per axis and per required |d| a step out and the step back (the way back is
     a revisit), mixed with three-axis diagonal steps that pull towards the origin, in an order drawn from `seed`; every step has
     |d| <= size per axis (what ws_shift_begin and LocalMap.shift admit)."""
     size = np.asarray(size, dtype=np.int64)
@@ -156,13 +156,14 @@ def make_walk(size, seed, diagonals=4):
     while np.any(pos != 0):  # home, in steps the window admits
         pos = pos - np.clip(pos, -size, size)
         walk.append(pos.copy())
-    return [tuple(int(v) for v in p) for p in walk]
+    base = np.asarray(base, dtype=np.int64)
+    return [tuple(int(v) for v in p + base) for p in walk]
 
 
-def walk_bounds(size, walk):
-    """a bounding box for every window of the walk, the windows between the axis steps of one shift included"""
+def walk_bounds(size, walk, base=(0, 0, 0)):
+    """a bounding box for every window of the walk from `base`, the windows between the axis steps of one shift included"""
     size = np.asarray(size, dtype=np.int64)
-    p = np.asarray([(0, 0, 0)] + list(walk), dtype=np.int64)
+    p = np.asarray([tuple(int(v) for v in base)] + list(walk), dtype=np.int64)
     return p.min(axis=0) - size // 2, p.max(axis=0) - size // 2 + size - 1
 
 
@@ -234,10 +235,12 @@ def draw_words(rng, n):
     return rng.integers(0, 2 ** 32, int(n), dtype=np.uint64).astype(np.uint32)
 
 
-def walk_coverage(size, walk, seed):
-    """what a walk holds, counted from the walk itself with the writes of run_walk between its steps (same seed, same boxes)"""
+def walk_coverage(size, walk, seed, base=(0, 0, 0)):
+    """what a walk from `base` holds, counted from the walk itself with the writes of run_walk between its steps (same seed, same
+    boxes); "origin" counts the returns to `base`"""
     size = np.asarray(size, dtype=np.int64)
-    w = World(size, *walk_bounds(size, walk), 0)
+    base = np.asarray(base, dtype=np.int64)
+    w = World(size, *walk_bounds(size, walk, base), 0, pos=base)
     rng = np.random.default_rng(seed)
     cov = {"steps": {(axis, d): 0 for axis in range(3) for d in step_sizes(int(size[axis]))}, "diagonal": 0, "corner": 0, "revisit": 0,
            "origin": 0, "seam_boxes": 0, "chunk_borders": 0, "negative_chunks": 0}
@@ -258,16 +261,16 @@ def walk_coverage(size, walk, seed):
             cov["negative_chunks"] += bool(np.any(lo // 64 < 0))
         cov["revisit"] += w.entering_is_revisit(new_pos)
         w.move(new_pos)
-        cov["origin"] += bool(np.all(w.pos == 0))
+        cov["origin"] += bool(np.all(w.pos == base))
     return cov
 
 
-def run_walk(size, walk, seed, route, default_raw, check_every=True, world=None):
-    """the walk through `route`, random boxes written between the shifts (mirrored into the model), the invariant after every step.
+def run_walk(size, walk, seed, route, default_raw, check_every=True, world=None, base=(0, 0, 0)):
+    """the walk from `base` (where the route's window already is) through `route`, random boxes written between the shifts (mirrored into the model), the invariant after every step.
     route: .insert(lo, hi, words), .shift(world, new_pos), .check(world) -- the last compares whatever the route can show
     (parameters, downloads) with the model"""
     size = np.asarray(size, dtype=np.int64)
-    w = world if world is not None else World(size, *walk_bounds(size, walk), default_raw)
+    w = world if world is not None else World(size, *walk_bounds(size, walk, base), default_raw, pos=base)
     rng = np.random.default_rng(seed)
     route.check(w)
     for new_pos in walk:
@@ -281,3 +284,38 @@ def run_walk(size, walk, seed, route, default_raw, check_every=True, world=None)
             route.check(w)
     route.check(w)
     return w
+
+
+# ---------------------------------------------------------------------------------------------------- far bases
+I32_MIN, I32_MAX = -2 ** 31, 2 ** 31 - 1
+
+
+def aligned_base(size, seed, signs):
+    """per axis the multiple of 64 size[k] of largest magnitude, with the sign given, for which the bounding box of the walk
+    (size, seed) from there still fits int32: ring offsets and chunk alignment are those of the walk from the origin"""
+    size = np.asarray(size, dtype=np.int64)
+    blo, bhi = walk_bounds(size, make_walk(size, seed))
+    unit = 64 * size
+    base = np.where(np.asarray(signs) > 0, (I32_MAX - bhi) // unit * unit, -((blo - I32_MIN) // unit * unit))
+    return tuple(int(v) for v in base)
+
+
+def touching_base(size, seed, hi_axis=0, lo_axis=1):
+    """the bounding box of the walk (size, seed) from there has voxel INT32_MAX as its last along hi_axis and INT32_MIN as its first
+    along lo_axis; the third axis is unaligned, at 2^30 + 37"""
+    size = np.asarray(size, dtype=np.int64)
+    blo, bhi = walk_bounds(size, make_walk(size, seed))
+    base = np.full(3, 2 ** 30 + 37, dtype=np.int64)
+    base[hi_axis] = I32_MAX - bhi[hi_axis]
+    base[lo_axis] = I32_MIN - blo[lo_axis]
+    return tuple(int(v) for v in base)
+
+
+def far_bases(size, seed):
+    """the bases the far-position tests run a walk from, by name"""
+    return {"aligned+-+": aligned_base(size, seed, (1, -1, 1)), "aligned-+-": aligned_base(size, seed, (-1, 1, -1)),
+            "touching": touching_base(size, seed)}
+
+
+def fits_int32(lo, hi):
+    return bool(np.all(np.asarray(lo) >= I32_MIN) and np.all(np.asarray(hi) <= I32_MAX))

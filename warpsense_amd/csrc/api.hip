@@ -484,6 +484,27 @@ int ws_map_download(ws_map *m, int which, int32_t size[3], int32_t pos[3], int32
 }
 
 // ---- box transfers: the device side of the map shift (only the slabs that leave / enter move)
+static int range_error(const char *name, const char *what)
+{
+  set_error(std::string(name) + what);
+  return WS_ERR_RANGE;
+}
+
+// The one rule for where a window may be: pos - size/2 .. pos - size/2 + size - 1 lies in int32 on every axis.  The kernels carry
+// world voxels in int32 and only ever form differences inside the window; the host computes the ends in 64 bits here and nowhere
+// else.  Its first voxel into lo, its last into hi (64 bits: they are also what the caller compares with), else WS_ERR_RANGE in
+// the name of the entry point.  ws_map_create, ws_map_set_params and ws_map_upload do not ask (the update has its own domain).
+static int window_fits(const int32_t size[3], const int32_t pos[3], const char *name, int64_t lo[3], int64_t hi[3])
+{
+  for (int k = 0; k < 3; ++k)
+  {
+    lo[k] = (int64_t)pos[k] - size[k] / 2;
+    hi[k] = lo[k] + size[k] - 1;
+    if (lo[k] < (int64_t)INT32_MIN || hi[k] > (int64_t)INT32_MAX) return range_error(name, ": the window pos - size/2 .. pos - size/2 + size - 1 does not fit int32");
+  }
+  return WS_OK;
+}
+
 // The one copy of the box rules.  [lo, hi] in world voxels, both ends included, against the window of map `which`: its first voxel
 // into l, its extent into ext.  lo == hi == NULL is the whole window where `allow_whole`.  `name` starts the error texts.
 static int resolve_box(const ws_map *m, int which, const int32_t lo[3], const int32_t hi[3], bool allow_whole, const char *name, int32_t l[3], int32_t ext[3])
@@ -491,18 +512,22 @@ static int resolve_box(const ws_map *m, int which, const int32_t lo[3], const in
   const auto bad = [name](const char *what) { return invalid((std::string(name) + what).c_str()); };
   if (!allow_whole && (!lo || !hi)) return bad(": bad argument");
   const MapParams &p = m->par[which];
+  int64_t wlo[3], whi[3];
+  WS_TRY(window_fits(p.size, p.pos, name, wlo, whi));
   for (int k = 0; k < 3; ++k)
   {
     if (!lo)
     {
-      l[k] = p.pos[k] - p.size[k] / 2;
+      l[k] = (int32_t)wlo[k];
       ext[k] = p.size[k];
       continue;
     }
     if (hi[k] < lo[k]) return bad(": hi < lo");
-    if (std::abs(lo[k] - p.pos[k]) > p.size[k] / 2 || std::abs(hi[k] - p.pos[k]) > p.size[k] / 2) return bad(": box outside the local map window");
+    // within size/2 of pos, in 64 bits (INT32_MIN - pos wraps in 32)
+    const int64_t half = p.size[k] / 2;
+    if (std::llabs((long long)lo[k] - p.pos[k]) > half || std::llabs((long long)hi[k] - p.pos[k]) > half) return bad(": box outside the local map window");
     l[k] = lo[k];
-    ext[k] = hi[k] - lo[k] + 1;
+    ext[k] = (int32_t)((int64_t)hi[k] - lo[k] + 1); // <= size + 1
     // (an even size admits pos - size/2 .. pos + size/2: size + 1 voxels, the first and the last the same ring cell -- two lanes
     // of an insert would store to one address)
     if (ext[k] > p.size[k]) return bad(": box wraps onto itself (more voxels than the ring holds along an axis)");
@@ -651,12 +676,6 @@ int ws_debug_surface_timing(ws_map *m, int32_t enable, float ms_out[3])
 // (store_mesh.hip, store_raycast.hip; their entry points are further down).  An entry point checks what is its own, takes its lock and
 // hands the shared flow its result holder, its stream and, as lambdas, the launchers of its source; `name` starts the refusal texts.
 extern "C++" {
-static int range_error(const char *name, const char *what)
-{
-  set_error(std::string(name) + what);
-  return WS_ERR_RANGE;
-}
-
 static int mesh_corners_fit(const int32_t lo[3], const int32_t hi[3], int32_t res, const char *name)
 {
   for (int k = 0; k < 3; ++k)
@@ -1010,34 +1029,34 @@ static int plan_shift(const int32_t size[3], const int32_t pos0[3], const int32_
   copy3(pos, pos0);
   copy3(out->offset, offset0);
   out->n = 0;
-  const auto window = [&](int32_t lo[3], int32_t hi[3]) { // of `pos` as it is now
-    for (int k = 0; k < 3; ++k) lo[k] = pos[k] - size[k] / 2, hi[k] = lo[k] + size[k] - 1;
-  };
+  // Every window of the plan fits int32 (window_fits), the one the shift starts from included.  An axis moves once, so a window
+  // between two axis steps is per axis the first window's range or the last one's: asking after every step asks for all of them.
+  // Per axis, x then y then z: the step's size first (WS_ERR_INVALID), then the window behind it (WS_ERR_RANGE).
+  int64_t lo[3], hi[3];
+  WS_TRY(window_fits(size, pos, name, lo, hi));
   for (int axis = 0; axis < 3; ++axis)
   {
     const int64_t d = (int64_t)new_pos[axis] - pos[axis];
     if (d == 0) continue;
     if (std::llabs((long long)d) > size[axis]) return invalid((std::string(name) + ": shift larger than the window").c_str());
+    int64_t start[3] = {lo[0], lo[1], lo[2]}, end[3] = {hi[0], hi[1], hi[2]}; // the window before the step
+    pos[axis] = new_pos[axis];
+    WS_TRY(window_fits(size, pos, name, lo, hi)); // ... and behind it
     const int i = out->n++;
     out->axis[i] = axis;
     out->d[i] = (int32_t)d;
-    int32_t start[3], end[3];
-    window(start, end);
     if (d > 0)
-      end[axis] = start[axis] + (int32_t)d - 1;
+      end[axis] = start[axis] + d - 1;
     else
-      start[axis] = end[axis] + (int32_t)d + 1;
-    copy3(out->leave_lo[i], start);
-    copy3(out->leave_hi[i], end);
-    pos[axis] += (int32_t)d;
+      start[axis] = end[axis] + d + 1;
+    for (int k = 0; k < 3; ++k) out->leave_lo[i][k] = (int32_t)start[k], out->leave_hi[i][k] = (int32_t)end[k];
     out->offset[axis] = (int32_t)((((int64_t)out->offset[axis] + d) % size[axis] + size[axis]) % size[axis]);
-    window(start, end);
+    for (int k = 0; k < 3; ++k) start[k] = lo[k], end[k] = hi[k];
     if (d > 0)
-      start[axis] = end[axis] - ((int32_t)d - 1);
+      start[axis] = end[axis] - (d - 1);
     else
-      end[axis] = start[axis] - (int32_t)d - 1;
-    copy3(out->enter_lo[i], start);
-    copy3(out->enter_hi[i], end);
+      end[axis] = start[axis] - d - 1;
+    for (int k = 0; k < 3; ++k) out->enter_lo[i][k] = (int32_t)start[k], out->enter_hi[i][k] = (int32_t)end[k];
   }
   return WS_OK;
 }
