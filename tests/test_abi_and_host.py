@@ -24,6 +24,76 @@ def test_library_exports_every_declared_symbol():
     assert L.ws_version() >= 1
 
 
+def _declared_entry_points():
+    header = open(os.path.join(ROOT, "include", "warpsense_hip.h")).read()
+    return set(re.findall(r"\b(ws_[a-z0-9_]+)\s*\(", header)) - {"ws_status"}
+
+
+def test_library_exports_nothing_unprefixed():
+    """The library is loaded into other people's programs: beside the declared ws_* entry points it may define only names that cannot
+    collide with theirs -- C++-mangled ones (the ws:: helpers, the kernel stubs) and the toolchain's own, which begin with an
+    underscore.  A host helper with C linkage (a definition inside a linkage block that is not static) would show up here."""
+    import shutil
+    import subprocess
+    from warpsense_amd import _lib
+    nm = shutil.which("nm") or "/opt/rocm/llvm/bin/llvm-nm"
+    assert os.path.exists(nm), "no nm on PATH and no /opt/rocm/llvm/bin/llvm-nm"
+    out = subprocess.run([nm, "-D", "--defined-only", _lib.LIB_PATH], check=True, stdout=subprocess.PIPE, text=True).stdout
+    defined = {ln.split()[-1].split("@")[0] for ln in out.splitlines() if ln.split()}
+    assert defined, out
+    declared = _declared_entry_points()
+    stray = sorted(s for s in defined if s not in declared and not s.startswith("_"))
+    assert not stray, stray
+    exported = {s for s in defined if s.startswith("ws_")}
+    assert exported == declared, exported ^ declared
+
+
+# one entry point of every host file of the library, with arguments it refuses before any device call
+_REFUSED = [
+    ("ws_ctx_set_stream", (None, None)),                         # api_core.hip
+    ("ws_map_download", (None, 0, None, None, None, None)),      # api_map.hip
+    ("ws_map_surface", (None, 0, None, None, 0, 0, None)),       # api_query.hip
+    ("ws_map_mesh", (None, 0, None, None, 0, None, None)),
+    ("ws_store_distance", (None, None, None, 1, 0, None)),       # api_store.hip
+    ("ws_tsdf_integrate", (None,)),                              # api_tsdf.hip
+    ("ws_reg_iterate", (None, None, None, 50, 0, None, None, None, None)),  # api_reg.hip
+    ("ws_scan_download", (None, None, 0, None)),                 # api_scan.hip
+]
+
+
+def test_one_last_error_slot_across_the_host_files():
+    """ws_last_error is one thread-local text whichever file of the library refused: every refusal is read back under its entry
+    point's name, and another thread's refusals leave this thread's text alone."""
+    import threading
+    from warpsense_amd import _lib
+    L = _lib.load()
+    WS_ERR_INVALID = -1
+
+    def refuse_all():
+        for name, args in _REFUSED:
+            assert getattr(L, name)(*args) == WS_ERR_INVALID, name
+            text = L.ws_last_error().decode()
+            assert text.startswith(name + ":"), (name, text)
+
+    refuse_all()
+    assert L.ws_ctx_set_stream(None, None) == WS_ERR_INVALID
+    mine = L.ws_last_error()
+    failed = []
+
+    def other():
+        try:
+            assert L.ws_last_error() == b""  # (a thread that has refused nothing yet)
+            refuse_all()
+        except BaseException as exc:  # noqa: BLE001 -- reported by the test's own thread
+            failed.append(exc)
+
+    t = threading.Thread(target=other)
+    t.start()
+    t.join()
+    assert not failed, failed
+    assert L.ws_last_error() == mine and mine.startswith(b"ws_ctx_set_stream:")
+
+
 def test_no_cpu_fallback_in_product_package():
     """nothing under warpsense_amd/ may import or link the oracle."""
     pkg = os.path.join(ROOT, "warpsense_amd")

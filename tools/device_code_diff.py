@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""Is the device code of two builds the same?  For every object file of the library in two build directories: take the gfx950
-code object out of the fat binary, disassemble it and compare -- the whole listing (addresses and encodings included), and the
-kernels' names and register / scratch / LDS figures from the code object's metadata.  Runs without a GPU.
+"""Is the device code of two builds the same?  For every object file of the library in either of two build directories: take the
+gfx950 code object out of the fat binary, disassemble it and compare -- the whole listing (addresses and encodings included), and
+the kernels' names and register / scratch / LDS figures from the code object's metadata.  An object that only one build has (a
+renamed or split host file) counts as one without device code there: it compares equal iff the other side has none either.  Runs
+without a GPU.
 
     python tools/device_code_diff.py OTHER_TREE/warpsense_amd/build warpsense_amd/build [--json out.json]
 
@@ -25,8 +27,8 @@ def run(*cmd):
 
 def code_object(obj, tmp):
     fat, co = os.path.join(tmp, "fat"), os.path.join(tmp, "co")
-    if ".hip_fatbin" not in run(os.path.join(LLVM, "llvm-objdump"), "-h", obj):
-        return [], {}  # host code only (api.hip has no kernels)
+    if not os.path.exists(obj) or ".hip_fatbin" not in run(os.path.join(LLVM, "llvm-objdump"), "-h", obj):
+        return [], {}  # not in this build, or host code only (the api_*.hip files have no kernels)
     run(os.path.join(LLVM, "llvm-objcopy"), f"--dump-section=.hip_fatbin={fat}", obj)
     run(os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", f"--input={fat}", f"--targets={TARGET}", f"--output={co}")
     listing = run(os.path.join(LLVM, "llvm-objdump"), "-d", co).split("\n")[2:]  # (the first lines name the file)
@@ -42,15 +44,22 @@ def code_object(obj, tmp):
     return listing, kernels
 
 
+def instructions(listing):
+    return sum(1 for ln in listing if ln.startswith("\t"))
+
+
 def main():
     a_dir, b_dir = sys.argv[1], sys.argv[2]
     report, differ = {}, False
-    for name in sorted(f for f in os.listdir(a_dir) if f.endswith(".o")):
+    for name in sorted({f for d in (a_dir, b_dir) for f in os.listdir(d) if f.endswith(".o")}):
         with tempfile.TemporaryDirectory() as ta, tempfile.TemporaryDirectory() as tb:
             la, ka = code_object(os.path.join(a_dir, name), ta)
             lb, kb = code_object(os.path.join(b_dir, name), tb)
         same = la == lb and ka == kb
-        entry = {"identical": same, "kernels": len(ka), "instructions": sum(1 for ln in la if ln.startswith("\t"))}
+        entry = {"identical": same, "kernels": max(len(ka), len(kb)), "instructions": max(instructions(la), instructions(lb))}
+        missing = [side for side, d in (("a", a_dir), ("b", b_dir)) if not os.path.exists(os.path.join(d, name))]
+        if missing:
+            entry["only_in"] = "b" if missing == ["a"] else "a"
         if not same:
             differ = True
             entry["kernels_a"], entry["kernels_b"] = ka, kb

@@ -1,0 +1,306 @@
+// api_query.hip — the queries of a map's window: surface cloud, mesh, ray cast and distance field (ws_map_surface, ws_map_mesh,
+// ws_map_raycast, ws_map_distance and what goes with each), and the parts of the query cores of ws_api.h that are no templates.
+#include <algorithm>
+
+#include "ws_api.h"
+
+using namespace ws;
+
+// ---- surface cloud: publish_local_map's extraction (visualization/map.h:14-121) on the device, map_surface.hip
+int ws_map_surface(ws_map *m, int which, const int32_t lo[3], const int32_t hi[3], int32_t band, uint32_t flags, size_t *n_out)
+{
+  if (!m || (which != WS_MAP_AVG && which != WS_MAP_NEW) || (flags & ~WS_SURFACE_MARKER) || ((lo == nullptr) != (hi == nullptr)))
+    return invalid("ws_map_surface: bad argument");
+  WS_SETTLE(m);
+  std::lock_guard<std::mutex> lock(m->surf.mu);
+  ws_map::Surface &q = m->surf;
+  int rc = q.timer.arm();
+  int32_t l[3], ext[3];
+  if (rc == WS_OK) rc = resolve_box(m, which, lo, hi, true, "ws_map_surface", l, ext);
+  if (rc == WS_OK) rc = q.total.alloc(1);
+  if (rc != WS_OK) return rc;
+  if (band <= 0) band = m->tau;
+  const bool marker = (flags & WS_SURFACE_MARKER) != 0;
+  hipStream_t s = m->ctx->stream;
+  const size_t n_cols = (size_t)ext[0] * (size_t)ext[1], blocks = surface_blocks_for((int64_t)n_cols); // n_cols < 2^31 (ws_map_create)
+  if (n_cols > q.col_cnt.cap || blocks > q.blk_tot.cap || blocks > q.blk_off.cap)
+  {
+    WS_HIP(hipStreamSynchronize(s));
+    rc = q.col_cnt.grow(n_cols, sizeof(uint32_t));
+    if (rc == WS_OK) rc = q.blk_tot.grow(blocks, sizeof(uint32_t));
+    if (rc == WS_OK) rc = q.blk_off.grow(blocks, sizeof(unsigned long long));
+    if (rc != WS_OK) return rc;
+  }
+  q.n = 0;
+  q.has_marker = false;
+  rc = launch_surface_count(m, which, l, ext, band);
+  if (rc != WS_OK) return rc;
+  WS_HIP(hipStreamSynchronize(s)); // the one host read the call needs: the output is sized from the counted total
+  const size_t total = (size_t)*q.total.host;
+  rc = q.rec.grow(total, 16);
+  if (rc == WS_OK && marker) rc = q.marker.grow(total, 7 * sizeof(float));
+  if (rc != WS_OK) return rc;
+  if (total)
+  {
+    // (the kernel's bound holds for both buffers)
+    rc = launch_surface_emit(m, which, l, ext, band, marker, marker ? std::min(q.rec.cap, q.marker.cap) : q.rec.cap);
+    if (rc != WS_OK) return rc;
+    WS_HIP(hipStreamSynchronize(s));
+  }
+  q.n = total;
+  q.has_marker = marker;
+  if (n_out) *n_out = total;
+  return map_take_error(m);
+}
+
+const void *ws_map_surface_records_dev(const ws_map *m, size_t *n)
+{
+  if (n) *n = m ? m->surf.n : 0;
+  return m && m->surf.n ? m->surf.rec.p : nullptr;
+}
+
+const float *ws_map_surface_marker_dev(const ws_map *m, size_t *n)
+{
+  const bool have = m && m->surf.has_marker && m->surf.n;
+  if (n) *n = have ? m->surf.n : 0;
+  return have ? static_cast<const float *>(m->surf.marker.p) : nullptr;
+}
+
+int ws_map_surface_download(ws_map *m, void *records_host, float *marker_host, size_t capacity_points, size_t *n_out)
+{
+  if (!m || !n_out) return invalid("ws_map_surface_download: NULL argument");
+  std::lock_guard<std::mutex> lock(m->surf.mu);
+  *n_out = m->surf.n;
+  const size_t k = std::min(capacity_points, m->surf.n);
+  if (k == 0) return WS_OK;
+  if (marker_host && !m->surf.has_marker) return invalid("ws_map_surface_download: the last ws_map_surface did not ask for WS_SURFACE_MARKER");
+  if (records_host) WS_HIP(hipMemcpyAsync(records_host, m->surf.rec.p, k * 16, hipMemcpyDeviceToHost, m->ctx->stream));
+  if (marker_host) WS_HIP(hipMemcpyAsync(marker_host, m->surf.marker.p, k * 7 * sizeof(float), hipMemcpyDeviceToHost, m->ctx->stream));
+  WS_HIP(hipStreamSynchronize(m->ctx->stream));
+  return WS_OK;
+}
+
+// ws_debug_*_timing: the times of the last call between the event pairs of `pairs`, then the switch
+int ws::query_timing(hipStream_t s, QueryTimer &t, int32_t enable, float *ms_out, const int (*pairs)[2], int n)
+{
+  const int rc = t.read(ms_out, pairs, n, s);
+  if (rc == WS_OK) t.set(enable);
+  return rc;
+}
+
+int ws_debug_surface_timing(ws_map *m, int32_t enable, float ms_out[3])
+{
+  if (!m) return invalid("ws_debug_surface_timing: map is NULL");
+  std::lock_guard<std::mutex> lock(m->surf.mu);
+  static const int pairs[3][2] = {{0, 1}, {1, 2}, {3, 4}};
+  return query_timing(m->ctx->stream, m->surf.timer, enable, ms_out, pairs, 3);
+}
+
+// ---- mesh and ray cast: what the host cores of ws_api.h (mesh_run, raycast_check, raycast_run) need beside them, for the window of
+// a map here and for the chunks of the store in api_store.hip
+int ws::mesh_corners_fit(const int32_t lo[3], const int32_t hi[3], int32_t res, const char *name)
+{
+  for (int k = 0; k < 3; ++k)
+    for (int64_t c : {(int64_t)lo[k], (int64_t)hi[k]})
+      if (((c < 0 ? -c : c) + 1) * (int64_t)res > (int64_t)INT32_MAX) return range_error(name, ": a box corner in millimetres does not fit int32");
+  return WS_OK;
+}
+
+int ws::mesh_publish(MeshResult &q, size_t nv, size_t nf, size_t *n_vertices, size_t *n_faces)
+{
+  q.nv = nv, q.nf = nf;
+  if (n_vertices) *n_vertices = nv;
+  if (n_faces) *n_faces = nf;
+  return WS_OK;
+}
+
+const void *ws::mesh_vertices_dev(const MeshResult *q, size_t *n)
+{
+  if (n) *n = q ? q->nv : 0;
+  return q && q->nv ? q->vert.p : nullptr;
+}
+
+const uint32_t *ws::mesh_faces_dev(const MeshResult *q, size_t *n)
+{
+  if (n) *n = q ? q->nf : 0;
+  return q && q->nf ? static_cast<const uint32_t *>(q->face.p) : nullptr;
+}
+
+int ws::mesh_download(const MeshResult &q, hipStream_t s, void *vertices_host, uint32_t *faces_host, size_t cap_vertices, size_t cap_faces, size_t *n_vertices,
+                      size_t *n_faces)
+{
+  *n_vertices = q.nv;
+  *n_faces = q.nf;
+  const size_t kv = vertices_host ? std::min(cap_vertices, q.nv) : 0, kf = faces_host ? std::min(cap_faces, q.nf) : 0;
+  if (kv) WS_HIP(hipMemcpyAsync(vertices_host, q.vert.p, kv * 16, hipMemcpyDeviceToHost, s));
+  if (kf) WS_HIP(hipMemcpyAsync(faces_host, q.face.p, kf * 12, hipMemcpyDeviceToHost, s));
+  if (kv || kf) WS_HIP(hipStreamSynchronize(s));
+  return WS_OK;
+}
+
+const void *ws::raycast_records_dev(const RayResult *q, size_t *n)
+{
+  if (n) *n = q ? q->n : 0;
+  return q && q->n ? q->rec.p : nullptr;
+}
+
+const int32_t *ws::raycast_gradient_dev(const RayResult *q, size_t *n)
+{
+  const bool have = q && q->has_grad && q->n;
+  if (n) *n = have ? q->n : 0;
+  return have ? static_cast<const int32_t *>(q->grad.p) : nullptr;
+}
+
+// `name`, `call`: the download entry point, and the entry point whose flag it misses
+int ws::raycast_download(const RayResult &q, hipStream_t s, const char *name, const char *call, void *records_host, int32_t *gradient_host, size_t capacity_rays,
+                         size_t *n_out)
+{
+  *n_out = q.n;
+  const size_t k = std::min(capacity_rays, q.n);
+  if (k == 0) return WS_OK;
+  if (gradient_host && !q.has_grad) return invalid(std::string(name) + ": the last " + call + " did not ask for WS_RAYCAST_GRADIENT");
+  if (records_host) WS_HIP(hipMemcpyAsync(records_host, q.rec.p, k * 16, hipMemcpyDeviceToHost, s));
+  if (gradient_host) WS_HIP(hipMemcpyAsync(gradient_host, q.grad.p, k * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  WS_HIP(hipStreamSynchronize(s));
+  return WS_OK;
+}
+
+// ---- mesh: naive surface nets over a device map, map_mesh.hip (the rules are stated in warpsense_hip.h)
+int ws_map_mesh(ws_map *m, int which, const int32_t lo[3], const int32_t hi[3], uint32_t flags, size_t *n_vertices, size_t *n_faces)
+{
+  if (!m || (which != WS_MAP_AVG && which != WS_MAP_NEW) || (flags & ~WS_MESH_ANY_WEIGHT) || ((lo == nullptr) != (hi == nullptr)))
+    return invalid("ws_map_mesh: bad argument");
+  WS_SETTLE(m);
+  std::lock_guard<std::mutex> lock(m->mesh.mu);
+  MeshResult &q = m->mesh;
+  WS_TRY(q.timer.arm());
+  int32_t l[3], ext[3];
+  WS_TRY(resolve_box(m, which, lo, hi, true, "ws_map_mesh", l, ext));
+  const int32_t h[3] = {l[0] + (ext[0] - 1), l[1] + (ext[1] - 1), l[2] + (ext[2] - 1)}; // (a voxel of the window)
+  WS_TRY(mesh_corners_fit(l, h, m->res, "ws_map_mesh"));
+  mesh_publish(q, 0, 0, n_vertices, n_faces);
+  const uint64_t n_words = (uint64_t)ext[0] * (uint64_t)ext[1] * (uint64_t)((ext[2] + 63) / 64);
+  if (n_words >= (1ull << 31)) return range_error("ws_map_mesh", ": box too large (columns x 64-voxel words must stay below 2^31)");
+  if (ext[0] < 2 || ext[1] < 2 || ext[2] < 2) return map_take_error(m); // one voxel thick along an axis: no cells
+  WS_TRY(mesh_run(
+      q, m->ctx->stream, "ws_map_mesh", n_words, n_vertices, n_faces, [&] { return launch_mesh_count(m, q, which, l, ext, flags); },
+      [&] { return launch_mesh_emit(m, q, which, l, ext, flags); }));
+  return map_take_error(m);
+}
+
+const void *ws_map_mesh_vertices_dev(const ws_map *m, size_t *n) { return mesh_vertices_dev(m ? &m->mesh : nullptr, n); }
+
+const uint32_t *ws_map_mesh_faces_dev(const ws_map *m, size_t *n) { return mesh_faces_dev(m ? &m->mesh : nullptr, n); }
+
+int ws_map_mesh_download(ws_map *m, void *vertices_host, uint32_t *faces_host, size_t cap_vertices, size_t cap_faces, size_t *n_vertices, size_t *n_faces)
+{
+  if (!m || !n_vertices || !n_faces) return invalid("ws_map_mesh_download: NULL argument");
+  std::lock_guard<std::mutex> lock(m->mesh.mu);
+  return mesh_download(m->mesh, m->ctx->stream, vertices_host, faces_host, cap_vertices, cap_faces, n_vertices, n_faces);
+}
+
+int ws_debug_mesh_timing(ws_map *m, int32_t enable, float ms_out[3])
+{
+  if (!m) return invalid("ws_debug_mesh_timing: map is NULL");
+  std::lock_guard<std::mutex> lock(m->mesh.mu);
+  return query_timing(m->ctx->stream, m->mesh.timer, enable, ms_out, MESH_PAIRS, 3);
+}
+
+// ---- ray cast: the range image of a device map, map_raycast.hip (the rules are stated in warpsense_hip.h)
+static int map_raycast(ws_map *m, int which, const int32_t origin[3], const int32_t *dirs, bool dirs_on_host, size_t n, int32_t max_range, uint32_t flags,
+                       size_t *n_hits)
+{
+  WS_TRY(raycast_check("ws_map_raycast", !m || (which != WS_MAP_AVG && which != WS_MAP_NEW), origin, dirs, n, max_range, m ? m->res : 0, flags,
+                       [] { return WS_OK; }));
+  WS_SETTLE(m);
+  std::lock_guard<std::mutex> lock(m->ray.mu);
+  RayResult &q = m->ray;
+  WS_TRY(raycast_run(
+      q, m->ctx->stream, dirs, dirs_on_host, n, flags, n_hits, false, [] { return WS_OK; },
+      [&](const int32_t *dirs_dev) { return launch_raycast(m, q, which, origin, dirs_dev, n, max_range, flags); }));
+  return map_take_error(m);
+}
+
+int ws_map_raycast(ws_map *m, int which, const int32_t origin_mm[3], const int32_t *dirs_host, size_t n, int32_t max_range_mm, uint32_t flags, size_t *n_hits)
+{
+  return map_raycast(m, which, origin_mm, dirs_host, true, n, max_range_mm, flags, n_hits);
+}
+
+int ws_map_raycast_dev(ws_map *m, int which, const int32_t origin_mm[3], const int32_t *dirs_dev, size_t n, int32_t max_range_mm, uint32_t flags, size_t *n_hits)
+{
+  return map_raycast(m, which, origin_mm, dirs_dev, false, n, max_range_mm, flags, n_hits);
+}
+
+const void *ws_map_raycast_records_dev(const ws_map *m, size_t *n) { return raycast_records_dev(m ? &m->ray : nullptr, n); }
+
+const int32_t *ws_map_raycast_gradient_dev(const ws_map *m, size_t *n) { return raycast_gradient_dev(m ? &m->ray : nullptr, n); }
+
+int ws_map_raycast_download(ws_map *m, void *records_host, int32_t *gradient_host, size_t capacity_rays, size_t *n_out)
+{
+  if (!m || !n_out) return invalid("ws_map_raycast_download: NULL argument");
+  std::lock_guard<std::mutex> lock(m->ray.mu);
+  return raycast_download(m->ray, m->ctx->stream, "ws_map_raycast_download", "ws_map_raycast", records_host, gradient_host, capacity_rays, n_out);
+}
+
+int ws_debug_raycast_timing(ws_map *m, int32_t enable, float ms_out[3])
+{
+  if (!m) return invalid("ws_debug_raycast_timing: map is NULL");
+  std::lock_guard<std::mutex> lock(m->ray.mu);
+  return query_timing(m->ctx->stream, m->ray.timer, enable, ms_out, RAY_PAIRS, 3);
+}
+
+// ---- distance field: the same beside distance_check and distance_run.  The window and the store differ in pass 0 only.
+const uint32_t *ws::distance_dev(const DistResult *q, size_t *n)
+{
+  if (n) *n = q ? q->n : 0;
+  return q && q->n ? static_cast<const uint32_t *>(q->rec.p) : nullptr;
+}
+
+int ws::distance_download(const DistResult &q, hipStream_t s, uint32_t *host, size_t capacity, size_t *n_out)
+{
+  *n_out = q.n;
+  const size_t k = host ? std::min(capacity, q.n) : 0;
+  if (k == 0) return WS_OK;
+  WS_HIP(hipMemcpyAsync(host, q.rec.p, k * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  WS_HIP(hipStreamSynchronize(s));
+  return WS_OK;
+}
+
+// ---- distance field: the exact Euclidean transform of a device map, map_distance.hip (the rules are stated in warpsense_hip.h)
+int ws_map_distance(ws_map *m, int which, const int32_t lo[3], const int32_t hi[3], int32_t max_dist_vox, uint32_t flags, size_t *n_sites)
+{
+  std::unique_lock<std::mutex> lock;
+  int32_t l[3], ext[3];
+  uint32_t e32[3];
+  size_t n = 0;
+  WS_TRY(distance_check(
+      "ws_map_distance", !m || (which != WS_MAP_AVG && which != WS_MAP_NEW), lo, hi, max_dist_vox, flags,
+      [&](uint64_t e[3]) {
+        WS_SETTLE(m);
+        lock = std::unique_lock<std::mutex>(m->dist.mu);
+        WS_TRY(m->dist.timer.arm());
+        WS_TRY(resolve_box(m, which, lo, hi, true, "ws_map_distance", l, ext)); // ext[0] ext[1] < 2^31, ext[2] <= 2^20
+        for (int k = 0; k < 3; ++k) e[k] = (uint64_t)ext[k];
+        return (int)WS_OK;
+      },
+      e32, &n));
+  DistResult &q = m->dist;
+  WS_TRY(distance_run(q, m->ctx->stream, e32, max_dist_vox, flags, n, n_sites, [&] { return launch_dist_classify(m, q, which, l, ext, max_dist_vox, flags); }));
+  return map_take_error(m);
+}
+
+const uint32_t *ws_map_distance_dev(const ws_map *m, size_t *n) { return distance_dev(m ? &m->dist : nullptr, n); }
+
+int ws_map_distance_download(ws_map *m, uint32_t *host, size_t capacity, size_t *n_out)
+{
+  if (!m || !n_out) return invalid("ws_map_distance_download: NULL argument");
+  std::lock_guard<std::mutex> lock(m->dist.mu);
+  return distance_download(m->dist, m->ctx->stream, host, capacity, n_out);
+}
+
+int ws_debug_distance_timing(ws_map *m, int32_t enable, float ms_out[4])
+{
+  if (!m) return invalid("ws_debug_distance_timing: map is NULL");
+  std::lock_guard<std::mutex> lock(m->dist.mu);
+  return query_timing(m->ctx->stream, m->dist.timer, enable, ms_out, DIST_PAIRS, 4);
+}

@@ -1,0 +1,719 @@
+// api_store.hip — the chunk store, the global map in device memory (ws_store_*, ws_shift_device; kernels in map_store.hip): directory,
+// segments and slot tables, the box transfers between a map's window and the chunks, and the store's mesh, ray cast and distance field,
+// which run the host cores of ws_api.h over the chunks a call lists (store_mesh.hip, store_raycast.hip, store_distance.hip).
+#include <algorithm>
+#include <array>
+#include <cstring>
+#include <new>
+#include <set>
+
+#include "ws_api.h"
+
+using namespace ws;
+
+// ---- the chunk store: the global map in device memory (map_store.hip)
+namespace
+{
+using StoreKey = std::array<int32_t, 3>;
+inline int32_t chunk_of(int32_t v) { return v >= 0 ? v / STORE_CS : -((-(int64_t)v + STORE_CS - 1) / STORE_CS); } // floor(v / 64)
+
+// the chunks an inclusive world box overlaps: first key and count per axis
+struct ChunkRange
+{
+  int32_t c0[3], nc[3];
+  size_t n;
+  ChunkRange(const int32_t lo[3], const int32_t hi[3])
+  {
+    n = 1;
+    for (int k = 0; k < 3; ++k)
+    {
+      c0[k] = chunk_of(lo[k]);
+      nc[k] = chunk_of(hi[k]) - c0[k] + 1;
+      n *= (size_t)nc[k];
+    }
+  }
+  StoreKey key(size_t i) const // x major, like the slot table
+  {
+    const size_t plane = (size_t)nc[1] * (size_t)nc[2];
+    return {c0[0] + (int32_t)(i / plane), c0[1] + (int32_t)(i % plane / (size_t)nc[2]), c0[2] + (int32_t)(i % (size_t)nc[2])};
+  }
+};
+
+uint64_t store_capacity(const ws_store *st) { return (uint64_t)st->segs.size() << st->seg_shift; }
+
+uint32_t *store_slot_ptr(const ws_store *st, uint32_t slot)
+{
+  return st->seg_ptr[slot >> st->seg_shift] + (size_t)(slot & ((1u << st->seg_shift) - 1u)) * (size_t)STORE_CHUNK_WORDS;
+}
+
+// Segments for `chunks` chunks in all.  Adding one waits for the stream (the kernels in flight read the old segment table); a failed
+// allocation gives back what this call added, so the store is as it was.
+int store_grow(ws_store *st, uint64_t chunks)
+{
+  if (chunks <= store_capacity(st)) return WS_OK;
+  if (chunks >= 0x7fffffffull) return invalid("ws_store: more than 2^31 - 1 chunks");
+  const size_t had = st->segs.size(), want = (size_t)((chunks + (1ull << st->seg_shift) - 1) >> st->seg_shift);
+  WS_HIP(hipStreamSynchronize(st->ctx->stream));
+  int rc = WS_OK;
+  DevBuf tab;
+  for (size_t i = had; i < want && rc == WS_OK; ++i)
+  {
+    st->segs.emplace_back();
+    rc = st->segs.back().alloc((size_t)STORE_CHUNK_WORDS << st->seg_shift, sizeof(uint32_t));
+    if (rc == WS_OK) st->seg_ptr.push_back(st->segs.back().as<uint32_t>());
+  }
+  if (rc == WS_OK) rc = tab.alloc(want, sizeof(uint32_t *));
+  if (rc == WS_OK)
+  {
+    const hipError_t e = hipMemcpy(tab.p, st->seg_ptr.data(), want * sizeof(uint32_t *), hipMemcpyHostToDevice);
+    if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy (segment table)", __FILE__, __LINE__);
+  }
+  if (rc != WS_OK)
+  {
+    tab.release();
+    for (size_t i = had; i < st->segs.size(); ++i) st->segs[i].release();
+    st->segs.resize(had);
+    st->seg_ptr.resize(had);
+    return rc;
+  }
+  st->seg_tab.release();
+  st->seg_tab = tab; // (DevBuf is a plain pair: the store owns the new table now)
+  return WS_OK;
+}
+
+// chunks that can still be created without a new segment / at all
+uint64_t store_unused(const ws_store *st) { return st->free_slots.size() + (store_capacity(st) - st->next_slot); }
+
+// Room for `fresh` more chunks: WS_ERR_CAPACITY beyond max_chunks, segments where they are missing.  Nothing else changes.
+int store_make_room(ws_store *st, uint64_t fresh, const char *name)
+{
+  if (st->max_chunks && st->dir.size() + fresh > st->max_chunks)
+  {
+    set_error(std::string(name) + ": the store would hold more than max_chunks chunks");
+    return WS_ERR_CAPACITY;
+  }
+  if (fresh <= store_unused(st)) return WS_OK;
+  return store_grow(st, (uint64_t)st->next_slot + (fresh - st->free_slots.size()));
+}
+
+uint32_t store_take_slot(ws_store *st) // (store_make_room has been asked)
+{
+  if (!st->free_slots.empty())
+  {
+    const uint32_t s = st->free_slots.back();
+    st->free_slots.pop_back();
+    return s;
+  }
+  return st->next_slot++;
+}
+
+// room for n words in one slot table (pinned + device) and its event
+int store_table_reserve(ws_store::Table &t, size_t n)
+{
+  if (!t.done) WS_HIP(hipEventCreateWithFlags(&t.done, hipEventDisableTiming));
+  if (n <= t.host.cap) return WS_OK;
+  WS_TRY(t.host.alloc(n, sizeof(uint32_t), HostBlock::PINNED));
+  return t.dev.alloc(n, sizeof(uint32_t));
+}
+
+// The next slot table of the ring, for n words: waits only for the launch that read this table STORE_TABLES calls ago.  The tables are
+// sized when the store is created (STORE_TABLE_WORDS); a box that overlaps more chunks makes one grow here, which allocates.
+int store_table(ws_store *st, size_t n, ws_store::Table **out)
+{
+  ws_store::Table &t = st->tab[st->tab_next];
+  st->tab_next = (st->tab_next + 1) % STORE_TABLES;
+  if (t.used) WS_HIP(hipEventSynchronize(t.done));
+  t.used = false;
+  WS_TRY(store_table_reserve(t, n > t.host.cap ? n + n / 8 : n));
+  *out = &t;
+  return WS_OK;
+}
+
+// One launch: the box of `which` (window `par`) into the chunks or back.  The directory already holds every chunk a save needs (a
+// save table never holds STORE_ABSENT: the kernel would read that word as slot 2^31 - 1, flagged new).  A chunk this call created
+// and nothing has written yet is flagged STORE_NEW by the first save that meets it -- that launch writes it whole -- and is absent
+// to a load: a later slab of the same shift will write it.
+int store_enqueue(ws_store *st, ws_map *m, const MapParams &par, int which, const int32_t lo[3], const int32_t hi[3], bool save)
+{
+  const ChunkRange cr(lo, hi);
+  ws_store::Table *t = nullptr;
+  WS_TRY(store_table(st, cr.n, &t));
+  uint32_t *w = t->host.as<uint32_t>();
+  bool any_new = false;
+  for (size_t i = 0; i < cr.n; ++i)
+  {
+    const auto it = st->dir.find(cr.key(i));
+    if (it == st->dir.end() || (!save && !it->second.written))
+    {
+      if (save)
+      {
+        set_error("ws_store: internal error, a save met a chunk without a slot");
+        return WS_ERR_INTERNAL;
+      }
+      w[i] = STORE_ABSENT;
+      continue;
+    }
+    w[i] = it->second.slot | (it->second.written ? 0u : STORE_NEW);
+    any_new |= !it->second.written;
+    it->second.written = true;
+  }
+  hipStream_t s = st->ctx->stream;
+  WS_HIP(hipMemcpyAsync(t->dev.p, t->host.p, cr.n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+  WS_TRY(launch_store_copy(st, m, par, which, lo, hi, cr.c0, cr.nc, t->dev.as<uint32_t>(), save, any_new, s));
+  WS_HIP(hipEventRecord(t->done, s));
+  t->used = true;
+  return WS_OK;
+}
+
+// the keys of `lo .. hi` the directory does not hold yet, into `fresh` (a set: each once)
+void store_missing(const ws_store *st, const int32_t lo[3], const int32_t hi[3], std::set<StoreKey> &fresh)
+{
+  const ChunkRange cr(lo, hi);
+  for (size_t i = 0; i < cr.n; ++i)
+  {
+    const StoreKey key = cr.key(i);
+    if (!st->dir.count(key)) fresh.insert(key);
+  }
+}
+
+// gives the chunks of `fresh` their slots (unwritten) / takes them back after a failure half-way
+void store_admit(ws_store *st, const std::set<StoreKey> &fresh)
+{
+  for (const StoreKey &k : fresh) st->dir[k] = ws_store::Entry{store_take_slot(st), false};
+}
+void store_evict(ws_store *st, const std::set<StoreKey> &fresh)
+{
+  for (const StoreKey &k : fresh)
+  {
+    const auto it = st->dir.find(k);
+    if (it == st->dir.end()) continue;
+    st->free_slots.push_back(it->second.slot);
+    st->dir.erase(it);
+  }
+}
+
+int store_args(const ws_store *st, const ws_map *m, int which, const char *name)
+{
+  if (!st || !m || (which != WS_MAP_AVG && which != WS_MAP_NEW)) return invalid((std::string(name) + ": bad argument").c_str());
+  if (st->ctx != m->ctx) return invalid((std::string(name) + ": the store belongs to another context").c_str());
+  return WS_OK;
+}
+} // namespace
+
+int ws_store_create(ws_context *ctx, uint32_t fill_entry, uint64_t max_chunks, uint32_t segment_chunks, ws_store **out)
+{
+  if (!ctx || !out) return invalid("ws_store_create: NULL argument");
+  if (segment_chunks > (1u << 16)) return invalid("ws_store_create: segment_chunks beyond 65 536 (64 GB per segment)");
+  ws_store *st = new (std::nothrow) ws_store();
+  if (!st) return invalid("ws_store_create: out of host memory");
+  st->ctx = ctx;
+  st->fill = fill_entry;
+  st->max_chunks = max_chunks;
+  // the default: 256 chunks = 256 MB per segment; any other value is rounded up to a power of two (the kernels shift and mask)
+  const uint32_t want = segment_chunks ? segment_chunks : 256u;
+  while ((1u << st->seg_shift) < want) ++st->seg_shift;
+  // the slot tables and their events now: no shift allocates them
+  for (ws_store::Table &t : st->tab)
+  {
+    const int rc = store_table_reserve(t, STORE_TABLE_WORDS);
+    if (rc != WS_OK)
+    {
+      st->release();
+      delete st;
+      return rc;
+    }
+  }
+  *out = st;
+  return WS_OK;
+}
+
+int ws_store_destroy(ws_store *st)
+{
+  if (!st) return WS_OK;
+  (void)hipStreamSynchronize(st->ctx->stream);
+  st->release();
+  delete st;
+  return WS_OK;
+}
+
+int ws_store_reserve(ws_store *st, uint64_t chunks)
+{
+  if (!st) return invalid("ws_store_reserve: store is NULL");
+  std::lock_guard<std::mutex> lock(st->mu);
+  if (st->max_chunks && chunks > st->max_chunks) chunks = st->max_chunks;
+  return store_grow(st, chunks);
+}
+
+int ws_store_count(const ws_store *st, uint64_t *chunks, uint64_t *capacity_chunks)
+{
+  if (!st) return invalid("ws_store_count: store is NULL");
+  std::lock_guard<std::mutex> lock(const_cast<ws_store *>(st)->mu);
+  if (chunks) *chunks = st->dir.size();
+  if (capacity_chunks) *capacity_chunks = store_capacity(st);
+  return WS_OK;
+}
+
+int ws_store_keys(const ws_store *st, int32_t *keys, size_t capacity, size_t *n_out)
+{
+  if (!st || (!keys && capacity)) return invalid("ws_store_keys: bad argument");
+  std::lock_guard<std::mutex> lock(const_cast<ws_store *>(st)->mu);
+  size_t i = 0;
+  for (const auto &kv : st->dir)
+  {
+    if (i >= capacity) break;
+    for (int k = 0; k < 3; ++k) keys[3 * i + k] = kv.first[k];
+    ++i;
+  }
+  if (n_out) *n_out = st->dir.size();
+  return WS_OK;
+}
+
+int ws_store_has(const ws_store *st, const int32_t key[3])
+{
+  if (!st || !key) return 0;
+  std::lock_guard<std::mutex> lock(const_cast<ws_store *>(st)->mu);
+  return st->dir.count({key[0], key[1], key[2]}) ? 1 : 0;
+}
+
+int ws_store_get_chunk(ws_store *st, const int32_t key[3], uint32_t *host, int32_t *found)
+{
+  if (!st || !key || !host) return invalid("ws_store_get_chunk: NULL argument");
+  std::lock_guard<std::mutex> lock(st->mu);
+  const auto it = st->dir.find({key[0], key[1], key[2]});
+  if (found) *found = it != st->dir.end();
+  if (it == st->dir.end()) return WS_OK;
+  WS_HIP(hipMemcpyAsync(host, store_slot_ptr(st, it->second.slot), (size_t)STORE_CHUNK_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, st->ctx->stream));
+  WS_HIP(hipStreamSynchronize(st->ctx->stream));
+  return WS_OK;
+}
+
+int ws_store_put_chunk(ws_store *st, const int32_t key[3], const uint32_t *host)
+{
+  if (!st || !key || !host) return invalid("ws_store_put_chunk: NULL argument");
+  std::lock_guard<std::mutex> lock(st->mu);
+  const StoreKey k = {key[0], key[1], key[2]};
+  auto it = st->dir.find(k);
+  if (it == st->dir.end())
+  {
+    WS_TRY(store_make_room(st, 1, "ws_store_put_chunk"));
+    it = st->dir.emplace(k, ws_store::Entry{store_take_slot(st), true}).first;
+  }
+  WS_HIP(hipMemcpyAsync(store_slot_ptr(st, it->second.slot), host, (size_t)STORE_CHUNK_WORDS * sizeof(uint32_t), hipMemcpyHostToDevice, st->ctx->stream));
+  WS_HIP(hipStreamSynchronize(st->ctx->stream)); // the host buffer may be reused by the caller
+  return WS_OK;
+}
+
+int ws_store_drop_chunk(ws_store *st, const int32_t key[3])
+{
+  if (!st || !key) return invalid("ws_store_drop_chunk: NULL argument");
+  std::lock_guard<std::mutex> lock(st->mu);
+  const auto it = st->dir.find({key[0], key[1], key[2]});
+  if (it == st->dir.end()) return invalid("ws_store_drop_chunk: the store has no such chunk");
+  // whatever still reads or writes the slot was enqueued before whatever the next owner of the slot enqueues
+  st->free_slots.push_back(it->second.slot);
+  st->dir.erase(it);
+  return WS_OK;
+}
+
+const uint32_t *ws_store_chunk_dev(const ws_store *st, const int32_t key[3])
+{
+  if (!st || !key) return nullptr;
+  std::lock_guard<std::mutex> lock(const_cast<ws_store *>(st)->mu);
+  const auto it = st->dir.find({key[0], key[1], key[2]});
+  return it == st->dir.end() ? nullptr : store_slot_ptr(st, it->second.slot);
+}
+
+static int store_box(ws_store *st, ws_map *m, int which, const int32_t lo[3], const int32_t hi[3], bool save, const char *name)
+{
+  WS_TRY(store_args(st, m, which, name));
+  WS_SETTLE(m);
+  std::lock_guard<std::mutex> lock(st->mu);
+  int32_t l[3], ext[3];
+  WS_TRY(resolve_box(m, which, lo, hi, false, name, l, ext));
+  WS_TRY(st->timer[0].arm());
+  st->timer[1].marked = st->timer[2].marked = 0;
+  std::set<StoreKey> fresh;
+  if (save)
+  {
+    store_missing(st, lo, hi, fresh);
+    WS_TRY(store_make_room(st, fresh.size(), name));
+    store_admit(st, fresh); // (nothing below can fail before the launch is being enqueued)
+  }
+  st->timer[0].mark(save ? 0 : 1, st->ctx->stream);
+  const int rc = store_enqueue(st, m, m->par[which], which, lo, hi, save);
+  st->timer[0].mark(save ? 1 : 2, st->ctx->stream);
+  if (rc != WS_OK)
+  {
+    store_evict(st, fresh);
+    return rc;
+  }
+  if (!save && which == WS_MAP_NEW) m->new_is_default = false;
+  return WS_OK;
+}
+
+int ws_store_save_box(ws_store *st, ws_map *m, int which, const int32_t lo[3], const int32_t hi[3])
+{
+  return store_box(st, m, which, lo, hi, true, "ws_store_save_box");
+}
+
+int ws_store_load_box(ws_store *st, ws_map *m, int which, const int32_t lo[3], const int32_t hi[3])
+{
+  return store_box(st, m, which, lo, hi, false, "ws_store_load_box");
+}
+
+int ws_shift_device(ws_map *m, ws_store *st, const int32_t new_pos[3])
+{
+  WS_TRY(store_args(st, m, WS_MAP_AVG, "ws_shift_device"));
+  if (!new_pos) return invalid("ws_shift_device: new_pos is NULL");
+  std::unique_lock<std::mutex> lock(st->mu, std::defer_lock); // taken in ready(), after the refusals, and held to the end of the call
+  ws_shift_plan_t plan;
+  std::set<StoreKey> fresh; // the chunks this call has created
+  hipStream_t s = m->ctx->stream;
+  const int rc = run_shift(
+      m, new_pos, "ws_shift_device", ": a shift of this map is in flight (ws_shift_end)", plan,
+      [&]() -> int {
+        lock.lock();
+        for (QueryTimer &t : st->timer) WS_TRY(t.arm());
+        // every chunk the leaving slabs of ALL axes create, before the first launch: a call that cannot get them changes nothing
+        std::set<StoreKey> missing;
+        for (int i = 0; i < plan.n; ++i) store_missing(st, plan.leave_lo[i], plan.leave_hi[i], missing);
+        WS_TRY(store_make_room(st, missing.size(), "ws_shift_device"));
+        store_admit(st, missing);
+        fresh.swap(missing);
+        return WS_OK;
+      },
+      [&](int i, const MapParams &par) -> int {
+        st->timer[i].mark(0, s);
+        const int rc_save = store_enqueue(st, m, par, WS_MAP_AVG, plan.leave_lo[i], plan.leave_hi[i], true);
+        st->timer[i].mark(1, s);
+        if (rc_save != WS_OK) st->timer[i].mark(2, s); // the step ends here, its load is never enqueued: close its second interval too
+        return rc_save;
+      },
+      [&](int i, const MapParams &par) -> int {
+        const int rc_load = store_enqueue(st, m, par, WS_MAP_AVG, plan.enter_lo[i], plan.enter_hi[i], false);
+        st->timer[i].mark(2, s);
+        return rc_load;
+      },
+      []() -> int { return WS_OK; });
+  if (rc != WS_OK) store_evict(st, fresh); // (after a refusal, which holds no lock, `fresh` is empty)
+  return rc;
+}
+
+int ws_store_chunks_of_box(const int32_t lo[3], const int32_t hi[3], int32_t *keys, size_t capacity, size_t *n_out)
+{
+  if (!lo || !hi || (!keys && capacity)) return invalid("ws_store_chunks_of_box: bad argument");
+  for (int k = 0; k < 3; ++k)
+    if (hi[k] < lo[k]) return invalid("ws_store_chunks_of_box: hi < lo");
+  const ChunkRange cr(lo, hi);
+  for (size_t i = 0; i < cr.n && i < capacity; ++i)
+  {
+    const StoreKey key = cr.key(i); // x major, z fastest: ascending (cx, cy, cz)
+    for (int k = 0; k < 3; ++k) keys[3 * i + k] = key[k];
+  }
+  if (n_out) *n_out = cr.n;
+  return WS_OK;
+}
+
+int ws_debug_store_timing(ws_store *st, int32_t enable, float ms_out[2])
+{
+  if (!st) return invalid("ws_debug_store_timing: store is NULL");
+  std::lock_guard<std::mutex> lock(st->mu);
+  static const int pairs[2][2] = {{0, 1}, {1, 2}};
+  float sum[2] = {0.f, 0.f};
+  for (QueryTimer &t : st->timer)
+  {
+    float ms[2] = {0.f, 0.f};
+    WS_TRY(t.read(ms_out ? ms : nullptr, pairs, 2, st->ctx->stream));
+    sum[0] += ms[0], sum[1] += ms[1];
+    t.set(enable);
+  }
+  if (ms_out) ms_out[0] = sum[0], ms_out[1] = sum[1];
+  return WS_OK;
+}
+
+// ---- the mesh, the ray cast and the distance field of the store: the rules and the host flow of ws_map_mesh, ws_map_raycast and
+// ws_map_distance over the chunks, store_mesh.hip, store_raycast.hip and store_distance.hip (the semantics are stated in warpsense_hip.h)
+namespace
+{
+// The box of a query, into l and h.  First the refusal of a box whose hi < lo, in the name of the entry point; then the store's lock,
+// into `lock` for the rest of the call; then the box: the call's, or without one all of int32 where `everything` (a ray cast), else
+// the bounding box of the present chunks (keys are floor(int32 / 64): 64 k + 63 fits), which leaves l > h in an empty store.
+// (ws_store_raycast calls this among its argument checks: its later refusals return with the lock held until then.)
+int store_query_box(ws_store *st, const char *name, const int32_t lo[3], const int32_t hi[3], bool everything, std::unique_lock<std::mutex> &lock, int32_t l[3],
+                    int32_t h[3])
+{
+  for (int k = 0; k < 3 && lo; ++k)
+    if (hi[k] < lo[k]) return invalid(std::string(name) + ": hi < lo");
+  lock = std::unique_lock<std::mutex>(st->mu);
+  for (int k = 0; k < 3; ++k) l[k] = lo ? lo[k] : everything ? INT32_MIN : INT32_MAX, h[k] = lo ? hi[k] : everything ? INT32_MAX : INT32_MIN;
+  if (!lo && !everything)
+    for (const auto &kv : st->dir)
+      for (int k = 0; k < 3; ++k) l[k] = std::min(l[k], kv.first[k] * STORE_CS), h[k] = std::max(h[k], kv.first[k] * STORE_CS + STORE_CS - 1);
+  return WS_OK;
+}
+
+// The written chunks a query lists, {cx, cy, cz, slot} ascending like the directory: those the box overlaps, or without a box
+// (lo == NULL) all of them.  The directory is ordered by cx first and only the keys of the box's cx range are visited: nothing here
+// follows the volume of the box.
+void store_list(const ws_store *st, const int32_t *lo, const int32_t *hi, std::vector<StoreRaySlot> &listed)
+{
+  const auto put = [&](const StoreKey &key, const ws_store::Entry &e) { listed.push_back(StoreRaySlot{key[0], key[1], key[2], e.slot}); };
+  listed.clear();
+  if (!lo)
+  {
+    for (const auto &kv : st->dir)
+      if (kv.second.written) put(kv.first, kv.second);
+    return;
+  }
+  const ChunkRange cr(lo, hi);
+  for (auto it = st->dir.lower_bound(StoreKey{cr.c0[0], INT32_MIN, INT32_MIN}); it != st->dir.end() && it->first[0] - cr.c0[0] < cr.nc[0]; ++it)
+  {
+    bool in = it->second.written;
+    for (int k = 1; k < 3; ++k) in = in && it->first[k] >= cr.c0[k] && it->first[k] - cr.c0[k] < cr.nc[k];
+    if (in) put(it->first, it->second);
+  }
+}
+
+// The lookup of the listed chunks (store_ray_table_fill) in the pinned table of a ray cast or a distance call: its places, and the
+// fill.  A table that is too small is replaced with its device twin: the caller has synchronised the stream then.
+size_t store_lookup_places(size_t n) { return n ? store_ray_table_slots(n) : 0; }
+int store_lookup_fill(HostBlock &host, DevBuf &dev, const std::vector<StoreRaySlot> &listed)
+{
+  const size_t places = store_lookup_places(listed.size());
+  if (places > host.cap)
+  {
+    WS_TRY(host.alloc(places, sizeof(StoreRaySlot), HostBlock::PINNED));
+    WS_TRY(dev.alloc(places, sizeof(StoreRaySlot)));
+  }
+  if (!listed.empty()) store_ray_table_fill(listed.data(), listed.size(), host.as<StoreRaySlot>());
+  return WS_OK;
+}
+
+// A store call waits for the stream even after a failed enqueue (whose error it reports): the pinned table of the call must be free
+// again when the call returns.
+int store_enqueued(const ws_store *st, int rc)
+{
+  if (rc != WS_OK) (void)hipStreamSynchronize(st->ctx->stream);
+  return rc;
+}
+
+// The tables of a mesh call over the n listed chunks (0 < n < 2^19), into st->mesh.table_host: per chunk the four counts that place
+// its 4096 words in world order, its key and slot, and the list positions of its 26 neighbours.  Everything is O(n log n).
+int store_mesh_tables(ws_store *st, const std::vector<StoreRaySlot> &listed)
+{
+  const size_t n = listed.size();
+  if (store_mesh_table_bytes(n) > st->mesh.table_host.cap)
+  {
+    WS_HIP(hipStreamSynchronize(st->ctx->stream));
+    const size_t want = store_mesh_table_bytes(n + n / 8);
+    WS_TRY(st->mesh.table_host.alloc(want, 1, HostBlock::PINNED));
+    WS_TRY(st->mesh.table_dev.alloc(want, 1));
+  }
+  uint32_t *grp = st->mesh.table_host.as<uint32_t>();
+  uint32_t *nb = grp + 8 * n;
+  std::memcpy(grp + 4 * n, listed.data(), n * sizeof(StoreRaySlot)); // {cx, cy, cz, slot} per chunk
+  for (size_t b = 0; b < n;) // the chunks of one cx: [b, e)
+  {
+    size_t e = b;
+    while (e < n && listed[e].cx == listed[b].cx) ++e;
+    for (size_t p = b; p < e;) // the chunks of one (cx, cy): [p, q)
+    {
+      size_t q = p;
+      while (q < e && listed[q].cy == listed[p].cy) ++q;
+      for (size_t i = p; i < q; ++i)
+        grp[4 * i + 0] = (uint32_t)b, grp[4 * i + 1] = (uint32_t)(e - b), grp[4 * i + 2] = (uint32_t)(p - b), grp[4 * i + 3] = (uint32_t)(q - p);
+      p = q;
+    }
+    b = e;
+  }
+  const auto before = [](const StoreRaySlot &e, const StoreKey &k) { return StoreKey{e.cx, e.cy, e.cz} < k; };
+  for (size_t i = 0; i < n; ++i)
+    for (int c = 0; c < 27; ++c)
+    {
+      // (keys are floor(int32 / 64): a step of one cannot overflow)
+      const StoreKey k = {listed[i].cx + c / 9 - 1, listed[i].cy + c / 3 % 3 - 1, listed[i].cz + c % 3 - 1};
+      const auto it = std::lower_bound(listed.begin(), listed.end(), k, before);
+      const bool found = it != listed.end() && it->cx == k[0] && it->cy == k[1] && it->cz == k[2];
+      nb[27 * i + c] = found ? (uint32_t)(it - listed.begin()) : 0xffffffffu;
+    }
+  return WS_OK;
+}
+} // namespace
+
+int ws_store_mesh(ws_store *st, const int32_t lo[3], const int32_t hi[3], int32_t map_resolution, uint32_t flags, size_t *n_vertices, size_t *n_faces)
+{
+  if (!st || (flags & ~WS_MESH_ANY_WEIGHT) || ((lo == nullptr) != (hi == nullptr)) || map_resolution <= 0) return invalid("ws_store_mesh: bad argument");
+  std::unique_lock<std::mutex> lock;
+  StoreMeshCall c;
+  WS_TRY(store_query_box(st, "ws_store_mesh", lo, hi, false, lock, c.lo, c.hi));
+  ws_store::Mesh &q = st->mesh;
+  WS_TRY(q.timer.arm());
+  if (c.lo[0] > c.hi[0]) return mesh_publish(q, 0, 0, n_vertices, n_faces); // no box and no chunk
+  WS_TRY(mesh_corners_fit(c.lo, c.hi, map_resolution, "ws_store_mesh"));
+  if (c.hi[0] == c.lo[0] || c.hi[1] == c.lo[1] || c.hi[2] == c.lo[2]) return mesh_publish(q, 0, 0, n_vertices, n_faces); // one voxel thick along an axis: no cells
+  std::vector<StoreRaySlot> listed;
+  store_list(st, c.lo, c.hi, listed);
+  if (listed.empty()) return mesh_publish(q, 0, 0, n_vertices, n_faces); // the box meets no present chunk
+  if (listed.size() >= (1u << 19)) return range_error("ws_store_mesh", ": the box overlaps 2^19 present chunks or more (4096 words each must stay below 2^31)");
+  WS_TRY(store_mesh_tables(st, listed));
+  c.n_chunks = (uint32_t)listed.size();
+  c.res = map_resolution;
+  c.flags = flags;
+  return mesh_run(
+      q, st->ctx->stream, "ws_store_mesh", (uint64_t)c.n_chunks * 4096u, n_vertices, n_faces, [&] { return store_enqueued(st, launch_store_mesh_count(st, q, c)); },
+      [&] { return store_enqueued(st, launch_store_mesh_emit(st, q, c)); });
+}
+
+const void *ws_store_mesh_vertices_dev(const ws_store *st, size_t *n) { return mesh_vertices_dev(st ? &st->mesh : nullptr, n); }
+
+const uint32_t *ws_store_mesh_faces_dev(const ws_store *st, size_t *n) { return mesh_faces_dev(st ? &st->mesh : nullptr, n); }
+
+int ws_store_mesh_download(ws_store *st, void *vertices_host, uint32_t *faces_host, size_t cap_vertices, size_t cap_faces, size_t *n_vertices, size_t *n_faces)
+{
+  if (!st || !n_vertices || !n_faces) return invalid("ws_store_mesh_download: NULL argument");
+  std::lock_guard<std::mutex> lock(st->mu);
+  return mesh_download(st->mesh, st->ctx->stream, vertices_host, faces_host, cap_vertices, cap_faces, n_vertices, n_faces);
+}
+
+int ws_debug_store_mesh_timing(ws_store *st, int32_t enable, float ms_out[3])
+{
+  if (!st) return invalid("ws_debug_store_mesh_timing: store is NULL");
+  std::lock_guard<std::mutex> lock(st->mu);
+  return query_timing(st->ctx->stream, st->mesh.timer, enable, ms_out, MESH_PAIRS, 3);
+}
+
+static int store_raycast(ws_store *st, const int32_t lo[3], const int32_t hi[3], const int32_t origin[3], const int32_t *dirs, bool dirs_on_host, size_t n,
+                         int32_t max_range, int32_t res, uint32_t flags, size_t *n_hits)
+{
+  std::unique_lock<std::mutex> lock;
+  StoreRayCall c;
+  c.res = res;
+  WS_TRY(raycast_check("ws_store_raycast", !st || ((lo == nullptr) != (hi == nullptr)), origin, dirs, n, max_range, res, flags, [&] {
+    WS_TRY(store_query_box(st, "ws_store_raycast", lo, hi, true, lock, c.lo, c.hi));
+    return res <= 0 ? invalid("ws_store_raycast: map_resolution <= 0") : (int)WS_OK;
+  }));
+  ws_store::Ray &q = st->ray;
+  std::vector<StoreRaySlot> listed;
+  store_list(st, lo, hi, listed); // (without a box: every written chunk)
+  if (listed.size() >= (1u << 19)) return range_error("ws_store_raycast", ": the call lists 2^19 present chunks or more");
+  c.n_chunks = (uint32_t)listed.size();
+  // the live box: the bounding box of the listed chunks (keys are floor(int32 / 64): 64 k + 63 fits), cut to the box
+  for (int k = 0; k < 3; ++k) c.blo[k] = INT32_MAX, c.bhi[k] = INT32_MIN;
+  for (const StoreRaySlot &e : listed)
+  {
+    const int32_t key[3] = {e.cx, e.cy, e.cz};
+    for (int k = 0; k < 3; ++k) c.blo[k] = std::min(c.blo[k], key[k] * STORE_CS), c.bhi[k] = std::max(c.bhi[k], key[k] * STORE_CS + STORE_CS - 1);
+  }
+  for (int k = 0; k < 3; ++k) c.blo[k] = std::max(c.blo[k], c.lo[k]), c.bhi[k] = std::min(c.bhi[k], c.hi[k]);
+  // (no listed chunk: the call still launches and answers no-hit for every ray)
+  return raycast_run(
+      q, st->ctx->stream, dirs, dirs_on_host, n, flags, n_hits, store_lookup_places(listed.size()) > q.table_host.cap,
+      [&] { return store_lookup_fill(q.table_host, q.table_dev, listed); },
+      [&](const int32_t *dirs_dev) { return store_enqueued(st, launch_store_raycast(st, q, c, origin, dirs_dev, n, max_range, flags)); });
+}
+
+int ws_store_raycast(ws_store *st, const int32_t lo[3], const int32_t hi[3], const int32_t origin_mm[3], const int32_t *dirs_host, size_t n, int32_t max_range_mm,
+                     int32_t map_resolution, uint32_t flags, size_t *n_hits)
+{
+  return store_raycast(st, lo, hi, origin_mm, dirs_host, true, n, max_range_mm, map_resolution, flags, n_hits);
+}
+
+int ws_store_raycast_dev(ws_store *st, const int32_t lo[3], const int32_t hi[3], const int32_t origin_mm[3], const int32_t *dirs_dev, size_t n, int32_t max_range_mm,
+                         int32_t map_resolution, uint32_t flags, size_t *n_hits)
+{
+  return store_raycast(st, lo, hi, origin_mm, dirs_dev, false, n, max_range_mm, map_resolution, flags, n_hits);
+}
+
+const void *ws_store_raycast_records_dev(const ws_store *st, size_t *n) { return raycast_records_dev(st ? &st->ray : nullptr, n); }
+
+const int32_t *ws_store_raycast_gradient_dev(const ws_store *st, size_t *n) { return raycast_gradient_dev(st ? &st->ray : nullptr, n); }
+
+int ws_store_raycast_download(ws_store *st, void *records_host, int32_t *gradient_host, size_t capacity_rays, size_t *n_out)
+{
+  if (!st || !n_out) return invalid("ws_store_raycast_download: NULL argument");
+  std::lock_guard<std::mutex> lock(st->mu);
+  return raycast_download(st->ray, st->ctx->stream, "ws_store_raycast_download", "ws_store_raycast", records_host, gradient_host, capacity_rays, n_out);
+}
+
+int ws_debug_store_raycast_timing(ws_store *st, int32_t enable, float ms_out[3])
+{
+  if (!st) return invalid("ws_debug_store_raycast_timing: store is NULL");
+  std::lock_guard<std::mutex> lock(st->mu);
+  return query_timing(st->ctx->stream, st->ray.timer, enable, ms_out, RAY_PAIRS, 3);
+}
+
+// ---- the distance field of the store: the rules and the host flow of ws_map_distance over the chunks, store_distance.hip
+int ws_store_distance(ws_store *st, const int32_t lo[3], const int32_t hi[3], int32_t max_dist_vox, uint32_t flags, size_t *n_sites)
+{
+  std::unique_lock<std::mutex> lock;
+  StoreDistCall c;
+  uint32_t ext[3];
+  size_t n = 0;
+  WS_TRY(distance_check(
+      "ws_store_distance", !st, lo, hi, max_dist_vox, flags,
+      [&](uint64_t e[3]) {
+        WS_TRY(store_query_box(st, "ws_store_distance", lo, hi, false, lock, c.lo, c.hi));
+        WS_TRY(st->dist.timer.arm());
+        if (c.lo[0] > c.hi[0]) return (int)WS_OK; // no box and no chunk: zero records
+        for (int k = 0; k < 3; ++k) e[k] = (uint64_t)((int64_t)c.hi[k] - (int64_t)c.lo[k]) + 1u;
+        return (int)WS_OK;
+      },
+      ext, &n));
+  ws_store::Dist &q = st->dist;
+  hipStream_t s = st->ctx->stream;
+  // the present chunks the box overlaps, and the z range they cover inside it
+  std::vector<StoreRaySlot> listed;
+  if (n) store_list(st, c.lo, c.hi, listed);
+  if (listed.size() >= (1u << 19)) return range_error("ws_store_distance", ": the box overlaps 2^19 present chunks or more");
+  c.n_chunks = (uint32_t)listed.size();
+  c.nx = ext[0], c.ny = ext[1];
+  c.zlo = 1, c.zhi = 0;
+  if (c.n_chunks)
+  {
+    c.zlo = INT32_MAX, c.zhi = INT32_MIN;
+    for (const StoreRaySlot &e : listed) c.zlo = std::min(c.zlo, e.cz * STORE_CS), c.zhi = std::max(c.zhi, e.cz * STORE_CS + STORE_CS - 1);
+    c.zlo = std::max(c.zlo, c.lo[2]), c.zhi = std::min(c.zhi, c.hi[2]);
+  }
+  return store_enqueued(st, distance_run(q, s, ext, max_dist_vox, flags, n, n_sites, [&] {
+    if (store_lookup_places(listed.size()) > q.table_host.cap) WS_HIP(hipStreamSynchronize(s));
+    WS_TRY(store_lookup_fill(q.table_host, q.table_dev, listed));
+    return launch_store_dist_classify(st, q, c, max_dist_vox, flags);
+  }));
+}
+
+const uint32_t *ws_store_distance_dev(const ws_store *st, size_t *n) { return distance_dev(st ? &st->dist : nullptr, n); }
+
+int ws_store_distance_download(ws_store *st, uint32_t *host, size_t capacity, size_t *n_out)
+{
+  if (!st || !n_out) return invalid("ws_store_distance_download: NULL argument");
+  std::lock_guard<std::mutex> lock(st->mu);
+  return distance_download(st->dist, st->ctx->stream, host, capacity, n_out);
+}
+
+int ws_debug_store_distance_timing(ws_store *st, int32_t enable, float ms_out[4])
+{
+  if (!st) return invalid("ws_debug_store_distance_timing: store is NULL");
+  std::lock_guard<std::mutex> lock(st->mu);
+  return query_timing(st->ctx->stream, st->dist.timer, enable, ms_out, DIST_PAIRS, 4);
+}
+
+int ws_debug_store_raycast_table(const int32_t *keys_slots, size_t n, int32_t *table, size_t capacity_places, size_t *n_places)
+{
+  if ((n && table && !keys_slots) || !n_places || n >= (1u << 19)) return invalid("ws_debug_store_raycast_table: bad argument");
+  *n_places = store_ray_table_slots(n);
+  if (!table) return WS_OK;
+  if (capacity_places < *n_places) return invalid("ws_debug_store_raycast_table: the table does not fit");
+  std::vector<StoreRaySlot> in(n), out(*n_places);
+  if (n) std::memcpy(in.data(), keys_slots, n * sizeof(StoreRaySlot));
+  store_ray_table_fill(in.data(), n, out.data());
+  std::memcpy(table, out.data(), out.size() * sizeof(StoreRaySlot));
+  return WS_OK;
+}
+
+uint32_t ws_debug_store_raycast_find(const int32_t *table, size_t n_places, const int32_t key[3])
+{
+  if (!table || !key || n_places < 2 || (n_places & (n_places - 1))) return STORE_ABSENT;
+  std::vector<StoreRaySlot> t(n_places);
+  std::memcpy(t.data(), table, n_places * sizeof(StoreRaySlot));
+  return store_ray_find(t.data(), (uint32_t)n_places - 1u, key[0], key[1], key[2]);
+}

@@ -40,7 +40,7 @@ __global__ __launch_bounds__(256) void store_copy_kernel(StoreArgs a)
   for (uint32_t c = blockIdx.y; c < a.n_chunks; c += gridDim.y)
   {
     const uint32_t word = a.table[c];
-    const bool absent = word == STORE_ABSENT; // (a load's table only: the host never puts it into a save's, store_enqueue in api.hip)
+    const bool absent = word == STORE_ABSENT; // (a load's table only: the host never puts it into a save's, store_enqueue in api_store.hip)
     const bool whole = SAVE && (word & STORE_NEW) != 0;
     uint32_t *chunk = nullptr;
     if (!absent)

@@ -2265,7 +2265,7 @@ int launch_reg_loop(ws_reg *r, const ws_map *m, int32_t res, uint32_t flags, con
   return WS_OK;
 }
 
-// host image of PeerBlock (api.hip fills it: the mailbox pointers are peer-mapped or local device addresses)
+// host image of PeerBlock (api_reg.hip fills it: the mailbox pointers are peer-mapped or local device addresses)
 size_t reg_peer_block_bytes() { return sizeof(PeerBlock); }
 void reg_peer_block_fill(void *host_image, void *const mailbox[8], int rank, int world)
 {

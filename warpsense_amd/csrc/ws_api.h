@@ -1,0 +1,222 @@
+// ws_api.h — what the host files of the C API (api_*.hip) share, and nothing else: the refusals, the map's settle-and-report
+// steps, the box rules, and the host cores that the queries of a map window (api_query.hip) and of the chunk store (api_store.hip)
+// both run.  What one file uses alone is static in that file.  Everything here is in namespace ws or a template: it mangles, so the
+// library exports no unprefixed C name beside the ws_* entry points (tests/test_abi_and_host.py holds that).
+#pragma once
+
+#include <algorithm>
+#include <string>
+
+#include "ws_internal.h"
+
+namespace ws
+{
+// ---- api_core.hip: the refusals (the text goes to the thread's last error), and the two things a call owes the context
+int invalid(const char *msg);
+int invalid(const std::string &msg);
+int range_error(const char *name, const char *what);
+void servers_leave(ws_context *ctx); // a resident server of ws_reg_iterate leaves the stream to whoever enqueues other work
+int ctx_take_errors(ws_context *ctx);
+// every entry point that takes a map looks at the verdict of the scan in flight first (settle_tsdf, tsdf_update.hip)
+#define WS_SETTLE(map_ptr)                                                   \
+  do                                                                         \
+  {                                                                          \
+    ws::servers_leave((map_ptr)->ctx);                                       \
+    const int rc_settle__ = ws::settle_tsdf(const_cast<ws_map *>(map_ptr));  \
+    if (rc_settle__ != WS_OK) return rc_settle__;                            \
+  } while (0)
+
+inline void copy3(int32_t dst[3], const int32_t src[3])
+{
+  dst[0] = src[0];
+  dst[1] = src[1];
+  dst[2] = src[2];
+}
+
+// ---- api_map.hip: the sticky device error word of a map, the box rules, the plan and the axis step of a shift
+int map_take_error(ws_map *m);
+int resolve_box(const ws_map *m, int which, const int32_t lo[3], const int32_t hi[3], bool allow_whole, const char *name, int32_t l[3], int32_t ext[3]);
+int plan_shift(const int32_t size[3], const int32_t pos0[3], const int32_t offset0[3], const int32_t new_pos[3], const char *name, ws_shift_plan_t *out);
+void move_axis(MapParams par[2], int axis, int32_t d);
+
+// ---- api_query.hip: the parts of the query cores that are no templates
+int query_timing(hipStream_t s, QueryTimer &t, int32_t enable, float *ms_out, const int (*pairs)[2], int n);
+int mesh_corners_fit(const int32_t lo[3], const int32_t hi[3], int32_t res, const char *name);
+int mesh_publish(MeshResult &q, size_t nv, size_t nf, size_t *n_vertices, size_t *n_faces);
+const void *mesh_vertices_dev(const MeshResult *q, size_t *n);
+const uint32_t *mesh_faces_dev(const MeshResult *q, size_t *n);
+int mesh_download(const MeshResult &q, hipStream_t s, void *vertices_host, uint32_t *faces_host, size_t cap_vertices, size_t cap_faces, size_t *n_vertices,
+                  size_t *n_faces);
+const void *raycast_records_dev(const RayResult *q, size_t *n);
+const int32_t *raycast_gradient_dev(const RayResult *q, size_t *n);
+int raycast_download(const RayResult &q, hipStream_t s, const char *name, const char *call, void *records_host, int32_t *gradient_host, size_t capacity_rays,
+                     size_t *n_out);
+const uint32_t *distance_dev(const DistResult *q, size_t *n);
+int distance_download(const DistResult &q, hipStream_t s, uint32_t *host, size_t capacity, size_t *n_out);
+// the event pairs of ws_debug_*_timing (QueryTimer::read)
+constexpr int MESH_PAIRS[3][2] = {{0, 1}, {1, 2}, {3, 4}}, RAY_PAIRS[3][2] = {{0, 1}, {1, 2}, {2, 3}}, DIST_PAIRS[4][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 4}};
+
+// ---- mesh, ray cast and distance field: one host core each for the window of a map (map_mesh.hip, map_raycast.hip, map_distance.hip)
+// and for the chunks of the store (store_mesh.hip, store_raycast.hip, store_distance.hip).  An entry point checks what is its own, takes
+// its lock and hands the shared flow its result holder, its stream and, as lambdas, the launchers of its source; `name` starts the
+// refusal texts.
+
+// The flow of a mesh call over `n_words` words (< 2^31), from "the old result is dropped" to the publish.  count() and emit() enqueue
+// the passes of the source and return at once; what a source owes its caller after a failed enqueue is theirs (store_enqueued).
+template <typename Count, typename Emit>
+int mesh_run(MeshResult &q, hipStream_t s, const char *name, uint64_t n_words, size_t *n_vertices, size_t *n_faces, Count count, Emit emit)
+{
+  mesh_publish(q, 0, 0, n_vertices, n_faces); // (whatever happens from here on, the old result is gone: its buffers may be replaced)
+  WS_TRY(q.total.alloc(2, false));
+  const size_t need = mesh_scratch_bytes(n_words);
+  if (need > q.scratch.cap)
+  {
+    WS_HIP(hipStreamSynchronize(s));
+    WS_TRY(q.scratch.grow(need, 1));
+  }
+  WS_TRY(count());
+  WS_HIP(hipStreamSynchronize(s)); // the one host read the call needs: the outputs are sized from the two totals
+  const unsigned long long nv = q.total.host[0], nq = q.total.host[1];
+  if (nv > 0xffffffffull) return range_error(name, ": more than 2^32 - 1 vertices");
+  WS_TRY(q.vert.grow((size_t)nv, 16));
+  WS_TRY(q.face.grow((size_t)nq * 2, 12));
+  if (nv)
+  {
+    WS_TRY(emit());
+    WS_HIP(hipStreamSynchronize(s));
+  }
+  return mesh_publish(q, (size_t)nv, (size_t)nq * 2, n_vertices, n_faces);
+}
+
+// The argument check of a ray cast.  `bad`: what the entry point found wrong with its own leading arguments; more(): its further
+// checks, which come before those of the ranges.
+template <typename More>
+int raycast_check(const char *name, bool bad, const int32_t *origin, const int32_t *dirs, size_t n, int32_t max_range, int32_t res, uint32_t flags, More more)
+{
+  const uint32_t known = WS_RAYCAST_ANY_WEIGHT | WS_RAYCAST_GRADIENT | WS_RAYCAST_TARGETS;
+  if (bad || (flags & ~known) || !origin || (n && !dirs)) return invalid(std::string(name) + ": bad argument");
+  WS_TRY(more());
+  if (max_range <= 0) return invalid(std::string(name) + ": max_range_mm <= 0");
+  if (res > 1024) return range_error(name, ": the resolution must not exceed 1024 mm (the interpolant is carried times res^3 in 64 bits)");
+  if (n > ((size_t)1 << 27)) return range_error(name, ": more than 2^27 rays");
+  for (int k = 0; k < 3; ++k)
+  {
+    const int64_t o = origin[k];
+    if ((o < 0 ? -o : o) + (int64_t)max_range + 2 * (int64_t)res > (int64_t)INT32_MAX) return range_error(name, ": |origin| + max_range + 2 res does not fit int32");
+  }
+  return WS_OK;
+}
+
+// The flow of a ray cast whose arguments have passed raycast_check: arm, drop the old result, grow, upload the directions, launch,
+// synchronise, publish.  own_room: the source has buffers of its own that must grow; prepare() grows them (the stream has been
+// synchronised then) and fills them; launch(directions on the device) enqueues the passes of the source, like count() of mesh_run.
+template <typename Prepare, typename Launch>
+int raycast_run(RayResult &q, hipStream_t s, const int32_t *dirs, bool dirs_on_host, size_t n, uint32_t flags, size_t *n_hits, bool own_room, Prepare prepare,
+                Launch launch)
+{
+  WS_TRY(q.timer.arm());
+  if (n_hits) *n_hits = 0;
+  q.n = 0; // (whatever happens from here on, the old result is gone: its buffers may be replaced)
+  q.has_grad = false;
+  if (n == 0) return WS_OK;
+  const bool grad = (flags & WS_RAYCAST_GRADIENT) != 0;
+  WS_TRY(q.hits.alloc(1));
+  if (n > q.rec.cap || (grad && n > q.grad.cap) || (dirs_on_host && n > q.dirs.cap) || own_room)
+  {
+    WS_HIP(hipStreamSynchronize(s));
+    WS_TRY(q.rec.grow(n, 16));
+    if (grad) WS_TRY(q.grad.grow(n, 3 * sizeof(int32_t)));
+    if (dirs_on_host) WS_TRY(q.dirs.grow(n, 3 * sizeof(int32_t)));
+  }
+  WS_TRY(prepare());
+  q.timer.mark(0, s);
+  if (dirs_on_host)
+  {
+    WS_HIP(hipMemcpyAsync(q.dirs.p, dirs, n * 3 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    dirs = static_cast<const int32_t *>(q.dirs.p);
+  }
+  WS_TRY(launch(dirs));
+  WS_HIP(hipStreamSynchronize(s));
+  q.n = n;
+  q.has_grad = grad;
+  if (n_hits) *n_hits = (size_t)*q.hits.host;
+  return WS_OK;
+}
+
+// The argument check of a distance call.  `bad`: what the entry point found wrong with its own leading arguments; box(e): its lock and
+// its box, which come behind the checks of the flags and of R -- the extents in 64 bits, all zero for "nothing to do".  ext and *n
+// receive the extents the passes take and the number of records.
+template <typename Box>
+int distance_check(const char *name, bool bad, const int32_t *lo, const int32_t *hi, int32_t R, uint32_t flags, Box box, uint32_t ext[3], size_t *n)
+{
+  const uint32_t known = WS_DISTANCE_ANY_WEIGHT | WS_DISTANCE_UNKNOWN_OCCUPIED | WS_DISTANCE_COLUMNS;
+  if (bad || (flags & ~known) || ((lo == nullptr) != (hi == nullptr))) return invalid(std::string(name) + ": bad argument");
+  if (R < 1 || R > 255) return range_error(name, ": max_dist_vox must be 1 .. 255 (its square is carried in 16 bits)");
+  uint64_t e[3] = {0, 0, 0};
+  WS_TRY(box(e));
+  const bool columns = (flags & WS_DISTANCE_COLUMNS) != 0;
+  // (every extent is at most 2^32; one of 2^32 is too many records by itself, and the products of the others fit 64 bits)
+  const uint64_t n_cols = e[0] > 0xffffffffull || e[1] > 0xffffffffull ? ~0ull : e[0] * e[1];
+  if (n_cols > 0xffffffffull || (!columns && n_cols * e[2] > 0xffffffffull)) return range_error(name, ": more than 2^32 - 1 records");
+  if ((columns ? e[1] : e[2]) > (uint64_t)DIST_MAX_LINE) return range_error(name, ": more than 16 776 960 voxels along the fastest axis of the records");
+  for (int k = 0; k < 3; ++k) ext[k] = (uint32_t)std::min<uint64_t>(e[k], 0xffffffffull); // (under COLUMNS the passes do not read ext[2])
+  *n = (size_t)(columns ? n_cols : n_cols * e[2]);
+  return WS_OK;
+}
+
+// The flow of a distance call whose arguments have passed distance_check, from "the old result is dropped" to the publish.  pass0()
+// enqueues the source's classification into q.rec and the first plane of q.plane and returns at once.
+template <typename Pass0>
+int distance_run(DistResult &q, hipStream_t s, const uint32_t ext[3], int32_t R, uint32_t flags, size_t n, size_t *n_sites, Pass0 pass0)
+{
+  if (n_sites) *n_sites = 0;
+  q.n = 0; // (whatever happens from here on, the old result is gone: its buffers may be replaced)
+  if (n == 0) return WS_OK;
+  WS_TRY(q.sites.alloc(1));
+  if (n > q.rec.cap || n > q.plane.cap)
+  {
+    WS_HIP(hipStreamSynchronize(s));
+    WS_TRY(q.rec.grow(n, sizeof(uint32_t)));
+    WS_TRY(q.plane.grow(n, 2 * sizeof(uint16_t))); // both planes
+  }
+  WS_TRY(pass0());
+  WS_TRY(dist_passes(s, q.timer, q.rec.as<uint32_t>(), q.plane.as<uint16_t>(), ext, R, flags));
+  WS_TRY(q.sites.fetch(s));
+  WS_HIP(hipStreamSynchronize(s));
+  q.n = n;
+  if (n_sites) *n_sites = (size_t)*q.sites.host;
+  return WS_OK;
+}
+
+// ---- map shift: one shift of both maps' windows, for ws_shift_begin (api_map.hip) and ws_shift_device (api_store.hip), which
+// differ in what happens to a slab that leaves and to one that enters.  `name` is the entry point and `open_text` its words for a
+// ticket in flight.  After the shared refusals and the plan (into `plan`): ready() before the first launch; per step leave(i, par),
+// the axis step, enter(i, par), on a COPY of the parameters (the box kernels take them by value); done() behind the last step.  The
+// copy is committed only when all of it has been enqueued: the first error is returned with the host's view of both maps as it was
+// (ADVICE r2).
+template <class Ready, class Leave, class Enter, class Done>
+int run_shift(ws_map *m, const int32_t new_pos[3], const char *name, const char *open_text, ws_shift_plan_t &plan, Ready ready, Leave leave,
+              Enter enter, Done done)
+{
+  WS_SETTLE(m);
+  if (m->shift_open) return invalid((std::string(name) + open_text).c_str());
+  // only new_map's WINDOW moves (DeviceMapMemWrapper::update_params), which is right iff it holds (tau, 0) everywhere -- not between
+  // ws_tsdf_scatter_dev and ws_tsdf_integrate, nor for a map created from non-default host data that has not been integrated yet
+  if (!m->new_is_default)
+    return invalid((std::string(name) + ": new_map holds entries that have not been integrated (ws_tsdf_integrate first)").c_str());
+  const MapParams &p0 = m->par[WS_MAP_AVG];
+  WS_TRY(plan_shift(p0.size, p0.pos, p0.offset, new_pos, name, &plan));
+  WS_TRY(ready());
+  MapParams par[2] = {m->par[0], m->par[1]};
+  int rc = WS_OK;
+  for (int i = 0; i < plan.n && rc == WS_OK; ++i)
+  {
+    rc = leave(i, par[WS_MAP_AVG]);
+    move_axis(par, plan.axis[i], plan.d[i]);
+    if (rc == WS_OK) rc = enter(i, par[WS_MAP_AVG]);
+  }
+  if (rc == WS_OK) rc = done();
+  if (rc == WS_OK) m->par[0] = par[0], m->par[1] = par[1];
+  return rc;
+}
+} // namespace ws

@@ -368,7 +368,7 @@ struct QueryTimer
 
 // ---- what a mesh call and a ray-cast call leave behind, whatever they ran over: the window of a map (ws_map::Mesh, ws_map::Raycast)
 // or the chunks of the store (ws_store::Mesh, ws_store::Ray).  Everything is allocated on first use and grown on demand; the one flow
-// of each query (mesh_run, raycast_run in api.hip) and the launchers of the four .hip files take these, not their owners.
+// of each query (mesh_run, raycast_run in ws_api.h) and the launchers of the four .hip files take these, not their owners.
 struct MeshResult
 {
   QueryTimer timer;                    // 0 count passes 1 scans 2, 3 emit passes 4
@@ -387,7 +387,7 @@ struct RayResult
   bool has_grad = false;               // the last call also wrote `grad`
   void release() { timer.release(), hits.release(); for (DevBuf *b : {&dirs, &rec, &grad}) b->release(); }
 };
-// ... and a distance call (ws_map::Distance, ws_store::Dist; the one flow is distance_run in api.hip)
+// ... and a distance call (ws_map::Distance, ws_store::Dist; the one flow is distance_run in ws_api.h)
 struct DistResult
 {
   QueryTimer timer;                    // 0 pass 0, 1 x 2 y 3 z 4
@@ -709,7 +709,7 @@ int launch_tsdf_scatter(ws_map *m, const int32_t *xyz_dev, size_t n, const int32
 int settle_tsdf(ws_map *m); // the verdict of the scan in flight (repeats an aborted scan); every entry point that takes a map calls it first
 size_t ray_setup_bytes();
 int launch_scatter_prep(ws_map *m);
-int resize_records(ws_map *m, uint64_t sub_chunks); // api.hip: (re)allocate the pool (waits for the stream)
+int resize_records(ws_map *m, uint64_t sub_chunks); // api_map.hip: (re)allocate the pool (waits for the stream)
 uint64_t subs_for_scan(const ws_map *m, uint64_t need_records, uint64_t n_points); // sub-chunks the pool should hold for a scan of that record bound
 int launch_tsdf_integrate(ws_map *m);
 int launch_tsdf_stats(ws_map *m); // fills the last_* statistics of TsdfCounters from the per-workgroup slots
@@ -828,7 +828,7 @@ void reg_server_mail_stop(void *mail, uint32_t launch_id);
 int reg_server_mail_answer(const void *mail, uint32_t seq, int64_t sums[44]);
 int reg_server_mail_selftest();
 uint32_t reg_server_mail_exited(const void *mail);
-// the bin rule of a sweep (ws_sweep_t, checked by api.hip) and its pose table on the device
+// the bin rule of a sweep (ws_sweep_t, checked by api_scan.hip) and its pose table on the device
 struct PreSweep
 {
   const int32_t *table; // [k][16] to_int_mat(poses[b]), column-major, one 64-byte row per bin
@@ -856,4 +856,5 @@ int reg_default_blocks();
 int reg_loop_supported(int device);
 int launch_solve6_test(ws_context *ctx, const double *A_dev, const double *b_dev, size_t n, double *x_dev, int32_t *status_dev);
 size_t reg_barrier_bytes();
+size_t reg_partials_bytes();
 } // namespace ws
