@@ -1,6 +1,6 @@
 // barrier_bench.hip — how fast can 256 resident workgroups (one per CU, 8 XCDs) meet on MI355X?
 // Build + run on the GPU box:  hipcc --offload-arch=gfx950 -O3 tools/barrier_bench.hip -o /tmp/bb && /tmp/bb
-// Used to choose the grid barrier of reg_loop_kernel (warpsense_amd/csrc/registration.hip); numbers in DESIGN.md.
+// Used to choose the grid barrier of reg_loop_kernel (warpsense_amd/csrc/reg_loop.hip, the exchange in reg_exchange.h); numbers in DESIGN.md.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdint>

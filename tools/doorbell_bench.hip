@@ -1,5 +1,5 @@
 // doorbell_bench.hip -- what a host <-> resident-kernel round trip costs on this box (round 6: the resident server behind
-// ws_reg_iterate, registration.hip: reg_server_kernel).  The host writes a request number, a resident kernel sees it and answers
+// ws_reg_iterate, reg_server.hip: reg_server_kernel).  The host writes a request number, a resident kernel sees it and answers
 // by writing the number into host-mapped memory, the host spins on that.  Variants:
 //   bell in host-mapped memory (the GPU polls over the fabric)  |  bell in fine-grained DEVICE memory written by the host through the BAR
 //   one workgroup answers  |  workgroup 0 forwards the bell through device memory and the LAST of G workgroups to see it answers

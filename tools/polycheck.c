@@ -1,4 +1,4 @@
-/* Validation of the sine / cosine polynomials of gn_step (registration.hip) against the C library: what the Gauss-Newton update
+/* Validation of the sine / cosine polynomials of gn_step (reg_gn.h) against the C library: what the Gauss-Newton update
  * uses are (float)sin(theta) and (float)(1 - cos(theta)); both polynomial forms (separate multiply/add, fused multiply-add) must give
  * the same two floats as libm for every angle below 0.25 rad.   gcc -O2 -ffp-contract=off tools/polycheck.c -lm && ./a.out */
 #include <math.h>

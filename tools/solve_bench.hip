@@ -1,5 +1,5 @@
 // solve_bench.hip — how long does one wave need for the 6x6 solve of the Gauss-Newton update?  Variants of solve6_wave
-// (warpsense_amd/csrc/registration.hip) timed as a dependent chain on one wave.
+// (warpsense_amd/csrc/reg_gn.h) timed as a dependent chain on one wave.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math tools/solve_bench.hip -o /tmp/sb && /tmp/sb
 #include <hip/hip_runtime.h>
 #include <cstdio>

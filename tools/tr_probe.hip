@@ -2,7 +2,7 @@
 #include <cstdio>
 #include <cstdint>
 typedef int v2i __attribute__((ext_vector_type(2)));
-// What does ds_read_b64_tr_b8 (gfx950) return?  Probe behind mfma_consume (registration.hip): hipcc --offload-arch=gfx950 -O2 tools/tr_probe.hip
+// What does ds_read_b64_tr_b8 (gfx950) return?  Probe behind mfma_consume (reg_points.h): hipcc --offload-arch=gfx950 -O2 tools/tr_probe.hip
 // LDS image: 64 "points" x 48 bytes (32 used); byte value at (point p, rowbyte r) = we store 16-bit id in two planes
 __global__ void probe(uint32_t *out_lo, uint32_t *out_hi, int plane)
 {

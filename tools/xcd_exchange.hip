@@ -83,7 +83,7 @@ __global__ __launch_bounds__(THREADS) void exch_kernel(uint64_t *accum /* [2][NG
     {
       const uint32_t half = lane < 32 ? (uint32_t)(uint64_t)v : (uint32_t)((uint64_t)v >> 32);
       add_word<SCOPE>(&buf[(size_t)g * 64 + lane], (1ull << 56) | half);
-      // first poll a little later (registration.hip: polling at once delays the very adds it waits for)
+      // first poll a little later (reg_exchange.h: polling at once delays the very adds it waits for)
       for (int s = 0; s < first_sleep; ++s) __builtin_amdgcn_s_sleep(1);
       uint64_t w[NG];
       int guard = 0;

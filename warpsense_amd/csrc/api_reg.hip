@@ -1,6 +1,7 @@
 // api_reg.hip — registration (ws_reg_*, ws_register_cloud*): create and prepare, one iteration through the resident server or one
 // launch, the resident loop with its launch-per-iteration route, many start poses in one launch, the peers of a multi-GPU loop, and
-// the test entries of all of them; the kernels and their launchers are in registration.hip.
+// the test entries of all of them; the kernels and their launchers are in reg_loop.hip,
+// reg_launches.hip, reg_server.hip and reg_batch.hip.
 #include <algorithm>
 #include <atomic>
 #include <chrono>

@@ -79,7 +79,7 @@ struct ScatterArgs
   TsdfCounters *counters;
   uint32_t *status; // host-mapped: [0] sticky error bits, [4..5] record bound of the scan in flight, [6] its sequence number, [8] / [9] see ws_map::status_host
 };
-// 264 bytes of kernel arguments instead of 256 cost reg_loop_kernel 30 % (registration.hip); the same bound here
+// 264 bytes of kernel arguments instead of 256 cost reg_loop_kernel 30 % (reg_loop.hip); the same bound here
 static_assert(sizeof(ScatterArgs) <= 256, "ScatterArgs: more than 256 bytes of kernel arguments");
 
 #define REC_S(a) ((int32_t)((a).rec_fmt & 0xffu))

@@ -548,7 +548,7 @@ struct ws_reg
   ws::DevBuf pass_arrived;            // uint32: arrival counter of reg_pass_kernel (zero between launches, which are ordered on the stream)
   ws::HostBlock iter_host;            // int64, mapped: the 44 sums of ws_reg_iterate, then the call's sequence number
   uint32_t iter_seq = 0;
-  // the resident server behind ws_reg_iterate (reg_server_kernel, registration.hip): requests travel through host-mapped memory
+  // the resident server behind ws_reg_iterate (reg_server_kernel, reg_server.hip): requests travel through host-mapped memory
   ws::HostBlock srv_mail;             // ServerMail, mapped
   ws::DevBuf srv_ctl;                 // uint32: device words of the server (bell, pose, arrival counters), zero at creation
   std::atomic<uint32_t> srv_launch{0};   // id of the last server launched (0: none yet); it lives until ServerMail::exited says so
@@ -814,20 +814,6 @@ struct StoreDistCall
 };
 int launch_store_dist_classify(ws_store *st, ws_store::Dist &q, const StoreDistCall &c, int32_t R, uint32_t flags);
 
-int launch_reg_iteration(ws_reg *r, const ws_map *m, int32_t res, uint32_t flags, int32_t k);
-// reg_pass_kernel over points [first, first + count): from the newest state (first the update from `sums` if `apply`) into `sums`;
-// or, given a pose T, without a state into host-mapped `sums`, then `seq`
-int launch_reg_pass(ws_reg *r, const ws_map *m, int32_t res, uint32_t flags, size_t first, size_t count, int64_t *sums, int apply,
-                    const float *T = nullptr, uint32_t seq = 0);
-int launch_reg_solve(ws_reg *r, const int64_t *sums_dev);
-int launch_reg_server(ws_reg *r, const ws_map *m, int32_t res, uint32_t flags, uint32_t launch_id, uint32_t served, uint32_t idle_us);
-size_t reg_server_mail_bytes();
-size_t reg_server_ctl_bytes();
-void reg_server_mail_write(void *mail, const float T[16], uint32_t seq);
-void reg_server_mail_stop(void *mail, uint32_t launch_id);
-int reg_server_mail_answer(const void *mail, uint32_t seq, int64_t sums[44]);
-int reg_server_mail_selftest();
-uint32_t reg_server_mail_exited(const void *mail);
 // the bin rule of a sweep (ws_sweep_t, checked by api_scan.hip) and its pose table on the device
 struct PreSweep
 {
@@ -841,20 +827,39 @@ struct PreSweep
 };
 int launch_scan_preprocess(ws_scan *sc, const float *xyz_dev, size_t n, size_t stride, const int32_t M[16], int32_t res, const PreSweep *sweep = nullptr);
 size_t pre_table_slots(size_t max_points);
+
+// ---- registration: the kernels and their launchers, one file per route (the routes: head of reg_loop.hip)
+// reg_loop.hip: the resident loop, alone or with peers
 int launch_reg_loop(ws_reg *r, const ws_map *m, int32_t res, uint32_t flags, const ws::GnCore &init, bool peers = false, size_t first = 0, size_t count = 0);
-// reg_batch_kernel: k workgroups, one Gauss-Newton loop each, from the start records in ws_reg::batch into its result records
-int launch_reg_batch(ws_reg *r, const ws_map *m, int32_t res, uint32_t flags, size_t k, int32_t max_iterations, float it_weight_gradient, float epsilon);
-size_t reg_batch_record_bytes(); // start + result record of one hypothesis
-void reg_batch_write(void *records, size_t k, const float T[16]);
-void reg_batch_read(const void *records, size_t n, size_t k, float T[16], int32_t *iterations, int32_t *e, int32_t *c);
-int reg_batch_default_variant();
+int reg_loop_supported(int device);
+size_t reg_barrier_bytes();
 size_t reg_peer_block_bytes();
 void reg_peer_block_fill(void *host_image, void *const mailbox[8], int rank, int world);
 size_t reg_mailbox_bytes();
 int reg_groups();
 int reg_default_blocks();
-int reg_loop_supported(int device);
+// reg_launches.hip: one launch per iteration, one launch per call, the solve alone
+int launch_reg_iteration(ws_reg *r, const ws_map *m, int32_t res, uint32_t flags, int32_t k);
+// reg_pass_kernel over points [first, first + count): from the newest state (first the update from `sums` if `apply`) into `sums`;
+// or, given a pose T, without a state into host-mapped `sums`, then `seq`
+int launch_reg_pass(ws_reg *r, const ws_map *m, int32_t res, uint32_t flags, size_t first, size_t count, int64_t *sums, int apply,
+                    const float *T = nullptr, uint32_t seq = 0);
+int launch_reg_solve(ws_reg *r, const int64_t *sums_dev);
 int launch_solve6_test(ws_context *ctx, const double *A_dev, const double *b_dev, size_t n, double *x_dev, int32_t *status_dev);
-size_t reg_barrier_bytes();
 size_t reg_partials_bytes();
+// reg_server.hip: the resident server and the host's half of its mailbox
+int launch_reg_server(ws_reg *r, const ws_map *m, int32_t res, uint32_t flags, uint32_t launch_id, uint32_t served, uint32_t idle_us);
+size_t reg_server_mail_bytes();
+size_t reg_server_ctl_bytes();
+void reg_server_mail_write(void *mail, const float T[16], uint32_t seq);
+void reg_server_mail_stop(void *mail, uint32_t launch_id);
+int reg_server_mail_answer(const void *mail, uint32_t seq, int64_t sums[44]);
+int reg_server_mail_selftest();
+uint32_t reg_server_mail_exited(const void *mail);
+// reg_batch.hip: reg_batch_kernel, k workgroups, one Gauss-Newton loop each, from the start records in ws_reg::batch into its result records
+int launch_reg_batch(ws_reg *r, const ws_map *m, int32_t res, uint32_t flags, size_t k, int32_t max_iterations, float it_weight_gradient, float epsilon);
+size_t reg_batch_record_bytes(); // start + result record of one hypothesis
+void reg_batch_write(void *records, size_t k, const float T[16]);
+void reg_batch_read(const void *records, size_t n, size_t k, float T[16], int32_t *iterations, int32_t *e, int32_t *c);
+int reg_batch_default_variant();
 } // namespace ws
