@@ -394,6 +394,44 @@ int ws_store_chunks_of_box(const int32_t lo[3], const int32_t hi[3], int32_t *ke
  * last save_box / load_box / shift on the store (summed over the axes of a shift) */
 int ws_debug_store_timing(ws_store *st, int32_t enable, float ms_out[2]);
 
+/* The surface cloud of the store: ws_map_surface over the chunks of the global map, wherever they lie -- the point cloud of everything
+ * mapped, including what the window has left -- on the device, without a chunk leaving HBM.
+ *   field: that of ws_store_mesh: a voxel of a present chunk holds that chunk's entry.  A voxel of an absent chunk never qualifies,
+ *     whatever fill_entry is.
+ *   predicate, record and marker: word for word those of ws_map_surface.  A voxel qualifies iff weight > 0 && abs(value) < band (abs
+ *     on the value as int32, so -32768 never qualifies); the 16-byte record is int32 x, y, z in world voxels, then uint32 raw; with
+ *     WS_SURFACE_MARKER 7 float32 per record in a second array of the same order, (float)x * (float)map_resolution / 1000.f per axis,
+ *     then r, g, b, a from value / (float)tau.  The store knows neither tau nor the resolution, the caller passes both: tau <= 0 or
+ *     map_resolution <= 0 is WS_ERR_INVALID; band <= 0 means tau.  The flag values are WS_SURFACE_RECORDS and WS_SURFACE_MARKER;
+ *     unknown flag bits: WS_ERR_INVALID.
+ *   box: inclusive world voxels [lo, hi], anywhere in int32 voxel space; it need not lie in any window.  Extents are formed in 64 bits.
+ *     Both NULL: every present chunk, i.e. the bounding box of the present chunks, as for ws_store_mesh.  Exactly one NULL, or
+ *     hi < lo: WS_ERR_INVALID.  An empty store, or a box that meets no present chunk, is WS_OK with *n_out = 0.
+ *   order: records in ascending world (x, y, z), z fastest -- over the whole box, across chunk borders.  Consequence: if a window
+ *     holds the same voxels as the store inside a box, and tau and map_resolution are the map's, ws_map_surface on that window and box
+ *     returns the same bytes, records and marker (what ws_store_load_box writes for an absent chunk must not qualify either: a
+ *     fill_entry of weight 0).
+ *   limits: a box that overlaps 2^19 present chunks or more (512 GB of voxels) is WS_ERR_RANGE.  On a refusal nothing is launched, and
+ *     the last result stays.  Counts and offsets are 64-bit: there is no 2^32 record limit.  An allocation that fails is WS_ERR_HIP
+ *     and leaves the store usable.
+ *   ordering: the work is stream-ordered behind every save, load and shift already enqueued on the store's context; the call
+ *     synchronises (the count comes back), is read-only on the chunks and is serialised with the other store calls by the store's
+ *     mutex.
+ *   result buffers: they belong to the store, are not allocated before the first call and grow on demand; they stay valid until
+ *     the next ws_store_surface on the store -- later saves, loads, shifts and drops leave them untouched -- and are apart from
+ *     those of ws_store_mesh, ws_store_raycast and ws_store_distance.  Every output write is bounded by the buffers' capacities.
+ *   cost: scratch, tables and work follow the number of present chunks the box overlaps (4096 words of 64 voxels per chunk, 8 bytes
+ *     of scratch per word plus 12 bytes per 256 words: 32 KB per chunk, plus 32 bytes of tables), never the volume of the box: three
+ *     chunks a million voxels apart cost three chunks, and nothing is refused because the bounding box is large. */
+int ws_store_surface(ws_store *st, const int32_t lo[3], const int32_t hi[3], int32_t band, int32_t tau, int32_t map_resolution, uint32_t flags, size_t *n_out);
+const void *ws_store_surface_records_dev(const ws_store *st, size_t *n); /* device memory, n x 16 bytes; NULL when n == 0 */
+const float *ws_store_surface_marker_dev(const ws_store *st, size_t *n); /* device memory, n x 7 floats; NULL unless the last call asked for it */
+/* copies at most capacity_points points (a prefix) and always reports the total in *n_out; either host pointer may be NULL */
+int ws_store_surface_download(ws_store *st, void *records_host, float *marker_host, size_t capacity_points, size_t *n_out);
+/* Measurement entry, as ws_debug_surface_timing: ms_out receives the device time of the count passes (the masks and their totals), the
+ * scan and the emit pass of the last call */
+int ws_debug_store_surface_timing(ws_store *st, int32_t enable, float ms_out[3]);
+
 /* The mesh of the store: the surface nets of ws_map_mesh over the chunks of the global map, wherever they lie -- the mesh of the
  * whole run, not of the window -- on the device, without a chunk leaving HBM.
  *   field: a voxel of a present chunk holds that chunk's entry.  A voxel of an absent chunk is NOT VALID, whatever fill_entry is,

@@ -334,6 +334,13 @@ public:
 private:
   ws_store *store_ = nullptr;
 };
+// the surface cloud of the device global map (visualization.hpp, ws_store_surface)
+inline SurfaceCloud global_map_cloud(DeviceGlobalMap &g, int tau, int resolution, bool marker = true, const rm::Pointi *lo = nullptr, const rm::Pointi *hi = nullptr,
+                                     int band = 0)
+{
+  return global_map_cloud(g.handle(), tau, resolution, marker, lo, hi, band);
+}
+
 // the mesh of the device global map (visualization.hpp, ws_store_mesh)
 inline SurfaceMesh global_map_mesh(DeviceGlobalMap &g, int resolution, bool any_weight = false, const rm::Pointi *lo = nullptr, const rm::Pointi *hi = nullptr)
 {
@@ -630,6 +637,17 @@ public:
     local_map_.window(wlo, whi);
     WS_CHECK(ws_store_save_box(device_global_map_->handle(), gpu_.tsdf().handle(), WS_MAP_AVG, &wlo.x, &whi.x));
     return global_map_mesh(*device_global_map_, params_.map_resolution, any_weight, lo, hi);
+  }
+  // The surface cloud of everything the run has seen: the window into the device chunks, as global_mesh does, then the cloud of the
+  // store -- nothing leaves the device but the records
+  SurfaceCloud global_surface(bool marker = true, const rm::Pointi *lo = nullptr, const rm::Pointi *hi = nullptr, int band = 0)
+  {
+    if (!device_global_map_) throw std::logic_error("global_surface: no DeviceGlobalMap attached");
+    wait_shift();
+    rm::Pointi wlo, whi;
+    local_map_.window(wlo, whi);
+    WS_CHECK(ws_store_save_box(device_global_map_->handle(), gpu_.tsdf().handle(), WS_MAP_AVG, &wlo.x, &whi.x));
+    return global_map_cloud(*device_global_map_, params_.tau, params_.map_resolution, marker, lo, hi, band);
   }
   // The predicted scan from anywhere the run has been: the window into the device chunks, as global_mesh does, then the ray cast of
   // the store -- nothing leaves the device but the records

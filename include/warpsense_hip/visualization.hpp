@@ -1,6 +1,7 @@
 // visualization.hpp — the data behind the reference's two map markers (include/warpsense/visualization/map.h), without ROS:
 //
 //   local_map_cloud      publish_local_map           map.h:14-121    the surface cloud of a DEVICE map, over ws_map_surface
+//   global_map_cloud     pcl_writer's exported map, without the export                        the surface cloud of the device global map, over ws_store_surface
 //   local_map_mesh       (no counterpart: the reference sends the user to an offline mesher)   a triangle mesh, over ws_map_mesh
 //   global_map_mesh      (no counterpart)                                                     the mesh of the device global map, over ws_store_mesh
 //   local_map_raycast    (no counterpart: the reference leaves all viewing to RViz)            a predicted scan, over ws_map_raycast
@@ -49,6 +50,22 @@ inline SurfaceCloud local_map_cloud(cuda::TSDFCuda &tsdf, int which = WS_MAP_AVG
   if (marker) out.marker.resize(n * 7);
   size_t got = 0;
   WS_CHECK(ws_map_surface_download(tsdf.handle(), n ? out.records.data() : nullptr, n && marker ? out.marker.data() : nullptr, n, &got));
+  return out;
+}
+
+// The surface cloud of the global map in device memory (the rules: warpsense_hip.h at ws_store_surface): the qualifying voxels of the
+// store's chunks inside the inclusive world-voxel box [lo, hi] (both nullptr: every present chunk), in the order of local_map_cloud
+// across chunk borders.  tau, resolution: the map's (the store knows neither).  (app.hpp adds the overload that takes a DeviceGlobalMap.)
+inline SurfaceCloud global_map_cloud(ws_store *store, int tau, int resolution, bool marker = true, const rmagine::Pointi *lo = nullptr,
+                                     const rmagine::Pointi *hi = nullptr, int band = 0)
+{
+  SurfaceCloud out;
+  size_t n = 0;
+  WS_CHECK(ws_store_surface(store, lo ? &lo->x : nullptr, hi ? &hi->x : nullptr, band, tau, resolution, marker ? WS_SURFACE_MARKER : WS_SURFACE_RECORDS, &n));
+  out.records.resize(n);
+  if (marker) out.marker.resize(n * 7);
+  size_t got = 0;
+  WS_CHECK(ws_store_surface_download(store, n ? out.records.data() : nullptr, n && marker ? out.marker.data() : nullptr, n, &got));
   return out;
 }
 

@@ -1,0 +1,57 @@
+// store_surface_dropin.cpp — MappingNode::global_surface and warpsense::global_map_cloud (include/warpsense_hip/app.hpp,
+// visualization.hpp) from C++: scans along a walk of the window through the device global map, then the surface cloud of the store over
+// the C ABI, and digests of its bytes for tests/test_gpu_store_surface_dropin.py.
+//   store_surface_dropin scans.bin n_points edge resolution tau max_weight segment_chunks x0 y0 z0 [x1 y1 z1 ...]
+// scans.bin: one scan of n_points x 3 int32 (map frame, mm) per window position, in order
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+
+#include "warpsense_hip/app.hpp"
+
+static unsigned long long fnv1a(const void *data, size_t bytes)
+{
+  unsigned long long h = 1469598103934665603ull;
+  const unsigned char *p = static_cast<const unsigned char *>(data);
+  for (size_t i = 0; i < bytes; ++i) h = (h ^ p[i]) * 1099511628211ull;
+  return h;
+}
+
+static void report(const char *name, const warpsense::SurfaceCloud &c)
+{
+  printf("%s %zu %016llx %016llx\n", name, c.records.size(), fnv1a(c.records.data(), c.records.size() * sizeof(warpsense::SurfaceRecord)),
+         c.marker.empty() ? 0ull : fnv1a(c.marker.data(), c.marker.size() * sizeof(float)));
+}
+
+int main(int argc, char **argv)
+{
+  if (argc < 11 || (argc - 8) % 3 != 0) return 2;
+  const size_t n = (size_t)atoll(argv[2]);
+  const int edge = atoi(argv[3]), steps = (argc - 8) / 3;
+  cuda::HotPathParams hot;
+  hot.map_resolution = atoi(argv[4]);
+  hot.tau = atoi(argv[5]);
+  hot.max_weight = atoi(argv[6]);
+  FILE *f = fopen(argv[1], "rb");
+  if (!f) return 2;
+
+  warpsense::GlobalMap global((int16_t)hot.tau, 0);
+  warpsense::LocalMap local(edge, edge, edge, global);
+  warpsense::MappingNode node(hot, local);
+  warpsense::DeviceGlobalMap store(global.get_default_tsdf_entry(), 0, (uint32_t)atoi(argv[7]));
+  node.attach(&store);
+  std::vector<rmagine::Pointi> scan(n);
+  for (int k = 0; k < steps; ++k)
+  {
+    const rmagine::Pointi pos(atoi(argv[8 + 3 * k]), atoi(argv[9 + 3 * k]), atoi(argv[10 + 3 * k]));
+    if (fread(scan.data(), sizeof(rmagine::Pointi), n, f) != n) return 3;
+    if (k) node.shift_map_device(pos);
+    node.gpu().tsdf().update_tsdf(scan, pos, rmagine::Pointi(0, 0, 32768));
+  }
+  fclose(f);
+  report("global", node.global_surface());
+  printf("chunks %zu\n", store.count());
+  const rmagine::Pointi lo(-20, -40, -30), hi(70, 10, 30); // a box that is in no window of the walk
+  report("box", warpsense::global_map_cloud(store, hot.tau, hot.map_resolution, false, &lo, &hi, hot.tau / 2));
+  return 0;
+}

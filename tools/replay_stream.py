@@ -68,6 +68,9 @@ def main():
                     "TSDFMapping.surface_mesh) as binary little-endian PLY into DIR, after every N-th scan like --surface-ply")
     ap.add_argument("--global-mesh-ply", default=None, metavar="FILE", help="after the last scan: the mesh of the WHOLE run, window and every chunk that "
                     "has left it, from the device global map (TSDFMapping.global_mesh, ws_store_mesh); needs --device-global-map")
+    ap.add_argument("--global-surface-ply", default=None, metavar="FILE", help="after the last scan: the surface cloud of the WHOLE run, window and every "
+                    "chunk that has left it, from the device global map (TSDFMapping.global_surface_cloud, ws_store_surface) as PLY; needs "
+                    "--device-global-map")
     ap.add_argument("--global-raycast-ply", default=None, metavar="FILE", help="after the last scan: the predicted scan from the pose of the FIRST scan, "
                     "which the window has left, through the device global map (TSDFMapping.global_raycast, ws_store_raycast) as PLY, and its hit "
                     "share printed next to that of the window's raycast from the same pose; needs --device-global-map")
@@ -96,6 +99,8 @@ def main():
     args = ap.parse_args()
     if args.global_mesh_ply and not args.device_global_map:
         ap.error("--global-mesh-ply requires --device-global-map")
+    if args.global_surface_ply and not args.device_global_map:
+        ap.error("--global-surface-ply requires --device-global-map")
     if args.global_raycast_ply and not args.device_global_map:
         ap.error("--global-raycast-ply requires --device-global-map")
     if args.global_distance_npy and not args.device_global_map:
@@ -190,6 +195,16 @@ def main():
         global_mesh = {"file": args.global_mesh_ply, "vertices": int(len(gv)), "faces": int(len(gf)), "chunks": app.gpu_.device_global_map_.count(), "call_s": tg}
         print(f"global mesh: {len(gv)} vertices, {len(gf)} faces from {global_mesh['chunks']} chunks in {1000.0 * tg:.2f} ms (save_box + ws_store_mesh + download)",
               file=sys.stderr)
+    global_surface = None
+    if args.global_surface_ply:
+        tg = time.perf_counter()
+        _, gm = app.gpu_.global_surface_cloud(marker=True)
+        tg = time.perf_counter() - tg
+        os.makedirs(os.path.dirname(os.path.abspath(args.global_surface_ply)), exist_ok=True)
+        points = W.write_surface_ply(args.global_surface_ply, gm)
+        global_surface = {"file": args.global_surface_ply, "points": int(points), "chunks": app.gpu_.device_global_map_.count(), "call_s": tg}
+        print(f"global surface: {points} points from {global_surface['chunks']} chunks in {1000.0 * tg:.2f} ms (save_box + ws_store_surface + download)",
+              file=sys.stderr)
     global_distance = None
     if args.global_distance_npy:
         tg = time.perf_counter()
@@ -245,6 +260,7 @@ def main():
                       "surface_ply": surface if args.surface_ply else None,
                       "mesh_ply": mesh if args.mesh_ply else None,
                       "global_mesh_ply": global_mesh,
+                      "global_surface_ply": global_surface,
                       "global_raycast_ply": global_raycast,
                       "global_distance_npy": global_distance,
                       "raycast_ply": raycast if args.raycast_ply else None,

@@ -37,6 +37,7 @@ EXPORTS = [
     "ws_store_create", "ws_store_destroy", "ws_store_reserve", "ws_store_count", "ws_store_keys", "ws_store_has", "ws_store_get_chunk", "ws_store_put_chunk",
     "ws_store_drop_chunk", "ws_store_chunk_dev", "ws_store_save_box", "ws_store_load_box", "ws_shift_device", "ws_store_chunks_of_box", "ws_debug_store_timing",
     "ws_store_distance", "ws_store_distance_dev", "ws_store_distance_download", "ws_debug_store_distance_timing",
+    "ws_store_surface", "ws_store_surface_records_dev", "ws_store_surface_marker_dev", "ws_store_surface_download", "ws_debug_store_surface_timing",
     "ws_store_mesh", "ws_store_mesh_vertices_dev", "ws_store_mesh_faces_dev", "ws_store_mesh_download", "ws_debug_store_mesh_timing",
     "ws_store_raycast", "ws_store_raycast_dev", "ws_store_raycast_records_dev", "ws_store_raycast_gradient_dev", "ws_store_raycast_download",
     "ws_debug_store_raycast_timing", "ws_debug_store_raycast_table", "ws_debug_store_raycast_find",
@@ -249,6 +250,13 @@ def load() -> C.CDLL:
     L.ws_shift_device.argtypes = [vp, vp, vp]
     L.ws_store_chunks_of_box.argtypes = [vp, vp, vp, sz, P(sz)]
     L.ws_debug_store_timing.argtypes = [vp, i32, vp]
+    L.ws_store_surface.argtypes = [vp, vp, vp, i32, i32, i32, u32, P(sz)]
+    L.ws_store_surface_records_dev.argtypes = [vp, P(sz)]
+    L.ws_store_surface_records_dev.restype = vp
+    L.ws_store_surface_marker_dev.argtypes = [vp, P(sz)]
+    L.ws_store_surface_marker_dev.restype = vp
+    L.ws_store_surface_download.argtypes = [vp, vp, vp, sz, P(sz)]
+    L.ws_debug_store_surface_timing.argtypes = [vp, i32, vp]
     L.ws_store_mesh.argtypes = [vp, vp, vp, i32, u32, P(sz), P(sz)]
     L.ws_store_mesh_vertices_dev.argtypes = [vp, P(sz)]
     L.ws_store_mesh_vertices_dev.restype = vp

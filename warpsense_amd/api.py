@@ -482,6 +482,31 @@ class GlobalMap:
         return buf
 
 
+def _surface_call(L, name, owner, lead, lo, hi, band, tail, marker, device):
+    """The surface call `name` (ws_map_surface, ws_store_surface) on owner.handle and its result: `lead` are the arguments of the entry
+    point before the box, `tail` those between the band and the flags.  owner keeps the device tensors' memory alive."""
+    if (lo is None) != (hi is None):
+        raise WsError("surface: give both lo and hi, or neither")
+    n = C.c_size_t(0)
+    flags = _lib.WS_SURFACE_MARKER if marker else _lib.WS_SURFACE_RECORDS
+    check(getattr(L, name)(owner.handle, *lead, _ptr(_i3(lo)) if lo is not None else None, _ptr(_i3(hi)) if hi is not None else None,
+                           int(band) if band is not None else 0, *tail, flags, C.byref(n)), name)
+    n = int(n.value)
+    if device:
+        cnt = C.c_size_t(0)
+        rec = _device_tensor(getattr(L, name + "_records_dev")(owner.handle, C.byref(cnt)), (n, 4), "<i4", owner)
+        if not marker:
+            return rec
+        return rec, _device_tensor(getattr(L, name + "_marker_dev")(owner.handle, C.byref(cnt)), (n, 7), "<f4", owner)
+    rec = np.empty(n, dtype=SURFACE_RECORD)
+    mk = np.empty((n, 7), dtype=np.float32) if marker else None
+    got = C.c_size_t(0)
+    check(getattr(L, name + "_download")(owner.handle, _ptr(rec), _ptr(mk), n, C.byref(got)), name + "_download")
+    if int(got.value) != n:
+        raise WsError("surface: another call replaced the result before it was downloaded")
+    return (rec, mk) if marker else rec
+
+
 def _mesh_call(L, name, owner, lead, lo, hi, tail, any_weight, device):
     """The mesh call `name` (ws_map_mesh, ws_store_mesh) on owner.handle and its result: `lead` and `tail` are the arguments of the
     entry point before and behind the box.  owner keeps the device tensors' memory alive."""
@@ -627,6 +652,23 @@ class DeviceGlobalMap:
         ms = (C.c_float * 2)()
         check(self._L.ws_debug_store_timing(self.handle, int(enable), ms), "ws_debug_store_timing")
         return float(ms[0]), float(ms[1])
+
+    def surface(self, tau, resolution, lo=None, hi=None, band=None, marker=False, device=False):
+        """The surface cloud of the chunks on the device (ws_store_surface; the rules are those of ws_map_surface, stated in
+        include/warpsense_hip.h): every voxel of a present chunk inside the inclusive world-voxel box [lo, hi] (both None: every
+        present chunk) with weight > 0 and abs(value) < band (None: tau), in ascending world (x, y, z), z fastest, across chunk
+        borders.  Voxels of absent chunks never qualify.  tau, resolution: the map's (the store knows neither); they decide the
+        marker's colour and point.
+
+        Returns the same forms as DeviceMapMemWrapper.surface: the records, or with `marker` (records, (n, 7) float32);
+        device=True: torch tensors that ALIAS the store's buffers, valid until the next surface() on this store."""
+        return _surface_call(self._L, "ws_store_surface", self, (), lo, hi, band, (int(tau), int(resolution)), marker, device)
+
+    def surface_timing(self, enable: int = -1):
+        """device milliseconds of the count passes, the scan and the emit pass of the last surface() (ws_debug_store_surface_timing)"""
+        ms = (C.c_float * 3)()
+        check(self._L.ws_debug_store_surface_timing(self.handle, int(enable), ms), "ws_debug_store_surface_timing")
+        return tuple(float(v) for v in ms)
 
     def mesh(self, resolution, lo=None, hi=None, any_weight=False, device=False):
         """The mesh of the chunks on the device (ws_store_mesh; the rules are those of ws_map_mesh, stated in
@@ -883,27 +925,7 @@ class DeviceMapMemWrapper:
         a pair (records, (n, 7) float32: x y z in metres, r g b a as the reference computes them).
         device=True: torch tensors on the GPU instead — (n, 4) int32 and (n, 7) float32 — that ALIAS the library's buffers:
         valid until the next surface() on this TSDFCuda, copy them (.clone()) to keep them."""
-        t = self._t
-        if (lo is None) != (hi is None):
-            raise WsError("surface: give both lo and hi, or neither")
-        n = C.c_size_t(0)
-        flags = _lib.WS_SURFACE_MARKER if marker else _lib.WS_SURFACE_RECORDS
-        check(t._L.ws_map_surface(t.handle, self._which, _ptr(_i3(lo)) if lo is not None else None, _ptr(_i3(hi)) if hi is not None else None,
-                                  int(band) if band is not None else 0, flags, C.byref(n)), "ws_map_surface")
-        n = int(n.value)
-        if device:
-            cnt = C.c_size_t(0)
-            rec = _device_tensor(t._L.ws_map_surface_records_dev(t.handle, C.byref(cnt)), (n, 4), "<i4", t)
-            if not marker:
-                return rec
-            return rec, _device_tensor(t._L.ws_map_surface_marker_dev(t.handle, C.byref(cnt)), (n, 7), "<f4", t)
-        rec = np.empty(n, dtype=SURFACE_RECORD)
-        mk = np.empty((n, 7), dtype=np.float32) if marker else None
-        got = C.c_size_t(0)
-        check(t._L.ws_map_surface_download(t.handle, _ptr(rec), _ptr(mk), n, C.byref(got)), "ws_map_surface_download")
-        if int(got.value) != n:
-            raise WsError("surface: another call replaced the result before it was downloaded")
-        return (rec, mk) if marker else rec
+        return _surface_call(self._t._L, "ws_map_surface", self._t, (self._which,), lo, hi, band, (), marker, device)
 
     def mesh(self, lo=None, hi=None, any_weight=False, device=False):
         """A triangle mesh of this map by naive surface nets on the device (ws_map_mesh; the rules are stated in
@@ -1443,6 +1465,18 @@ class TSDFMapping:
             lo, hi = self.local_map_.window()
             self.device_global_map_.save_box(self.tsdf_, lo, hi)
             return self.device_global_map_.mesh(int(self.params_.map.resolution), **kw)
+
+    def global_surface_cloud(self, **kw):
+        """The surface cloud of everything the run has seen, including what the window has left: the window goes into the chunks of
+        device_global_map exactly as in global_mesh (ws_store_save_box behind wait_shift, under the mapping's lock like a writer),
+        then DeviceGlobalMap.surface with the map's tau and resolution.  Keywords: lo, hi, band, marker, device."""
+        if self.device_global_map_ is None:
+            raise WsError("global_surface_cloud: this TSDFMapping has no device_global_map")
+        self.wait_shift()
+        with self.mutex_:
+            lo, hi = self.local_map_.window()
+            self.device_global_map_.save_box(self.tsdf_, lo, hi)
+            return self.device_global_map_.surface(self.tsdf_.tau_, int(self.params_.map.resolution), **kw)
 
     def global_distance_field(self, lo=None, hi=None, max_dist_m=1.0, unknown_occupied=False, columns=False, any_weight=False, device=False):
         """The distance field of everything the run has seen: the window goes into the chunks of device_global_map exactly as in

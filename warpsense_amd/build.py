@@ -22,8 +22,8 @@ ROOT = os.path.dirname(PKG_DIR)
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libwarpsense_hip.so")
 H5_LIB_PATH = os.path.join(PKG_DIR, "libwarpsense_h5.so")  # optional: global-map file (needs the HDF5 C library)
-SOURCES = ["api_core.hip", "api_map.hip", "api_query.hip", "api_store.hip", "api_tsdf.hip", "api_reg.hip", "api_scan.hip", "tsdf_update.hip", "tsdf_integrate.hip", "reg_routes.hip", "reg_batch.hip", "scan_preprocess.hip", "map_surface.hip", "map_mesh.hip", "map_raycast.hip", "map_distance.hip", "map_store.hip", "store_mesh.hip", "store_raycast.hip", "store_distance.hip"]
-HEADERS = [os.path.join(CSRC, "ws_internal.h"), os.path.join(CSRC, "ws_api.h"), os.path.join(CSRC, "ws_device.h"), os.path.join(CSRC, "ws_march.h"), os.path.join(CSRC, "ws_dda.h"), os.path.join(CSRC, "ws_mesh.h"), os.path.join(CSRC, "ws_raycast.h"),
+SOURCES = ["api_core.hip", "api_map.hip", "api_query.hip", "api_store.hip", "api_tsdf.hip", "api_reg.hip", "api_scan.hip", "tsdf_update.hip", "tsdf_integrate.hip", "reg_routes.hip", "reg_batch.hip", "scan_preprocess.hip", "map_surface.hip", "map_mesh.hip", "map_raycast.hip", "map_distance.hip", "map_store.hip", "store_surface.hip", "store_mesh.hip", "store_raycast.hip", "store_distance.hip"]
+HEADERS = [os.path.join(CSRC, "ws_internal.h"), os.path.join(CSRC, "ws_api.h"), os.path.join(CSRC, "ws_device.h"), os.path.join(CSRC, "ws_march.h"), os.path.join(CSRC, "ws_dda.h"), os.path.join(CSRC, "ws_mesh.h"), os.path.join(CSRC, "ws_raycast.h"), os.path.join(CSRC, "ws_surface.h"), os.path.join(CSRC, "ws_store_words.h"),
            os.path.join(CSRC, "reg_reduce.h"), os.path.join(CSRC, "reg_gn.h"), os.path.join(CSRC, "reg_points.h"), os.path.join(CSRC, "reg_exchange.h"),
            os.path.join(CSRC, "reg_loop.hip"), os.path.join(CSRC, "reg_launches.hip"), os.path.join(CSRC, "reg_server.hip"),  # the parts of reg_routes.hip
            os.path.join(ROOT, "include", "warpsense_hip.h")]

@@ -14,70 +14,56 @@ int ws_map_surface(ws_map *m, int which, const int32_t lo[3], const int32_t hi[3
   WS_SETTLE(m);
   std::lock_guard<std::mutex> lock(m->surf.mu);
   ws_map::Surface &q = m->surf;
-  int rc = q.timer.arm();
+  WS_TRY(q.timer.arm());
   int32_t l[3], ext[3];
-  if (rc == WS_OK) rc = resolve_box(m, which, lo, hi, true, "ws_map_surface", l, ext);
-  if (rc == WS_OK) rc = q.total.alloc(1);
-  if (rc != WS_OK) return rc;
+  WS_TRY(resolve_box(m, which, lo, hi, true, "ws_map_surface", l, ext));
   if (band <= 0) band = m->tau;
-  const bool marker = (flags & WS_SURFACE_MARKER) != 0;
-  hipStream_t s = m->ctx->stream;
-  const size_t n_cols = (size_t)ext[0] * (size_t)ext[1], blocks = surface_blocks_for((int64_t)n_cols); // n_cols < 2^31 (ws_map_create)
-  if (n_cols > q.col_cnt.cap || blocks > q.blk_tot.cap || blocks > q.blk_off.cap)
-  {
-    WS_HIP(hipStreamSynchronize(s));
-    rc = q.col_cnt.grow(n_cols, sizeof(uint32_t));
-    if (rc == WS_OK) rc = q.blk_tot.grow(blocks, sizeof(uint32_t));
-    if (rc == WS_OK) rc = q.blk_off.grow(blocks, sizeof(unsigned long long));
-    if (rc != WS_OK) return rc;
-  }
-  q.n = 0;
-  q.has_marker = false;
-  rc = launch_surface_count(m, which, l, ext, band);
-  if (rc != WS_OK) return rc;
-  WS_HIP(hipStreamSynchronize(s)); // the one host read the call needs: the output is sized from the counted total
-  const size_t total = (size_t)*q.total.host;
-  rc = q.rec.grow(total, 16);
-  if (rc == WS_OK && marker) rc = q.marker.grow(total, 7 * sizeof(float));
-  if (rc != WS_OK) return rc;
-  if (total)
-  {
-    // (the kernel's bound holds for both buffers)
-    rc = launch_surface_emit(m, which, l, ext, band, marker, marker ? std::min(q.rec.cap, q.marker.cap) : q.rec.cap);
-    if (rc != WS_OK) return rc;
-    WS_HIP(hipStreamSynchronize(s));
-  }
-  q.n = total;
-  q.has_marker = marker;
-  if (n_out) *n_out = total;
+  const size_t n_cols = (size_t)ext[0] * (size_t)ext[1]; // n_cols < 2^31 (ws_map_create)
+  WS_TRY(surface_run(
+      q, m->ctx->stream, surface_blocks_for((int64_t)n_cols), (flags & WS_SURFACE_MARKER) != 0, n_out, n_cols > q.col_cnt.cap,
+      [&] { return q.col_cnt.grow(n_cols, sizeof(uint32_t)); }, [&] { return launch_surface_count(m, which, l, ext, band); },
+      [&](size_t cap) { return launch_surface_emit(m, which, l, ext, band, (flags & WS_SURFACE_MARKER) != 0, cap); }));
   return map_take_error(m);
 }
 
-const void *ws_map_surface_records_dev(const ws_map *m, size_t *n)
+// ---- surface cloud: what the host core of ws_api.h (surface_run) needs beside it, for the window of a map here and for the chunks of
+// the store in api_store.hip
+const void *ws::surface_records_dev(const SurfResult *q, size_t *n)
 {
-  if (n) *n = m ? m->surf.n : 0;
-  return m && m->surf.n ? m->surf.rec.p : nullptr;
+  if (n) *n = q ? q->n : 0;
+  return q && q->n ? q->rec.p : nullptr;
 }
 
-const float *ws_map_surface_marker_dev(const ws_map *m, size_t *n)
+const float *ws::surface_marker_dev(const SurfResult *q, size_t *n)
 {
-  const bool have = m && m->surf.has_marker && m->surf.n;
-  if (n) *n = have ? m->surf.n : 0;
-  return have ? static_cast<const float *>(m->surf.marker.p) : nullptr;
+  const bool have = q && q->has_marker && q->n;
+  if (n) *n = have ? q->n : 0;
+  return have ? static_cast<const float *>(q->marker.p) : nullptr;
 }
+
+// `name`, `call`: the download entry point, and the entry point whose flag it misses
+int ws::surface_download(const SurfResult &q, hipStream_t s, const char *name, const char *call, void *records_host, float *marker_host, size_t capacity_points,
+                         size_t *n_out)
+{
+  *n_out = q.n;
+  const size_t k = std::min(capacity_points, q.n);
+  if (k == 0) return WS_OK;
+  if (marker_host && !q.has_marker) return invalid(std::string(name) + ": the last " + call + " did not ask for WS_SURFACE_MARKER");
+  if (records_host) WS_HIP(hipMemcpyAsync(records_host, q.rec.p, k * 16, hipMemcpyDeviceToHost, s));
+  if (marker_host) WS_HIP(hipMemcpyAsync(marker_host, q.marker.p, k * 7 * sizeof(float), hipMemcpyDeviceToHost, s));
+  WS_HIP(hipStreamSynchronize(s));
+  return WS_OK;
+}
+
+const void *ws_map_surface_records_dev(const ws_map *m, size_t *n) { return surface_records_dev(m ? &m->surf : nullptr, n); }
+
+const float *ws_map_surface_marker_dev(const ws_map *m, size_t *n) { return surface_marker_dev(m ? &m->surf : nullptr, n); }
 
 int ws_map_surface_download(ws_map *m, void *records_host, float *marker_host, size_t capacity_points, size_t *n_out)
 {
   if (!m || !n_out) return invalid("ws_map_surface_download: NULL argument");
   std::lock_guard<std::mutex> lock(m->surf.mu);
-  *n_out = m->surf.n;
-  const size_t k = std::min(capacity_points, m->surf.n);
-  if (k == 0) return WS_OK;
-  if (marker_host && !m->surf.has_marker) return invalid("ws_map_surface_download: the last ws_map_surface did not ask for WS_SURFACE_MARKER");
-  if (records_host) WS_HIP(hipMemcpyAsync(records_host, m->surf.rec.p, k * 16, hipMemcpyDeviceToHost, m->ctx->stream));
-  if (marker_host) WS_HIP(hipMemcpyAsync(marker_host, m->surf.marker.p, k * 7 * sizeof(float), hipMemcpyDeviceToHost, m->ctx->stream));
-  WS_HIP(hipStreamSynchronize(m->ctx->stream));
-  return WS_OK;
+  return surface_download(m->surf, m->ctx->stream, "ws_map_surface_download", "ws_map_surface", records_host, marker_host, capacity_points, n_out);
 }
 
 // ws_debug_*_timing: the times of the last call between the event pairs of `pairs`, then the switch
@@ -92,8 +78,7 @@ int ws_debug_surface_timing(ws_map *m, int32_t enable, float ms_out[3])
 {
   if (!m) return invalid("ws_debug_surface_timing: map is NULL");
   std::lock_guard<std::mutex> lock(m->surf.mu);
-  static const int pairs[3][2] = {{0, 1}, {1, 2}, {3, 4}};
-  return query_timing(m->ctx->stream, m->surf.timer, enable, ms_out, pairs, 3);
+  return query_timing(m->ctx->stream, m->surf.timer, enable, ms_out, SURF_PAIRS, 3);
 }
 
 // ---- mesh and ray cast: what the host cores of ws_api.h (mesh_run, raycast_check, raycast_run) need beside them, for the window of

@@ -1,6 +1,7 @@
 // api_store.hip — the chunk store, the global map in device memory (ws_store_*, ws_shift_device; kernels in map_store.hip): directory,
-// segments and slot tables, the box transfers between a map's window and the chunks, and the store's mesh, ray cast and distance field,
-// which run the host cores of ws_api.h over the chunks a call lists (store_mesh.hip, store_raycast.hip, store_distance.hip).
+// segments and slot tables, the box transfers between a map's window and the chunks, and the store's surface cloud, mesh, ray cast and
+// distance field, which run the host cores of ws_api.h over the chunks a call lists (store_surface.hip, store_mesh.hip,
+// store_raycast.hip, store_distance.hip).
 #include <algorithm>
 #include <array>
 #include <cstring>
@@ -431,8 +432,9 @@ int ws_debug_store_timing(ws_store *st, int32_t enable, float ms_out[2])
   return WS_OK;
 }
 
-// ---- the mesh, the ray cast and the distance field of the store: the rules and the host flow of ws_map_mesh, ws_map_raycast and
-// ws_map_distance over the chunks, store_mesh.hip, store_raycast.hip and store_distance.hip (the semantics are stated in warpsense_hip.h)
+// ---- the surface cloud, the mesh, the ray cast and the distance field of the store: the rules and the host flow of ws_map_surface,
+// ws_map_mesh, ws_map_raycast and ws_map_distance over the chunks, store_surface.hip, store_mesh.hip, store_raycast.hip and
+// store_distance.hip (the semantics are stated in warpsense_hip.h)
 namespace
 {
 // The box of a query, into l and h.  First the refusal of a box whose hi < lo, in the name of the entry point; then the store's lock,
@@ -497,20 +499,21 @@ int store_enqueued(const ws_store *st, int rc)
   return rc;
 }
 
-// The tables of a mesh call over the n listed chunks (0 < n < 2^19), into st->mesh.table_host: per chunk the four counts that place
-// its 4096 words in world order, its key and slot, and the list positions of its 26 neighbours.  Everything is O(n log n).
-int store_mesh_tables(ws_store *st, const std::vector<StoreRaySlot> &listed)
+// Room for `need` bytes of chunk tables of a surface or mesh call, pinned and on the device (`want` where they have to grow, which
+// waits for the stream: the kernels in flight read the old table)
+int store_tables_reserve(ws_store *st, HostBlock &host, DevBuf &dev, size_t need, size_t want)
+{
+  if (need <= host.cap && need <= dev.cap) return WS_OK; // (both: a failed allocation of the second leaves the first one grown)
+  WS_HIP(hipStreamSynchronize(st->ctx->stream));
+  WS_TRY(host.alloc(want, 1, HostBlock::PINNED));
+  return dev.alloc(want, 1);
+}
+
+// The word-space tables of the n listed chunks (0 < n < 2^19) at `grp`, store_word_table_bytes(n): per chunk the four counts
+// {B, N, P, n} that place its 4096 words in world order (ws_store_words.h), then its key and slot
+void store_word_tables(const std::vector<StoreRaySlot> &listed, uint32_t *grp)
 {
   const size_t n = listed.size();
-  if (store_mesh_table_bytes(n) > st->mesh.table_host.cap)
-  {
-    WS_HIP(hipStreamSynchronize(st->ctx->stream));
-    const size_t want = store_mesh_table_bytes(n + n / 8);
-    WS_TRY(st->mesh.table_host.alloc(want, 1, HostBlock::PINNED));
-    WS_TRY(st->mesh.table_dev.alloc(want, 1));
-  }
-  uint32_t *grp = st->mesh.table_host.as<uint32_t>();
-  uint32_t *nb = grp + 8 * n;
   std::memcpy(grp + 4 * n, listed.data(), n * sizeof(StoreRaySlot)); // {cx, cy, cz, slot} per chunk
   for (size_t b = 0; b < n;) // the chunks of one cx: [b, e)
   {
@@ -526,6 +529,17 @@ int store_mesh_tables(ws_store *st, const std::vector<StoreRaySlot> &listed)
     }
     b = e;
   }
+}
+
+// The tables of a mesh call over the n listed chunks (0 < n < 2^19), into st->mesh.table_host: the word-space tables, and the list
+// positions of every chunk's 26 neighbours.  Everything is O(n log n).
+int store_mesh_tables(ws_store *st, const std::vector<StoreRaySlot> &listed)
+{
+  const size_t n = listed.size();
+  WS_TRY(store_tables_reserve(st, st->mesh.table_host, st->mesh.table_dev, store_mesh_table_bytes(n), store_mesh_table_bytes(n + n / 8)));
+  uint32_t *grp = st->mesh.table_host.as<uint32_t>();
+  uint32_t *nb = grp + 8 * n;
+  store_word_tables(listed, grp);
   const auto before = [](const StoreRaySlot &e, const StoreKey &k) { return StoreKey{e.cx, e.cy, e.cz} < k; };
   for (size_t i = 0; i < n; ++i)
     for (int c = 0; c < 27; ++c)
@@ -539,6 +553,53 @@ int store_mesh_tables(ws_store *st, const std::vector<StoreRaySlot> &listed)
   return WS_OK;
 }
 } // namespace
+
+int ws_store_surface(ws_store *st, const int32_t lo[3], const int32_t hi[3], int32_t band, int32_t tau, int32_t map_resolution, uint32_t flags, size_t *n_out)
+{
+  if (!st || (flags & ~WS_SURFACE_MARKER) || ((lo == nullptr) != (hi == nullptr)) || tau <= 0 || map_resolution <= 0) return invalid("ws_store_surface: bad argument");
+  std::unique_lock<std::mutex> lock;
+  StoreSurfCall c;
+  WS_TRY(store_query_box(st, "ws_store_surface", lo, hi, false, lock, c.lo, c.hi));
+  ws_store::Surface &q = st->surf;
+  std::vector<StoreRaySlot> listed;
+  if (c.lo[0] <= c.hi[0]) store_list(st, c.lo, c.hi, listed); // (else: no box and no chunk)
+  if (listed.size() >= (1u << 19)) return range_error("ws_store_surface", ": the box overlaps 2^19 present chunks or more (4096 words each must stay below 2^31)");
+  WS_TRY(q.timer.arm());
+  if (listed.empty()) // an empty store, or the box meets no present chunk
+  {
+    q.n = 0, q.has_marker = false;
+    if (n_out) *n_out = 0;
+    return WS_OK;
+  }
+  c.n_chunks = (uint32_t)listed.size();
+  c.band = band <= 0 ? tau : band, c.tau = tau, c.res = map_resolution;
+  const bool marker = (flags & WS_SURFACE_MARKER) != 0;
+  const size_t n_words = (size_t)c.n_chunks * 4096u, n = listed.size();
+  WS_TRY(store_tables_reserve(st, q.table_host, q.table_dev, store_word_table_bytes(n), store_word_table_bytes(n + n / 8)));
+  store_word_tables(listed, q.table_host.as<uint32_t>());
+  return surface_run(
+      q, st->ctx->stream, store_surface_blocks(c.n_chunks), marker, n_out, n_words > q.mask.cap, [&] { return q.mask.grow(n_words, sizeof(uint64_t)); },
+      [&] { return store_enqueued(st, launch_store_surface_count(st, q, c)); },
+      [&](size_t cap) { return store_enqueued(st, launch_store_surface_emit(st, q, c, marker, cap)); });
+}
+
+const void *ws_store_surface_records_dev(const ws_store *st, size_t *n) { return surface_records_dev(st ? &st->surf : nullptr, n); }
+
+const float *ws_store_surface_marker_dev(const ws_store *st, size_t *n) { return surface_marker_dev(st ? &st->surf : nullptr, n); }
+
+int ws_store_surface_download(ws_store *st, void *records_host, float *marker_host, size_t capacity_points, size_t *n_out)
+{
+  if (!st || !n_out) return invalid("ws_store_surface_download: NULL argument");
+  std::lock_guard<std::mutex> lock(st->mu);
+  return surface_download(st->surf, st->ctx->stream, "ws_store_surface_download", "ws_store_surface", records_host, marker_host, capacity_points, n_out);
+}
+
+int ws_debug_store_surface_timing(ws_store *st, int32_t enable, float ms_out[3])
+{
+  if (!st) return invalid("ws_debug_store_surface_timing: store is NULL");
+  std::lock_guard<std::mutex> lock(st->mu);
+  return query_timing(st->ctx->stream, st->surf.timer, enable, ms_out, SURF_PAIRS, 3);
+}
 
 int ws_store_mesh(ws_store *st, const int32_t lo[3], const int32_t hi[3], int32_t map_resolution, uint32_t flags, size_t *n_vertices, size_t *n_faces)
 {

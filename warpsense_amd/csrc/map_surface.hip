@@ -13,12 +13,11 @@
 // most two contiguous storage runs: [zs0, size_z) then [0, ...).  Each run is read as ALIGNED 16-byte loads (four voxels per lane,
 // 1 KiB per wave instruction) whose first and last group are masked: size_z is odd for the reference's maps, so no column starts on
 // a 16-byte boundary.  The maps carry 16 bytes of slack behind the last voxel (ws_map_create), which the last group may touch.
-#include "ws_device.h"
+// Which voxel qualifies, its record and its marker are the rules of ws_surface.h, which the cloud of the chunk store shares.
+#include "ws_surface.h"
 
 namespace ws
 {
-typedef uint32_t su32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int SURF_COLS = 16; // columns per workgroup: four per wave, one after the other
 constexpr int SURF_WAVES = 4;
 constexpr int SURF_COUNT = 0, SURF_EMIT = 1, SURF_EMIT_MARKER = 2;
@@ -35,7 +34,6 @@ struct SurfArgs
   unsigned long long cap;             // records the output buffers hold
 };
 
-__device__ __forceinline__ bool surf_pred(uint32_t raw, int32_t band) { return entry_weight(raw) > 0 && iabs32(entry_value(raw)) < band; }
 __device__ __forceinline__ uint32_t lanes_below(unsigned long long mask)
 {
   return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
@@ -72,9 +70,7 @@ __global__ __launch_bounds__(256) void surface_kernel(SurfArgs a)
     const int64_t cbase = box_column(a.box, col, x, y, zs0);
     const int32_t len_a = min(a.box.ez, a.box.mp.size[2] - zs0); // voxels up to the ring seam; the rest starts at storage z 0
     unsigned long long out = base + __shfl(before, ci, 64);
-    // publish_local_map's point (map.h:51-53): (float)x * (float)map_resolution / 1000.f -- a rounded product, then a correctly
-    // rounded division (no contraction, no reciprocal: -ffp-contract=off and hipcc's default IEEE division)
-    const float px = (float)x * fres / 1000.f, py = (float)y * fres / 1000.f;
+    const float px = surf_metres(x, fres), py = surf_metres(y, fres);
     uint32_t cnt = 0;
 #pragma unroll
     for (int run = 0; run < 2; ++run)
@@ -108,23 +104,8 @@ __global__ __launch_bounds__(256) void surface_kernel(SurfArgs a)
             if (!q[j]) continue;
             if (o < a.cap) // (the count pass sized the buffers; a map that changed in between must not write beyond them)
             {
-              const int32_t z = z0 + j;
-              const su32x4 r = {(uint32_t)x, (uint32_t)y, (uint32_t)z, raw[j]};
-              a.rec[o] = r;
-              if (MODE == SURF_EMIT_MARKER)
-              {
-                const int32_t val = entry_value(raw[j]);
-                float *m = a.marker + o * 7ull;
-                m[0] = px;
-                m[1] = py;
-                m[2] = (float)z * fres / 1000.f;
-                // map.h:55-64: r = value / (float)tau, g = 0 for value >= 0, else r = 0, g = -value / (float)tau; b = 0, a = 1
-                const float c = (float)(val >= 0 ? val : -val) / ftau;
-                m[3] = val >= 0 ? c : 0.f;
-                m[4] = val >= 0 ? 0.f : c;
-                m[5] = 0.f;
-                m[6] = 1.f;
-              }
+              surf_put_record(a.rec, o, x, y, z0 + j, raw[j]);
+              if (MODE == SURF_EMIT_MARKER) surf_put_marker(a.marker, o, px, py, z0 + j, raw[j], fres, ftau);
             }
             ++o;
           }

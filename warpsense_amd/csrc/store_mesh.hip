@@ -15,7 +15,8 @@
 // and ascends exactly like the output order, so the ONE flat scan of map_mesh.hip places every vertex and face.  The list is sorted,
 // so chunk i has r = i - B - P, and the way back needs no search: the chunk at list position t / 4096 has the word's cx (the words of
 // one cx are 4096 N consecutive indices from 4096 B), which gives B, N and lx; the chunk at position B + v / 64 of the remainder v
-// has the word's (cx, cy), which gives P, n, ly and r (StoreWord::find).
+// has the word's (cx, cy), which gives P, n, ly and r (StoreWord::find, in ws_store_words.h: the store's surface cloud walks the same
+// word space).
 //
 //   store_mesh_bits_kernel     one wave per four chunk columns, lane = z: the words of the listed chunks, bits outside the box cleared
 //   store_mesh_cells_kernel    |
@@ -27,62 +28,18 @@
 // Tables per call (the host's, store_mesh_tables in api_store.hip): per listed chunk {B, N, P, n}, {cx, cy, cz, slot} and 27 neighbour
 // entries (dx + 1) * 9 + (dy + 1) * 3 + (dz + 1), of which the passes use (0,0,0), the seven of {0,1}^3 and the seven of {0,-1}^3.
 #include "ws_mesh.h"
+#include "ws_store_words.h"
 
 namespace ws
 {
-constexpr uint32_t SM_NONE = 0xffffffffu;
-typedef uint32_t su32x4 __attribute__((ext_vector_type(4)));
-
-struct StoreMeshArgs : MeshBuffers
+struct StoreMeshArgs : MeshBuffers, StoreWords
 {
-  uint32_t n_chunks, n_words; // listed chunks; 4096 words each (n_words < 2^31)
   int32_t res;
   uint32_t any_weight;
   int32_t lo[3], hi[3];       // the box, inclusive world voxels
-  const su32x4 *grp;          // [n_chunks] B, N, P, n
-  const mi32x4 *key;          // [n_chunks] cx, cy, cz, slot
   const uint32_t *nb;         // [n_chunks][27] list position of the neighbour chunk, or SM_NONE
-  uint32_t *const *segs;      // base pointers of the store's segments
-  uint32_t seg_shift;
 };
 
-__device__ __forceinline__ uint32_t sm_word(const su32x4 g, uint32_t i, uint32_t lx, uint32_t ly)
-{
-  return 4096u * g.x + lx * 64u * g.y + 64u * g.z + ly * g.w + (i - g.x - g.z);
-}
-__device__ __forceinline__ const uint32_t *sm_chunk(const StoreMeshArgs &a, uint32_t i)
-{
-  const uint32_t slot = (uint32_t)a.key[i].w;
-  return a.segs[slot >> a.seg_shift] + (size_t)(slot & ((1u << a.seg_shift) - 1u)) * (size_t)STORE_CHUNK_WORDS;
-}
-
-// a word of the sparse space: its chunk (list position), its column in the chunk
-struct StoreWord
-{
-  uint32_t i, lx, ly;
-  su32x4 g;
-  __device__ __forceinline__ void find(const StoreMeshArgs &a, uint32_t t)
-  {
-    const su32x4 gx = a.grp[t >> 12];      // a chunk of the word's cx
-    const uint32_t u = t - 4096u * gx.x;
-    lx = u / (64u * gx.y);
-    const uint32_t v = u - lx * 64u * gx.y;
-    g = a.grp[gx.x + (v >> 6)];            // a chunk of the word's (cx, cy)
-    const uint32_t w = v - 64u * g.z;
-    ly = w / g.w;
-    i = g.x + g.z + (w - ly * g.w);
-  }
-  // index of the word at column (lx + dx, ly + dy) of the chunk dz above, dx, dy, dz in {-1, 0, 1}; SM_NONE: no such word (a zero word)
-  __device__ __forceinline__ uint32_t at(const StoreMeshArgs &a, int dx, int dy, int dz) const
-  {
-    const int nx = (int)lx + dx, ny = (int)ly + dy;
-    const int cx = nx >> 6, cy = ny >> 6; // -1, 0, 1
-    if (cx == 0 && cy == 0 && dz == 0) return sm_word(g, i, (uint32_t)nx, (uint32_t)ny);
-    const uint32_t j = a.nb[(size_t)i * 27u + (uint32_t)((cx + 1) * 9 + (cy + 1) * 3 + (dz + 1))];
-    if (j == SM_NONE) return SM_NONE;
-    return sm_word(a.grp[j], j, (uint32_t)(nx & 63), (uint32_t)(ny & 63));
-  }
-};
 __device__ __forceinline__ mu64 sm_load(const mu64 *words, uint32_t t) { return t == SM_NONE ? 0ull : words[t]; }
 
 // ---- pass 1: the chunks, once.  A workgroup takes 16 columns of one x plane of a chunk, a wave four of them: four aligned 256-byte
@@ -261,22 +218,17 @@ __global__ __launch_bounds__(256) void store_mesh_face_kernel(StoreMeshArgs a)
 }
 
 // ---- host side
-size_t store_mesh_table_bytes(size_t n_chunks) { return n_chunks * (16 + 16 + 27 * 4); }
+size_t store_mesh_table_bytes(size_t n_chunks) { return store_word_table_bytes(n_chunks) + n_chunks * 27 * 4; }
 
 static StoreMeshArgs store_mesh_args(const ws_store *st, const ws_store::Mesh &q, const StoreMeshCall &c, bool emit)
 {
   StoreMeshArgs a;
-  a.n_chunks = c.n_chunks;
-  a.n_words = c.n_chunks * 4096u;
   a.res = c.res;
   a.any_weight = (c.flags & WS_MESH_ANY_WEIGHT) ? 1u : 0u;
   for (int k = 0; k < 3; ++k) a.lo[k] = c.lo[k], a.hi[k] = c.hi[k];
   const char *tab = static_cast<const char *>(q.table_dev.p);
-  a.grp = reinterpret_cast<const su32x4 *>(tab);
-  a.key = reinterpret_cast<const mi32x4 *>(tab + (size_t)c.n_chunks * 16);
-  a.nb = reinterpret_cast<const uint32_t *>(tab + (size_t)c.n_chunks * 32);
-  a.segs = st->seg_tab.as<uint32_t *>();
-  a.seg_shift = st->seg_shift;
+  store_words_bind(a, st, tab, c.n_chunks);
+  a.nb = reinterpret_cast<const uint32_t *>(tab + store_word_table_bytes(c.n_chunks));
   mesh_bind(a, q, a.n_words, emit);
   return a;
 }

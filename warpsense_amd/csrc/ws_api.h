@@ -43,6 +43,10 @@ void move_axis(MapParams par[2], int axis, int32_t d);
 int query_timing(hipStream_t s, QueryTimer &t, int32_t enable, float *ms_out, const int (*pairs)[2], int n);
 int mesh_corners_fit(const int32_t lo[3], const int32_t hi[3], int32_t res, const char *name);
 int mesh_publish(MeshResult &q, size_t nv, size_t nf, size_t *n_vertices, size_t *n_faces);
+const void *surface_records_dev(const SurfResult *q, size_t *n);
+const float *surface_marker_dev(const SurfResult *q, size_t *n);
+int surface_download(const SurfResult &q, hipStream_t s, const char *name, const char *call, void *records_host, float *marker_host, size_t capacity_points,
+                     size_t *n_out);
 const void *mesh_vertices_dev(const MeshResult *q, size_t *n);
 const uint32_t *mesh_faces_dev(const MeshResult *q, size_t *n);
 int mesh_download(const MeshResult &q, hipStream_t s, void *vertices_host, uint32_t *faces_host, size_t cap_vertices, size_t cap_faces, size_t *n_vertices,
@@ -54,12 +58,45 @@ int raycast_download(const RayResult &q, hipStream_t s, const char *name, const 
 const uint32_t *distance_dev(const DistResult *q, size_t *n);
 int distance_download(const DistResult &q, hipStream_t s, uint32_t *host, size_t capacity, size_t *n_out);
 // the event pairs of ws_debug_*_timing (QueryTimer::read)
-constexpr int MESH_PAIRS[3][2] = {{0, 1}, {1, 2}, {3, 4}}, RAY_PAIRS[3][2] = {{0, 1}, {1, 2}, {2, 3}}, DIST_PAIRS[4][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 4}};
+constexpr int SURF_PAIRS[3][2] = {{0, 1}, {1, 2}, {3, 4}}, MESH_PAIRS[3][2] = {{0, 1}, {1, 2}, {3, 4}}, RAY_PAIRS[3][2] = {{0, 1}, {1, 2}, {2, 3}}, DIST_PAIRS[4][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 4}};
 
-// ---- mesh, ray cast and distance field: one host core each for the window of a map (map_mesh.hip, map_raycast.hip, map_distance.hip)
-// and for the chunks of the store (store_mesh.hip, store_raycast.hip, store_distance.hip).  An entry point checks what is its own, takes
+// ---- surface cloud, mesh, ray cast and distance field: one host core each for the window of a map (map_surface.hip, map_mesh.hip,
+// map_raycast.hip, map_distance.hip) and for the chunks of the store (store_surface.hip, store_mesh.hip, store_raycast.hip,
+// store_distance.hip).  An entry point checks what is its own, takes
 // its lock and hands the shared flow its result holder, its stream and, as lambdas, the launchers of its source; `name` starts the
 // refusal texts.
+
+// The flow of a surface call whose count pass leaves `blocks` workgroup totals, from the scratch to the publish.  own_room: the source
+// has scratch of its own that must grow; grow() grows it (the stream has been synchronised then).  count() enqueues the count pass
+// and the scan, emit(cap) the emit pass, which writes no record at or beyond `cap`; both return at once.
+template <typename Grow, typename Count, typename Emit>
+int surface_run(SurfResult &q, hipStream_t s, size_t blocks, bool marker, size_t *n_out, bool own_room, Grow grow, Count count, Emit emit)
+{
+  WS_TRY(q.total.alloc(1));
+  if (own_room || blocks > q.blk_tot.cap || blocks > q.blk_off.cap)
+  {
+    WS_HIP(hipStreamSynchronize(s));
+    WS_TRY(grow());
+    WS_TRY(q.blk_tot.grow(blocks, sizeof(uint32_t)));
+    WS_TRY(q.blk_off.grow(blocks, sizeof(unsigned long long)));
+  }
+  q.n = 0; // (whatever happens from here on, the old result is gone: its buffers may be replaced)
+  q.has_marker = false;
+  WS_TRY(count());
+  WS_HIP(hipStreamSynchronize(s)); // the one host read the call needs: the output is sized from the counted total
+  const size_t total = (size_t)*q.total.host;
+  WS_TRY(q.rec.grow(total, 16));
+  if (marker) WS_TRY(q.marker.grow(total, 7 * sizeof(float)));
+  if (total)
+  {
+    WS_TRY(emit(marker ? std::min(q.rec.cap, q.marker.cap) : q.rec.cap)); // (the kernel's bound holds for both buffers)
+    WS_HIP(hipStreamSynchronize(s));
+  }
+  q.n = total;
+  q.has_marker = marker;
+  if (n_out) *n_out = total;
+  return WS_OK;
+}
 
 // The flow of a mesh call over `n_words` words (< 2^31), from "the old result is dropped" to the publish.  count() and emit() enqueue
 // the passes of the source and return at once; what a source owes its caller after a failed enqueue is theirs (store_enqueued).

@@ -8,6 +8,10 @@
 
 namespace ws
 {
+// four 32-bit words as one 16-byte access: a record, a row of a chunk table
+typedef uint32_t su32x4 __attribute__((ext_vector_type(4)));
+typedef int32_t mi32x4 __attribute__((ext_vector_type(4)));
+
 __device__ __forceinline__ int32_t wmul(int32_t a, int32_t b) { return (int32_t)((uint32_t)a * (uint32_t)b); }
 __device__ __forceinline__ int32_t wadd(int32_t a, int32_t b) { return (int32_t)((uint32_t)a + (uint32_t)b); }
 __device__ __forceinline__ int32_t wsub(int32_t a, int32_t b) { return (int32_t)((uint32_t)a - (uint32_t)b); }

@@ -387,6 +387,18 @@ struct RayResult
   bool has_grad = false;               // the last call also wrote `grad`
   void release() { timer.release(), hits.release(); for (DevBuf *b : {&dirs, &rec, &grad}) b->release(); }
 };
+// ... a surface call (ws_map::Surface, ws_store::Surface; the one flow is surface_run in ws_api.h): the per-workgroup totals of the
+// count pass and their scan, and the two outputs.  What a source counts per column or per word is its own
+struct SurfResult
+{
+  QueryTimer timer;                    // events around the launches: 0 count 1 scan 2, 3 emit 4
+  DevBuf blk_tot, blk_off;             // uint32 / uint64 [workgroups of the emit pass] qualifying voxels, and their exclusive scan
+  DevCounter total;                    // the scan's last element
+  DevBuf rec, marker;                  // 16-byte records; 7 floats per record
+  size_t n = 0;                        // records of the last call
+  bool has_marker = false;             // the last call also wrote `marker`
+  void release() { timer.release(), total.release(); for (DevBuf *b : {&blk_tot, &blk_off, &rec, &marker}) b->release(); }
+};
 // ... and a distance call (ws_map::Distance, ws_store::Dist; the one flow is distance_run in ws_api.h)
 struct DistResult
 {
@@ -466,17 +478,11 @@ struct ws_map
   uint32_t last_error_bits = 0;  // device error bits already taken from `status`, not yet shown by ws_tsdf_stats
   // The map queries: each keeps the result of its last call and the scratch of its passes apart from the others', all of it allocated
   // on first use and grown on demand.  `mu` serialises the calls that use them (the reference's readers hold a SHARED lock).
-  struct Surface // ws_map_surface (map_surface.hip)
+  struct Surface : ws::SurfResult // ws_map_surface (map_surface.hip)
   {
     std::mutex mu;
-    ws::QueryTimer timer;                // events around the three launches: 0 count 1 scan 2, 3 emit 4
     ws::DevBuf col_cnt;                  // uint32 [columns of the box] qualifying voxels per (x, y) column
-    ws::DevBuf blk_tot, blk_off;         // uint32 / uint64 [workgroups of the count pass] the same per workgroup, and its exclusive scan
-    ws::DevCounter total;                // the scan's last element
-    ws::DevBuf rec, marker;              // 16-byte records; 7 floats per record
-    size_t n = 0;                        // records of the last call
-    bool has_marker = false;             // the last call also wrote `marker`
-    void release() { timer.release(), total.release(); for (ws::DevBuf *b : {&col_cnt, &blk_tot, &blk_off, &rec, &marker}) b->release(); }
+    void release() { SurfResult::release(), col_cnt.release(); }
   } surf;
   struct Mesh : ws::MeshResult // ws_map_mesh (map_mesh.hip)
   {
@@ -634,8 +640,16 @@ struct ws_store
   } tab[ws::STORE_TABLES];
   int tab_next = 0;
   ws::QueryTimer timer[3]; // per axis of a shift: 0 save 1 load 2 (ws_store_save_box / _load_box use the first)
-  // ws_store_mesh (store_mesh.hip), ws_store_raycast (store_raycast.hip) and ws_store_distance (store_distance.hip): the results of the
-  // last calls, apart from each other, and the chunk table of the call in flight; the store's mutex serialises the calls
+  // ws_store_surface (store_surface.hip), ws_store_mesh (store_mesh.hip), ws_store_raycast (store_raycast.hip) and ws_store_distance
+  // (store_distance.hip): the results of the last calls, apart from each other, and the chunk table of the call in flight; the store's
+  // mutex serialises the calls
+  struct Surface : ws::SurfResult
+  {
+    ws::DevBuf mask;                     // uint64 [4096 per listed chunk] the qualifying voxels of a word, bit = z
+    ws::HostBlock table_host;            // bytes, pinned: the call's chunk tables (store_word_table_bytes); free again when the call returns, which synchronises
+    ws::DevBuf table_dev;                // ... and the copy the kernels read
+    void release() { SurfResult::release(), mask.release(), table_host.release(), table_dev.release(); }
+  } surf;
   struct Mesh : ws::MeshResult
   {
     ws::HostBlock table_host;            // bytes, pinned: the call's chunk tables (store_mesh_table_bytes); free again when the call returns, which synchronises
@@ -656,6 +670,7 @@ struct ws_store
   } dist;
   void release()
   {
+    surf.release();
     mesh.release();
     ray.release();
     dist.release();
@@ -750,9 +765,23 @@ struct StoreMeshCall
   uint32_t flags;
   int32_t lo[3], hi[3]; // the box, inclusive world voxels
 };
-size_t store_mesh_table_bytes(size_t n_chunks);
+inline size_t store_word_table_bytes(size_t n_chunks) { return n_chunks * (16 + 16); } // {B, N, P, n} and {cx, cy, cz, slot}: ws_store_words.h
+size_t store_mesh_table_bytes(size_t n_chunks); // those two tables, then the neighbour positions
 int launch_store_mesh_count(ws_store *st, ws_store::Mesh &q, const StoreMeshCall &c);
 int launch_store_mesh_emit(ws_store *st, ws_store::Mesh &q, const StoreMeshCall &c);
+
+// store_surface.hip: the passes of map_surface.hip over the chunks the call lists.  The host has written the two word-space tables of
+// `n_chunks` listed chunks ({B, N, P, n}, then {cx, cy, cz, slot}: the head of the mesh's tables) into q.table_host; the total arrives
+// in q.total.host after a stream synchronise, and the emit pass writes no record at or beyond `cap`
+struct StoreSurfCall
+{
+  uint32_t n_chunks;    // 0 < n_chunks < 2^19: 4096 words each
+  int32_t band, tau, res;
+  int32_t lo[3], hi[3]; // the box, inclusive world voxels
+};
+size_t store_surface_blocks(uint32_t n_chunks); // workgroups of the emit pass: entries of blk_tot and blk_off
+int launch_store_surface_count(ws_store *st, ws_store::Surface &q, const StoreSurfCall &c);
+int launch_store_surface_emit(ws_store *st, ws_store::Surface &q, const StoreSurfCall &c, bool marker, size_t cap);
 
 // store_raycast.hip: the march of ws_raycast.h over the chunks the call lists.  The kernels find a chunk through an open-addressing
 // table key -> slot of a power-of-two size >= 2 x listed chunks (linear probing from store_ray_hash; an empty place has slot

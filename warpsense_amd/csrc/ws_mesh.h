@@ -11,7 +11,6 @@ namespace ws
 {
 typedef unsigned long long mu64;
 typedef uint32_t mu32x2 __attribute__((ext_vector_type(2)));
-typedef int32_t mi32x4 __attribute__((ext_vector_type(4)));
 
 constexpr uint32_t MESH_WORDS = 256; // words per workgroup of the word passes (one per thread)
 
