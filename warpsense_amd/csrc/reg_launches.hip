@@ -65,6 +65,10 @@ __global__ __launch_bounds__(REG_THREADS) void reg_iter_kernel(IterArgs a)
       if (blockIdx.x == 0)
       {
         cur->core = st;
+        // a launch enqueued behind the end of the loop carries the sums of the last update along with the state: the host
+        // reads both from the buffer of the last launch (ws_debug_reg_sums)
+        if (a.k > 0 && !need_update)
+          for (int i = 0; i < 44; ++i) cur->sums[i] = prev->sums[i];
         if (stop && a.host_flag) __hip_atomic_store(a.host_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       }
     }
