@@ -164,7 +164,7 @@ __global__ void k_ring(const MarchFrame *frames, int n_frames, uint64_t base, ui
     const int64_t want = (((v - pos + off) % size) + size) % size;
     const int32_t got = ring_b(div_res_b((int32_t)y, f), f.ringB[0], size);
     if (got != want) fail(rep, y, res, pos, size, got, want);
-    // mirrored: the walk of the free pass divides s y and puts the sign back in the ring constant (tsdf_update.hip, march_free)
+    // mirrored: the walk of the free pass divides s y and puts the sign back in the ring constant (tsdf_free.hip, march_free)
     const uint32_t kc = (uint32_t)f.ringB[0] + 2u * (uint32_t)f.divBq + 1u;
     const int32_t gotm = ring_m(div_res_b((int32_t)-y, f), ~0u, kc, size);
     if (gotm != want) fail(rep, -y, res, pos, size, gotm, want);

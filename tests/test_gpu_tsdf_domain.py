@@ -1,5 +1,5 @@
 """GPU parity of the TSDF update and the registration at the integer-domain edges of the ray set-up (ray_setup_block,
-tsdf_update.hip): odd resolutions and free tau / max_weight, rays on both sides of each term of the `fast` predicate, windows
+tsdf_setup.hip): odd resolutions and free tau / max_weight, rays on both sides of each term of the `fast` predicate, windows
 beyond the biased route's reach (MarchFrame::biased_ok), the record key's step / fan fields at every split of rec_format, and
 key-range rays at the edges of the set-up's workgroups.  Every case states the boundary it is about and asserts -- through a
 numpy restatement of the set-up's per-ray predicates -- that its scan holds rays on both sides of it."""
@@ -428,7 +428,7 @@ def test_key_fields_at_their_last_admitted_value(n, tau):
     check_registration(t, oa, np.ascontiguousarray(pts[pr["ok"] & ~dropped]), res)
 
 
-ERR_RANGE_BIT = 2  # the device's error bit for a ray outside the key range (tsdf_update.hip: ERR_RANGE)
+ERR_RANGE_BIT = 2  # the device's error bit for a ray outside the key range (tsdf_scatter.h: ERR_RANGE)
 
 
 # ---------------------------------------------------------------- 5: key-range rays at the set-up's workgroup edges

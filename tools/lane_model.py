@@ -3,7 +3,7 @@
 
 The SQ counters (tools/pmc_lanes.sh) say how many lanes the EXEC mask leaves on; the branch-free phases of the marches keep
 lanes on whose results are thrown away, so this model walks the synthetic OS1-128 scan with the work decomposition of the
-kernels (warpsense_amd/csrc/tsdf_update.hip) and counts, per phase, lane-slots that carry a live unit of work:
+kernels (warpsense_amd/csrc/tsdf_free.hip, tsdf_tail.hip) and counts, per phase, lane-slots that carry a live unit of work:
 
   free pass   64 rays x 4 lanes per workgroup, lane c walks the steps [c*ch, (c+1)*ch) of the free-space part
               sample phase: live = the lane still has samples; emit phase: batches of 64 queued candidates

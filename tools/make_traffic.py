@@ -65,8 +65,10 @@ def main(prefix):
         except Exception:
             sha = "unknown"
     h = hashlib.sha256()
-    for f_ in ("tsdf_update.hip", "tsdf_integrate.hip", "ws_march.h", "ws_dda.h", "ws_device.h", "reg_reduce.h", "reg_gn.h", "reg_points.h", "reg_exchange.h", "reg_loop.hip", "reg_launches.hip", "reg_server.hip", "reg_batch.hip", "ws_api.h", "api_core.hip", "api_map.hip", "api_query.hip", "api_store.hip", "api_tsdf.hip", "api_reg.hip", "api_scan.hip"):
-        with open(os.path.join(root, "warpsense_amd", "csrc", f_), "rb") as fh:
+    sys.path.insert(0, root)
+    from warpsense_amd.build import dependencies
+    for f_ in dependencies():  # what the library is built from
+        with open(f_, "rb") as fh:
             h.update(fh.read())
     out["git_sha"] = sha
     out["csrc_sha256_16"] = h.hexdigest()[:16]

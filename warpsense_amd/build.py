@@ -9,6 +9,9 @@ WS_EXTRA_FLAGS adds compiler flags, e.g. the instrumentation switches of the ker
 ticks from a few workgroups; never used in the shipped build):
     -DWS_REG_TIMING / -DWS_REG_TIMING_GN   phases of the resident registration loop / of the Gauss-Newton update
     -DWS_REG_BLOCKS=.. -DWS_REG_THREADS=..  grid shape of the registration kernels (default 256 x 512)
+    -DWS_TAIL_TIMING / -DWS_FREE_TIMING / -DWS_RESOLVE_TIMING   busy ticks per workgroup of the tail march / free pass / resolve
+                                            (tsdf_tail.hip, tsdf_free.hip, tsdf_resolve.hip; read by tools/*_timing.py)
+    -DWS_TAIL_KO=.. -DWS_RESOLVE_KO=..      knock-out builds of the tail march / the resolve for timing (bit masks; results wrong)
 """
 from __future__ import annotations
 
@@ -22,11 +25,7 @@ ROOT = os.path.dirname(PKG_DIR)
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libwarpsense_hip.so")
 H5_LIB_PATH = os.path.join(PKG_DIR, "libwarpsense_h5.so")  # optional: global-map file (needs the HDF5 C library)
-SOURCES = ["api_core.hip", "api_map.hip", "api_query.hip", "api_store.hip", "api_tsdf.hip", "api_reg.hip", "api_scan.hip", "tsdf_update.hip", "tsdf_integrate.hip", "reg_routes.hip", "reg_batch.hip", "scan_preprocess.hip", "map_surface.hip", "map_mesh.hip", "map_raycast.hip", "map_distance.hip", "map_store.hip", "store_surface.hip", "store_mesh.hip", "store_raycast.hip", "store_distance.hip"]
-HEADERS = [os.path.join(CSRC, "ws_internal.h"), os.path.join(CSRC, "ws_api.h"), os.path.join(CSRC, "ws_device.h"), os.path.join(CSRC, "ws_march.h"), os.path.join(CSRC, "ws_dda.h"), os.path.join(CSRC, "ws_mesh.h"), os.path.join(CSRC, "ws_raycast.h"), os.path.join(CSRC, "ws_surface.h"), os.path.join(CSRC, "ws_store_words.h"),
-           os.path.join(CSRC, "reg_reduce.h"), os.path.join(CSRC, "reg_gn.h"), os.path.join(CSRC, "reg_points.h"), os.path.join(CSRC, "reg_exchange.h"),
-           os.path.join(CSRC, "reg_loop.hip"), os.path.join(CSRC, "reg_launches.hip"), os.path.join(CSRC, "reg_server.hip"),  # the parts of reg_routes.hip
-           os.path.join(ROOT, "include", "warpsense_hip.h")]
+SOURCES = ["api_core.hip", "api_map.hip", "api_query.hip", "api_store.hip", "api_tsdf.hip", "api_reg.hip", "api_scan.hip", "tsdf_update.hip", "tsdf_setup.hip", "tsdf_marches.hip", "tsdf_resolve.hip", "tsdf_integrate.hip", "reg_routes.hip", "reg_batch.hip", "scan_preprocess.hip", "map_surface.hip", "map_mesh.hip", "map_raycast.hip", "map_distance.hip", "map_store.hip", "store_surface.hip", "store_mesh.hip", "store_raycast.hip", "store_distance.hip"]
 ARCH = "gfx950"
 
 
@@ -44,12 +43,16 @@ def flags() -> list[str]:
             "-Wall", "-Wno-unused-function", *os.environ.get("WS_EXTRA_FLAGS", "").split(), f"-I{os.path.join(ROOT, 'include')}", f"-I{CSRC}"]
 
 
+def dependencies() -> list[str]:
+    """What the library is built from: every header and source in csrc/ (a unit may #include other .hip files) and the public header."""
+    return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hip"))) + [os.path.join(ROOT, "include", "warpsense_hip.h")]
+
+
 def needs_build() -> bool:
     if not os.path.exists(LIB_PATH):
         return True
     t = os.path.getmtime(LIB_PATH)
-    deps = [os.path.join(CSRC, s) for s in SOURCES] + HEADERS
-    return any(os.path.getmtime(d) > t for d in deps)
+    return any(os.path.getmtime(d) > t for d in dependencies())
 
 
 def build_variant(name: str, extra_flags: str, verbose: bool = False) -> str:

@@ -8,7 +8,8 @@
 
 using namespace ws;
 
-constexpr size_t AZ_ALLOC = 1024 * 64 + 8; // direction-bin histogram / offsets (tsdf_update.hip: AZ_BINS + 2 entries)
+constexpr size_t AZ_ALLOC = 1024 * 64 + 8; // direction-bin histogram / offsets
+static_assert(AZ_ALLOC >= (size_t)AZ_BINS + 2, "az_hist / az_off: AZ_BINS + 2 entries (ray_sort_kernel, tsdf_setup.hip)");
 
 // candidate records of the ray tails: the pool of sub-chunks (32 x 8 bytes, one tile each) and the (tile, entry number) ->
 // entry hash for tiles of more than TILE_DIRECT sub-chunks (two slots per sub-chunk of the pool; keys, then uint32 values)

@@ -1,5 +1,5 @@
 // api_tsdf.hip — the entry points of the TSDF update (ws_tsdf_*): what they check, settle and enqueue; the kernels and their launchers
-// are in tsdf_update.hip and tsdf_integrate.hip.
+// are in tsdf_update.hip (the scatter's host logic; its stages in tsdf_setup / tail / free / resolve.hip) and tsdf_integrate.hip.
 #include "ws_api.h"
 
 using namespace ws;

@@ -3,7 +3,8 @@
 //   integrate_sparse_kernel   the same over the touched tiles only (the separate route; the default folds it into tile_resolve_kernel)
 //   box_copy / box_fill       slabs of the ring buffer <-> a dense box (device side of the map shift)
 //   tsdf_stats_kernel         statistics of the last update from the per-workgroup slots
-// Split from tsdf_update.hip in round 6 (that file holds the scatter: set-up, marches, resolve, and the host logic around them).
+// Split from tsdf_update.hip in round 6 (that file held the scatter: set-up, marches, resolve, and the host logic around them; today
+// it is the host logic, and the stages are in tsdf_setup.hip, tsdf_tail.hip, tsdf_free.hip and tsdf_resolve.hip).
 #include "ws_march.h"
 
 namespace ws

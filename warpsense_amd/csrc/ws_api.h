@@ -17,7 +17,7 @@ int invalid(const std::string &msg);
 int range_error(const char *name, const char *what);
 void servers_leave(ws_context *ctx); // a resident server of ws_reg_iterate leaves the stream to whoever enqueues other work
 int ctx_take_errors(ws_context *ctx);
-// every entry point that takes a map looks at the verdict of the scan in flight first (settle_tsdf, tsdf_update.hip)
+// every entry point that takes a map looks at the verdict of the scan in flight first (settle_tsdf, tsdf_update.hip: the host logic of the scatter)
 #define WS_SETTLE(map_ptr)                                                   \
   do                                                                         \
   {                                                                          \

@@ -125,7 +125,7 @@ constexpr int SUB_BITS = 5, SUB_RECS = 1 << SUB_BITS, TILE_DIRECT = 128;
 constexpr uint32_t SUB_WAVE_FIRST = 128; // sub-chunks a wave of the tail march starts with
 constexpr uint32_t SUB_REFILL = 32;      // and what it asks the pool for when it runs low
 #ifndef WS_TAIL_WAVES
-#define WS_TAIL_WAVES 4 // waves per workgroup of the tail march (tsdf_update.hip)
+#define WS_TAIL_WAVES 4 // waves per workgroup of the tail march (tsdf_tail.hip)
 #endif
 constexpr uint32_t SUB_WG_BLOCK = WS_TAIL_WAVES * SUB_WAVE_FIRST; // ... the fixed block of ids of a work item (its waves' shares side by side)
 constexpr uint32_t SUB_ID_LIMIT = (1u << 27) - 2u;  // an entry is id << 5 | fill - 1, + 1 in the hash
@@ -134,6 +134,7 @@ constexpr uint32_t SUB_ID_LIMIT = (1u << 27) - 2u;  // an entry is id << 5 | fil
 // tiles through the list and finds the others by scanning these planes.
 __host__ __device__ inline size_t tile_flag_plane_bytes(int64_t n_tiles) { return ((size_t)n_tiles + 16 + 255) & ~(size_t)255; }
 constexpr uint32_t SUB_LOST = 0xffffffffu; // the pool was exhausted (scan aborted): nothing is written, nothing published
+constexpr int AZ_BINS = 8192; // sort bins of the rays: polar cells around the sensor (ray_setup_block, tsdf_setup.hip); bin AZ_BINS = ray without steps
 
 struct TileEntry // 16 bytes: one touched tile of the scan in flight
 {
