@@ -292,6 +292,64 @@ int ws_map_raycast_download(ws_map *map, void *records_host, int32_t *gradient_h
  * form), of the march and of the gradient pass of the last call */
 int ws_debug_raycast_timing(ws_map *map, int32_t enable, float ms_out[3]);
 
+/* Point sample of a device map: what the map says at n given points -- the fifth query, after surface cloud, mesh, ray cast and
+ * distance field.  Integers only.  All products and quotients are int64, "floor" is floor division.  The result is exact and the same
+ * bytes on every run.
+ *   validity, sample lattice and T(p): those of ws_map_raycast: h = res / 2 truncated, q = p - h, b = floor(q / res), f = q - b res.
+ *     The cell is b + {0,1}^3 and is valid iff all 8 voxels are valid.  WS_SAMPLE_ANY_WEIGHT works as WS_RAYCAST_ANY_WEIGHT.
+ *   input: n x 3 int32, map-frame points in mm, host or device (_dev form; the array must stay untouched until the call returns).  A
+ *     point with a component of magnitude >= 2^30 is a dead point: class 0, record all zero.
+ *   record, 16 bytes per point, in input order:
+ *     int32 d_mm = floor(T(p) / res^3), or 0 if the cell is not valid.
+ *     int32 weight, the smallest corner weight of the cell (of |weight| under ANY_WEIGHT), or 0 if the cell is not valid.
+ *     uint32 cls.
+ *     uint32 raw, the packed entry of the nearest voxel g = floor(p / res) per axis.  g is always one of the cell's corners, so this
+ *       costs no extra load.  It is given whenever g lies in the field, valid or not: inside the window.  Otherwise it is 0.  This is
+ *       the voxel the registration itself looks up.
+ *   classes, decided by band_mm (band_mm <= 0 means the map's tau):
+ *     0 UNKNOWN  cell not valid
+ *     1 FREE     d_mm >= band
+ *     2 SURFACE  -band < d_mm < band
+ *     3 INSIDE   d_mm <= -band
+ *     counts[4] (uint64, may be NULL) receives the number of points per class.  The call synchronises, as the other queries do.
+ *   WS_SAMPLE_GRADIENT: a second array, 3 int32 per point in input order.  It uses the gradient rule of ws_map_raycast at
+ *     g = floor(p / res): value(g + e_k) - value(g - e_k) if all six neighbours are valid, else 0, 0, 0.  Dead points also get 0, 0, 0.
+ *   WS_SAMPLE_SELECT_UNKNOWN / _FREE / _SURFACE / _INSIDE (four flag bits): with any of them set, a third array holds the input points
+ *     whose class is selected, 3 int32 each, in input order.  It is an ordered compaction.  Its length is the sum of the selected
+ *     counts.  It is device memory fit to be handed to ws_tsdf_update_dev, ws_reg_prepare_dev or
+ *     ws_map_raycast_dev(..., WS_RAYCAST_TARGETS).
+ *   errors: WS_ERR_INVALID: unknown flag bits, bad `which`.  WS_ERR_RANGE: res > 1024, n > 2^27.  On a refusal nothing is launched and
+ *     the last result stays.  n == 0 is WS_OK, counts zero, nothing written; the result is then that of a call without points (the
+ *     earlier one is gone, as after any accepted call).  A call that was accepted and then fails (WS_ERR_HIP: an allocation, a
+ *     launch) also leaves no result: the earlier one is dropped before the buffers grow.
+ *   ownership and ordering: the buffers belong to the map and are not allocated before the first call.  They grow on demand and stay
+ *     valid until the next sample call on the same map.  They are apart from the buffers of the other four queries.  The calls are
+ *     read-only on the maps and stream-ordered on the context's stream.  They are serialised inside the library like the other
+ *     queries.  Every output write is bounded by the buffers' capacities. */
+#define WS_SAMPLE_DEFAULT 0u
+#define WS_SAMPLE_ANY_WEIGHT 1u
+#define WS_SAMPLE_GRADIENT 2u
+#define WS_SAMPLE_SELECT_UNKNOWN 4u
+#define WS_SAMPLE_SELECT_FREE 8u
+#define WS_SAMPLE_SELECT_SURFACE 16u
+#define WS_SAMPLE_SELECT_INSIDE 32u
+#define WS_SAMPLE_UNKNOWN 0u
+#define WS_SAMPLE_FREE 1u
+#define WS_SAMPLE_SURFACE 2u
+#define WS_SAMPLE_INSIDE 3u
+int ws_map_sample(ws_map *map, int which, const int32_t *points_host, size_t n, int32_t band_mm, uint32_t flags, uint64_t counts[4]);
+int ws_map_sample_dev(ws_map *map, int which, const int32_t *points_dev, size_t n, int32_t band_mm, uint32_t flags, uint64_t counts[4]);
+const void *ws_map_sample_records_dev(const ws_map *map, size_t *n);     /* device memory, n x 16 bytes; NULL when n == 0 */
+const int32_t *ws_map_sample_gradient_dev(const ws_map *map, size_t *n); /* n x 3 int32; NULL unless the last call asked for it */
+const int32_t *ws_map_sample_selected_dev(const ws_map *map, size_t *n); /* n_selected x 3 int32; NULL unless asked for, or empty */
+/* copies at most capacity_points records (and gradients) and capacity_selected selected points (prefixes) and always reports the
+ * totals; any host pointer may be NULL, and so may n_selected */
+int ws_map_sample_download(ws_map *map, void *records_host, int32_t *gradient_host, int32_t *selected_host, size_t capacity_points, size_t capacity_selected,
+                           size_t *n_out, size_t *n_selected);
+/* Measurement entry, as ws_debug_surface_timing: ms_out receives the device time of the upload of the points (0 for the _dev form), of
+ * the sample pass and of the select passes (scan and emit) of the last call */
+int ws_debug_sample_timing(ws_map *map, int32_t enable, float ms_out[3]);
+
 /* Distance field of a device map: per voxel of a box the squared Euclidean distance, in voxels, to the nearest obstacle of that
  * box -- the untruncated distance a planner, a collision checker or a cost map asks for, which the TSDF (truncated at tau) cannot
  * give.  Integers only: the result is exact and the same bytes on every run.  "d2" is a squared distance in voxels.
@@ -502,6 +560,29 @@ const void *ws_store_raycast_records_dev(const ws_store *st, size_t *n);     /* 
 const int32_t *ws_store_raycast_gradient_dev(const ws_store *st, size_t *n); /* n x 3 int32; NULL unless the last call asked for it */
 /* copies at most capacity_rays records (and gradients: a prefix) and always reports the number of rays; either host pointer may be NULL */
 int ws_store_raycast_download(ws_store *st, void *records_host, int32_t *gradient_host, size_t capacity_rays, size_t *n_out);
+/* The point sample of the store: ws_map_sample over the chunks of the global map, wherever they lie.
+ *   rules: word for word those of ws_map_sample -- the cell, T, the 16-byte record, the classes, the gradient at g, the selection, the
+ *     flags.  The field is that of ws_store_raycast: a voxel of an absent chunk is not valid whatever fill_entry is; voxels outside
+ *     [lo, hi] are not valid; both lo and hi NULL means everything; exactly one of them NULL, or hi < lo, is WS_ERR_INVALID.  `raw` is
+ *     given whenever g lies in a present chunk and inside the box, else 0.
+ *   band_mm <= 0 is WS_ERR_INVALID (the store does not know a tau), and so is map_resolution <= 0.  WS_ERR_RANGE: res > 1024,
+ *     n > 2^27, or the call lists 2^19 present chunks or more.  On a refusal nothing is launched and the last result stays.
+ *   consequence, as for the ray cast: if a window holds the same voxels as the store inside a box, the box is that window, and
+ *     fill_entry has weight 0, then ws_map_sample and ws_store_sample return the same bytes in all three arrays.  (One word is excepted,
+ *     by the rule of `raw` above: where g lies in an absent chunk the store gives 0 and the window gives what ws_store_load_box wrote
+ *     there, fill_entry.)
+ *   The buffers belong to the store, grow on demand, stay valid until the next ws_store_sample on it -- later saves, loads, shifts and
+ *     drops leave them untouched -- and are apart from those of the other queries; the store's lock serialises the calls. */
+int ws_store_sample(ws_store *st, const int32_t lo[3], const int32_t hi[3], const int32_t *points_host, size_t n, int32_t band_mm, int32_t map_resolution,
+                    uint32_t flags, uint64_t counts[4]);
+int ws_store_sample_dev(ws_store *st, const int32_t lo[3], const int32_t hi[3], const int32_t *points_dev, size_t n, int32_t band_mm, int32_t map_resolution,
+                        uint32_t flags, uint64_t counts[4]);
+const void *ws_store_sample_records_dev(const ws_store *st, size_t *n);     /* device memory, n x 16 bytes; NULL when n == 0 */
+const int32_t *ws_store_sample_gradient_dev(const ws_store *st, size_t *n); /* n x 3 int32; NULL unless the last call asked for it */
+const int32_t *ws_store_sample_selected_dev(const ws_store *st, size_t *n); /* n_selected x 3 int32; NULL unless asked for, or empty */
+int ws_store_sample_download(ws_store *st, void *records_host, int32_t *gradient_host, int32_t *selected_host, size_t capacity_points, size_t capacity_selected,
+                             size_t *n_out, size_t *n_selected);
+int ws_debug_store_sample_timing(ws_store *st, int32_t enable, float ms_out[3]);
 /* Measurement entry, as ws_debug_raycast_timing: ms_out receives the device time of the upload (the chunk lookup and, for the host
  * form, the directions), of the march and of the gradient pass of the last call */
 int ws_debug_store_raycast_timing(ws_store *st, int32_t enable, float ms_out[3]);

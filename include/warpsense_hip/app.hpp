@@ -323,6 +323,12 @@ public:
   {
     return global_map_distance(store_, max_dist_vox, unknown_occupied, columns, any_weight, lo, hi);
   }
+  // what the chunks say at given points (visualization.hpp, ws_store_sample)
+  PointSample sample(int resolution, const std::vector<rm::Pointi> &points, int32_t band_mm, bool any_weight = false, bool with_gradient = false, uint32_t select = 0,
+                     const rm::Pointi *lo = nullptr, const rm::Pointi *hi = nullptr)
+  {
+    return global_map_sample(store_, resolution, points, band_mm, any_weight, with_gradient, select, lo, hi);
+  }
   // every chunk merged into the host global map (and through it into its file)
   void flush_to(GlobalMap &g)
   {
@@ -352,6 +358,13 @@ inline RayCast global_map_raycast(DeviceGlobalMap &g, int resolution, const rm::
                                   bool any_weight = false, bool with_gradient = false, const rm::Pointi *lo = nullptr, const rm::Pointi *hi = nullptr, bool targets = false)
 {
   return global_map_raycast(g.handle(), resolution, origin_mm, dirs, max_range_mm, any_weight, with_gradient, lo, hi, targets);
+}
+
+// the point sample of the device global map (visualization.hpp, ws_store_sample)
+inline PointSample global_map_sample(DeviceGlobalMap &g, int resolution, const std::vector<rm::Pointi> &points, int32_t band_mm, bool any_weight = false,
+                                     bool with_gradient = false, uint32_t select = 0, const rm::Pointi *lo = nullptr, const rm::Pointi *hi = nullptr)
+{
+  return global_map_sample(g.handle(), resolution, points, band_mm, any_weight, with_gradient, select, lo, hi);
 }
 
 // ---------------------------------------------------------------------------------------------------- LocalMap
@@ -661,6 +674,23 @@ public:
     WS_CHECK(ws_store_save_box(device_global_map_->handle(), gpu_.tsdf().handle(), WS_MAP_AVG, &wlo.x, &whi.x));
     return global_map_raycast(*device_global_map_, params_.map_resolution, origin_mm, dirs, max_range_mm, any_weight, with_gradient, lo, hi, targets);
   }
+  // What the averaged map says at map-frame points in millimetres (local_map_sample); band_mm <= 0: tau
+  PointSample sample(const std::vector<rm::Pointi> &points, int32_t band_mm = 0, bool any_weight = false, bool with_gradient = false, uint32_t select = 0)
+  {
+    return local_map_sample(gpu_.tsdf(), points, band_mm, any_weight, with_gradient, select);
+  }
+  // The same of everything the run has seen: the window into the device chunks, as global_mesh does, then the sample of the store.
+  // band_mm <= 0: tau
+  PointSample global_sample(const std::vector<rm::Pointi> &points, int32_t band_mm = 0, bool any_weight = false, bool with_gradient = false, uint32_t select = 0,
+                            const rm::Pointi *lo = nullptr, const rm::Pointi *hi = nullptr)
+  {
+    if (!device_global_map_) throw std::logic_error("global_sample: no DeviceGlobalMap attached");
+    wait_shift();
+    rm::Pointi wlo, whi;
+    local_map_.window(wlo, whi);
+    WS_CHECK(ws_store_save_box(device_global_map_->handle(), gpu_.tsdf().handle(), WS_MAP_AVG, &wlo.x, &whi.x));
+    return global_map_sample(*device_global_map_, params_.map_resolution, points, band_mm > 0 ? band_mm : params_.tau, any_weight, with_gradient, select, lo, hi);
+  }
   // The cost map of everything the run has seen: the window into the device chunks, as global_mesh does, then the distance field of
   // the store -- nothing leaves the device but the records
   DistanceField global_distance(int32_t max_dist_vox, bool unknown_occupied = false, bool columns = false, bool any_weight = false, const rm::Pointi *lo = nullptr,
@@ -703,6 +733,10 @@ struct AppParams
   // the pose change between the last two scans (the identity for the first two)
   bool deskew_constant_velocity = false;
   uint32_t sweep_bins = 1024; // poses per sweep; also the columns of the default rule (by index, ring-major)
+  // true: the points of a scan that the averaged map holds as FREE at the scan's pose (ws_map_sample, band tau: observed free space, the
+  // sign of a moving object) are dropped on the device before the update and the registration; App::last_rejected() counts them.  An
+  // empty map is UNKNOWN everywhere: the first scan drops nothing
+  bool reject_dynamic = false;
 };
 
 // wall-clock microseconds of the stages of one cloud_callback -- the reference's RuntimeEvaluator forms "preprocess", "tsdf",
@@ -756,6 +790,18 @@ public:
     }
     else
       n_pts = pre_.preprocess(cloud_xyz, n, stride_floats, pose_, params_.hot.map_resolution); // App::preprocess :119-148
+    const int32_t *pts_dev = pre_.points_dev();
+    last_rejected_ = 0;
+    if (params_.reject_dynamic)
+    {
+      // The kept points are the sample's selection: they live in the map's sample buffer until the next sample call on this map, so
+      // nothing else may sample the map before this callback's update and registration have taken them
+      uint64_t counts[4] = {0, 0, 0, 0};
+      WS_CHECK(ws_map_sample_dev(node_.gpu().tsdf().handle(), WS_MAP_AVG, pts_dev, n_pts, 0,
+                                 WS_SAMPLE_SELECT_UNKNOWN | WS_SAMPLE_SELECT_SURFACE | WS_SAMPLE_SELECT_INSIDE, counts));
+      pts_dev = ws_map_sample_selected_dev(node_.gpu().tsdf().handle(), &n_pts);
+      last_rejected_ = (size_t)counts[WS_SAMPLE_FREE];
+    }
     const clk::time_point t1 = clk::now();
     if (!initialized_ || distance_m(last_tsdf_pose_, pose_) > 0.3f || shifted_)
     {
@@ -763,7 +809,7 @@ public:
       last_tsdf_pose_ = pose_;
       rm::Pointi pos_rm, up_rm;
       node_.gpu().convert_pose_to_gpu(pose_, pos_rm, up_rm);
-      node_.gpu().tsdf().update_tsdf_dev(pre_.points_dev(), n_pts, pos_rm, up_rm);
+      node_.gpu().tsdf().update_tsdf_dev(pts_dev, n_pts, pos_rm, up_rm);
       shifted_ = false;
       ++n_updates_;
     }
@@ -773,7 +819,7 @@ public:
       pre = *pretransform;
     else
       pre.setIdentity();
-    node_.gpu().registration().prepare_registration_dev(pre_.points_dev(), n_pts);
+    node_.gpu().registration().prepare_registration_dev(pts_dev, n_pts);
     const rm::Matrix4x4f transform =
         node_.gpu().registration().register_cloud(node_.gpu().tsdf().device_map(), pre, params_.hot.max_iterations, params_.hot.it_weight_gradient,
                                                   params_.hot.epsilon, params_.hot.map_resolution, &last_iterations_);
@@ -857,6 +903,7 @@ public:
   int last_iterations() const { return last_iterations_; }
   const StageTimes &last_times() const { return times_; }
   size_t last_points() const { return last_points_; }
+  size_t last_rejected() const { return last_rejected_; } // AppParams::reject_dynamic: points of the last scan dropped as FREE
   int n_updates() const { return n_updates_; }
   int n_shifts() const { return n_shifts_; }
   MappingNode &node() { return node_; }
@@ -886,7 +933,7 @@ private:
   rm::Matrix4x4f last_pose_, before_last_pose_; // pose_ after the last two scans (last_motion)
   bool initialized_ = false, shifted_ = false;
   int last_iterations_ = 0, n_updates_ = 0, n_shifts_ = 0, n_scans_ = 0;
-  size_t last_points_ = 0;
+  size_t last_points_ = 0, last_rejected_ = 0;
   StageTimes times_;
 };
 

@@ -6,6 +6,7 @@
 //   global_map_mesh      (no counterpart)                                                     the mesh of the device global map, over ws_store_mesh
 //   local_map_raycast    (no counterpart: the reference leaves all viewing to RViz)            a predicted scan, over ws_map_raycast
 //   global_map_raycast   (no counterpart)                                                     a predicted scan from anywhere the run has been, over ws_store_raycast
+//   local_map_sample / global_map_sample   (no counterpart)                                   what the map says at given points, over ws_map_sample / ws_store_sample
 //   local_map_distance   (no counterpart: the reference has no distance field)                   a cost map, over ws_map_distance
 //   global_map_distance  (no counterpart)                                                     the cost map of the whole run, over ws_store_distance
 //   local_map_skeleton   publish_local_map_skeleton  map.h:175-227   the 24 end points of the window's line list (host only)
@@ -164,6 +165,71 @@ inline RayCast global_map_raycast(ws_store *store, int resolution, const rmagine
   size_t got = 0;
   WS_CHECK(ws_store_raycast_download(store, dirs.empty() ? nullptr : out.records.data(), with_gradient && !dirs.empty() ? &out.gradient.data()->x : nullptr,
                                      dirs.size(), &got));
+  return out;
+}
+
+struct SampleRecord // one record of ws_map_sample
+{
+  int32_t d_mm;   // floor(T(p) / res^3); 0 where the cell is not valid
+  int32_t weight; // the smallest corner weight of the cell; 0 where it is not valid
+  uint32_t cls;   // WS_SAMPLE_UNKNOWN, _FREE, _SURFACE, _INSIDE
+  uint32_t raw;   // the packed entry of the nearest voxel; 0 where the field has none
+};
+static_assert(sizeof(SampleRecord) == 16, "ws_map_sample writes 16-byte records");
+
+struct PointSample
+{
+  std::vector<SampleRecord> records;      // in input order
+  std::vector<rmagine::Pointi> gradient;  // with_gradient: value(g + e_k) - value(g - e_k) at the nearest voxel; else empty
+  std::vector<rmagine::Pointi> selected;  // the input points of the selected classes, in input order
+  uint64_t counts[4] = {0, 0, 0, 0};      // points per class
+};
+
+namespace detail
+{
+// select: bit c set selects class c (WS_SAMPLE_UNKNOWN .. WS_SAMPLE_INSIDE)
+inline uint32_t sample_flags(bool any_weight, bool with_gradient, uint32_t select)
+{
+  return (any_weight ? WS_SAMPLE_ANY_WEIGHT : 0u) | (with_gradient ? WS_SAMPLE_GRADIENT : 0u) | ((select & 15u) * WS_SAMPLE_SELECT_UNKNOWN);
+}
+inline void sample_room(PointSample &out, size_t n, bool with_gradient, uint32_t select)
+{
+  out.records.resize(n);
+  if (with_gradient) out.gradient.resize(n);
+  size_t n_sel = 0;
+  for (int c = 0; c < 4; ++c)
+    if ((select >> c) & 1u) n_sel += (size_t)out.counts[c];
+  out.selected.resize(n_sel);
+}
+} // namespace detail
+
+// What map `which` says at map-frame points in millimetres (the rules: warpsense_hip.h at ws_map_sample).  band_mm <= 0: the map's
+// tau.  select: bit c set selects class c; the input points of the selected classes come back in input order.
+inline PointSample local_map_sample(cuda::TSDFCuda &tsdf, const std::vector<rmagine::Pointi> &points, int32_t band_mm = 0, bool any_weight = false,
+                                    bool with_gradient = false, uint32_t select = 0, int which = WS_MAP_AVG)
+{
+  PointSample out;
+  WS_CHECK(ws_map_sample(tsdf.handle(), which, points.empty() ? nullptr : &points.data()->x, points.size(), band_mm,
+                         detail::sample_flags(any_weight, with_gradient, select), out.counts));
+  detail::sample_room(out, points.size(), with_gradient, select);
+  size_t got = 0, got_sel = 0;
+  WS_CHECK(ws_map_sample_download(tsdf.handle(), out.records.data(), out.gradient.empty() ? nullptr : &out.gradient.data()->x,
+                                  out.selected.empty() ? nullptr : &out.selected.data()->x, points.size(), out.selected.size(), &got, &got_sel));
+  return out;
+}
+
+// The same of the global map in device memory (the rules: warpsense_hip.h at ws_store_sample), through everything the store's chunks
+// hold inside the inclusive world-voxel box [lo, hi] (both nullptr: everything).  resolution: the map's, in mm per voxel; band_mm > 0.
+inline PointSample global_map_sample(ws_store *store, int resolution, const std::vector<rmagine::Pointi> &points, int32_t band_mm, bool any_weight = false,
+                                     bool with_gradient = false, uint32_t select = 0, const rmagine::Pointi *lo = nullptr, const rmagine::Pointi *hi = nullptr)
+{
+  PointSample out;
+  WS_CHECK(ws_store_sample(store, lo ? &lo->x : nullptr, hi ? &hi->x : nullptr, points.empty() ? nullptr : &points.data()->x, points.size(), band_mm, resolution,
+                           detail::sample_flags(any_weight, with_gradient, select), out.counts));
+  detail::sample_room(out, points.size(), with_gradient, select);
+  size_t got = 0, got_sel = 0;
+  WS_CHECK(ws_store_sample_download(store, out.records.data(), out.gradient.empty() ? nullptr : &out.gradient.data()->x,
+                                    out.selected.empty() ? nullptr : &out.selected.data()->x, points.size(), out.selected.size(), &got, &got_sel));
   return out;
 }
 

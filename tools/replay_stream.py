@@ -96,6 +96,8 @@ def main():
                     "scan k - 1 and scan k (synthetic.os1_128_sweep; the first one stands), instead of a snapshot from the pose of scan k")
     ap.add_argument("--deskew", action="store_true", help="App(deskew='constant-velocity'): one pose per firing column, the motion during a sweep "
                     "taken from the last two registered poses")
+    ap.add_argument("--reject-dynamic", action="store_true", help="App(reject_dynamic=True): the points of a scan that the map holds as observed free "
+                    "space are dropped on the device before the update and the registration; prints the number dropped per scan")
     args = ap.parse_args()
     if args.global_mesh_ply and not args.device_global_map:
         ap.error("--global-mesh-ply requires --device-global-map")
@@ -113,7 +115,7 @@ def main():
                       W.RegistrationParams(200, 0.1, 0.03))
     t0 = time.perf_counter()
     app = W.App(params, args.h5, async_shift=args.async_shift, shift="device" if args.device_global_map else None,
-                deskew="constant-velocity" if args.deskew else None)
+                deskew="constant-velocity" if args.deskew else None, reject_dynamic=args.reject_dynamic)
     t_setup = time.perf_counter() - t0
     he = tuple(1000.0 * r for r in args.room)
     clouds = []
@@ -237,6 +239,9 @@ def main():
                           "chunks": app.gpu_.device_global_map_.count(), "call_s": tg}
         print(f"global raycast from the first pose: hit share {share:.3f} (the window's raycast from the same pose: {share_w:.3f}), "
               f"{global_raycast['chunks']} chunks, {1000.0 * tg:.2f} ms (save_box + ws_store_raycast + download)", file=sys.stderr)
+    if args.reject_dynamic:
+        for k, t in enumerate(app.timings):
+            print(f"scan {k + 1}: rejected {t['rejected']} of {t['points'] + t['rejected']} points in {1000.0 * t['reject']:.2f} ms", file=sys.stderr)
     stages = {}
     for key in ("preprocess", "tsdf", "registration", "total"):
         vals = [t[key] for t in app.timings if key in t]

@@ -39,12 +39,19 @@ EXPORTS = [
     "ws_store_distance", "ws_store_distance_dev", "ws_store_distance_download", "ws_debug_store_distance_timing",
     "ws_store_surface", "ws_store_surface_records_dev", "ws_store_surface_marker_dev", "ws_store_surface_download", "ws_debug_store_surface_timing",
     "ws_store_mesh", "ws_store_mesh_vertices_dev", "ws_store_mesh_faces_dev", "ws_store_mesh_download", "ws_debug_store_mesh_timing",
+    "ws_map_sample", "ws_map_sample_dev", "ws_map_sample_records_dev", "ws_map_sample_gradient_dev", "ws_map_sample_selected_dev", "ws_map_sample_download",
+    "ws_debug_sample_timing",
+    "ws_store_sample", "ws_store_sample_dev", "ws_store_sample_records_dev", "ws_store_sample_gradient_dev", "ws_store_sample_selected_dev",
+    "ws_store_sample_download", "ws_debug_store_sample_timing",
     "ws_store_raycast", "ws_store_raycast_dev", "ws_store_raycast_records_dev", "ws_store_raycast_gradient_dev", "ws_store_raycast_download",
     "ws_debug_store_raycast_timing", "ws_debug_store_raycast_table", "ws_debug_store_raycast_find",
 ]
 WS_SURFACE_RECORDS, WS_SURFACE_MARKER = 0, 1
 WS_MESH_DEFAULT, WS_MESH_ANY_WEIGHT = 0, 1
 WS_RAYCAST_DEFAULT, WS_RAYCAST_ANY_WEIGHT, WS_RAYCAST_GRADIENT, WS_RAYCAST_TARGETS = 0, 1, 2, 4
+WS_SAMPLE_DEFAULT, WS_SAMPLE_ANY_WEIGHT, WS_SAMPLE_GRADIENT = 0, 1, 2
+WS_SAMPLE_SELECT_UNKNOWN, WS_SAMPLE_SELECT_FREE, WS_SAMPLE_SELECT_SURFACE, WS_SAMPLE_SELECT_INSIDE = 4, 8, 16, 32
+SAMPLE_CLASSES = ("unknown", "free", "surface", "inside")  # class c of a sample record; WS_SAMPLE_SELECT_* is 4 << c
 WS_DISTANCE_DEFAULT, WS_DISTANCE_ANY_WEIGHT, WS_DISTANCE_UNKNOWN_OCCUPIED, WS_DISTANCE_COLUMNS = 0, 1, 2, 4
 
 
@@ -171,6 +178,17 @@ def load() -> C.CDLL:
     L.ws_map_raycast_gradient_dev.restype = vp
     L.ws_map_raycast_download.argtypes = [vp, vp, vp, sz, P(sz)]
     L.ws_debug_raycast_timing.argtypes = [vp, i32, vp]
+    L.ws_map_sample.argtypes = [vp, C.c_int, vp, sz, i32, u32, vp]
+    L.ws_map_sample_dev.argtypes = [vp, C.c_int, vp, sz, i32, u32, vp]
+    L.ws_store_sample.argtypes = [vp, vp, vp, vp, sz, i32, i32, u32, vp]
+    L.ws_store_sample_dev.argtypes = [vp, vp, vp, vp, sz, i32, i32, u32, vp]
+    for owner in ("map", "store"):
+        for part in ("records", "gradient", "selected"):
+            f = getattr(L, f"ws_{owner}_sample_{part}_dev")
+            f.argtypes, f.restype = [vp, P(sz)], vp
+        getattr(L, f"ws_{owner}_sample_download").argtypes = [vp, vp, vp, vp, sz, sz, P(sz), P(sz)]
+    L.ws_debug_sample_timing.argtypes = [vp, i32, vp]
+    L.ws_debug_store_sample_timing.argtypes = [vp, i32, vp]
     L.ws_map_distance.argtypes = [vp, C.c_int, vp, vp, i32, u32, P(sz)]
     L.ws_map_distance_dev.argtypes = [vp, P(sz)]
     L.ws_map_distance_dev.restype = vp

@@ -87,6 +87,12 @@ VERT = np.dtype([("x_mm", "<i4"), ("y_mm", "<i4"), ("z_mm", "<i4"), ("weight", "
 RAY = np.dtype([("x_mm", "<i4"), ("y_mm", "<i4"), ("z_mm", "<i4"), ("range_mm", "<i4")])
 
 
+# one record of ws_map_sample: the interpolated signed distance in mm, the smallest corner weight of the cell, the class (0 unknown,
+# 1 free, 2 surface, 3 inside) and the packed entry of the nearest voxel (16 bytes)
+SAMPLE = np.dtype([("d_mm", "<i4"), ("weight", "<i4"), ("cls", "<u4"), ("raw", "<u4")])
+SAMPLE_CLASSES = _lib.SAMPLE_CLASSES
+
+
 def distance_class(rec):
     """The class bits of ws_map_distance records: 2 occupied, 1 free, 0 unknown (uint8)."""
     return (np.asarray(rec, dtype=np.uint32) >> np.uint32(30)).astype(np.uint8)
@@ -551,6 +557,62 @@ def _raycast_call(L, name, handle, lead, origin_mm, dirs, max_range_mm, tail, an
     return rec, grad, int(hits.value)
 
 
+class _SampleSelection:
+    """what keeps the selection of a sample call reachable as DevicePoints: the owner of the buffers, and the way back to the host"""
+
+    def __init__(self, L, name, owner, n_sel):
+        self._L, self._name, self._owner, self._n = L, name, owner, int(n_sel)
+
+    def download(self) -> np.ndarray:
+        out = np.empty((self._n, 3), dtype=np.int32)
+        n, ns = C.c_size_t(0), C.c_size_t(0)
+        check(getattr(self._L, self._name + "_download")(self._owner.handle, None, None, _ptr(out), 0, self._n, C.byref(n), C.byref(ns)), self._name + "_download")
+        if int(ns.value) != self._n:
+            raise WsError("sample: another call replaced the selection before it was downloaded")
+        return out
+
+
+def _sample_flags(any_weight, gradient, select):
+    flags = (_lib.WS_SAMPLE_ANY_WEIGHT if any_weight else 0) | (_lib.WS_SAMPLE_GRADIENT if gradient else 0)
+    for name in ([select] if isinstance(select, str) else (select or ())):
+        if name not in SAMPLE_CLASSES:
+            raise WsError(f"sample: select names classes out of {SAMPLE_CLASSES}, not {name!r}")
+        flags |= _lib.WS_SAMPLE_SELECT_UNKNOWN << SAMPLE_CLASSES.index(name)
+    return flags
+
+
+def _sample_call(L, name, owner, lead, points, band_mm, tail, any_weight, gradient, select, device):
+    """The point sample `name` (ws_map_sample, ws_store_sample; name + "_dev" for points on the device) on owner.handle and its
+    result: `lead` are the arguments of the entry point before the points, `tail` those between the band and the flags.  Returns
+    (records, counts, gradient | None, selection | None); owner keeps device results' memory alive."""
+    n = int(points.shape[0])
+    flags = _sample_flags(any_weight, gradient, select)
+    selecting = (flags >> 2) != 0
+    counts = np.zeros(4, dtype=np.uint64)
+    if _is_device(points):
+        name_call, pts = name + "_dev", points
+    else:
+        name_call, pts = name, np.ascontiguousarray(points, dtype=np.int32).reshape(-1, 3)
+    check(getattr(L, name_call)(owner.handle, *lead, _ptr(pts), n, int(band_mm), *tail, flags, _ptr(counts)), name_call)
+    n_sel = int(sum(int(counts[c]) for c in range(4) if (flags >> (2 + c)) & 1))
+    cnt = C.c_size_t(0)
+    if device:
+        rec = _device_tensor(getattr(L, name + "_records_dev")(owner.handle, C.byref(cnt)), (n, 4), "<i4", owner)
+        if int(cnt.value) != n:
+            raise WsError("sample: another call replaced the result")
+        grad = _device_tensor(getattr(L, name + "_gradient_dev")(owner.handle, C.byref(cnt)), (n, 3), "<i4", owner) if gradient else None
+        sel = DevicePoints(getattr(L, name + "_selected_dev")(owner.handle, C.byref(cnt)) or 0, n_sel, _SampleSelection(L, name, owner, n_sel)) if selecting else None
+        return rec, counts, grad, sel
+    rec = np.empty(n, dtype=SAMPLE)
+    grad = np.empty((n, 3), dtype=np.int32) if gradient else None
+    sel = np.empty((n_sel, 3), dtype=np.int32) if selecting else None
+    got, got_sel = C.c_size_t(0), C.c_size_t(0)
+    check(getattr(L, name + "_download")(owner.handle, _ptr(rec), _ptr(grad), _ptr(sel), n, n_sel, C.byref(got), C.byref(got_sel)), name + "_download")
+    if int(got.value) != n or (selecting and int(got_sel.value) != n_sel):
+        raise WsError("sample: another call replaced the result before it was downloaded")
+    return rec, counts, grad, sel
+
+
 def _distance_call(L, name, owner, lead, lo, hi, max_dist_vox, unknown_occupied, columns, any_weight, device, default_shape):
     """The distance call `name` (ws_map_distance, ws_store_distance) on owner.handle and its result: `lead` are the arguments of the
     entry point before the box, default_shape() the extent of the box that lo = hi = None stands for.  owner keeps a device tensor's
@@ -698,6 +760,22 @@ class DeviceGlobalMap:
         rec, grad, self.last_hits = _raycast_call(self._L, "ws_store_raycast", self.handle, box, origin_mm, dirs, max_range_mm, (int(resolution),),
                                                   any_weight, gradient, targets)
         return rec, grad
+
+    def sample(self, resolution, points, band_mm, lo=None, hi=None, any_weight=False, gradient=False, select=None, device=False):
+        """What the chunks on the device say at `points` (ws_store_sample; the rules are those of ws_map_sample, stated in
+        include/warpsense_hip.h), through everything the store holds inside the inclusive world-voxel box [lo, hi] (both None:
+        everything).  Voxels of absent chunks are not valid.  resolution: the map's, in mm per voxel; band_mm > 0.  The other arguments
+        and the returned (records, counts, gradient | None, selection | None) are those of DeviceMapMemWrapper.sample."""
+        if (lo is None) != (hi is None):
+            raise WsError("sample: give both lo and hi, or neither")
+        box = (_ptr(_i3(lo)) if lo is not None else None, _ptr(_i3(hi)) if hi is not None else None)
+        return _sample_call(self._L, "ws_store_sample", self, box, points, band_mm, (int(resolution),), any_weight, gradient, select, device)
+
+    def sample_timing(self, enable: int = -1):
+        """device milliseconds of the upload, the sample pass and the select passes of the last sample() (ws_debug_store_sample_timing)"""
+        ms = (C.c_float * 3)()
+        check(self._L.ws_debug_store_sample_timing(self.handle, int(enable), ms), "ws_debug_store_sample_timing")
+        return tuple(float(v) for v in ms)
 
     def raycast_timing(self, enable: int = -1):
         """device milliseconds of the upload, the march and the gradient pass of the last raycast() (ws_debug_store_raycast_timing)"""
@@ -952,6 +1030,22 @@ class DeviceMapMemWrapper:
         rec, grad, self.last_hits = _raycast_call(self._t._L, "ws_map_raycast", self._t.handle, (self._which,), origin_mm, dirs, max_range_mm, (),
                                                   any_weight, gradient, targets)
         return rec, grad
+
+    def sample(self, points, band_mm=None, any_weight=False, gradient=False, select=None, device=False):
+        """What this map says at `points` (ws_map_sample; the rules are stated in include/warpsense_hip.h): (n, 3) int32 map-frame
+        points in millimetres, a numpy array or a device array (a CUDA tensor, DevicePoints).  band_mm: the half-width of the SURFACE
+        class (None: the map's tau).  any_weight: voxels with a negative weight count as observed too (the rule of the registration).
+        select: class names out of SAMPLE_CLASSES ("unknown", "free", "surface", "inside"); the input points of those classes come
+        back in input order.
+
+        Returns (records, counts, gradient, selection): a numpy array of dtype SAMPLE (d_mm, weight, cls, raw) in input order; the
+        number of points per class (uint64 [4]); with gradient=True an (n, 3) int32 array of central differences of the TSDF value
+        at the nearest voxel (zeros where a neighbour is unobserved), else None; with `select` the (k, 3) int32 selected points, else
+        None.  device=True: records and gradient are torch tensors on the GPU ((n, 4) / (n, 3) int32) and the selection is a
+        DevicePoints that update_tsdf and prepare_registration accept; all three ALIAS the library's buffers and are valid until the
+        next sample() on this TSDFCuda."""
+        return _sample_call(self._t._L, "ws_map_sample", self._t, (self._which,), points, 0 if band_mm is None else band_mm, (), any_weight, gradient, select,
+                            device)
 
     def distance(self, lo=None, hi=None, max_dist_vox=20, unknown_occupied=False, columns=False, any_weight=False, device=False):
         """The distance field of this map on the device (ws_map_distance; the rules are stated in include/warpsense_hip.h): per
@@ -1536,6 +1630,42 @@ class TSDFMapping:
             points_mm = points_mm.to_host() if hasattr(points_mm, "to_host") else points_mm.cpu().numpy()
         d = np.asarray(points_mm, dtype=np.float64).reshape(-1, 3) - origin.astype(np.float64)
         return np.where(rec["range_mm"] >= 0, rec["range_mm"].astype(np.float64) - np.sqrt(np.sum(d * d, axis=1)), np.nan)
+
+    def sample(self, points_mm, **kw):
+        """DeviceMapMemWrapper.sample on avg_map() at map-frame points (n x 3 int32 millimetres, numpy or on the device), under the
+        mapping's lock like a reader.  Returns (records, counts, gradient | None, selection | None)."""
+        with self.mutex_:
+            return self.tsdf_.avg_map().sample(points_mm, **kw)
+
+    def global_sample(self, points_mm, band_mm=None, **kw):
+        """sample against the chunks of device_global_map: the window goes into the chunks as in global_raycast, then
+        DeviceGlobalMap.sample at the map's resolution.  band_mm None: the map's tau.  Keywords: lo, hi, any_weight, gradient, select,
+        device."""
+        if self.device_global_map_ is None:
+            raise WsError("global_sample: this TSDFMapping has no device_global_map")
+        self.wait_shift()
+        with self.mutex_:
+            lo, hi = self.local_map_.window()
+            self.device_global_map_.save_box(self.tsdf_, lo, hi)
+            return self.device_global_map_.sample(int(self.params_.map.resolution), points_mm, int(self.params_.map.tau) if band_mm is None else band_mm, **kw)
+
+    def scan_consistency(self, points_mm, pose=None, band_mm=None):
+        """How a scan agrees with the averaged map, in one pass over its points: points_mm are the scan in the map frame (n x 3 int32
+        millimetres, numpy or on the device); with `pose` (4 x 4, translation in mm) they are in the sensor frame and are moved by it
+        first (on the host, rounded to nearest).  Returns a dict: the fractions "unknown", "free", "surface", "inside" of the points
+        per class of sample() at band_mm (None: tau), and "mean_abs_d_mm", the mean |d_mm| over the SURFACE class (NaN without
+        one)."""
+        if pose is not None:
+            if _is_device(points_mm):
+                points_mm = points_mm.to_host() if hasattr(points_mm, "to_host") else points_mm.cpu().numpy()
+            P = np.asarray(pose, dtype=np.float64).reshape(4, 4)
+            points_mm = np.rint(np.asarray(points_mm, dtype=np.float64).reshape(-1, 3) @ P[:3, :3].T + P[:3, 3]).astype(np.int32)
+        rec, counts, _, _ = self.sample(points_mm, band_mm=band_mm)
+        n = max(int(counts.sum()), 1)
+        out = {name: float(counts[c]) / n for c, name in enumerate(SAMPLE_CLASSES)}
+        surf = rec["cls"] == 2
+        out["mean_abs_d_mm"] = float(np.mean(np.abs(rec["d_mm"][surf].astype(np.float64)))) if surf.any() else float("nan")
+        return out
 
     def _global_range_mm(self, origin):
         """the diagonal of the bounding box of the present chunks in mm, capped so that |origin| + range + 2 res fits int32"""

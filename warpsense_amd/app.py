@@ -22,7 +22,10 @@ from .api import (DeviceGlobalMap, GlobalMap, LocalMap, Params, ScanPreprocessor
 
 class App:
     def __init__(self, params: Params, filename: str | None = None, ctx=None, max_points: int = 128 * 1024, async_shift: bool = False, shift: str | None = None,
-                 deskew: str | None = None, sweep_bins: int | None = None):
+                 deskew: str | None = None, sweep_bins: int | None = None, reject_dynamic: bool = False):
+        # reject_dynamic: the points of a scan that the averaged map holds as FREE at the scan's pose (TSDFMapping.sample: observed
+        # free space at least tau in front of any surface -- the sign of a moving object) are dropped on the device before the update
+        # and the registration; timings[i]["rejected"] counts them.  An empty map is UNKNOWN everywhere: the first scan drops nothing
         # deskew: None -- every point of a scan is transformed with the one pose of the scan (the reference); "constant-velocity" --
         # one pose per time bin of the sweep (ScanPreprocessor.preprocess_sweep, `sweep_bins` of them, default 1024), the motion
         # during the sweep taken to be the pose change between the last two scans
@@ -36,6 +39,7 @@ class App:
         if deskew not in (None, "constant-velocity"):
             raise ValueError(f"App: deskew must be None or 'constant-velocity', not {deskew!r}")
         self.deskew_ = deskew
+        self.reject_dynamic_ = bool(reject_dynamic)
         self.sweep_bins_ = 1024 if sweep_bins is None else int(sweep_bins)
         self.async_shift_ = bool(async_shift) if shift is None else shift == "async"
         self.device_shift_ = shift == "device"
@@ -117,6 +121,13 @@ class App:
         t0 = time.perf_counter()
         scan_points = self.preprocess(cloud, sweep_motion, sweep)
         t["preprocess"] = time.perf_counter() - t0
+        if self.reject_dynamic_:
+            tr = time.perf_counter()
+            # The kept points ALIAS the sample buffer of the mapping until its next sample(): nothing else (scan_consistency from
+            # another thread, say) may sample this mapping before the update and the registration below have taken them
+            _, counts, _, scan_points = self.gpu_.sample(scan_points, select=("unknown", "surface", "inside"), device=True)
+            t["reject"] = time.perf_counter() - tr
+            t["rejected"] = int(counts[1])
         distance_tsdf = np.linalg.norm(self.last_tsdf_pose_[:3, 3] / np.float32(1000) - self.pose_[:3, 3] / np.float32(1000))
         if not self.initialized_ or distance_tsdf > 0.3 or self.shifted_:
             self.initialized_ = True

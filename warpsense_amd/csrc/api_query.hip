@@ -1,5 +1,5 @@
-// api_query.hip — the queries of a map's window: surface cloud, mesh, ray cast and distance field (ws_map_surface, ws_map_mesh,
-// ws_map_raycast, ws_map_distance and what goes with each), and the parts of the query cores of ws_api.h that are no templates.
+// api_query.hip — the queries of a map's window: surface cloud, mesh, ray cast, point sample and distance field (ws_map_surface, ws_map_mesh,
+// ws_map_raycast, ws_map_sample, ws_map_distance and what goes with each), and the parts of the query cores of ws_api.h that are no templates.
 #include <algorithm>
 
 #include "ws_api.h"
@@ -232,6 +232,90 @@ int ws_debug_raycast_timing(ws_map *m, int32_t enable, float ms_out[3])
   if (!m) return invalid("ws_debug_raycast_timing: map is NULL");
   std::lock_guard<std::mutex> lock(m->ray.mu);
   return query_timing(m->ctx->stream, m->ray.timer, enable, ms_out, RAY_PAIRS, 3);
+}
+
+// ---- point sample: what the host cores of ws_api.h (sample_check, sample_run) need beside them, for the window of a map here and
+// for the chunks of the store in api_store.hip
+const void *ws::sample_records_dev(const SampleResult *q, size_t *n)
+{
+  if (n) *n = q ? q->n : 0;
+  return q && q->n ? q->rec.p : nullptr;
+}
+
+const int32_t *ws::sample_gradient_dev(const SampleResult *q, size_t *n)
+{
+  const bool have = q && q->has_grad && q->n;
+  if (n) *n = have ? q->n : 0;
+  return have ? static_cast<const int32_t *>(q->grad.p) : nullptr;
+}
+
+const int32_t *ws::sample_selected_dev(const SampleResult *q, size_t *n)
+{
+  const bool have = q && q->has_sel && q->n_sel;
+  if (n) *n = have ? q->n_sel : 0;
+  return have ? static_cast<const int32_t *>(q->sel.p) : nullptr;
+}
+
+// `name`, `call`: the download entry point, and the entry point whose flag it misses
+int ws::sample_download(const SampleResult &q, hipStream_t s, const char *name, const char *call, void *records_host, int32_t *gradient_host,
+                        int32_t *selected_host, size_t capacity_points, size_t capacity_selected, size_t *n_out, size_t *n_selected)
+{
+  *n_out = q.n;
+  if (n_selected) *n_selected = q.n_sel;
+  const size_t k = std::min(capacity_points, q.n), ks = selected_host ? std::min(capacity_selected, q.n_sel) : 0;
+  if (k && gradient_host && !q.has_grad) return invalid(std::string(name) + ": the last " + call + " did not ask for WS_SAMPLE_GRADIENT");
+  if (selected_host && capacity_selected && q.n && !q.has_sel) return invalid(std::string(name) + ": the last " + call + " did not ask for a selection");
+  if (k && records_host) WS_HIP(hipMemcpyAsync(records_host, q.rec.p, k * 16, hipMemcpyDeviceToHost, s));
+  if (k && gradient_host) WS_HIP(hipMemcpyAsync(gradient_host, q.grad.p, k * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  if (ks) WS_HIP(hipMemcpyAsync(selected_host, q.sel.p, ks * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  if (k || ks) WS_HIP(hipStreamSynchronize(s));
+  return WS_OK;
+}
+
+// ---- point sample: the map's value at given points, map_sample.hip (the rules are stated in warpsense_hip.h)
+static int map_sample(ws_map *m, int which, const int32_t *points, bool points_on_host, size_t n, int32_t band, uint32_t flags, uint64_t counts[4])
+{
+  WS_TRY(sample_check("ws_map_sample", !m || (which != WS_MAP_AVG && which != WS_MAP_NEW), points, n, m ? m->res : 0, flags, [] { return WS_OK; }));
+  WS_SETTLE(m);
+  std::lock_guard<std::mutex> lock(m->sample.mu);
+  SampleResult &q = m->sample;
+  if (band <= 0) band = m->tau;
+  WS_TRY(sample_run(
+      q, m->ctx->stream, points, points_on_host, n, flags, counts, false, [] { return WS_OK; },
+      [&](const int32_t *pts_dev) { return launch_sample(m, q, which, pts_dev, n, band, flags); }));
+  return map_take_error(m);
+}
+
+int ws_map_sample(ws_map *m, int which, const int32_t *points_host, size_t n, int32_t band_mm, uint32_t flags, uint64_t counts[4])
+{
+  return map_sample(m, which, points_host, true, n, band_mm, flags, counts);
+}
+
+int ws_map_sample_dev(ws_map *m, int which, const int32_t *points_dev, size_t n, int32_t band_mm, uint32_t flags, uint64_t counts[4])
+{
+  return map_sample(m, which, points_dev, false, n, band_mm, flags, counts);
+}
+
+const void *ws_map_sample_records_dev(const ws_map *m, size_t *n) { return sample_records_dev(m ? &m->sample : nullptr, n); }
+
+const int32_t *ws_map_sample_gradient_dev(const ws_map *m, size_t *n) { return sample_gradient_dev(m ? &m->sample : nullptr, n); }
+
+const int32_t *ws_map_sample_selected_dev(const ws_map *m, size_t *n) { return sample_selected_dev(m ? &m->sample : nullptr, n); }
+
+int ws_map_sample_download(ws_map *m, void *records_host, int32_t *gradient_host, int32_t *selected_host, size_t capacity_points, size_t capacity_selected,
+                           size_t *n_out, size_t *n_selected)
+{
+  if (!m || !n_out) return invalid("ws_map_sample_download: NULL argument");
+  std::lock_guard<std::mutex> lock(m->sample.mu);
+  return sample_download(m->sample, m->ctx->stream, "ws_map_sample_download", "ws_map_sample", records_host, gradient_host, selected_host, capacity_points,
+                         capacity_selected, n_out, n_selected);
+}
+
+int ws_debug_sample_timing(ws_map *m, int32_t enable, float ms_out[3])
+{
+  if (!m) return invalid("ws_debug_sample_timing: map is NULL");
+  std::lock_guard<std::mutex> lock(m->sample.mu);
+  return query_timing(m->ctx->stream, m->sample.timer, enable, ms_out, SAMPLE_PAIRS, 3);
 }
 
 // ---- distance field: the same beside distance_check and distance_run.  The window and the store differ in pass 0 only.

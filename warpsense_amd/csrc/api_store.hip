@@ -703,6 +703,71 @@ int ws_debug_store_raycast_timing(ws_store *st, int32_t enable, float ms_out[3])
   return query_timing(st->ctx->stream, st->ray.timer, enable, ms_out, RAY_PAIRS, 3);
 }
 
+// ---- the point sample of the store: the rules and the host flow of ws_map_sample over the chunks, store_sample.hip
+static int store_sample(ws_store *st, const int32_t lo[3], const int32_t hi[3], const int32_t *points, bool points_on_host, size_t n, int32_t band, int32_t res,
+                        uint32_t flags, uint64_t counts[4])
+{
+  std::unique_lock<std::mutex> lock;
+  StoreRayCall c;
+  c.res = res;
+  WS_TRY(sample_check("ws_store_sample", !st || ((lo == nullptr) != (hi == nullptr)) || band <= 0, points, n, res, flags, [&] {
+    WS_TRY(store_query_box(st, "ws_store_sample", lo, hi, true, lock, c.lo, c.hi));
+    return res <= 0 ? invalid("ws_store_sample: map_resolution <= 0") : (int)WS_OK;
+  }));
+  ws_store::Sample &q = st->sample;
+  std::vector<StoreRaySlot> listed;
+  store_list(st, lo, hi, listed); // (without a box: every written chunk)
+  if (listed.size() >= (1u << 19)) return range_error("ws_store_sample", ": the call lists 2^19 present chunks or more");
+  c.n_chunks = (uint32_t)listed.size();
+  // the live box: the bounding box of the listed chunks (keys are floor(int32 / 64): 64 k + 63 fits), cut to the box
+  for (int k = 0; k < 3; ++k) c.blo[k] = INT32_MAX, c.bhi[k] = INT32_MIN;
+  for (const StoreRaySlot &e : listed)
+  {
+    const int32_t key[3] = {e.cx, e.cy, e.cz};
+    for (int k = 0; k < 3; ++k) c.blo[k] = std::min(c.blo[k], key[k] * STORE_CS), c.bhi[k] = std::max(c.bhi[k], key[k] * STORE_CS + STORE_CS - 1);
+  }
+  for (int k = 0; k < 3; ++k) c.blo[k] = std::max(c.blo[k], c.lo[k]), c.bhi[k] = std::min(c.bhi[k], c.hi[k]);
+  // (no listed chunk: the call still launches and answers UNKNOWN for every point)
+  return sample_run(
+      q, st->ctx->stream, points, points_on_host, n, flags, counts, store_lookup_places(listed.size()) > q.table_host.cap,
+      [&] { return store_lookup_fill(q.table_host, q.table_dev, listed); },
+      [&](const int32_t *pts_dev) { return store_enqueued(st, launch_store_sample(st, q, c, pts_dev, n, band, flags)); });
+}
+
+int ws_store_sample(ws_store *st, const int32_t lo[3], const int32_t hi[3], const int32_t *points_host, size_t n, int32_t band_mm, int32_t map_resolution,
+                    uint32_t flags, uint64_t counts[4])
+{
+  return store_sample(st, lo, hi, points_host, true, n, band_mm, map_resolution, flags, counts);
+}
+
+int ws_store_sample_dev(ws_store *st, const int32_t lo[3], const int32_t hi[3], const int32_t *points_dev, size_t n, int32_t band_mm, int32_t map_resolution,
+                        uint32_t flags, uint64_t counts[4])
+{
+  return store_sample(st, lo, hi, points_dev, false, n, band_mm, map_resolution, flags, counts);
+}
+
+const void *ws_store_sample_records_dev(const ws_store *st, size_t *n) { return sample_records_dev(st ? &st->sample : nullptr, n); }
+
+const int32_t *ws_store_sample_gradient_dev(const ws_store *st, size_t *n) { return sample_gradient_dev(st ? &st->sample : nullptr, n); }
+
+const int32_t *ws_store_sample_selected_dev(const ws_store *st, size_t *n) { return sample_selected_dev(st ? &st->sample : nullptr, n); }
+
+int ws_store_sample_download(ws_store *st, void *records_host, int32_t *gradient_host, int32_t *selected_host, size_t capacity_points, size_t capacity_selected,
+                             size_t *n_out, size_t *n_selected)
+{
+  if (!st || !n_out) return invalid("ws_store_sample_download: NULL argument");
+  std::lock_guard<std::mutex> lock(st->mu);
+  return sample_download(st->sample, st->ctx->stream, "ws_store_sample_download", "ws_store_sample", records_host, gradient_host, selected_host, capacity_points,
+                         capacity_selected, n_out, n_selected);
+}
+
+int ws_debug_store_sample_timing(ws_store *st, int32_t enable, float ms_out[3])
+{
+  if (!st) return invalid("ws_debug_store_sample_timing: store is NULL");
+  std::lock_guard<std::mutex> lock(st->mu);
+  return query_timing(st->ctx->stream, st->sample.timer, enable, ms_out, SAMPLE_PAIRS, 3);
+}
+
 // ---- the distance field of the store: the rules and the host flow of ws_map_distance over the chunks, store_distance.hip
 int ws_store_distance(ws_store *st, const int32_t lo[3], const int32_t hi[3], int32_t max_dist_vox, uint32_t flags, size_t *n_sites)
 {

@@ -55,10 +55,15 @@ const void *raycast_records_dev(const RayResult *q, size_t *n);
 const int32_t *raycast_gradient_dev(const RayResult *q, size_t *n);
 int raycast_download(const RayResult &q, hipStream_t s, const char *name, const char *call, void *records_host, int32_t *gradient_host, size_t capacity_rays,
                      size_t *n_out);
+const void *sample_records_dev(const SampleResult *q, size_t *n);
+const int32_t *sample_gradient_dev(const SampleResult *q, size_t *n);
+const int32_t *sample_selected_dev(const SampleResult *q, size_t *n);
+int sample_download(const SampleResult &q, hipStream_t s, const char *name, const char *call, void *records_host, int32_t *gradient_host, int32_t *selected_host,
+                    size_t capacity_points, size_t capacity_selected, size_t *n_out, size_t *n_selected);
 const uint32_t *distance_dev(const DistResult *q, size_t *n);
 int distance_download(const DistResult &q, hipStream_t s, uint32_t *host, size_t capacity, size_t *n_out);
 // the event pairs of ws_debug_*_timing (QueryTimer::read)
-constexpr int SURF_PAIRS[3][2] = {{0, 1}, {1, 2}, {3, 4}}, MESH_PAIRS[3][2] = {{0, 1}, {1, 2}, {3, 4}}, RAY_PAIRS[3][2] = {{0, 1}, {1, 2}, {2, 3}}, DIST_PAIRS[4][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 4}};
+constexpr int SURF_PAIRS[3][2] = {{0, 1}, {1, 2}, {3, 4}}, MESH_PAIRS[3][2] = {{0, 1}, {1, 2}, {3, 4}}, RAY_PAIRS[3][2] = {{0, 1}, {1, 2}, {2, 3}}, SAMPLE_PAIRS[3][2] = {{0, 1}, {1, 2}, {2, 3}}, DIST_PAIRS[4][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 4}};
 
 // ---- surface cloud, mesh, ray cast and distance field: one host core each for the window of a map (map_surface.hip, map_mesh.hip,
 // map_raycast.hip, map_distance.hip) and for the chunks of the store (store_surface.hip, store_mesh.hip, store_raycast.hip,
@@ -177,6 +182,68 @@ int raycast_run(RayResult &q, hipStream_t s, const int32_t *dirs, bool dirs_on_h
   q.n = n;
   q.has_grad = grad;
   if (n_hits) *n_hits = (size_t)*q.hits.host;
+  return WS_OK;
+}
+
+// The argument check of a point sample.  `bad`: what the entry point found wrong with its own leading arguments; more(): its further
+// checks, which come before those of the ranges.
+template <typename More> int sample_check(const char *name, bool bad, const int32_t *points, size_t n, int32_t res, uint32_t flags, More more)
+{
+  const uint32_t known = WS_SAMPLE_ANY_WEIGHT | WS_SAMPLE_GRADIENT | WS_SAMPLE_SELECT_UNKNOWN | WS_SAMPLE_SELECT_FREE | WS_SAMPLE_SELECT_SURFACE | WS_SAMPLE_SELECT_INSIDE;
+  if (bad || (flags & ~known) || (n && !points)) return invalid(std::string(name) + ": bad argument");
+  WS_TRY(more());
+  if (res > 1024) return range_error(name, ": the resolution must not exceed 1024 mm (the interpolant is carried times res^3 in 64 bits)");
+  if (n > ((size_t)1 << 27)) return range_error(name, ": more than 2^27 points");
+  return WS_OK;
+}
+
+// The flow of a point sample whose arguments have passed sample_check: arm, drop the old result, grow, upload the points, launch,
+// synchronise, publish.  own_room, prepare() and launch(points on the device) are those of raycast_run.  The selection is sized for
+// every point of the call, so nothing is read back before the one synchronise at the end.
+template <typename Prepare, typename Launch>
+int sample_run(SampleResult &q, hipStream_t s, const int32_t *points, bool points_on_host, size_t n, uint32_t flags, uint64_t counts[4], bool own_room,
+               Prepare prepare, Launch launch)
+{
+  WS_TRY(q.timer.arm());
+  if (counts) counts[0] = counts[1] = counts[2] = counts[3] = 0;
+  q.n = q.n_sel = 0; // (whatever happens from here on, the old result is gone: its buffers may be replaced)
+  q.has_grad = q.has_sel = false;
+  if (n == 0) return WS_OK;
+  const bool grad = (flags & WS_SAMPLE_GRADIENT) != 0;
+  const uint32_t select = (flags / WS_SAMPLE_SELECT_UNKNOWN) & 15u;
+  const size_t blocks = (n + 255) / 256; // (SAMPLE_WG, ws_sample.h)
+  WS_TRY(q.counts.alloc(5));
+  if (n > q.rec.cap || (grad && n > q.grad.cap) || (points_on_host && n > q.pts.cap) || (select && (n > q.sel.cap || blocks > q.blk_tot.cap || blocks > q.blk_off.cap)) ||
+      own_room)
+  {
+    WS_HIP(hipStreamSynchronize(s));
+    WS_TRY(q.rec.grow(n, 16));
+    if (grad) WS_TRY(q.grad.grow(n, 3 * sizeof(int32_t)));
+    if (points_on_host) WS_TRY(q.pts.grow(n, 3 * sizeof(int32_t)));
+    if (select)
+    {
+      WS_TRY(q.sel.grow(n, 3 * sizeof(int32_t)));
+      WS_TRY(q.blk_tot.grow(blocks, sizeof(uint32_t)));
+      WS_TRY(q.blk_off.grow(blocks, sizeof(unsigned long long)));
+    }
+  }
+  WS_TRY(prepare());
+  q.timer.mark(0, s);
+  if (points_on_host)
+  {
+    WS_HIP(hipMemcpyAsync(q.pts.p, points, n * 3 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    points = static_cast<const int32_t *>(q.pts.p);
+  }
+  WS_TRY(launch(points));
+  WS_HIP(hipStreamSynchronize(s));
+  q.n = n;
+  q.has_grad = grad;
+  q.has_sel = select != 0;
+  for (int c = 0; c < 4; ++c)
+  {
+    if (counts) counts[c] = q.counts.host[c];
+    if ((select >> c) & 1u) q.n_sel += (size_t)q.counts.host[c];
+  }
   return WS_OK;
 }
 

@@ -410,6 +410,17 @@ struct DistResult
   size_t n = 0;                        // records of the last call
   void release() { timer.release(), sites.release(); for (DevBuf *b : {&rec, &plane}) b->release(); }
 };
+// ... and a sample call (ws_map::Sample, ws_store::Sample; the one flow is sample_run in ws_api.h)
+struct SampleResult
+{
+  QueryTimer timer;                    // 0 upload 1 sample pass 2 scan and emit pass 3
+  DevBuf pts, rec, grad, sel;          // int32 [points][3] staging of host points; 16-byte records; int32 [points][3]; int32 [selected][3]
+  DevBuf blk_tot, blk_off;             // uint32 / uint64 [workgroups] selected points, and their exclusive scan
+  DevCounter counts;                   // points per class [4], then the scan's total
+  size_t n = 0, n_sel = 0;             // points and selected points of the last call
+  bool has_grad = false, has_sel = false; // the last call also wrote `grad` / `sel`
+  void release() { timer.release(), counts.release(); for (DevBuf *b : {&pts, &rec, &grad, &sel, &blk_tot, &blk_off}) b->release(); }
+};
 
 } // namespace ws
 
@@ -497,6 +508,10 @@ struct ws_map
   {
     std::mutex mu;
   } dist;
+  struct Sample : ws::SampleResult // ws_map_sample (map_sample.hip)
+  {
+    std::mutex mu;
+  } sample;
   // The scan whose verdict (did its records fit the pool?) has not been looked at yet: ws_tsdf_update* return after the
   // launches, like the reference's update_tsdf (update_tsdf.cu:165); the next call that takes this map settles it first
   // (settle_tsdf: the verdict is in host-mapped memory ~0.35 ms after the launches) and repeats the scan if it was aborted.
@@ -527,7 +542,7 @@ struct ws_map
                           &tile_list, &rec, &big_keys, &block_stats, &counters, &box_stage, &shift_stage_dev})
       b->release();
     for (ws::HostBlock *b : {&counters_host, &status, &shift_stage_host}) b->release();
-    surf.release(), mesh.release(), ray.release(), dist.release();
+    surf.release(), mesh.release(), ray.release(), dist.release(), sample.release();
   }
 };
 
@@ -669,12 +684,19 @@ struct ws_store
     ws::DevBuf table_dev;                // ... and the copy the kernel reads
     void release() { DistResult::release(), table_host.release(), table_dev.release(); }
   } dist;
+  struct Sample : ws::SampleResult // ws_store_sample (store_sample.hip)
+  {
+    ws::HostBlock table_host;            // StoreRaySlot, pinned: the call's chunk lookup; free again when the call returns, which synchronises
+    ws::DevBuf table_dev;                // ... and the copy the kernels read
+    void release() { SampleResult::release(), table_host.release(), table_dev.release(); }
+  } sample;
   void release()
   {
     surf.release();
     mesh.release();
     ray.release();
     dist.release();
+    sample.release();
     for (ws::DevBuf &b : segs) b.release();
     segs.clear(), seg_ptr.clear();
     seg_tab.release();
@@ -741,6 +763,9 @@ int launch_mesh_count(ws_map *m, MeshResult &q, int which, const int32_t lo[3], 
 int launch_mesh_emit(ws_map *m, MeshResult &q, int which, const int32_t lo[3], const int32_t ext[3], uint32_t flags);
 // map_raycast.hip: the march and, with WS_RAYCAST_GRADIENT, the gradient pass (the hit count arrives in q.hits.host after a stream synchronise)
 int launch_raycast(ws_map *m, RayResult &q, int which, const int32_t origin[3], const int32_t *dirs_dev, size_t n, int32_t max_range, uint32_t flags);
+// map_sample.hip: the sample pass and, with a selection, the scan and the emit pass (the class counts arrive in q.counts.host after a
+// stream synchronise)
+int launch_sample(ws_map *m, SampleResult &q, int which, const int32_t *pts_dev, size_t n, int32_t band, uint32_t flags);
 // map_distance.hip: pass 0 over the ring (it clears q.sites.dev and marks events 0, 1), and the line passes over the records of a box
 // of extent `ext` that a pass 0 has prepared (events 1 .. 4; `plane`: two planes of one uint16 per record, the first one written by
 // pass 0; under WS_DISTANCE_COLUMNS ext[2] is not read).  A line of the fastest axis holds at most DIST_MAX_LINE voxels.
@@ -832,6 +857,9 @@ struct StoreRayCall
   int32_t blo[3], bhi[3]; // the bounding box of the listed chunks, cut to the box
 };
 int launch_store_raycast(ws_store *st, ws_store::Ray &q, const StoreRayCall &c, const int32_t origin[3], const int32_t *dirs_dev, size_t n, int32_t max_range, uint32_t flags);
+// store_sample.hip: the passes of map_sample.hip over the chunks the call lists, found through the lookup of store_raycast.hip in
+// q.table_host (`c`: the box and the live box of a ray cast)
+int launch_store_sample(ws_store *st, ws_store::Sample &q, const StoreRayCall &c, const int32_t *pts_dev, size_t n, int32_t band, uint32_t flags);
 
 // store_distance.hip: pass 0 of the distance field over the chunks the call lists (it clears q.sites.dev and marks events 0, 1).  The
 // host has written the lookup of store_raycast.hip (store_ray_table_fill) for `n_chunks` listed chunks into q.table_host

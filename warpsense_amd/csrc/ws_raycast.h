@@ -331,6 +331,28 @@ __device__ __forceinline__ void ray_count_hits(const ri32x4 &out, unsigned long 
   if ((threadIdx.x & 63u) == 0 && hit) atomicAdd(hits, (unsigned long long)__popcll(hit));
 }
 
+// the central differences at voxel c, if all six neighbours are valid; else 0, 0, 0
+template <class Field> __device__ __forceinline__ void ray_gradient_at(const Field &fld, const int32_t c[3], bool any_weight, int32_t g[3])
+{
+  g[0] = g[1] = g[2] = 0;
+  if (!fld.grad_inside(c)) return;
+  bool ok = true;
+  int32_t diff[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+  {
+    int32_t v[3] = {c[0], c[1], c[2]};
+    uint32_t hi = 0u, lo = 0u;
+    v[k] = c[k] + 1;
+    ok = fld.entry(v, hi) && ok;
+    v[k] = c[k] - 1;
+    ok = fld.entry(v, lo) && ok;
+    ok = ok && ray_valid(hi, any_weight) && ray_valid(lo, any_weight);
+    diff[k] = entry_value(hi) - entry_value(lo);
+  }
+  if (ok) g[0] = diff[0], g[1] = diff[1], g[2] = diff[2];
+}
+
 // the gradient of ray i from its record: at g = floor(hit / res) the central differences, if all six neighbours are valid
 template <class Field> __device__ __forceinline__ void ray_gradient(const RayCommon &a, const Field &fld, uint32_t i)
 {
@@ -343,24 +365,7 @@ template <class Field> __device__ __forceinline__ void ray_gradient(const RayCom
     int32_t c[3], f;
 #pragma unroll
     for (int k = 0; k < 3; ++k) c[k] = floor_div(hp[k], a.rdiv, f);
-    if (fld.grad_inside(c))
-    {
-      bool ok = true;
-      int32_t diff[3];
-#pragma unroll
-      for (int k = 0; k < 3; ++k)
-      {
-        int32_t v[3] = {c[0], c[1], c[2]};
-        uint32_t hi = 0u, lo = 0u;
-        v[k] = c[k] + 1;
-        ok = fld.entry(v, hi) && ok;
-        v[k] = c[k] - 1;
-        ok = fld.entry(v, lo) && ok;
-        ok = ok && ray_valid(hi, any_weight) && ray_valid(lo, any_weight);
-        diff[k] = entry_value(hi) - entry_value(lo);
-      }
-      if (ok) g[0] = diff[0], g[1] = diff[1], g[2] = diff[2];
-    }
+    ray_gradient_at(fld, c, any_weight, g);
   }
   a.grad[3 * (size_t)i + 0] = g[0];
   a.grad[3 * (size_t)i + 1] = g[1];
