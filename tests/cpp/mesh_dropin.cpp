@@ -6,14 +6,7 @@
 #include <vector>
 
 #include "warpsense_hip/app.hpp"
-
-static unsigned long long fnv1a(const void *data, size_t bytes)
-{
-  unsigned long long h = 1469598103934665603ull;
-  const unsigned char *p = static_cast<const unsigned char *>(data);
-  for (size_t i = 0; i < bytes; ++i) h = (h ^ p[i]) * 1099511628211ull;
-  return h;
-}
+#include "dropin_common.hpp"
 
 static void report(const char *name, const warpsense::SurfaceMesh &m)
 {

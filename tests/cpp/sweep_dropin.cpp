@@ -10,16 +10,7 @@
 
 #include "warpsense_hip/app.hpp"
 #include "warpsense_hip/mapping.hpp"
-
-template <typename T>
-static bool read_all(const char *path, std::vector<T> &v)
-{
-  FILE *f = fopen(path, "rb");
-  if (!f) return false;
-  const bool ok = fread(v.data(), sizeof(T), v.size(), f) == v.size();
-  fclose(f);
-  return ok;
-}
+#include "dropin_common.hpp"
 
 static bool write_all(const std::string &path, const void *p, size_t bytes)
 {

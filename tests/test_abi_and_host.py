@@ -1,6 +1,5 @@
 """CPU tests of the boundary: the C-ABI library loads and exports every declared symbol (no compute without
 a GPU), the host-side helpers match the oracle, and the multi-rank registration driver is exact (gloo)."""
-import ctypes as C
 import os
 import re
 
@@ -8,6 +7,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from reg_scenes import OracleGnBackend
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -138,44 +138,6 @@ def test_shard_ranges_partition_the_cloud():
             assert spans[0][0] == 0 and sum(c for _, c in spans) == n
             for (a, ca), (b, _) in zip(spans, spans[1:]):
                 assert a + ca == b
-
-
-# ------------------------------------------------------------------ multi-rank driver over gloo (world size 2)
-class OracleGnBackend:
-    """Test double for HipGnBackend: per-rank partial sums and the solve come from the CPU oracle, so the
-    sharding + all-reduce + identical-solve logic of warpsense_amd.dist runs without a GPU."""
-
-    class State(C.Structure):
-        _fields_ = [("T", C.c_float * 16), ("center", C.c_int32 * 3), ("alpha", C.c_float), ("prev", C.c_float * 4),
-                    ("it_weight_gradient", C.c_float), ("epsilon", C.c_float), ("max_iterations", C.c_int32),
-                    ("iterations", C.c_int32), ("finished", C.c_int32)]
-
-    def __init__(self, omap, points, res):
-        import torch
-        self.m, self.pts, self.res = omap, np.ascontiguousarray(points, dtype=np.int32), res
-        self.st = self.State()
-        self.sums = torch.zeros(44, dtype=torch.int64)
-
-    def begin(self, T_in, max_iterations, it_weight_gradient, epsilon):
-        T = O.colmajor(T_in)
-        O.lib().wso_gn_begin(C.byref(self.st), O._p(T), int(max_iterations), C.c_float(it_weight_gradient), C.c_float(epsilon))
-
-    def accumulate(self, first, count):
-        T = np.ctypeslib.as_array(self.st.T).reshape(4, 4).T
-        if self.st.finished or self.st.iterations >= self.st.max_iterations:
-            return self.sums
-        h, g, e, c = O.reg_iterate(self.m, T, self.pts[first:first + count], self.res)
-        flat = np.concatenate([h.T.reshape(-1), g, [e, c]]).astype(np.int64)
-        self.sums.copy_(__import__("torch").from_numpy(flat))
-        return self.sums
-
-    def solve(self, sums):
-        s = np.ascontiguousarray(sums.numpy(), dtype=np.int64)
-        O.lib().wso_gn_update(C.byref(self.st), O._p(s))
-
-    def poll(self):
-        fin = bool(self.st.finished or self.st.iterations >= self.st.max_iterations)
-        return fin, int(self.st.iterations), np.ctypeslib.as_array(self.st.T).reshape(4, 4).T.copy()
 
 
 def _gloo_worker(rank, world, port, q, drop=0):

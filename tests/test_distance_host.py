@@ -6,8 +6,9 @@ import re
 
 import numpy as np
 
-import test_gpu_distance as D
-import test_mesh_host as H
+from distance_model import CTYPE, brute
+import distance_model as D
+import query_model as QM
 
 NEW = ["ws_map_distance", "ws_map_distance_dev", "ws_map_distance_download", "ws_debug_distance_timing"]
 FLAGS = {"WS_DISTANCE_DEFAULT": 0, "WS_DISTANCE_ANY_WEIGHT": 1, "WS_DISTANCE_UNKNOWN_OCCUPIED": 2, "WS_DISTANCE_COLUMNS": 4}
@@ -17,7 +18,7 @@ def test_library_exports_and_header_declares_the_distance_entry_points():
     from warpsense_amd import _lib
     import warpsense_amd as W
     L = _lib.load()
-    h = H._header()
+    h = QM._header()
     for name in NEW:
         assert hasattr(L, name), name
         assert name in _lib.EXPORTS
@@ -30,15 +31,11 @@ def test_library_exports_and_header_declares_the_distance_entry_points():
         assert phrase in h, phrase
 
 
-CTYPE = dict(H.CTYPE)
-CTYPE.update({"float [4]": C.c_void_p})
-
-
 def test_ctypes_signatures_agree_with_the_header():
     from warpsense_amd import _lib
     L = _lib.load()
     for name in NEW:
-        ret, params = H._declared(name)
+        ret, params = QM._declared(name)
         fn = getattr(L, name)
         want = [CTYPE[p] for p in params]
         assert list(fn.argtypes) == want, (name, params, fn.argtypes)
@@ -46,18 +43,6 @@ def test_ctypes_signatures_agree_with_the_header():
             assert fn.restype is C.c_void_p, name  # a pointer must not be cut to the default 32-bit int
         else:
             assert ret == "int" and fn.restype is C.c_int, name
-
-
-def brute(box, R, **kw):
-    """the rule as it is written: d2(v) = min(R^2, min over sites s of |v - s|^2), every pair evaluated"""
-    site, cls = D.sites_and_classes(box, **kw)
-    v = np.argwhere(np.ones(site.shape, dtype=bool)).astype(np.int64)
-    s = np.argwhere(site).astype(np.int64)
-    d2 = np.full(len(v), R * R, dtype=np.int64)
-    for i in range(0, len(s), 256):
-        diff = v[:, None, :] - s[None, i:i + 256, :]
-        d2 = np.minimum(d2, np.min(np.sum(diff * diff, axis=2), axis=1))
-    return (cls.astype(np.uint32) << np.uint32(30)) | d2.reshape(site.shape).astype(np.uint32), len(s)
 
 
 def test_model_equals_the_brute_force_minimum():

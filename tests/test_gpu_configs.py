@@ -43,7 +43,7 @@ def _need_memory(ok: bool, what: str):
 
 
 def test_config2_stream_on_the_1025_sliding_map():
-    import test_gpu_replay as R
+    import scan_clouds as R
     import warpsense_amd as W
     _need_memory(_free_host_gb() >= 48 and _free_gpu_gb() >= 24, "needs ~48 GB of host memory (oracle maps) and ~24 GB on the GPU")
     tau, res, mw, size = 1000, 50, 640, (1024, 1024, 1024)

@@ -5,118 +5,19 @@ np.array_equal on the raw uint32 records.
 The model is separable like the kernels, but it is a witness only because tests/test_distance_host.py holds it against a
 brute-force minimum over all (voxel, site) pairs on every box shape, range and flag combination used here."""
 import ctypes as C
-import itertools
-import os
-import shutil
 import subprocess
 import time
 
 import numpy as np
 import pytest
 
-import test_gpu_surface as G
+from distance_model import FLAGS, RANGES, RES, SIZES, TAU, check_inputs, draw_entries, model, model_box, same, seeds_for, sites_and_classes
+from dropin_build import build_dropin
+import query_model as QM
+import surface_model as G
 from warpsense_amd import synthetic as S
 
 pytestmark = pytest.mark.gpu
-ROOT = G.ROOT
-TAU, RES, SIZES, PLANTED = G.TAU, G.RES, G.SIZES, G.PLANTED
-RANGES = (1, 3, 7, 40, 255)
-FLAGS = [dict(any_weight=a, unknown_occupied=u, columns=c) for a, u, c in itertools.product((False, True), repeat=3)]
-P_OCCUPIED = 0.002
-
-
-# ------------------------------------------------------------------------------------------------ the numpy model
-def unpack(box):
-    value = (box & 0xFFFF).astype(np.uint16).view(np.int16).astype(np.int32)
-    weight = (box >> 16).astype(np.uint16).view(np.int16).astype(np.int32)
-    return value, weight
-
-
-def classes(box, any_weight=False):
-    """2 occupied (valid and value < 0), 1 free (valid and value >= 0), 0 unknown (not valid)"""
-    value, weight = unpack(box)
-    valid = weight != 0 if any_weight else weight > 0
-    return np.where(valid, np.where(value < 0, 2, 1), 0).astype(np.uint8)
-
-
-def sites_and_classes(box, any_weight=False, unknown_occupied=False, columns=False):
-    cls = classes(box, any_weight)
-    if not columns:
-        return (cls == 2) | (unknown_occupied & (cls == 0)), cls
-    occ, unk, fre = (np.any(cls == k, axis=2) for k in (2, 0, 1))
-    site = occ | (unknown_occupied & unk)
-    return site, np.where(occ, 2, np.where(site, 0, np.where(fre, 1, 0))).astype(np.uint8)
-
-
-def line_pass(g, axis, R):
-    """g'(i) = min(g(i), min over 1 <= |d| <= R of g(i + d) + d^2) along `axis`; g <= R^2 on entry, so g' is too"""
-    g = np.moveaxis(g, axis, 0)
-    out = g.copy()
-    for d in range(1, min(R, g.shape[0] - 1) + 1):
-        np.minimum(out[d:], g[:-d] + d * d, out=out[d:])
-        np.minimum(out[:-d], g[d:] + d * d, out=out[:-d])
-    return np.moveaxis(out, 0, axis)
-
-
-def model_box(box, R, any_weight=False, unknown_occupied=False, columns=False):
-    """(records shaped like the box, or (nx, ny) for columns; number of sites)"""
-    assert 1 <= R <= 255
-    site, cls = sites_and_classes(box, any_weight, unknown_occupied, columns)
-    g = np.where(site, 0, R * R).astype(np.int32)
-    for axis in range(g.ndim):
-        g = line_pass(g, axis, R)
-    return (cls.astype(np.uint32) << np.uint32(30)) | g.astype(np.uint32), int(np.count_nonzero(site))
-
-
-def model(host, R, lo=None, hi=None, **kw):
-    if lo is None:
-        lo, hi = G.window(host.size_, host.pos_)
-    lo, hi = np.asarray(lo, dtype=np.int64), np.asarray(hi, dtype=np.int64)
-    return model_box(G.ring_box(host.data_, host.size_, host.pos_, host.offset_, lo, hi), R, **kw)
-
-
-def same(got, want):
-    return got.dtype == want.dtype == np.uint32 and got.shape == want.shape and np.array_equal(got, want)
-
-
-# ------------------------------------------------------------------------------------------------ arbitrary-entry maps
-def draw_entries(size, seed, tau=TAU):
-    """Uniformly random entries would make half the voxels sites and every d2 tiny.  Here a voxel is occupied with probability
-    0.002 (positive weight, value in [-2 tau, -1]); every other voxel has a value in [0, 2 tau] and a weight uniform in
-    [-640, 640] -- all three signs, and a negative weight never comes with a negative value, so WS_DISTANCE_ANY_WEIGHT turns
-    unknown voxels into free ones and the site share stays.  Then the edge entries of test_gpu_surface.PLANTED at fixed places
-    (three of them sites by default, three more under ANY_WEIGHT)."""
-    import warpsense_amd as W
-    rng = np.random.default_rng(seed)
-    n = int(np.prod(size))
-    occ = rng.random(n) < P_OCCUPIED
-    value = np.where(occ, -rng.integers(1, 2 * tau + 1, n), rng.integers(0, 2 * tau + 1, n))
-    weight = np.where(occ, rng.integers(1, 641, n), rng.integers(-640, 641, n))
-    where = rng.permutation(n)[:len(PLANTED)]
-    for i, (w, v) in zip(where, PLANTED):
-        value[i], weight[i] = v, w
-    return W.pack_entry(value, weight).astype(np.uint32)
-
-
-def seeds_for(size, which):
-    """picked without a GPU so that check_inputs holds for all seven shapes and both maps (tests/test_distance_host.py)"""
-    return sum(size) + 1000 * which
-
-
-def check_inputs(raw, size):
-    """The input condition, on the MODEL's output before the device is asked: default flags, R in {3, 7}: at least 3 sites, at
-    least 3 % of the records strictly between 0 and R^2 and at least 2 % at R^2; every planted entry is there."""
-    value, weight = unpack(raw)
-    for pw, pv in PLANTED:
-        assert np.any((weight == pw) & (value == pv)), (pw, pv)
-    shares = []
-    for R in (3, 7):
-        rec, n_sites = model_box(raw.reshape(size), R)
-        d2 = rec & np.uint32(0xFFFFFF)
-        between, clamp = np.count_nonzero((d2 > 0) & (d2 < R * R)) / d2.size, np.count_nonzero(d2 == R * R) / d2.size
-        assert n_sites >= 3 and between >= 0.03 and clamp >= 0.02, (size, R, n_sites, between, clamp)
-        shares.append((n_sites, between, clamp))
-    return shares
 
 
 def boxes_of(lo, hi):
@@ -143,23 +44,23 @@ def test_arbitrary_entries_match_the_model(size):
         check_inputs(v.data_, size)
     t = W.TSDFCuda(views[0], TAU, 640, RES)
     t.new_map().to_device(views[1])
-    lo, hi = G.window(size, pos)
+    lo, hi = QM.window(size, pos)
     compared = 0
     for which in (0, 1):
         host = W.DeviceMap(size, off, np.empty(n, dtype=np.uint32), pos)
-        G.wrapper(t, which).to_host(host)
+        QM.wrapper(t, which).to_host(host)
         assert np.array_equal(host.data_, views[which].data_)
         for name, (a, b) in boxes_of(lo, hi).items():
             for kw in FLAGS:
                 for R in RANGES:
                     want, n_sites = model(host, R, a, b, **kw)
-                    got = G.wrapper(t, which).distance(lo=a, hi=b, max_dist_vox=R, **kw)
-                    assert same(got, want) and G.wrapper(t, which).last_sites == n_sites, (size, which, name, kw, R)
+                    got = QM.wrapper(t, which).distance(lo=a, hi=b, max_dist_vox=R, **kw)
+                    assert same(got, want) and QM.wrapper(t, which).last_sites == n_sites, (size, which, name, kw, R)
                     compared += 1
     assert compared == 2 * 5 * 8 * 5
     for which in (0, 1):  # read-only on the maps
         host = W.DeviceMap(size, off, np.empty(n, dtype=np.uint32), pos)
-        G.wrapper(t, which).to_host(host)
+        QM.wrapper(t, which).to_host(host)
         assert np.array_equal(host.data_, views[which].data_)
 
 
@@ -185,16 +86,16 @@ def test_rotated_rings_after_the_shift_sequence():
         tm.shift_map(new_pos)
         assert tm.tsdf().avg_map().distance(max_dist_vox=3).shape == (21, 17, 13)  # (a call between two shifts)
     for which in (0, 1):
-        host = G.download(W, tm, lm, which)
+        host = QM.download(W, tm, lm, which)
         assert all(int(o) != 0 for o in host.offset_) and list(host.pos_) == [-2, 5, -3]
-        lo, hi = G.window(host.size_, host.pos_)
+        lo, hi = QM.window(host.size_, host.pos_)
         seam = [int(lo[k] + (-(lo[k] - host.pos_[k] + host.offset_[k])) % host.size_[k]) for k in range(3)]
         assert all(lo[k] < seam[k] <= hi[k] for k in range(3)), seam
         for a, b in ((None, None), (tuple(s - 2 for s in seam), tuple(s + 1 for s in seam))):
             for kw in FLAGS:
                 for R in (3, 40):
                     want, n_sites = model(host, R, a, b, **kw)
-                    assert same(G.wrapper(tm.tsdf(), which).distance(lo=a, hi=b, max_dist_vox=R, **kw), want), (which, a, kw, R)
+                    assert same(QM.wrapper(tm.tsdf(), which).distance(lo=a, hi=b, max_dist_vox=R, **kw), want), (which, a, kw, R)
         assert model(host, 7)[1] >= 3
 
 
@@ -246,12 +147,12 @@ def test_columns_with_a_column_whose_only_site_is_an_unknown_voxel():
 
 # ------------------------------------------------------------------------------------------------ buffers, errors
 def test_repeatable_apart_from_the_other_results_downloads_and_error_codes():
-    import test_gpu_mesh as M
-    import test_gpu_raycast as RC
+    import mesh_model as M
+    import raycast_model as RC
     W, tm, lm = make_maps((15, 15, 15), seed=22)
     t = tm.tsdf()
     avg, L = t.avg_map(), t._L
-    before = [G.download(W, tm, lm, which).data_.copy() for which in (0, 1)]
+    before = [QM.download(W, tm, lm, which).data_.copy() for which in (0, 1)]
     rec = avg.distance(max_dist_vox=7)
     assert same(avg.distance(max_dist_vox=7), rec) and same(tm.distance_field(max_dist_m=0.35), rec)  # 350 mm / 50 mm = 7 voxels
     assert same(tm.distance_field(max_dist_m=0.301), rec) and not same(tm.distance_field(max_dist_m=0.3), rec)  # ceil
@@ -260,18 +161,18 @@ def test_repeatable_apart_from_the_other_results_downloads_and_error_codes():
     # the results of the surface cloud, the mesh and the ray cast survive a distance call, and the other way round
     surf = avg.surface()
     vert, face = avg.mesh(any_weight=True)  # (half the weights are not positive: the default rule leaves hardly a valid cell)
-    o, d = RC.random_rays((15, 15, 15), seed=3, lo=G.window(lm.size, lm.pos)[0], n=300)
+    o, d = RC.random_rays((15, 15, 15), seed=3, lo=QM.window(lm.size, lm.pos)[0], n=300)
     rays, _ = avg.raycast(o, d.astype(np.int32), 3000)
     rec40 = avg.distance(max_dist_vox=40, unknown_occupied=True)
     n = C.c_size_t(0)
     got = np.zeros(len(surf), dtype=G.REC)
-    assert L.ws_map_surface_download(t.handle, got.ctypes.data_as(C.c_void_p), None, len(surf), C.byref(n)) == 0 and G.same(got, surf)
+    assert L.ws_map_surface_download(t.handle, got.ctypes.data_as(C.c_void_p), None, len(surf), C.byref(n)) == 0 and QM.same(got, surf)
     gv, gf = C.c_size_t(0), C.c_size_t(0)
     pv, pf = np.zeros(len(vert), dtype=M.VERT), np.zeros((len(face), 3), dtype=np.uint32)
     assert L.ws_map_mesh_download(t.handle, pv.ctypes.data_as(C.c_void_p), pf.ctypes.data_as(C.c_void_p), len(vert), len(face), C.byref(gv), C.byref(gf)) == 0
     assert M.same((pv, pf), (vert, face)) and len(vert) > 0
     pr = np.zeros(300, dtype=RC.RAY)
-    assert L.ws_map_raycast_download(t.handle, pr.ctypes.data_as(C.c_void_p), None, 300, C.byref(n)) == 0 and G.same(pr, rays)
+    assert L.ws_map_raycast_download(t.handle, pr.ctypes.data_as(C.c_void_p), None, 300, C.byref(n)) == 0 and QM.same(pr, rays)
     avg.surface(band=1)
     avg.mesh()
     avg.raycast(o, d[:10].astype(np.int32), 3000)
@@ -283,9 +184,9 @@ def test_repeatable_apart_from_the_other_results_downloads_and_error_codes():
     assert L.ws_map_distance_dev(t.handle, C.byref(n)) and n.value == 15 ** 3
     # both maps are bit-identical before and after
     for which in (0, 1):
-        assert np.array_equal(G.download(W, tm, lm, which).data_, before[which])
+        assert np.array_equal(QM.download(W, tm, lm, which).data_, before[which])
     # the error codes of the rules
-    lo, hi = (np.asarray(v, dtype=np.int32) for v in G.window(lm.size, lm.pos))
+    lo, hi = (np.asarray(v, dtype=np.int32) for v in QM.window(lm.size, lm.pos))
     p = lambda a: a.ctypes.data_as(C.c_void_p)
     assert L.ws_map_distance(t.handle, 0, None, None, 0, 0, None) == -5 and L.ws_map_distance(t.handle, 0, None, None, 256, 0, None) == -5  # WS_ERR_RANGE
     assert L.ws_map_distance(t.handle, 0, None, None, 1, 0, None) == 0 and L.ws_map_distance(t.handle, 0, None, None, 255, 0, None) == 0
@@ -366,8 +267,8 @@ def test_after_real_scans_at_benchmark_size():
     assert n_sites > 100_000 and avg.last_sites == n_sites and same(got, want)
     assert same(avg.distance(max_dist_vox=8), got)  # the same bytes twice
     del want
-    lo, hi = G.window(host.size_, host.pos_)
-    box = G.ring_box(host.data_, host.size_, host.pos_, host.offset_, lo, hi)
+    lo, hi = QM.window(host.size_, host.pos_)
+    box = QM.ring_box(host.data_, host.size_, host.pos_, host.offset_, lo, hi)
     site, cls = sites_and_classes(box)
     site_xyz = np.argwhere(site)
     rng = np.random.default_rng(513)
@@ -395,13 +296,7 @@ def test_after_real_scans_at_benchmark_size():
 # ------------------------------------------------------------------------------------------------ C++ twin
 def test_cpp_twin_matches_the_python_route(tmp_path):
     import warpsense_amd as W
-    cxx = shutil.which("g++")
-    assert cxx is not None, "the C++ drop-in needs g++"
-    exe = tmp_path / "distance_dropin"
-    lib = os.path.join(ROOT, "warpsense_amd")
-    subprocess.check_call([cxx, "-O2", "-std=c++17", "-Wall", "-ffp-contract=off", f"-I{os.path.join(ROOT, 'include')}",
-                           os.path.join(ROOT, "tests", "cpp", "distance_dropin.cpp"), "-o", str(exe), f"-L{lib}", f"-Wl,-rpath,{lib}",
-                           "-Wl,-rpath,/opt/rocm/lib", "-lwarpsense_hip", "-lpthread"])
+    exe = build_dropin("distance_dropin", tmp_path)
     tau, res, mw, edge = 1000, 50, 640, 65
     pts = S.os1_128_scan(rings=32, azimuths=256, half_extents_mm=(1400.0, 1300.0, 900.0), seed=2)
     pts.tofile(tmp_path / "scan.bin")
@@ -418,7 +313,7 @@ def test_cpp_twin_matches_the_python_route(tmp_path):
 
     def line(rec, sites):
         ext = rec.shape if rec.ndim == 3 else rec.shape + (1,)
-        return [str(v) for v in ext] + [str(sites), f"{G.fnv1a(rec.tobytes()):016x}"]
+        return [str(v) for v in ext] + [str(sites), f"{QM.fnv1a(rec.tobytes()):016x}"]
     rec = tm.distance_field(max_dist_m=1.0)  # 20 voxels
     assert avg.last_sites > 1000 and np.count_nonzero((W.distance_d2(rec) > 0) & (W.distance_d2(rec) < 400)) > 10_000
     assert lines["window"] == line(rec, avg.last_sites)

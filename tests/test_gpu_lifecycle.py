@@ -14,14 +14,10 @@ it: hipMemGetInfo moves in the runtime's own granules, so a leak shows as a mult
 import numpy as np
 import pytest
 
+from lifecycle_model import CYCLES, MARGIN
 from warpsense_amd import synthetic as S
 
 pytestmark = pytest.mark.gpu
-
-CYCLES = 5
-PARENT_LARGEST_DROP = 0  # bytes, see above
-SMALLEST_BUFFER = 4      # bytes: ws_reg::pass_arrived
-MARGIN = PARENT_LARGEST_DROP + SMALLEST_BUFFER
 
 TAU, RES, SIZE = 1000, 50, (96, 96, 48)
 

@@ -10,10 +10,10 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
-from test_gpu_sweep import both_routes as both_routes_sweep
-from test_preprocess import POSES, make_cloud
-from test_preprocess_edges_host import EDGE_RES, edge_cloud, probe_adversarial_points
-from test_sweep_host import rigid
+from scan_clouds import both_routes as both_routes_sweep
+from scan_clouds import POSES, make_cloud
+from scan_clouds import EDGE_RES, edge_cloud, probe_adversarial_points
+from scan_clouds import rigid
 
 pytestmark = pytest.mark.gpu
 

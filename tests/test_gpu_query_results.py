@@ -7,10 +7,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import test_gpu_mesh as M
-import test_gpu_raycast as R
-import test_gpu_store_mesh as SM
-import test_gpu_surface as G
+import mesh_model as M
+import query_model as QM
+import raycast_model as R
+import store_scenes as SM
 
 pytestmark = pytest.mark.gpu
 TAU, RES, MW = SM.TAU, SM.RES, SM.MW
@@ -37,7 +37,7 @@ class Pair:
         self.store = SM.make_store(SM.seam_chunks())
         lm = W.LocalMap(127, 127, 127, TAU, 0)
         self.t = W.TSDFCuda(lm.device_map(), TAU, MW, RES)
-        lo, hi = G.window(lm.size, lm.pos)
+        lo, hi = QM.window(lm.size, lm.pos)
         assert tuple(lo) == (-63,) * 3 and tuple(hi) == (63,) * 3
         self.store.load_box(self.t, lo, hi)
         self.L, self.dirs = self.store._L, rays()
@@ -118,7 +118,7 @@ def test_results_are_independent(alone):
         for q in reversed(QUERIES):
             got = p.download(q)
             assert counted[q] == alone[q][0], q
-            assert all(G.same(g, w) for g, w in zip(got, alone[q][1])), q
+            assert all(QM.same(g, w) for g, w in zip(got, alone[q][1])), q
     finally:
         p.close()
 

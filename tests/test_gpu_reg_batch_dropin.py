@@ -1,28 +1,20 @@
 """The C++ drop-in of the batched registration (tests/cpp/reg_batch_dropin.cpp): register_cloud_batch through compat.hpp equals the
 single C++ call bit for bit, and both equal the Python route."""
-import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
-import test_gpu_reg_batch as B
+from dropin_build import build_dropin
+import reg_scenes as B
 from warpsense_amd import synthetic as S
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_cpp_batch_equals_the_single_cpp_call_and_the_python_route(tmp_path):
     import warpsense_amd as W
-    cxx = shutil.which("g++")
-    assert cxx is not None, "the C++ drop-in needs g++"
-    exe = tmp_path / "reg_batch_dropin"
-    lib = os.path.join(ROOT, "warpsense_amd")
-    subprocess.check_call([cxx, "-O2", "-std=c++17", "-Wall", "-ffp-contract=off", f"-I{os.path.join(ROOT, 'include')}",
-                           os.path.join(ROOT, "tests", "cpp", "reg_batch_dropin.cpp"), "-o", str(exe), f"-L{lib}", f"-Wl,-rpath,{lib}",
-                           "-Wl,-rpath,/opt/rocm/lib", "-lwarpsense_hip", "-lpthread"])
+    exe = build_dropin("reg_batch_dropin", tmp_path)
     tau, res, mw, edge, max_it = 1000, 50, 640, 129, 60
     pts = S.os1_128_scan(rings=32, azimuths=256, half_extents_mm=(2600.0, 2300.0, 1000.0), seed=21)
     q = B.batch_cloud(pts)

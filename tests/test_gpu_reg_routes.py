@@ -16,9 +16,9 @@ import pytest
 
 import oracle_lib as O
 import reg_cases as RC
-from test_gpu_reg_batch import check_batch_equals_single
-from test_gpu_registration import _server, pose_error
-from test_gpu_sharded import _OracleLoop
+from reg_scenes import check_batch_equals_single
+from reg_scenes import _server, pose_error
+from reg_scenes import _OracleLoop
 
 pytestmark = pytest.mark.gpu
 

@@ -3,37 +3,10 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from reg_scenes import _server, build_scene, pose_error
 from warpsense_amd import synthetic as S
 
 pytestmark = pytest.mark.gpu
-
-
-def build_scene(size=(128, 128, 64), tau=1000, res=50, mw=640, rings=64, az=512, he=(2600.0, 2300.0, 1000.0), scans=1):
-    import torch
-    import warpsense_amd as W
-    params = W.Params(W.MapParams(resolution=res, max_distance=tau / 1000.0, max_weight=mw // 64,
-                                  size=tuple(s * res / 1000.0 for s in size)))
-    lm = W.LocalMap(size[0], size[1], size[2], tau, 0)
-    reg = W.TSDFRegistration(params, lm)
-    oa = O.OracleMap(size, tau, 0)
-    on = oa.copy()
-    pts = None
-    for k in range(scans):
-        pts = S.os1_128_scan(rings=rings, azimuths=az, half_extents_mm=he, seed=21 + k)
-        O.update_tsdf(oa, on, pts, (0, 0, 0), (0, 0, 32768), tau, mw, res)
-        reg.update_tsdf(torch.from_numpy(pts).cuda(), pose=np.eye(4, dtype=np.float32))
-    return reg, oa, pts, res
-
-
-def pose_error(A, B):
-    A = np.asarray(A, dtype=np.float64)
-    B = np.asarray(B, dtype=np.float64)
-    dt = np.linalg.norm(A[:3, 3] - B[:3, 3]) / 1000.0  # mm -> m
-    R = A[:3, :3] @ B[:3, :3].T
-    # atan2 form: well conditioned near 0 (arccos of a float32-rounded trace is not)
-    k = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]]) / 2
-    ang = np.arctan2(np.linalg.norm(k), (np.trace(R) - 1) / 2)
-    return dt, ang
 
 
 @pytest.mark.parametrize("flags", [0, 1])
@@ -305,14 +278,6 @@ def test_loop_sums_on_a_map_of_arbitrary_entries(n, res):
     h, g, e, c = rc.perform_registration(tsdf.device_map(), T2, res)
     assert (e, c) == (eo, co) and np.array_equal(g, go) and np.array_equal(h, ho)
     rc.close()
-
-
-def _server(reg_cuda, enable=-1, idle_us=0):
-    import ctypes as C
-    n = C.c_int32(0)
-    rc = reg_cuda._L.ws_debug_reg_server(reg_cuda.handle, int(enable), int(idle_us), C.byref(n))
-    assert rc == 0
-    return n.value
 
 
 def test_perform_registration_through_the_resident_server():

@@ -2,73 +2,10 @@
 (src/warpsense/app.cpp:65-117) — checked against the same sequence driven through the CPU oracle."""
 import numpy as np
 import pytest
+from scan_clouds import _angle, oracle_replay, sensor_clouds
 
-import oracle_lib as O
-from warpsense_amd import synthetic as S
 
 pytestmark = pytest.mark.gpu
-
-
-def _angle(Ra, Rb):
-    R = Ra.astype(np.float64).T @ Rb.astype(np.float64)
-    return float(np.arctan2(np.linalg.norm([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]]) / 2.0, (np.trace(R) - 1.0) / 2.0))
-
-
-def sensor_clouds(n_scans, step_mm):
-    """a sensor moving along +x through a box room; clouds in the SENSOR frame (metres)"""
-    clouds = []
-    for k in range(n_scans):
-        sensor = np.array([k * step_mm, 0.5 * k * step_mm, 0.0])
-        pts = S.os1_128_scan(sensor_mm=tuple(sensor), rings=32, azimuths=256, half_extents_mm=(2600.0, 2200.0, 1100.0), seed=100 + k)
-        clouds.append(((pts.astype(np.float64) - sensor) / 1000.0).astype(np.float32))
-    return clouds
-
-
-def oracle_replay(clouds, size, tau, mw, res, reg, shift_m):
-    """cloud_callback + map_shift with every device step replaced by the oracle"""
-    import warpsense_amd as W
-    lm = W.LocalMap(*size, tau, 0)
-    om = O.OracleMap(size, tau, 0)
-    on = om.copy()
-    pose = np.eye(4, dtype=np.float32)
-    last_tsdf, last_shift = pose.copy(), pose.copy()
-    initialized = shifted = False
-    poses, its, updates, shifts = [], [], 0, 0
-    for cloud in clouds:
-        scan = O.preprocess(cloud, pose, res)
-        d = np.linalg.norm(last_tsdf[:3, 3] / np.float32(1000) - pose[:3, 3] / np.float32(1000))
-        if not initialized or d > 0.3 or shifted:
-            initialized, last_tsdf, shifted = True, pose.copy(), False
-            pos, up = W.to_map(pose, res), W.to_int_mat(pose)[:3, 2]
-            O.update_tsdf(om, on, scan, pos, up, tau, mw, res)
-            updates += 1
-        T, it, _ = O.register_cloud(om, scan, np.eye(4), reg[0], reg[1], reg[2], res)
-        T = T.astype(np.float32)
-        # app.cpp:172-176 in float32, products summed in index order -- spelled out: numpy's matmul goes through BLAS, whose
-        # summation order / FMA use is not specified (it differed from the index-order sum by one ulp on the GPU box, which
-        # the bit-exact pose assertion below caught once it stopped being a silent skip)
-        R = np.zeros((3, 3), dtype=np.float32)
-        for i in range(3):
-            for j in range(3):
-                acc = np.float32(0)
-                for k in range(3):
-                    acc = np.float32(acc + np.float32(T[i, k] * pose[k, j]))
-                R[i, j] = acc
-        pose[:3, :3] = R
-        pose[:3, 3] += T[:3, 3]
-        poses.append(pose.copy())
-        its.append(it)
-        if np.linalg.norm(last_shift[:3, 3] / np.float32(1000) - pose[:3, 3] / np.float32(1000)) >= shift_m:
-            last_shift = pose.copy()
-            lm.data[:] = om.data
-            lm.pos[:], lm.offset[:] = om.pos, om.offset
-            lm.shift(W.to_map(pose, res))
-            om = O.OracleMap(size, tau, 0, pos=lm.pos, offset=lm.offset)
-            om.data[:] = lm.data
-            on = O.OracleMap(size, tau, 0, pos=lm.pos, offset=lm.offset)
-            shifted = True
-            shifts += 1
-    return poses, its, updates, shifts, om
 
 
 def test_replay_matches_oracle_sequence(tmp_path):

@@ -8,11 +8,11 @@ import itertools
 import numpy as np
 import pytest
 
-import test_gpu_mesh as M
-import test_gpu_raycast as R
-import test_gpu_surface as G
-import test_sample_host as H
-from warpsense_amd import synthetic as S
+import mesh_model as M
+import query_model as QM
+import raycast_model as R
+import sample_model as H
+from scan_clouds import CLUSTER_AT, app_stream, room_scan
 
 pytestmark = pytest.mark.gpu
 TAU, RES = H.TAU, H.RES
@@ -41,7 +41,7 @@ def test_random_maps_match_the_model(size, seed, res):
         _, _, _, ring, pts, band = cases[which]
         p32 = pts.astype(np.int32)
         p_dev = torch.from_numpy(p32).cuda()
-        w = G.wrapper(t, which)
+        w = QM.wrapper(t, which)
         for any_weight in (False, True):
             want = H.model(ring, res, pts, band, any_weight, select=(H.FREE, H.INSIDE))
             kw = dict(band_mm=band, any_weight=any_weight, gradient=True, select=("free", "inside"))
@@ -82,7 +82,7 @@ def test_rotated_rings_after_the_shift_sequence():
     for new_pos in [(3, 0, 0), (3, -4, 2), (10, -4, 2), (10, 5, -3), (-2, 5, -3)]:
         tm.shift_map(new_pos)
     for which in (0, 1):
-        host = G.download(W, tm, lm, which)
+        host = QM.download(W, tm, lm, which)
         assert all(int(o) != 0 for o in host.offset_) and list(host.pos_) == [-2, 5, -3]
         ring = R.Ring(host.data_, host.size_, host.pos_, host.offset_)
         pts = H.window_points(ring.lo, ring.hi, RES, seed=17 + which, n=4096)
@@ -92,7 +92,7 @@ def test_rotated_rings_after_the_shift_sequence():
             n_grad = int(np.count_nonzero(np.any(want[2] != 0, axis=1)))
             print(which, any_weight, want[1].tolist(), n_grad)
             assert want[1].min() >= 16 and n_grad >= 16
-            got = G.wrapper(tm.tsdf(), which).sample(pts.astype(np.int32), any_weight=any_weight, gradient=True, select=("surface", "inside"))  # band: the map's tau
+            got = QM.wrapper(tm.tsdf(), which).sample(pts.astype(np.int32), any_weight=any_weight, gradient=True, select=("surface", "inside"))  # band: the map's tau
             assert H.same(got, want), (which, any_weight)
 
 
@@ -103,7 +103,7 @@ def test_even_window_sizes(size):
         _, _, _, ring, pts, band = cases[which]
         want = H.model(ring, RES, pts, band, True, select=(H.FREE,))
         assert want[1].min() >= 16 and np.count_nonzero(np.any(want[2] != 0, axis=1)) >= 16
-        assert H.same(G.wrapper(t, which).sample(pts.astype(np.int32), band_mm=band, any_weight=True, gradient=True, select=("free",)), want), which
+        assert H.same(QM.wrapper(t, which).sample(pts.astype(np.int32), band_mm=band, any_weight=True, gradient=True, select=("free",)), want), which
     t.close()
 
 
@@ -125,13 +125,13 @@ def test_prefix_downloads_refusals_and_no_points():
     avg.surface(), avg.mesh(), avg.raycast((0, 0, 0), p32[:50], 3000)
     pr, pg, ps = np.zeros(233, dtype=H.SAMPLE), np.zeros((233, 3), dtype=np.int32), np.zeros((5, 3), dtype=np.int32)
     assert L.ws_map_sample_download(t.handle, vp(pr), vp(pg), vp(ps), 233, 5, C.byref(n), C.byref(ns)) == 0
-    assert (n.value, ns.value) == (700, len(sel)) and G.same(pr, rec[:233]) and G.same(pg, grad[:233]) and G.same(ps, sel[:5])
+    assert (n.value, ns.value) == (700, len(sel)) and QM.same(pr, rec[:233]) and QM.same(pg, grad[:233]) and QM.same(ps, sel[:5])
     assert L.ws_map_sample_download(t.handle, None, None, None, 0, 0, C.byref(n), C.byref(ns)) == 0 and (n.value, ns.value) == (700, len(sel))
 
     def last_is_intact():
         a, b, c = np.zeros(700, dtype=H.SAMPLE), np.zeros((700, 3), dtype=np.int32), np.zeros((len(sel), 3), dtype=np.int32)
         assert L.ws_map_sample_download(t.handle, vp(a), vp(b), vp(c), 700, len(sel), C.byref(n), C.byref(ns)) == 0
-        return (n.value, ns.value) == (700, len(sel)) and G.same(a, rec) and G.same(b, grad) and G.same(c, sel)
+        return (n.value, ns.value) == (700, len(sel)) and QM.same(a, rec) and QM.same(b, grad) and QM.same(c, sel)
 
     # every refusal returns its code, launches nothing and leaves the last result readable
     cnt = np.full(4, 77, dtype=np.uint64)
@@ -169,14 +169,6 @@ def test_prefix_downloads_refusals_and_no_points():
     ms = (C.c_float * 3)()
     assert L.ws_debug_sample_timing(t.handle, 0, ms) == 0 and ms[1] > 0 and ms[2] > 0
     t.close()
-
-
-# ------------------------------------------------------------------------------------------------ 5: composition
-CLUSTER_AT = (600, 0, 0)
-
-
-def room_scan(k, sensor):
-    return S.os1_128_scan(sensor_mm=sensor, rings=32, azimuths=256, half_extents_mm=(1400.0, 1300.0, 900.0), seed=2 + k)
 
 
 def test_after_real_scans_a_cluster_in_mid_room_is_free():
@@ -222,23 +214,6 @@ def test_after_real_scans_a_cluster_in_mid_room_is_free():
     assert np.array_equal(maps[0], maps[1]) and not np.array_equal(maps[0], host.data_)
     assert np.array_equal(poses[0][0], poses[1][0]) and poses[0][1] == poses[1][1] > 0
     t.close(), ta.close(), tb.close()
-
-
-APP_CLUSTER_AT = (300, 800, 0)  # beside the path (never nearer than 0.5 m), y >= 0.3 m in every sensor frame (the filter of App::preprocess), in space the first scan saw free
-
-
-def app_stream(n_scans, cluster_from=1):
-    """sensor-frame clouds (metres) of a sensor moving through the room of test_gpu_replay; from scan `cluster_from` on, 200 points of
-    a thing that stands at APP_CLUSTER_AT +- 100 mm in the world, where the first scan saw free space"""
-    clouds = []
-    cluster = np.asarray(APP_CLUSTER_AT) + np.random.default_rng(5).integers(-100, 101, (200, 3))
-    for k in range(n_scans):
-        sensor = np.array([k * 180.0, 90.0 * k, 0.0])
-        pts = S.os1_128_scan(sensor_mm=tuple(sensor), rings=32, azimuths=256, half_extents_mm=(2600.0, 2200.0, 1100.0), seed=100 + k)
-        if k >= cluster_from:
-            pts = np.concatenate([pts, cluster])
-        clouds.append(((pts.astype(np.float64) - sensor) / 1000.0).astype(np.float32))
-    return clouds
 
 
 def test_app_rejects_dynamic_points_only_when_asked():

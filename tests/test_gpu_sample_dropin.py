@@ -1,37 +1,29 @@
 """The C++ drop-in of the point sample (include/warpsense_hip/visualization.hpp, app.hpp) against the Python route: the wrappers for the
 window and for the store give the same bytes, and AppParams::reject_dynamic the same rejected counts and poses as App(reject_dynamic=True).
 Same C ABI underneath, so everything must agree exactly.  tests/cpp/sample_dropin.cpp prints counts and FNV-1a digests."""
-import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
-import test_gpu_sample as T
-import test_gpu_surface as G
+from dropin_build import build_dropin
+import query_model as QM
+import scan_clouds as T
 from warpsense_amd import synthetic as S
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    cxx = shutil.which("g++")
-    assert cxx is not None, "the C++ drop-in needs g++"
-    out = tmp_path_factory.mktemp("sample_dropin") / "sample_dropin"
-    lib = os.path.join(ROOT, "warpsense_amd")
-    subprocess.check_call([cxx, "-O2", "-std=c++17", "-Wall", "-ffp-contract=off", f"-I{os.path.join(ROOT, 'include')}",
-                           os.path.join(ROOT, "tests", "cpp", "sample_dropin.cpp"), "-o", str(out), f"-L{lib}", f"-Wl,-rpath,{lib}",
-                           "-Wl,-rpath,/opt/rocm/lib", "-lwarpsense_hip", "-lpthread"])
+    out = build_dropin("sample_dropin", tmp_path_factory.mktemp("sample_dropin"))
     return str(out)
 
 
 def line_of(result):
     """what sample_dropin.cpp prints for a (records, counts, gradient | None, selection | None)"""
     rec, counts, grad, sel = result
-    h = lambda a: f"{G.fnv1a(b'' if a is None else a.tobytes()):016x}"
+    h = lambda a: f"{QM.fnv1a(b'' if a is None else a.tobytes()):016x}"
     return [str(len(rec))] + [str(int(c)) for c in counts] + [h(rec), h(grad), str(0 if sel is None else len(sel)), h(sel)]
 
 
@@ -58,7 +50,7 @@ def test_wrappers_give_the_bytes_of_the_python_route(exe, tmp_path):
     b = t.avg_map().sample(points, any_weight=True, select=("surface",))
     assert lines["window_any"] == line_of(b) and lines["window_any"] != lines["window"]
     store = W.DeviceGlobalMap(tau, 0)
-    lo, hi = G.window(lm.size, lm.pos)
+    lo, hi = QM.window(lm.size, lm.pos)
     store.save_box(t, lo, hi)
     c = store.sample(res, points, tau // 2, gradient=True, select=("free", "unknown"))
     assert lines["store"] == line_of(c)

@@ -6,7 +6,6 @@ buffer) holding the whole prepared cloud and accumulating only its range [r*N/G,
 with the oracle's loop (registration.cu:347-368 x tsdf_registration.cpp:55-92).  A second test runs the real driver
 (warpsense_amd.dist.sharded_register_cloud, the `iterate` route) in two processes that share cuda:0 and all-reduce over gloo.
 """
-import ctypes as C
 import os
 import socket
 
@@ -14,39 +13,17 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from reg_scenes import _OracleLoop
 from warpsense_amd import synthetic as S
 
 pytestmark = pytest.mark.gpu
 
 
 def _scene(rings=32, az=256):
-    import test_gpu_registration as R
+    import reg_scenes as R
     reg, oa, pts, res = R.build_scene(rings=rings, az=az)
     q = S.transform_points_mm(pts, S.perturbation(30, -22, 7, 1.4))
     return reg, oa, q, res
-
-
-class _OracleLoop:
-    """the oracle's Gauss-Newton loop, one step at a time (wso_gn_begin / wso_reg_iterate / wso_gn_update)"""
-
-    def __init__(self, omap, points, res, T_in, max_iterations, it_weight_gradient, epsilon):
-        from test_abi_and_host import OracleGnBackend
-        self.b = OracleGnBackend(omap, points, res)
-        self.b.begin(T_in, max_iterations, it_weight_gradient, epsilon)
-        self.n = points.shape[0]
-
-    def finished(self):
-        return self.b.poll()[0]
-
-    def sums(self):
-        return self.b.accumulate(0, self.n).numpy().copy()
-
-    def update(self, sums):
-        import torch
-        self.b.solve(torch.from_numpy(np.ascontiguousarray(sums, dtype=np.int64)))
-
-    def result(self):
-        return self.b.poll()
 
 
 @pytest.mark.parametrize("route", ["iterate", "accumulate"])

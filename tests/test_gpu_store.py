@@ -1,62 +1,19 @@
 """The global map in device memory (ws_store_*, ws_shift_device, map_store.hip) against the world model of tests/window_model.py and
 against today's host route (TSDFMapping.shift_map with an in-memory GlobalMap).  Every comparison is np.array_equal."""
-import ctypes as C
 import os
 
 import numpy as np
 import pytest
 
-import window_model as M
-from test_gpu_map_window import MW, RES, TAU, MappingRoute, RawRoute, _default, _i3, _p, _params, check_device, download, get_params, same_state, state
 from window_model import WALKS
+import window_model as M
+from window_routes import MW, RES, TAU, MappingRoute, RawRoute, _default, _i3, _p, _params, check_device, download, get_params, same_state, state
+from window_routes import CW, StoreRoute, chunk_box, same_store, store_state
 from warpsense_amd import synthetic as S
 
 pytestmark = pytest.mark.gpu
 
 WS_ERR_INVALID, WS_ERR_CAPACITY = -1, -4
-CW = 64 ** 3
-
-
-class StoreRoute:
-    """TSDFMapping.shift_map_device with a DeviceGlobalMap"""
-
-    def __init__(self, size, segment_chunks=0, max_chunks=0, base=None):
-        import warpsense_amd as W
-        self.lm = W.LocalMap(*size, TAU, 0)
-        assert tuple(self.lm.size) == tuple(size)
-        if base is not None:  # the window starts there: through the parameters, before the device map exists
-            self.lm.pos[:] = base
-            self.lm.offset[:] = M.model_offset(size, base)
-        self.store = W.DeviceGlobalMap(TAU, 0, max_chunks=max_chunks, segment_chunks=segment_chunks)
-        self.tm = W.TSDFMapping(_params(size), self.lm, device_global_map=self.store)
-        self.t = self.tm.tsdf()
-
-    def insert(self, lo, hi, words):
-        self.t.avg_map().insert_box(lo, hi, words)
-
-    def shift(self, w, new_pos):
-        self.tm.shift_map_device(new_pos)
-
-    def check(self, w):
-        check_device(self.t, w)
-        assert np.array_equal(self.lm.pos, w.pos) and np.array_equal(self.lm.offset, w.offset())
-
-    def chunks(self):
-        return {key: self.store.chunk(key) for key in self.store.keys()}
-
-    def finish(self, w):
-        chunks = self.chunks()
-        w.check_chunks(chunks)
-        return chunks
-
-
-def store_state(store):
-    keys = store.keys()
-    return keys, [store.chunk(k) for k in keys]
-
-
-def same_store(a, b):
-    return a[0] == b[0] and all(np.array_equal(x, y) for x, y in zip(a[1], b[1]))
 
 
 # ------------------------------------------------------------------------------------------------ 1. the walks
@@ -99,15 +56,6 @@ def rotated_world(size, pos, seed):
     w.write(lo, hi, M.draw_words(np.random.default_rng(seed), np.prod(size)))
     assert np.all(w.offset() != 0)
     return w
-
-
-def chunk_box(key, lo, hi):
-    """chunk-and-box as (slices of the chunk, world lo, world hi), None if they do not meet"""
-    base = np.asarray(key, dtype=np.int64) * 64
-    it = M.box_inter(base, base + 63, np.asarray(lo, dtype=np.int64), np.asarray(hi, dtype=np.int64))
-    if it is None:
-        return None
-    return tuple(slice(int(it[0][k] - base[k]), int(it[1][k] - base[k]) + 1) for k in range(3)), it[0], it[1]
 
 
 @pytest.mark.parametrize("size,pos", [((71, 61, 67), (40, -25, 30)), ((16, 18, 20), (3, -2, 5)), ((70, 66, 130), (-31, 40, -70))])

@@ -1,6 +1,6 @@
 """ws_store_distance — the distance field of the global map in device memory (the rules are stated in include/warpsense_hip.h)
-against the numpy model that ws_map_distance is held to (test_gpu_distance.model_box), applied to a dense box assembled from host
-copies of the chunks (test_gpu_store_mesh.assemble) with every voxel of an absent chunk raw 0: weight 0, unknown.  Every comparison
+against the numpy model that ws_map_distance is held to (distance_model.model_box), applied to a dense box assembled from host
+copies of the chunks (store_scenes.assemble) with every voxel of an absent chunk raw 0: weight 0, unknown.  Every comparison
 is bit for bit on the raw uint32 records, and on the site count.
 
 tests/test_store_distance_host.py holds the assembled-box model against the brute-force minimum and checks the input condition of
@@ -11,64 +11,14 @@ import itertools
 import numpy as np
 import pytest
 
-import test_gpu_distance as D
-import test_gpu_store_mesh as SM
-import test_gpu_surface as G
+import distance_model as D
+import query_model as QM
+from store_distance_scenes import CS, CUT_BOXES, CW, FLAGS, MW, PILLAR_Y, PILLAR_Y_SEED, PILLAR_Z, PILLAR_Z_SEED, RANGES, RES, SEAM_SEED, TAU, WINDOW_SEED, make_store, model, pillar_chunks, seam_chunks, seam_model
+import store_scenes as SM
 
 pytestmark = pytest.mark.gpu
-TAU, RES, MW = D.TAU, D.RES, 640
-CS, CW = SM.CS, SM.CW
 WS_ERR_INVALID, WS_ERR_RANGE = -1, -5
-FLAGS, RANGES = D.FLAGS, D.RANGES
-FLAG_BITS = lambda kw: (1 if kw.get("any_weight") else 0) | (2 if kw.get("unknown_occupied") else 0) | (4 if kw.get("columns") else 0)
 KMAX, KMIN = (2 ** 31 - 1) // CS, -(2 ** 31) // CS  # the last and the first chunk key of int32 voxel space
-
-# ------------------------------------------------------------------------------------------------ the draws
-# one draw of test_gpu_distance.draw_entries per chunk; tests/test_store_distance_host.py checks each against D.check_inputs
-SEAM_SEED, PILLAR_Z_SEED, PILLAR_Y_SEED, WINDOW_SEED = 7100, 7200, 7300, 7400
-SEAM_KEYS, ABSENT = SM.SEAM_KEYS, SM.ABSENT
-PILLAR_Z = [(0, 0, k) for k in range(-2, 3)]
-PILLAR_Y = [(0, k, 0) for k in range(-2, 3)]
-HOLE = 2  # the middle chunk of a pillar is absent
-SEEDS = ([((CS,) * 3, SEAM_SEED + i) for i in range(8)] + [((CS,) * 3, PILLAR_Z_SEED + i) for i in range(5)]
-         + [((CS,) * 3, PILLAR_Y_SEED + i) for i in range(5)] + [((65,) * 3, WINDOW_SEED)])
-_CACHE = {}
-
-
-def drawn(keys, seed, absent=()):
-    return {key: D.draw_entries((CS,) * 3, seed + i) for i, key in enumerate(keys) if key not in absent}
-
-
-def seam_chunks():
-    if "seam" not in _CACHE:
-        _CACHE["seam"] = drawn(SEAM_KEYS, SEAM_SEED, (ABSENT,))
-    return _CACHE["seam"]
-
-
-def pillar_chunks(keys, seed):
-    if seed not in _CACHE:
-        _CACHE[seed] = drawn(keys, seed, (keys[HOLE],))
-    return _CACHE[seed]
-
-
-def model(chunks, lo, hi, R, **kw):
-    """(records, sites) of the rules on the dense box [lo, hi] of `chunks`; absent chunks are weight-0 entries"""
-    return D.model_box(SM.assemble(chunks, lo, hi), R, **kw)
-
-
-def seam_model(lo, hi, R, **kw):
-    key = ("seam", tuple(lo), tuple(hi), R, FLAG_BITS(kw))
-    if key not in _CACHE:
-        _CACHE[key] = model(seam_chunks(), lo, hi, R, **kw)
-    return _CACHE[key]
-
-
-def make_store(chunks, segment_chunks=2, shift=(0, 0, 0)):
-    import warpsense_amd as W
-    store = W.DeviceGlobalMap(TAU, 0, segment_chunks=segment_chunks)
-    for key in sorted(chunks):
-        store.put_chunk(tuple(int(k + s) for k, s in zip(key, shift)), chunks[key])
-    return store
 
 
 @pytest.fixture(scope="module")
@@ -101,10 +51,6 @@ def check(store, chunks, lo, hi, R, what, **kw):
     got = store.distance(lo=lo, hi=hi, max_dist_vox=R, **kw)
     assert D.same(got, want) and store.last_sites == n_sites, (what, lo, hi, R, kw, store.last_sites, n_sites)
     return got
-
-
-# ------------------------------------------------------------------------------------------------ 1. seams
-CUT_BOXES = SM.CUT_BOXES  # both contain the common corner of the eight chunks, neither is chunk-aligned
 
 
 @pytest.mark.parametrize("box", range(len(CUT_BOXES)))
@@ -202,7 +148,7 @@ def test_same_bytes_as_the_window():
     t = W.TSDFCuda(lm.device_map(), TAU, MW, RES)
     store = W.DeviceGlobalMap(TAU, 0, segment_chunks=2)
     try:
-        lo, hi = G.window(lm.size, lm.pos)
+        lo, hi = QM.window(lm.size, lm.pos)
         assert tuple(lo) == (-32,) * 3 and tuple(hi) == (32,) * 3 and (store.default_raw >> 16) == 0  # fill_entry has weight 0
         t.avg_map().insert_box(lo, hi, D.draw_entries((65,) * 3, WINDOW_SEED))
         store.save_box(t, lo, hi)
@@ -297,8 +243,8 @@ def test_drop_put_and_old_results():
 
 # ------------------------------------------------------------------------------------------------ 7. results and downloads
 def test_repeatable_partial_downloads_and_apart_from_the_other_results(seam_store):
-    import test_gpu_mesh as M
-    import test_gpu_raycast as RC
+    import mesh_model as M
+    import raycast_model as RC
     import warpsense_amd as W
     L, h = seam_store._L, seam_store.handle
     lo, hi = CUT_BOXES[0]
@@ -319,7 +265,7 @@ def test_repeatable_partial_downloads_and_apart_from_the_other_results(seam_stor
     # the store's mesh and ray-cast results and a window's distance result survive a store distance call, and the other way round
     lm = W.LocalMap(15, 15, 15, TAU, 0)
     t = W.TSDFCuda(lm.device_map(), TAU, MW, RES)
-    wlo, whi = G.window(lm.size, lm.pos)
+    wlo, whi = QM.window(lm.size, lm.pos)
     t.avg_map().insert_box(wlo, whi, D.draw_entries((15,) * 3, 22))
     wrec = t.avg_map().distance(max_dist_vox=7)
     vert, face = seam_store.mesh(RES, any_weight=True)
@@ -332,7 +278,7 @@ def test_repeatable_partial_downloads_and_apart_from_the_other_results(seam_stor
     assert L.ws_store_mesh_download(h, pv.ctypes.data_as(C.c_void_p), pf.ctypes.data_as(C.c_void_p), len(vert), len(face), C.byref(gv), C.byref(gf)) == 0
     assert M.same((pv, pf), (vert, face))
     pr = np.zeros(300, dtype=RC.RAY)
-    assert L.ws_store_raycast_download(h, pr.ctypes.data_as(C.c_void_p), None, 300, C.byref(n)) == 0 and n.value == 300 and G.same(pr, rays)
+    assert L.ws_store_raycast_download(h, pr.ctypes.data_as(C.c_void_p), None, 300, C.byref(n)) == 0 and n.value == 300 and QM.same(pr, rays)
     got = np.zeros(wrec.size, dtype=np.uint32)
     assert t._L.ws_map_distance_download(t.handle, got.ctypes.data_as(C.c_void_p), got.size, C.byref(n)) == 0 and np.array_equal(got, wrec.reshape(-1))
     seam_store.mesh(RES)
@@ -351,7 +297,7 @@ def test_repeatable_partial_downloads_and_apart_from_the_other_results(seam_stor
 
 # ------------------------------------------------------------------------------------------------ 8. error codes
 def test_error_codes_leave_the_last_result_and_launch_nothing():
-    from test_gpu_store import same_store, store_state
+    from window_routes import same_store, store_state
     import warpsense_amd as W
     chunks = {(0, 0, 0): seam_chunks()[(0, 0, 0)]}
     store = make_store(chunks)
@@ -395,7 +341,7 @@ def test_error_codes_leave_the_last_result_and_launch_nothing():
 def test_after_real_use():
     """the three-position walk of test_gpu_store_mesh.test_after_real_use: the window shifts through the device global map"""
     import warpsense_amd as W
-    from test_gpu_map_window import _params
+    from window_routes import _params
     size = (65, 65, 65)
     lm = W.LocalMap(*size, TAU, 0, W.GlobalMap(TAU, 0))
     store = W.DeviceGlobalMap(TAU, 0, segment_chunks=2)
@@ -438,7 +384,7 @@ def test_create_distance_destroy_gives_its_memory_back():
     before it by more than that file's margin; the first cycle warms the runtime's pools and is left out"""
     import torch
     import warpsense_amd as W
-    from test_gpu_lifecycle import CYCLES, MARGIN
+    from lifecycle_model import CYCLES, MARGIN
     chunks = {k: seam_chunks()[k] for k in ((-1, -1, -1), (0, 0, 0))}
     free = []
     for _ in range(CYCLES):

@@ -1,18 +1,16 @@
 """The C++ drop-in of the device global map (tests/cpp/store_dropin.cpp): MappingNode::shift_map_device along a walk read from a
 file prints the digests of the window and of every chunk that the Python route gives, and so does its write_back."""
-import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
-import test_gpu_store as G
+from dropin_build import build_dropin
 import window_model as M
-from test_gpu_map_window import MW, RES, TAU, _default, download
+from window_routes import MW, RES, TAU, _default, download
+import window_routes as G
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def digest(words):
@@ -41,13 +39,7 @@ class Recorder:
 
 
 def test_cpp_shift_map_device_equals_the_python_route(tmp_path):
-    cxx = shutil.which("g++")
-    assert cxx is not None, "the C++ drop-in needs g++"
-    exe = tmp_path / "store_dropin"
-    lib = os.path.join(ROOT, "warpsense_amd")
-    subprocess.check_call([cxx, "-O2", "-std=c++17", "-Wall", "-ffp-contract=off", f"-I{os.path.join(ROOT, 'include')}",
-                           os.path.join(ROOT, "tests", "cpp", "store_dropin.cpp"), "-o", str(exe), f"-L{lib}", f"-Wl,-rpath,{lib}",
-                           "-Wl,-rpath,/opt/rocm/lib", "-lwarpsense_hip", "-lpthread"])
+    exe = build_dropin("store_dropin", tmp_path)
     size, seed = M.WALKS[0]
     walk = M.make_walk(size, seed)
     rec = Recorder(G.StoreRoute(size, segment_chunks=2))

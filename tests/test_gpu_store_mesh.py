@@ -6,130 +6,12 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import test_gpu_mesh as M
-import test_gpu_surface as G
+import mesh_model as M
+import query_model as QM
+from store_scenes import CS, CUT_BOXES, CW, MW, RES, TAU, WALK, _SEAM, bounding_box, check_seam_inputs, crossing_faces, far_chunks, make_store, model_store, raw_mesh, seam_chunks, seam_model, seam_world, split, walk_scan
 
 pytestmark = pytest.mark.gpu
-TAU, RES, MW = M.TAU, M.RES, 640
-CS, CW = 64, 64 ** 3
 WS_ERR_INVALID, WS_ERR_RANGE = -1, -5
-
-
-# ------------------------------------------------------------------------------------------------ the model on chunks
-def bounding_box(keys):
-    k = np.asarray(sorted(keys), dtype=np.int64).reshape(-1, 3)
-    return k.min(axis=0) * CS, k.max(axis=0) * CS + CS - 1
-
-
-def assemble(chunks, lo, hi):
-    """the dense box [lo, hi] (inclusive world voxels) of raw entries: box[x - lo] = the voxel of its chunk (index lx * 4096 + ly * 64
-    + lz, key = floor(voxel / 64)), raw 0 where `chunks` (key -> 262 144 uint32) has no such chunk"""
-    lo, hi = np.asarray(lo, dtype=np.int64), np.asarray(hi, dtype=np.int64)
-    box = np.zeros(tuple(int(v) for v in hi - lo + 1), dtype=np.uint32)
-    for key, data in chunks.items():
-        base = np.asarray(key, dtype=np.int64) * CS
-        a, b = np.maximum(lo, base), np.minimum(hi, base + CS - 1)
-        if np.any(a > b):
-            continue
-        src = np.asarray(data, dtype=np.uint32).reshape(CS, CS, CS)
-        box[tuple(slice(int(a[k] - lo[k]), int(b[k] - lo[k]) + 1) for k in range(3))] = \
-            src[tuple(slice(int(a[k] - base[k]), int(b[k] - base[k]) + 1) for k in range(3))]
-    return box
-
-
-def model_store(chunks, res, lo=None, hi=None, any_weight=False):
-    if lo is None:
-        if not chunks:
-            return np.empty(0, dtype=M.VERT), np.empty((0, 3), dtype=np.uint32)
-        lo, hi = bounding_box(chunks)
-    return M.model_box(assemble(chunks, lo, hi), np.asarray(lo, dtype=np.int64), res, any_weight)
-
-
-def word_index(keys):
-    """The world-order formula of store_mesh.hip: for the chunk list `keys` (n x 3) the index of every word, shape (n, 64, 64) over
-    (chunk, lx, ly): 4096 B[cx] + lx 64 N[cx] + 64 P[cx, cy] + ly n[cx, cy] + r"""
-    keys = np.asarray(keys, dtype=np.int64).reshape(-1, 3)
-    n_chunks = len(keys)
-    B, N, P, n, r = (np.zeros(n_chunks, dtype=np.int64) for _ in range(5))
-    for i, (cx, cy, cz) in enumerate(keys):
-        same_x, same_xy = keys[:, 0] == cx, (keys[:, 0] == cx) & (keys[:, 1] == cy)
-        B[i], N[i] = np.count_nonzero(keys[:, 0] < cx), np.count_nonzero(same_x)
-        P[i], n[i] = np.count_nonzero(same_x & (keys[:, 1] < cy)), np.count_nonzero(same_xy)
-        r[i] = np.count_nonzero(same_xy & (keys[:, 2] < cz))
-    lx, ly = np.arange(CS, dtype=np.int64)[None, :, None], np.arange(CS, dtype=np.int64)[None, None, :]
-    return 4096 * B[:, None, None] + lx * 64 * N[:, None, None] + 64 * P[:, None, None] + ly * n[:, None, None] + r[:, None, None]
-
-
-# ------------------------------------------------------------------------------------------------ the seam store
-ABSENT = (0, 0, -1)
-SEAM_KEYS = [(cx, cy, cz) for cx in (-1, 0) for cy in (-1, 0) for cz in (-1, 0)]
-SPHERE = ((64.3, 63.6, 64.6), 40.2)  # centre in box coordinates (world + 64), radius in voxels: around the common corner
-
-
-def split(world):
-    """a 128^3 array over the world voxels [-64, 63]^3 as the eight chunks (-1..0)^3"""
-    return {k: np.ascontiguousarray(world[tuple(slice(CS * (c + 1), CS * (c + 2)) for c in k)]).reshape(-1) for k in SEAM_KEYS}
-
-
-_SEAM = {}
-
-
-def seam_world():
-    """the sphere where its value is inside the truncation band, random entries in the slabs within 3 voxels of every chunk face,
-    weight 0 elsewhere; the planted pairs of test_gpu_mesh across the z seam"""
-    if "world" not in _SEAM:
-        import warpsense_amd as W
-        sphere = M.sphere_box(2 * CS, *SPHERE).reshape((2 * CS,) * 3)
-        value, weight = M.unpack(sphere)
-        weight = np.where(np.abs(value) < TAU, weight, 0)
-        rv, rw = M.unpack(M.draw_entries((2 * CS,) * 3, seed=128).reshape((2 * CS,) * 3))
-        near = np.isin(np.arange(2 * CS) % CS, (0, 1, 2, 61, 62, 63))
-        slab = near[:, None, None] | near[None, :, None] | near[None, None, :]
-        value, weight = np.where(slab, rv, value), np.where(slab, rw, weight)
-        z = CS - 1  # world z = -1 and 0: the pair straddles the z seam, in the chunks (-1, -1, -1) and (-1, -1, 0)
-        for p, ((va, wa), (vb, wb)) in enumerate(M.PLANT_PAIRS):
-            x, y = CS - 10 - 3 * p, CS - 12 - 2 * p
-            weight[x:x + 2, y:y + 2, z - 1:z + 3] = np.maximum(np.abs(weight[x:x + 2, y:y + 2, z - 1:z + 3]), 1)
-            value[x, y, z], weight[x, y, z] = va, wa
-            value[x, y, z + 1], weight[x, y, z + 1] = vb, wb
-        _SEAM["world"] = W.pack_entry(value.reshape(-1), weight.reshape(-1)).astype(np.uint32).reshape((2 * CS,) * 3)
-        _SEAM["sphere"] = sphere
-    return _SEAM["world"]
-
-
-def seam_chunks():
-    if "chunks" not in _SEAM:
-        chunks = split(seam_world())
-        del chunks[ABSENT]
-        _SEAM["chunks"] = chunks
-    return _SEAM["chunks"]
-
-
-def seam_model(any_weight=False, lo=None, hi=None):
-    """the model's mesh of the seam store, computed once per case"""
-    key = ("model", any_weight, None if lo is None else (tuple(lo), tuple(hi)))
-    if key not in _SEAM:
-        _SEAM[key] = model_store(seam_chunks(), RES, lo, hi, any_weight)
-    return _SEAM[key]
-
-
-def check_seam_inputs():
-    """conditions on the INPUTS: the planted pairs straddle the z seam, and the model's mesh is not small under either rule"""
-    value, weight = M.unpack(seam_world())
-    for p, ((va, wa), (vb, wb)) in enumerate(M.PLANT_PAIRS):
-        x, y = CS - 10 - 3 * p, CS - 12 - 2 * p
-        assert (value[x, y, CS - 1], weight[x, y, CS - 1], value[x, y, CS], weight[x, y, CS]) == (va, wa, vb, wb)
-    for any_weight in (False, True):
-        vert, face = seam_model(any_weight)
-        assert len(vert) > 100 and len(face) > 100, (any_weight, len(vert), len(face))
-
-
-def make_store(chunks, segment_chunks=2):
-    import warpsense_amd as W
-    store = W.DeviceGlobalMap(TAU, 0, segment_chunks=segment_chunks)
-    for key in sorted(chunks):
-        store.put_chunk(key, chunks[key])
-    return store
 
 
 @pytest.fixture(scope="module")
@@ -138,14 +20,6 @@ def seam_store():
     store = make_store(seam_chunks())
     yield store
     store.close()
-
-
-def raw_mesh(store, lo, hi, res, flags=0):
-    nv, nf = C.c_size_t(7), C.c_size_t(7)
-    p = lambda v: None if v is None else np.ascontiguousarray(v, dtype=np.int32).ctypes.data_as(C.c_void_p)
-    a, b = (None if v is None else np.ascontiguousarray(v, dtype=np.int32) for v in (lo, hi))
-    rc = store._L.ws_store_mesh(store.handle, p(a), p(b), res, flags, C.byref(nv), C.byref(nf))
-    return rc, nv.value, nf.value
 
 
 def totals(store):
@@ -183,15 +57,11 @@ def test_sphere_over_eight_chunks_is_closed():
         store.close()
 
 
-# ------------------------------------------------------------------------------------------------ 2. the window's bytes
-CUT_BOXES = [((-40, -29, -50), (37, 45, 20)), ((-64, -3, -7), (63, 2, 9))]
-
-
 def test_same_bytes_as_the_window_mesh(seam_store):
     import warpsense_amd as W
     lm = W.LocalMap(129, 129, 129, TAU, 0)
     t = W.TSDFCuda(lm.device_map(), TAU, MW, RES)
-    lo, hi = G.window(lm.size, lm.pos)
+    lo, hi = QM.window(lm.size, lm.pos)
     assert tuple(lo) == (-64,) * 3 and tuple(hi) == (64,) * 3 and (seam_store.default_raw >> 16) == 0  # fill_entry has weight 0
     seam_store.load_box(t, lo, hi)
     for a, b in [((-64,) * 3, (63,) * 3)] + CUT_BOXES:
@@ -236,20 +106,6 @@ def test_boxes(seam_store):
     n = C.c_size_t(9)
     assert empty._L.ws_store_mesh_vertices_dev(empty.handle, C.byref(n)) is None and n.value == 0
     empty.close()
-
-
-# ------------------------------------------------------------------------------------------------ 4. far-apart chunks
-FAR_KEYS = [(-200, 150, -20), (0, 0, 0), (200, -150, 20)]
-
-
-def far_chunks():
-    out = {}
-    for i, key in enumerate(FAR_KEYS):
-        if i == 1:
-            out[key] = M.sphere_box(CS, (31.4, 32.2, 30.7), 21.3).reshape(-1)
-        else:
-            out[key] = M.draw_entries((CS,) * 3, seed=400 + i)
-    return out
 
 
 def test_far_apart_chunks_cost_three_chunks():
@@ -301,7 +157,7 @@ def test_drop_put_and_old_results():
         assert tuple(dv.shape) == (len(want[0]), 4) and tuple(df.shape) == (len(want[1]), 3)
         lm = W.LocalMap(21, 17, 13, TAU, 0)
         t = W.TSDFCuda(lm.device_map(), TAU, MW, RES)
-        lo, hi = G.window(lm.size, lm.pos)
+        lo, hi = QM.window(lm.size, lm.pos)
         t.avg_map().insert_box(lo, hi, M.draw_entries(tuple(int(s) for s in lm.size), seed=5))
         store.save_box(t, lo, hi)
         assert np.array_equal(dv.cpu().numpy().view(np.uint8).reshape(-1), want[0].view(np.uint8).reshape(-1))
@@ -325,11 +181,11 @@ def test_repeatable_and_partial_downloads(seam_store):
     gv, gf = C.c_size_t(0), C.c_size_t(0)
     L, h = seam_store._L, seam_store.handle
     assert L.ws_store_mesh_download(h, pv.ctypes.data_as(C.c_void_p), pf.ctypes.data_as(C.c_void_p), cv, cf, C.byref(gv), C.byref(gf)) == 0
-    assert (gv.value, gf.value) == (len(vert), len(face)) and G.same(pv[:cv], vert[:cv]) and G.same(pf[:cf], face[:cf])
+    assert (gv.value, gf.value) == (len(vert), len(face)) and QM.same(pv[:cv], vert[:cv]) and QM.same(pf[:cf], face[:cf])
     assert not pv[cv:].view(np.uint8).any() and not pf[cf:].any()  # a prefix, nothing beyond the capacity
     assert L.ws_store_mesh_download(h, None, None, 0, 0, C.byref(gv), C.byref(gf)) == 0 and (gv.value, gf.value) == (len(vert), len(face))
     only_f = np.zeros((len(face), 3), dtype=np.uint32)
-    assert L.ws_store_mesh_download(h, None, only_f.ctypes.data_as(C.c_void_p), 0, len(face), C.byref(gv), C.byref(gf)) == 0 and G.same(only_f, face)
+    assert L.ws_store_mesh_download(h, None, only_f.ctypes.data_as(C.c_void_p), 0, len(face), C.byref(gv), C.byref(gf)) == 0 and QM.same(only_f, face)
     ms = seam_store.mesh_timing(1)
     seam_store.mesh(RES)
     ms = seam_store.mesh_timing(0)
@@ -338,7 +194,7 @@ def test_repeatable_and_partial_downloads(seam_store):
 
 # ------------------------------------------------------------------------------------------------ 7. WS_ERR_RANGE
 def test_range_errors_launch_nothing():
-    from test_gpu_store import same_store, store_state
+    from window_routes import same_store, store_state
     far = 671090  # 64 * 671090 * 50 mm is beyond int32
     assert (CS * far + 1) * RES > 2 ** 31 - 1 and CS * far + CS - 1 < 2 ** 31
     chunks = {(0, 0, 0): far_chunks()[(0, 0, 0)]}
@@ -359,29 +215,9 @@ def test_range_errors_launch_nothing():
         store.close()
 
 
-# ------------------------------------------------------------------------------------------------ 8. after real use
-WALK = [(0, 0, 0), (40, 0, 0), (80, 0, 0)]  # window positions (voxels); the sensor stands in the middle of the window
-ROOM = (4500.0, 1300.0, 900.0)
-
-
-def walk_scan(k):
-    from warpsense_amd import synthetic as S
-    return S.os1_128_scan(sensor_mm=tuple(float(c * RES) for c in WALK[k]), rings=32, azimuths=256, half_extents_mm=ROOM, seed=20 + k)
-
-
-def crossing_faces(vert, face, res):
-    """faces with vertices in two different chunks: vertices strictly on both sides of a chunk border plane"""
-    n = 0
-    S = CS * res
-    for name in ("x_mm", "y_mm", "z_mm"):
-        q = vert[name][face.astype(np.int64)].astype(np.int64) - res // 2  # a vertex of cell c lies in [c res, (c + 1) res]
-        n += int(np.count_nonzero(np.floor_divide(q.max(axis=1) - 1, S) > np.floor_divide(q.min(axis=1), S)))
-    return n
-
-
 def test_after_real_use():
     import warpsense_amd as W
-    from test_gpu_map_window import _params
+    from window_routes import _params
     size = (65, 65, 65)
     g = W.GlobalMap(TAU, 0)
     lm = W.LocalMap(*size, TAU, 0, g)

@@ -1,29 +1,21 @@
 """The C++ drop-in of the mesh of the device global map (tests/cpp/store_mesh_dropin.cpp): MappingNode::global_mesh along the walk
 of test_gpu_store_mesh.test_after_real_use prints the digests of the bytes the Python route gives."""
-import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
-import test_gpu_store_mesh as SM
-import test_gpu_surface as G
-from test_gpu_map_window import _params
+from dropin_build import build_dropin
+import query_model as QM
+import store_scenes as SM
+from window_routes import _params
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_cpp_global_mesh_equals_the_python_route(tmp_path):
     import warpsense_amd as W
-    cxx = shutil.which("g++")
-    assert cxx is not None, "the C++ drop-in needs g++"
-    exe = tmp_path / "store_mesh_dropin"
-    lib = os.path.join(ROOT, "warpsense_amd")
-    subprocess.check_call([cxx, "-O2", "-std=c++17", "-Wall", "-ffp-contract=off", f"-I{os.path.join(ROOT, 'include')}",
-                           os.path.join(ROOT, "tests", "cpp", "store_mesh_dropin.cpp"), "-o", str(exe), f"-L{lib}", f"-Wl,-rpath,{lib}",
-                           "-Wl,-rpath,/opt/rocm/lib", "-lwarpsense_hip", "-lpthread"])
+    exe = build_dropin("store_mesh_dropin", tmp_path)
     scans = [SM.walk_scan(k) for k in range(len(SM.WALK))]
     np.concatenate(scans).tofile(tmp_path / "scans.bin")
     edge = 65
@@ -40,7 +32,7 @@ def test_cpp_global_mesh_equals_the_python_route(tmp_path):
 
     def line(mesh):
         vert, face = mesh
-        return [str(len(vert)), str(len(face)), f"{G.fnv1a(vert.tobytes()):016x}", f"{G.fnv1a(face.tobytes()):016x}"]
+        return [str(len(vert)), str(len(face)), f"{QM.fnv1a(vert.tobytes()):016x}", f"{QM.fnv1a(face.tobytes()):016x}"]
 
     vert, face = tm.global_mesh()
     assert len(vert) > 1000 and len(face) > 1000 and SM.crossing_faces(vert, face, SM.RES) >= 1

@@ -1,5 +1,5 @@
 """ws_store_raycast — the ray cast of the global map in device memory (the rules are stated in include/warpsense_hip.h) against the
-numpy model that ws_map_raycast is held to (test_gpu_raycast.model), applied to the `Chunks` field of test_store_raycast_host: host
+numpy model that ws_map_raycast is held to (raycast_model.model), applied to the `Chunks` field of store_raycast_scenes: host
 copies of the chunks, absent chunks and voxels outside the box not valid.  Every comparison is on the raw bytes of the records and
 of the gradient, for all rays.  The ray sets are those of test_store_raycast_host, which checks without a GPU that each has hits and
 no-hits in the model."""
@@ -8,11 +8,12 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import test_gpu_mesh as M
-import test_gpu_raycast as R
-import test_gpu_store_mesh as SM
-import test_gpu_surface as G
-import test_store_raycast_host as H
+import mesh_model as M
+import query_model as QM
+import raycast_model as R
+from store_raycast_scenes import raw_cast
+import store_raycast_scenes as H
+import store_scenes as SM
 
 pytestmark = pytest.mark.gpu
 TAU, RES, MW = SM.TAU, SM.RES, SM.MW
@@ -39,14 +40,6 @@ def seam_store():
     store.close()
 
 
-def raw_cast(store, origin, d, n, rng, res=RES, flags=0, lo=None, hi=None):
-    p = lambda v: None if v is None else v.ctypes.data_as(C.c_void_p)
-    a, b = (None if v is None else np.ascontiguousarray(v, dtype=np.int32) for v in (lo, hi))
-    o = np.ascontiguousarray(origin, dtype=np.int32)
-    hits = C.c_size_t(77)
-    return store._L.ws_store_raycast(store.handle, p(a), p(b), p(o), p(d), n, rng, res, flags, C.byref(hits)), hits.value
-
-
 def result(store, n_cap=None):
     """(rays, records, device pointer) of the last result, through the download entry"""
     L, n = store._L, C.c_size_t(0)
@@ -68,7 +61,7 @@ def test_seam_chunks_match_the_model(seam_store):
     got = seam_store.raycast(RES, case["origin"], d_dev, case["range"], gradient=True)
     assert R.same(got, H.want(case))
     rec, grad = cast(seam_store, case, gradient=False)
-    assert grad is None and G.same(rec, H.want(case)[0])
+    assert grad is None and QM.same(rec, H.want(case)[0])
     # hits whose cell straddles a chunk border exist on every axis, and the sphere is where it should be
     rec = H.want(H.seam_cases()[0])[0]
     b = (np.stack([rec["x_mm"], rec["y_mm"], rec["z_mm"]], axis=1)[rec["range_mm"] >= 0] - RES // 2) // RES
@@ -100,7 +93,7 @@ def test_same_bytes_as_the_window_raycast(seam_store):
     import warpsense_amd as W
     lm = W.LocalMap(129, 129, 129, TAU, 0)
     t = W.TSDFCuda(lm.device_map(), TAU, MW, RES)
-    lo, hi = G.window(lm.size, lm.pos)
+    lo, hi = QM.window(lm.size, lm.pos)
     assert tuple(lo) == (-64,) * 3 and tuple(hi) == (64,) * 3 and (seam_store.default_raw >> 16) == 0  # fill_entry has weight 0
     seam_store.load_box(t, lo, hi)
     cases = H.seam_cases()
@@ -153,7 +146,7 @@ def test_refusals_launch_nothing_and_leave_the_last_result(seam_store):
     want = H.want(case)
     check(seam_store, case)
     n0, rec0, ptr0 = result(seam_store)
-    assert n0 == len(want[0]) and G.same(rec0, want[0])
+    assert n0 == len(want[0]) and QM.same(rec0, want[0])
     d = np.ascontiguousarray(np.asarray(case["dirs"]).astype(np.int32))
     o = case["origin"]
     call = lambda **kw: raw_cast(seam_store, kw.pop("origin", o), d, kw.pop("n", len(d)), kw.pop("rng", 3000), **kw)[0]
@@ -164,7 +157,7 @@ def test_refusals_launch_nothing_and_leave_the_last_result(seam_store):
     assert call(origin=(0, 2 ** 31 - 1 - 3000 - 2 * RES + 1, 0)) == WS_ERR_RANGE
     assert call(origin=(0, 0, -(2 ** 31 - 1 - 3000 - 2 * RES + 1))) == WS_ERR_RANGE
     n1, rec1, ptr1 = result(seam_store)
-    assert (n1, ptr1) == (n0, ptr0) and G.same(rec1, rec0)  # nothing was launched, the last result stays
+    assert (n1, ptr1) == (n0, ptr0) and QM.same(rec1, rec0)  # nothing was launched, the last result stays
     assert call(origin=(0, -(2 ** 31 - 1 - 3000 - 2 * RES), 0)) == 0  # the edge of the range is served ...
     assert call(res=1024) == 0
     n = C.c_size_t(9)
@@ -196,7 +189,7 @@ def test_buffers_repeat_prefix_and_old_results():
         k = len(want[0]) // 3
         part_r, part_g = np.zeros(k + 1, dtype=R.RAY), np.zeros((k + 1, 3), dtype=np.int32)
         assert L.ws_store_raycast_download(h, part_r.ctypes.data_as(C.c_void_p), part_g.ctypes.data_as(C.c_void_p), k, C.byref(got)) == 0
-        assert got.value == len(want[0]) and G.same(part_r[:k], want[0][:k]) and G.same(part_g[:k], want[1][:k])
+        assert got.value == len(want[0]) and QM.same(part_r[:k], want[0][:k]) and QM.same(part_g[:k], want[1][:k])
         assert not part_r[k:].view(np.uint8).any() and not part_g[k:].any()  # a prefix, nothing beyond the capacity
         assert L.ws_store_raycast_download(h, None, None, 0, C.byref(got)) == 0 and got.value == len(want[0])
         ptr_r, ptr_g = L.ws_store_raycast_records_dev(h, C.byref(n)), L.ws_store_raycast_gradient_dev(h, C.byref(n))
@@ -204,7 +197,7 @@ def test_buffers_repeat_prefix_and_old_results():
         # the result stays readable while the store goes on: a save_box that creates and overwrites chunks, a drop, a put into its slot
         lm = W.LocalMap(21, 17, 13, TAU, 0)
         t = W.TSDFCuda(lm.device_map(), TAU, MW, RES)
-        lo, hi = G.window(lm.size, lm.pos)
+        lo, hi = QM.window(lm.size, lm.pos)
         t.avg_map().insert_box(lo, hi, M.draw_entries(tuple(int(s) for s in lm.size), seed=5))
         store.save_box(t, lo, hi)
         slots = store.capacity()
@@ -220,7 +213,7 @@ def test_buffers_repeat_prefix_and_old_results():
         now = {key: store.chunk(key) for key in store.keys()}
         assert len(now) == 8  # the save created (0, 0, -1)
         fresh = dict(case, name="seam sphere after the changes", chunks=lambda: now)
-        assert not G.same(H.want(fresh)[0], want[0])
+        assert not QM.same(H.want(fresh)[0], want[0])
         check(store, fresh)
         # without WS_RAYCAST_GRADIENT there is no gradient to fetch
         cast(store, case, gradient=False)
@@ -244,7 +237,7 @@ def walk_pose(k):
 
 def test_after_real_use():
     import warpsense_amd as W
-    from test_gpu_map_window import _params
+    from window_routes import _params
     from warpsense_amd import synthetic as S
     size = (65, 65, 65)
     g = W.GlobalMap(TAU, 0)
@@ -276,7 +269,7 @@ def test_after_real_use():
     want_w = R.model_of(host, RES, o, d, rng)
     print("global hits", H.hits_of(want[0]), "window hits", H.hits_of(want_w[0]), "of", len(d), "range", rng)
     assert H.hits_of(want[0]) > H.hits_of(want_w[0]) and H.hits_of(want[0]) > 200  # the model says the global cast sees more
-    assert R.same((rec, grad), want) and G.same(rec_w, want_w[0])
+    assert R.same((rec, grad), want) and QM.same(rec_w, want_w[0])
     assert H.hits_of(rec) > H.hits_of(rec_w)
     assert R.same(tm.global_raycast(first, dirs, any_weight=True, gradient=True), R.model(H.Chunks(chunks), RES, o, d, rng, True))
     # the residual of the last scan at the last pose: the window's values wherever both hit inside the window

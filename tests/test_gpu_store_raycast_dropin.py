@@ -1,31 +1,23 @@
 """The C++ drop-in of the ray cast of the device global map (tests/cpp/store_raycast_dropin.cpp): MappingNode::global_raycast along
 the walk of test_gpu_store_mesh.test_after_real_use, from the first pose after the window has moved on, prints the digests of the
 bytes the Python route gives."""
-import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
-import test_gpu_store_mesh as SM
-import test_gpu_surface as G
-from test_gpu_map_window import _params
+from dropin_build import build_dropin
+import query_model as QM
+import store_scenes as SM
+from window_routes import _params
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_cpp_global_raycast_equals_the_python_route(tmp_path):
     import warpsense_amd as W
     from warpsense_amd import synthetic as S
-    cxx = shutil.which("g++")
-    assert cxx is not None, "the C++ drop-in needs g++"
-    exe = tmp_path / "store_raycast_dropin"
-    lib = os.path.join(ROOT, "warpsense_amd")
-    subprocess.check_call([cxx, "-O2", "-std=c++17", "-Wall", "-ffp-contract=off", f"-I{os.path.join(ROOT, 'include')}",
-                           os.path.join(ROOT, "tests", "cpp", "store_raycast_dropin.cpp"), "-o", str(exe), f"-L{lib}", f"-Wl,-rpath,{lib}",
-                           "-Wl,-rpath,/opt/rocm/lib", "-lwarpsense_hip", "-lpthread"])
+    exe = build_dropin("store_raycast_dropin", tmp_path)
     scans = [SM.walk_scan(k) for k in range(len(SM.WALK))]
     np.concatenate(scans).tofile(tmp_path / "scans.bin")
     pose = np.eye(4)
@@ -48,7 +40,7 @@ def test_cpp_global_raycast_equals_the_python_route(tmp_path):
     def line(cast):
         rec, grad = cast
         hits = int(np.count_nonzero(rec["range_mm"] >= 0))
-        return [str(len(rec)), str(hits), f"{G.fnv1a(rec.tobytes()):016x}", "-" if grad is None else f"{G.fnv1a(grad.tobytes()):016x}"]
+        return [str(len(rec)), str(hits), f"{QM.fnv1a(rec.tobytes()):016x}", "-" if grad is None else f"{QM.fnv1a(grad.tobytes()):016x}"]
 
     got = tm.global_raycast(pose, S.os1_128_dirs().reshape(-1, 3)[::16], max_range_mm=rng, gradient=True)
     assert np.count_nonzero(got[0]["range_mm"] >= 0) > 1000 and np.any(got[1] != 0)

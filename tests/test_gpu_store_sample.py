@@ -1,15 +1,15 @@
 """ws_store_sample — the point sample of the global map in device memory (the rules are stated in include/warpsense_hip.h) against
-the numpy model of tests/test_sample_host.py applied to the `Chunks` field of test_store_raycast_host: host copies of the chunks, absent
+the numpy model of tests/sample_model.py applied to the `Chunks` field of store_raycast_scenes: host copies of the chunks, absent
 chunks and voxels outside the box not valid.  Every comparison is on the raw bytes of the records, the gradient and the selection."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
-import test_gpu_store_mesh as SM
-import test_gpu_surface as G
-import test_sample_host as H
-import test_store_raycast_host as SH
+import query_model as QM
+import sample_model as H
+import store_raycast_scenes as SH
+import store_scenes as SM
 
 pytestmark = pytest.mark.gpu
 TAU, RES, MW = SM.TAU, SM.RES, SM.MW
@@ -78,7 +78,7 @@ FAR = [(2 ** 24 - 2, 0, -(2 ** 24 - 1)), (-(2 ** 24 - 1), 5, 7)]  # at res 1 the
 
 
 def test_far_apart_chunks_with_keys_near_2_24():
-    import test_gpu_mesh as M
+    import mesh_model as M
     chunks = {key: M.draw_entries((CS,) * 3, seed=500 + i) for i, key in enumerate(FAR)}
     store = SM.make_store(chunks, segment_chunks=0)
     rng = np.random.default_rng(9)
@@ -104,7 +104,7 @@ def test_same_bytes_as_the_window_sample(seam_store, seam_points):
     import warpsense_amd as W
     lm = W.LocalMap(129, 129, 129, TAU, 0)
     t = W.TSDFCuda(lm.device_map(), TAU, MW, RES)
-    lo, hi = G.window(lm.size, lm.pos)
+    lo, hi = QM.window(lm.size, lm.pos)
     assert tuple(lo) == (-64,) * 3 and tuple(hi) == (64,) * 3 and (seam_store.default_raw >> 16) == 0  # fill_entry has weight 0
     seam_store.load_box(t, lo, hi)
     p32 = seam_points.astype(np.int32)
@@ -146,7 +146,7 @@ def test_refusals_and_results_that_survive_later_changes(seam_points):
         n, ns = C.c_size_t(0), C.c_size_t(0)
         assert L.ws_store_sample_download(store.handle, a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), c.ctypes.data_as(C.c_void_p), 900, len(sel),
                                           C.byref(n), C.byref(ns)) == 0
-        return (n.value, ns.value) == (900, len(sel)) and G.same(a, rec) and G.same(b, grad) and G.same(c, sel)
+        return (n.value, ns.value) == (900, len(sel)) and QM.same(a, rec) and QM.same(b, grad) and QM.same(c, sel)
 
     assert call(lo=lo3) == WS_ERR_INVALID and call(hi=hi3) == WS_ERR_INVALID and call(lo=hi3, hi=lo3) == WS_ERR_INVALID  # one NULL; hi < lo
     assert call(band=0) == WS_ERR_INVALID and call(band=-1) == WS_ERR_INVALID and call(res=0) == WS_ERR_INVALID and call(flags=64) == WS_ERR_INVALID
@@ -158,7 +158,7 @@ def test_refusals_and_results_that_survive_later_changes(seam_points):
     # later saves and drops leave the result as it is
     lm = W.LocalMap(33, 33, 33, TAU, 0)
     t = W.TSDFCuda(lm.device_map(), TAU, MW, RES)
-    store.save_box(t, *G.window(lm.size, lm.pos))
+    store.save_box(t, *QM.window(lm.size, lm.pos))
     store.drop_chunk(sorted(chunks)[0])
     assert last_is_intact()
     # n == 0
@@ -178,7 +178,7 @@ def test_after_a_real_walk_points_in_the_part_the_window_has_left():
     TSDFMapping.global_sample answers for all of them from the chunks, byte for byte the model on the written-back global map, while
     the window no longer knows those it has left."""
     import warpsense_amd as W
-    from test_gpu_map_window import _params
+    from window_routes import _params
     size = (65, 65, 65)
     g = W.GlobalMap(TAU, 0)
     lm = W.LocalMap(*size, TAU, 0, g)
@@ -208,8 +208,8 @@ def test_after_a_real_walk_points_in_the_part_the_window_has_left():
     assert np.all(got_w[0]["cls"][left] == H.UNKNOWN) and not got_w[0]["raw"][left].any()
     host = W.DeviceMap(lm.size.copy(), lm.offset.copy(), np.empty_like(lm.data), lm.pos.copy())
     tm.tsdf().avg_map().to_host(host)
-    import test_gpu_raycast as R
+    import raycast_model as R
     assert H.same(got_w, H.model(R.Ring(host.data_, host.size_, host.pos_, host.offset_), RES, pts, TAU, select=(H.SURFACE,)))
     both = (got_w[0]["cls"] != H.UNKNOWN)
-    assert both.sum() >= 16 and G.same(got_w[0][both], got[0][both])
+    assert both.sum() >= 16 and QM.same(got_w[0][both], got[0][both])
     store.close()

@@ -1,69 +1,19 @@
 """ws_store_surface — the surface cloud of the global map in device memory (the rules are stated in include/warpsense_hip.h) against
-the numpy model that ws_map_surface is held to (test_gpu_surface.model_box), applied to a dense array assembled from host copies of
-the chunks with every voxel of an absent chunk set to raw 0 (test_gpu_store_mesh.assemble).  Every comparison is on the raw bytes of
+the numpy model that ws_map_surface is held to (surface_model.model_box), applied to a dense array assembled from host copies of
+the chunks with every voxel of an absent chunk set to raw 0 (store_scenes.assemble).  Every comparison is on the raw bytes of
 the records and of the marker floats."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
-import test_gpu_store_mesh as SM
-import test_gpu_surface as G
+import query_model as QM
+import store_scenes as SM
+from store_surface_scenes import BAND, CS, CW, MW, RES, TAU, check_far_inputs, check_seam_inputs, far_chunks, model_store, same2, seam_chunks, seam_model
+import surface_model as G
 
 pytestmark = pytest.mark.gpu
-TAU, RES, MW = G.TAU, G.RES, 640
-CS, CW = SM.CS, SM.CW
 WS_ERR_INVALID = -1
-BAND = TAU // 3
-
-
-# ------------------------------------------------------------------------------------------------ the model on chunks
-def model_store(chunks, tau, res, lo=None, hi=None, band=None):
-    if lo is None:
-        if not chunks:
-            return np.empty(0, dtype=G.REC), np.empty((0, 7), dtype=G.F)
-        lo, hi = SM.bounding_box(chunks)
-    lo = np.asarray(lo, dtype=np.int64)
-    return G.model_box(SM.assemble(chunks, lo, hi), lo, tau, res, band)
-
-
-# ------------------------------------------------------------------------------------------------ the seam store
-_SEAM = {}
-
-
-def seam_chunks():
-    """the seven chunks of test_gpu_store_mesh's seam store -- (-1..0)^3 without (0, 0, -1) -- filled with test_gpu_surface.draw_entries:
-    weights <= 0, |value| >= band and -32768 all occur, in every chunk"""
-    if "chunks" not in _SEAM:
-        _SEAM["chunks"] = {k: G.draw_entries(CW, seed=640 + i).astype(np.uint32) for i, k in enumerate(SM.SEAM_KEYS) if k != SM.ABSENT}
-    return _SEAM["chunks"]
-
-
-def seam_model(lo=None, hi=None, band=None):
-    """the model's cloud of the seam store, computed once per case"""
-    key = (None if lo is None else (tuple(lo), tuple(hi)), band)
-    if key not in _SEAM:
-        _SEAM[key] = model_store(seam_chunks(), TAU, RES, lo, hi, band)
-    return _SEAM[key]
-
-
-def check_seam_inputs():
-    """conditions on the INPUTS: the model's cloud is not small, every present chunk has a record on each of its six faces, and both
-    branches of the predicate decide somewhere alone"""
-    for data in seam_chunks().values():
-        G.check_inputs(data)
-    rec, _ = seam_model()
-    assert len(rec) > 1000
-    for key in seam_chunks():
-        mine = np.all([rec[n] // CS == key[k] for k, n in enumerate("xyz")], axis=0)
-        for n in "xyz":
-            local = rec[n][mine] % CS
-            assert np.any(local == 0) and np.any(local == CS - 1), (key, n)
-    raw = np.concatenate(list(seam_chunks().values()))
-    v = (raw & 0xFFFF).astype(np.uint16).view(np.int16).astype(np.int32)
-    w = (raw >> 16).astype(np.uint16).view(np.int16).astype(np.int32)
-    for band in (TAU, BAND):
-        assert np.any((w <= 0) & (np.abs(v) < band)) and np.any((w > 0) & (np.abs(v) >= band)), band
 
 
 @pytest.fixture(scope="module")
@@ -88,10 +38,6 @@ def total(store):
     return n.value
 
 
-def same2(got, want):
-    return G.same(got[0], want[0]) and G.same(got[1], want[1])
-
-
 # ------------------------------------------------------------------------------------------------ 1. the default box
 def test_default_box_matches_the_model(seam_store):
     check_seam_inputs()
@@ -100,13 +46,13 @@ def test_default_box_matches_the_model(seam_store):
         got, want = seam_store.surface(TAU, RES, band=band, marker=True), seam_model(band=band)
         print(band, len(want[0]))
         assert len(want[0]) > 1000 and same2(got, want), band
-        assert G.same(seam_store.surface(TAU, RES, band=band), want[0])
+        assert QM.same(seam_store.surface(TAU, RES, band=band), want[0])
     assert len(seam_model(band=BAND)[0]) < len(seam_model()[0])
     assert same2(seam_store.surface(TAU, RES, band=0, marker=True), seam_model())  # band <= 0 means tau
     assert same2(seam_store.surface(TAU, RES, lo=(-CS,) * 3, hi=(CS - 1,) * 3, marker=True), seam_model())  # the bounding box
     # the marker follows the caller's tau and resolution, the records do not
     got = seam_store.surface(2 * TAU, 3 * RES, band=TAU, marker=True)
-    assert same2(got, model_store(seam_chunks(), 2 * TAU, 3 * RES, band=TAU)) and G.same(got[0], seam_model()[0])
+    assert same2(got, model_store(seam_chunks(), 2 * TAU, 3 * RES, band=TAU)) and QM.same(got[0], seam_model()[0])
 
 
 # ------------------------------------------------------------------------------------------------ 2. boxes
@@ -139,7 +85,7 @@ def test_same_bytes_as_the_window_surface(seam_store):
     import warpsense_amd as W
     lm = W.LocalMap(127, 127, 127, TAU, 0)
     t = W.TSDFCuda(lm.device_map(), TAU, MW, RES)
-    lo, hi = G.window(lm.size, lm.pos)
+    lo, hi = QM.window(lm.size, lm.pos)
     assert tuple(lo) == (-63,) * 3 and tuple(hi) == (63,) * 3 and (seam_store.default_raw >> 16) == 0  # fill_entry has weight 0
     seam_store.load_box(t, lo, hi)
     for a, b in [(lo, hi), CUT, ((-63, -5, -7), (63, 4, 9))]:
@@ -148,22 +94,6 @@ def test_same_bytes_as_the_window_surface(seam_store):
             got_store = seam_store.surface(TAU, RES, lo=a, hi=b, band=band, marker=True)
             assert len(got_store[0]) > 1000 and same2(got_store, got_window) and same2(got_store, seam_model(tuple(a), tuple(b), band)), (a, b, band)
     t.close()
-
-
-# ------------------------------------------------------------------------------------------------ 4. far-apart chunks
-FAR_KEYS = [(-15700, 15650, -20), (0, 0, 0), (15700, -15650, 20)]  # a million voxels apart
-
-
-def far_chunks():
-    return {key: G.draw_entries(CW, seed=500 + i).astype(np.uint32) for i, key in enumerate(FAR_KEYS)}
-
-
-def check_far_inputs():
-    """a condition on the INPUTS: neighbours a million voxels apart along x and y, and no dense pass over their bounding box can run"""
-    lo, hi = SM.bounding_box(far_chunks())
-    assert int((hi - lo)[:2].min()) > 2_000_000 and float(np.prod((hi - lo + 1).astype(np.float64))) > 1e15
-    assert all(-2 ** 31 <= int(c) < 2 ** 31 for c in list(lo) + list(hi))
-    return lo, hi
 
 
 def test_far_apart_chunks_cost_three_chunks():
@@ -198,7 +128,7 @@ def test_far_apart_chunks_cost_three_chunks():
 # ------------------------------------------------------------------------------------------------ 5. directory dynamics
 def test_empty_dropped_put_and_old_results():
     import warpsense_amd as W
-    from test_gpu_map_window import _params
+    from window_routes import _params
     empty = W.DeviceGlobalMap(TAU, 0)
     n = C.c_size_t(9)
     assert raw_surface(empty, None, None, 0, TAU, RES) == (0, 0) and raw_surface(empty, (-5, -5, -5), (5, 5, 5), 0, TAU, RES, flags=1) == (0, 0)
@@ -235,7 +165,7 @@ def test_empty_dropped_put_and_old_results():
         lm = W.LocalMap(*size, TAU, 0, W.GlobalMap(TAU, 0))
         tm = W.TSDFMapping(_params(size), lm, device_global_map=store)
         t = tm.tsdf()
-        lo, hi = G.window(lm.size, lm.pos)
+        lo, hi = QM.window(lm.size, lm.pos)
         t.avg_map().insert_box(lo, hi, G.draw_entries(int(np.prod(size)), seed=5))
         store.save_box(t, lo, hi)
         store.load_box(t, lo, hi)
@@ -264,11 +194,11 @@ def test_repeatable_partial_downloads_and_device_tensors(seam_store):
     n = C.c_size_t(0)
     L, h = seam_store._L, seam_store.handle
     assert L.ws_store_surface_download(h, prec.ctypes.data_as(C.c_void_p), pmk.ctypes.data_as(C.c_void_p), cap, C.byref(n)) == 0
-    assert n.value == len(rec) and G.same(prec[:cap], rec[:cap]) and G.same(pmk[:cap], mk[:cap])
+    assert n.value == len(rec) and QM.same(prec[:cap], rec[:cap]) and QM.same(pmk[:cap], mk[:cap])
     assert not prec[cap:].view(np.uint8).any() and not pmk[cap:].any()  # a prefix, nothing beyond the capacity
     assert L.ws_store_surface_download(h, None, None, 0, C.byref(n)) == 0 and n.value == len(rec)
     only_mk = np.zeros((len(rec), 7), dtype=G.F)
-    assert L.ws_store_surface_download(h, None, only_mk.ctypes.data_as(C.c_void_p), len(rec), C.byref(n)) == 0 and G.same(only_mk, mk)
+    assert L.ws_store_surface_download(h, None, only_mk.ctypes.data_as(C.c_void_p), len(rec), C.byref(n)) == 0 and QM.same(only_mk, mk)
     drec, dmk = seam_store.surface(TAU, RES, marker=True, device=True)
     assert drec.is_cuda and dmk.is_cuda and tuple(drec.shape) == (len(rec), 4) and tuple(dmk.shape) == (len(rec), 7)
     assert drec.data_ptr() == L.ws_store_surface_records_dev(h, C.byref(n)) and n.value == len(rec)
@@ -312,7 +242,7 @@ def test_refusals_launch_nothing_and_keep_the_last_result(seam_store):
 # ------------------------------------------------------------------------------------------------ 8. after real use
 def test_after_real_use():
     import warpsense_amd as W
-    from test_gpu_map_window import _params
+    from window_routes import _params
     size = (65, 65, 65)
     g = W.GlobalMap(TAU, 0)
     lm = W.LocalMap(*size, TAU, 0, g)
@@ -336,5 +266,5 @@ def test_after_real_use():
     left = int(np.count_nonzero(rec["x"] < lo[0]))  # what the window has left is in the cloud
     print(len(store.keys()), len(want[0]), left)
     assert len(want[0]) > 1000 and same2((rec, mk), want) and left > 100
-    assert G.same(tm.global_surface_cloud(band=TAU // 2), model_store(chunks, TAU, RES, band=TAU // 2)[0])
+    assert QM.same(tm.global_surface_cloud(band=TAU // 2), model_store(chunks, TAU, RES, band=TAU // 2)[0])
     store.close()

@@ -1,30 +1,22 @@
 """The C++ drop-in of the surface cloud of the device global map (tests/cpp/store_surface_dropin.cpp): MappingNode::global_surface and
 warpsense::global_map_cloud along the walk of test_gpu_store_mesh.test_after_real_use print the count and the digests of the bytes the
 Python route gives."""
-import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
-import test_gpu_store_mesh as SM
-import test_gpu_surface as G
-from test_gpu_map_window import _params
+from dropin_build import build_dropin
+import query_model as QM
+import store_scenes as SM
+from window_routes import _params
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_cpp_global_surface_equals_the_python_route(tmp_path):
     import warpsense_amd as W
-    cxx = shutil.which("g++")
-    assert cxx is not None, "the C++ drop-in needs g++"
-    exe = tmp_path / "store_surface_dropin"
-    lib = os.path.join(ROOT, "warpsense_amd")
-    subprocess.check_call([cxx, "-O2", "-std=c++17", "-Wall", "-ffp-contract=off", f"-I{os.path.join(ROOT, 'include')}",
-                           os.path.join(ROOT, "tests", "cpp", "store_surface_dropin.cpp"), "-o", str(exe), f"-L{lib}", f"-Wl,-rpath,{lib}",
-                           "-Wl,-rpath,/opt/rocm/lib", "-lwarpsense_hip", "-lpthread"])
+    exe = build_dropin("store_surface_dropin", tmp_path)
     scans = [SM.walk_scan(k) for k in range(len(SM.WALK))]
     np.concatenate(scans).tofile(tmp_path / "scans.bin")
     edge = 65
@@ -40,8 +32,8 @@ def test_cpp_global_surface_equals_the_python_route(tmp_path):
         tm.update_tsdf(scans[k], pos_rm=pos, up_rm=(0, 0, 32768))
     rec, mk = tm.global_surface_cloud(marker=True)
     assert len(rec) > 1000
-    assert lines["global"] == [str(len(rec)), f"{G.fnv1a(rec.tobytes()):016x}", f"{G.fnv1a(mk.tobytes()):016x}"]
+    assert lines["global"] == [str(len(rec)), f"{QM.fnv1a(rec.tobytes()):016x}", f"{QM.fnv1a(mk.tobytes()):016x}"]
     assert lines["chunks"] == [str(store.count())] and store.count() >= 10
     box = store.surface(SM.TAU, SM.RES, lo=(-20, -40, -30), hi=(70, 10, 30), band=SM.TAU // 2)
-    assert 100 < len(box) < len(rec) and lines["box"] == [str(len(box)), f"{G.fnv1a(box.tobytes()):016x}", "0" * 16]
+    assert 100 < len(box) < len(rec) and lines["box"] == [str(len(box)), f"{QM.fnv1a(box.tobytes()):016x}", "0" * 16]
     store.close()

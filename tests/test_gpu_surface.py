@@ -4,97 +4,18 @@ np.array_equal on the raw bytes of the records and of the marker floats.
 
 The model is a line-for-line port of map.h:19-75 (the reference lines are cited in it); it is not part of the oracle."""
 import os
-import shutil
 import subprocess
 import time
 
 import numpy as np
 import pytest
 
+from dropin_build import build_dropin
+from query_model import download, fnv1a, same, window, wrapper
+from surface_model import F, REC, RES, SIZES, TAU, check_inputs, draw_entries, model, model_box, skeleton_model
 from warpsense_amd import synthetic as S
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REC = np.dtype([("x", "<i4"), ("y", "<i4"), ("z", "<i4"), ("raw", "<u4")])
-F = np.float32
-
-
-# ------------------------------------------------------------------------------------------------ the numpy model
-def model_box(box, lo, tau, res, band=None):
-    """publish_local_map on a dense box of raw entries, box[ix, iy, iz] = values.value(lo + (ix, iy, iz)) (map.h:44).
-    Returns (records, marker (n, 7) float32)."""
-    band = tau if band is None or band <= 0 else band
-    value = (box & 0xFFFF).astype(np.uint16).view(np.int16).astype(np.int32)  # TSDFEntry::value(), promoted to int for abs()
-    weight = (box >> 16).astype(np.uint16).view(np.int16).astype(np.int32)
-    keep = (weight > 0) & (np.abs(value) < band)       # map.h:45: if (val.weight() <= 0 || abs(val.value()) >= tau) continue;
-    ix, iy, iz = np.nonzero(keep)                      # C order == the collapse(3) schedule(static) concatenation, map.h:35-40, 78-104
-    rec = np.empty(len(ix), dtype=REC)
-    rec["x"], rec["y"], rec["z"] = lo[0] + ix, lo[1] + iy, lo[2] + iz
-    rec["raw"] = box[keep]
-    val = value[keep]
-    mk = np.empty((len(ix), 7), dtype=F)
-    for k, name in enumerate("xyz"):
-        mk[:, k] = (rec[name].astype(F) * F(res)) / F(1000.0)  # map.h:51-53: (float)x * (float)map_resolution / 1000.f
-    pos = val >= 0
-    with np.errstate(invalid="ignore"):
-        mk[:, 3] = np.where(pos, val.astype(F) / F(tau), F(0))      # map.h:55-58: color.r = val.value() / (float)tau; color.g = 0
-        mk[:, 4] = np.where(pos, F(0), (-val).astype(F) / F(tau))   # map.h:60-63: color.r = 0; color.g = -val.value() / (float)tau
-    mk[:, 5] = 0                                                    # map.h:33: color.b = 0
-    mk[:, 6] = 1                                                    # map.h:32: color.a = 1
-    return rec, mk
-
-
-def ring_box(data, size, pos, offset, lo, hi):
-    """values.value(x, y, z) for the inclusive box: HDF5LocalMap::get_index, z fastest"""
-    size, pos, offset = (np.asarray(v, dtype=np.int64) for v in (size, pos, offset))
-    ax = [(np.arange(lo[k], hi[k] + 1, dtype=np.int64) - pos[k] + offset[k] + size[k]) % size[k] for k in range(3)]
-    return data.reshape(tuple(int(s) for s in size))[np.ix_(ax[0], ax[1], ax[2])]
-
-
-def window(size, pos):
-    """map.h:19-26: left = pos - size / 2, right = pos + size / 2 (odd sizes); for an even size each ring cell once"""
-    size, pos = np.asarray(size, dtype=np.int64), np.asarray(pos, dtype=np.int64)
-    lo = pos - size // 2
-    return lo, lo + size - 1
-
-
-def model(host, tau, res, lo=None, hi=None, band=None):
-    if lo is None:
-        lo, hi = window(host.size_, host.pos_)
-    lo, hi = np.asarray(lo, dtype=np.int64), np.asarray(hi, dtype=np.int64)
-    return model_box(ring_box(host.data_, host.size_, host.pos_, host.offset_, lo, hi), lo, tau, res, band)
-
-
-def same(got, want):
-    return got.dtype == want.dtype and got.shape == want.shape and np.array_equal(got.view(np.uint8), want.view(np.uint8))
-
-
-# ------------------------------------------------------------------------------------------------ arbitrary-entry maps
-TAU, RES = 1000, 50
-SIZES = [(21, 17, 13), (15, 15, 15), (16, 18, 20), (15, 17, 24), (17, 15, 25), (19, 15, 26), (15, 19, 27)]  # one even; size[2] % 4 = 0, 1, 2, 3
-PLANTED = [(w, v) for w in (-1, 0, 1) for v in (TAU - 1, -(TAU - 1), TAU, -TAU, -32768, 0)]
-
-
-def draw_entries(n, seed, tau=TAU):
-    """values uniform in [-2 tau, 2 tau] (P(|v| < tau) = 1999/4001), weights uniform in [-640, 640] (P(w > 0) = 640/1281): a quarter
-    qualifies and both branches of the predicate are well populated; then every edge of the predicate planted at fixed places"""
-    import warpsense_amd as W
-    rng = np.random.default_rng(seed)
-    value, weight = rng.integers(-2 * tau, 2 * tau + 1, n), rng.integers(-640, 641, n)
-    where = rng.permutation(n)[:len(PLANTED)]
-    for i, (w, v) in zip(where, PLANTED):
-        value[i], weight[i] = v, w
-    return W.pack_entry(value, weight)
-
-
-def check_inputs(raw, tau=TAU):
-    """a condition on the INPUTS: every planted category is there and the qualifying share is 0.25 +- 3 sigma inside [0.10, 0.40]"""
-    v = (raw & 0xFFFF).astype(np.uint16).view(np.int16).astype(np.int32)
-    w = (raw >> 16).astype(np.uint16).view(np.int16).astype(np.int32)
-    for pw, pv in PLANTED:
-        assert np.any((w == pw) & (v == pv)), (pw, pv)
-    share = np.count_nonzero((w > 0) & (np.abs(v) < tau)) / raw.size
-    assert 0.10 <= share <= 0.40, share
 
 
 def make_maps(size, seed):
@@ -110,16 +31,6 @@ def make_maps(size, seed):
     check_inputs(other.data)
     tm.tsdf().new_map().to_device(other.device_map())
     return W, tm, lm
-
-
-def download(W, tm, lm, which=0):
-    host = W.DeviceMap(lm.size.copy(), lm.offset.copy(), np.empty_like(lm.data), lm.pos.copy())
-    (tm.tsdf().avg_map() if which == 0 else tm.tsdf().new_map()).to_host(host)
-    return host
-
-
-def wrapper(t, which):
-    return t.avg_map() if which == 0 else t.new_map()
 
 
 @pytest.mark.parametrize("size", SIZES)
@@ -334,46 +245,9 @@ def test_byte_offsets_beyond_4_gib():
     assert whole == counted > 1_000_000
 
 
-# ------------------------------------------------------------------------------------------------ C++ twin
-def skeleton_model(size, pos, res):
-    """numpy port of publish_local_map_skeleton's arithmetic (map.h:175-227)"""
-    scale = F(res) / F(1000.0)                                                        # (float)map_resolution / 1000.f
-    br = [int(np.trunc(F(int(pos[k]) - int(size[k]) // 2) * scale)) for k in range(3)]  # map.h:182-183: int *= float truncates
-    tl = [int(np.trunc(F(int(pos[k]) + int(size[k]) // 2) * scale)) for k in range(3)]  # map.h:184-185
-    d = [tl[k] - br[k] for k in range(3)]                                              # map.h:188
-    pts = []
-
-    def rect(zoff):  # draw_rectangle, map.h:150-173
-        bbr = [br[0], br[1], br[2] + zoff]
-        btr = [bbr[0] + d[0], bbr[1], bbr[2]]
-        btl = [btr[0], btr[1] + d[1], btr[2]]
-        bbl = [btl[0] - d[0], btl[1], btl[2]]
-        pts.extend([bbr, btr, btr, btl, btl, bbl, bbl, bbr])
-    rect(0)
-    rect(d[2])
-    pts.extend([tl, [tl[0], tl[1], tl[2] - d[2]]])                                    # map.h:195-199
-    pts.extend([br, [br[0], br[1], br[2] + d[2]]])                                    # map.h:201-205
-    pts.extend([[tl[0] - d[0], tl[1], tl[2]], [tl[0] - d[0], tl[1], tl[2] - d[2]]])   # map.h:207-216
-    pts.extend([[br[0] + d[0], br[1], br[2]], [br[0] + d[0], br[1], br[2] + d[2]]])   # map.h:218-227
-    return np.array(pts, dtype=np.float64)
-
-
-def fnv1a(b: bytes) -> int:
-    h = 1469598103934665603
-    for chunk in np.frombuffer(b, dtype=np.uint8).tolist():
-        h = ((h ^ chunk) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
-    return h
-
-
 def test_cpp_twin_matches_the_python_route(tmp_path):
     import warpsense_amd as W
-    cxx = shutil.which("g++")
-    assert cxx is not None, "the C++ drop-in needs g++"
-    exe = tmp_path / "surface_dropin"
-    lib = os.path.join(ROOT, "warpsense_amd")
-    subprocess.check_call([cxx, "-O2", "-std=c++17", "-Wall", "-ffp-contract=off", f"-I{os.path.join(ROOT, 'include')}",
-                           os.path.join(ROOT, "tests", "cpp", "surface_dropin.cpp"), "-o", str(exe), f"-L{lib}", f"-Wl,-rpath,{lib}",
-                           "-Wl,-rpath,/opt/rocm/lib", "-lwarpsense_hip", "-lpthread"])
+    exe = build_dropin("surface_dropin", tmp_path)
     tau, res, mw, edge = 1000, 50, 640, 65
     pts = S.os1_128_scan(rings=32, azimuths=256, half_extents_mm=(1400.0, 1300.0, 900.0), seed=2)
     pts.tofile(tmp_path / "scan.bin")

@@ -3,21 +3,12 @@ that to the oracle) bit for bit including the order, for host and for device inp
 import numpy as np
 import pytest
 
-from test_preprocess import POSES, make_cloud
-from test_sweep_host import rigid
+from scan_clouds import POSES, make_cloud
+from scan_clouds import rigid
+from scan_clouds import both_routes
 from warpsense_amd import synthetic as S
 
 pytestmark = pytest.mark.gpu
-
-
-def both_routes(pre, cloud, poses, res, **rule):
-    """the call with the cloud on the host and on the device; the two must agree, the first is returned"""
-    import torch
-    host = pre.preprocess_sweep(cloud, poses, res, **rule)
-    n_host, got = len(host), host.to_host()
-    dev = pre.preprocess_sweep(torch.from_numpy(np.ascontiguousarray(cloud)).cuda(), poses, res, **rule)
-    assert len(dev) == n_host == len(got) and np.array_equal(dev.to_host(), got)
-    return got
 
 
 @pytest.fixture(scope="module")
@@ -179,7 +170,7 @@ def test_sweep_output_feeds_update_and_registration():
 
 def test_app_with_identity_motion_is_todays_app_and_constant_velocity_follows_the_sensor():
     import warpsense_amd as W
-    from test_gpu_replay import sensor_clouds
+    from scan_clouds import sensor_clouds
     tau, res, mw, size, shift_m = 1000, 50, 640, (128, 128, 64), 0.6
     params = W.Params(W.MapParams(resolution=res, max_distance=tau / 1000.0, max_weight=mw // 64, size=tuple(s * res / 1000.0 for s in size), shift=shift_m),
                       W.RegistrationParams(200, 0.1, 0.03))

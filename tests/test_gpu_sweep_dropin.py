@@ -1,28 +1,20 @@
 """The C++ drop-in of the motion-compensated pre-processing (tests/cpp/sweep_dropin.cpp): warpsense::sweep_poses and
 ScanPreprocessor::preprocess_sweep through compat.hpp give the bytes of the Python calls."""
-import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
-from test_sweep_host import rigid
+from dropin_build import build_dropin
+from scan_clouds import rigid
 from warpsense_amd import synthetic as S
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_cpp_sweep_equals_the_python_route(tmp_path):
     import warpsense_amd as W
-    cxx = shutil.which("g++")
-    assert cxx is not None, "the C++ drop-in needs g++"
-    exe = tmp_path / "sweep_dropin"
-    lib = os.path.join(ROOT, "warpsense_amd")
-    subprocess.check_call([cxx, "-O2", "-std=c++17", "-Wall", "-ffp-contract=off", f"-I{os.path.join(ROOT, 'include')}",
-                           os.path.join(ROOT, "tests", "cpp", "sweep_dropin.cpp"), "-o", str(exe), f"-L{lib}", f"-Wl,-rpath,{lib}",
-                           "-Wl,-rpath,/opt/rocm/lib", "-lwarpsense_hip", "-lpthread"])
+    exe = build_dropin("sweep_dropin", tmp_path)
     res, k, rings, azimuths = 50, 24, 16, 96
     begin, end = rigid(-150.0, 60.0, 0.0, -4.0), rigid(180.0, 140.0, 10.0, 6.0)
     motion = (np.linalg.inv(begin) @ end).astype(np.float32)

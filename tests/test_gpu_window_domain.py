@@ -12,10 +12,10 @@ import os
 import numpy as np
 import pytest
 
-import window_model as M
-from test_gpu_map_window import MW, RES, TAU, MappingRoute, RawRoute, _default, _i3, _p, _params, check_device, same_state, state
-from test_gpu_store import CW, StoreRoute, chunk_box, same_store, store_state
 from window_model import I32_MAX, I32_MIN, WALKS
+import window_model as M
+from window_routes import MW, RES, TAU, MappingRoute, RawRoute, _default, _i3, _p, _params, check_device, same_state, state
+from window_routes import CW, StoreRoute, chunk_box, same_store, store_state
 
 pytestmark = pytest.mark.gpu
 

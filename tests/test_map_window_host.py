@@ -4,35 +4,10 @@ tests/test_gpu_map_window.py runs the same walks (same shapes, same seeds) throu
 import numpy as np
 import pytest
 
-import window_model as M
+from window_host_routes import HostRoute, TAU
 from window_model import WALKS
-
-TAU = 1000
+import window_model as M
 WS_ERR_INVALID = -1
-
-
-class HostRoute:
-    """LocalMap.shift on a host map with an in-memory GlobalMap"""
-
-    def __init__(self, size):
-        import warpsense_amd as W
-        self.W = W
-        self.lm = W.LocalMap(*size, TAU, 0)
-        assert tuple(self.lm.size) == tuple(size)
-
-    def insert(self, lo, hi, words):
-        lm = self.lm
-        ax = M.ring_axes(lm.size, lm.pos, lm.offset, lo, hi)
-        lm.data.reshape(tuple(int(s) for s in lm.size))[np.ix_(*ax)] = words.reshape(tuple(int(v) for v in hi - lo + 1))
-
-    def shift(self, world, new_pos):
-        self.lm.shift(new_pos)
-
-    def check(self, w):
-        lm = self.lm
-        assert np.array_equal(lm.pos, w.pos) and np.array_equal(lm.offset, w.offset())
-        assert np.array_equal(lm.data, w.ring())
-        w.check_chunks(lm.map_.chunks)
 
 
 @pytest.mark.parametrize("size,seed", WALKS)

@@ -1,21 +1,16 @@
 """The mesh without a GPU: the boundary (symbols, header, ctypes signatures), the numpy model of the surface-nets rules
-(tests/test_gpu_mesh.py) against a hand-computed literal and on two sphere maps (closed, Euler characteristic 2, volume, distance
+(tests/mesh_model.py) against a hand-computed literal and on two sphere maps (closed, Euler characteristic 2, volume, distance
 to the sphere), holes in the map, and the PLY writer."""
 import ctypes as C
-import os
 import re
 import struct
 
 import numpy as np
 
-import test_gpu_mesh as M
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from mesh_model import sphere_mesh_numbers
+import mesh_model as M
+from query_model import CTYPE, _declared, _header
 NEW = ["ws_map_mesh", "ws_map_mesh_vertices_dev", "ws_map_mesh_faces_dev", "ws_map_mesh_download", "ws_debug_mesh_timing"]
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "warpsense_hip.h")).read()
 
 
 def test_library_exports_and_header_declares_the_mesh_entry_points():
@@ -32,24 +27,6 @@ def test_library_exports_and_header_declares_the_mesh_entry_points():
     for phrase in ("(2 |va| res + m) / (2 m)", "ascending cell (x, y, z), z fastest", "ascending owner voxel (x, y, z), z fastest, then axis 0, 1, 2",
                    "may be referenced by no face"):
         assert phrase in h, phrase
-
-
-CTYPE = {"ws_map *": C.c_void_p, "const ws_map *": C.c_void_p, "int": C.c_int, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "size_t": C.c_size_t,
-         "const int32_t [3]": C.c_void_p, "float [3]": C.c_void_p, "void *": C.c_void_p, "uint32_t *": C.c_void_p, "size_t *": C.POINTER(C.c_size_t)}
-
-
-def _declared(name):
-    """(return type, [parameter types]) of `name` as the header declares it, parameter names stripped"""
-    m = re.search(r"\n([A-Za-z_0-9 ]+?[ \*])" + name + r"\s*\(([^)]*)\)\s*;", _header())
-    assert m, name
-    params = []
-    for p in m.group(2).split(","):
-        p = re.sub(r"/\*.*?\*/", "", p).strip()
-        arr = re.search(r"\[(\d+)\]$", p)
-        p = re.sub(r"\[\d+\]$", "", p).strip()
-        t = re.sub(r"\b[a-z_0-9]+$", "", p).strip()  # drop the parameter's name
-        params.append(t + (f" [{arr.group(1)}]" if arr else ""))
-    return m.group(1).strip(), params
 
 
 def test_ctypes_signatures_agree_with_the_header():
@@ -85,21 +62,6 @@ def test_model_reproduces_the_hand_computed_case():
     assert M.model_counts(box) == (4, 2) and M.model_counts(box[:, :, :1]) == (0, 0)
     # |-32768| is 32768; m = 1
     assert (2 * 32768 * 50 + 65535) // (2 * 65535) == 25 and (2 * 0 * 50 + 1) // 2 == 0 and (2 * 1 * 50 + 1) // 2 == 50
-
-
-def sphere_mesh_numbers(edge, centre, radius, res=M.RES, tau=M.TAU):
-    """the model's mesh of a sphere map: closed, Euler characteristic 2; returns (volume / the sphere's, largest distance of a vertex
-    to the sphere in mm)"""
-    box = M.sphere_box(edge, centre, radius, res=res, tau=tau).reshape((edge,) * 3)
-    vert, face = M.model_box(box, M.SPHERE_LO, res)
-    rep = M.mesh_report(vert, face)
-    assert rep["closed"] and rep["directed_once"] and rep["chi"] == 2 and rep["unreferenced"] == 0, rep
-    sphere = 4.0 / 3.0 * np.pi * (radius * res) ** 3
-    p = np.stack([vert["x_mm"], vert["y_mm"], vert["z_mm"]], axis=1).astype(np.float64)
-    c = (np.asarray(M.SPHERE_LO) + np.asarray(centre)) * res
-    dist = np.abs(np.sqrt(np.sum((p - c) ** 2, axis=1)) - radius * res)
-    print(edge, res, len(vert), len(face), rep["volume"] / sphere, dist.max())
-    return rep["volume"] / sphere, float(dist.max())
 
 
 def test_sphere_maps_give_closed_meshes_of_the_right_size():
@@ -147,7 +109,7 @@ def test_ply_writer_round_trips(tmp_path):
 
 
 def test_committed_seeds_give_meshes_that_are_not_small():
-    """the draws of tests/test_gpu_mesh.py, checked where no GPU is needed"""
+    """the draws of tests/mesh_model.py, checked where no GPU is needed"""
     for size in M.SIZES:
         for which in (0, 1):
             M.check_inputs(M.draw_entries(size, M.seeds_for(size, which)), size)

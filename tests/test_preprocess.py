@@ -6,54 +6,8 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from scan_clouds import POSES, make_cloud, numpy_preprocess
 from warpsense_amd import synthetic as S
-
-
-def _wrap32(v: int) -> int:
-    return (v + 2 ** 31) % 2 ** 32 - 2 ** 31
-
-
-def numpy_preprocess(xyz, pose, res):
-    """independent restatement: float32 arithmetic step by step, wrapping int32 products, a python set"""
-    f = np.float32
-    a = np.asarray(xyz, dtype=np.float32)[:, :3]
-    M = (np.asarray(pose, dtype=np.float32) * f(32768)).astype(np.int32)  # to_int_mat
-    out, seen = [], set()
-    for x, y, z in a:
-        if not (np.isfinite(x) and np.isfinite(y) and np.isfinite(z)):
-            continue
-        if float(x) < 0.3 and float(y) < 0.3 and float(z) < 0.3:
-            continue
-        c = [int(np.int32(f(f(np.floor(f(f(v * f(1000.0)) / f(res)))) * f(res)) + f(res // 2))) for v in (x, y, z)]
-        q = []
-        for r in range(3):
-            acc = 0
-            for k in range(3):
-                acc = _wrap32(acc + _wrap32(int(M[r, k]) * c[k]))
-            acc = _wrap32(acc + int(M[r, 3]))
-            q.append(int(abs(acc) // 32768) * (1 if acc >= 0 else -1))  # C division truncates toward zero
-        q = tuple(q)
-        if q not in seen:
-            seen.add(q)
-            out.append(q)
-    return np.array(out, dtype=np.int32).reshape(-1, 3)
-
-
-def make_cloud(n, seed, stride=3):
-    rng = np.random.default_rng(seed)
-    a = np.zeros((n, stride), dtype=np.float32)
-    a[:, :3] = rng.uniform(-12.0, 12.0, size=(n, 3)).astype(np.float32)
-    k = n // 5
-    a[:k, :3] = np.round(a[:k, :3] * 20) / 20          # many points on voxel borders (multiples of 50 mm)
-    a[k:2 * k, :3] = a[:k, :3] + np.float32(0.004)      # near-duplicates: same voxel as another point
-    a[2 * k:2 * k + 10, :3] = [0.1, 0.2, -0.4]          # dropped: all three below 0.3
-    a[2 * k + 10:2 * k + 20, :3] = [0.1, 0.5, -3.0]     # kept: y >= 0.3
-    if stride > 3:
-        a[:, 3:] = rng.uniform(0, 255, size=(n, stride - 3))
-    return a
-
-
-POSES = [np.eye(4, dtype=np.float32), S.perturbation(1234.5, -987.25, 40.0, 17.0), S.perturbation(-20000.0, 15000.0, -800.0, -133.0)]
 
 
 @pytest.mark.parametrize("res", [50, 64, 20])

@@ -5,14 +5,13 @@ clears the thresholds the GPU tests assert."""
 import numpy as np
 import pytest
 
-import test_gpu_distance as D
-import test_gpu_mesh as M
-import test_gpu_query_domain as Q
-import test_gpu_raycast as R
-import test_gpu_store_mesh as SM
-import test_gpu_surface as G
-import test_mesh_host as MH
-import test_store_raycast_host as H
+import distance_model as D
+import mesh_model as M
+import query_domain_scenes as Q
+import query_model as QM
+import raycast_model as R
+import store_scenes as SM
+import surface_model as G
 
 
 # ------------------------------------------------------------------------------------------------ hand-worked single cells
@@ -107,7 +106,7 @@ def test_sphere_at_other_resolutions(res):
         core, dist, err = R.check_sphere(rec, o, d, c_mm, radius * res, bound=1.25 * ray_err)  # every core ray hits, none that misses does
         assert dist <= 1.25 * ray_dist
         seen.append(core)
-        ratio, far = MH.sphere_mesh_numbers(edge, centre, radius, res=res, tau=tau)
+        ratio, far = M.sphere_mesh_numbers(edge, centre, radius, res=res, tau=tau)
         assert abs(ratio - 1.0) < 1.25 * vol and far < 1.25 * mesh_dist
     assert seen == cores
 
@@ -136,7 +135,7 @@ def test_every_model_moves_with_the_window(row):
         (va, fa), (vb, fb) = M.model(views[0], res, any_weight=any_weight), M.model(views[2], res, any_weight=any_weight)
         assert len(fa) > 100 and M.same((vb, fb), (Q.moved_vert(va, s * res), fa))
     (ra, ma), (rb, mb) = G.model(views[0], Q.TAU, res), G.model(views[2], Q.TAU, res)
-    assert len(ra) > 100 and G.same(rb, Q.moved_surface(ra, s)) and np.array_equal(ma[:, 3:], mb[:, 3:])
+    assert len(ra) > 100 and QM.same(rb, Q.moved_surface(ra, s)) and np.array_equal(ma[:, 3:], mb[:, 3:])
     for kw in ({}, dict(unknown_occupied=True), dict(columns=True)):
         assert D.same(D.model(views[3], 5, **kw)[0], D.model(views[1], 5, **kw)[0])
 
@@ -152,15 +151,15 @@ def test_window_fixtures_clear_their_thresholds_in_the_model():
             n_hit, n_grad = Q.counts(R.model(ring, res, o, d, rng, any_weight))
             print(res, pos, any_weight, "hits", n_hit, "gradients", n_grad)
             assert n_hit > 500 and n_grad > 300
-    lo, hi = G.window(Q.SIZE, Q.NEAR)
+    lo, hi = QM.window(Q.SIZE, Q.NEAR)
     for a, b in ((lo, hi), Q.inner_box(Q.NEAR)):
-        box = G.ring_box(Q.entries()[0], Q.SIZE, Q.NEAR, Q.OFF, a, b)
+        box = QM.ring_box(Q.entries()[0], Q.SIZE, Q.NEAR, Q.OFF, a, b)
         for any_weight in (False, True):
             nv, nf = M.model_counts(box, any_weight)
             print("mesh", tuple(b - a + 1), any_weight, nv, nf)
             assert nv > 100 and nf > 100
         assert len(G.model_box(box, a, Q.TAU, 50)[0]) > 100
-        dbox = G.ring_box(Q.entries()[1], Q.SIZE, Q.NEAR, Q.OFF, a, b)
+        dbox = QM.ring_box(Q.entries()[1], Q.SIZE, Q.NEAR, Q.OFF, a, b)
         for kw in ({}, dict(unknown_occupied=True), dict(columns=True)):
             rec, n_sites = D.model_box(dbox, 5, **kw)
             d2 = rec & np.uint32(0xFFFFFF)

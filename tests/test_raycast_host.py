@@ -7,9 +7,9 @@ import struct
 
 import numpy as np
 
-import test_gpu_mesh as M
-import test_gpu_raycast as R
-import test_mesh_host as H
+import mesh_model as M
+import query_model as QM
+import raycast_model as R
 
 NEW = ["ws_map_raycast", "ws_map_raycast_dev", "ws_map_raycast_records_dev", "ws_map_raycast_gradient_dev", "ws_map_raycast_download",
        "ws_debug_raycast_timing"]
@@ -20,7 +20,7 @@ def test_library_exports_and_header_declares_the_raycast_entry_points():
     from warpsense_amd import _lib
     import warpsense_amd as W
     L = _lib.load()
-    h = H._header()
+    h = QM._header()
     for name in NEW:
         assert hasattr(L, name), name
         assert name in _lib.EXPORTS
@@ -35,7 +35,7 @@ def test_library_exports_and_header_declares_the_raycast_entry_points():
         assert phrase in h, phrase
 
 
-CTYPE = dict(H.CTYPE)
+CTYPE = dict(QM.CTYPE)
 CTYPE.update({"const int32_t *": C.c_void_p, "int32_t *": C.c_void_p})
 
 
@@ -43,7 +43,7 @@ def test_ctypes_signatures_agree_with_the_header():
     from warpsense_amd import _lib
     L = _lib.load()
     for name in NEW:
-        ret, params = H._declared(name)
+        ret, params = QM._declared(name)
         fn = getattr(L, name)
         want = [CTYPE[p] for p in params]
         assert list(fn.argtypes) == want, (name, params, fn.argtypes)

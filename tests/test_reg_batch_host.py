@@ -2,15 +2,14 @@
 exact-fraction model, the candidate lattice, and -- on the CPU oracle alone -- the input condition of the GPU tests in
 tests/test_gpu_reg_batch.py: the committed pose list ends its loops in every possible way, the kidnap case needs the lattice."""
 import ctypes as C
-import re
 from fractions import Fraction
+import re
 
 import numpy as np
 
 import oracle_lib as O
-import test_gpu_reg_batch as B
-import test_gpu_registration as R
-import test_mesh_host as H
+import query_model as QM
+import reg_scenes as B
 from warpsense_amd import synthetic as S
 
 NEW = ["ws_register_cloud_batch", "ws_reg_batch_best"]
@@ -21,7 +20,7 @@ def test_library_exports_and_header_declares_the_batch_entry_points():
     from warpsense_amd import _lib
     import warpsense_amd as W
     L = _lib.load()
-    h = H._header()
+    h = QM._header()
     for name in NEW:
         assert hasattr(L, name), name
         assert name in _lib.EXPORTS
@@ -42,7 +41,7 @@ CTYPE = {"ws_reg *": C.c_void_p, "const ws_map *": C.c_void_p, "const float *": 
 
 def _declared(name):
     """(return type, [parameter types]) as the header declares `name`, parameter names stripped"""
-    m = re.search(r"\n([A-Za-z_0-9 ]+?[ \*])" + name + r"\s*\(([^)]*)\)\s*;", H._header())
+    m = re.search(r"\n([A-Za-z_0-9 ]+?[ \*])" + name + r"\s*\(([^)]*)\)\s*;", QM._header())
     assert m, name
     params = [re.sub(r"\b[A-Za-z_0-9]+$", "", re.sub(r"/\*.*?\*/", "", p).strip()).strip() for p in m.group(2).split(",")]
     return m.group(1).strip(), params
@@ -191,11 +190,11 @@ def test_kidnap_case_needs_the_lattice_and_the_lattice_finds_the_pose():
     ec = np.array([O.reg_iterate(oa, T, q, res, 0)[2:] for T in finals], dtype=np.int32)
     best = W.batch_best(ec[:, 0], ec[:, 1], int(np.ceil(B.KIDNAP_MIN_FRACTION * len(q))))
     assert best == B.KIDNAP_BEST
-    dt, ang = R.pose_error(finals[best], truth)
+    dt, ang = B.pose_error(finals[best], truth)
     assert dt < 1e-2 and ang < 1e-2, (dt, ang)
     # the wrong guess alone (candidate 0 is the guess itself) ends farther from the truth than the best candidate
-    alone = R.pose_error(finals[0], truth)
+    alone = B.pose_error(finals[0], truth)
     assert alone[0] > dt and alone[1] > ang and alone[0] > 0.5, alone
     # ... also when it is given the tracker's full iteration budget
     T200 = O.register_cloud(oa, q, guess, prm.max_iterations, prm.it_weight_gradient, prm.epsilon, res)[0]
-    assert R.pose_error(T200, truth)[0] > dt
+    assert B.pose_error(T200, truth)[0] > dt

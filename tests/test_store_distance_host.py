@@ -6,11 +6,10 @@ import re
 
 import numpy as np
 
-import test_distance_host as DH
-import test_gpu_distance as D
-import test_gpu_store_distance as SD
-import test_gpu_store_mesh as SM
-import test_mesh_host as MH
+import distance_model as DH
+import query_model as QM
+import store_distance_scenes as SD
+import store_scenes as SM
 
 NEW = ["ws_store_distance", "ws_store_distance_dev", "ws_store_distance_download", "ws_debug_store_distance_timing"]
 CTYPE = dict(DH.CTYPE, **{"ws_store *": C.c_void_p, "const ws_store *": C.c_void_p})
@@ -19,13 +18,13 @@ CTYPE = dict(DH.CTYPE, **{"ws_store *": C.c_void_p, "const ws_store *": C.c_void
 def test_library_exports_and_header_declares_the_store_distance_entry_points():
     from warpsense_amd import _lib
     L = _lib.load()
-    h = MH._header()
+    h = QM._header()
     for name in NEW:
         assert hasattr(L, name), name
         assert name in _lib.EXPORTS
         assert re.search(r"\b" + name + r"\s*\(", h), name
     for name in NEW:
-        ret, params = MH._declared(name)
+        ret, params = QM._declared(name)
         fn = getattr(L, name)
         want = [CTYPE[p] for p in params]
         assert list(fn.argtypes) == want, (name, params, fn.argtypes)
@@ -36,7 +35,7 @@ def test_library_exports_and_header_declares_the_store_distance_entry_points():
 
 
 def test_header_states_the_rules():
-    h = MH._header()
+    h = QM._header()
     block = h[h.index("/* The distance field of the store"):h.index("int ws_debug_store_distance_timing")]
     flat = re.sub(r"\s*\n \*\s*", " ", block)
     for phrase in ("absent chunk is NOT VALID", "whatever fill_entry is", "it counts in *n_sites", "word for word the rule set of ws_map_distance",
@@ -57,11 +56,11 @@ def test_assembled_model_equals_the_brute_force_minimum():
     box = SM.assemble(chunks, lo, hi)
     assert box.shape == (10, 11, 10) and not box[5:, 4:, :6].any() and np.count_nonzero(box) > 700  # the absent octant is raw 0
     compared = 0
-    for kw in D.FLAGS:
+    for kw in DH.FLAGS:
         for R in (1, 3, 7):
             want, n_sites = DH.brute(box, R, **kw)
             got, n_model = SD.model(chunks, lo, hi, R, **kw)
-            assert D.same(got, want) and n_model == n_sites, (kw, R)
+            assert DH.same(got, want) and n_model == n_sites, (kw, R)
             compared += 1
             if kw["unknown_occupied"] and not kw["columns"]:
                 assert n_sites >= 5 * 7 * 6 and not got[5:, 4:, :6].any()  # every voxel of the absent chunk is a site
@@ -73,11 +72,11 @@ def test_committed_seeds_meet_the_input_condition():
     between 0 and R^2, at least 2 % at R^2 (test_gpu_distance.check_inputs)"""
     assert len(SD.SEEDS) == 19 and len(set(SD.SEEDS)) == 19
     for shape, seed in SD.SEEDS:
-        shares = D.check_inputs(D.draw_entries(shape, seed), shape)
+        shares = DH.check_inputs(DH.draw_entries(shape, seed), shape)
         print(shape, seed, [(n, round(b, 3), round(c, 3)) for n, b, c in shares])
     # the chunks of the GPU tests are these draws
-    assert np.array_equal(SD.seam_chunks()[(-1, -1, -1)], D.draw_entries((64,) * 3, SD.SEAM_SEED))
-    assert np.array_equal(SD.pillar_chunks(SD.PILLAR_Z, SD.PILLAR_Z_SEED)[(0, 0, 2)], D.draw_entries((64,) * 3, SD.PILLAR_Z_SEED + 4))
+    assert np.array_equal(SD.seam_chunks()[(-1, -1, -1)], DH.draw_entries((64,) * 3, SD.SEAM_SEED))
+    assert np.array_equal(SD.pillar_chunks(SD.PILLAR_Z, SD.PILLAR_Z_SEED)[(0, 0, 2)], DH.draw_entries((64,) * 3, SD.PILLAR_Z_SEED + 4))
     assert SD.PILLAR_Z[SD.HOLE] == (0, 0, 0) and (0, 0, 0) not in SD.pillar_chunks(SD.PILLAR_Z, SD.PILLAR_Z_SEED)
     assert SD.PILLAR_Y[SD.HOLE] == (0, 0, 0) and (0, 0, 0) not in SD.pillar_chunks(SD.PILLAR_Y, SD.PILLAR_Y_SEED)
 

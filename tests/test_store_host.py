@@ -6,6 +6,7 @@ import re
 
 import numpy as np
 import pytest
+from window_host_routes import expected_keys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["ws_store_create", "ws_store_destroy", "ws_store_reserve", "ws_store_count", "ws_store_keys", "ws_store_has", "ws_store_get_chunk",
@@ -20,11 +21,6 @@ def _i3(v):
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p)
-
-
-def expected_keys(lo, hi):
-    c0, c1 = np.floor_divide(np.asarray(lo, dtype=np.int64), 64), np.floor_divide(np.asarray(hi, dtype=np.int64), 64)
-    return np.array([(x, y, z) for x in range(c0[0], c1[0] + 1) for y in range(c0[1], c1[1] + 1) for z in range(c0[2], c1[2] + 1)], dtype=np.int32)
 
 
 BOXES = [((-100, -1, 0), (70, 64, 63)),          # negative coordinates, and chunk borders inside

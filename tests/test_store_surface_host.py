@@ -5,19 +5,19 @@ import re
 
 import numpy as np
 
-import test_gpu_store_mesh as SM
-import test_gpu_store_surface as SS
-import test_gpu_surface as G
-import test_mesh_host as MH
+import query_model as QM
+import store_scenes as SM
+import store_surface_scenes as SS
+import surface_model as G
 
 NEW = ["ws_store_surface", "ws_store_surface_records_dev", "ws_store_surface_marker_dev", "ws_store_surface_download", "ws_debug_store_surface_timing"]
-CTYPE = dict(MH.CTYPE, **{"ws_store *": C.c_void_p, "const ws_store *": C.c_void_p, "float *": C.c_void_p})
+CTYPE = dict(QM.CTYPE, **{"ws_store *": C.c_void_p, "const ws_store *": C.c_void_p, "float *": C.c_void_p})
 
 
 def test_library_exports_and_header_declares_the_store_surface_entry_points():
     from warpsense_amd import _lib
     L = _lib.load()
-    h = MH._header()
+    h = QM._header()
     for name in NEW:
         assert hasattr(L, name), name
         assert name in _lib.EXPORTS
@@ -32,7 +32,7 @@ def test_ctypes_signatures_agree_with_the_header():
     from warpsense_amd import _lib
     L = _lib.load()
     for name in NEW:
-        ret, params = MH._declared(name)
+        ret, params = QM._declared(name)
         fn = getattr(L, name)
         want = [CTYPE[p] for p in params]
         assert list(fn.argtypes) == want, (name, params, fn.argtypes)

@@ -1,21 +1,17 @@
 """The surface cloud without a GPU: the boundary (symbols, header, ctypes signatures), the numpy model of publish_local_map
-(tests/test_gpu_surface.py) against a hand-written literal of the reference's KAT map, the skeleton arithmetic against
+(tests/surface_model.py) against a hand-written literal of the reference's KAT map, the skeleton arithmetic against
 hand-computed windows, and the PLY writer."""
 import ctypes as C
-import os
 import re
 import struct
 
 import numpy as np
 
-import test_gpu_surface as G
+from query_model import _declared, _header
+import query_model as QM
+import surface_model as G
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["ws_map_surface", "ws_map_surface_records_dev", "ws_map_surface_marker_dev", "ws_map_surface_download", "ws_debug_surface_timing"]
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "warpsense_hip.h")).read()
 
 
 def test_library_exports_and_header_declares_the_surface_entry_points():
@@ -33,20 +29,6 @@ def test_library_exports_and_header_declares_the_surface_entry_points():
 
 CTYPE = {"ws_map *": C.c_void_p, "const ws_map *": C.c_void_p, "int": C.c_int, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "size_t": C.c_size_t,
          "const int32_t [3]": C.c_void_p, "float [3]": C.c_void_p, "void *": C.c_void_p, "float *": C.c_void_p, "size_t *": C.POINTER(C.c_size_t)}
-
-
-def _declared(name):
-    """(return type, [parameter types]) of `name` as the header declares it, parameter names stripped"""
-    m = re.search(r"([A-Za-z_ ]+?[ \*])" + name + r"\s*\(([^)]*)\)\s*;", _header())
-    assert m, name
-    params = []
-    for p in m.group(2).split(","):
-        p = re.sub(r"/\*.*?\*/", "", p).strip()
-        arr = re.search(r"\[(\d+)\]$", p)
-        p = re.sub(r"\[\d+\]$", "", p).strip()
-        t = re.sub(r"\b[a-z_0-9]+$", "", p).strip()  # drop the parameter's name
-        params.append(t + (f" [{arr.group(1)}]" if arr else ""))
-    return m.group(1).strip(), params
 
 
 def test_ctypes_signatures_agree_with_the_header():
@@ -92,7 +74,7 @@ def test_model_reproduces_the_reference_kat_map():
                      [5, 0, 0, 0, 0, 0, 1],
                      [6, 0, 0, 0, f(1000) / f(3000), 0, 1],
                      [7, 0, 0, 0, f(2000) / f(3000), 0, 1]], dtype=np.float32)  # x * 1000 / 1000.f = x metres
-    assert G.same(mk, want)
+    assert QM.same(mk, want)
     # a narrower band keeps |value| < 1500 only
     rec2, _ = G.model(Host, tau, res, band=1500)
     assert [int(r["x"]) for r in rec2] == [4, 5, 6]
@@ -142,7 +124,7 @@ def test_ply_writer_round_trips(tmp_path):
 
 
 def test_committed_seeds_give_well_populated_inputs():
-    """the draws of tests/test_gpu_surface.py, checked where no GPU is needed: planted categories present, share in [0.10, 0.40]"""
+    """the draws of tests/surface_model.py, checked where no GPU is needed: planted categories present, share in [0.10, 0.40]"""
     for size in G.SIZES:
         n = int(np.prod(size))
         for which in (0, 1):

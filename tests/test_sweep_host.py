@@ -5,21 +5,11 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
-from test_preprocess import POSES, make_cloud
+from scan_clouds import POSES, make_cloud
+from scan_clouds import rigid
 from warpsense_amd import synthetic as S
 
 ROOM = (2000.0, 1800.0, 900.0)
-
-
-def rigid(tx, ty, tz, yaw_deg, pitch_deg=0.0):
-    """4x4 double: yaw about z, then pitch about y, translation in mm"""
-    a, b = np.deg2rad(yaw_deg), np.deg2rad(pitch_deg)
-    Rz = np.array([[np.cos(a), -np.sin(a), 0.0], [np.sin(a), np.cos(a), 0.0], [0.0, 0.0, 1.0]])
-    Ry = np.array([[np.cos(b), 0.0, np.sin(b)], [0.0, 1.0, 0.0], [-np.sin(b), 0.0, np.cos(b)]])
-    T = np.eye(4)
-    T[:3, :3] = Rz @ Ry
-    T[:3, 3] = (tx, ty, tz)
-    return T
 
 
 def numpy_sweep_poses(pose_end, motion, k):

@@ -10,9 +10,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import window_model as M
-from test_map_window_host import HostRoute, TAU
+from window_host_routes import HostRoute, TAU
 from window_model import I32_MAX, I32_MIN, WALKS
+import window_model as M
 
 WS_ERR_INVALID, WS_ERR_RANGE = -1, -5
 SIZES = [(21, 17, 13), (16, 18, 20), (3, 19, 5), (4, 4, 4)]
@@ -234,7 +234,7 @@ def test_shift_plan_refuses_a_window_that_is_outside_to_begin_with():
 # ------------------------------------------------------------------------------------------------ chunk keys at the edges
 def test_chunks_of_box_at_the_ends_of_int32():
     import warpsense_amd as W
-    from test_store_host import expected_keys
+    from window_host_routes import expected_keys
     top, bottom = 2 ** 25 - 1, -2 ** 25
     boxes = [((I32_MAX, I32_MAX, I32_MAX), (I32_MAX, I32_MAX, I32_MAX)),
              ((I32_MIN, I32_MIN, I32_MIN), (I32_MIN, I32_MIN, I32_MIN)),

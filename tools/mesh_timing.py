@@ -5,7 +5,7 @@ session and interleaved:
       context's stream (ws_debug_mesh_timing), bytes and the map-read rate of the count passes; the whole call end to end
       including the download of vertices and faces (host clock);
   (b) ws_map_surface on the same map: count / scan / emit (ws_debug_surface_timing);
-  (c) the host route: ws_map_download alone, and download + the numpy model (tests/test_gpu_mesh.py) on the room box.
+  (c) the host route: ws_map_download alone, and download + the numpy model (tests/mesh_model.py) on the room box.
 
     python tools/mesh_timing.py [--map 512] [--repeats 20] [--warmup 3] [--out profiles/mesh_timing.json]
 
@@ -42,7 +42,8 @@ def main():
     import warpsense_amd as W
     from warpsense_amd import _lib
     from warpsense_amd import synthetic as S
-    import test_gpu_mesh as M
+    import mesh_model as M
+    import query_model as QM
     assert torch.cuda.is_available(), "this measurement needs the GPU"
 
     tau, mw, res = 1000, 640, args.res
@@ -87,7 +88,7 @@ def main():
         t1 = time.perf_counter()
         counts = None
         if with_model:
-            box = M.G.ring_box(host_buf, size, pos, off, np.asarray(room_lo, dtype=np.int64), np.asarray(room_hi, dtype=np.int64))
+            box = QM.ring_box(host_buf, size, pos, off, np.asarray(room_lo, dtype=np.int64), np.asarray(room_hi, dtype=np.int64))
             v, f = M.model_box(box, room_lo, res)
             counts = (len(v), len(f))
         return t1 - t0, time.perf_counter() - t1, counts

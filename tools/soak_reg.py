@@ -66,7 +66,7 @@ def main():
         if args.server:
             import ctypes as C
             sys.path.insert(0, os.path.join(ROOT, "tests"))
-            from test_abi_and_host import OracleGnBackend
+            from reg_scenes import OracleGnBackend
             st = OracleGnBackend.State()
             O.lib().wso_gn_begin(C.byref(st), O._p(O.colmajor(np.eye(4, dtype=np.float32))), int(max_it), C.c_float(rp.it_weight_gradient), C.c_float(rp.epsilon))
             reg.reg_.prepare_registration(q)

@@ -64,7 +64,7 @@ def run(mode, scans, size, with_b, writeback=True):
     import oracle_lib as O
     import warpsense_amd as W
     from warpsense_amd import synthetic as S
-    from test_abi_and_host import OracleGnBackend
+    from reg_scenes import OracleGnBackend
     tau, res, mw = 1000, 50, 640
     shape = (size, size, size // 2)
     params = W.Params(W.MapParams(resolution=res, max_distance=tau / 1000.0, max_weight=mw // 64, size=tuple(s * res / 1000.0 for s in shape)))
