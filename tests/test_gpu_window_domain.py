@@ -369,7 +369,7 @@ class ThinMap:
 
     def __init__(self, size, pos, offset):
         import warpsense_amd as W
-        from warpsense_amd.api import _device_tensor
+        from warpsense_amd._abi import _device_tensor
         self.size, self.pos, self.offset = (np.asarray(v, dtype=np.int64) for v in (size, pos, offset))
         self.t = W.TSDFCuda(W.DeviceMap(_i3(size), _i3(offset), None, _i3(pos)), TAU, MW, RES)
         self.ring = _device_tensor(self.t.avg_map().device_ptr(), tuple(int(v) for v in size), "<i4", self.t)

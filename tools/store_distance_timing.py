@@ -88,7 +88,7 @@ def main():
         window_times(*c), store_times(*c)
         pw, ps = L.ws_map_distance_dev(h, C.byref(n)), L.ws_store_distance_dev(hs, C.byref(n))
         shape = (int(n.value),)
-        same["columns" if c[1] else "voxels"] = bool(torch.equal(W.api._device_tensor(pw, shape, "<i4", t), W.api._device_tensor(ps, shape, "<i4", store)))
+        same["columns" if c[1] else "voxels"] = bool(torch.equal(W._abi._device_tensor(pw, shape, "<i4", t), W._abi._device_tensor(ps, shape, "<i4", store)))
     _lib.check(L.ws_debug_distance_timing(h, 0, None), "ws_debug_distance_timing")
     _lib.check(L.ws_debug_store_distance_timing(hs, 0, None), "ws_debug_store_distance_timing")
 

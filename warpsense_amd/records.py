@@ -1,0 +1,101 @@
+"""The record dtypes of the map queries, what takes distance records apart, and the PLY writers."""
+from __future__ import annotations
+
+import numpy as np
+
+from . import _lib
+
+# one record of ws_map_surface: world voxel coordinates and the packed entry (16 bytes)
+SURFACE_RECORD = np.dtype([("x", "<i4"), ("y", "<i4"), ("z", "<i4"), ("raw", "<u4")])
+
+
+# one vertex of ws_map_mesh: world position in millimetres and the smallest corner weight of its cell (16 bytes)
+VERT = np.dtype([("x_mm", "<i4"), ("y_mm", "<i4"), ("z_mm", "<i4"), ("weight", "<u4")])
+
+
+# one record of ws_map_raycast: the hit point and the range along the ray in millimetres; no hit: 0, 0, 0, -1 (16 bytes)
+RAY = np.dtype([("x_mm", "<i4"), ("y_mm", "<i4"), ("z_mm", "<i4"), ("range_mm", "<i4")])
+
+
+# one record of ws_map_sample: the interpolated signed distance in mm, the smallest corner weight of the cell, the class (0 unknown,
+# 1 free, 2 surface, 3 inside) and the packed entry of the nearest voxel (16 bytes)
+SAMPLE = np.dtype([("d_mm", "<i4"), ("weight", "<i4"), ("cls", "<u4"), ("raw", "<u4")])
+SAMPLE_CLASSES = _lib.SAMPLE_CLASSES
+
+
+def distance_class(rec):
+    """The class bits of ws_map_distance records: 2 occupied, 1 free, 0 unknown (uint8)."""
+    return (np.asarray(rec, dtype=np.uint32) >> np.uint32(30)).astype(np.uint8)
+
+
+def distance_d2(rec):
+    """The squared distance in voxels of ws_map_distance records (bits 0..23, uint32), clamped at max_dist_vox squared."""
+    return np.asarray(rec, dtype=np.uint32) & np.uint32(0xFFFFFF)
+
+
+def distance_mm(rec, res):
+    """The distance of ws_map_distance records in millimetres, res * sqrt(d2) as float32 -- the only float of the route, and it
+    is made on the host."""
+    return (np.float32(res) * np.sqrt(distance_d2(rec).astype(np.float32))).astype(np.float32)
+
+
+def write_surface_ply(path, marker):
+    """The marker cloud of DeviceMapMemWrapper.surface(marker=True) as a binary little-endian PLY: float x y z (metres) and
+    uchar red green blue (the reference's r / g / b in [0, 1) scaled by 255 and truncated)."""
+    marker = np.asarray(marker, dtype=np.float32).reshape(-1, 7)
+    out = np.empty(len(marker), dtype=np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")]))
+    out["x"], out["y"], out["z"] = marker[:, 0], marker[:, 1], marker[:, 2]
+    for name, col in (("red", 3), ("green", 4), ("blue", 5)):
+        out[name] = np.clip(marker[:, col] * np.float32(255.0), 0.0, 255.0).astype(np.uint8)
+    header = ("ply\nformat binary_little_endian 1.0\ncomment warpsense_amd surface cloud\n"
+              f"element vertex {len(out)}\nproperty float x\nproperty float y\nproperty float z\n"
+              "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n")
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(out.tobytes())
+    return len(out)
+
+
+def write_mesh_ply(path, vertices, faces):
+    """The mesh of DeviceMapMemWrapper.mesh() as a binary little-endian PLY: float x y z in metres (mm / 1000.f in single
+    precision), faces as a uchar count (3) and int vertex indices.  Returns (vertices, faces) written."""
+    vertices = np.asarray(vertices, dtype=VERT).reshape(-1)
+    faces = np.asarray(faces, dtype=np.uint32).reshape(-1, 3)
+    v = np.empty(len(vertices), dtype=np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4")]))
+    for name in "xyz":
+        v[name] = vertices[name + "_mm"].astype(np.float32) / np.float32(1000.0)
+    f = np.empty(len(faces), dtype=np.dtype([("n", "u1"), ("i", "<i4", (3,))]))
+    f["n"] = 3
+    f["i"] = faces.astype(np.int32)
+    header = ("ply\nformat binary_little_endian 1.0\ncomment warpsense_amd surface-nets mesh\n"
+              f"element vertex {len(v)}\nproperty float x\nproperty float y\nproperty float z\n"
+              f"element face {len(f)}\nproperty list uchar int vertex_indices\nend_header\n")
+    with open(path, "wb") as out:
+        out.write(header.encode("ascii"))
+        out.write(v.tobytes())
+        out.write(f.tobytes())
+    return len(v), len(f)
+
+
+def write_raycast_ply(path, records, gradient=None):
+    """The hits of DeviceMapMemWrapper.raycast() (records with range_mm >= 0) as a binary little-endian PLY point cloud: float x y z
+    in metres (mm / 1000.f in single precision, as write_mesh_ply) and, when `gradient` is given, float nx ny nz: the gradient
+    normalised in float64, then cast (a zero gradient stays zero).  Returns the number of points written."""
+    records = np.asarray(records, dtype=RAY).reshape(-1)
+    hit = records["range_mm"] >= 0
+    names = ["x", "y", "z"] + (["nx", "ny", "nz"] if gradient is not None else [])
+    v = np.empty(int(np.count_nonzero(hit)), dtype=np.dtype([(n, "<f4") for n in names]))
+    for name in "xyz":
+        v[name] = records[name + "_mm"][hit].astype(np.float32) / np.float32(1000.0)
+    if gradient is not None:
+        g = np.asarray(gradient, dtype=np.int32).reshape(-1, 3)[hit].astype(np.float64)
+        length = np.sqrt(np.sum(g * g, axis=1))
+        g = g / np.where(length > 0, length, 1.0)[:, None]
+        for k, name in enumerate(("nx", "ny", "nz")):
+            v[name] = g[:, k].astype(np.float32)
+    header = ("ply\nformat binary_little_endian 1.0\ncomment warpsense_amd ray cast\n"
+              f"element vertex {len(v)}\n" + "".join(f"property float {n}\n" for n in names) + "end_header\n")
+    with open(path, "wb") as out:
+        out.write(header.encode("ascii"))
+        out.write(v.tobytes())
+    return len(v)

@@ -1,0 +1,202 @@
+"""The global map in device memory (ws_store_*): DeviceGlobalMap, the device twin of GlobalMap, and its queries."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._abi import _i3, _i3c, _ptr, pack_entry
+from ._lib import WS_MAP_AVG, check
+from .context import Context
+from .global_map import GlobalMap
+from .queries import _box_ptrs, _distance_call, _mesh_call, _raycast_call, _sample_call, _surface_call, _timing
+
+
+class DeviceGlobalMap:
+    """The global map in device memory (ws_store, include/warpsense_hip.h): the device twin of GlobalMap.  64^3-voxel chunks of raw
+    uint32 entries in HBM, index x*4096 + y*64 + z, keyed by floor(world voxel / 64); chunks never seen hold the default entry.  The
+    key -> slot directory is the host's.  TSDFMapping(..., device_global_map=this).shift_map_device saves the leaving slabs into
+    it and loads the entering ones from it in stream order; flush_to() merges it into a host GlobalMap (and its .h5 file)."""
+
+    CHUNK_SIZE = 64
+    CHUNK_WORDS = 64 ** 3
+
+    def __init__(self, default_value, default_weight=0, max_chunks: int = 0, segment_chunks: int = 0, ctx: Context | None = None):
+        self.ctx = ctx or Context.default()
+        self._L = self.ctx._L
+        self.default_raw = int(pack_entry(default_value, default_weight))
+        h = C.c_void_p()
+        check(self._L.ws_store_create(self.ctx.handle, self.default_raw, int(max_chunks), int(segment_chunks), C.byref(h)), "ws_store_create")
+        self.handle = h
+
+    def count(self) -> int:
+        n = C.c_uint64(0)
+        check(self._L.ws_store_count(self.handle, C.byref(n), None), "ws_store_count")
+        return int(n.value)
+
+    def capacity(self) -> int:
+        n = C.c_uint64(0)
+        check(self._L.ws_store_count(self.handle, None, C.byref(n)), "ws_store_count")
+        return int(n.value)
+
+    def reserve(self, n: int):
+        """segments for n chunks now, so that no shift has to allocate (and wait for the device)"""
+        check(self._L.ws_store_reserve(self.handle, int(n)), "ws_store_reserve")
+
+    def keys(self) -> list:
+        """the chunk keys, ascending (cx, cy, cz)"""
+        n = C.c_size_t(0)
+        check(self._L.ws_store_keys(self.handle, None, 0, C.byref(n)), "ws_store_keys")
+        keys = np.zeros((n.value, 3), dtype=np.int32)
+        check(self._L.ws_store_keys(self.handle, _ptr(keys), n.value, C.byref(n)), "ws_store_keys")
+        return [tuple(int(v) for v in k) for k in keys[:n.value]]
+
+    def has_chunk(self, cx, cy, cz) -> bool:
+        return bool(self._L.ws_store_has(self.handle, _i3c((cx, cy, cz))))
+
+    def chunk(self, key):
+        """a host copy of one chunk (262 144 uint32), None if the store does not hold it"""
+        out = np.empty(self.CHUNK_WORDS, dtype=np.uint32)
+        found = C.c_int32(0)
+        check(self._L.ws_store_get_chunk(self.handle, _i3c(tuple(key)), _ptr(out), C.byref(found)), "ws_store_get_chunk")
+        return out if found.value else None
+
+    def put_chunk(self, key, data):
+        data = np.ascontiguousarray(data, dtype=np.uint32).reshape(-1)
+        assert data.size == self.CHUNK_WORDS
+        check(self._L.ws_store_put_chunk(self.handle, _i3c(tuple(key)), _ptr(data)), "ws_store_put_chunk")
+
+    def drop_chunk(self, key):
+        check(self._L.ws_store_drop_chunk(self.handle, _i3c(tuple(key))), "ws_store_drop_chunk")
+
+    def save_box(self, tsdf: "TSDFCuda", lo, hi, which: int = WS_MAP_AVG):
+        """the box [lo, hi] of the window of `tsdf` into the chunks (ws_store_save_box; stream-ordered, no wait)"""
+        check(self._L.ws_store_save_box(self.handle, tsdf.handle, int(which), _ptr(_i3(lo)), _ptr(_i3(hi))), "ws_store_save_box")
+
+    def load_box(self, tsdf: "TSDFCuda", lo, hi, which: int = WS_MAP_AVG):
+        """the chunks into the box [lo, hi] of the window of `tsdf`, the default entry where there is no chunk (ws_store_load_box)"""
+        check(self._L.ws_store_load_box(self.handle, tsdf.handle, int(which), _ptr(_i3(lo)), _ptr(_i3(hi))), "ws_store_load_box")
+
+    def timing(self, enable: int = -1):
+        """device milliseconds of the save and of the load launches of the last call (ws_debug_store_timing)"""
+        return _timing(self._L, "ws_debug_store_timing", self.handle, 2, enable)
+
+    def surface(self, tau, resolution, lo=None, hi=None, band=None, marker=False, device=False):
+        """The surface cloud of the chunks on the device (ws_store_surface; the rules are those of ws_map_surface, stated in
+        include/warpsense_hip.h): every voxel of a present chunk inside the inclusive world-voxel box [lo, hi] (both None: every
+        present chunk) with weight > 0 and abs(value) < band (None: tau), in ascending world (x, y, z), z fastest, across chunk
+        borders.  Voxels of absent chunks never qualify.  tau, resolution: the map's (the store knows neither); they decide the
+        marker's colour and point.
+
+        Returns the same forms as DeviceMapMemWrapper.surface: the records, or with `marker` (records, (n, 7) float32);
+        device=True: torch tensors that ALIAS the store's buffers, valid until the next surface() on this store."""
+        return _surface_call(self._L, "ws_store_surface", self, (), lo, hi, band, (int(tau), int(resolution)), marker, device)
+
+    def surface_timing(self, enable: int = -1):
+        """device milliseconds of the count passes, the scan and the emit pass of the last surface() (ws_debug_store_surface_timing)"""
+        return _timing(self._L, "ws_debug_store_surface_timing", self.handle, 3, enable)
+
+    def mesh(self, resolution, lo=None, hi=None, any_weight=False, device=False):
+        """The mesh of the chunks on the device (ws_store_mesh; the rules are those of ws_map_mesh, stated in
+        include/warpsense_hip.h): the surface of everything the store holds inside the inclusive world-voxel box [lo, hi] (both
+        None: the bounding box of the present chunks), in the order of DeviceMapMemWrapper.mesh across chunk borders.  Voxels of
+        absent chunks are not valid.  resolution: the map's, in mm per voxel (the store does not know it).
+
+        Returns (vertices, faces) like DeviceMapMemWrapper.mesh; device=True: torch tensors that ALIAS the store's buffers, valid
+        until the next mesh() on this store."""
+        return _mesh_call(self._L, "ws_store_mesh", self, (), lo, hi, (int(resolution),), any_weight, device)
+
+    def mesh_timing(self, enable: int = -1):
+        """device milliseconds of the count passes, the scan and the emit passes of the last mesh() (ws_debug_store_mesh_timing)"""
+        return _timing(self._L, "ws_debug_store_mesh_timing", self.handle, 3, enable)
+
+    def raycast(self, resolution, origin_mm, dirs, max_range_mm, lo=None, hi=None, any_weight=False, gradient=False, targets=False):
+        """Ray cast of the chunks on the device (ws_store_raycast; the rules are those of ws_map_raycast, stated in
+        include/warpsense_hip.h): per ray the first crossing of the surface from the outside within max_range_mm, through
+        everything the store holds inside the inclusive world-voxel box [lo, hi] (both None: everything).  Voxels of absent chunks
+        are not valid.  resolution: the map's, in mm per voxel.  origin_mm, dirs, targets, any_weight, gradient and the returned
+        (records, gradient | None) are those of DeviceMapMemWrapper.raycast; `last_hits` keeps the call's number of hits."""
+        box = _box_ptrs("raycast", lo, hi)
+        rec, grad, self.last_hits = _raycast_call(self._L, "ws_store_raycast", self.handle, box, origin_mm, dirs, max_range_mm, (int(resolution),),
+                                                  any_weight, gradient, targets)
+        return rec, grad
+
+    def sample(self, resolution, points, band_mm, lo=None, hi=None, any_weight=False, gradient=False, select=None, device=False):
+        """What the chunks on the device say at `points` (ws_store_sample; the rules are those of ws_map_sample, stated in
+        include/warpsense_hip.h), through everything the store holds inside the inclusive world-voxel box [lo, hi] (both None:
+        everything).  Voxels of absent chunks are not valid.  resolution: the map's, in mm per voxel; band_mm > 0.  The other arguments
+        and the returned (records, counts, gradient | None, selection | None) are those of DeviceMapMemWrapper.sample."""
+        box = _box_ptrs("sample", lo, hi)
+        return _sample_call(self._L, "ws_store_sample", self, box, points, band_mm, (int(resolution),), any_weight, gradient, select, device)
+
+    def sample_timing(self, enable: int = -1):
+        """device milliseconds of the upload, the sample pass and the select passes of the last sample() (ws_debug_store_sample_timing)"""
+        return _timing(self._L, "ws_debug_store_sample_timing", self.handle, 3, enable)
+
+    def raycast_timing(self, enable: int = -1):
+        """device milliseconds of the upload, the march and the gradient pass of the last raycast() (ws_debug_store_raycast_timing)"""
+        return _timing(self._L, "ws_debug_store_raycast_timing", self.handle, 3, enable)
+
+    def distance(self, lo=None, hi=None, max_dist_vox=20, unknown_occupied=False, columns=False, any_weight=False, device=False):
+        """The distance field of the chunks on the device (ws_store_distance; the rules are those of ws_map_distance, stated in
+        include/warpsense_hip.h): per voxel of the inclusive world-voxel box [lo, hi] (both None: the bounding box of the present
+        chunks) the squared Euclidean distance in voxels to the nearest occupied voxel of the box, clamped at max_dist_vox squared
+        (1 .. 255).  Voxels of absent chunks are unknown: with unknown_occupied they are sites.  columns, any_weight, the returned
+        uint32 records shaped (nx, ny, nz) or (nx, ny) and `last_sites` are those of DeviceMapMemWrapper.distance.  Unlike mesh()
+        and raycast() the result is dense: 8 bytes of device memory per record of the box.
+        device=True: a torch int32 tensor of that shape on the GPU that ALIASES the store's buffer, valid until the next distance()
+        on this store."""
+        def bounding_shape():
+            keys = np.asarray(self.keys(), dtype=np.int64).reshape(-1, 3)
+            return tuple(int(v) for v in (keys.max(axis=0) - keys.min(axis=0) + 1) * self.CHUNK_SIZE) if len(keys) else (0, 0, 0)
+        rec, self.last_sites = _distance_call(self._L, "ws_store_distance", self, (), lo, hi, max_dist_vox, unknown_occupied, columns, any_weight,
+                                              device, bounding_shape)
+        return rec
+
+    def distance_timing(self, enable: int = -1):
+        """device milliseconds of pass 0 and of the x, y and z passes of the last distance() (ws_debug_store_distance_timing)"""
+        return _timing(self._L, "ws_debug_store_distance_timing", self.handle, 4, enable)
+
+    def flush_to(self, global_map: GlobalMap):
+        """every chunk merged into a host GlobalMap: into its chunk cache (activate_chunk), or, for a map with a file, straight
+        into the file (GlobalMap._write_chunk) unless the chunk is active in the cache"""
+        for key in self.keys():
+            data = self.chunk(key)
+            with global_map.lock:
+                if global_map._file is not None and key not in global_map.chunks:
+                    global_map._write_chunk(key, data)
+                else:
+                    global_map.activate_chunk(*key)[:] = data
+
+    def load_from(self, global_map: GlobalMap, keys=None):
+        """chunks of a host GlobalMap (None: all it holds, in memory and in its file) into the store, to continue a saved map"""
+        if keys is None:
+            keys = set(global_map.chunks) | (set(global_map._in_file) if global_map._file is not None else set())
+        for key in sorted(tuple(int(v) for v in k) for k in keys):
+            if not global_map.has_chunk(*key):
+                continue
+            with global_map.lock:
+                self.put_chunk(key, global_map.activate_chunk(*key))
+
+    def close(self):
+        if self.handle:
+            self._L.ws_store_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def chunks_of_box(lo, hi) -> np.ndarray:
+    """host only: the (n, 3) chunk keys an inclusive world-voxel box overlaps, ascending (ws_store_chunks_of_box)"""
+    L = _lib.load()
+    n = C.c_size_t(0)
+    lo, hi = _i3(lo), _i3(hi)
+    check(L.ws_store_chunks_of_box(_ptr(lo), _ptr(hi), None, 0, C.byref(n)), "ws_store_chunks_of_box")
+    keys = np.zeros((n.value, 3), dtype=np.int32)
+    check(L.ws_store_chunks_of_box(_ptr(lo), _ptr(hi), _ptr(keys), n.value, C.byref(n)), "ws_store_chunks_of_box")
+    return keys
