@@ -2,66 +2,13 @@
 // restatement of the same operation, computed in the same thread, over the domain each helper's exactness argument states.
 // Every mismatch is counted; the first few are recorded with their inputs.  Prints one line per helper, exits 1 on any mismatch.
 #include <cstdint>
-#include <cstdio>
-#include <cstdlib>
 #include <vector>
 
 #include "ws_march.h"
 
+#include "unit_report.hpp"
+
 using namespace ws;
-
-#define CHECK_HIP(x)                                                                                                                   \
-  do                                                                                                                                   \
-  {                                                                                                                                    \
-    hipError_t e_ = (x);                                                                                                               \
-    if (e_ != hipSuccess)                                                                                                              \
-    {                                                                                                                                  \
-      printf("HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__);                                                  \
-      exit(2);                                                                                                                         \
-    }                                                                                                                                  \
-  } while (0)
-
-constexpr int MAX_REC = 8;
-struct Report
-{
-  unsigned long long mismatches;
-  unsigned long long checked;
-  uint32_t n_rec;
-  uint32_t pad;
-  long long rec[MAX_REC][6]; // inputs and the two results of the first mismatches
-};
-
-__device__ void fail(Report *r, long long a, long long b, long long c, long long d, long long got, long long want)
-{
-  atomicAdd(&r->mismatches, 1ull);
-  const uint32_t i = atomicAdd(&r->n_rec, 1u);
-  if (i < MAX_REC)
-  {
-    r->rec[i][0] = a;
-    r->rec[i][1] = b;
-    r->rec[i][2] = c;
-    r->rec[i][3] = d;
-    r->rec[i][4] = got;
-    r->rec[i][5] = want;
-  }
-}
-// one add per thread and launch: how many cases were looked at (a kernel that silently skipped its domain fails the count)
-__device__ void count(Report *r, unsigned long long n)
-{
-  if (n) atomicAdd(&r->checked, n);
-}
-
-__device__ __forceinline__ uint64_t mix64(uint64_t z)
-{
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-constexpr uint32_t GRID = 4096, BLOCK = 256;
-#define FOR_RANGE(i, base, n)                                                                                                          \
-  for (uint64_t i = (base) + (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < (base) + (n); i += (uint64_t)GRID * BLOCK)
 
 // trunc(x / d) as plain 64-bit arithmetic: q is it iff x - q d lies in [0, d) (x >= 0) or (-d, 0] (x < 0), q d of x's sign or 0
 __device__ __forceinline__ bool is_trunc_quotient(int64_t x, int64_t d, int64_t q)
@@ -334,35 +281,62 @@ __global__ void k_div_i64(uint64_t base, uint64_t n, Report *rep)
   count(rep, c);
 }
 
-// ---------------------------------------------------------------------------------------------------------------------------
-static Report *g_rep;
-static int g_bad = 0;
-
-static void begin() { CHECK_HIP(hipMemset(g_rep, 0, sizeof(Report))); }
-static void finish(const char *name, unsigned long long expect_checked)
+// ---- div_trunc_i64 on the operands its argument is about: the double division below 2^53 can only go wrong where num / den is
+// within a rounding error of an integer, i.e. num = q den + e with e in {-1, 0, 1} and |num| as large as the branch admits; the
+// switch to the plain division is at 2^53.  Two families, both signs of each operand:
+//   near: for every den of the list, num = +-(2^53 + delta), delta in [-4, 4].  The list: every power of two and every divisor of
+//         2^53 - 1 and 2^53 + 1 up to 2^53 - 1 (1 and 2^53 - 1 among them), so every num is q den + e with |e| <= 5, within 4 of 2^53.
+//   mult: for EDGE_DENS divisors of every magnitude in [1, 2^53 - 1] and A in {2^53, 2^52, 2^40}: the multiple of den next below A
+//         and the one at or next above it, each with e in {-1, 0, 1}.  |num| is within den of A: at A = 2^53 the lower multiple takes
+//         the double division, the upper one the plain division (or the double one, where q den - 1 = 2^53 - 1).
+constexpr uint64_t EDGE_DENS = 1ull << 20, EDGE_PER_DEN = 3 * 2 * 3 * 4, EDGE_PER_NEAR = 9 * 4;
+__host__ __device__ inline int64_t edge_den(uint64_t j)
 {
-  CHECK_HIP(hipGetLastError());
-  CHECK_HIP(hipDeviceSynchronize());
-  Report r;
-  CHECK_HIP(hipMemcpy(&r, g_rep, sizeof r, hipMemcpyDeviceToHost));
-  printf("%-22s checked %14llu  mismatches %llu\n", name, r.checked, r.mismatches);
-  for (uint32_t j = 0; j < r.n_rec && j < (uint32_t)MAX_REC; ++j)
-    printf("    in (%lld, %lld, %lld, %lld): got %lld, want %lld\n", r.rec[j][0], r.rec[j][1], r.rec[j][2], r.rec[j][3], r.rec[j][4], r.rec[j][5]);
-  if (r.mismatches || (expect_checked && r.checked != expect_checked) || r.checked == 0)
+  const int64_t top = (1ll << 53) - 1;
+  const int64_t special[8] = {1, 2, 3, top, top - 1, 1ll << 26, (1ll << 26) + 1, 94906266 /* ceil(sqrt(2^53)) */};
+  if (j < 8) return special[j];
+  const uint64_t h = mix64(j), g = mix64(h);
+  const int64_t d = (int64_t)(h >> (11 + g % 53)); // every magnitude up to 2^53 - 1
+  return d ? d : 1;
+}
+__global__ void k_div_i64_edges(const int64_t *near_dens, uint64_t n_near, uint64_t base, uint64_t n, Report *rep)
+{
+  unsigned long long c = 0;
+  FOR_RANGE(i, base, n)
   {
-    if (expect_checked && r.checked != expect_checked) printf("    expected %llu cases\n", expect_checked);
-    g_bad = 1;
+    int64_t num, den;
+    uint64_t t = i;
+    if (i < n_near * EDGE_PER_NEAR)
+    {
+      const uint32_t sg = (uint32_t)(t % 4); t /= 4;
+      const int64_t delta = (int64_t)(t % 9) - 4; t /= 9;
+      den = near_dens[t];
+      num = (1ll << 53) + delta;
+      if (sg & 1) num = -num;
+      if (sg & 2) den = -den;
+    }
+    else
+    {
+      t -= n_near * EDGE_PER_NEAR;
+      const uint32_t sg = (uint32_t)(t % 4); t /= 4;
+      const int64_t e = (int64_t)(t % 3) - 1; t /= 3;
+      const uint32_t hi = (uint32_t)(t % 2); t /= 2;
+      const uint32_t which = (uint32_t)(t % 3); t /= 3;
+      den = edge_den(t);
+      const int64_t A = which == 0 ? (1ll << 53) : (which == 1 ? (1ll << 52) : (1ll << 40));
+      const int64_t q = (A - 1) / den + (int64_t)hi; // q den < A <= (q + 1) den
+      num = q * den + e;                             // below 2^54
+      if (sg & 1) num = -num;
+      if (sg & 2) den = -den;
+    }
+    const int64_t got = div_trunc_i64(num, den), want = num / den;
+    if (got != want) fail(rep, num, den, 0, 0, got, want);
+    ++c;
   }
-  fflush(stdout);
-}
-// a long index space in launches of at most 2^34 cases (each launch well below a second)
-template <class F>
-static void chunked(uint64_t n, F &&launch)
-{
-  const uint64_t STEP = 1ull << 34;
-  for (uint64_t b = 0; b < n; b += STEP) launch(b, n - b < STEP ? n - b : STEP);
+  count(rep, c);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
 int main()
 {
   CHECK_HIP(hipMalloc((void **)&g_rep, sizeof(Report)));
@@ -501,6 +475,36 @@ int main()
   begin();
   k_div_i64<<<G, B>>>(0, 1ull << 28, g_rep);
   finish("div_trunc_i64", 1ull << 28);
+
+  {
+    // the divisors of the `near` family; each is checked to divide the number it is listed for
+    std::vector<int64_t> nd;
+    for (int j = 0; j <= 52; ++j) nd.push_back(1ll << j);
+    const int64_t top = (1ll << 53) - 1;
+    const int64_t pm[3] = {6361, 69431, 20394401};       // 2^53 - 1
+    const int64_t pp[3] = {3, 107, 28059810762433ll};    // 2^53 + 1
+    for (int m = 1; m < 8; ++m)
+    {
+      int64_t a = 1, b = 1;
+      for (int k = 0; k < 3; ++k)
+        if (m & (1 << k)) a *= pm[k], b *= pp[k];
+      if (top % a != 0 || (top + 2) % b != 0)
+      {
+        printf("div_trunc_i64 (edges): %lld or %lld is no divisor\n", (long long)a, (long long)b);
+        g_bad = 1;
+      }
+      nd.push_back(a);
+      if (b <= top) nd.push_back(b);
+    }
+    int64_t *d_nd;
+    CHECK_HIP(hipMalloc((void **)&d_nd, nd.size() * sizeof(int64_t)));
+    CHECK_HIP(hipMemcpy(d_nd, nd.data(), nd.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    const uint64_t n_edges = nd.size() * EDGE_PER_NEAR + EDGE_DENS * EDGE_PER_DEN; // 66 * 36 + 2^20 * 72 = 75 499 848 >= 2^26
+    begin();
+    k_div_i64_edges<<<G, B>>>(d_nd, nd.size(), 0, n_edges, g_rep);
+    finish("div_trunc_i64 (edges)", n_edges);
+    CHECK_HIP(hipFree(d_nd));
+  }
 
   CHECK_HIP(hipFree(g_rep));
   printf(g_bad ? "FAILED\n" : "ok\n");

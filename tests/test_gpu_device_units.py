@@ -1,7 +1,10 @@
 """The device's fixed-point helpers (ws_device.h, ws_march.h) held to plain int64 / double arithmetic over the domains their
 exactness arguments state, evaluated on the GPU itself (tests/cpp/device_units.hip): make_fastdiv_dev, div_trunc, div_res,
 div_res_b with ring_b / ring_m, trunc15_biased, the three forms of the weight ramp, integrate_entry, the sqrt of l2norm_i /
-l2norm_l and div_trunc_i64.  The whole suite scans only reach these through whole maps."""
+l2norm_l and div_trunc_i64 -- on random operands, and on the ones its argument is about: numerators within one of a multiple of the
+divisor, at 2^53 where it switches between the double and the plain division.  The whole suite scans only reach these through whole
+maps.  The helpers of the map queries have a program of their own: tests/cpp/query_units.hip, tests/test_gpu_query_units.py; both
+programs share tests/cpp/unit_report.hpp."""
 import os
 import subprocess
 
@@ -21,4 +24,4 @@ def test_device_helpers_match_plain_integer_arithmetic(tmp_path):
     print(out.stdout)
     assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stdout + out.stderr
     lines = [ln for ln in out.stdout.splitlines() if "mismatches" in ln]
-    assert len(lines) == 12 and all(ln.rstrip().endswith("mismatches 0") for ln in lines), out.stdout
+    assert len(lines) == 13 and all(ln.rstrip().endswith("mismatches 0") for ln in lines), out.stdout

@@ -76,6 +76,29 @@ def test_sizes_and_every_select_mask():
     t.close()
 
 
+def test_selection_over_more_than_1024_workgroups():
+    """262 144 + 77 points are 1025 workgroup totals: the smallest count at which the scan of the selection gives a thread more than
+    one total (scan_block_totals, ws_device.h: seg > 1), with a ragged last workgroup."""
+    size, seed = R.RANDOM_MAPS[0]
+    t, cases = upload(size, seed, RES)
+    _, _, _, ring, _, band = cases[0]
+    n = 262144 + 77
+    reps = []
+    while sum(len(p) for p in reps) < n:
+        reps.append(H.window_points(ring.lo, ring.hi, RES, seed=4000 + len(reps)))
+    pts = np.concatenate(reps)[:n]
+    assert len(pts) == n and (n + 255) // 256 == 1025
+    want = H.model(ring, RES, pts, band, True, select=(H.UNKNOWN, H.SURFACE))
+    cls = want[0]["cls"]
+    for part in (cls[:256], cls[262144:]):  # every class in the first and in the last (77-point) workgroup
+        assert len(part) in (256, 77) and all(np.count_nonzero(part == c) > 0 for c in ALL), np.bincount(part, minlength=4)
+    got = t.avg_map().sample(pts.astype(np.int32), band_mm=band, any_weight=True, select=("unknown", "surface"))
+    print(got[1].tolist(), len(got[3]))
+    assert len(want[3]) == int(want[1][H.UNKNOWN] + want[1][H.SURFACE]) > 1024
+    assert H.same(got, want)
+    t.close()
+
+
 # ------------------------------------------------------------------------------------------------ 3: rotated rings, even sizes
 def test_rotated_rings_after_the_shift_sequence():
     W, tm, lm = M.make_maps((21, 17, 13), seed=5)
