@@ -392,6 +392,53 @@ int ws_map_distance_download(ws_map *map, uint32_t *host, size_t capacity, size_
  * line passes of the last call (under WS_DISTANCE_COLUMNS: pass 0, the x pass, the y pass, 0) */
 int ws_debug_distance_timing(ws_map *map, int32_t enable, float ms_out[4]);
 
+/* Frontier of a device map: where the known world ends.  The update writes observed free space explicitly (weight > 0, value = tau);
+ * a voxel no ray reached keeps weight 0.  The frontier of a box is the set of its observed-free voxels that touch a never-observed
+ * voxel of the box, and with WS_FRONTIER_CLUSTERS its connected patches with size, bounding box and coordinate sum -- a planner
+ * consumes goals, not voxels.  Integers only; the same bytes on every run.
+ *   box: inclusive world voxels [lo, hi] under the rules of ws_map_surface (both NULL: the whole window, each ring cell once; outside
+ *     the window, hi < lo or more voxels than the ring holds along an axis: WS_ERR_INVALID).
+ *   classes of a voxel, from its entry's two int16: VALID iff weight > 0; with WS_FRONTIER_ANY_WEIGHT iff weight != 0 (as
+ *     WS_DISTANCE_ANY_WEIGHT).  FREE iff valid and value >= min_value.  UNKNOWN iff not valid.
+ *   min_value: 0 means any non-negative value, the FREE of ws_map_distance; the map's tau keeps the frontier a truncation distance
+ *     away from surfaces (only the free-space candidates carry value = tau).  min_value < 0 or > 32767: WS_ERR_RANGE.
+ *   frontier voxel: a voxel v of the box that is FREE and has at least one of its six face neighbours INSIDE THE BOX UNKNOWN.  A
+ *     neighbour outside the box is ignored: it is neither known nor unknown, and the rim of a box is not a frontier because of the
+ *     rim.  As with ws_map_distance, the result of a box is NOT the restriction of a larger box's result to it.
+ *   record, 16 bytes: int32 x, y, z in world voxels, then uint32 mask: bits 0..5 are set for an UNKNOWN neighbour at -x, +x, -y, +y,
+ *     -z, +z, the other bits are 0.  Records come in ascending world (x, y, z), z fastest, the order of ws_map_surface.
+ *   WS_FRONTIER_CLUSTERS adds two arrays.  Two frontier voxels are connected if they differ by at most 1 on every axis (the
+ *     26-neighbourhood); a cluster is a connected component of the records OF THIS CALL.  Clusters are numbered 0 .. K - 1 by the
+ *     record index of their first member, ascending: record 0 is in cluster 0.  labels: one uint32 per record, in record order, the
+ *     number of its cluster.  cluster table, K rows of 64 bytes: uint32 first (record index of the first member), uint32 count,
+ *     int32 lo[3], int32 hi[3] (the bounding box in world voxels), int64 sum[3] at offset 32 (the sum of the members' coordinates:
+ *     |coordinate| < 2^31 and count < 2^31, it cannot overflow), 8 zero bytes.  With this flag more than 2^31 - 1 records is
+ *     WS_ERR_RANGE and leaves an empty result.  No size filter runs on the device: the table is small, callers filter it.
+ *   errors: unknown flag bits, bad `which`, exactly one NULL box pointer: WS_ERR_INVALID.  On a refusal nothing is launched and the
+ *     last result stays.  Zero records is WS_OK with NULL device pointers.
+ * Synchronises (*n_out and *n_clusters, either may be NULL, receive the numbers of records and of clusters; without the flag
+ * *n_clusters = 0).  The buffers belong to the map, grow on demand and stay valid until the next ws_map_frontier on it; they are apart
+ * from those of every other query, none of which invalidates this result.  Every output write is bounded by the buffers' capacities.
+ * Read-only on the maps; calls that use the buffers are serialised inside the library.  Nothing is allocated before the first call;
+ * an allocation that fails returns WS_ERR_HIP and leaves the map usable.
+ * The implementation: the count / scan / emit compaction of ws_map_surface with a 7-point stencil, then a union-find over the sorted
+ * records (neighbours by binary search, hooks by compare-and-swap of the larger root under the smaller, so the root of a component is
+ * its smallest record index whatever the order of execution), an ordered scan of the roots and integer atomics for the table. */
+#define WS_FRONTIER_DEFAULT 0u
+#define WS_FRONTIER_ANY_WEIGHT 1u
+#define WS_FRONTIER_CLUSTERS 2u
+int ws_map_frontier(ws_map *map, int which, const int32_t lo[3], const int32_t hi[3], int32_t min_value, uint32_t flags, size_t *n_out, size_t *n_clusters);
+const void *ws_map_frontier_records_dev(const ws_map *map, size_t *n);     /* device memory, n x 16 bytes; NULL when n == 0 */
+const uint32_t *ws_map_frontier_labels_dev(const ws_map *map, size_t *n);  /* n uint32; NULL unless the last call asked for clusters */
+const void *ws_map_frontier_clusters_dev(const ws_map *map, size_t *n);    /* n x 64 bytes; NULL unless the last call asked for them */
+/* copies at most cap_records records (and labels) and cap_clusters rows (prefixes) and always reports the totals; any host pointer
+ * may be NULL, and so may n_clusters.  Asking for labels or rows that the last call did not produce: WS_ERR_INVALID */
+int ws_map_frontier_download(ws_map *map, void *records_host, uint32_t *labels_host, void *clusters_host, size_t cap_records, size_t cap_clusters, size_t *n_out,
+                             size_t *n_clusters);
+/* Measurement entry, as ws_debug_surface_timing: ms_out receives the device time of the count pass, the scan, the emit pass and the
+ * clustering of the last call (the clustering spans one host read, of the number of clusters; 0 without WS_FRONTIER_CLUSTERS) */
+int ws_debug_frontier_timing(ws_map *map, int32_t enable, float ms_out[4]);
+
 /* ------------------------------------------------------------------ the global map in device memory ---- */
 /* ws_store: the device twin of HDF5GlobalMap (src/map/hdf5_global_map.cpp) -- a pool of 64^3-voxel chunks in HBM, so that a map shift
  * is a device-to-device copy in stream order: the leaving slabs, the window move and the entering slabs with revisits and corners,
@@ -631,6 +678,37 @@ int ws_store_distance_download(ws_store *st, uint32_t *host, size_t capacity, si
  * upload lies in front of it) and of the x, y and z line passes of the last call (under WS_DISTANCE_COLUMNS: pass 0, the x pass, the
  * y pass, 0) */
 int ws_debug_store_distance_timing(ws_store *st, int32_t enable, float ms_out[4]);
+
+/* The frontier of the store: ws_map_frontier over the chunks of the global map, wherever they lie -- what the whole run has not
+ * covered yet, not what the window has not -- on the device, without a chunk leaving HBM.
+ *   field: a voxel of a present chunk holds that chunk's entry.  A voxel of an absent chunk inside the box is UNKNOWN whatever
+ *     fill_entry is, as in ws_store_distance; it is never FREE.
+ *   rules: everything else is word for word the rule set of ws_map_frontier applied to that field: the classes and
+ *     WS_FRONTIER_ANY_WEIGHT, min_value (a raw value: the store needs neither tau nor the resolution), the frontier voxel with its
+ *     neighbours inside the box only, the record, the order across chunk borders, WS_FRONTIER_CLUSTERS with labels, numbering, table
+ *     and the 2^31 - 1 limit.
+ *   box: the rules of ws_store_surface: inclusive world voxels [lo, hi] anywhere in int32, both NULL: the bounding box of the present
+ *     chunks; exactly one NULL or hi < lo: WS_ERR_INVALID; 2^19 or more present chunks in the box: WS_ERR_RANGE.  The faces of the
+ *     bounding box are the rim of the box and therefore no frontier: a caller who wants the outer faces of the mapped volume as
+ *     frontier passes a box ONE VOXEL LARGER than the bounding box on every side (the voxels of that shell lie in absent chunks or
+ *     hold whatever the chunks hold).  An empty store, or a box that meets no present chunk, is WS_OK with zero records.
+ *   consequence: if a window holds the same voxels as the store inside a box, ws_map_frontier on that window and box returns the same
+ *     bytes: records, labels and table.  What ws_store_load_box writes for an absent chunk must be UNKNOWN as well: a fill_entry of
+ *     weight 0.
+ *   errors, ordering, result buffers: those of ws_store_surface.  On a refusal nothing is launched and the last result stays; the
+ *     call synchronises; the buffers belong to the store, stay valid until the next ws_store_frontier and are apart from those of
+ *     every other query.  Every output write is bounded by the buffers' capacities.
+ *   cost: scratch, tables and work of the extraction follow the number of present chunks the box overlaps (32 KB of scratch and 56
+ *     bytes of tables per chunk), never the volume of the box; the clustering follows the records (8 bytes each). */
+int ws_store_frontier(ws_store *st, const int32_t lo[3], const int32_t hi[3], int32_t min_value, uint32_t flags, size_t *n_out, size_t *n_clusters);
+const void *ws_store_frontier_records_dev(const ws_store *st, size_t *n);    /* device memory, n x 16 bytes; NULL when n == 0 */
+const uint32_t *ws_store_frontier_labels_dev(const ws_store *st, size_t *n); /* n uint32; NULL unless the last call asked for clusters */
+const void *ws_store_frontier_clusters_dev(const ws_store *st, size_t *n);   /* n x 64 bytes; NULL unless the last call asked for them */
+/* as ws_map_frontier_download */
+int ws_store_frontier_download(ws_store *st, void *records_host, uint32_t *labels_host, void *clusters_host, size_t cap_records, size_t cap_clusters, size_t *n_out,
+                               size_t *n_clusters);
+/* Measurement entry, as ws_debug_frontier_timing (the chunk tables' upload lies in front of the count pass) */
+int ws_debug_store_frontier_timing(ws_store *st, int32_t enable, float ms_out[4]);
 
 /* ------------------------------------------------------------------ TSDF update ---- */
 /* TSDFCuda::update_tsdf(scan_points, scanner_pos, up) — update_tsdf.cu:143-166.

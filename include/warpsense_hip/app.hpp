@@ -323,6 +323,11 @@ public:
   {
     return global_map_distance(store_, max_dist_vox, unknown_occupied, columns, any_weight, lo, hi);
   }
+  // where the chunks' known world ends (visualization.hpp, ws_store_frontier)
+  Frontier frontier(bool clusters = true, int32_t min_value = 0, bool any_weight = false, const rm::Pointi *lo = nullptr, const rm::Pointi *hi = nullptr)
+  {
+    return global_map_frontier(store_, clusters, min_value, any_weight, lo, hi);
+  }
   // what the chunks say at given points (visualization.hpp, ws_store_sample)
   PointSample sample(int resolution, const std::vector<rm::Pointi> &points, int32_t band_mm, bool any_weight = false, bool with_gradient = false, uint32_t select = 0,
                      const rm::Pointi *lo = nullptr, const rm::Pointi *hi = nullptr)
@@ -345,6 +350,13 @@ inline SurfaceCloud global_map_cloud(DeviceGlobalMap &g, int tau, int resolution
                                      int band = 0)
 {
   return global_map_cloud(g.handle(), tau, resolution, marker, lo, hi, band);
+}
+
+// the frontier of the device global map (visualization.hpp, ws_store_frontier)
+inline Frontier global_map_frontier(DeviceGlobalMap &g, bool clusters = true, int32_t min_value = 0, bool any_weight = false, const rm::Pointi *lo = nullptr,
+                                    const rm::Pointi *hi = nullptr)
+{
+  return global_map_frontier(g.handle(), clusters, min_value, any_weight, lo, hi);
 }
 
 // the mesh of the device global map (visualization.hpp, ws_store_mesh)
@@ -702,6 +714,32 @@ public:
     local_map_.window(wlo, whi);
     WS_CHECK(ws_store_save_box(device_global_map_->handle(), gpu_.tsdf().handle(), WS_MAP_AVG, &wlo.x, &whi.x));
     return device_global_map_->distance(max_dist_vox, unknown_occupied, columns, any_weight, lo, hi);
+  }
+  // Where the window's known free space ends (local_map_frontier on the averaged map)
+  Frontier frontier(bool clusters = true, int32_t min_value = 0, bool any_weight = false, const rm::Pointi *lo = nullptr, const rm::Pointi *hi = nullptr)
+  {
+    return local_map_frontier(gpu_.tsdf(), WS_MAP_AVG, clusters, min_value, any_weight, lo, hi);
+  }
+  // The frontier of everything the run has seen: the window into the device chunks, as global_mesh does, then the frontier of the
+  // store.  Without a box: the bounding box of the chunks grown by one voxel on every side (cut to int32), so that the outer faces of
+  // the mapped volume are frontier too
+  Frontier global_frontier(bool clusters = true, int32_t min_value = 0, bool any_weight = false, const rm::Pointi *lo = nullptr, const rm::Pointi *hi = nullptr)
+  {
+    if (!device_global_map_) throw std::logic_error("global_frontier: no DeviceGlobalMap attached");
+    wait_shift();
+    rm::Pointi wlo, whi;
+    local_map_.window(wlo, whi);
+    WS_CHECK(ws_store_save_box(device_global_map_->handle(), gpu_.tsdf().handle(), WS_MAP_AVG, &wlo.x, &whi.x));
+    if (lo || hi) return device_global_map_->frontier(clusters, min_value, any_weight, lo, hi);
+    const std::vector<DeviceGlobalMap::Key> keys = device_global_map_->keys();
+    if (keys.empty()) return device_global_map_->frontier(clusters, min_value, any_weight);
+    int64_t a[3] = {INT64_MAX, INT64_MAX, INT64_MAX}, b[3] = {INT64_MIN, INT64_MIN, INT64_MIN};
+    for (const DeviceGlobalMap::Key &c : keys)
+      for (int k = 0; k < 3; ++k) a[k] = std::min<int64_t>(a[k], c[k]), b[k] = std::max<int64_t>(b[k], c[k]);
+    const int64_t cs = GlobalMap::CHUNK_SIZE;
+    const auto cut = [](int64_t v) { return (int32_t)std::min<int64_t>(std::max<int64_t>(v, INT32_MIN), INT32_MAX); };
+    const rm::Pointi glo(cut(a[0] * cs - 1), cut(a[1] * cs - 1), cut(a[2] * cs - 1)), ghi(cut((b[0] + 1) * cs), cut((b[1] + 1) * cs), cut((b[2] + 1) * cs));
+    return device_global_map_->frontier(clusters, min_value, any_weight, &glo, &ghi);
   }
   // the reference's route, kept for comparison: whole window to the host array of the local map
   void download() { gpu_.tsdf().avg_map().to_host(view_); }

@@ -9,6 +9,7 @@
 //   local_map_sample / global_map_sample   (no counterpart)                                   what the map says at given points, over ws_map_sample / ws_store_sample
 //   local_map_distance   (no counterpart: the reference has no distance field)                   a cost map, over ws_map_distance
 //   global_map_distance  (no counterpart)                                                     the cost map of the whole run, over ws_store_distance
+//   local_map_frontier / global_map_frontier   (no counterpart)                               where the known world ends, over ws_map_frontier / ws_store_frontier
 //   local_map_skeleton   publish_local_map_skeleton  map.h:175-227   the 24 end points of the window's line list (host only)
 //
 // The reference walks every voxel of a host map (after a whole-map download for the CUDA map, test/pcd2tsdf.cpp:134-137); here
@@ -67,6 +68,63 @@ inline SurfaceCloud global_map_cloud(ws_store *store, int tau, int resolution, b
   if (marker) out.marker.resize(n * 7);
   size_t got = 0;
   WS_CHECK(ws_store_surface_download(store, n ? out.records.data() : nullptr, n && marker ? out.marker.data() : nullptr, n, &got));
+  return out;
+}
+
+struct FrontierRecord // one record of ws_map_frontier
+{
+  int32_t x, y, z; // world voxels
+  uint32_t mask;   // bits 0..5: an UNKNOWN neighbour at -x +x -y +y -z +z
+};
+struct FrontierCluster // one row of its cluster table
+{
+  uint32_t first, count; // record index of the first member, members
+  int32_t lo[3], hi[3];  // the bounding box in world voxels
+  int64_t sum[3];        // the sum of the members' coordinates
+  uint64_t pad;
+};
+static_assert(sizeof(FrontierRecord) == 16 && sizeof(FrontierCluster) == 64, "ws_map_frontier writes 16-byte records and 64-byte rows");
+
+struct Frontier
+{
+  std::vector<FrontierRecord> records;   // ascending world (x, y, z), z fastest
+  std::vector<uint32_t> labels;          // the cluster number of every record; empty unless asked for
+  std::vector<FrontierCluster> clusters; // numbered by their first record; empty unless asked for
+};
+
+// The frontier of `which` (the rules: warpsense_hip.h at ws_map_frontier) inside the inclusive world-voxel box [lo, hi] (both nullptr:
+// the whole window): the voxels that are observed free (value >= min_value; 0: any non-negative value) and touch a never-observed
+// voxel of the box; with `clusters` their 26-connected patches as labels and a table.
+inline Frontier local_map_frontier(cuda::TSDFCuda &tsdf, int which = WS_MAP_AVG, bool clusters = true, int32_t min_value = 0, bool any_weight = false,
+                                   const rmagine::Pointi *lo = nullptr, const rmagine::Pointi *hi = nullptr)
+{
+  Frontier out;
+  size_t n = 0, k = 0;
+  const uint32_t flags = (any_weight ? WS_FRONTIER_ANY_WEIGHT : 0u) | (clusters ? WS_FRONTIER_CLUSTERS : 0u);
+  WS_CHECK(ws_map_frontier(tsdf.handle(), which, lo ? &lo->x : nullptr, hi ? &hi->x : nullptr, min_value, flags, &n, &k));
+  out.records.resize(n);
+  if (clusters) out.labels.resize(n), out.clusters.resize(k);
+  size_t got = 0, got_k = 0;
+  WS_CHECK(ws_map_frontier_download(tsdf.handle(), n ? out.records.data() : nullptr, n && clusters ? out.labels.data() : nullptr,
+                                    k && clusters ? out.clusters.data() : nullptr, n, k, &got, &got_k));
+  return out;
+}
+
+// The frontier of the global map in device memory (the rules: warpsense_hip.h at ws_store_frontier) inside the inclusive world-voxel
+// box [lo, hi] (both nullptr: the bounding box of the present chunks, whose faces are no frontier: pass a box one voxel larger to get the
+// outer faces of the mapped volume).  Voxels of absent chunks are unknown.  (app.hpp adds the overload that takes a DeviceGlobalMap.)
+inline Frontier global_map_frontier(ws_store *store, bool clusters = true, int32_t min_value = 0, bool any_weight = false, const rmagine::Pointi *lo = nullptr,
+                                    const rmagine::Pointi *hi = nullptr)
+{
+  Frontier out;
+  size_t n = 0, k = 0;
+  const uint32_t flags = (any_weight ? WS_FRONTIER_ANY_WEIGHT : 0u) | (clusters ? WS_FRONTIER_CLUSTERS : 0u);
+  WS_CHECK(ws_store_frontier(store, lo ? &lo->x : nullptr, hi ? &hi->x : nullptr, min_value, flags, &n, &k));
+  out.records.resize(n);
+  if (clusters) out.labels.resize(n), out.clusters.resize(k);
+  size_t got = 0, got_k = 0;
+  WS_CHECK(ws_store_frontier_download(store, n ? out.records.data() : nullptr, n && clusters ? out.labels.data() : nullptr,
+                                      k && clusters ? out.clusters.data() : nullptr, n, k, &got, &got_k));
   return out;
 }
 

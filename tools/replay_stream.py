@@ -4,7 +4,7 @@ sliding TSDF map @ 5 cm, one MI355X): sensor clouds in float metres -> device pr
 
     python tools/replay_stream.py --map 1024 --scans 30 [--h5 /tmp/stream.h5] [--async-shift | --device-global-map] [--surface-ply DIR [--surface-every N]] [--mesh-ply DIR]
                                    [--raycast-ply DIR] [--distance-npy DIR [--distance-m M]] [--global-distance-npy FILE [--global-distance-m M]]
-                                   [--moving-sweeps] [--deskew]
+                                   [--moving-sweeps] [--deskew] [--frontier-ply DIR] [--global-frontier-ply FILE]
 
 Prints one JSON line: scans/s over the stream and the mean per-stage times (the reference's RuntimeEvaluator
 forms "preprocess", "tsdf", "registration", "total")."""
@@ -71,6 +71,10 @@ def main():
     ap.add_argument("--global-surface-ply", default=None, metavar="FILE", help="after the last scan: the surface cloud of the WHOLE run, window and every "
                     "chunk that has left it, from the device global map (TSDFMapping.global_surface_cloud, ws_store_surface) as PLY; needs "
                     "--device-global-map")
+    ap.add_argument("--frontier-ply", default=None, metavar="DIR", help="after every TSDF update: the clustered frontier of the window (TSDFMapping.frontier, "
+                    "ws_map_frontier) as binary little-endian PLY (xyz + mask + cluster) into DIR")
+    ap.add_argument("--global-frontier-ply", default=None, metavar="FILE", help="after the last scan: the clustered frontier of the WHOLE run from the device "
+                    "global map (TSDFMapping.global_frontier, ws_store_frontier) as PLY; needs --device-global-map")
     ap.add_argument("--global-raycast-ply", default=None, metavar="FILE", help="after the last scan: the predicted scan from the pose of the FIRST scan, "
                     "which the window has left, through the device global map (TSDFMapping.global_raycast, ws_store_raycast) as PLY, and its hit "
                     "share printed next to that of the window's raycast from the same pose; needs --device-global-map")
@@ -103,6 +107,8 @@ def main():
         ap.error("--global-mesh-ply requires --device-global-map")
     if args.global_surface_ply and not args.device_global_map:
         ap.error("--global-surface-ply requires --device-global-map")
+    if args.global_frontier_ply and not args.device_global_map:
+        ap.error("--global-frontier-ply requires --device-global-map")
     if args.global_raycast_ply and not args.device_global_map:
         ap.error("--global-raycast-ply requires --device-global-map")
     if args.global_distance_npy and not args.device_global_map:
@@ -136,6 +142,10 @@ def main():
     mesh = {"files": 0, "vertices": 0, "faces": 0, "seconds": 0.0}
     if args.surface_ply:
         os.makedirs(args.surface_ply, exist_ok=True)
+    frontier = {"files": 0, "records": 0, "clusters": 0, "seconds": 0.0}
+    if args.frontier_ply:
+        os.makedirs(args.frontier_ply, exist_ok=True)
+    updates_seen = 0
     if args.mesh_ply:
         os.makedirs(args.mesh_ply, exist_ok=True)
     raycast = {"files": 0, "hits": 0, "median_abs_residual_mm": [], "seconds": 0.0}
@@ -156,6 +166,14 @@ def main():
             kidnap = relocalize_after_kidnap(app, c, args, np.array([1000.0 * args.step * k, 500.0 * args.step * k, 0.0]))
         app.cloud_callback(c)
         busy += time.perf_counter() - tb
+        if args.frontier_ply and app.n_updates > updates_seen:  # after every update of the map
+            ts = time.perf_counter()
+            rec, labels, table = app.gpu_.frontier(clusters=True)
+            frontier["records"] = W.write_frontier_ply(os.path.join(args.frontier_ply, f"frontier_{k + 1:05d}.ply"), rec, args.res, labels)
+            frontier["clusters"] = int(len(table))
+            frontier["files"] += 1
+            frontier["seconds"] += time.perf_counter() - ts
+        updates_seen = app.n_updates
         if args.surface_ply and (k + 1) % max(args.surface_every, 1) == 0:
             ts = time.perf_counter()
             _, marker = app.gpu_.surface_cloud(marker=True)
@@ -207,6 +225,18 @@ def main():
         global_surface = {"file": args.global_surface_ply, "points": int(points), "chunks": app.gpu_.device_global_map_.count(), "call_s": tg}
         print(f"global surface: {points} points from {global_surface['chunks']} chunks in {1000.0 * tg:.2f} ms (save_box + ws_store_surface + download)",
               file=sys.stderr)
+    global_frontier = None
+    if args.global_frontier_ply:
+        tg = time.perf_counter()
+        rec, labels, table = app.gpu_.global_frontier(clusters=True)
+        tg = time.perf_counter() - tg
+        os.makedirs(os.path.dirname(os.path.abspath(args.global_frontier_ply)), exist_ok=True)
+        W.write_frontier_ply(args.global_frontier_ply, rec, args.res, labels)
+        goals = W.frontier_goals(table, args.res, min_size=10)
+        global_frontier = {"file": args.global_frontier_ply, "records": int(len(rec)), "clusters": int(len(table)), "clusters_of_10_or_more": int(len(goals[1])),
+                           "chunks": app.gpu_.device_global_map_.count(), "call_s": tg}
+        print(f"global frontier: {len(rec)} records in {len(table)} clusters from {global_frontier['chunks']} chunks in {1000.0 * tg:.2f} ms "
+              "(save_box + ws_store_frontier + download)", file=sys.stderr)
     global_distance = None
     if args.global_distance_npy:
         tg = time.perf_counter()
@@ -266,6 +296,8 @@ def main():
                       "mesh_ply": mesh if args.mesh_ply else None,
                       "global_mesh_ply": global_mesh,
                       "global_surface_ply": global_surface,
+                      "frontier_ply": frontier if args.frontier_ply else None,
+                      "global_frontier_ply": global_frontier,
                       "global_raycast_ply": global_raycast,
                       "global_distance_npy": global_distance,
                       "raycast_ply": raycast if args.raycast_ply else None,

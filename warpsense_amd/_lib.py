@@ -45,6 +45,10 @@ EXPORTS = [
     "ws_store_sample_download", "ws_debug_store_sample_timing",
     "ws_store_raycast", "ws_store_raycast_dev", "ws_store_raycast_records_dev", "ws_store_raycast_gradient_dev", "ws_store_raycast_download",
     "ws_debug_store_raycast_timing", "ws_debug_store_raycast_table", "ws_debug_store_raycast_find",
+    "ws_map_frontier", "ws_map_frontier_records_dev", "ws_map_frontier_labels_dev", "ws_map_frontier_clusters_dev", "ws_map_frontier_download",
+    "ws_debug_frontier_timing",
+    "ws_store_frontier", "ws_store_frontier_records_dev", "ws_store_frontier_labels_dev", "ws_store_frontier_clusters_dev", "ws_store_frontier_download",
+    "ws_debug_store_frontier_timing",
 ]
 WS_SURFACE_RECORDS, WS_SURFACE_MARKER = 0, 1
 WS_MESH_DEFAULT, WS_MESH_ANY_WEIGHT = 0, 1
@@ -53,6 +57,7 @@ WS_SAMPLE_DEFAULT, WS_SAMPLE_ANY_WEIGHT, WS_SAMPLE_GRADIENT = 0, 1, 2
 WS_SAMPLE_SELECT_UNKNOWN, WS_SAMPLE_SELECT_FREE, WS_SAMPLE_SELECT_SURFACE, WS_SAMPLE_SELECT_INSIDE = 4, 8, 16, 32
 SAMPLE_CLASSES = ("unknown", "free", "surface", "inside")  # class c of a sample record; WS_SAMPLE_SELECT_* is 4 << c
 WS_DISTANCE_DEFAULT, WS_DISTANCE_ANY_WEIGHT, WS_DISTANCE_UNKNOWN_OCCUPIED, WS_DISTANCE_COLUMNS = 0, 1, 2, 4
+WS_FRONTIER_DEFAULT, WS_FRONTIER_ANY_WEIGHT, WS_FRONTIER_CLUSTERS = 0, 1, 2
 
 
 class WsError(RuntimeError):
@@ -194,6 +199,15 @@ def load() -> C.CDLL:
     L.ws_map_distance_dev.restype = vp
     L.ws_map_distance_download.argtypes = [vp, vp, sz, P(sz)]
     L.ws_debug_distance_timing.argtypes = [vp, i32, vp]
+    L.ws_map_frontier.argtypes = [vp, C.c_int, vp, vp, i32, u32, P(sz), P(sz)]
+    L.ws_store_frontier.argtypes = [vp, vp, vp, i32, u32, P(sz), P(sz)]
+    for owner in ("map", "store"):
+        for part in ("records", "labels", "clusters"):
+            f = getattr(L, f"ws_{owner}_frontier_{part}_dev")
+            f.argtypes, f.restype = [vp, P(sz)], vp
+        getattr(L, f"ws_{owner}_frontier_download").argtypes = [vp, vp, vp, vp, sz, sz, P(sz), P(sz)]
+    L.ws_debug_frontier_timing.argtypes = [vp, i32, vp]
+    L.ws_debug_store_frontier_timing.argtypes = [vp, i32, vp]
     L.ws_shift_plan.argtypes = [vp, vp, vp, vp, P(ShiftPlan)]
     L.ws_shift_begin.argtypes = [vp, vp, u32, P(vp)]
     L.ws_shift_count.argtypes = [vp]

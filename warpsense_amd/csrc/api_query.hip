@@ -373,3 +373,92 @@ int ws_debug_distance_timing(ws_map *m, int32_t enable, float ms_out[4])
   std::lock_guard<std::mutex> lock(m->dist.mu);
   return query_timing(m->ctx->stream, m->dist.timer, enable, ms_out, DIST_PAIRS, 4);
 }
+
+// ---- frontier: what the host core of ws_api.h (frontier_run) needs beside it, for the window of a map here and for the chunks of the
+// store in api_store.hip
+int ws::frontier_check(const char *name, bool bad, const int32_t *lo, const int32_t *hi, int32_t min_value, uint32_t flags)
+{
+  const uint32_t known = WS_FRONTIER_ANY_WEIGHT | WS_FRONTIER_CLUSTERS;
+  if (bad || (flags & ~known) || ((lo == nullptr) != (hi == nullptr))) return invalid(std::string(name) + ": bad argument");
+  if (min_value < 0 || min_value > 32767) return range_error(name, ": min_value must be 0 .. 32767 (a raw int16 value; 0: any non-negative value)");
+  return WS_OK;
+}
+
+int ws::frontier_publish(FrontierResult &q, size_t n, size_t k, bool clusters, size_t *n_out, size_t *n_clusters)
+{
+  q.n = n, q.n_clusters = k, q.has_clusters = clusters;
+  if (n_out) *n_out = n;
+  if (n_clusters) *n_clusters = k;
+  return WS_OK;
+}
+
+const uint32_t *ws::frontier_labels_dev(const FrontierResult *q, size_t *n)
+{
+  const bool have = q && q->has_clusters && q->n;
+  if (n) *n = have ? q->n : 0;
+  return have ? static_cast<const uint32_t *>(q->labels.p) : nullptr;
+}
+
+const void *ws::frontier_clusters_dev(const FrontierResult *q, size_t *n)
+{
+  const bool have = q && q->has_clusters && q->n_clusters;
+  if (n) *n = have ? q->n_clusters : 0;
+  return have ? q->clusters.p : nullptr;
+}
+
+// `name`, `call`: the download entry point, and the entry point whose flag it misses
+int ws::frontier_download(const FrontierResult &q, hipStream_t s, const char *name, const char *call, void *records_host, uint32_t *labels_host, void *clusters_host,
+                          size_t cap_records, size_t cap_clusters, size_t *n_out, size_t *n_clusters)
+{
+  *n_out = q.n;
+  if (n_clusters) *n_clusters = q.n_clusters;
+  if (q.n && !q.has_clusters && ((labels_host && cap_records) || (clusters_host && cap_clusters)))
+    return invalid(std::string(name) + ": the last " + call + " did not ask for WS_FRONTIER_CLUSTERS");
+  const size_t k = std::min(cap_records, q.n), kc = clusters_host ? std::min(cap_clusters, q.n_clusters) : 0;
+  if (k && records_host) WS_HIP(hipMemcpyAsync(records_host, q.rec.p, k * 16, hipMemcpyDeviceToHost, s));
+  if (k && labels_host) WS_HIP(hipMemcpyAsync(labels_host, q.labels.p, k * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  if (kc) WS_HIP(hipMemcpyAsync(clusters_host, q.clusters.p, kc * 64, hipMemcpyDeviceToHost, s));
+  if (k || kc) WS_HIP(hipStreamSynchronize(s));
+  return WS_OK;
+}
+
+// ---- frontier: the observed-free voxels of a box that touch a never-observed one, and their clusters, map_frontier.hip (the rules are
+// stated in warpsense_hip.h)
+int ws_map_frontier(ws_map *m, int which, const int32_t lo[3], const int32_t hi[3], int32_t min_value, uint32_t flags, size_t *n_out, size_t *n_clusters)
+{
+  WS_TRY(frontier_check("ws_map_frontier", !m || (which != WS_MAP_AVG && which != WS_MAP_NEW), lo, hi, min_value, flags));
+  WS_SETTLE(m);
+  std::lock_guard<std::mutex> lock(m->frontier.mu);
+  ws_map::Frontier &q = m->frontier;
+  int32_t l[3], ext[3];
+  WS_TRY(resolve_box(m, which, lo, hi, true, "ws_map_frontier", l, ext));
+  WS_TRY(q.timer.arm());
+  const size_t n_cols = (size_t)ext[0] * (size_t)ext[1]; // n_cols < 2^31 (ws_map_create)
+  WS_TRY(frontier_run(
+      q, m->ctx->stream, "ws_map_frontier", surface_blocks_for((int64_t)n_cols), flags, n_out, n_clusters, n_cols > q.col_cnt.cap,
+      [&] { return q.col_cnt.grow(n_cols, sizeof(uint32_t)); }, [&] { return launch_frontier_count(m, which, l, ext, min_value, flags); },
+      [&](size_t cap) { return launch_frontier_emit(m, which, l, ext, min_value, flags, cap); }));
+  return map_take_error(m);
+}
+
+const void *ws_map_frontier_records_dev(const ws_map *m, size_t *n) { return surface_records_dev(m ? &m->frontier : nullptr, n); }
+
+const uint32_t *ws_map_frontier_labels_dev(const ws_map *m, size_t *n) { return frontier_labels_dev(m ? &m->frontier : nullptr, n); }
+
+const void *ws_map_frontier_clusters_dev(const ws_map *m, size_t *n) { return frontier_clusters_dev(m ? &m->frontier : nullptr, n); }
+
+int ws_map_frontier_download(ws_map *m, void *records_host, uint32_t *labels_host, void *clusters_host, size_t cap_records, size_t cap_clusters, size_t *n_out,
+                             size_t *n_clusters)
+{
+  if (!m || !n_out) return invalid("ws_map_frontier_download: NULL argument");
+  std::lock_guard<std::mutex> lock(m->frontier.mu);
+  return frontier_download(m->frontier, m->ctx->stream, "ws_map_frontier_download", "ws_map_frontier", records_host, labels_host, clusters_host, cap_records,
+                           cap_clusters, n_out, n_clusters);
+}
+
+int ws_debug_frontier_timing(ws_map *m, int32_t enable, float ms_out[4])
+{
+  if (!m) return invalid("ws_debug_frontier_timing: map is NULL");
+  std::lock_guard<std::mutex> lock(m->frontier.mu);
+  return query_timing(m->ctx->stream, m->frontier.timer, enable, ms_out, FRONTIER_PAIRS, 4);
+}

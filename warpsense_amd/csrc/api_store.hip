@@ -843,3 +843,75 @@ uint32_t ws_debug_store_raycast_find(const int32_t *table, size_t n_places, cons
   std::memcpy(t.data(), table, n_places * sizeof(StoreRaySlot));
   return store_ray_find(t.data(), (uint32_t)n_places - 1u, key[0], key[1], key[2]);
 }
+
+// ---- the frontier of the store: the rules and the host flow of ws_map_frontier over the chunks, store_frontier.hip
+namespace
+{
+// The tables of a frontier call over the n listed chunks (0 < n < 2^19), into st->frontier.table_host: the word-space tables, and the
+// list positions of every chunk's six face neighbours, -x +x -y +y -z +z
+int store_frontier_tables(ws_store *st, const std::vector<StoreRaySlot> &listed)
+{
+  const size_t n = listed.size();
+  WS_TRY(store_tables_reserve(st, st->frontier.table_host, st->frontier.table_dev, store_frontier_table_bytes(n), store_frontier_table_bytes(n + n / 8)));
+  uint32_t *grp = st->frontier.table_host.as<uint32_t>();
+  uint32_t *nb = grp + 8 * n;
+  store_word_tables(listed, grp);
+  const auto before = [](const StoreRaySlot &e, const StoreKey &k) { return StoreKey{e.cx, e.cy, e.cz} < k; };
+  for (size_t i = 0; i < n; ++i)
+    for (int d = 0; d < 6; ++d)
+    {
+      // (keys are floor(int32 / 64): a step of one cannot overflow)
+      StoreKey k = {listed[i].cx, listed[i].cy, listed[i].cz};
+      k[d >> 1] += (d & 1) ? 1 : -1;
+      const auto it = std::lower_bound(listed.begin(), listed.end(), k, before);
+      const bool found = it != listed.end() && it->cx == k[0] && it->cy == k[1] && it->cz == k[2];
+      nb[6 * i + d] = found ? (uint32_t)(it - listed.begin()) : 0xffffffffu;
+    }
+  return WS_OK;
+}
+} // namespace
+
+int ws_store_frontier(ws_store *st, const int32_t lo[3], const int32_t hi[3], int32_t min_value, uint32_t flags, size_t *n_out, size_t *n_clusters)
+{
+  WS_TRY(frontier_check("ws_store_frontier", !st, lo, hi, min_value, flags));
+  std::unique_lock<std::mutex> lock;
+  StoreFrontierCall c;
+  WS_TRY(store_query_box(st, "ws_store_frontier", lo, hi, false, lock, c.lo, c.hi));
+  ws_store::Frontier &q = st->frontier;
+  std::vector<StoreRaySlot> listed;
+  if (c.lo[0] <= c.hi[0]) store_list(st, c.lo, c.hi, listed); // (else: no box and no chunk)
+  if (listed.size() >= (1u << 19)) return range_error("ws_store_frontier", ": the box overlaps 2^19 present chunks or more (4096 words each must stay below 2^31)");
+  WS_TRY(q.timer.arm());
+  if (listed.empty()) // an empty store, or the box meets no present chunk: nothing in it is free
+    return frontier_publish(q, 0, 0, (flags & WS_FRONTIER_CLUSTERS) != 0, n_out, n_clusters);
+  c.n_chunks = (uint32_t)listed.size();
+  c.min_value = min_value, c.flags = flags;
+  const size_t n_words = (size_t)c.n_chunks * 4096u;
+  WS_TRY(store_frontier_tables(st, listed));
+  return frontier_run(
+      q, st->ctx->stream, "ws_store_frontier", store_surface_blocks(c.n_chunks), flags, n_out, n_clusters, n_words > q.mask.cap,
+      [&] { return q.mask.grow(n_words, sizeof(uint64_t)); }, [&] { return store_enqueued(st, launch_store_frontier_count(st, q, c)); },
+      [&](size_t cap) { return store_enqueued(st, launch_store_frontier_emit(st, q, c, cap)); });
+}
+
+const void *ws_store_frontier_records_dev(const ws_store *st, size_t *n) { return surface_records_dev(st ? &st->frontier : nullptr, n); }
+
+const uint32_t *ws_store_frontier_labels_dev(const ws_store *st, size_t *n) { return frontier_labels_dev(st ? &st->frontier : nullptr, n); }
+
+const void *ws_store_frontier_clusters_dev(const ws_store *st, size_t *n) { return frontier_clusters_dev(st ? &st->frontier : nullptr, n); }
+
+int ws_store_frontier_download(ws_store *st, void *records_host, uint32_t *labels_host, void *clusters_host, size_t cap_records, size_t cap_clusters, size_t *n_out,
+                               size_t *n_clusters)
+{
+  if (!st || !n_out) return invalid("ws_store_frontier_download: NULL argument");
+  std::lock_guard<std::mutex> lock(st->mu);
+  return frontier_download(st->frontier, st->ctx->stream, "ws_store_frontier_download", "ws_store_frontier", records_host, labels_host, clusters_host, cap_records,
+                           cap_clusters, n_out, n_clusters);
+}
+
+int ws_debug_store_frontier_timing(ws_store *st, int32_t enable, float ms_out[4])
+{
+  if (!st) return invalid("ws_debug_store_frontier_timing: store is NULL");
+  std::lock_guard<std::mutex> lock(st->mu);
+  return query_timing(st->ctx->stream, st->frontier.timer, enable, ms_out, FRONTIER_PAIRS, 4);
+}

@@ -74,8 +74,9 @@ constexpr int SURF_PAIRS[3][2] = {{0, 1}, {1, 2}, {3, 4}}, MESH_PAIRS[3][2] = {{
 // The flow of a surface call whose count pass leaves `blocks` workgroup totals, from the scratch to the publish.  own_room: the source
 // has scratch of its own that must grow; grow() grows it (the stream has been synchronised then).  count() enqueues the count pass
 // and the scan, emit(cap) the emit pass, which writes no record at or beyond `cap`; both return at once.
-template <typename Grow, typename Count, typename Emit>
-int surface_run(SurfResult &q, hipStream_t s, size_t blocks, bool marker, size_t *n_out, bool own_room, Grow grow, Count count, Emit emit)
+// sized(total): the caller's word on the counted total before any output is sized from it (a refusal leaves an empty result).
+template <typename Grow, typename Count, typename Emit, typename Sized>
+int surface_run(SurfResult &q, hipStream_t s, size_t blocks, bool marker, size_t *n_out, bool own_room, Grow grow, Count count, Emit emit, Sized sized)
 {
   WS_TRY(q.total.alloc(1));
   if (own_room || blocks > q.blk_tot.cap || blocks > q.blk_off.cap)
@@ -90,6 +91,7 @@ int surface_run(SurfResult &q, hipStream_t s, size_t blocks, bool marker, size_t
   WS_TRY(count());
   WS_HIP(hipStreamSynchronize(s)); // the one host read the call needs: the output is sized from the counted total
   const size_t total = (size_t)*q.total.host;
+  WS_TRY(sized(total));
   WS_TRY(q.rec.grow(total, 16));
   if (marker) WS_TRY(q.marker.grow(total, 7 * sizeof(float)));
   if (total)
@@ -101,6 +103,12 @@ int surface_run(SurfResult &q, hipStream_t s, size_t blocks, bool marker, size_t
   q.has_marker = marker;
   if (n_out) *n_out = total;
   return WS_OK;
+}
+
+template <typename Grow, typename Count, typename Emit>
+int surface_run(SurfResult &q, hipStream_t s, size_t blocks, bool marker, size_t *n_out, bool own_room, Grow grow, Count count, Emit emit)
+{
+  return surface_run(q, s, blocks, marker, n_out, own_room, grow, count, emit, [](size_t) { return (int)WS_OK; });
 }
 
 // The flow of a mesh call over `n_words` words (< 2^31), from "the old result is dropped" to the publish.  count() and emit() enqueue
@@ -290,6 +298,37 @@ int distance_run(DistResult &q, hipStream_t s, const uint32_t ext[3], int32_t R,
   q.n = n;
   if (n_sites) *n_sites = (size_t)*q.sites.host;
   return WS_OK;
+}
+
+// ---- frontier (map_frontier.hip for the window of a map, store_frontier.hip for the chunks of the store): its extraction is the
+// flow of a surface call, its clustering works on the records alone.  frontier_check: the refusals that come before the lock and the
+// box, `bad` as above.  frontier_run: grow(), count() and emit(cap) are those of surface_run.
+int frontier_check(const char *name, bool bad, const int32_t *lo, const int32_t *hi, int32_t min_value, uint32_t flags);
+const uint32_t *frontier_labels_dev(const FrontierResult *q, size_t *n);
+const void *frontier_clusters_dev(const FrontierResult *q, size_t *n);
+int frontier_download(const FrontierResult &q, hipStream_t s, const char *name, const char *call, void *records_host, uint32_t *labels_host, void *clusters_host,
+                      size_t cap_records, size_t cap_clusters, size_t *n_out, size_t *n_clusters);
+int frontier_publish(FrontierResult &q, size_t n, size_t k, bool clusters, size_t *n_out, size_t *n_clusters);
+constexpr int FRONTIER_PAIRS[4][2] = {{0, 1}, {1, 2}, {3, 4}, {4, 5}};
+
+template <typename Grow, typename Count, typename Emit>
+int frontier_run(FrontierResult &q, hipStream_t s, const char *name, size_t blocks, uint32_t flags, size_t *n_out, size_t *n_clusters, bool own_room, Grow grow,
+                 Count count, Emit emit)
+{
+  const bool clusters = (flags & WS_FRONTIER_CLUSTERS) != 0;
+  frontier_publish(q, 0, 0, false, n_out, n_clusters); // (whatever happens from here on, the old result is gone: its buffers may be replaced)
+  WS_TRY(surface_run(q, s, blocks, false, nullptr, own_room, grow, count, emit, [&](size_t total) {
+    // (before the record buffer grows: q.n is 0 here, the refusal leaves an empty result and allocates nothing)
+    if (clusters && total > 0x7fffffffull) return range_error(name, ": more than 2^31 - 1 records under WS_FRONTIER_CLUSTERS");
+    return (int)WS_OK;
+  }));
+  const size_t n = q.n;
+  if (clusters && n)
+  {
+    q.n = 0;
+    WS_TRY(frontier_clusters(q, s, n));
+  }
+  return frontier_publish(q, n, clusters ? q.n_clusters : 0, clusters, n_out, n_clusters);
 }
 
 // ---- map shift: one shift of both maps' windows, for ws_shift_begin (api_map.hip) and ws_shift_device (api_store.hip), which

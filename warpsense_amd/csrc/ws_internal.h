@@ -320,7 +320,7 @@ struct DevCounter
 // events around the launches of a query (ws_debug_*_timing)
 struct QueryTimer
 {
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // (the frontier marks six, the others up to five)
   bool on = false;
   uint32_t marked = 0; // bit i: ev[i] has been recorded since the last arm() / set()
   // the start of a query call: nothing recorded yet, and the events exist if they are wanted
@@ -421,6 +421,18 @@ struct SampleResult
   bool has_grad = false, has_sel = false; // the last call also wrote `grad` / `sel`
   void release() { timer.release(), counts.release(); for (DevBuf *b : {&pts, &rec, &grad, &sel, &blk_tot, &blk_off}) b->release(); }
 };
+// ... and a frontier call (ws_map::Frontier, ws_store::Frontier): its extraction IS a surface call (surface_run in ws_api.h; no marker),
+// and with WS_FRONTIER_CLUSTERS the clustering of the sorted records follows (frontier_clusters, map_frontier.hip)
+struct FrontierResult : SurfResult // timer: 0 count 1 scan 2, 3 emit 4 clustering 5
+{
+  DevBuf parent, labels;               // uint32 [records]: union-find parents, then the heads' numbers; roots, then the labels
+  DevBuf head_tot, head_off;           // uint32 / uint64 [records / 256] cluster heads per workgroup, and their exclusive scan
+  DevCounter heads;                    // the scan's last element: the number of clusters
+  DevBuf clusters;                     // 64-byte rows
+  size_t n_clusters = 0;               // rows of the last call
+  bool has_clusters = false;           // the last call also wrote `labels` and `clusters`
+  void release() { SurfResult::release(), heads.release(); for (DevBuf *b : {&parent, &labels, &head_tot, &head_off, &clusters}) b->release(); }
+};
 
 } // namespace ws
 
@@ -512,6 +524,12 @@ struct ws_map
   {
     std::mutex mu;
   } sample;
+  struct Frontier : ws::FrontierResult // ws_map_frontier (map_frontier.hip)
+  {
+    std::mutex mu;
+    ws::DevBuf col_cnt;                  // uint32 [columns of the box] frontier voxels per (x, y) column
+    void release() { FrontierResult::release(), col_cnt.release(); }
+  } frontier;
   // The scan whose verdict (did its records fit the pool?) has not been looked at yet: ws_tsdf_update* return after the
   // launches, like the reference's update_tsdf (update_tsdf.cu:165); the next call that takes this map settles it first
   // (settle_tsdf: the verdict is in host-mapped memory ~0.35 ms after the launches) and repeats the scan if it was aborted.
@@ -542,7 +560,7 @@ struct ws_map
                           &tile_list, &rec, &big_keys, &block_stats, &counters, &box_stage, &shift_stage_dev})
       b->release();
     for (ws::HostBlock *b : {&counters_host, &status, &shift_stage_host}) b->release();
-    surf.release(), mesh.release(), ray.release(), dist.release(), sample.release();
+    surf.release(), mesh.release(), ray.release(), dist.release(), sample.release(), frontier.release();
   }
 };
 
@@ -690,8 +708,16 @@ struct ws_store
     ws::DevBuf table_dev;                // ... and the copy the kernels read
     void release() { SampleResult::release(), table_host.release(), table_dev.release(); }
   } sample;
+  struct Frontier : ws::FrontierResult // ws_store_frontier (store_frontier.hip)
+  {
+    ws::DevBuf mask;                     // uint64 [4096 per listed chunk] the frontier voxels of a word, bit = z
+    ws::HostBlock table_host;            // bytes, pinned: the call's chunk tables (store_frontier_table_bytes); free again when the call returns, which synchronises
+    ws::DevBuf table_dev;                // ... and the copy the kernels read
+    void release() { FrontierResult::release(), mask.release(), table_host.release(), table_dev.release(); }
+  } frontier;
   void release()
   {
+    frontier.release();
     surf.release();
     mesh.release();
     ray.release();
@@ -808,6 +834,26 @@ struct StoreSurfCall
 size_t store_surface_blocks(uint32_t n_chunks); // workgroups of the emit pass: entries of blk_tot and blk_off
 int launch_store_surface_count(ws_store *st, ws_store::Surface &q, const StoreSurfCall &c);
 int launch_store_surface_emit(ws_store *st, ws_store::Surface &q, const StoreSurfCall &c, bool marker, size_t cap);
+
+// map_frontier.hip: the passes of map_surface.hip with the 7-point rule of ws_frontier.h (count + scan, the total arrives in
+// q.total.host after a stream synchronise; then the emit pass, which writes no record at or beyond `cap`), and the clustering of the
+// n sorted records in q.rec of a window or of the store: labels and cluster table (it synchronises once in between, for the number of
+// clusters, and marks events 4 and 5)
+int launch_frontier_count(ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], int32_t min_value, uint32_t flags);
+int launch_frontier_emit(ws_map *m, int which, const int32_t lo[3], const int32_t ext[3], int32_t min_value, uint32_t flags, size_t cap);
+int frontier_clusters(FrontierResult &q, hipStream_t s, size_t n);
+// store_frontier.hip: the same over the chunks the call lists.  The host has written the two word-space tables of `n_chunks` listed
+// chunks and the list positions of every chunk's six face neighbours (store_frontier_table_bytes) into q.table_host
+struct StoreFrontierCall
+{
+  uint32_t n_chunks;    // 0 < n_chunks < 2^19: 4096 words each
+  int32_t min_value;
+  uint32_t flags;
+  int32_t lo[3], hi[3]; // the box, inclusive world voxels
+};
+inline size_t store_frontier_table_bytes(size_t n_chunks) { return store_word_table_bytes(n_chunks) + n_chunks * 6 * sizeof(uint32_t); }
+int launch_store_frontier_count(ws_store *st, ws_store::Frontier &q, const StoreFrontierCall &c);
+int launch_store_frontier_emit(ws_store *st, ws_store::Frontier &q, const StoreFrontierCall &c, size_t cap);
 
 // store_raycast.hip: the march of ws_raycast.h over the chunks the call lists.  The kernels find a chunk through an open-addressing
 // table key -> slot of a power-of-two size >= 2 x listed chunks (linear probing from store_ray_hash; an empty place has slot

@@ -11,7 +11,7 @@ from ._abi import _i3, _i3c, _is_device, _ptr, pack_entry, unpack_entry
 from ._lib import WS_MAP_AVG, WS_MAP_NEW, check
 from .context import Context
 from .global_map import GlobalMap
-from .queries import _distance_call, _mesh_call, _raycast_call, _sample_call, _surface_call
+from .queries import _distance_call, _frontier_call, _mesh_call, _raycast_call, _sample_call, _surface_call, _timing
 
 
 class DeviceMap:
@@ -248,6 +248,24 @@ class DeviceMapMemWrapper:
         rec, self.last_sites = _distance_call(self._t._L, "ws_map_distance", self._t, (self._which,), lo, hi, max_dist_vox, unknown_occupied, columns,
                                               any_weight, device, window_shape)
         return rec
+
+    def frontier(self, lo=None, hi=None, min_value=0, any_weight=False, clusters=False, device=False):
+        """The frontier of this map on the device (ws_map_frontier; the rules are stated in include/warpsense_hip.h): the voxels of
+        the inclusive world-voxel box [lo, hi] (both None: the whole window) that are observed free (weight > 0, value >=
+        min_value) and touch a never-observed voxel of the box, in ascending world (x, y, z), z fastest.  min_value: 0 for any
+        non-negative value, the map's tau to stay a truncation distance away from surfaces.  any_weight: voxels with a negative
+        weight count as observed too.  clusters: also the 26-connected patches of the records.
+
+        Returns the records as a numpy array of dtype FRONTIER_RECORD (x, y, z in world voxels, mask of unknown neighbours); with
+        `clusters` a triple (records, labels, table): one uint32 cluster number per record and the table of dtype FRONTIER_CLUSTER
+        (first, count, lo, hi, sum), clusters numbered by their first record; frontier_goals(table, resolution) turns it into goals.
+        device=True: torch int32 tensors on the GPU instead -- (n, 4), (n,) and (k, 16) -- that ALIAS the library's buffers: valid
+        until the next frontier() on this TSDFCuda, copy them (.clone()) to keep them."""
+        return _frontier_call(self._t._L, "ws_map_frontier", self._t, (self._which,), lo, hi, min_value, any_weight, clusters, device)
+
+    def frontier_timing(self, enable: int = -1):
+        """device milliseconds of the count pass, the scan, the emit pass and the clustering of the last frontier() (ws_debug_frontier_timing)"""
+        return _timing(self._t._L, "ws_debug_frontier_timing", self._t.handle, 4, enable)
 
     def dev(self):
         return self._t.handle

@@ -162,6 +162,25 @@ class TSDFMapping:
             return store.distance(lo=lo, hi=hi, max_dist_vox=vox, unknown_occupied=unknown_occupied, columns=columns, any_weight=any_weight,
                                   device=device)
 
+    def frontier(self, **kw):
+        """The frontier of the averaged map (DeviceMapMemWrapper.frontier on avg_map()), under the mapping's lock like a reader: where
+        the window's known free space ends.  Keywords: lo, hi, min_value, any_weight, clusters, device."""
+        with self.mutex_:
+            return self.tsdf_.avg_map().frontier(**kw)
+
+    def global_frontier(self, lo=None, hi=None, **kw):
+        """The frontier of everything the run has seen: the window goes into the chunks of device_global_map exactly as in global_mesh
+        (ws_store_save_box behind wait_shift, under the mapping's lock like a writer), then DeviceGlobalMap.frontier.  The default box
+        is the bounding box of the chunks GROWN BY ONE VOXEL on every side (cut to int32), so that the outer faces of the mapped volume are frontier
+        too.  Keywords: min_value, any_weight, clusters, device."""
+        with self._window_in_store("global_frontier") as store:
+            if lo is None and hi is None:
+                keys = np.asarray(store.keys(), dtype=np.int64).reshape(-1, 3)
+                if len(keys):
+                    lo = np.maximum(keys.min(axis=0) * store.CHUNK_SIZE - 1, -2 ** 31)  # (cut to int32 voxel space)
+                    hi = np.minimum((keys.max(axis=0) + 1) * store.CHUNK_SIZE, 2 ** 31 - 1)
+            return store.frontier(lo=lo, hi=hi, **kw)
+
     @staticmethod
     def raycast_rays(pose, dirs):
         """The integers of a ray cast from a pose, in float64 numpy: origin = the pose's translation in metres times 1000, rounded

@@ -1,5 +1,5 @@
 """What the window map (ws_map_*) and the chunk store (ws_store_*) share on the host side of their queries: the box, the call,
-the download or the device tensors of surface, mesh, ray cast, point sample and distance field, and the timing read-out."""
+the download or the device tensors of surface, mesh, ray cast, point sample, distance field and frontier, and the timing read-out."""
 from __future__ import annotations
 
 import ctypes as C
@@ -9,7 +9,7 @@ import numpy as np
 from . import _lib
 from ._abi import _device_tensor, _i3, _is_device, _ptr
 from ._lib import WsError, check
-from .records import RAY, SAMPLE, SAMPLE_CLASSES, SURFACE_RECORD, VERT
+from .records import FRONTIER_CLUSTER, FRONTIER_RECORD, RAY, SAMPLE, SAMPLE_CLASSES, SURFACE_RECORD, VERT
 from .scan import DevicePoints
 
 
@@ -176,3 +176,31 @@ def _distance_call(L, name, owner, lead, lo, hi, max_dist_vox, unknown_occupied,
     if int(cnt.value) != n:
         raise WsError("distance: another call replaced the result before it was downloaded")
     return rec.reshape(shape), int(sites.value)
+
+
+def _frontier_call(L, name, owner, lead, lo, hi, min_value, any_weight, clusters, device):
+    """The frontier call `name` (ws_map_frontier, ws_store_frontier) on owner.handle and its result: `lead` are the arguments of the
+    entry point before the box.  Returns the records, or with `clusters` (records, labels, table); owner keeps the device tensors'
+    memory alive."""
+    box = _box_ptrs("frontier", lo, hi)
+    n, k = C.c_size_t(0), C.c_size_t(0)
+    flags = (_lib.WS_FRONTIER_ANY_WEIGHT if any_weight else 0) | (_lib.WS_FRONTIER_CLUSTERS if clusters else 0)
+    check(getattr(L, name)(owner.handle, *lead, *box, int(min_value), flags, C.byref(n), C.byref(k)), name)
+    n, k = int(n.value), int(k.value)
+    if device:
+        cnt = C.c_size_t(0)
+        rec = _device_tensor(getattr(L, name + "_records_dev")(owner.handle, C.byref(cnt)), (n, 4), "<i4", owner)
+        if int(cnt.value) != n:
+            raise WsError("frontier: another call replaced the result")
+        if not clusters:
+            return rec
+        return (rec, _device_tensor(getattr(L, name + "_labels_dev")(owner.handle, C.byref(cnt)), (n,), "<i4", owner),
+                _device_tensor(getattr(L, name + "_clusters_dev")(owner.handle, C.byref(cnt)), (k, 16), "<i4", owner))
+    rec = np.empty(n, dtype=FRONTIER_RECORD)
+    labels = np.empty(n, dtype=np.uint32) if clusters else None
+    table = np.empty(k, dtype=FRONTIER_CLUSTER) if clusters else None
+    got, got_k = C.c_size_t(0), C.c_size_t(0)
+    check(getattr(L, name + "_download")(owner.handle, _ptr(rec), _ptr(labels), _ptr(table), n, k, C.byref(got), C.byref(got_k)), name + "_download")
+    if int(got.value) != n or (clusters and int(got_k.value) != k):
+        raise WsError("frontier: another call replaced the result before it was downloaded")
+    return (rec, labels, table) if clusters else rec

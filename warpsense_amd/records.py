@@ -99,3 +99,41 @@ def write_raycast_ply(path, records, gradient=None):
         out.write(header.encode("ascii"))
         out.write(v.tobytes())
     return len(v)
+
+
+# one record of ws_map_frontier: world voxel coordinates and the mask of UNKNOWN neighbours, bits 0..5 = -x +x -y +y -z +z (16 bytes)
+FRONTIER_RECORD = np.dtype([("x", "<i4"), ("y", "<i4"), ("z", "<i4"), ("mask", "<u4")])
+# one row of its cluster table: record index of the first member, members, bounding box in world voxels, coordinate sums (64 bytes)
+FRONTIER_CLUSTER = np.dtype([("first", "<u4"), ("count", "<u4"), ("lo", "<i4", (3,)), ("hi", "<i4", (3,)), ("sum", "<i8", (3,)), ("pad", "<u8")])
+
+
+def frontier_goals(clusters, resolution, min_size=1):
+    """What a planner takes from the cluster table of a frontier call: the clusters of at least min_size voxels, largest first (ties
+    by `first`), as (centroids, sizes, lo, hi) -- (k, 3) float64 centroids in metres (sum / count * resolution / 1000), uint32 sizes,
+    and the (k, 3) int32 corners of the bounding boxes in world voxels.  Host only: no size filter runs on the device."""
+    clusters = np.asarray(clusters, dtype=FRONTIER_CLUSTER).reshape(-1)
+    keep = clusters[clusters["count"] >= int(min_size)]
+    keep = keep[np.lexsort((keep["first"], -keep["count"].astype(np.int64)))]
+    centroid = keep["sum"].astype(np.float64) / keep["count"].astype(np.float64)[:, None] * float(resolution) / 1000.0
+    return centroid.reshape(-1, 3), keep["count"].copy(), keep["lo"].copy(), keep["hi"].copy()
+
+
+def write_frontier_ply(path, records, resolution, labels=None):
+    """The records of a frontier call as a binary little-endian PLY point cloud: float x y z in metres (voxel * resolution / 1000 in
+    single precision, the point of write_surface_ply), uchar mask and, when `labels` is given, int cluster.  Returns the number of
+    points written."""
+    records = np.asarray(records, dtype=FRONTIER_RECORD).reshape(-1)
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("mask", "u1")] + ([("cluster", "<i4")] if labels is not None else [])
+    v = np.empty(len(records), dtype=np.dtype(fields))
+    for name in "xyz":
+        v[name] = records[name].astype(np.float32) * np.float32(resolution) / np.float32(1000.0)
+    v["mask"] = records["mask"].astype(np.uint8)
+    if labels is not None:
+        v["cluster"] = np.asarray(labels, dtype=np.uint32).reshape(-1).astype(np.int32)
+    header = ("ply\nformat binary_little_endian 1.0\ncomment warpsense_amd frontier\n"
+              f"element vertex {len(v)}\nproperty float x\nproperty float y\nproperty float z\nproperty uchar mask\n"
+              + ("property int cluster\n" if labels is not None else "") + "end_header\n")
+    with open(path, "wb") as out:
+        out.write(header.encode("ascii"))
+        out.write(v.tobytes())
+    return len(v)

@@ -10,7 +10,7 @@ from ._abi import _i3, _i3c, _ptr, pack_entry
 from ._lib import WS_MAP_AVG, check
 from .context import Context
 from .global_map import GlobalMap
-from .queries import _box_ptrs, _distance_call, _mesh_call, _raycast_call, _sample_call, _surface_call, _timing
+from .queries import _box_ptrs, _distance_call, _frontier_call, _mesh_call, _raycast_call, _sample_call, _surface_call, _timing
 
 
 class DeviceGlobalMap:
@@ -157,6 +157,19 @@ class DeviceGlobalMap:
     def distance_timing(self, enable: int = -1):
         """device milliseconds of pass 0 and of the x, y and z passes of the last distance() (ws_debug_store_distance_timing)"""
         return _timing(self._L, "ws_debug_store_distance_timing", self.handle, 4, enable)
+
+    def frontier(self, lo=None, hi=None, min_value=0, any_weight=False, clusters=False, device=False):
+        """The frontier of the chunks on the device (ws_store_frontier; the rules are those of ws_map_frontier, stated in
+        include/warpsense_hip.h): the observed-free voxels of the inclusive world-voxel box [lo, hi] (both None: the bounding box of
+        the present chunks) that touch a never-observed voxel of the box, across chunk borders.  Voxels of absent chunks are unknown.
+        The faces of the box are no frontier: pass a box one voxel larger than the bounding box to get the outer faces of the mapped
+        volume.  The arguments and the returned records or (records, labels, table) are those of DeviceMapMemWrapper.frontier;
+        device=True: torch tensors that ALIAS the store's buffers, valid until the next frontier() on this store."""
+        return _frontier_call(self._L, "ws_store_frontier", self, (), lo, hi, min_value, any_weight, clusters, device)
+
+    def frontier_timing(self, enable: int = -1):
+        """device milliseconds of the count passes, the scan, the emit pass and the clustering of the last frontier() (ws_debug_store_frontier_timing)"""
+        return _timing(self._L, "ws_debug_store_frontier_timing", self.handle, 4, enable)
 
     def flush_to(self, global_map: GlobalMap):
         """every chunk merged into a host GlobalMap: into its chunk cache (activate_chunk), or, for a map with a file, straight
