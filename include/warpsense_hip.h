@@ -439,6 +439,78 @@ int ws_map_frontier_download(ws_map *map, void *records_host, uint32_t *labels_h
  * clustering of the last call (the clustering spans one host read, of the number of clusters; 0 without WS_FRONTIER_CLUSTERS) */
 int ws_debug_frontier_timing(ws_map *map, int32_t enable, float ms_out[4]);
 
+/* Reach of a device map: the geodesic field.  Per record of the map's last distance result the cost of the cheapest path from a set of
+ * seeds (the robot) that keeps a given clearance from the obstacles -- whether a frontier goal can be reached, how far it is along
+ * free space, and by which way.  Integers only: the costs are exact and the same bytes on every run.
+ *   input: the dense result of the LAST ws_map_distance on this map as it lies in device memory: its box (lo and extent), its
+ *     `class | d2` records and whether it was made under WS_DISTANCE_COLUMNS.  No distance call yet: WS_ERR_INVALID.  The reach never
+ *     reads the TSDF itself.
+ *   traversable: a record is traversable iff its class is FREE (1) and d2 >= clear_d2; with WS_REACH_UNKNOWN_FREE (the optimistic
+ *     planner) class UNKNOWN (0) counts as well.  0 <= clear_d2 <= 65025, else WS_ERR_RANGE.  Under WS_DISTANCE_UNKNOWN_OCCUPIED an
+ *     unknown voxel is a site, d2 = 0: it is not traversable for any clear_d2 >= 1.
+ *   steps: between two records that differ by at most 1 on every axis (the 26-neighbourhood of a volume, the 8-neighbourhood between
+ *     columns), both traversable.  A face step weighs 10, an edge step 14, a corner step 17.  A neighbour outside the box does not
+ *     exist, as with ws_map_frontier.  clear_d2 >= 2 keeps a diagonal step from passing between two face-adjacent sites, that
+ *     is sites that are face neighbours of its ends: such an end has d2 = 1 and is not traversable.
+ *   seeds: n_seeds world voxels (n x 3 int32 in host memory), 1 <= n_seeds <= 2^20; under WS_DISTANCE_COLUMNS z is ignored.  A seed
+ *     outside the box or on a record that is not traversable is dropped; *n_seeded receives the number of seeds kept (a voxel given
+ *     twice counts twice).  No seed kept is WS_OK with every cost unreachable, like a distance box without sites.
+ *   field: one uint32 per record of the distance result, in its order: the minimum over all step sequences from any kept seed of
+ *     the sum of the weights, 0xFFFFFFFF where there is none; a kept seed has 0.  More than (2^32 - 2) / 17 records: WS_ERR_RANGE
+ *     (the cost could overflow).  The minimum defines the bytes; the implementation gets there another way and leaves them the same.
+ *   *n_reached: the records with a finite cost.  *rounds: the relaxation rounds that ran (this number, unlike the costs, may differ
+ *     between two runs).  Any of the three may be NULL.
+ *   max_rounds: the cap on the rounds, 0 for the default of 64 x tiles of the box + 64.  A round settles at least every record whose
+ *     cheapest path has that many steps, so records + 1 rounds always suffice -- which is 512 x tiles: the default is the TIGHTER of
+ *     the two, and a legitimate labyrinth can hit it (a one-voxel corridor that crosses a tile face on nearly every step needs
+ *     about one round per step).  A caller who expects such a map passes max_rounds, up to the number of records + 1.  At the cap
+ *     with tiles still listed: WS_ERR_RANGE, "not converged" in ws_last_error; the call leaves NO result, the previous reach
+ *     result is gone too, and ws_debug_reach_timing reads zeros.
+ *   errors: unknown flag bits, NULL seeds, n_seeds = 0 or > 2^20, no distance result: WS_ERR_INVALID before anything is launched; the
+ *     last reach result stays (also after a clear_d2 out of range).
+ * The implementation (map_reach.hip): the box is cut into tiles of 512 records (8 x 8 x 8; 16 x 32 columns).  A round is one launch
+ * with one workgroup per listed tile: it loads the tile and a halo of one record into LDS, relaxes there until nothing changes or 32
+ * sweeps are used up, writes its own tile and lists for the next round every tile across whose face, edge or corner it lowered a
+ * cost, and itself if it ran out of sweeps.  The host reads one word per round, the length of the next list.
+ * Synchronises.  The result belongs to the map, is allocated on first use, and carries its own box: a later ws_map_distance does not
+ * invalidate it, and it invalidates no other query's result.  An allocation that fails returns WS_ERR_HIP and leaves the map usable.
+ * Calls that use the result are serialised inside the library. */
+#define WS_REACH_DEFAULT 0u
+#define WS_REACH_UNKNOWN_FREE 1u
+#define WS_REACH_UNREACHABLE 0xFFFFFFFFu
+int ws_map_reach(ws_map *map, const int32_t *seeds_host, size_t n_seeds, int32_t clear_d2, uint32_t flags, uint32_t max_rounds, size_t *n_seeded, size_t *n_reached,
+                 uint32_t *rounds);
+const uint32_t *ws_map_reach_dev(const ws_map *map, size_t *n); /* device memory, n costs; NULL when n == 0 */
+/* copies at most `capacity` costs (a prefix) and always reports the total in *n_out; host may be NULL */
+int ws_map_reach_download(ws_map *map, uint32_t *host, size_t capacity, size_t *n_out);
+/* The box the last reach result carries: its first world voxel, its extent (nx, ny, nz; under columns nx, ny, 1) and whether it is a
+ * column map; all zero without a result or without records.  Any pointer may be NULL. */
+int ws_map_reach_box(ws_map *map, int32_t lo[3], uint32_t ext[3], int32_t *columns);
+/* The costs of the last reach result at n world voxels: int32 triples, `stride` int32 words apart (3, or 4: the 16-byte records of
+ * ws_map_frontier in device memory feed straight into the _dev form); under columns z is ignored.  A voxel outside the box of the
+ * result: 0xFFFFFFFF.  n <= 2^27.  The first form takes and fills host memory, the _dev form device memory.  Both synchronise.  No
+ * reach result, a stride other than 3 or 4, a NULL pointer with n > 0: WS_ERR_INVALID. */
+int ws_map_reach_lookup(ws_map *map, const int32_t *points_host, size_t n, int32_t stride, uint32_t *cost_host);
+int ws_map_reach_lookup_dev(ws_map *map, const int32_t *points_dev, size_t n, int32_t stride, uint32_t *cost_dev);
+/* The paths of the last reach result from g goal voxels (g x 3 int32 in host memory, 1 <= g <= 2^20) back to a seed, one wave per goal.
+ * The predecessor of a reached voxel v is the FIRST neighbour p in ascending (dx, dy, dz) order with cost[p] + w(p, v) == cost[v]; one
+ * exists at every reached voxel that is no seed, the cost falls with every step, and the walk is bounded by cost / 10 steps besides.
+ *   headers_host, g x 16 bytes: uint32 cost, steps (of the whole path), written (records of this goal), status: 0 reached, 1 not
+ *     reachable, 2 outside the box (cost 0xFFFFFFFF, steps = written = 0 for both).
+ *   records_host, g x cap_steps x 16 bytes, may be NULL when cap_steps = 0 (a pure cost query): int32 x, y, z, cost -- the goal first,
+ *     the seed last (steps + 1 records); a longer path leaves its first cap_steps records and still reports its true steps.  Records
+ *     beyond `written` are zero.  Under columns z is the goal's.  g x cap_steps <= 2^26, else WS_ERR_RANGE.  Synchronises. */
+int ws_map_reach_paths(ws_map *map, const int32_t *goals_host, size_t g, uint32_t cap_steps, void *headers_host, void *records_host);
+/* Measurement entry, as ws_debug_surface_timing: ms_out receives the device time of the seeding (clears, upload, seed pass), of all
+ * rounds as one span (it includes the host's read per round) and of the count pass of the last ws_map_reach */
+int ws_debug_reach_timing(ws_map *map, int32_t enable, float ms_out[3]);
+/* Measurement entry: the number of tiles each round of the last ws_map_reach listed, in round order (at most `capacity` of them, a
+ * prefix; *n_out receives the number of rounds; host may be NULL) */
+int ws_debug_reach_active(ws_map *map, uint32_t *host, size_t capacity, size_t *n_out);
+/* The constants of the implementation: out[0] the sweeps per round and tile, out[1..3] the tile of a volume along x, y, z, out[4..5]
+ * the tile of a column map along x, y, out[6] the default rounds per tile, out[7] = 0 */
+int ws_debug_reach_params(int32_t out[8]);
+
 /* ------------------------------------------------------------------ the global map in device memory ---- */
 /* ws_store: the device twin of HDF5GlobalMap (src/map/hdf5_global_map.cpp) -- a pool of 64^3-voxel chunks in HBM, so that a map shift
  * is a device-to-device copy in stream order: the leaving slabs, the window move and the entering slabs with revisits and corners,
@@ -709,6 +781,24 @@ int ws_store_frontier_download(ws_store *st, void *records_host, uint32_t *label
                                size_t *n_clusters);
 /* Measurement entry, as ws_debug_frontier_timing (the chunk tables' upload lies in front of the count pass) */
 int ws_debug_store_frontier_timing(ws_store *st, int32_t enable, float ms_out[4]);
+
+/* The reach of the store: ws_map_reach over the last ws_store_distance result of this store, word for word -- the same rules, the same
+ * kernels, the same limits and refusals.  A voxel of an absent chunk is UNKNOWN in that result: blocked by default, passable under
+ * WS_REACH_UNKNOWN_FREE (unless the distance call ran under WS_DISTANCE_UNKNOWN_OCCUPIED and clear_d2 >= 1).  A distance result
+ * without records (an empty store asked without a box) gives a reach result without records: WS_OK, every lookup 0xFFFFFFFF.
+ *   consequence: if a window holds the same voxels as the store inside a box, ws_map_reach behind ws_map_distance on that window and
+ *     box returns the same bytes -- costs, lookups and paths.
+ * The result belongs to the store, carries its own box and is apart from every other query's; later saves, loads, shifts, drops and
+ * distance calls leave it untouched. */
+int ws_store_reach(ws_store *st, const int32_t *seeds_host, size_t n_seeds, int32_t clear_d2, uint32_t flags, uint32_t max_rounds, size_t *n_seeded, size_t *n_reached,
+                   uint32_t *rounds);
+const uint32_t *ws_store_reach_dev(const ws_store *st, size_t *n); /* device memory, n costs; NULL when n == 0 */
+int ws_store_reach_download(ws_store *st, uint32_t *host, size_t capacity, size_t *n_out);
+int ws_store_reach_box(ws_store *st, int32_t lo[3], uint32_t ext[3], int32_t *columns);
+int ws_store_reach_lookup(ws_store *st, const int32_t *points_host, size_t n, int32_t stride, uint32_t *cost_host);
+int ws_store_reach_lookup_dev(ws_store *st, const int32_t *points_dev, size_t n, int32_t stride, uint32_t *cost_dev);
+int ws_store_reach_paths(ws_store *st, const int32_t *goals_host, size_t g, uint32_t cap_steps, void *headers_host, void *records_host);
+int ws_debug_store_reach_timing(ws_store *st, int32_t enable, float ms_out[3]);
 
 /* ------------------------------------------------------------------ TSDF update ---- */
 /* TSDFCuda::update_tsdf(scan_points, scanner_pos, up) — update_tsdf.cu:143-166.

@@ -328,6 +328,12 @@ public:
   {
     return global_map_frontier(store_, clusters, min_value, any_weight, lo, hi);
   }
+  // path costs over the last distance() of the chunks, and the paths back from goals (visualization.hpp, ws_store_reach)
+  ReachField reach(const std::vector<rm::Pointi> &seeds, int32_t clear_d2 = 0, bool unknown_free = false, uint32_t max_rounds = 0)
+  {
+    return global_map_reach(store_, seeds, clear_d2, unknown_free, max_rounds);
+  }
+  ReachPaths reach_paths(const std::vector<rm::Pointi> &goals, uint32_t cap_steps) { return global_map_reach_paths(store_, goals, cap_steps); }
   // what the chunks say at given points (visualization.hpp, ws_store_sample)
   PointSample sample(int resolution, const std::vector<rm::Pointi> &points, int32_t band_mm, bool any_weight = false, bool with_gradient = false, uint32_t select = 0,
                      const rm::Pointi *lo = nullptr, const rm::Pointi *hi = nullptr)
@@ -357,6 +363,16 @@ inline Frontier global_map_frontier(DeviceGlobalMap &g, bool clusters = true, in
                                     const rm::Pointi *hi = nullptr)
 {
   return global_map_frontier(g.handle(), clusters, min_value, any_weight, lo, hi);
+}
+
+// the reach of the device global map and its paths (visualization.hpp, ws_store_reach)
+inline ReachField global_map_reach(DeviceGlobalMap &g, const std::vector<rm::Pointi> &seeds, int32_t clear_d2 = 0, bool unknown_free = false, uint32_t max_rounds = 0)
+{
+  return global_map_reach(g.handle(), seeds, clear_d2, unknown_free, max_rounds);
+}
+inline ReachPaths global_map_reach_paths(DeviceGlobalMap &g, const std::vector<rm::Pointi> &goals, uint32_t cap_steps)
+{
+  return global_map_reach_paths(g.handle(), goals, cap_steps);
 }
 
 // the mesh of the device global map (visualization.hpp, ws_store_mesh)
@@ -740,6 +756,30 @@ public:
     const auto cut = [](int64_t v) { return (int32_t)std::min<int64_t>(std::max<int64_t>(v, INT32_MIN), INT32_MAX); };
     const rm::Pointi glo(cut(a[0] * cs - 1), cut(a[1] * cs - 1), cut(a[2] * cs - 1)), ghi(cut((b[0] + 1) * cs), cut((b[1] + 1) * cs), cut((b[2] + 1) * cs));
     return device_global_map_->frontier(clusters, min_value, any_weight, &glo, &ghi);
+  }
+  // How far every voxel of the window (or of [lo, hi]) is from `seeds` (world voxels) along free space that keeps clear_vox voxels
+  // from the obstacles: the distance field with a range one voxel beyond the clearance, then local_map_reach on it
+  ReachField reach(const std::vector<rm::Pointi> &seeds, int32_t clear_vox = 0, bool unknown_free = false, const rm::Pointi *lo = nullptr,
+                   const rm::Pointi *hi = nullptr, bool columns = false, uint32_t max_rounds = 0)
+  {
+    if (clear_vox < 0 || clear_vox > 254) throw std::invalid_argument("reach: the clearance is 0 .. 254 voxels");
+    WS_CHECK(ws_map_distance(gpu_.tsdf().handle(), WS_MAP_AVG, lo ? &lo->x : nullptr, hi ? &hi->x : nullptr, clear_vox + 1,
+                             columns ? WS_DISTANCE_COLUMNS : WS_DISTANCE_DEFAULT, nullptr));
+    return local_map_reach(gpu_.tsdf(), seeds, clear_vox * clear_vox, unknown_free, max_rounds);
+  }
+  // the same over everything the run has seen: the window into the device chunks, as global_mesh does, then distance and reach of the store
+  ReachField global_reach(const std::vector<rm::Pointi> &seeds, int32_t clear_vox = 0, bool unknown_free = false, const rm::Pointi *lo = nullptr,
+                          const rm::Pointi *hi = nullptr, bool columns = false, uint32_t max_rounds = 0)
+  {
+    if (!device_global_map_) throw std::logic_error("global_reach: no DeviceGlobalMap attached");
+    if (clear_vox < 0 || clear_vox > 254) throw std::invalid_argument("reach: the clearance is 0 .. 254 voxels");
+    wait_shift();
+    rm::Pointi wlo, whi;
+    local_map_.window(wlo, whi);
+    WS_CHECK(ws_store_save_box(device_global_map_->handle(), gpu_.tsdf().handle(), WS_MAP_AVG, &wlo.x, &whi.x));
+    WS_CHECK(ws_store_distance(device_global_map_->handle(), lo ? &lo->x : nullptr, hi ? &hi->x : nullptr, clear_vox + 1,
+                               columns ? WS_DISTANCE_COLUMNS : WS_DISTANCE_DEFAULT, nullptr));
+    return device_global_map_->reach(seeds, clear_vox * clear_vox, unknown_free, max_rounds);
   }
   // the reference's route, kept for comparison: whole window to the host array of the local map
   void download() { gpu_.tsdf().avg_map().to_host(view_); }

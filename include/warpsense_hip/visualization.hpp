@@ -10,6 +10,7 @@
 //   local_map_distance   (no counterpart: the reference has no distance field)                   a cost map, over ws_map_distance
 //   global_map_distance  (no counterpart)                                                     the cost map of the whole run, over ws_store_distance
 //   local_map_frontier / global_map_frontier   (no counterpart)                               where the known world ends, over ws_map_frontier / ws_store_frontier
+//   local_map_reach / global_map_reach, local_map_reach_paths / global_map_reach_paths   (no counterpart)   path costs and paths, over ws_map_reach / ws_store_reach
 //   local_map_skeleton   publish_local_map_skeleton  map.h:175-227   the 24 end points of the window's line list (host only)
 //
 // The reference walks every voxel of a host map (after a whole-map download for the CUDA map, test/pcd2tsdf.cpp:134-137); here
@@ -125,6 +126,89 @@ inline Frontier global_map_frontier(ws_store *store, bool clusters = true, int32
   size_t got = 0, got_k = 0;
   WS_CHECK(ws_store_frontier_download(store, n ? out.records.data() : nullptr, n && clusters ? out.labels.data() : nullptr,
                                       k && clusters ? out.clusters.data() : nullptr, n, k, &got, &got_k));
+  return out;
+}
+
+struct ReachField // the result of ws_map_reach / ws_store_reach
+{
+  std::vector<uint32_t> cost; // one per record of the distance result it ran on, in its order; WS_REACH_UNREACHABLE without a path
+  size_t seeded = 0, reached = 0;
+  uint32_t rounds = 0;
+  rmagine::Pointi lo;         // the box of the result: first voxel, and the extent (nx, ny, nz; a column map: nx, ny, 1)
+  uint32_t ext[3] = {0, 0, 0};
+  bool columns = false;
+};
+struct ReachPathHeader // one goal of ws_map_reach_paths
+{
+  uint32_t cost, steps, written, status; // status: 0 reached, 1 not reachable, 2 outside the box
+};
+struct ReachPathRecord
+{
+  int32_t x, y, z; // world voxels
+  uint32_t cost;
+};
+static_assert(sizeof(ReachPathHeader) == 16 && sizeof(ReachPathRecord) == 16, "ws_map_reach_paths writes 16-byte headers and records");
+struct ReachPaths
+{
+  std::vector<ReachPathHeader> headers; // one per goal
+  std::vector<ReachPathRecord> records; // cap_steps per goal, goal first; zero beyond `written`
+  uint32_t cap_steps = 0;
+};
+
+// The geodesic field over the LAST distance result of the map (the rules: warpsense_hip.h at ws_map_reach): call local_map_distance
+// first.  seeds: world voxels.  clear_d2: the squared clearance in voxels a path keeps.
+inline ReachField local_map_reach(cuda::TSDFCuda &tsdf, const std::vector<rmagine::Pointi> &seeds, int32_t clear_d2 = 0, bool unknown_free = false,
+                                  uint32_t max_rounds = 0)
+{
+  ReachField out;
+  WS_CHECK(ws_map_reach(tsdf.handle(), seeds.empty() ? nullptr : &seeds[0].x, seeds.size(), clear_d2, unknown_free ? WS_REACH_UNKNOWN_FREE : WS_REACH_DEFAULT,
+                        max_rounds, &out.seeded, &out.reached, &out.rounds));
+  size_t n = 0, got = 0;
+  int32_t columns = 0;
+  ws_map_reach_dev(tsdf.handle(), &n);
+  out.cost.resize(n);
+  WS_CHECK(ws_map_reach_download(tsdf.handle(), n ? out.cost.data() : nullptr, n, &got));
+  WS_CHECK(ws_map_reach_box(tsdf.handle(), &out.lo.x, out.ext, &columns));
+  out.columns = columns != 0;
+  return out;
+}
+
+// the same over the last distance result of the global map in device memory (ws_store_reach; app.hpp adds the DeviceGlobalMap overload)
+inline ReachField global_map_reach(ws_store *store, const std::vector<rmagine::Pointi> &seeds, int32_t clear_d2 = 0, bool unknown_free = false,
+                                   uint32_t max_rounds = 0)
+{
+  ReachField out;
+  WS_CHECK(ws_store_reach(store, seeds.empty() ? nullptr : &seeds[0].x, seeds.size(), clear_d2, unknown_free ? WS_REACH_UNKNOWN_FREE : WS_REACH_DEFAULT, max_rounds,
+                          &out.seeded, &out.reached, &out.rounds));
+  size_t n = 0, got = 0;
+  int32_t columns = 0;
+  ws_store_reach_dev(store, &n);
+  out.cost.resize(n);
+  WS_CHECK(ws_store_reach_download(store, n ? out.cost.data() : nullptr, n, &got));
+  WS_CHECK(ws_store_reach_box(store, &out.lo.x, out.ext, &columns));
+  out.columns = columns != 0;
+  return out;
+}
+
+// The paths of the last reach result from `goals` (world voxels) back to a seed (ws_map_reach_paths); cap_steps = 0: the headers alone
+inline ReachPaths local_map_reach_paths(cuda::TSDFCuda &tsdf, const std::vector<rmagine::Pointi> &goals, uint32_t cap_steps)
+{
+  ReachPaths out;
+  out.cap_steps = cap_steps;
+  out.headers.resize(goals.size());
+  out.records.resize(goals.size() * (size_t)cap_steps);
+  if (!goals.empty())
+    WS_CHECK(ws_map_reach_paths(tsdf.handle(), &goals[0].x, goals.size(), cap_steps, out.headers.data(), cap_steps ? out.records.data() : nullptr));
+  return out;
+}
+
+inline ReachPaths global_map_reach_paths(ws_store *store, const std::vector<rmagine::Pointi> &goals, uint32_t cap_steps)
+{
+  ReachPaths out;
+  out.cap_steps = cap_steps;
+  out.headers.resize(goals.size());
+  out.records.resize(goals.size() * (size_t)cap_steps);
+  if (!goals.empty()) WS_CHECK(ws_store_reach_paths(store, &goals[0].x, goals.size(), cap_steps, out.headers.data(), cap_steps ? out.records.data() : nullptr));
   return out;
 }
 

@@ -4,7 +4,7 @@ sliding TSDF map @ 5 cm, one MI355X): sensor clouds in float metres -> device pr
 
     python tools/replay_stream.py --map 1024 --scans 30 [--h5 /tmp/stream.h5] [--async-shift | --device-global-map] [--surface-ply DIR [--surface-every N]] [--mesh-ply DIR]
                                    [--raycast-ply DIR] [--distance-npy DIR [--distance-m M]] [--global-distance-npy FILE [--global-distance-m M]]
-                                   [--moving-sweeps] [--deskew] [--frontier-ply DIR] [--global-frontier-ply FILE]
+                                   [--moving-sweeps] [--deskew] [--frontier-ply DIR] [--global-frontier-ply FILE] [--reach-ply DIR [--reach-clearance-m M]]
 
 Prints one JSON line: scans/s over the stream and the mean per-stage times (the reference's RuntimeEvaluator
 forms "preprocess", "tsdf", "registration", "total")."""
@@ -73,6 +73,10 @@ def main():
                     "--device-global-map")
     ap.add_argument("--frontier-ply", default=None, metavar="DIR", help="after every TSDF update: the clustered frontier of the window (TSDFMapping.frontier, "
                     "ws_map_frontier) as binary little-endian PLY (xyz + mask + cluster) into DIR")
+    ap.add_argument("--reach-ply", default=None, metavar="DIR", help="after every TSDF update: the paths from the sensor to the reachable frontier clusters of the "
+                    "window (TSDFMapping.reachable_frontier: ws_map_distance, ws_map_reach, ws_map_frontier, ws_map_reach_lookup_dev, ws_map_reach_paths) as "
+                    "binary little-endian PLY (vertices with path number and cost, edges) into DIR")
+    ap.add_argument("--reach-clearance-m", type=float, default=0.2, metavar="M", help="... that keep M metres from the obstacles")
     ap.add_argument("--global-frontier-ply", default=None, metavar="FILE", help="after the last scan: the clustered frontier of the WHOLE run from the device "
                     "global map (TSDFMapping.global_frontier, ws_store_frontier) as PLY; needs --device-global-map")
     ap.add_argument("--global-raycast-ply", default=None, metavar="FILE", help="after the last scan: the predicted scan from the pose of the FIRST scan, "
@@ -145,6 +149,9 @@ def main():
     frontier = {"files": 0, "records": 0, "clusters": 0, "seconds": 0.0}
     if args.frontier_ply:
         os.makedirs(args.frontier_ply, exist_ok=True)
+    reach = {"files": 0, "clusters": 0, "reachable": 0, "rounds": 0, "seconds": 0.0}
+    if args.reach_ply:
+        os.makedirs(args.reach_ply, exist_ok=True)
     updates_seen = 0
     if args.mesh_ply:
         os.makedirs(args.mesh_ply, exist_ok=True)
@@ -173,6 +180,16 @@ def main():
             frontier["clusters"] = int(len(table))
             frontier["files"] += 1
             frontier["seconds"] += time.perf_counter() - ts
+        if args.reach_ply and app.n_updates > updates_seen:  # after every update of the map: where the robot can go from where it is
+            ts = time.perf_counter()
+            pose_m = app.pose_.astype(np.float64).copy()
+            pose_m[:3, 3] /= 1000.0  # (the app keeps millimetres)
+            got = app.gpu_.reachable_frontier(pose=pose_m, clearance_m=args.reach_clearance_m, cap_steps=4096)
+            if got["headers"] is not None:
+                W.write_path_ply(os.path.join(args.reach_ply, f"reach_{k + 1:05d}.ply"), got["headers"], got["paths"], args.res)
+                reach["files"] += 1
+            reach["clusters"], reach["reachable"], reach["rounds"] = int(len(got["table"])), int(len(got["reachable"])), int(app.gpu_.last_reach["rounds"])
+            reach["seconds"] += time.perf_counter() - ts
         updates_seen = app.n_updates
         if args.surface_ply and (k + 1) % max(args.surface_every, 1) == 0:
             ts = time.perf_counter()
@@ -297,6 +314,7 @@ def main():
                       "global_mesh_ply": global_mesh,
                       "global_surface_ply": global_surface,
                       "frontier_ply": frontier if args.frontier_ply else None,
+                      "reach_ply": reach if args.reach_ply else None,
                       "global_frontier_ply": global_frontier,
                       "global_raycast_ply": global_raycast,
                       "global_distance_npy": global_distance,

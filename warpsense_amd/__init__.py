@@ -9,6 +9,8 @@ from .api import (Context, DeviceGlobalMap, chunks_of_box, DeviceMap, DeviceMapM
 from ._lib import (WS_INTEGRATE_DENSE, WS_INTEGRATE_SPARSE, WS_INTEGRATE_SPARSE_SEPARATE, WS_MAP_AVG, WS_MAP_NEW, WS_REG_ALL_POINTS,  # noqa: F401
                    WS_REG_COMPAT_REFERENCE_LAUNCH, WS_REG_LOOP_LAUNCHES, WS_REG_LOOP_RESIDENT, WS_DISTANCE_ANY_WEIGHT, WS_DISTANCE_COLUMNS, WS_DISTANCE_DEFAULT, WS_DISTANCE_UNKNOWN_OCCUPIED, WS_FRONTIER_ANY_WEIGHT, WS_FRONTIER_CLUSTERS, WS_FRONTIER_DEFAULT, WS_MESH_ANY_WEIGHT, WS_MESH_DEFAULT, WS_RAYCAST_ANY_WEIGHT, WS_RAYCAST_DEFAULT, WS_RAYCAST_GRADIENT, WS_RAYCAST_TARGETS, WS_SURFACE_MARKER, WS_SURFACE_RECORDS, WsError)
 from .records import FRONTIER_CLUSTER, FRONTIER_RECORD, frontier_goals, write_frontier_ply  # noqa: F401
+from .records import REACH_PATH_HEADER, REACH_PATH_RECORD, REACH_UNREACHABLE, reach_mm, write_path_ply  # noqa: F401
+from ._lib import WS_REACH_DEFAULT, WS_REACH_UNKNOWN_FREE, WS_REACH_UNREACHABLE  # noqa: F401
 
 __all__ = [n for n in dir() if not n.startswith("_")]
 from .app import App  # noqa: F401,E402

@@ -49,6 +49,10 @@ EXPORTS = [
     "ws_debug_frontier_timing",
     "ws_store_frontier", "ws_store_frontier_records_dev", "ws_store_frontier_labels_dev", "ws_store_frontier_clusters_dev", "ws_store_frontier_download",
     "ws_debug_store_frontier_timing",
+    "ws_map_reach", "ws_map_reach_dev", "ws_map_reach_download", "ws_map_reach_box", "ws_store_reach_box", "ws_map_reach_lookup", "ws_map_reach_lookup_dev", "ws_map_reach_paths", "ws_debug_reach_timing",
+    "ws_debug_reach_params", "ws_debug_reach_active",
+    "ws_store_reach", "ws_store_reach_dev", "ws_store_reach_download", "ws_store_reach_lookup", "ws_store_reach_lookup_dev", "ws_store_reach_paths",
+    "ws_debug_store_reach_timing",
 ]
 WS_SURFACE_RECORDS, WS_SURFACE_MARKER = 0, 1
 WS_MESH_DEFAULT, WS_MESH_ANY_WEIGHT = 0, 1
@@ -58,6 +62,7 @@ WS_SAMPLE_SELECT_UNKNOWN, WS_SAMPLE_SELECT_FREE, WS_SAMPLE_SELECT_SURFACE, WS_SA
 SAMPLE_CLASSES = ("unknown", "free", "surface", "inside")  # class c of a sample record; WS_SAMPLE_SELECT_* is 4 << c
 WS_DISTANCE_DEFAULT, WS_DISTANCE_ANY_WEIGHT, WS_DISTANCE_UNKNOWN_OCCUPIED, WS_DISTANCE_COLUMNS = 0, 1, 2, 4
 WS_FRONTIER_DEFAULT, WS_FRONTIER_ANY_WEIGHT, WS_FRONTIER_CLUSTERS = 0, 1, 2
+WS_REACH_DEFAULT, WS_REACH_UNKNOWN_FREE, WS_REACH_UNREACHABLE = 0, 1, 0xFFFFFFFF
 
 
 class WsError(RuntimeError):
@@ -208,6 +213,19 @@ def load() -> C.CDLL:
         getattr(L, f"ws_{owner}_frontier_download").argtypes = [vp, vp, vp, vp, sz, sz, P(sz), P(sz)]
     L.ws_debug_frontier_timing.argtypes = [vp, i32, vp]
     L.ws_debug_store_frontier_timing.argtypes = [vp, i32, vp]
+    for owner in ("map", "store"):
+        getattr(L, f"ws_{owner}_reach").argtypes = [vp, vp, sz, i32, u32, u32, P(sz), P(sz), vp]
+        f = getattr(L, f"ws_{owner}_reach_dev")
+        f.argtypes, f.restype = [vp, P(sz)], vp
+        getattr(L, f"ws_{owner}_reach_download").argtypes = [vp, vp, sz, P(sz)]
+        getattr(L, f"ws_{owner}_reach_box").argtypes = [vp, vp, vp, vp]
+        getattr(L, f"ws_{owner}_reach_lookup").argtypes = [vp, vp, sz, i32, vp]
+        getattr(L, f"ws_{owner}_reach_lookup_dev").argtypes = [vp, vp, sz, i32, vp]
+        getattr(L, f"ws_{owner}_reach_paths").argtypes = [vp, vp, sz, u32, vp, vp]
+    L.ws_debug_reach_timing.argtypes = [vp, i32, vp]
+    L.ws_debug_store_reach_timing.argtypes = [vp, i32, vp]
+    L.ws_debug_reach_params.argtypes = [vp]
+    L.ws_debug_reach_active.argtypes = [vp, vp, sz, P(sz)]
     L.ws_shift_plan.argtypes = [vp, vp, vp, vp, P(ShiftPlan)]
     L.ws_shift_begin.argtypes = [vp, vp, u32, P(vp)]
     L.ws_shift_count.argtypes = [vp]

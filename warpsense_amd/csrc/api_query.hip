@@ -354,7 +354,7 @@ int ws_map_distance(ws_map *m, int which, const int32_t lo[3], const int32_t hi[
       },
       e32, &n));
   DistResult &q = m->dist;
-  WS_TRY(distance_run(q, m->ctx->stream, e32, max_dist_vox, flags, n, n_sites, [&] { return launch_dist_classify(m, q, which, l, ext, max_dist_vox, flags); }));
+  WS_TRY(distance_run(q, m->ctx->stream, l, e32, max_dist_vox, flags, n, n_sites, [&] { return launch_dist_classify(m, q, which, l, ext, max_dist_vox, flags); }));
   return map_take_error(m);
 }
 
@@ -461,4 +461,223 @@ int ws_debug_frontier_timing(ws_map *m, int32_t enable, float ms_out[4])
   if (!m) return invalid("ws_debug_frontier_timing: map is NULL");
   std::lock_guard<std::mutex> lock(m->frontier.mu);
   return query_timing(m->ctx->stream, m->frontier.timer, enable, ms_out, FRONTIER_PAIRS, 4);
+}
+
+// ---- reach: what the host core of ws_api.h (reach_run) needs beside it, for the window of a map here and for the store in
+// api_store.hip.  reach_rounds is the flow behind the refusals, from "the old result is dropped" to the publish: seeding, then one launch
+// and one read per round until the list of the next round is empty.
+int ws::reach_rounds(ReachResult &q, const DistResult &d, hipStream_t s, const char *name, const int32_t *seeds, size_t n_seeds, int32_t clear_d2, uint32_t flags,
+                     uint32_t max_rounds, size_t *n_seeded, size_t *n_reached, uint32_t *rounds)
+{
+  const bool columns = (d.flags & WS_DISTANCE_COLUMNS) != 0;
+  if (d.n > (size_t)(0xfffffffeull / 17ull)) return range_error(name, ": more than (2^32 - 2) / 17 records (a cost could overflow 32 bits)");
+  WS_TRY(q.timer.arm());
+  if (n_seeded) *n_seeded = 0;
+  if (n_reached) *n_reached = 0;
+  if (rounds) *rounds = 0;
+  q.n = 0; // (whatever happens from here on, the old result is gone: its buffers may be replaced)
+  q.have = false;
+  ReachBox &b = q.box;
+  copy3(b.lo, d.lo);
+  b.columns = columns ? 1u : 0u;
+  b.e[0] = columns ? 1u : d.ext[0], b.e[1] = columns ? d.ext[0] : d.ext[1], b.e[2] = columns ? d.ext[1] : d.ext[2];
+  if (d.n == 0)
+  {
+    b.e[0] = b.e[1] = b.e[2] = 0u;
+    q.have = true;
+    return WS_OK;
+  }
+  const size_t n = d.n, n_tiles = (size_t)reach_tiles(b);
+  WS_TRY(q.words.alloc(4));
+  if (n > q.cost.cap || n_tiles > q.mark.cap || 2 * n_tiles > q.list.cap || n_seeds > q.seeds.cap)
+  {
+    WS_HIP(hipStreamSynchronize(s));
+    WS_TRY(q.cost.grow(n, sizeof(uint32_t)));
+    WS_TRY(q.mark.grow(n_tiles, sizeof(uint32_t)));
+    WS_TRY(q.list.grow(2 * n_tiles, sizeof(uint32_t)));
+    WS_TRY(q.seeds.grow(n_seeds, 3 * sizeof(int32_t)));
+  }
+  const uint32_t *dist = d.rec.as<uint32_t>();
+  const uint64_t cap = max_rounds ? (uint64_t)max_rounds : std::min<uint64_t>((uint64_t)REACH_ROUNDS_PER_TILE * n_tiles + 64u, 0xfffffffeull);
+  WS_HIP(hipMemcpyAsync(q.seeds.p, seeds, n_seeds * 3 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  WS_TRY(launch_reach_seed(q, s, dist, n_seeds, (uint32_t)clear_d2, flags));
+  WS_HIP(hipStreamSynchronize(s));
+  const size_t kept = (size_t)q.words.host[0];
+  uint64_t active = q.words.host[3]; // round r reads list r & 1
+  uint32_t r = 0;
+  q.active.clear();
+  while (active)
+  {
+    if ((uint64_t)r >= cap)
+    {
+      q.timer.marked = 0; // (a call without a result leaves no times either: ws_debug_reach_timing reads zeros)
+      set_error(std::string(name) + ": not converged after " + std::to_string(r) + " rounds (max_rounds); no result is left");
+      return WS_ERR_RANGE;
+    }
+    ++r;
+    q.active.push_back((uint32_t)std::min<uint64_t>(active, 0xffffffffull));
+    WS_TRY(launch_reach_round(q, s, dist, r, (uint32_t)std::min<uint64_t>(active, 0xffffffffull), (uint32_t)clear_d2, flags));
+    WS_HIP(hipStreamSynchronize(s)); // the one host read of a round: the length of the next list sizes the next launch
+    active = q.words.host[2 + ((r + 1u) & 1u)];
+  }
+  WS_TRY(launch_reach_count(q, s));
+  WS_HIP(hipStreamSynchronize(s));
+  q.n = n;
+  q.have = true;
+  if (n_seeded) *n_seeded = kept;
+  if (n_reached) *n_reached = (size_t)q.words.host[1];
+  if (rounds) *rounds = r;
+  return WS_OK;
+}
+
+const uint32_t *ws::reach_dev(const ReachResult *q, size_t *n)
+{
+  if (n) *n = q ? q->n : 0;
+  return q && q->n ? static_cast<const uint32_t *>(q->cost.p) : nullptr;
+}
+
+int ws::reach_box(const ReachResult &q, int32_t lo[3], uint32_t ext[3], int32_t *columns)
+{
+  const bool have = q.have && q.n;
+  for (int k = 0; k < 3; ++k)
+  {
+    if (lo) lo[k] = have ? q.box.lo[k] : 0;
+    if (ext) ext[k] = !have ? 0u : q.box.columns ? (k < 2 ? q.box.e[k + 1] : 1u) : q.box.e[k];
+  }
+  if (columns) *columns = have && q.box.columns ? 1 : 0;
+  return WS_OK;
+}
+
+int ws::reach_download(const ReachResult &q, hipStream_t s, uint32_t *host, size_t capacity, size_t *n_out)
+{
+  *n_out = q.n;
+  const size_t k = host ? std::min(capacity, q.n) : 0;
+  if (k == 0) return WS_OK;
+  WS_HIP(hipMemcpyAsync(host, q.cost.p, k * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  WS_HIP(hipStreamSynchronize(s));
+  return WS_OK;
+}
+
+int ws::reach_lookup(ReachResult &q, hipStream_t s, const char *name, const int32_t *points, bool on_host, size_t n, int32_t stride, uint32_t *cost)
+{
+  if ((stride != 3 && stride != 4) || (n && (!points || !cost))) return invalid(std::string(name) + ": bad argument");
+  if (!q.have) return invalid(std::string(name) + ": no reach result");
+  if (n > ((size_t)1 << 27)) return range_error(name, ": more than 2^27 points");
+  if (n == 0) return WS_OK;
+  uint32_t *out = cost;
+  if (on_host)
+  {
+    if (n * (size_t)stride > q.pts.cap || n > q.out.cap)
+    {
+      WS_HIP(hipStreamSynchronize(s));
+      WS_TRY(q.pts.grow(n * (size_t)stride, sizeof(int32_t)));
+      WS_TRY(q.out.grow(n, sizeof(uint32_t)));
+    }
+    WS_HIP(hipMemcpyAsync(q.pts.p, points, n * (size_t)stride * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    points = q.pts.as<int32_t>();
+    out = q.out.as<uint32_t>();
+  }
+  WS_TRY(launch_reach_lookup(q, s, points, n, stride, out));
+  if (on_host) WS_HIP(hipMemcpyAsync(cost, out, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  WS_HIP(hipStreamSynchronize(s));
+  return WS_OK;
+}
+
+int ws::reach_paths(ReachResult &q, hipStream_t s, const char *name, const int32_t *goals_host, size_t g, uint32_t cap_steps, void *headers_host, void *records_host)
+{
+  if (!goals_host || !headers_host || g == 0 || g > ((size_t)1 << 20) || (cap_steps && !records_host)) return invalid(std::string(name) + ": bad argument");
+  if (!q.have) return invalid(std::string(name) + ": no reach result");
+  const size_t n_rec = g * (size_t)cap_steps;
+  if (n_rec > ((size_t)1 << 26)) return range_error(name, ": more than 2^26 path records (goals x cap_steps)");
+  if (g > q.goals.cap || g > q.hdr.cap || n_rec > q.steps.cap)
+  {
+    WS_HIP(hipStreamSynchronize(s));
+    WS_TRY(q.goals.grow(g, 3 * sizeof(int32_t)));
+    WS_TRY(q.hdr.grow(g, 16));
+    WS_TRY(q.steps.grow(n_rec, 16));
+  }
+  WS_HIP(hipMemcpyAsync(q.goals.p, goals_host, g * 3 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  WS_TRY(launch_reach_paths(q, s, g, cap_steps));
+  WS_HIP(hipMemcpyAsync(headers_host, q.hdr.p, g * 16, hipMemcpyDeviceToHost, s));
+  if (n_rec) WS_HIP(hipMemcpyAsync(records_host, q.steps.p, n_rec * 16, hipMemcpyDeviceToHost, s));
+  WS_HIP(hipStreamSynchronize(s));
+  return WS_OK;
+}
+
+// ---- reach: the geodesic field over the last distance result of the map, map_reach.hip (the rules are stated in warpsense_hip.h)
+int ws_map_reach(ws_map *m, const int32_t *seeds_host, size_t n_seeds, int32_t clear_d2, uint32_t flags, uint32_t max_rounds, size_t *n_seeded, size_t *n_reached,
+                 uint32_t *rounds)
+{
+  if (!m) return invalid("ws_map_reach: bad argument");
+  std::unique_lock<std::mutex> lock_dist, lock;
+  return reach_run(m->reach, m->dist, m->ctx->stream, "ws_map_reach", seeds_host, n_seeds, clear_d2, flags, max_rounds, n_seeded, n_reached, rounds, [&] {
+    WS_SETTLE(m);
+    lock_dist = std::unique_lock<std::mutex>(m->dist.mu); // (the order of every call that holds both)
+    lock = std::unique_lock<std::mutex>(m->reach.mu);
+    return (int)WS_OK;
+  });
+}
+
+const uint32_t *ws_map_reach_dev(const ws_map *m, size_t *n) { return reach_dev(m ? &m->reach : nullptr, n); }
+
+int ws_map_reach_download(ws_map *m, uint32_t *host, size_t capacity, size_t *n_out)
+{
+  if (!m || !n_out) return invalid("ws_map_reach_download: NULL argument");
+  std::lock_guard<std::mutex> lock(m->reach.mu);
+  return reach_download(m->reach, m->ctx->stream, host, capacity, n_out);
+}
+
+int ws_map_reach_box(ws_map *m, int32_t lo[3], uint32_t ext[3], int32_t *columns)
+{
+  if (!m) return invalid("ws_map_reach_box: map is NULL");
+  std::lock_guard<std::mutex> lock(m->reach.mu);
+  return reach_box(m->reach, lo, ext, columns);
+}
+
+int ws_map_reach_lookup(ws_map *m, const int32_t *points_host, size_t n, int32_t stride, uint32_t *cost_host)
+{
+  if (!m) return invalid("ws_map_reach_lookup: bad argument");
+  WS_SETTLE(m);
+  std::lock_guard<std::mutex> lock(m->reach.mu);
+  return reach_lookup(m->reach, m->ctx->stream, "ws_map_reach_lookup", points_host, true, n, stride, cost_host);
+}
+
+int ws_map_reach_lookup_dev(ws_map *m, const int32_t *points_dev, size_t n, int32_t stride, uint32_t *cost_dev)
+{
+  if (!m) return invalid("ws_map_reach_lookup_dev: bad argument");
+  WS_SETTLE(m);
+  std::lock_guard<std::mutex> lock(m->reach.mu);
+  return reach_lookup(m->reach, m->ctx->stream, "ws_map_reach_lookup_dev", points_dev, false, n, stride, cost_dev);
+}
+
+int ws_map_reach_paths(ws_map *m, const int32_t *goals_host, size_t g, uint32_t cap_steps, void *headers_host, void *records_host)
+{
+  if (!m) return invalid("ws_map_reach_paths: bad argument");
+  WS_SETTLE(m);
+  std::lock_guard<std::mutex> lock(m->reach.mu);
+  return reach_paths(m->reach, m->ctx->stream, "ws_map_reach_paths", goals_host, g, cap_steps, headers_host, records_host);
+}
+
+int ws_debug_reach_timing(ws_map *m, int32_t enable, float ms_out[3])
+{
+  if (!m) return invalid("ws_debug_reach_timing: map is NULL");
+  std::lock_guard<std::mutex> lock(m->reach.mu);
+  return query_timing(m->ctx->stream, m->reach.timer, enable, ms_out, REACH_PAIRS, 3);
+}
+
+int ws_debug_reach_active(ws_map *m, uint32_t *host, size_t capacity, size_t *n_out)
+{
+  if (!m || !n_out) return invalid("ws_debug_reach_active: NULL argument");
+  std::lock_guard<std::mutex> lock(m->reach.mu);
+  *n_out = m->reach.active.size();
+  if (host) std::copy_n(m->reach.active.begin(), std::min(capacity, m->reach.active.size()), host);
+  return WS_OK;
+}
+
+int ws_debug_reach_params(int32_t out[8])
+{
+  if (!out) return invalid("ws_debug_reach_params: NULL argument");
+  const int32_t v[8] = {REACH_SWEEPS, REACH_VA, REACH_VB, REACH_VC, REACH_CB, REACH_CC, (int32_t)REACH_ROUNDS_PER_TILE, 0};
+  std::copy(v, v + 8, out);
+  return WS_OK;
 }

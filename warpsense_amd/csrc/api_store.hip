@@ -800,7 +800,7 @@ int ws_store_distance(ws_store *st, const int32_t lo[3], const int32_t hi[3], in
     for (const StoreRaySlot &e : listed) c.zlo = std::min(c.zlo, e.cz * STORE_CS), c.zhi = std::max(c.zhi, e.cz * STORE_CS + STORE_CS - 1);
     c.zlo = std::max(c.zlo, c.lo[2]), c.zhi = std::min(c.zhi, c.hi[2]);
   }
-  return store_enqueued(st, distance_run(q, s, ext, max_dist_vox, flags, n, n_sites, [&] {
+  return store_enqueued(st, distance_run(q, s, c.lo, ext, max_dist_vox, flags, n, n_sites, [&] {
     if (store_lookup_places(listed.size()) > q.table_host.cap) WS_HIP(hipStreamSynchronize(s));
     WS_TRY(store_lookup_fill(q.table_host, q.table_dev, listed));
     return launch_store_dist_classify(st, q, c, max_dist_vox, flags);
@@ -914,4 +914,64 @@ int ws_debug_store_frontier_timing(ws_store *st, int32_t enable, float ms_out[4]
   if (!st) return invalid("ws_debug_store_frontier_timing: store is NULL");
   std::lock_guard<std::mutex> lock(st->mu);
   return query_timing(st->ctx->stream, st->frontier.timer, enable, ms_out, FRONTIER_PAIRS, 4);
+}
+
+// ---- the reach of the store: ws_map_reach over the last ws_store_distance result (map_reach.hip reads its records alone)
+int ws_store_reach(ws_store *st, const int32_t *seeds_host, size_t n_seeds, int32_t clear_d2, uint32_t flags, uint32_t max_rounds, size_t *n_seeded, size_t *n_reached,
+                   uint32_t *rounds)
+{
+  if (!st) return invalid("ws_store_reach: bad argument");
+  std::unique_lock<std::mutex> lock;
+  return reach_run(st->reach, st->dist, st->ctx->stream, "ws_store_reach", seeds_host, n_seeds, clear_d2, flags, max_rounds, n_seeded, n_reached, rounds, [&] {
+    servers_leave(st->ctx);
+    lock = std::unique_lock<std::mutex>(st->mu);
+    return (int)WS_OK;
+  });
+}
+
+const uint32_t *ws_store_reach_dev(const ws_store *st, size_t *n) { return reach_dev(st ? &st->reach : nullptr, n); }
+
+int ws_store_reach_download(ws_store *st, uint32_t *host, size_t capacity, size_t *n_out)
+{
+  if (!st || !n_out) return invalid("ws_store_reach_download: NULL argument");
+  std::lock_guard<std::mutex> lock(st->mu);
+  return reach_download(st->reach, st->ctx->stream, host, capacity, n_out);
+}
+
+int ws_store_reach_box(ws_store *st, int32_t lo[3], uint32_t ext[3], int32_t *columns)
+{
+  if (!st) return invalid("ws_store_reach_box: store is NULL");
+  std::lock_guard<std::mutex> lock(st->mu);
+  return reach_box(st->reach, lo, ext, columns);
+}
+
+int ws_store_reach_lookup(ws_store *st, const int32_t *points_host, size_t n, int32_t stride, uint32_t *cost_host)
+{
+  if (!st) return invalid("ws_store_reach_lookup: bad argument");
+  servers_leave(st->ctx);
+  std::lock_guard<std::mutex> lock(st->mu);
+  return reach_lookup(st->reach, st->ctx->stream, "ws_store_reach_lookup", points_host, true, n, stride, cost_host);
+}
+
+int ws_store_reach_lookup_dev(ws_store *st, const int32_t *points_dev, size_t n, int32_t stride, uint32_t *cost_dev)
+{
+  if (!st) return invalid("ws_store_reach_lookup_dev: bad argument");
+  servers_leave(st->ctx);
+  std::lock_guard<std::mutex> lock(st->mu);
+  return reach_lookup(st->reach, st->ctx->stream, "ws_store_reach_lookup_dev", points_dev, false, n, stride, cost_dev);
+}
+
+int ws_store_reach_paths(ws_store *st, const int32_t *goals_host, size_t g, uint32_t cap_steps, void *headers_host, void *records_host)
+{
+  if (!st) return invalid("ws_store_reach_paths: bad argument");
+  servers_leave(st->ctx);
+  std::lock_guard<std::mutex> lock(st->mu);
+  return reach_paths(st->reach, st->ctx->stream, "ws_store_reach_paths", goals_host, g, cap_steps, headers_host, records_host);
+}
+
+int ws_debug_store_reach_timing(ws_store *st, int32_t enable, float ms_out[3])
+{
+  if (!st) return invalid("ws_debug_store_reach_timing: store is NULL");
+  std::lock_guard<std::mutex> lock(st->mu);
+  return query_timing(st->ctx->stream, st->reach.timer, enable, ms_out, REACH_PAIRS, 3);
 }

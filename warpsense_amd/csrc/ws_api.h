@@ -279,11 +279,19 @@ int distance_check(const char *name, bool bad, const int32_t *lo, const int32_t 
 // The flow of a distance call whose arguments have passed distance_check, from "the old result is dropped" to the publish.  pass0()
 // enqueues the source's classification into q.rec and the first plane of q.plane and returns at once.
 template <typename Pass0>
-int distance_run(DistResult &q, hipStream_t s, const uint32_t ext[3], int32_t R, uint32_t flags, size_t n, size_t *n_sites, Pass0 pass0)
+int distance_run(DistResult &q, hipStream_t s, const int32_t lo[3], const uint32_t ext[3], int32_t R, uint32_t flags, size_t n, size_t *n_sites, Pass0 pass0)
 {
   if (n_sites) *n_sites = 0;
   q.n = 0; // (whatever happens from here on, the old result is gone: its buffers may be replaced)
-  if (n == 0) return WS_OK;
+  q.have = false;
+  // what a reach call needs of this result beside its records: the box and the flags (published with `have`)
+  for (int k = 0; k < 3; ++k) q.lo[k] = n ? lo[k] : 0, q.ext[k] = n ? ext[k] : 0u;
+  q.flags = flags;
+  if (n == 0)
+  {
+    q.have = true;
+    return WS_OK;
+  }
   WS_TRY(q.sites.alloc(1));
   if (n > q.rec.cap || n > q.plane.cap)
   {
@@ -296,6 +304,7 @@ int distance_run(DistResult &q, hipStream_t s, const uint32_t ext[3], int32_t R,
   WS_TRY(q.sites.fetch(s));
   WS_HIP(hipStreamSynchronize(s));
   q.n = n;
+  q.have = true;
   if (n_sites) *n_sites = (size_t)*q.sites.host;
   return WS_OK;
 }
@@ -329,6 +338,30 @@ int frontier_run(FrontierResult &q, hipStream_t s, const char *name, size_t bloc
     WS_TRY(frontier_clusters(q, s, n));
   }
   return frontier_publish(q, n, clusters ? q.n_clusters : 0, clusters, n_out, n_clusters);
+}
+
+// ---- reach (map_reach.hip): the geodesic field over the records of a distance result.  The window of a map and the store differ in
+// nothing but their locks.  reach_run: enter() settles the
+// owner and takes its locks -- behind the refusals that need neither, in front of the look at the distance result.  The others are no
+// templates (api_query.hip): their callers hold the lock.
+const uint32_t *reach_dev(const ReachResult *q, size_t *n);
+int reach_box(const ReachResult &q, int32_t lo[3], uint32_t ext[3], int32_t *columns);
+int reach_download(const ReachResult &q, hipStream_t s, uint32_t *host, size_t capacity, size_t *n_out);
+int reach_lookup(ReachResult &q, hipStream_t s, const char *name, const int32_t *points, bool on_host, size_t n, int32_t stride, uint32_t *cost);
+int reach_paths(ReachResult &q, hipStream_t s, const char *name, const int32_t *goals_host, size_t g, uint32_t cap_steps, void *headers_host, void *records_host);
+int reach_rounds(ReachResult &q, const DistResult &d, hipStream_t s, const char *name, const int32_t *seeds, size_t n_seeds, int32_t clear_d2, uint32_t flags,
+                 uint32_t max_rounds, size_t *n_seeded, size_t *n_reached, uint32_t *rounds);
+constexpr int REACH_PAIRS[3][2] = {{0, 1}, {1, 2}, {2, 3}};
+
+template <typename Enter>
+int reach_run(ReachResult &q, const DistResult &d, hipStream_t s, const char *name, const int32_t *seeds, size_t n_seeds, int32_t clear_d2, uint32_t flags,
+              uint32_t max_rounds, size_t *n_seeded, size_t *n_reached, uint32_t *rounds, Enter enter)
+{
+  if ((flags & ~WS_REACH_UNKNOWN_FREE) || !seeds || n_seeds == 0 || n_seeds > ((size_t)1 << 20)) return invalid(std::string(name) + ": bad argument");
+  if (clear_d2 < 0 || clear_d2 > 65025) return range_error(name, ": clear_d2 must be 0 .. 65025 (255 squared, the largest d2 of a distance record)");
+  WS_TRY(enter());
+  if (!d.have) return invalid(std::string(name) + ": no distance result yet (the reach runs on the records of the last distance call)");
+  return reach_rounds(q, d, s, name, seeds, n_seeds, clear_d2, flags, max_rounds, n_seeded, n_reached, rounds);
 }
 
 // ---- map shift: one shift of both maps' windows, for ws_shift_begin (api_map.hip) and ws_shift_device (api_store.hip), which

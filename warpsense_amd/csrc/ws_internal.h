@@ -408,7 +408,13 @@ struct DistResult
   DevBuf plane;                        // 2 x uint16 per record: ping-pong planes of the running minimum
   DevCounter sites;                    // site voxels / site columns of the last call
   size_t n = 0;                        // records of the last call
-  void release() { timer.release(), sites.release(); for (DevBuf *b : {&rec, &plane}) b->release(); }
+  // what ws_map_reach / ws_store_reach need of the last call beside its records: `have` once a call has succeeded (n may be 0),
+  // its box (first voxel and extent; ext[2] is not read under WS_DISTANCE_COLUMNS) and its flags
+  bool have = false;
+  int32_t lo[3] = {0, 0, 0};
+  uint32_t ext[3] = {0, 0, 0};
+  uint32_t flags = 0;
+  void release() { timer.release(), sites.release(), have = false, n = 0; for (DevBuf *b : {&rec, &plane}) b->release(); }
 };
 // ... and a sample call (ws_map::Sample, ws_store::Sample; the one flow is sample_run in ws_api.h)
 struct SampleResult
@@ -432,6 +438,33 @@ struct FrontierResult : SurfResult // timer: 0 count 1 scan 2, 3 emit 4 clusteri
   size_t n_clusters = 0;               // rows of the last call
   bool has_clusters = false;           // the last call also wrote `labels` and `clusters`
   void release() { SurfResult::release(), heads.release(); for (DevBuf *b : {&parent, &labels, &head_tot, &head_off, &clusters}) b->release(); }
+};
+// ... and a reach call (ws_map::Reach, ws_store::reach; the one flow is reach_run in ws_api.h, the kernels are in map_reach.hip).  The
+// result carries its own box: lookups and paths need the costs alone, so a later distance call leaves it valid.
+struct ReachBox // the box of a reach result as its kernels take it (ws_reach.h)
+{
+  int32_t lo[3];    // first world voxel
+  uint32_t e[3];    // extents of the record index (a, b, c), c fastest: (nx, ny, nz), and (1, nx, ny) under WS_DISTANCE_COLUMNS
+  uint32_t columns; // != 0: a = 0, b = x - lo[0], c = y - lo[1], z is ignored
+};
+struct ReachResult
+{
+  QueryTimer timer;                    // 0 seeding 1 rounds 2 count 3
+  DevBuf cost;                         // uint32: one cost per record of the distance result
+  DevBuf mark, list;                   // uint32 [tiles]: the last round a tile was queued for; uint32 [2][tiles]: the tile lists of this round and the next
+  DevBuf seeds;                        // int32 [seeds][3] staging of the host seeds
+  DevCounter words;                    // [0] kept seeds [1] reached records [2] [3] lengths of the two tile lists
+  DevBuf pts, out;                     // staging of a host lookup: int32 [points][stride], uint32 [points]
+  DevBuf goals, hdr, steps;            // paths: int32 [goals][3], 16-byte headers, 16-byte records [goals][cap_steps]
+  size_t n = 0;                        // costs of the last call
+  bool have = false;                   // a call has succeeded since the last failure (n may be 0)
+  ReachBox box = {};
+  std::vector<uint32_t> active;        // the tiles listed per round of the last call (ws_debug_reach_active)
+  void release()
+  {
+    timer.release(), words.release(), have = false, n = 0;
+    for (DevBuf *b : {&cost, &mark, &list, &seeds, &pts, &out, &goals, &hdr, &steps}) b->release();
+  }
 };
 
 } // namespace ws
@@ -530,6 +563,10 @@ struct ws_map
     ws::DevBuf col_cnt;                  // uint32 [columns of the box] frontier voxels per (x, y) column
     void release() { FrontierResult::release(), col_cnt.release(); }
   } frontier;
+  struct Reach : ws::ReachResult // ws_map_reach (map_reach.hip); a reach call holds dist.mu, then mu
+  {
+    std::mutex mu;
+  } reach;
   // The scan whose verdict (did its records fit the pool?) has not been looked at yet: ws_tsdf_update* return after the
   // launches, like the reference's update_tsdf (update_tsdf.cu:165); the next call that takes this map settles it first
   // (settle_tsdf: the verdict is in host-mapped memory ~0.35 ms after the launches) and repeats the scan if it was aborted.
@@ -560,7 +597,7 @@ struct ws_map
                           &tile_list, &rec, &big_keys, &block_stats, &counters, &box_stage, &shift_stage_dev})
       b->release();
     for (ws::HostBlock *b : {&counters_host, &status, &shift_stage_host}) b->release();
-    surf.release(), mesh.release(), ray.release(), dist.release(), sample.release(), frontier.release();
+    surf.release(), mesh.release(), ray.release(), dist.release(), sample.release(), frontier.release(), reach.release();
   }
 };
 
@@ -715,8 +752,10 @@ struct ws_store
     ws::DevBuf table_dev;                // ... and the copy the kernels read
     void release() { FrontierResult::release(), mask.release(), table_host.release(), table_dev.release(); }
   } frontier;
+  ws::ReachResult reach; // ws_store_reach (map_reach.hip: it reads the records of `dist` alone)
   void release()
   {
+    reach.release();
     frontier.release();
     surf.release();
     mesh.release();
@@ -854,6 +893,22 @@ struct StoreFrontierCall
 inline size_t store_frontier_table_bytes(size_t n_chunks) { return store_word_table_bytes(n_chunks) + n_chunks * 6 * sizeof(uint32_t); }
 int launch_store_frontier_count(ws_store *st, ws_store::Frontier &q, const StoreFrontierCall &c);
 int launch_store_frontier_emit(ws_store *st, ws_store::Frontier &q, const StoreFrontierCall &c, size_t cap);
+
+// map_reach.hip: the geodesic field over the records of a distance result, of a window or of the store alike.  reach_tiles: the tiles
+// of a box.  launch_reach_seed clears costs, marks and words, takes the n_seeds seeds in q.seeds (it marks events 0, 1) and queues
+// their tiles for round 1; launch_reach_round runs round `r` over the `active` tiles of its list; launch_reach_count counts the
+// finite costs (events 2, 3).  The words arrive in q.words.host after fetch and a stream synchronise.
+constexpr uint32_t REACH_INF = 0xffffffffu;
+constexpr int REACH_SWEEPS = 32;             // S: sweeps of a tile in LDS per round
+constexpr int REACH_VA = 8, REACH_VB = 8, REACH_VC = 8;  // the tile of a volume, in (a, b, c) of ReachBox: 512 records
+constexpr int REACH_CA = 1, REACH_CB = 16, REACH_CC = 32; // the tile of a column map: 512 records, 32 along the fastest axis
+constexpr uint32_t REACH_ROUNDS_PER_TILE = 64; // max_rounds = 0 stands for REACH_ROUNDS_PER_TILE x tiles + 64
+uint64_t reach_tiles(const ReachBox &b);
+int launch_reach_seed(ReachResult &q, hipStream_t s, const uint32_t *dist, size_t n_seeds, uint32_t clear_d2, uint32_t flags);
+int launch_reach_round(ReachResult &q, hipStream_t s, const uint32_t *dist, uint32_t r, uint32_t active, uint32_t clear_d2, uint32_t flags);
+int launch_reach_count(ReachResult &q, hipStream_t s);
+int launch_reach_lookup(const ReachResult &q, hipStream_t s, const int32_t *pts_dev, size_t n, int32_t stride, uint32_t *out_dev);
+int launch_reach_paths(ReachResult &q, hipStream_t s, size_t g, uint32_t cap_steps);
 
 // store_raycast.hip: the march of ws_raycast.h over the chunks the call lists.  The kernels find a chunk through an open-addressing
 // table key -> slot of a power-of-two size >= 2 x listed chunks (linear probing from store_ray_hash; an empty place has slot

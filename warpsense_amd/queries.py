@@ -1,5 +1,5 @@
 """What the window map (ws_map_*) and the chunk store (ws_store_*) share on the host side of their queries: the box, the call,
-the download or the device tensors of surface, mesh, ray cast, point sample, distance field and frontier, and the timing read-out."""
+the download or the device tensors of surface, mesh, ray cast, point sample, distance field, frontier and reach, and the timing read-out."""
 from __future__ import annotations
 
 import ctypes as C
@@ -9,7 +9,7 @@ import numpy as np
 from . import _lib
 from ._abi import _device_tensor, _i3, _is_device, _ptr
 from ._lib import WsError, check
-from .records import FRONTIER_CLUSTER, FRONTIER_RECORD, RAY, SAMPLE, SAMPLE_CLASSES, SURFACE_RECORD, VERT
+from .records import FRONTIER_CLUSTER, FRONTIER_RECORD, REACH_PATH_HEADER, REACH_PATH_RECORD, RAY, SAMPLE, SAMPLE_CLASSES, SURFACE_RECORD, VERT
 from .scan import DevicePoints
 
 
@@ -204,3 +204,57 @@ def _frontier_call(L, name, owner, lead, lo, hi, min_value, any_weight, clusters
     if int(got.value) != n or (clusters and int(got_k.value) != k):
         raise WsError("frontier: another call replaced the result before it was downloaded")
     return (rec, labels, table) if clusters else rec
+
+
+def _reach_call(L, name, owner, seeds, clear_d2, unknown_free, max_rounds, device):
+    """The reach call `name` (ws_map_reach, ws_store_reach) on owner.handle, over the owner's last distance result.  Returns (costs,
+    info): one uint32 cost per record of that result, shaped like it ((nx, ny, nz), or (nx, ny) for a column map: the box the
+    reach result carries, name + "_box"), and info = dict(seeded, reached, rounds).  owner keeps a device tensor's memory alive."""
+    seeds = np.ascontiguousarray(seeds, dtype=np.int32).reshape(-1, 3)
+    kept, reached, rounds = C.c_size_t(0), C.c_size_t(0), C.c_uint32(0)
+    flags = _lib.WS_REACH_UNKNOWN_FREE if unknown_free else 0
+    check(getattr(L, name)(owner.handle, _ptr(seeds), len(seeds), int(clear_d2), flags, int(max_rounds), C.byref(kept), C.byref(reached), C.byref(rounds)), name)
+    info = dict(seeded=int(kept.value), reached=int(reached.value), rounds=int(rounds.value))
+    cnt = C.c_size_t(0)
+    ptr = getattr(L, name + "_dev")(owner.handle, C.byref(cnt))
+    n = int(cnt.value)
+    ext, columns = np.zeros(3, dtype=np.uint32), C.c_int32(0)
+    check(getattr(L, name + "_box")(owner.handle, None, _ptr(ext), C.byref(columns)), name + "_box")
+    shape = tuple(int(v) for v in (ext[:2] if columns.value else ext))
+    if int(np.prod(shape, dtype=np.int64)) != n:
+        raise WsError("reach: another call replaced the result")
+    if device:
+        return _device_tensor(ptr, shape, "<i4", owner), info
+    cost = np.empty(n, dtype=np.uint32)
+    check(getattr(L, name + "_download")(owner.handle, _ptr(cost), n, C.byref(cnt)), name + "_download")
+    if int(cnt.value) != n:
+        raise WsError("reach: another call replaced the result before it was downloaded")
+    return cost.reshape(shape), info
+
+
+def _reach_lookup_call(L, name, owner, points):
+    """The costs of the owner's reach result at `points` (name: ws_map_reach_lookup, ws_store_reach_lookup): an (n, 3) or (n, 4) int32
+    numpy array -> uint32 numpy array; a CUDA tensor of such rows (the records of a frontier call with device=True) -> an int32 CUDA
+    tensor of the same bits, through the _dev form."""
+    if _is_device(points):
+        import torch
+        n, stride = int(points.shape[0]), int(points.shape[1])
+        out = torch.empty(n, dtype=torch.int32, device=points.device)
+        check(getattr(L, name + "_dev")(owner.handle, _ptr(points), n, stride, _ptr(out)), name + "_dev")
+        return out
+    points = np.ascontiguousarray(points, dtype=np.int32)
+    points = points.reshape(-1, points.shape[-1] if points.ndim == 2 else 3)
+    out = np.empty(len(points), dtype=np.uint32)
+    check(getattr(L, name)(owner.handle, _ptr(points), len(points), int(points.shape[1]), _ptr(out)), name)
+    return out
+
+
+def _reach_paths_call(L, name, owner, goals, cap_steps):
+    """The paths of the owner's reach result from `goals` ((g, 3) int32 world voxels) back to a seed.  Returns (headers, records): dtype
+    REACH_PATH_HEADER [g] and REACH_PATH_RECORD [g, cap_steps] (the first headers["written"][i] of row i are the path, goal first)."""
+    goals = np.ascontiguousarray(goals, dtype=np.int32).reshape(-1, 3)
+    hdr = np.zeros(len(goals), dtype=REACH_PATH_HEADER)
+    rec = np.zeros((len(goals), int(cap_steps)), dtype=REACH_PATH_RECORD)
+    if len(goals):
+        check(getattr(L, name)(owner.handle, _ptr(goals), len(goals), int(cap_steps), _ptr(hdr), _ptr(rec) if cap_steps else None), name)
+    return hdr, rec

@@ -137,3 +137,44 @@ def write_frontier_ply(path, records, resolution, labels=None):
         out.write(header.encode("ascii"))
         out.write(v.tobytes())
     return len(v)
+
+
+# ws_map_reach_paths: the header of a goal (status 0 reached, 1 not reachable, 2 outside the box) and one record of its path, 16 bytes each
+REACH_PATH_HEADER = np.dtype([("cost", "<u4"), ("steps", "<u4"), ("written", "<u4"), ("status", "<u4")])
+REACH_PATH_RECORD = np.dtype([("x", "<i4"), ("y", "<i4"), ("z", "<i4"), ("cost", "<u4")])
+REACH_UNREACHABLE = _lib.WS_REACH_UNREACHABLE
+
+
+def reach_mm(cost, resolution):
+    """The path length in millimetres that a cost of ws_map_reach stands for: cost * resolution / 10 (a face step weighs 10) as float64;
+    an unreachable cost becomes inf."""
+    cost = np.asarray(cost, dtype=np.uint32)
+    return np.where(cost == np.uint32(REACH_UNREACHABLE), np.inf, cost.astype(np.float64) * float(resolution) / 10.0)
+
+
+def write_path_ply(path, headers, records, resolution):
+    """The paths of reach_paths as a binary little-endian PLY: the written records of every reached goal as vertices (float x y z in
+    metres, voxel * resolution / 1000 in single precision, int path, uint cost) and an edge between consecutive records of a path.
+    Returns (vertices, edges) written."""
+    headers = np.asarray(headers, dtype=REACH_PATH_HEADER).reshape(-1)
+    records = np.asarray(records, dtype=REACH_PATH_RECORD).reshape(len(headers), -1)
+    rows = [records[i, :int(h["written"])] for i, h in enumerate(headers)]
+    n = sum(len(r) for r in rows)
+    v = np.empty(n, dtype=np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("path", "<i4"), ("cost", "<u4")]))
+    e = np.empty(sum(max(len(r) - 1, 0) for r in rows), dtype=np.dtype([("vertex1", "<i4"), ("vertex2", "<i4")]))
+    at = ae = 0
+    for i, r in enumerate(rows):
+        for name in "xyz":
+            v[name][at:at + len(r)] = r[name].astype(np.float32) * np.float32(resolution) / np.float32(1000.0)
+        v["path"][at:at + len(r)], v["cost"][at:at + len(r)] = i, r["cost"]
+        k = max(len(r) - 1, 0)
+        e["vertex1"][ae:ae + k], e["vertex2"][ae:ae + k] = np.arange(at, at + k), np.arange(at + 1, at + 1 + k)
+        at, ae = at + len(r), ae + k
+    header = ("ply\nformat binary_little_endian 1.0\ncomment warpsense_amd reach paths\n"
+              f"element vertex {len(v)}\nproperty float x\nproperty float y\nproperty float z\nproperty int path\nproperty uint cost\n"
+              f"element edge {len(e)}\nproperty int vertex1\nproperty int vertex2\nend_header\n")
+    with open(path, "wb") as out:
+        out.write(header.encode("ascii"))
+        out.write(v.tobytes())
+        out.write(e.tobytes())
+    return len(v), len(e)

@@ -10,7 +10,7 @@ from ._abi import _i3, _i3c, _ptr, pack_entry
 from ._lib import WS_MAP_AVG, check
 from .context import Context
 from .global_map import GlobalMap
-from .queries import _box_ptrs, _distance_call, _frontier_call, _mesh_call, _raycast_call, _sample_call, _surface_call, _timing
+from .queries import _box_ptrs, _distance_call, _frontier_call, _reach_call, _reach_lookup_call, _reach_paths_call, _mesh_call, _raycast_call, _sample_call, _surface_call, _timing
 
 
 class DeviceGlobalMap:
@@ -170,6 +170,32 @@ class DeviceGlobalMap:
     def frontier_timing(self, enable: int = -1):
         """device milliseconds of the count passes, the scan, the emit pass and the clustering of the last frontier() (ws_debug_store_frontier_timing)"""
         return _timing(self._L, "ws_debug_store_frontier_timing", self.handle, 4, enable)
+
+    def reach(self, seeds, clear_d2=0, unknown_free=False, max_rounds=0, device=False):
+        """The geodesic field over the LAST distance() result of this store (ws_store_reach; the rules are stated in
+        include/warpsense_hip.h): per record the cost of the cheapest 26-connected (columns: 8-connected) path from `seeds` ((n, 3)
+        int32 world voxels) over records that are free (unknown_free: or unknown) with d2 >= clear_d2; a face step weighs 10, an edge
+        step 14, a corner step 17, unreachable is 0xFFFFFFFF (reach_mm turns costs into millimetres).  max_rounds: 0 for the default
+        cap.  Returns the uint32 costs shaped like that distance result; `last_reach` keeps dict(seeded, reached, rounds).
+        device=True: a torch int32 tensor on the GPU that ALIASES the library's buffer, valid until the next reach()."""
+        cost, self.last_reach = _reach_call(self._L, "ws_store_reach", self, seeds, clear_d2, unknown_free, max_rounds, device)
+        return cost
+
+    def reach_lookup(self, points):
+        """The costs of the last reach() at world voxels: an (n, 3) or (n, 4) int32 numpy array gives a uint32 numpy array; a CUDA
+        tensor of such rows -- the records of frontier(device=True) -- gives an int32 CUDA tensor of the same bits.  Outside the box
+        of the reach result: 0xFFFFFFFF."""
+        return _reach_lookup_call(self._L, "ws_store_reach_lookup", self, points)
+
+    def reach_paths(self, goals, cap_steps=0):
+        """The paths of the last reach() from `goals` ((g, 3) int32 world voxels) back to a seed.  Returns (headers, records) of dtypes
+        REACH_PATH_HEADER [g] (cost, steps, written, status: 0 reached, 1 not reachable, 2 outside) and REACH_PATH_RECORD
+        [g, cap_steps] (x, y, z, cost; goal first); cap_steps = 0 asks for the headers alone."""
+        return _reach_paths_call(self._L, "ws_store_reach_paths", self, goals, cap_steps)
+
+    def reach_timing(self, enable: int = -1):
+        """device milliseconds of the seeding, of all rounds as one span and of the count pass of the last reach() (ws_debug_store_reach_timing)"""
+        return _timing(self._L, "ws_debug_store_reach_timing", self.handle, 3, enable)
 
     def flush_to(self, global_map: GlobalMap):
         """every chunk merged into a host GlobalMap: into its chunk cache (activate_chunk), or, for a map with a file, straight
