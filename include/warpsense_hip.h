@@ -511,6 +511,58 @@ int ws_debug_reach_active(ws_map *map, uint32_t *host, size_t capacity, size_t *
  * the tile of a column map along x, y, out[6] the default rounds per tile, out[7] = 0 */
 int ws_debug_reach_params(int32_t out[8]);
 
+/* View gain of a device map: what the sensor would see from there.  For m candidate origins and one fan of n directions shared by all
+ * of them, per view the UNKNOWN and the FREE samples its rays meet before an OCCUPIED voxel blocks them, as counts and weighted by k^2
+ * -- the unknown volume a pose opens onto, for many poses in one launch.  Integers only: the same bytes on every run.  All products
+ * are int64; "trunc" is C division, "floor" is floor division.
+ *   box: inclusive world voxels [lo, hi] under the rules of ws_map_frontier (both NULL: the whole window, each ring cell once; exactly
+ *     one NULL, outside the window, hi < lo or more voxels than the ring holds along an axis: WS_ERR_INVALID).
+ *   classes of a voxel, the frontier's, from its entry's two int16: VALID iff weight > 0; with WS_GAIN_ANY_WEIGHT iff weight != 0.
+ *     FREE iff valid and value >= min_value, OCCUPIED iff valid and value < min_value, UNKNOWN iff not valid.  min_value < 0 or
+ *     > 32767: WS_ERR_RANGE.
+ *   views: m origins o_j (int32 mm, map frame, m x 3 in host memory).  fan: n directions d_i (3 int32, n x 3 in host memory) under the
+ *     rules of ws_map_raycast: any length; a ray with |component| >= 2^30 or L == 0 is DEAD.
+ *   samples, exactly those of ws_map_raycast: step = max(res / 2, 1), K = max_range / step, L = floor(sqrt(dx^2 + dy^2 + dz^2)),
+ *     p_k = o_j + trunc(d_i k step / L) per axis for k = 0 .. K; the voxel of a sample is v_k = floor(p_k / res) per axis (ONE entry:
+ *     a class lookup, no interpolation).
+ *   walk of (view j, ray i), k ascending: v_k outside the box counts for nothing and blocks nothing, the walk goes on (the ray may
+ *     enter the box later).  v_k OCCUPIED: the ray is BLOCKED at k, this and all later samples count for nothing.  v_k UNKNOWN:
+ *     unknown += 1, unknown_k2 += k^2.  v_k FREE: free += 1, free_k2 += k^2.  Unknown voxels do not block.
+ *   k^2: the rays of a fan own disjoint solid angles, and a sample at range k step stands for a volume proportional to
+ *     (k step)^2 step: unknown_k2 step^3 dOmega is the unknown volume the view would see, without counting a voxel near the origin
+ *     once per ray.
+ *   record per view, 32 bytes, in view order: uint64 unknown_k2, uint64 free_k2, uint32 unknown, uint32 free, uint32 blocked (rays
+ *     that ended at an OCCUPIED voxel), uint32 live (rays that are not dead).
+ *   WS_GAIN_RAYS adds m x n records of 8 bytes, view-major: uint32 unknown (the UNKNOWN samples of that ray), int32 stop (the k of the
+ *     blocking sample, -1 for none, -2 for a dead ray).
+ *   limits: max_range <= 0, m == 0 with a non-NULL best_unknown_k2, unknown flag bits, bad `which`, a NULL array with a non-zero
+ *     count: WS_ERR_INVALID.  Otherwise n == 0 or m == 0: WS_OK, nothing written, the last result stays.  WS_ERR_RANGE: K > 8191,
+ *     n > 2^19, m > 65535, m n > 2^27 under WS_GAIN_RAYS, res > 1024, |o| + max_range + 2 res does not fit int32 on an axis.  With
+ *     these bounds no counter can overflow (the sum of k^2 of a ray is below 2^38, times 2^19 rays below 2^57).  On a refusal nothing
+ *     is launched and the last result stays.
+ * Synchronises (*best_unknown_k2, may be NULL, receives the largest unknown_k2 of the views).  The result buffers belong to the map,
+ * grow on demand and stay valid until the next view-gain call on it; they are apart from those of every other query, none of which
+ * invalidates this result.  Read-only on the maps; calls that use the buffers are serialised inside the library.  Nothing is allocated
+ * before the first call; an allocation that fails returns WS_ERR_HIP and leaves the map usable.
+ * The walk above defines the bytes; the implementation shortens it only where they stay the same: it keeps the class while the voxel
+ * stays, and ends a ray once it has left the box for good.  map_gain.hip: L, the per-step quotient and remainder and the signs
+ * depend on the direction alone and are prepared once per fan; then grid (ceil(n / 64), m), one lane per ray, the wave's lanes summed
+ * across lanes (ballot and popcount for the ray counts) and one integer atomic add per wave and field into the view's record. */
+#define WS_GAIN_DEFAULT 0u
+#define WS_GAIN_ANY_WEIGHT 1u
+#define WS_GAIN_RAYS 2u
+int ws_map_view_gain(ws_map *map, int which, const int32_t lo[3], const int32_t hi[3], const int32_t *origins_host, size_t m, const int32_t *dirs_host, size_t n,
+                     int32_t max_range_mm, int32_t min_value, uint32_t flags, uint64_t *best_unknown_k2);
+const void *ws_map_view_gain_records_dev(const ws_map *map, size_t *n); /* device memory, n x 32 bytes; NULL when n == 0 */
+const void *ws_map_view_gain_rays_dev(const ws_map *map, size_t *n);    /* n = views x rays records of 8 bytes; NULL unless the last call asked for them */
+/* copies at most cap_views view records and cap_rays ray records (prefixes) and always reports the totals; either host pointer may be
+ * NULL, and so may n_rays.  Asking for ray records that the last call did not produce: WS_ERR_INVALID */
+int ws_map_view_gain_download(ws_map *map, void *records_host, void *rays_host, size_t cap_views, size_t cap_rays, size_t *n_views, size_t *n_rays);
+/* Measurement entry, as ws_debug_surface_timing: ms_out receives the device time of the upload of origins and fan (with the clearing
+ * of the records), of the fan preparation and the march (which holds the wave-level reduction), and of the pass over the records
+ * that finds the maximum */
+int ws_debug_view_gain_timing(ws_map *map, int32_t enable, float ms_out[3]);
+
 /* ------------------------------------------------------------------ the global map in device memory ---- */
 /* ws_store: the device twin of HDF5GlobalMap (src/map/hdf5_global_map.cpp) -- a pool of 64^3-voxel chunks in HBM, so that a map shift
  * is a device-to-device copy in stream order: the leaving slabs, the window move and the entering slabs with revisits and corners,
@@ -799,6 +851,25 @@ int ws_store_reach_lookup(ws_store *st, const int32_t *points_host, size_t n, in
 int ws_store_reach_lookup_dev(ws_store *st, const int32_t *points_dev, size_t n, int32_t stride, uint32_t *cost_dev);
 int ws_store_reach_paths(ws_store *st, const int32_t *goals_host, size_t g, uint32_t cap_steps, void *headers_host, void *records_host);
 int ws_debug_store_reach_timing(ws_store *st, int32_t enable, float ms_out[3]);
+
+/* The view gain of the store: ws_map_view_gain over the chunks of the global map, wherever they lie.
+ *   field: a voxel of the box in an absent chunk is UNKNOWN: it counts, and it blocks nothing.
+ *   box: as for ws_store_frontier: inclusive world voxels; both NULL: the bounding box of the present chunks (an empty store: an empty
+ *     box, every sample is outside it); exactly one NULL or hi < lo: WS_ERR_INVALID; 2^19 or more present chunks in the box:
+ *     WS_ERR_RANGE.
+ *   map_resolution: the store does not know the map's resolution, the caller passes it (mm per voxel); <= 0: WS_ERR_INVALID.
+ *   rules: everything else is word for word the rule set of ws_map_view_gain: classes, views, fan, samples, walk, records, flags,
+ *     limits and refusals.
+ *   consequence: if a window holds the same voxels as the store inside a box, ws_map_view_gain on that window and box returns the
+ *     same bytes.
+ * The result belongs to the store and is apart from every other query's; the call synchronises, and the store's lock serialises it. */
+int ws_store_view_gain(ws_store *st, const int32_t lo[3], const int32_t hi[3], const int32_t *origins_host, size_t m, const int32_t *dirs_host, size_t n,
+                       int32_t max_range_mm, int32_t map_resolution, int32_t min_value, uint32_t flags, uint64_t *best_unknown_k2);
+const void *ws_store_view_gain_records_dev(const ws_store *st, size_t *n); /* device memory, n x 32 bytes; NULL when n == 0 */
+const void *ws_store_view_gain_rays_dev(const ws_store *st, size_t *n);    /* n = views x rays records of 8 bytes; NULL unless the last call asked for them */
+/* as ws_map_view_gain_download */
+int ws_store_view_gain_download(ws_store *st, void *records_host, void *rays_host, size_t cap_views, size_t cap_rays, size_t *n_views, size_t *n_rays);
+int ws_debug_store_view_gain_timing(ws_store *st, int32_t enable, float ms_out[3]);
 
 /* ------------------------------------------------------------------ TSDF update ---- */
 /* TSDFCuda::update_tsdf(scan_points, scanner_pos, up) — update_tsdf.cu:143-166.

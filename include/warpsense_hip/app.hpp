@@ -328,6 +328,12 @@ public:
   {
     return global_map_frontier(store_, clusters, min_value, any_weight, lo, hi);
   }
+  // what the sensor would see from candidate poses, through the chunks (visualization.hpp, ws_store_view_gain)
+  ViewGain view_gain(int resolution, const std::vector<rm::Pointi> &origins, const std::vector<rm::Pointi> &dirs, int32_t max_range_mm, int32_t min_value = 0,
+                     bool any_weight = false, bool with_rays = false, const rm::Pointi *lo = nullptr, const rm::Pointi *hi = nullptr)
+  {
+    return global_map_view_gain(store_, resolution, origins, dirs, max_range_mm, min_value, any_weight, with_rays, lo, hi);
+  }
   // path costs over the last distance() of the chunks, and the paths back from goals (visualization.hpp, ws_store_reach)
   ReachField reach(const std::vector<rm::Pointi> &seeds, int32_t clear_d2 = 0, bool unknown_free = false, uint32_t max_rounds = 0)
   {
@@ -363,6 +369,13 @@ inline Frontier global_map_frontier(DeviceGlobalMap &g, bool clusters = true, in
                                     const rm::Pointi *hi = nullptr)
 {
   return global_map_frontier(g.handle(), clusters, min_value, any_weight, lo, hi);
+}
+
+// the view gain of the device global map (visualization.hpp, ws_store_view_gain)
+inline ViewGain global_map_view_gain(DeviceGlobalMap &g, int resolution, const std::vector<rm::Pointi> &origins, const std::vector<rm::Pointi> &dirs, int32_t max_range_mm,
+                                     int32_t min_value = 0, bool any_weight = false, bool with_rays = false, const rm::Pointi *lo = nullptr, const rm::Pointi *hi = nullptr)
+{
+  return global_map_view_gain(g.handle(), resolution, origins, dirs, max_range_mm, min_value, any_weight, with_rays, lo, hi);
 }
 
 // the reach of the device global map and its paths (visualization.hpp, ws_store_reach)
@@ -756,6 +769,24 @@ public:
     const auto cut = [](int64_t v) { return (int32_t)std::min<int64_t>(std::max<int64_t>(v, INT32_MIN), INT32_MAX); };
     const rm::Pointi glo(cut(a[0] * cs - 1), cut(a[1] * cs - 1), cut(a[2] * cs - 1)), ghi(cut((b[0] + 1) * cs), cut((b[1] + 1) * cs), cut((b[2] + 1) * cs));
     return device_global_map_->frontier(clusters, min_value, any_weight, &glo, &ghi);
+  }
+  // What the sensor would see from `origins` (map frame, mm) along the fan `dirs` in the averaged map (local_map_view_gain)
+  ViewGain view_gain(const std::vector<rm::Pointi> &origins, const std::vector<rm::Pointi> &dirs, int32_t max_range_mm, int32_t min_value = 0, bool any_weight = false,
+                     bool with_rays = false, const rm::Pointi *lo = nullptr, const rm::Pointi *hi = nullptr)
+  {
+    return local_map_view_gain(gpu_.tsdf(), origins, dirs, max_range_mm, WS_MAP_AVG, min_value, any_weight, with_rays, lo, hi);
+  }
+  // The same through everything the run has seen: the window into the device chunks, as global_mesh does, then the view gain of the
+  // store (without a box: the bounding box of the chunks)
+  ViewGain global_view_gain(const std::vector<rm::Pointi> &origins, const std::vector<rm::Pointi> &dirs, int32_t max_range_mm, int32_t min_value = 0,
+                            bool any_weight = false, bool with_rays = false, const rm::Pointi *lo = nullptr, const rm::Pointi *hi = nullptr)
+  {
+    if (!device_global_map_) throw std::logic_error("global_view_gain: no DeviceGlobalMap attached");
+    wait_shift();
+    rm::Pointi wlo, whi;
+    local_map_.window(wlo, whi);
+    WS_CHECK(ws_store_save_box(device_global_map_->handle(), gpu_.tsdf().handle(), WS_MAP_AVG, &wlo.x, &whi.x));
+    return device_global_map_->view_gain(params_.map_resolution, origins, dirs, max_range_mm, min_value, any_weight, with_rays, lo, hi);
   }
   // How far every voxel of the window (or of [lo, hi]) is from `seeds` (world voxels) along free space that keeps clear_vox voxels
   // from the obstacles: the distance field with a range one voxel beyond the clearance, then local_map_reach on it

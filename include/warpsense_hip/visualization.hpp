@@ -11,6 +11,7 @@
 //   global_map_distance  (no counterpart)                                                     the cost map of the whole run, over ws_store_distance
 //   local_map_frontier / global_map_frontier   (no counterpart)                               where the known world ends, over ws_map_frontier / ws_store_frontier
 //   local_map_reach / global_map_reach, local_map_reach_paths / global_map_reach_paths   (no counterpart)   path costs and paths, over ws_map_reach / ws_store_reach
+//   local_map_view_gain / global_map_view_gain   (no counterpart)                             what the sensor would see from candidate poses, over ws_map_view_gain / ws_store_view_gain
 //   local_map_skeleton   publish_local_map_skeleton  map.h:175-227   the 24 end points of the window's line list (host only)
 //
 // The reference walks every voxel of a host map (after a whole-map download for the CUDA map, test/pcd2tsdf.cpp:134-137); here
@@ -126,6 +127,65 @@ inline Frontier global_map_frontier(ws_store *store, bool clusters = true, int32
   size_t got = 0, got_k = 0;
   WS_CHECK(ws_store_frontier_download(store, n ? out.records.data() : nullptr, n && clusters ? out.labels.data() : nullptr,
                                       k && clusters ? out.clusters.data() : nullptr, n, k, &got, &got_k));
+  return out;
+}
+
+struct ViewGainRecord // one record of ws_map_view_gain per view
+{
+  uint64_t unknown_k2, free_k2; // the sums of k^2 over the UNKNOWN / FREE samples
+  uint32_t unknown, free_n;     // UNKNOWN / FREE samples
+  uint32_t blocked, live;       // rays that ended at an OCCUPIED voxel; rays that are not dead
+};
+struct ViewGainRay // with rays: one record per (view, ray), view-major
+{
+  uint32_t unknown; // the UNKNOWN samples of the ray
+  int32_t stop;     // the k of the blocking sample, -1 for none, -2 for a dead ray
+};
+static_assert(sizeof(ViewGainRecord) == 32 && sizeof(ViewGainRay) == 8, "ws_map_view_gain writes 32-byte view records and 8-byte ray records");
+
+struct ViewGain
+{
+  std::vector<ViewGainRecord> records; // one per origin, in their order
+  std::vector<ViewGainRay> rays;       // [view][ray]; empty unless asked for
+  uint64_t best_unknown_k2 = 0;        // the largest unknown_k2 of the views
+};
+
+// What the sensor would see from `origins` (map frame, mm) along the one fan `dirs` (any length, the rules of local_map_raycast) in
+// `which` (the rules: warpsense_hip.h at ws_map_view_gain) inside the inclusive world-voxel box [lo, hi] (both nullptr: the whole
+// window): per view the UNKNOWN and FREE samples before a voxel with value < min_value blocks the ray, as counts and weighted by k^2.
+// No origin or no direction: an empty result, nothing is called.
+inline ViewGain local_map_view_gain(cuda::TSDFCuda &tsdf, const std::vector<rmagine::Pointi> &origins, const std::vector<rmagine::Pointi> &dirs, int32_t max_range_mm,
+                                    int which = WS_MAP_AVG, int32_t min_value = 0, bool any_weight = false, bool with_rays = false, const rmagine::Pointi *lo = nullptr,
+                                    const rmagine::Pointi *hi = nullptr)
+{
+  ViewGain out;
+  if (origins.empty() || dirs.empty()) return out;
+  const uint32_t flags = (any_weight ? WS_GAIN_ANY_WEIGHT : 0u) | (with_rays ? WS_GAIN_RAYS : 0u);
+  WS_CHECK(ws_map_view_gain(tsdf.handle(), which, lo ? &lo->x : nullptr, hi ? &hi->x : nullptr, &origins[0].x, origins.size(), &dirs[0].x, dirs.size(), max_range_mm,
+                            min_value, flags, &out.best_unknown_k2));
+  out.records.resize(origins.size());
+  if (with_rays) out.rays.resize(origins.size() * dirs.size());
+  size_t got = 0, got_rays = 0;
+  WS_CHECK(ws_map_view_gain_download(tsdf.handle(), out.records.data(), with_rays ? out.rays.data() : nullptr, out.records.size(), out.rays.size(), &got, &got_rays));
+  return out;
+}
+
+// The same through the global map in device memory (the rules: warpsense_hip.h at ws_store_view_gain) inside the inclusive world-voxel
+// box [lo, hi] (both nullptr: the bounding box of the present chunks).  Voxels of absent chunks are unknown: they count and block
+// nothing.  resolution: the map's (the store does not know it).  (app.hpp adds the overload that takes a DeviceGlobalMap.)
+inline ViewGain global_map_view_gain(ws_store *store, int resolution, const std::vector<rmagine::Pointi> &origins, const std::vector<rmagine::Pointi> &dirs,
+                                     int32_t max_range_mm, int32_t min_value = 0, bool any_weight = false, bool with_rays = false, const rmagine::Pointi *lo = nullptr,
+                                     const rmagine::Pointi *hi = nullptr)
+{
+  ViewGain out;
+  if (origins.empty() || dirs.empty()) return out;
+  const uint32_t flags = (any_weight ? WS_GAIN_ANY_WEIGHT : 0u) | (with_rays ? WS_GAIN_RAYS : 0u);
+  WS_CHECK(ws_store_view_gain(store, lo ? &lo->x : nullptr, hi ? &hi->x : nullptr, &origins[0].x, origins.size(), &dirs[0].x, dirs.size(), max_range_mm, resolution,
+                              min_value, flags, &out.best_unknown_k2));
+  out.records.resize(origins.size());
+  if (with_rays) out.rays.resize(origins.size() * dirs.size());
+  size_t got = 0, got_rays = 0;
+  WS_CHECK(ws_store_view_gain_download(store, out.records.data(), with_rays ? out.rays.data() : nullptr, out.records.size(), out.rays.size(), &got, &got_rays));
   return out;
 }
 

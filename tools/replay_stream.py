@@ -77,6 +77,11 @@ def main():
                     "window (TSDFMapping.reachable_frontier: ws_map_distance, ws_map_reach, ws_map_frontier, ws_map_reach_lookup_dev, ws_map_reach_paths) as "
                     "binary little-endian PLY (vertices with path number and cost, edges) into DIR")
     ap.add_argument("--reach-clearance-m", type=float, default=0.2, metavar="M", help="... that keep M metres from the obstacles")
+    ap.add_argument("--next-view-csv", default=None, metavar="FILE", help="after every TSDF update: the next best view among the reachable frontier clusters of the "
+                    "window (TSDFMapping.next_best_view: reachable_frontier, ws_map_view_gain, rank_views) as one line of FILE: scan number, the winner's goal "
+                    "voxel x y z, its path cost, its unknown_k2, the number of candidates (-1 -1 -1, 4294967295 and 0 without a candidate); the "
+                    "clearance is --reach-clearance-m")
+    ap.add_argument("--next-view-range-m", type=float, default=5.0, metavar="M", help="... with rays of M metres")
     ap.add_argument("--global-frontier-ply", default=None, metavar="FILE", help="after the last scan: the clustered frontier of the WHOLE run from the device "
                     "global map (TSDFMapping.global_frontier, ws_store_frontier) as PLY; needs --device-global-map")
     ap.add_argument("--global-raycast-ply", default=None, metavar="FILE", help="after the last scan: the predicted scan from the pose of the FIRST scan, "
@@ -152,6 +157,11 @@ def main():
     reach = {"files": 0, "clusters": 0, "reachable": 0, "rounds": 0, "seconds": 0.0}
     if args.reach_ply:
         os.makedirs(args.reach_ply, exist_ok=True)
+    next_view = {"lines": 0, "candidates": 0, "seconds": 0.0}
+    next_view_file = None
+    if args.next_view_csv:
+        next_view_file = open(args.next_view_csv, "w")
+        next_view_file.write("scan,goal_x,goal_y,goal_z,path_cost,unknown_k2,candidates\n")
     updates_seen = 0
     if args.mesh_ply:
         os.makedirs(args.mesh_ply, exist_ok=True)
@@ -190,6 +200,19 @@ def main():
                 reach["files"] += 1
             reach["clusters"], reach["reachable"], reach["rounds"] = int(len(got["table"])), int(len(got["reachable"])), int(app.gpu_.last_reach["rounds"])
             reach["seconds"] += time.perf_counter() - ts
+        if next_view_file is not None and app.n_updates > updates_seen:  # after every update of the map: where to look next
+            ts = time.perf_counter()
+            pose_m = app.pose_.astype(np.float64).copy()
+            pose_m[:3, 3] /= 1000.0  # (the app keeps millimetres)
+            nbv = app.gpu_.next_best_view(pose=pose_m, clearance_m=args.reach_clearance_m, max_range_m=args.next_view_range_m)
+            win = nbv["winner"]
+            goal = nbv["goal"][win] if win >= 0 else (-1, -1, -1)
+            cost = int(nbv["cost"][win]) if win >= 0 else 0xFFFFFFFF
+            gain = int(nbv["records"]["unknown_k2"][nbv["order"][0]]) if win >= 0 else 0
+            next_view_file.write(f"{k + 1},{int(goal[0])},{int(goal[1])},{int(goal[2])},{cost},{gain},{len(nbv['candidates'])}\n")
+            next_view["lines"] += 1
+            next_view["candidates"] = int(len(nbv["candidates"]))
+            next_view["seconds"] += time.perf_counter() - ts
         updates_seen = app.n_updates
         if args.surface_ply and (k + 1) % max(args.surface_every, 1) == 0:
             ts = time.perf_counter()
@@ -294,6 +317,8 @@ def main():
         vals = [t[key] for t in app.timings if key in t]
         stages[key + "_ms"] = 1000.0 * float(np.mean(vals)) if vals else None
     true_last = np.array([1000.0 * args.step * (args.scans - 1), 500.0 * args.step * (args.scans - 1), 0.0])
+    if next_view_file is not None:
+        next_view_file.close()
     t3 = time.perf_counter()
     app.terminate()
     t4 = time.perf_counter()
@@ -315,6 +340,7 @@ def main():
                       "global_surface_ply": global_surface,
                       "frontier_ply": frontier if args.frontier_ply else None,
                       "reach_ply": reach if args.reach_ply else None,
+                      "next_view_csv": next_view if args.next_view_csv else None,
                       "global_frontier_ply": global_frontier,
                       "global_raycast_ply": global_raycast,
                       "global_distance_npy": global_distance,

@@ -11,6 +11,8 @@ from ._lib import (WS_INTEGRATE_DENSE, WS_INTEGRATE_SPARSE, WS_INTEGRATE_SPARSE_
 from .records import FRONTIER_CLUSTER, FRONTIER_RECORD, frontier_goals, write_frontier_ply  # noqa: F401
 from .records import REACH_PATH_HEADER, REACH_PATH_RECORD, REACH_UNREACHABLE, reach_mm, write_path_ply  # noqa: F401
 from ._lib import WS_REACH_DEFAULT, WS_REACH_UNKNOWN_FREE, WS_REACH_UNREACHABLE  # noqa: F401
+from .records import VIEW_GAIN_RAY, VIEW_GAIN_RECORD, gain_volume_m3, rank_views, view_fan  # noqa: F401
+from ._lib import WS_GAIN_ANY_WEIGHT, WS_GAIN_DEFAULT, WS_GAIN_RAYS  # noqa: F401
 
 __all__ = [n for n in dir() if not n.startswith("_")]
 from .app import App  # noqa: F401,E402

@@ -53,6 +53,8 @@ EXPORTS = [
     "ws_debug_reach_params", "ws_debug_reach_active",
     "ws_store_reach", "ws_store_reach_dev", "ws_store_reach_download", "ws_store_reach_lookup", "ws_store_reach_lookup_dev", "ws_store_reach_paths",
     "ws_debug_store_reach_timing",
+    "ws_map_view_gain", "ws_map_view_gain_records_dev", "ws_map_view_gain_rays_dev", "ws_map_view_gain_download", "ws_debug_view_gain_timing",
+    "ws_store_view_gain", "ws_store_view_gain_records_dev", "ws_store_view_gain_rays_dev", "ws_store_view_gain_download", "ws_debug_store_view_gain_timing",
 ]
 WS_SURFACE_RECORDS, WS_SURFACE_MARKER = 0, 1
 WS_MESH_DEFAULT, WS_MESH_ANY_WEIGHT = 0, 1
@@ -63,6 +65,7 @@ SAMPLE_CLASSES = ("unknown", "free", "surface", "inside")  # class c of a sample
 WS_DISTANCE_DEFAULT, WS_DISTANCE_ANY_WEIGHT, WS_DISTANCE_UNKNOWN_OCCUPIED, WS_DISTANCE_COLUMNS = 0, 1, 2, 4
 WS_FRONTIER_DEFAULT, WS_FRONTIER_ANY_WEIGHT, WS_FRONTIER_CLUSTERS = 0, 1, 2
 WS_REACH_DEFAULT, WS_REACH_UNKNOWN_FREE, WS_REACH_UNREACHABLE = 0, 1, 0xFFFFFFFF
+WS_GAIN_DEFAULT, WS_GAIN_ANY_WEIGHT, WS_GAIN_RAYS = 0, 1, 2
 
 
 class WsError(RuntimeError):
@@ -225,6 +228,15 @@ def load() -> C.CDLL:
     L.ws_debug_reach_timing.argtypes = [vp, i32, vp]
     L.ws_debug_store_reach_timing.argtypes = [vp, i32, vp]
     L.ws_debug_reach_params.argtypes = [vp]
+    L.ws_map_view_gain.argtypes = [vp, C.c_int, vp, vp, vp, sz, vp, sz, i32, i32, u32, vp]
+    L.ws_store_view_gain.argtypes = [vp, vp, vp, vp, sz, vp, sz, i32, i32, i32, u32, vp]
+    for owner in ("map", "store"):
+        for part in ("records", "rays"):
+            f = getattr(L, f"ws_{owner}_view_gain_{part}_dev")
+            f.argtypes, f.restype = [vp, P(sz)], vp
+        getattr(L, f"ws_{owner}_view_gain_download").argtypes = [vp, vp, vp, sz, sz, P(sz), P(sz)]
+    L.ws_debug_view_gain_timing.argtypes = [vp, i32, vp]
+    L.ws_debug_store_view_gain_timing.argtypes = [vp, i32, vp]
     L.ws_debug_reach_active.argtypes = [vp, vp, sz, P(sz)]
     L.ws_shift_plan.argtypes = [vp, vp, vp, vp, P(ShiftPlan)]
     L.ws_shift_begin.argtypes = [vp, vp, u32, P(vp)]

@@ -681,3 +681,71 @@ int ws_debug_reach_params(int32_t out[8])
   std::copy(v, v + 8, out);
   return WS_OK;
 }
+
+// ---- view gain: what the host core of ws_api.h (gain_check, gain_run) needs beside it, for the window of a map here and for the chunks
+// of the store in api_store.hip
+const void *ws::gain_records_dev(const GainResult *q, size_t *n)
+{
+  if (n) *n = q ? q->m : 0;
+  return q && q->m ? q->rec.p : nullptr;
+}
+
+const void *ws::gain_rays_dev(const GainResult *q, size_t *n)
+{
+  const bool have = q && q->has_rays && q->m;
+  if (n) *n = have ? q->m * q->n : 0;
+  return have ? q->rays.p : nullptr;
+}
+
+// `name`, `call`: the download entry point, and the entry point whose flag it misses
+int ws::gain_download(const GainResult &q, hipStream_t s, const char *name, const char *call, void *records_host, void *rays_host, size_t cap_views, size_t cap_rays,
+                      size_t *n_views, size_t *n_rays)
+{
+  const size_t total = q.has_rays ? q.m * q.n : 0;
+  *n_views = q.m;
+  if (n_rays) *n_rays = total;
+  if (q.m && !q.has_rays && rays_host && cap_rays) return invalid(std::string(name) + ": the last " + call + " did not ask for WS_GAIN_RAYS");
+  const size_t k = records_host ? std::min(cap_views, q.m) : 0, kr = rays_host ? std::min(cap_rays, total) : 0;
+  if (k) WS_HIP(hipMemcpyAsync(records_host, q.rec.p, k * 32, hipMemcpyDeviceToHost, s));
+  if (kr) WS_HIP(hipMemcpyAsync(rays_host, q.rays.p, kr * 8, hipMemcpyDeviceToHost, s));
+  if (k || kr) WS_HIP(hipStreamSynchronize(s));
+  return WS_OK;
+}
+
+// ---- view gain: the unknown volume m candidate poses would see along one fan, map_gain.hip (the rules are stated in warpsense_hip.h)
+int ws_map_view_gain(ws_map *m, int which, const int32_t lo[3], const int32_t hi[3], const int32_t *origins_host, size_t n_views, const int32_t *dirs_host, size_t n,
+                     int32_t max_range_mm, int32_t min_value, uint32_t flags, uint64_t *best_unknown_k2)
+{
+  WS_TRY(gain_check("ws_map_view_gain", !m || (which != WS_MAP_AVG && which != WS_MAP_NEW), lo, hi, origins_host, n_views, dirs_host, n, max_range_mm, min_value,
+                    m ? m->res : 0, flags, best_unknown_k2, [] { return (int)WS_OK; }));
+  WS_SETTLE(m);
+  std::lock_guard<std::mutex> lock(m->gain.mu);
+  GainResult &q = m->gain;
+  int32_t l[3], ext[3];
+  WS_TRY(resolve_box(m, which, lo, hi, true, "ws_map_view_gain", l, ext));
+  if (n_views == 0 || n == 0) return WS_OK; // nothing written, the last result stays
+  GainCall c;
+  c.m = n_views, c.n = n;
+  for (int k = 0; k < 3; ++k) c.lo[k] = l[k], c.hi[k] = l[k] + ext[k] - 1;
+  c.res = m->res, c.max_range = max_range_mm, c.min_value = min_value, c.flags = flags;
+  WS_TRY(gain_run(q, m->ctx->stream, c, origins_host, dirs_host, best_unknown_k2, false, [] { return (int)WS_OK; }, [&] { return launch_map_gain(m, q, which, c); }));
+  return map_take_error(m);
+}
+
+const void *ws_map_view_gain_records_dev(const ws_map *m, size_t *n) { return gain_records_dev(m ? &m->gain : nullptr, n); }
+
+const void *ws_map_view_gain_rays_dev(const ws_map *m, size_t *n) { return gain_rays_dev(m ? &m->gain : nullptr, n); }
+
+int ws_map_view_gain_download(ws_map *m, void *records_host, void *rays_host, size_t cap_views, size_t cap_rays, size_t *n_views, size_t *n_rays)
+{
+  if (!m || !n_views) return invalid("ws_map_view_gain_download: NULL argument");
+  std::lock_guard<std::mutex> lock(m->gain.mu);
+  return gain_download(m->gain, m->ctx->stream, "ws_map_view_gain_download", "ws_map_view_gain", records_host, rays_host, cap_views, cap_rays, n_views, n_rays);
+}
+
+int ws_debug_view_gain_timing(ws_map *m, int32_t enable, float ms_out[3])
+{
+  if (!m) return invalid("ws_debug_view_gain_timing: map is NULL");
+  std::lock_guard<std::mutex> lock(m->gain.mu);
+  return query_timing(m->ctx->stream, m->gain.timer, enable, ms_out, GAIN_PAIRS, 3);
+}

@@ -975,3 +975,47 @@ int ws_debug_store_reach_timing(ws_store *st, int32_t enable, float ms_out[3])
   std::lock_guard<std::mutex> lock(st->mu);
   return query_timing(st->ctx->stream, st->reach.timer, enable, ms_out, REACH_PAIRS, 3);
 }
+
+// ---- the view gain of the store: the rules and the host flow of ws_map_view_gain over the chunks, store_gain.hip
+int ws_store_view_gain(ws_store *st, const int32_t lo[3], const int32_t hi[3], const int32_t *origins_host, size_t n_views, const int32_t *dirs_host, size_t n,
+                       int32_t max_range_mm, int32_t map_resolution, int32_t min_value, uint32_t flags, uint64_t *best_unknown_k2)
+{
+  std::unique_lock<std::mutex> lock;
+  GainCall c;
+  WS_TRY(gain_check("ws_store_view_gain", !st, lo, hi, origins_host, n_views, dirs_host, n, max_range_mm, min_value, map_resolution, flags, best_unknown_k2, [&] {
+    if (map_resolution <= 0) return invalid("ws_store_view_gain: map_resolution <= 0");
+    for (int k = 0; k < 3 && lo; ++k)
+      if (hi[k] < lo[k]) return invalid("ws_store_view_gain: hi < lo");
+    return (int)WS_OK;
+  }));
+  servers_leave(st->ctx);
+  WS_TRY(store_query_box(st, "ws_store_view_gain", lo, hi, false, lock, c.lo, c.hi)); // (without a box: the bounding box of the chunks; none: empty)
+  if (n_views == 0 || n == 0) return WS_OK; // nothing written, the last result stays
+  ws_store::Gain &q = st->gain;
+  std::vector<StoreRaySlot> listed;
+  if (c.lo[0] <= c.hi[0]) store_list(st, c.lo, c.hi, listed);
+  if (listed.size() >= (1u << 19)) return range_error("ws_store_view_gain", ": the box overlaps 2^19 present chunks or more");
+  c.m = n_views, c.n = n;
+  c.res = map_resolution, c.max_range = max_range_mm, c.min_value = min_value, c.flags = flags;
+  return gain_run(
+      q, st->ctx->stream, c, origins_host, dirs_host, best_unknown_k2, store_lookup_places(listed.size()) > q.table_host.cap,
+      [&] { return store_lookup_fill(q.table_host, q.table_dev, listed); }, [&] { return store_enqueued(st, launch_store_gain(st, q, c, (uint32_t)listed.size())); });
+}
+
+const void *ws_store_view_gain_records_dev(const ws_store *st, size_t *n) { return gain_records_dev(st ? &st->gain : nullptr, n); }
+
+const void *ws_store_view_gain_rays_dev(const ws_store *st, size_t *n) { return gain_rays_dev(st ? &st->gain : nullptr, n); }
+
+int ws_store_view_gain_download(ws_store *st, void *records_host, void *rays_host, size_t cap_views, size_t cap_rays, size_t *n_views, size_t *n_rays)
+{
+  if (!st || !n_views) return invalid("ws_store_view_gain_download: NULL argument");
+  std::lock_guard<std::mutex> lock(st->mu);
+  return gain_download(st->gain, st->ctx->stream, "ws_store_view_gain_download", "ws_store_view_gain", records_host, rays_host, cap_views, cap_rays, n_views, n_rays);
+}
+
+int ws_debug_store_view_gain_timing(ws_store *st, int32_t enable, float ms_out[3])
+{
+  if (!st) return invalid("ws_debug_store_view_gain_timing: store is NULL");
+  std::lock_guard<std::mutex> lock(st->mu);
+  return query_timing(st->ctx->stream, st->gain.timer, enable, ms_out, GAIN_PAIRS, 3);
+}

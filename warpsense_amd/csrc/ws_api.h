@@ -364,6 +364,68 @@ int reach_run(ReachResult &q, const DistResult &d, hipStream_t s, const char *na
   return reach_rounds(q, d, s, name, seeds, n_seeds, clear_d2, flags, max_rounds, n_seeded, n_reached, rounds);
 }
 
+// ---- view gain (map_gain.hip for the window of a map, store_gain.hip for the chunks of the store).  gain_check: every refusal that
+// needs neither a lock nor the box, `bad` and more() as above; among these the INVALID ones come first.  The box's own refusals (outside
+// the window, more voxels than the ring holds) follow under the lock, behind the ranges, as in ws_map_frontier.  gain_run: the flow of a checked call with
+// m, n > 0, from "the old result is dropped" to the publish; own_room, prepare() and launch() are those of raycast_run.
+const void *gain_records_dev(const GainResult *q, size_t *n);
+const void *gain_rays_dev(const GainResult *q, size_t *n);
+int gain_download(const GainResult &q, hipStream_t s, const char *name, const char *call, void *records_host, void *rays_host, size_t cap_views, size_t cap_rays,
+                  size_t *n_views, size_t *n_rays);
+constexpr int GAIN_PAIRS[3][2] = {{0, 1}, {1, 2}, {2, 3}};
+
+template <typename More>
+int gain_check(const char *name, bool bad, const int32_t *lo, const int32_t *hi, const int32_t *origins, size_t m, const int32_t *dirs, size_t n, int32_t max_range,
+               int32_t min_value, int32_t res, uint32_t flags, const uint64_t *best, More more)
+{
+  const uint32_t known = WS_GAIN_ANY_WEIGHT | WS_GAIN_RAYS;
+  if (bad || (flags & ~known) || ((lo == nullptr) != (hi == nullptr)) || (m && !origins) || (n && !dirs)) return invalid(std::string(name) + ": bad argument");
+  if (max_range <= 0) return invalid(std::string(name) + ": max_range_mm <= 0");
+  if (m == 0 && best) return invalid(std::string(name) + ": no view, but a result is asked for");
+  WS_TRY(more());
+  if (min_value < 0 || min_value > 32767) return range_error(name, ": min_value must be 0 .. 32767 (a raw int16 value; 0: any non-negative value)");
+  if (res > 1024) return range_error(name, ": the resolution must not exceed 1024 mm");
+  if (max_range / (res / 2 > 1 ? res / 2 : 1) > 8191) return range_error(name, ": more than 8192 samples per ray (max_range / step > 8191)");
+  if (n > ((size_t)1 << 19)) return range_error(name, ": more than 2^19 rays in the fan");
+  if (m > 65535) return range_error(name, ": more than 65535 views");
+  if ((flags & WS_GAIN_RAYS) && m * n > ((size_t)1 << 27)) return range_error(name, ": more than 2^27 ray records under WS_GAIN_RAYS");
+  for (size_t j = 0; j < 3 * m; ++j)
+  {
+    const int64_t o = origins[j];
+    if ((o < 0 ? -o : o) + (int64_t)max_range + 2 * (int64_t)res > (int64_t)INT32_MAX) return range_error(name, ": |origin| + max_range + 2 res does not fit int32");
+  }
+  return WS_OK;
+}
+
+template <typename Prepare, typename Launch>
+int gain_run(GainResult &q, hipStream_t s, const GainCall &c, const int32_t *origins, const int32_t *dirs, uint64_t *best, bool own_room, Prepare prepare, Launch launch)
+{
+  WS_TRY(q.timer.arm());
+  q.m = q.n = 0; // (whatever happens from here on, the old result is gone: its buffers may be replaced)
+  q.has_rays = false;
+  const bool rays = (c.flags & WS_GAIN_RAYS) != 0;
+  WS_TRY(q.best.alloc(1));
+  if (c.m > q.org.cap || c.m > q.rec.cap || c.n > q.dirs.cap || c.n > q.prep.cap || (rays && c.m * c.n > q.rays.cap) || own_room)
+  {
+    WS_HIP(hipStreamSynchronize(s));
+    WS_TRY(q.org.grow(c.m, 3 * sizeof(int32_t)));
+    WS_TRY(q.rec.grow(c.m, 32));
+    WS_TRY(q.dirs.grow(c.n, 3 * sizeof(int32_t)));
+    WS_TRY(q.prep.grow(c.n, 32));
+    if (rays) WS_TRY(q.rays.grow(c.m * c.n, 8));
+  }
+  WS_TRY(prepare());
+  q.timer.mark(0, s);
+  WS_HIP(hipMemcpyAsync(q.org.p, origins, c.m * 3 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  WS_HIP(hipMemcpyAsync(q.dirs.p, dirs, c.n * 3 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  WS_TRY(launch());
+  WS_HIP(hipStreamSynchronize(s));
+  q.m = c.m, q.n = c.n;
+  q.has_rays = rays;
+  if (best) *best = (uint64_t)*q.best.host;
+  return WS_OK;
+}
+
 // ---- map shift: one shift of both maps' windows, for ws_shift_begin (api_map.hip) and ws_shift_device (api_store.hip), which
 // differ in what happens to a slab that leaves and to one that enters.  `name` is the entry point and `open_text` its words for a
 // ticket in flight.  After the shared refusals and the plan (into `plan`): ready() before the first launch; per step leave(i, par),

@@ -466,6 +466,18 @@ struct ReachResult
     for (DevBuf *b : {&cost, &mark, &list, &seeds, &pts, &out, &goals, &hdr, &steps}) b->release();
   }
 };
+// ... and a view-gain call (ws_map::Gain, ws_store::Gain; the one flow is gain_run in ws_api.h, the rules are in ws_gain.h)
+struct GainResult
+{
+  QueryTimer timer;                    // 0 upload 1 fan preparation and march 2 maximum 3
+  DevBuf org, dirs;                    // int32 [views][3], int32 [rays][3]: staging of the host arrays
+  DevBuf prep;                         // 32 bytes per ray of the fan: what depends on the direction alone
+  DevBuf rec, rays;                    // 32-byte view records; 8-byte ray records [views][rays]
+  DevCounter best;                     // the largest unknown_k2 of the last call
+  size_t m = 0, n = 0;                 // views and rays of the last call
+  bool has_rays = false;               // the last call also wrote `rays`
+  void release() { timer.release(), best.release(), m = n = 0; for (DevBuf *b : {&org, &dirs, &prep, &rec, &rays}) b->release(); }
+};
 
 } // namespace ws
 
@@ -567,6 +579,10 @@ struct ws_map
   {
     std::mutex mu;
   } reach;
+  struct Gain : ws::GainResult // ws_map_view_gain (map_gain.hip)
+  {
+    std::mutex mu;
+  } gain;
   // The scan whose verdict (did its records fit the pool?) has not been looked at yet: ws_tsdf_update* return after the
   // launches, like the reference's update_tsdf (update_tsdf.cu:165); the next call that takes this map settles it first
   // (settle_tsdf: the verdict is in host-mapped memory ~0.35 ms after the launches) and repeats the scan if it was aborted.
@@ -597,7 +613,7 @@ struct ws_map
                           &tile_list, &rec, &big_keys, &block_stats, &counters, &box_stage, &shift_stage_dev})
       b->release();
     for (ws::HostBlock *b : {&counters_host, &status, &shift_stage_host}) b->release();
-    surf.release(), mesh.release(), ray.release(), dist.release(), sample.release(), frontier.release(), reach.release();
+    surf.release(), mesh.release(), ray.release(), dist.release(), sample.release(), frontier.release(), reach.release(), gain.release();
   }
 };
 
@@ -753,8 +769,15 @@ struct ws_store
     void release() { FrontierResult::release(), mask.release(), table_host.release(), table_dev.release(); }
   } frontier;
   ws::ReachResult reach; // ws_store_reach (map_reach.hip: it reads the records of `dist` alone)
+  struct Gain : ws::GainResult // ws_store_view_gain (store_gain.hip)
+  {
+    ws::HostBlock table_host;            // StoreRaySlot, pinned: the call's chunk lookup; free again when the call returns, which synchronises
+    ws::DevBuf table_dev;                // ... and the copy the kernels read
+    void release() { GainResult::release(), table_host.release(), table_dev.release(); }
+  } gain;
   void release()
   {
+    gain.release();
     reach.release();
     frontier.release();
     surf.release();
@@ -961,6 +984,19 @@ int launch_store_raycast(ws_store *st, ws_store::Ray &q, const StoreRayCall &c, 
 // store_sample.hip: the passes of map_sample.hip over the chunks the call lists, found through the lookup of store_raycast.hip in
 // q.table_host (`c`: the box and the live box of a ray cast)
 int launch_store_sample(ws_store *st, ws_store::Sample &q, const StoreRayCall &c, const int32_t *pts_dev, size_t n, int32_t band, uint32_t flags);
+
+// map_gain.hip, store_gain.hip: the view gain of a checked call (gain_check, ws_api.h) whose origins and directions are in q.org and
+// q.dirs: clear, fan preparation, march, maximum (events 1 .. 3; the maximum arrives in q.best.host after a stream synchronise).  For
+// the store the host has written the lookup of store_raycast.hip for `n_chunks` listed chunks into q.table_host
+struct GainCall
+{
+  size_t m, n;          // views (1 .. 65535), rays of the fan (1 .. 2^19)
+  int32_t lo[3], hi[3]; // the box, inclusive world voxels (lo > hi: empty)
+  int32_t res, max_range, min_value;
+  uint32_t flags;
+};
+int launch_map_gain(ws_map *m, GainResult &q, int which, const GainCall &c);
+int launch_store_gain(ws_store *st, ws_store::Gain &q, const GainCall &c, uint32_t n_chunks);
 
 // store_distance.hip: pass 0 of the distance field over the chunks the call lists (it clears q.sites.dev and marks events 0, 1).  The
 // host has written the lookup of store_raycast.hip (store_ray_table_fill) for `n_chunks` listed chunks into q.table_host

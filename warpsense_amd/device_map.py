@@ -11,7 +11,7 @@ from ._abi import _i3, _i3c, _is_device, _ptr, pack_entry, unpack_entry
 from ._lib import WS_MAP_AVG, WS_MAP_NEW, check
 from .context import Context
 from .global_map import GlobalMap
-from .queries import _distance_call, _frontier_call, _reach_call, _reach_lookup_call, _reach_paths_call, _mesh_call, _raycast_call, _sample_call, _surface_call, _timing
+from .queries import _distance_call, _frontier_call, _reach_call, _reach_lookup_call, _reach_paths_call, _mesh_call, _raycast_call, _sample_call, _surface_call, _timing, _view_gain_call
 
 
 class DeviceMap:
@@ -292,6 +292,27 @@ class DeviceMapMemWrapper:
     def reach_timing(self, enable: int = -1):
         """device milliseconds of the seeding, of all rounds as one span and of the count pass of the last reach() (ws_debug_reach_timing)"""
         return _timing(self._t._L, "ws_debug_reach_timing", self._t.handle, 3, enable)
+
+    def view_gain(self, origins_mm, dirs, max_range_mm, lo=None, hi=None, min_value=0, any_weight=False, rays=False, device=False):
+        """What the sensor would see from candidate poses (ws_map_view_gain; the rules are stated in include/warpsense_hip.h): for each
+        of the (m, 3) int32 map-frame origins in millimetres and the one fan of (n, 3) int32 directions (view_fan makes one) the
+        UNKNOWN and FREE samples its rays meet inside the inclusive world-voxel box [lo, hi] (both None: the whole window) before an
+        occupied voxel (valid, value < min_value) blocks them, as counts and weighted by k^2.  any_weight: voxels with a negative
+        weight count as observed too.
+
+        Returns the records as a numpy array of dtype VIEW_GAIN_RECORD, one per origin; with `rays` a pair (records, (m, n) array of
+        VIEW_GAIN_RAY).  `last_view_gain` keeps dict(best_unknown_k2, views, rays).  gain_volume_m3 and rank_views read the records.
+        device=True: torch int32 tensors on the GPU instead -- (m, 8) and (m, n, 2) -- that ALIAS the library's buffers: valid until
+        the next view_gain() on this TSDFCuda, copy them (.clone()) to keep them."""
+        rec, ray, best = _view_gain_call(self._t._L, "ws_map_view_gain", self._t, (self._which,), lo, hi, origins_mm, dirs, max_range_mm, (), min_value,
+                                         any_weight, rays, device)
+        self.last_view_gain = dict(best_unknown_k2=best, views=int(rec.shape[0]), rays=int(np.asarray(dirs).reshape(-1, 3).shape[0]))
+        return (rec, ray) if rays else rec
+
+    def view_gain_timing(self, enable: int = -1):
+        """device milliseconds of the upload, of the fan preparation with the march, and of the maximum pass of the last view_gain()
+        (ws_debug_view_gain_timing)"""
+        return _timing(self._t._L, "ws_debug_view_gain_timing", self._t.handle, 3, enable)
 
     def dev(self):
         return self._t.handle

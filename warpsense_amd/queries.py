@@ -1,5 +1,6 @@
 """What the window map (ws_map_*) and the chunk store (ws_store_*) share on the host side of their queries: the box, the call,
-the download or the device tensors of surface, mesh, ray cast, point sample, distance field, frontier and reach, and the timing read-out."""
+the download or the device tensors of surface, mesh, ray cast, point sample, distance field, frontier, reach and view gain, and the
+timing read-out."""
 from __future__ import annotations
 
 import ctypes as C
@@ -9,7 +10,7 @@ import numpy as np
 from . import _lib
 from ._abi import _device_tensor, _i3, _is_device, _ptr
 from ._lib import WsError, check
-from .records import FRONTIER_CLUSTER, FRONTIER_RECORD, REACH_PATH_HEADER, REACH_PATH_RECORD, RAY, SAMPLE, SAMPLE_CLASSES, SURFACE_RECORD, VERT
+from .records import VIEW_GAIN_RAY, VIEW_GAIN_RECORD, FRONTIER_CLUSTER, FRONTIER_RECORD, REACH_PATH_HEADER, REACH_PATH_RECORD, RAY, SAMPLE, SAMPLE_CLASSES, SURFACE_RECORD, VERT
 from .scan import DevicePoints
 
 
@@ -258,3 +259,34 @@ def _reach_paths_call(L, name, owner, goals, cap_steps):
     if len(goals):
         check(getattr(L, name)(owner.handle, _ptr(goals), len(goals), int(cap_steps), _ptr(hdr), _ptr(rec) if cap_steps else None), name)
     return hdr, rec
+
+
+def _view_gain_call(L, name, owner, lead, lo, hi, origins_mm, dirs, max_range_mm, tail, min_value, any_weight, rays, device):
+    """The view-gain call `name` (ws_map_view_gain, ws_store_view_gain) on owner.handle and its result: `lead` are the arguments of the
+    entry point before the box, `tail` those between the range and min_value.  Returns (records, rays | None, best): one
+    VIEW_GAIN_RECORD per origin, with `rays` a (views, rays) array of VIEW_GAIN_RAY, and the largest unknown_k2; device=True: torch
+    int32 tensors on the GPU instead -- (views, 8) and (views, rays, 2) -- that alias the library's buffers.  No origin or no
+    direction: empty arrays, nothing is called."""
+    box = _box_ptrs("view_gain", lo, hi)
+    org = np.ascontiguousarray(origins_mm, dtype=np.int32).reshape(-1, 3)
+    d = np.ascontiguousarray(dirs, dtype=np.int32).reshape(-1, 3)
+    m, n = len(org), len(d)
+    if m == 0 or n == 0:
+        return np.zeros(m if n else 0, dtype=VIEW_GAIN_RECORD), (np.zeros((m, n), dtype=VIEW_GAIN_RAY) if rays else None), 0
+    flags = (_lib.WS_GAIN_ANY_WEIGHT if any_weight else 0) | (_lib.WS_GAIN_RAYS if rays else 0)
+    best = C.c_uint64(0)
+    check(getattr(L, name)(owner.handle, *lead, *box, _ptr(org), m, _ptr(d), n, int(max_range_mm), *tail, int(min_value), flags, C.byref(best)), name)
+    cnt = C.c_size_t(0)
+    if device:
+        rec = _device_tensor(getattr(L, name + "_records_dev")(owner.handle, C.byref(cnt)), (m, 8), "<i4", owner)
+        if int(cnt.value) != m:
+            raise WsError("view_gain: another call replaced the result")
+        ray = _device_tensor(getattr(L, name + "_rays_dev")(owner.handle, C.byref(cnt)), (m, n, 2), "<i4", owner) if rays else None
+        return rec, ray, int(best.value)
+    rec = np.empty(m, dtype=VIEW_GAIN_RECORD)
+    ray = np.empty((m, n), dtype=VIEW_GAIN_RAY) if rays else None
+    got, got_r = C.c_size_t(0), C.c_size_t(0)
+    check(getattr(L, name + "_download")(owner.handle, _ptr(rec), _ptr(ray), m, m * n if rays else 0, C.byref(got), C.byref(got_r)), name + "_download")
+    if int(got.value) != m or (rays and int(got_r.value) != m * n):
+        raise WsError("view_gain: another call replaced the result before it was downloaded")
+    return rec, ray, int(best.value)

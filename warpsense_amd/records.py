@@ -4,6 +4,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib
+from ._lib import WsError
 
 # one record of ws_map_surface: world voxel coordinates and the packed entry (16 bytes)
 SURFACE_RECORD = np.dtype([("x", "<i4"), ("y", "<i4"), ("z", "<i4"), ("raw", "<u4")])
@@ -178,3 +179,45 @@ def write_path_ply(path, headers, records, resolution):
         out.write(v.tobytes())
         out.write(e.tobytes())
     return len(v), len(e)
+
+
+# one record of ws_map_view_gain per view (32 bytes), and with WS_GAIN_RAYS one per (view, ray), view-major (8 bytes): stop is the k of
+# the blocking sample, -1 for none, -2 for a dead ray
+VIEW_GAIN_RECORD = np.dtype([("unknown_k2", "<u8"), ("free_k2", "<u8"), ("unknown", "<u4"), ("free", "<u4"), ("blocked", "<u4"), ("live", "<u4")])
+VIEW_GAIN_RAY = np.dtype([("unknown", "<u4"), ("stop", "<i4")])
+
+
+def view_fan(rings, azimuths, v_fov_deg):
+    """The fan of a view-gain call: rings x azimuths directions, elevations spread evenly over v_fov_deg around the horizon (one ring:
+    the horizon), azimuths evenly around the circle, ring-major.  Integers by the scaling of TSDFMapping.raycast_rays: the largest
+    component is 2^20 in magnitude, rounded to nearest, so no direction is zero.  Returns (rings * azimuths, 3) int32."""
+    rings, azimuths = int(rings), int(azimuths)
+    if rings < 1 or azimuths < 1:
+        raise WsError("view_fan: rings and azimuths must be at least 1")
+    el = np.deg2rad(np.linspace(-0.5, 0.5, rings) * float(v_fov_deg)) if rings > 1 else np.zeros(1)
+    az = 2.0 * np.pi * np.arange(azimuths, dtype=np.float64) / azimuths
+    d = np.stack([np.cos(el)[:, None] * np.cos(az)[None, :], np.cos(el)[:, None] * np.sin(az)[None, :],
+                  np.sin(el)[:, None] * np.ones(azimuths)[None, :]], axis=-1).reshape(-1, 3)
+    d = d * (float(1 << 20) / np.max(np.abs(d), axis=1))[:, None]
+    return np.rint(d).astype(np.int32)
+
+
+def gain_volume_m3(records, resolution, solid_angle_per_ray):
+    """The unknown volume in cubic metres that the views of a view-gain call would see: unknown_k2 * step^3 * solid_angle_per_ray with
+    step = max(resolution / 2, 1) mm (a sample at range k step stands for (k step)^2 step of volume per steradian), as float64."""
+    records = np.asarray(records, dtype=VIEW_GAIN_RECORD).reshape(-1)
+    step_m = max(int(resolution) // 2, 1) / 1000.0
+    return records["unknown_k2"].astype(np.float64) * step_m ** 3 * float(solid_angle_per_ray)
+
+
+def rank_views(records, cost, resolution, lam_per_m):
+    """Rank the views of a view-gain call by what they show against what the way there costs: score = unknown_k2 * exp(-lam_per_m *
+    reach_mm(cost) / 1000) in float64 on the host; an unreachable view (cost 0xFFFFFFFF) scores -inf.  Returns (order, score): the view
+    indices by descending score, ties to the lower index."""
+    records = np.asarray(records, dtype=VIEW_GAIN_RECORD).reshape(-1)
+    mm = reach_mm(np.asarray(cost, dtype=np.uint32).reshape(-1), resolution)
+    if len(mm) != len(records):
+        raise WsError("rank_views: one cost per view")
+    with np.errstate(invalid="ignore"):
+        score = np.where(np.isinf(mm), -np.inf, records["unknown_k2"].astype(np.float64) * np.exp(-float(lam_per_m) * np.where(np.isinf(mm), 0.0, mm) / 1000.0))
+    return np.argsort(-score, kind="stable"), score

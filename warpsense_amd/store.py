@@ -10,7 +10,7 @@ from ._abi import _i3, _i3c, _ptr, pack_entry
 from ._lib import WS_MAP_AVG, check
 from .context import Context
 from .global_map import GlobalMap
-from .queries import _box_ptrs, _distance_call, _frontier_call, _reach_call, _reach_lookup_call, _reach_paths_call, _mesh_call, _raycast_call, _sample_call, _surface_call, _timing
+from .queries import _box_ptrs, _distance_call, _frontier_call, _reach_call, _reach_lookup_call, _reach_paths_call, _mesh_call, _raycast_call, _sample_call, _surface_call, _timing, _view_gain_call
 
 
 class DeviceGlobalMap:
@@ -170,6 +170,23 @@ class DeviceGlobalMap:
     def frontier_timing(self, enable: int = -1):
         """device milliseconds of the count passes, the scan, the emit pass and the clustering of the last frontier() (ws_debug_store_frontier_timing)"""
         return _timing(self._L, "ws_debug_store_frontier_timing", self.handle, 4, enable)
+
+    def view_gain(self, resolution, origins_mm, dirs, max_range_mm, lo=None, hi=None, min_value=0, any_weight=False, rays=False, device=False):
+        """What the sensor would see from candidate poses, through the chunks on the device (ws_store_view_gain; the rules are those of
+        ws_map_view_gain, stated in include/warpsense_hip.h) inside the inclusive world-voxel box [lo, hi] (both None: the bounding box
+        of the present chunks).  Voxels of absent chunks are unknown: they count, and block nothing.  resolution: the map's, in mm
+        per voxel.  The other arguments, the returned records or (records, rays) and `last_view_gain` are those of
+        DeviceMapMemWrapper.view_gain; device=True: torch tensors that ALIAS the store's buffers, valid until the next view_gain() on
+        this store."""
+        rec, ray, best = _view_gain_call(self._L, "ws_store_view_gain", self, (), lo, hi, origins_mm, dirs, max_range_mm, (int(resolution),), min_value,
+                                         any_weight, rays, device)
+        self.last_view_gain = dict(best_unknown_k2=best, views=int(rec.shape[0]), rays=int(np.asarray(dirs).reshape(-1, 3).shape[0]))
+        return (rec, ray) if rays else rec
+
+    def view_gain_timing(self, enable: int = -1):
+        """device milliseconds of the upload, of the fan preparation with the march, and of the maximum pass of the last view_gain()
+        (ws_debug_store_view_gain_timing)"""
+        return _timing(self._L, "ws_debug_store_view_gain_timing", self.handle, 3, enable)
 
     def reach(self, seeds, clear_d2=0, unknown_free=False, max_rounds=0, device=False):
         """The geodesic field over the LAST distance() result of this store (ws_store_reach; the rules are stated in
