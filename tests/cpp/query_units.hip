@@ -613,23 +613,6 @@ __global__ void k_block_scan(uint32_t *in, uint32_t *out)
 // ---- scan_block_totals (ws_device.h): one workgroup of 1024 threads, as the five kernels that share it launch it
 __global__ void k_scan_totals(const uint32_t *tot, unsigned long long *off, uint32_t n, unsigned long long *total) { scan_block_totals(tot, off, n, total); }
 
-// a line whose comparison ran on the host: the report goes through the same finish()
-static void finish_host(const char *name, const Report &r, unsigned long long expect)
-{
-  CHECK_HIP(hipMemcpy(g_rep, &r, sizeof r, hipMemcpyHostToDevice));
-  finish(name, expect);
-}
-static void host_fail(Report &r, long long a, long long b, long long c, long long d, long long got, long long want)
-{
-  ++r.mismatches;
-  if (r.n_rec < (uint32_t)MAX_REC)
-  {
-    const long long v[6] = {a, b, c, d, got, want};
-    for (int k = 0; k < 6; ++k) r.rec[r.n_rec][k] = v[k];
-  }
-  ++r.n_rec;
-}
-
 int main()
 {
   CHECK_HIP(hipMalloc((void **)&g_rep, sizeof(Report)));

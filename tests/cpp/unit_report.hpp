@@ -1,4 +1,4 @@
-// unit_report.hpp — the scaffolding of the device unit programs (device_units.hip, query_units.hip): a report in device memory that
+// unit_report.hpp — the scaffolding of the device unit programs (device_units.hip, query_units.hip, gn_units.hip): a report in device memory that
 // counts cases and mismatches and keeps the inputs of the first few, the index loop of the check kernels, and the line printed per
 // helper.  Included once per program, after the library's headers.
 #pragma once
@@ -85,4 +85,21 @@ static void chunked(uint64_t n, F &&launch)
 {
   const uint64_t STEP = 1ull << 34;
   for (uint64_t b = 0; b < n; b += STEP) launch(b, n - b < STEP ? n - b : STEP);
+}
+
+// a line whose comparison ran on the host: the report goes through the same finish()
+static void finish_host(const char *name, const Report &r, unsigned long long expect)
+{
+  CHECK_HIP(hipMemcpy(g_rep, &r, sizeof r, hipMemcpyHostToDevice));
+  finish(name, expect);
+}
+static void host_fail(Report &r, long long a, long long b, long long c, long long d, long long got, long long want)
+{
+  ++r.mismatches;
+  if (r.n_rec < (uint32_t)MAX_REC)
+  {
+    const long long v[6] = {a, b, c, d, got, want};
+    for (int k = 0; k < 6; ++k) r.rec[r.n_rec][k] = v[k];
+  }
+  ++r.n_rec;
 }
