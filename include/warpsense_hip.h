@@ -871,6 +871,59 @@ const void *ws_store_view_gain_rays_dev(const ws_store *st, size_t *n);    /* n 
 int ws_store_view_gain_download(ws_store *st, void *records_host, void *rays_host, size_t cap_views, size_t cap_rays, size_t *n_views, size_t *n_rays);
 int ws_debug_store_view_gain_timing(ws_store *st, int32_t enable, float ms_out[3]);
 
+/* One store fused into another under a rigid pose: SRC is resampled on the voxel lattice of DST and integrated into it with the
+ * weighted average of the TSDF update, on the device, without a chunk leaving HBM.  Two runs of one site, a map loaded from a file
+ * and the map of the current run, or a submap that a registration has moved, become one map that keeps its TSDF.  The rule uses
+ * integers only: products and sums are int64, "floor" is floor division, and the result is the same bytes on every run.
+ *   pull transform: the map from the frame of DST to the frame of SRC, 15 int32: rot_q30[9] row-major, every entry in
+ *     [-2^30, 2^30] (else WS_ERR_INVALID); pivot_dst_mm[3]; pivot_src_mm[3].
+ *   voxel mapping: for the centre p = v res + h (h = res / 2 truncated) of the world voxel v of DST, axis k gets
+ *     q_k = floor((sum_j rot[k][j] (p_j - pivot_dst_j) + 2^29) / 2^30) + pivot_src_k.  Orthonormality is not required of rot: the
+ *     bytes follow from the matrix as given.  Every voxel with a component of |p - pivot_dst| >= 2^24 mm is outside the call and is
+ *     never touched; with that limit no sum exceeds 2^56.  The voxels the call looks at are those of the candidate chunks of its plan
+ *     (below), which for a rotation are all that can receive anything.
+ *   sample: the cell of ws_store_sample at q in the field of SRC (base voxel floor((q - h) / res), fractions f, T): a voxel of an
+ *     absent chunk is not valid, and a voxel is valid iff weight > 0 (there is no ANY_WEIGHT variant).  One change makes
+ *     lattice-aligned poses exact: a corner whose trilinear coefficient is zero takes part neither in validity nor in the weight
+ *     (with f_k = 0 on an axis only the low plane of that axis counts).  nv = floor(T / res^3); nw = the smallest weight among the
+ *     corners that take part.  A point the sample calls dead (a component of q of magnitude >= 2^30) is not valid.
+ *   integrate: wso_update_avg's rule (cu_avg_tsdf_krnl of the reference) on the entry (ev, ew) of DST; a voxel of an absent chunk of
+ *     DST holds fill_entry.  Sample not valid: the voxel is untouched.  ew > 0: value (ev ew + nv nw) / (ew + nw) with C's truncating
+ *     division, weight min(max_weight, ew + nw), both cast to int16.  Otherwise the entry becomes (nv, nw).
+ *   chunks: a chunk of DST exists after the call iff it existed before or at least one of its voxels received a valid sample.  A
+ *     chunk the call creates holds fill_entry wherever nothing was fused.
+ *   stats[6]: candidate chunks of DST examined; chunks created; voxels averaged (ew > 0); voxels set (ew <= 0); over the averaged
+ *     voxels the sum of |nv - ev|; over the averaged voxels the sum of min(nw, ew).  Integer adds, exact whatever the order.  The
+ *     fifth divided by the third is the disagreement of the two maps under this pose, in mm.
+ *   flags: WS_FUSE_DEFAULT; WS_FUSE_COUNT_ONLY: every statistic as the real call would report it, "chunks created" included, and no
+ *     byte of DST and no entry of its directory changes (the chunk limit of DST is not looked at).  Unknown bits: WS_ERR_INVALID.
+ *   refusals, nothing changed and nothing launched: WS_ERR_INVALID: a NULL argument, dst == src, stores of different contexts,
+ *     max_weight outside 1 .. 32767, a fill_entry of DST with weight > 0, a rot_q30 entry out of range.  WS_ERR_RANGE: map_resolution
+ *     < 1 or > 1024; 2^23 candidate chunks or more, or 2^19 chunks of SRC or more.  WS_ERR_CAPACITY: the chunks to create do not fit
+ *     under max_chunks of DST; this is decided after the count pass and before any write.  WS_ERR_HIP: a segment cannot be allocated.
+ *     An empty SRC is WS_OK with zero statistics.
+ *   plan: the host maps the eight corners of every chunk of SRC, grown by two voxels, forward with the transpose of rot in double
+ *     precision; the candidates are the chunks of DST those boxes (2 mm more per side) overlap, clipped to the 2^24 mm limit,
+ *     ascending.  The rounding of q is below 1 mm, so for a rotation this is a superset of what can receive anything, and the result
+ *     does not depend on how generous it is.  A count pass over the candidates leaves the per-chunk counts and the statistics; the
+ *     host reads them (the one synchronisation besides the end of the call), gives the absent candidates with a non-zero count their
+ *     slots, which are filled with fill_entry on the device, and a write pass over the candidates with a non-zero count samples again
+ *     and integrates in place.
+ *   ordering: both stores' locks are taken in address order; the work is stream-ordered behind everything enqueued on either store;
+ *     the call synchronises before it returns.  SRC is only read.  The result buffers of DST's queries stay untouched. */
+typedef struct ws_fuse_pose
+{
+  int32_t rot_q30[9];
+  int32_t pivot_dst_mm[3];
+  int32_t pivot_src_mm[3];
+} ws_fuse_pose;
+#define WS_FUSE_DEFAULT 0u
+#define WS_FUSE_COUNT_ONLY 1u
+int ws_store_fuse(ws_store *dst, ws_store *src, const ws_fuse_pose *pull, int32_t map_resolution, int32_t max_weight, uint32_t flags, uint64_t stats[6]);
+/* Measurement entry, as ws_debug_store_view_gain_timing: ms_out receives the device time of the plan's upload, of the count pass and of
+ * the write pass (with the fill of the created chunks) of the last call with this store as DST */
+int ws_debug_store_fuse_timing(ws_store *dst, int32_t enable, float ms_out[3]);
+
 /* ------------------------------------------------------------------ TSDF update ---- */
 /* TSDFCuda::update_tsdf(scan_points, scanner_pos, up) — update_tsdf.cu:143-166.
  * xyz_host: n x 3 int32 (rmagine::Pointi AoS); scanner_pos in voxel units, up scaled by 32768.

@@ -346,6 +346,16 @@ public:
   {
     return global_map_sample(store_, resolution, points, band_mm, any_weight, with_gradient, select, lo, hi);
   }
+  // `other` resampled on this map's lattice under the pull transform and integrated into it (ws_store_fuse); resolution: the
+  // maps', in mm per voxel, which a store does not know -- the contract of the Python DeviceGlobalMap.fuse
+  FuseStats fuse(DeviceGlobalMap &other, const FusePose &pose, int max_weight, bool count_only, int resolution)
+  {
+    uint64_t s[6] = {0, 0, 0, 0, 0, 0};
+    WS_CHECK(ws_store_fuse(store_, other.store_, &pose, resolution, max_weight, count_only ? WS_FUSE_COUNT_ONLY : WS_FUSE_DEFAULT, s));
+    FuseStats out;
+    out.candidates = s[0], out.created = s[1], out.averaged = s[2], out.set = s[3], out.sum_abs_diff = s[4], out.sum_min_weight = s[5];
+    return out;
+  }
   // every chunk merged into the host global map (and through it into its file)
   void flush_to(GlobalMap &g)
   {
@@ -775,6 +785,20 @@ public:
                      bool with_rays = false, const rm::Pointi *lo = nullptr, const rm::Pointi *hi = nullptr)
   {
     return local_map_view_gain(gpu_.tsdf(), origins, dirs, max_range_mm, WS_MAP_AVG, min_value, any_weight, with_rays, lo, hi);
+  }
+  // Another map fused into everything the run has seen: the window into the device chunks, as global_mesh does, the fuse of the
+  // store at the map's resolution (max_weight < 0: the map's), and, unless count_only, the window loaded back from the chunks, so
+  // that it holds the merged voxels and a later save does not undo the merge
+  FuseStats merge_map(DeviceGlobalMap &other, const FusePose &pose, int max_weight = -1, bool count_only = false)
+  {
+    if (!device_global_map_) throw std::logic_error("merge_map: no DeviceGlobalMap attached");
+    wait_shift();
+    rm::Pointi wlo, whi;
+    local_map_.window(wlo, whi);
+    WS_CHECK(ws_store_save_box(device_global_map_->handle(), gpu_.tsdf().handle(), WS_MAP_AVG, &wlo.x, &whi.x));
+    const FuseStats st = device_global_map_->fuse(other, pose, max_weight < 0 ? params_.max_weight : max_weight, count_only, params_.map_resolution);
+    if (!count_only) WS_CHECK(ws_store_load_box(device_global_map_->handle(), gpu_.tsdf().handle(), WS_MAP_AVG, &wlo.x, &whi.x));
+    return st;
   }
   // The same through everything the run has seen: the window into the device chunks, as global_mesh does, then the view gain of the
   // store (without a box: the bounding box of the chunks)

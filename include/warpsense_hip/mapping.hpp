@@ -10,6 +10,7 @@
 #pragma once
 
 #include <cmath>
+#include <stdexcept>
 #include <memory>
 #include <mutex>
 #include <shared_mutex>
@@ -259,5 +260,39 @@ inline std::vector<rmagine::Matrix4x4f> sweep_poses(const rmagine::Matrix4x4f &p
   WS_CHECK(ws_sweep_poses(&pose_end.data[0][0], &motion.data[0][0], k, &out[0].data[0][0]));
   out.resize(k);
   return out;
+}
+
+// ---- one device global map fused into another (ws_store_fuse, warpsense_hip.h)
+using FusePose = ws_fuse_pose;
+// stats[6] of ws_store_fuse
+struct FuseStats
+{
+  uint64_t candidates = 0, created = 0, averaged = 0, set = 0, sum_abs_diff = 0, sum_min_weight = 0;
+  // the mean |nv - ev| over the averaged voxels: how far the two maps are apart under the pose; nan without any
+  double disagreement_mm() const { return averaged ? (double)sum_abs_diff / (double)averaged : std::nan(""); }
+};
+// The pull transform of a rigid transform T (row-major 4 x 4 double, mm) that takes points of SRC into the frame of DST, as the
+// Python fuse_pose makes it: rot_q30 = rint(R^T 2^30) clipped, pivot_src the given point (rounded) or zeros, pivot_dst =
+// rint(R pivot_src + t).  The sub-millimetre remainder of the translation is dropped.
+inline FusePose fuse_pose(const double T[16], const double *pivot_src_mm = nullptr)
+{
+  for (int i = 0; i < 16; ++i)
+    if (!std::isfinite(T[i])) throw std::invalid_argument("fuse_pose: a finite 4 x 4 matrix is expected");
+  FusePose p;
+  double ps[3];
+  for (int k = 0; k < 3; ++k) ps[k] = pivot_src_mm ? std::nearbyint(pivot_src_mm[k]) : 0.0;
+  for (int i = 0; i < 3; ++i)
+  {
+    for (int j = 0; j < 3; ++j)
+    {
+      const double q = std::nearbyint(T[4 * j + i] * 1073741824.0); // R^T
+      p.rot_q30[3 * i + j] = (int32_t)(q < -1073741824.0 ? -1073741824.0 : (q > 1073741824.0 ? 1073741824.0 : q));
+    }
+    const double pd = std::nearbyint(T[4 * i] * ps[0] + T[4 * i + 1] * ps[1] + T[4 * i + 2] * ps[2] + T[4 * i + 3]);
+    if (!(std::fabs(pd) < 2147483648.0) || !(std::fabs(ps[i]) < 2147483648.0)) throw std::invalid_argument("fuse_pose: a pivot outside int32");
+    p.pivot_dst_mm[i] = (int32_t)pd;
+    p.pivot_src_mm[i] = (int32_t)ps[i];
+  }
+  return p;
 }
 } // namespace warpsense

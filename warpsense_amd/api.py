@@ -24,6 +24,8 @@ This module only gathers the names; the code lives in one module per subsystem, 
     queries.py       what window and store queries share: box, call, result, timing (api_query)
     global_map.py    GlobalMap on the host and its .h5 file, pose_to_values
     store.py         DeviceGlobalMap, chunks_of_box                                 (api_store)
+    fuse.py          fuse_pose, FuseStats: one global map fused into another        (api_store)
+    merge.py         merge_map and align_map of TSDFMapping
     device_map.py    DeviceMap, LocalMap, DeviceMapMemWrapper, TSDFCuda             (api_map, api_tsdf)
     registration.py  RegistrationCuda, batch_best, candidate_poses                  (api_reg)
     mapping.py       the parameters, TSDFMapping, TSDFRegistration
@@ -43,3 +45,4 @@ from .records import VIEW_GAIN_RAY, VIEW_GAIN_RECORD, gain_volume_m3, rank_views
 from .registration import RegistrationCuda, batch_best, candidate_poses  # noqa: F401
 from .scan import DevicePoints, ScanPreprocessor, preprocess_sweep_host, sweep_bins, sweep_poses, to_int_mat, to_map  # noqa: F401
 from .store import DeviceGlobalMap, chunks_of_box  # noqa: F401
+from .fuse import FuseStats, fuse_pose, pose_transform  # noqa: F401

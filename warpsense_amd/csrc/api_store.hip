@@ -4,11 +4,14 @@
 // store_raycast.hip, store_distance.hip).
 #include <algorithm>
 #include <array>
+#include <cmath>
 #include <cstring>
+#include <functional>
 #include <new>
 #include <set>
 
 #include "ws_api.h"
+#include "ws_fuse.h"
 
 using namespace ws;
 
@@ -1018,4 +1021,223 @@ int ws_debug_store_view_gain_timing(ws_store *st, int32_t enable, float ms_out[3
   if (!st) return invalid("ws_debug_store_view_gain_timing: store is NULL");
   std::lock_guard<std::mutex> lock(st->mu);
   return query_timing(st->ctx->stream, st->gain.timer, enable, ms_out, GAIN_PAIRS, 3);
+}
+
+// ---- one store fused into another under a rigid pose: the plan, the count pass, the host step and the write pass of ws_store_fuse
+// (the rules are stated in warpsense_hip.h and live in ws_fuse.h; the kernels in store_fuse.hip)
+namespace
+{
+constexpr int FUSE_PAIRS[3][2] = {{0, 1}, {1, 2}, {2, 3}};
+
+inline int64_t floor_div64(int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); } // b > 0
+
+// The candidate chunks of DST: every src chunk, grown by two voxels, mapped forward with the transpose of rot in double precision;
+// the chunks its bounding box (2 mm more per side) overlaps, clipped to the reach around pivot_dst and to int32 voxels.  A superset of
+// what can receive anything: the rounding of q is below 1 mm.
+void fuse_candidates(const ws_store *src, const ws_fuse_pose &pull, int32_t res, std::set<StoreKey> &cand)
+{
+  const int64_t h = res / 2;
+  int64_t vlo[3], vhi[3]; // the dst voxels inside the reach and inside int32
+  for (int k = 0; k < 3; ++k)
+  {
+    vlo[k] = std::max<int64_t>(-floor_div64(-((int64_t)pull.pivot_dst_mm[k] - (FUSE_REACH - 1) - h), res), INT32_MIN); // ceil
+    vhi[k] = std::min<int64_t>(floor_div64((int64_t)pull.pivot_dst_mm[k] + (FUSE_REACH - 1) - h, res), INT32_MAX);
+  }
+  double R[9];
+  for (int i = 0; i < 9; ++i) R[i] = (double)pull.rot_q30[i] / 1073741824.0;
+  for (const auto &kv : src->dir)
+  {
+    if (!kv.second.written) continue;
+    double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
+    for (int c = 0; c < 8; ++c)
+    {
+      double q[3];
+      for (int k = 0; k < 3; ++k)
+        q[k] = ((double)kv.first[k] * STORE_CS + (((c >> k) & 1) ? STORE_CS + 2 : -2)) * (double)res - (double)pull.pivot_src_mm[k];
+      for (int k = 0; k < 3; ++k) // p = rot^T q + pivot_dst
+      {
+        const double p = R[k] * q[0] + R[3 + k] * q[1] + R[6 + k] * q[2] + (double)pull.pivot_dst_mm[k];
+        lo[k] = std::min(lo[k], p), hi[k] = std::max(hi[k], p);
+      }
+    }
+    int64_t c0[3], c1[3];
+    bool any = true;
+    for (int k = 0; k < 3; ++k)
+    {
+      // the voxels whose centre v res + h lies in [lo - 2, hi + 2]; far outside the reach the doubles are cut before the conversion
+      const double a = std::max(lo[k] - 2.0, -4e12), b = std::min(hi[k] + 2.0, 4e12);
+      const int64_t v0 = std::max(floor_div64((int64_t)std::floor(a) - h, res), vlo[k]), v1 = std::min(floor_div64((int64_t)std::ceil(b) - h, res) + 1, vhi[k]);
+      any = any && v0 <= v1;
+      c0[k] = floor_div64(v0, STORE_CS), c1[k] = floor_div64(v1, STORE_CS);
+    }
+    if (!any) continue;
+    for (int64_t x = c0[0]; x <= c1[0]; ++x)
+      for (int64_t y = c0[1]; y <= c1[1]; ++y)
+        for (int64_t z = c0[2]; z <= c1[2]; ++z) cand.insert(StoreKey{(int32_t)x, (int32_t)y, (int32_t)z});
+  }
+}
+
+// the words of the count pass: room for n candidates, cleared in stream order
+int fuse_words(ws_store *dst, size_t n)
+{
+  ws_store::Fuse &q = dst->fuse;
+  const size_t words = 2 * FUSE_STATS_DEV + n;
+  if (words > q.words.cap || words > q.words_host.cap)
+  {
+    WS_HIP(hipStreamSynchronize(dst->ctx->stream));
+    WS_TRY(q.words.alloc(words + words / 8, sizeof(uint32_t)));
+    WS_TRY(q.words_host.alloc(words + words / 8, sizeof(uint32_t), HostBlock::PINNED));
+  }
+  WS_HIP(hipMemsetAsync(q.words.p, 0, words * sizeof(uint32_t), dst->ctx->stream));
+  return WS_OK;
+}
+
+// everything of the call that enqueues; the caller synchronises after a failure
+int fuse_run(ws_store *dst, ws_store *src, const ws_fuse_pose &pull, int32_t res, int32_t max_weight, bool count_only, uint64_t stats[6])
+{
+  hipStream_t s = dst->ctx->stream;
+  ws_store::Fuse &q = dst->fuse;
+  std::set<StoreKey> cand;
+  fuse_candidates(src, pull, res, cand);
+  if (cand.size() >= FUSE_MAX_CANDIDATES) return range_error("ws_store_fuse", ": 2^23 candidate chunks of DST or more");
+  stats[0] = cand.size();
+  if (cand.empty()) return WS_OK;
+  std::vector<StoreRaySlot> listed;
+  store_list(src, nullptr, nullptr, listed);
+  if (listed.size() >= (1u << 19)) return range_error("ws_store_fuse", ": SRC holds 2^19 chunks or more");
+
+  // the plan: the lookup of SRC's chunks in a table of SRC's ring, the candidates in one of DST's
+  const size_t places = store_ray_table_slots(listed.size()), n = cand.size();
+  ws_store::Table *ts = nullptr, *td = nullptr;
+  WS_TRY(store_table(src, places * 4, &ts));
+  WS_TRY(store_table(dst, n * 4, &td));
+  store_ray_table_fill(listed.data(), listed.size(), ts->host.as<StoreRaySlot>());
+  FuseCand *ch = td->host.as<FuseCand>();
+  size_t i = 0;
+  for (const StoreKey &k : cand)
+  {
+    const auto it = dst->dir.find(k);
+    ch[i++] = FuseCand{k[0], k[1], k[2], it == dst->dir.end() ? STORE_ABSENT : it->second.slot};
+  }
+  WS_TRY(fuse_words(dst, n));
+  q.timer.mark(0, s);
+  WS_HIP(hipMemcpyAsync(ts->dev.p, ts->host.p, places * sizeof(StoreRaySlot), hipMemcpyHostToDevice, s));
+  WS_HIP(hipMemcpyAsync(td->dev.p, td->host.p, n * sizeof(FuseCand), hipMemcpyHostToDevice, s));
+  q.timer.mark(1, s);
+
+  FuseArgs a;
+  for (int k = 0; k < 9; ++k) a.rot[k] = pull.rot_q30[k];
+  for (int k = 0; k < 3; ++k) a.pd[k] = pull.pivot_dst_mm[k], a.ps[k] = pull.pivot_src_mm[k];
+  a.res = res, a.half = res / 2, a.max_weight = max_weight, a.fill = dst->fill;
+  a.rdiv = make_fastdiv(res);
+  a.res3 = (int64_t)res * res * res;
+  a.tdiv = make_fuse_div(a.res3);
+  a.cand = td->dev.as<FuseCand>();
+  a.src_table = ts->dev.as<StoreRaySlot>();
+  a.src_mask = (uint32_t)places - 1u;
+  a.src_segs = src->seg_tab.as<uint32_t *>(), a.src_shift = src->seg_shift;
+  a.dst_segs = dst->seg_tab.as<uint32_t *>(), a.dst_shift = dst->seg_shift;
+  a.stats = q.words.as<unsigned long long>();
+  a.counts = q.words.as<uint32_t>() + 2 * FUSE_STATS_DEV;
+  WS_TRY(launch_store_fuse(s, a, n, false));
+  q.timer.mark(2, s);
+  WS_HIP(hipEventRecord(td->done, s));
+  td->used = true;
+  WS_HIP(hipMemcpyAsync(q.words_host.p, q.words.p, (2 * FUSE_STATS_DEV + n) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  WS_HIP(hipStreamSynchronize(s)); // the one host read of the call: which chunks receive anything decides what is created
+
+  const unsigned long long *sums = q.words_host.as<unsigned long long>();
+  const uint32_t *counts = q.words_host.as<uint32_t>() + 2 * FUSE_STATS_DEV;
+  for (int k = 0; k < 4; ++k) stats[2 + k] = sums[k];
+  std::vector<FuseCand> work; // the candidates with a non-zero count (ch stays readable: its table is not handed out again before the call ends)
+  std::set<StoreKey> fresh;
+  for (i = 0; i < n; ++i)
+  {
+    if (!counts[i]) continue;
+    work.push_back(ch[i]);
+    if (ch[i].slot == STORE_ABSENT) fresh.insert(StoreKey{ch[i].cx, ch[i].cy, ch[i].cz});
+  }
+  stats[1] = fresh.size();
+  if (count_only || work.empty())
+  {
+    q.timer.mark(3, s);
+    WS_HIP(hipEventRecord(ts->done, s));
+    ts->used = true;
+    return WS_OK;
+  }
+
+  {
+    const int rc_room = store_make_room(dst, fresh.size(), "ws_store_fuse");
+    if (rc_room != WS_OK) // refused before any write; the table of SRC has been read by the count pass
+    {
+      (void)hipEventRecord(ts->done, s);
+      ts->used = true;
+      return rc_room;
+    }
+  }
+  for (const StoreKey &k : fresh) dst->dir[k] = ws_store::Entry{store_take_slot(dst), true};
+  int rc = WS_OK;
+  ws_store::Table *tw = nullptr;
+  for (FuseCand &c : work)
+    if (c.slot == STORE_ABSENT && rc == WS_OK)
+    {
+      c.slot = dst->dir[StoreKey{c.cx, c.cy, c.cz}].slot;
+      rc = fill_u32(dst->ctx, store_slot_ptr(dst, c.slot), dst->fill, STORE_CHUNK_WORDS);
+    }
+  if (rc == WS_OK) rc = store_table(dst, work.size() * 4, &tw);
+  if (rc == WS_OK)
+  {
+    std::memcpy(tw->host.p, work.data(), work.size() * sizeof(FuseCand));
+    const hipError_t e = hipMemcpyAsync(tw->dev.p, tw->host.p, work.size() * sizeof(FuseCand), hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync (write table)", __FILE__, __LINE__);
+  }
+  if (rc == WS_OK)
+  {
+    a.cand = tw->dev.as<FuseCand>();
+    a.dst_segs = dst->seg_tab.as<uint32_t *>(); // (a new segment replaces the table)
+    rc = launch_store_fuse(s, a, work.size(), true);
+  }
+  if (rc != WS_OK) // nothing of DST's existing chunks has been written: the write pass was not enqueued
+  {
+    (void)hipStreamSynchronize(s);
+    store_evict(dst, fresh);
+    return rc;
+  }
+  q.timer.mark(3, s);
+  WS_HIP(hipEventRecord(ts->done, s));
+  WS_HIP(hipEventRecord(tw->done, s));
+  ts->used = tw->used = true;
+  return WS_OK;
+}
+} // namespace
+
+int ws_store_fuse(ws_store *dst, ws_store *src, const ws_fuse_pose *pull, int32_t map_resolution, int32_t max_weight, uint32_t flags, uint64_t stats[6])
+{
+  if (!dst || !src || !pull || !stats) return invalid("ws_store_fuse: NULL argument");
+  if (flags & ~WS_FUSE_COUNT_ONLY) return invalid("ws_store_fuse: unknown flag bits");
+  if (dst == src) return invalid("ws_store_fuse: dst and src are the same store");
+  if (dst->ctx != src->ctx) return invalid("ws_store_fuse: the stores belong to different contexts");
+  if (max_weight < 1 || max_weight > 32767) return invalid("ws_store_fuse: max_weight must be 1 .. 32767");
+  if ((int16_t)(dst->fill >> 16) > 0) return invalid("ws_store_fuse: the fill_entry of dst has a weight > 0");
+  for (int k = 0; k < 9; ++k)
+    if (pull->rot_q30[k] < -(1 << 30) || pull->rot_q30[k] > (1 << 30)) return invalid("ws_store_fuse: a rot_q30 entry beyond +-2^30");
+  if (map_resolution < 1 || map_resolution > 1024) return range_error("ws_store_fuse", ": the resolution must be 1 .. 1024 mm");
+  servers_leave(dst->ctx);
+  // both locks, in address order
+  ws_store *first = std::less<ws_store *>()(dst, src) ? dst : src, *second = first == dst ? src : dst;
+  std::lock_guard<std::mutex> lock_a(first->mu), lock_b(second->mu);
+  WS_TRY(dst->fuse.timer.arm());
+  uint64_t out[6] = {0, 0, 0, 0, 0, 0};
+  const int rc = store_enqueued(dst, fuse_run(dst, src, *pull, map_resolution, max_weight, (flags & WS_FUSE_COUNT_ONLY) != 0, out));
+  if (rc != WS_OK) return rc;
+  WS_HIP(hipStreamSynchronize(dst->ctx->stream));
+  for (int k = 0; k < 6; ++k) stats[k] = out[k];
+  return WS_OK;
+}
+
+int ws_debug_store_fuse_timing(ws_store *dst, int32_t enable, float ms_out[3])
+{
+  if (!dst) return invalid("ws_debug_store_fuse_timing: store is NULL");
+  std::lock_guard<std::mutex> lock(dst->mu);
+  return query_timing(dst->ctx->stream, dst->fuse.timer, enable, ms_out, FUSE_PAIRS, 3);
 }

@@ -775,8 +775,16 @@ struct ws_store
     ws::DevBuf table_dev;                // ... and the copy the kernels read
     void release() { GainResult::release(), table_host.release(), table_dev.release(); }
   } gain;
+  struct Fuse // ws_store_fuse with this store as DST (store_fuse.hip)
+  {
+    ws::DevBuf words;      // uint64 [4] the sums of the count pass, then uint32 [candidates] the per-chunk counts
+    ws::HostBlock words_host; // ... and the pinned block the host reads them from
+    ws::QueryTimer timer;
+    void release() { words.release(), words_host.release(), timer.release(); }
+  } fuse;
   void release()
   {
+    fuse.release();
     gain.release();
     reach.release();
     frontier.release();

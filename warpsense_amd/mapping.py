@@ -13,6 +13,7 @@ from ._lib import WS_REG_ALL_POINTS, WsError, check
 from .context import Context
 from .device_map import DeviceMap, LocalMap, TSDFCuda
 from .global_map import GlobalMap
+from .merge import FuseQueries
 from .gain import GainQueries
 from .reach import ReachQueries
 from .records import SAMPLE_CLASSES
@@ -71,7 +72,7 @@ def _dirs_or_os1(dirs):
     return dirs
 
 
-class TSDFMapping(ReachQueries, GainQueries):
+class TSDFMapping(ReachQueries, GainQueries, FuseQueries):
     """cuda::TSDFMapping without ROS (the protected constructor path, tsdf_mapping.cpp:30-41)."""
 
     def __init__(self, params: Params, local_map: LocalMap, ctx: Context | None = None, device_global_map: "DeviceGlobalMap | None" = None):

@@ -9,6 +9,7 @@ from . import _lib
 from ._abi import _i3, _i3c, _ptr, pack_entry
 from ._lib import WS_MAP_AVG, check
 from .context import Context
+from .fuse import FuseStats, _fuse_call, fuse_pose
 from .global_map import GlobalMap
 from .queries import _box_ptrs, _distance_call, _frontier_call, _reach_call, _reach_lookup_call, _reach_paths_call, _mesh_call, _raycast_call, _sample_call, _surface_call, _timing, _view_gain_call
 
@@ -213,6 +214,27 @@ class DeviceGlobalMap:
     def reach_timing(self, enable: int = -1):
         """device milliseconds of the seeding, of all rounds as one span and of the count pass of the last reach() (ws_debug_store_reach_timing)"""
         return _timing(self._L, "ws_debug_store_reach_timing", self.handle, 3, enable)
+
+    def fuse(self, other: "DeviceGlobalMap", T_src_to_dst, max_weight, count_only=False, pivot_src_mm=None, *, resolution) -> FuseStats:
+        """`other` resampled on this map's voxel lattice under a rigid pose and integrated into it with the weighted average of the
+        TSDF update, on the device (ws_store_fuse; the rules are stated in include/warpsense_hip.h).  T_src_to_dst: the 4 x 4
+        float64 transform in mm from the frame of `other` into this map's (fuse_pose makes the integer pull transform from it,
+        around pivot_src_mm), or the 15 int32 of a ws_fuse_pose as they are.  resolution: the maps', in mm per voxel (a store does
+        not know it); max_weight: 1 .. 32767.  count_only: the statistics of the call without a change to this map --
+        FuseStats.disagreement_mm then says how well the two maps agree under the pose.  `other` is only read."""
+        pose = np.asarray(T_src_to_dst)
+        pose = pose if pose.size == 15 else fuse_pose(pose, pivot_src_mm)
+        return _fuse_call(self._L, self, other, pose, resolution, max_weight, count_only)
+
+    @property
+    def last_fuse_timing(self):
+        """device milliseconds of the plan's upload, the count pass and the write pass of the last fuse() into this map (zeros unless
+        fuse_timing(1) switched the events on before it)"""
+        return self.fuse_timing()
+
+    def fuse_timing(self, enable: int = -1):
+        """ws_debug_store_fuse_timing: read the last call's three spans; enable 1 / 0 switches the events on / off"""
+        return _timing(self._L, "ws_debug_store_fuse_timing", self.handle, 3, enable)
 
     def flush_to(self, global_map: GlobalMap):
         """every chunk merged into a host GlobalMap: into its chunk cache (activate_chunk), or, for a map with a file, straight
