@@ -125,7 +125,8 @@ int ws_map_download(ws_map *map, int which, int32_t size[3], int32_t pos[3], int
  * WS_ERR_INVALID, nothing is moved): no box addresses a ring cell twice.  ws_map_surface, _mesh, _distance use the same rule.
  * Where a window may be: pos - size/2 .. pos - size/2 + size - 1 must lie in int32 on every axis (the last voxel may be INT32_MAX,
  * the first INT32_MIN).  A map whose window does not (ws_map_create, ws_map_set_params and ws_map_upload do not ask) is refused
- * here, by the three queries and by ws_store_save_box / ws_store_load_box with WS_ERR_RANGE before anything is allocated or
+ * here, by the three queries, by ws_map_frontier, ws_map_view_gain and ws_map_sample (which takes no box: its kernel forms the
+ * window's ends in int32) and by ws_store_save_box / ws_store_load_box with WS_ERR_RANGE before anything is allocated or
  * launched; the inside-the-window test itself is made in 64 bits. */
 int ws_map_extract_box(ws_map *map, int which, const int32_t lo[3], const int32_t hi[3], uint32_t *host_out);
 int ws_map_insert_box(ws_map *map, int which, const int32_t lo[3], const int32_t hi[3], const uint32_t *host_in);
@@ -318,7 +319,8 @@ int ws_debug_raycast_timing(ws_map *map, int32_t enable, float ms_out[3]);
  *     whose class is selected, 3 int32 each, in input order.  It is an ordered compaction.  Its length is the sum of the selected
  *     counts.  It is device memory fit to be handed to ws_tsdf_update_dev, ws_reg_prepare_dev or
  *     ws_map_raycast_dev(..., WS_RAYCAST_TARGETS).
- *   errors: WS_ERR_INVALID: unknown flag bits, bad `which`.  WS_ERR_RANGE: res > 1024, n > 2^27.  On a refusal nothing is launched and
+ *   errors: WS_ERR_INVALID: unknown flag bits, bad `which`.  WS_ERR_RANGE: res > 1024, n > 2^27, a window that does not lie in int32
+ *     (the rule stated at ws_map_extract_box).  On a refusal nothing is launched and
  *     the last result stays.  n == 0 is WS_OK, counts zero, nothing written; the result is then that of a call without points (the
  *     earlier one is gone, as after any accepted call).  A call that was accepted and then fails (WS_ERR_HIP: an allocation, a
  *     launch) also leaves no result: the earlier one is dropped before the buffers grow.

@@ -12,6 +12,7 @@ import os
 import numpy as np
 import pytest
 
+from edge_domain_scenes import BOTTOM_KEY, TOP_KEY
 from window_model import I32_MAX, I32_MIN, WALKS
 import window_model as M
 from window_routes import MW, RES, TAU, MappingRoute, RawRoute, _default, _i3, _p, _params, check_device, same_state, state
@@ -20,7 +21,6 @@ from window_routes import CW, StoreRoute, chunk_box, same_store, store_state
 pytestmark = pytest.mark.gpu
 
 WS_ERR_INVALID, WS_ERR_RANGE = -1, -5
-TOP_KEY, BOTTOM_KEY = 2 ** 25 - 1, -2 ** 25
 
 
 def _sync():

@@ -275,7 +275,11 @@ int ws::sample_download(const SampleResult &q, hipStream_t s, const char *name, 
 // ---- point sample: the map's value at given points, map_sample.hip (the rules are stated in warpsense_hip.h)
 static int map_sample(ws_map *m, int which, const int32_t *points, bool points_on_host, size_t n, int32_t band, uint32_t flags, uint64_t counts[4])
 {
-  WS_TRY(sample_check("ws_map_sample", !m || (which != WS_MAP_AVG && which != WS_MAP_NEW), points, n, m ? m->res : 0, flags, [] { return WS_OK; }));
+  // (the kernel forms the window's ends in int32: a window that does not lie in int32 is refused like a box query's, before anything moves)
+  WS_TRY(sample_check("ws_map_sample", !m || (which != WS_MAP_AVG && which != WS_MAP_NEW), points, n, m ? m->res : 0, flags, [&] {
+    int32_t l[3], ext[3];
+    return resolve_box(m, which, nullptr, nullptr, true, "ws_map_sample", l, ext);
+  }));
   WS_SETTLE(m);
   std::lock_guard<std::mutex> lock(m->sample.mu);
   SampleResult &q = m->sample;
