@@ -31,8 +31,9 @@ def identity_pose(pivot=(0, 0, 0)):
     return np.array([Q30, 0, 0, 0, Q30, 0, 0, 0, Q30, *pivot, *pivot], dtype=np.int32)
 
 
-def candidates(src_keys, pose, res):
-    """the candidate chunk keys of DST, ascending: the plan of the library, operation for operation (double precision)"""
+def candidates(src_keys, pose, res, grow=2):
+    """the candidate chunk keys of DST, ascending: the plan of the library, operation for operation (double precision).  grow: the
+    voxels a chunk of SRC is grown by, 2 in the library (test_fuse_domain_host.py looks at plans that are less generous)"""
     pose = np.asarray(pose, dtype=np.int64)
     pd, ps = pose[9:12], pose[12:15]
     h = res // 2
@@ -43,7 +44,7 @@ def candidates(src_keys, pose, res):
     for key in src_keys:
         lo, hi = np.full(3, 1e300), np.full(3, -1e300)
         for c in range(8):
-            q = np.array([(float(key[k]) * CS + ((CS + 2) if (c >> k) & 1 else -2)) * float(res) - float(ps[k]) for k in range(3)])
+            q = np.array([(float(key[k]) * CS + ((CS + grow) if (c >> k) & 1 else -grow)) * float(res) - float(ps[k]) for k in range(3)])
             for k in range(3):
                 p = R[k] * q[0] + R[3 + k] * q[1] + R[6 + k] * q[2] + float(pd[k])
                 lo[k], hi[k] = min(lo[k], p), max(hi[k], p)
@@ -146,9 +147,9 @@ def sample(src, res, q):
     return valid_all, nv_all, nw_all
 
 
-def fuse(dst, src, pose, res, max_weight, fill):
+def fuse(dst, src, pose, res, max_weight, fill, grow=2):
     """(DST's chunks after the call, stats (6,) uint64)"""
-    cand = candidates(sorted(src), pose, res)
+    cand = candidates(sorted(src), pose, res, grow)
     out = {k: np.array(v, dtype=np.uint32).reshape(-1) for k, v in dst.items()}
     stats = [len(cand), 0, 0, 0, 0, 0]
     if not src:
@@ -177,6 +178,83 @@ def fuse(dst, src, pose, res, max_weight, fill):
         stats[4] += int(np.abs(nv - ev)[avg].sum())
         stats[5] += int(np.minimum(nw, ew)[avg].sum())
     return out, np.array(stats, dtype=np.uint64)
+
+
+def receiving(src, pose, res, voxels):
+    """(v, nv, nw): those of the DST world voxels `voxels` (n, 3) that receive a valid sample, ascending, and their samples.  A world
+    voxel is an int32: rows beyond that are no voxels of DST"""
+    v = np.unique(np.asarray(voxels, dtype=np.int64).reshape(-1, 3), axis=0)
+    v = v[np.all((v >= -2 ** 31) & (v < 2 ** 31), axis=1)]
+    if not len(v) or not src:
+        return np.zeros((0, 3), dtype=np.int64), np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
+    q, inside = pull(pose, v * res + res // 2)
+    valid, nv, nw = sample(src, res, q)
+    valid &= inside
+    return v[valid], nv[valid], nw[valid]
+
+
+def fuse_at(dst, src, pose, res, max_weight, fill, voxels):
+    """(DST's chunks after the call, stats[1:6]) from the rule applied to an explicit list of DST world voxels (n, 3): pull, sample and
+    integrate voxel by voxel.  Nothing of the plan takes part: neither candidates() nor may_receive().  It is the call's result iff
+    `voxels` holds every voxel that receives a valid sample (receivers() below)."""
+    v, nv, nw = receiving(src, pose, res, voxels)
+    out = {k: np.array(d, dtype=np.uint32).reshape(-1) for k, d in dst.items()}
+    stats = [0, 0, 0, 0, 0]
+    if len(v):
+        keys, inv = np.unique(v >> 6, axis=0, return_inverse=True)
+        inv = np.asarray(inv).reshape(-1)
+        l = v & 63
+        idx = l[:, 0] * 4096 + l[:, 1] * 64 + l[:, 2]
+        for i, key in enumerate(keys):
+            key = tuple(int(c) for c in key)
+            m = inv == i
+            if key not in out:
+                out[key] = np.full(CW, fill, dtype=np.uint32)
+                stats[0] += 1
+            ev, ew = unpack(out[key][idx[m]])
+            avg = ew > 0
+            v_avg = tdiv(ev * ew + nv[m] * nw[m], np.where(avg, ew + nw[m], 1))
+            out[key][idx[m]] = np.where(avg, pack(v_avg, np.minimum(max_weight, ew + nw[m])), pack(nv[m], nw[m])).astype(np.uint32)
+            stats[1] += int(avg.sum())
+            stats[2] += int((~avg).sum())
+            stats[3] += int(np.abs(nv[m] - ev)[avg].sum())
+            stats[4] += int(np.minimum(nw[m], ew)[avg].sum())
+    return out, np.array(stats, dtype=np.uint64)
+
+
+def receivers(src, pose, res, margin=3):
+    """The DST world voxels (n, 3) int64 within +-margin voxels per axis of the image of an observed SRC voxel: for every voxel b of
+    SRC with weight > 0 its low corner point c = b res + h is mapped forward, m = rot^T (c - pivot_src) + pivot_dst in double
+    precision, and the voxels floor(m / res) + [-margin, margin]^3 are listed.  Voxel by voxel: nothing is shared with the chunk plan.
+
+    Why this holds every voxel that can receive anything, for a rotation: a valid sample needs its base voxel b valid, since the
+    corner (0, 0, 0) has the coefficient prod (res - f_k) > 0.  q then lies within [0, res)^3 of c: q = c + f with integer
+    0 <= f_k <= res - 1.  q is rot (p - pivot_dst) + pivot_src rounded to the nearest integer per axis, and rot_q30 is the rotation
+    rounded to 2^-30 per entry, which over |p - pivot_dst| < 2^24 adds less than 0.05 mm: rot (p - pivot_dst) + pivot_src = c + f + e
+    with |e_k| < 0.55.  So p = m + rot^T (f + e), and per axis |p - m| <= |f + e|_2 < sqrt(3) (res - 0.45): p lies within
+    res sqrt(3) + 1 mm of the mapped point, under 1.74 voxels per axis.  The voxel of p is v = (p - h) / res, and with
+    v0 = floor(m / res):  -1.74 - 0.5 < v - v0 < 1.74 + 1, so |v - v0| <= 2.  The default margin of 3 leaves an outer shell that no
+    valid sample may lie on (tests/test_fuse_domain_host.py holds every scene to that)."""
+    pose = np.asarray(pose, dtype=np.int64)
+    R, pd, ps = pose[:9].reshape(3, 3).astype(np.float64) / float(Q30), pose[9:12].astype(np.float64), pose[12:15].astype(np.float64)
+    local = np.stack(np.meshgrid(*(np.arange(CS, dtype=np.int64),) * 3, indexing="ij"), axis=-1).reshape(-1, 3)
+    base = []
+    for key in sorted(src):
+        b = local[unpack(np.asarray(src[key], dtype=np.uint32).reshape(-1))[1] > 0] + np.asarray(key, dtype=np.int64) * CS
+        m = ((b * res + res // 2).astype(np.float64) - ps) @ R + pd  # rot^T (c - pivot_src) + pivot_dst, row by row
+        base.append(np.floor(m / res).astype(np.int64))
+    if not base or not sum(len(b) for b in base):
+        return np.zeros((0, 3), dtype=np.int64)
+    base = np.unique(np.concatenate(base), axis=0)
+    r = np.arange(-margin, margin + 1, dtype=np.int64)
+    shell = np.stack(np.meshgrid(r, r, r, indexing="ij"), axis=-1).reshape(-1, 3)
+    return np.unique((base[:, None, :] + shell[None, :, :]).reshape(-1, 3), axis=0)
+
+
+def same_at(got, want):
+    """(chunks, stats) of a call against fuse_at's pair: the key set, every chunk's bytes and stats[1:6]"""
+    return (sorted(got[0]) == sorted(want[0]) and all(np.asarray(got[0][k], dtype=np.uint32).tobytes() == want[0][k].tobytes() for k in want[0])
+            and [int(v) for v in got[1]][-5:] == [int(v) for v in want[1]])
 
 
 def same(got, want):
