@@ -926,6 +926,43 @@ int ws_store_fuse(ws_store *dst, ws_store *src, const ws_fuse_pose *pull, int32_
  * the write pass (with the fill of the created chunks) of the last call with this store as DST */
 int ws_debug_store_fuse_timing(ws_store *dst, int32_t enable, float ms_out[3]);
 
+/* A store at half the resolution of another: every voxel of DST is 2 x 2 x 2 voxels of SRC, computed on the device without a chunk
+ * leaving HBM.  Every ws_store_* query takes the resolution as an argument, so the coarse store is queried, meshed, loaded into a
+ * window and registered against like any other, with twice the map_resolution.  The rule uses integers only and the result is the
+ * same bytes on every run.
+ *   children: the coarse world voxel V has the eight children 2 V + (i, j, k), i, j, k in {0, 1}, for negative coordinates too.  The
+ *     parent of the chunk key k is k >> 1 per axis (arithmetic shift, floor(k / 2)); a chunk of DST is fed by the up to eight chunks
+ *     2 K + {0, 1}^3 of SRC.  A child in an absent chunk of SRC is unobserved.
+ *   rule: a child is observed iff its weight is > 0 (there is no ANY_WEIGHT variant).  n = the number of observed children, S = the
+ *     sum of their values, W = the smallest of their weights.  With n >= min_observed the coarse entry is (floor(S / n), W), the
+ *     floor toward minus infinity; otherwise it is the fill_entry of DST.  |S| <= 2^18: everything is int32.
+ *   min_observed: 1 .. 8.  With 8 and an even resolution r the coarse entry is what ws_store_sample reports at the centre
+ *     (2 V + 1) r of the coarse voxel, where every trilinear fraction is r / 2: x = floor(S / 8), y = W, the cell valid.
+ *   listed chunks: with dst_keys == NULL the parents of every chunk of SRC; otherwise the n_keys given keys, in any order, duplicates
+ *     allowed.  A listed chunk with at least one child chunk in SRC exists in DST afterwards (created if need be) and all 262 144 of
+ *     its words are written, each with the coarse entry or fill_entry.  A listed chunk without a child chunk is not created; if it
+ *     exists, it is filled with fill_entry.  A chunk of DST that is not listed keeps every byte.
+ *   plan: which chunks are created follows from the two directories alone, so there is no count pass and no host read.  The new
+ *     chunks are counted before the launch (WS_ERR_CAPACITY, nothing changed, if they do not fit under max_chunks of DST), one row
+ *     per chunk {dst slot, eight child slots} travels through a slot table of DST's ring, and one launch writes the chunks.
+ *   stats: NULL: the call returns after enqueueing, stream-ordered on the context's stream behind everything enqueued on either
+ *     store.  Otherwise the call synchronises and reports: chunks processed; chunks created; coarse voxels that received a value;
+ *     coarse voxels with 1 <= n < min_observed.  Integer adds, exact whatever the order.
+ *   refusals, nothing changed and nothing launched: WS_ERR_INVALID: a NULL store, dst == src, stores of different contexts,
+ *     min_observed outside 1 .. 8, unknown flag bits, n_keys > 0 with NULL keys, a fill_entry of DST with weight > 0.  WS_ERR_RANGE:
+ *     2^23 chunks to write or more.  WS_ERR_CAPACITY: see above.  WS_ERR_HIP: a segment cannot be allocated.  A HIP error while
+ *     enqueueing takes the chunks the call created out of the directory again.  An empty SRC with dst_keys == NULL is WS_OK.
+ *   ordering: both stores' locks are taken in address order.  SRC is only read.  The result buffers of DST's queries stay untouched.
+ *   ws_store_parents_of: host only, no device: the parents of n keys, unique and ascending (cx, cy, cz); copies at most `capacity`
+ *     keys and always reports the count. */
+#define WS_COARSEN_DEFAULT 0u
+int ws_store_coarsen(ws_store *dst, ws_store *src, const int32_t *dst_keys /* n_keys x 3 or NULL */, size_t n_keys, int32_t min_observed, uint32_t flags,
+                     uint64_t stats[4] /* may be NULL */);
+int ws_store_parents_of(const int32_t *keys /* n x 3 */, size_t n, int32_t *parents /* capacity x 3 */, size_t capacity, size_t *n_out);
+/* Measurement entry, as ws_debug_store_fuse_timing: ms_out receives the device time of the plan's upload and of the pass of the last
+ * call with this store as DST */
+int ws_debug_store_coarsen_timing(ws_store *dst, int32_t enable, float ms_out[2]);
+
 /* ------------------------------------------------------------------ TSDF update ---- */
 /* TSDFCuda::update_tsdf(scan_points, scanner_pos, up) — update_tsdf.cu:143-166.
  * xyz_host: n x 3 int32 (rmagine::Pointi AoS); scanner_pos in voxel units, up scaled by 32768.

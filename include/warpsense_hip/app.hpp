@@ -356,6 +356,19 @@ public:
     out.candidates = s[0], out.created = s[1], out.averaged = s[2], out.set = s[3], out.sum_abs_diff = s[4], out.sum_min_weight = s[5];
     return out;
   }
+  // this map at half the resolution into `dst` (ws_store_coarsen): the chunks `keys` of dst rebuilt whole, nullptr: the parents of
+  // every chunk of this map; with_stats = false returns after enqueueing with zero statistics -- the contract of the Python
+  // DeviceGlobalMap.coarsen
+  CoarsenStats coarsen(DeviceGlobalMap &dst, const std::vector<Key> *keys = nullptr, int min_observed = 8, bool with_stats = true)
+  {
+    uint64_t s[4] = {0, 0, 0, 0};
+    const int32_t *k = keys && !keys->empty() ? (*keys)[0].data() : nullptr;
+    const int32_t none[3] = {0, 0, 0}; // (an empty list is not "every parent")
+    WS_CHECK(ws_store_coarsen(dst.store_, store_, keys ? (k ? k : none) : nullptr, keys ? keys->size() : 0, min_observed, WS_COARSEN_DEFAULT, with_stats ? s : nullptr));
+    CoarsenStats out;
+    out.chunks = s[0], out.created = s[1], out.valued = s[2], out.short_of = s[3];
+    return out;
+  }
   // every chunk merged into the host global map (and through it into its file)
   void flush_to(GlobalMap &g)
   {
@@ -417,6 +430,54 @@ inline PointSample global_map_sample(DeviceGlobalMap &g, int resolution, const s
 {
   return global_map_sample(g.handle(), resolution, points, band_mm, any_weight, with_gradient, select, lo, hi);
 }
+
+// ---------------------------------------------------------------------------------------------------- MapPyramid
+// `levels` coarser copies of a DeviceGlobalMap, each with twice the voxel edge of the one below (DeviceGlobalMap::coarsen) -- the
+// contract of the Python MapPyramid.  store(0) is the base, which the pyramid does not own; store(l) is queried like any
+// DeviceGlobalMap with resolution(l) = resolution << l.  The levels follow the base only when rebuild() or refresh() is called.
+class MapPyramid
+{
+public:
+  using Key = DeviceGlobalMap::Key;
+  MapPyramid(DeviceGlobalMap &base, int levels, int resolution, const TSDFEntry &default_entry, int min_observed = 8, uint32_t segment_chunks = 0)
+      : base_(base), resolution_(resolution), min_observed_(min_observed)
+  {
+    if (levels < 1) throw std::invalid_argument("MapPyramid: levels must be at least 1");
+    for (int l = 0; l < levels; ++l) stores_.emplace_back(new DeviceGlobalMap(default_entry, 0, segment_chunks));
+  }
+  int levels() const { return (int)stores_.size(); }
+  int min_observed() const { return min_observed_; }
+  DeviceGlobalMap &store(int level) { return level == 0 ? base_ : *stores_.at((size_t)level - 1); }
+  int resolution(int level) const { return resolution_ << level; }
+  // every level from the one below, over the parents of all its chunks
+  std::vector<CoarsenStats> rebuild(bool with_stats = true)
+  {
+    std::vector<CoarsenStats> out;
+    for (int l = 1; l <= levels(); ++l) out.push_back(store(l - 1).coarsen(store(l), nullptr, min_observed_, with_stats));
+    return out;
+  }
+  // after a change of the base inside the inclusive box [lo, hi] of base voxels: level 1 recomputes the parents of the chunks the box
+  // overlaps, every level above the parents of those; nothing else is touched
+  std::vector<CoarsenStats> refresh(const rm::Pointi &lo, const rm::Pointi &hi, bool with_stats = true)
+  {
+    size_t n = 0;
+    WS_CHECK(ws_store_chunks_of_box(&lo.x, &hi.x, nullptr, 0, &n));
+    std::vector<Key> keys(n);
+    WS_CHECK(ws_store_chunks_of_box(&lo.x, &hi.x, keys[0].data(), n, &n));
+    std::vector<CoarsenStats> out;
+    for (int l = 1; l <= levels(); ++l)
+    {
+      keys = parents_of(keys);
+      out.push_back(store(l - 1).coarsen(store(l), &keys, min_observed_, with_stats));
+    }
+    return out;
+  }
+
+private:
+  DeviceGlobalMap &base_;
+  int resolution_, min_observed_;
+  std::vector<std::unique_ptr<DeviceGlobalMap>> stores_;
+};
 
 // ---------------------------------------------------------------------------------------------------- LocalMap
 // The in-memory state of HDF5LocalMap (hdf5_local_map.cpp:5-20): odd sizes, offset = size / 2, default-filled.
@@ -489,6 +550,7 @@ public:
   {
     if (!device_global_map_) throw std::logic_error("shift_map_device: no DeviceGlobalMap attached");
     wait_shift();
+    pyramid_touch(); // (the leaving slabs go into chunks that global_pyramid has to refresh)
     WS_CHECK(ws_shift_device(gpu_.tsdf().handle(), device_global_map_->handle(), &new_pos.x));
     local_map_.follow(new_pos);
   }
@@ -798,7 +860,31 @@ public:
     WS_CHECK(ws_store_save_box(device_global_map_->handle(), gpu_.tsdf().handle(), WS_MAP_AVG, &wlo.x, &whi.x));
     const FuseStats st = device_global_map_->fuse(other, pose, max_weight < 0 ? params_.max_weight : max_weight, count_only, params_.map_resolution);
     if (!count_only) WS_CHECK(ws_store_load_box(device_global_map_->handle(), gpu_.tsdf().handle(), WS_MAP_AVG, &wlo.x, &whi.x));
+    if (!count_only) pyramid_all_ = true; // (the fuse wrote chunks anywhere: global_pyramid rebuilds)
     return st;
+  }
+  // Coarser levels of everything the run has seen: the window into the device chunks, as global_mesh does, then a MapPyramid over the
+  // store, rebuilt (the first call, other levels or min_observed, after merge_map) or refreshed over the windows the node has held
+  // since the last call.  The node keeps the pyramid; chunks written into the store behind its back want MapPyramid::rebuild().
+  MapPyramid &global_pyramid(int levels, int min_observed = 8, uint32_t segment_chunks = 0)
+  {
+    if (!device_global_map_) throw std::logic_error("global_pyramid: no DeviceGlobalMap attached");
+    wait_shift();
+    rm::Pointi wlo, whi;
+    local_map_.window(wlo, whi);
+    WS_CHECK(ws_store_save_box(device_global_map_->handle(), gpu_.tsdf().handle(), WS_MAP_AVG, &wlo.x, &whi.x));
+    if (!pyramid_ || &pyramid_->store(0) != device_global_map_ || pyramid_->levels() != levels || pyramid_->min_observed() != min_observed)
+    {
+      pyramid_.reset(new MapPyramid(*device_global_map_, levels, params_.map_resolution, local_map_.global_map().get_default_tsdf_entry(), min_observed, segment_chunks));
+      pyramid_all_ = true, pyramid_dirty_ = false;
+    }
+    pyramid_touch();
+    if (pyramid_all_)
+      pyramid_->rebuild(false);
+    else
+      pyramid_->refresh(dirty_lo_, dirty_hi_, false);
+    pyramid_all_ = pyramid_dirty_ = false;
+    return *pyramid_;
   }
   // The same through everything the run has seen: the window into the device chunks, as global_mesh does, then the view gain of the
   // store (without a box: the bounding box of the chunks)
@@ -842,11 +928,27 @@ public:
   SurfaceCloud surface(bool marker = true) { return local_map_cloud(gpu_.tsdf(), WS_MAP_AVG, marker); }
 
 private:
+  // the present window joins the box that global_pyramid has to refresh
+  void pyramid_touch()
+  {
+    if (!pyramid_) return;
+    rm::Pointi lo, hi;
+    local_map_.window(lo, hi);
+    if (pyramid_dirty_)
+    {
+      lo = rm::Pointi(std::min(lo.x, dirty_lo_.x), std::min(lo.y, dirty_lo_.y), std::min(lo.z, dirty_lo_.z));
+      hi = rm::Pointi(std::max(hi.x, dirty_hi_.x), std::max(hi.y, dirty_hi_.y), std::max(hi.z, dirty_hi_.z));
+    }
+    dirty_lo_ = lo, dirty_hi_ = hi, pyramid_dirty_ = true;
+  }
   cuda::HotPathParams params_;
   LocalMap &local_map_;
   cuda::DeviceMap view_;
   cuda::TSDFRegistration gpu_;
   DeviceGlobalMap *device_global_map_ = nullptr;
+  std::unique_ptr<MapPyramid> pyramid_; // global_pyramid's, with the box of base voxels that changed since it last ran
+  bool pyramid_all_ = false, pyramid_dirty_ = false;
+  rm::Pointi dirty_lo_, dirty_hi_;
   std::thread shift_worker_;
   std::string shift_error_; // written by the worker, read after join()
 };

@@ -9,8 +9,10 @@
 // reinterpret_casts between the two (tsdf_registration.cpp:32).  Map ownership stays with the caller.
 #pragma once
 
+#include <array>
 #include <cmath>
 #include <stdexcept>
+#include <vector>
 #include <memory>
 #include <mutex>
 #include <shared_mutex>
@@ -294,5 +296,22 @@ inline FusePose fuse_pose(const double T[16], const double *pivot_src_mm = nullp
     p.pivot_src_mm[i] = (int32_t)ps[i];
   }
   return p;
+}
+
+// ---- a device global map at half the resolution of another (ws_store_coarsen, warpsense_hip.h)
+// stats[4] of ws_store_coarsen
+struct CoarsenStats
+{
+  uint64_t chunks = 0, created = 0, valued = 0, short_of = 0; // short_of: coarse voxels with 1 <= n < min_observed (Python: short)
+};
+// host only: the parents k >> 1 of chunk keys, unique and ascending (cx, cy, cz) (ws_store_parents_of)
+inline std::vector<std::array<int32_t, 3>> parents_of(const std::vector<std::array<int32_t, 3>> &keys)
+{
+  size_t n = 0;
+  const int32_t *in = keys.empty() ? nullptr : keys[0].data();
+  WS_CHECK(ws_store_parents_of(in, keys.size(), nullptr, 0, &n));
+  std::vector<std::array<int32_t, 3>> out(n);
+  WS_CHECK(ws_store_parents_of(in, keys.size(), n ? out[0].data() : nullptr, n, &n));
+  return out;
 }
 } // namespace warpsense

@@ -68,6 +68,8 @@ def main():
                     "TSDFMapping.surface_mesh) as binary little-endian PLY into DIR, after every N-th scan like --surface-ply")
     ap.add_argument("--global-mesh-ply", default=None, metavar="FILE", help="after the last scan: the mesh of the WHOLE run, window and every chunk that "
                     "has left it, from the device global map (TSDFMapping.global_mesh, ws_store_mesh); needs --device-global-map")
+    ap.add_argument("--global-mesh-level", type=int, default=0, metavar="L", help="the level of detail of --global-mesh-ply: 0 the map's resolution, L the "
+                    "store coarsened L times (voxels of 2^L times the edge; TSDFMapping.global_pyramid, ws_store_coarsen)")
     ap.add_argument("--global-surface-ply", default=None, metavar="FILE", help="after the last scan: the surface cloud of the WHOLE run, window and every "
                     "chunk that has left it, from the device global map (TSDFMapping.global_surface_cloud, ws_store_surface) as PLY; needs "
                     "--device-global-map")
@@ -114,6 +116,8 @@ def main():
     args = ap.parse_args()
     if args.global_mesh_ply and not args.device_global_map:
         ap.error("--global-mesh-ply requires --device-global-map")
+    if args.global_mesh_level < 0 or (args.global_mesh_level and not args.global_mesh_ply):
+        ap.error("--global-mesh-level is a level >= 0 and requires --global-mesh-ply")
     if args.global_surface_ply and not args.device_global_map:
         ap.error("--global-surface-ply requires --device-global-map")
     if args.global_frontier_ply and not args.device_global_map:
@@ -248,12 +252,14 @@ def main():
     global_mesh = None
     if args.global_mesh_ply:
         tg = time.perf_counter()
-        gv, gf = app.gpu_.global_mesh()
+        gv, gf = app.gpu_.global_mesh(level=args.global_mesh_level)
         tg = time.perf_counter() - tg
         os.makedirs(os.path.dirname(os.path.abspath(args.global_mesh_ply)), exist_ok=True)
         W.write_mesh_ply(args.global_mesh_ply, gv, gf)
-        global_mesh = {"file": args.global_mesh_ply, "vertices": int(len(gv)), "faces": int(len(gf)), "chunks": app.gpu_.device_global_map_.count(), "call_s": tg}
-        print(f"global mesh: {len(gv)} vertices, {len(gf)} faces from {global_mesh['chunks']} chunks in {1000.0 * tg:.2f} ms (save_box + ws_store_mesh + download)",
+        global_mesh = {"file": args.global_mesh_ply, "vertices": int(len(gv)), "faces": int(len(gf)), "chunks": app.gpu_.device_global_map_.count(), "call_s": tg,
+                       "level": args.global_mesh_level}
+        route = "save_box + ws_store_mesh + download" if not args.global_mesh_level else "save_box + ws_store_coarsen per level + ws_store_mesh + download"
+        print(f"global mesh (level {args.global_mesh_level}): {len(gv)} vertices, {len(gf)} faces from {global_mesh['chunks']} chunks in {1000.0 * tg:.2f} ms ({route})",
               file=sys.stderr)
     global_surface = None
     if args.global_surface_ply:

@@ -15,6 +15,8 @@ from .records import VIEW_GAIN_RAY, VIEW_GAIN_RECORD, gain_volume_m3, rank_views
 from ._lib import WS_GAIN_ANY_WEIGHT, WS_GAIN_DEFAULT, WS_GAIN_RAYS  # noqa: F401
 from .fuse import FuseStats, fuse_pose, pose_transform  # noqa: F401
 from ._lib import WS_FUSE_COUNT_ONLY, WS_FUSE_DEFAULT  # noqa: F401
+from .pyramid import CoarsenStats, MapPyramid, parents_of  # noqa: F401
+from ._lib import WS_COARSEN_DEFAULT  # noqa: F401
 
 __all__ = [n for n in dir() if not n.startswith("_")]
 from .app import App  # noqa: F401,E402

@@ -56,6 +56,7 @@ EXPORTS = [
     "ws_map_view_gain", "ws_map_view_gain_records_dev", "ws_map_view_gain_rays_dev", "ws_map_view_gain_download", "ws_debug_view_gain_timing",
     "ws_store_view_gain", "ws_store_view_gain_records_dev", "ws_store_view_gain_rays_dev", "ws_store_view_gain_download", "ws_debug_store_view_gain_timing",
     "ws_store_fuse", "ws_debug_store_fuse_timing",
+    "ws_store_coarsen", "ws_store_parents_of", "ws_debug_store_coarsen_timing",
 ]
 WS_SURFACE_RECORDS, WS_SURFACE_MARKER = 0, 1
 WS_MESH_DEFAULT, WS_MESH_ANY_WEIGHT = 0, 1
@@ -68,6 +69,7 @@ WS_FRONTIER_DEFAULT, WS_FRONTIER_ANY_WEIGHT, WS_FRONTIER_CLUSTERS = 0, 1, 2
 WS_REACH_DEFAULT, WS_REACH_UNKNOWN_FREE, WS_REACH_UNREACHABLE = 0, 1, 0xFFFFFFFF
 WS_GAIN_DEFAULT, WS_GAIN_ANY_WEIGHT, WS_GAIN_RAYS = 0, 1, 2
 WS_FUSE_DEFAULT, WS_FUSE_COUNT_ONLY = 0, 1
+WS_COARSEN_DEFAULT = 0
 
 
 class WsError(RuntimeError):
@@ -241,6 +243,9 @@ def load() -> C.CDLL:
     L.ws_debug_store_view_gain_timing.argtypes = [vp, i32, vp]
     L.ws_store_fuse.argtypes = [vp, vp, vp, i32, i32, u32, vp]
     L.ws_debug_store_fuse_timing.argtypes = [vp, i32, vp]
+    L.ws_store_coarsen.argtypes = [vp, vp, vp, sz, i32, u32, vp]
+    L.ws_store_parents_of.argtypes = [vp, sz, vp, sz, P(sz)]
+    L.ws_debug_store_coarsen_timing.argtypes = [vp, i32, vp]
     L.ws_debug_reach_active.argtypes = [vp, vp, sz, P(sz)]
     L.ws_shift_plan.argtypes = [vp, vp, vp, vp, P(ShiftPlan)]
     L.ws_shift_begin.argtypes = [vp, vp, u32, P(vp)]

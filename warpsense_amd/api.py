@@ -26,6 +26,7 @@ This module only gathers the names; the code lives in one module per subsystem, 
     store.py         DeviceGlobalMap, chunks_of_box                                 (api_store)
     fuse.py          fuse_pose, FuseStats: one global map fused into another        (api_store)
     merge.py         merge_map and align_map of TSDFMapping
+    pyramid.py       CoarsenStats, parents_of, MapPyramid, global_pyramid           (api_store)
     device_map.py    DeviceMap, LocalMap, DeviceMapMemWrapper, TSDFCuda             (api_map, api_tsdf)
     registration.py  RegistrationCuda, batch_best, candidate_poses                  (api_reg)
     mapping.py       the parameters, TSDFMapping, TSDFRegistration
@@ -46,3 +47,4 @@ from .registration import RegistrationCuda, batch_best, candidate_poses  # noqa:
 from .scan import DevicePoints, ScanPreprocessor, preprocess_sweep_host, sweep_bins, sweep_poses, to_int_mat, to_map  # noqa: F401
 from .store import DeviceGlobalMap, chunks_of_box  # noqa: F401
 from .fuse import FuseStats, fuse_pose, pose_transform  # noqa: F401
+from .pyramid import CoarsenStats, MapPyramid, parents_of  # noqa: F401

@@ -1,7 +1,8 @@
 // api_store.hip — the chunk store, the global map in device memory (ws_store_*, ws_shift_device; kernels in map_store.hip): directory,
 // segments and slot tables, the box transfers between a map's window and the chunks, and the store's surface cloud, mesh, ray cast and
 // distance field, which run the host cores of ws_api.h over the chunks a call lists (store_surface.hip, store_mesh.hip,
-// store_raycast.hip, store_distance.hip).
+// store_raycast.hip, store_distance.hip), and the two calls that write one store from another: ws_store_fuse (store_fuse.hip) and
+// ws_store_coarsen (store_coarsen.hip).
 #include <algorithm>
 #include <array>
 #include <cmath>
@@ -11,6 +12,7 @@
 #include <set>
 
 #include "ws_api.h"
+#include "ws_coarsen.h"
 #include "ws_fuse.h"
 
 using namespace ws;
@@ -1240,4 +1242,148 @@ int ws_debug_store_fuse_timing(ws_store *dst, int32_t enable, float ms_out[3])
   if (!dst) return invalid("ws_debug_store_fuse_timing: store is NULL");
   std::lock_guard<std::mutex> lock(dst->mu);
   return query_timing(dst->ctx->stream, dst->fuse.timer, enable, ms_out, FUSE_PAIRS, 3);
+}
+
+// ---- a store at half the resolution of another: the plan and the one pass of ws_store_coarsen (the rule is stated in
+// warpsense_hip.h and lives in ws_coarsen.h; the kernel in store_coarsen.hip)
+namespace
+{
+constexpr int COARSEN_PAIRS[2][2] = {{0, 1}, {1, 2}};
+
+inline StoreKey parent_of(const StoreKey &k) { return {k[0] >> 1, k[1] >> 1, k[2] >> 1}; } // (arithmetic shift: floor(k / 2))
+
+// The slots of the eight children of dst chunk `key` in SRC into w[1 .. 8], index cx * 4 + cy * 2 + cz: STORE_ABSENT where SRC has no
+// such chunk, has not written it yet, or the child's key 2 key + {0, 1} does not lie in int32.  Returns whether any child exists.
+bool coarsen_children(const ws_store *src, const StoreKey &key, uint32_t *w)
+{
+  bool any = false;
+  for (int c = 0; c < 8; ++c)
+  {
+    const int64_t ck[3] = {2 * (int64_t)key[0] + (c >> 2), 2 * (int64_t)key[1] + ((c >> 1) & 1), 2 * (int64_t)key[2] + (c & 1)};
+    w[1 + c] = STORE_ABSENT;
+    if (ck[0] < INT32_MIN || ck[0] > INT32_MAX || ck[1] < INT32_MIN || ck[1] > INT32_MAX || ck[2] < INT32_MIN || ck[2] > INT32_MAX) continue;
+    const auto it = src->dir.find(StoreKey{(int32_t)ck[0], (int32_t)ck[1], (int32_t)ck[2]});
+    if (it == src->dir.end() || !it->second.written) continue;
+    w[1 + c] = it->second.slot;
+    any = true;
+  }
+  return any;
+}
+
+// everything of the call behind its refusals; both locks are held
+int coarsen_run(ws_store *dst, ws_store *src, const std::set<StoreKey> &listed, int32_t min_observed, uint64_t *stats)
+{
+  hipStream_t s = dst->ctx->stream;
+  ws_store::Coarsen &q = dst->coarsen;
+  // the plan is a directory decision: one row per listed chunk that exists afterwards, the chunks to create counted before any launch
+  std::vector<uint32_t> rows;
+  std::vector<StoreKey> row_key;
+  std::set<StoreKey> fresh;
+  for (const StoreKey &k : listed)
+  {
+    uint32_t w[COARSEN_ROW] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    const bool any = coarsen_children(src, k, w);
+    const auto it = dst->dir.find(k);
+    if (it == dst->dir.end() && !any) continue; // no child and no chunk: not created
+    if (it == dst->dir.end()) fresh.insert(k);
+    else w[0] = it->second.slot;
+    rows.insert(rows.end(), w, w + COARSEN_ROW);
+    row_key.push_back(k);
+  }
+  const size_t n = row_key.size();
+  if (n >= COARSEN_MAX_CHUNKS) return range_error("ws_store_coarsen", ": 2^23 chunks of DST or more");
+  if (stats) stats[0] = n, stats[1] = fresh.size(), stats[2] = stats[3] = 0;
+  if (n == 0) return WS_OK;
+  WS_TRY(store_make_room(dst, fresh.size(), "ws_store_coarsen"));
+  if (stats && (!q.words.cap || !q.words_host.cap))
+  {
+    WS_TRY(q.words.alloc(2, sizeof(unsigned long long)));
+    WS_TRY(q.words_host.alloc(2, sizeof(unsigned long long), HostBlock::PINNED));
+  }
+  for (const StoreKey &k : fresh) dst->dir[k] = ws_store::Entry{store_take_slot(dst), true}; // (the pass writes every word of them)
+  for (size_t i = 0; i < n; ++i)
+    if (fresh.count(row_key[i])) rows[i * COARSEN_ROW] = dst->dir[row_key[i]].slot;
+
+  const auto enqueue = [&]() -> int {
+    ws_store::Table *t = nullptr;
+    WS_TRY(store_table(dst, rows.size(), &t));
+    std::memcpy(t->host.p, rows.data(), rows.size() * sizeof(uint32_t));
+    if (stats) WS_HIP(hipMemsetAsync(q.words.p, 0, 2 * sizeof(unsigned long long), s));
+    q.timer.mark(0, s);
+    WS_HIP(hipMemcpyAsync(t->dev.p, t->host.p, rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    q.timer.mark(1, s);
+    CoarsenArgs a;
+    a.rows = t->dev.as<uint32_t>();
+    a.src_segs = src->seg_tab.as<uint32_t *>(), a.src_shift = src->seg_shift;
+    a.dst_segs = dst->seg_tab.as<uint32_t *>(), a.dst_shift = dst->seg_shift; // (after store_make_room: a new segment replaces the table)
+    a.fill = dst->fill, a.min_observed = min_observed;
+    a.stats = stats ? q.words.as<unsigned long long>() : nullptr;
+    WS_TRY(launch_store_coarsen(s, a, n));
+    q.timer.mark(2, s);
+    WS_HIP(hipEventRecord(t->done, s));
+    t->used = true;
+    if (stats) WS_HIP(hipMemcpyAsync(q.words_host.p, q.words.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    return WS_OK;
+  };
+  const int rc = enqueue();
+  if (rc != WS_OK) // the created chunks leave the directory again; launches already enqueued still run
+  {
+    (void)hipStreamSynchronize(s);
+    store_evict(dst, fresh);
+    return rc;
+  }
+  if (!stats) return WS_OK;
+  WS_HIP(hipStreamSynchronize(s));
+  stats[2] = q.words_host.as<unsigned long long>()[0], stats[3] = q.words_host.as<unsigned long long>()[1];
+  return WS_OK;
+}
+} // namespace
+
+int ws_store_parents_of(const int32_t *keys, size_t n, int32_t *parents, size_t capacity, size_t *n_out)
+{
+  if ((!keys && n) || (!parents && capacity)) return invalid("ws_store_parents_of: bad argument");
+  std::set<StoreKey> up;
+  for (size_t i = 0; i < n; ++i) up.insert(parent_of(StoreKey{keys[3 * i], keys[3 * i + 1], keys[3 * i + 2]}));
+  size_t i = 0;
+  for (const StoreKey &k : up)
+  {
+    if (i >= capacity) break;
+    for (int a = 0; a < 3; ++a) parents[3 * i + a] = k[a];
+    ++i;
+  }
+  if (n_out) *n_out = up.size();
+  return WS_OK;
+}
+
+int ws_store_coarsen(ws_store *dst, ws_store *src, const int32_t *dst_keys, size_t n_keys, int32_t min_observed, uint32_t flags, uint64_t stats[4])
+{
+  if (!dst || !src) return invalid("ws_store_coarsen: NULL argument");
+  if (flags != WS_COARSEN_DEFAULT) return invalid("ws_store_coarsen: unknown flag bits");
+  if (dst == src) return invalid("ws_store_coarsen: dst and src are the same store");
+  if (dst->ctx != src->ctx) return invalid("ws_store_coarsen: the stores belong to different contexts");
+  if (min_observed < 1 || min_observed > 8) return invalid("ws_store_coarsen: min_observed must be 1 .. 8");
+  if (n_keys && !dst_keys) return invalid("ws_store_coarsen: n_keys > 0 with NULL keys");
+  if ((int16_t)(dst->fill >> 16) > 0) return invalid("ws_store_coarsen: the fill_entry of dst has a weight > 0");
+  servers_leave(dst->ctx);
+  // both locks, in address order
+  ws_store *first = std::less<ws_store *>()(dst, src) ? dst : src, *second = first == dst ? src : dst;
+  std::lock_guard<std::mutex> lock_a(first->mu), lock_b(second->mu);
+  WS_TRY(dst->coarsen.timer.arm());
+  std::set<StoreKey> listed;
+  if (dst_keys)
+    for (size_t i = 0; i < n_keys; ++i) listed.insert(StoreKey{dst_keys[3 * i], dst_keys[3 * i + 1], dst_keys[3 * i + 2]});
+  else
+    for (const auto &kv : src->dir)
+      if (kv.second.written) listed.insert(parent_of(kv.first));
+  uint64_t out[4] = {0, 0, 0, 0};
+  WS_TRY(coarsen_run(dst, src, listed, min_observed, stats ? out : nullptr));
+  for (int k = 0; k < 4 && stats; ++k) stats[k] = out[k];
+  return WS_OK;
+}
+
+int ws_debug_store_coarsen_timing(ws_store *dst, int32_t enable, float ms_out[2])
+{
+  if (!dst) return invalid("ws_debug_store_coarsen_timing: store is NULL");
+  std::lock_guard<std::mutex> lock(dst->mu);
+  return query_timing(dst->ctx->stream, dst->coarsen.timer, enable, ms_out, COARSEN_PAIRS, 2);
 }

@@ -782,8 +782,16 @@ struct ws_store
     ws::QueryTimer timer;
     void release() { words.release(), words_host.release(), timer.release(); }
   } fuse;
+  struct Coarsen // ws_store_coarsen with this store as DST (store_coarsen.hip)
+  {
+    ws::DevBuf words;         // uint64 [2] the sums of the pass: voxels that received a value, voxels short of min_observed
+    ws::HostBlock words_host; // ... and the pinned block the host reads them from
+    ws::QueryTimer timer;     // 0 upload of the plan 1 the pass 2
+    void release() { words.release(), words_host.release(), timer.release(); }
+  } coarsen;
   void release()
   {
+    coarsen.release();
     fuse.release();
     gain.release();
     reach.release();

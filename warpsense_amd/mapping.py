@@ -14,6 +14,7 @@ from .context import Context
 from .device_map import DeviceMap, LocalMap, TSDFCuda
 from .global_map import GlobalMap
 from .merge import FuseQueries
+from .pyramid import PyramidQueries
 from .gain import GainQueries
 from .reach import ReachQueries
 from .records import SAMPLE_CLASSES
@@ -72,7 +73,7 @@ def _dirs_or_os1(dirs):
     return dirs
 
 
-class TSDFMapping(ReachQueries, GainQueries, FuseQueries):
+class TSDFMapping(ReachQueries, GainQueries, FuseQueries, PyramidQueries):
     """cuda::TSDFMapping without ROS (the protected constructor path, tsdf_mapping.cpp:30-41)."""
 
     def __init__(self, params: Params, local_map: LocalMap, ctx: Context | None = None, device_global_map: "DeviceGlobalMap | None" = None):
@@ -138,10 +139,13 @@ class TSDFMapping(ReachQueries, GainQueries, FuseQueries):
             self.device_global_map_.save_box(self.tsdf_, lo, hi)
             yield self.device_global_map_
 
-    def global_mesh(self, **kw):
+    def global_mesh(self, level=0, **kw):
         """The mesh of everything the run has seen: the window goes into the chunks of device_global_map (ws_store_save_box, the
         first step of write_back, with its capacity refusals), then DeviceGlobalMap.mesh at the map's resolution -- under the
-        mapping's lock like a writer, nothing leaves the device but the mesh.  Keywords: lo, hi, any_weight, device."""
+        mapping's lock like a writer, nothing leaves the device but the mesh.  Keywords: lo, hi, any_weight, device.
+        level > 0: the mesh of that level of global_pyramid at its resolution (PyramidQueries._level_mesh)."""
+        if level:
+            return self._level_mesh(int(level), **kw)
         with self._window_in_store("global_mesh") as store:
             return store.mesh(int(self.params_.map.resolution), **kw)
 
@@ -398,6 +402,7 @@ class TSDFMapping(ReachQueries, GainQueries, FuseQueries):
         lm = self.local_map_
         new_pos = _i3(new_pos)
         with self.mutex_:
+            self._pyramid_touch(*lm.window())  # (the leaving slabs go into chunks that global_pyramid has to refresh)
             check(self.tsdf_._L.ws_shift_device(self.tsdf_.handle, self.device_global_map_.handle, _ptr(new_pos)), "ws_shift_device")
             lm.follow(new_pos)
 

@@ -34,6 +34,7 @@ class FuseQueries:
                 if not count_only:
                     lo, hi = self.local_map_.window()
                     store.load_box(self.tsdf_, lo, hi)
+                    self._pyramid_touch()  # (the fuse wrote chunks anywhere: global_pyramid rebuilds)
             finally:
                 if tmp is not None:
                     tmp.close()

@@ -11,6 +11,7 @@ from ._lib import WS_MAP_AVG, check
 from .context import Context
 from .fuse import FuseStats, _fuse_call, fuse_pose
 from .global_map import GlobalMap
+from .pyramid import CoarsenStats, _coarsen_call
 from .queries import _box_ptrs, _distance_call, _frontier_call, _reach_call, _reach_lookup_call, _reach_paths_call, _mesh_call, _raycast_call, _sample_call, _surface_call, _timing, _view_gain_call
 
 
@@ -235,6 +236,19 @@ class DeviceGlobalMap:
     def fuse_timing(self, enable: int = -1):
         """ws_debug_store_fuse_timing: read the last call's three spans; enable 1 / 0 switches the events on / off"""
         return _timing(self._L, "ws_debug_store_fuse_timing", self.handle, 3, enable)
+
+    def coarsen(self, dst: "DeviceGlobalMap", keys=None, min_observed=8, stats=True) -> CoarsenStats | None:
+        """This map at half the resolution into `dst`, on the device (ws_store_coarsen; the rule is stated in
+        include/warpsense_hip.h): every voxel of `dst` is 2 x 2 x 2 voxels of this map, the floor of the mean of the observed
+        ones (weight > 0) with the smallest of their weights where at least min_observed (1 .. 8) are observed, the default entry
+        of `dst` elsewhere.  keys: the (n, 3) chunks of `dst` to rebuild whole (None: the parents of every chunk of this map);
+        every other chunk of `dst` keeps its bytes.  stats=False returns None after enqueueing, without a wait.  This map is only
+        read; `dst` is queried with twice this map's resolution."""
+        return _coarsen_call(self._L, self, dst, keys, min_observed, stats)
+
+    def coarsen_timing(self, enable: int = -1):
+        """device milliseconds of the plan's upload and of the pass of the last coarsen() INTO this map (ws_debug_store_coarsen_timing)"""
+        return _timing(self._L, "ws_debug_store_coarsen_timing", self.handle, 2, enable)
 
     def flush_to(self, global_map: GlobalMap):
         """every chunk merged into a host GlobalMap: into its chunk cache (activate_chunk), or, for a map with a file, straight
