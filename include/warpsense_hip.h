@@ -963,6 +963,63 @@ int ws_store_parents_of(const int32_t *keys /* n x 3 */, size_t n, int32_t *pare
  * call with this store as DST */
 int ws_debug_store_coarsen_timing(ws_store *dst, int32_t enable, float ms_out[2]);
 
+/* Change detection between two stores: WHERE the store CUR ("now") differs from the store REF ("before") under a rigid pose -- what
+ * has appeared, what has been taken away -- as ordered records with clusters and exact statistics, on the device, without a chunk
+ * leaving HBM.  The rule uses integers only and the result is the same bytes on every run.
+ *   lattice and transform: the comparison runs on the voxel lattice of CUR.  The map from the frame of CUR to the frame of REF is the
+ *     pull transform of ws_store_fuse with CUR in the place of DST and REF in the place of SRC: the same ws_fuse_pose, the same voxel
+ *     mapping q(p) for the centre p = v res + h, the same reach (a voxel with a component of |p - pivot_dst| >= 2^24 mm is outside
+ *     the call) and the same dead rule (a component of q of magnitude >= 2^30: the sample is not valid).
+ *   voxels examined: the voxels of the PRESENT chunks of CUR that lie in the inclusive world-voxel box [lo, hi] and within the reach.
+ *     The box rules are those of ws_store_frontier: both NULL: the bounding box of the present chunks; exactly one NULL or hi < lo:
+ *     WS_ERR_INVALID; a box that meets no present chunk: WS_OK with zero records and zero statistics; 2^19 or more present chunks in
+ *     the box: WS_ERR_RANGE.  A voxel of an absent chunk of CUR is unknown and is never examined.
+ *   CUR side: the entry (ev, ew); KNOWN iff ew >= min_weight.
+ *   REF side: the sample of ws_store_fuse at q, exactly as the fuse takes it, gives (nv, nw) or "not valid": corners with a zero
+ *     coefficient take no part, a corner is valid iff its weight is > 0, a voxel of an absent chunk is not valid.  KNOWN iff the
+ *     sample is valid and nw >= min_weight.
+ *   classes of a known side with value d (ev, or nv): OCCUPIED iff |d| < band; FREE iff d >= free_value; otherwise neither.  Raw
+ *     values, as in the frontier: the store knows no tau.
+ *   kinds: APPEARED (1) iff CUR is OCCUPIED and REF is FREE; VANISHED (2) iff CUR is FREE and REF is OCCUPIED.  Nothing else is a
+ *     record; unknown on either side is never a change.
+ *   record: 16 bytes: x, y, z in world voxels of CUR, then the word (uint16)nv | kind << 16.  The records come in the output order of
+ *     ws_store_frontier: ascending world (x, y, z), z fastest, across chunk borders.
+ *   stats[6]: chunks of CUR listed; voxels known on both sides; voxels appeared; voxels vanished; voxels known in CUR and not in REF
+ *     (new ground); over the voxels known on both sides the sum of |nv - ev|.  Integer adds, exact whatever the order; they always
+ *     cover both kinds, whatever the flags select.
+ *   flags: WS_CHANGES_APPEARED, WS_CHANGES_VANISHED: the kinds that become records (WS_CHANGES_DEFAULT: both).  WS_CHANGES_CLUSTERS:
+ *     the labels and the 64-byte cluster table of ws_map_frontier over the selected records, with its numbering and its 2^31 - 1
+ *     limit; with both kinds selected a moved object whose old and new place touch is one cluster.  Unknown bits, or no kind bit:
+ *     WS_ERR_INVALID.
+ *   refusals, nothing launched and the last result stays: WS_ERR_INVALID: a NULL store, pose or stats; cur == ref; stores of
+ *     different contexts; a rot_q30 entry out of range; the box (above).  WS_ERR_RANGE: map_resolution < 1 or > 1024; band < 1;
+ *     free_value < band or > 32767; min_weight < 1 or > 32767; 2^19 or more chunks of REF, or of CUR in the box.
+ *   consequences: under the identity pose (rot = 2^30 I, equal pivots) every fraction is 0 and the rule is a plain voxel-by-voxel
+ *     comparison of the two entries (the REF entry counts with weight > 0 and >= min_weight).  A store compared with a byte copy of
+ *     itself gives zero records, and stats[1] equals its voxels with weight >= min_weight.
+ *   ordering and ownership: both stores' locks are taken in address order; the work is stream-ordered behind everything enqueued on
+ *     either store; the call synchronises.  Both stores are only read.  The result belongs to CUR, is apart from every other query's
+ *     result (the frontier's included) and stays valid until the next ws_store_changes with this store as CUR.  Every output write is
+ *     bounded by the buffers' capacities.
+ *   cost: a count pass over the listed chunks of CUR (one coalesced read of CUR; REF is gathered only by the lanes whose CUR entry is
+ *     known), the scan, and an emit pass that samples again on the voxels of the records: no buffer follows the number of voxels
+ *     (32 KB of scratch and 32 bytes of tables per listed chunk, 16 bytes per chunk place of REF's lookup). */
+#define WS_CHANGES_APPEARED 1u
+#define WS_CHANGES_VANISHED 2u
+#define WS_CHANGES_CLUSTERS 4u
+#define WS_CHANGES_DEFAULT 3u
+int ws_store_changes(ws_store *cur, ws_store *ref, const ws_fuse_pose *pull, int32_t map_resolution, const int32_t lo[3], const int32_t hi[3], int32_t band,
+                     int32_t free_value, int32_t min_weight, uint32_t flags, size_t *n_out, size_t *n_clusters, uint64_t stats[6]);
+const void *ws_store_changes_records_dev(const ws_store *cur, size_t *n);    /* device memory, n x 16 bytes; NULL when n == 0 */
+const uint32_t *ws_store_changes_labels_dev(const ws_store *cur, size_t *n); /* n uint32; NULL unless the last call asked for clusters */
+const void *ws_store_changes_clusters_dev(const ws_store *cur, size_t *n);   /* n x 64 bytes; NULL unless the last call asked for them */
+/* as ws_map_frontier_download */
+int ws_store_changes_download(ws_store *cur, void *records_host, uint32_t *labels_host, void *clusters_host, size_t cap_records, size_t cap_clusters, size_t *n_out,
+                              size_t *n_clusters);
+/* Measurement entry, as ws_debug_store_frontier_timing: ms_out receives the device time of the tables' upload with the count pass, of
+ * the scan, of the emit pass and of the clustering of the last call with this store as CUR */
+int ws_debug_store_changes_timing(ws_store *cur, int32_t enable, float ms_out[4]);
+
 /* ------------------------------------------------------------------ TSDF update ---- */
 /* TSDFCuda::update_tsdf(scan_points, scanner_pos, up) — update_tsdf.cu:143-166.
  * xyz_host: n x 3 int32 (rmagine::Pointi AoS); scanner_pos in voxel units, up scaled by 32768.

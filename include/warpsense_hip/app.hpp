@@ -270,6 +270,15 @@ private:
 #endif
 };
 
+// what DeviceGlobalMap::changes returns (ws_store_changes)
+struct Changes
+{
+  std::vector<ChangeRecord> records;     // ascending world (x, y, z), z fastest
+  std::vector<uint32_t> labels;          // the cluster number of every record; empty unless asked for
+  std::vector<FrontierCluster> clusters; // numbered by their first record; empty unless asked for
+  ChangeStats stats;
+};
+
 // ---------------------------------------------------------------------------------------------------- DeviceGlobalMap
 // The global map in device memory (ws_store, warpsense_hip.h): 64^3 chunks in HBM, the key -> slot directory on the host.  A
 // MappingNode that has one attached shifts with device-to-device copies (shift_map_device) and writes back through it.
@@ -354,6 +363,26 @@ public:
     WS_CHECK(ws_store_fuse(store_, other.store_, &pose, resolution, max_weight, count_only ? WS_FUSE_COUNT_ONLY : WS_FUSE_DEFAULT, s));
     FuseStats out;
     out.candidates = s[0], out.created = s[1], out.averaged = s[2], out.set = s[3], out.sum_abs_diff = s[4], out.sum_min_weight = s[5];
+    return out;
+  }
+  // Where this map ("now") differs from `ref` ("before") under the pull transform (ws_store_changes): band and free_value are raw
+  // values, kinds WS_CHANGES_APPEARED | WS_CHANGES_VANISHED; resolution: the maps', in mm per voxel -- the contract of the Python
+  // DeviceGlobalMap.changes.  Both maps are only read
+  Changes changes(DeviceGlobalMap &ref, const FusePose &pose, int resolution, int band, int free_value, int min_weight = 1, uint32_t kinds = WS_CHANGES_DEFAULT,
+                  bool clusters = false, const rm::Pointi *lo = nullptr, const rm::Pointi *hi = nullptr)
+  {
+    Changes out;
+    size_t n = 0, k = 0;
+    uint64_t s[6] = {0, 0, 0, 0, 0, 0};
+    const uint32_t flags = (kinds & WS_CHANGES_DEFAULT) | (clusters ? WS_CHANGES_CLUSTERS : 0u);
+    WS_CHECK(ws_store_changes(store_, ref.store_, &pose, resolution, lo ? &lo->x : nullptr, hi ? &hi->x : nullptr, band, free_value, min_weight, flags, &n, &k, s));
+    out.records.resize(n);
+    if (clusters) out.labels.resize(n), out.clusters.resize(k);
+    size_t got = 0, got_k = 0;
+    WS_CHECK(ws_store_changes_download(store_, n ? out.records.data() : nullptr, n && clusters ? out.labels.data() : nullptr,
+                                       k && clusters ? out.clusters.data() : nullptr, n, clusters ? k : 0, &got, &got_k));
+    if (got != n || (clusters && got_k != k)) throw std::runtime_error("DeviceGlobalMap::changes: another call replaced the result before it was downloaded");
+    out.stats.chunks = s[0], out.stats.known_both = s[1], out.stats.appeared = s[2], out.stats.vanished = s[3], out.stats.new_ground = s[4], out.stats.sum_abs_diff = s[5];
     return out;
   }
   // this map at half the resolution into `dst` (ws_store_coarsen): the chunks `keys` of dst rebuilt whole, nullptr: the parents of
@@ -862,6 +891,19 @@ public:
     if (!count_only) WS_CHECK(ws_store_load_box(device_global_map_->handle(), gpu_.tsdf().handle(), WS_MAP_AVG, &wlo.x, &whi.x));
     if (!count_only) pyramid_all_ = true; // (the fuse wrote chunks anywhere: global_pyramid rebuilds)
     return st;
+  }
+  // Where everything the run has seen differs from an earlier map: the window into the device chunks, as global_mesh does, then
+  // DeviceGlobalMap::changes at the map's resolution (band < 0: the resolution; free_value < 0: tau)
+  Changes map_changes(DeviceGlobalMap &ref, const FusePose &pose, int band = -1, int free_value = -1, int min_weight = 1, uint32_t kinds = WS_CHANGES_DEFAULT,
+                      bool clusters = false, const rm::Pointi *lo = nullptr, const rm::Pointi *hi = nullptr)
+  {
+    if (!device_global_map_) throw std::logic_error("map_changes: no DeviceGlobalMap attached");
+    wait_shift();
+    rm::Pointi wlo, whi;
+    local_map_.window(wlo, whi);
+    WS_CHECK(ws_store_save_box(device_global_map_->handle(), gpu_.tsdf().handle(), WS_MAP_AVG, &wlo.x, &whi.x));
+    return device_global_map_->changes(ref, pose, params_.map_resolution, band < 0 ? params_.map_resolution : band, free_value < 0 ? params_.tau : free_value,
+                                       min_weight, kinds, clusters, lo, hi);
   }
   // Coarser levels of everything the run has seen: the window into the device chunks, as global_mesh does, then a MapPyramid over the
   // store, rebuilt (the first call, other levels or min_observed, after merge_map) or refreshed over the windows the node has held

@@ -298,6 +298,24 @@ inline FusePose fuse_pose(const double T[16], const double *pivot_src_mm = nullp
   return p;
 }
 
+// ---- where one device global map differs from another (ws_store_changes, warpsense_hip.h)
+// stats[6] of ws_store_changes; they cover both kinds whatever the call selected
+struct ChangeStats
+{
+  uint64_t chunks = 0, known_both = 0, appeared = 0, vanished = 0, new_ground = 0, sum_abs_diff = 0;
+  // the volume of the appeared and vanished voxels, in cubic metres
+  double changed_volume_m3(int resolution) const { const double r = (double)resolution / 1000.0; return (double)(appeared + vanished) * r * r * r; }
+  // the mean |nv - ev| over the voxels known on both sides; nan without any
+  double disagreement_mm() const { return known_both ? (double)sum_abs_diff / (double)known_both : std::nan(""); }
+};
+struct ChangeRecord // one record of ws_store_changes
+{
+  int32_t x, y, z;   // world voxels of the current map
+  int16_t ref_value; // what the reference map holds at the place
+  uint16_t kind;     // 1 appeared, 2 vanished
+};
+static_assert(sizeof(ChangeRecord) == 16, "ws_store_changes writes 16-byte records");
+
 // ---- a device global map at half the resolution of another (ws_store_coarsen, warpsense_hip.h)
 // stats[4] of ws_store_coarsen
 struct CoarsenStats

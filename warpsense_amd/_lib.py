@@ -57,6 +57,8 @@ EXPORTS = [
     "ws_store_view_gain", "ws_store_view_gain_records_dev", "ws_store_view_gain_rays_dev", "ws_store_view_gain_download", "ws_debug_store_view_gain_timing",
     "ws_store_fuse", "ws_debug_store_fuse_timing",
     "ws_store_coarsen", "ws_store_parents_of", "ws_debug_store_coarsen_timing",
+    "ws_store_changes", "ws_store_changes_records_dev", "ws_store_changes_labels_dev", "ws_store_changes_clusters_dev", "ws_store_changes_download",
+    "ws_debug_store_changes_timing",
 ]
 WS_SURFACE_RECORDS, WS_SURFACE_MARKER = 0, 1
 WS_MESH_DEFAULT, WS_MESH_ANY_WEIGHT = 0, 1
@@ -70,6 +72,7 @@ WS_REACH_DEFAULT, WS_REACH_UNKNOWN_FREE, WS_REACH_UNREACHABLE = 0, 1, 0xFFFFFFFF
 WS_GAIN_DEFAULT, WS_GAIN_ANY_WEIGHT, WS_GAIN_RAYS = 0, 1, 2
 WS_FUSE_DEFAULT, WS_FUSE_COUNT_ONLY = 0, 1
 WS_COARSEN_DEFAULT = 0
+WS_CHANGES_APPEARED, WS_CHANGES_VANISHED, WS_CHANGES_CLUSTERS, WS_CHANGES_DEFAULT = 1, 2, 4, 3
 
 
 class WsError(RuntimeError):
@@ -246,6 +249,11 @@ def load() -> C.CDLL:
     L.ws_store_coarsen.argtypes = [vp, vp, vp, sz, i32, u32, vp]
     L.ws_store_parents_of.argtypes = [vp, sz, vp, sz, P(sz)]
     L.ws_debug_store_coarsen_timing.argtypes = [vp, i32, vp]
+    L.ws_store_changes.argtypes = [vp, vp, vp, i32, vp, vp, i32, i32, i32, u32, P(sz), P(sz), vp]
+    for f in (L.ws_store_changes_records_dev, L.ws_store_changes_labels_dev, L.ws_store_changes_clusters_dev):
+        f.argtypes, f.restype = [vp, P(sz)], vp
+    L.ws_store_changes_download.argtypes = [vp, vp, vp, vp, sz, sz, P(sz), P(sz)]
+    L.ws_debug_store_changes_timing.argtypes = [vp, i32, vp]
     L.ws_debug_reach_active.argtypes = [vp, vp, sz, P(sz)]
     L.ws_shift_plan.argtypes = [vp, vp, vp, vp, P(ShiftPlan)]
     L.ws_shift_begin.argtypes = [vp, vp, u32, P(vp)]

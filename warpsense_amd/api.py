@@ -27,6 +27,7 @@ This module only gathers the names; the code lives in one module per subsystem, 
     fuse.py          fuse_pose, FuseStats: one global map fused into another        (api_store)
     merge.py         merge_map and align_map of TSDFMapping
     pyramid.py       CoarsenStats, parents_of, MapPyramid, global_pyramid           (api_store)
+    changes.py       ChangeStats, ChangeResult, write_changes_ply: where two maps differ (api_store)
     device_map.py    DeviceMap, LocalMap, DeviceMapMemWrapper, TSDFCuda             (api_map, api_tsdf)
     registration.py  RegistrationCuda, batch_best, candidate_poses                  (api_reg)
     mapping.py       the parameters, TSDFMapping, TSDFRegistration
@@ -48,3 +49,4 @@ from .scan import DevicePoints, ScanPreprocessor, preprocess_sweep_host, sweep_b
 from .store import DeviceGlobalMap, chunks_of_box  # noqa: F401
 from .fuse import FuseStats, fuse_pose, pose_transform  # noqa: F401
 from .pyramid import CoarsenStats, MapPyramid, parents_of  # noqa: F401
+from .changes import CHANGE_RECORD, ChangeResult, ChangeStats, write_changes_ply  # noqa: F401

@@ -1,8 +1,8 @@
 // api_store.hip — the chunk store, the global map in device memory (ws_store_*, ws_shift_device; kernels in map_store.hip): directory,
 // segments and slot tables, the box transfers between a map's window and the chunks, and the store's surface cloud, mesh, ray cast and
 // distance field, which run the host cores of ws_api.h over the chunks a call lists (store_surface.hip, store_mesh.hip,
-// store_raycast.hip, store_distance.hip), and the two calls that write one store from another: ws_store_fuse (store_fuse.hip) and
-// ws_store_coarsen (store_coarsen.hip).
+// store_raycast.hip, store_distance.hip), the two calls that write one store from another: ws_store_fuse (store_fuse.hip) and
+// ws_store_coarsen (store_coarsen.hip), and the call that compares one store with another: ws_store_changes (store_changes.hip).
 #include <algorithm>
 #include <array>
 #include <cmath>
@@ -12,6 +12,7 @@
 #include <set>
 
 #include "ws_api.h"
+#include "ws_changes.h"
 #include "ws_coarsen.h"
 #include "ws_fuse.h"
 
@@ -493,6 +494,22 @@ int store_lookup_fill(HostBlock &host, DevBuf &dev, const std::vector<StoreRaySl
     WS_TRY(dev.alloc(places, sizeof(StoreRaySlot)));
   }
   if (!listed.empty()) store_ray_table_fill(listed.data(), listed.size(), host.as<StoreRaySlot>());
+  return WS_OK;
+}
+
+// The lookup of EVERY written chunk of `src` (store_ray_table_fill), filled into the next slot table of its ring: what a call that
+// samples one store on the lattice of another reads it through (ws_store_fuse, ws_store_changes).  `places`: the table's places;
+// the caller enqueues the upload of places * sizeof(StoreRaySlot) bytes and records the table's event behind the last launch that
+// reads it.  2^19 chunks or more: WS_ERR_RANGE in the name of the entry point, with `too_many`.  An empty store gives a table
+// without a chunk: every lookup is absent.
+int store_lookup_plan(ws_store *src, const char *name, const char *too_many, ws_store::Table **ts, size_t *places)
+{
+  std::vector<StoreRaySlot> listed;
+  store_list(src, nullptr, nullptr, listed);
+  if (listed.size() >= (1u << 19)) return range_error(name, too_many);
+  *places = store_ray_table_slots(listed.size());
+  WS_TRY(store_table(src, *places * 4, ts));
+  store_ray_table_fill(listed.data(), listed.size(), (*ts)->host.as<StoreRaySlot>());
   return WS_OK;
 }
 
@@ -1104,16 +1121,13 @@ int fuse_run(ws_store *dst, ws_store *src, const ws_fuse_pose &pull, int32_t res
   if (cand.size() >= FUSE_MAX_CANDIDATES) return range_error("ws_store_fuse", ": 2^23 candidate chunks of DST or more");
   stats[0] = cand.size();
   if (cand.empty()) return WS_OK;
-  std::vector<StoreRaySlot> listed;
-  store_list(src, nullptr, nullptr, listed);
-  if (listed.size() >= (1u << 19)) return range_error("ws_store_fuse", ": SRC holds 2^19 chunks or more");
 
   // the plan: the lookup of SRC's chunks in a table of SRC's ring, the candidates in one of DST's
-  const size_t places = store_ray_table_slots(listed.size()), n = cand.size();
+  size_t places = 0;
+  const size_t n = cand.size();
   ws_store::Table *ts = nullptr, *td = nullptr;
-  WS_TRY(store_table(src, places * 4, &ts));
+  WS_TRY(store_lookup_plan(src, "ws_store_fuse", ": SRC holds 2^19 chunks or more", &ts, &places));
   WS_TRY(store_table(dst, n * 4, &td));
-  store_ray_table_fill(listed.data(), listed.size(), ts->host.as<StoreRaySlot>());
   FuseCand *ch = td->host.as<FuseCand>();
   size_t i = 0;
   for (const StoreKey &k : cand)
@@ -1386,4 +1400,98 @@ int ws_debug_store_coarsen_timing(ws_store *dst, int32_t enable, float ms_out[2]
   if (!dst) return invalid("ws_debug_store_coarsen_timing: store is NULL");
   std::lock_guard<std::mutex> lock(dst->mu);
   return query_timing(dst->ctx->stream, dst->coarsen.timer, enable, ms_out, COARSEN_PAIRS, 2);
+}
+
+// ---- where two stores differ under a rigid pose: the host flow of ws_store_changes (the rules are stated in warpsense_hip.h and live
+// in ws_changes.h; the kernels in store_changes.hip).  The extraction is the flow of the store's frontier, the lookup of REF the plan
+// of the fuse.
+int ws_store_changes(ws_store *cur, ws_store *ref, const ws_fuse_pose *pull, int32_t map_resolution, const int32_t lo[3], const int32_t hi[3], int32_t band,
+                     int32_t free_value, int32_t min_weight, uint32_t flags, size_t *n_out, size_t *n_clusters, uint64_t stats[6])
+{
+  const uint32_t kinds = WS_CHANGES_APPEARED | WS_CHANGES_VANISHED;
+  if (!cur || !ref || !pull || !stats) return invalid("ws_store_changes: NULL argument");
+  if (flags & ~(kinds | WS_CHANGES_CLUSTERS)) return invalid("ws_store_changes: unknown flag bits");
+  if (!(flags & kinds)) return invalid("ws_store_changes: neither WS_CHANGES_APPEARED nor WS_CHANGES_VANISHED");
+  if (cur == ref) return invalid("ws_store_changes: cur and ref are the same store");
+  if (cur->ctx != ref->ctx) return invalid("ws_store_changes: the stores belong to different contexts");
+  if ((lo == nullptr) != (hi == nullptr)) return invalid("ws_store_changes: exactly one of lo and hi is NULL");
+  for (int k = 0; k < 9; ++k)
+    if (pull->rot_q30[k] < -(1 << 30) || pull->rot_q30[k] > (1 << 30)) return invalid("ws_store_changes: a rot_q30 entry beyond +-2^30");
+  if (map_resolution < 1 || map_resolution > 1024) return range_error("ws_store_changes", ": the resolution must be 1 .. 1024 mm");
+  if (band < 1) return range_error("ws_store_changes", ": band must be >= 1");
+  if (free_value < band || free_value > 32767) return range_error("ws_store_changes", ": free_value must be band .. 32767");
+  if (min_weight < 1 || min_weight > 32767) return range_error("ws_store_changes", ": min_weight must be 1 .. 32767");
+  servers_leave(cur->ctx);
+  // both locks, in address order (store_query_box takes CUR's behind its own refusal)
+  std::unique_lock<std::mutex> lock_cur, lock_ref;
+  if (std::less<ws_store *>()(ref, cur)) lock_ref = std::unique_lock<std::mutex>(ref->mu);
+  StoreChangesCall c;
+  WS_TRY(store_query_box(cur, "ws_store_changes", lo, hi, false, lock_cur, c.lo, c.hi));
+  if (!lock_ref.owns_lock()) lock_ref = std::unique_lock<std::mutex>(ref->mu);
+  ws_store::Changes &q = cur->changes;
+  hipStream_t s = cur->ctx->stream;
+  const bool clusters = (flags & WS_CHANGES_CLUSTERS) != 0;
+  std::vector<StoreRaySlot> listed;
+  if (c.lo[0] <= c.hi[0]) store_list(cur, c.lo, c.hi, listed); // (else: no box and no chunk)
+  if (listed.size() >= (1u << 19)) return range_error("ws_store_changes", ": the box overlaps 2^19 present chunks of CUR or more (4096 words each must stay below 2^31)");
+  if (listed.empty()) // an empty store, or the box meets no present chunk: nothing is examined, and no plan is made (REF's limit holds all the same)
+  {
+    size_t n_ref = 0;
+    for (const auto &kv : ref->dir) n_ref += kv.second.written ? 1 : 0;
+    if (n_ref >= (1u << 19)) return range_error("ws_store_changes", ": REF holds 2^19 chunks or more");
+    WS_TRY(q.timer.arm());
+    for (int k = 0; k < 6; ++k) stats[k] = 0;
+    return frontier_publish(q, 0, 0, clusters, n_out, n_clusters);
+  }
+  ws_store::Table *ts = nullptr;
+  WS_TRY(store_lookup_plan(ref, "ws_store_changes", ": REF holds 2^19 chunks or more", &ts, &c.ref_places));
+  WS_TRY(q.timer.arm());
+  c.n_chunks = (uint32_t)listed.size();
+  c.pull = *pull;
+  c.res = map_resolution, c.band = band, c.free_value = free_value, c.min_weight = min_weight;
+  c.kinds = flags & kinds;
+  c.ref_table_dev = ts->dev.p;
+  const size_t n = listed.size(), n_words = n * 4096u;
+  WS_TRY(q.stats.alloc(CH_STATS_DEV));
+  WS_TRY(store_tables_reserve(cur, q.table_host, q.table_dev, store_word_table_bytes(n), store_word_table_bytes(n + n / 8)));
+  store_word_tables(listed, q.table_host.as<uint32_t>());
+  const int rc = frontier_run(
+      q, s, "ws_store_changes", store_surface_blocks(c.n_chunks), clusters ? WS_FRONTIER_CLUSTERS : WS_FRONTIER_DEFAULT, n_out, n_clusters, n_words > q.mask.cap,
+      [&] { return q.mask.grow(n_words, sizeof(uint64_t)); },
+      [&] {
+        q.timer.mark(0, s);
+        const hipError_t e = hipMemcpyAsync(ts->dev.p, ts->host.p, c.ref_places * sizeof(StoreRaySlot), hipMemcpyHostToDevice, s);
+        if (e != hipSuccess) return store_enqueued(cur, hip_fail(e, "hipMemcpyAsync (lookup of REF)", __FILE__, __LINE__));
+        return store_enqueued(cur, launch_store_changes_count(cur, ref, q, c));
+      },
+      [&](size_t cap) { return store_enqueued(cur, launch_store_changes_emit(cur, ref, q, c, cap)); });
+  // (every pass that reads REF's table has been waited for by now, or never ran)
+  (void)hipEventRecord(ts->done, s);
+  ts->used = true;
+  if (rc != WS_OK) return rc;
+  stats[0] = c.n_chunks;
+  for (uint32_t k = 0; k < CH_STATS_DEV; ++k) stats[1 + k] = q.stats.host[k];
+  return WS_OK;
+}
+
+const void *ws_store_changes_records_dev(const ws_store *cur, size_t *n) { return surface_records_dev(cur ? &cur->changes : nullptr, n); }
+
+const uint32_t *ws_store_changes_labels_dev(const ws_store *cur, size_t *n) { return frontier_labels_dev(cur ? &cur->changes : nullptr, n); }
+
+const void *ws_store_changes_clusters_dev(const ws_store *cur, size_t *n) { return frontier_clusters_dev(cur ? &cur->changes : nullptr, n); }
+
+int ws_store_changes_download(ws_store *cur, void *records_host, uint32_t *labels_host, void *clusters_host, size_t cap_records, size_t cap_clusters, size_t *n_out,
+                              size_t *n_clusters)
+{
+  if (!cur || !n_out) return invalid("ws_store_changes_download: NULL argument");
+  std::lock_guard<std::mutex> lock(cur->mu);
+  return frontier_download(cur->changes, cur->ctx->stream, "ws_store_changes_download", "ws_store_changes", records_host, labels_host, clusters_host, cap_records,
+                           cap_clusters, n_out, n_clusters);
+}
+
+int ws_debug_store_changes_timing(ws_store *cur, int32_t enable, float ms_out[4])
+{
+  if (!cur) return invalid("ws_debug_store_changes_timing: store is NULL");
+  std::lock_guard<std::mutex> lock(cur->mu);
+  return query_timing(cur->ctx->stream, cur->changes.timer, enable, ms_out, FRONTIER_PAIRS, 4);
 }

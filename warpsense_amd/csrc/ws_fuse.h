@@ -85,7 +85,8 @@ __device__ __forceinline__ bool fuse_dead(int64_t q) { return q <= -(1ll << 30) 
 
 // The sample of SRC in the cell with base voxel b and fractions f (0 <= f < res): a corner whose trilinear coefficient is zero takes
 // part neither in validity nor in the weight.  false: not valid.  nv = floor(T / res^3), nw = the smallest weight that takes part.
-__device__ __forceinline__ bool fuse_sample(const FuseArgs &a, StoreField &fld, const int32_t b[3], const int32_t f[3], int32_t &nv, int32_t &nw)
+// Args: res, res3 and tdiv are read (FuseArgs; the ChangesArgs of ws_changes.h)
+template <typename Args> __device__ __forceinline__ bool fuse_sample(const Args &a, StoreField &fld, const int32_t b[3], const int32_t f[3], int32_t &nv, int32_t &nw)
 {
   const int32_t wx[2] = {a.res - f[0], f[0]}, wy[2] = {a.res - f[1], f[1]}, wz[2] = {a.res - f[2], f[2]};
   int64_t T = 0;

@@ -768,6 +768,14 @@ struct ws_store
     ws::DevBuf table_dev;                // ... and the copy the kernels read
     void release() { FrontierResult::release(), mask.release(), table_host.release(), table_dev.release(); }
   } frontier;
+  struct Changes : ws::FrontierResult // ws_store_changes with this store as CUR (store_changes.hip); timer: 0 uploads and count 1 scan 2, 3 emit 4 clustering 5
+  {
+    ws::DevBuf mask;                     // uint64 [4096 per listed chunk] the records of a word, bit = z
+    ws::HostBlock table_host;            // bytes, pinned: the call's word-space tables (store_word_table_bytes); free again when the call returns, which synchronises
+    ws::DevBuf table_dev;                // ... and the copy the kernels read
+    ws::DevCounter stats;                // the sums of the count pass (CH_STATS_DEV, ws_changes.h)
+    void release() { FrontierResult::release(), mask.release(), table_host.release(), table_dev.release(), stats.release(); }
+  } changes;
   ws::ReachResult reach; // ws_store_reach (map_reach.hip: it reads the records of `dist` alone)
   struct Gain : ws::GainResult // ws_store_view_gain (store_gain.hip)
   {
@@ -796,6 +804,7 @@ struct ws_store
     gain.release();
     reach.release();
     frontier.release();
+    changes.release();
     surf.release();
     mesh.release();
     ray.release();
@@ -932,6 +941,21 @@ struct StoreFrontierCall
 inline size_t store_frontier_table_bytes(size_t n_chunks) { return store_word_table_bytes(n_chunks) + n_chunks * 6 * sizeof(uint32_t); }
 int launch_store_frontier_count(ws_store *st, ws_store::Frontier &q, const StoreFrontierCall &c);
 int launch_store_frontier_emit(ws_store *st, ws_store::Frontier &q, const StoreFrontierCall &c, size_t cap);
+// store_changes.hip: the passes of ws_store_changes over the chunks of CUR the call lists, in the flow of the store's frontier.  The
+// host has written the two word-space tables of the `n_chunks` listed chunks into q.table_host and enqueued the upload of REF's
+// chunk lookup (`ref_places` places at ref_table_dev); the sums arrive in q.stats.host after a stream synchronise
+struct StoreChangesCall
+{
+  uint32_t n_chunks;    // 0 < n_chunks < 2^19: 4096 words each
+  ws_fuse_pose pull;
+  int32_t res, band, free_value, min_weight;
+  uint32_t kinds;       // WS_CHANGES_APPEARED | WS_CHANGES_VANISHED: the kinds that become records
+  int32_t lo[3], hi[3]; // the box, inclusive world voxels of CUR
+  const void *ref_table_dev;
+  size_t ref_places;
+};
+int launch_store_changes_count(ws_store *cur, const ws_store *ref, ws_store::Changes &q, const StoreChangesCall &c);
+int launch_store_changes_emit(ws_store *cur, const ws_store *ref, ws_store::Changes &q, const StoreChangesCall &c, size_t cap);
 
 // map_reach.hip: the geodesic field over the records of a distance result, of a window or of the store alike.  reach_tiles: the tiles
 // of a box.  launch_reach_seed clears costs, marks and words, takes the n_seeds seeds in q.seeds (it marks events 0, 1) and queues

@@ -1,5 +1,5 @@
-"""merge_map and align_map of TSDFMapping (mapping.py): another global map fused into the one of this run (fuse.py, ws_store_fuse),
-and its pose found by the existing registration."""
+"""merge_map, map_changes and align_map of TSDFMapping (mapping.py): another global map fused into the one of this run (fuse.py,
+ws_store_fuse) or compared with it (changes.py, ws_store_changes), and its pose found by the existing registration."""
 from __future__ import annotations
 
 import numpy as np
@@ -39,6 +39,29 @@ class FuseQueries:
                 if tmp is not None:
                     tmp.close()
         return stats
+
+    def map_changes(self, ref_store, T_ref_to_cur=None, band=None, free_value=None, min_weight=1, lo=None, hi=None, kinds="both", clusters=False,
+                    pivot_ref_mm=None):
+        """Where everything this run has seen differs from an earlier map (DeviceGlobalMap.changes, ws_store_changes): the window goes
+        into the chunks of device_global_map exactly as in global_mesh, and the store is compared with ref_store, a DeviceGlobalMap
+        or a host GlobalMap (loaded into a temporary one), under T_ref_to_cur (4 x 4, mm, from the frame of the earlier map into
+        this one's; None: the identity).  band: None for the resolution; free_value: None for tau.  Returns a ChangeResult."""
+        m = self.params_.map
+        res = int(m.resolution)
+        with self._window_in_store("map_changes") as store:
+            tmp = None
+            if isinstance(ref_store, GlobalMap):
+                value, weight = unpack_entry(ref_store.default_raw)
+                tmp = DeviceGlobalMap(int(value), int(weight), ctx=store.ctx)
+            try:
+                if tmp is not None:
+                    tmp.load_from(ref_store)
+                return store.changes(tmp if tmp is not None else ref_store, T_ref_to_cur, pivot_ref_mm, resolution=res, band=res if band is None else int(band),
+                                     free_value=int(self.tsdf_.tau_) if free_value is None else int(free_value), min_weight=min_weight, lo=lo, hi=hi,
+                                     kinds=kinds, clusters=clusters)
+            finally:
+                if tmp is not None:
+                    tmp.close()
 
     def align_map(self, other, T_guess, max_points=65536, band=None):
         """The pose of another map against the window of this one: the surface cloud of `other` (DeviceGlobalMap.surface, records on

@@ -9,6 +9,7 @@ from . import _lib
 from ._abi import _i3, _i3c, _ptr, pack_entry
 from ._lib import WS_MAP_AVG, check
 from .context import Context
+from .changes import ChangeResult, _changes_call
 from .fuse import FuseStats, _fuse_call, fuse_pose
 from .global_map import GlobalMap
 from .pyramid import CoarsenStats, _coarsen_call
@@ -236,6 +237,26 @@ class DeviceGlobalMap:
     def fuse_timing(self, enable: int = -1):
         """ws_debug_store_fuse_timing: read the last call's three spans; enable 1 / 0 switches the events on / off"""
         return _timing(self._L, "ws_debug_store_fuse_timing", self.handle, 3, enable)
+
+    def changes(self, ref: "DeviceGlobalMap", pose=None, pivot_ref_mm=None, *, resolution, band, free_value, min_weight=1, lo=None, hi=None, kinds="both",
+                clusters=False) -> ChangeResult:
+        """Where this map ("now") differs from `ref` ("before"), on the device (ws_store_changes; the rule is stated in
+        include/warpsense_hip.h): on this map's voxel lattice, inside the inclusive world-voxel box [lo, hi] (both None: the bounding
+        box of the present chunks), a voxel whose entry has weight >= min_weight is compared with the fuse's sample of `ref` at its
+        place.  abs(value) < band is occupied, value >= free_value is free (raw values; band <= free_value); occupied here and free
+        there has APPEARED (kind 1), free here and occupied there has VANISHED (kind 2); unknown on either side is never a change.
+        pose: None for the identity, the 4 x 4 float64 transform in mm from the frame of `ref` into this map's (fuse_pose makes the
+        integer pull transform from it, around pivot_ref_mm), or the 15 int32 of a ws_fuse_pose.  resolution: the maps', in mm per
+        voxel.  kinds: "both", "appeared" or "vanished" become records; clusters: 26-connected clusters of the records as in
+        frontier().  Both maps are only read.  Returns a ChangeResult."""
+        pose = np.eye(4) if pose is None else np.asarray(pose)
+        pose = pose if pose.size == 15 else fuse_pose(pose, pivot_ref_mm)
+        return _changes_call(self._L, self, ref, pose, resolution, lo, hi, band, free_value, min_weight, kinds, clusters)
+
+    def changes_timing(self, enable: int = -1):
+        """device milliseconds of the uploads with the count pass, the scan, the emit pass and the clustering of the last changes()
+        (ws_debug_store_changes_timing)"""
+        return _timing(self._L, "ws_debug_store_changes_timing", self.handle, 4, enable)
 
     def coarsen(self, dst: "DeviceGlobalMap", keys=None, min_observed=8, stats=True) -> CoarsenStats | None:
         """This map at half the resolution into `dst`, on the device (ws_store_coarsen; the rule is stated in
