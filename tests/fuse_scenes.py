@@ -67,9 +67,9 @@ def sphere_and_floor(shift=(0.0, 0.0, 0.0), weight=20, res=RES):
     return split(F.pack(value, np.where(np.abs(d) < TAU, weight, 0)).reshape(128, 128, 128), (-1, -1, -1))
 
 
-def make_store(chunks, max_chunks=0, fill=(TAU, 0)):
+def make_store(chunks, max_chunks=0, fill=(TAU, 0), segment_chunks=2):
     import warpsense_amd as W
-    store = W.DeviceGlobalMap(fill[0], fill[1], max_chunks=max_chunks, segment_chunks=2)
+    store = W.DeviceGlobalMap(fill[0], fill[1], max_chunks=max_chunks, segment_chunks=segment_chunks)
     for key in sorted(chunks):
         store.put_chunk(key, chunks[key])
     return store

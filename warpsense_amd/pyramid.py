@@ -68,7 +68,8 @@ class MapPyramid:
 
     def rebuild(self, stats=True):
         """every level from the one below, over the parents of all its chunks; returns the CoarsenStats per level (None each
-        with stats=False, which waits for nothing)"""
+        with stats=False, which waits for nothing).  A chunk dropped from the base leaves its ancestors as they were: that wants
+        refresh() of the dropped chunk's box."""
         return [self._stores[l - 1].coarsen(self._stores[l], None, self.min_observed, stats) for l in range(1, self.levels + 1)]
 
     def refresh(self, lo, hi, stats=True):
@@ -115,7 +116,8 @@ class PyramidQueries:
         """Coarser levels of everything the run has seen: the window goes into the chunks of device_global_map exactly as in
         global_mesh, then a MapPyramid over it is rebuilt (the first call, other levels or min_observed, or after merge_map) or
         refreshed over the windows the mapping has held since the last call.  Returns the pyramid, which the mapping keeps; chunks
-        written into the store behind the mapping's back want MapPyramid.rebuild()."""
+        written into the store behind the mapping's back want MapPyramid.rebuild(); a chunk dropped from the store wants
+        MapPyramid.refresh() of its box, which a rebuild does not cover."""
         with self._window_in_store("global_pyramid") as store:
             lo, hi = self.local_map_.window()
             p = getattr(self, "_pyramid", None)
