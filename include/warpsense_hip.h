@@ -1020,6 +1020,68 @@ int ws_store_changes_download(ws_store *cur, void *records_host, uint32_t *label
  * the scan, of the emit pass and of the clustering of the last call with this store as CUR */
 int ws_debug_store_changes_timing(ws_store *cur, int32_t enable, float ms_out[4]);
 
+/* ------------------------------------------------------------------ packed snapshots of the global map ---- */
+/* The chunks of a store in a packed form that removes the redundancy of a TSDF chunk (space never seen holds the default entry, free
+ * space one repeated word), made and expanded on the device, the same bytes on every run.  The chunk set stays the host
+ * directory's: the device classifies the bricks inside the chunks the host names and writes them in a fixed order.
+ *   bricks: a chunk is 64^3 words, index x*4096 + y*64 + z; it is 8 x 8 x 8 bricks of 8^3 words.  The word at (x, y, z) is word
+ *     (x&7)*64 + (y&7)*8 + (z&7) of brick b = ((x>>3)*8 + (y>>3))*8 + (z>>3).
+ *   class of a brick, on raw uint32 words against a `fill` word: 0 default: every word == fill, no payload; 1 uniform: every word
+ *     equals the brick's word 0 and that word != fill, 1 payload word; 2 dense: anything else, 512 payload words.  Code 3 is invalid.
+ *   header: WS_PACK_HEADER_WORDS = 40 uint32 per chunk: [0..2] the key (int32); [3] the number of class-1 bricks; [4] the number of
+ *     class-2 bricks; [5], [6] low and high word of the index of the chunk's first payload word (64-bit, counted in words); [7] 0;
+ *     [8..39] the class codes, 2 bits per brick: brick b sits in word 8 + b/16, bits 2*(b%16).
+ *   payload: one uint32 stream.  Chunks come in header order, and headers in strictly ascending key order (cx, then cy, then cz).
+ *     Inside a chunk the bricks ascend; class 1 gives its word, class 2 its 512 words in brick word order.  A chunk contributes
+ *     [3] + 512*[4] words, and its first word index is the sum of the contributions of the chunks before it.
+ *
+ * ws_store_pack packs the chunks `keys` names (n_keys x 3; NULL: every chunk of the store), in ascending key order whatever the order
+ *   given, against the store's own fill_entry.  A named key the store does not hold, a key named twice, NULL keys with n_keys > 0,
+ *   unknown flag bits: WS_ERR_INVALID, nothing launched, the last result stays.  The result (headers, payload) stays in buffers the
+ *   store owns, apart from every other query's result, valid until the next ws_store_pack on this store.  The store is only read.
+ *   stats[4] (may be NULL): default, uniform and dense bricks, and the bytes of headers + payload.  The call synchronises (the payload
+ *   is sized from the scanned total); an allocation that fails is WS_ERR_HIP and leaves an empty result.  Counts and offsets are 64-bit.
+ *   flags: WS_PACK_DEFAULT; WS_PACK_EMIT_DIRECT (measurement): the emit pass writes the payload straight from the lanes that read
+ *   the chunk, in 32-byte runs, not through LDS; the bytes are the same.
+ * ws_store_unpack / ws_store_unpack_dev: every listed chunk is created or overwritten WHOLE: class 0 bricks get `fill` (the
+ *   argument, so a clone is byte-exact even into a store with another default), class 1 bricks their word, class 2 bricks their 512
+ *   words.  Chunks not listed keep their bytes.  The headers are always the host's (the directory is the host's) and are validated
+ *   first (ws_pack_check): every failure of the stream is WS_ERR_INVALID; more chunks than max_chunks allows: WS_ERR_CAPACITY; no
+ *   memory for a segment or the staging: WS_ERR_HIP.  All refusals come before the first launch and leave the store unchanged.  Slots
+ *   are handed out on the host before the launch.  ws_store_unpack_dev (payload in device memory: payload_words uint32 the caller
+ *   keeps unchanged until the launch has run) is stream-ordered and does not wait for the device unless a segment is allocated;
+ *   ws_store_unpack (payload in host memory) returns when the caller's buffers may be reused.  flags: 0.
+ * ws_pack_check, ws_pack_expand_chunk, ws_pack_chunk: host only, no GPU and no context -- the CPU statement of the rule, for tools
+ *   that read and write packed files.  ws_pack_check accepts a header list iff the keys ascend strictly, no class code is 3, the
+ *   counts equal the class map, the first-word indices equal the running sum (64 bits), the total equals payload_words and word 7 is
+ *   zero; else WS_ERR_INVALID with the reason in ws_last_error.  ws_pack_expand_chunk expands one chunk from its header and ITS OWN
+ *   payload words (the stream at the header's first-word index) into out[262144].  ws_pack_chunk packs one chunk into a header
+ *   (first-word index 0: whoever assembles a stream writes the running sum) and its own payload words; *words receives their number,
+ *   and WS_ERR_CAPACITY is returned, with nothing written to payload_out, if cap_words is smaller. */
+#define WS_PACK_HEADER_WORDS 40
+#define WS_PACK_DEFAULT 0u
+#define WS_PACK_EMIT_DIRECT 1u
+int ws_store_pack(ws_store *st, const int32_t *keys /* n_keys x 3 or NULL: every chunk */, size_t n_keys, uint32_t flags, size_t *n_chunks, uint64_t *payload_words,
+                  uint64_t stats[4] /* may be NULL */);
+const uint32_t *ws_store_pack_headers_dev(const ws_store *st, size_t *n_chunks);        /* device memory, n_chunks x 40 uint32; NULL when 0 */
+const uint32_t *ws_store_pack_payload_dev(const ws_store *st, uint64_t *payload_words); /* device memory; NULL when 0 */
+/* Copies the last result to the host.  *n_chunks and *payload_words always receive the sizes; a capacity too small for a part that is
+ * asked for: WS_ERR_CAPACITY, nothing copied.  headers_host or payload_host may be NULL: that part is not copied and its capacity
+ * not looked at. */
+int ws_store_pack_download(ws_store *st, uint32_t *headers_host, uint32_t *payload_host, size_t cap_chunks, uint64_t cap_words, size_t *n_chunks,
+                           uint64_t *payload_words);
+int ws_store_unpack(ws_store *st, const uint32_t *headers_host, const uint32_t *payload_host, size_t n_chunks, uint64_t payload_words, uint32_t fill, uint32_t flags);
+int ws_store_unpack_dev(ws_store *st, const uint32_t *headers_host, const uint32_t *payload_dev, size_t n_chunks, uint64_t payload_words, uint32_t fill,
+                        uint32_t flags);
+int ws_pack_check(const uint32_t *headers, size_t n_chunks, uint64_t payload_words);
+int ws_pack_expand_chunk(const uint32_t *header, const uint32_t *payload, uint32_t fill, uint32_t *out /* 262144 */);
+int ws_pack_chunk(const uint32_t *chunk /* 262144 */, const int32_t key[3], uint32_t fill, uint32_t *header_out, uint32_t *payload_out, uint64_t cap_words,
+                  uint64_t *words);
+/* Measurement entry, as ws_debug_store_surface_timing: ms_out receives the device time of the classify pass, of the scan and of the
+ * emit pass of the last ws_store_pack on this store -- or, if a ws_store_unpack came after it, that call's launch in ms_out[0] and
+ * zeros */
+int ws_debug_store_pack_timing(ws_store *st, int32_t enable, float ms_out[3]);
+
 /* ------------------------------------------------------------------ TSDF update ---- */
 /* TSDFCuda::update_tsdf(scan_points, scanner_pos, up) — update_tsdf.cu:143-166.
  * xyz_host: n x 3 int32 (rmagine::Pointi AoS); scanner_pos in voxel units, up scaled by 32768.

@@ -290,6 +290,7 @@ public:
   explicit DeviceGlobalMap(const TSDFEntry &default_entry, uint64_t max_chunks = 0, uint32_t segment_chunks = 0)
   {
     WS_CHECK(ws_store_create(cuda::detail::context(), default_entry.raw(), max_chunks, segment_chunks, &store_));
+    fill_ = default_entry.raw();
   }
   ~DeviceGlobalMap() { ws_store_destroy(store_); }
   DeviceGlobalMap(const DeviceGlobalMap &) = delete;
@@ -398,6 +399,53 @@ public:
     out.chunks = s[0], out.created = s[1], out.valued = s[2], out.short_of = s[3];
     return out;
   }
+  // Chunks of this map in packed form, made on the device (ws_store_pack): the chunks `keys` names (nullptr: every chunk) in
+  // ascending key order; download = false leaves the payload on the device (ws_store_pack_payload_dev, valid until the next pack) --
+  // the contract of the Python DeviceGlobalMap.pack.  This map is only read
+  PackedMap pack(const std::vector<Key> *keys = nullptr, bool download = true)
+  {
+    PackedMap out;
+    out.fill = fill();
+    if (keys && keys->empty()) return out; // (an empty list is not "every chunk")
+    size_t n = 0;
+    uint64_t s[4] = {0, 0, 0, 0};
+    WS_CHECK(ws_store_pack(store_, keys ? (*keys)[0].data() : nullptr, keys ? keys->size() : 0, WS_PACK_DEFAULT, &n, &out.payload_words, s));
+    out.headers.resize(n * WS_PACK_HEADER_WORDS);
+    if (download) out.payload.resize((size_t)out.payload_words);
+    size_t got = 0;
+    uint64_t got_w = 0;
+    WS_CHECK(ws_store_pack_download(store_, n ? out.headers.data() : nullptr, download && out.payload_words ? out.payload.data() : nullptr, n,
+                                    download ? out.payload_words : 0, &got, &got_w));
+    if (got != n || got_w != out.payload_words) throw std::runtime_error("DeviceGlobalMap::pack: another call replaced the result before it was downloaded");
+    out.default_bricks = s[0], out.uniform_bricks = s[1], out.dense_bricks = s[2], out.bytes = s[3];
+    return out;
+  }
+  // the chunks of `p` created or overwritten whole, default bricks with p.fill (ws_store_unpack); the others keep their bytes
+  void unpack(const PackedMap &p)
+  {
+    if (p.payload.size() != p.payload_words) throw std::invalid_argument("DeviceGlobalMap::unpack: the payload is not on the host");
+    WS_CHECK(ws_store_unpack(store_, p.headers.data(), p.payload.data(), p.n_chunks(), p.payload_words, p.fill, 0));
+  }
+  // ... from a payload in device memory (ws_store_unpack_dev): stream-ordered, no wait
+  void unpack_dev(const PackedMap &p, const uint32_t *payload_dev)
+  {
+    WS_CHECK(ws_store_unpack_dev(store_, p.headers.data(), payload_dev, p.n_chunks(), p.payload_words, p.fill, 0));
+  }
+  // a byte-exact copy of this map into `other` (its listed chunks are overwritten): pack, then unpack from the payload where it lies
+  // on the device; only the headers visit the host.  Returns after the copy has run
+  void clone_into(DeviceGlobalMap &other)
+  {
+    const PackedMap p = pack(nullptr, false);
+    other.unpack_dev(p, ws_store_pack_payload_dev(store_, nullptr));
+    WS_CHECK(ws_sync(cuda::detail::context()));
+  }
+  std::unique_ptr<DeviceGlobalMap> clone()
+  {
+    std::unique_ptr<DeviceGlobalMap> other(new DeviceGlobalMap(TSDFEntry(fill()), 0, 0));
+    clone_into(*other);
+    return other;
+  }
+  uint32_t fill() const { return fill_; }
   // every chunk merged into the host global map (and through it into its file)
   void flush_to(GlobalMap &g)
   {
@@ -408,6 +456,7 @@ public:
 
 private:
   ws_store *store_ = nullptr;
+  uint32_t fill_ = 0;
 };
 // the surface cloud of the device global map (visualization.hpp, ws_store_surface)
 inline SurfaceCloud global_map_cloud(DeviceGlobalMap &g, int tau, int resolution, bool marker = true, const rm::Pointi *lo = nullptr, const rm::Pointi *hi = nullptr,
@@ -904,6 +953,17 @@ public:
     WS_CHECK(ws_store_save_box(device_global_map_->handle(), gpu_.tsdf().handle(), WS_MAP_AVG, &wlo.x, &whi.x));
     return device_global_map_->changes(ref, pose, params_.map_resolution, band < 0 ? params_.map_resolution : band, free_value < 0 ? params_.tau : free_value,
                                        min_weight, kinds, clusters, lo, hi);
+  }
+  // Everything the run has seen in packed form: the window into the device chunks, as global_mesh does, then DeviceGlobalMap::pack
+  // (the `.wspk` file of such a stream is written by the Python PackedMap.save)
+  PackedMap global_packed()
+  {
+    if (!device_global_map_) throw std::logic_error("global_packed: no DeviceGlobalMap attached");
+    wait_shift();
+    rm::Pointi wlo, whi;
+    local_map_.window(wlo, whi);
+    WS_CHECK(ws_store_save_box(device_global_map_->handle(), gpu_.tsdf().handle(), WS_MAP_AVG, &wlo.x, &whi.x));
+    return device_global_map_->pack();
   }
   // Coarser levels of everything the run has seen: the window into the device chunks, as global_mesh does, then a MapPyramid over the
   // store, rebuilt (the first call, other levels or min_observed, after merge_map) or refreshed over the windows the node has held

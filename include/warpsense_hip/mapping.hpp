@@ -316,6 +316,37 @@ struct ChangeRecord // one record of ws_store_changes
 };
 static_assert(sizeof(ChangeRecord) == 16, "ws_store_changes writes 16-byte records");
 
+// ---- chunks of a device global map in packed form (ws_store_pack, warpsense_hip.h): what DeviceGlobalMap::pack returns and
+// DeviceGlobalMap::unpack takes
+struct PackedMap
+{
+  std::vector<uint32_t> headers; // WS_PACK_HEADER_WORDS per chunk, ascending keys
+  std::vector<uint32_t> payload; // the stream (empty after pack(..., false): the payload stayed on the device)
+  uint32_t fill = 0;             // the raw word the default bricks stand for
+  uint64_t payload_words = 0;
+  uint64_t default_bricks = 0, uniform_bricks = 0, dense_bricks = 0, bytes = 0; // stats[4] of ws_store_pack
+  size_t n_chunks() const { return headers.size() / WS_PACK_HEADER_WORDS; }
+  std::array<int32_t, 3> key(size_t i) const
+  {
+    const uint32_t *h = headers.data() + i * WS_PACK_HEADER_WORDS;
+    return {(int32_t)h[0], (int32_t)h[1], (int32_t)h[2]};
+  }
+  // packed bytes / (chunks x 1 MiB); 0 for no chunk
+  double ratio() const { return n_chunks() ? (double)bytes / ((double)n_chunks() * 1048576.0) : 0.0; }
+  // ws_pack_check: throws unless the headers are a valid stream of payload_words words
+  void check() const { WS_CHECK(ws_pack_check(headers.data(), n_chunks(), payload_words)); }
+  // chunk i expanded on the host (ws_pack_expand_chunk): 64^3 words
+  std::vector<uint32_t> chunk(size_t i) const
+  {
+    const uint32_t *h = headers.data() + i * WS_PACK_HEADER_WORDS;
+    const uint64_t first = (uint64_t)h[5] | ((uint64_t)h[6] << 32), words = (uint64_t)h[3] + 512ull * h[4];
+    if (first + words > payload.size()) throw std::runtime_error("PackedMap::chunk: the payload is not on the host");
+    std::vector<uint32_t> out(64 * 64 * 64);
+    WS_CHECK(ws_pack_expand_chunk(h, payload.data() + first, fill, out.data()));
+    return out;
+  }
+};
+
 // ---- a device global map at half the resolution of another (ws_store_coarsen, warpsense_hip.h)
 // stats[4] of ws_store_coarsen
 struct CoarsenStats

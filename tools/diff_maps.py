@@ -5,7 +5,7 @@ under a pose -- what has appeared, what has been taken away, how large and where
     python tools/diff_maps.py now.h5 before.h5 --resolution 64 --tau 600 --xyz-mm 13 -7 4 --rpy-deg 0 3 17 --ply changes.ply
     python tools/diff_maps.py now.npz before.npz --pose pose.txt --align --window 257 --min-size 20
 
-The maps, the pose options and --align are those of tools/merge_maps.py; the pose takes points of REF into the frame of CUR.  --band
+The maps (.h5, .npz or .wspk), the pose options and --align are those of tools/merge_maps.py; the pose takes points of REF into the frame of CUR.  --band
 and --free-value are raw values (defaults: the resolution and tau).  Prints the statistics and the clusters of at least --min-size
 voxels (largest first: kinds, size, volume, centroid in metres, bounding box in voxels) as one JSON line; --ply writes the records
 as a point cloud, appeared green and vanished red."""

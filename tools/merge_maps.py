@@ -4,8 +4,8 @@
     python tools/merge_maps.py dst.h5 src.h5 merged.h5 --resolution 64 --tau 600 --max-weight 640 --xyz-mm 13 -7 4 --rpy-deg 0 3 17
     python tools/merge_maps.py dst.npz src.npz merged.npz --pose pose.txt --align --window 257
 
-Maps are .h5 global maps (where libwarpsense_h5.so is built) or .npz chunk dumps with `keys` (n, 3) int32 and `chunks` (n, 262144)
-uint32.  The pose takes points of SRC into the frame of DST: a text file with a 4 x 4 matrix in mm, or --xyz-mm and --rpy-deg (roll,
+Maps are .h5 global maps (where libwarpsense_h5.so is built), .npz chunk dumps with `keys` (n, 3) int32 and `chunks` (n, 262144)
+uint32, or .wspk packed snapshots (warpsense_amd.PackedMap: written by the device's pack, read on the host).  The pose takes points of SRC into the frame of DST: a text file with a 4 x 4 matrix in mm, or --xyz-mm and --rpy-deg (roll,
 pitch, yaw; R = Rz Ry Rx).  --align refines it first (TSDFRegistration.align_map against a window of DST around --centre-vox).
 Prints the statistics as one JSON line."""
 import argparse
@@ -21,6 +21,8 @@ import warpsense_amd as W  # noqa: E402
 
 def load(path, tau):
     """a host GlobalMap of the file"""
+    if path.endswith(".wspk"):
+        return W.PackedMap.load(path).to_global_map(W.GlobalMap(tau, 0))
     if path.endswith(".npz"):
         z = np.load(path)
         g = W.GlobalMap(tau, 0)
@@ -31,6 +33,9 @@ def load(path, tau):
 
 
 def save(store, path, tau, params):
+    if path.endswith(".wspk"):
+        store.save_packed(path, tau=int(tau), **({"resolution": int(params.resolution)} if hasattr(params, "resolution") else {}))
+        return
     if path.endswith(".npz"):
         keys = store.keys()
         np.savez_compressed(path, keys=np.asarray(keys, dtype=np.int32).reshape(-1, 3),

@@ -2,7 +2,7 @@
 sliding TSDF map @ 5 cm, one MI355X): sensor clouds in float metres -> device pre-processing -> TSDF update
 (when the sensor moved > 0.3 m) -> Point-to-TSDF registration -> pose -> map shift (device-side slabs).
 
-    python tools/replay_stream.py --map 1024 --scans 30 [--h5 /tmp/stream.h5] [--async-shift | --device-global-map] [--surface-ply DIR [--surface-every N]] [--mesh-ply DIR]
+    python tools/replay_stream.py --map 1024 --scans 30 [--h5 /tmp/stream.h5] [--async-shift | --device-global-map] [--surface-ply DIR [--surface-every N]] [--mesh-ply DIR] [--global-packed FILE.wspk]
                                    [--raycast-ply DIR] [--distance-npy DIR [--distance-m M]] [--global-distance-npy FILE [--global-distance-m M]]
                                    [--moving-sweeps] [--deskew] [--frontier-ply DIR] [--global-frontier-ply FILE] [--reach-ply DIR [--reach-clearance-m M]]
 
@@ -68,6 +68,8 @@ def main():
                     "TSDFMapping.surface_mesh) as binary little-endian PLY into DIR, after every N-th scan like --surface-ply")
     ap.add_argument("--global-mesh-ply", default=None, metavar="FILE", help="after the last scan: the mesh of the WHOLE run, window and every chunk that "
                     "has left it, from the device global map (TSDFMapping.global_mesh, ws_store_mesh); needs --device-global-map")
+    ap.add_argument("--global-packed", default=None, metavar="FILE", help="after the last scan: the WHOLE run, window and every chunk that has left it, as a "
+                    "packed snapshot (.wspk; TSDFMapping.save_global_packed, ws_store_pack); needs --device-global-map")
     ap.add_argument("--global-mesh-level", type=int, default=0, metavar="L", help="the level of detail of --global-mesh-ply: 0 the map's resolution, L the "
                     "store coarsened L times (voxels of 2^L times the edge; TSDFMapping.global_pyramid, ws_store_coarsen)")
     ap.add_argument("--global-surface-ply", default=None, metavar="FILE", help="after the last scan: the surface cloud of the WHOLE run, window and every "
@@ -116,6 +118,8 @@ def main():
     args = ap.parse_args()
     if args.global_mesh_ply and not args.device_global_map:
         ap.error("--global-mesh-ply requires --device-global-map")
+    if args.global_packed and not args.device_global_map:
+        ap.error("--global-packed requires --device-global-map")
     if args.global_mesh_level < 0 or (args.global_mesh_level and not args.global_mesh_ply):
         ap.error("--global-mesh-level is a level >= 0 and requires --global-mesh-ply")
     if args.global_surface_ply and not args.device_global_map:
@@ -261,6 +265,16 @@ def main():
         route = "save_box + ws_store_mesh + download" if not args.global_mesh_level else "save_box + ws_store_coarsen per level + ws_store_mesh + download"
         print(f"global mesh (level {args.global_mesh_level}): {len(gv)} vertices, {len(gf)} faces from {global_mesh['chunks']} chunks in {1000.0 * tg:.2f} ms ({route})",
               file=sys.stderr)
+    global_packed = None
+    if args.global_packed:
+        tg = time.perf_counter()
+        os.makedirs(os.path.dirname(os.path.abspath(args.global_packed)), exist_ok=True)
+        gp = app.gpu_.save_global_packed(args.global_packed)
+        tg = time.perf_counter() - tg
+        global_packed = {"file": args.global_packed, "chunks": gp.n_chunks, "bricks_default_uniform_dense": list(gp.stats[:3]), "bytes": int(gp.stats[3]),
+                         "ratio": gp.ratio, "call_s": tg}
+        print(f"global packed: {gp.n_chunks} chunks, {gp.stats[3] / 1e6:.1f} MB, ratio {gp.ratio:.4f} in {1000.0 * tg:.2f} ms (save_box + ws_store_pack + download + file)",
+              file=sys.stderr)
     global_surface = None
     if args.global_surface_ply:
         tg = time.perf_counter()
@@ -344,6 +358,7 @@ def main():
                       "mesh_ply": mesh if args.mesh_ply else None,
                       "global_mesh_ply": global_mesh,
                       "global_surface_ply": global_surface,
+                      "global_packed": global_packed,
                       "frontier_ply": frontier if args.frontier_ply else None,
                       "reach_ply": reach if args.reach_ply else None,
                       "next_view_csv": next_view if args.next_view_csv else None,

@@ -18,6 +18,7 @@ from ._lib import WS_FUSE_COUNT_ONLY, WS_FUSE_DEFAULT  # noqa: F401
 from .pyramid import CoarsenStats, MapPyramid, parents_of  # noqa: F401
 from ._lib import WS_COARSEN_DEFAULT  # noqa: F401
 from .changes import CHANGE_RECORD, ChangeResult, ChangeStats, write_changes_ply  # noqa: F401
+from .pack import PackedMap  # noqa: F401
 from ._lib import WS_CHANGES_APPEARED, WS_CHANGES_CLUSTERS, WS_CHANGES_DEFAULT, WS_CHANGES_VANISHED  # noqa: F401
 
 __all__ = [n for n in dir() if not n.startswith("_")]

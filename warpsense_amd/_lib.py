@@ -59,6 +59,8 @@ EXPORTS = [
     "ws_store_coarsen", "ws_store_parents_of", "ws_debug_store_coarsen_timing",
     "ws_store_changes", "ws_store_changes_records_dev", "ws_store_changes_labels_dev", "ws_store_changes_clusters_dev", "ws_store_changes_download",
     "ws_debug_store_changes_timing",
+    "ws_store_pack", "ws_store_pack_headers_dev", "ws_store_pack_payload_dev", "ws_store_pack_download", "ws_store_unpack", "ws_store_unpack_dev",
+    "ws_pack_check", "ws_pack_expand_chunk", "ws_pack_chunk", "ws_debug_store_pack_timing",
 ]
 WS_SURFACE_RECORDS, WS_SURFACE_MARKER = 0, 1
 WS_MESH_DEFAULT, WS_MESH_ANY_WEIGHT = 0, 1
@@ -73,6 +75,7 @@ WS_GAIN_DEFAULT, WS_GAIN_ANY_WEIGHT, WS_GAIN_RAYS = 0, 1, 2
 WS_FUSE_DEFAULT, WS_FUSE_COUNT_ONLY = 0, 1
 WS_COARSEN_DEFAULT = 0
 WS_CHANGES_APPEARED, WS_CHANGES_VANISHED, WS_CHANGES_CLUSTERS, WS_CHANGES_DEFAULT = 1, 2, 4, 3
+WS_PACK_HEADER_WORDS, WS_PACK_DEFAULT, WS_PACK_EMIT_DIRECT = 40, 0, 1
 
 
 class WsError(RuntimeError):
@@ -254,6 +257,16 @@ def load() -> C.CDLL:
         f.argtypes, f.restype = [vp, P(sz)], vp
     L.ws_store_changes_download.argtypes = [vp, vp, vp, vp, sz, sz, P(sz), P(sz)]
     L.ws_debug_store_changes_timing.argtypes = [vp, i32, vp]
+    L.ws_store_pack.argtypes = [vp, vp, sz, u32, P(sz), P(C.c_uint64), vp]
+    L.ws_store_pack_headers_dev.argtypes, L.ws_store_pack_headers_dev.restype = [vp, P(sz)], vp
+    L.ws_store_pack_payload_dev.argtypes, L.ws_store_pack_payload_dev.restype = [vp, P(C.c_uint64)], vp
+    L.ws_store_pack_download.argtypes = [vp, vp, vp, sz, C.c_uint64, P(sz), P(C.c_uint64)]
+    L.ws_store_unpack.argtypes = [vp, vp, vp, sz, C.c_uint64, u32, u32]
+    L.ws_store_unpack_dev.argtypes = [vp, vp, vp, sz, C.c_uint64, u32, u32]
+    L.ws_pack_check.argtypes = [vp, sz, C.c_uint64]
+    L.ws_pack_expand_chunk.argtypes = [vp, vp, u32, vp]
+    L.ws_pack_chunk.argtypes = [vp, vp, u32, vp, vp, C.c_uint64, P(C.c_uint64)]
+    L.ws_debug_store_pack_timing.argtypes = [vp, i32, vp]
     L.ws_debug_reach_active.argtypes = [vp, vp, sz, P(sz)]
     L.ws_shift_plan.argtypes = [vp, vp, vp, vp, P(ShiftPlan)]
     L.ws_shift_begin.argtypes = [vp, vp, u32, P(vp)]

@@ -21,7 +21,6 @@ using namespace ws;
 // ---- the chunk store: the global map in device memory (map_store.hip)
 namespace
 {
-using StoreKey = std::array<int32_t, 3>;
 inline int32_t chunk_of(int32_t v) { return v >= 0 ? v / STORE_CS : -((-(int64_t)v + STORE_CS - 1) / STORE_CS); } // floor(v / 64)
 
 // the chunks an inclusive world box overlaps: first key and count per axis
@@ -91,6 +90,11 @@ int store_grow(ws_store *st, uint64_t chunks)
 // chunks that can still be created without a new segment / at all
 uint64_t store_unused(const ws_store *st) { return st->free_slots.size() + (store_capacity(st) - st->next_slot); }
 
+} // namespace
+
+// (declared in ws_api.h: api_pack.hip hands out slots and takes tables by the same rules)
+namespace ws
+{
 // Room for `fresh` more chunks: WS_ERR_CAPACITY beyond max_chunks, segments where they are missing.  Nothing else changes.
 int store_make_room(ws_store *st, uint64_t fresh, const char *name)
 {
@@ -113,6 +117,10 @@ uint32_t store_take_slot(ws_store *st) // (store_make_room has been asked)
   }
   return st->next_slot++;
 }
+} // namespace ws
+
+namespace
+{
 
 // room for n words in one slot table (pinned + device) and its event
 int store_table_reserve(ws_store::Table &t, size_t n)
@@ -123,6 +131,10 @@ int store_table_reserve(ws_store::Table &t, size_t n)
   return t.dev.alloc(n, sizeof(uint32_t));
 }
 
+} // namespace
+
+namespace ws
+{
 // The next slot table of the ring, for n words: waits only for the launch that read this table STORE_TABLES calls ago.  The tables are
 // sized when the store is created (STORE_TABLE_WORDS); a box that overlaps more chunks makes one grow here, which allocates.
 int store_table(ws_store *st, size_t n, ws_store::Table **out)
@@ -135,6 +147,10 @@ int store_table(ws_store *st, size_t n, ws_store::Table **out)
   *out = &t;
   return WS_OK;
 }
+} // namespace ws
+
+namespace
+{
 
 // One launch: the box of `which` (window `par`) into the chunks or back.  The directory already holds every chunk a save needs (a
 // save table never holds STORE_ABSENT: the kernel would read that word as slot 2^31 - 1, flagged new).  A chunk this call created
@@ -188,7 +204,8 @@ void store_admit(ws_store *st, const std::set<StoreKey> &fresh)
 {
   for (const StoreKey &k : fresh) st->dir[k] = ws_store::Entry{store_take_slot(st), false};
 }
-void store_evict(ws_store *st, const std::set<StoreKey> &fresh)
+} // namespace
+void ws::store_evict(ws_store *st, const std::set<StoreKey> &fresh)
 {
   for (const StoreKey &k : fresh)
   {
@@ -198,6 +215,8 @@ void store_evict(ws_store *st, const std::set<StoreKey> &fresh)
     st->dir.erase(it);
   }
 }
+namespace
+{
 
 int store_args(const ws_store *st, const ws_map *m, int which, const char *name)
 {

@@ -65,6 +65,13 @@ int distance_download(const DistResult &q, hipStream_t s, uint32_t *host, size_t
 // the event pairs of ws_debug_*_timing (QueryTimer::read)
 constexpr int SURF_PAIRS[3][2] = {{0, 1}, {1, 2}, {3, 4}}, MESH_PAIRS[3][2] = {{0, 1}, {1, 2}, {3, 4}}, RAY_PAIRS[3][2] = {{0, 1}, {1, 2}, {2, 3}}, SAMPLE_PAIRS[3][2] = {{0, 1}, {1, 2}, {2, 3}}, DIST_PAIRS[4][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 4}};
 
+// ---- api_store.hip: what the calls that create chunks share with api_pack.hip.  The caller holds the store's lock.
+using StoreKey = std::array<int32_t, 3>;
+int store_make_room(ws_store *st, uint64_t fresh, const char *name); // room for `fresh` more chunks: WS_ERR_CAPACITY beyond max_chunks, segments where they are missing (which waits for the stream)
+uint32_t store_take_slot(ws_store *st);                              // (store_make_room has been asked)
+void store_evict(ws_store *st, const std::set<StoreKey> &fresh);     // the chunks of `fresh` leave the directory, their slots are free again
+int store_table(ws_store *st, size_t n, ws_store::Table **out);      // the next slot table of the ring, for n words
+
 // ---- surface cloud, mesh, ray cast and distance field: one host core each for the window of a map (map_surface.hip, map_mesh.hip,
 // map_raycast.hip, map_distance.hip) and for the chunks of the store (store_surface.hip, store_mesh.hip, store_raycast.hip,
 // store_distance.hip).  An entry point checks what is its own, takes

@@ -797,8 +797,21 @@ struct ws_store
     ws::QueryTimer timer;     // 0 upload of the plan 1 the pass 2
     void release() { words.release(), words_host.release(), timer.release(); }
   } coarsen;
+  struct Pack // ws_store_pack of this store, and ws_store_unpack into it (store_pack.hip)
+  {
+    ws::QueryTimer timer;     // a pack: 0 classify 1 scan 2, 3 emit 4; an unpack: 0 launch 1
+    ws::DevBuf headers;       // uint32 [WS_PACK_HEADER_WORDS per packed chunk]
+    ws::DevBuf payload;       // uint32: the payload stream
+    ws::DevCounter words;     // the scan's sums: payload words, uniform bricks, dense bricks
+    ws::DevBuf stage;         // uint32: the payload of a ws_store_unpack from host memory
+    size_t n = 0;             // chunks of the last pack
+    uint64_t n_words = 0;     // payload words of the last pack
+    bool unpacked_last = false; // the timer holds an unpack's events
+    void release() { timer.release(), words.release(), n = 0, n_words = 0; for (ws::DevBuf *b : {&headers, &payload, &stage}) b->release(); }
+  } pack;
   void release()
   {
+    pack.release();
     coarsen.release();
     fuse.release();
     gain.release();
@@ -956,6 +969,15 @@ struct StoreChangesCall
 };
 int launch_store_changes_count(ws_store *cur, const ws_store *ref, ws_store::Changes &q, const StoreChangesCall &c);
 int launch_store_changes_emit(ws_store *cur, const ws_store *ref, ws_store::Changes &q, const StoreChangesCall &c, size_t cap);
+
+// store_pack.hip: the passes of ws_store_pack over the `n` chunks of `table_dev` ({cx, cy, cz, slot} each, ascending keys) into
+// q.headers (classify: class maps, counts and keys; scan: the first-word indices, and q.words.dev = payload words, uniform bricks,
+// dense bricks) and, once the host has sized q.payload from the total, into q.payload (emit, which writes no word at or beyond
+// `cap`); and the pass of ws_store_unpack: `n` chunks whose headers and slots ({WS_PACK_HEADER_WORDS words} x n, then n slots)
+// are at table_dev
+int launch_store_pack_count(ws_store *st, ws_store::Pack &q, const void *table_dev, size_t n);
+int launch_store_pack_emit(ws_store *st, ws_store::Pack &q, const void *table_dev, size_t n, bool direct, uint64_t cap);
+int launch_store_unpack(ws_store *st, ws_store::Pack &q, const uint32_t *table_dev, size_t n, const uint32_t *payload_dev, uint32_t fill);
 
 // map_reach.hip: the geodesic field over the records of a distance result, of a window or of the store alike.  reach_tiles: the tiles
 // of a box.  launch_reach_seed clears costs, marks and words, takes the n_seeds seeds in q.seeds (it marks events 0, 1) and queues

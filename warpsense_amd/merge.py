@@ -7,11 +7,13 @@ import numpy as np
 from ._abi import unpack_entry
 from ._lib import WsError
 from .global_map import GlobalMap
+from .pack import PackQueries
 from .store import DeviceGlobalMap
 
 
-class FuseQueries:
-    """merge_map and align_map of TSDFMapping (mapping.py): the fuse behind the mapping's lock and its window"""
+class FuseQueries(PackQueries):
+    """merge_map and align_map of TSDFMapping (mapping.py): the fuse behind the mapping's lock and its window; with PackQueries, what
+    brings another map in or this one out: save_global_packed, load_global_packed"""
 
     def merge_map(self, other, T_src_to_dst, max_weight=None, count_only=False, pivot_src_mm=None):
         """Another map fused into everything this run has seen (DeviceGlobalMap.fuse, ws_store_fuse): the window goes into the chunks

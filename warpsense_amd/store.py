@@ -6,12 +6,13 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._abi import _i3, _i3c, _ptr, pack_entry
+from ._abi import _i3, _i3c, _ptr, pack_entry, unpack_entry
 from ._lib import WS_MAP_AVG, check
 from .context import Context
 from .changes import ChangeResult, _changes_call
 from .fuse import FuseStats, _fuse_call, fuse_pose
 from .global_map import GlobalMap
+from .pack import PackedMap, _pack_call, _unpack_call
 from .pyramid import CoarsenStats, _coarsen_call
 from .queries import _box_ptrs, _distance_call, _frontier_call, _reach_call, _reach_lookup_call, _reach_paths_call, _mesh_call, _raycast_call, _sample_call, _surface_call, _timing, _view_gain_call
 
@@ -270,6 +271,48 @@ class DeviceGlobalMap:
     def coarsen_timing(self, enable: int = -1):
         """device milliseconds of the plan's upload and of the pass of the last coarsen() INTO this map (ws_debug_store_coarsen_timing)"""
         return _timing(self._L, "ws_debug_store_coarsen_timing", self.handle, 2, enable)
+
+    def pack(self, keys=None, device=False, direct=False) -> PackedMap:
+        """Chunks of this map in packed form, made on the device (ws_store_pack; the format is stated in include/warpsense_hip.h):
+        the (n, 3) chunks `keys` names (None: every chunk), in ascending key order whatever the order given, as 40-word headers
+        and one payload stream in which a brick of 8^3 words that is all default takes nothing and one that repeats one word takes
+        one word.  A key the map does not hold, or one named twice, raises.  device=True: the payload is an int32 torch tensor
+        that ALIASES the store's buffer, valid until the next pack() on this store (the headers always come to the host).
+        direct: the emit pass without its LDS staging (measurement; the bytes are the same).  This map is only read."""
+        return _pack_call(self._L, self, keys, device, direct)
+
+    def unpack(self, packed: PackedMap):
+        """The chunks of `packed` created or overwritten whole (ws_store_unpack, or ws_store_unpack_dev for a payload on the device);
+        default bricks get packed.fill, whatever this map's default is.  Chunks that are not listed keep their bytes.  A stream
+        that fails ws_pack_check, or more chunks than max_chunks allows, raises and leaves the map unchanged."""
+        _unpack_call(self._L, self, packed)
+
+    def clone(self, ctx: Context | None = None) -> "DeviceGlobalMap":
+        """A byte-exact copy of this map as a new DeviceGlobalMap with the same default: pack(), then unpack from the payload where
+        it lies on the device; only the headers visit the host.  Returns after the copy has run."""
+        value, weight = (int(v) for v in unpack_entry(self.default_raw))
+        other = DeviceGlobalMap(value, weight, ctx=ctx or self.ctx)
+        other.unpack(self.pack(device=True))
+        check(self._L.ws_sync(other.ctx.handle), "ws_sync")
+        return other
+
+    def save_packed(self, path, **meta) -> PackedMap:
+        """this map packed into a `.wspk` file (PackedMap.save); meta: resolution=, tau= and whatever else the file should say"""
+        packed = self.pack()
+        packed.resolution, packed.tau = meta.pop("resolution", None), meta.pop("tau", None)
+        packed.save(path, **meta)
+        return packed
+
+    def load_packed(self, path) -> PackedMap:
+        """the chunks of a `.wspk` file into this map (PackedMap.load, unpack); returns the PackedMap with the file's metadata"""
+        packed = PackedMap.load(path)
+        self.unpack(packed)
+        return packed
+
+    def pack_timing(self, enable: int = -1):
+        """device milliseconds of the classify pass, the scan and the emit pass of the last pack(), or of the last unpack()'s launch
+        and zeros if that came later (ws_debug_store_pack_timing)"""
+        return _timing(self._L, "ws_debug_store_pack_timing", self.handle, 3, enable)
 
     def flush_to(self, global_map: GlobalMap):
         """every chunk merged into a host GlobalMap: into its chunk cache (activate_chunk), or, for a map with a file, straight
