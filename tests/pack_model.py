@@ -85,11 +85,20 @@ def word(b, w):
     return at((b >> 6) * 8 + (w >> 6), ((b >> 3) & 7) * 8 + ((w >> 3) & 7), (b & 7) * 8 + (w & 7))
 
 
+def odd_word(b):
+    """the one word of brick b that differs in the odd_* cases: 197 is odd, so every word number is the odd one of exactly one brick"""
+    return (197 * b + 61) % 512
+
+
+# the bricks of the `halves` case, all in the brick column 168 .. 175 (one wave's ballots): (brick, its one odd word or None for a
+# uniform brick, the bit that differs from fill)
+HALVES = ((168, 300, 0), (170, 37, 31), (171, None, 31), (173, None, 0))
+
 _CASES = {}
 
 
 def brick_cases(fill=FILL, other=OTHER):
-    """{name: chunk}: the nine chunks of the brick cases (made once, never written to)"""
+    """{name: chunk}: the twelve chunks of the brick cases (made once, never written to)"""
     key = (int(fill), int(other))
     if key in _CASES:
         return _CASES[key]
@@ -122,18 +131,34 @@ def brick_cases(fill=FILL, other=OTHER):
     mode = rng.integers(0, 3, 512)
     b = np.where(mode[:, None] == 0, fill, np.where(mode[:, None] == 1, other, np.where(rng.random((512, 512)) < 0.5, fill, other))).astype(np.uint32)
     c["two_words"] = unbricks(b)
+    # every brick has ONE deciding word, and every word number 0 .. 511 is the deciding one of one brick: in fill (a classifier blind
+    # to that position calls the brick default) and in a uniform brick (it calls the brick uniform)
+    odd = odd_word(np.arange(512))
+    b = np.full((512, 512), fill, dtype=np.uint32)
+    b[np.arange(512), odd] = other
+    c["odd_in_fill"] = unbricks(b)
+    b = np.full((512, 512), other, dtype=np.uint32)
+    b[np.arange(512), odd] = other ^ np.uint32(1)
+    c["odd_in_uniform"] = unbricks(b)
+    # a difference from fill in the lowest or in the highest bit alone, in one word of a brick and in all of them
+    c["halves"] = full(fill)
+    for brick, w, bit in HALVES:
+        for i in range(512) if w is None else (w,):
+            c["halves"][word(brick, i)] = fill ^ np.uint32(1 << bit)
     for v in c.values():
         v.setflags(write=False)
     _CASES[key] = c
     return c
 
 
-# the keys the nine cases live under in a store: negative ones, and the key ends of two_store_scenes.KEY_END_KEYS
+# the keys the cases live under in a store: negative ones, and the key ends of two_store_scenes.KEY_END_KEYS
 IMAX, IMIN = 2 ** 31 - 1, -2 ** 31
 CASE_KEYS = {"all_fill": (0, 0, 0), "one_word": (-1, -1, -1), "single_first": (IMAX, IMIN, 0), "single_last": (IMAX - 1, IMIN, 0), "but_last": (IMIN, IMAX, -1),
-             "word0_fill": (-3, 2, -2), "neighbours": (0, 0, 1), "random": (0, -1, 0), "two_words": (5, 5, 5)}
+             "word0_fill": (-3, 2, -2), "neighbours": (0, 0, 1), "random": (0, -1, 0), "two_words": (5, 5, 5),
+             "odd_in_fill": (-7, 3, 4), "odd_in_uniform": (3, -4, 2), "halves": (1, 0, -5)}
+N_CASES = len(CASE_KEYS)
 
 
 def case_store(fill=FILL, other=OTHER):
-    """{key: chunk} of the nine cases"""
+    """{key: chunk} of the cases"""
     return {CASE_KEYS[name]: chunk for name, chunk in brick_cases(fill, other).items()}

@@ -8,6 +8,7 @@ import pytest
 
 import fuse_scenes as S
 import pack_model as PM
+import pack_scenes as PS
 import two_store_scenes as T
 import warpsense_amd as W
 from warpsense_amd._abi import _ptr
@@ -31,7 +32,7 @@ def same(packed, want):
 
 @pytest.fixture(scope="module")
 def cases():
-    """the store of the nine brick cases (keys negative and at both key ends), the model's stream over it, and its pack"""
+    """the store of the twelve brick cases (keys negative and at both key ends), the model's stream over it, and its pack"""
     chunks = PM.case_store()
     store = make(chunks)
     return dict(chunks=chunks, store=store, want=PM.pack(chunks, PM.FILL), packed=store.pack())
@@ -56,7 +57,7 @@ def test_each_brick_case_alone(name):
 
 
 def test_all_cases_in_one_store_and_twice_the_same_bytes(cases):
-    assert same(cases["packed"], cases["want"]) and cases["packed"].n_chunks == 9
+    assert same(cases["packed"], cases["want"]) and cases["packed"].n_chunks == 12
     assert all(v > 0 for v in cases["packed"].stats) and 0 < cases["packed"].ratio < 1
     again, direct = cases["store"].pack(), cases["store"].pack(direct=True)
     for p in (again, direct):
@@ -83,7 +84,7 @@ def test_absent_and_repeated_keys_are_refused_and_the_last_result_stays(cases):
     assert L.ws_store_pack(store.handle, None, 0, 2, C.byref(n), C.byref(words), None) == WS_ERR_INVALID  # an unknown flag bit
     headers, payload = np.zeros_like(want[0]), np.zeros_like(want[1])
     assert L.ws_store_pack_download(store.handle, _ptr(headers), _ptr(payload), len(headers), len(payload), C.byref(n), C.byref(words)) == 0
-    assert (n.value, words.value) == (9, len(want[1])) and headers.tobytes() == want[0].tobytes() and payload.tobytes() == want[1].tobytes()
+    assert (n.value, words.value) == (12, len(want[1])) and headers.tobytes() == want[0].tobytes() and payload.tobytes() == want[1].tobytes()
 
 
 def test_a_download_capacity_too_small_reports_the_sizes(cases):
@@ -91,13 +92,13 @@ def test_a_download_capacity_too_small_reports_the_sizes(cases):
     want = PM.pack(cases["chunks"], PM.FILL)
     store.pack()
     headers, payload = np.zeros_like(want[0]), np.zeros_like(want[1])
-    for cap_c, cap_w in ((8, len(payload)), (9, len(payload) - 1), (0, 0)):
+    for cap_c, cap_w in ((11, len(payload)), (12, len(payload) - 1), (0, 0)):
         n, words = C.c_size_t(0), C.c_uint64(0)
         assert L.ws_store_pack_download(store.handle, _ptr(headers), _ptr(payload), cap_c, cap_w, C.byref(n), C.byref(words)) == WS_ERR_CAPACITY
-        assert (n.value, words.value) == (9, len(payload)) and not headers.any() and not payload.any()
+        assert (n.value, words.value) == (12, len(payload)) and not headers.any() and not payload.any()
     # the device pointers carry the same counts
     n, words = C.c_size_t(0), C.c_uint64(0)
-    assert L.ws_store_pack_headers_dev(store.handle, C.byref(n)) and L.ws_store_pack_payload_dev(store.handle, C.byref(words)) and (n.value, words.value) == (9, len(payload))
+    assert L.ws_store_pack_headers_dev(store.handle, C.byref(n)) and L.ws_store_pack_payload_dev(store.handle, C.byref(words)) and (n.value, words.value) == (12, len(payload))
 
 
 def test_an_aged_store_of_two_chunk_segments():
@@ -159,15 +160,102 @@ def test_a_corrupted_stream_and_a_full_store_change_nothing(cases):
     with pytest.raises(W.WsError, match="status -1"):
         dst.unpack(W.PackedMap(p.headers[::-1], p.payload, p.fill))
     small_own = {(7, 7, 7): T.observed(91), (0, 0, 1): T.observed(92)}
-    small = S.make_store(small_own, max_chunks=10, fill=(-32768, 3))  # 2 + 9 - 1 shared = 10 fit; one more does not
+    small = S.make_store(small_own, max_chunks=13, fill=(-32768, 3))  # 2 + 12 - 1 shared = 13 fit; one more does not
     small.unpack(p)
-    assert small.count() == 10
-    small2 = S.make_store(small_own, max_chunks=9, fill=(-32768, 3))
+    assert small.count() == 13
+    small2 = S.make_store(small_own, max_chunks=12, fill=(-32768, 3))
     with pytest.raises(W.WsError, match="status -4"):
         small2.unpack(p)
     for store, want in ((dst, before), (small2, small_own)):
         got = S.read(store)
         assert sorted(got) == sorted(want) and all(got[k].tobytes() == want[k].tobytes() for k in want)
+
+
+def same_chunks(store, sc, keys):
+    for k in keys:
+        assert store.chunk(k).tobytes() == sc["chunks"][k].tobytes(), (k, sc["names"][k])
+    return True
+
+
+@pytest.fixture(scope="module")
+def aged130():
+    """130 chunks (three waves of the scan) in a store of four-chunk segments whose slots are neither fresh nor in key order: the
+    chunks at the odd places go in first, five of them are dropped, then all go in, the absent ones into the freed and the new slots"""
+    sc = PS.scene(130)
+    store = W.DeviceGlobalMap(FILL[0], FILL[1], segment_chunks=4)
+    first = sc["keys"][1::2]
+    h, p, _ = PS.stream(sc, first)
+    store.unpack(W.PackedMap(h, p, int(PM.FILL)))
+    assert store.keys() == first and same_chunks(store, sc, first[::13])
+    dropped = first[3::14]
+    assert len(dropped) == 5
+    for k in dropped:
+        store.drop_chunk(k)
+    assert store.count() == 60
+    want = PS.stream(sc)
+    store.unpack(W.PackedMap(want[0], want[1], int(PM.FILL)))
+    d = T.Directory(4)  # the same history on the replay of the directory rules
+    d.create(first)
+    for k in dropped:
+        d.drop(k)
+    d.create(sc["keys"])
+    mixed, reused, spans = T.claims(d, sc["keys"])
+    assert mixed and reused == 5 and spans == 33 and store.capacity() == d.capacity() == 132
+    yield dict(scene=sc, store=store, want=want)
+    store.close()
+
+
+def test_130_chunks_in_aged_slots(aged130):
+    sc, store, want = aged130["scene"], aged130["store"], aged130["want"]
+    assert store.count() == 130 and store.keys() == sc["keys"]
+    got = S.read(store)
+    assert sorted(got) == sc["keys"] and all(got[k].tobytes() == sc["chunks"][k].tobytes() for k in sc["keys"])
+    assert same(store.pack(), want) and same(store.pack(direct=True), want)
+    rng = np.random.default_rng(70)
+    keys = sorted((sc["keys"][i] for i in rng.choice(130, 70, replace=False)), reverse=True)
+    assert len(set(keys)) == 70 and same(store.pack(keys=keys), PM.pack(sc["chunks"], PM.FILL, keys))
+
+
+def test_a_small_result_after_a_large_one(aged130):
+    """the buffers of a pack are kept: a later, smaller result must not show what an earlier one left in them"""
+    sc, store, L = aged130["scene"], aged130["store"], aged130["store"]._L
+    by_name = lambda name: next(k for k in sc["keys"] if sc["names"][k] == name)
+    assert same(store.pack(), aged130["want"])
+    p = store.pack(keys=[by_name("all_fill")])
+    assert same(p, PM.pack(sc["chunks"], PM.FILL, [by_name("all_fill")])) and p.n_chunks == 1 and p.payload_words == 0 and p.stats == (512, 0, 0, 160)
+    words = C.c_uint64(7)
+    assert not L.ws_store_pack_payload_dev(store.handle, C.byref(words)) and words.value == 0
+    n = C.c_size_t(7)
+    assert L.ws_store_pack_headers_dev(store.handle, C.byref(n)) and n.value == 1
+    one = [by_name("random")]
+    assert same(store.pack(keys=one), PM.pack(sc["chunks"], PM.FILL, one)) and same(store.pack(keys=one, direct=True), PM.pack(sc["chunks"], PM.FILL, one))
+
+
+def test_1030_chunks_through_unpack_and_pack():
+    """more chunks than one round of the scan (1024), about 1 GiB of store: the model's stream in, the same bytes out; then the
+    payload stays on the device, into a second store and back into the store it came from"""
+    import time
+    t0 = time.perf_counter()
+    sc = PS.scene(1030)
+    want = PS.stream(sc)
+    store, second = make({}, segment_chunks=0), make({}, segment_chunks=0)
+    try:
+        store.unpack(W.PackedMap(want[0], want[1], int(PM.FILL)))
+        assert store.count() == 1030 and store.keys() == sc["keys"]
+        assert same(store.pack(), want)
+        rng = np.random.default_rng(1030)
+        ends = [0, 1, 63, 64, 1023, 1024, 1029]
+        places = ends + sorted(int(i) for i in rng.choice([i for i in range(1030) if i not in ends], 24, replace=False))
+        assert len(set(places)) == 31 and same_chunks(store, sc, [sc["keys"][i] for i in places])
+        p = store.pack(device=True)
+        assert p.on_device and p.payload_words == len(want[1]) and p.headers.tobytes() == want[0].tobytes()
+        second.unpack(p)
+        assert second.count() == 1030 and same(second.pack(), want)
+        store.unpack(store.pack(device=True))
+        assert store.count() == 1030 and same(store.pack(), want)
+    finally:
+        store.close(), second.close()
+    print("1030 chunks: %.2f s, %.1f MB of payload" % (time.perf_counter() - t0, 4e-6 * len(want[1])))
 
 
 def test_pack_timing_reports_three_passes_then_the_unpack(cases):

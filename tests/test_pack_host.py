@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import pack_model as PM
+import pack_scenes as PS
 import query_model as QM
 import warpsense_amd as W
 from warpsense_amd import _lib
@@ -59,6 +60,32 @@ def test_the_cases_hold_what_their_names_say():
     assert k["neighbours"][160:168].tolist() == [2, 1, 2, 0, 0, 0, 2, 1] and k["neighbours"][504:506].tolist() == [1, 2]
     assert (k["random"] == 2).all()
     assert all(int((k["two_words"] == c).sum()) > 100 for c in (0, 1, 2))
+    assert len(CASES) == 12 == PM.N_CASES and len(set(PM.CASE_KEYS.values())) == 12 and sorted(PM.CASE_KEYS) == sorted(CASES)
+    # the odd word of the 512 bricks is each of the 512 word numbers once
+    rows, odd = np.arange(512), PM.odd_word(np.arange(512))
+    assert sorted(odd.tolist()) == list(range(512)) and [PM.odd_word(b) for b in (0, 1, 511)] == [61, 258, (197 * 511 + 61) % 512]
+    for name, flat, masked_class in (("odd_in_fill", PM.FILL, 0), ("odd_in_uniform", PM.OTHER, 1)):
+        b = PM.bricks(CASES[name])
+        assert (k[name] == 2).all()
+        # exactly one word of every brick is unlike its other 511, which are all alike: it is word odd_word(b)
+        assert ((b != flat).sum(axis=1) == 1).all() and (b[rows, odd] != flat).all()
+        # with that one word masked the class is 0 resp. 1, for every brick: each of the 512 positions decides one brick's class
+        masked = b.copy()
+        masked[rows, odd] = flat
+        assert (PM.classes(PM.unbricks(masked), PM.FILL) == masked_class).all()
+        for w in (0, 7, 8, 63, 64, 448, 511):  # ... and a model blind to ONE word number gets exactly the brick that owns it wrong
+            blind = b.copy()
+            blind[:, w] = b[:, (w + 1) % 512]
+            wrong = np.flatnonzero(PM.classes(PM.unbricks(blind), PM.FILL) != 2)
+            assert wrong.tolist() == [int(np.flatnonzero(odd == w)[0])], (name, w, wrong)
+    halves = {brick: (w, bit) for brick, w, bit in PM.HALVES}
+    assert sorted(halves) == [168, 170, 171, 173] and len({brick >> 3 for brick in halves}) == 1  # one brick column
+    assert k["halves"][sorted(halves)].tolist() == [2, 2, 1, 1] and int((k["halves"] != 0).sum()) == 4
+    b = PM.bricks(CASES["halves"])
+    for brick, (w, bit) in halves.items():
+        unlike = np.flatnonzero(b[brick] != PM.FILL)
+        assert unlike.tolist() == ([w] if w is not None else list(range(512))) and set((b[brick][unlike] ^ PM.FILL).tolist()) == {1 << bit}
+    assert sorted({bit for _, bit in halves.values()}) == [0, 31] and {(w is None, bit) for w, bit in halves.values()} == {(a, c) for a in (False, True) for c in (0, 31)}
 
 
 def test_capacity_of_pack_chunk():
@@ -126,11 +153,41 @@ def test_check_carries_offsets_beyond_2_to_the_32_words():
     assert int(p.offsets[-1]) == (n - 1) * 512 * 512
 
 
+def test_the_scene_of_many_chunks_is_what_the_model_packs():
+    """the stamped stream of pack_scenes equals PM.pack chunk by chunk (N = 130), its keys are spread, its cases weighted"""
+    sc = PS.scene(130)
+    made = PS.scene_keys(130)
+    assert sorted(made) == sc["keys"] and made != sc["keys"] and all(end in made for end in PS.KEY_ENDS) and min(min(k) for k in made[:20]) < 0
+    headers, payload, stats = PS.stream(sc)
+    want = PM.pack(sc["chunks"], PM.FILL)
+    assert headers.tobytes() == want[0].tobytes() and payload.tobytes() == want[1].tobytes() and stats == want[2]
+    sub = sc["keys"][1::2]
+    hs, ps, ss = PS.stream(sc, sub[::-1])
+    want = PM.pack(sc["chunks"], PM.FILL, sub)
+    assert hs.tobytes() == want[0].tobytes() and ps.tobytes() == want[1].tobytes() and ss == want[2]
+    for n in (130, 1030):
+        names = [PS.case_of(i) for i in range(n)]
+        assert set(names) == set(CASES) and sum(name in PS.CHEAP for name in names) >= 0.9 * n
+        assert all(names[i] in ("random", "two_words") for i in range(19, n, 20)) and names.count("odd_in_fill") >= 2 <= names.count("odd_in_uniform")
+
+
+def test_check_accepts_a_stream_of_1030_chunks_and_chunks_expand_to_their_source():
+    sc = PS.scene(1030)
+    headers, payload, stats = PS.stream(sc)
+    n = len(headers)
+    assert n == 1030 and c_check(headers, len(payload)) == 0 and 10e6 < 4 * len(payload) < 100e6
+    assert c_check(headers[:1025], int(headers[1025, 5]) | int(headers[1025, 6]) << 32) == 0 and c_check(headers, len(payload) - 1) == -1
+    p = W.PackedMap(headers, payload, int(PM.FILL))
+    assert p.stats == tuple(stats) and p.keys == sc["keys"]
+    for i in (0, 63, 64, 1023, 1024, n - 1):
+        assert p.chunk(i).tobytes() == sc["chunks"][sc["keys"][i]].tobytes(), i
+
+
 def test_packed_map_file_round_trip(tmp_path):
     headers, payload, stats = model_stream()
     p = W.PackedMap(headers, payload, int(PM.FILL), resolution=64, tau=600)
-    assert p.stats == tuple(stats) and p.n_chunks == 9 and p.keys == sorted(PM.case_store()) and not p.on_device
-    assert p.ratio == pytest.approx(stats[3] / (9 * 4 * PM.CW)) and 0 < p.ratio < 1
+    assert p.stats == tuple(stats) and p.n_chunks == 12 and p.keys == sorted(PM.case_store()) and not p.on_device
+    assert p.ratio == pytest.approx(stats[3] / (12 * 4 * PM.CW)) and 0 < p.ratio < 1
     path = str(tmp_path / "map.wspk")
     p.save(path, note="a test")
     q = W.PackedMap.load(path)

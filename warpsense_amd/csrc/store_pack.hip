@@ -23,6 +23,7 @@ namespace
 {
 constexpr uint32_t PACK_WG = 256, PACK_PARTS = 16; // threads of a workgroup; workgroups of a chunk (four brick columns each)
 constexpr uint32_t PACK_STAGE_STRIDE = 264;       // words of a staged half brick (256) + 8
+static_assert(PACK_WG == PACK_OFFSETS_WG, "pack_brick_offsets (ws_pack.h) takes two bricks per thread of the emit and unpack workgroups");
 
 struct PackArgs
 {
@@ -54,30 +55,6 @@ __device__ __forceinline__ uint32_t *pack_chunk_ptr(uint32_t *const *segs, uint3
 
 // the first word of this wave's brick column in a chunk, for this lane: column (x, y) of it is at + x * 4096 + y * 64
 __device__ __forceinline__ uint32_t pack_column_at(uint32_t bx, uint32_t by, uint32_t lane) { return bx * 8u * 4096u + by * 8u * 64u + lane; }
-
-// The class map of a header into map[32] and the 512 brick offsets (payload words in front of a brick, inside its chunk) into
-// off[512]; all 256 threads call it, and it ends with a barrier.  part[4]: scratch.
-__device__ __forceinline__ void pack_brick_offsets(const uint32_t *header, uint32_t *map, uint32_t *off, uint32_t *part)
-{
-  const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
-  if (t < 32u) map[t] = header[PACK_HDR_MAP + t];
-  __syncthreads();
-  const uint32_t s0 = pack_class_words(pack_map_code(map, 2u * t)), s1 = pack_class_words(pack_map_code(map, 2u * t + 1u));
-  uint32_t v = s0 + s1; // inclusive scan over the wave, then over the four waves
-#pragma unroll
-  for (uint32_t o = 1; o < 64u; o <<= 1)
-  {
-    const uint32_t up = __shfl_up(v, o, 64);
-    if (lane >= o) v += up;
-  }
-  if (lane == 63u) part[wave] = v;
-  __syncthreads();
-  uint32_t before = 0;
-  for (uint32_t w = 0; w < wave; ++w) before += part[w];
-  off[2u * t] = before + v - s0 - s1;
-  off[2u * t + 1u] = before + v - s1;
-  __syncthreads();
-}
 
 __global__ __launch_bounds__(PACK_WG) void pack_classify_kernel(PackArgs a)
 {
@@ -127,54 +104,12 @@ __global__ __launch_bounds__(PACK_WG) void pack_classify_kernel(PackArgs a)
   }
 }
 
-__device__ __forceinline__ unsigned long long pack_wave_sum(unsigned long long v)
-{
-#pragma unroll
-  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // one workgroup: the exclusive 64-bit scan of the chunks' payload words into their headers; sums[3]: payload words, uniform bricks,
-// dense bricks of the call
-__global__ __launch_bounds__(1024) void pack_scan_kernel(uint32_t *headers, uint32_t n, unsigned long long *sums)
+// dense bricks of the call (pack_scan, ws_pack.h)
+__global__ __launch_bounds__(PACK_SCAN_WG) void pack_scan_kernel(uint32_t *headers, uint32_t n, unsigned long long *sums)
 {
-  __shared__ unsigned long long wtot[16], red[2][16];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  unsigned long long carry = 0, n_uniform = 0, n_dense = 0;
-  for (uint32_t base = 0; base < n; base += 1024u)
-  {
-    const uint32_t i = base + threadIdx.x; // (n < 2^31: no wrap)
-    uint32_t *h = headers + (size_t)i * PACK_HDR;
-    unsigned long long words = 0;
-    if (i < n)
-    {
-      words = pack_chunk_words(h);
-      n_uniform += h[PACK_HDR_UNIFORM], n_dense += h[PACK_HDR_DENSE];
-    }
-    unsigned long long v = words;
-#pragma unroll
-    for (uint32_t o = 1; o < 64u; o <<= 1)
-    {
-      const unsigned long long up = __shfl_up(v, o, 64);
-      if (lane >= o) v += up;
-    }
-    if (lane == 63u) wtot[wave] = v;
-    __syncthreads();
-    unsigned long long before = 0, all = 0;
-    for (uint32_t w = 0; w < 16u; ++w) before += w < wave ? wtot[w] : 0ull, all += wtot[w];
-    if (i < n) pack_set_first(h, carry + before + v - words);
-    carry += all;
-    __syncthreads();
-  }
-  n_uniform = pack_wave_sum(n_uniform), n_dense = pack_wave_sum(n_dense);
-  if (lane == 0u) red[0][wave] = n_uniform, red[1][wave] = n_dense;
-  __syncthreads();
-  if (threadIdx.x == 0u)
-  {
-    unsigned long long u = 0, d = 0;
-    for (uint32_t w = 0; w < 16u; ++w) u += red[0][w], d += red[1][w];
-    sums[0] = carry, sums[1] = u, sums[2] = d;
-  }
+  __shared__ unsigned long long wtot[PACK_SCAN_WG / 64], red[2][PACK_SCAN_WG / 64];
+  pack_scan(headers, n, sums, wtot, red);
 }
 
 template <bool DIRECT>
@@ -283,7 +218,7 @@ int launch_store_pack_count(ws_store *st, ws_store::Pack &q, const void *table_d
   hipLaunchKernelGGL(pack_classify_kernel, dim3(PACK_PARTS, (unsigned)std::min<size_t>(n, 65535)), dim3(PACK_WG), 0, s, a);
   WS_HIP(hipGetLastError());
   q.timer.mark(1, s);
-  hipLaunchKernelGGL(pack_scan_kernel, dim3(1), dim3(1024), 0, s, a.headers, a.n, q.words.dev);
+  hipLaunchKernelGGL(pack_scan_kernel, dim3(1), dim3(PACK_SCAN_WG), 0, s, a.headers, a.n, q.words.dev);
   WS_HIP(hipGetLastError());
   q.timer.mark(2, s);
   return WS_OK;

@@ -7,6 +7,10 @@
 
 #include "warpsense_hip.h"
 
+#ifdef __HIPCC__
+#include <hip/hip_runtime.h>
+#endif
+
 #ifndef __HIPCC__
 #ifndef __host__
 #define __host__
@@ -56,4 +60,83 @@ __host__ __device__ inline void pack_set_first(uint32_t *header, uint64_t first)
   header[PACK_HDR_OFF_LO] = (uint32_t)first;
   header[PACK_HDR_OFF_HI] = (uint32_t)(first >> 32);
 }
+
+#ifdef __HIPCC__
+// ---- the two scans of the kernels (store_pack.hip); tests/cpp/pack_units.hip runs them on the device on their own
+constexpr uint32_t PACK_OFFSETS_WG = 256, PACK_SCAN_WG = 1024; // the workgroups the two functions below are written for
+
+// The class map of a header into map[32] and the 512 brick offsets (payload words in front of a brick, inside its chunk) into
+// off[512]; all 256 threads call it, and it ends with a barrier.  part[4]: scratch.
+__device__ __forceinline__ void pack_brick_offsets(const uint32_t *header, uint32_t *map, uint32_t *off, uint32_t *part)
+{
+  const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+  if (t < 32u) map[t] = header[PACK_HDR_MAP + t];
+  __syncthreads();
+  const uint32_t s0 = pack_class_words(pack_map_code(map, 2u * t)), s1 = pack_class_words(pack_map_code(map, 2u * t + 1u));
+  uint32_t v = s0 + s1; // inclusive scan over the wave, then over the four waves
+#pragma unroll
+  for (uint32_t o = 1; o < 64u; o <<= 1)
+  {
+    const uint32_t up = __shfl_up(v, o, 64);
+    if (lane >= o) v += up;
+  }
+  if (lane == 63u) part[wave] = v;
+  __syncthreads();
+  uint32_t before = 0;
+  for (uint32_t w = 0; w < wave; ++w) before += part[w];
+  off[2u * t] = before + v - s0 - s1;
+  off[2u * t + 1u] = before + v - s1;
+  __syncthreads();
+}
+
+__device__ __forceinline__ unsigned long long pack_wave_sum(unsigned long long v)
+{
+#pragma unroll
+  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// The exclusive 64-bit scan of the chunks' payload words into the first-word fields of their n headers, in rounds of 1024 chunks;
+// sums[3]: payload words, uniform bricks, dense bricks of all of them.  The 1024 threads of ONE workgroup call it.  wtot[16],
+// red[2][16]: scratch in LDS.
+__device__ __forceinline__ void pack_scan(uint32_t *headers, uint32_t n, unsigned long long *sums, unsigned long long *wtot, unsigned long long (*red)[PACK_SCAN_WG / 64])
+{
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  unsigned long long carry = 0, n_uniform = 0, n_dense = 0;
+  for (uint32_t base = 0; base < n; base += 1024u)
+  {
+    const uint32_t i = base + threadIdx.x; // (n < 2^31: no wrap)
+    uint32_t *h = headers + (size_t)i * PACK_HDR;
+    unsigned long long words = 0;
+    if (i < n)
+    {
+      words = pack_chunk_words(h);
+      n_uniform += h[PACK_HDR_UNIFORM], n_dense += h[PACK_HDR_DENSE];
+    }
+    unsigned long long v = words;
+#pragma unroll
+    for (uint32_t o = 1; o < 64u; o <<= 1)
+    {
+      const unsigned long long up = __shfl_up(v, o, 64);
+      if (lane >= o) v += up;
+    }
+    if (lane == 63u) wtot[wave] = v;
+    __syncthreads();
+    unsigned long long before = 0, all = 0;
+    for (uint32_t w = 0; w < 16u; ++w) before += w < wave ? wtot[w] : 0ull, all += wtot[w];
+    if (i < n) pack_set_first(h, carry + before + v - words);
+    carry += all;
+    __syncthreads();
+  }
+  n_uniform = pack_wave_sum(n_uniform), n_dense = pack_wave_sum(n_dense);
+  if (lane == 0u) red[0][wave] = n_uniform, red[1][wave] = n_dense;
+  __syncthreads();
+  if (threadIdx.x == 0u)
+  {
+    unsigned long long u = 0, d = 0;
+    for (uint32_t w = 0; w < 16u; ++w) u += red[0][w], d += red[1][w];
+    sums[0] = carry, sums[1] = u, sums[2] = d;
+  }
+}
+#endif
 } // namespace ws
