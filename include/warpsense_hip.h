@@ -394,6 +394,65 @@ int ws_map_distance_download(ws_map *map, uint32_t *host, size_t capacity, size_
  * line passes of the last call (under WS_DISTANCE_COLUMNS: pass 0, the x pass, the y pass, 0) */
 int ws_debug_distance_timing(ws_map *map, int32_t enable, float ms_out[4]);
 
+/* Ground of a device map: per (x, y) column of a box the one level something can stand on, its sub-voxel height and the largest
+ * height step to the neighbouring columns -- the elevation layer a ground robot plans on.  WS_DISTANCE_COLUMNS models one flat
+ * floor: a ramp is a wall where it enters the height band, a kerb blocks or vanishes with the band, a hole or a stair head reads as
+ * free ground, a table blocks only if the band cuts it.  The TSDF holds what is needed to do better: a zero crossing with free space
+ * above it is a place to stand.  Integers only: the result is exact and the same bytes on every run.
+ *   box: inclusive world voxels [lo, hi] under the box rules of ws_map_distance (both NULL: the whole window; outside the window,
+ *     hi < lo, exactly one NULL or more voxels than the ring holds along an axis: WS_ERR_INVALID).  More than 2^32 - 1 columns:
+ *     WS_ERR_RANGE.
+ *   classes of a voxel: those of ws_map_distance, 0 UNKNOWN, 1 FREE (valid, value >= 0), 2 OCCUPIED (valid, value < 0).  VALID iff
+ *     weight > 0; with WS_GROUND_ANY_WEIGHT iff weight != 0.
+ *   headroom: clear_vox = H, 1 <= H <= 64, else WS_ERR_RANGE.  (The walk goes down a column in steps of 64 voxels and carries ONE
+ *     64-bit word of the step above: headroom of up to 64 voxels above a voxel of a step ends in the step above at the latest.)
+ *   level: voxel z of column (x, y) is a level iff z and z + H lie in the box's z range, class(z) = OCCUPIED, class(z + 1) = FREE and
+ *     class(z + k) = FREE for k = 2 .. H.  With WS_GROUND_UNKNOWN_HEADROOM, UNKNOWN is accepted as well for k = 2 .. H; z + 1 must be
+ *     FREE in every case, because the height needs its value.  Voxels outside the box never count: as with the frontier and the
+ *     distance field, the result of a box is NOT the restriction of a larger box's result to it.
+ *   the level of a column: its lowest level; under WS_GROUND_TOP its highest.  One level per column: a caller who wants one storey
+ *     of several cuts it with the box's z range.
+ *   height: with v0 = value(z) < 0 and v1 = value(z + 1) >= 0, frac = min(255, floor(256 (-v0) / (v1 - v0))) and h = 256 z + frac as
+ *     int64: the zero crossing in 1/256 voxel, between voxel centres.
+ *   class of a column: 1 GROUND if it has a level; else 2 BLOCKED if any voxel of it in the box is OCCUPIED; else 3 VOID if any is
+ *     FREE (a hole, a stair head: seen, and nothing to stand on); else 0 UNKNOWN.
+ *   step, defined for a GROUND column c only: min(65535, max |h(c) - h(n)|) over the up to 8 neighbouring columns n of the box that
+ *     are GROUND; 0 if there is none.
+ *   record, 8 bytes per column in the column order of ws_map_distance (x major, y fastest): int32 z, the level's voxel (0 without a
+ *     level); uint32 w: bits 0..7 frac, bits 8..23 step, bits 30..31 the column's class, the rest 0.  nx ny records.
+ *   counts[4] (may be NULL) receives the columns per class.  A box of zero columns is WS_OK.
+ * Every refusal comes before the first launch and leaves the last result in place.  Synchronises.  The result buffer belongs to the
+ * map, grows on demand, stays valid until the next ws_map_ground on it and is apart from every other query's: neither invalidates
+ * the other.  Read-only on the maps; calls that use the result buffer are serialised inside the library.  Nothing is allocated before
+ * the first call; an allocation that fails returns WS_ERR_HIP and leaves the map usable. */
+#define WS_GROUND_DEFAULT 0u
+#define WS_GROUND_ANY_WEIGHT 1u
+#define WS_GROUND_UNKNOWN_HEADROOM 2u
+#define WS_GROUND_TOP 4u
+#define WS_GROUND_CLASS_UNKNOWN 0u
+#define WS_GROUND_CLASS_GROUND 1u
+#define WS_GROUND_CLASS_BLOCKED 2u
+#define WS_GROUND_CLASS_VOID 3u
+int ws_map_ground(ws_map *map, int which, const int32_t lo[3], const int32_t hi[3], int32_t clear_vox, uint32_t flags, uint64_t counts[4]);
+const void *ws_map_ground_dev(const ws_map *map, size_t *n); /* device memory, n 8-byte records; NULL before the first call (n == 0) */
+/* copies at most `capacity` records (a prefix) and always reports the total in *n_out; host may be NULL */
+int ws_map_ground_download(ws_map *map, void *host, size_t capacity, size_t *n_out);
+/* the box of the last ground result: its first world voxel and its extent (ext[2] saturates at 2^32 - 1); either may be NULL.  No
+ * ground result yet: WS_ERR_INVALID */
+int ws_map_ground_box(ws_map *map, int32_t lo[3], uint32_t ext[3]);
+/* Measurement entry, as ws_debug_distance_timing: ms_out receives the device time of pass 1 (levels) and pass 2 (steps) of the last call */
+int ws_debug_ground_timing(ws_map *map, int32_t enable, float ms_out[2]);
+/* The bridge to the planner: a ws_map_distance(..., WS_DISTANCE_COLUMNS) in every respect -- the same checks of max_dist_vox and of
+ * the record counts, the same line passes, the map's distance result is REPLACED, and the box and flags it publishes let ws_map_reach
+ * treat it as a column map -- except that pass 0 reads the records of the last ws_map_ground instead of the TSDF:
+ *   FREE (1): a GROUND column with step <= max_step_q8 (1/256 voxel).  OCCUPIED (2), a site: BLOCKED, VOID, or GROUND above the step.
+ *   UNKNOWN (0): a site iff WS_DISTANCE_UNKNOWN_OCCUPIED.
+ *   flags: WS_DISTANCE_UNKNOWN_OCCUPIED is the one accepted bit (WS_DISTANCE_COLUMNS is implied, and is what the published flags
+ *     hold); anything else is WS_ERR_INVALID.  No ground result yet: WS_ERR_INVALID.  max_step_q8 outside 0 .. 65535: WS_ERR_RANGE.
+ * The box is that of the ground result (its z range is kept as the published box's).  A refusal launches nothing and leaves the last
+ * distance result in place.  The ground result stays as it is. */
+int ws_map_ground_distance(ws_map *map, int32_t max_step_q8, int32_t max_dist_vox, uint32_t flags, size_t *n_sites);
+
 /* Frontier of a device map: where the known world ends.  The update writes observed free space explicitly (weight > 0, value = tau);
  * a voxel no ray reached keeps weight 0.  The frontier of a box is the set of its observed-free voxels that touch a never-observed
  * voxel of the box, and with WS_FRONTIER_CLUSTERS its connected patches with size, bounding box and coordinate sum -- a planner
@@ -804,6 +863,34 @@ int ws_store_distance_download(ws_store *st, uint32_t *host, size_t capacity, si
  * upload lies in front of it) and of the x, y and z line passes of the last call (under WS_DISTANCE_COLUMNS: pass 0, the x pass, the
  * y pass, 0) */
 int ws_debug_store_distance_timing(ws_store *st, int32_t enable, float ms_out[4]);
+
+/* The ground of the store: ws_map_ground applied to the field of ws_store_distance -- the elevation layer of the whole run -- on the
+ * device, without a chunk leaving HBM.
+ *   field: a voxel of a present chunk holds that chunk's entry; a voxel of an absent chunk is UNKNOWN, whatever fill_entry is.
+ *   rules: everything else is word for word the rule set of ws_map_ground applied to that field: the classes and
+ *     WS_GROUND_ANY_WEIGHT, 1 <= clear_vox <= 64 (else WS_ERR_RANGE), the level and WS_GROUND_UNKNOWN_HEADROOM (under which the unknown
+ *     voxels of an absent chunk inside the box are headroom), the lowest level or WS_GROUND_TOP, height, column class, step, the
+ *     8-byte record, the column order and counts[4].
+ *   box: the box rules of ws_store_distance: inclusive world voxels [lo, hi] anywhere in int32 voxel space, extents formed in 64 bits;
+ *     both NULL: the bounding box of the present chunks, and an empty store is WS_OK with zero records; exactly one NULL, or hi < lo:
+ *     WS_ERR_INVALID.  A box over no present chunk: every column UNKNOWN.
+ *   limits: more than 2^32 - 1 columns is WS_ERR_RANGE (the z extent is bounded only by int32), and so is a box that overlaps 2^19
+ *     present chunks or more.  Unknown flag bits: WS_ERR_INVALID.  Every refusal comes before the first launch and leaves the last
+ *     result in place.  An allocation that fails is WS_ERR_HIP and leaves the store usable.
+ *   consequence: if a window holds the same voxels as the store inside a box, the box lies in that window, and fill_entry has weight
+ *     0, ws_map_ground on that window and box returns the same bytes and the same counts, under every flag combination.
+ *   ordering and result buffer: as for ws_store_distance; the result is apart from every other query's of the store.
+ *   cost: 16 bytes per column of the box for the result and the scratch of pass 2.  Pass 1 follows the present chunks: absent chunks
+ *     are never read and a column is walked only across the z range of the listed chunks. */
+int ws_store_ground(ws_store *st, const int32_t lo[3], const int32_t hi[3], int32_t clear_vox, uint32_t flags, uint64_t counts[4]);
+const void *ws_store_ground_dev(const ws_store *st, size_t *n); /* device memory, n 8-byte records; NULL before the first call (n == 0) */
+int ws_store_ground_download(ws_store *st, void *host, size_t capacity, size_t *n_out); /* as ws_map_ground_download */
+int ws_store_ground_box(ws_store *st, int32_t lo[3], uint32_t ext[3]);                  /* as ws_map_ground_box */
+/* Measurement entry, as ws_debug_ground_timing (the chunk table's upload lies in front of pass 1) */
+int ws_debug_store_ground_timing(ws_store *st, int32_t enable, float ms_out[2]);
+/* ws_map_ground_distance over the last ws_store_ground result of this store, word for word: it replaces the store's distance result,
+ * which ws_store_reach then treats as a column map */
+int ws_store_ground_distance(ws_store *st, int32_t max_step_q8, int32_t max_dist_vox, uint32_t flags, size_t *n_sites);
 
 /* The frontier of the store: ws_map_frontier over the chunks of the global map, wherever they lie -- what the whole run has not
  * covered yet, not what the window has not -- on the device, without a chunk leaving HBM.

@@ -333,6 +333,16 @@ public:
   {
     return global_map_distance(store_, max_dist_vox, unknown_occupied, columns, any_weight, lo, hi);
   }
+  // the ground layer of the chunks, and the column distance field over it (visualization.hpp, ws_store_ground, ws_store_ground_distance)
+  GroundLayer ground(int32_t clear_vox, bool any_weight = false, bool unknown_headroom = false, bool top = false, const rm::Pointi *lo = nullptr,
+                     const rm::Pointi *hi = nullptr)
+  {
+    return global_map_ground(store_, clear_vox, any_weight, unknown_headroom, top, lo, hi);
+  }
+  DistanceField ground_distance(int32_t max_step_q8, int32_t max_dist_vox, bool unknown_occupied = false)
+  {
+    return global_map_ground_distance(store_, max_step_q8, max_dist_vox, unknown_occupied);
+  }
   // where the chunks' known world ends (visualization.hpp, ws_store_frontier)
   Frontier frontier(bool clusters = true, int32_t min_value = 0, bool any_weight = false, const rm::Pointi *lo = nullptr, const rm::Pointi *hi = nullptr)
   {
@@ -893,6 +903,23 @@ public:
     local_map_.window(wlo, whi);
     WS_CHECK(ws_store_save_box(device_global_map_->handle(), gpu_.tsdf().handle(), WS_MAP_AVG, &wlo.x, &whi.x));
     return device_global_map_->distance(max_dist_vox, unknown_occupied, columns, any_weight, lo, hi);
+  }
+  // The ground layer of the averaged map (local_map_ground): one level per column under clear_vox voxels of headroom
+  GroundLayer ground(int32_t clear_vox, bool any_weight = false, bool unknown_headroom = false, bool top = false, const rm::Pointi *lo = nullptr,
+                     const rm::Pointi *hi = nullptr)
+  {
+    return local_map_ground(gpu_.tsdf(), clear_vox, any_weight, unknown_headroom, top, lo, hi);
+  }
+  // The same of everything the run has seen: the window into the device chunks, as global_mesh does, then the ground of the store
+  GroundLayer global_ground(int32_t clear_vox, bool any_weight = false, bool unknown_headroom = false, bool top = false, const rm::Pointi *lo = nullptr,
+                            const rm::Pointi *hi = nullptr)
+  {
+    if (!device_global_map_) throw std::logic_error("global_ground: no DeviceGlobalMap attached");
+    wait_shift();
+    rm::Pointi wlo, whi;
+    local_map_.window(wlo, whi);
+    WS_CHECK(ws_store_save_box(device_global_map_->handle(), gpu_.tsdf().handle(), WS_MAP_AVG, &wlo.x, &whi.x));
+    return device_global_map_->ground(clear_vox, any_weight, unknown_headroom, top, lo, hi);
   }
   // Where the window's known free space ends (local_map_frontier on the averaged map)
   Frontier frontier(bool clusters = true, int32_t min_value = 0, bool any_weight = false, const rm::Pointi *lo = nullptr, const rm::Pointi *hi = nullptr)

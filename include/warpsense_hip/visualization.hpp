@@ -9,6 +9,7 @@
 //   local_map_sample / global_map_sample   (no counterpart)                                   what the map says at given points, over ws_map_sample / ws_store_sample
 //   local_map_distance   (no counterpart: the reference has no distance field)                   a cost map, over ws_map_distance
 //   global_map_distance  (no counterpart)                                                     the cost map of the whole run, over ws_store_distance
+//   local_map_ground / global_map_ground (no counterpart)                                    the elevation layer a ground robot plans on, over ws_map_ground / ws_store_ground
 //   local_map_frontier / global_map_frontier   (no counterpart)                               where the known world ends, over ws_map_frontier / ws_store_frontier
 //   local_map_reach / global_map_reach, local_map_reach_paths / global_map_reach_paths   (no counterpart)   path costs and paths, over ws_map_reach / ws_store_reach
 //   local_map_view_gain / global_map_view_gain   (no counterpart)                             what the sensor would see from candidate poses, over ws_map_view_gain / ws_store_view_gain
@@ -499,6 +500,93 @@ inline DistanceField global_map_distance(ws_store *store, int32_t max_dist_vox, 
   }
   WS_CHECK(ws_store_distance(store, lo ? &lo->x : nullptr, hi ? &hi->x : nullptr, max_dist_vox, flags, &out.sites));
   if (columns) out.extent[2] = 1;
+  size_t n = 0;
+  WS_CHECK(ws_store_distance_download(store, nullptr, 0, &n));
+  out.records.resize(n);
+  WS_CHECK(ws_store_distance_download(store, n ? out.records.data() : nullptr, n, &n));
+  return out;
+}
+
+struct GroundLayer
+{
+  struct Record
+  {
+    int32_t z;  // the level's voxel (0 without a level)
+    uint32_t w; // bits 0..7 frac, bits 8..23 step, bits 30..31 the column's class
+  };
+  int32_t lo[3] = {0, 0, 0};     // the box's first world voxel
+  uint32_t extent[3] = {0, 0, 0}; // nx, ny, nz of the box
+  std::vector<Record> records;    // nx ny columns, x major, y fastest
+  uint64_t counts[4] = {0, 0, 0, 0}; // columns per class: unknown, ground, blocked, void
+  static uint32_t cls(const Record &r) { return r.w >> 30; }
+  static uint32_t frac(const Record &r) { return r.w & 0xffu; }
+  static uint32_t step_q8(const Record &r) { return (r.w >> 8) & 0xffffu; }
+  static int64_t height_q8(const Record &r) { return (int64_t)r.z * 256 + (int64_t)(r.w & 0xffu); }
+  static double height_mm(const Record &r, int resolution) { return (double)height_q8(r) * ((double)resolution / 256.0); }
+};
+
+namespace detail
+{
+inline uint32_t ground_flags(bool any_weight, bool unknown_headroom, bool top)
+{
+  return (any_weight ? WS_GROUND_ANY_WEIGHT : 0u) | (unknown_headroom ? WS_GROUND_UNKNOWN_HEADROOM : 0u) | (top ? WS_GROUND_TOP : 0u);
+}
+} // namespace detail
+
+// The ground layer of `which` (the rules: warpsense_hip.h at ws_map_ground) inside the inclusive world-voxel box [lo, hi] (both nullptr:
+// the whole window): per column the lowest (top: the highest) occupied voxel under a free one with clear_vox (1 .. 64) voxels of
+// headroom, its sub-voxel height and the largest height step to the neighbouring ground columns.
+inline GroundLayer local_map_ground(cuda::TSDFCuda &tsdf, int32_t clear_vox, bool any_weight = false, bool unknown_headroom = false, bool top = false,
+                                    const rmagine::Pointi *lo = nullptr, const rmagine::Pointi *hi = nullptr, int which = WS_MAP_AVG)
+{
+  GroundLayer out;
+  WS_CHECK(ws_map_ground(tsdf.handle(), which, lo ? &lo->x : nullptr, hi ? &hi->x : nullptr, clear_vox, detail::ground_flags(any_weight, unknown_headroom, top), out.counts));
+  WS_CHECK(ws_map_ground_box(tsdf.handle(), out.lo, out.extent));
+  size_t n = 0;
+  WS_CHECK(ws_map_ground_download(tsdf.handle(), nullptr, 0, &n));
+  out.records.resize(n);
+  WS_CHECK(ws_map_ground_download(tsdf.handle(), n ? out.records.data() : nullptr, n, &n));
+  return out;
+}
+
+// The column distance field over the last local_map_ground of the map (ws_map_ground_distance): it replaces the map's distance
+// result, and local_map_reach then plans over it.  max_step_q8: the largest step of a free column in 1/256 voxel.
+inline DistanceField local_map_ground_distance(cuda::TSDFCuda &tsdf, int32_t max_step_q8, int32_t max_dist_vox, bool unknown_occupied = false)
+{
+  DistanceField out;
+  uint32_t ext[3] = {0, 0, 0};
+  WS_CHECK(ws_map_ground_distance(tsdf.handle(), max_step_q8, max_dist_vox, unknown_occupied ? WS_DISTANCE_UNKNOWN_OCCUPIED : 0u, &out.sites));
+  WS_CHECK(ws_map_ground_box(tsdf.handle(), nullptr, ext));
+  out.extent[0] = (int32_t)ext[0], out.extent[1] = (int32_t)ext[1], out.extent[2] = 1;
+  size_t n = 0;
+  WS_CHECK(ws_map_distance_download(tsdf.handle(), nullptr, 0, &n));
+  out.records.resize(n);
+  WS_CHECK(ws_map_distance_download(tsdf.handle(), n ? out.records.data() : nullptr, n, &n));
+  return out;
+}
+
+// The same two over the global map in device memory (ws_store_ground, ws_store_ground_distance): the box need not lie in any window
+// (both nullptr: the bounding box of the present chunks); voxels of absent chunks are unknown.  (app.hpp adds DeviceGlobalMap::ground.)
+inline GroundLayer global_map_ground(ws_store *store, int32_t clear_vox, bool any_weight = false, bool unknown_headroom = false, bool top = false,
+                                     const rmagine::Pointi *lo = nullptr, const rmagine::Pointi *hi = nullptr)
+{
+  GroundLayer out;
+  WS_CHECK(ws_store_ground(store, lo ? &lo->x : nullptr, hi ? &hi->x : nullptr, clear_vox, detail::ground_flags(any_weight, unknown_headroom, top), out.counts));
+  WS_CHECK(ws_store_ground_box(store, out.lo, out.extent));
+  size_t n = 0;
+  WS_CHECK(ws_store_ground_download(store, nullptr, 0, &n));
+  out.records.resize(n);
+  WS_CHECK(ws_store_ground_download(store, n ? out.records.data() : nullptr, n, &n));
+  return out;
+}
+
+inline DistanceField global_map_ground_distance(ws_store *store, int32_t max_step_q8, int32_t max_dist_vox, bool unknown_occupied = false)
+{
+  DistanceField out;
+  uint32_t ext[3] = {0, 0, 0};
+  WS_CHECK(ws_store_ground_distance(store, max_step_q8, max_dist_vox, unknown_occupied ? WS_DISTANCE_UNKNOWN_OCCUPIED : 0u, &out.sites));
+  WS_CHECK(ws_store_ground_box(store, nullptr, ext));
+  out.extent[0] = (int32_t)ext[0], out.extent[1] = (int32_t)ext[1], out.extent[2] = 1;
   size_t n = 0;
   WS_CHECK(ws_store_distance_download(store, nullptr, 0, &n));
   out.records.resize(n);

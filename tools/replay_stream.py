@@ -5,6 +5,7 @@ sliding TSDF map @ 5 cm, one MI355X): sensor clouds in float metres -> device pr
     python tools/replay_stream.py --map 1024 --scans 30 [--h5 /tmp/stream.h5] [--async-shift | --device-global-map] [--surface-ply DIR [--surface-every N]] [--mesh-ply DIR] [--global-packed FILE.wspk]
                                    [--raycast-ply DIR] [--distance-npy DIR [--distance-m M]] [--global-distance-npy FILE [--global-distance-m M]]
                                    [--moving-sweeps] [--deskew] [--frontier-ply DIR] [--global-frontier-ply FILE] [--reach-ply DIR [--reach-clearance-m M]]
+                                   [--ground-npy DIR [--ground-height-m M]]
 
 Prints one JSON line: scans/s over the stream and the mean per-stage times (the reference's RuntimeEvaluator
 forms "preprocess", "tsdf", "registration", "total")."""
@@ -81,6 +82,10 @@ def main():
                     "window (TSDFMapping.reachable_frontier: ws_map_distance, ws_map_reach, ws_map_frontier, ws_map_reach_lookup_dev, ws_map_reach_paths) as "
                     "binary little-endian PLY (vertices with path number and cost, edges) into DIR")
     ap.add_argument("--reach-clearance-m", type=float, default=0.2, metavar="M", help="... that keep M metres from the obstacles")
+    ap.add_argument("--ground-npy", default=None, metavar="DIR", help="after every TSDF update: the ground layer of the window (TSDFMapping.ground, ws_map_ground) "
+                    "into DIR as ground_height_NNNNN.npy (millimetres, float64, NaN without a level) and ground_class_NNNNN.npy (uint8: 0 unknown, 1 ground, 2 blocked, "
+                    "3 void), shaped (nx, ny) like the window")
+    ap.add_argument("--ground-height-m", type=float, default=1.0, metavar="M", help="... under M metres of headroom (at most 64 voxels)")
     ap.add_argument("--next-view-csv", default=None, metavar="FILE", help="after every TSDF update: the next best view among the reachable frontier clusters of the "
                     "window (TSDFMapping.next_best_view: reachable_frontier, ws_map_view_gain, rank_views) as one line of FILE: scan number, the winner's goal "
                     "voxel x y z, its path cost, its unknown_k2, the number of candidates (-1 -1 -1, 4294967295 and 0 without a candidate); the "
@@ -165,6 +170,9 @@ def main():
     reach = {"files": 0, "clusters": 0, "reachable": 0, "rounds": 0, "seconds": 0.0}
     if args.reach_ply:
         os.makedirs(args.reach_ply, exist_ok=True)
+    ground = {"files": 0, "ground": 0, "blocked": 0, "void": 0, "seconds": 0.0}
+    if args.ground_npy:
+        os.makedirs(args.ground_npy, exist_ok=True)
     next_view = {"lines": 0, "candidates": 0, "seconds": 0.0}
     next_view_file = None
     if args.next_view_csv:
@@ -208,6 +216,14 @@ def main():
                 reach["files"] += 1
             reach["clusters"], reach["reachable"], reach["rounds"] = int(len(got["table"])), int(len(got["reachable"])), int(app.gpu_.last_reach["rounds"])
             reach["seconds"] += time.perf_counter() - ts
+        if args.ground_npy and app.n_updates > updates_seen:  # after every update of the map: where the robot can stand
+            ts = time.perf_counter()
+            g = app.gpu_.ground(robot_height_m=args.ground_height_m)
+            np.save(os.path.join(args.ground_npy, f"ground_height_{k + 1:05d}.npy"), g.height_mm(args.res))
+            np.save(os.path.join(args.ground_npy, f"ground_class_{k + 1:05d}.npy"), g.cls)
+            ground["ground"], ground["blocked"], ground["void"] = int(g.counts[1]), int(g.counts[2]), int(g.counts[3])
+            ground["files"] += 1
+            ground["seconds"] += time.perf_counter() - ts
         if next_view_file is not None and app.n_updates > updates_seen:  # after every update of the map: where to look next
             ts = time.perf_counter()
             pose_m = app.pose_.astype(np.float64).copy()
@@ -361,6 +377,7 @@ def main():
                       "global_packed": global_packed,
                       "frontier_ply": frontier if args.frontier_ply else None,
                       "reach_ply": reach if args.reach_ply else None,
+                      "ground_npy": ground if args.ground_npy else None,
                       "next_view_csv": next_view if args.next_view_csv else None,
                       "global_frontier_ply": global_frontier,
                       "global_raycast_ply": global_raycast,

@@ -19,6 +19,8 @@ from .pyramid import CoarsenStats, MapPyramid, parents_of  # noqa: F401
 from ._lib import WS_COARSEN_DEFAULT  # noqa: F401
 from .changes import CHANGE_RECORD, ChangeResult, ChangeStats, write_changes_ply  # noqa: F401
 from .pack import PackedMap  # noqa: F401
+from .ground import GROUND_RECORD, GroundResult, max_step_q8  # noqa: F401
+from ._lib import WS_GROUND_ANY_WEIGHT, WS_GROUND_DEFAULT, WS_GROUND_TOP, WS_GROUND_UNKNOWN_HEADROOM  # noqa: F401
 from ._lib import WS_CHANGES_APPEARED, WS_CHANGES_CLUSTERS, WS_CHANGES_DEFAULT, WS_CHANGES_VANISHED  # noqa: F401
 
 __all__ = [n for n in dir() if not n.startswith("_")]

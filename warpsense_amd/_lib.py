@@ -59,6 +59,8 @@ EXPORTS = [
     "ws_store_coarsen", "ws_store_parents_of", "ws_debug_store_coarsen_timing",
     "ws_store_changes", "ws_store_changes_records_dev", "ws_store_changes_labels_dev", "ws_store_changes_clusters_dev", "ws_store_changes_download",
     "ws_debug_store_changes_timing",
+    "ws_map_ground", "ws_map_ground_dev", "ws_map_ground_download", "ws_map_ground_box", "ws_debug_ground_timing", "ws_map_ground_distance",
+    "ws_store_ground", "ws_store_ground_dev", "ws_store_ground_download", "ws_store_ground_box", "ws_debug_store_ground_timing", "ws_store_ground_distance",
     "ws_store_pack", "ws_store_pack_headers_dev", "ws_store_pack_payload_dev", "ws_store_pack_download", "ws_store_unpack", "ws_store_unpack_dev",
     "ws_pack_check", "ws_pack_expand_chunk", "ws_pack_chunk", "ws_debug_store_pack_timing",
 ]
@@ -69,6 +71,8 @@ WS_SAMPLE_DEFAULT, WS_SAMPLE_ANY_WEIGHT, WS_SAMPLE_GRADIENT = 0, 1, 2
 WS_SAMPLE_SELECT_UNKNOWN, WS_SAMPLE_SELECT_FREE, WS_SAMPLE_SELECT_SURFACE, WS_SAMPLE_SELECT_INSIDE = 4, 8, 16, 32
 SAMPLE_CLASSES = ("unknown", "free", "surface", "inside")  # class c of a sample record; WS_SAMPLE_SELECT_* is 4 << c
 WS_DISTANCE_DEFAULT, WS_DISTANCE_ANY_WEIGHT, WS_DISTANCE_UNKNOWN_OCCUPIED, WS_DISTANCE_COLUMNS = 0, 1, 2, 4
+WS_GROUND_DEFAULT, WS_GROUND_ANY_WEIGHT, WS_GROUND_UNKNOWN_HEADROOM, WS_GROUND_TOP = 0, 1, 2, 4
+GROUND_CLASSES = ("unknown", "ground", "blocked", "void")  # class c of a ground record
 WS_FRONTIER_DEFAULT, WS_FRONTIER_ANY_WEIGHT, WS_FRONTIER_CLUSTERS = 0, 1, 2
 WS_REACH_DEFAULT, WS_REACH_UNKNOWN_FREE, WS_REACH_UNREACHABLE = 0, 1, 0xFFFFFFFF
 WS_GAIN_DEFAULT, WS_GAIN_ANY_WEIGHT, WS_GAIN_RAYS = 0, 1, 2
@@ -217,6 +221,13 @@ def load() -> C.CDLL:
     L.ws_map_distance_dev.restype = vp
     L.ws_map_distance_download.argtypes = [vp, vp, sz, P(sz)]
     L.ws_debug_distance_timing.argtypes = [vp, i32, vp]
+    L.ws_map_ground.argtypes = [vp, C.c_int, vp, vp, i32, u32, vp]
+    L.ws_map_ground_dev.argtypes = [vp, P(sz)]
+    L.ws_map_ground_dev.restype = vp
+    L.ws_map_ground_download.argtypes = [vp, vp, sz, P(sz)]
+    L.ws_map_ground_box.argtypes = [vp, vp, vp]
+    L.ws_debug_ground_timing.argtypes = [vp, i32, vp]
+    L.ws_map_ground_distance.argtypes = [vp, i32, i32, u32, P(sz)]
     L.ws_map_frontier.argtypes = [vp, C.c_int, vp, vp, i32, u32, P(sz), P(sz)]
     L.ws_store_frontier.argtypes = [vp, vp, vp, i32, u32, P(sz), P(sz)]
     for owner in ("map", "store"):
@@ -361,6 +372,13 @@ def load() -> C.CDLL:
     L.ws_store_distance_dev.restype = vp
     L.ws_store_distance_download.argtypes = [vp, vp, sz, P(sz)]
     L.ws_debug_store_distance_timing.argtypes = [vp, i32, vp]
+    L.ws_store_ground.argtypes = [vp, vp, vp, i32, u32, vp]
+    L.ws_store_ground_dev.argtypes = [vp, P(sz)]
+    L.ws_store_ground_dev.restype = vp
+    L.ws_store_ground_download.argtypes = [vp, vp, sz, P(sz)]
+    L.ws_store_ground_box.argtypes = [vp, vp, vp]
+    L.ws_debug_store_ground_timing.argtypes = [vp, i32, vp]
+    L.ws_store_ground_distance.argtypes = [vp, i32, i32, u32, P(sz)]
     L.ws_store_raycast.argtypes = [vp, vp, vp, vp, vp, sz, i32, i32, u32, P(sz)]
     L.ws_store_raycast_dev.argtypes = [vp, vp, vp, vp, vp, sz, i32, i32, u32, P(sz)]
     L.ws_store_raycast_records_dev.argtypes = [vp, P(sz)]

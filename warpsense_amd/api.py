@@ -28,6 +28,7 @@ This module only gathers the names; the code lives in one module per subsystem, 
     merge.py         merge_map and align_map of TSDFMapping
     pyramid.py       CoarsenStats, parents_of, MapPyramid, global_pyramid           (api_store)
     changes.py       ChangeStats, ChangeResult, write_changes_ply: where two maps differ (api_store)
+    ground.py        GROUND_RECORD, GroundResult: levels, heights and steps of the ground  (api_query, api_store)
     pack.py          PackedMap: packed snapshots of the global map and their .wspk file (api_pack)
     device_map.py    DeviceMap, LocalMap, DeviceMapMemWrapper, TSDFCuda             (api_map, api_tsdf)
     registration.py  RegistrationCuda, batch_best, candidate_poses                  (api_reg)
@@ -52,3 +53,4 @@ from .fuse import FuseStats, fuse_pose, pose_transform  # noqa: F401
 from .pyramid import CoarsenStats, MapPyramid, parents_of  # noqa: F401
 from .changes import CHANGE_RECORD, ChangeResult, ChangeStats, write_changes_ply  # noqa: F401
 from .pack import PackedMap  # noqa: F401
+from .ground import GROUND_RECORD, GroundResult, max_step_q8  # noqa: F401

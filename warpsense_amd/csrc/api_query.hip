@@ -378,6 +378,106 @@ int ws_debug_distance_timing(ws_map *m, int32_t enable, float ms_out[4])
   return query_timing(m->ctx->stream, m->dist.timer, enable, ms_out, DIST_PAIRS, 4);
 }
 
+// ---- ground: the same beside ground_check and ground_run.  The window and the store differ in pass 1 only.
+const void *ws::ground_dev(const GroundResult *q, size_t *n)
+{
+  if (n) *n = q ? q->n : 0;
+  return q && q->n ? q->rec.p : nullptr;
+}
+
+int ws::ground_download(const GroundResult &q, hipStream_t s, void *host, size_t capacity, size_t *n_out)
+{
+  *n_out = q.n;
+  const size_t k = host ? std::min(capacity, q.n) : 0;
+  if (k == 0) return WS_OK;
+  WS_HIP(hipMemcpyAsync(host, q.rec.p, k * 8, hipMemcpyDeviceToHost, s));
+  WS_HIP(hipStreamSynchronize(s));
+  return WS_OK;
+}
+
+int ws::ground_box(const GroundResult &q, const char *name, int32_t lo[3], uint32_t ext[3])
+{
+  if (!q.have) return invalid(std::string(name) + ": no ground result yet");
+  for (int k = 0; k < 3; ++k)
+  {
+    if (lo) lo[k] = q.lo[k];
+    if (ext) ext[k] = q.ext[k];
+  }
+  return WS_OK;
+}
+
+// ---- ground: the elevation layer of a device map, map_ground.hip (the rules are stated in warpsense_hip.h)
+int ws_map_ground(ws_map *m, int which, const int32_t lo[3], const int32_t hi[3], int32_t clear_vox, uint32_t flags, uint64_t counts[4])
+{
+  std::unique_lock<std::mutex> lock;
+  int32_t l[3], ext[3];
+  uint32_t e32[3];
+  size_t n = 0;
+  WS_TRY(ground_check(
+      "ws_map_ground", !m || (which != WS_MAP_AVG && which != WS_MAP_NEW), lo, hi, clear_vox, flags,
+      [&](uint64_t e[3]) {
+        WS_SETTLE(m);
+        lock = std::unique_lock<std::mutex>(m->ground.mu);
+        WS_TRY(m->ground.timer.arm());
+        WS_TRY(resolve_box(m, which, lo, hi, true, "ws_map_ground", l, ext)); // ext[0] ext[1] < 2^31, ext[2] <= 2^20
+        for (int k = 0; k < 3; ++k) e[k] = (uint64_t)ext[k];
+        return (int)WS_OK;
+      },
+      e32, &n));
+  GroundResult &q = m->ground;
+  WS_TRY(ground_run(q, m->ctx->stream, l, e32, n, counts, [&] { return launch_ground_levels(m, q, which, l, ext, clear_vox, flags); }));
+  return map_take_error(m);
+}
+
+const void *ws_map_ground_dev(const ws_map *m, size_t *n) { return ground_dev(m ? &m->ground : nullptr, n); }
+
+int ws_map_ground_download(ws_map *m, void *host, size_t capacity, size_t *n_out)
+{
+  if (!m || !n_out) return invalid("ws_map_ground_download: NULL argument");
+  std::lock_guard<std::mutex> lock(m->ground.mu);
+  return ground_download(m->ground, m->ctx->stream, host, capacity, n_out);
+}
+
+int ws_map_ground_box(ws_map *m, int32_t lo[3], uint32_t ext[3])
+{
+  if (!m) return invalid("ws_map_ground_box: map is NULL");
+  std::lock_guard<std::mutex> lock(m->ground.mu);
+  return ground_box(m->ground, "ws_map_ground_box", lo, ext);
+}
+
+int ws_debug_ground_timing(ws_map *m, int32_t enable, float ms_out[2])
+{
+  if (!m) return invalid("ws_debug_ground_timing: map is NULL");
+  std::lock_guard<std::mutex> lock(m->ground.mu);
+  return query_timing(m->ctx->stream, m->ground.timer, enable, ms_out, GROUND_PAIRS, 2);
+}
+
+// the bridge to the planner: a column distance call whose pass 0 reads the last ground result (ground.mu, then dist.mu)
+int ws_map_ground_distance(ws_map *m, int32_t max_step_q8, int32_t max_dist_vox, uint32_t flags, size_t *n_sites)
+{
+  std::unique_lock<std::mutex> ground_lock, lock;
+  int32_t l[3] = {0, 0, 0};
+  uint32_t e32[3];
+  size_t n = 0;
+  WS_TRY(ground_distance_check(
+      "ws_map_ground_distance", !m, max_step_q8, max_dist_vox, flags,
+      [&](uint64_t e[3]) {
+        WS_SETTLE(m);
+        ground_lock = std::unique_lock<std::mutex>(m->ground.mu);
+        lock = std::unique_lock<std::mutex>(m->dist.mu);
+        if (!m->ground.have) return invalid("ws_map_ground_distance: no ground result yet (the call runs on the records of the last ws_map_ground)");
+        WS_TRY(m->dist.timer.arm());
+        for (int k = 0; k < 3; ++k) e[k] = m->ground.n ? (uint64_t)m->ground.ext[k] : 0u, l[k] = m->ground.lo[k];
+        return (int)WS_OK;
+      },
+      e32, &n));
+  DistResult &q = m->dist;
+  const uint32_t dflags = flags | WS_DISTANCE_COLUMNS;
+  WS_TRY(distance_run(q, m->ctx->stream, l, e32, max_dist_vox, dflags, n, n_sites,
+                      [&] { return launch_ground_sites(m->ctx->stream, m->ground, q, (uint32_t)max_step_q8, max_dist_vox, dflags); }));
+  return map_take_error(m);
+}
+
 // ---- frontier: what the host core of ws_api.h (frontier_run) needs beside it, for the window of a map here and for the chunks of the
 // store in api_store.hip
 int ws::frontier_check(const char *name, bool bad, const int32_t *lo, const int32_t *hi, int32_t min_value, uint32_t flags)

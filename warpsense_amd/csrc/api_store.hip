@@ -864,6 +864,92 @@ int ws_debug_store_distance_timing(ws_store *st, int32_t enable, float ms_out[4]
   return query_timing(st->ctx->stream, st->dist.timer, enable, ms_out, DIST_PAIRS, 4);
 }
 
+// ---- the ground of the store: the rules and the host flow of ws_map_ground over the chunks, store_ground.hip
+int ws_store_ground(ws_store *st, const int32_t lo[3], const int32_t hi[3], int32_t clear_vox, uint32_t flags, uint64_t counts[4])
+{
+  std::unique_lock<std::mutex> lock;
+  StoreDistCall c;
+  uint32_t ext[3];
+  size_t n = 0;
+  WS_TRY(ground_check(
+      "ws_store_ground", !st, lo, hi, clear_vox, flags,
+      [&](uint64_t e[3]) {
+        WS_TRY(store_query_box(st, "ws_store_ground", lo, hi, false, lock, c.lo, c.hi));
+        WS_TRY(st->ground.timer.arm());
+        if (c.lo[0] > c.hi[0]) return (int)WS_OK; // no box and no chunk: zero records
+        for (int k = 0; k < 3; ++k) e[k] = (uint64_t)((int64_t)c.hi[k] - (int64_t)c.lo[k]) + 1u;
+        return (int)WS_OK;
+      },
+      ext, &n));
+  ws_store::Ground &q = st->ground;
+  hipStream_t s = st->ctx->stream;
+  // the present chunks the box overlaps, and the z range they cover inside it
+  std::vector<StoreRaySlot> listed;
+  if (n) store_list(st, c.lo, c.hi, listed);
+  if (listed.size() >= (1u << 19)) return range_error("ws_store_ground", ": the box overlaps 2^19 present chunks or more");
+  c.n_chunks = (uint32_t)listed.size();
+  c.nx = ext[0], c.ny = ext[1];
+  c.zlo = 1, c.zhi = 0;
+  if (c.n_chunks)
+  {
+    c.zlo = INT32_MAX, c.zhi = INT32_MIN;
+    for (const StoreRaySlot &e : listed) c.zlo = std::min(c.zlo, e.cz * STORE_CS), c.zhi = std::max(c.zhi, e.cz * STORE_CS + STORE_CS - 1);
+    c.zlo = std::max(c.zlo, c.lo[2]), c.zhi = std::min(c.zhi, c.hi[2]);
+  }
+  return store_enqueued(st, ground_run(q, s, c.lo, ext, n, counts, [&] {
+    if (store_lookup_places(listed.size()) > q.table_host.cap) WS_HIP(hipStreamSynchronize(s));
+    WS_TRY(store_lookup_fill(q.table_host, q.table_dev, listed));
+    return launch_store_ground_levels(st, q, c, clear_vox, flags);
+  }));
+}
+
+const void *ws_store_ground_dev(const ws_store *st, size_t *n) { return ground_dev(st ? &st->ground : nullptr, n); }
+
+int ws_store_ground_download(ws_store *st, void *host, size_t capacity, size_t *n_out)
+{
+  if (!st || !n_out) return invalid("ws_store_ground_download: NULL argument");
+  std::lock_guard<std::mutex> lock(st->mu);
+  return ground_download(st->ground, st->ctx->stream, host, capacity, n_out);
+}
+
+int ws_store_ground_box(ws_store *st, int32_t lo[3], uint32_t ext[3])
+{
+  if (!st) return invalid("ws_store_ground_box: store is NULL");
+  std::lock_guard<std::mutex> lock(st->mu);
+  return ground_box(st->ground, "ws_store_ground_box", lo, ext);
+}
+
+int ws_debug_store_ground_timing(ws_store *st, int32_t enable, float ms_out[2])
+{
+  if (!st) return invalid("ws_debug_store_ground_timing: store is NULL");
+  std::lock_guard<std::mutex> lock(st->mu);
+  return query_timing(st->ctx->stream, st->ground.timer, enable, ms_out, GROUND_PAIRS, 2);
+}
+
+// the bridge to the planner: a column distance call whose pass 0 reads the last ground result of the store
+int ws_store_ground_distance(ws_store *st, int32_t max_step_q8, int32_t max_dist_vox, uint32_t flags, size_t *n_sites)
+{
+  std::unique_lock<std::mutex> lock;
+  int32_t l[3] = {0, 0, 0};
+  uint32_t ext[3];
+  size_t n = 0;
+  WS_TRY(ground_distance_check(
+      "ws_store_ground_distance", !st, max_step_q8, max_dist_vox, flags,
+      [&](uint64_t e[3]) {
+        lock = std::unique_lock<std::mutex>(st->mu);
+        if (!st->ground.have) return invalid("ws_store_ground_distance: no ground result yet (the call runs on the records of the last ws_store_ground)");
+        WS_TRY(st->dist.timer.arm());
+        for (int k = 0; k < 3; ++k) e[k] = st->ground.n ? (uint64_t)st->ground.ext[k] : 0u, l[k] = st->ground.lo[k];
+        return (int)WS_OK;
+      },
+      ext, &n));
+  ws_store::Dist &q = st->dist;
+  hipStream_t s = st->ctx->stream;
+  const uint32_t dflags = flags | WS_DISTANCE_COLUMNS;
+  return store_enqueued(st, distance_run(q, s, l, ext, max_dist_vox, dflags, n, n_sites,
+                                         [&] { return launch_ground_sites(s, st->ground, q, (uint32_t)max_step_q8, max_dist_vox, dflags); }));
+}
+
 int ws_debug_store_raycast_table(const int32_t *keys_slots, size_t n, int32_t *table, size_t capacity_places, size_t *n_places)
 {
   if ((n && table && !keys_slots) || !n_places || n >= (1u << 19)) return invalid("ws_debug_store_raycast_table: bad argument");

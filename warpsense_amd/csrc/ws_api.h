@@ -316,6 +316,68 @@ int distance_run(DistResult &q, hipStream_t s, const int32_t lo[3], const uint32
   return WS_OK;
 }
 
+// ---- ground (map_ground.hip for the window of a map, store_ground.hip for the chunks of the store): the checks and the flow of a
+// ground call, `bad` and box(e) as for distance_check, and the check of the bridge to the distance field, whose flow is distance_run.
+const void *ground_dev(const GroundResult *q, size_t *n);
+int ground_download(const GroundResult &q, hipStream_t s, void *host, size_t capacity, size_t *n_out);
+int ground_box(const GroundResult &q, const char *name, int32_t lo[3], uint32_t ext[3]);
+constexpr int GROUND_PAIRS[2][2] = {{0, 1}, {1, 2}};
+
+template <typename Box>
+int ground_check(const char *name, bool bad, const int32_t *lo, const int32_t *hi, int32_t clear_vox, uint32_t flags, Box box, uint32_t ext[3], size_t *n)
+{
+  const uint32_t known = WS_GROUND_ANY_WEIGHT | WS_GROUND_UNKNOWN_HEADROOM | WS_GROUND_TOP;
+  if (bad || (flags & ~known) || ((lo == nullptr) != (hi == nullptr))) return invalid(std::string(name) + ": bad argument");
+  if (clear_vox < 1 || clear_vox > GROUND_MAX_CLEAR) return range_error(name, ": clear_vox must be 1 .. 64 (a step of the column walk carries one 64-bit word of the step above)");
+  uint64_t e[3] = {0, 0, 0};
+  WS_TRY(box(e));
+  const uint64_t n_cols = e[0] > 0xffffffffull || e[1] > 0xffffffffull ? ~0ull : e[0] * e[1];
+  if (n_cols > 0xffffffffull) return range_error(name, ": more than 2^32 - 1 columns");
+  for (int k = 0; k < 3; ++k) ext[k] = (uint32_t)std::min<uint64_t>(e[k], 0xffffffffull);
+  *n = e[2] ? (size_t)n_cols : 0;
+  return WS_OK;
+}
+
+// The flow of a ground call whose arguments have passed ground_check, from "the old result is dropped" to the publish.  pass1()
+// enqueues the source's levels into q.lvl and returns at once.
+template <typename Pass1> int ground_run(GroundResult &q, hipStream_t s, const int32_t lo[3], const uint32_t ext[3], size_t n, uint64_t counts[4], Pass1 pass1)
+{
+  if (counts) counts[0] = counts[1] = counts[2] = counts[3] = 0;
+  q.n = 0; // (whatever happens from here on, the old result is gone: its buffers may be replaced)
+  q.have = false;
+  for (int k = 0; k < 3; ++k) q.lo[k] = n ? lo[k] : 0, q.ext[k] = n ? ext[k] : 0u;
+  if (n == 0)
+  {
+    q.have = true;
+    return WS_OK;
+  }
+  WS_TRY(q.counts.alloc(4));
+  if (n > q.lvl.cap || n > q.rec.cap)
+  {
+    WS_HIP(hipStreamSynchronize(s));
+    WS_TRY(q.lvl.grow(n, 8));
+    WS_TRY(q.rec.grow(n, 8));
+  }
+  WS_TRY(pass1());
+  WS_TRY(ground_steps(s, q, ext[0], ext[1]));
+  WS_TRY(q.counts.fetch(s, 4));
+  WS_HIP(hipStreamSynchronize(s));
+  q.n = n;
+  q.have = true;
+  for (int c = 0; c < 4 && counts; ++c) counts[c] = (uint64_t)q.counts.host[c];
+  return WS_OK;
+}
+
+// The argument check of ws_*_ground_distance: its own refusals, then those of a distance call under WS_DISTANCE_COLUMNS.  box(e):
+// the locks, the look at the ground result ("none yet" is the entry point's refusal) and its extents.
+template <typename Box>
+int ground_distance_check(const char *name, bool bad, int32_t max_step_q8, int32_t R, uint32_t flags, Box box, uint32_t ext[3], size_t *n)
+{
+  if (bad || (flags & ~WS_DISTANCE_UNKNOWN_OCCUPIED)) return invalid(std::string(name) + ": bad argument");
+  if (max_step_q8 < 0 || max_step_q8 > 65535) return range_error(name, ": max_step_q8 must be 0 .. 65535 (the step of a ground record)");
+  return distance_check(name, false, nullptr, nullptr, R, flags | WS_DISTANCE_COLUMNS, box, ext, n);
+}
+
 // ---- frontier (map_frontier.hip for the window of a map, store_frontier.hip for the chunks of the store): its extraction is the
 // flow of a surface call, its clustering works on the records alone.  frontier_check: the refusals that come before the lock and the
 // box, `bad` as above.  frontier_run: grow(), count() and emit(cap) are those of surface_run.

@@ -416,6 +416,22 @@ struct DistResult
   uint32_t flags = 0;
   void release() { timer.release(), sites.release(), have = false, n = 0; for (DevBuf *b : {&rec, &plane}) b->release(); }
 };
+// ... and a ground call (ws_map::Ground, ws_store::Ground; the one flow is ground_run in ws_api.h, the rules are in ws_ground.h)
+constexpr int32_t GROUND_MAX_CLEAR = 64;         // clear_vox: a step of the column walk carries ONE 64-bit word of the step above (ws_ground.h)
+constexpr uint32_t GROUND_PER_LAUNCH = 1u << 24; // columns of one launch of a ground pass
+struct GroundResult
+{
+  QueryTimer timer;                    // 0 pass 1 (levels) 1 pass 2 (steps) 2
+  DevBuf lvl, rec;                     // 8 bytes per column: the records of pass 1 (step 0), and the records of the result
+  DevCounter counts;                   // columns per class [4]
+  size_t n = 0;                        // records of the last call
+  // what ws_map_ground_distance / ws_store_ground_distance need of the last call beside its records: `have` once a call has
+  // succeeded (n may be 0), and its box (first voxel and extent; ext[2] saturates at 2^32 - 1)
+  bool have = false;
+  int32_t lo[3] = {0, 0, 0};
+  uint32_t ext[3] = {0, 0, 0};
+  void release() { timer.release(), counts.release(), have = false, n = 0; for (DevBuf *b : {&lvl, &rec}) b->release(); }
+};
 // ... and a sample call (ws_map::Sample, ws_store::Sample; the one flow is sample_run in ws_api.h)
 struct SampleResult
 {
@@ -565,6 +581,10 @@ struct ws_map
   {
     std::mutex mu;
   } dist;
+  struct Ground : ws::GroundResult // ws_map_ground (map_ground.hip); ws_map_ground_distance holds mu, then dist.mu
+  {
+    std::mutex mu;
+  } ground;
   struct Sample : ws::SampleResult // ws_map_sample (map_sample.hip)
   {
     std::mutex mu;
@@ -613,7 +633,7 @@ struct ws_map
                           &tile_list, &rec, &big_keys, &block_stats, &counters, &box_stage, &shift_stage_dev})
       b->release();
     for (ws::HostBlock *b : {&counters_host, &status, &shift_stage_host}) b->release();
-    surf.release(), mesh.release(), ray.release(), dist.release(), sample.release(), frontier.release(), reach.release(), gain.release();
+    surf.release(), mesh.release(), ray.release(), dist.release(), ground.release(), sample.release(), frontier.release(), reach.release(), gain.release();
   }
 };
 
@@ -755,6 +775,12 @@ struct ws_store
     ws::DevBuf table_dev;                // ... and the copy the kernel reads
     void release() { DistResult::release(), table_host.release(), table_dev.release(); }
   } dist;
+  struct Ground : ws::GroundResult // ws_store_ground (store_ground.hip)
+  {
+    ws::HostBlock table_host;            // StoreRaySlot, pinned: the call's chunk lookup; free again when the call returns, which synchronises
+    ws::DevBuf table_dev;                // ... and the copy the kernel reads
+    void release() { GroundResult::release(), table_host.release(), table_dev.release(); }
+  } ground;
   struct Sample : ws::SampleResult // ws_store_sample (store_sample.hip)
   {
     ws::HostBlock table_host;            // StoreRaySlot, pinned: the call's chunk lookup; free again when the call returns, which synchronises
@@ -822,6 +848,7 @@ struct ws_store
     mesh.release();
     ray.release();
     dist.release();
+    ground.release();
     sample.release();
     for (ws::DevBuf &b : segs) b.release();
     segs.clear(), seg_ptr.clear();
@@ -898,6 +925,12 @@ int launch_sample(ws_map *m, SampleResult &q, int which, const int32_t *pts_dev,
 constexpr uint32_t DIST_MAX_LINE = 65535u * 256u;
 int launch_dist_classify(ws_map *m, DistResult &q, int which, const int32_t lo[3], const int32_t ext[3], int32_t R, uint32_t flags);
 int dist_passes(hipStream_t s, QueryTimer &t, uint32_t *rec, uint16_t *plane, const uint32_t ext[3], int32_t R, uint32_t flags);
+// map_ground.hip: pass 1 over the ring (it clears q.counts.dev and marks events 0, 1); pass 2 over the records of pass 1, of a window
+// or of the store alike (events 1, 2); and pass 0 of ws_*_ground_distance over the records of a ground result: the classes and g0 of
+// a column distance field (it clears d.sites.dev and marks events 0, 1 of d)
+int launch_ground_levels(ws_map *m, GroundResult &q, int which, const int32_t lo[3], const int32_t ext[3], int32_t H, uint32_t flags);
+int ground_steps(hipStream_t s, GroundResult &q, uint32_t nx, uint32_t ny);
+int launch_ground_sites(hipStream_t s, const GroundResult &q, DistResult &d, uint32_t max_step, int32_t R, uint32_t flags);
 int fill_u32(ws_context *ctx, uint32_t *dst, uint32_t value, int64_t n);
 int launch_box_fill(ws_map *m, const ws::MapParams &par, int which, const int32_t lo[3], const int32_t ext[3], uint32_t value, hipStream_t stream);
 int check_all_equal_host(const uint32_t *data, int64_t n, uint32_t value);
@@ -1070,6 +1103,10 @@ struct StoreDistCall
   uint32_t nx, ny;      // columns of the box (nx ny < 2^32)
 };
 int launch_store_dist_classify(ws_store *st, ws_store::Dist &q, const StoreDistCall &c, int32_t R, uint32_t flags);
+
+// store_ground.hip: pass 1 of the ground layer over the chunks the call lists (it clears q.counts.dev and marks events 0, 1); the
+// call and the lookup are those of the distance field
+int launch_store_ground_levels(ws_store *st, ws_store::Ground &q, const StoreDistCall &c, int32_t H, uint32_t flags);
 
 // the bin rule of a sweep (ws_sweep_t, checked by api_scan.hip) and its pose table on the device
 struct PreSweep

@@ -11,6 +11,7 @@ from ._abi import _i3, _i3c, _is_device, _ptr, pack_entry, unpack_entry
 from ._lib import WS_MAP_AVG, WS_MAP_NEW, check
 from .context import Context
 from .global_map import GlobalMap
+from .ground import _ground_call, _ground_distance_call
 from .queries import _distance_call, _frontier_call, _reach_call, _reach_lookup_call, _reach_paths_call, _mesh_call, _raycast_call, _sample_call, _surface_call, _timing, _view_gain_call
 
 
@@ -248,6 +249,28 @@ class DeviceMapMemWrapper:
         rec, self.last_sites = _distance_call(self._t._L, "ws_map_distance", self._t, (self._which,), lo, hi, max_dist_vox, unknown_occupied, columns,
                                               any_weight, device, window_shape)
         return rec
+
+    def ground(self, lo=None, hi=None, clear_vox=20, any_weight=False, unknown_headroom=False, top=False, device=False):
+        """The ground layer of this map on the device (ws_map_ground; the rules are stated in include/warpsense_hip.h): per (x, y)
+        column of the inclusive world-voxel box [lo, hi] (both None: the whole window) the lowest (top: the highest) occupied voxel
+        with a free voxel right above it and clear_vox (1 .. 64) free voxels of headroom (unknown_headroom: unknown ones count above
+        the first), its sub-voxel height and the largest height step to the neighbouring ground columns.  any_weight: voxels with a
+        negative weight count as observed too.  Returns a GroundResult (records shaped (nx, ny), lo, ext, counts per class).
+        device=True: its records are a torch int32 tensor (nx, ny, 2) that ALIASES the library's buffer, valid until the next ground()
+        on this TSDFCuda."""
+        return _ground_call(self._t._L, "ws_map_ground", self._t, (self._which,), lo, hi, clear_vox, any_weight, unknown_headroom, top, device)
+
+    def ground_distance(self, max_step_q8, max_dist_vox=20, unknown_occupied=False, device=False):
+        """The column distance field over the LAST ground() result of this TSDFCuda (ws_map_ground_distance): a column is free iff it
+        is ground and its step is at most max_step_q8 (1/256 voxel); blocked, void and steeper columns are sites, unknown ones with
+        unknown_occupied.  It REPLACES the result of distance(): reach() then plans over it as over distance(columns=True).  Returns
+        the uint32 records shaped (nx, ny); `last_sites` keeps the number of site columns."""
+        rec, self.last_sites = _ground_distance_call(self._t._L, "ws_map_ground_distance", self._t, max_step_q8, max_dist_vox, unknown_occupied, device)
+        return rec
+
+    def ground_timing(self, enable: int = -1):
+        """device milliseconds of pass 1 (levels) and pass 2 (steps) of the last ground() (ws_debug_ground_timing)"""
+        return _timing(self._t._L, "ws_debug_ground_timing", self._t.handle, 2, enable)
 
     def frontier(self, lo=None, hi=None, min_value=0, any_weight=False, clusters=False, device=False):
         """The frontier of this map on the device (ws_map_frontier; the rules are stated in include/warpsense_hip.h): the voxels of

@@ -16,7 +16,7 @@ from .global_map import GlobalMap
 from .merge import FuseQueries
 from .pyramid import PyramidQueries
 from .gain import GainQueries
-from .reach import ReachQueries
+from .ground import GroundQueries
 from .records import SAMPLE_CLASSES
 from .registration import RegistrationCuda, batch_best, candidate_poses
 from .scan import to_int_mat, to_map
@@ -73,7 +73,7 @@ def _dirs_or_os1(dirs):
     return dirs
 
 
-class TSDFMapping(ReachQueries, GainQueries, FuseQueries, PyramidQueries):
+class TSDFMapping(GroundQueries, GainQueries, FuseQueries, PyramidQueries):
     """cuda::TSDFMapping without ROS (the protected constructor path, tsdf_mapping.cpp:30-41)."""
 
     def __init__(self, params: Params, local_map: LocalMap, ctx: Context | None = None, device_global_map: "DeviceGlobalMap | None" = None):

@@ -14,6 +14,7 @@ from .fuse import FuseStats, _fuse_call, fuse_pose
 from .global_map import GlobalMap
 from .pack import PackedMap, _pack_call, _unpack_call
 from .pyramid import CoarsenStats, _coarsen_call
+from .ground import _ground_call, _ground_distance_call
 from .queries import _box_ptrs, _distance_call, _frontier_call, _reach_call, _reach_lookup_call, _reach_paths_call, _mesh_call, _raycast_call, _sample_call, _surface_call, _timing, _view_gain_call
 
 
@@ -161,6 +162,23 @@ class DeviceGlobalMap:
     def distance_timing(self, enable: int = -1):
         """device milliseconds of pass 0 and of the x, y and z passes of the last distance() (ws_debug_store_distance_timing)"""
         return _timing(self._L, "ws_debug_store_distance_timing", self.handle, 4, enable)
+
+    def ground(self, lo=None, hi=None, clear_vox=20, any_weight=False, unknown_headroom=False, top=False, device=False):
+        """The ground layer of the chunks on the device (ws_store_ground; the rules are those of ws_map_ground, stated in
+        include/warpsense_hip.h) over the inclusive world-voxel box [lo, hi] (both None: the bounding box of the present chunks).
+        Voxels of absent chunks are unknown.  The arguments and the returned GroundResult are those of DeviceMapMemWrapper.ground;
+        device=True: its records ALIAS the store's buffer, valid until the next ground() on this store."""
+        return _ground_call(self._L, "ws_store_ground", self, (), lo, hi, clear_vox, any_weight, unknown_headroom, top, device)
+
+    def ground_distance(self, max_step_q8, max_dist_vox=20, unknown_occupied=False, device=False):
+        """The column distance field over the LAST ground() result of this store (ws_store_ground_distance), as
+        DeviceMapMemWrapper.ground_distance: it REPLACES the result of distance(), and reach() plans over it."""
+        rec, self.last_sites = _ground_distance_call(self._L, "ws_store_ground_distance", self, max_step_q8, max_dist_vox, unknown_occupied, device)
+        return rec
+
+    def ground_timing(self, enable: int = -1):
+        """device milliseconds of pass 1 (levels) and pass 2 (steps) of the last ground() (ws_debug_store_ground_timing)"""
+        return _timing(self._L, "ws_debug_store_ground_timing", self.handle, 2, enable)
 
     def frontier(self, lo=None, hi=None, min_value=0, any_weight=False, clusters=False, device=False):
         """The frontier of the chunks on the device (ws_store_frontier; the rules are those of ws_map_frontier, stated in
