@@ -54,7 +54,7 @@ _REFUSED = [
     ("ws_map_download", (None, 0, None, None, None, None)),      # api_map.hip
     ("ws_map_surface", (None, 0, None, None, 0, 0, None)),       # api_query.hip
     ("ws_map_mesh", (None, 0, None, None, 0, None, None)),
-    ("ws_store_distance", (None, None, None, 1, 0, None)),       # api_store.hip
+    ("ws_store_distance", (None, None, None, 1, 0, None)),       # api_store_query.hip
     ("ws_tsdf_integrate", (None,)),                              # api_tsdf.hip
     ("ws_reg_iterate", (None, None, None, 50, 0, None, None, None, None)),  # api_reg.hip
     ("ws_scan_download", (None, None, 0, None)),                 # api_scan.hip

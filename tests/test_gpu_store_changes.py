@@ -196,7 +196,7 @@ def test_refusals_leave_the_last_result_and_the_frontier_is_apart():
     invalid = [dict(cur=None), dict(ref=None), dict(pose=None), dict(stats=False), dict(ref=cur), dict(ref=foreign), dict(pose=bad_rot), dict(lo=a), dict(hi=b),
                dict(lo=b, hi=a), dict(flags=8 | 3), dict(flags=4), dict(flags=0)]
     # (the two WS_ERR_RANGE refusals for 2^19 chunks or more, of REF and of CUR in the box, need half a terabyte of chunks: they are
-    # covered only by reading store_lookup_plan and the listed.size() check of ws_store_changes in api_store.hip)
+    # covered only by reading store_lookup_plan and the listed.size() check of ws_store_changes in api_store_pair.hip)
     ranged = [dict(res=0), dict(res=1025), dict(band=0), dict(free_value=BAND - 1), dict(free_value=32768), dict(mw=0), dict(mw=32768)]
     for code, cases in ((WS_ERR_INVALID, invalid), (WS_ERR_RANGE, ranged)):
         for kw in cases:

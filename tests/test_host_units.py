@@ -1,4 +1,5 @@
-"""Host-side units of the record key / voxel-byte layout and the owning memory types (ws_internal.h) and of the walk over column changes (ws_dda.h), built and
+"""Host-side units of the record key / voxel-byte layout and the owning memory types (ws_internal.h), of the chunk-list core of the
+store (ws_store_list.h) and of the walk over column changes (ws_dda.h), built and
 run on the CPU: no GPU needed (hipcc cross-compiles; only host code runs)."""
 import os
 import shutil
@@ -39,6 +40,21 @@ def test_owning_types_are_empty_after_a_failed_allocation(tmp_path):
                            os.path.join(ROOT, "tests", "cpp", "owner_units.hip"), "-o", str(exe)])
     out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and out.stdout.strip().startswith("ok:"), out.stdout + out.stderr
+
+
+def test_chunk_list_core_equals_its_brute_force_restatement(tmp_path):
+    """ws_store_list.h, what every call on the chunk store derives from the chunks it lists: the live box and the z range against a
+    min / max over all chunks, the neighbour positions against a linear search, the word-space counts {B, N, P, n} against counting,
+    ChunkRange::key against a triple loop -- on an empty list, one chunk, a block without its centre, unequal runs, both ends of
+    the key domain, and boxes that cut or miss the chunks; and the listing limit against the places of the chunk lookup.
+    (tests/cpp/store_list_units.hip)"""
+    if not os.path.exists(_hipcc()):
+        pytest.skip("hipcc not installed")
+    exe = tmp_path / "store_list_units"
+    subprocess.check_call([_hipcc(), "--offload-arch=gfx950", "-O1", "-std=c++17", "-Wall", "-Werror", f"-I{os.path.join(ROOT, 'include')}", f"-I{CSRC}",
+                           os.path.join(ROOT, "tests", "cpp", "store_list_units.hip"), "-o", str(exe)])
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stdout + out.stderr
 
 
 def test_column_change_walk_equals_the_sample_walk(tmp_path):

@@ -23,12 +23,12 @@ This module only gathers the names; the code lives in one module per subsystem, 
     scan.py          DevicePoints, ScanPreprocessor, the sweep rules and host model (api_scan)
     queries.py       what window and store queries share: box, call, result, timing (api_query)
     global_map.py    GlobalMap on the host and its .h5 file, pose_to_values
-    store.py         DeviceGlobalMap, chunks_of_box                                 (api_store)
-    fuse.py          fuse_pose, FuseStats: one global map fused into another        (api_store)
+    store.py         DeviceGlobalMap, chunks_of_box                                 (api_store, api_store_query)
+    fuse.py          fuse_pose, FuseStats: one global map fused into another        (api_store_pair)
     merge.py         merge_map and align_map of TSDFMapping
-    pyramid.py       CoarsenStats, parents_of, MapPyramid, global_pyramid           (api_store)
-    changes.py       ChangeStats, ChangeResult, write_changes_ply: where two maps differ (api_store)
-    ground.py        GROUND_RECORD, GroundResult: levels, heights and steps of the ground  (api_query, api_store)
+    pyramid.py       CoarsenStats, parents_of, MapPyramid, global_pyramid           (api_store_pair)
+    changes.py       ChangeStats, ChangeResult, write_changes_ply: where two maps differ (api_store_pair)
+    ground.py        GROUND_RECORD, GroundResult: levels, heights and steps of the ground  (api_query, api_store_query)
     pack.py          PackedMap: packed snapshots of the global map and their .wspk file (api_pack)
     device_map.py    DeviceMap, LocalMap, DeviceMapMemWrapper, TSDFCuda             (api_map, api_tsdf)
     registration.py  RegistrationCuda, batch_best, candidate_poses                  (api_reg)

@@ -1,6 +1,6 @@
 // api_core.hip — the ground the other host files of the C API stand on (include/warpsense_hip.h; api_map.hip, api_query.hip,
-// api_store.hip, api_tsdf.hip, api_reg.hip, api_scan.hip): the last error of a thread, the refusals, the context with its stream
-// ordering and hipEvent profiling.  No kernels here or in any api_*.hip.  Entry points are defined at file scope: the header has
+// api_store.hip, api_store_query.hip, api_store_pair.hip, api_pack.hip, api_tsdf.hip, api_reg.hip, api_scan.hip): the last error of a
+// thread, the refusals, the context with its stream ordering and hipEvent profiling.  No kernels here or in any api_*.hip.  Entry points are defined at file scope: the header has
 // declared each of them with C linkage, so no file wraps anything in a linkage block.  What the files share is in ws_api.h.
 #include <cmath>
 #include <new>

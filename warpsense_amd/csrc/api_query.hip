@@ -27,7 +27,7 @@ int ws_map_surface(ws_map *m, int which, const int32_t lo[3], const int32_t hi[3
 }
 
 // ---- surface cloud: what the host core of ws_api.h (surface_run) needs beside it, for the window of a map here and for the chunks of
-// the store in api_store.hip
+// the store in api_store_query.hip
 const void *ws::surface_records_dev(const SurfResult *q, size_t *n)
 {
   if (n) *n = q ? q->n : 0;
@@ -82,7 +82,7 @@ int ws_debug_surface_timing(ws_map *m, int32_t enable, float ms_out[3])
 }
 
 // ---- mesh and ray cast: what the host cores of ws_api.h (mesh_run, raycast_check, raycast_run) need beside them, for the window of
-// a map here and for the chunks of the store in api_store.hip
+// a map here and for the chunks of the store in api_store_query.hip
 int ws::mesh_corners_fit(const int32_t lo[3], const int32_t hi[3], int32_t res, const char *name)
 {
   for (int k = 0; k < 3; ++k)
@@ -235,7 +235,7 @@ int ws_debug_raycast_timing(ws_map *m, int32_t enable, float ms_out[3])
 }
 
 // ---- point sample: what the host cores of ws_api.h (sample_check, sample_run) need beside them, for the window of a map here and
-// for the chunks of the store in api_store.hip
+// for the chunks of the store in api_store_query.hip
 const void *ws::sample_records_dev(const SampleResult *q, size_t *n)
 {
   if (n) *n = q ? q->n : 0;
@@ -479,7 +479,7 @@ int ws_map_ground_distance(ws_map *m, int32_t max_step_q8, int32_t max_dist_vox,
 }
 
 // ---- frontier: what the host core of ws_api.h (frontier_run) needs beside it, for the window of a map here and for the chunks of the
-// store in api_store.hip
+// store in api_store_query.hip
 int ws::frontier_check(const char *name, bool bad, const int32_t *lo, const int32_t *hi, int32_t min_value, uint32_t flags)
 {
   const uint32_t known = WS_FRONTIER_ANY_WEIGHT | WS_FRONTIER_CLUSTERS;
@@ -568,7 +568,7 @@ int ws_debug_frontier_timing(ws_map *m, int32_t enable, float ms_out[4])
 }
 
 // ---- reach: what the host core of ws_api.h (reach_run) needs beside it, for the window of a map here and for the store in
-// api_store.hip.  reach_rounds is the flow behind the refusals, from "the old result is dropped" to the publish: seeding, then one launch
+// api_store_query.hip.  reach_rounds is the flow behind the refusals, from "the old result is dropped" to the publish: seeding, then one launch
 // and one read per round until the list of the next round is empty.
 int ws::reach_rounds(ReachResult &q, const DistResult &d, hipStream_t s, const char *name, const int32_t *seeds, size_t n_seeds, int32_t clear_d2, uint32_t flags,
                      uint32_t max_rounds, size_t *n_seeded, size_t *n_reached, uint32_t *rounds)
@@ -787,7 +787,7 @@ int ws_debug_reach_params(int32_t out[8])
 }
 
 // ---- view gain: what the host core of ws_api.h (gain_check, gain_run) needs beside it, for the window of a map here and for the chunks
-// of the store in api_store.hip
+// of the store in api_store_query.hip
 const void *ws::gain_records_dev(const GainResult *q, size_t *n)
 {
   if (n) *n = q ? q->m : 0;

@@ -1,5 +1,5 @@
 // store_changes.hip — the passes of ws_store_changes (include/warpsense_hip.h; the rules are in ws_changes.h, the host flow in
-// api_store.hip): the voxels of the store CUR whose class differs from that of the store REF sampled at their place under a rigid pull
+// api_store_pair.hip): the voxels of the store CUR whose class differs from that of the store REF sampled at their place under a rigid pull
 // transform, as ordered records.  The ordered stream compaction is that of store_frontier.hip in the word space of ws_store_words.h;
 // the transform and the sample are the fuse's (ws_fuse.h).
 //

@@ -1,5 +1,5 @@
 // store_coarsen.hip — the one pass of ws_store_coarsen (include/warpsense_hip.h; the rule is in ws_coarsen.h, the plan in
-// api_store.hip): whole chunks of DST rebuilt from the up to eight chunks of SRC they cover, 2 x 2 x 2 voxels into one.
+// api_store_pair.hip): whole chunks of DST rebuilt from the up to eight chunks of SRC they cover, 2 x 2 x 2 voxels into one.
 //
 // A workgroup is 4 x 4 z columns of one dst chunk; a wave owns one column of 64 coarse voxels at a time, lane = z, so the store is one
 // coalesced 256-byte access.  The children of a column lie in four columns of SRC (x and y pairs) of 128 consecutive z words: a lane

@@ -1,4 +1,4 @@
-// store_fuse.hip — the two passes of ws_store_fuse (include/warpsense_hip.h; the rules are in ws_fuse.h, the plan in api_store.hip):
+// store_fuse.hip — the two passes of ws_store_fuse (include/warpsense_hip.h; the rules are in ws_fuse.h, the plan in api_store_pair.hip):
 // one chunk store resampled on the lattice of another under a rigid pull transform and integrated into it.
 //
 //   store_fuse_kernel<false>   count pass: per candidate dst chunk the voxels that receive a valid sample, and the sums of the

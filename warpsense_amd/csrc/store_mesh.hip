@@ -25,7 +25,7 @@
 //   store_mesh_vertex_kernel   |  neighbour is absent or not listed: a zero word); the vertex pass gathers the eight corners from up
 //   store_mesh_face_kernel     |  to eight chunks through the segment table
 //
-// Tables per call (the host's, store_mesh_tables in api_store.hip): per listed chunk {B, N, P, n}, {cx, cy, cz, slot} and 27 neighbour
+// Tables per call (the host's, store_mesh_tables in api_store_query.hip): per listed chunk {B, N, P, n}, {cx, cy, cz, slot} and 27 neighbour
 // entries (dx + 1) * 9 + (dy + 1) * 3 + (dz + 1), of which the passes use (0,0,0), the seven of {0,1}^3 and the seven of {0,-1}^3.
 #include "ws_mesh.h"
 #include "ws_store_words.h"

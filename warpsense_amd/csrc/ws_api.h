@@ -1,13 +1,16 @@
 // ws_api.h — what the host files of the C API (api_*.hip) share, and nothing else: the refusals, the map's settle-and-report
-// steps, the box rules, and the host cores that the queries of a map window (api_query.hip) and of the chunk store (api_store.hip)
-// both run.  What one file uses alone is static in that file.  Everything here is in namespace ws or a template: it mangles, so the
-// library exports no unprefixed C name beside the ws_* entry points (tests/test_abi_and_host.py holds that).
+// steps, the box rules, what the three host files of the chunk store share (api_store.hip: the store itself; api_store_query.hip:
+// the calls that read one store; api_store_pair.hip: the calls over two stores) with each other and with api_pack.hip, and the host
+// cores that the queries of a map window (api_query.hip) and of the chunk store (api_store_query.hip) both run.  What one file
+// uses alone is static in that file.  Everything here is in namespace ws or a template: it mangles, so the library exports no
+// unprefixed C name beside the ws_* entry points (tests/test_abi_and_host.py holds that).
 #pragma once
 
 #include <algorithm>
 #include <string>
 
 #include "ws_internal.h"
+#include "ws_store_list.h"
 
 namespace ws
 {
@@ -65,12 +68,29 @@ int distance_download(const DistResult &q, hipStream_t s, uint32_t *host, size_t
 // the event pairs of ws_debug_*_timing (QueryTimer::read)
 constexpr int SURF_PAIRS[3][2] = {{0, 1}, {1, 2}, {3, 4}}, MESH_PAIRS[3][2] = {{0, 1}, {1, 2}, {3, 4}}, RAY_PAIRS[3][2] = {{0, 1}, {1, 2}, {2, 3}}, SAMPLE_PAIRS[3][2] = {{0, 1}, {1, 2}, {2, 3}}, DIST_PAIRS[4][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 4}};
 
-// ---- api_store.hip: what the calls that create chunks share with api_pack.hip.  The caller holds the store's lock.
-using StoreKey = std::array<int32_t, 3>;
+// ---- api_store.hip: the directory, the segments and the slot-table ring, for the calls that create chunks or take a slot table
+// (api_store_pair.hip, api_pack.hip).  The caller holds the store's lock.  (StoreKey and the chunk list: ws_store_list.h)
 int store_make_room(ws_store *st, uint64_t fresh, const char *name); // room for `fresh` more chunks: WS_ERR_CAPACITY beyond max_chunks, segments where they are missing (which waits for the stream)
 uint32_t store_take_slot(ws_store *st);                              // (store_make_room has been asked)
 void store_evict(ws_store *st, const std::set<StoreKey> &fresh);     // the chunks of `fresh` leave the directory, their slots are free again
 int store_table(ws_store *st, size_t n, ws_store::Table **out);      // the next slot table of the ring, for n words
+uint32_t *store_slot_ptr(const ws_store *st, uint32_t slot);         // the 64^3 words of a slot
+
+// ---- api_store_query.hip: the box, the list and the chunk tables of a call that reads a store, for the calls over two stores too
+// (api_store_pair.hip).  But for store_box_refuse the caller holds the store's lock.
+int store_box_refuse(const char *name, const int32_t lo[3], const int32_t hi[3]);                             // a box whose hi < lo, in the name of the entry point
+void store_box_of(const ws_store *st, const int32_t lo[3], const int32_t hi[3], bool everything, int32_t l[3], int32_t h[3]); // the call's box, or the default without one
+void store_list(const ws_store *st, const int32_t *lo, const int32_t *hi, std::vector<StoreRaySlot> &listed); // the written chunks the box overlaps (all without one), ascending
+int store_enqueued(const ws_store *st, int rc);                                                               // waits for the stream after a failed enqueue, whose error it returns
+// the tables of a call over the listed chunks into host (dev: its twin): the word-space tables, then the neighbour positions at n_off offsets; bytes(n): their size
+int store_chunk_tables(ws_store *st, HostBlock &host, DevBuf &dev, const std::vector<StoreRaySlot> &listed, size_t (*bytes)(size_t), const int32_t (*off)[3], int n_off);
+// a ws_debug_store_*_timing entry point: the timer of the result holder `q` of the store
+template <typename Q, int N> int store_timing(ws_store *st, const char *name, Q ws_store::*q, int32_t enable, float *ms_out, const int (&pairs)[N][2])
+{
+  if (!st) return invalid(std::string(name) + ": store is NULL");
+  std::lock_guard<std::mutex> lock(st->mu);
+  return query_timing(st->ctx->stream, (st->*q).timer, enable, ms_out, pairs, N);
+}
 
 // ---- surface cloud, mesh, ray cast and distance field: one host core each for the window of a map (map_surface.hip, map_mesh.hip,
 // map_raycast.hip, map_distance.hip) and for the chunks of the store (store_surface.hip, store_mesh.hip, store_raycast.hip,

@@ -1,6 +1,6 @@
 // ws_changes.h — the rules of ws_store_changes (stated in include/warpsense_hip.h): the classes of a known side, the verdict on one
 // voxel of CUR against the sample of REF at its place, and the record's word.  Everything that decides a byte is here, as functions
-// of values; store_changes.hip holds the passes that call them and api_store.hip the host flow.  The transform and the sample are
+// of values; store_changes.hip holds the passes that call them and api_store_pair.hip the host flow.  The transform and the sample are
 // those of the fuse (ws_fuse.h: fuse_pull, fuse_dead, fuse_sample over the StoreField lookup); the word space is that of the store's
 // surface cloud and frontier (ws_store_words.h).
 #pragma once

@@ -1,6 +1,6 @@
 // ws_coarsen.h — the rule of ws_store_coarsen (stated in include/warpsense_hip.h): one coarse entry from the eight entries of the
 // 2 x 2 x 2 voxels it covers.  Everything that decides a byte is here, as functions of integers that the host can run as well;
-// store_coarsen.hip holds the kernel that calls them and api_store.hip the plan.
+// store_coarsen.hip holds the kernel that calls them and api_store_pair.hip the plan.
 #pragma once
 
 #include "ws_device.h"

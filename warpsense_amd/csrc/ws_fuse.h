@@ -1,7 +1,7 @@
 // ws_fuse.h — the rules of ws_store_fuse (stated in include/warpsense_hip.h): the pull transform of a dst voxel centre into the frame
 // of SRC, the trilinear sample of SRC there with the zero-coefficient rule, and the weighted-average integrate into the dst entry.
 // Everything that decides a byte is here, as functions of integers; store_fuse.hip holds the two passes that call them and
-// api_store.hip the plan.  The cell (base voxel, fractions, T) is that of ws_raycast.h / ws_sample.h; SRC is read through the chunk
+// api_store_pair.hip the plan.  The cell (base voxel, fractions, T) is that of ws_raycast.h / ws_sample.h; SRC is read through the chunk
 // lookup of ws_field_store.h.
 #pragma once
 

@@ -2,7 +2,7 @@
 // include/warpsense_hip.h): the levels of 64 voxels of a column from their class masks, the level a column keeps, the sub-voxel height,
 // the record's word, the step between two heights and the class a ground record has in a column distance field.  Everything that
 // decides a byte is here, as functions of values; map_ground.hip and store_ground.hip hold the walks that call them, api_query.hip and
-// api_store.hip the host flow.
+// api_store_query.hip the host flow.
 //
 // A step of a column walk is 64 consecutive z voxels, bit b of a mask = voxel b of the step.  The walk goes DOWN the column and
 // carries the masks of the step above: a level at bit 63 stands under bit 0 of that step, and headroom of up to 64 voxels above a

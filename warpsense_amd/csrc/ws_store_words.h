@@ -3,8 +3,8 @@
 //
 //     t = 4096 B + lx 64 N + 64 P + ly n + r
 //
-// ascends like world (x, y, cz).  The host writes, per listed chunk, {B, N, P, n} and {cx, cy, cz, slot} (store_word_tables in
-// api_store.hip; store_word_table_bytes, ws_internal.h); the way back from t to the chunk and the column needs two table reads and no search.
+// ascends like world (x, y, cz).  The host writes, per listed chunk, {B, N, P, n} and {cx, cy, cz, slot} (store_word_tables,
+// ws_store_list.h; store_word_table_bytes, ws_internal.h); the way back from t to the chunk and the column needs two table reads and no search.
 #pragma once
 
 #include "ws_device.h"
