@@ -624,6 +624,76 @@ int ws_map_view_gain_download(ws_map *map, void *records_host, void *rays_host, 
  * that finds the maximum */
 int ws_debug_view_gain_timing(ws_map *map, int32_t enable, float ms_out[3]);
 
+/* Clearance of candidate trajectories: does a body keep clear of the obstacles along a motion?  For T trajectories of P poses each and a
+ * body of K spheres, per trajectory the smallest margin between a sphere and the nearest obstacle, the first colliding pose, the counts
+ * and a soft cost, and the index of the best trajectory -- the scoring step of a local planner (DWA, MPPI, lattice primitives) for a few
+ * thousand rollouts in one launch.  Integers only: the same bytes on every run.  All products and sums are int64; "floor" is floor
+ * division.
+ *   input: the dense result of the LAST distance call on this map (ws_map_distance or ws_map_ground_distance) as it lies in device
+ *     memory: its box (lo and extent), its `class | d2` records, whether it was made under WS_DISTANCE_COLUMNS, and its clamp
+ *     R = max_dist_vox.  No distance result yet: WS_ERR_INVALID.  The TSDF is never read.
+ *   resolution: res is the map's (ws_map_create), as for ws_map_sample; res > 1024: WS_ERR_RANGE.
+ *   body: K spheres, 1 <= K <= 64, K x 4 int32 in host memory: off_mm[3], the centre in the body frame with |component| <= 2^20, and
+ *     radius_mm in 0 .. 65535.
+ *   poses: T x P records of 12 int32, trajectory-major: rot_q30[9], row-major, every entry in [-2^30, 2^30] (the convention of
+ *     ws_fuse_pose; orthonormality is not required), then pos_mm[3] with |component| < 2^30.  1 <= P <= 65535, T <= 2^20,
+ *     T P <= 2^21.  The device calls do not read the poses on the host and so do not check these two domains: the arithmetic below is
+ *     int64 and, the body being checked (|off| <= 2^20: |sum| <= 3 * 2^51), total over all int32 values of a pose, and inside the domains every centre fits int32.
+ *   sample (t, p, k): the centre c_a = pos_a + floor((sum_j rot[a][j] off_j + 2^29) / 2^30) on each axis a; its voxel v = floor(c / res)
+ *     per axis.  Under columns z is ignored.  The sample is OUTSIDE when v lies outside the box of the distance result.  Otherwise, with
+ *     class and d2 of the record at v: margin = isqrt(d2 res^2) - radius_k, isqrt the exact floor square root (its argument is below
+ *     2^36).  HIT iff margin < 0.  UNKNOWN iff the class is 0 -- counted, nothing more; under WS_DISTANCE_UNKNOWN_OCCUPIED an unknown
+ *     record is a site, d2 = 0, so it is a HIT as well.  penalty = max(0, soft_mm - margin)^2, soft_mm in 0 .. 65535.
+ *   The distance is between voxel CENTRES: the obstacle's surface may be up to half a voxel diagonal nearer than the records say, and the
+ *     sphere's centre up to half a diagonal from its voxel's centre.  A caller who must not touch pads the radii by res sqrt(3) (by
+ *     res sqrt(2) under columns).
+ *   R res < max radius + soft_mm: WS_ERR_RANGE -- the clamp of d2 at R^2 could hide a penalty.
+ *   record per trajectory, 32 bytes, in trajectory order, all fields over the samples of the trajectory that are not OUTSIDE:
+ *     int32 min_margin (INT32_MAX without such a sample), int32 first_hit (the smallest pose index with a HIT, -1 for none),
+ *     uint32 argmin (p * 64 + k of the first sample in (p, k) order that attains min_margin, 0xFFFFFFFF for none), uint32 hits,
+ *     uint32 outside (the OUTSIDE samples), uint32 unknown, uint64 cost (the sum of the penalties).
+ *   WS_CLEARANCE_POSES adds T x P records of 8 bytes, trajectory-major: int32 the smallest margin of the pose (INT32_MAX for none),
+ *     uint16 hits, uint16 outside.
+ *   *best (int64, may be NULL): the index of the trajectory with no hit and no outside sample whose (cost, index) is smallest, -1 when
+ *     there is none.  With WS_CLEARANCE_OUTSIDE_OK outside samples do not disqualify.  It is found on the device in a last pass.
+ *   limits: unknown flag bits, a NULL array with a non-zero count: WS_ERR_INVALID.  K, P, T, T P, soft_mm, an offset or a radius out of
+ *     range: WS_ERR_RANGE.  With these limits no counter or cost can overflow (2^22 samples times a penalty below 2^34).  T == 0 (behind
+ *     those checks of the arguments, in front of the look at the distance result: it is WS_OK without one, and whatever its R): WS_OK,
+ *     nothing is written, the last result stays, *best is left alone.  Every refusal comes before the first launch
+ *     and leaves the last result in place.
+ * Synchronises.  The result buffers belong to the map, grow on demand and stay valid until the next clearance call on it; they are apart
+ * from those of every other query, none of which invalidates this result.  Read-only on the maps and on the distance result; calls are
+ * serialised inside the library.  Nothing is allocated before the first call; an allocation that fails returns WS_ERR_HIP and leaves
+ * the map usable.
+ * The implementation (map_clearance.hip): one workgroup of 256 lanes per trajectory, the body in LDS; G, the power of two >= K,
+ * consecutive lanes take one pose, lane k sphere k, and the groups stride over the poses; a lane rotates its own offset and gathers one
+ * record.  The wave folds a biased 64-bit (margin, index) key by min, first_hit by min, counts and cost by adds, the four waves meet in
+ * LDS, one record store per trajectory: no atomics and nothing to clear.  The float in isqrt is an estimate that two integer loops
+ * correct; no result depends on it. */
+#define WS_CLEARANCE_DEFAULT 0u
+#define WS_CLEARANCE_POSES 1u
+#define WS_CLEARANCE_OUTSIDE_OK 2u
+int ws_map_clearance(ws_map *map, const int32_t *poses_host, size_t n_traj, size_t n_poses, const int32_t *body_host, size_t k, int32_t soft_mm, uint32_t flags,
+                     int64_t *best);
+/* the same with the poses already in device memory (the body stays a host array) */
+int ws_map_clearance_dev(ws_map *map, const int32_t *poses_dev, size_t n_traj, size_t n_poses, const int32_t *body_host, size_t k, int32_t soft_mm, uint32_t flags,
+                         int64_t *best);
+const void *ws_map_clearance_records_dev(const ws_map *map, size_t *n); /* device memory, n x 32 bytes; NULL when n == 0 */
+const void *ws_map_clearance_poses_dev(const ws_map *map, size_t *n);   /* n = T x P records of 8 bytes; NULL unless the last call asked for them */
+/* copies at most cap_traj trajectory records and cap_poses pose records (prefixes) and always reports the totals; either host pointer
+ * may be NULL, and so may n_poses.  Asking for pose records that the last call did not produce: WS_ERR_INVALID */
+int ws_map_clearance_download(ws_map *map, void *records_host, void *poses_host, size_t cap_traj, size_t cap_poses, size_t *n_traj, size_t *n_poses);
+/* Measurement entry, as ws_debug_surface_timing: ms_out receives the device time of the upload of body and poses, of the trajectory
+ * pass, and of the pass over the records that finds the best */
+int ws_debug_clearance_timing(ws_map *map, int32_t enable, float ms_out[3]);
+/* ws_clearance_centres, ws_clearance_margin: host only, no GPU and no context -- the CPU statement of the two rules above, for tools and
+ * tests.  ws_clearance_centres writes the voxel (3 int32) of every sample of n_poses poses (12 int32 each) and a body of k spheres,
+ * n_poses x k x 3, pose-major; it checks k, res (1 .. 1024), the body and here also the domains of the poses (WS_ERR_RANGE).
+ * ws_clearance_margin returns isqrt(d2 res^2) - radius_mm; arguments outside d2 <= 65025, 1 <= res <= 1024, 0 <= radius_mm <= 65535
+ * are clamped to these ranges. */
+int ws_clearance_centres(const int32_t *poses, size_t n_poses, const int32_t *body, size_t k, int32_t res, int32_t *voxels_out);
+int32_t ws_clearance_margin(uint32_t d2, int32_t res, int32_t radius_mm);
+
 /* ------------------------------------------------------------------ the global map in device memory ---- */
 /* ws_store: the device twin of HDF5GlobalMap (src/map/hdf5_global_map.cpp) -- a pool of 64^3-voxel chunks in HBM, so that a map shift
  * is a device-to-device copy in stream order: the leaving slabs, the window move and the entering slabs with revisits and corners,
@@ -959,6 +1029,23 @@ const void *ws_store_view_gain_rays_dev(const ws_store *st, size_t *n);    /* n 
 /* as ws_map_view_gain_download */
 int ws_store_view_gain_download(ws_store *st, void *records_host, void *rays_host, size_t cap_views, size_t cap_rays, size_t *n_views, size_t *n_rays);
 int ws_debug_store_view_gain_timing(ws_store *st, int32_t enable, float ms_out[3]);
+
+/* The clearance of the store: ws_map_clearance over the last distance result of the store (ws_store_distance or
+ * ws_store_ground_distance) -- the one host flow and the one kernel file of the window's call.
+ *   map_resolution: mm per voxel, 1 .. 1024 (the store keeps none, as for ws_store_sample); <= 0: WS_ERR_INVALID, > 1024: WS_ERR_RANGE.
+ *   rules: everything else is word for word the rule set of ws_map_clearance: input, body, poses, samples, margin, records, flags, *best,
+ *     limits and errors.  The records of an absent chunk inside the box of the distance call are UNKNOWN and show as such.
+ *   consequence: if a window's distance result and the store's hold the same box and records, the two calls return the same bytes.
+ * Synchronises.  The result belongs to the store and is apart from every other query's. */
+int ws_store_clearance(ws_store *st, const int32_t *poses_host, size_t n_traj, size_t n_poses, const int32_t *body_host, size_t k, int32_t soft_mm,
+                       int32_t map_resolution, uint32_t flags, int64_t *best);
+int ws_store_clearance_dev(ws_store *st, const int32_t *poses_dev, size_t n_traj, size_t n_poses, const int32_t *body_host, size_t k, int32_t soft_mm,
+                           int32_t map_resolution, uint32_t flags, int64_t *best);
+const void *ws_store_clearance_records_dev(const ws_store *st, size_t *n); /* device memory, n x 32 bytes; NULL when n == 0 */
+const void *ws_store_clearance_poses_dev(const ws_store *st, size_t *n);   /* n = T x P records of 8 bytes; NULL unless the last call asked for them */
+/* as ws_map_clearance_download */
+int ws_store_clearance_download(ws_store *st, void *records_host, void *poses_host, size_t cap_traj, size_t cap_poses, size_t *n_traj, size_t *n_poses);
+int ws_debug_store_clearance_timing(ws_store *st, int32_t enable, float ms_out[3]);
 
 /* One store fused into another under a rigid pose: SRC is resampled on the voxel lattice of DST and integrated into it with the
  * weighted average of the TSDF update, on the device, without a chunk leaving HBM.  Two runs of one site, a map loaded from a file

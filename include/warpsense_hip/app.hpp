@@ -354,6 +354,12 @@ public:
   {
     return global_map_view_gain(store_, resolution, origins, dirs, max_range_mm, min_value, any_weight, with_rays, lo, hi);
   }
+  // candidate trajectories against the last distance() or ground_distance() of the chunks (visualization.hpp, ws_store_clearance)
+  Clearance clearance(int resolution, const std::vector<ClearanceInput> &poses, size_t n_poses, const std::vector<ClearanceSphere> &body, int32_t soft_mm = 0,
+                      bool per_pose = false, bool outside_ok = false)
+  {
+    return global_map_clearance(store_, resolution, poses, n_poses, body, soft_mm, per_pose, outside_ok);
+  }
   // path costs over the last distance() of the chunks, and the paths back from goals (visualization.hpp, ws_store_reach)
   ReachField reach(const std::vector<rm::Pointi> &seeds, int32_t clear_d2 = 0, bool unknown_free = false, uint32_t max_rounds = 0)
   {
@@ -487,6 +493,13 @@ inline ViewGain global_map_view_gain(DeviceGlobalMap &g, int resolution, const s
                                      int32_t min_value = 0, bool any_weight = false, bool with_rays = false, const rm::Pointi *lo = nullptr, const rm::Pointi *hi = nullptr)
 {
   return global_map_view_gain(g.handle(), resolution, origins, dirs, max_range_mm, min_value, any_weight, with_rays, lo, hi);
+}
+
+// the clearance of the device global map (visualization.hpp, ws_store_clearance)
+inline Clearance global_map_clearance(DeviceGlobalMap &g, int resolution, const std::vector<ClearanceInput> &poses, size_t n_poses, const std::vector<ClearanceSphere> &body,
+                                      int32_t soft_mm = 0, bool per_pose = false, bool outside_ok = false)
+{
+  return global_map_clearance(g.handle(), resolution, poses, n_poses, body, soft_mm, per_pose, outside_ok);
 }
 
 // the reach of the device global map and its paths (visualization.hpp, ws_store_reach)
@@ -1050,6 +1063,40 @@ public:
     WS_CHECK(ws_store_distance(device_global_map_->handle(), lo ? &lo->x : nullptr, hi ? &hi->x : nullptr, clear_vox + 1,
                                columns ? WS_DISTANCE_COLUMNS : WS_DISTANCE_DEFAULT, nullptr));
     return device_global_map_->reach(seeds, clear_vox * clear_vox, unknown_free, max_rounds);
+  }
+  // Candidate trajectories scored against the averaged map: the distance field of the window (or of [lo, hi]; columns: the 2-D field of
+  // a ground robot) with a range of max_dist_vox voxels (0: the largest radius + soft_mm, rounded up, plus one), then local_map_clearance
+  Clearance score_trajectories(const std::vector<ClearanceInput> &poses, size_t n_poses, const std::vector<ClearanceSphere> &body, int32_t soft_mm = 0,
+                               bool columns = true, bool per_pose = false, bool outside_ok = false, int32_t max_dist_vox = 0, bool unknown_occupied = false,
+                               const rm::Pointi *lo = nullptr, const rm::Pointi *hi = nullptr)
+  {
+    const uint32_t flags = (columns ? WS_DISTANCE_COLUMNS : 0u) | (unknown_occupied ? WS_DISTANCE_UNKNOWN_OCCUPIED : 0u);
+    WS_CHECK(ws_map_distance(gpu_.tsdf().handle(), WS_MAP_AVG, lo ? &lo->x : nullptr, hi ? &hi->x : nullptr, score_range(body, soft_mm, max_dist_vox), flags, nullptr));
+    return local_map_clearance(gpu_.tsdf(), poses, n_poses, body, soft_mm, per_pose, outside_ok);
+  }
+  // the same over everything the run has seen: the window into the device chunks, as global_mesh does, then distance and clearance of the store
+  Clearance global_score_trajectories(const std::vector<ClearanceInput> &poses, size_t n_poses, const std::vector<ClearanceSphere> &body, int32_t soft_mm = 0,
+                                      bool columns = true, bool per_pose = false, bool outside_ok = false, int32_t max_dist_vox = 0, bool unknown_occupied = false,
+                                      const rm::Pointi *lo = nullptr, const rm::Pointi *hi = nullptr)
+  {
+    if (!device_global_map_) throw std::logic_error("global_score_trajectories: no DeviceGlobalMap attached");
+    const int32_t range = score_range(body, soft_mm, max_dist_vox);
+    wait_shift();
+    rm::Pointi wlo, whi;
+    local_map_.window(wlo, whi);
+    WS_CHECK(ws_store_save_box(device_global_map_->handle(), gpu_.tsdf().handle(), WS_MAP_AVG, &wlo.x, &whi.x));
+    const uint32_t flags = (columns ? WS_DISTANCE_COLUMNS : 0u) | (unknown_occupied ? WS_DISTANCE_UNKNOWN_OCCUPIED : 0u);
+    WS_CHECK(ws_store_distance(device_global_map_->handle(), lo ? &lo->x : nullptr, hi ? &hi->x : nullptr, range, flags, nullptr));
+    return device_global_map_->clearance(params_.map_resolution, poses, n_poses, body, soft_mm, per_pose, outside_ok);
+  }
+  // the range of the distance call behind score_trajectories, in voxels
+  int32_t score_range(const std::vector<ClearanceSphere> &body, int32_t soft_mm, int32_t max_dist_vox) const
+  {
+    int64_t need = 0;
+    for (const ClearanceSphere &s : body) need = std::max<int64_t>(need, s.radius_mm);
+    const int64_t res = params_.map_resolution, vox = max_dist_vox > 0 ? max_dist_vox : (need + soft_mm + res - 1) / res + 1;
+    if (vox < 1 || vox > 255) throw std::invalid_argument("score_trajectories: the distance range must be 1 .. 255 voxels");
+    return (int32_t)vox;
   }
   // the reference's route, kept for comparison: whole window to the host array of the local map
   void download() { gpu_.tsdf().avg_map().to_host(view_); }

@@ -13,6 +13,7 @@
 //   local_map_frontier / global_map_frontier   (no counterpart)                               where the known world ends, over ws_map_frontier / ws_store_frontier
 //   local_map_reach / global_map_reach, local_map_reach_paths / global_map_reach_paths   (no counterpart)   path costs and paths, over ws_map_reach / ws_store_reach
 //   local_map_view_gain / global_map_view_gain   (no counterpart)                             what the sensor would see from candidate poses, over ws_map_view_gain / ws_store_view_gain
+//   local_map_clearance / global_map_clearance   (no counterpart)                             candidate trajectories of a body of spheres against the last distance result, over ws_map_clearance / ws_store_clearance
 //   local_map_skeleton   publish_local_map_skeleton  map.h:175-227   the 24 end points of the window's line list (host only)
 //
 // The reference walks every voxel of a host map (after a whole-map download for the CUDA map, test/pcd2tsdf.cpp:134-137); here
@@ -187,6 +188,71 @@ inline ViewGain global_map_view_gain(ws_store *store, int resolution, const std:
   if (with_rays) out.rays.resize(origins.size() * dirs.size());
   size_t got = 0, got_rays = 0;
   WS_CHECK(ws_store_view_gain_download(store, out.records.data(), with_rays ? out.rays.data() : nullptr, out.records.size(), out.rays.size(), &got, &got_rays));
+  return out;
+}
+
+struct ClearanceRecord // one record of ws_map_clearance per trajectory
+{
+  int32_t min_margin, first_hit;           // the smallest margin (INT32_MAX without a sample inside the box); the first pose with a hit, -1 for none
+  uint32_t argmin, hits, outside, unknown; // p * 64 + k of the first sample at min_margin (0xFFFFFFFF for none); the counts
+  uint64_t cost;                           // the sum of max(0, soft_mm - margin)^2
+};
+struct ClearancePose // with per_pose: one record per (trajectory, pose), trajectory-major
+{
+  int32_t min_margin;
+  uint16_t hits, outside;
+};
+static_assert(sizeof(ClearanceRecord) == 32 && sizeof(ClearancePose) == 8, "ws_map_clearance writes 32-byte trajectory records and 8-byte pose records");
+struct ClearanceSphere // one sphere of the body: the centre in the body frame and the radius, mm
+{
+  int32_t off_mm[3], radius_mm;
+};
+struct ClearanceInput // one pose of a trajectory: rot_q30 row-major (the convention of ws_fuse_pose), then the position in the map frame, mm
+{
+  int32_t rot_q30[9], pos_mm[3];
+};
+static_assert(sizeof(ClearanceSphere) == 16 && sizeof(ClearanceInput) == 48, "ws_map_clearance reads 4 int32 per sphere and 12 per pose");
+
+struct Clearance
+{
+  std::vector<ClearanceRecord> records; // one per trajectory, in their order
+  std::vector<ClearancePose> poses;     // [trajectory][pose]; empty unless asked for
+  int64_t best = -1;                    // the trajectory without a hit (and without an outside sample unless outside_ok) of the smallest (cost, index)
+};
+
+// `poses` (trajectory-major, n_poses per trajectory) and a body of spheres against the LAST distance result of the map (ws_map_distance
+// or ws_map_ground_distance; the rules: warpsense_hip.h at ws_map_clearance).  No pose: an empty result, nothing is called.
+inline Clearance local_map_clearance(cuda::TSDFCuda &tsdf, const std::vector<ClearanceInput> &poses, size_t n_poses, const std::vector<ClearanceSphere> &body,
+                                     int32_t soft_mm = 0, bool per_pose = false, bool outside_ok = false)
+{
+  Clearance out;
+  if (poses.empty() || n_poses == 0) return out;
+  if (poses.size() % n_poses) throw std::invalid_argument("local_map_clearance: the poses are no whole number of trajectories");
+  const size_t t = poses.size() / n_poses;
+  const uint32_t flags = (per_pose ? WS_CLEARANCE_POSES : 0u) | (outside_ok ? WS_CLEARANCE_OUTSIDE_OK : 0u);
+  WS_CHECK(ws_map_clearance(tsdf.handle(), poses[0].rot_q30, t, n_poses, body.empty() ? nullptr : body[0].off_mm, body.size(), soft_mm, flags, &out.best));
+  out.records.resize(t);
+  if (per_pose) out.poses.resize(poses.size());
+  size_t got = 0, got_poses = 0;
+  WS_CHECK(ws_map_clearance_download(tsdf.handle(), out.records.data(), per_pose ? out.poses.data() : nullptr, out.records.size(), out.poses.size(), &got, &got_poses));
+  return out;
+}
+
+// The same against the last distance result of the global map in device memory (ws_store_distance or ws_store_ground_distance).
+// resolution: the map's (the store does not know it).  (app.hpp adds the overload that takes a DeviceGlobalMap.)
+inline Clearance global_map_clearance(ws_store *store, int resolution, const std::vector<ClearanceInput> &poses, size_t n_poses, const std::vector<ClearanceSphere> &body,
+                                      int32_t soft_mm = 0, bool per_pose = false, bool outside_ok = false)
+{
+  Clearance out;
+  if (poses.empty() || n_poses == 0) return out;
+  if (poses.size() % n_poses) throw std::invalid_argument("global_map_clearance: the poses are no whole number of trajectories");
+  const size_t t = poses.size() / n_poses;
+  const uint32_t flags = (per_pose ? WS_CLEARANCE_POSES : 0u) | (outside_ok ? WS_CLEARANCE_OUTSIDE_OK : 0u);
+  WS_CHECK(ws_store_clearance(store, poses[0].rot_q30, t, n_poses, body.empty() ? nullptr : body[0].off_mm, body.size(), soft_mm, resolution, flags, &out.best));
+  out.records.resize(t);
+  if (per_pose) out.poses.resize(poses.size());
+  size_t got = 0, got_poses = 0;
+  WS_CHECK(ws_store_clearance_download(store, out.records.data(), per_pose ? out.poses.data() : nullptr, out.records.size(), out.poses.size(), &got, &got_poses));
   return out;
 }
 

@@ -5,7 +5,7 @@ sliding TSDF map @ 5 cm, one MI355X): sensor clouds in float metres -> device pr
     python tools/replay_stream.py --map 1024 --scans 30 [--h5 /tmp/stream.h5] [--async-shift | --device-global-map] [--surface-ply DIR [--surface-every N]] [--mesh-ply DIR] [--global-packed FILE.wspk]
                                    [--raycast-ply DIR] [--distance-npy DIR [--distance-m M]] [--global-distance-npy FILE [--global-distance-m M]]
                                    [--moving-sweeps] [--deskew] [--frontier-ply DIR] [--global-frontier-ply FILE] [--reach-ply DIR [--reach-clearance-m M]]
-                                   [--ground-npy DIR [--ground-height-m M]]
+                                   [--ground-npy DIR [--ground-height-m M]] [--rollouts-csv FILE [--rollouts-radius-m M]]
 
 Prints one JSON line: scans/s over the stream and the mean per-stage times (the reference's RuntimeEvaluator
 forms "preprocess", "tsdf", "registration", "total")."""
@@ -91,6 +91,10 @@ def main():
                     "voxel x y z, its path cost, its unknown_k2, the number of candidates (-1 -1 -1, 4294967295 and 0 without a candidate); the "
                     "clearance is --reach-clearance-m")
     ap.add_argument("--next-view-range-m", type=float, default=5.0, metavar="M", help="... with rays of M metres")
+    ap.add_argument("--rollouts-csv", default=None, metavar="FILE", help="after every TSDF update: the best of a fan of constant-curvature rollouts from the current "
+                    "pose over the window's column distance (arc_rollouts, TSDFMapping.score_trajectories, ws_map_clearance) as one line of FILE: scan number, "
+                    "the best trajectory (-1 without one), its speed and yaw rate, its cost and smallest margin in mm, the trajectories with a hit, the fan's size")
+    ap.add_argument("--rollouts-radius-m", type=float, default=0.3, metavar="M", help="... for a body of one sphere of M metres, with as much again as soft range")
     ap.add_argument("--global-frontier-ply", default=None, metavar="FILE", help="after the last scan: the clustered frontier of the WHOLE run from the device "
                     "global map (TSDFMapping.global_frontier, ws_store_frontier) as PLY; needs --device-global-map")
     ap.add_argument("--global-raycast-ply", default=None, metavar="FILE", help="after the last scan: the predicted scan from the pose of the FIRST scan, "
@@ -178,6 +182,13 @@ def main():
     if args.next_view_csv:
         next_view_file = open(args.next_view_csv, "w")
         next_view_file.write("scan,goal_x,goal_y,goal_z,path_cost,unknown_k2,candidates\n")
+    rollouts = {"lines": 0, "trajectories": 0, "with_a_best": 0, "seconds": 0.0}
+    rollouts_file = None
+    if args.rollouts_csv:
+        rollouts_file = open(args.rollouts_csv, "w")
+        rollouts_file.write("scan,best,speed_mps,yaw_rate_rps,cost,min_margin_mm,hit_trajectories,trajectories\n")
+        fan_speeds, fan_rates = np.linspace(0.25, 1.5, 6), np.linspace(-0.8, 0.8, 17)
+        fan_body = W.body_spheres([[0.0, 0.0, 0.0]], args.rollouts_radius_m)
     updates_seen = 0
     if args.mesh_ply:
         os.makedirs(args.mesh_ply, exist_ok=True)
@@ -237,6 +248,20 @@ def main():
             next_view["lines"] += 1
             next_view["candidates"] = int(len(nbv["candidates"]))
             next_view["seconds"] += time.perf_counter() - ts
+        if rollouts_file is not None and app.n_updates > updates_seen:  # after every update of the map: which way to drive
+            ts = time.perf_counter()
+            pose_m = app.pose_.astype(np.float64).copy()
+            pose_m[:3, 3] /= 1000.0  # (the app keeps millimetres)
+            fan = W.arc_rollouts(pose_m, fan_speeds, fan_rates, steps=20, dt=0.2)
+            sc = app.gpu_.score_trajectories(fan, fan_body, soft_m=args.rollouts_radius_m)
+            b = sc.best
+            speed, rate = (fan_speeds[b // len(fan_rates)], fan_rates[b % len(fan_rates)]) if b >= 0 else (0.0, 0.0)
+            cost, margin = (int(sc.records["cost"][b]), int(sc.records["min_margin"][b])) if b >= 0 else (0, 0)
+            rollouts_file.write(f"{k + 1},{b},{speed:.3f},{rate:.3f},{cost},{margin},{int(np.count_nonzero(sc.records['hits']))},{len(fan)}\n")
+            rollouts["lines"] += 1
+            rollouts["trajectories"] = int(len(fan))
+            rollouts["with_a_best"] += int(b >= 0)
+            rollouts["seconds"] += time.perf_counter() - ts
         updates_seen = app.n_updates
         if args.surface_ply and (k + 1) % max(args.surface_every, 1) == 0:
             ts = time.perf_counter()
@@ -355,6 +380,8 @@ def main():
     true_last = np.array([1000.0 * args.step * (args.scans - 1), 500.0 * args.step * (args.scans - 1), 0.0])
     if next_view_file is not None:
         next_view_file.close()
+    if rollouts_file is not None:
+        rollouts_file.close()
     t3 = time.perf_counter()
     app.terminate()
     t4 = time.perf_counter()
@@ -379,6 +406,7 @@ def main():
                       "reach_ply": reach if args.reach_ply else None,
                       "ground_npy": ground if args.ground_npy else None,
                       "next_view_csv": next_view if args.next_view_csv else None,
+                      "rollouts_csv": rollouts if args.rollouts_csv else None,
                       "global_frontier_ply": global_frontier,
                       "global_raycast_ply": global_raycast,
                       "global_distance_npy": global_distance,

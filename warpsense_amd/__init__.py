@@ -13,6 +13,8 @@ from .records import REACH_PATH_HEADER, REACH_PATH_RECORD, REACH_UNREACHABLE, re
 from ._lib import WS_REACH_DEFAULT, WS_REACH_UNKNOWN_FREE, WS_REACH_UNREACHABLE  # noqa: F401
 from .records import VIEW_GAIN_RAY, VIEW_GAIN_RECORD, gain_volume_m3, rank_views, view_fan  # noqa: F401
 from ._lib import WS_GAIN_ANY_WEIGHT, WS_GAIN_DEFAULT, WS_GAIN_RAYS  # noqa: F401
+from .clearance import CLEARANCE_POSE, CLEARANCE_RECORD, ClearanceResult, arc_rollouts, body_spheres, clearance_centres, clearance_margin, trajectory_poses  # noqa: F401
+from ._lib import WS_CLEARANCE_DEFAULT, WS_CLEARANCE_OUTSIDE_OK, WS_CLEARANCE_POSES  # noqa: F401
 from .fuse import FuseStats, fuse_pose, pose_transform  # noqa: F401
 from ._lib import WS_FUSE_COUNT_ONLY, WS_FUSE_DEFAULT  # noqa: F401
 from .pyramid import CoarsenStats, MapPyramid, parents_of  # noqa: F401

@@ -55,6 +55,9 @@ EXPORTS = [
     "ws_debug_store_reach_timing",
     "ws_map_view_gain", "ws_map_view_gain_records_dev", "ws_map_view_gain_rays_dev", "ws_map_view_gain_download", "ws_debug_view_gain_timing",
     "ws_store_view_gain", "ws_store_view_gain_records_dev", "ws_store_view_gain_rays_dev", "ws_store_view_gain_download", "ws_debug_store_view_gain_timing",
+    "ws_map_clearance", "ws_map_clearance_dev", "ws_map_clearance_records_dev", "ws_map_clearance_poses_dev", "ws_map_clearance_download", "ws_debug_clearance_timing",
+    "ws_store_clearance", "ws_store_clearance_dev", "ws_store_clearance_records_dev", "ws_store_clearance_poses_dev", "ws_store_clearance_download",
+    "ws_debug_store_clearance_timing", "ws_clearance_centres", "ws_clearance_margin",
     "ws_store_fuse", "ws_debug_store_fuse_timing",
     "ws_store_coarsen", "ws_store_parents_of", "ws_debug_store_coarsen_timing",
     "ws_store_changes", "ws_store_changes_records_dev", "ws_store_changes_labels_dev", "ws_store_changes_clusters_dev", "ws_store_changes_download",
@@ -76,6 +79,7 @@ GROUND_CLASSES = ("unknown", "ground", "blocked", "void")  # class c of a ground
 WS_FRONTIER_DEFAULT, WS_FRONTIER_ANY_WEIGHT, WS_FRONTIER_CLUSTERS = 0, 1, 2
 WS_REACH_DEFAULT, WS_REACH_UNKNOWN_FREE, WS_REACH_UNREACHABLE = 0, 1, 0xFFFFFFFF
 WS_GAIN_DEFAULT, WS_GAIN_ANY_WEIGHT, WS_GAIN_RAYS = 0, 1, 2
+WS_CLEARANCE_DEFAULT, WS_CLEARANCE_POSES, WS_CLEARANCE_OUTSIDE_OK = 0, 1, 2
 WS_FUSE_DEFAULT, WS_FUSE_COUNT_ONLY = 0, 1
 WS_COARSEN_DEFAULT = 0
 WS_CHANGES_APPEARED, WS_CHANGES_VANISHED, WS_CHANGES_CLUSTERS, WS_CHANGES_DEFAULT = 1, 2, 4, 3
@@ -258,6 +262,19 @@ def load() -> C.CDLL:
         getattr(L, f"ws_{owner}_view_gain_download").argtypes = [vp, vp, vp, sz, sz, P(sz), P(sz)]
     L.ws_debug_view_gain_timing.argtypes = [vp, i32, vp]
     L.ws_debug_store_view_gain_timing.argtypes = [vp, i32, vp]
+    L.ws_map_clearance.argtypes = [vp, vp, sz, sz, vp, sz, i32, u32, P(i64)]
+    L.ws_map_clearance_dev.argtypes = [vp, vp, sz, sz, vp, sz, i32, u32, P(i64)]
+    L.ws_store_clearance.argtypes = [vp, vp, sz, sz, vp, sz, i32, i32, u32, P(i64)]
+    L.ws_store_clearance_dev.argtypes = [vp, vp, sz, sz, vp, sz, i32, i32, u32, P(i64)]
+    for owner in ("map", "store"):
+        for part in ("records", "poses"):
+            f = getattr(L, f"ws_{owner}_clearance_{part}_dev")
+            f.argtypes, f.restype = [vp, P(sz)], vp
+        getattr(L, f"ws_{owner}_clearance_download").argtypes = [vp, vp, vp, sz, sz, P(sz), P(sz)]
+    L.ws_debug_clearance_timing.argtypes = [vp, i32, vp]
+    L.ws_debug_store_clearance_timing.argtypes = [vp, i32, vp]
+    L.ws_clearance_centres.argtypes = [vp, sz, vp, sz, i32, vp]
+    L.ws_clearance_margin.argtypes, L.ws_clearance_margin.restype = [u32, i32, i32], i32
     L.ws_store_fuse.argtypes = [vp, vp, vp, i32, i32, u32, vp]
     L.ws_debug_store_fuse_timing.argtypes = [vp, i32, vp]
     L.ws_store_coarsen.argtypes = [vp, vp, vp, sz, i32, u32, vp]

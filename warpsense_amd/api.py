@@ -45,6 +45,7 @@ from .global_map import GlobalMap, pose_to_values  # noqa: F401
 from .mapping import MapParams, Params, RegistrationParams, TSDFMapping, TSDFRegistration  # noqa: F401
 from .records import (FRONTIER_CLUSTER, FRONTIER_RECORD, REACH_PATH_HEADER, REACH_PATH_RECORD, REACH_UNREACHABLE, frontier_goals, reach_mm, write_frontier_ply, write_path_ply, RAY, SAMPLE, SAMPLE_CLASSES, SURFACE_RECORD, VERT, distance_class, distance_d2, distance_mm,  # noqa: F401
                       write_mesh_ply, write_raycast_ply, write_surface_ply)
+from .clearance import CLEARANCE_POSE, CLEARANCE_RECORD, ClearanceResult, arc_rollouts, body_spheres, clearance_centres, clearance_margin, trajectory_poses  # noqa: F401
 from .records import VIEW_GAIN_RAY, VIEW_GAIN_RECORD, gain_volume_m3, rank_views, view_fan  # noqa: F401
 from .registration import RegistrationCuda, batch_best, candidate_poses  # noqa: F401
 from .scan import DevicePoints, ScanPreprocessor, preprocess_sweep_host, sweep_bins, sweep_poses, to_int_mat, to_map  # noqa: F401

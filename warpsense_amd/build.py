@@ -25,7 +25,7 @@ ROOT = os.path.dirname(PKG_DIR)
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libwarpsense_hip.so")
 H5_LIB_PATH = os.path.join(PKG_DIR, "libwarpsense_h5.so")  # optional: global-map file (needs the HDF5 C library)
-SOURCES = ["api_core.hip", "api_map.hip", "api_query.hip", "api_store.hip", "api_store_query.hip", "api_store_pair.hip", "api_pack.hip", "api_tsdf.hip", "api_reg.hip", "api_scan.hip", "tsdf_update.hip", "tsdf_setup.hip", "tsdf_marches.hip", "tsdf_resolve.hip", "tsdf_integrate.hip", "reg_routes.hip", "reg_batch.hip", "scan_preprocess.hip", "map_surface.hip", "map_mesh.hip", "map_raycast.hip", "map_sample.hip", "map_distance.hip", "map_ground.hip", "map_frontier.hip", "map_reach.hip", "map_gain.hip", "map_store.hip", "store_surface.hip", "store_mesh.hip", "store_raycast.hip", "store_sample.hip", "store_distance.hip", "store_ground.hip", "store_frontier.hip", "store_gain.hip", "store_fuse.hip", "store_coarsen.hip", "store_changes.hip", "store_pack.hip"]
+SOURCES = ["api_core.hip", "api_map.hip", "api_query.hip", "api_store.hip", "api_store_query.hip", "api_store_pair.hip", "api_pack.hip", "api_tsdf.hip", "api_reg.hip", "api_scan.hip", "tsdf_update.hip", "tsdf_setup.hip", "tsdf_marches.hip", "tsdf_resolve.hip", "tsdf_integrate.hip", "reg_routes.hip", "reg_batch.hip", "scan_preprocess.hip", "map_surface.hip", "map_mesh.hip", "map_raycast.hip", "map_sample.hip", "map_distance.hip", "map_ground.hip", "map_frontier.hip", "map_reach.hip", "map_gain.hip", "map_clearance.hip", "map_store.hip", "store_surface.hip", "store_mesh.hip", "store_raycast.hip", "store_sample.hip", "store_distance.hip", "store_ground.hip", "store_frontier.hip", "store_gain.hip", "store_fuse.hip", "store_coarsen.hip", "store_changes.hip", "store_pack.hip"]
 ARCH = "gfx950"
 
 

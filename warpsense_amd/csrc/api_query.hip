@@ -1,8 +1,10 @@
 // api_query.hip — the queries of a map's window: surface cloud, mesh, ray cast, point sample and distance field (ws_map_surface, ws_map_mesh,
-// ws_map_raycast, ws_map_sample, ws_map_distance and what goes with each), and the parts of the query cores of ws_api.h that are no templates.
+// ws_map_raycast, ws_map_sample, ws_map_distance and what goes with each), ground, frontier, reach, view gain and clearance, and the parts
+// of the query cores of ws_api.h that are no templates.
 #include <algorithm>
 
 #include "ws_api.h"
+#include "ws_clearance.h"
 
 using namespace ws;
 
@@ -852,4 +854,169 @@ int ws_debug_view_gain_timing(ws_map *m, int32_t enable, float ms_out[3])
   if (!m) return invalid("ws_debug_view_gain_timing: map is NULL");
   std::lock_guard<std::mutex> lock(m->gain.mu);
   return query_timing(m->ctx->stream, m->gain.timer, enable, ms_out, GAIN_PAIRS, 3);
+}
+
+// ---- clearance: what the host core of ws_api.h (clearance_run) needs beside it, for the window of a map here and for the store in
+// api_store_query.hip.  clearance_check: every refusal that needs neither a lock nor the distance result; among these the INVALID ones
+// come first.  clearance_flow: the refusals that look at the distance result, then the flow from "the old result is dropped" to the
+// publish.
+int ws::clearance_check(const char *name, bool bad, const int32_t *poses, size_t t, size_t p, const int32_t *body, size_t k, int32_t soft, int32_t res, uint32_t flags,
+                        int32_t *reach_mm)
+{
+  const uint32_t known = WS_CLEARANCE_POSES | WS_CLEARANCE_OUTSIDE_OK;
+  if (bad || (flags & ~known) || (t && p && !poses) || (k && !body)) return invalid(std::string(name) + ": bad argument");
+  if (res <= 0) return invalid(std::string(name) + ": map_resolution <= 0");
+  if (res > 1024) return range_error(name, ": the resolution must not exceed 1024 mm");
+  if (k < 1 || k > CLEAR_MAX_SPHERES) return range_error(name, ": the body must have 1 .. 64 spheres");
+  if (p < 1 || p > (size_t)CLEAR_MAX_LENGTH) return range_error(name, ": a trajectory must have 1 .. 65535 poses");
+  if (t > ((size_t)1 << 20)) return range_error(name, ": more than 2^20 trajectories");
+  if (t * p > ((size_t)1 << 21)) return range_error(name, ": more than 2^21 poses in all");
+  if (soft < 0 || soft > CLEAR_MAX_LENGTH) return range_error(name, ": soft_mm must be 0 .. 65535");
+  int32_t widest = 0;
+  for (size_t i = 0; i < k; ++i)
+  {
+    const int32_t *b = body + 4 * i;
+    for (int a = 0; a < 3; ++a)
+      if (b[a] < -CLEAR_MAX_OFFSET || b[a] > CLEAR_MAX_OFFSET) return range_error(name, ": a sphere's offset exceeds 2^20 mm on an axis");
+    if (b[3] < 0 || b[3] > CLEAR_MAX_LENGTH) return range_error(name, ": a sphere's radius must be 0 .. 65535 mm");
+    widest = std::max(widest, b[3]);
+  }
+  *reach_mm = widest + soft;
+  return WS_OK;
+}
+
+int ws::clearance_flow(ClearanceResult &q, const DistResult &d, hipStream_t s, const char *name, const int32_t *poses, bool poses_on_host, size_t t, size_t p,
+                       const int32_t *body, size_t k, int32_t soft, int32_t res, uint32_t flags, int32_t reach_mm, int64_t *best)
+{
+  if (t == 0) return WS_OK; // nothing written, the last result stays; the distance result is not looked at
+  if (!d.have) return invalid(std::string(name) + ": no distance result yet (the call runs on the records of the last distance call)");
+  if ((int64_t)d.R * res < (int64_t)reach_mm)
+    return range_error(name, ": max_dist_vox x resolution of the distance result is below the largest radius + soft_mm (the clamp of d2 could hide a penalty)");
+  WS_TRY(q.timer.arm());
+  q.t = q.p = 0; // (whatever happens from here on, the old result is gone: its buffers may be replaced)
+  q.has_poses = false;
+  const bool pose_rec = (flags & WS_CLEARANCE_POSES) != 0;
+  const size_t n = t * p;
+  WS_TRY(q.best.alloc(1));
+  if ((poses_on_host && n > q.poses.cap) || CLEAR_MAX_SPHERES > q.body.cap || t > q.rec.cap || (pose_rec && n > q.pose_rec.cap))
+  {
+    WS_HIP(hipStreamSynchronize(s));
+    if (poses_on_host) WS_TRY(q.poses.grow(n, 12 * sizeof(int32_t)));
+    WS_TRY(q.body.grow(CLEAR_MAX_SPHERES, 4 * sizeof(int32_t), DevBuf::EXACT));
+    WS_TRY(q.rec.grow(t, sizeof(ClearRecord)));
+    if (pose_rec) WS_TRY(q.pose_rec.grow(n, sizeof(ClearPose)));
+  }
+  q.timer.mark(0, s);
+  WS_HIP(hipMemcpyAsync(q.body.p, body, k * 4 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  if (poses_on_host)
+  {
+    WS_HIP(hipMemcpyAsync(q.poses.p, poses, n * 12 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    poses = q.poses.as<int32_t>();
+  }
+  ClearCall c;
+  c.t = t, c.p = p, c.k = (uint32_t)k, c.res = res, c.soft = soft, c.flags = flags;
+  WS_TRY(launch_clearance(q, d, s, c, poses));
+  WS_HIP(hipStreamSynchronize(s));
+  q.t = t, q.p = p;
+  q.has_poses = pose_rec;
+  if (best) *best = (int64_t)*q.best.host;
+  return WS_OK;
+}
+
+const void *ws::clearance_records_dev(const ClearanceResult *q, size_t *n)
+{
+  if (n) *n = q ? q->t : 0;
+  return q && q->t ? q->rec.p : nullptr;
+}
+
+const void *ws::clearance_poses_dev(const ClearanceResult *q, size_t *n)
+{
+  const bool have = q && q->has_poses && q->t;
+  if (n) *n = have ? q->t * q->p : 0;
+  return have ? q->pose_rec.p : nullptr;
+}
+
+// `name`, `call`: the download entry point, and the entry point whose flag it misses
+int ws::clearance_download(const ClearanceResult &q, hipStream_t s, const char *name, const char *call, void *records_host, void *poses_host, size_t cap_traj,
+                           size_t cap_poses, size_t *n_traj, size_t *n_poses)
+{
+  const size_t total = q.has_poses ? q.t * q.p : 0;
+  *n_traj = q.t;
+  if (n_poses) *n_poses = total;
+  if (q.t && !q.has_poses && poses_host && cap_poses) return invalid(std::string(name) + ": the last " + call + " did not ask for WS_CLEARANCE_POSES");
+  const size_t k = records_host ? std::min(cap_traj, q.t) : 0, kp = poses_host ? std::min(cap_poses, total) : 0;
+  if (k) WS_HIP(hipMemcpyAsync(records_host, q.rec.p, k * sizeof(ClearRecord), hipMemcpyDeviceToHost, s));
+  if (kp) WS_HIP(hipMemcpyAsync(poses_host, q.pose_rec.p, kp * sizeof(ClearPose), hipMemcpyDeviceToHost, s));
+  if (k || kp) WS_HIP(hipStreamSynchronize(s));
+  return WS_OK;
+}
+
+// ---- clearance: trajectories of a body of spheres against the last distance result of the map, map_clearance.hip (the rules are
+// stated in warpsense_hip.h)
+static int map_clearance(ws_map *m, const char *name, const int32_t *poses, bool poses_on_host, size_t t, size_t p, const int32_t *body, size_t k, int32_t soft,
+                         uint32_t flags, int64_t *best)
+{
+  if (!m) return invalid(std::string(name) + ": bad argument");
+  std::unique_lock<std::mutex> lock_dist, lock;
+  return clearance_run(m->clear, m->dist, m->ctx->stream, name, false, poses, poses_on_host, t, p, body, k, soft, m->res, flags, best, [&] {
+    WS_SETTLE(m);
+    lock_dist = std::unique_lock<std::mutex>(m->dist.mu); // (the order of every call that holds both)
+    lock = std::unique_lock<std::mutex>(m->clear.mu);
+    return (int)WS_OK;
+  });
+}
+
+int ws_map_clearance(ws_map *m, const int32_t *poses_host, size_t n_traj, size_t n_poses, const int32_t *body_host, size_t k, int32_t soft_mm, uint32_t flags,
+                     int64_t *best)
+{
+  return map_clearance(m, "ws_map_clearance", poses_host, true, n_traj, n_poses, body_host, k, soft_mm, flags, best);
+}
+
+int ws_map_clearance_dev(ws_map *m, const int32_t *poses_dev, size_t n_traj, size_t n_poses, const int32_t *body_host, size_t k, int32_t soft_mm, uint32_t flags,
+                         int64_t *best)
+{
+  return map_clearance(m, "ws_map_clearance_dev", poses_dev, false, n_traj, n_poses, body_host, k, soft_mm, flags, best);
+}
+
+const void *ws_map_clearance_records_dev(const ws_map *m, size_t *n) { return clearance_records_dev(m ? &m->clear : nullptr, n); }
+
+const void *ws_map_clearance_poses_dev(const ws_map *m, size_t *n) { return clearance_poses_dev(m ? &m->clear : nullptr, n); }
+
+int ws_map_clearance_download(ws_map *m, void *records_host, void *poses_host, size_t cap_traj, size_t cap_poses, size_t *n_traj, size_t *n_poses)
+{
+  if (!m || !n_traj) return invalid("ws_map_clearance_download: NULL argument");
+  std::lock_guard<std::mutex> lock(m->clear.mu);
+  return clearance_download(m->clear, m->ctx->stream, "ws_map_clearance_download", "ws_map_clearance", records_host, poses_host, cap_traj, cap_poses, n_traj, n_poses);
+}
+
+int ws_debug_clearance_timing(ws_map *m, int32_t enable, float ms_out[3])
+{
+  if (!m) return invalid("ws_debug_clearance_timing: map is NULL");
+  std::lock_guard<std::mutex> lock(m->clear.mu);
+  return query_timing(m->ctx->stream, m->clear.timer, enable, ms_out, CLEAR_PAIRS, 3);
+}
+
+// ---- clearance: the two host-only statements of the rules (ws_clearance.h), no GPU and no context
+int ws_clearance_centres(const int32_t *poses, size_t n_poses, const int32_t *body, size_t k, int32_t res, int32_t *voxels_out)
+{
+  if ((n_poses && (!poses || !voxels_out)) || (k && !body)) return invalid("ws_clearance_centres: NULL argument");
+  int32_t reach_mm = 0;
+  WS_TRY(clearance_check("ws_clearance_centres", false, poses, 0, 1, body, k, 0, res, 0u, &reach_mm));
+  for (size_t i = 0; i < n_poses * 12; ++i)
+  {
+    const int64_t v = poses[i];
+    if (i % 12 < 9 ? (v < -((int64_t)1 << 30) || v > ((int64_t)1 << 30)) : (v <= -((int64_t)1 << 30) || v >= ((int64_t)1 << 30)))
+      return range_error("ws_clearance_centres", ": a pose leaves its domain (rot_q30 in [-2^30, 2^30], |pos_mm| < 2^30)");
+  }
+  for (size_t i = 0; i < n_poses; ++i)
+    for (size_t j = 0; j < k; ++j)
+      for (int a = 0; a < 3; ++a) voxels_out[(i * k + j) * 3 + a] = (int32_t)clear_voxel(clear_centre(poses + 12 * i, body + 4 * j, a), res);
+  return WS_OK;
+}
+
+int32_t ws_clearance_margin(uint32_t d2, int32_t res, int32_t radius_mm)
+{
+  const uint32_t d = std::min(d2, 65025u);
+  const int32_t r = std::min(std::max(res, 1), 1024), rad = std::min(std::max(radius_mm, 0), (int32_t)CLEAR_MAX_LENGTH);
+  return clear_margin(d, r, rad);
 }

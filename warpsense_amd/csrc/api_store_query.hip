@@ -1,5 +1,5 @@
 // api_store_query.hip — the calls that read one chunk store (api_store.hip): its surface cloud, mesh, ray cast, point sample, distance
-// field, ground with ws_store_ground_distance, frontier, reach and view gain, with their _dev, _download, _box and _timing entry
+// field, ground with ws_store_ground_distance, frontier, reach, view gain and clearance, with their _dev, _download, _box and _timing entry
 // points, and ws_debug_store_raycast_table / _find.  Each runs the host core of its window-side twin (ws_api.h, api_query.hip) over the
 // chunks the call lists (ws_store_list.h), with the kernels of store_surface.hip, store_mesh.hip, store_raycast.hip, store_sample.hip,
 // store_distance.hip, store_ground.hip, store_frontier.hip, map_reach.hip and store_gain.hip (the semantics are stated in
@@ -610,4 +610,46 @@ int ws_store_view_gain_download(ws_store *st, void *records_host, void *rays_hos
 int ws_debug_store_view_gain_timing(ws_store *st, int32_t enable, float ms_out[3])
 {
   return store_timing(st, "ws_debug_store_view_gain_timing", &ws_store::gain, enable, ms_out, GAIN_PAIRS);
+}
+
+// ---- the clearance of the store: ws_map_clearance over the last ws_store_distance result (map_clearance.hip reads its records alone)
+static int store_clearance(ws_store *st, const char *name, const int32_t *poses, bool poses_on_host, size_t t, size_t p, const int32_t *body, size_t k, int32_t soft,
+                           int32_t map_resolution, uint32_t flags, int64_t *best)
+{
+  if (!st) return invalid(std::string(name) + ": bad argument");
+  std::unique_lock<std::mutex> lock;
+  return clearance_run(st->clear, st->dist, st->ctx->stream, name, false, poses, poses_on_host, t, p, body, k, soft, map_resolution, flags, best, [&] {
+    servers_leave(st->ctx);
+    lock = std::unique_lock<std::mutex>(st->mu);
+    return (int)WS_OK;
+  });
+}
+
+int ws_store_clearance(ws_store *st, const int32_t *poses_host, size_t n_traj, size_t n_poses, const int32_t *body_host, size_t k, int32_t soft_mm,
+                       int32_t map_resolution, uint32_t flags, int64_t *best)
+{
+  return store_clearance(st, "ws_store_clearance", poses_host, true, n_traj, n_poses, body_host, k, soft_mm, map_resolution, flags, best);
+}
+
+int ws_store_clearance_dev(ws_store *st, const int32_t *poses_dev, size_t n_traj, size_t n_poses, const int32_t *body_host, size_t k, int32_t soft_mm,
+                           int32_t map_resolution, uint32_t flags, int64_t *best)
+{
+  return store_clearance(st, "ws_store_clearance_dev", poses_dev, false, n_traj, n_poses, body_host, k, soft_mm, map_resolution, flags, best);
+}
+
+const void *ws_store_clearance_records_dev(const ws_store *st, size_t *n) { return clearance_records_dev(st ? &st->clear : nullptr, n); }
+
+const void *ws_store_clearance_poses_dev(const ws_store *st, size_t *n) { return clearance_poses_dev(st ? &st->clear : nullptr, n); }
+
+int ws_store_clearance_download(ws_store *st, void *records_host, void *poses_host, size_t cap_traj, size_t cap_poses, size_t *n_traj, size_t *n_poses)
+{
+  if (!st || !n_traj) return invalid("ws_store_clearance_download: NULL argument");
+  std::lock_guard<std::mutex> lock(st->mu);
+  return clearance_download(st->clear, st->ctx->stream, "ws_store_clearance_download", "ws_store_clearance", records_host, poses_host, cap_traj, cap_poses, n_traj,
+                            n_poses);
+}
+
+int ws_debug_store_clearance_timing(ws_store *st, int32_t enable, float ms_out[3])
+{
+  return store_timing(st, "ws_debug_store_clearance_timing", &ws_store::clear, enable, ms_out, CLEAR_PAIRS);
 }

@@ -314,6 +314,7 @@ int distance_run(DistResult &q, hipStream_t s, const int32_t lo[3], const uint32
   // what a reach call needs of this result beside its records: the box and the flags (published with `have`)
   for (int k = 0; k < 3; ++k) q.lo[k] = n ? lo[k] : 0, q.ext[k] = n ? ext[k] : 0u;
   q.flags = flags;
+  q.R = R;
   if (n == 0)
   {
     q.have = true;
@@ -513,6 +514,30 @@ int gain_run(GainResult &q, hipStream_t s, const GainCall &c, const int32_t *ori
   q.has_rays = rays;
   if (best) *best = (uint64_t)*q.best.host;
   return WS_OK;
+}
+
+// ---- clearance (map_clearance.hip): trajectories of a body of spheres against the records of a distance result.  The window of a map
+// and the store differ in their locks and in where the resolution comes from.  clearance_run: the refusals that need no lock, then
+// enter() settles the owner and takes its locks, then clearance_flow (api_query.hip): the look at the distance result, its refusal, and
+// the flow from "the old result is dropped" to the publish.
+const void *clearance_records_dev(const ClearanceResult *q, size_t *n);
+const void *clearance_poses_dev(const ClearanceResult *q, size_t *n);
+int clearance_download(const ClearanceResult &q, hipStream_t s, const char *name, const char *call, void *records_host, void *poses_host, size_t cap_traj,
+                       size_t cap_poses, size_t *n_traj, size_t *n_poses);
+int clearance_check(const char *name, bool bad, const int32_t *poses, size_t t, size_t p, const int32_t *body, size_t k, int32_t soft, int32_t res, uint32_t flags,
+                    int32_t *reach_mm);
+int clearance_flow(ClearanceResult &q, const DistResult &d, hipStream_t s, const char *name, const int32_t *poses, bool poses_on_host, size_t t, size_t p,
+                   const int32_t *body, size_t k, int32_t soft, int32_t res, uint32_t flags, int32_t reach_mm, int64_t *best);
+constexpr int CLEAR_PAIRS[3][2] = {{0, 1}, {1, 2}, {2, 3}};
+
+template <typename Enter>
+int clearance_run(ClearanceResult &q, const DistResult &d, hipStream_t s, const char *name, bool bad, const int32_t *poses, bool poses_on_host, size_t t, size_t p,
+                  const int32_t *body, size_t k, int32_t soft, int32_t res, uint32_t flags, int64_t *best, Enter enter)
+{
+  int32_t reach_mm = 0; // the largest radius + soft_mm: how far a penalty looks
+  WS_TRY(clearance_check(name, bad, poses, t, p, body, k, soft, res, flags, &reach_mm));
+  WS_TRY(enter());
+  return clearance_flow(q, d, s, name, poses, poses_on_host, t, p, body, k, soft, res, flags, reach_mm, best);
 }
 
 // ---- map shift: one shift of both maps' windows, for ws_shift_begin (api_map.hip) and ws_shift_device (api_store.hip), which

@@ -409,11 +409,13 @@ struct DistResult
   DevCounter sites;                    // site voxels / site columns of the last call
   size_t n = 0;                        // records of the last call
   // what ws_map_reach / ws_store_reach need of the last call beside its records: `have` once a call has succeeded (n may be 0),
-  // its box (first voxel and extent; ext[2] is not read under WS_DISTANCE_COLUMNS) and its flags
+  // its box (first voxel and extent; ext[2] is not read under WS_DISTANCE_COLUMNS) and its flags; ws_map_clearance / ws_store_clearance
+  // need its clamp besides (max_dist_vox: no d2 of the records exceeds R R)
   bool have = false;
   int32_t lo[3] = {0, 0, 0};
   uint32_t ext[3] = {0, 0, 0};
   uint32_t flags = 0;
+  int32_t R = 0;
   void release() { timer.release(), sites.release(), have = false, n = 0; for (DevBuf *b : {&rec, &plane}) b->release(); }
 };
 // ... and a ground call (ws_map::Ground, ws_store::Ground; the one flow is ground_run in ws_api.h, the rules are in ws_ground.h)
@@ -493,6 +495,18 @@ struct GainResult
   size_t m = 0, n = 0;                 // views and rays of the last call
   bool has_rays = false;               // the last call also wrote `rays`
   void release() { timer.release(), best.release(), m = n = 0; for (DevBuf *b : {&org, &dirs, &prep, &rec, &rays}) b->release(); }
+};
+// ... and a clearance call (ws_map::Clearance, ws_store::clear; the one flow is clearance_run in ws_api.h, the rules are in
+// ws_clearance.h, the kernels in map_clearance.hip: they read the records of a distance result alone)
+struct ClearanceResult
+{
+  QueryTimer timer;                    // 0 upload 1 trajectories 2 best 3
+  DevBuf poses, body;                  // int32 [trajectories x poses][12] staging of host poses; int32 [64][4] the body
+  DevBuf rec, pose_rec;                // 32-byte trajectory records; 8-byte pose records [trajectories][poses]
+  DevCounter best;                     // the index of the best trajectory as int64, -1 for none
+  size_t t = 0, p = 0;                 // trajectories and poses per trajectory of the last call
+  bool has_poses = false;              // the last call also wrote `pose_rec`
+  void release() { timer.release(), best.release(), t = p = 0; for (DevBuf *b : {&poses, &body, &rec, &pose_rec}) b->release(); }
 };
 
 } // namespace ws
@@ -603,6 +617,10 @@ struct ws_map
   {
     std::mutex mu;
   } gain;
+  struct Clearance : ws::ClearanceResult // ws_map_clearance (map_clearance.hip); a clearance call holds dist.mu, then mu
+  {
+    std::mutex mu;
+  } clear;
   // The scan whose verdict (did its records fit the pool?) has not been looked at yet: ws_tsdf_update* return after the
   // launches, like the reference's update_tsdf (update_tsdf.cu:165); the next call that takes this map settles it first
   // (settle_tsdf: the verdict is in host-mapped memory ~0.35 ms after the launches) and repeats the scan if it was aborted.
@@ -633,7 +651,7 @@ struct ws_map
                           &tile_list, &rec, &big_keys, &block_stats, &counters, &box_stage, &shift_stage_dev})
       b->release();
     for (ws::HostBlock *b : {&counters_host, &status, &shift_stage_host}) b->release();
-    surf.release(), mesh.release(), ray.release(), dist.release(), ground.release(), sample.release(), frontier.release(), reach.release(), gain.release();
+    surf.release(), mesh.release(), ray.release(), dist.release(), ground.release(), sample.release(), frontier.release(), reach.release(), gain.release(), clear.release();
   }
 };
 
@@ -809,6 +827,7 @@ struct ws_store
     ws::DevBuf table_dev;                // ... and the copy the kernels read
     void release() { GainResult::release(), table_host.release(), table_dev.release(); }
   } gain;
+  ws::ClearanceResult clear; // ws_store_clearance (map_clearance.hip: it reads the records of `dist` alone)
   struct Fuse // ws_store_fuse with this store as DST (store_fuse.hip)
   {
     ws::DevBuf words;      // uint64 [4] the sums of the count pass, then uint32 [candidates] the per-chunk counts
@@ -841,6 +860,7 @@ struct ws_store
     coarsen.release();
     fuse.release();
     gain.release();
+    clear.release();
     reach.release();
     frontier.release();
     changes.release();
@@ -1092,6 +1112,18 @@ struct GainCall
 };
 int launch_map_gain(ws_map *m, GainResult &q, int which, const GainCall &c);
 int launch_store_gain(ws_store *st, ws_store::Gain &q, const GainCall &c, uint32_t n_chunks);
+
+// map_clearance.hip: the trajectories of a checked call (clearance_run, ws_api.h) over the records of a distance result, of a window or
+// of the store alike: the trajectory pass (events 1, 2) and the pass that finds the best (event 3; it arrives in q.best.host after a
+// stream synchronise).  The body is in q.body, the poses at poses_dev
+struct ClearCall
+{
+  size_t t, p;          // trajectories (1 .. 2^20), poses of each (1 .. 65535)
+  uint32_t k;           // spheres of the body (1 .. 64)
+  int32_t res, soft;
+  uint32_t flags;
+};
+int launch_clearance(ClearanceResult &q, const DistResult &d, hipStream_t s, const ClearCall &c, const int32_t *poses_dev);
 
 // store_distance.hip: pass 0 of the distance field over the chunks the call lists (it clears q.sites.dev and marks events 0, 1).  The
 // host has written the lookup of store_raycast.hip (store_ray_table_fill) for `n_chunks` listed chunks into q.table_host

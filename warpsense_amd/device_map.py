@@ -9,6 +9,7 @@ import numpy as np
 from . import _lib
 from ._abi import _i3, _i3c, _is_device, _ptr, pack_entry, unpack_entry
 from ._lib import WS_MAP_AVG, WS_MAP_NEW, check
+from .clearance import _clearance_call
 from .context import Context
 from .global_map import GlobalMap
 from .ground import _ground_call, _ground_distance_call
@@ -336,6 +337,19 @@ class DeviceMapMemWrapper:
         """device milliseconds of the upload, of the fan preparation with the march, and of the maximum pass of the last view_gain()
         (ws_debug_view_gain_timing)"""
         return _timing(self._t._L, "ws_debug_view_gain_timing", self._t.handle, 3, enable)
+
+    def clearance(self, poses, body, soft_mm=0, per_pose=False, outside_ok=False, device=False):
+        """Candidate trajectories against the LAST distance() or ground_distance() result of this TSDFCuda (ws_map_clearance; the rules
+        are stated in include/warpsense_hip.h): poses (T, P, 12) int32 (trajectory_poses; a CUDA tensor takes the _dev form), body
+        (k, 4) int32 (body_spheres), soft_mm the range of the soft cost.  per_pose: also one record per pose.  outside_ok: samples
+        outside the box of the distance result do not disqualify a trajectory from `best`.  Returns a ClearanceResult; device=True:
+        its arrays are torch tensors that ALIAS the library's buffers, valid until the next clearance() on this TSDFCuda."""
+        return _clearance_call(self._t._L, "ws_map_clearance", self._t, poses, body, soft_mm, (), per_pose, outside_ok, device)
+
+    def clearance_timing(self, enable: int = -1):
+        """device milliseconds of the upload, of the trajectory pass and of the pass that finds the best of the last clearance()
+        (ws_debug_clearance_timing)"""
+        return _timing(self._t._L, "ws_debug_clearance_timing", self._t.handle, 3, enable)
 
     def dev(self):
         return self._t.handle

@@ -9,7 +9,8 @@ import numpy as np
 
 from . import _lib
 from ._abi import WEIGHT_RESOLUTION, _i3, _is_device, _ptr
-from ._lib import WS_REG_ALL_POINTS, WsError, check
+from ._lib import SAMPLE_CLASSES, WS_REG_ALL_POINTS, WsError, check
+from .clearance import ClearanceQueries
 from .context import Context
 from .device_map import DeviceMap, LocalMap, TSDFCuda
 from .global_map import GlobalMap
@@ -17,7 +18,6 @@ from .merge import FuseQueries
 from .pyramid import PyramidQueries
 from .gain import GainQueries
 from .ground import GroundQueries
-from .records import SAMPLE_CLASSES
 from .registration import RegistrationCuda, batch_best, candidate_poses
 from .scan import to_int_mat, to_map
 from .store import DeviceGlobalMap
@@ -73,7 +73,7 @@ def _dirs_or_os1(dirs):
     return dirs
 
 
-class TSDFMapping(GroundQueries, GainQueries, FuseQueries, PyramidQueries):
+class TSDFMapping(GroundQueries, GainQueries, ClearanceQueries, FuseQueries, PyramidQueries):
     """cuda::TSDFMapping without ROS (the protected constructor path, tsdf_mapping.cpp:30-41)."""
 
     def __init__(self, params: Params, local_map: LocalMap, ctx: Context | None = None, device_global_map: "DeviceGlobalMap | None" = None):

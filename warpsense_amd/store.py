@@ -14,6 +14,7 @@ from .fuse import FuseStats, _fuse_call, fuse_pose
 from .global_map import GlobalMap
 from .pack import PackedMap, _pack_call, _unpack_call
 from .pyramid import CoarsenStats, _coarsen_call
+from .clearance import _clearance_call
 from .ground import _ground_call, _ground_distance_call
 from .queries import _box_ptrs, _distance_call, _frontier_call, _reach_call, _reach_lookup_call, _reach_paths_call, _mesh_call, _raycast_call, _sample_call, _surface_call, _timing, _view_gain_call
 
@@ -209,6 +210,18 @@ class DeviceGlobalMap:
         """device milliseconds of the upload, of the fan preparation with the march, and of the maximum pass of the last view_gain()
         (ws_debug_store_view_gain_timing)"""
         return _timing(self._L, "ws_debug_store_view_gain_timing", self.handle, 3, enable)
+
+    def clearance(self, resolution, poses, body, soft_mm=0, per_pose=False, outside_ok=False, device=False):
+        """Candidate trajectories against the LAST distance() or ground_distance() result of this store (ws_store_clearance; the rules
+        are those of ws_map_clearance, stated in include/warpsense_hip.h).  resolution: the map's, in mm per voxel.  The other
+        arguments and the returned ClearanceResult are those of DeviceMapMemWrapper.clearance; device=True: tensors that ALIAS the
+        store's buffers, valid until the next clearance() on this store."""
+        return _clearance_call(self._L, "ws_store_clearance", self, poses, body, soft_mm, (int(resolution),), per_pose, outside_ok, device)
+
+    def clearance_timing(self, enable: int = -1):
+        """device milliseconds of the upload, of the trajectory pass and of the pass that finds the best of the last clearance()
+        (ws_debug_store_clearance_timing)"""
+        return _timing(self._L, "ws_debug_store_clearance_timing", self.handle, 3, enable)
 
     def reach(self, seeds, clear_d2=0, unknown_free=False, max_rounds=0, device=False):
         """The geodesic field over the LAST distance() result of this store (ws_store_reach; the rules are stated in
